@@ -151,6 +151,39 @@ def build_model(qat_vit_amd, student, backend, dev):
     return prepare(stu, backend).to(dev)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_GRAD_ELEMS = 1 << 23      # gradient elements written (32 MB of float32): all of them if the model has no more, else a fixed sample
+
+
+def dump_outputs(path, model, last):
+    """--dump-outputs: what the last timed step handed its caller, one float32 / float64 .npy per array, for comparing two builds output for output.
+    logits, loss ([loss, ce, kd]) and teacher_logits (with --teacher) are whole.  grads is every parameter's gradient, flattened and concatenated in
+    named_parameters() order - whole if it has at most DUMP_GRAD_ELEMS elements, else the elements at DUMP_GRAD_ELEMS sorted positions drawn by a CPU
+    torch.randperm seeded with 0 (the same positions in every run of the same model); grad_norms holds each parameter gradient's full L2 norm and
+    buffers every buffer of the model (fake-quant scales, zero points, observer ranges and flags) in named_buffers() order."""
+    import numpy as np
+
+    params = [p for _, p in model.named_parameters()]
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach() for p in params]
+    flat = torch.cat([g.reshape(-1).float() for g in grads])
+    if flat.numel() > DUMP_GRAD_ELEMS:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_GRAD_ELEMS].sort().values
+        flat = flat[idx.to(flat.device)]
+    arrays = {"logits": last["logits"].float(), "loss": last["loss"].float(), "grads": flat,
+              "grad_norms": torch.stack([g.double().norm() for g in grads]),
+              "buffers": torch.cat([b.detach().reshape(-1).double() for _, b in model.named_buffers()])}
+    if last.get("teacher_logits") is not None:
+        arrays["teacher_logits"] = last["teacher_logits"].float()
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} ({total / 1e6:.1f} MB) to {path}", file=sys.stderr)
+
+
 def timed_steps(step, steps, warmup, world, dev):
     """W untimed steps, then exactly K timed ones bracketed by barrier + synchronize on both sides; MAX over ranks."""
     for _ in range(warmup):
@@ -186,7 +219,11 @@ def main():
     ap.add_argument("--no-kernel-rates", action="store_true")
     ap.add_argument("--no-kernel-legs", action="store_true", help="skip the per-GEMM-class HIP-event legs (no roofline object; profiling tools)")
     ap.add_argument("--no-extras", action="store_true", help="skip the C3 / C5 legs that follow the headline measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (logits, loss, gradients, "
+                                                          "fake-quant state) as DIR/<name>.npy (rank 0; <= 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_workers(args.gpus, sys.argv[1:])          # never returns
@@ -222,6 +259,7 @@ def main():
 
     L = native.lib()  # fail loudly before any timing if the HIP library is missing
     torch.manual_seed(0)
+    last = {}   # what the latest step returned to its caller: --dump-outputs writes it
 
     def make_config(student, qbackend, with_teacher, batch):
         """(step function, engine) for one configuration; synthetic N(0,1) images generated on the device once, seed 1234 + rank."""
@@ -251,8 +289,9 @@ def main():
                 p.grad = None
             t_out = teacher_only() if teacher is not None else None
             out = model(x)
-            loss, _ = F.kd_ce_loss(out, t_out, y, 4.0, 0.5, 0.1)
+            loss, parts = F.kd_ce_loss(out, t_out, y, 4.0, 0.5, 0.1)
             loss.backward()
+            last.update(logits=out.detach(), loss=parts.detach(), teacher_logits=t_out)   # detached: keeps no autograd graph alive
 
         return step, eng, model, x, y, (teacher_only if teacher is not None else None)
 
@@ -265,9 +304,12 @@ def main():
         gstep = GraphedStudentStep(model, x, y)
 
         def step():  # noqa: F811
-            gstep(x, y)
+            out, _, parts = gstep(x, y)
+            last.update(logits=out, loss=parts, teacher_logits=None)
 
     dt = timed_steps(step, args.steps, args.warmup, world, dev)     # the headline: no profiling hooks are active
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)
 
     # ---- N > 1: the record proves what ran - group size, transport, library version, one distinct device per rank, the bucket plan and the collective
     # time left exposed behind the last backward kernel (HIP events on the compute stream, extra steps outside the headline)

@@ -30,6 +30,26 @@ def test_bench_json_contract(native_lib):
     assert d["value"] > 0 and abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) < 0.02 * d["value"]
 
 
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("form", [[], ["--graph"], ["--teacher", "--backend", "x86"]], ids=["eager", "graph", "teacher"])
+def test_bench_dump_outputs(native_lib, tmp_path, form):
+    """--dump-outputs DIR: the last timed step's logits, loss, gradients and buffers as float32 / float64 .npy files, 64 MB at most in all."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--no-cpu-baseline",
+                        "--no-kernel-rates", "--no-kernel-legs", "--no-extras", "--dump-outputs", str(tmp_path / "out")] + form,
+                       capture_output=True, text=True, timeout=540, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    z = {f.stem: np.load(f) for f in (tmp_path / "out").glob("*.npy")}
+    assert set(z) == {"logits", "loss", "grads", "grad_norms", "buffers"} | ({"teacher_logits"} if "--teacher" in form else set()), sorted(z)
+    assert all(a.dtype in (np.float32, np.float64) for a in z.values())
+    assert sum(a.nbytes for a in z.values()) <= 64 << 20
+    assert z["logits"].shape == (8, 10) and z["loss"].shape == (3,) and z["grads"].shape == (1 << 23,) and z["grad_norms"].shape == (152,)
+    assert all(np.isfinite(a).all() for a in z.values()) and (z["grad_norms"] > 0).any()
+
+
 @pytest.mark.timeout(900)
 def test_bench_starts_its_own_workers(native_lib):
     """`bench.py --gpus 2` started directly (no torchrun, no WORLD_SIZE): the parent spawns both ranks before touching the GPU and relays
