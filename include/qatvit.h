@@ -343,6 +343,21 @@ int qatvit_teacher_forward_f16(const qatvit_cfg* cfg, void* const* params, void*
                                const float* images, float* logits, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Float (pre-QAT) student step: forward + backward of the UNPREPARED QATWrapper(vit_*_patch16_224), fp32-accurate.
+ * Replaces: `student_out = model(images)` ... `loss.backward()` of the reference's float epochs (qat_trainer.py:295-361 before
+ * prepare_qat; train_final.sh runs them in fp32, the Optuna objective under autocast + GradScaler).
+ *  cfg: same struct (the quantisation fields are ignored); cfg->batch is a run-time argument - a workspace sized for batch B serves
+ *  every batch <= B.  Limits: embed_dim % 128 == 0 and <= 768, head_dim 32 or 64, <= 224 tokens, depth <= 12, no dropout / drop-path.
+ *  params / grads: fp32 tensors in the student's order above.  grads must be ZERO on entry: the backward accumulates into them.
+ *  Every GEMM operand is a bf16 (hi, lo) pair, three MFMA passes per product (hi.hi + lo.hi + hi.lo), fp32 accumulate; the attention
+ *  backward runs in fp32 FMA.  The forward leaves in the workspace what the backward reads (one forward per workspace at a time). */
+int64_t qatvit_float_student_workspace_bytes(const qatvit_cfg* cfg);
+int qatvit_float_student_init(const qatvit_cfg* cfg, void* workspace, void* stream);
+int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream);
+int qatvit_float_student_backward(const qatvit_cfg* cfg, void* const* params, const float* dlogits, void* const* grads, void* workspace,
+                                  void* stream);
+
+/* ---------------------------------------------------------------------------
  * Integer inference forward of the trained student from its exported integers.
  * Replaces: the last-epoch  convert(base.eval()) ... evaluate_quantized_cpu(...)  of qat_trainer.py:376-388 (an eager int8 model for the CPU
  * backends only).  int8 MFMA for every grid x grid product; qparams are frozen, so each GEMM epilogue quantises at once: no pre-fake-quant fp32

@@ -254,4 +254,13 @@ int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B
 // true where launch_attn_bwd takes the fused kernel (the only one with the one-plane output)
 bool attn_bwd_is_fused(int T, int H, int D, bool codes);
 
+// ---- teacher.hip: the float forward pieces (bf16 (hi, lo) pairs; the float student step shares them)
+// lse (optional): log-sum-exp of the scaled scores per query, [B][H][T]
+int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16 = 0, float* lse = nullptr);
+int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st);
+// mode 0: x = [cls; Y] + pos, mode 1: x = x_prev + Y; then LayerNorm(x) as a (hi, lo) pair, mean / rstd per row (optional)
+int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
+                               const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st);
+int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st);   // n % 4 == 0
+
 }  // namespace qv

@@ -70,7 +70,8 @@ template <int MODE, int NV>
 __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict__ x_prev, const float* __restrict__ Y, const float* __restrict__ cls,
                                                         const float* __restrict__ pos, float* __restrict__ x_new, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, __bf16* __restrict__ h_hi,
-                                                        __bf16* __restrict__ h_lo, int64_t M, int D, int T, int f16) {
+                                                        __bf16* __restrict__ h_lo, int64_t M, int D, int T, int f16,
+                                                        float* __restrict__ mean_out = nullptr, float* __restrict__ rstd_out = nullptr) {
     const int lane = threadIdx.x & 63;
     bool act[NV];
     int cc[NV];
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict_
             if (act[j]) qq += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
         }
         const float rs = rsqrtf(wave_sum(qq) / (float)D + eps);
+        if (mean_out && lane == 0) { mean_out[row] = mu; rstd_out[row] = rs; }   // (the float student step's LayerNorm backward; the teacher passes nullptr)
 #pragma unroll
         for (int j = 0; j < NV; ++j)
             if (act[j])
@@ -218,7 +220,8 @@ __device__ inline bool t_wave_retile8(float* sO, const f32x4 (&acc)[HD / 16], fl
 constexpr int kTW = 8;  // waves per workgroup
 template <int HD, int NKT>
 __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __restrict__ qkv, int B, int T, int H, int D, float scale,
-                                                             __bf16* __restrict__ O_hi, __bf16* __restrict__ O_lo, int f16) {
+                                                             __bf16* __restrict__ O_hi, __bf16* __restrict__ O_lo, int f16,
+                                                             float* __restrict__ lse = nullptr) {
     constexpr int IMG = NKT * 16 * HD * 2, CH = HD / 8, KK = HD / 32, ND = HD / 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sKh = smem;            // row images of K (hi, lo)
@@ -301,6 +304,8 @@ __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __rest
         l += __shfl_xor(l, 16, 64);
         l += __shfl_xor(l, 32, 64);
         const float invl = 1.0f / l;
+        // log-sum-exp of the scaled scores per query, [b][h][t] (the float student step's attention backward; the teacher passes nullptr)
+        if (lse && g == 0 && qt * 16 + r < T) lse[((int64_t)b * H + h) * T + qt * 16 + r] = m + logf(l);
         f32x4 o[ND];
 #pragma unroll
         for (int jd = 0; jd < ND; ++jd) o[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -358,21 +363,40 @@ static int rows_grid_t(int64_t rows) {
 }
 
 template <int HD, int NKT>
-static void launch_attn_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16) {
+static void launch_attn_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16, float* lse) {
     const size_t lds = (size_t)4 * NKT * 16 * HD * 2 + (size_t)kTW * 8 * (HD + 4) * sizeof(float);
     static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_fwd_float<HD, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
     (void)once;
     k_attn_fwd_float<HD, NKT><<<B * H, kTW * 64, lds, st>>>(qkv, B, T, H, D, 1.0f / sqrtf((float)HD), reinterpret_cast<__bf16*>(O_hi),
-                                                            reinterpret_cast<__bf16*>(O_lo), f16);
+                                                            reinterpret_cast<__bf16*>(O_lo), f16, lse);
 }
 
-int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16 = 0) {
+int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16, float* lse) {
     const int hd = D / H;
     if (D % H != 0 || (hd != 64 && hd != 32) || T > 224) { set_error("teacher attention: head_dim %d / T %d unsupported", hd, T); return 1; }
-    if (hd == 64 && T > 32) launch_attn_float<64, 14>(qkv, B, T, H, D, O_hi, O_lo, st, f16);
-    else if (hd == 64) launch_attn_float<64, 2>(qkv, B, T, H, D, O_hi, O_lo, st, f16);
-    else if (T > 32) launch_attn_float<32, 14>(qkv, B, T, H, D, O_hi, O_lo, st, f16);
-    else launch_attn_float<32, 2>(qkv, B, T, H, D, O_hi, O_lo, st, f16);
+    if (hd == 64 && T > 32) launch_attn_float<64, 14>(qkv, B, T, H, D, O_hi, O_lo, st, f16, lse);
+    else if (hd == 64) launch_attn_float<64, 2>(qkv, B, T, H, D, O_hi, O_lo, st, f16, lse);
+    else if (T > 32) launch_attn_float<32, 14>(qkv, B, T, H, D, O_hi, O_lo, st, f16, lse);
+    else launch_attn_float<32, 2>(qkv, B, T, H, D, O_hi, O_lo, st, f16, lse);
+    return 0;
+}
+
+// the forward pieces the float student step (float_step.hip) shares, always in the bf16-pair form
+int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st) {
+    const int64_t n = (int64_t)B * (H / P) * (W / P) * C * P * P;
+    k_patches_split<<<flat_grid_t(n / 4), 256, 0, st>>>(img, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), B, C, H, W, P, 0);
+    return 0;
+}
+int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
+                               const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st) {
+    __bf16* hh = reinterpret_cast<__bf16*>(h_hi);
+    __bf16* hl = reinterpret_cast<__bf16*>(h_lo);
+    if (mode == 0) launch_resid_ln_split<0>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
+    else launch_resid_ln_split<1>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
+    return 0;
+}
+int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st) {
+    k_gelu_split<<<flat_grid_t(n / 4), 256, 0, st>>>(Y, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), n / 4);
     return 0;
 }
 

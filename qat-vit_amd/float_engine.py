@@ -1,0 +1,210 @@
+"""Host side of the native float (pre-QAT) student step (``qatvit_float_student_*``, include/qatvit.h).
+
+The reference trains the FLOAT student for the first ``qat_start_epoch`` epochs (qat_trainer.py:295-361 before ``prepare_qat``):
+in fp32 in train_final.sh, under ``torch.amp.autocast`` + ``GradScaler`` in the Optuna objective.  ``native_float(wrapper)`` opts an
+unprepared ``QATWrapper(vit_*_patch16_224)`` into the native step: its ``forward`` on a CUDA tensor then runs
+``qatvit_float_student_forward`` and autograd's backward ``qatvit_float_student_backward``, fp32-accurate (bf16 (hi, lo) pairs, three
+MFMA passes per product) whatever autocast says.  Without the opt-in nothing changes: the float tree is ordinary ``nn.Module`` code.
+
+Engines live in a ``WeakKeyDictionary`` keyed by the wrapper, never on the module, so ``copy.deepcopy`` / ``prepare_qat(inplace=False)``
+copy no ctypes state; a copy is not opted in.  A prepared wrapper always takes the QAT engine (engine.py) first.
+"""
+from __future__ import annotations
+
+import ctypes
+import weakref
+from typing import List, Optional
+
+import torch
+import torch.nn as nn
+
+from . import native
+
+_OPTED = weakref.WeakKeyDictionary()   # wrapper -> FloatStudentEngine (or None until its first CUDA forward)
+
+
+def _student_params(model: nn.Module) -> List[torch.Tensor]:
+    pe = model.patch_embed.proj
+    ps = [pe.weight, pe.bias, model.cls_token, model.pos_embed]
+    for b in model.blocks:
+        ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias,
+               b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
+    return ps + [model.norm.weight, model.norm.bias, model.head.weight, model.head.bias]
+
+
+def check_shape(model: nn.Module) -> None:
+    """Raise unless the native float step covers this tree (the QAT engine's limits)."""
+    from .vit import VisionTransformer
+
+    if not isinstance(model, VisionTransformer):
+        raise RuntimeError(f"native float step: expected the ViT student tree, got {type(model).__name__}")
+    D, heads, depth = model.embed_dim, model.num_heads, len(model.blocks)
+    hd = D // heads
+    why = []
+    if D % 128 or D > 768:
+        why.append(f"embed_dim {D} (a multiple of 128, <= 768)")
+    if D % heads or hd not in (32, 64):
+        why.append(f"head_dim {hd} (32 or 64)")
+    if model.patch_embed.num_patches + 1 > 224:
+        why.append(f"{model.patch_embed.num_patches + 1} tokens (<= 224)")
+    if depth < 1 or depth > 12:
+        why.append(f"depth {depth} (1..12)")
+    pe = model.patch_embed.proj
+    if pe.kernel_size[0] % 4 or (pe.in_channels * pe.kernel_size[0] * pe.kernel_size[1]) % 128:
+        why.append("patch embedding (patch size a multiple of 4, in_chans * patch^2 a multiple of 128)")
+    if type(model.head) is not nn.Linear or type(pe) is not nn.Conv2d:
+        why.append("head / patch embedding are not plain Linear / Conv2d")
+    for b in model.blocks:
+        if b.mlp.fc1.weight.shape[0] % 128:
+            why.append(f"mlp hidden {b.mlp.fc1.weight.shape[0]} (a multiple of 128)")
+            break
+    for m in model.modules():
+        if isinstance(m, nn.Dropout) and m.p != 0.0:
+            why.append("dropout != 0")
+            break
+    for b in model.blocks:
+        if not all(isinstance(getattr(b, n), nn.Identity) for n in ("ls1", "ls2", "drop_path1", "drop_path2")):
+            why.append("layer scale / drop-path")
+            break
+    if why:
+        raise RuntimeError("native float step: unsupported model: " + "; ".join(why))
+
+
+class FloatStudentEngine:
+    def __init__(self, wrapper: nn.Module):
+        model = wrapper.model
+        check_shape(model)
+        self.lib = native.lib()
+        self.params = _student_params(model)
+        dev = self.params[0].device
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or not p.is_cuda:
+                raise RuntimeError("native float step: the parameters must be contiguous fp32 tensors on one CUDA device")
+        self.device = dev
+        blocks = list(model.blocks)
+        pe = model.patch_embed.proj
+        self._cfg_kw = dict(
+            img_size=model.patch_embed.img_size, patch_size=model.patch_embed.patch_size, in_chans=pe.weight.shape[1], embed_dim=model.embed_dim,
+            depth=len(blocks), num_heads=blocks[0].attn.num_heads, mlp_hidden=blocks[0].mlp.fc1.weight.shape[0], num_classes=model.head.weight.shape[0],
+            act_qmin=0, act_qmax=255, w_qmin=-128, w_qmax=127, w_per_channel=0, averaging_const=0.01, ln_eps=float(blocks[0].norm1.eps),
+        )
+        self._ptrs_key = tuple(p.data_ptr() for p in self.params)
+        self._ptr_params = (ctypes.c_void_p * len(self.params))(*self._ptrs_key)
+        self.workspace: Optional[torch.Tensor] = None
+        self.capacity = 0           # the batch the workspace is sized for
+        self.generation = 0         # bumped by every forward: the workspace holds the activations of exactly one forward
+        self.grad_numel = sum(p.numel() for p in self.params)
+
+    def cfg_for(self, batch: int) -> native.Cfg:
+        return native.Cfg(batch=batch, **self._cfg_kw)
+
+    def workspace_bytes(self, batch: int) -> int:
+        n = self.lib.qatvit_float_student_workspace_bytes(ctypes.byref(self.cfg_for(batch)))
+        if n <= 0:
+            raise RuntimeError("qatvit_float_student_workspace_bytes: " + self.lib.qatvit_last_error().decode())
+        return n
+
+    def _reserve(self, batch: int) -> None:
+        if batch <= self.capacity:
+            return
+        nbytes = self.workspace_bytes(batch)
+        self.workspace = None
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.capacity = batch
+        native.check(self.lib.qatvit_float_student_init(ctypes.byref(self.cfg_for(batch)), self.workspace.data_ptr(), native.stream_ptr()),
+                     "qatvit_float_student_init")
+
+    def stale(self) -> bool:
+        return tuple(p.data_ptr() for p in self.params) != self._ptrs_key
+
+    def forward(self, images: torch.Tensor) -> torch.Tensor:
+        k = self._cfg_kw
+        if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[1:]) != (k["in_chans"], k["img_size"], k["img_size"]):
+            raise RuntimeError(f"expected images of shape (B, {k['in_chans']}, {k['img_size']}, {k['img_size']}), got {tuple(images.shape)}")
+        if not images.is_cuda or images.device != self.device:
+            raise RuntimeError(f"native float step: images on {images.device}, parameters on {self.device}")
+        images = images.to(torch.float32).contiguous()
+        self._reserve(images.shape[0])
+        c = self.cfg_for(images.shape[0])
+        logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
+        self.generation += 1
+        native.check(self.lib.qatvit_float_student_forward(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
+                                                           self.workspace.data_ptr(), native.stream_ptr()), "qatvit_float_student_forward")
+        return logits
+
+    def backward(self, dlogits: torch.Tensor, batch: int) -> List[torch.Tensor]:
+        c = self.cfg_for(batch)
+        dlogits = dlogits.to(torch.float32).contiguous()
+        flat = torch.zeros(self.grad_numel, dtype=torch.float32, device=self.device)
+        views, o = [], 0
+        for p in self.params:
+            views.append(flat[o:o + p.numel()].view(p.shape))
+            o += p.numel()
+        gptr = (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
+        native.check(self.lib.qatvit_float_student_backward(ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr, self.workspace.data_ptr(),
+                                                            native.stream_ptr()), "qatvit_float_student_backward")
+        return views
+
+
+class _FloatStudentStep(torch.autograd.Function):
+    # cast_inputs=float32: inside torch.autocast("cuda") the step keeps its own (fp32-accurate) arithmetic and returns fp32 logits
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, images, engine, *params):
+        ctx.engine = engine
+        out = engine.forward(images)
+        ctx.generation = engine.generation
+        ctx.batch = images.shape[0]
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dlogits):
+        # as engine._StudentStep: the gradients are views of one flat buffer assigned to .grad directly (DDP's post-accumulate-grad hooks
+        # fire on that assignment)
+        eng = ctx.engine
+        if eng.generation != ctx.generation:
+            raise RuntimeError(
+                "qat-vit_amd: another forward of this model ran between this forward and its backward; the native step keeps the "
+                "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
+                "forward/backward per micro-batch)."
+            )
+        grads = eng.backward(dlogits, ctx.batch)
+        for p, g in zip(eng.params, grads):
+            if p.grad is None:
+                p.grad = g
+            else:
+                p.grad.add_(g)
+        return (None, None) + (None,) * len(grads)
+
+
+def native_float(wrapper: nn.Module) -> nn.Module:
+    """Opt an unprepared ``QATWrapper(vit_*_patch16_224)`` into the native float step; returns the wrapper.
+
+    The parameters must already be on the GPU; the shape is checked here.  Afterwards ``wrapper(x)`` on a CUDA tensor runs the native
+    forward (and its backward), a CPU tensor raises; ``prepare_qat`` of the wrapper is unaffected (a prepared wrapper takes the QAT engine)."""
+    from .model_registry import QATWrapper
+
+    if not isinstance(wrapper, QATWrapper):
+        raise TypeError(f"native_float expects a QATWrapper, got {type(wrapper).__name__}")
+    if hasattr(wrapper.quant, "activation_post_process"):
+        raise RuntimeError("native_float: the wrapper is already prepared for QAT (it runs the native QAT step)")
+    if any(not p.is_cuda for p in wrapper.parameters()):
+        raise RuntimeError("native_float: move the model to the GPU first (model.cuda()); the native float step runs on MI355X only")
+    _OPTED[wrapper] = FloatStudentEngine(wrapper)
+    return wrapper
+
+
+def is_native_float(wrapper) -> bool:
+    return wrapper in _OPTED
+
+
+def engine_of(wrapper) -> Optional[FloatStudentEngine]:
+    return _OPTED.get(wrapper)
+
+
+def float_forward(wrapper, images: torch.Tensor) -> torch.Tensor:
+    eng = _OPTED.get(wrapper)
+    if eng is None or eng.stale():   # parameters re-allocated (e.g. .to()): the float step keeps no state, rebuild
+        eng = _OPTED[wrapper] = FloatStudentEngine(wrapper)
+    return _FloatStudentStep.apply(images, eng, *eng.params)

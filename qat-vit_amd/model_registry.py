@@ -13,7 +13,8 @@ entries and ``get_model_complexity``'s constants.  ``PLATFORM`` is the constant 
 
 The difference that matters: once ``prepare_qat`` has run on the wrapper and the input is
 a CUDA(HIP) tensor, ``QATWrapper.forward`` executes in libqatvit.so.  A prepared (QAT) wrapper refuses
-CPU tensors - there is no CPU fallback for the hot path; the float tree before ``prepare_qat`` is plain ``nn.Module`` code.
+CPU tensors - there is no CPU fallback for the hot path; the float tree before ``prepare_qat`` is plain ``nn.Module`` code
+unless ``native_float(wrapper)`` opted it into the native float step (float_engine.py).
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ import torch
 import torch.nn as nn
 from torch.ao.quantization import DeQuantStub, QuantStub
 
-from . import engine
+from . import engine, float_engine
 from .vit import create_vit
 
 PLATFORM = "mi355x"
@@ -51,6 +52,10 @@ class QATWrapper(nn.Module):
             if not x.is_cuda:
                 raise RuntimeError("qat-vit_amd executes the QAT student on MI355X only; got a CPU tensor (no CPU fallback exists)")
             return self.dequant(engine.student_forward(self, x))
+        if float_engine.is_native_float(self):   # native_float() opted this float wrapper in: native float step, MI355X only
+            if not x.is_cuda:
+                raise RuntimeError("qat-vit_amd: this float student was opted into the native step (native_float); got a CPU tensor (no CPU fallback exists)")
+            return self.dequant(float_engine.float_forward(self, x))
         # float (pre-QAT) or convert()-ed tree: the stubs are identities / stock quantized modules
         # (torch/ao/quantization/stubs.py:25-26,43-44); ordinary nn.Module code on whatever device the tree lives on
         return self.dequant(self.model(self.quant(x)))

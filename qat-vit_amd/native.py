@@ -65,6 +65,10 @@ SIGNATURES = {
     "qatvit_teacher_workspace_bytes": (c_int64, [c_void_p]),
     "qatvit_teacher_forward": (c_int, [c_void_p] * 8),
     "qatvit_teacher_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "qatvit_float_student_workspace_bytes": (c_int64, [c_void_p]),
+    "qatvit_float_student_init": (c_int, [c_void_p] * 3),
+    "qatvit_float_student_forward": (c_int, [c_void_p] * 6),
+    "qatvit_float_student_backward": (c_int, [c_void_p] * 6),
     "qatvit_infer_workspace_bytes": (c_int64, [c_void_p]),
     "qatvit_infer_prepare": (c_int, [c_void_p] * 6),
     "qatvit_infer_forward": (c_int, [c_void_p] * 8),
