@@ -1267,17 +1267,12 @@ static void launch3(int which, const AttnArgs& a, hipStream_t st) {
     const int grid = a.B * a.H;
     static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_fwd<HD, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * img + kAW * 8 * (HD + 4) * 4)),
                         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_dq<HD, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * img + kAW * 8 * (HD + 4) * 4)),
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_dkv<HD, NKT, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * img + NKT * 128)),
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_dkv<HD, NKT, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * img + NKT * 128)), true);
+                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_dkv<HD, NKT, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * img + NKT * 128)), true);
     (void)once;
     const size_t scratch = (size_t)kAW * 8 * (HD + 4) * sizeof(float);   // half-tile re-tiling scratch: 2 workgroups per CU (fwd, dQ)
     if (which == 0) k_attn_fwd<HD, NKT><<<grid, kAW * 64, 2 * img + scratch, st>>>(a);
     else if (which == 1) k_attn_bwd_dq<HD, NKT><<<grid, kAW * 64, 2 * img + scratch, st>>>(a);
-    else {
-        static const int dkv16 = getenv("QATVIT_ATTN_DKV16") ? atoi(getenv("QATVIT_ATTN_DKV16")) : 0;   // 16 waves x one key tile each (tuning)
-        if (dkv16 && NKT > 8) k_attn_bwd_dkv<HD, NKT, 16><<<grid, 16 * 64, 3 * img + NKT * 128, st>>>(a);
-        else k_attn_bwd_dkv<HD, NKT, 8><<<grid, kAW * 64, 3 * img + NKT * 128, st>>>(a);
-    }
+    else k_attn_bwd_dkv<HD, NKT, 8><<<grid, kAW * 64, 3 * img + NKT * 128, st>>>(a);
 }
 
 static int dispatch(int which, const AttnArgs& a, hipStream_t st) {
@@ -1307,8 +1302,7 @@ int launch_attn_fwd(const float* qkv, const float* qp, int qmin, int qmax, int B
 }
 
 bool attn_bwd_is_fused(int T, int H, int D, bool codes) {
-    static const bool fused_on = !(getenv("QATVIT_ATTN_BWD_FUSED") && atoi(getenv("QATVIT_ATTN_BWD_FUSED")) == 0);
-    return fused_on && codes && H > 0 && D % H == 0 && D / H == 64 && T > 32 && T <= 224;
+    return knobs().attn_bwd_fused && codes && H > 0 && D % H == 0 && D / H == 64 && T > 32 && T <= 224;
 }
 
 int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B, int T, int H, int D, const void* O_hi, const void* O_lo,

@@ -1,6 +1,7 @@
 // extern "C" surface of libqatvit.so: argument validation + error strings around the
 // launchers.  Declarations and the reference call sites they replace: include/qatvit.h.
 #include <stdarg.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/qatvit.h"
@@ -14,6 +15,17 @@ void set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+static bool knob(const char* name) {
+    const char* v = getenv(name);
+    return !v || atoi(v) != 0;
+}
+const Knobs& knobs() {
+    static const Knobs k{knob("QATVIT_I8"), knob("QATVIT_F16"), knob("QATVIT_FC2_CODES"), knob("QATVIT_FC1_BITS"), knob("QATVIT_FC2W_CODES"),
+                         knob("QATVIT_WBATCH"), knob("QATVIT_ATTN_CODES"), knob("QATVIT_QKV_2PASS"), knob("QATVIT_LNB_FUSE"), knob("QATVIT_QP_LATE"),
+                         knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP")};
+    return k;
 }
 }  // namespace qv
 

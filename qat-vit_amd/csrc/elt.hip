@@ -237,55 +237,6 @@ __global__ __launch_bounds__(256) void k_ln_apply_quant(const float* __restrict_
     }
 }
 
-// Row form of k_ln_apply_quant (the same arithmetic per element): one wave per row, lane l holds columns 4 l + 256 j - gamma / beta stay in registers, mean / rstd are one
-// value per row, so a row costs NV 16-byte loads and NV stores instead of five address instructions per float4.  Measured EQUAL to the flat form (24.5 vs 23.7 us per launch in
-// the step: the pass is paced by HBM, not by its address instructions): QATVIT_LN_APPLY_ROWS=1 selects it, the flat form stays the default.
-template <int NV>
-__global__ __launch_bounds__(256) void k_ln_apply_quant_rows(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ qp, int qmin,
-                                                             int qmax, __bf16* __restrict__ out, int64_t M, int D, int8_t* __restrict__ out8, int center, int out_f16,
-                                                             const QpLate late) {
-    __shared__ float sQp[4];
-    QP q;
-    if (late.stats) { const float4 r = qp_late_resolve(late, sQp); q = QP{r.x, r.y, r.z, r.w}; }
-    else q = load_qp(qp);
-    const int lane = threadIdx.x & 63;
-    bool act[NV];
-    int cc[NV];
-    float4 g[NV], b[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c = lane * 4 + 256 * j;
-        act[j] = c < D;
-        cc[j] = act[j] ? c : 0;
-        g[j] = *reinterpret_cast<const float4*>(gamma + cc[j]);
-        b[j] = *reinterpret_cast<const float4*>(beta + cc[j]);
-    }
-    const float sh = q.zp - (float)center;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * 4) {
-        float4 v[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) v[j] = *reinterpret_cast<const float4*>(x + row * D + cc[j]);
-        const float mu = mean[row], rs = rstd[row];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) pin4(v[j]);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            if (!act[j]) continue;
-            bf16x4 o;
-            o[0] = (__bf16)fqi((v[j].x - mu) * rs * g[j].x + b[j].x, q, qmin, qmax);
-            o[1] = (__bf16)fqi((v[j].y - mu) * rs * g[j].y + b[j].y, q, qmin, qmax);
-            o[2] = (__bf16)fqi((v[j].z - mu) * rs * g[j].z + b[j].z, q, qmin, qmax);
-            o[3] = (__bf16)fqi((v[j].w - mu) * rs * g[j].w + b[j].w, q, qmin, qmax);
-            if (out && out_f16) *reinterpret_cast<uint2*>(out + row * D + cc[j]) = make_uint2(pk_f16((float)o[0], (float)o[1]), pk_f16((float)o[2], (float)o[3]));
-            else if (out) *reinterpret_cast<bf16x4*>(out + row * D + cc[j]) = o;
-            if (out8)
-                *reinterpret_cast<char4*>(out8 + row * D + cc[j]) = make_char4((signed char)((float)o[0] + sh), (signed char)((float)o[1] + sh),
-                                                                              (signed char)((float)o[2] + sh), (signed char)((float)o[3] + sh));
-        }
-    }
-}
-
 // ---------------------------------------------------------------- inference: LayerNorm + quantise in one pass
 // out8[row][c] = q(LN(x)[row][c]) - center as int8 with FROZEN qparams (no observer statistics: nothing depends on a global min/max, so the
 // row statistics, the normalisation and the quantisation fuse into one read of x).  The arithmetic is the training path's, operation for
@@ -765,16 +716,6 @@ int launch_resid_fq_lnstats(int mode, const float* x_prev, const float* Y, const
 
 int launch_ln_apply_quant(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp, int qmin,
                           int qmax, void* out_bf16, int64_t M, int D, hipStream_t st, void* out8, int center, bool out_f16, const QpLate* late) {
-    static const bool rows = getenv("QATVIT_LN_APPLY_ROWS") && atoi(getenv("QATVIT_LN_APPLY_ROWS")) != 0;   // 1: one wave per row (measured equal: 24.5 vs 23.7 us per launch)
-    const int nv = (D + 255) / 256;
-    if (rows && D % 4 == 0 && nv >= 1 && nv <= kMaxV) {
-        const int grid = rows_grid(M);
-#define QV_LNA(NV_) k_ln_apply_quant_rows<NV_><<<grid, 256, 0, st>>>(x, mean, rstd, gamma, beta, qp, qmin, qmax, reinterpret_cast<__bf16*>(out_bf16), M, D, \
-                                                                    reinterpret_cast<int8_t*>(out8), center, out_f16 ? 1 : 0, late ? *late : QpLate{})
-        if (nv == 1) QV_LNA(1); else if (nv == 2) QV_LNA(2); else QV_LNA(3);
-#undef QV_LNA
-        return 0;
-    }
     k_ln_apply_quant<<<flat_grid(M * (D / 4)), 256, 0, st>>>(x, mean, rstd, gamma, beta, qp, qmin, qmax, reinterpret_cast<__bf16*>(out_bf16), M, D,
                                                              reinterpret_cast<int8_t*>(out8), center, out_f16 ? 1 : 0, late ? *late : QpLate{});
     return 0;
@@ -813,7 +754,7 @@ int launch_ln_bwd_fq(int acc, const float* dH, const float* x, const float* mean
                      const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T,
                      int cls_only, hipStream_t st, const LnBwdNext* next) {
     if (D % 4 != 0 || D > 256 * kMaxV) { set_error("ln_bwd_fq: D=%d unsupported", D); return 1; }
-    static const int rpw = getenv("QATVIT_LNB_ROWS") ? atoi(getenv("QATVIT_LNB_ROWS")) : 16;   // rows per wave (8 waves per block): fewer blocks = fewer same-address dgamma/dbeta atomics (12 ns each, serialised)
+    constexpr int rpw = 16;   // rows per wave (8 waves per block): fewer blocks = fewer same-address dgamma/dbeta atomics (12 ns each, serialised)
     int grid = (int)((M + 8 * rpw - 1) / (8 * rpw));
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;

@@ -64,7 +64,49 @@ static int wparam(const Dims& d, int wi) {  // index of the weight tensor in par
     return P_BLOCK0 + B_COUNT * blk + map[k];
 }
 
+// Which form every GEMM, attention pass and LayerNorm backward of a configuration runs: decided once, from the knob table (qv_common.h Knobs) and the
+// shapes.  All blocks share their shapes, so all blocks take the same forms.  What stays per call: the flags (QATVIT_FWD_X16, QATVIT_BWD_DY16,
+// QATVIT_BWD_CALIBRATE), injection, the stage range, and the M each strip launch checks (i8_strip_covers).
+struct Forms {
+    bool i8;                 // the grid x grid forward GEMMs (patch-embed, qkv, fc1) on int8 MFMA where their shapes allow (linear_fwd_grid)
+    bool w_batched;          // the weight preparation as three multi-tensor launches (the only writer of the fp16 weight copies)
+    bool late;               // late-resolved qparams (qv_kernels.h QpLate): LayerNorm / proj / fc2 outputs, qkv / fc1 where the strip kernel's code pass consumes them
+    bool f16_proj, f16_fc2;  // the float operands of the proj / fc2 forward GEMMs as fp16 (hi, lo) pairs (else bf16 pairs)
+    bool fc2_codes;          // fc2's forward A operand as one byte per element + a 256-entry table of fp16 pairs (else the two fp16 planes)
+    bool fc1_code_bits;      // the backward's fc1 codes as that byte plane + one STE mask bit per element (else the uint16 plane; needs the tall dgrad tile)
+    bool fc2w_codes;         // fc2's weight gradient from the byte plane + a bf16-pair table (else the bf16 planes; needs the 128 x 384 wgrad tile)
+    bool attn_codes;         // the attention backward reads the codes its forward saved (else it re-quantises the fp32 qkv)
+    bool qkv_2pass;          // the qkv GEMM as a statistics pass + a pass writing codes and mask bits in the attention layout (the fp32 qkv never exists)
+    bool attn_bwd_fused;     // the fused attention backward (head_dim 64, 33..224 tokens, saved codes)
+    bool lnb;                // the LayerNorm backward in the fc1 / qkv dgrad epilogue (NTPost mode 8: the 208 x 384 tile holds whole rows)
+    bool x_plane_from_q8;    // the one-plane qkv / fc1 weight gradients read the int8 plane of the LayerNorm outputs (q - center) instead of the fp16 one
+    bool tn_stream;          // the per-block gradient planes + stream-K scratch exist (the one-plane weight gradients then run at the end of the call)
+    bool dy16;               // the one-plane backward covers this configuration
+};
+static Forms forms_of(const qatvit_cfg& c, const Dims& d) {
+    const Knobs& k = knobs();
+    const bool byte_codes = c.act_qmax - c.act_qmin <= 255;
+    Forms f{};
+    f.i8 = k.i8;
+    f.w_batched = k.wbatch && d.n_w <= kMaxW;
+    f.late = k.qp_late && d.n_act <= kMaxActFq;
+    f.f16_proj = k.f16 && f.w_batched && d.D % 384 == 0;   // the fp16-pair GEMM: N % 384 == 0, K % 32 == 0 (proj: N = K = D; fc2: N = D, K = Hd)
+    f.f16_fc2 = f.f16_proj && d.Hd % 32 == 0;
+    f.fc2_codes = f.f16_fc2 && k.fc2_codes && d.Hd % 64 == 0 && byte_codes;
+    f.fc1_code_bits = f.fc2_codes && k.fc1_bits && f.i8 && d.Hd % 384 == 0;
+    f.fc2w_codes = f.fc1_code_bits && k.fc2w_codes;
+    f.attn_codes = k.attn_codes && byte_codes;
+    f.qkv_2pass = k.qkv_2pass && f.attn_codes && f.i8 && (3 * d.D) % 384 == 0 && d.D % 64 == 0 && (d.D / d.H) % 32 == 0;
+    f.attn_bwd_fused = attn_bwd_is_fused(d.T, d.H, d.D, f.attn_codes);
+    f.lnb = k.lnb_fuse && d.D == 384;
+    f.x_plane_from_q8 = f.i8 && k.tn_q8 && d.D % 384 == 0;
+    f.tn_stream = k.tn_stream && d.D % 384 == 0 && d.Hd % 384 == 0;
+    f.dy16 = f.i8 && f.w_batched && d.D % 384 == 0 && d.Hd % 384 == 0 && f.qkv_2pass && f.attn_bwd_fused && f.f16_proj && f.fc2w_codes;
+    return f;
+}
+
 struct Plan {
+    Forms form;
     // byte offsets into the workspace
     int64_t stats, qp_act, qp_w, imgq, Y0, meanF, rstdF, hq, logits_pre;
     int64_t x_in, x_mid, mean1, rstd1, mean2, rstd2, h1q, qkv, O_hi, O_lo, lse, Yproj, h2q, Y1, G_hi, G_lo, Y2, mproj, m2, qkv8, qkvm, G8, glut, Y1m, glutq;  // per-block base, stride blk (mproj / m2: STE mask bits of Yproj / Y2)
@@ -87,19 +129,10 @@ enum { DS_FC2 = 0, DS_FC1, DS_PROJ, DS_QKV, DS_COUNT };
 
 static int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
-// QATVIT_TN_STREAM (default on): the one-plane backward keeps every block's gradient planes and runs the weight gradients of a whole backward call as one persistent
-// stream-K launch per X form (gemm.hip k_tn_stream).  The planes are part of the workspace where the shapes allow the form (dy16_supported decides at run time).
-static bool tn_stream_on() {
-    static const bool on = !(getenv("QATVIT_TN_STREAM") && atoi(getenv("QATVIT_TN_STREAM")) == 0);
-    return on;
-}
-static bool tn_stream_planes(const qatvit_cfg& c) {
-    return tn_stream_on() && c.embed_dim % 384 == 0 && c.mlp_hidden % 384 == 0;
-}
-
 static int make_plan(const qatvit_cfg& c, Plan* p) {
     const Dims d = dims_of(c);
     if (d.depth > 64) { set_error("engine: depth %d > 64", d.depth); return 1; }
+    p->form = forms_of(c, d);
     int64_t o = 0;
     auto take = [&](int64_t bytes) { int64_t r = o; o += al(bytes); return r; };
     const int64_t M = d.M, D = d.D, Hd = d.Hd;
@@ -181,7 +214,7 @@ static int make_plan(const qatvit_cfg& c, Plan* p) {
     p->dY0_hi = take((int64_t)d.B * d.np * D * 2); p->dY0_lo = take((int64_t)d.B * d.np * D * 2);
     p->tn_scratch = take(kTnScratchBytes);   // split partials of the weight-gradient GEMMs (two-phase, non-atomic reduction)
     p->dyp = p->tn_stream = -1; p->dyp_stride = 0;
-    if (tn_stream_planes(c)) {
+    if (p->form.tn_stream) {
         p->dyp_p = al(M * D * 2); p->dyp_h = p->dyp_p + al(M * D * 2); p->dyp_q = p->dyp_h + al(M * Hd * 2);
         p->dyp_stride = p->dyp_q + al(M * 3 * D * 2);
         p->dyp = take(p->dyp_stride * d.depth);
@@ -242,69 +275,6 @@ struct ProfScope {
     }
 };
 
-// QATVIT_I8=0: the grid x grid forward GEMMs (patch-embed, qkv, fc1) on bf16 MFMA instead of int8 MFMA (bit-identical results)
-static bool use_i8() {
-    static const int on = getenv("QATVIT_I8") ? atoi(getenv("QATVIT_I8")) : 1;
-    return on != 0;
-}
-
-// QATVIT_F16=0: the float operands of the proj / fc2 FORWARD GEMMs as bf16 (hi, lo) pairs (2^-17 per element) instead of fp16 pairs (2^-23):
-// the round-1 arithmetic, kept to measure what the extra precision buys (tests/test_gpu_stage_parity.py flip table)
-static bool use_f16() {
-    static const int on = getenv("QATVIT_F16") ? atoi(getenv("QATVIT_F16")) : 1;
-    return on != 0;
-}
-
-// QATVIT_FC2_CODES=0: fc2's forward A operand as the two fp16 planes (4 B per element written by fc1's storing pass and read back) instead of
-// one byte per element expanded through a 256-entry table inside the GEMM (k_gemm_nt_ac) - the same bits either way
-static bool fc2_codes() {
-    static const int on = getenv("QATVIT_FC2_CODES") ? atoi(getenv("QATVIT_FC2_CODES")) : 1;
-    return on != 0;
-}
-
-// QATVIT_FC1_BITS=0: the backward's fc1 codes as the uint16 plane (grid index | in-range bit << 15: 2 B per element written by fc1's storing pass and
-// read by the fc2 dgrad epilogue) instead of the byte plane fc2's forward reads anyway + one STE mask bit per element (1.125 B read, 0.125 B written)
-static bool fc1_bits() {
-    static const int on = getenv("QATVIT_FC1_BITS") ? atoi(getenv("QATVIT_FC1_BITS")) : 1;
-    return on != 0;
-}
-
-// QATVIT_FC2W_CODES=0: fc2's weight gradient reads gelu(fq(fc1)) as the bf16 (hi, lo) planes fc1's storing pass wrote (4 B per element written and read)
-// instead of the byte plane + a 256-entry bf16-pair table expanded inside the wgrad kernel (launch_gemm_tn_codes) - the same bits either way
-static bool fc2w_codes() {
-    static const int on = getenv("QATVIT_FC2W_CODES") ? atoi(getenv("QATVIT_FC2W_CODES")) : 1;
-    return on != 0;
-}
-
-// QATVIT_WBATCH=0: one launch triple per weight instead of three multi-tensor launches (tuning; also the path of models deeper than the
-// tables hold).  That path does not write the fp16 weight copies, so the fp16-pair forward GEMMs are off with it.
-static bool w_batched(const Dims& d) {
-    static const int wbatch = getenv("QATVIT_WBATCH") ? atoi(getenv("QATVIT_WBATCH")) : 1;
-    return wbatch && d.n_w <= kMaxW;
-}
-
-// QATVIT_ATTN_CODES=0: the attention backward re-quantises the pre-FQ qkv tensor instead of reading the codes its forward saved (tuning / A-B)
-static bool attn_codes(const qatvit_cfg& c) {
-    static const int on = getenv("QATVIT_ATTN_CODES") ? atoi(getenv("QATVIT_ATTN_CODES")) : 1;
-    return on != 0 && c.act_qmax - c.act_qmin <= 255;
-}
-
-// QATVIT_QKV_2PASS=0: the qkv GEMM once, writing its fp32 pre-fake-quant output (232 MB per block at batch 256) that the attention forward reads back,
-// quantises and saves as codes - instead of twice (a statistics-only pass for the observer, then a pass whose epilogue quantises with the fresh
-// qparams and writes the uint8 codes + STE mask bits in the attention layout: the fp32 tensor never exists, the attention forward reads 1 B per element)
-static bool qkv_2pass(const qatvit_cfg& c) {
-    static const int on = getenv("QATVIT_QKV_2PASS") ? atoi(getenv("QATVIT_QKV_2PASS")) : 1;
-    const int hd = c.embed_dim / c.num_heads;
-    return on != 0 && attn_codes(c) && use_i8() && (3 * c.embed_dim) % 384 == 0 && c.embed_dim % 64 == 0 && hd % 32 == 0;
-}
-
-// QATVIT_LNB_FUSE=0: the LayerNorm backward as its own kernel behind the fc1 / qkv dgrad GEMM (re-reads the fp32 gradient those wrote) instead
-// of inside their epilogue (embed_dim 384 only: the 208 x 384 tile holds whole rows)
-static bool lnb_fuse() {
-    static const int on = getenv("QATVIT_LNB_FUSE") ? atoi(getenv("QATVIT_LNB_FUSE")) : 1;
-    return on != 0;
-}
-
 struct Ctx {
     const qatvit_cfg& c;
     Dims d;
@@ -338,15 +308,11 @@ struct Ctx {
     int a_norm() const { return A_BLOCK0 + AB_COUNT * d.depth; }
     int a_head() const { return a_norm() + 1; }
     int widx(int blk_i, int k) const { return 1 + WB_COUNT * blk_i + k; }
-    // ---- late qparams (qv_kernels.h QpLate, QATVIT_QP_LATE=0 switches it off): the quantizers whose consumer kernel resolves the observer / qparams update
-    // itself - the LayerNorm outputs (k_ln_apply_quant), the proj / fc2 outputs (k_resid_fq_lnstats) of every block always, the qkv / fc1 outputs where the
-    // strip kernel's code pass is their consumer (decided by the caller: late_strip) - need no k_qparams launch behind the producer of their statistics
-    static bool late_on() {
-        static const int on = getenv("QATVIT_QP_LATE") ? atoi(getenv("QATVIT_QP_LATE")) : 1;
-        return on != 0;
-    }
+    // ---- late qparams (qv_kernels.h QpLate, Forms::late): the quantizers whose consumer kernel resolves the observer / qparams update itself - the
+    // LayerNorm outputs (k_ln_apply_quant), the proj / fc2 outputs (k_resid_fq_lnstats) of every block always, the qkv / fc1 outputs where the strip
+    // kernel's code pass is their consumer (decided by the caller: late_strip) - need no k_qparams launch behind the producer of their statistics
     bool late_kind(int ai) const {
-        if (!late_on() || d.n_act > kMaxActFq || ai < A_BLOCK0 || ai >= A_BLOCK0 + AB_COUNT * d.depth) return false;
+        if (!p.form.late || ai < A_BLOCK0 || ai >= A_BLOCK0 + AB_COUNT * d.depth) return false;
         const int k = (ai - A_BLOCK0) % AB_COUNT;
         return k == AB_N1 || k == AB_N2 || k == AB_PROJ || k == AB_FC2;
     }
@@ -357,7 +323,7 @@ struct Ctx {
     }
     // the staged states into the modules' buffers: once at the end of every forward call
     int commit_late() const {
-        if (!late_on() || d.n_act > kMaxActFq) return 0;
+        if (!p.form.late) return 0;
         QpCommitTab t{};
         t.n = d.n_act; t.staged = at<float>(p.qp_staged); t.stats = at<uint32_t>(p.stats);
         for (int ai = 0; ai < d.n_act; ++ai) { t.rmin[ai] = act[ai].min_val; t.rmax[ai] = act[ai].max_val; t.scale[ai] = act[ai].scale; t.zp[ai] = act[ai].zero_point; }
@@ -385,11 +351,9 @@ struct Ctx {
         const QpLate L = lt ? late(ai) : QpLate{};
         // a QATVIT_FWD_X16 forward whose backward takes the byte plane (k_gemm_tn_q8) writes no 2-byte plane at all: the forward GEMM reads out8 too
         const bool x16 = (flags & QATVIT_FWD_X16) != 0;
-        return launch_ln_apply_quant(xrow, mean, rstd, gamma, beta, act_qp(ai), c.act_qmin, c.act_qmax, x16 && x_plane_from_q8() ? nullptr : out16, d.M, d.D, st,
-                                     use_i8() ? out8 : nullptr, center(), x16, lt ? &L : nullptr);
+        return launch_ln_apply_quant(xrow, mean, rstd, gamma, beta, act_qp(ai), c.act_qmin, c.act_qmax, x16 && p.form.x_plane_from_q8 ? nullptr : out16, d.M, d.D,
+                                     st, p.form.i8 ? out8 : nullptr, center(), x16, lt ? &L : nullptr);
     }
-    // the qkv / fc1 weight gradients of the one-plane backward read the int8 plane of the LayerNorm outputs (q - center) instead of the fp16 one
-    bool x_plane_from_q8() const { return use_i8() && tn_q8_enabled() && d.D % 384 == 0; }
     void qparams_act(int ai) const {
         const qatvit_fq& f = act[ai];
         launch_qparams(act_stats(ai), f.min_val, f.max_val, f.scale, f.zero_point, f.observer_on, f.fake_quant_on, c.averaging_const,
@@ -437,19 +401,15 @@ struct Ctx {
         qparams_after(ai_out, true);
         return 0;
     }
-    bool f16_ok(int wi) const {
-        int N, K; wshape(d, wi, &N, &K);
-        return use_f16() && w_batched(d) && p.w16_off[wi] >= 0 && N % 384 == 0 && K % 32 == 0;
-    }
     int center() const { return (c.act_qmin + c.act_qmax + 1) / 2; }
     // the same forward product with int8 operands: A8 = q - center written next to the bf16 grid by its producer, weight integers + row sums
     // from k_w_quant_all.  Falls back to the bf16 form for shapes the int8 tile does not cover.
-    // late_strip: the output quantizer's qparams are resolved by the strip kernel's code pass (the caller checked strip_consumes): the statistics pass
+    // late_strip: the output quantizer's qparams are resolved by the strip kernel's code pass (the caller checked late_in_strip): the statistics pass
     // (post mode 3) then launches no k_qparams, the code pass gets the QpLate record
     int linear_fwd_grid(const void* A16, const void* A8, int M, int wi, const float* a_qp, const float* bias, float* C, int ai_out,
                         const NTPost* post = nullptr, bool with_stats = true, bool late_strip = false) const {
         int N, K; wshape(d, wi, &N, &K);
-        if (!use_i8() || N % 384 != 0 || K % 64 != 0) return linear_fwd(A16, nullptr, M, wi, a_qp, bias, C, ai_out, post, with_stats);
+        if (!p.form.i8 || N % 384 != 0 || K % 64 != 0) return linear_fwd(A16, nullptr, M, wi, a_qp, bias, C, ai_out, post, with_stats);
         const qatvit_fq& f = wfq[wi];
         {
             ProfScope ps(prof, !post ? 2 : post->mode == 3 ? 7 : post->mode == 4 ? 8 : post->mode == 7 ? 9 : 2, (post && post->mode == 3) ? 0.0 : 2.0 * M * N * K, st);
@@ -457,18 +417,18 @@ struct Ctx {
             const QpLate L = code_pass ? late(ai_out) : QpLate{};
             if (launch_gemm_nt_i8(A8, at<void>(p.w8_off[wi]), at<int32_t>(p.wsum_off[wi]), a_qp, center(), C, M, N, K, K, K, N, a_qp,
                                   c.w_per_channel ? nullptr : f.scale, c.w_per_channel ? f.scale : nullptr, bias,
-                                  with_stats ? act_stats(ai_out) : nullptr, kStatSlots, st, post,
-                                  (w_batched(d) && p.w8f_off[wi] >= 0) ? at<void>(p.w8f_off[wi]) : nullptr, code_pass ? &L : nullptr))
+                                  with_stats ? act_stats(ai_out) : nullptr, kStatSlots, st, post, w8f(wi), code_pass ? &L : nullptr))
                 return 1;
         }
         qparams_after(ai_out, with_stats, late_strip);
         return 0;
     }
+    // the int8 weight of layer wi in fragment order (the strip kernel's B operand), where the forward wrote it
+    void* w8f(int wi) const { return p.form.i8 && p.form.w_batched && p.w8f_off[wi] >= 0 ? at<void>(p.w8f_off[wi]) : nullptr; }
     // will the strip kernel's code pass (post2) be the consumer of quantizer-of-layer-wi's statistics?  (then it resolves the qparams itself)
-    bool strip_consumes(int M, int wi, const NTPost* post2) const {
+    bool late_in_strip(int M, int wi, const NTPost* post2) const {
         int N, K; wshape(d, wi, &N, &K);
-        return late_on() && d.n_act <= kMaxActFq && use_i8() && N % 384 == 0 && K % 64 == 0 && w_batched(d) && p.w8f_off[wi] >= 0 &&
-               i8_strip_covers(at<void>(p.w8f_off[wi]), M, N, K, K, N, post2);
+        return p.form.late && i8_strip_covers(w8f(wi), M, N, K, K, N, post2);
     }
     // the per-channel weight scale of layer wi, which its dY producer folds in (nullptr for per-tensor)
     const float* dy_colscale(int wi) const { return c.w_per_channel ? wfq[wi].scale : nullptr; }
@@ -502,17 +462,10 @@ struct Ctx {
 // One transformer block of the forward, in four parts that each start where the stage-level parity tests inject the oracle's tensor (behind
 // a fake-quantizer that would otherwise amplify upstream one-step flips): 0 = norm1 -> qkv GEMM; 1 = attention -> proj -> residual;
 // 2 = norm2 -> fc1 -> GELU; 3 = fc2 -> residual.
-// fc1's codes for the backward as the uint8 plane + mask bits (needs the forward's fc2-from-codes form, the int8 storing pass, the tall dgrad tile)
-static bool fc1_code_bits(const Ctx& x, int i) {
-    const Dims& d = x.d;
-    return fc1_bits() && use_i8() && fc2_codes() && x.f16_ok(x.widx(i, WB_FC2)) && d.Hd % 384 == 0 && d.D % 64 == 0 && d.Hd % 128 == 0 &&
-           x.c.act_qmax - x.c.act_qmin <= 255;
-}
-// fc2's weight gradient from the byte plane + bf16-pair table (needs the code-bits form above and the 128 x 384 wgrad tile)
-static bool fc2w_code_form(const Ctx& x, int i) { return fc2w_codes() && fc1_code_bits(x, i) && x.d.D % 128 == 0 && x.d.Hd % 384 == 0; }
 static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) {
     const Dims& d = x.d;
     const Plan& p = x.p;
+    const Forms& F = p.form;
     const qatvit_cfg& c = x.c;
     hipStream_t st = x.st;
     const int qa = c.act_qmin, qb = c.act_qmax;
@@ -523,11 +476,11 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
         if (parts & 1) {   // ---- part 0: norm1 -> qkv   (every quantizer's observer / qparams update runs behind the producer of its statistics)
         x.ln_apply(xin, x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.aidx(i, AB_N1), x.blk<void>(p.h1q, i),
                    x.blk<void>(p.h1q8, i));
-        if (qkv_2pass(c)) {
+        if (F.qkv_2pass) {
             NTPost p2{};
             p2.mode = 7; p2.qp = x.act_qp(x.aidx(i, AB_QKV)); p2.qmin = qa; p2.qmax = qb;
             p2.out8 = x.blk<void>(p.qkv8, i); p2.out8_mask = x.blk<void>(p.qkvm, i); p2.code_T = (int)d.T; p2.code_hd = (int)(d.D / d.H);
-            const bool lt = x.strip_consumes(M, x.widx(i, WB_QKV), &p2);   // the code pass resolves the qkv quantizer's qparams itself: no k_qparams launch between the passes
+            const bool lt = x.late_in_strip(M, x.widx(i, WB_QKV), &p2);   // the code pass resolves the qkv quantizer's qparams itself: no k_qparams launch between the passes
             const NTPost p1{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 3, nullptr};
             if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(x.aidx(i, AB_N1)), x.bprm(i, B_QKVB), nullptr,
                                   x.aidx(i, AB_QKV), &p1, true, lt))
@@ -539,18 +492,15 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
                                      x.blk<float>(p.qkv, i), x.aidx(i, AB_QKV)))
             return 1;
         }
-        const bool proj16 = x.f16_ok(x.widx(i, WB_PROJ)), fc2_16 = x.f16_ok(x.widx(i, WB_FC2));
-        const bool fc2_c = fc2_16 && fc2_codes() && d.Hd % 64 == 0 && c.act_qmax - c.act_qmin <= 255;
-        const bool fc1_b = fc2_c && fc1_code_bits(x, i);   // the backward reads the byte plane + mask bits: no uint16 plane is written
         float* const scal16 = x.blk<float>(p.scal16, i);
         if (parts & 2) {   // ---- part 1: attention -> proj -> residual (+ statistics of norm2)
-        const bool from_codes = qkv_2pass(c) && !qkv_injected;   // part 0 left the code plane (and ran the observer); an injected fp32 qkv takes the one-pass route
+        const bool from_codes = F.qkv_2pass && !qkv_injected;   // part 0 left the code plane (and ran the observer); an injected fp32 qkv takes the one-pass route
         if (launch_attn_fwd(from_codes ? nullptr : x.blk<float>(p.qkv, i), x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i),
-                            x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i), st, proj16 ? x.blk<void>(p.O16_hi, i) : nullptr,
-                            proj16 ? x.blk<void>(p.O16_lo, i) : nullptr, proj16 ? scal16 : nullptr, attn_codes(x.c) ? x.blk<void>(p.qkv8, i) : nullptr,
-                            attn_codes(x.c) ? x.blk<void>(p.qkvm, i) : nullptr))
+                            x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i), st, F.f16_proj ? x.blk<void>(p.O16_hi, i) : nullptr,
+                            F.f16_proj ? x.blk<void>(p.O16_lo, i) : nullptr, F.f16_proj ? scal16 : nullptr, F.attn_codes ? x.blk<void>(p.qkv8, i) : nullptr,
+                            F.attn_codes ? x.blk<void>(p.qkvm, i) : nullptr))
             return 1;
-        if (proj16) {
+        if (F.f16_proj) {
             if (x.linear_fwd_f16(x.blk<void>(p.O16_hi, i), x.blk<void>(p.O16_lo, i), scal16, M, x.widx(i, WB_PROJ), x.bprm(i, B_PROJB), x.blk<float>(p.Yproj, i),
                                  x.aidx(i, AB_PROJ)))
                 return 1;
@@ -571,11 +521,11 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
             // bit) for the backward.  The fp32 pre-FQ tensor and the separate fq+gelu pass (620 MB per block) disappear.
             NTPost p2{nullptr, x.act_qp(x.aidx(i, AB_FC1)), qa, qb, nullptr, x.blk<void>(p.G_hi, i), x.blk<void>(p.G_lo, i), 4,
                       x.blk<void>(p.Y1, i)};
-            if (fc2_c) { p2.out8 = x.blk<void>(p.G8, i); p2.lut_out = x.blk<uint32_t>(p.glut, i); p2.out16_scale = scal16 + 1; }
-            if (fc1_b) { p2.code = nullptr; p2.out8_mask = x.blk<void>(p.Y1m, i); }
-            if (fc1_b && fc2w_code_form(x, i)) { p2.out_hi = p2.out_lo = nullptr; p2.lutq_out = x.blk<uint32_t>(p.glutq, i); }   // no 4-byte plane of gelu(fq(fc1)) at all
-            else if (fc2_16) { p2.out16_hi = x.at<void>(p.G16_hi); p2.out16_lo = x.at<void>(p.G16_lo); p2.out16_scale = scal16 + 1; }
-            const bool lt = x.strip_consumes(M, x.widx(i, WB_FC1), &p2);   // (as for qkv: the code pass resolves the fc1 quantizer's qparams)
+            if (F.fc2_codes) { p2.out8 = x.blk<void>(p.G8, i); p2.lut_out = x.blk<uint32_t>(p.glut, i); p2.out16_scale = scal16 + 1; }
+            if (F.fc1_code_bits) { p2.code = nullptr; p2.out8_mask = x.blk<void>(p.Y1m, i); }   // the backward reads the byte plane + mask bits: no uint16 plane
+            if (F.fc2w_codes) { p2.out_hi = p2.out_lo = nullptr; p2.lutq_out = x.blk<uint32_t>(p.glutq, i); }   // no 4-byte plane of gelu(fq(fc1)) at all
+            else if (F.f16_fc2) { p2.out16_hi = x.at<void>(p.G16_hi); p2.out16_lo = x.at<void>(p.G16_lo); p2.out16_scale = scal16 + 1; }
+            const bool lt = x.late_in_strip(M, x.widx(i, WB_FC1), &p2);   // (as for qkv: the code pass resolves the fc1 quantizer's qparams)
             const NTPost p1{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 3, nullptr};
             if (x.linear_fwd_grid(x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.act_qp(x.aidx(i, AB_N2)), x.bprm(i, B_FC1B), nullptr,
                              x.aidx(i, AB_FC1), &p1, true, lt))
@@ -586,11 +536,11 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
         }
         }
         if (parts & 8) {   // ---- part 3: fc2 -> residual (+ statistics of the next LayerNorm)
-        if (fc2_c) {
+        if (F.fc2_codes) {
             if (x.linear_fwd_codes(x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glut, i), scal16 + 1, M, x.widx(i, WB_FC2), x.bprm(i, B_FC2B), x.blk<float>(p.Y2, i),
                                    x.aidx(i, AB_FC2)))
                 return 1;
-        } else if (fc2_16) {
+        } else if (F.f16_fc2) {
             if (x.linear_fwd_f16(x.at<void>(p.G16_hi), x.at<void>(p.G16_lo), scal16 + 1, M, x.widx(i, WB_FC2), x.bprm(i, B_FC2B), x.blk<float>(p.Y2, i),
                                  x.aidx(i, AB_FC2)))
                 return 1;
@@ -656,6 +606,7 @@ static int fwd_part(const Ctx& x, int block, int part, bool inject) {
 static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int s_to, bool inject) {
     const Dims& d = x.d;
     const Plan& p = x.p;
+    const Forms& F = p.form;
     const qatvit_cfg& c = x.c;
     hipStream_t st = x.st;
     const int qa = c.act_qmin, qb = c.act_qmax;
@@ -663,9 +614,9 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
     if (s_from == 0) {
     // a forward from the start observes from empty accumulators: statistics a partial call (a stage range) produced for a consumer that never ran do not leak
     // into this step (the late-resolved quantizers' accumulators are re-armed by their consumer's commit, not behind their producer)
-    if (Ctx::late_on()) launch_ws_init(x.at<uint32_t>(p.stats), (int64_t)d.n_act * kStatSlots * kStatStride / 2, st);
+    if (F.late) launch_ws_init(x.at<uint32_t>(p.stats), (int64_t)d.n_act * kStatSlots * kStatStride / 2, st);
     // ---- weights: observe, qparams, integer operands (row-major and transposed) - all 50 tensors in three launches
-    if (w_batched(d)) {
+    if (F.w_batched) {
         WObsTab to{};
         WQpTab tq{};
         WQuantTab tw{};
@@ -688,12 +639,13 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
             tq.obs_on[wi] = f.observer_on; tq.fq_on[wi] = f.fake_quant_on;
             tq.qp[wi] = x.w_qp(wi); tw.qp[wi] = x.w_qp(wi);
             tw.wq[wi] = x.at<void>(p.w_off[wi]); tw.wqT[wi] = x.at<void>(p.wT_off[wi]);
-            tw.w8[wi] = use_i8() ? x.at<void>(p.w8_off[wi]) : nullptr;
-            tw.w16[wi] = x.f16_ok(wi) ? x.at<void>(p.w16_off[wi]) : nullptr;
-            tw.w8f[wi] = (use_i8() && p.w8f_off[wi] >= 0) ? x.at<void>(p.w8f_off[wi]) : nullptr;
-            tw.wsum[wi] = use_i8() ? x.at<int32_t>(p.wsum_off[wi]) : nullptr;
+            tw.w8[wi] = F.i8 ? x.at<void>(p.w8_off[wi]) : nullptr;
+            const bool w16 = p.w16_off[wi] >= 0 && ((wi - 1) % WB_COUNT == WB_PROJ ? F.f16_proj : F.f16_fc2);   // (w16_off: proj and fc2 only)
+            tw.w16[wi] = w16 ? x.at<void>(p.w16_off[wi]) : nullptr;
+            tw.w8f[wi] = x.w8f(wi);
+            tw.wsum[wi] = F.i8 ? x.at<int32_t>(p.wsum_off[wi]) : nullptr;
         }
-        if (use_i8()) launch_zero_i32(x.at<int32_t>(p.wsum_base), p.wsum_bytes / 4, st);   // row sums are accumulated with integer atomics
+        if (F.i8) launch_zero_i32(x.at<int32_t>(p.wsum_base), p.wsum_bytes / 4, st);   // row sums are accumulated with integer atomics
         launch_w_observe_all(to, st);
         launch_w_qparams_all(tq, st);
         launch_w_quant_all(tw, st);
@@ -713,7 +665,7 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
     launch_minmax(images, 1, (int64_t)d.B * d.chans * d.img * d.img, 0, x.act_stats(A_IN), kStatSlots, st);
     x.qparams_act(A_IN);
     if (launch_img_patches(images, x.at<void>(p.imgq), x.act_qp(A_IN), qa, qb, d.B, d.chans, d.img, d.img, d.patch, st,
-                           use_i8() ? x.at<void>(p.imgq8) : nullptr, x.center()))
+                           F.i8 ? x.at<void>(p.imgq8) : nullptr, x.center()))
         return 1;
     if (x.linear_fwd_grid(x.at<void>(p.imgq), x.at<void>(p.imgq8), d.B * d.np, 0, x.act_qp(A_IN), x.prm(P_PE_B), x.at<float>(p.Y0), A_PE)) return 1;
     if (x.resid_lnstats(0, nullptr, x.at<float>(p.Y0), A_PE, x.prm(P_CLS), x.prm(P_POS), x.blk<float>(p.x_in, 0), x.blk<float>(p.mean1, 0),
@@ -734,269 +686,277 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
     return 0;
 }
 
-// Can this configuration run the one-plane backward?  It needs the forms every one-plane kernel was written for: the 208 x 384 tiles, the fused
-// attention backward (head_dim 64, 33..224 tokens, saved codes), fc1's codes + mask bits, the fused next-branch output of the LayerNorm backward.
-static bool dy16_supported(const Ctx& x) {
-    const Dims& d = x.d;
-    static const bool ln_fuse = !(getenv("QATVIT_LN_FUSE") && atoi(getenv("QATVIT_LN_FUSE")) == 0);
-    return ln_fuse && use_i8() && w_batched(d) && d.D % 384 == 0 && d.Hd % 384 == 0 && qkv_2pass(x.c) && attn_bwd_is_fused(d.T, d.H, d.D, attn_codes(x.c)) &&
-           x.f16_ok(x.widx(0, WB_PROJ)) && fc1_code_bits(x, 0) && fc2w_code_form(x, 0);
-}
-
-// stages: 0 = head + final norm; 1..depth = blocks depth-1..0; depth+1 = embedding
+// ---- the backward.  stages: 0 = head + final norm; 1..depth = blocks depth-1..0; depth+1 = embedding
 // `inject`: the gradient entering stage_from (dxA = d loss / d x_in[depth - stage_from + 1] for a block stage, / d x_in[0] for the embedding
-// stage) was written by the caller; a block stage then rebuilds the masked (hi, lo) copy of it that the previous stage's fused
-// LayerNorm backward would have left for the fc2 weight / data gradient GEMMs.
+// stage) was written by the caller; a block stage then rebuilds the masked copy of it that the previous stage's fused LayerNorm backward would
+// have left for the fc2 weight / data gradient GEMMs.  (Every LayerNorm backward also emits the masked gradient of the branch output that precedes
+// it - from the mask bits of the forward - so the stages of one call run in order; dxA carries over anyway.)
 // x.flags & QATVIT_BWD_DY16: the one-plane form - every gradient that feeds a dgrad / wgrad pair (the masked residual gradient entering fc2 and proj,
 // the fc1 and qkv output gradients) is ONE fp16 plane scaled by a power of two chosen from the previous backward's maxima (dy16.hip) instead of a bf16
 // (hi, lo) pair: one MFMA pass and 2 B per element in eight GEMMs per block.  QATVIT_BWD_CALIBRATE: the pair form, recording those maxima.
-static int bwd(const Ctx& x, const float* dlogits, void* const* grads, int stage_from, int stage_to, bool inject) {
+struct Bwd {
+    const Ctx& x;
+    void* const* grads;
+    bool dy, cal;
+    bool stream;   // deferred weight gradients (k_tn_stream): every block's gradient planes stay in the workspace, the GEMMs are collected here and run at the end of the call
+    float* dxA;    // the gradient w.r.t. the current block's OUTPUT at stage entry
+    float* dxB;    // ... w.r.t. x_mid inside a block
+    std::vector<TNStreamGemm> sg[3];
+    double sflops[3] = {0.0, 0.0, 0.0};
+
+    float* G(int i) const { return reinterpret_cast<float*>(grads[i]); }
+    float* BG(int blk_i, int k) const { return G(P_BLOCK0 + B_COUNT * blk_i + k); }
+    // the one-plane gradient planes of block blk_i - 0 fc2-in, 1 proj-in, 2 fc1-out, 3 qkv-out: one set per block where the weight gradients are deferred, else shared
+    void* plane(int blk_i, int which) const {
+        const Plan& p = x.p;
+        if (!stream) return x.at<void>(which <= 1 ? p.dYs_hi : which == 2 ? p.dY1_hi : p.dqkv_hi);
+        return x.at<char>(p.dyp) + (int64_t)blk_i * p.dyp_stride + (which == 0 ? 0 : which == 1 ? p.dyp_p : which == 2 ? p.dyp_h : p.dyp_q);
+    }
+    // calibration: the maximum of a tensor the pair form just wrote (its hi plane) into the tensor's slot
+    void calib(const void* hi, int64_t n, int blk_i, int k) const { if (cal) launch_absmax_bf16(hi, n, x.dy_slot(blk_i, k), x.st); }
+    // NTPost mode 8: the dgrad GEMM into the output of block i's norm2 (n2) or norm1 runs that LayerNorm's backward in its epilogue (dx_in: the residual
+    // gradient it adds to) and emits nx's masked gradient of the branch output in front of it
+    NTPost lnb_post(int i, bool n2, const float* dx_in, const LnBwdNext& nx) const {
+        const Plan& p = x.p;
+        NTPost post{};
+        post.mode = 8; post.qp = x.act_qp(x.aidx(i, n2 ? AB_N2 : AB_N1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax;
+        post.lnb_x = x.blk<float>(n2 ? p.x_mid : p.x_in, i); post.lnb_mean = x.blk<float>(n2 ? p.mean2 : p.mean1, i); post.lnb_rstd = x.blk<float>(n2 ? p.rstd2 : p.rstd1, i);
+        post.lnb_gamma = x.bprm(i, n2 ? B_N2W : B_N1W); post.lnb_beta = x.bprm(i, n2 ? B_N2B : B_N1B); post.lnb_dx_in = dx_in;
+        post.lnb_dgamma = BG(i, n2 ? B_N2W : B_N1W); post.lnb_dbeta = BG(i, n2 ? B_N2B : B_N1B);
+        post.lnb_nmask = nx.maskbits; post.colscale = nx.colscale; post.out_hi = nx.out_hi; post.out_lo = nx.out_lo;
+        post.o16_mul = nx.o16_mul; post.o16_amax = nx.o16_amax;
+        return post;
+    }
+    // NTPost mode 9: the fc2 dgrad of block i applies the GELU backward and fc1's STE mask from the forward's byte codes + mask bits: the fc1 output gradient
+    NTPost gelu_post(int i, void* out_hi, void* out_lo) const {
+        NTPost post{};
+        post.mode = 9; post.qp = x.act_qp(x.aidx(i, AB_FC1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax; post.colscale = x.dy_colscale(x.widx(i, WB_FC1));
+        post.out_hi = out_hi; post.out_lo = out_lo; post.code8 = x.blk<void>(x.p.G8, i); post.code_mask = x.blk<void>(x.p.Y1m, i);
+        return post;
+    }
+    int head(const float* dlogits);
+    int block_one_plane(int i, bool injected);
+    int block_pair(int i, bool injected);
+    int embed();
+    int flush();
+};
+
+int Bwd::head(const float* dlogits) {
     const Dims& d = x.d;
     const Plan& p = x.p;
+    const qatvit_cfg& c = x.c;
+    const int base = P_BLOCK0 + B_COUNT * d.depth, wh = d.n_w - 1, last = d.depth - 1;
+    launch_head_bwd(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), c.act_qmin, c.act_qmax, x.at<float>(p.hq), x.act_qp(x.a_norm()),
+                    x.at<void>(p.w_off[wh]), x.prm(base + 2), x.wfq[wh].scale, x.wfq[wh].zero_point, c.w_per_channel, c.w_qmin, c.w_qmax,
+                    G(base + 2), G(base + 3), x.at<float>(p.dh), d.B, d.D, d.C, x.st);
+    LnBwdNext nx{x.blk<void>(p.m2, last), x.dy_colscale(x.widx(last, WB_FC2)), plane(last, 0), x.at<void>(p.dYs_lo)};
+    if (dy) { nx.o16_mul = x.dy_mul(last, DS_FC2); nx.o16_amax = x.dy_slot(last, DS_FC2); }
+    if (launch_ln_bwd_fq(0, x.at<float>(p.dh), x.blk<float>(p.x_in, d.depth), x.at<float>(p.meanF), x.at<float>(p.rstdF), x.prm(base), x.prm(base + 1),
+                         x.act_qp(x.a_norm()), c.act_qmin, c.act_qmax, nullptr, dxA, G(base), G(base + 1), d.M, d.D, d.T, 1, x.st, &nx))
+        return 1;
+    calib(nx.out_hi, d.M * d.D, last, DS_FC2);
+    return 0;
+}
+
+// one block, one-plane form.  Same dataflow as the pair form below; every dY is one fp16 plane in the hi buffer of the pair.
+int Bwd::block_one_plane(int i, bool injected) {
+    const Dims& d = x.d;
+    const Plan& p = x.p;
+    const Forms& F = p.form;
     const qatvit_cfg& c = x.c;
     hipStream_t st = x.st;
     const int qa = c.act_qmin, qb = c.act_qmax;
     const int M = (int)d.M;
-    auto G = [&](int i) { return reinterpret_cast<float*>(grads[i]); };
-    auto BG = [&](int blk_i, int k) { return reinterpret_cast<float*>(grads[P_BLOCK0 + B_COUNT * blk_i + k]); };
-    // residual-stream gradient ping-pongs between dxA and dxB; stage s starts with it in buffer (s & 1 ? A : B)... keep it simple:
-    // dxA always holds the gradient w.r.t. the current block's OUTPUT at stage entry.
-    float* dxA = x.at<float>(p.dxA);
-    float* dxB = x.at<float>(p.dxB);
-    // QATVIT_LN_FUSE (default on): every LayerNorm backward also emits the masked (hi, lo) gradient of the branch output that precedes
-    // it - from the mask bits of the forward - instead of a k_mask_bwd pass re-reading dx and the fp32 pre-FQ tensor.  Stages must then
-    // run in order within one backward (they already had to: dxA carries over).
-    static const bool ln_fuse = !(getenv("QATVIT_LN_FUSE") && atoi(getenv("QATVIT_LN_FUSE")) == 0);
-    void* dYh_all = x.at<void>(p.dYs_hi);
-    void* const dYl_all = x.at<void>(p.dYs_lo);
-    const bool dy = (x.flags & QATVIT_BWD_DY16) != 0, cal = (x.flags & QATVIT_BWD_CALIBRATE) != 0;
-    // deferred weight gradients (k_tn_stream): every block's gradient planes stay in the workspace, the GEMMs are collected here and run at the end of this call
-    const bool stream = dy && p.dyp >= 0 && x.x_plane_from_q8();
-    auto plane = [&](int blk_i, int which) -> void* {   // 0 fc2-in, 1 proj-in, 2 fc1-out, 3 qkv-out
-        if (!stream) return x.at<void>(which <= 1 ? p.dYs_hi : which == 2 ? p.dY1_hi : p.dqkv_hi);
-        return x.at<char>(p.dyp) + (int64_t)blk_i * p.dyp_stride + (which == 0 ? 0 : which == 1 ? p.dyp_p : which == 2 ? p.dyp_h : p.dyp_q);
-    };
-    std::vector<TNStreamGemm> sg[3];
-    double sflops[3] = {0.0, 0.0, 0.0};
-    if (stream) dYh_all = plane(d.depth - 1, 0);
-    if (dy && cal) { set_error("student backward: QATVIT_BWD_DY16 and QATVIT_BWD_CALIBRATE exclude each other"); return 1; }
-    if ((dy || cal) && !dy16_supported(x)) { set_error("student backward: the one-plane form does not cover this configuration (qatvit_student_dy16_supported)"); return 1; }
-    uint32_t* const dystate = x.at<uint32_t>(p.dy16);
-    const int nslots = DS_COUNT * d.depth;
-    if ((dy || cal) && (stage_from == 0 || inject)) launch_dy16_begin(dystate, nslots, stage_from == 0 ? dlogits : nullptr, d.B * d.C, st);
-    // calibration: the maximum of a tensor the pair form just wrote (its hi plane) into the tensor's slot
-    auto calib = [&](const void* hi, int64_t n, int blk_i, int k) { if (cal && blk_i >= 0) launch_absmax_bf16(hi, n, x.dy_slot(blk_i, k), st); };
-    for (int s = stage_from; s <= stage_to; ++s) {
-        if (s == 0) {
-            const int base = P_BLOCK0 + B_COUNT * d.depth;
-            const int wh = d.n_w - 1;
-            launch_head_bwd(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), qa, qb, x.at<float>(p.hq), x.act_qp(x.a_norm()),
-                            x.at<void>(p.w_off[wh]), x.prm(base + 2), x.wfq[wh].scale, x.wfq[wh].zero_point, c.w_per_channel, c.w_qmin, c.w_qmax,
-                            G(base + 2), G(base + 3), x.at<float>(p.dh), d.B, d.D, d.C, st);
-            LnBwdNext nx{x.blk<void>(p.m2, d.depth - 1), x.dy_colscale(x.widx(d.depth - 1, WB_FC2)), dYh_all, dYl_all};
-            if (dy) { nx.o16_mul = x.dy_mul(d.depth - 1, DS_FC2); nx.o16_amax = x.dy_slot(d.depth - 1, DS_FC2); }
-            if (launch_ln_bwd_fq(0, x.at<float>(p.dh), x.blk<float>(p.x_in, d.depth), x.at<float>(p.meanF), x.at<float>(p.rstdF), x.prm(base),
-                                 x.prm(base + 1), x.act_qp(x.a_norm()), qa, qb, nullptr, dxA, G(base), G(base + 1), d.M, d.D, d.T, 1, st,
-                                 ln_fuse ? &nx : nullptr))
-                return 1;
-            calib(dYh_all, d.M * d.D, d.depth - 1, DS_FC2);
-        } else if (s <= d.depth && dy) {
-            // ---- one block, one-plane form.  Same dataflow as the pair form below; every dY is one fp16 plane in the hi buffer of the pair.
-            const int i = d.depth - s;
-            void* dY16 = plane(i, 0);      // the masked gradient entering fc2
-            void* dYp16 = plane(i, 1);     // ... entering proj (the same buffer as dY16 unless the weight gradients are deferred)
-            void* dY1_16 = plane(i, 2);
-            void* dqkv16 = plane(i, 3);
-            const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
-            float* const scal16 = x.blk<float>(p.scal16, i);
-            auto wscale1 = [&](int wi) { return c.w_per_channel ? nullptr : x.wfq[wi].scale; };
-            // wgrad of layer wi from the plane P16 (slot k): X as fp16 integers (X_lo == nullptr), an fp16 pair, or codes + a table of fp16 pairs
-            // (X8: the same grid integers as q - center, one byte each - the forward's int8 operand; taken instead of the fp16 plane where k_gemm_tn_q8 applies)
-            auto wgrad16 = [&](const void* P16, int k, int wi, const void* X_hi, const void* X_lo, const void* Xc, const uint32_t* lut, const float* s_x, float* dW,
-                               float* db, const void* X8 = nullptr) -> int {
-                int N, K; wshape(d, wi, &N, &K);
-                const qatvit_fq& f = x.wfq[wi];
-                const float* rdiv = c.w_per_channel ? f.scale : nullptr;
-                if (stream && !X_lo) {   // collected: one persistent launch per X form at the end of the call
-                    const int m = X8 ? 0 : Xc ? 1 : 2;
-                    sg[m].push_back(TNStreamGemm{P16, X8 ? X8 : Xc ? Xc : X_hi, lut, s_x, x.dy_inv(i, k), dW, x.prm(wparam(d, wi)), f.scale, f.zero_point, db, rdiv, N, K, N, K, K});
-                    sflops[m] += 2.0 * M * N * K;
-                    return 0;
-                }
-                ProfScope ps(x.prof, (wi == w_proj || Xc) ? 6 : 3, 2.0 * M * N * K, st);
-                if (X8 && x.x_plane_from_q8())
-                    return launch_gemm_tn_q8_dy16(P16, X8, s_x, x.center(), dW, M, N, K, N, K, K, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point,
-                                                  c.w_per_channel, c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
-                if (Xc)
-                    return launch_gemm_tn_codes_dy16(P16, Xc, lut, dW, M, N, K, N, K, K, s_x, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel,
-                                                     c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
-                return launch_gemm_tn_dy16(P16, X_hi, X_lo, dW, M, N, K, N, K, K, s_x, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel,
-                                           c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
-            };
-            auto dgrad16 = [&](const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
-                int N, K; wshape(d, wi, &N, &K);
-                ProfScope ps(x.prof, !post ? 1 : post->mode == 8 ? 4 : 5, 2.0 * M * N * K, st);
-                return launch_gemm_nt_dy16(P16, x.wT16(wi), dX, M, K, N, N, N, K, wscale1(wi), x.dy_inv(i, k), st, post);
-            };
-            // ---- MLP branch
-            if (inject && s == stage_from)
-                launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, dY16, nullptr, d.M * d.D, st,
-                                x.dy_mul(i, DS_FC2), x.dy_slot(i, DS_FC2));
-            if (wgrad16(dY16, DS_FC2, w_fc2, nullptr, nullptr, x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glut, i), scal16 + 1, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
-            {   // fc2 dgrad + GELU backward + fc1's STE mask -> the fc1 output gradient, one plane
-                NTPost post{};
-                post.mode = 9; post.qp = x.act_qp(x.aidx(i, AB_FC1)); post.qmin = qa; post.qmax = qb; post.colscale = x.dy_colscale(w_fc1);
-                post.out_hi = dY1_16; post.code8 = x.blk<void>(p.G8, i); post.code_mask = x.blk<void>(p.Y1m, i);
-                post.o16_mul = x.dy_mul(i, DS_FC1); post.o16_amax = x.dy_slot(i, DS_FC1);
-                bool strip = false;
-                if (x.wT16f_ok(w_fc2) && f16_strip_enabled()) {   // the A-stationary strip form (f16strip.hip): the gradient plane fetched once for all four column tiles
-                    ProfScope ps(x.prof, 5, 2.0 * M * d.D * d.Hd, st);
-                    strip = launch_f16_strip_gelu_bwd(dY16, x.wT16f(w_fc2), nullptr, M, d.Hd, d.D, d.D, d.Hd, wscale1(w_fc2), x.dy_inv(i, DS_FC2), st, &post);
-                }
-                if (!strip && dgrad16(dY16, DS_FC2, w_fc2, nullptr, &post)) return 1;
-            }
-            if (wgrad16(dY1_16, DS_FC1, w_fc1, x.blk<void>(p.h2q, i), nullptr, nullptr, nullptr, x.act_qp(x.aidx(i, AB_N2)), BG(i, B_FC1W), BG(i, B_FC1B),
-                        x.blk<void>(p.h2q8, i)))
-                return 1;
-            const bool lnb = lnb_fuse() && d.D == 384;
-            LnBwdNext nx_proj{x.blk<void>(p.mproj, i), x.dy_colscale(w_proj), dYp16, nullptr, x.dy_mul(i, DS_PROJ), x.dy_slot(i, DS_PROJ)};
-            if (lnb) {
-                NTPost post{};
-                post.mode = 8; post.qp = x.act_qp(x.aidx(i, AB_N2)); post.qmin = qa; post.qmax = qb;
-                post.lnb_x = x.blk<float>(p.x_mid, i); post.lnb_mean = x.blk<float>(p.mean2, i); post.lnb_rstd = x.blk<float>(p.rstd2, i);
-                post.lnb_gamma = x.bprm(i, B_N2W); post.lnb_beta = x.bprm(i, B_N2B); post.lnb_dx_in = dxA; post.lnb_dgamma = BG(i, B_N2W); post.lnb_dbeta = BG(i, B_N2B);
-                post.lnb_nmask = nx_proj.maskbits; post.colscale = nx_proj.colscale; post.out_hi = dYp16;
-                post.o16_mul = nx_proj.o16_mul; post.o16_amax = nx_proj.o16_amax;
-                if (dgrad16(dY1_16, DS_FC1, w_fc1, dxB, &post)) return 1;
-            } else {
-                if (dgrad16(dY1_16, DS_FC1, w_fc1, x.at<float>(p.dH), nullptr)) return 1;
-                if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_mid, i), x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W),
-                                     x.bprm(i, B_N2B), x.act_qp(x.aidx(i, AB_N2)), qa, qb, dxA, dxB, BG(i, B_N2W), BG(i, B_N2B), d.M, d.D, d.T, 0, st, &nx_proj))
-                    return 1;
-            }
-            // ---- attention branch (dxB = gradient w.r.t. x_mid)
-            // (the float X operands - attention output, gelu output - enter the one-plane weight gradients rounded to fp16 like dY itself: one pass;
-            //  QATVIT_DY16_XPAIR=1 keeps them as fp16 (hi, lo) pairs, two passes)
-            static const bool xpair = getenv("QATVIT_DY16_XPAIR") && atoi(getenv("QATVIT_DY16_XPAIR")) != 0;
-            if (wgrad16(dYp16, DS_PROJ, w_proj, x.blk<void>(p.O16_hi, i), xpair ? x.blk<void>(p.O16_lo, i) : nullptr, nullptr, nullptr, scal16, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
-            if (dgrad16(dYp16, DS_PROJ, w_proj, x.at<float>(p.dO), nullptr)) return 1;
-            if (launch_attn_bwd(nullptr, x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i),
-                                x.at<float>(p.delta), x.at<float>(p.dO), dqkv16, nullptr, x.dy_colscale(w_qkv), st, x.blk<void>(p.qkv8, i), x.blk<void>(p.qkvm, i),
-                                x.dy_mul(i, DS_QKV), x.dy_slot(i, DS_QKV)))
-                return 1;
-            if (wgrad16(dqkv16, DS_QKV, w_qkv, x.blk<void>(p.h1q, i), nullptr, nullptr, nullptr, x.act_qp(x.aidx(i, AB_N1)), BG(i, B_QKVW), BG(i, B_QKVB),
-                        x.blk<void>(p.h1q8, i)))
-                return 1;
-            void* const dYnext = i > 0 ? plane(i - 1, 0) : dY16;   // the next block's fc2-in plane (its own buffer when the weight gradients are deferred)
-            LnBwdNext nx_fc2{i > 0 ? x.blk<void>(p.m2, i - 1) : nullptr, i > 0 ? x.dy_colscale(x.widx(i - 1, WB_FC2)) : nullptr, dYnext, nullptr,
-                             i > 0 ? x.dy_mul(i - 1, DS_FC2) : nullptr, i > 0 ? x.dy_slot(i - 1, DS_FC2) : nullptr};
-            if (lnb) {
-                NTPost post{};
-                post.mode = 8; post.qp = x.act_qp(x.aidx(i, AB_N1)); post.qmin = qa; post.qmax = qb;
-                post.lnb_x = x.blk<float>(p.x_in, i); post.lnb_mean = x.blk<float>(p.mean1, i); post.lnb_rstd = x.blk<float>(p.rstd1, i);
-                post.lnb_gamma = x.bprm(i, B_N1W); post.lnb_beta = x.bprm(i, B_N1B); post.lnb_dx_in = dxB; post.lnb_dgamma = BG(i, B_N1W); post.lnb_dbeta = BG(i, B_N1B);
-                if (i > 0) { post.lnb_nmask = nx_fc2.maskbits; post.colscale = nx_fc2.colscale; post.out_hi = dYnext; }
-                // (block 0 emits no next-branch gradient; the epilogue still wants a scale / maximum target: its own slot, which nothing reads afterwards)
-                post.o16_mul = i > 0 ? nx_fc2.o16_mul : x.dy_mul(0, DS_QKV); post.o16_amax = i > 0 ? nx_fc2.o16_amax : x.dy_slot(0, DS_QKV);
-                if (dgrad16(dqkv16, DS_QKV, w_qkv, dxA, &post)) return 1;
-            } else {
-                if (dgrad16(dqkv16, DS_QKV, w_qkv, x.at<float>(p.dH), nullptr)) return 1;
-                if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_in, i), x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W),
-                                     x.bprm(i, B_N1B), x.act_qp(x.aidx(i, AB_N1)), qa, qb, dxB, dxA, BG(i, B_N1W), BG(i, B_N1B), d.M, d.D, d.T, 0, st,
-                                     i > 0 ? &nx_fc2 : nullptr))
-                    return 1;
-            }
-        } else if (s <= d.depth) {
-            const int i = d.depth - s;
-            void* dYh = x.at<void>(p.dYs_hi);
-            void* dYl = x.at<void>(p.dYs_lo);
-            const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
-            // ---- MLP branch
-            if (!ln_fuse || (inject && s == stage_from)) {
-                launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, dYh, dYl, d.M * d.D, st);
-                calib(dYh, d.M * d.D, i, DS_FC2);
-            }
-            if (fc2w_code_form(x, i)) {
-                if (x.linear_wgrad_codes(dYh, dYl, M, w_fc2, x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glutq, i), BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
-            } else if (x.linear_wgrad(dYh, dYl, M, w_fc2, x.blk<void>(p.G_hi, i), x.blk<void>(p.G_lo, i), nullptr, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
-            {   // fc2 dgrad with the GELU backward + fc1's STE mask fused into its epilogue: dY1 = (dYs . W_fc2) * gelu'(fq(Y1)) * mask(Y1)
-                NTPost post{x.blk<float>(p.Y1, i), x.act_qp(x.aidx(i, AB_FC1)), qa, qb, x.dy_colscale(w_fc1), x.at<void>(p.dY1_hi),
-                            x.at<void>(p.dY1_lo)};
-                post.Y = nullptr; post.mode = 5; post.code = x.blk<void>(p.Y1, i);   // the Y1 slot holds the uint16 codes
-                if (fc1_code_bits(x, i)) { post.mode = 9; post.code = nullptr; post.code8 = x.blk<void>(p.G8, i); post.code_mask = x.blk<void>(p.Y1m, i); }
-                if (x.linear_dgrad(dYh, dYl, M, w_fc2, nullptr, &post)) return 1;
-            }
-            calib(x.at<void>(p.dY1_hi), d.M * d.Hd, i, DS_FC1);
-            if (x.linear_wgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, x.blk<void>(p.h2q, i), nullptr, x.act_qp(x.aidx(i, AB_N2)),
-                               BG(i, B_FC1W), BG(i, B_FC1B)))
-                return 1;
-            const LnBwdNext nx_proj{x.blk<void>(p.mproj, i), x.dy_colscale(w_proj), dYh, dYl};
-            const bool lnb = ln_fuse && lnb_fuse() && d.D == 384;   // the dgrad tile holds whole LayerNorm rows: its epilogue IS the LayerNorm backward
-            if (lnb) {
-                NTPost post{};
-                post.mode = 8; post.qp = x.act_qp(x.aidx(i, AB_N2)); post.qmin = qa; post.qmax = qb;
-                post.lnb_x = x.blk<float>(p.x_mid, i); post.lnb_mean = x.blk<float>(p.mean2, i); post.lnb_rstd = x.blk<float>(p.rstd2, i);
-                post.lnb_gamma = x.bprm(i, B_N2W); post.lnb_beta = x.bprm(i, B_N2B); post.lnb_dx_in = dxA; post.lnb_dgamma = BG(i, B_N2W); post.lnb_dbeta = BG(i, B_N2B);
-                post.lnb_nmask = nx_proj.maskbits; post.colscale = nx_proj.colscale; post.out_hi = dYh; post.out_lo = dYl;
-                if (x.linear_dgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, dxB, &post)) return 1;
-            } else {
-                if (x.linear_dgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, x.at<float>(p.dH))) return 1;
-                if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_mid, i), x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i),
-                                     x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.act_qp(x.aidx(i, AB_N2)), qa, qb, dxA, dxB, BG(i, B_N2W), BG(i, B_N2B), d.M,
-                                     d.D, d.T, 0, st, ln_fuse ? &nx_proj : nullptr))
-                    return 1;
-            }
-            // ---- attention branch (dxB = gradient w.r.t. x_mid)
-            if (!ln_fuse) launch_mask_bwd(0, dxB, x.blk<float>(p.Yproj, i), x.act_qp(x.aidx(i, AB_PROJ)), qa, qb, x.dy_colscale(w_proj), d.D, dYh, dYl, d.M * d.D, st);
-            calib(dYh, d.M * d.D, i, DS_PROJ);
-            if (x.linear_wgrad(dYh, dYl, M, w_proj, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), nullptr, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
-            if (x.linear_dgrad(dYh, dYl, M, w_proj, x.at<float>(p.dO))) return 1;
-            if (launch_attn_bwd(x.blk<float>(p.qkv, i), x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i),
-                                x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i), x.at<float>(p.delta), x.at<float>(p.dO), x.at<void>(p.dqkv_hi),
-                                x.at<void>(p.dqkv_lo), x.dy_colscale(w_qkv), st, attn_codes(c) ? x.blk<void>(p.qkv8, i) : nullptr,
-                                attn_codes(c) ? x.blk<void>(p.qkvm, i) : nullptr))
-                return 1;
-            calib(x.at<void>(p.dqkv_hi), d.M * 3 * d.D, i, DS_QKV);
-            if (x.linear_wgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, x.blk<void>(p.h1q, i), nullptr, x.act_qp(x.aidx(i, AB_N1)),
-                               BG(i, B_QKVW), BG(i, B_QKVB)))
-                return 1;
-            const LnBwdNext nx_fc2{i > 0 ? x.blk<void>(p.m2, i - 1) : nullptr, i > 0 ? x.dy_colscale(x.widx(i - 1, WB_FC2)) : nullptr, dYh, dYl};
-            if (lnb) {
-                NTPost post{};
-                post.mode = 8; post.qp = x.act_qp(x.aidx(i, AB_N1)); post.qmin = qa; post.qmax = qb;
-                post.lnb_x = x.blk<float>(p.x_in, i); post.lnb_mean = x.blk<float>(p.mean1, i); post.lnb_rstd = x.blk<float>(p.rstd1, i);
-                post.lnb_gamma = x.bprm(i, B_N1W); post.lnb_beta = x.bprm(i, B_N1B); post.lnb_dx_in = dxB; post.lnb_dgamma = BG(i, B_N1W); post.lnb_dbeta = BG(i, B_N1B);
-                if (i > 0) { post.lnb_nmask = nx_fc2.maskbits; post.colscale = nx_fc2.colscale; post.out_hi = dYh; post.out_lo = dYl; }
-                if (x.linear_dgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, dxA, &post)) return 1;
-            } else {
-                if (x.linear_dgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, x.at<float>(p.dH))) return 1;
-                if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_in, i), x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i),
-                                     x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.act_qp(x.aidx(i, AB_N1)), qa, qb, dxB, dxA, BG(i, B_N1W), BG(i, B_N1B), d.M,
-                                     d.D, d.T, 0, st,
-                                     (ln_fuse && i > 0) ? &nx_fc2 : nullptr))
-                    return 1;
-            }
-            if (i > 0) calib(dYh, d.M * d.D, i - 1, DS_FC2);
-        } else {
-            launch_embed_bwd(dxA, x.at<float>(p.Y0), x.act_qp(A_PE), qa, qb, G(P_POS), G(P_CLS), x.at<void>(p.dY0_hi), x.at<void>(p.dY0_lo), d.B,
-                             d.T, d.D, st);
-            // (no dgrad into the image, so dY0 is not pre-scaled by the per-channel weight scale)
-            if (x.linear_wgrad(x.at<void>(p.dY0_hi), x.at<void>(p.dY0_lo), d.B * d.np, 0, x.at<void>(p.imgq), nullptr, x.act_qp(A_IN), G(P_PE_W),
-                               G(P_PE_B), false))
-                return 1;
+    void* dY16 = plane(i, 0);      // the masked gradient entering fc2
+    void* dYp16 = plane(i, 1);     // ... entering proj (the same buffer as dY16 unless the weight gradients are deferred)
+    void* dY1_16 = plane(i, 2);
+    void* dqkv16 = plane(i, 3);
+    const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
+    float* const scal16 = x.blk<float>(p.scal16, i);
+    auto wscale1 = [&](int wi) { return c.w_per_channel ? nullptr : x.wfq[wi].scale; };
+    // wgrad of layer wi from the plane P16 (slot k): X as fp16 (grid integers; proj: the attention output rounded to fp16 like dY itself: one pass), or codes + a table
+    // of fp16 pairs (X8: the same grid integers as q - center, one byte each - the forward's int8 operand; taken instead of the fp16 plane where k_gemm_tn_q8 applies)
+    auto wgrad16 = [&](const void* P16, int k, int wi, const void* X, const void* Xc, const uint32_t* lut, const float* s_x, float* dW, float* db,
+                       const void* X8 = nullptr) -> int {
+        int N, K; wshape(d, wi, &N, &K);
+        const qatvit_fq& f = x.wfq[wi];
+        const float* rdiv = c.w_per_channel ? f.scale : nullptr;
+        if (stream) {   // collected: one persistent launch per X form at the end of the call
+            const int m = X8 ? 0 : Xc ? 1 : 2;
+            sg[m].push_back(TNStreamGemm{P16, X8 ? X8 : Xc ? Xc : X, lut, s_x, x.dy_inv(i, k), dW, x.prm(wparam(d, wi)), f.scale, f.zero_point, db, rdiv, N, K, N, K, K});
+            sflops[m] += 2.0 * M * N * K;
+            return 0;
         }
+        ProfScope ps(x.prof, (wi == w_proj || Xc) ? 6 : 3, 2.0 * M * N * K, st);
+        if (X8 && F.x_plane_from_q8)
+            return launch_gemm_tn_q8_dy16(P16, X8, s_x, x.center(), dW, M, N, K, N, K, K, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point,
+                                          c.w_per_channel, c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
+        if (Xc)
+            return launch_gemm_tn_codes_dy16(P16, Xc, lut, dW, M, N, K, N, K, K, s_x, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel,
+                                             c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
+        return launch_gemm_tn_dy16(P16, X, nullptr, dW, M, N, K, N, K, K, s_x, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel,
+                                   c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
+    };
+    auto dgrad16 = [&](const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
+        int N, K; wshape(d, wi, &N, &K);
+        ProfScope ps(x.prof, !post ? 1 : post->mode == 8 ? 4 : 5, 2.0 * M * N * K, st);
+        return launch_gemm_nt_dy16(P16, x.wT16(wi), dX, M, K, N, N, N, K, wscale1(wi), x.dy_inv(i, k), st, post);
+    };
+    // ---- MLP branch
+    if (injected)
+        launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, dY16, nullptr, d.M * d.D, st,
+                        x.dy_mul(i, DS_FC2), x.dy_slot(i, DS_FC2));
+    if (wgrad16(dY16, DS_FC2, w_fc2, nullptr, x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glut, i), scal16 + 1, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
+    {   // fc2 dgrad + GELU backward + fc1's STE mask -> the fc1 output gradient, one plane
+        NTPost post = gelu_post(i, dY1_16, nullptr);
+        post.o16_mul = x.dy_mul(i, DS_FC1); post.o16_amax = x.dy_slot(i, DS_FC1);
+        bool strip = false;
+        if (x.wT16f_ok(w_fc2) && knobs().f16_strip) {   // the A-stationary strip form (f16strip.hip): the gradient plane fetched once for all four column tiles
+            ProfScope ps(x.prof, 5, 2.0 * M * d.D * d.Hd, st);
+            strip = launch_f16_strip_gelu_bwd(dY16, x.wT16f(w_fc2), nullptr, M, d.Hd, d.D, d.D, d.Hd, wscale1(w_fc2), x.dy_inv(i, DS_FC2), st, &post);
+        }
+        if (!strip && dgrad16(dY16, DS_FC2, w_fc2, nullptr, &post)) return 1;
     }
-    // (the scale bookkeeping and the overflow flag first: they depend on the producers of the planes only, and the host's mirror of the flag - qatvit_student_dy16_set_mirror -
-    //  is written here, 2 - 3 ms before the deferred weight gradients below are done)
-    if (dy || cal) launch_dy16_end(dystate, nslots, dy ? 1 : 0, st);
-    for (int m = 0; m < 3; ++m) {   // the collected weight gradients: one persistent launch (+ its fix-up) per X form and <= 24 GEMMs
+    if (wgrad16(dY1_16, DS_FC1, w_fc1, x.blk<void>(p.h2q, i), nullptr, nullptr, x.act_qp(x.aidx(i, AB_N2)), BG(i, B_FC1W), BG(i, B_FC1B), x.blk<void>(p.h2q8, i)))
+        return 1;
+    const LnBwdNext nx_proj{x.blk<void>(p.mproj, i), x.dy_colscale(w_proj), dYp16, nullptr, x.dy_mul(i, DS_PROJ), x.dy_slot(i, DS_PROJ)};
+    if (F.lnb) {
+        const NTPost post = lnb_post(i, true, dxA, nx_proj);
+        if (dgrad16(dY1_16, DS_FC1, w_fc1, dxB, &post)) return 1;
+    } else {
+        if (dgrad16(dY1_16, DS_FC1, w_fc1, x.at<float>(p.dH), nullptr)) return 1;
+        if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_mid, i), x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W),
+                             x.bprm(i, B_N2B), x.act_qp(x.aidx(i, AB_N2)), qa, qb, dxA, dxB, BG(i, B_N2W), BG(i, B_N2B), d.M, d.D, d.T, 0, st, &nx_proj))
+            return 1;
+    }
+    // ---- attention branch (dxB = gradient w.r.t. x_mid)
+    if (wgrad16(dYp16, DS_PROJ, w_proj, x.blk<void>(p.O16_hi, i), nullptr, nullptr, scal16, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
+    if (dgrad16(dYp16, DS_PROJ, w_proj, x.at<float>(p.dO), nullptr)) return 1;
+    if (launch_attn_bwd(nullptr, x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i),
+                        x.at<float>(p.delta), x.at<float>(p.dO), dqkv16, nullptr, x.dy_colscale(w_qkv), st, x.blk<void>(p.qkv8, i), x.blk<void>(p.qkvm, i),
+                        x.dy_mul(i, DS_QKV), x.dy_slot(i, DS_QKV)))
+        return 1;
+    if (wgrad16(dqkv16, DS_QKV, w_qkv, x.blk<void>(p.h1q, i), nullptr, nullptr, x.act_qp(x.aidx(i, AB_N1)), BG(i, B_QKVW), BG(i, B_QKVB), x.blk<void>(p.h1q8, i)))
+        return 1;
+    // the next block's fc2-in plane (its own buffer when the weight gradients are deferred).  Block 0 emits no next-branch gradient; the fused epilogue still
+    // wants a scale / maximum target: its own qkv slot, which nothing reads afterwards
+    const LnBwdNext nx_fc2 = i > 0 ? LnBwdNext{x.blk<void>(p.m2, i - 1), x.dy_colscale(x.widx(i - 1, WB_FC2)), plane(i - 1, 0), nullptr, x.dy_mul(i - 1, DS_FC2),
+                                               x.dy_slot(i - 1, DS_FC2)}
+                                   : LnBwdNext{nullptr, nullptr, nullptr, nullptr, x.dy_mul(0, DS_QKV), x.dy_slot(0, DS_QKV)};
+    if (F.lnb) {
+        const NTPost post = lnb_post(i, false, dxB, nx_fc2);
+        return dgrad16(dqkv16, DS_QKV, w_qkv, dxA, &post);
+    }
+    if (dgrad16(dqkv16, DS_QKV, w_qkv, x.at<float>(p.dH), nullptr)) return 1;
+    return launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_in, i), x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B),
+                            x.act_qp(x.aidx(i, AB_N1)), qa, qb, dxB, dxA, BG(i, B_N1W), BG(i, B_N1B), d.M, d.D, d.T, 0, st, i > 0 ? &nx_fc2 : nullptr);
+}
+
+// one block, bf16 (hi, lo) pair form (also the calibrating step of the one-plane form)
+int Bwd::block_pair(int i, bool injected) {
+    const Dims& d = x.d;
+    const Plan& p = x.p;
+    const Forms& F = p.form;
+    const qatvit_cfg& c = x.c;
+    hipStream_t st = x.st;
+    const int qa = c.act_qmin, qb = c.act_qmax;
+    const int M = (int)d.M;
+    void* dYh = x.at<void>(p.dYs_hi);
+    void* dYl = x.at<void>(p.dYs_lo);
+    const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
+    // ---- MLP branch
+    if (injected) {
+        launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, dYh, dYl, d.M * d.D, st);
+        calib(dYh, d.M * d.D, i, DS_FC2);
+    }
+    if (F.fc2w_codes) {
+        if (x.linear_wgrad_codes(dYh, dYl, M, w_fc2, x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glutq, i), BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
+    } else if (x.linear_wgrad(dYh, dYl, M, w_fc2, x.blk<void>(p.G_hi, i), x.blk<void>(p.G_lo, i), nullptr, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
+    {   // fc2 dgrad with the GELU backward + fc1's STE mask fused into its epilogue: dY1 = (dYs . W_fc2) * gelu'(fq(Y1)) * mask(Y1)
+        NTPost post = gelu_post(i, x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo));
+        if (!F.fc1_code_bits) { post.mode = 5; post.code = x.blk<void>(p.Y1, i); post.code8 = post.code_mask = nullptr; }   // the Y1 slot holds the uint16 codes
+        if (x.linear_dgrad(dYh, dYl, M, w_fc2, nullptr, &post)) return 1;
+    }
+    calib(x.at<void>(p.dY1_hi), d.M * d.Hd, i, DS_FC1);
+    if (x.linear_wgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, x.blk<void>(p.h2q, i), nullptr, x.act_qp(x.aidx(i, AB_N2)), BG(i, B_FC1W), BG(i, B_FC1B)))
+        return 1;
+    const LnBwdNext nx_proj{x.blk<void>(p.mproj, i), x.dy_colscale(w_proj), dYh, dYl};
+    if (F.lnb) {
+        const NTPost post = lnb_post(i, true, dxA, nx_proj);
+        if (x.linear_dgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, dxB, &post)) return 1;
+    } else {
+        if (x.linear_dgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, x.at<float>(p.dH))) return 1;
+        if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_mid, i), x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B),
+                             x.act_qp(x.aidx(i, AB_N2)), qa, qb, dxA, dxB, BG(i, B_N2W), BG(i, B_N2B), d.M, d.D, d.T, 0, st, &nx_proj))
+            return 1;
+    }
+    // ---- attention branch (dxB = gradient w.r.t. x_mid)
+    calib(dYh, d.M * d.D, i, DS_PROJ);
+    if (x.linear_wgrad(dYh, dYl, M, w_proj, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), nullptr, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
+    if (x.linear_dgrad(dYh, dYl, M, w_proj, x.at<float>(p.dO))) return 1;
+    if (launch_attn_bwd(x.blk<float>(p.qkv, i), x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i),
+                        x.blk<float>(p.lse, i), x.at<float>(p.delta), x.at<float>(p.dO), x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), x.dy_colscale(w_qkv), st,
+                        F.attn_codes ? x.blk<void>(p.qkv8, i) : nullptr, F.attn_codes ? x.blk<void>(p.qkvm, i) : nullptr))
+        return 1;
+    calib(x.at<void>(p.dqkv_hi), d.M * 3 * d.D, i, DS_QKV);
+    if (x.linear_wgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, x.blk<void>(p.h1q, i), nullptr, x.act_qp(x.aidx(i, AB_N1)), BG(i, B_QKVW), BG(i, B_QKVB)))
+        return 1;
+    const LnBwdNext nx_fc2 = i > 0 ? LnBwdNext{x.blk<void>(p.m2, i - 1), x.dy_colscale(x.widx(i - 1, WB_FC2)), dYh, dYl} : LnBwdNext{nullptr, nullptr, nullptr, nullptr};
+    if (F.lnb) {
+        const NTPost post = lnb_post(i, false, dxB, nx_fc2);
+        if (x.linear_dgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, dxA, &post)) return 1;
+    } else {
+        if (x.linear_dgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, x.at<float>(p.dH))) return 1;
+        if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_in, i), x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B),
+                             x.act_qp(x.aidx(i, AB_N1)), qa, qb, dxB, dxA, BG(i, B_N1W), BG(i, B_N1B), d.M, d.D, d.T, 0, st, i > 0 ? &nx_fc2 : nullptr))
+            return 1;
+    }
+    if (i > 0) calib(dYh, d.M * d.D, i - 1, DS_FC2);
+    return 0;
+}
+
+int Bwd::embed() {
+    const Dims& d = x.d;
+    const Plan& p = x.p;
+    launch_embed_bwd(dxA, x.at<float>(p.Y0), x.act_qp(A_PE), x.c.act_qmin, x.c.act_qmax, G(P_POS), G(P_CLS), x.at<void>(p.dY0_hi), x.at<void>(p.dY0_lo), d.B,
+                     d.T, d.D, x.st);
+    // (no dgrad into the image, so dY0 is not pre-scaled by the per-channel weight scale)
+    return x.linear_wgrad(x.at<void>(p.dY0_hi), x.at<void>(p.dY0_lo), d.B * d.np, 0, x.at<void>(p.imgq), nullptr, x.act_qp(A_IN), G(P_PE_W), G(P_PE_B), false);
+}
+
+// the collected weight gradients: one persistent launch (+ its fix-up) per X form and <= 24 GEMMs
+int Bwd::flush() {
+    const qatvit_cfg& c = x.c;
+    for (int m = 0; m < 3; ++m) {
         for (size_t o = 0; o < sg[m].size(); o += 24) {
             const int n = (int)std::min<size_t>(24, sg[m].size() - o);
-            ProfScope ps(x.prof, m == 0 ? 3 : 6, sflops[m] * n / (double)sg[m].size(), st);
-            if (launch_tn_stream(m, sg[m].data() + o, n, M, x.center(), c.w_per_channel, c.w_qmin, c.w_qmax, x.at<float>(p.tn_stream), tn_stream_scratch_bytes(), st)) return 1;
+            ProfScope ps(x.prof, m == 0 ? 3 : 6, sflops[m] * n / (double)sg[m].size(), x.st);
+            if (launch_tn_stream(m, sg[m].data() + o, n, (int)x.d.M, x.center(), c.w_per_channel, c.w_qmin, c.w_qmax, x.at<float>(x.p.tn_stream),
+                                 tn_stream_scratch_bytes(), x.st))
+                return 1;
         }
     }
     return 0;
+}
+
+static int bwd(const Ctx& x, const float* dlogits, void* const* grads, int stage_from, int stage_to, bool inject) {
+    const Dims& d = x.d;
+    const Forms& F = x.p.form;
+    const bool dy = (x.flags & QATVIT_BWD_DY16) != 0, cal = (x.flags & QATVIT_BWD_CALIBRATE) != 0;
+    if (dy && cal) { set_error("student backward: QATVIT_BWD_DY16 and QATVIT_BWD_CALIBRATE exclude each other"); return 1; }
+    if ((dy || cal) && !F.dy16) { set_error("student backward: the one-plane form does not cover this configuration (qatvit_student_dy16_supported)"); return 1; }
+    Bwd b{x, grads, dy, cal, dy && F.tn_stream && F.x_plane_from_q8, x.at<float>(x.p.dxA), x.at<float>(x.p.dxB)};
+    uint32_t* const dystate = x.at<uint32_t>(x.p.dy16);
+    const int nslots = DS_COUNT * d.depth;
+    if ((dy || cal) && (stage_from == 0 || inject)) launch_dy16_begin(dystate, nslots, stage_from == 0 ? dlogits : nullptr, d.B * d.C, x.st);
+    for (int s = stage_from; s <= stage_to; ++s) {
+        const bool injected = inject && s == stage_from;
+        if (s == 0 ? b.head(dlogits) : s > d.depth ? b.embed() : dy ? b.block_one_plane(d.depth - s, injected) : b.block_pair(d.depth - s, injected)) return 1;
+    }
+    // (the scale bookkeeping and the overflow flag first: they depend on the producers of the planes only, and the host's mirror of the flag - qatvit_student_dy16_set_mirror -
+    //  is written here, 2 - 3 ms before the deferred weight gradients are done)
+    if (dy || cal) launch_dy16_end(dystate, nslots, dy ? 1 : 0, x.st);
+    return b.flush();
 }
 
 }  // namespace qv
@@ -1046,7 +1006,7 @@ static int run_forward(const qatvit_cfg* cfg, void* const* params, const qatvit_
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
     if (make_plan(*cfg, &x.p)) return 1;
     x.flags = flags & QATVIT_FWD_X16;
-    QV_CHECK_ARG(!x.flags || dy16_supported(x), "%s: QATVIT_FWD_X16 needs a configuration the one-plane backward covers (qatvit_student_dy16_supported)", who);
+    QV_CHECK_ARG(!x.flags || x.p.form.dy16, "%s: QATVIT_FWD_X16 needs a configuration the one-plane backward covers (qatvit_student_dy16_supported)", who);
     if (fwd(x, images, logits, stage_from, stage_to, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
     if (x.commit_late()) return 1;
     QV_CHECK_LAUNCH(who);
@@ -1074,7 +1034,7 @@ int qatvit_student_forward_part(const qatvit_cfg* cfg, void* const* params, cons
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
     if (make_plan(*cfg, &x.p)) return 1;
     x.flags = flags & QATVIT_FWD_X16;
-    QV_CHECK_ARG(!x.flags || dy16_supported(x), "qatvit_student_forward_part: QATVIT_FWD_X16 needs a configuration the one-plane backward covers");
+    QV_CHECK_ARG(!x.flags || x.p.form.dy16, "qatvit_student_forward_part: QATVIT_FWD_X16 needs a configuration the one-plane backward covers");
     if (fwd_part(x, block, part, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
     if (x.commit_late()) return 1;
     QV_CHECK_LAUNCH("qatvit_student_forward_part");
@@ -1110,9 +1070,9 @@ int qatvit_student_backward_stages(const qatvit_cfg* cfg, void* const* params, c
 
 int32_t qatvit_student_dy16_supported(const qatvit_cfg* cfg) {
     if (!cfg || check_cfg(*cfg)) return 0;
-    Ctx x{*cfg, dims_of(*cfg), Plan(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (make_plan(*cfg, &x.p)) return 0;
-    return dy16_supported(x) ? 1 : 0;
+    Plan p;
+    if (make_plan(*cfg, &p)) return 0;
+    return p.form.dy16 ? 1 : 0;
 }
 
 int qatvit_student_dy16_set_mirror(const qatvit_cfg* cfg, void* workspace, void* host_pinned, void* stream) {
@@ -1131,7 +1091,7 @@ int qatvit_student_dy16_to_pair(const qatvit_cfg* cfg, void* workspace, void* st
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr};
     if (make_plan(*cfg, &x.p)) return 1;
     for (int i = 0; i < x.d.depth; ++i) {
-        if (x.x_plane_from_q8()) {   // the X16 forward wrote the byte planes only: q - zp = q8 + center - zp as bf16 integers
+        if (x.p.form.x_plane_from_q8) {   // the X16 forward wrote the byte planes only: q - zp = q8 + center - zp as bf16 integers
             if (launch_q8_to_bf16int(x.blk<void>(x.p.h1q8, i), x.act_qp(x.aidx(i, AB_N1)), x.center(), x.blk<void>(x.p.h1q, i), x.d.M * x.d.D, x.st)) return 1;
             if (launch_q8_to_bf16int(x.blk<void>(x.p.h2q8, i), x.act_qp(x.aidx(i, AB_N2)), x.center(), x.blk<void>(x.p.h2q, i), x.d.M * x.d.D, x.st)) return 1;
             continue;

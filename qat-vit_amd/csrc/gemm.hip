@@ -2097,10 +2097,6 @@ int launch_gemm_tn_dy16(const void* P16, const void* Q_hi, const void* Q_lo, flo
 }
 
 // The byte-Q forms of the one-plane weight gradient (k_gemm_tn_q8).  QATVIT_TN_Q8=0: the fp16-plane / expand-through-LDS kernels instead.
-bool tn_q8_enabled() {
-    static const bool on = !(getenv("QATVIT_TN_Q8") && atoi(getenv("QATVIT_TN_Q8")) == 0);
-    return on;
-}
 template <int MODE>
 static int gemm_tn_q8_impl(const void* P16, const void* Q8, const uint32_t* lutQ16, int center, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
                            const float* s1, const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
@@ -2138,7 +2134,7 @@ int launch_gemm_tn_q8_dy16(const void* P16, const void* Q8, const float* a_qp, i
 
 // Weight gradient with the Q operand as uint8 table indices + a 256-entry table of bf16 (hi | lo << 16) pairs (fc2: Q = gelu(fq(fc1 output))): the
 // 128 x 384 tile of launch_gemm_tn's split-Q form, the same MFMAs in the same order - bit-identical to it on the expanded planes.
-template <bool DY16, int TQ = 2>   // TQ = 1 (one-plane form only): the hi half of every table entry alone - X rounded to fp16, one MFMA pass
+template <bool DY16>   // DY16 (the one-plane form): the hi half of every table entry alone - X rounded to fp16, one MFMA pass (TQ = 1)
 static int gemm_tn_codes_impl(const void* P_hi, const void* P_lo, const void* Qc, const uint32_t* lutQ, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
                               const float* s1, const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
                               float* dbias, const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
@@ -2146,7 +2142,7 @@ static int gemm_tn_codes_impl(const void* P_hi, const void* P_lo, const void* Qc
         set_error("gemm_tn_codes: unsupported arguments M=%d N=%d Kw=%d ldp=%d ldq=%d (need N%%128==0, Kw%%384==0, ldp%%8==0, ldq%%16==0)", M, N, Kw, ldp, ldq);
         return 1;
     }
-    constexpr int TP = DY16 ? 1 : 2;
+    constexpr int TP = DY16 ? 1 : 2, TQ = DY16 ? 1 : 2;
     TNArgs a = tn_args(P_hi, DY16 ? P_hi : P_lo, nullptr, nullptr, C, M, N, Kw, ldp, ldq, ldc, s1, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div);
     a.Qc = reinterpret_cast<const uint8_t*>(Qc); a.lutQ = lutQ; a.s2 = s2;
     const int tiles = (N / 128) * (Kw / 384);
@@ -2173,13 +2169,9 @@ int launch_gemm_tn_codes(const void* P_hi, const void* P_lo, const void* Qc, con
 int launch_gemm_tn_codes_dy16(const void* P16, const void* Qc, const uint32_t* lutQ16, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
                               const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
                               const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
-    static const int xpair = getenv("QATVIT_DY16_XPAIR") ? atoi(getenv("QATVIT_DY16_XPAIR")) : 0;   // QATVIT_DY16_XPAIR=1: the float X operands as fp16 (hi, lo) pairs
-    if (!xpair && tn_q8_enabled() && ldq % 16 == 0 && Kw % 384 == 0)
+    if (knobs().tn_q8 && ldq % 16 == 0 && Kw % 384 == 0)
         return gemm_tn_q8_impl<1>(P16, Qc, lutQ16, 0, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div, st, partial,
                                   partial_bytes);
-    if (!xpair)
-        return gemm_tn_codes_impl<true, 1>(P16, nullptr, Qc, lutQ16, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias,
-                                           row_div, st, partial, partial_bytes);
     return gemm_tn_codes_impl<true>(P16, nullptr, Qc, lutQ16, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
                                     st, partial, partial_bytes);
 }
@@ -2492,9 +2484,8 @@ int launch_tn_stream(int mode, const TNStreamGemm* items, int n, int M, int cent
     for (int i = 0; i < n; ++i) tiles += (items[i].N / 128) * (items[i].Kw / 384);
     {   // A batch whose tiles do not tile the chip in lockstep (144 fc2 tiles on 256 CUs) as TWO aligned launches where a cut exists: free spans share nothing through L2
         // (the fc2 launch fetched 4.7 GB for 1.4 GB of operands).  k GEMMs x s1 splits and n - k GEMMs x s2 splits, both >= 90 % of the CUs.
-        static const bool split2 = !(getenv("QATVIT_TN_STREAM_SPLIT2") && atoi(getenv("QATVIT_TN_STREAM_SPLIT2")) == 0);
         auto fill_ok = [&](int t) { const int sp = t > 0 && cus / t > 0 ? cus / t : 1; return t > 0 && t <= cus && (int64_t)t * sp * 10 >= (int64_t)cus * 9; };
-        if (split2 && n >= 2 && tiles <= cus && !fill_ok(tiles)) {
+        if (n >= 2 && tiles <= cus && !fill_ok(tiles)) {
             int t1 = 0;
             for (int k = 1; k < n; ++k) {
                 t1 += (items[k - 1].N / 128) * (items[k - 1].Kw / 384);
@@ -2510,10 +2501,9 @@ int launch_tn_stream(int mode, const TNStreamGemm* items, int n, int M, int cent
     // backward's 252 grid-X tiles measured 1.85 us per step against 0.97).  Otherwise (144 fc2 tiles on 256 CUs) stream-K spans cut where they fall.
     const int splits = tiles > 0 && cus / tiles > 0 ? cus / tiles : 1;
     // More tiles than CUs (ViT-B: 1008): whole tiles round-robin, round r = tiles r * cus .. - every round starts its tiles together (lockstep sharing as in the aligned
-    // plan, no cut tile); taken when the last round is at least 60 % full or there are >= 3 rounds (QATVIT_TN_STREAM_RR=0: free spans)
-    static const bool rr_on = !(getenv("QATVIT_TN_STREAM_RR") && atoi(getenv("QATVIT_TN_STREAM_RR")) == 0);
+    // plan, no cut tile); taken when the last round is at least 60 % full or there are >= 3 rounds
     const int rr_rounds = (tiles + cus - 1) / cus;
-    const bool rr = rr_on && tiles > cus && ((int64_t)tiles * 10 >= (int64_t)rr_rounds * cus * 8);
+    const bool rr = tiles > cus && ((int64_t)tiles * 10 >= (int64_t)rr_rounds * cus * 8);
     const bool aligned = rr || (tiles > 0 && tiles <= cus && (int64_t)tiles * splits * 10 >= (int64_t)cus * 9);
     const int upw_al = (a.steps + splits - 1) / splits;
     a.steps_pad = aligned ? upw_al * splits : a.steps;

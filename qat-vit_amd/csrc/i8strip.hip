@@ -420,10 +420,6 @@ static void strip_launch(const I8StripArgs& a0, hipStream_t st) {
 static int strip_ntl(int N, int K) {   // K = 384: 3 or 4 column tiles per workgroup (qkv 1152 / fc1 1536 of ViT-S); K = 768: all 6 or 8 of them (qkv 2304 / fc1 3072 of ViT-B)
     return K == 384 ? (N % (4 * 384) == 0 ? 4 : N % (3 * 384) == 0 ? 3 : 0) : (N == 6 * 384 ? 6 : N == 8 * 384 ? 8 : 0);
 }
-static bool strip_on() {
-    static const int on = getenv("QATVIT_I8_STRIP") ? atoi(getenv("QATVIT_I8_STRIP")) : 1;   // 0: the general tall kernel (A/B arm of the bit-identity test)
-    return on != 0;
-}
 // the kernel's 32-bit / 24-bit address arithmetic: the A-strip DMA offset (m0 + row) * lda + .. is a uint32; mode 4 forms __umul24(row, ldc) + column as a
 // uint32; mode 7 floors (row + 0.5) * (1 / T) in fp32 (exact with margin for row < 2^20, T < 2^10)
 static bool strip_addressable(int M, int N, int lda, int ldc, int mode) {
@@ -433,7 +429,7 @@ static bool strip_addressable(int M, int N, int lda, int ldc, int mode) {
     return true;
 }
 bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post) {
-    if (!strip_on() || !B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !strip_addressable(M, N, lda, ldc, post->mode) || !strip_ntl(N, K)) return false;
+    if (!knobs().i8_strip || !B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !strip_addressable(M, N, lda, ldc, post->mode) || !strip_ntl(N, K)) return false;
     if (post->mode == 3) return true;
     if (!post->out8 || !post->out8_mask || post->qmax - post->qmin >= 256) return false;
     if (post->mode == 7) return post->code_hd == 64 && (N / 3) % 384 == 0 && post->code_T >= 1 && post->code_T < 1024;
@@ -444,7 +440,7 @@ bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, con
 bool launch_i8_strip(const void* A8, const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, int ldc,
                      const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
                      const NTPost* post, bool force, const QpLate* late) {
-    if ((!strip_on() && !force) || !B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !s1 || !strip_addressable(M, N, lda, ldc, post->mode)) return false;
+    if ((!knobs().i8_strip && !force) || !B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !s1 || !strip_addressable(M, N, lda, ldc, post->mode)) return false;
     const int ntl = strip_ntl(N, K);
     if (!ntl) return false;
     const bool wide = K == 768;

@@ -10,6 +10,28 @@ constexpr int kWave = 64;
 
 void set_error(const char* fmt, ...);
 
+// The QATVIT_* knobs of the library, read from the environment once per process on first use (capi.hip).  Each one switches a form off for an
+// A/B or bit-identity comparison (tests/test_gpu_knobs.py); unset = on, set = atoi(value) != 0.  Which form a configuration runs is decided from
+// these and its shapes in one place: engine.hip Forms.
+struct Knobs {
+    bool i8;              // QATVIT_I8: the grid x grid forward GEMMs (patch-embed, qkv, fc1) on int8 MFMA; 0: bf16 MFMA (the same bits)
+    bool f16;             // QATVIT_F16: the float operands of the proj / fc2 forward GEMMs as fp16 (hi, lo) pairs; 0: bf16 pairs (the round-1 arithmetic)
+    bool fc2_codes;       // QATVIT_FC2_CODES: fc2's forward A operand as one byte per element + a 256-entry fp16-pair table; 0: the two fp16 planes
+    bool fc1_bits;        // QATVIT_FC1_BITS: the backward's fc1 codes as that byte plane + one STE mask bit per element; 0: the uint16 code plane
+    bool fc2w_codes;      // QATVIT_FC2W_CODES: fc2's weight gradient from the byte plane + a bf16-pair table; 0: from the bf16 (hi, lo) planes
+    bool wbatch;          // QATVIT_WBATCH: weight preparation as three multi-tensor launches; 0: one launch triple per weight (the deep-model path)
+    bool attn_codes;      // QATVIT_ATTN_CODES: the attention backward reads the codes its forward saved; 0: it re-quantises the fp32 qkv
+    bool qkv_2pass;       // QATVIT_QKV_2PASS: the qkv GEMM as a statistics pass + a pass writing codes and mask bits; 0: once, fp32 output
+    bool lnb_fuse;        // QATVIT_LNB_FUSE: the LayerNorm backward in the fc1 / qkv dgrad epilogue (embed_dim 384); 0: its own kernel
+    bool qp_late;         // QATVIT_QP_LATE: the observer / qparams update inside the consumer kernel (QpLate); 0: a k_qparams launch behind the producer
+    bool tn_stream;       // QATVIT_TN_STREAM: the one-plane weight gradients of a backward call as one stream-K launch per X form; 0: one launch per GEMM
+    bool tn_q8;           // QATVIT_TN_Q8: one-plane weight gradients with a byte X operand (k_gemm_tn_q8); 0: the fp16-plane / expand-through-LDS kernels
+    bool attn_bwd_fused;  // QATVIT_ATTN_BWD_FUSED: one fused attention backward kernel where its shape holds; 0: k_attn_bwd_dq + k_attn_bwd_dkv
+    bool f16_strip;       // QATVIT_F16_STRIP: the one-plane fc2 dgrad on the A-stationary strip kernel; 0: the general tall tile
+    bool i8_strip;        // QATVIT_I8_STRIP: the K = 384 / 768 int8 GEMMs on the A-stationary strip kernel; 0: the general tall kernel
+};
+const Knobs& knobs();
+
 #define QV_CHECK_ARG(cond, ...)                 \
     do {                                        \
         if (!(cond)) {                          \

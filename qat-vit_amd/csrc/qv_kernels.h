@@ -121,7 +121,6 @@ int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N
                         hipStream_t st, const NTPost* post = nullptr);
 // ---- f16strip.hip: the fc2 dgrad + GELU backward of the one-plane backward, A-stationary (K = 384, N = 1536); B16f = the transposed weight integers as fp16 in
 // fragment order (w8f_offset on their 768-byte rows).  true when it took the request; false -> launch_gemm_nt_dy16 with epilogue mode 9
-bool f16_strip_enabled();   // QATVIT_F16_STRIP != 0
 bool launch_f16_strip_gelu_bwd(const void* A16, const void* B16f, float* unused, int M, int N, int K, int lda, int ldc, const float* s1, const float* s2, hipStream_t st,
                                const NTPost* post);
 // ---- i8strip.hip: the K = 384 two-pass forward GEMMs (qkv, fc1), A-stationary; returns true when it covered (and launched) the request
@@ -161,7 +160,6 @@ int launch_gemm_tn_codes_dy16(const void* P16, const void* Qc, const uint32_t* l
 int launch_gemm_tn_q8_dy16(const void* P16, const void* Q8, const float* a_qp, int center, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s2,
                            const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias, const float* row_div,
                            hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
-bool tn_q8_enabled();   // QATVIT_TN_Q8 (default on)
 // the weight gradients of one backward call, one persistent stream-K launch per X form (gemm.hip k_tn_stream): mode 0 = X as int8 grid plane (s1 = the activation's
 // qparams, `center`), 1 = uint8 codes + table (lut), 2 = fp16 plane.  All items share M.  partial: >= tn_stream_scratch_bytes().
 struct TNStreamGemm {

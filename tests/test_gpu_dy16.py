@@ -77,9 +77,8 @@ def test_wgrad_one_plane_vs_fp64(native_lib, M, N, Kw, kind):
         tl = (tab - th.float()).to(torch.float16)
         lut = ((th.view(torch.int16).int() & 0xffff) | (tl.view(torch.int16).int() << 16)).contiguous()
         qc = torch.randint(0, 256, (M, Kw), generator=g, device="cuda").to(torch.uint8)
-        # (the table's lo halves are ignored unless QATVIT_DY16_XPAIR=1: the float X operand enters the one-plane weight gradient rounded to fp16)
-        import os
-        xv = (th.float() + (tl.float() if os.environ.get("QATVIT_DY16_XPAIR", "0") != "0" else 0.0))[qc.long()]
+        # (the table's lo halves are ignored: the float X operand enters the one-plane weight gradient rounded to fp16)
+        xv = th.float()[qc.long()]
     dW = torch.zeros(N, Kw, device="cuda")
     db = torch.zeros(N, device="cuda")
     scratch = torch.empty(native_lib.qatvit_gemm_tn_scratch_bytes(), dtype=torch.uint8, device="cuda")

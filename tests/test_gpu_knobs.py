@@ -19,7 +19,6 @@ KNOBS = {
     "QATVIT_QKV_2PASS=0": "bits",          # qkv GEMM once, fp32 output, attention quantises on load
     "QATVIT_F16_STRIP=0": "bits",          # fc2 dgrad + GELU backward of the one-plane backward on the general tall tile (epilogue 19) instead of the A-stationary strip kernel
     "QATVIT_DY16_MIRROR=0": "bits",        # the overflow flag read behind a stream synchronisation instead of from the pinned mirror the backward writes before its weight gradients
-    "QATVIT_LN_APPLY_ROWS=1": "bits",      # k_ln_apply_quant as one wave per row instead of its flat form (one float4 per thread)
     "QATVIT_QP_LATE=0": "bits",            # a k_qparams launch behind every producer of statistics instead of the update inside the consumer kernel (72 launches per step)
     "QATVIT_I8_STRIP=0": "bits",           # the two-pass K = 384 GEMMs (qkv, fc1) on the general tall tile instead of the A-stationary strip kernel
     "QATVIT_I8=0": "bits",                 # grid x grid GEMMs on bf16 MFMA
@@ -40,14 +39,12 @@ KNOBS = {
     "QATVIT_ATTN_BWD_FUSED=0": (1e-9, 3e-5),
     "QATVIT_ATTN_CODES=0": (1e-9, 3e-5),    # attention backward re-quantises the fp32 qkv (implies the one-pass qkv GEMM and the two-kernel backward)
     # the backward's arithmetic forms (round 4): the default one-plane form against the bf16-pair form (every dY 2^-12 instead of 2^-17 per element:
-    # 1e-3 per gradient tensor is the bar of tests/test_gpu_dy16.py; this depth-2 step stays far below it), and the float X operands of the
-    # proj / fc2 weight gradients as fp16 pairs instead of fp16.  The forward is the same bit for bit (logits: 0).
+    # 1e-3 per gradient tensor is the bar of tests/test_gpu_dy16.py; this depth-2 step stays far below it).  The forward is the same bit for bit (logits: 0).
     "QATVIT_DY16=0": "bits",
-    "QATVIT_DY16_XPAIR=1": "bits",
     "QATVIT_F16=0": (0.1, 0.06),            # bf16 pairs for the forward float operands (2^-17 instead of 2^-23: one-step flips possible)
 }
 ATOMIC = ("bias", "norm", "cls_token", "pos_embed")
-ONE_PLANE_FORMS = ("QATVIT_DY16=0", "QATVIT_DY16_XPAIR=1")   # step 1 (calibration = the pair form) is bit-identical under these two; step 2 differs at 2^-12 per element
+ONE_PLANE_FORMS = ("QATVIT_DY16=0",)   # step 1 (calibration = the pair form) is bit-identical under it; step 2 differs at 2^-12 per element
 
 
 def run(tmp_path, tag, env_kv, backend):
