@@ -356,6 +356,19 @@ int qatvit_float_student_init(const qatvit_cfg* cfg, void* workspace, void* stre
 int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream);
 int qatvit_float_student_backward(const qatvit_cfg* cfg, void* const* params, const float* dlogits, void* const* grads, void* workspace,
                                   void* stream);
+/* Observe-only form: the PREPARED student with fake_quant_enabled = 0 on every fake-quant module (torch.ao.quantization.disable_fake_quant).  Stock
+ * FusedMovingAvgObsFakeQuantize then passes every tensor through unchanged (gradient: the identity) and, where observer_enabled = 1, still moves
+ * running_min / running_max by the EMA (c = cfg->averaging_const); scale / zero_point are not written.  The forward is qatvit_float_student_forward
+ * - the same arithmetic, bit for bit - that also reduces the min / max at all fake-quant points: the images, the patch-embedding / qkv / proj / fc1 /
+ * fc2 / head outputs (fp32 with bias; proj and fc2 before the residual add, fc1 before GELU), the fp32 norm1 / norm2 / final-norm outputs, and the
+ * weights (per tensor, or per output channel with cfg->w_per_channel).  Every observer is folded at the end of the forward with its module's own
+ * device flags (nothing in the forward reads the quantisers' state).  The backward is qatvit_float_student_backward unchanged.
+ *  observe: a device buffer of qatvit_float_student_observe_bytes(cfg) bytes (batch independent), bound once to the modules' buffers by
+ *  qatvit_float_student_observe_init (act_fq / weight_fq in the orders above; synchronises the stream) before its first forward. */
+int64_t qatvit_float_student_observe_bytes(const qatvit_cfg* cfg);
+int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* act_fq, const qatvit_fq* weight_fq, void* observe, void* stream);
+int qatvit_float_student_forward_observe(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* observe,
+                                         void* stream);
 
 /* ---------------------------------------------------------------------------
  * Integer inference forward of the trained student from its exported integers.

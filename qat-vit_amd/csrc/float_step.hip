@@ -72,10 +72,14 @@ __global__ void k_fs_consts(float* qp_off, uint32_t* ones, int64_t nwords) {
 
 // ---------------------------------------------------------------- head (cls pooling), fp32: B x C x D is tiny
 // hn[b,:] = LN(x[b,0,:]) from the saved row statistics; logits[b,c] = hn[b,:] . W[c,:] + bias[c]
+// STATS (observe-only forward): the min / max of the logits into kStatSlots accumulator pairs, one atomic per wave
+template <bool STATS = false>
 __global__ __launch_bounds__(256) void k_fs_head_fwd(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ W,
-                                                     const float* __restrict__ bias, float* __restrict__ hn, float* __restrict__ logits, int D, int T, int C) {
+                                                     const float* __restrict__ bias, float* __restrict__ hn, float* __restrict__ logits, int D, int T, int C,
+                                                     uint32_t* __restrict__ stats = nullptr) {
     extern __shared__ float sh[];
+    float smn = INFINITY, smx = -INFINITY;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row = (int64_t)b * T;
     const float mu = mean[row], rs = rstd[row];
@@ -90,6 +94,10 @@ __global__ __launch_bounds__(256) void k_fs_head_fwd(const float* __restrict__ x
         for (int k = lane; k < D; k += 64) acc += sh[k] * W[(int64_t)c * D + k];
         acc = wave_sum(acc);
         if (lane == 0) logits[(int64_t)b * C + c] = acc + bias[c];
+        if constexpr (STATS) { smn = fminf(smn, acc + bias[c]); smx = fmaxf(smx, acc + bias[c]); }
+    }
+    if constexpr (STATS) {
+        if (lane == 0) stat_atomic(stats, kStatSlots, smn, smx);   // (the sums are wave-uniform: lane 0 holds the wave's min / max)
     }
 }
 // one thread per output element, fixed summation order (no atomics):
@@ -391,14 +399,52 @@ int qatvit_float_student_init(const qatvit_cfg* cfg, void* workspace, void* stre
     return 0;
 }
 
-// params: fp32 tensors in the student's order (include/qatvit.h).  Leaves in the workspace everything qatvit_float_student_backward reads.
-int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && params && images && logits && workspace, "qatvit_float_student_forward: null argument");
-    if (fs_check(*cfg)) return 1;
+// ---------------------------------------------------------------- observe-only form (include/qatvit.h qatvit_float_student_forward_observe)
+// The observe buffer: the fold table (one ObsFoldEntry per fake-quant module, act_fq order then weight_fq order), then the min / max accumulators -
+// kStatSlots pairs per activation quantizer and per per-tensor weight quantizer, 2 words per channel for a per-channel one.  Batch independent.
+struct ObsPlan {
+    int n_act, n_w, nblocks;
+    int64_t tab, act_stats, w_stats[kMaxW], stats_words, total;
+};
+static int fs_n_act(const qatvit_cfg& c) { return 4 + 6 * c.depth; }
+static int fs_n_w(const qatvit_cfg& c) { return 2 + 4 * c.depth; }
+static void fs_wshape_all(const qatvit_cfg& c, int wi, int* N, int* K) {   // fs_weight_shape plus the head (the last weight quantizer)
+    if (wi == 1 + 4 * c.depth) { *N = c.num_classes; *K = c.embed_dim; return; }
+    fs_weight_shape(c, wi, N, K);
+}
+static ObsPlan obs_plan(const qatvit_cfg& c) {
+    ObsPlan p{};
+    p.n_act = fs_n_act(c);
+    p.n_w = fs_n_w(c);
+    int64_t o = 0;
+    auto take = [&](int64_t b) { int64_t r = o; o += (b + 255) & ~(int64_t)255; return r; };
+    p.tab = take((int64_t)(p.n_act + p.n_w) * sizeof(ObsFoldEntry));
+    int64_t words = (int64_t)p.n_act * kStatSlots * kStatStride;
+    p.nblocks = p.n_act;
+    for (int wi = 0; wi < p.n_w; ++wi) {
+        int N, K;
+        fs_wshape_all(c, wi, &N, &K);
+        p.w_stats[wi] = words;
+        words += c.w_per_channel ? 2 * (int64_t)N : kStatSlots * kStatStride;
+        p.nblocks += c.w_per_channel ? (N + 63) / 64 : 1;
+    }
+    p.stats_words = words;
+    p.act_stats = take(words * 4);
+    p.total = o;
+    return p;
+}
+// statistics of one forward: where each producer accumulates (nullptr everywhere: the plain float forward)
+struct FsObs {
+    uint32_t* stats = nullptr;   // the accumulators (ObsPlan::act_stats)
+    const ObsPlan* p = nullptr;
+    uint32_t* act(int ai) const { return stats ? stats + (int64_t)ai * kStatSlots * kStatStride : nullptr; }
+    uint32_t* w(int wi) const { return stats + p->w_stats[wi]; }
+};
+
+static int fs_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, hipStream_t st, const FsObs& ob) {
     const qatvit_cfg& c = *cfg;
     const FsPlan p = fs_plan(c);
     char* ws = reinterpret_cast<char*>(workspace);
-    hipStream_t st = (hipStream_t)stream;
     const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden;
     const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth;
     const int64_t M = (int64_t)c.batch * T;
@@ -423,34 +469,120 @@ int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, con
         t.blk0[t.n] = blocks;
         k_fs_wsplit<<<blocks, 256, 0, st>>>(t);
     }
-    auto gemm = [&](int64_t ah, int64_t al, int wi, const float* bias, float* C, int N, int K, int Mrows) {
-        return launch_gemm_nt(V(ah), V(al), V(p.w_hi[wi]), C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, nullptr, 1, st, V(p.w_lo[wi]), nullptr);
+    // (act_fq order: 0 quant, 1 patch_embed.proj, per block 2 + 6 i + {norm1, qkv, proj, norm2, fc1, fc2}, then norm, head)
+    auto gemm = [&](int64_t ah, int64_t al, int wi, const float* bias, float* C, int N, int K, int Mrows, int ai) {
+        return launch_gemm_nt(V(ah), V(al), V(p.w_hi[wi]), C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, ob.act(ai), ob.stats ? kStatSlots : 1, st,
+                              V(p.w_lo[wi]), nullptr);
     };
+    if (ob.stats) {   // re-arm every accumulator; the images' and the weights' statistics (the QAT forward's weight pass, fq.hip k_w_observe_all)
+        launch_ws_init(ob.stats, ob.p->stats_words / 2, st);
+        launch_minmax(images, 1, (int64_t)c.batch * c.in_chans * c.img_size * c.img_size, 0, ob.act(0), kStatSlots, st);
+        WObsTab to{};
+        to.n = ob.p->n_w;
+        to.per_channel = c.w_per_channel;
+        to.nslots = kStatSlots;
+        for (int wi = 0; wi < to.n; ++wi) {
+            static const int kW[4] = {2, 4, 8, 10};
+            fs_wshape_all(c, wi, &to.N[wi], &to.K[wi]);
+            to.W[wi] = wi == 0 ? prm(0) : wi == 1 + 4 * L ? prm(4 + 12 * L + 2) : bprm((wi - 1) / 4, kW[(wi - 1) % 4]);
+            to.ws[wi] = ob.w(wi);
+        }
+        launch_w_observe_all(to, st);
+    }
     launch_patches_split(images, V(p.p_hi), V(p.p_lo), c.batch, c.in_chans, c.img_size, c.img_size, c.patch_size, st);
-    if (gemm(p.p_hi, p.p_lo, 0, prm(1), F(p.Y0), D, Kpe, c.batch * np)) return 1;
+    if (gemm(p.p_hi, p.p_lo, 0, prm(1), F(p.Y0), D, Kpe, c.batch * np, 1)) return 1;
     launch_resid_ln_split_save(0, nullptr, F(p.Y0), prm(2), prm(3), F(p.blk[0].x), bprm(0, 0), bprm(0, 1), c.ln_eps, V(p.blk[0].h1_hi), V(p.blk[0].h1_lo),
-                               F(p.blk[0].mean1), F(p.blk[0].rstd1), M, D, T, st);
+                               F(p.blk[0].mean1), F(p.blk[0].rstd1), M, D, T, st, ob.act(2));
     for (int i = 0; i < L; ++i) {
         const FsBlock& k = p.blk[i];
-        const int w0 = 1 + 4 * i;
-        if (gemm(k.h1_hi, k.h1_lo, w0 + 0, bprm(i, 3), F(k.qkv), 3 * D, D, (int)M)) return 1;
+        const int w0 = 1 + 4 * i, a0 = 2 + 6 * i;
+        if (gemm(k.h1_hi, k.h1_lo, w0 + 0, bprm(i, 3), F(k.qkv), 3 * D, D, (int)M, a0 + 1)) return 1;
         if (launch_attn_fwd_float(F(k.qkv), c.batch, T, c.num_heads, D, V(k.O_hi), V(k.O_lo), st, 0, F(k.lse))) return 1;
-        if (gemm(k.O_hi, k.O_lo, w0 + 1, bprm(i, 5), F(p.Y), D, D, (int)M)) return 1;
+        if (gemm(k.O_hi, k.O_lo, w0 + 1, bprm(i, 5), F(p.Y), D, D, (int)M, a0 + 2)) return 1;
         launch_resid_ln_split_save(1, F(k.x), F(p.Y), nullptr, nullptr, F(k.xm), bprm(i, 6), bprm(i, 7), c.ln_eps, V(k.h2_hi), V(k.h2_lo), F(k.mean2),
-                                   F(k.rstd2), M, D, T, st);
-        if (gemm(k.h2_hi, k.h2_lo, w0 + 2, bprm(i, 9), F(k.Y1), Hd, D, (int)M)) return 1;
+                                   F(k.rstd2), M, D, T, st, ob.act(a0 + 3));
+        if (gemm(k.h2_hi, k.h2_lo, w0 + 2, bprm(i, 9), F(k.Y1), Hd, D, (int)M, a0 + 4)) return 1;
         launch_gelu_split(F(k.Y1), V(k.G_hi), V(k.G_lo), M * Hd, st);
-        if (gemm(k.G_hi, k.G_lo, w0 + 3, bprm(i, 11), F(p.Y), D, Hd, (int)M)) return 1;
+        if (gemm(k.G_hi, k.G_lo, w0 + 3, bprm(i, 11), F(p.Y), D, Hd, (int)M, a0 + 5)) return 1;
         const bool last = i + 1 == L;
         const FsBlock* nx = last ? nullptr : &p.blk[i + 1];
         launch_resid_ln_split_save(1, F(k.xm), F(p.Y), nullptr, nullptr, last ? F(p.x_last) : F(nx->x), last ? prm(4 + 12 * L) : bprm(i + 1, 0),
                                    last ? prm(4 + 12 * L + 1) : bprm(i + 1, 1), c.ln_eps, last ? V(p.hf_hi) : V(nx->h1_hi), last ? V(p.hf_lo) : V(nx->h1_lo),
-                                   last ? F(p.meanf) : F(nx->mean1), last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st);
+                                   last ? F(p.meanf) : F(nx->mean1), last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, ob.act(last ? 2 + 6 * L : a0 + 6));
     }
     const int hb = 4 + 12 * L;
-    k_fs_head_fwd<<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3), F(p.hn), logits,
-                                                          D, T, c.num_classes);
+    if (ob.stats) {
+        k_fs_head_fwd<true><<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3),
+                                                                    F(p.hn), logits, D, T, c.num_classes, ob.act(3 + 6 * L));
+        // every observer at once: nothing in this forward read the quantisers' state, so folding at the end is the stock update
+        launch_obs_fold(reinterpret_cast<const ObsFoldEntry*>(reinterpret_cast<char*>(ob.stats) - ob.p->act_stats + ob.p->tab), ob.p->n_act + ob.p->n_w,
+                        ob.p->nblocks, c.averaging_const, st);
+    } else {
+        k_fs_head_fwd<<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3), F(p.hn),
+                                                              logits, D, T, c.num_classes);
+    }
+    return 0;
+}
+
+// params: fp32 tensors in the student's order (include/qatvit.h).  Leaves in the workspace everything qatvit_float_student_backward reads.
+int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream) {
+    QV_CHECK_ARG(cfg && params && images && logits && workspace, "qatvit_float_student_forward: null argument");
+    if (fs_check(*cfg)) return 1;
+    if (fs_forward(cfg, params, images, logits, workspace, (hipStream_t)stream, FsObs{})) return 1;
     QV_CHECK_LAUNCH("qatvit_float_student_forward");
+    return 0;
+}
+
+int64_t qatvit_float_student_observe_bytes(const qatvit_cfg* cfg) {
+    if (!cfg) { set_error("qatvit_float_student_observe_bytes: null argument"); return -1; }
+    if (fs_check(*cfg)) return -1;
+    return obs_plan(*cfg).total;
+}
+
+int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* act_fq, const qatvit_fq* weight_fq, void* observe, void* stream) {
+    QV_CHECK_ARG(cfg && act_fq && weight_fq && observe, "qatvit_float_student_observe_init: null argument");
+    if (fs_check(*cfg)) return 1;
+    const qatvit_cfg& c = *cfg;
+    const ObsPlan p = obs_plan(c);
+    char* ob = reinterpret_cast<char*>(observe);
+    uint32_t* stats = reinterpret_cast<uint32_t*>(ob + p.act_stats);
+    ObsFoldEntry tab[4 + 6 * 12 + 2 + 4 * 12];
+    int blk = 0;
+    for (int ai = 0; ai < p.n_act; ++ai) {
+        const qatvit_fq& f = act_fq[ai];
+        tab[ai] = ObsFoldEntry{stats + (int64_t)ai * kStatSlots * kStatStride, f.min_val, f.max_val, f.scale, f.zero_point, f.observer_on, f.fake_quant_on,
+                               1, kStatSlots, 0, c.act_qmin, c.act_qmax, blk};
+        blk += 1;
+    }
+    for (int wi = 0; wi < p.n_w; ++wi) {
+        const qatvit_fq& f = weight_fq[wi];
+        int N, K;
+        fs_wshape_all(c, wi, &N, &K);
+        tab[p.n_act + wi] = ObsFoldEntry{stats + p.w_stats[wi], f.min_val, f.max_val, f.scale, f.zero_point, f.observer_on, f.fake_quant_on,
+                                         c.w_per_channel ? N : 1, c.w_per_channel ? 1 : kStatSlots, 1, c.w_qmin, c.w_qmax, blk};
+        blk += c.w_per_channel ? (N + 63) / 64 : 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemcpyAsync(ob + p.tab, tab, sizeof(ObsFoldEntry) * (p.n_act + p.n_w), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {   // (once per buffer: the host table is gone after this call)
+        set_error("qatvit_float_student_observe_init: copying the fold table failed");
+        return 2;
+    }
+    launch_ws_init(stats, p.stats_words / 2, st);
+    QV_CHECK_LAUNCH("qatvit_float_student_observe_init");
+    return 0;
+}
+
+int qatvit_float_student_forward_observe(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* observe,
+                                         void* stream) {
+    QV_CHECK_ARG(cfg && params && images && logits && workspace && observe, "qatvit_float_student_forward_observe: null argument");
+    if (fs_check(*cfg)) return 1;
+    const ObsPlan p = obs_plan(*cfg);
+    FsObs ob;
+    ob.stats = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(observe) + p.act_stats);
+    ob.p = &p;
+    if (fs_forward(cfg, params, images, logits, workspace, (hipStream_t)stream, ob)) return 1;
+    QV_CHECK_LAUNCH("qatvit_float_student_forward_observe");
     return 0;
 }
 

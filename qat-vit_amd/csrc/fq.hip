@@ -293,6 +293,23 @@ int launch_w_qparams_all(WQpTab& t, hipStream_t st) {
     return 0;
 }
 
+// the observe-only forward's single fold (qv_kernels.h ObsFoldEntry): workgroup b takes the last entry whose blk0 <= b (binary search, wave-uniform)
+__global__ __launch_bounds__(64) void k_obs_fold(const ObsFoldEntry* __restrict__ tab, int n, float c) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].blk0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const ObsFoldEntry e = tab[lo];
+    qparams_body(e.ws, e.rmin, e.rmax, e.scale, e.zp, e.obs_on, e.fq_on, c, e.qmin, e.qmax, e.channels, e.symmetric, nullptr, 0, e.nslots, b - e.blk0);
+}
+int launch_obs_fold(const ObsFoldEntry* tab, int n, int nblocks, float c, hipStream_t st) {
+    k_obs_fold<<<nblocks, 64, 0, st>>>(tab, n, c);
+    return 0;
+}
+
 int launch_fq_backward(const float* dy, const uint8_t* mask_bits, float* dx, int64_t n, hipStream_t st) {
     k_fq_backward<<<stream_grid(n >> 3), 256, 0, st>>>(dy, mask_bits, dx, n);
     return 0;

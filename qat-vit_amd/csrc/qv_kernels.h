@@ -222,6 +222,14 @@ int launch_w_observe_all(WObsTab& t, hipStream_t st);      // fills blk0
 int launch_w_qparams_all(WQpTab& t, hipStream_t st);       // fills blk0
 int launch_w_quant_all(WQuantTab& t, hipStream_t st);      // fills blk0
 int launch_zero_i32(int32_t* p, int64_t n, hipStream_t st);
+// ---- observe-only forward (fq.hip): every observer of a forward folded in ONE launch.  One 64-lane workgroup per per-tensor entry (nslots
+// accumulator pairs), ceil(channels / 64) per per-channel entry (2 words per channel); qparams_body with reset_ws = 0 and no qp output: observer_on = 0
+// leaves running_min / max as they are, fake_quant_on = 0 leaves scale / zero_point.  tab: DEVICE array of n entries, blk0 ascending from 0.
+struct ObsFoldEntry {
+    uint32_t* ws; float* rmin; float* rmax; float* scale; int32_t* zp; const int64_t* obs_on; const int64_t* fq_on;
+    int32_t channels, nslots, symmetric, qmin, qmax, blk0;
+};
+int launch_obs_fold(const ObsFoldEntry* tab, int n, int nblocks, float c, hipStream_t st);
 int launch_wquant(const float* W, const float* qp, int per_channel, int qmin, int qmax, void* wq, void* wqT, int N, int K, hipStream_t st);
 
 // ---- dy16.hip: scale state of the one-plane backward.  Every gradient tensor that feeds a dgrad / wgrad GEMM pair has a slot:
@@ -256,9 +264,11 @@ bool attn_bwd_is_fused(int T, int H, int D, bool codes);
 // lse (optional): log-sum-exp of the scaled scores per query, [B][H][T]
 int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16 = 0, float* lse = nullptr);
 int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st);
-// mode 0: x = [cls; Y] + pos, mode 1: x = x_prev + Y; then LayerNorm(x) as a (hi, lo) pair, mean / rstd per row (optional)
+// mode 0: x = [cls; Y] + pos, mode 1: x = x_prev + Y; then LayerNorm(x) as a (hi, lo) pair, mean / rstd per row (optional); stats (optional):
+// kStatSlots {min, max} accumulator pairs that take the min / max of the fp32 LayerNorm outputs (the observe-only forward)
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
-                               const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st);
+                               const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
+                               uint32_t* stats = nullptr);
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st);   // n % 4 == 0
 
 }  // namespace qv

@@ -66,13 +66,17 @@ __device__ inline void t_pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y
 // NV = ceil(D / 256) column groups per lane.  All loads of the row are issued first, branch-free and pinned (a lane past D reads column 0
 // and is masked out): one `if (c < D)` region per group let LLVM sink each group's loads to its uses - three dependent HBM round trips
 // per row at D = 768.  gamma / beta once per thread.
-template <int MODE, int NV>
+// STATS (the observe-only student forward): min / max of the fp32 LayerNorm outputs, one wave reduction and one accumulator atomic per wave
+// (kStatSlots pairs); the instantiations without it are the teacher's and the float step's, unchanged.
+template <int MODE, int NV, bool STATS = false>
 __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict__ x_prev, const float* __restrict__ Y, const float* __restrict__ cls,
                                                         const float* __restrict__ pos, float* __restrict__ x_new, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, __bf16* __restrict__ h_hi,
                                                         __bf16* __restrict__ h_lo, int64_t M, int D, int T, int f16,
-                                                        float* __restrict__ mean_out = nullptr, float* __restrict__ rstd_out = nullptr) {
+                                                        float* __restrict__ mean_out = nullptr, float* __restrict__ rstd_out = nullptr,
+                                                        uint32_t* __restrict__ stats = nullptr) {
     const int lane = threadIdx.x & 63;
+    float smn = INFINITY, smx = -INFINITY;
     bool act[NV];
     int cc[NV];
     float4 g[NV], bb[NV];
@@ -115,19 +119,36 @@ __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict_
         }
         const float rs = rsqrtf(wave_sum(qq) / (float)D + eps);
         if (mean_out && lane == 0) { mean_out[row] = mu; rstd_out[row] = rs; }   // (the float student step's LayerNorm backward; the teacher passes nullptr)
+        if constexpr (STATS) {
 #pragma unroll
-        for (int j = 0; j < NV; ++j)
-            if (act[j])
-                st_split4(h_hi, h_lo, row * D + cc[j], v[j].x * rs * g[j].x + bb[j].x, v[j].y * rs * g[j].y + bb[j].y, v[j].z * rs * g[j].z + bb[j].z,
-                          v[j].w * rs * g[j].w + bb[j].w, f16);
+            for (int j = 0; j < NV; ++j)
+                if (act[j]) {
+                    const float o0 = v[j].x * rs * g[j].x + bb[j].x, o1 = v[j].y * rs * g[j].y + bb[j].y, o2 = v[j].z * rs * g[j].z + bb[j].z,
+                                o3 = v[j].w * rs * g[j].w + bb[j].w;
+                    smn = fminf(smn, fminf(fminf(o0, o1), fminf(o2, o3)));
+                    smx = fmaxf(smx, fmaxf(fmaxf(o0, o1), fmaxf(o2, o3)));
+                    st_split4(h_hi, h_lo, row * D + cc[j], o0, o1, o2, o3, f16);
+                }
+        } else {
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (act[j])
+                    st_split4(h_hi, h_lo, row * D + cc[j], v[j].x * rs * g[j].x + bb[j].x, v[j].y * rs * g[j].y + bb[j].y, v[j].z * rs * g[j].z + bb[j].z,
+                              v[j].w * rs * g[j].w + bb[j].w, f16);
+        }
+    }
+    if constexpr (STATS) {
+        smn = wave_min(smn);
+        smx = wave_max(smx);
+        if (lane == 0) stat_atomic(stats, kStatSlots, smn, smx);
     }
 }
-template <int MODE, typename... A>
+template <int MODE, bool STATS = false, typename... A>
 static void launch_resid_ln_split(int grid, hipStream_t st, int D, A... a) {
     const int nv = (D + 255) / 256;
-    if (nv == 1) k_resid_ln_split<MODE, 1><<<grid, 256, 0, st>>>(a...);
-    else if (nv == 2) k_resid_ln_split<MODE, 2><<<grid, 256, 0, st>>>(a...);
-    else k_resid_ln_split<MODE, 3><<<grid, 256, 0, st>>>(a...);
+    if (nv == 1) k_resid_ln_split<MODE, 1, STATS><<<grid, 256, 0, st>>>(a...);
+    else if (nv == 2) k_resid_ln_split<MODE, 2, STATS><<<grid, 256, 0, st>>>(a...);
+    else k_resid_ln_split<MODE, 3, STATS><<<grid, 256, 0, st>>>(a...);
 }
 
 __device__ inline float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
@@ -388,9 +409,15 @@ int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int
     return 0;
 }
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
-                               const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st) {
+                               const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
+                               uint32_t* stats) {
     __bf16* hh = reinterpret_cast<__bf16*>(h_hi);
     __bf16* hl = reinterpret_cast<__bf16*>(h_lo);
+    if (stats) {
+        if (mode == 0) launch_resid_ln_split<0, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats);
+        else launch_resid_ln_split<1, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats);
+        return 0;
+    }
     if (mode == 0) launch_resid_ln_split<0>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
     else launch_resid_ln_split<1>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
     return 0;

@@ -119,6 +119,70 @@ def staged_backward_allreduce(flat: torch.Tensor, layout: FlatGradLayout, bucket
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Fake-quant mode: pure host logic (no native library, no GPU) so that a CPU test drives the decision the engine takes.
+# torch.ao.quantization.disable_fake_quant / enable_fake_quant write `fake_quant_enabled` in place, which bumps the tensor's `_version`: comparing the
+# versions is a host-only check; the flags themselves are read (one device-to-host copy) only when a version moved.
+
+QAT = "qat"            # fake-quant on everywhere: the quantised step (qatvit_student_*)
+OBSERVE = "observe"    # fake-quant off everywhere: the float step + the observer updates (qatvit_float_student_forward_observe)
+
+
+class FqModeState:
+    """What the last decision saw: the `_version` of every `fake_quant_enabled` tensor and the mode chosen from them.  `reads` counts the host
+    reads of the flags."""
+
+    def __init__(self):
+        self.versions: Optional[Tuple[int, ...]] = None
+        self.mode: Optional[str] = None
+        self.reads = 0
+
+
+def fq_versions(flags: Sequence[torch.Tensor]) -> Tuple[int, ...]:
+    return tuple(t._version for t in flags)
+
+
+def decide_fq_mode(state: FqModeState, flags: Sequence[torch.Tensor], names: Sequence[str]) -> str:
+    """flags: the modules' `fake_quant_enabled` tensors (fq_flags_and_names).  QAT when every one is 1, OBSERVE when every one is 0; a mix raises
+    (before the caller launches anything) and leaves `state` as it was.  Unchanged versions since the last decision: its mode, without reading a
+    flag (about 15 us of host time for ViT-S)."""
+    versions = fq_versions(flags)
+    if versions == state.versions:
+        return state.mode
+    on = (torch.stack([t.reshape(-1)[0] for t in flags]) != 0).tolist()   # the one host read
+    state.reads += 1
+    if all(on):
+        mode = QAT
+    elif not any(on):
+        mode = OBSERVE
+    else:
+        def some(xs):
+            return ", ".join(xs[:8]) + (f" (+{len(xs) - 8} more)" if len(xs) > 8 else "")
+        en = [n for n, o in zip(names, on) if o]
+        dis = [n for n, o in zip(names, on) if not o]
+        raise RuntimeError(
+            f"qat-vit_amd: fake-quant is enabled on {len(en)} modules ({some(en)}) and disabled on {len(dis)} ({some(dis)}); the native step supports "
+            "fake_quant_enabled = 1 everywhere (QAT) or 0 everywhere (observe-only) - apply torch.ao.quantization.enable_fake_quant / disable_fake_quant "
+            "to the whole model")
+    state.versions, state.mode = versions, mode
+    return mode
+
+
+def fq_modules_and_names(wrapper: torch.nn.Module):
+    """The 126 (ViT-S) fake-quant modules of a prepared QATWrapper(ViT), activation order then weight order (include/qatvit.h), and their
+    qualified names in the wrapper."""
+    _, act, wfq = collect_student(wrapper)
+    names = {id(m): n for n, m in wrapper.named_modules()}
+    fqs = list(act) + list(wfq)
+    return fqs, [names.get(id(f), type(f).__name__) for f in fqs]
+
+
+def fq_flags_and_names(wrapper: torch.nn.Module):
+    """The `fake_quant_enabled` tensors of fq_modules_and_names (disable_fake_quant / enable_fake_quant write them in place) and the names."""
+    fqs, names = fq_modules_and_names(wrapper)
+    return [f.fake_quant_enabled for f in fqs], names
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 
 def _fq_of(mod, attr):
     fq = getattr(mod, attr, None)
@@ -226,11 +290,17 @@ class StudentEngine:
         for f in wfq:
             if not f.is_symmetric_quant or f.is_per_channel != w0.is_per_channel or (f.is_per_channel and f.ch_axis != 0):
                 raise RuntimeError("weight fake-quant must be symmetric, all per-tensor or all per-channel (axis 0)")
-        # fake-quant must be on everywhere (the GEMM operands ARE the quantisation grids); observers may be on or off - the kernels read
-        # `observer_enabled` on the device every step, so torch.ao.quantization.disable_observer / enable_observer work at any time
-        flags = torch.stack([f.fake_quant_enabled[0] for f in act + wfq])
-        if not bool((flags == 1).all().item()):  # one-time host read
-            raise RuntimeError("the native step needs fake_quant_enabled = 1 on every fake-quant module")
+        # Observers may be on or off - the kernels read `observer_enabled` on the device every step, so torch.ao.quantization.disable_observer /
+        # enable_observer work at any time.  Fake-quant is on everywhere (the quantised step: the GEMM operands ARE the quantisation grids) or off
+        # everywhere (the observe-only step); every forward decides which (decide_mode)
+        self._fq_flags, self._fq_names = fq_flags_and_names(wrapper)
+        self._fq_state = FqModeState()
+        self.fq_mode: Optional[str] = None       # the mode of the most recent forward
+        # observe-only resources, allocated by the first observe-only forward beside the QAT workspace (which keeps the dy16 scale history and the
+        # addresses a captured hipGraph is bound to)
+        self.f_workspace: Optional[torch.Tensor] = None
+        self.f_capacity = 0
+        self.observe_buf: Optional[torch.Tensor] = None
         hd = blocks[0].attn.head_dim
         self._cfg_kw = dict(
             img_size=m.patch_embed.img_size, patch_size=m.patch_embed.patch_size, in_chans=pe.weight.shape[1],
@@ -406,15 +476,34 @@ class StudentEngine:
         if tuple(p.data_ptr() for p in self.params) != self._param_ptrs_key:
             raise RuntimeError("student parameters were re-allocated after the native engine was built (e.g. .to()); rebuild the wrapper")
 
-    def _check_images(self, images: torch.Tensor) -> native.Cfg:
+    def _check_shape(self, images: torch.Tensor) -> None:
         c0 = self.cfg
         if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[1:]) != (c0.in_chans, c0.img_size, c0.img_size) or images.dtype != torch.float32:
             raise RuntimeError(f"expected fp32 images of shape (B, {c0.in_chans}, {c0.img_size}, {c0.img_size}), got {tuple(images.shape)} {images.dtype}")
         self._check_ptrs()
+
+    def _check_images(self, images: torch.Tensor) -> native.Cfg:
+        self._check_shape(images)
         self._reserve(images.shape[0])
         return self.cfg_for(images.shape[0])
 
+    def fq_versions(self) -> Tuple[int, ...]:
+        return fq_versions(self._fq_flags)
+
+    def decide_mode(self) -> str:
+        """The fake-quant mode of the next forward (decide_fq_mode).  Back from observe-only to QAT, the one-plane backward's scale history is as old
+        as the last QAT step: the next QAT backward calibrates (the pair form) again."""
+        prev = self._fq_state.mode
+        mode = decide_fq_mode(self._fq_state, self._fq_flags, self._fq_names)
+        if mode == QAT and prev == OBSERVE:
+            self._dy16_calibrated = False
+        return mode
+
     def forward(self, images: torch.Tensor) -> torch.Tensor:
+        mode = self.decide_mode()                # (a mix of flags raises here, before any launch or collective)
+        self.fq_mode = mode
+        if mode == OBSERVE:
+            return self._forward_observe(images)
         c = self._check_images(images)
         self.cfg = c
         # Rank 0's fake-quant state is authoritative at the start of every TRAINING forward (what DDP's buffer broadcast does
@@ -431,6 +520,58 @@ class StudentEngine:
                                                             logits.data_ptr(), self.workspace.data_ptr(), 0, c.depth + 1, FWD_X16 if self._fwd_x16 else 0,
                                                             native.stream_ptr()), "qatvit_student_forward")
         return logits
+
+    # ------------------------------------------------------------------ observe-only step (fake-quant off everywhere)
+    def _reserve_observe(self, c: native.Cfg) -> None:
+        L, cp = self.lib, ctypes.byref(c)
+        if self.observe_buf is None:
+            n = L.qatvit_float_student_observe_bytes(cp)
+            if n <= 0:
+                raise RuntimeError("observe-only step: " + L.qatvit_last_error().decode())
+            buf = torch.empty(n, dtype=torch.uint8, device=self.device)
+            native.check(L.qatvit_float_student_observe_init(cp, self._act_structs, self._w_structs, buf.data_ptr(), native.stream_ptr()),
+                         "qatvit_float_student_observe_init")
+            self.observe_buf = buf
+        if c.batch > self.f_capacity:
+            n = L.qatvit_float_student_workspace_bytes(cp)
+            if n <= 0:
+                raise RuntimeError("observe-only step: " + L.qatvit_last_error().decode())
+            self.f_workspace = None
+            self.f_workspace = torch.empty(n, dtype=torch.uint8, device=self.device)
+            native.check(L.qatvit_float_student_init(cp, self.f_workspace.data_ptr(), native.stream_ptr()), "qatvit_float_student_init")
+            self.f_capacity = c.batch
+
+    def _forward_observe(self, images: torch.Tensor) -> torch.Tensor:
+        """Stock semantics with fake_quant_enabled = 0 everywhere: the float network, whose observers (where observer_enabled = 1) still take their
+        EMA step; scale / zero_point stay.  The data-parallel state broadcast of a training forward is the QAT step's."""
+        self._check_shape(images)
+        c = self.cfg_for(images.shape[0])
+        self._reserve_observe(c)
+        self.cfg = c
+        if self.pg is not None and self.sync_state:
+            self._broadcast_fq_state()
+        images = images.contiguous()
+        logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
+        self.generation += 1
+        self._fwd_x16 = False
+        native.check(self.lib.qatvit_float_student_forward_observe(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
+                                                                   self.f_workspace.data_ptr(), self.observe_buf.data_ptr(), native.stream_ptr()),
+                     "qatvit_float_student_forward_observe")
+        return logits
+
+    def backward_observe(self, dlogits: torch.Tensor, c: native.Cfg) -> List[torch.Tensor]:
+        """The float step's backward (every STE mask is 1: the gradient stock computes); in a data-parallel group one average of the whole flat
+        gradient afterwards."""
+        flat, views, gptr = self._grad_buffers()
+        native.check(self.lib.qatvit_float_student_backward(ctypes.byref(c), self._ptr_params, dlogits.contiguous().data_ptr(), gptr,
+                                                            self.f_workspace.data_ptr(), native.stream_ptr()), "qatvit_float_student_backward")
+        if self.pg is not None:
+            if dist.get_backend(self.pg) == "nccl":
+                dist.all_reduce(flat, op=dist.ReduceOp.AVG, group=self.pg)
+            else:                                # gloo has no AVG
+                dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.pg)
+                flat.div_(dist.get_world_size(self.pg))
+        return views
 
     def _grad_buffers(self):
         flat = torch.zeros(self.grad_numel, dtype=torch.float32, device=self.device)
@@ -556,6 +697,7 @@ class _StudentStep(torch.autograd.Function):
         ctx.generation = engine.generation
         ctx.step_cfg = engine.cfg
         ctx.x16 = engine._fwd_x16
+        ctx.mode = engine.fq_mode
         return out
 
     @staticmethod
@@ -575,7 +717,10 @@ class _StudentStep(torch.autograd.Function):
                 "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
                 "forward/backward per micro-batch)."
             )
-        grads = eng.backward(dlogits, ctx.step_cfg, ctx.x16)
+        if ctx.mode == OBSERVE:
+            grads = eng.backward_observe(dlogits, ctx.step_cfg)
+        else:
+            grads = eng.backward(dlogits, ctx.step_cfg, ctx.x16)
         for p, g in zip(eng.params, grads):
             if p.grad is None:
                 p.grad = g

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import functional as F
-from .engine import engine_of
+from .engine import QAT, engine_of, fq_flags_and_names
 
 
 class GraphedStudentStep:
@@ -21,6 +21,10 @@ class GraphedStudentStep:
                  kd_alpha: float = 0.5, label_smoothing: float = 0.1, warmup: int = 2):
         if not images.is_cuda:
             raise RuntimeError("GraphedStudentStep runs on MI355X only")
+        flags, _ = fq_flags_and_names(model)
+        if not bool((torch.stack([t.reshape(-1)[0] for t in flags]) != 0).all()):
+            raise RuntimeError("GraphedStudentStep: fake-quant is disabled (torch.ao.quantization.disable_fake_quant); the observe-only step is not "
+                               "captured - run it eagerly, or enable fake-quant on every module before capturing")
         self.model = model
         self.x = images.clone()
         self.y = labels.clone()
@@ -35,6 +39,10 @@ class GraphedStudentStep:
         eng = engine_of(model)
         if eng is None or eng.pg is not None:
             raise RuntimeError("GraphedStudentStep: needs a prepared single-GPU student (no data-parallel group)")
+        if eng.fq_mode != QAT:
+            raise RuntimeError("GraphedStudentStep: the observe-only step (fake-quant disabled) is not captured")
+        # a replay does not pass through the engine's per-forward mode decision: the fake-quant flags must stay as they were at capture
+        self._fq_versions = eng.fq_versions()
         # the graph records raw addresses of the engine's workspace and fake-quant arena: keep the engine alive and pin its workspace
         # (a later, larger batch would otherwise re-allocate it under the graph)
         self.engine = eng
@@ -83,6 +91,9 @@ class GraphedStudentStep:
             raise RuntimeError("GraphedStudentStep: closed")
         if engine_of(self.model) is not self.engine:
             raise RuntimeError("GraphedStudentStep: the model was re-bound to another native engine after capture; capture again")
+        if self.engine.fq_versions() != self._fq_versions:
+            raise RuntimeError("GraphedStudentStep: the fake-quant flags changed since capture (enable_fake_quant / disable_fake_quant); the graph "
+                               "replays the quantised step - run the step eagerly, or capture again with fake-quant on")
         if images.shape != self.x.shape:
             raise RuntimeError(f"GraphedStudentStep was captured for batch shape {tuple(self.x.shape)}, got {tuple(images.shape)}")
         self.x.copy_(images)
