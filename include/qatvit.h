@@ -369,6 +369,24 @@ int64_t qatvit_float_student_observe_bytes(const qatvit_cfg* cfg);
 int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* act_fq, const qatvit_fq* weight_fq, void* observe, void* stream);
 int qatvit_float_student_forward_observe(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* observe,
                                          void* stream);
+/* fp16 (autocast) form: what the step computes inside torch.autocast("cuda", dtype=torch.float16), following stock autocast.  Every GEMM operand is
+ * ONE fp16 plane (the weights are re-cast by every forward, as stored and transposed), one v_mfma_f32_16x16x32_f16 pass per product, fp32 accumulate;
+ * the residual stream, LayerNorm, softmax statistics and lse stay fp32, GEMM outputs are kept in fp32.  Overflow follows stock: every tensor stock
+ * holds in fp16 overflows to +-inf where it is rounded to fp16, and the Linear / Conv2d weight and bias gradients (fp16 in stock) become +-inf
+ * where |g| exceeds fp16's range - so GradScaler skips the same kinds of steps.  Limits: those of the fp32 form, plus embed_dim and mlp_hidden
+ * multiples of 384.  Separate workspace (smaller than the fp32 form's), sized and initialised like it.
+ *  forward: logits_f16 = [batch, num_classes] fp16.  backward: dlogits_f16 = [batch, num_classes] fp16; grads as qatvit_float_student_backward
+ *  (fp32, ZERO on entry). */
+int64_t qatvit_float_student_amp_workspace_bytes(const qatvit_cfg* cfg);
+int qatvit_float_student_amp_init(const qatvit_cfg* cfg, void* workspace, void* stream);
+int qatvit_float_student_amp_forward(const qatvit_cfg* cfg, void* const* params, const float* images, void* logits_f16, void* workspace, void* stream);
+int qatvit_float_student_amp_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_f16, void* const* grads, void* workspace,
+                                      void* stream);
+/* The fp16 form's attention backward alone (kernel-level checks): qkv fp32 [B*T, 3*D], O16 fp16 [B*T, D], lse fp32 [B][H][T] (natural log of the
+ * softmax denominator of the scaled scores), dO fp32 [B*T, D] -> dqkv16 fp16 [B*T, 3*D] (dQ, dK, dV in the qkv layout).  qkv and dO are rounded
+ * to fp16 on load.  One fused kernel, one workgroup per (image, head); head_dim 32 or 64, T <= 224. */
+int qatvit_float_student_amp_attn_backward(const float* qkv, const void* O16, const float* lse, const float* dO, int32_t B, int32_t T, int32_t H,
+                                           int32_t D, void* dqkv16, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Integer inference forward of the trained student from its exported integers.

@@ -1,0 +1,626 @@
+// Float (pre-QAT) student step, fp16 form: what the step computes inside torch.autocast("cuda", dtype=torch.float16), native on gfx950.
+//
+// Replaces: the reference's autocast float epochs (the Optuna objective: autocast + GradScaler before prepare_qat).  Stock autocast runs every
+// Linear / Conv2d / matmul on fp16 operands with fp32 accumulation and keeps the residual stream, LayerNorm and softmax in fp32; this form does
+// the same with one fp16 plane per GEMM operand and one v_mfma_f32_16x16x32_f16 pass per product:
+//   forward   the teacher's one-pass fp16 pieces (k_patches_split / k_resid_ln_split / k_attn_fwd_float with f16), keeping LayerNorm mean / rstd,
+//             lse, the fc1 pre-activation and the fp16 activation planes the weight gradients read; GEMM outputs stay fp32; fp16 logits.
+//   backward  dgrad = launch_gemm_nt_dy16 and wgrad = launch_gemm_tn_dy16 with unit scales; the LayerNorm backward of the float step (its fused
+//             next-branch output as one fp16 plane); new here: the head, GELU', embedding and attention backward in their fp16 forms.
+// Overflow follows stock (GradScaler must skip the same steps): every tensor stock holds in fp16 is rounded to nearest (fp16 overflow -> +-inf,
+// NaN propagates) where it becomes fp16 - dlogits, dhn, the fc2 dgrad output, dO, dP, dS, dQKV, dY0 - and the
+// Linear / Conv2d weight and bias gradients (fp16 tensors under stock autocast, fp32 sums here) take one post-pass: |g| beyond fp16's range -> +-inf.
+#include "../../include/qatvit.h"
+
+#include "qv_common.h"
+#include "qv_kernels.h"
+
+namespace qv {
+
+typedef _Float16 fa_f16x8 __attribute__((ext_vector_type(8)));
+typedef float fa_f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ inline float f16r(float v) { return (float)(_Float16)v; }   // round to fp16 and back (RNE: beyond 65520 -> inf)
+
+// ---------------------------------------------------------------- weights as fp16, as stored and transposed (one launch per step)
+struct FaWTab {
+    const float* W[kMaxW];
+    _Float16* w[kMaxW];
+    _Float16* wT[kMaxW];
+    int N[kMaxW], K[kMaxW], blk0[kMaxW + 1];
+    int n;
+};
+__global__ __launch_bounds__(256) void k_fa_wcast(const FaWTab t) {
+    __shared__ float tile[32][33];
+    int wi = 0;
+    while (wi + 1 < t.n && (int)blockIdx.x >= t.blk0[wi + 1]) ++wi;
+    const int N = t.N[wi], K = t.K[wi], tilesK = (K + 31) / 32, local = (int)blockIdx.x - t.blk0[wi];
+    const int n0 = (local / tilesK) * 32, k0 = (local % tilesK) * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int n = n0 + ty + 8 * i, k = k0 + tx;
+        float v = 0.f;
+        if (n < N && k < K) {
+            v = t.W[wi][(int64_t)n * K + k];
+            t.w[wi][(int64_t)n * K + k] = (_Float16)v;
+        }
+        tile[ty + 8 * i][tx] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = k0 + ty + 8 * i, n = n0 + tx;
+        if (n < N && k < K) t.wT[wi][(int64_t)k * N + n] = (_Float16)tile[tx][ty + 8 * i];
+    }
+}
+
+// ---------------------------------------------------------------- head: cls LayerNorm (fp32) -> fp16 Linear -> fp16 logits
+// hn16[b,:] = fp16(LN(x[b,0,:])) (kept as fp32 values for the backward); logits[b,c] = fp16(hn16[b,:] . fp16(W[c,:]) + fp16(bias[c]))
+__global__ __launch_bounds__(256) void k_fa_head_fwd(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ W,
+                                                     const float* __restrict__ bias, float* __restrict__ hn, _Float16* __restrict__ logits, int D, int T, int C) {
+    extern __shared__ float sh[];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row = (int64_t)b * T;
+    const float mu = mean[row], rs = rstd[row];
+    for (int c = threadIdx.x; c < D; c += 256) {
+        const float v = f16r((x[row * D + c] - mu) * rs * gamma[c] + beta[c]);
+        sh[c] = v;
+        hn[(int64_t)b * D + c] = v;
+    }
+    __syncthreads();
+    for (int c = wave; c < C; c += 4) {
+        float acc = 0.f;
+        for (int k = lane; k < D; k += 64) acc += sh[k] * f16r(W[(int64_t)c * D + k]);
+        acc = wave_sum(acc);
+        if (lane == 0) logits[(int64_t)b * C + c] = (_Float16)(acc + f16r(bias[c]));
+    }
+}
+// one thread per output element, fixed summation order: dW[c,d] = sum_b dl[b,c] hn16[b,d]; dbias[c] = sum_b dl[b,c];
+// dhn[b,d] = fp16(sum_c dl[b,c] fp16(W[c,d]))  (stock: the fp16 Linear's input gradient)
+__global__ __launch_bounds__(256) void k_fa_head_bwd(const _Float16* __restrict__ dl, const float* __restrict__ hn, const float* __restrict__ W,
+                                                     float* __restrict__ dW, float* __restrict__ dbias, float* __restrict__ dhn, int B, int D, int C) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const int64_t nW = (int64_t)C * D, nH = (int64_t)B * D;
+    if (i < nW) {
+        const int c = (int)(i / D), d = (int)(i % D);
+        float a0 = 0.f, a1 = 0.f;
+        int b = 0;
+        for (; b + 1 < B; b += 2) {
+            a0 += (float)dl[(int64_t)b * C + c] * hn[(int64_t)b * D + d];
+            a1 += (float)dl[(int64_t)(b + 1) * C + c] * hn[(int64_t)(b + 1) * D + d];
+        }
+        if (b < B) a0 += (float)dl[(int64_t)b * C + c] * hn[(int64_t)b * D + d];
+        dW[i] = a0 + a1;
+    } else if (i < nW + nH) {
+        const int64_t j = i - nW;
+        const int b = (int)(j / D), d = (int)(j % D);
+        float a = 0.f;
+        for (int c = 0; c < C; ++c) a += (float)dl[(int64_t)b * C + c] * f16r(W[(int64_t)c * D + d]);
+        dhn[j] = f16r(a);
+    } else if (i < nW + nH + C) {
+        const int c = (int)(i - nW - nH);
+        float a = 0.f;
+        for (int b = 0; b < B; ++b) a += (float)dl[(int64_t)b * C + c];
+        dbias[c] = a;
+    }
+}
+
+// ---------------------------------------------------------------- elementwise
+// G16 = fp16(gelu(Y1))  (the fc2 forward operand and its weight-gradient operand)
+__global__ __launch_bounds__(256) void k_fa_gelu(const float* __restrict__ Y, _Float16* __restrict__ G, int64_t n4) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 v = reinterpret_cast<const float4*>(Y)[i];
+        *reinterpret_cast<uint2*>(G + i * 4) = make_uint2(pk_f16(gelu_fwd(v.x), gelu_fwd(v.y)), pk_f16(gelu_fwd(v.z), gelu_fwd(v.w)));
+    }
+}
+// dY1_16 = fp16(fp16(dG) * gelu'(Y1)),  gelu'(x) = Phi(x) + x phi(x)
+__device__ inline float gelu_grad(float x) {
+    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * __expf(-0.5f * x * x);
+}
+__global__ __launch_bounds__(256) void k_fa_gelu_bwd(const float* __restrict__ dG, const float* __restrict__ Y, _Float16* __restrict__ out, int64_t n4) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 g = reinterpret_cast<const float4*>(dG)[i];
+        const float4 y = reinterpret_cast<const float4*>(Y)[i];
+        *reinterpret_cast<uint2*>(out + i * 4) = make_uint2(pk_f16(f16r(g.x) * gelu_grad(y.x), f16r(g.y) * gelu_grad(y.y)),
+                                                            pk_f16(f16r(g.z) * gelu_grad(y.z), f16r(g.w) * gelu_grad(y.w)));
+    }
+}
+// embedding backward: dpos[t,:] = sum_b dx[b,t,:], dcls = dpos[0,:] (fp32, fixed order); dY0_16[b*np + t-1, :] = fp16(dx[b,t,:]) for t >= 1
+__global__ __launch_bounds__(64) void k_fa_embed_bwd(const float* __restrict__ dx, float* __restrict__ dpos, float* __restrict__ dcls, _Float16* __restrict__ dY0,
+                                                     int B, int T, int D) {
+    const int d4 = D / 4;
+    const int64_t n4 = (int64_t)T * d4;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const int t = (int)(i / d4), c = (int)(i % d4) * 4;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int b = 0; b < B; ++b) {
+            const float4 g = *reinterpret_cast<const float4*>(dx + ((int64_t)b * T + t) * D + c);
+            acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w;
+            if (t > 0) *reinterpret_cast<uint2*>(dY0 + ((int64_t)b * (T - 1) + (t - 1)) * D + c) = make_uint2(pk_f16(g.x, g.y), pk_f16(g.z, g.w));
+        }
+        *reinterpret_cast<float4*>(dpos + (int64_t)t * D + c) = acc;
+        if (t == 0) *reinterpret_cast<float4*>(dcls + c) = acc;
+    }
+}
+// the overflow rule of the fp16 weight / bias gradients: g -> fp16(g) where that is +-inf (NaN stays NaN); every other value keeps its fp32 sum
+constexpr int kFaMaxG = 2 + 8 * 12 + 2;
+struct FaInfTab { float* g[kFaMaxG]; int64_t n[kFaMaxG]; int count; };
+__global__ __launch_bounds__(256) void k_fa_inf_rule(const FaInfTab t) {
+    const int k = blockIdx.y;
+    float* g = t.g[k];
+    const int64_t n = t.n[k];
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = g[i], r = f16r(v);
+        if (__builtin_isinf(r)) g[i] = r;
+    }
+}
+
+// ---------------------------------------------------------------- attention backward on fp16 MFMA, fused: one workgroup per (image, head)
+// With s = head_dim^-0.5 and the forward's lse, per (image, head):
+//   P = exp(s Q K^T - lse)    dP = fp16(dO V^T)    dS = fp16(P * (dP - delta)),  delta_i = fp16(dO_i) . O16_i
+//   dQ = fp16(s dS K)    dK = fp16(s dS^T Q)    dV = fp16(fp16(P)^T dO)
+// The head's Q, K, V and dO (rounded to fp16, as stock holds them) are staged once into LDS as [token][HD + 8] rows, tokens padded to Tp = T rounded
+// up to 32 (zero rows; padded queries and keys are masked to P = 0).  P and dS never leave the chip: each wave takes 16-key tiles and sweeps the
+// queries in chunks of 32 - S^T and dP^T as v_mfma_f32_16x16x32_f16 tiles (keys on the rows), P and dS rounded to fp16 into a per-wave 16 x 32 LDS
+// scratch, read back as the A fragment of dV += P^T dO and dK += dS^T Q - then takes 16-query tiles and recomputes S, dP, dS with the queries on the
+// rows for dQ += dS K (the dK / dV sweep cannot hand its dS to dQ without a [T, T] plane).  The B fragments of those three products run over tokens
+// at a fixed feature: eight 2-byte LDS reads each.  MFMA 16x16x32 layout: A fragment lane l = row l % 16, k 8 (l / 16) .. + 7; B the same with the
+// column; accumulator e of lane l = row 4 (l / 16) + e, column l % 16.
+constexpr int kFaWaves = 8, kFaScr = 40;   // scratch row stride in fp16 (32 + 8: 16-B aligned rows)
+__device__ inline void fa_wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }   // LDS is in order per wave; stop the compiler reordering
+template <int HD>
+__device__ inline fa_f16x8 fa_col8(const _Float16* s, int row0, int col) {   // s[(row0 + j) * (HD + 8) + col], j = 0..7
+    fa_f16x8 v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = s[(row0 + j) * (HD + 8) + col];
+    return v;
+}
+template <int HD>
+__global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float* __restrict__ qkv, const _Float16* __restrict__ O16, const float* __restrict__ lse,
+                                                                    const float* __restrict__ dO, int T, int H, int D, float scale, _Float16* __restrict__ dqkv) {
+    constexpr int LDH = HD + 8, CH = HD / 8, KK = HD / 32, ND = HD / 16;
+    const int Tp = (T + 31) & ~31;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    _Float16* sQ = reinterpret_cast<_Float16*>(smem);
+    _Float16* sK = sQ + Tp * LDH;
+    _Float16* sV = sK + Tp * LDH;
+    _Float16* sD = sV + Tp * LDH;   // dO
+    float* sL = reinterpret_cast<float*>(sD + Tp * LDH);
+    float* sDel = sL + Tp;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    _Float16* scrP = reinterpret_cast<_Float16*>(sDel + Tp) + wave * 2 * 16 * kFaScr;
+    _Float16* scrS = scrP + 16 * kFaScr;
+    const int b = blockIdx.x / H, h = blockIdx.x % H, ld = 3 * D;
+    const int64_t row0 = (int64_t)b * T;
+    for (int i = threadIdx.x; i < Tp * CH; i += kFaWaves * 64) {   // staging: 8 features of one token per thread
+        const int t = i / CH, c = (i % CH) * 8;
+        fa_f16x8 q, k, v, d;
+        if (t < T) {
+            const float* src = qkv + (row0 + t) * ld + h * HD + c;
+            const float* ds = dO + (row0 + t) * D + h * HD + c;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { q[j] = (_Float16)src[j]; k[j] = (_Float16)src[D + j]; v[j] = (_Float16)src[2 * D + j]; d[j] = (_Float16)ds[j]; }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) q[j] = k[j] = v[j] = d[j] = (_Float16)0.f;
+        }
+        *reinterpret_cast<fa_f16x8*>(sQ + t * LDH + c) = q;
+        *reinterpret_cast<fa_f16x8*>(sK + t * LDH + c) = k;
+        *reinterpret_cast<fa_f16x8*>(sV + t * LDH + c) = v;
+        *reinterpret_cast<fa_f16x8*>(sD + t * LDH + c) = d;
+    }
+    for (int t = threadIdx.x; t < Tp; t += kFaWaves * 64) sL[t] = t < T ? lse[((int64_t)b * H + h) * T + t] : 0.f;
+    __syncthreads();
+    for (int t = threadIdx.x; t < Tp; t += kFaWaves * 64) {   // delta from the staged fp16 dO and the forward's fp16 O
+        float a = 0.f;
+        if (t < T) {
+            const _Float16* o = O16 + (row0 + t) * D + h * HD;
+#pragma unroll
+            for (int c = 0; c < HD; c += 8) {
+                const fa_f16x8 ov = *reinterpret_cast<const fa_f16x8*>(o + c);
+                const fa_f16x8 dv = *reinterpret_cast<const fa_f16x8*>(sD + t * LDH + c);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a += (float)dv[j] * (float)ov[j];
+            }
+        }
+        sDel[t] = a;
+    }
+    __syncthreads();
+    const int ntile = Tp / 16;
+    // ---- dK, dV: 16 keys per wave tile, the queries in chunks of 32
+    for (int kt = wave; kt < ntile; kt += kFaWaves) {
+        const int k0 = kt * 16;
+        fa_f32x4 dV[ND], dK[ND];
+#pragma unroll
+        for (int jd = 0; jd < ND; ++jd) dV[jd] = dK[jd] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int qc = 0; qc < Tp; qc += 32) {
+            fa_f32x4 st[2], dpt[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                st[u] = dpt[u] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) {
+                    const int c = 32 * kk + 8 * g, qr = qc + 16 * u + r;
+                    st[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sK + (k0 + r) * LDH + c),
+                                                                   *reinterpret_cast<const fa_f16x8*>(sQ + qr * LDH + c), st[u], 0, 0, 0);
+                    dpt[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sV + (k0 + r) * LDH + c),
+                                                                    *reinterpret_cast<const fa_f16x8*>(sD + qr * LDH + c), dpt[u], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int q = qc + 16 * u + r;
+                const float lq = sL[q], dq = sDel[q];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int key = k0 + 4 * g + e;
+                    const float p = (q < T && key < T) ? __expf(scale * st[u][e] - lq) : 0.f;
+                    scrP[(4 * g + e) * kFaScr + 16 * u + r] = (_Float16)p;
+                    scrS[(4 * g + e) * kFaScr + 16 * u + r] = (_Float16)(p * (f16r(dpt[u][e]) - dq));
+                }
+            }
+            fa_wave_lds_fence();
+            const fa_f16x8 ap = *reinterpret_cast<const fa_f16x8*>(scrP + r * kFaScr + 8 * g);
+            const fa_f16x8 as = *reinterpret_cast<const fa_f16x8*>(scrS + r * kFaScr + 8 * g);
+#pragma unroll
+            for (int jd = 0; jd < ND; ++jd) {
+                dV[jd] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ap, fa_col8<HD>(sD, qc + 8 * g, 16 * jd + r), dV[jd], 0, 0, 0);
+                dK[jd] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as, fa_col8<HD>(sQ, qc + 8 * g, 16 * jd + r), dK[jd], 0, 0, 0);
+            }
+            fa_wave_lds_fence();
+        }
+#pragma unroll
+        for (int jd = 0; jd < ND; ++jd)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int key = k0 + 4 * g + e;
+                if (key < T) {
+                    _Float16* o = dqkv + (row0 + key) * ld + h * HD + 16 * jd + r;
+                    o[D] = (_Float16)(scale * dK[jd][e]);
+                    o[2 * D] = (_Float16)dV[jd][e];
+                }
+            }
+    }
+    // ---- dQ: 16 queries per wave tile, S / dP / dS recomputed with the queries on the rows, the keys in chunks of 32
+    for (int qt = wave; qt < ntile; qt += kFaWaves) {
+        const int q0 = qt * 16;
+        fa_f32x4 dQ[ND];
+#pragma unroll
+        for (int jd = 0; jd < ND; ++jd) dQ[jd] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+        float lq[4], dq[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { lq[e] = sL[q0 + 4 * g + e]; dq[e] = sDel[q0 + 4 * g + e]; }
+        for (int kc = 0; kc < Tp; kc += 32) {
+            fa_f32x4 s[2], dp[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                s[u] = dp[u] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) {
+                    const int c = 32 * kk + 8 * g, kr = kc + 16 * u + r;
+                    s[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sQ + (q0 + r) * LDH + c),
+                                                                  *reinterpret_cast<const fa_f16x8*>(sK + kr * LDH + c), s[u], 0, 0, 0);
+                    dp[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sD + (q0 + r) * LDH + c),
+                                                                   *reinterpret_cast<const fa_f16x8*>(sV + kr * LDH + c), dp[u], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int key = kc + 16 * u + r;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int q = q0 + 4 * g + e;
+                    const float p = (q < T && key < T) ? __expf(scale * s[u][e] - lq[e]) : 0.f;
+                    scrS[(4 * g + e) * kFaScr + 16 * u + r] = (_Float16)(p * (f16r(dp[u][e]) - dq[e]));
+                }
+            }
+            fa_wave_lds_fence();
+            const fa_f16x8 as = *reinterpret_cast<const fa_f16x8*>(scrS + r * kFaScr + 8 * g);
+#pragma unroll
+            for (int jd = 0; jd < ND; ++jd)
+                dQ[jd] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as, fa_col8<HD>(sK, kc + 8 * g, 16 * jd + r), dQ[jd], 0, 0, 0);
+            fa_wave_lds_fence();
+        }
+#pragma unroll
+        for (int jd = 0; jd < ND; ++jd)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int q = q0 + 4 * g + e;
+                if (q < T) dqkv[(row0 + q) * ld + h * HD + 16 * jd + r] = (_Float16)(scale * dQ[jd][e]);
+            }
+    }
+}
+
+static size_t fa_attn_lds_bytes(int T, int HD) {
+    const size_t Tp = (size_t)((T + 31) & ~31);
+    return 4 * Tp * (HD + 8) * 2 + 2 * Tp * 4 + (size_t)kFaWaves * 2 * 16 * kFaScr * 2;
+}
+template <int HD>
+static void launch_fa_attn_fused(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st) {
+    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_fa_attn_bwd_fused<HD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  (int)fa_attn_lds_bytes(224, HD)),
+                        true);
+    (void)once;
+    k_fa_attn_bwd_fused<HD><<<B * H, kFaWaves * 64, fa_attn_lds_bytes(T, HD), st>>>(qkv, reinterpret_cast<const _Float16*>(O16), lse, dO, T, H, D,
+                                                                                    1.0f / sqrtf((float)HD), reinterpret_cast<_Float16*>(dqkv16));
+}
+
+int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st) {
+    const int hd = H > 0 ? D / H : 0;
+    if (B < 1 || H < 1 || D % H != 0 || (hd != 64 && hd != 32) || T < 1 || T > 224 || !qkv || !O16 || !lse || !dO || !dqkv16) {
+        set_error("attn_bwd_f16: unsupported arguments B=%d T=%d H=%d D=%d (head_dim 32 or 64, T <= 224)", B, T, H, D);
+        return 1;
+    }
+    if (hd == 64) launch_fa_attn_fused<64>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
+    else launch_fa_attn_fused<32>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
+    return 0;
+}
+
+// the disabled quantiser {1, 1, 0, 0} (its first word is also the unit scale of the one-plane GEMMs) and the all-ones STE mask
+__global__ void k_fa_consts(float* qp_off, uint32_t* ones, int64_t nwords) {
+    const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i0 == 0) { qp_off[0] = 1.f; qp_off[1] = 1.f; qp_off[2] = 0.f; qp_off[3] = 0.f; }
+    for (int64_t i = i0; i < nwords; i += (int64_t)gridDim.x * blockDim.x) ones[i] = 0xffffffffu;
+}
+
+static int flat_grid_fa(int64_t n) {
+    int64_t b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
+
+}  // namespace qv
+
+using namespace qv;
+
+extern "C" {
+
+// Workspace: a batch-independent head (constants, the fp16 weight planes, the weight-gradient scratch) and the batch-sized rest.
+struct FaBlock { int64_t x, xm, h1, h2, mean1, rstd1, mean2, rstd2, qkv, O, lse, Y1, G; };
+struct FaPlan {
+    int64_t qp_off, amax, w16[kMaxW], w16T[kMaxW], tn_partial;
+    int64_t ones, p16, Y0, x_last, meanf, rstdf, hf, hn;
+    FaBlock blk[12];
+    int64_t Y, dx, dx2, dp, dG, dY1, dh, dO, dqkv, dhn, dY0;
+    int64_t ones_words, total;
+};
+static int fa_check(const qatvit_cfg& c) {
+    const int hd = c.num_heads > 0 ? c.embed_dim / c.num_heads : 0;
+    const int np = c.patch_size > 0 ? (c.img_size / c.patch_size) * (c.img_size / c.patch_size) : 0;
+    if (c.batch < 1 || c.depth < 1 || c.depth > 12 || c.embed_dim % 384 != 0 || c.embed_dim > 768 || c.mlp_hidden % 384 != 0 || c.num_heads < 1 ||
+        c.embed_dim % c.num_heads != 0 || (hd != 32 && hd != 64) || c.patch_size % 4 != 0 || c.img_size % c.patch_size != 0 || np + 1 > 224 ||
+        (c.in_chans * c.patch_size * c.patch_size) % 128 != 0 || c.num_classes < 1) {
+        set_error("float student amp: unsupported config (batch %d depth %d dim %d hidden %d heads %d img %d patch %d): needs dim and hidden multiples "
+                  "of 384, dim <= 768, head_dim 32 or 64, <= 224 tokens, depth <= 12", c.batch, c.depth, c.embed_dim, c.mlp_hidden, c.num_heads, c.img_size,
+                  c.patch_size);
+        return 1;
+    }
+    return 0;
+}
+static void fa_weight_shape(const qatvit_cfg& c, int wi, int* N, int* K) {
+    const int D = c.embed_dim, Hd = c.mlp_hidden;
+    if (wi == 0) { *N = D; *K = c.in_chans * c.patch_size * c.patch_size; return; }
+    switch ((wi - 1) % 4) {
+        case 0: *N = 3 * D; *K = D; break;
+        case 1: *N = D; *K = D; break;
+        case 2: *N = Hd; *K = D; break;
+        default: *N = D; *K = Hd; break;
+    }
+}
+static FaPlan fa_plan(const qatvit_cfg& c) {
+    FaPlan p{};
+    int64_t o = 0;
+    auto take = [&](int64_t b) { int64_t r = o; o += (b + 255) & ~(int64_t)255; return r; };
+    const int64_t np = (int64_t)(c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, B = c.batch, M = B * T, D = c.embed_dim,
+                  Hd = c.mlp_hidden, H = c.num_heads, Kpe = (int64_t)c.in_chans * c.patch_size * c.patch_size;
+    p.qp_off = take(16);
+    p.amax = take((int64_t)kDyAmaxSlots * kDyAmaxStride * 4);
+    for (int wi = 0; wi < 1 + 4 * c.depth; ++wi) {
+        int N, K;
+        fa_weight_shape(c, wi, &N, &K);
+        p.w16[wi] = take((int64_t)N * K * 2);
+        p.w16T[wi] = take((int64_t)N * K * 2);
+    }
+    p.tn_partial = take(kTnScratchBytes);
+    p.ones_words = ln_maskbits_bytes(M, (int)D) / 4;
+    p.ones = take(ln_maskbits_bytes(M, (int)D));
+    p.p16 = take(B * np * Kpe * 2);
+    p.Y0 = take(B * np * D * 4);
+    for (int i = 0; i < c.depth; ++i) {
+        FaBlock& k = p.blk[i];
+        k.x = take(M * D * 4); k.xm = take(M * D * 4);
+        k.h1 = take(M * D * 2); k.h2 = take(M * D * 2);
+        k.mean1 = take(M * 4); k.rstd1 = take(M * 4); k.mean2 = take(M * 4); k.rstd2 = take(M * 4);
+        k.qkv = take(M * 3 * D * 4);
+        k.O = take(M * D * 2);
+        k.lse = take(B * H * T * 4);
+        k.Y1 = take(M * Hd * 4);
+        k.G = take(M * Hd * 2);
+    }
+    p.x_last = take(M * D * 4);
+    p.meanf = take(M * 4); p.rstdf = take(M * 4);
+    p.hf = take(M * D * 2);
+    p.hn = take(B * D * 4);
+    p.Y = take(M * D * 4);
+    p.dx = take(M * D * 4); p.dx2 = take(M * D * 4);
+    p.dp = take(M * D * 2);
+    p.dG = take(M * Hd * 4);
+    p.dY1 = take(M * Hd * 2);
+    p.dh = take(M * D * 4);
+    p.dO = take(M * D * 4);
+    p.dqkv = take(M * 3 * D * 2);
+    p.dhn = take(B * D * 4);
+    p.dY0 = take(B * np * D * 2);
+    p.total = o;
+    return p;
+}
+
+int64_t qatvit_float_student_amp_workspace_bytes(const qatvit_cfg* cfg) {
+    if (!cfg) { set_error("qatvit_float_student_amp_workspace_bytes: null argument"); return -1; }
+    if (fa_check(*cfg)) return -1;
+    return fa_plan(*cfg).total;
+}
+
+static void fa_consts(const FaPlan& p, char* ws, hipStream_t st) {
+    k_fa_consts<<<flat_grid_fa(p.ones_words), 256, 0, st>>>(reinterpret_cast<float*>(ws + p.qp_off), reinterpret_cast<uint32_t*>(ws + p.ones), p.ones_words);
+}
+
+int qatvit_float_student_amp_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
+    QV_CHECK_ARG(cfg && workspace, "qatvit_float_student_amp_init: null argument");
+    if (fa_check(*cfg)) return 1;
+    fa_consts(fa_plan(*cfg), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_float_student_amp_init");
+    return 0;
+}
+
+int qatvit_float_student_amp_forward(const qatvit_cfg* cfg, void* const* params, const float* images, void* logits_f16, void* workspace, void* stream) {
+    QV_CHECK_ARG(cfg && params && images && logits_f16 && workspace, "qatvit_float_student_amp_forward: null argument");
+    if (fa_check(*cfg)) return 1;
+    const qatvit_cfg& c = *cfg;
+    const FaPlan p = fa_plan(c);
+    char* ws = reinterpret_cast<char*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden;
+    const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth;
+    const int64_t M = (int64_t)c.batch * T;
+    auto F = [&](int64_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto V = [&](int64_t off) { return reinterpret_cast<void*>(ws + off); };
+    auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
+    auto bprm = [&](int blk, int k) { return prm(4 + 12 * blk + k); };
+    fa_consts(p, ws, st);
+    {   // the weights as fp16, as stored and transposed, in one launch
+        FaWTab t{};
+        t.n = 1 + 4 * L;
+        int blocks = 0;
+        for (int wi = 0; wi < t.n; ++wi) {
+            fa_weight_shape(c, wi, &t.N[wi], &t.K[wi]);
+            static const int kW[4] = {2, 4, 8, 10};   // qkv, proj, fc1, fc2 weights within a block's 12 parameters
+            t.W[wi] = wi == 0 ? prm(0) : bprm((wi - 1) / 4, kW[(wi - 1) % 4]);
+            t.w[wi] = reinterpret_cast<_Float16*>(ws + p.w16[wi]);
+            t.wT[wi] = reinterpret_cast<_Float16*>(ws + p.w16T[wi]);
+            t.blk0[wi] = blocks;
+            blocks += ((t.N[wi] + 31) / 32) * ((t.K[wi] + 31) / 32);
+        }
+        t.blk0[t.n] = blocks;
+        k_fa_wcast<<<blocks, 256, 0, st>>>(t);
+    }
+    // one fp16 pass per GEMM, fp32 output + fp32 bias
+    auto gemm = [&](int64_t a16, int wi, const float* bias, float* C, int N, int K, int Mrows) {
+        return launch_gemm_nt(V(a16), nullptr, V(p.w16[wi]), C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, nullptr, 1, st, nullptr, nullptr, true);
+    };
+    launch_patches_split(images, V(p.p16), nullptr, c.batch, c.in_chans, c.img_size, c.img_size, c.patch_size, st, 1);
+    if (gemm(p.p16, 0, prm(1), F(p.Y0), D, Kpe, c.batch * np)) return 1;
+    launch_resid_ln_split_save(0, nullptr, F(p.Y0), prm(2), prm(3), F(p.blk[0].x), bprm(0, 0), bprm(0, 1), c.ln_eps, V(p.blk[0].h1), nullptr, F(p.blk[0].mean1),
+                               F(p.blk[0].rstd1), M, D, T, st, nullptr, 1);
+    for (int i = 0; i < L; ++i) {
+        const FaBlock& k = p.blk[i];
+        const int w0 = 1 + 4 * i;
+        if (gemm(k.h1, w0 + 0, bprm(i, 3), F(k.qkv), 3 * D, D, (int)M)) return 1;
+        if (launch_attn_fwd_float(F(k.qkv), c.batch, T, c.num_heads, D, V(k.O), nullptr, st, 1, F(k.lse))) return 1;
+        if (gemm(k.O, w0 + 1, bprm(i, 5), F(p.Y), D, D, (int)M)) return 1;
+        launch_resid_ln_split_save(1, F(k.x), F(p.Y), nullptr, nullptr, F(k.xm), bprm(i, 6), bprm(i, 7), c.ln_eps, V(k.h2), nullptr, F(k.mean2), F(k.rstd2), M, D, T,
+                                   st, nullptr, 1);
+        if (gemm(k.h2, w0 + 2, bprm(i, 9), F(k.Y1), Hd, D, (int)M)) return 1;
+        k_fa_gelu<<<flat_grid_fa(M * Hd / 4), 256, 0, st>>>(F(k.Y1), reinterpret_cast<_Float16*>(ws + k.G), M * Hd / 4);
+        if (gemm(k.G, w0 + 3, bprm(i, 11), F(p.Y), D, Hd, (int)M)) return 1;
+        const bool last = i + 1 == L;
+        const FaBlock* nx = last ? nullptr : &p.blk[i + 1];
+        launch_resid_ln_split_save(1, F(k.xm), F(p.Y), nullptr, nullptr, last ? F(p.x_last) : F(nx->x), last ? prm(4 + 12 * L) : bprm(i + 1, 0),
+                                   last ? prm(4 + 12 * L + 1) : bprm(i + 1, 1), c.ln_eps, last ? V(p.hf) : V(nx->h1), nullptr, last ? F(p.meanf) : F(nx->mean1),
+                                   last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, nullptr, 1);
+    }
+    const int hb = 4 + 12 * L;
+    k_fa_head_fwd<<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3), F(p.hn),
+                                                          reinterpret_cast<_Float16*>(logits_f16), D, T, c.num_classes);
+    QV_CHECK_LAUNCH("qatvit_float_student_amp_forward");
+    return 0;
+}
+
+int qatvit_float_student_amp_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_f16, void* const* grads, void* workspace, void* stream) {
+    QV_CHECK_ARG(cfg && params && dlogits_f16 && grads && workspace, "qatvit_float_student_amp_backward: null argument");
+    if (fa_check(*cfg)) return 1;
+    const qatvit_cfg& c = *cfg;
+    const FaPlan p = fa_plan(c);
+    char* ws = reinterpret_cast<char*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden, H = c.num_heads;
+    const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth;
+    const int64_t M = (int64_t)c.batch * T;
+    auto F = [&](int64_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto V = [&](int64_t off) { return reinterpret_cast<void*>(ws + off); };
+    auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
+    auto grd = [&](int i) { return reinterpret_cast<float*>(grads[i]); };
+    const float* qp_off = F(p.qp_off);
+    const float* one = qp_off;   // 1.0f
+    float* partial = F(p.tn_partial);
+    // dgrad: C[M, N] = dY16[M, K] . W[K, N], the transposed fp16 weight as the B operand ([N, K] row-major)
+    auto dgrad = [&](int64_t a16, int wi, float* C, int N, int K) {
+        return launch_gemm_nt_dy16(V(a16), V(p.w16T[wi]), C, (int)M, N, K, K, K, N, one, one, st);
+    };
+    // wgrad: dW[N, Kw] += dY16[Mr, N]^T . X16[Mr, Kw], dbias[N] += column sums of dY16
+    auto wgrad = [&](int64_t p16, int64_t x16, float* dW, float* db, int N, int Kw, int Mr) {
+        return launch_gemm_tn_dy16(V(p16), V(x16), nullptr, dW, Mr, N, Kw, N, Kw, Kw, one, one, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
+                                   kTnScratchBytes);
+    };
+    // the LayerNorm backward's second output: the residual gradient as the fp16 plane dp (mask all ones, unit multiplier)
+    LnBwdNext next{V(p.ones), nullptr, V(p.dp), nullptr, one, reinterpret_cast<uint32_t*>(ws + p.amax)};
+    const int hb = 4 + 12 * L;
+    {
+        const int64_t n = (int64_t)c.num_classes * D + (int64_t)c.batch * D + c.num_classes;
+        k_fa_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const _Float16*>(dlogits_f16), F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3),
+                                                              F(p.dhn), c.batch, D, c.num_classes);
+    }
+    if (launch_ln_bwd_fq(0, F(p.dhn), F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), qp_off, 0, 255, nullptr, F(p.dx), grd(hb), grd(hb + 1), M, D, T,
+                         1, st, &next))
+        return 1;
+    for (int i = L - 1; i >= 0; --i) {
+        const FaBlock& k = p.blk[i];
+        const int w0 = 1 + 4 * i, g0 = 4 + 12 * i;
+        // fc2 (input G), then GELU' on the fc1 pre-activation
+        if (wgrad(p.dp, k.G, grd(g0 + 10), grd(g0 + 11), D, Hd, (int)M)) return 1;
+        if (dgrad(p.dp, w0 + 3, F(p.dG), Hd, D)) return 1;
+        k_fa_gelu_bwd<<<flat_grid_fa(M * Hd / 4), 256, 0, st>>>(F(p.dG), F(k.Y1), reinterpret_cast<_Float16*>(ws + p.dY1), M * Hd / 4);
+        // fc1 (input h2), norm2 backward + the residual: dx2 = dx + LNbwd(dh2), and its fp16 plane for proj
+        if (wgrad(p.dY1, k.h2, grd(g0 + 8), grd(g0 + 9), Hd, D, (int)M)) return 1;
+        if (dgrad(p.dY1, w0 + 2, F(p.dh), D, Hd)) return 1;
+        if (launch_ln_bwd_fq(1, F(p.dh), F(k.xm), F(k.mean2), F(k.rstd2), prm(g0 + 6), prm(g0 + 7), qp_off, 0, 255, F(p.dx), F(p.dx2), grd(g0 + 6), grd(g0 + 7), M,
+                             D, T, 0, st, &next))
+            return 1;
+        // proj (input O), attention, qkv (input h1); norm1 backward: dx = dx2 + LNbwd(dh1)
+        if (wgrad(p.dp, k.O, grd(g0 + 4), grd(g0 + 5), D, D, (int)M)) return 1;
+        if (dgrad(p.dp, w0 + 1, F(p.dO), D, D)) return 1;
+        if (launch_attn_bwd_f16(F(k.qkv), V(k.O), F(k.lse), F(p.dO), c.batch, T, H, D, V(p.dqkv), st)) return 1;
+        if (wgrad(p.dqkv, k.h1, grd(g0 + 2), grd(g0 + 3), 3 * D, D, (int)M)) return 1;
+        if (dgrad(p.dqkv, w0 + 0, F(p.dh), D, 3 * D)) return 1;
+        if (launch_ln_bwd_fq(1, F(p.dh), F(k.x), F(k.mean1), F(k.rstd1), prm(g0 + 0), prm(g0 + 1), qp_off, 0, 255, F(p.dx2), F(p.dx), grd(g0 + 0), grd(g0 + 1), M,
+                             D, T, 0, st, i > 0 ? &next : nullptr))
+            return 1;
+    }
+    // embedding: pos / cls gradients and dY0 (the patch rows of dx) as fp16, then the patch-embedding weight gradient over the saved patches
+    k_fa_embed_bwd<<<(int)(((int64_t)T * (D / 4) + 63) / 64), 64, 0, st>>>(F(p.dx), grd(3), grd(2), reinterpret_cast<_Float16*>(ws + p.dY0), c.batch, T, D);
+    if (wgrad(p.dY0, p.p16, grd(0), grd(1), D, Kpe, c.batch * np)) return 1;
+    {   // the overflow rule of the fp16 Linear / Conv2d gradients
+        FaInfTab t{};
+        auto add = [&](int i, int64_t n) { t.g[t.count] = grd(i); t.n[t.count] = n; ++t.count; };
+        add(0, (int64_t)D * Kpe); add(1, D);
+        for (int i = 0; i < L; ++i) {
+            const int g0 = 4 + 12 * i;
+            add(g0 + 2, (int64_t)3 * D * D); add(g0 + 3, 3 * D); add(g0 + 4, (int64_t)D * D); add(g0 + 5, D);
+            add(g0 + 8, (int64_t)Hd * D); add(g0 + 9, Hd); add(g0 + 10, (int64_t)D * Hd); add(g0 + 11, D);
+        }
+        add(hb + 2, (int64_t)c.num_classes * D); add(hb + 3, c.num_classes);
+        k_fa_inf_rule<<<dim3(64, t.count), 256, 0, st>>>(t);
+    }
+    QV_CHECK_LAUNCH("qatvit_float_student_amp_backward");
+    return 0;
+}
+
+int qatvit_float_student_amp_attn_backward(const float* qkv, const void* O16, const float* lse, const float* dO, int32_t B, int32_t T, int32_t H, int32_t D,
+                                           void* dqkv16, void* stream) {
+    if (launch_attn_bwd_f16(qkv, O16, lse, dO, B, T, H, D, dqkv16, (hipStream_t)stream)) return 1;
+    QV_CHECK_LAUNCH("qatvit_float_student_amp_attn_backward");
+    return 0;
+}
+
+}  // extern "C"

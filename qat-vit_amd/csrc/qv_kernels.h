@@ -263,12 +263,16 @@ bool attn_bwd_is_fused(int T, int H, int D, bool codes);
 // ---- teacher.hip: the float forward pieces (bf16 (hi, lo) pairs; the float student step shares them)
 // lse (optional): log-sum-exp of the scaled scores per query, [B][H][T]
 int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16 = 0, float* lse = nullptr);
-int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st);
+// f16 != 0: fp16 bit patterns instead of bf16 (lo == nullptr: the one-plane form keeps the hi part only; the same for launch_resid_ln_split_save)
+int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st, int f16 = 0);
 // mode 0: x = [cls; Y] + pos, mode 1: x = x_prev + Y; then LayerNorm(x) as a (hi, lo) pair, mean / rstd per row (optional); stats (optional):
 // kStatSlots {min, max} accumulator pairs that take the min / max of the fp32 LayerNorm outputs (the observe-only forward)
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
-                               uint32_t* stats = nullptr);
+                               uint32_t* stats = nullptr, int f16 = 0);
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st);   // n % 4 == 0
+// ---- float_amp.hip: the fp16 (autocast) form of the float student step.  Fused attention backward on v_mfma_f32_16x16x32_f16, one workgroup per
+// (image, head): qkv / dO fp32 [B*T, 3D] / [B*T, D] (rounded to fp16 on load), O16 fp16 [B*T, D], lse [B][H][T] -> dqkv16 fp16 [B*T, 3D]
+int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st);
 
 }  // namespace qv

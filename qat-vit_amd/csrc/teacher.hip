@@ -402,15 +402,15 @@ int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_
     return 0;
 }
 
-// the forward pieces the float student step (float_step.hip) shares, always in the bf16-pair form
-int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st) {
+// the forward pieces the float student step (float_step.hip) shares: the bf16-pair form, or (f16, float_amp.hip) one fp16 plane
+int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st, int f16) {
     const int64_t n = (int64_t)B * (H / P) * (W / P) * C * P * P;
-    k_patches_split<<<flat_grid_t(n / 4), 256, 0, st>>>(img, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), B, C, H, W, P, 0);
+    k_patches_split<<<flat_grid_t(n / 4), 256, 0, st>>>(img, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), B, C, H, W, P, f16);
     return 0;
 }
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
-                               uint32_t* stats) {
+                               uint32_t* stats, int f16) {
     __bf16* hh = reinterpret_cast<__bf16*>(h_hi);
     __bf16* hl = reinterpret_cast<__bf16*>(h_lo);
     if (stats) {
@@ -418,8 +418,8 @@ int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, co
         else launch_resid_ln_split<1, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats);
         return 0;
     }
-    if (mode == 0) launch_resid_ln_split<0>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
-    else launch_resid_ln_split<1>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
+    if (mode == 0) launch_resid_ln_split<0>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, f16, mean, rstd);
+    else launch_resid_ln_split<1>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, f16, mean, rstd);
     return 0;
 }
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st) {

@@ -4,7 +4,10 @@ The reference trains the FLOAT student for the first ``qat_start_epoch`` epochs 
 in fp32 in train_final.sh, under ``torch.amp.autocast`` + ``GradScaler`` in the Optuna objective.  ``native_float(wrapper)`` opts an
 unprepared ``QATWrapper(vit_*_patch16_224)`` into the native step: its ``forward`` on a CUDA tensor then runs
 ``qatvit_float_student_forward`` and autograd's backward ``qatvit_float_student_backward``, fp32-accurate (bf16 (hi, lo) pairs, three
-MFMA passes per product) whatever autocast says.  Without the opt-in nothing changes: the float tree is ordinary ``nn.Module`` code.
+MFMA passes per product) whatever autocast says.  ``native_float(wrapper, amp=True)`` adds the fp16 form
+(``qatvit_float_student_amp_*``): a forward inside ``torch.autocast("cuda", dtype=torch.float16)`` then follows stock autocast - fp16 GEMM
+operands, fp32 residual / LayerNorm / softmax, fp16 logits - and outside autocast runs the fp32-accurate form above; the choice is made per
+forward.  Without the opt-in nothing changes: the float tree is ordinary ``nn.Module`` code.
 
 Engines live in a ``WeakKeyDictionary`` keyed by the wrapper, never on the module, so ``copy.deepcopy`` / ``prepare_qat(inplace=False)``
 copy no ctypes state; a copy is not opted in.  A prepared wrapper always takes the QAT engine (engine.py) first.
@@ -32,8 +35,8 @@ def _student_params(model: nn.Module) -> List[torch.Tensor]:
     return ps + [model.norm.weight, model.norm.bias, model.head.weight, model.head.bias]
 
 
-def check_shape(model: nn.Module) -> None:
-    """Raise unless the native float step covers this tree (the QAT engine's limits)."""
+def check_shape(model: nn.Module, amp: bool = False) -> None:
+    """Raise unless the native float step covers this tree (the QAT engine's limits; amp: also the fp16 form's)."""
     from .vit import VisionTransformer
 
     if not isinstance(model, VisionTransformer):
@@ -66,14 +69,17 @@ def check_shape(model: nn.Module) -> None:
         if not all(isinstance(getattr(b, n), nn.Identity) for n in ("ls1", "ls2", "drop_path1", "drop_path2")):
             why.append("layer scale / drop-path")
             break
+    if amp and (D % 384 or model.blocks[0].mlp.fc1.weight.shape[0] % 384):
+        why.append(f"amp=True: embed_dim {D} and mlp hidden {model.blocks[0].mlp.fc1.weight.shape[0]} (multiples of 384 for the fp16 form)")
     if why:
         raise RuntimeError("native float step: unsupported model: " + "; ".join(why))
 
 
 class FloatStudentEngine:
-    def __init__(self, wrapper: nn.Module):
+    def __init__(self, wrapper: nn.Module, amp: bool = False):
         model = wrapper.model
-        check_shape(model)
+        check_shape(model, amp)
+        self.amp = amp
         self.lib = native.lib()
         self.params = _student_params(model)
         dev = self.params[0].device
@@ -92,7 +98,9 @@ class FloatStudentEngine:
         self._ptr_params = (ctypes.c_void_p * len(self.params))(*self._ptrs_key)
         self.workspace: Optional[torch.Tensor] = None
         self.capacity = 0           # the batch the workspace is sized for
-        self.generation = 0         # bumped by every forward: the workspace holds the activations of exactly one forward
+        self.generation = 0         # bumped by every forward of either form: the workspaces hold the activations of exactly one forward
+        self.workspace16: Optional[torch.Tensor] = None   # the fp16 form's own workspace, allocated by the first autocast forward
+        self.capacity16 = 0
         self.grad_numel = sum(p.numel() for p in self.params)
 
     def cfg_for(self, batch: int) -> native.Cfg:
@@ -114,16 +122,31 @@ class FloatStudentEngine:
         native.check(self.lib.qatvit_float_student_init(ctypes.byref(self.cfg_for(batch)), self.workspace.data_ptr(), native.stream_ptr()),
                      "qatvit_float_student_init")
 
+    def _reserve16(self, batch: int) -> None:
+        if batch <= self.capacity16:
+            return
+        c = self.cfg_for(batch)
+        nbytes = self.lib.qatvit_float_student_amp_workspace_bytes(ctypes.byref(c))
+        if nbytes <= 0:
+            raise RuntimeError("qatvit_float_student_amp_workspace_bytes: " + self.lib.qatvit_last_error().decode())
+        self.workspace16 = None
+        self.workspace16 = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.capacity16 = batch
+        native.check(self.lib.qatvit_float_student_amp_init(ctypes.byref(c), self.workspace16.data_ptr(), native.stream_ptr()),
+                     "qatvit_float_student_amp_init")
+
     def stale(self) -> bool:
         return tuple(p.data_ptr() for p in self.params) != self._ptrs_key
 
-    def forward(self, images: torch.Tensor) -> torch.Tensor:
+    def forward(self, images: torch.Tensor, f16: bool = False) -> torch.Tensor:
         k = self._cfg_kw
         if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[1:]) != (k["in_chans"], k["img_size"], k["img_size"]):
             raise RuntimeError(f"expected images of shape (B, {k['in_chans']}, {k['img_size']}, {k['img_size']}), got {tuple(images.shape)}")
         if not images.is_cuda or images.device != self.device:
             raise RuntimeError(f"native float step: images on {images.device}, parameters on {self.device}")
         images = images.to(torch.float32).contiguous()
+        if f16:
+            return self._forward16(images)
         self._reserve(images.shape[0])
         c = self.cfg_for(images.shape[0])
         logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
@@ -132,18 +155,50 @@ class FloatStudentEngine:
                                                            self.workspace.data_ptr(), native.stream_ptr()), "qatvit_float_student_forward")
         return logits
 
-    def backward(self, dlogits: torch.Tensor, batch: int) -> List[torch.Tensor]:
+    def _forward16(self, images: torch.Tensor) -> torch.Tensor:
+        self._reserve16(images.shape[0])
+        c = self.cfg_for(images.shape[0])
+        logits = torch.empty(c.batch, c.num_classes, dtype=torch.float16, device=self.device)
+        self.generation += 1
+        native.check(self.lib.qatvit_float_student_amp_forward(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
+                                                               self.workspace16.data_ptr(), native.stream_ptr()), "qatvit_float_student_amp_forward")
+        return logits
+
+    def backward(self, dlogits: torch.Tensor, batch: int, f16: bool = False) -> List[torch.Tensor]:
         c = self.cfg_for(batch)
-        dlogits = dlogits.to(torch.float32).contiguous()
+        dlogits = dlogits.to(torch.float16 if f16 else torch.float32).contiguous()
         flat = torch.zeros(self.grad_numel, dtype=torch.float32, device=self.device)
         views, o = [], 0
         for p in self.params:
             views.append(flat[o:o + p.numel()].view(p.shape))
             o += p.numel()
         gptr = (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
-        native.check(self.lib.qatvit_float_student_backward(ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr, self.workspace.data_ptr(),
-                                                            native.stream_ptr()), "qatvit_float_student_backward")
+        if f16:
+            native.check(self.lib.qatvit_float_student_amp_backward(ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr,
+                                                                    self.workspace16.data_ptr(), native.stream_ptr()), "qatvit_float_student_amp_backward")
+        else:
+            native.check(self.lib.qatvit_float_student_backward(ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr, self.workspace.data_ptr(),
+                                                                native.stream_ptr()), "qatvit_float_student_backward")
         return views
+
+
+def _step_backward(ctx, dlogits):
+    # as engine._StudentStep: the gradients are views of one flat buffer assigned to .grad directly (DDP's post-accumulate-grad hooks
+    # fire on that assignment)
+    eng = ctx.engine
+    if eng.generation != ctx.generation:
+        raise RuntimeError(
+            "qat-vit_amd: another forward of this model ran between this forward and its backward; the native step keeps the "
+            "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
+            "forward/backward per micro-batch)."
+        )
+    grads = eng.backward(dlogits, ctx.batch, ctx.f16)
+    for p, g in zip(eng.params, grads):
+        if p.grad is None:
+            p.grad = g
+        else:
+            p.grad.add_(g)
+    return (None, None) + (None,) * len(grads)
 
 
 class _FloatStudentStep(torch.autograd.Function):
@@ -155,34 +210,42 @@ class _FloatStudentStep(torch.autograd.Function):
         out = engine.forward(images)
         ctx.generation = engine.generation
         ctx.batch = images.shape[0]
+        ctx.f16 = False
         return out
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dlogits):
-        # as engine._StudentStep: the gradients are views of one flat buffer assigned to .grad directly (DDP's post-accumulate-grad hooks
-        # fire on that assignment)
-        eng = ctx.engine
-        if eng.generation != ctx.generation:
-            raise RuntimeError(
-                "qat-vit_amd: another forward of this model ran between this forward and its backward; the native step keeps the "
-                "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
-                "forward/backward per micro-batch)."
-            )
-        grads = eng.backward(dlogits, ctx.batch)
-        for p, g in zip(eng.params, grads):
-            if p.grad is None:
-                p.grad = g
-            else:
-                p.grad.add_(g)
-        return (None, None) + (None,) * len(grads)
+        return _step_backward(ctx, dlogits)
 
 
-def native_float(wrapper: nn.Module) -> nn.Module:
+class _FloatStudentAmpStep(torch.autograd.Function):
+    # the fp16 form (native_float(..., amp=True) inside fp16 autocast): fp16 logits as stock autocast's head Linear returns; ctx.f16 records
+    # the form for the backward
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, images, engine, *params):
+        ctx.engine = engine
+        out = engine.forward(images, f16=True)
+        ctx.generation = engine.generation
+        ctx.batch = images.shape[0]
+        ctx.f16 = True
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dlogits):
+        return _step_backward(ctx, dlogits)
+
+
+def native_float(wrapper: nn.Module, amp: bool = False) -> nn.Module:
     """Opt an unprepared ``QATWrapper(vit_*_patch16_224)`` into the native float step; returns the wrapper.
 
     The parameters must already be on the GPU; the shape is checked here.  Afterwards ``wrapper(x)`` on a CUDA tensor runs the native
-    forward (and its backward), a CPU tensor raises; ``prepare_qat`` of the wrapper is unaffected (a prepared wrapper takes the QAT engine)."""
+    forward (and its backward), a CPU tensor raises; ``prepare_qat`` of the wrapper is unaffected (a prepared wrapper takes the QAT engine).
+    amp=True: a forward inside ``torch.autocast("cuda", dtype=torch.float16)`` runs the fp16 form (fp16 logits, stock autocast's numerics and
+    overflow behaviour, for GradScaler); outside autocast the fp32-accurate form; bf16 autocast raises.  Needs embed_dim and mlp_hidden
+    multiples of 384."""
     from .model_registry import QATWrapper
 
     if not isinstance(wrapper, QATWrapper):
@@ -191,7 +254,7 @@ def native_float(wrapper: nn.Module) -> nn.Module:
         raise RuntimeError("native_float: the wrapper is already prepared for QAT (it runs the native QAT step)")
     if any(not p.is_cuda for p in wrapper.parameters()):
         raise RuntimeError("native_float: move the model to the GPU first (model.cuda()); the native float step runs on MI355X only")
-    _OPTED[wrapper] = FloatStudentEngine(wrapper)
+    _OPTED[wrapper] = FloatStudentEngine(wrapper, amp=bool(amp))
     return wrapper
 
 
@@ -206,5 +269,11 @@ def engine_of(wrapper) -> Optional[FloatStudentEngine]:
 def float_forward(wrapper, images: torch.Tensor) -> torch.Tensor:
     eng = _OPTED.get(wrapper)
     if eng is None or eng.stale():   # parameters re-allocated (e.g. .to()): the float step keeps no state, rebuild
-        eng = _OPTED[wrapper] = FloatStudentEngine(wrapper)
+        eng = _OPTED[wrapper] = FloatStudentEngine(wrapper, amp=eng.amp if eng is not None else False)
+    if eng.amp and torch.is_autocast_enabled("cuda"):   # decided per forward
+        dt = torch.get_autocast_dtype("cuda")
+        if dt != torch.float16:
+            raise RuntimeError(f"native float step (amp=True): autocast dtype {dt} is not supported; the fp16 form follows "
+                               "torch.autocast('cuda', dtype=torch.float16) only")
+        return _FloatStudentAmpStep.apply(images, eng, *eng.params)
     return _FloatStudentStep.apply(images, eng, *eng.params)
