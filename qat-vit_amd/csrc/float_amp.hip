@@ -10,6 +10,7 @@
 // Overflow follows stock (GradScaler must skip the same steps): every tensor stock holds in fp16 is rounded to nearest (fp16 overflow -> +-inf,
 // NaN propagates) where it becomes fp16 - dlogits, dhn, the fc2 dgrad output, dO, dP, dS, dQKV, dY0 - and the
 // Linear / Conv2d weight and bias gradients (fp16 tensors under stock autocast, fp32 sums here) take one post-pass: |g| beyond fp16's range -> +-inf.
+// This file holds the form's device code and its launchers; the host driver, shared with the pair form, is float_step.hip.
 #include "../../include/qatvit.h"
 
 #include "qv_common.h"
@@ -358,16 +359,54 @@ int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, con
     return 0;
 }
 
-// the disabled quantiser {1, 1, 0, 0} (its first word is also the unit scale of the one-plane GEMMs) and the all-ones STE mask
-__global__ void k_fa_consts(float* qp_off, uint32_t* ones, int64_t nwords) {
-    const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i0 == 0) { qp_off[0] = 1.f; qp_off[1] = 1.f; qp_off[2] = 0.f; qp_off[3] = 0.f; }
-    for (int64_t i = i0; i < nwords; i += (int64_t)gridDim.x * blockDim.x) ones[i] = 0xffffffffu;
+// ---------------------------------------------------------------- launchers (the host driver of both forms is float_step.hip)
+int launch_fa_wcast(int n, const float* const* W, void* const* w16, void* const* w16T, const int* N, const int* K, const int* blk0, hipStream_t st) {
+    FaWTab t{};
+    t.n = n;
+    for (int wi = 0; wi < n; ++wi) {
+        t.W[wi] = W[wi];
+        t.w[wi] = reinterpret_cast<_Float16*>(w16[wi]);
+        t.wT[wi] = reinterpret_cast<_Float16*>(w16T[wi]);
+        t.N[wi] = N[wi]; t.K[wi] = K[wi]; t.blk0[wi] = blk0[wi];
+    }
+    t.blk0[n] = blk0[n];
+    k_fa_wcast<<<blk0[n], 256, 0, st>>>(t);
+    return 0;
 }
 
-static int flat_grid_fa(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+int launch_fa_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias, float* hn,
+                       void* logits16, int B, int D, int T, int C, hipStream_t st) {
+    k_fa_head_fwd<<<B, 256, D * sizeof(float), st>>>(x, mean, rstd, gamma, beta, W, bias, hn, reinterpret_cast<_Float16*>(logits16), D, T, C);
+    return 0;
+}
+
+int launch_fa_head_bwd(const void* dl16, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st) {
+    const int64_t n = (int64_t)C * D + (int64_t)B * D + C;
+    k_fa_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const _Float16*>(dl16), hn, W, dW, dbias, dhn, B, D, C);
+    return 0;
+}
+
+int launch_fa_gelu(const float* Y, void* G16, int64_t n, hipStream_t st) {
+    k_fa_gelu<<<flat_grid_fs(n / 4), 256, 0, st>>>(Y, reinterpret_cast<_Float16*>(G16), n / 4);
+    return 0;
+}
+
+int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, hipStream_t st) {
+    k_fa_gelu_bwd<<<flat_grid_fs(n / 4), 256, 0, st>>>(dG, Y, reinterpret_cast<_Float16*>(dY16), n / 4);
+    return 0;
+}
+
+int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16, int B, int T, int D, hipStream_t st) {
+    k_fa_embed_bwd<<<(int)(((int64_t)T * (D / 4) + 63) / 64), 64, 0, st>>>(dx, dpos, dcls, reinterpret_cast<_Float16*>(dY0_16), B, T, D);
+    return 0;
+}
+
+int launch_fa_inf_rule(float* const* g, const int64_t* n, int count, hipStream_t st) {
+    FaInfTab t{};
+    for (int k = 0; k < count; ++k) { t.g[k] = g[k]; t.n[k] = n[k]; }
+    t.count = count;
+    k_fa_inf_rule<<<dim3(64, count), 256, 0, st>>>(t);
+    return 0;
 }
 
 }  // namespace qv
@@ -375,246 +414,6 @@ static int flat_grid_fa(int64_t n) {
 using namespace qv;
 
 extern "C" {
-
-// Workspace: a batch-independent head (constants, the fp16 weight planes, the weight-gradient scratch) and the batch-sized rest.
-struct FaBlock { int64_t x, xm, h1, h2, mean1, rstd1, mean2, rstd2, qkv, O, lse, Y1, G; };
-struct FaPlan {
-    int64_t qp_off, amax, w16[kMaxW], w16T[kMaxW], tn_partial;
-    int64_t ones, p16, Y0, x_last, meanf, rstdf, hf, hn;
-    FaBlock blk[12];
-    int64_t Y, dx, dx2, dp, dG, dY1, dh, dO, dqkv, dhn, dY0;
-    int64_t ones_words, total;
-};
-static int fa_check(const qatvit_cfg& c) {
-    const int hd = c.num_heads > 0 ? c.embed_dim / c.num_heads : 0;
-    const int np = c.patch_size > 0 ? (c.img_size / c.patch_size) * (c.img_size / c.patch_size) : 0;
-    if (c.batch < 1 || c.depth < 1 || c.depth > 12 || c.embed_dim % 384 != 0 || c.embed_dim > 768 || c.mlp_hidden % 384 != 0 || c.num_heads < 1 ||
-        c.embed_dim % c.num_heads != 0 || (hd != 32 && hd != 64) || c.patch_size % 4 != 0 || c.img_size % c.patch_size != 0 || np + 1 > 224 ||
-        (c.in_chans * c.patch_size * c.patch_size) % 128 != 0 || c.num_classes < 1) {
-        set_error("float student amp: unsupported config (batch %d depth %d dim %d hidden %d heads %d img %d patch %d): needs dim and hidden multiples "
-                  "of 384, dim <= 768, head_dim 32 or 64, <= 224 tokens, depth <= 12", c.batch, c.depth, c.embed_dim, c.mlp_hidden, c.num_heads, c.img_size,
-                  c.patch_size);
-        return 1;
-    }
-    return 0;
-}
-static void fa_weight_shape(const qatvit_cfg& c, int wi, int* N, int* K) {
-    const int D = c.embed_dim, Hd = c.mlp_hidden;
-    if (wi == 0) { *N = D; *K = c.in_chans * c.patch_size * c.patch_size; return; }
-    switch ((wi - 1) % 4) {
-        case 0: *N = 3 * D; *K = D; break;
-        case 1: *N = D; *K = D; break;
-        case 2: *N = Hd; *K = D; break;
-        default: *N = D; *K = Hd; break;
-    }
-}
-static FaPlan fa_plan(const qatvit_cfg& c) {
-    FaPlan p{};
-    int64_t o = 0;
-    auto take = [&](int64_t b) { int64_t r = o; o += (b + 255) & ~(int64_t)255; return r; };
-    const int64_t np = (int64_t)(c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, B = c.batch, M = B * T, D = c.embed_dim,
-                  Hd = c.mlp_hidden, H = c.num_heads, Kpe = (int64_t)c.in_chans * c.patch_size * c.patch_size;
-    p.qp_off = take(16);
-    p.amax = take((int64_t)kDyAmaxSlots * kDyAmaxStride * 4);
-    for (int wi = 0; wi < 1 + 4 * c.depth; ++wi) {
-        int N, K;
-        fa_weight_shape(c, wi, &N, &K);
-        p.w16[wi] = take((int64_t)N * K * 2);
-        p.w16T[wi] = take((int64_t)N * K * 2);
-    }
-    p.tn_partial = take(kTnScratchBytes);
-    p.ones_words = ln_maskbits_bytes(M, (int)D) / 4;
-    p.ones = take(ln_maskbits_bytes(M, (int)D));
-    p.p16 = take(B * np * Kpe * 2);
-    p.Y0 = take(B * np * D * 4);
-    for (int i = 0; i < c.depth; ++i) {
-        FaBlock& k = p.blk[i];
-        k.x = take(M * D * 4); k.xm = take(M * D * 4);
-        k.h1 = take(M * D * 2); k.h2 = take(M * D * 2);
-        k.mean1 = take(M * 4); k.rstd1 = take(M * 4); k.mean2 = take(M * 4); k.rstd2 = take(M * 4);
-        k.qkv = take(M * 3 * D * 4);
-        k.O = take(M * D * 2);
-        k.lse = take(B * H * T * 4);
-        k.Y1 = take(M * Hd * 4);
-        k.G = take(M * Hd * 2);
-    }
-    p.x_last = take(M * D * 4);
-    p.meanf = take(M * 4); p.rstdf = take(M * 4);
-    p.hf = take(M * D * 2);
-    p.hn = take(B * D * 4);
-    p.Y = take(M * D * 4);
-    p.dx = take(M * D * 4); p.dx2 = take(M * D * 4);
-    p.dp = take(M * D * 2);
-    p.dG = take(M * Hd * 4);
-    p.dY1 = take(M * Hd * 2);
-    p.dh = take(M * D * 4);
-    p.dO = take(M * D * 4);
-    p.dqkv = take(M * 3 * D * 2);
-    p.dhn = take(B * D * 4);
-    p.dY0 = take(B * np * D * 2);
-    p.total = o;
-    return p;
-}
-
-int64_t qatvit_float_student_amp_workspace_bytes(const qatvit_cfg* cfg) {
-    if (!cfg) { set_error("qatvit_float_student_amp_workspace_bytes: null argument"); return -1; }
-    if (fa_check(*cfg)) return -1;
-    return fa_plan(*cfg).total;
-}
-
-static void fa_consts(const FaPlan& p, char* ws, hipStream_t st) {
-    k_fa_consts<<<flat_grid_fa(p.ones_words), 256, 0, st>>>(reinterpret_cast<float*>(ws + p.qp_off), reinterpret_cast<uint32_t*>(ws + p.ones), p.ones_words);
-}
-
-int qatvit_float_student_amp_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && workspace, "qatvit_float_student_amp_init: null argument");
-    if (fa_check(*cfg)) return 1;
-    fa_consts(fa_plan(*cfg), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
-    QV_CHECK_LAUNCH("qatvit_float_student_amp_init");
-    return 0;
-}
-
-int qatvit_float_student_amp_forward(const qatvit_cfg* cfg, void* const* params, const float* images, void* logits_f16, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && params && images && logits_f16 && workspace, "qatvit_float_student_amp_forward: null argument");
-    if (fa_check(*cfg)) return 1;
-    const qatvit_cfg& c = *cfg;
-    const FaPlan p = fa_plan(c);
-    char* ws = reinterpret_cast<char*>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden;
-    const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth;
-    const int64_t M = (int64_t)c.batch * T;
-    auto F = [&](int64_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto V = [&](int64_t off) { return reinterpret_cast<void*>(ws + off); };
-    auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
-    auto bprm = [&](int blk, int k) { return prm(4 + 12 * blk + k); };
-    fa_consts(p, ws, st);
-    {   // the weights as fp16, as stored and transposed, in one launch
-        FaWTab t{};
-        t.n = 1 + 4 * L;
-        int blocks = 0;
-        for (int wi = 0; wi < t.n; ++wi) {
-            fa_weight_shape(c, wi, &t.N[wi], &t.K[wi]);
-            static const int kW[4] = {2, 4, 8, 10};   // qkv, proj, fc1, fc2 weights within a block's 12 parameters
-            t.W[wi] = wi == 0 ? prm(0) : bprm((wi - 1) / 4, kW[(wi - 1) % 4]);
-            t.w[wi] = reinterpret_cast<_Float16*>(ws + p.w16[wi]);
-            t.wT[wi] = reinterpret_cast<_Float16*>(ws + p.w16T[wi]);
-            t.blk0[wi] = blocks;
-            blocks += ((t.N[wi] + 31) / 32) * ((t.K[wi] + 31) / 32);
-        }
-        t.blk0[t.n] = blocks;
-        k_fa_wcast<<<blocks, 256, 0, st>>>(t);
-    }
-    // one fp16 pass per GEMM, fp32 output + fp32 bias
-    auto gemm = [&](int64_t a16, int wi, const float* bias, float* C, int N, int K, int Mrows) {
-        return launch_gemm_nt(V(a16), nullptr, V(p.w16[wi]), C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, nullptr, 1, st, nullptr, nullptr, true);
-    };
-    launch_patches_split(images, V(p.p16), nullptr, c.batch, c.in_chans, c.img_size, c.img_size, c.patch_size, st, 1);
-    if (gemm(p.p16, 0, prm(1), F(p.Y0), D, Kpe, c.batch * np)) return 1;
-    launch_resid_ln_split_save(0, nullptr, F(p.Y0), prm(2), prm(3), F(p.blk[0].x), bprm(0, 0), bprm(0, 1), c.ln_eps, V(p.blk[0].h1), nullptr, F(p.blk[0].mean1),
-                               F(p.blk[0].rstd1), M, D, T, st, nullptr, 1);
-    for (int i = 0; i < L; ++i) {
-        const FaBlock& k = p.blk[i];
-        const int w0 = 1 + 4 * i;
-        if (gemm(k.h1, w0 + 0, bprm(i, 3), F(k.qkv), 3 * D, D, (int)M)) return 1;
-        if (launch_attn_fwd_float(F(k.qkv), c.batch, T, c.num_heads, D, V(k.O), nullptr, st, 1, F(k.lse))) return 1;
-        if (gemm(k.O, w0 + 1, bprm(i, 5), F(p.Y), D, D, (int)M)) return 1;
-        launch_resid_ln_split_save(1, F(k.x), F(p.Y), nullptr, nullptr, F(k.xm), bprm(i, 6), bprm(i, 7), c.ln_eps, V(k.h2), nullptr, F(k.mean2), F(k.rstd2), M, D, T,
-                                   st, nullptr, 1);
-        if (gemm(k.h2, w0 + 2, bprm(i, 9), F(k.Y1), Hd, D, (int)M)) return 1;
-        k_fa_gelu<<<flat_grid_fa(M * Hd / 4), 256, 0, st>>>(F(k.Y1), reinterpret_cast<_Float16*>(ws + k.G), M * Hd / 4);
-        if (gemm(k.G, w0 + 3, bprm(i, 11), F(p.Y), D, Hd, (int)M)) return 1;
-        const bool last = i + 1 == L;
-        const FaBlock* nx = last ? nullptr : &p.blk[i + 1];
-        launch_resid_ln_split_save(1, F(k.xm), F(p.Y), nullptr, nullptr, last ? F(p.x_last) : F(nx->x), last ? prm(4 + 12 * L) : bprm(i + 1, 0),
-                                   last ? prm(4 + 12 * L + 1) : bprm(i + 1, 1), c.ln_eps, last ? V(p.hf) : V(nx->h1), nullptr, last ? F(p.meanf) : F(nx->mean1),
-                                   last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, nullptr, 1);
-    }
-    const int hb = 4 + 12 * L;
-    k_fa_head_fwd<<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3), F(p.hn),
-                                                          reinterpret_cast<_Float16*>(logits_f16), D, T, c.num_classes);
-    QV_CHECK_LAUNCH("qatvit_float_student_amp_forward");
-    return 0;
-}
-
-int qatvit_float_student_amp_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_f16, void* const* grads, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && params && dlogits_f16 && grads && workspace, "qatvit_float_student_amp_backward: null argument");
-    if (fa_check(*cfg)) return 1;
-    const qatvit_cfg& c = *cfg;
-    const FaPlan p = fa_plan(c);
-    char* ws = reinterpret_cast<char*>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden, H = c.num_heads;
-    const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth;
-    const int64_t M = (int64_t)c.batch * T;
-    auto F = [&](int64_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto V = [&](int64_t off) { return reinterpret_cast<void*>(ws + off); };
-    auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
-    auto grd = [&](int i) { return reinterpret_cast<float*>(grads[i]); };
-    const float* qp_off = F(p.qp_off);
-    const float* one = qp_off;   // 1.0f
-    float* partial = F(p.tn_partial);
-    // dgrad: C[M, N] = dY16[M, K] . W[K, N], the transposed fp16 weight as the B operand ([N, K] row-major)
-    auto dgrad = [&](int64_t a16, int wi, float* C, int N, int K) {
-        return launch_gemm_nt_dy16(V(a16), V(p.w16T[wi]), C, (int)M, N, K, K, K, N, one, one, st);
-    };
-    // wgrad: dW[N, Kw] += dY16[Mr, N]^T . X16[Mr, Kw], dbias[N] += column sums of dY16
-    auto wgrad = [&](int64_t p16, int64_t x16, float* dW, float* db, int N, int Kw, int Mr) {
-        return launch_gemm_tn_dy16(V(p16), V(x16), nullptr, dW, Mr, N, Kw, N, Kw, Kw, one, one, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
-                                   kTnScratchBytes);
-    };
-    // the LayerNorm backward's second output: the residual gradient as the fp16 plane dp (mask all ones, unit multiplier)
-    LnBwdNext next{V(p.ones), nullptr, V(p.dp), nullptr, one, reinterpret_cast<uint32_t*>(ws + p.amax)};
-    const int hb = 4 + 12 * L;
-    {
-        const int64_t n = (int64_t)c.num_classes * D + (int64_t)c.batch * D + c.num_classes;
-        k_fa_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const _Float16*>(dlogits_f16), F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3),
-                                                              F(p.dhn), c.batch, D, c.num_classes);
-    }
-    if (launch_ln_bwd_fq(0, F(p.dhn), F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), qp_off, 0, 255, nullptr, F(p.dx), grd(hb), grd(hb + 1), M, D, T,
-                         1, st, &next))
-        return 1;
-    for (int i = L - 1; i >= 0; --i) {
-        const FaBlock& k = p.blk[i];
-        const int w0 = 1 + 4 * i, g0 = 4 + 12 * i;
-        // fc2 (input G), then GELU' on the fc1 pre-activation
-        if (wgrad(p.dp, k.G, grd(g0 + 10), grd(g0 + 11), D, Hd, (int)M)) return 1;
-        if (dgrad(p.dp, w0 + 3, F(p.dG), Hd, D)) return 1;
-        k_fa_gelu_bwd<<<flat_grid_fa(M * Hd / 4), 256, 0, st>>>(F(p.dG), F(k.Y1), reinterpret_cast<_Float16*>(ws + p.dY1), M * Hd / 4);
-        // fc1 (input h2), norm2 backward + the residual: dx2 = dx + LNbwd(dh2), and its fp16 plane for proj
-        if (wgrad(p.dY1, k.h2, grd(g0 + 8), grd(g0 + 9), Hd, D, (int)M)) return 1;
-        if (dgrad(p.dY1, w0 + 2, F(p.dh), D, Hd)) return 1;
-        if (launch_ln_bwd_fq(1, F(p.dh), F(k.xm), F(k.mean2), F(k.rstd2), prm(g0 + 6), prm(g0 + 7), qp_off, 0, 255, F(p.dx), F(p.dx2), grd(g0 + 6), grd(g0 + 7), M,
-                             D, T, 0, st, &next))
-            return 1;
-        // proj (input O), attention, qkv (input h1); norm1 backward: dx = dx2 + LNbwd(dh1)
-        if (wgrad(p.dp, k.O, grd(g0 + 4), grd(g0 + 5), D, D, (int)M)) return 1;
-        if (dgrad(p.dp, w0 + 1, F(p.dO), D, D)) return 1;
-        if (launch_attn_bwd_f16(F(k.qkv), V(k.O), F(k.lse), F(p.dO), c.batch, T, H, D, V(p.dqkv), st)) return 1;
-        if (wgrad(p.dqkv, k.h1, grd(g0 + 2), grd(g0 + 3), 3 * D, D, (int)M)) return 1;
-        if (dgrad(p.dqkv, w0 + 0, F(p.dh), D, 3 * D)) return 1;
-        if (launch_ln_bwd_fq(1, F(p.dh), F(k.x), F(k.mean1), F(k.rstd1), prm(g0 + 0), prm(g0 + 1), qp_off, 0, 255, F(p.dx2), F(p.dx), grd(g0 + 0), grd(g0 + 1), M,
-                             D, T, 0, st, i > 0 ? &next : nullptr))
-            return 1;
-    }
-    // embedding: pos / cls gradients and dY0 (the patch rows of dx) as fp16, then the patch-embedding weight gradient over the saved patches
-    k_fa_embed_bwd<<<(int)(((int64_t)T * (D / 4) + 63) / 64), 64, 0, st>>>(F(p.dx), grd(3), grd(2), reinterpret_cast<_Float16*>(ws + p.dY0), c.batch, T, D);
-    if (wgrad(p.dY0, p.p16, grd(0), grd(1), D, Kpe, c.batch * np)) return 1;
-    {   // the overflow rule of the fp16 Linear / Conv2d gradients
-        FaInfTab t{};
-        auto add = [&](int i, int64_t n) { t.g[t.count] = grd(i); t.n[t.count] = n; ++t.count; };
-        add(0, (int64_t)D * Kpe); add(1, D);
-        for (int i = 0; i < L; ++i) {
-            const int g0 = 4 + 12 * i;
-            add(g0 + 2, (int64_t)3 * D * D); add(g0 + 3, 3 * D); add(g0 + 4, (int64_t)D * D); add(g0 + 5, D);
-            add(g0 + 8, (int64_t)Hd * D); add(g0 + 9, Hd); add(g0 + 10, (int64_t)D * Hd); add(g0 + 11, D);
-        }
-        add(hb + 2, (int64_t)c.num_classes * D); add(hb + 3, c.num_classes);
-        k_fa_inf_rule<<<dim3(64, t.count), 256, 0, st>>>(t);
-    }
-    QV_CHECK_LAUNCH("qatvit_float_student_amp_backward");
-    return 0;
-}
 
 int qatvit_float_student_amp_attn_backward(const float* qkv, const void* O16, const float* lse, const float* dO, int32_t B, int32_t T, int32_t H, int32_t D,
                                            void* dqkv16, void* stream) {

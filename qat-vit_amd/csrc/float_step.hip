@@ -290,41 +290,44 @@ static int launch_attn_bwd_float(const float* qkv, const void* O_hi, const void*
     return 0;
 }
 
-static int flat_grid_fs(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
 }  // namespace qv
 
 using namespace qv;
 
 extern "C" {
 
-// Workspace: a batch-independent head (constants, the weight pairs, the weight-gradient scratch) and the batch-sized rest.
+// The host driver of both forms of the step: the pair form (bf16 (hi, lo) pairs, three MFMA passes) and the fp16 form (f16: one fp16 plane per
+// GEMM operand, one pass; its device code and launchers are float_amp.hip's).  The fp16 form keeps each plane at the _hi offset.
+// Workspace: a batch-independent head (constants, the weight planes, the weight-gradient scratch) and the batch-sized rest.  The _lo planes and the
+// fp32 attention-backward scratch (Pm, dS, delta) are the pair form's only, amax (the fp16 residual gradient's maximum) the fp16 form's; a plane a
+// form does not take has offset -1.
 struct FsBlock { int64_t x, xm, h1_hi, h1_lo, h2_hi, h2_lo, mean1, rstd1, mean2, rstd2, qkv, O_hi, O_lo, lse, Y1, G_hi, G_lo; };
 struct FsPlan {
-    int64_t qp_off, w_hi[kMaxW], w_lo[kMaxW], w_hiT[kMaxW], w_loT[kMaxW], tn_partial;
+    int64_t qp_off, amax, w_hi[kMaxW], w_lo[kMaxW], w_hiT[kMaxW], w_loT[kMaxW], tn_partial;
     int64_t ones, p_hi, p_lo, Y0, x_last, meanf, rstdf, hf_hi, hf_lo, hn;
     FsBlock blk[12];
     int64_t Y, dx, dx2, dp_hi, dp_lo, dG, dY1_hi, dY1_lo, dh, dO, dqkv_hi, dqkv_lo, Pm, dS, delta, dhn, dY0_hi, dY0_lo;
     int64_t ones_words, total;
 };
-static int fs_check(const qatvit_cfg& c) {
+static int fs_check(const qatvit_cfg& c, bool f16) {
     const int hd = c.num_heads > 0 ? c.embed_dim / c.num_heads : 0;
     const int np = c.patch_size > 0 ? (c.img_size / c.patch_size) * (c.img_size / c.patch_size) : 0;
-    if (c.batch < 1 || c.depth < 1 || c.depth > 12 || c.embed_dim % 128 != 0 || c.embed_dim > 768 || c.mlp_hidden % 128 != 0 || c.num_heads < 1 ||
+    const int mult = f16 ? 384 : 128;
+    if (c.batch < 1 || c.depth < 1 || c.depth > 12 || c.embed_dim % mult != 0 || c.embed_dim > 768 || c.mlp_hidden % mult != 0 || c.num_heads < 1 ||
         c.embed_dim % c.num_heads != 0 || (hd != 32 && hd != 64) || c.patch_size % 4 != 0 || c.img_size % c.patch_size != 0 || np + 1 > 224 ||
         (c.in_chans * c.patch_size * c.patch_size) % 128 != 0 || c.num_classes < 1) {
-        set_error("float student: unsupported config (batch %d depth %d dim %d hidden %d heads %d img %d patch %d): needs dim %% 128 == 0 and <= 768, "
-                  "head_dim 32 or 64, <= 224 tokens, depth <= 12", c.batch, c.depth, c.embed_dim, c.mlp_hidden, c.num_heads, c.img_size, c.patch_size);
+        set_error("float student%s: unsupported config (batch %d depth %d dim %d hidden %d heads %d img %d patch %d): needs %s, head_dim 32 or 64, "
+                  "<= 224 tokens, depth <= 12", f16 ? " amp" : "", c.batch, c.depth, c.embed_dim, c.mlp_hidden, c.num_heads, c.img_size, c.patch_size,
+                  f16 ? "dim and hidden multiples of 384, dim <= 768" : "dim % 128 == 0 and <= 768");
         return 1;
     }
     return 0;
 }
+// weight wi: 0 patch embedding, 1 + 4 i + {0 qkv, 1 proj, 2 fc1, 3 fc2} of block i, 1 + 4 depth the head (the weight fake-quant order)
 static void fs_weight_shape(const qatvit_cfg& c, int wi, int* N, int* K) {
     const int D = c.embed_dim, Hd = c.mlp_hidden;
     if (wi == 0) { *N = D; *K = c.in_chans * c.patch_size * c.patch_size; return; }
+    if (wi == 1 + 4 * c.depth) { *N = c.num_classes; *K = D; return; }
     switch ((wi - 1) % 4) {
         case 0: *N = 3 * D; *K = D; break;
         case 1: *N = D; *K = D; break;
@@ -332,70 +335,76 @@ static void fs_weight_shape(const qatvit_cfg& c, int wi, int* N, int* K) {
         default: *N = D; *K = Hd; break;
     }
 }
-static FsPlan fs_plan(const qatvit_cfg& c) {
+static int fs_weight_param(const qatvit_cfg& c, int wi) {   // its index in the parameter order (include/qatvit.h); its bias follows it
+    static const int kW[4] = {2, 4, 8, 10};                  // qkv, proj, fc1, fc2 weights within a block's 12 parameters
+    return wi == 0 ? 0 : wi == 1 + 4 * c.depth ? 4 + 12 * c.depth + 2 : 4 + 12 * ((wi - 1) / 4) + kW[(wi - 1) % 4];
+}
+static FsPlan fs_plan(const qatvit_cfg& c, bool f16) {
     FsPlan p{};
     int64_t o = 0;
     auto take = [&](int64_t b) { int64_t r = o; o += (b + 255) & ~(int64_t)255; return r; };
+    auto pair = [&](int64_t b) { return f16 ? (int64_t)-1 : take(b); };   // taken by the pair form only
     const int64_t np = (int64_t)(c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, B = c.batch, M = B * T, D = c.embed_dim,
                   Hd = c.mlp_hidden, H = c.num_heads, Kpe = (int64_t)c.in_chans * c.patch_size * c.patch_size;
     p.qp_off = take(16);
+    p.amax = f16 ? take((int64_t)kDyAmaxSlots * kDyAmaxStride * 4) : -1;
     for (int wi = 0; wi < 1 + 4 * c.depth; ++wi) {
         int N, K;
         fs_weight_shape(c, wi, &N, &K);
-        p.w_hi[wi] = take((int64_t)N * K * 2); p.w_lo[wi] = take((int64_t)N * K * 2);
-        p.w_hiT[wi] = take((int64_t)N * K * 2); p.w_loT[wi] = take((int64_t)N * K * 2);
+        p.w_hi[wi] = take((int64_t)N * K * 2); p.w_lo[wi] = pair((int64_t)N * K * 2);
+        p.w_hiT[wi] = take((int64_t)N * K * 2); p.w_loT[wi] = pair((int64_t)N * K * 2);
     }
     p.tn_partial = take(kTnScratchBytes);
     p.ones_words = ln_maskbits_bytes(M, (int)D) / 4;
     p.ones = take(ln_maskbits_bytes(M, (int)D));
-    p.p_hi = take(B * np * Kpe * 2); p.p_lo = take(B * np * Kpe * 2);
+    p.p_hi = take(B * np * Kpe * 2); p.p_lo = pair(B * np * Kpe * 2);
     p.Y0 = take(B * np * D * 4);
     for (int i = 0; i < c.depth; ++i) {
         FsBlock& k = p.blk[i];
         k.x = take(M * D * 4); k.xm = take(M * D * 4);
-        k.h1_hi = take(M * D * 2); k.h1_lo = take(M * D * 2); k.h2_hi = take(M * D * 2); k.h2_lo = take(M * D * 2);
+        k.h1_hi = take(M * D * 2); k.h1_lo = pair(M * D * 2); k.h2_hi = take(M * D * 2); k.h2_lo = pair(M * D * 2);
         k.mean1 = take(M * 4); k.rstd1 = take(M * 4); k.mean2 = take(M * 4); k.rstd2 = take(M * 4);
         k.qkv = take(M * 3 * D * 4);
-        k.O_hi = take(M * D * 2); k.O_lo = take(M * D * 2);
+        k.O_hi = take(M * D * 2); k.O_lo = pair(M * D * 2);
         k.lse = take(B * H * T * 4);
         k.Y1 = take(M * Hd * 4);
-        k.G_hi = take(M * Hd * 2); k.G_lo = take(M * Hd * 2);
+        k.G_hi = take(M * Hd * 2); k.G_lo = pair(M * Hd * 2);
     }
     p.x_last = take(M * D * 4);
     p.meanf = take(M * 4); p.rstdf = take(M * 4);
-    p.hf_hi = take(M * D * 2); p.hf_lo = take(M * D * 2);
+    p.hf_hi = take(M * D * 2); p.hf_lo = pair(M * D * 2);
     p.hn = take(B * D * 4);
     p.Y = take(M * D * 4);
     p.dx = take(M * D * 4); p.dx2 = take(M * D * 4);
-    p.dp_hi = take(M * D * 2); p.dp_lo = take(M * D * 2);
+    p.dp_hi = take(M * D * 2); p.dp_lo = pair(M * D * 2);
     p.dG = take(M * Hd * 4);
-    p.dY1_hi = take(M * Hd * 2); p.dY1_lo = take(M * Hd * 2);
+    p.dY1_hi = take(M * Hd * 2); p.dY1_lo = pair(M * Hd * 2);
     p.dh = take(M * D * 4);
     p.dO = take(M * D * 4);
-    p.dqkv_hi = take(M * 3 * D * 2); p.dqkv_lo = take(M * 3 * D * 2);
-    p.Pm = take(B * H * T * T * 4); p.dS = take(B * H * T * T * 4);
-    p.delta = take(B * H * T * 4);
+    p.dqkv_hi = take(M * 3 * D * 2); p.dqkv_lo = pair(M * 3 * D * 2);
+    p.Pm = pair(B * H * T * T * 4); p.dS = pair(B * H * T * T * 4);
+    p.delta = pair(B * H * T * 4);
     p.dhn = take(B * D * 4);
-    p.dY0_hi = take(B * np * D * 2); p.dY0_lo = take(B * np * D * 2);
+    p.dY0_hi = take(B * np * D * 2); p.dY0_lo = pair(B * np * D * 2);
     p.total = o;
     return p;
 }
 
-int64_t qatvit_float_student_workspace_bytes(const qatvit_cfg* cfg) {
-    if (!cfg) { set_error("qatvit_float_student_workspace_bytes: null argument"); return -1; }
-    if (fs_check(*cfg)) return -1;
-    return fs_plan(*cfg).total;
+static int64_t fs_workspace_bytes(const char* fn, bool f16, const qatvit_cfg* cfg) {
+    if (!cfg) { set_error("%s: null argument", fn); return -1; }
+    if (fs_check(*cfg, f16)) return -1;
+    return fs_plan(*cfg, f16).total;
 }
 
 static void fs_consts(const FsPlan& p, char* ws, hipStream_t st) {
     k_fs_consts<<<flat_grid_fs(p.ones_words), 256, 0, st>>>(reinterpret_cast<float*>(ws + p.qp_off), reinterpret_cast<uint32_t*>(ws + p.ones), p.ones_words);
 }
 
-int qatvit_float_student_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && workspace, "qatvit_float_student_init: null argument");
-    if (fs_check(*cfg)) return 1;
-    fs_consts(fs_plan(*cfg), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
-    QV_CHECK_LAUNCH("qatvit_float_student_init");
+static int fs_init(const char* fn, bool f16, const qatvit_cfg* cfg, void* workspace, void* stream) {
+    QV_CHECK_ARG(cfg && workspace, "%s: null argument", fn);
+    if (fs_check(*cfg, f16)) return 1;
+    fs_consts(fs_plan(*cfg, f16), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
+    QV_CHECK_LAUNCH(fn);
     return 0;
 }
 
@@ -408,10 +417,6 @@ struct ObsPlan {
 };
 static int fs_n_act(const qatvit_cfg& c) { return 4 + 6 * c.depth; }
 static int fs_n_w(const qatvit_cfg& c) { return 2 + 4 * c.depth; }
-static void fs_wshape_all(const qatvit_cfg& c, int wi, int* N, int* K) {   // fs_weight_shape plus the head (the last weight quantizer)
-    if (wi == 1 + 4 * c.depth) { *N = c.num_classes; *K = c.embed_dim; return; }
-    fs_weight_shape(c, wi, N, K);
-}
 static ObsPlan obs_plan(const qatvit_cfg& c) {
     ObsPlan p{};
     p.n_act = fs_n_act(c);
@@ -423,7 +428,7 @@ static ObsPlan obs_plan(const qatvit_cfg& c) {
     p.nblocks = p.n_act;
     for (int wi = 0; wi < p.n_w; ++wi) {
         int N, K;
-        fs_wshape_all(c, wi, &N, &K);
+        fs_weight_shape(c, wi, &N, &K);
         p.w_stats[wi] = words;
         words += c.w_per_channel ? 2 * (int64_t)N : kStatSlots * kStatStride;
         p.nblocks += c.w_per_channel ? (N + 63) / 64 : 1;
@@ -441,107 +446,257 @@ struct FsObs {
     uint32_t* w(int wi) const { return stats + p->w_stats[wi]; }
 };
 
-static int fs_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, hipStream_t st, const FsObs& ob) {
+// params: fp32 tensors in the student's order (include/qatvit.h).  Leaves in the workspace everything fs_backward reads.  logits: fp32, or fp16 (f16).
+// observe (the pair form only): also every observer's step (qatvit_float_student_forward_observe).
+static int fs_forward(const char* fn, bool f16, const qatvit_cfg* cfg, void* const* params, const float* images, void* logits, void* workspace,
+                      void* observe, void* stream) {
+    QV_CHECK_ARG(cfg && params && images && logits && workspace, "%s: null argument", fn);
+    if (fs_check(*cfg, f16)) return 1;
     const qatvit_cfg& c = *cfg;
-    const FsPlan p = fs_plan(c);
+    const FsPlan p = fs_plan(c, f16);
+    ObsPlan op{};
+    FsObs ob;
+    if (observe) {
+        op = obs_plan(c);
+        ob.stats = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(observe) + op.act_stats);
+        ob.p = &op;
+    }
     char* ws = reinterpret_cast<char*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
     const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden;
     const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth;
     const int64_t M = (int64_t)c.batch * T;
     auto F = [&](int64_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto V = [&](int64_t off) { return reinterpret_cast<void*>(ws + off); };
+    auto V = [&](int64_t off) { return off < 0 ? nullptr : reinterpret_cast<void*>(ws + off); };
     auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
     auto bprm = [&](int blk, int k) { return prm(4 + 12 * blk + k); };
-    fs_consts(p, ws, st);   // (cheap; a workspace bound at another batch keeps working without a second init)
-    {   // the weights' (hi, lo) pairs, as stored and transposed, in one launch
+    // ---- the form's steps
+    auto weight_planes = [&] {   // the weights' (hi, lo) pairs or fp16 planes, as stored and transposed, in one launch
         FsWTab t{};
         t.n = 1 + 4 * L;
         int blocks = 0;
         for (int wi = 0; wi < t.n; ++wi) {
             fs_weight_shape(c, wi, &t.N[wi], &t.K[wi]);
-            static const int kW[4] = {2, 4, 8, 10};   // qkv, proj, fc1, fc2 weights within a block's 12 parameters
-            t.W[wi] = wi == 0 ? prm(0) : bprm((wi - 1) / 4, kW[(wi - 1) % 4]);
-            t.hi[wi] = reinterpret_cast<__bf16*>(ws + p.w_hi[wi]); t.lo[wi] = reinterpret_cast<__bf16*>(ws + p.w_lo[wi]);
-            t.hiT[wi] = reinterpret_cast<__bf16*>(ws + p.w_hiT[wi]); t.loT[wi] = reinterpret_cast<__bf16*>(ws + p.w_loT[wi]);
+            t.W[wi] = prm(fs_weight_param(c, wi));
+            t.hi[wi] = reinterpret_cast<__bf16*>(V(p.w_hi[wi])); t.lo[wi] = reinterpret_cast<__bf16*>(V(p.w_lo[wi]));
+            t.hiT[wi] = reinterpret_cast<__bf16*>(V(p.w_hiT[wi])); t.loT[wi] = reinterpret_cast<__bf16*>(V(p.w_loT[wi]));
             t.blk0[wi] = blocks;
             blocks += ((t.N[wi] + 31) / 32) * ((t.K[wi] + 31) / 32);
         }
         t.blk0[t.n] = blocks;
-        k_fs_wsplit<<<blocks, 256, 0, st>>>(t);
-    }
+        if (f16) launch_fa_wcast(t.n, t.W, reinterpret_cast<void* const*>(t.hi), reinterpret_cast<void* const*>(t.hiT), t.N, t.K, t.blk0, st);
+        else k_fs_wsplit<<<blocks, 256, 0, st>>>(t);
+    };
     // (act_fq order: 0 quant, 1 patch_embed.proj, per block 2 + 6 i + {norm1, qkv, proj, norm2, fc1, fc2}, then norm, head)
     auto gemm = [&](int64_t ah, int64_t al, int wi, const float* bias, float* C, int N, int K, int Mrows, int ai) {
         return launch_gemm_nt(V(ah), V(al), V(p.w_hi[wi]), C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, ob.act(ai), ob.stats ? kStatSlots : 1, st,
-                              V(p.w_lo[wi]), nullptr);
+                              V(p.w_lo[wi]), nullptr, f16);
     };
+    auto gelu = [&](const FsBlock& k) {
+        if (f16) launch_fa_gelu(F(k.Y1), V(k.G_hi), M * Hd, st);
+        else launch_gelu_split(F(k.Y1), V(k.G_hi), V(k.G_lo), M * Hd, st);
+    };
+    auto head = [&](const float* gamma, const float* beta, const float* W, const float* bias) {
+        if (f16)
+            launch_fa_head_fwd(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn), logits, c.batch, D, T, c.num_classes, st);
+        else if (ob.stats)
+            k_fs_head_fwd<true><<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn),
+                                                                        reinterpret_cast<float*>(logits), D, T, c.num_classes, ob.act(3 + 6 * L));
+        else
+            k_fs_head_fwd<<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn),
+                                                                  reinterpret_cast<float*>(logits), D, T, c.num_classes);
+    };
+    fs_consts(p, ws, st);   // (cheap; a workspace bound at another batch keeps working without a second init)
+    weight_planes();
     if (ob.stats) {   // re-arm every accumulator; the images' and the weights' statistics (the QAT forward's weight pass, fq.hip k_w_observe_all)
-        launch_ws_init(ob.stats, ob.p->stats_words / 2, st);
+        launch_ws_init(ob.stats, op.stats_words / 2, st);
         launch_minmax(images, 1, (int64_t)c.batch * c.in_chans * c.img_size * c.img_size, 0, ob.act(0), kStatSlots, st);
         WObsTab to{};
-        to.n = ob.p->n_w;
+        to.n = op.n_w;
         to.per_channel = c.w_per_channel;
         to.nslots = kStatSlots;
         for (int wi = 0; wi < to.n; ++wi) {
-            static const int kW[4] = {2, 4, 8, 10};
-            fs_wshape_all(c, wi, &to.N[wi], &to.K[wi]);
-            to.W[wi] = wi == 0 ? prm(0) : wi == 1 + 4 * L ? prm(4 + 12 * L + 2) : bprm((wi - 1) / 4, kW[(wi - 1) % 4]);
+            fs_weight_shape(c, wi, &to.N[wi], &to.K[wi]);
+            to.W[wi] = prm(fs_weight_param(c, wi));
             to.ws[wi] = ob.w(wi);
         }
         launch_w_observe_all(to, st);
     }
-    launch_patches_split(images, V(p.p_hi), V(p.p_lo), c.batch, c.in_chans, c.img_size, c.img_size, c.patch_size, st);
+    launch_patches_split(images, V(p.p_hi), V(p.p_lo), c.batch, c.in_chans, c.img_size, c.img_size, c.patch_size, st, f16);
     if (gemm(p.p_hi, p.p_lo, 0, prm(1), F(p.Y0), D, Kpe, c.batch * np, 1)) return 1;
     launch_resid_ln_split_save(0, nullptr, F(p.Y0), prm(2), prm(3), F(p.blk[0].x), bprm(0, 0), bprm(0, 1), c.ln_eps, V(p.blk[0].h1_hi), V(p.blk[0].h1_lo),
-                               F(p.blk[0].mean1), F(p.blk[0].rstd1), M, D, T, st, ob.act(2));
+                               F(p.blk[0].mean1), F(p.blk[0].rstd1), M, D, T, st, ob.act(2), f16);
     for (int i = 0; i < L; ++i) {
         const FsBlock& k = p.blk[i];
         const int w0 = 1 + 4 * i, a0 = 2 + 6 * i;
         if (gemm(k.h1_hi, k.h1_lo, w0 + 0, bprm(i, 3), F(k.qkv), 3 * D, D, (int)M, a0 + 1)) return 1;
-        if (launch_attn_fwd_float(F(k.qkv), c.batch, T, c.num_heads, D, V(k.O_hi), V(k.O_lo), st, 0, F(k.lse))) return 1;
+        if (launch_attn_fwd_float(F(k.qkv), c.batch, T, c.num_heads, D, V(k.O_hi), V(k.O_lo), st, f16, F(k.lse))) return 1;
         if (gemm(k.O_hi, k.O_lo, w0 + 1, bprm(i, 5), F(p.Y), D, D, (int)M, a0 + 2)) return 1;
         launch_resid_ln_split_save(1, F(k.x), F(p.Y), nullptr, nullptr, F(k.xm), bprm(i, 6), bprm(i, 7), c.ln_eps, V(k.h2_hi), V(k.h2_lo), F(k.mean2),
-                                   F(k.rstd2), M, D, T, st, ob.act(a0 + 3));
+                                   F(k.rstd2), M, D, T, st, ob.act(a0 + 3), f16);
         if (gemm(k.h2_hi, k.h2_lo, w0 + 2, bprm(i, 9), F(k.Y1), Hd, D, (int)M, a0 + 4)) return 1;
-        launch_gelu_split(F(k.Y1), V(k.G_hi), V(k.G_lo), M * Hd, st);
+        gelu(k);
         if (gemm(k.G_hi, k.G_lo, w0 + 3, bprm(i, 11), F(p.Y), D, Hd, (int)M, a0 + 5)) return 1;
         const bool last = i + 1 == L;
         const FsBlock* nx = last ? nullptr : &p.blk[i + 1];
         launch_resid_ln_split_save(1, F(k.xm), F(p.Y), nullptr, nullptr, last ? F(p.x_last) : F(nx->x), last ? prm(4 + 12 * L) : bprm(i + 1, 0),
                                    last ? prm(4 + 12 * L + 1) : bprm(i + 1, 1), c.ln_eps, last ? V(p.hf_hi) : V(nx->h1_hi), last ? V(p.hf_lo) : V(nx->h1_lo),
-                                   last ? F(p.meanf) : F(nx->mean1), last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, ob.act(last ? 2 + 6 * L : a0 + 6));
+                                   last ? F(p.meanf) : F(nx->mean1), last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, ob.act(last ? 2 + 6 * L : a0 + 6), f16);
     }
     const int hb = 4 + 12 * L;
-    if (ob.stats) {
-        k_fs_head_fwd<true><<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3),
-                                                                    F(p.hn), logits, D, T, c.num_classes, ob.act(3 + 6 * L));
-        // every observer at once: nothing in this forward read the quantisers' state, so folding at the end is the stock update
-        launch_obs_fold(reinterpret_cast<const ObsFoldEntry*>(reinterpret_cast<char*>(ob.stats) - ob.p->act_stats + ob.p->tab), ob.p->n_act + ob.p->n_w,
-                        ob.p->nblocks, c.averaging_const, st);
-    } else {
-        k_fs_head_fwd<<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3), F(p.hn),
-                                                              logits, D, T, c.num_classes);
-    }
+    head(prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3));
+    if (ob.stats)   // every observer at once: nothing in this forward read the quantisers' state, so folding at the end is the stock update
+        launch_obs_fold(reinterpret_cast<const ObsFoldEntry*>(reinterpret_cast<char*>(observe) + op.tab), op.n_act + op.n_w, op.nblocks, c.averaging_const, st);
+    QV_CHECK_LAUNCH(fn);
     return 0;
 }
 
-// params: fp32 tensors in the student's order (include/qatvit.h).  Leaves in the workspace everything qatvit_float_student_backward reads.
-int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && params && images && logits && workspace, "qatvit_float_student_forward: null argument");
-    if (fs_check(*cfg)) return 1;
-    if (fs_forward(cfg, params, images, logits, workspace, (hipStream_t)stream, FsObs{})) return 1;
-    QV_CHECK_LAUNCH("qatvit_float_student_forward");
+// dlogits [B, C]: fp32, or fp16 (f16); grads: fp32 tensors in the params order, ZERO on entry (weight / bias / LayerNorm gradients are accumulated
+// into them).  Reads what the last fs_forward of the same form on this workspace (same cfg) left there.
+static int fs_backward(const char* fn, bool f16, const qatvit_cfg* cfg, void* const* params, const void* dlogits, void* const* grads, void* workspace,
+                       void* stream) {
+    QV_CHECK_ARG(cfg && params && dlogits && grads && workspace, "%s: null argument", fn);
+    if (fs_check(*cfg, f16)) return 1;
+    const qatvit_cfg& c = *cfg;
+    const FsPlan p = fs_plan(c, f16);
+    char* ws = reinterpret_cast<char*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden, H = c.num_heads;
+    const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth, hb = 4 + 12 * L;
+    const int64_t M = (int64_t)c.batch * T;
+    auto F = [&](int64_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto V = [&](int64_t off) { return off < 0 ? nullptr : reinterpret_cast<void*>(ws + off); };
+    auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
+    auto grd = [&](int i) { return reinterpret_cast<float*>(grads[i]); };
+    const float* qp_off = F(p.qp_off);
+    const float* one = qp_off;   // 1.0f: the unit scale of the one-plane GEMMs
+    float* partial = F(p.tn_partial);
+    // ---- the form's steps
+    // dgrad: C[M, N] = A[M, K] . W[K, N]  with the transposed weight's planes as the B operand ([N, K] row-major)
+    auto dgrad = [&](int64_t ah, int64_t al, int wi, float* C, int N, int K) {
+        if (f16) return launch_gemm_nt_dy16(V(ah), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, one, one, st);
+        return launch_gemm_nt(V(ah), V(al), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st, V(p.w_loT[wi]), nullptr);
+    };
+    // wgrad: dW[N, Kw] += dY[Mr, N]^T . X[Mr, Kw], dbias[N] += column sums of dY
+    auto wgrad = [&](int64_t ph, int64_t pl, int64_t qh, int64_t ql, float* dW, float* db, int N, int Kw, int Mr) {
+        if (f16)
+            return launch_gemm_tn_dy16(V(ph), V(qh), nullptr, dW, Mr, N, Kw, N, Kw, Kw, one, one, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
+                                       kTnScratchBytes);
+        return launch_gemm_tn(V(ph), V(pl), V(qh), V(ql), dW, Mr, N, Kw, N, Kw, Kw, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
+                              kTnScratchBytes);
+    };
+    auto head = [&] {   // dhn, and the head's weight / bias gradients
+        if (f16) {
+            launch_fa_head_bwd(dlogits, F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), c.batch, D, c.num_classes, st);
+            return;
+        }
+        const int64_t n = (int64_t)c.num_classes * D + (int64_t)c.batch * D + c.num_classes;
+        k_fs_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const float*>(dlogits), F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn),
+                                                              c.batch, D, c.num_classes);
+    };
+    auto gelu_bwd = [&](const FsBlock& k) {   // dY1 = dG * gelu'(Y1)
+        if (f16) return launch_fa_gelu_bwd(F(p.dG), F(k.Y1), V(p.dY1_hi), M * Hd, st);
+        return launch_mask_bwd(1, F(p.dG), F(k.Y1), qp_off, 0, 255, nullptr, Hd, V(p.dY1_hi), V(p.dY1_lo), M * Hd, st);
+    };
+    auto attn_bwd = [&](const FsBlock& k) {   // dqkv from dO
+        if (f16) return launch_attn_bwd_f16(F(k.qkv), V(k.O_hi), F(k.lse), F(p.dO), c.batch, T, H, D, V(p.dqkv_hi), st);
+        return launch_attn_bwd_float(F(k.qkv), V(k.O_hi), V(k.O_lo), F(k.lse), F(p.dO), c.batch, T, H, D, F(p.Pm), F(p.dS), F(p.delta), V(p.dqkv_hi),
+                                     V(p.dqkv_lo), st);
+    };
+    auto embed_bwd = [&] {   // pos / cls gradients and dY0 (the patch rows of dx)
+        if (f16) launch_fa_embed_bwd(F(p.dx), grd(3), grd(2), V(p.dY0_hi), c.batch, T, D, st);
+        else launch_embed_bwd(F(p.dx), F(p.Y0), qp_off, 0, 255, grd(3), grd(2), V(p.dY0_hi), V(p.dY0_lo), c.batch, T, D, st);
+    };
+    auto fp16_overflow = [&] {   // the fp16 form: the overflow rule of the fp16 Linear / Conv2d weight and bias gradients
+        if (!f16) return;
+        float* g[2 * kMaxW];
+        int64_t n[2 * kMaxW];
+        int count = 0;
+        for (int wi = 0; wi < 2 + 4 * L; ++wi) {
+            int N, K;
+            fs_weight_shape(c, wi, &N, &K);
+            const int pi = fs_weight_param(c, wi);
+            g[count] = grd(pi); n[count++] = (int64_t)N * K;
+            g[count] = grd(pi + 1); n[count++] = N;
+        }
+        launch_fa_inf_rule(g, n, count, st);
+    };
+    // the LayerNorm backward's second output: the residual gradient as the next branch's GEMM operand dp (mask all ones; the fp16 form: unit multiplier)
+    LnBwdNext next{V(p.ones), nullptr, V(p.dp_hi), V(p.dp_lo), f16 ? one : nullptr, reinterpret_cast<uint32_t*>(V(p.amax))};
+    // head, then the final norm on the cls rows (dx of every other row = 0); the residual gradient leaves as fp32 (dx) and as dp
+    head();
+    if (launch_ln_bwd_fq(0, F(p.dhn), F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), qp_off, 0, 255, nullptr, F(p.dx), grd(hb), grd(hb + 1), M, D, T,
+                         1, st, &next))
+        return 1;
+    for (int i = L - 1; i >= 0; --i) {
+        const FsBlock& k = p.blk[i];
+        const int w0 = 1 + 4 * i, g0 = 4 + 12 * i;
+        // fc2 (input G = gelu(Y1)), then GELU' on the fc1 pre-activation
+        if (wgrad(p.dp_hi, p.dp_lo, k.G_hi, k.G_lo, grd(g0 + 10), grd(g0 + 11), D, Hd, (int)M)) return 1;
+        if (dgrad(p.dp_hi, p.dp_lo, w0 + 3, F(p.dG), Hd, D)) return 1;
+        if (gelu_bwd(k)) return 1;
+        // fc1 (input h2 = norm2(xm)), norm2 backward + the residual: dx2 = dx + LNbwd(dh2), and its dp for proj
+        if (wgrad(p.dY1_hi, p.dY1_lo, k.h2_hi, k.h2_lo, grd(g0 + 8), grd(g0 + 9), Hd, D, (int)M)) return 1;
+        if (dgrad(p.dY1_hi, p.dY1_lo, w0 + 2, F(p.dh), D, Hd)) return 1;
+        if (launch_ln_bwd_fq(1, F(p.dh), F(k.xm), F(k.mean2), F(k.rstd2), prm(g0 + 6), prm(g0 + 7), qp_off, 0, 255, F(p.dx), F(p.dx2), grd(g0 + 6), grd(g0 + 7), M,
+                             D, T, 0, st, &next))
+            return 1;
+        // proj (input O), attention, qkv (input h1 = norm1(x)); norm1 backward: dx = dx2 + LNbwd(dh1), the gradient of the block's input
+        if (wgrad(p.dp_hi, p.dp_lo, k.O_hi, k.O_lo, grd(g0 + 4), grd(g0 + 5), D, D, (int)M)) return 1;
+        if (dgrad(p.dp_hi, p.dp_lo, w0 + 1, F(p.dO), D, D)) return 1;
+        if (attn_bwd(k)) return 1;
+        if (wgrad(p.dqkv_hi, p.dqkv_lo, k.h1_hi, k.h1_lo, grd(g0 + 2), grd(g0 + 3), 3 * D, D, (int)M)) return 1;
+        if (dgrad(p.dqkv_hi, p.dqkv_lo, w0 + 0, F(p.dh), D, 3 * D)) return 1;
+        if (launch_ln_bwd_fq(1, F(p.dh), F(k.x), F(k.mean1), F(k.rstd1), prm(g0 + 0), prm(g0 + 1), qp_off, 0, 255, F(p.dx2), F(p.dx), grd(g0 + 0), grd(g0 + 1), M,
+                             D, T, 0, st, i > 0 ? &next : nullptr))
+            return 1;
+    }
+    // embedding, then the patch-embedding weight gradient over the saved patches
+    embed_bwd();
+    if (wgrad(p.dY0_hi, p.dY0_lo, p.p_hi, p.p_lo, grd(0), grd(1), D, Kpe, c.batch * np)) return 1;
+    fp16_overflow();
+    QV_CHECK_LAUNCH(fn);
     return 0;
+}
+
+// ---------------------------------------------------------------- the C ABI (include/qatvit.h)
+int64_t qatvit_float_student_workspace_bytes(const qatvit_cfg* cfg) { return fs_workspace_bytes("qatvit_float_student_workspace_bytes", false, cfg); }
+
+int qatvit_float_student_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
+    return fs_init("qatvit_float_student_init", false, cfg, workspace, stream);
+}
+
+int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream) {
+    return fs_forward("qatvit_float_student_forward", false, cfg, params, images, logits, workspace, nullptr, stream);
+}
+
+int qatvit_float_student_backward(const qatvit_cfg* cfg, void* const* params, const float* dlogits, void* const* grads, void* workspace, void* stream) {
+    return fs_backward("qatvit_float_student_backward", false, cfg, params, dlogits, grads, workspace, stream);
+}
+
+int64_t qatvit_float_student_amp_workspace_bytes(const qatvit_cfg* cfg) { return fs_workspace_bytes("qatvit_float_student_amp_workspace_bytes", true, cfg); }
+
+int qatvit_float_student_amp_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
+    return fs_init("qatvit_float_student_amp_init", true, cfg, workspace, stream);
+}
+
+int qatvit_float_student_amp_forward(const qatvit_cfg* cfg, void* const* params, const float* images, void* logits_f16, void* workspace, void* stream) {
+    return fs_forward("qatvit_float_student_amp_forward", true, cfg, params, images, logits_f16, workspace, nullptr, stream);
+}
+
+int qatvit_float_student_amp_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_f16, void* const* grads, void* workspace, void* stream) {
+    return fs_backward("qatvit_float_student_amp_backward", true, cfg, params, dlogits_f16, grads, workspace, stream);
 }
 
 int64_t qatvit_float_student_observe_bytes(const qatvit_cfg* cfg) {
     if (!cfg) { set_error("qatvit_float_student_observe_bytes: null argument"); return -1; }
-    if (fs_check(*cfg)) return -1;
+    if (fs_check(*cfg, false)) return -1;
     return obs_plan(*cfg).total;
 }
 
 int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* act_fq, const qatvit_fq* weight_fq, void* observe, void* stream) {
     QV_CHECK_ARG(cfg && act_fq && weight_fq && observe, "qatvit_float_student_observe_init: null argument");
-    if (fs_check(*cfg)) return 1;
+    if (fs_check(*cfg, false)) return 1;
     const qatvit_cfg& c = *cfg;
     const ObsPlan p = obs_plan(c);
     char* ob = reinterpret_cast<char*>(observe);
@@ -557,7 +712,7 @@ int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* ac
     for (int wi = 0; wi < p.n_w; ++wi) {
         const qatvit_fq& f = weight_fq[wi];
         int N, K;
-        fs_wshape_all(c, wi, &N, &K);
+        fs_weight_shape(c, wi, &N, &K);
         tab[p.n_act + wi] = ObsFoldEntry{stats + p.w_stats[wi], f.min_val, f.max_val, f.scale, f.zero_point, f.observer_on, f.fake_quant_on,
                                          c.w_per_channel ? N : 1, c.w_per_channel ? 1 : kStatSlots, 1, c.w_qmin, c.w_qmax, blk};
         blk += c.w_per_channel ? (N + 63) / 64 : 1;
@@ -575,82 +730,8 @@ int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* ac
 
 int qatvit_float_student_forward_observe(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* observe,
                                          void* stream) {
-    QV_CHECK_ARG(cfg && params && images && logits && workspace && observe, "qatvit_float_student_forward_observe: null argument");
-    if (fs_check(*cfg)) return 1;
-    const ObsPlan p = obs_plan(*cfg);
-    FsObs ob;
-    ob.stats = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(observe) + p.act_stats);
-    ob.p = &p;
-    if (fs_forward(cfg, params, images, logits, workspace, (hipStream_t)stream, ob)) return 1;
-    QV_CHECK_LAUNCH("qatvit_float_student_forward_observe");
-    return 0;
-}
-
-// dlogits [B, C] fp32; grads: fp32 tensors in the params order, ZERO on entry (weight / bias / LayerNorm gradients are accumulated into them).
-// Reads what the last qatvit_float_student_forward on this workspace (same cfg) left there.
-int qatvit_float_student_backward(const qatvit_cfg* cfg, void* const* params, const float* dlogits, void* const* grads, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && params && dlogits && grads && workspace, "qatvit_float_student_backward: null argument");
-    if (fs_check(*cfg)) return 1;
-    const qatvit_cfg& c = *cfg;
-    const FsPlan p = fs_plan(c);
-    char* ws = reinterpret_cast<char*>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden, H = c.num_heads;
-    const int Kpe = c.in_chans * c.patch_size * c.patch_size, L = c.depth;
-    const int64_t M = (int64_t)c.batch * T;
-    auto F = [&](int64_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto V = [&](int64_t off) { return reinterpret_cast<void*>(ws + off); };
-    auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
-    auto grd = [&](int i) { return reinterpret_cast<float*>(grads[i]); };
-    const float* qp_off = F(p.qp_off);
-    float* partial = F(p.tn_partial);
-    // dgrad: C[M, N] = A[M, K] . W[K, N]  with A a pair and W^T's pair as the B operand ([N, K] row-major)
-    auto dgrad = [&](int64_t ah, int64_t al, int wi, float* C, int N, int K) {
-        return launch_gemm_nt(V(ah), V(al), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st, V(p.w_loT[wi]), nullptr);
-    };
-    // wgrad: dW[N, Kw] += dY[Mr, N]^T . X[Mr, Kw], dbias[N] += column sums of dY
-    auto wgrad = [&](int64_t ph, int64_t pl, int64_t qh, int64_t ql, float* dW, float* db, int N, int Kw, int Mr) {
-        return launch_gemm_tn(V(ph), V(pl), V(qh), V(ql), dW, Mr, N, Kw, N, Kw, Kw, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
-                              kTnScratchBytes);
-    };
-    LnBwdNext next{V(p.ones), nullptr, V(p.dp_hi), V(p.dp_lo)};
-    // head, then the final norm on the cls rows (dx of every other row = 0); the residual gradient leaves as fp32 (dx) and as a pair (dp)
-    const int hb = 4 + 12 * L;
-    {
-        const int64_t n = (int64_t)c.num_classes * D + (int64_t)c.batch * D + c.num_classes;
-        k_fs_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(dlogits, F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), c.batch, D, c.num_classes);
-    }
-    if (launch_ln_bwd_fq(0, F(p.dhn), F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), qp_off, 0, 255, nullptr, F(p.dx), grd(hb), grd(hb + 1), M, D, T,
-                         1, st, &next))
-        return 1;
-    for (int i = L - 1; i >= 0; --i) {
-        const FsBlock& k = p.blk[i];
-        const int w0 = 1 + 4 * i, g0 = 4 + 12 * i;
-        // fc2 (input G = gelu(Y1)), then GELU' on the fc1 pre-activation
-        if (wgrad(p.dp_hi, p.dp_lo, k.G_hi, k.G_lo, grd(g0 + 10), grd(g0 + 11), D, Hd, (int)M)) return 1;
-        if (dgrad(p.dp_hi, p.dp_lo, w0 + 3, F(p.dG), Hd, D)) return 1;
-        if (launch_mask_bwd(1, F(p.dG), F(k.Y1), qp_off, 0, 255, nullptr, Hd, V(p.dY1_hi), V(p.dY1_lo), M * Hd, st)) return 1;
-        // fc1 (input h2 = norm2(xm)), norm2 backward + the residual: dx2 = dx + LNbwd(dh2), and its pair for proj
-        if (wgrad(p.dY1_hi, p.dY1_lo, k.h2_hi, k.h2_lo, grd(g0 + 8), grd(g0 + 9), Hd, D, (int)M)) return 1;
-        if (dgrad(p.dY1_hi, p.dY1_lo, w0 + 2, F(p.dh), D, Hd)) return 1;
-        if (launch_ln_bwd_fq(1, F(p.dh), F(k.xm), F(k.mean2), F(k.rstd2), prm(g0 + 6), prm(g0 + 7), qp_off, 0, 255, F(p.dx), F(p.dx2), grd(g0 + 6), grd(g0 + 7), M,
-                             D, T, 0, st, &next))
-            return 1;
-        // proj (input O), attention, qkv (input h1 = norm1(x)); norm1 backward: dx = dx2 + LNbwd(dh1), the gradient of the block's input
-        if (wgrad(p.dp_hi, p.dp_lo, k.O_hi, k.O_lo, grd(g0 + 4), grd(g0 + 5), D, D, (int)M)) return 1;
-        if (dgrad(p.dp_hi, p.dp_lo, w0 + 1, F(p.dO), D, D)) return 1;
-        launch_attn_bwd_float(F(k.qkv), V(k.O_hi), V(k.O_lo), F(k.lse), F(p.dO), c.batch, T, H, D, F(p.Pm), F(p.dS), F(p.delta), V(p.dqkv_hi), V(p.dqkv_lo), st);
-        if (wgrad(p.dqkv_hi, p.dqkv_lo, k.h1_hi, k.h1_lo, grd(g0 + 2), grd(g0 + 3), 3 * D, D, (int)M)) return 1;
-        if (dgrad(p.dqkv_hi, p.dqkv_lo, w0 + 0, F(p.dh), D, 3 * D)) return 1;
-        if (launch_ln_bwd_fq(1, F(p.dh), F(k.x), F(k.mean1), F(k.rstd1), prm(g0 + 0), prm(g0 + 1), qp_off, 0, 255, F(p.dx2), F(p.dx), grd(g0 + 0), grd(g0 + 1), M,
-                             D, T, 0, st, i > 0 ? &next : nullptr))
-            return 1;
-    }
-    // embedding: pos / cls gradients and dY0 (the patch rows of dx) as a pair, then the patch-embedding weight gradient over the saved patches
-    launch_embed_bwd(F(p.dx), F(p.Y0), qp_off, 0, 255, grd(3), grd(2), V(p.dY0_hi), V(p.dY0_lo), c.batch, T, D, st);
-    if (wgrad(p.dY0_hi, p.dY0_lo, p.p_hi, p.p_lo, grd(0), grd(1), D, Kpe, c.batch * np)) return 1;
-    QV_CHECK_LAUNCH("qatvit_float_student_backward");
-    return 0;
+    QV_CHECK_ARG(observe, "qatvit_float_student_forward_observe: null argument");
+    return fs_forward("qatvit_float_student_forward_observe", false, cfg, params, images, logits, workspace, observe, stream);
 }
 
 }  // extern "C"

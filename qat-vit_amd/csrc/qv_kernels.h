@@ -271,8 +271,26 @@ int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, co
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
                                uint32_t* stats = nullptr, int f16 = 0);
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st);   // n % 4 == 0
-// ---- float_amp.hip: the fp16 (autocast) form of the float student step.  Fused attention backward on v_mfma_f32_16x16x32_f16, one workgroup per
-// (image, head): qkv / dO fp32 [B*T, 3D] / [B*T, D] (rounded to fp16 on load), O16 fp16 [B*T, D], lse [B][H][T] -> dqkv16 fp16 [B*T, 3D]
+// ---- float_amp.hip: the fp16 (autocast) form of the float student step (its host driver is float_step.hip's).  Fused attention backward on
+// v_mfma_f32_16x16x32_f16, one workgroup per (image, head): qkv / dO fp32 [B*T, 3D] / [B*T, D] (rounded to fp16 on load), O16 fp16 [B*T, D],
+// lse [B][H][T] -> dqkv16 fp16 [B*T, 3D]
 int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st);
+// the n weights as fp16, as stored [N, K] and transposed, in one launch (blk0[wi]: first workgroup of weight wi, 32 x 32 tiles; blk0[n]: the total)
+int launch_fa_wcast(int n, const float* const* W, void* const* w16, void* const* w16T, const int* N, const int* K, const int* blk0, hipStream_t st);
+// head: hn = fp16(LN(cls rows)) kept as fp32 values, fp16 logits [B, C]; backward from fp16 dlogits (fixed summation order)
+int launch_fa_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias, float* hn,
+                       void* logits16, int B, int D, int T, int C, hipStream_t st);
+int launch_fa_head_bwd(const void* dl16, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st);
+int launch_fa_gelu(const float* Y, void* G16, int64_t n, hipStream_t st);                          // G16 = fp16(gelu(Y)), n % 4 == 0
+int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, hipStream_t st);     // dY16 = fp16(fp16(dG) gelu'(Y)), n % 4 == 0
+// dpos / dcls from dx [B*T, D] (fixed order), dY0_16 = fp16 of dx's patch rows
+int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16, int B, int T, int D, hipStream_t st);
+// the overflow rule of the fp16 Linear / Conv2d gradients on count <= 100 fp32 tensors g[k] of n[k] elements: g -> fp16(g) where that is +-inf
+int launch_fa_inf_rule(float* const* g, const int64_t* n, int count, hipStream_t st);
+// grid of the float step's flat elementwise kernels (float_step.hip, float_amp.hip)
+inline int flat_grid_fs(int64_t n) {
+    int64_t b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
 
 }  // namespace qv

@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 from torch.ao.quantization.fake_quantize import FusedMovingAvgObsFakeQuantize
 
-from . import native
+from . import float_engine, native
 
 STAGE_INJECT = 1  # QATVIT_STAGE_INJECT
 FWD_X16 = 2       # QATVIT_FWD_X16
@@ -200,11 +200,7 @@ def collect_student(wrapper: torch.nn.Module):
     m = wrapper.model
     blocks = list(m.blocks)
     pe = m.patch_embed.proj
-    ps = [pe.weight, pe.bias, m.cls_token, m.pos_embed]
-    for b in blocks:
-        ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias,
-               b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
-    ps += [m.norm.weight, m.norm.bias, m.head.weight, m.head.bias]
+    ps = native.vit_params(m)
     act = [_fq_of(wrapper.quant, "activation_post_process"), _fq_of(pe, "activation_post_process")]
     wfq = [_fq_of(pe, "weight_fake_quant")]
     for b in blocks:
@@ -275,7 +271,6 @@ class StudentEngine:
         self.device = dev
         self.lib = native.lib()
         blocks = list(m.blocks)
-        pe = m.patch_embed.proj
         ps, act, wfq = collect_student(wrapper)
         for p in ps:
             if p is None or p.dtype != torch.float32 or not p.is_contiguous():
@@ -298,16 +293,13 @@ class StudentEngine:
         self.fq_mode: Optional[str] = None       # the mode of the most recent forward
         # observe-only resources, allocated by the first observe-only forward beside the QAT workspace (which keeps the dy16 scale history and the
         # addresses a captured hipGraph is bound to)
-        self.f_workspace: Optional[torch.Tensor] = None
-        self.f_capacity = 0
+        self.float_form = float_engine.Form(*float_engine.FP32)
         self.observe_buf: Optional[torch.Tensor] = None
         hd = blocks[0].attn.head_dim
         self._cfg_kw = dict(
-            img_size=m.patch_embed.img_size, patch_size=m.patch_embed.patch_size, in_chans=pe.weight.shape[1],
-            embed_dim=m.embed_dim, depth=len(blocks), num_heads=blocks[0].attn.num_heads, mlp_hidden=blocks[0].mlp.fc1.weight.shape[0],
-            num_classes=m.head.weight.shape[0], act_qmin=a0.activation_post_process.quant_min, act_qmax=a0.activation_post_process.quant_max,
+            native.vit_shape(m), act_qmin=a0.activation_post_process.quant_min, act_qmax=a0.activation_post_process.quant_max,
             w_qmin=w0.activation_post_process.quant_min, w_qmax=w0.activation_post_process.quant_max, w_per_channel=int(w0.is_per_channel),
-            averaging_const=float(a0.activation_post_process.averaging_constant), ln_eps=float(blocks[0].norm1.eps),
+            averaging_const=float(a0.activation_post_process.averaging_constant),
         )
         self._cfgs: Dict[int, native.Cfg] = {}
         self.cfg = self.cfg_for(batch)           # the configuration of the most recent forward (tests read .cfg of the last step)
@@ -532,14 +524,7 @@ class StudentEngine:
             native.check(L.qatvit_float_student_observe_init(cp, self._act_structs, self._w_structs, buf.data_ptr(), native.stream_ptr()),
                          "qatvit_float_student_observe_init")
             self.observe_buf = buf
-        if c.batch > self.f_capacity:
-            n = L.qatvit_float_student_workspace_bytes(cp)
-            if n <= 0:
-                raise RuntimeError("observe-only step: " + L.qatvit_last_error().decode())
-            self.f_workspace = None
-            self.f_workspace = torch.empty(n, dtype=torch.uint8, device=self.device)
-            native.check(L.qatvit_float_student_init(cp, self.f_workspace.data_ptr(), native.stream_ptr()), "qatvit_float_student_init")
-            self.f_capacity = c.batch
+        self.float_form.reserve(c, self.device)
 
     def _forward_observe(self, images: torch.Tensor) -> torch.Tensor:
         """Stock semantics with fake_quant_enabled = 0 everywhere: the float network, whose observers (where observer_enabled = 1) still take their
@@ -555,7 +540,7 @@ class StudentEngine:
         self.generation += 1
         self._fwd_x16 = False
         native.check(self.lib.qatvit_float_student_forward_observe(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
-                                                                   self.f_workspace.data_ptr(), self.observe_buf.data_ptr(), native.stream_ptr()),
+                                                                   self.float_form.workspace.data_ptr(), self.observe_buf.data_ptr(), native.stream_ptr()),
                      "qatvit_float_student_forward_observe")
         return logits
 
@@ -563,8 +548,7 @@ class StudentEngine:
         """The float step's backward (every STE mask is 1: the gradient stock computes); in a data-parallel group one average of the whole flat
         gradient afterwards."""
         flat, views, gptr = self._grad_buffers()
-        native.check(self.lib.qatvit_float_student_backward(ctypes.byref(c), self._ptr_params, dlogits.contiguous().data_ptr(), gptr,
-                                                            self.f_workspace.data_ptr(), native.stream_ptr()), "qatvit_float_student_backward")
+        self.float_form.call("backward", ctypes.byref(c), self._ptr_params, dlogits.contiguous().data_ptr(), gptr)
         if self.pg is not None:
             if dist.get_backend(self.pg) == "nccl":
                 dist.all_reduce(flat, op=dist.ReduceOp.AVG, group=self.pg)

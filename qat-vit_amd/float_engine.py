@@ -26,15 +26,6 @@ from . import native
 _OPTED = weakref.WeakKeyDictionary()   # wrapper -> FloatStudentEngine (or None until its first CUDA forward)
 
 
-def _student_params(model: nn.Module) -> List[torch.Tensor]:
-    pe = model.patch_embed.proj
-    ps = [pe.weight, pe.bias, model.cls_token, model.pos_embed]
-    for b in model.blocks:
-        ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias,
-               b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
-    return ps + [model.norm.weight, model.norm.bias, model.head.weight, model.head.bias]
-
-
 def check_shape(model: nn.Module, amp: bool = False) -> None:
     """Raise unless the native float step covers this tree (the QAT engine's limits; amp: also the fp16 form's)."""
     from .vit import VisionTransformer
@@ -75,65 +66,70 @@ def check_shape(model: nn.Module, amp: bool = False) -> None:
         raise RuntimeError("native float step: unsupported model: " + "; ".join(why))
 
 
+# the two forms: (prefix of the C symbols, dtype of the logits and dlogits)
+FP32 = ("qatvit_float_student", torch.float32)        # fp32-accurate: bf16 (hi, lo) pairs, three MFMA passes
+FP16 = ("qatvit_float_student_amp", torch.float16)    # stock fp16 autocast
+
+
+class Form:
+    """One form of the float step: its C symbols and logits dtype, and its workspace with the batch that is sized for."""
+
+    def __init__(self, prefix: str, dtype: torch.dtype):
+        self.prefix, self.dtype = prefix, dtype
+        self.workspace: Optional[torch.Tensor] = None
+        self.capacity = 0
+
+    def call(self, name: str, *args) -> None:
+        """<prefix>_<name>(*args, workspace, stream), checked."""
+        fn = f"{self.prefix}_{name}"
+        native.check(getattr(native.lib(), fn)(*args, self.workspace.data_ptr(), native.stream_ptr()), fn)
+
+    def workspace_bytes(self, c: native.Cfg) -> int:
+        L = native.lib()
+        n = getattr(L, self.prefix + "_workspace_bytes")(ctypes.byref(c))
+        if n <= 0:
+            raise RuntimeError(f"{self.prefix}_workspace_bytes: " + L.qatvit_last_error().decode())
+        return n
+
+    def reserve(self, c: native.Cfg, device: torch.device) -> None:
+        if c.batch <= self.capacity:
+            return
+        nbytes = self.workspace_bytes(c)
+        self.workspace = None
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.capacity = c.batch
+        self.call("init", ctypes.byref(c))
+
+
 class FloatStudentEngine:
     def __init__(self, wrapper: nn.Module, amp: bool = False):
         model = wrapper.model
         check_shape(model, amp)
         self.amp = amp
         self.lib = native.lib()
-        self.params = _student_params(model)
+        self.params = native.vit_params(model)
         dev = self.params[0].device
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or not p.is_cuda:
                 raise RuntimeError("native float step: the parameters must be contiguous fp32 tensors on one CUDA device")
         self.device = dev
-        blocks = list(model.blocks)
-        pe = model.patch_embed.proj
-        self._cfg_kw = dict(
-            img_size=model.patch_embed.img_size, patch_size=model.patch_embed.patch_size, in_chans=pe.weight.shape[1], embed_dim=model.embed_dim,
-            depth=len(blocks), num_heads=blocks[0].attn.num_heads, mlp_hidden=blocks[0].mlp.fc1.weight.shape[0], num_classes=model.head.weight.shape[0],
-            act_qmin=0, act_qmax=255, w_qmin=-128, w_qmax=127, w_per_channel=0, averaging_const=0.01, ln_eps=float(blocks[0].norm1.eps),
-        )
+        self._cfg_kw = dict(native.vit_shape(model), act_qmin=0, act_qmax=255, w_qmin=-128, w_qmax=127, w_per_channel=0, averaging_const=0.01)
         self._ptrs_key = tuple(p.data_ptr() for p in self.params)
         self._ptr_params = (ctypes.c_void_p * len(self.params))(*self._ptrs_key)
-        self.workspace: Optional[torch.Tensor] = None
-        self.capacity = 0           # the batch the workspace is sized for
+        self.fp32, self.fp16 = Form(*FP32), Form(*FP16)   # each workspace allocated by the first forward of its form
         self.generation = 0         # bumped by every forward of either form: the workspaces hold the activations of exactly one forward
-        self.workspace16: Optional[torch.Tensor] = None   # the fp16 form's own workspace, allocated by the first autocast forward
-        self.capacity16 = 0
         self.grad_numel = sum(p.numel() for p in self.params)
 
     def cfg_for(self, batch: int) -> native.Cfg:
         return native.Cfg(batch=batch, **self._cfg_kw)
 
+    # the fp32 form's workspace, and each form's capacity, by the names callers read
+    workspace = property(lambda self: self.fp32.workspace)
+    capacity = property(lambda self: self.fp32.capacity)
+    capacity16 = property(lambda self: self.fp16.capacity)
+
     def workspace_bytes(self, batch: int) -> int:
-        n = self.lib.qatvit_float_student_workspace_bytes(ctypes.byref(self.cfg_for(batch)))
-        if n <= 0:
-            raise RuntimeError("qatvit_float_student_workspace_bytes: " + self.lib.qatvit_last_error().decode())
-        return n
-
-    def _reserve(self, batch: int) -> None:
-        if batch <= self.capacity:
-            return
-        nbytes = self.workspace_bytes(batch)
-        self.workspace = None
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.capacity = batch
-        native.check(self.lib.qatvit_float_student_init(ctypes.byref(self.cfg_for(batch)), self.workspace.data_ptr(), native.stream_ptr()),
-                     "qatvit_float_student_init")
-
-    def _reserve16(self, batch: int) -> None:
-        if batch <= self.capacity16:
-            return
-        c = self.cfg_for(batch)
-        nbytes = self.lib.qatvit_float_student_amp_workspace_bytes(ctypes.byref(c))
-        if nbytes <= 0:
-            raise RuntimeError("qatvit_float_student_amp_workspace_bytes: " + self.lib.qatvit_last_error().decode())
-        self.workspace16 = None
-        self.workspace16 = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.capacity16 = batch
-        native.check(self.lib.qatvit_float_student_amp_init(ctypes.byref(c), self.workspace16.data_ptr(), native.stream_ptr()),
-                     "qatvit_float_student_amp_init")
+        return self.fp32.workspace_bytes(self.cfg_for(batch))
 
     def stale(self) -> bool:
         return tuple(p.data_ptr() for p in self.params) != self._ptrs_key
@@ -145,41 +141,35 @@ class FloatStudentEngine:
         if not images.is_cuda or images.device != self.device:
             raise RuntimeError(f"native float step: images on {images.device}, parameters on {self.device}")
         images = images.to(torch.float32).contiguous()
-        if f16:
-            return self._forward16(images)
-        self._reserve(images.shape[0])
+        form = self.fp16 if f16 else self.fp32
         c = self.cfg_for(images.shape[0])
-        logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
+        form.reserve(c, self.device)
+        logits = torch.empty(c.batch, c.num_classes, dtype=form.dtype, device=self.device)
         self.generation += 1
-        native.check(self.lib.qatvit_float_student_forward(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
-                                                           self.workspace.data_ptr(), native.stream_ptr()), "qatvit_float_student_forward")
-        return logits
-
-    def _forward16(self, images: torch.Tensor) -> torch.Tensor:
-        self._reserve16(images.shape[0])
-        c = self.cfg_for(images.shape[0])
-        logits = torch.empty(c.batch, c.num_classes, dtype=torch.float16, device=self.device)
-        self.generation += 1
-        native.check(self.lib.qatvit_float_student_amp_forward(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
-                                                               self.workspace16.data_ptr(), native.stream_ptr()), "qatvit_float_student_amp_forward")
+        form.call("forward", ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr())
         return logits
 
     def backward(self, dlogits: torch.Tensor, batch: int, f16: bool = False) -> List[torch.Tensor]:
+        form = self.fp16 if f16 else self.fp32
         c = self.cfg_for(batch)
-        dlogits = dlogits.to(torch.float16 if f16 else torch.float32).contiguous()
+        dlogits = dlogits.to(form.dtype).contiguous()
         flat = torch.zeros(self.grad_numel, dtype=torch.float32, device=self.device)
         views, o = [], 0
         for p in self.params:
             views.append(flat[o:o + p.numel()].view(p.shape))
             o += p.numel()
         gptr = (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
-        if f16:
-            native.check(self.lib.qatvit_float_student_amp_backward(ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr,
-                                                                    self.workspace16.data_ptr(), native.stream_ptr()), "qatvit_float_student_amp_backward")
-        else:
-            native.check(self.lib.qatvit_float_student_backward(ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr, self.workspace.data_ptr(),
-                                                                native.stream_ptr()), "qatvit_float_student_backward")
+        form.call("backward", ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr)
         return views
+
+
+def _step_forward(ctx, images, engine, f16: bool):
+    ctx.engine = engine
+    out = engine.forward(images, f16)
+    ctx.generation = engine.generation
+    ctx.batch = images.shape[0]
+    ctx.f16 = f16
+    return out
 
 
 def _step_backward(ctx, dlogits):
@@ -206,12 +196,7 @@ class _FloatStudentStep(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, images, engine, *params):
-        ctx.engine = engine
-        out = engine.forward(images)
-        ctx.generation = engine.generation
-        ctx.batch = images.shape[0]
-        ctx.f16 = False
-        return out
+        return _step_forward(ctx, images, engine, False)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -225,12 +210,7 @@ class _FloatStudentAmpStep(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, images, engine, *params):
-        ctx.engine = engine
-        out = engine.forward(images, f16=True)
-        ctx.generation = engine.generation
-        ctx.batch = images.shape[0]
-        ctx.f16 = True
-        return out
+        return _step_forward(ctx, images, engine, True)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")

@@ -92,6 +92,25 @@ class Cfg(ctypes.Structure):
                [("averaging_const", c_float), ("ln_eps", c_float)]
 
 
+def vit_params(model) -> list:
+    """The parameters of a ViT tree in the order of the C ABI (include/qatvit.h): patch embedding, cls token, pos embedding, 12 per block,
+    final norm, head."""
+    pe = model.patch_embed.proj
+    ps = [pe.weight, pe.bias, model.cls_token, model.pos_embed]
+    for b in model.blocks:
+        ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias,
+               b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
+    return ps + [model.norm.weight, model.norm.bias, model.head.weight, model.head.bias]
+
+
+def vit_shape(model) -> dict:
+    """The shape fields of Cfg for a ViT tree, as keyword arguments (the caller adds batch and the quantiser fields)."""
+    b0 = model.blocks[0]
+    return dict(img_size=model.patch_embed.img_size, patch_size=model.patch_embed.patch_size, in_chans=model.patch_embed.proj.weight.shape[1],
+                embed_dim=model.embed_dim, depth=len(model.blocks), num_heads=b0.attn.num_heads, mlp_hidden=b0.mlp.fc1.weight.shape[0],
+                num_classes=model.head.weight.shape[0], ln_eps=float(b0.norm1.eps))
+
+
 class TNItem(ctypes.Structure):
     """struct qatvit_tn_item (include/qatvit.h)."""
     _fields_ = [(n, c_void_p) for n in ("P", "Q", "lut", "s1", "s2", "C", "W", "w_scale", "w_zp", "dbias", "row_div")] + [(n, c_int32) for n in ("N", "Kw", "ldp", "ldq", "ldc")]

@@ -33,21 +33,13 @@ class TeacherEngine:
         self.lib = native.lib()
         blocks = list(model.blocks)
         pe = model.patch_embed.proj
-        ps = [pe.weight, pe.bias, model.cls_token, model.pos_embed]
-        for b in blocks:
-            ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias,
-                   b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
-        ps += [model.norm.weight, model.norm.bias, model.head.weight, model.head.bias]
+        ps = native.vit_params(model)
         for p in ps:
             if p is None or p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
                 raise RuntimeError("teacher parameters must be contiguous fp32 tensors on one device")
         self.params = ps
-        self.cfg = native.Cfg(
-            batch=batch, img_size=model.patch_embed.img_size, patch_size=model.patch_embed.patch_size, in_chans=pe.weight.shape[1],
-            embed_dim=model.embed_dim, depth=len(blocks), num_heads=blocks[0].attn.num_heads, mlp_hidden=blocks[0].mlp.fc1.weight.shape[0],
-            num_classes=model.head.weight.shape[0], act_qmin=0, act_qmax=255, w_qmin=-128, w_qmax=127, w_per_channel=0,
-            averaging_const=0.01, ln_eps=float(blocks[0].norm1.eps),
-        )
+        self.cfg = native.Cfg(batch=batch, act_qmin=0, act_qmax=255, w_qmin=-128, w_qmax=127, w_per_channel=0, averaging_const=0.01,
+                              **native.vit_shape(model))
         self.weights = [pe.weight] + [w for b in blocks for w in (b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight)]
         self.passes = int(os.environ.get("QATVIT_TEACHER_PASSES", str(DEFAULT_PASSES)))
         if self.passes not in (1, 2, 3):

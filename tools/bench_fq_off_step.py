@@ -71,7 +71,7 @@ def main():
     print(f"observe-only step (fake-quant off):     {res['observe_ms']:8.2f} ms/step", flush=True)
     eng = engine_of(p)
     res["qat_workspace_mb"] = eng.workspace.numel() / 2**20
-    res["observe_float_workspace_mb"] = eng.f_workspace.numel() / 2**20
+    res["observe_float_workspace_mb"] = eng.float_form.workspace.numel() / 2**20
     res["observe_stats_kb"] = eng.observe_buf.numel() / 2**10
     print(f"  beside the QAT workspace ({res['qat_workspace_mb']:.0f} MiB): float workspace {res['observe_float_workspace_mb']:.0f} MiB, "
           f"observer statistics {res['observe_stats_kb']:.0f} KiB", flush=True)
