@@ -387,6 +387,20 @@ int qatvit_float_student_amp_backward(const qatvit_cfg* cfg, void* const* params
  * to fp16 on load.  One fused kernel, one workgroup per (image, head); head_dim 32 or 64, T <= 224. */
 int qatvit_float_student_amp_attn_backward(const float* qkv, const void* O16, const float* lse, const float* dO, int32_t B, int32_t T, int32_t H,
                                            int32_t D, void* dqkv16, void* stream);
+/* bf16 (autocast) form: what the step computes inside torch.autocast("cuda", dtype=torch.bfloat16) - the fp16 form above with every 16-bit plane
+ * in bf16 (round to nearest even, NaN kept) and every product one v_mfma_f32_16x16x32_bf16 pass, fp32 accumulate; logits and dlogits in bf16.  bf16
+ * has fp32's exponent range, so there is no overflow rule: inf and NaN reach the gradients as in stock.  Limits, workspace and calling sequence are
+ * the fp16 form's (its own workspace, of the fp16 form's size).
+ *  forward: logits_bf16 = [batch, num_classes] bf16.  backward: dlogits_bf16 = [batch, num_classes] bf16; grads fp32, ZERO on entry. */
+int64_t qatvit_float_student_bf16_workspace_bytes(const qatvit_cfg* cfg);
+int qatvit_float_student_bf16_init(const qatvit_cfg* cfg, void* workspace, void* stream);
+int qatvit_float_student_bf16_forward(const qatvit_cfg* cfg, void* const* params, const float* images, void* logits_bf16, void* workspace, void* stream);
+int qatvit_float_student_bf16_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_bf16, void* const* grads, void* workspace,
+                                       void* stream);
+/* The bf16 form's attention backward alone: as qatvit_float_student_amp_attn_backward with O16 and dqkv16 in bf16 (qkv and dO rounded to bf16 on
+ * load), on bf16 MFMA. */
+int qatvit_float_student_bf16_attn_backward(const float* qkv, const void* O16, const float* lse, const float* dO, int32_t B, int32_t T, int32_t H,
+                                            int32_t D, void* dqkv16, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Integer inference forward of the trained student from its exported integers.

@@ -351,7 +351,8 @@ __global__ __launch_bounds__(256) void k_mask_bwd(const float* __restrict__ d, c
 // time as the (hi, lo) bf16 pair that branch's dgrad / wgrad GEMMs read, multiplied by that output's STE mask (the ballot words
 // k_resid_fq_lnstats wrote in the forward) and the optional per-channel weight scale: what k_mask_bwd<0> would compute from a second
 // read of dx_out and of the fp32 pre-FQ tensor.
-template <int ACC, int NV, int WPB = 8, bool FUSE = false, bool O16 = false>   // WPB waves per block: column sums meet in LDS, so more waves per block = same atomics, more rows in flight
+// BF1: the fused next-branch gradient as ONE bf16 plane (nhi; the float step's bf16 form)
+template <int ACC, int NV, int WPB = 8, bool FUSE = false, bool O16 = false, bool BF1 = false>   // WPB waves per block: column sums meet in LDS, so more waves per block = same atomics, more rows in flight
 __global__ __launch_bounds__(WPB * 64) void k_ln_bwd_fq(const float* __restrict__ dH, int64_t dH_row_stride_rows, const float* __restrict__ x,
                                                    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                    const float* __restrict__ beta, const float* __restrict__ qp, int qmin, int qmax,
@@ -360,7 +361,7 @@ __global__ __launch_bounds__(WPB * 64) void k_ln_bwd_fq(const float* __restrict_
                                                    const unsigned long long* __restrict__ nmask, const float* __restrict__ ncs,
                                                    __bf16* __restrict__ nhi, __bf16* __restrict__ nlo, const float* __restrict__ o16_mul,
                                                    uint32_t* __restrict__ o16_amax) {
-    static_assert(!O16 || FUSE, "the one-plane output is the fused next-branch gradient");
+    static_assert((!O16 && !BF1) || (FUSE && !(O16 && BF1)), "the one-plane output is the fused next-branch gradient");
     const QP q = load_qp(qp);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float mul16 = 1.f, am16 = 0.f;
@@ -384,6 +385,7 @@ __global__ __launch_bounds__(WPB * 64) void k_ln_bwd_fq(const float* __restrict_
         const float f0 = (m0 >> lane) & 1 ? o.x * cs.x : 0.f, f1 = (m1 >> lane) & 1 ? o.y * cs.y : 0.f, f2 = (m2 >> lane) & 1 ? o.z * cs.z : 0.f,
                     f3 = (m3 >> lane) & 1 ? o.w * cs.w : 0.f;
         if constexpr (O16) store_f16x4(nhi, row * D + c, f0, f1, f2, f3, mul16, am16);
+        else if constexpr (BF1) *reinterpret_cast<uint2*>(nhi + row * D + c) = make_uint2(pk_bf16(f0, f1), pk_bf16(f2, f3));
         else store_split4(nhi, nlo, row * D + c, f0, f1, f2, f3);
     };
     constexpr int nv = NV;
@@ -768,6 +770,7 @@ int launch_ln_bwd_fq(int acc, const float* dH, const float* x, const float* mean
 #define QV_LNB(ACC_, NV_)                                                                                                                          \
     do {                                                                                                                                           \
         if (next && m16) k_ln_bwd_fq<ACC_, NV_, 8, true, true><<<grid, 512, 0, st>>>(dH, 0, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, nm, ncs, nh, nl, m16, a16); \
+        else if (next && !nl) k_ln_bwd_fq<ACC_, NV_, 8, true, false, true><<<grid, 512, 0, st>>>(dH, 0, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, nm, ncs, nh, nullptr, nullptr, nullptr); \
         else if (next) k_ln_bwd_fq<ACC_, NV_, 8, true><<<grid, 512, 0, st>>>(dH, 0, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, nm, ncs, nh, nl, nullptr, nullptr); \
         else k_ln_bwd_fq<ACC_, NV_, 8, false><<<grid, 512, 0, st>>>(dH, 0, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, nm, ncs, nh, nl, nullptr, nullptr); \
     } while (0)

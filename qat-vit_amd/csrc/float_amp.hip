@@ -10,7 +10,10 @@
 // Overflow follows stock (GradScaler must skip the same steps): every tensor stock holds in fp16 is rounded to nearest (fp16 overflow -> +-inf,
 // NaN propagates) where it becomes fp16 - dlogits, dhn, the fc2 dgrad output, dO, dP, dS, dQKV, dY0 - and the
 // Linear / Conv2d weight and bias gradients (fp16 tensors under stock autocast, fp32 sums here) take one post-pass: |g| beyond fp16's range -> +-inf.
-// This file holds the form's device code and its launchers; the host driver, shared with the pair form, is float_step.hip.
+// The bf16 form (torch.autocast(dtype=torch.bfloat16)) is the same device code on bf16 planes and v_mfma_f32_16x16x32_bf16: every kernel here but the
+// overflow rule is a template on the 16-bit element type E (_Float16 or __bf16).  bf16 has fp32's exponent range, so that form needs no overflow rule;
+// its roundings (v_cvt_pk_bf16_f32, round to nearest even, NaN kept) still carry inf and NaN into the gradients.
+// This file holds the one-plane forms' device code and its launchers; the host driver, shared with the pair form, is float_step.hip.
 #include "../../include/qatvit.h"
 
 #include "qv_common.h"
@@ -19,19 +22,36 @@
 namespace qv {
 
 typedef _Float16 fa_f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 fa_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float fa_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline float f16r(float v) { return (float)(_Float16)v; }   // round to fp16 and back (RNE: beyond 65520 -> inf)
+// the element type's pieces: 8-element MFMA fragment, the 16x16x32 MFMA, two floats packed (one v_cvt_pk), round and back
+template <typename E> struct Fa;
+template <> struct Fa<_Float16> {
+    typedef fa_f16x8 v8;
+    static __device__ __attribute__((always_inline)) fa_f32x4 mfma(v8 a, v8 b, fa_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+    static __device__ __attribute__((always_inline)) uint32_t pk(float a, float b) { return pk_f16(a, b); }
+    static __device__ __attribute__((always_inline)) float r(float v) { return f16r(v); }
+};
+template <> struct Fa<__bf16> {
+    typedef fa_bf16x8 v8;
+    static __device__ __attribute__((always_inline)) fa_f32x4 mfma(v8 a, v8 b, fa_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __attribute__((always_inline)) uint32_t pk(float a, float b) { return pk_bf16(a, b); }
+    static __device__ __attribute__((always_inline)) float r(float v) { return (float)(__bf16)v; }
+};
 
-// ---------------------------------------------------------------- weights as fp16, as stored and transposed (one launch per step)
+// ---------------------------------------------------------------- weights as fp16 / bf16, as stored and transposed (one launch per step)
+template <typename E>
 struct FaWTab {
     const float* W[kMaxW];
-    _Float16* w[kMaxW];
-    _Float16* wT[kMaxW];
+    E* w[kMaxW];
+    E* wT[kMaxW];
     int N[kMaxW], K[kMaxW], blk0[kMaxW + 1];
     int n;
 };
-__global__ __launch_bounds__(256) void k_fa_wcast(const FaWTab t) {
+template <typename E>
+__global__ __launch_bounds__(256) void k_fa_wcast(const FaWTab<E> t) {
     __shared__ float tile[32][33];
     int wi = 0;
     while (wi + 1 < t.n && (int)blockIdx.x >= t.blk0[wi + 1]) ++wi;
@@ -44,7 +64,7 @@ __global__ __launch_bounds__(256) void k_fa_wcast(const FaWTab t) {
         float v = 0.f;
         if (n < N && k < K) {
             v = t.W[wi][(int64_t)n * K + k];
-            t.w[wi][(int64_t)n * K + k] = (_Float16)v;
+            t.w[wi][(int64_t)n * K + k] = (E)v;
         }
         tile[ty + 8 * i][tx] = v;
     }
@@ -52,35 +72,37 @@ __global__ __launch_bounds__(256) void k_fa_wcast(const FaWTab t) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int k = k0 + ty + 8 * i, n = n0 + tx;
-        if (n < N && k < K) t.wT[wi][(int64_t)k * N + n] = (_Float16)tile[tx][ty + 8 * i];
+        if (n < N && k < K) t.wT[wi][(int64_t)k * N + n] = (E)tile[tx][ty + 8 * i];
     }
 }
 
-// ---------------------------------------------------------------- head: cls LayerNorm (fp32) -> fp16 Linear -> fp16 logits
+// ---------------------------------------------------------------- head: cls LayerNorm (fp32) -> fp16 Linear -> fp16 logits (the same in bf16)
 // hn16[b,:] = fp16(LN(x[b,0,:])) (kept as fp32 values for the backward); logits[b,c] = fp16(hn16[b,:] . fp16(W[c,:]) + fp16(bias[c]))
+template <typename E>
 __global__ __launch_bounds__(256) void k_fa_head_fwd(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ W,
-                                                     const float* __restrict__ bias, float* __restrict__ hn, _Float16* __restrict__ logits, int D, int T, int C) {
+                                                     const float* __restrict__ bias, float* __restrict__ hn, E* __restrict__ logits, int D, int T, int C) {
     extern __shared__ float sh[];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row = (int64_t)b * T;
     const float mu = mean[row], rs = rstd[row];
     for (int c = threadIdx.x; c < D; c += 256) {
-        const float v = f16r((x[row * D + c] - mu) * rs * gamma[c] + beta[c]);
+        const float v = Fa<E>::r((x[row * D + c] - mu) * rs * gamma[c] + beta[c]);
         sh[c] = v;
         hn[(int64_t)b * D + c] = v;
     }
     __syncthreads();
     for (int c = wave; c < C; c += 4) {
         float acc = 0.f;
-        for (int k = lane; k < D; k += 64) acc += sh[k] * f16r(W[(int64_t)c * D + k]);
+        for (int k = lane; k < D; k += 64) acc += sh[k] * Fa<E>::r(W[(int64_t)c * D + k]);
         acc = wave_sum(acc);
-        if (lane == 0) logits[(int64_t)b * C + c] = (_Float16)(acc + f16r(bias[c]));
+        if (lane == 0) logits[(int64_t)b * C + c] = (E)(acc + Fa<E>::r(bias[c]));
     }
 }
 // one thread per output element, fixed summation order: dW[c,d] = sum_b dl[b,c] hn16[b,d]; dbias[c] = sum_b dl[b,c];
 // dhn[b,d] = fp16(sum_c dl[b,c] fp16(W[c,d]))  (stock: the fp16 Linear's input gradient)
-__global__ __launch_bounds__(256) void k_fa_head_bwd(const _Float16* __restrict__ dl, const float* __restrict__ hn, const float* __restrict__ W,
+template <typename E>
+__global__ __launch_bounds__(256) void k_fa_head_bwd(const E* __restrict__ dl, const float* __restrict__ hn, const float* __restrict__ W,
                                                      float* __restrict__ dW, float* __restrict__ dbias, float* __restrict__ dhn, int B, int D, int C) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int64_t nW = (int64_t)C * D, nH = (int64_t)B * D;
@@ -98,8 +120,8 @@ __global__ __launch_bounds__(256) void k_fa_head_bwd(const _Float16* __restrict_
         const int64_t j = i - nW;
         const int b = (int)(j / D), d = (int)(j % D);
         float a = 0.f;
-        for (int c = 0; c < C; ++c) a += (float)dl[(int64_t)b * C + c] * f16r(W[(int64_t)c * D + d]);
-        dhn[j] = f16r(a);
+        for (int c = 0; c < C; ++c) a += (float)dl[(int64_t)b * C + c] * Fa<E>::r(W[(int64_t)c * D + d]);
+        dhn[j] = Fa<E>::r(a);
     } else if (i < nW + nH + C) {
         const int c = (int)(i - nW - nH);
         float a = 0.f;
@@ -110,26 +132,29 @@ __global__ __launch_bounds__(256) void k_fa_head_bwd(const _Float16* __restrict_
 
 // ---------------------------------------------------------------- elementwise
 // G16 = fp16(gelu(Y1))  (the fc2 forward operand and its weight-gradient operand)
-__global__ __launch_bounds__(256) void k_fa_gelu(const float* __restrict__ Y, _Float16* __restrict__ G, int64_t n4) {
+template <typename E>
+__global__ __launch_bounds__(256) void k_fa_gelu(const float* __restrict__ Y, E* __restrict__ G, int64_t n4) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const float4 v = reinterpret_cast<const float4*>(Y)[i];
-        *reinterpret_cast<uint2*>(G + i * 4) = make_uint2(pk_f16(gelu_fwd(v.x), gelu_fwd(v.y)), pk_f16(gelu_fwd(v.z), gelu_fwd(v.w)));
+        *reinterpret_cast<uint2*>(G + i * 4) = make_uint2(Fa<E>::pk(gelu_fwd(v.x), gelu_fwd(v.y)), Fa<E>::pk(gelu_fwd(v.z), gelu_fwd(v.w)));
     }
 }
 // dY1_16 = fp16(fp16(dG) * gelu'(Y1)),  gelu'(x) = Phi(x) + x phi(x)
 __device__ inline float gelu_grad(float x) {
     return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * __expf(-0.5f * x * x);
 }
-__global__ __launch_bounds__(256) void k_fa_gelu_bwd(const float* __restrict__ dG, const float* __restrict__ Y, _Float16* __restrict__ out, int64_t n4) {
+template <typename E>
+__global__ __launch_bounds__(256) void k_fa_gelu_bwd(const float* __restrict__ dG, const float* __restrict__ Y, E* __restrict__ out, int64_t n4) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const float4 g = reinterpret_cast<const float4*>(dG)[i];
         const float4 y = reinterpret_cast<const float4*>(Y)[i];
-        *reinterpret_cast<uint2*>(out + i * 4) = make_uint2(pk_f16(f16r(g.x) * gelu_grad(y.x), f16r(g.y) * gelu_grad(y.y)),
-                                                            pk_f16(f16r(g.z) * gelu_grad(y.z), f16r(g.w) * gelu_grad(y.w)));
+        *reinterpret_cast<uint2*>(out + i * 4) = make_uint2(Fa<E>::pk(Fa<E>::r(g.x) * gelu_grad(y.x), Fa<E>::r(g.y) * gelu_grad(y.y)),
+                                                            Fa<E>::pk(Fa<E>::r(g.z) * gelu_grad(y.z), Fa<E>::r(g.w) * gelu_grad(y.w)));
     }
 }
 // embedding backward: dpos[t,:] = sum_b dx[b,t,:], dcls = dpos[0,:] (fp32, fixed order); dY0_16[b*np + t-1, :] = fp16(dx[b,t,:]) for t >= 1
-__global__ __launch_bounds__(64) void k_fa_embed_bwd(const float* __restrict__ dx, float* __restrict__ dpos, float* __restrict__ dcls, _Float16* __restrict__ dY0,
+template <typename E>
+__global__ __launch_bounds__(64) void k_fa_embed_bwd(const float* __restrict__ dx, float* __restrict__ dpos, float* __restrict__ dcls, E* __restrict__ dY0,
                                                      int B, int T, int D) {
     const int d4 = D / 4;
     const int64_t n4 = (int64_t)T * d4;
@@ -139,7 +164,7 @@ __global__ __launch_bounds__(64) void k_fa_embed_bwd(const float* __restrict__ d
         for (int b = 0; b < B; ++b) {
             const float4 g = *reinterpret_cast<const float4*>(dx + ((int64_t)b * T + t) * D + c);
             acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w;
-            if (t > 0) *reinterpret_cast<uint2*>(dY0 + ((int64_t)b * (T - 1) + (t - 1)) * D + c) = make_uint2(pk_f16(g.x, g.y), pk_f16(g.z, g.w));
+            if (t > 0) *reinterpret_cast<uint2*>(dY0 + ((int64_t)b * (T - 1) + (t - 1)) * D + c) = make_uint2(Fa<E>::pk(g.x, g.y), Fa<E>::pk(g.z, g.w));
         }
         *reinterpret_cast<float4*>(dpos + (int64_t)t * D + c) = acc;
         if (t == 0) *reinterpret_cast<float4*>(dcls + c) = acc;
@@ -159,6 +184,7 @@ __global__ __launch_bounds__(256) void k_fa_inf_rule(const FaInfTab t) {
 }
 
 // ---------------------------------------------------------------- attention backward on fp16 MFMA, fused: one workgroup per (image, head)
+// (E = __bf16: the same in bf16 on v_mfma_f32_16x16x32_bf16)
 // With s = head_dim^-0.5 and the forward's lse, per (image, head):
 //   P = exp(s Q K^T - lse)    dP = fp16(dO V^T)    dS = fp16(P * (dP - delta)),  delta_i = fp16(dO_i) . O16_i
 //   dQ = fp16(s dS K)    dK = fp16(s dS^T Q)    dV = fp16(fp16(P)^T dO)
@@ -171,57 +197,58 @@ __global__ __launch_bounds__(256) void k_fa_inf_rule(const FaInfTab t) {
 // column; accumulator e of lane l = row 4 (l / 16) + e, column l % 16.
 constexpr int kFaWaves = 8, kFaScr = 40;   // scratch row stride in fp16 (32 + 8: 16-B aligned rows)
 __device__ inline void fa_wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }   // LDS is in order per wave; stop the compiler reordering
-template <int HD>
-__device__ inline fa_f16x8 fa_col8(const _Float16* s, int row0, int col) {   // s[(row0 + j) * (HD + 8) + col], j = 0..7
-    fa_f16x8 v;
+template <int HD, typename E>
+__device__ inline typename Fa<E>::v8 fa_col8(const E* s, int row0, int col) {   // s[(row0 + j) * (HD + 8) + col], j = 0..7
+    typename Fa<E>::v8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = s[(row0 + j) * (HD + 8) + col];
     return v;
 }
-template <int HD>
-__global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float* __restrict__ qkv, const _Float16* __restrict__ O16, const float* __restrict__ lse,
-                                                                    const float* __restrict__ dO, int T, int H, int D, float scale, _Float16* __restrict__ dqkv) {
+template <int HD, typename E>
+__global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float* __restrict__ qkv, const E* __restrict__ O16, const float* __restrict__ lse,
+                                                                    const float* __restrict__ dO, int T, int H, int D, float scale, E* __restrict__ dqkv) {
+    typedef typename Fa<E>::v8 v8;
     constexpr int LDH = HD + 8, CH = HD / 8, KK = HD / 32, ND = HD / 16;
     const int Tp = (T + 31) & ~31;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* sQ = reinterpret_cast<_Float16*>(smem);
-    _Float16* sK = sQ + Tp * LDH;
-    _Float16* sV = sK + Tp * LDH;
-    _Float16* sD = sV + Tp * LDH;   // dO
+    E* sQ = reinterpret_cast<E*>(smem);
+    E* sK = sQ + Tp * LDH;
+    E* sV = sK + Tp * LDH;
+    E* sD = sV + Tp * LDH;   // dO
     float* sL = reinterpret_cast<float*>(sD + Tp * LDH);
     float* sDel = sL + Tp;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-    _Float16* scrP = reinterpret_cast<_Float16*>(sDel + Tp) + wave * 2 * 16 * kFaScr;
-    _Float16* scrS = scrP + 16 * kFaScr;
+    E* scrP = reinterpret_cast<E*>(sDel + Tp) + wave * 2 * 16 * kFaScr;
+    E* scrS = scrP + 16 * kFaScr;
     const int b = blockIdx.x / H, h = blockIdx.x % H, ld = 3 * D;
     const int64_t row0 = (int64_t)b * T;
     for (int i = threadIdx.x; i < Tp * CH; i += kFaWaves * 64) {   // staging: 8 features of one token per thread
         const int t = i / CH, c = (i % CH) * 8;
-        fa_f16x8 q, k, v, d;
+        v8 q, k, v, d;
         if (t < T) {
             const float* src = qkv + (row0 + t) * ld + h * HD + c;
             const float* ds = dO + (row0 + t) * D + h * HD + c;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { q[j] = (_Float16)src[j]; k[j] = (_Float16)src[D + j]; v[j] = (_Float16)src[2 * D + j]; d[j] = (_Float16)ds[j]; }
+            for (int j = 0; j < 8; ++j) { q[j] = (E)src[j]; k[j] = (E)src[D + j]; v[j] = (E)src[2 * D + j]; d[j] = (E)ds[j]; }
         } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) q[j] = k[j] = v[j] = d[j] = (_Float16)0.f;
+            for (int j = 0; j < 8; ++j) q[j] = k[j] = v[j] = d[j] = (E)0.f;
         }
-        *reinterpret_cast<fa_f16x8*>(sQ + t * LDH + c) = q;
-        *reinterpret_cast<fa_f16x8*>(sK + t * LDH + c) = k;
-        *reinterpret_cast<fa_f16x8*>(sV + t * LDH + c) = v;
-        *reinterpret_cast<fa_f16x8*>(sD + t * LDH + c) = d;
+        *reinterpret_cast<v8*>(sQ + t * LDH + c) = q;
+        *reinterpret_cast<v8*>(sK + t * LDH + c) = k;
+        *reinterpret_cast<v8*>(sV + t * LDH + c) = v;
+        *reinterpret_cast<v8*>(sD + t * LDH + c) = d;
     }
     for (int t = threadIdx.x; t < Tp; t += kFaWaves * 64) sL[t] = t < T ? lse[((int64_t)b * H + h) * T + t] : 0.f;
     __syncthreads();
-    for (int t = threadIdx.x; t < Tp; t += kFaWaves * 64) {   // delta from the staged fp16 dO and the forward's fp16 O
+    for (int t = threadIdx.x; t < Tp; t += kFaWaves * 64) {   // delta from the staged fp16 dO and the forward's fp16 O (bf16: the same in bf16)
         float a = 0.f;
         if (t < T) {
-            const _Float16* o = O16 + (row0 + t) * D + h * HD;
+            const E* o = O16 + (row0 + t) * D + h * HD;
 #pragma unroll
             for (int c = 0; c < HD; c += 8) {
-                const fa_f16x8 ov = *reinterpret_cast<const fa_f16x8*>(o + c);
-                const fa_f16x8 dv = *reinterpret_cast<const fa_f16x8*>(sD + t * LDH + c);
+                const v8 ov = *reinterpret_cast<const v8*>(o + c);
+                const v8 dv = *reinterpret_cast<const v8*>(sD + t * LDH + c);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) a += (float)dv[j] * (float)ov[j];
             }
@@ -244,10 +271,8 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
 #pragma unroll
                 for (int kk = 0; kk < KK; ++kk) {
                     const int c = 32 * kk + 8 * g, qr = qc + 16 * u + r;
-                    st[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sK + (k0 + r) * LDH + c),
-                                                                   *reinterpret_cast<const fa_f16x8*>(sQ + qr * LDH + c), st[u], 0, 0, 0);
-                    dpt[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sV + (k0 + r) * LDH + c),
-                                                                    *reinterpret_cast<const fa_f16x8*>(sD + qr * LDH + c), dpt[u], 0, 0, 0);
+                    st[u] = Fa<E>::mfma(*reinterpret_cast<const v8*>(sK + (k0 + r) * LDH + c), *reinterpret_cast<const v8*>(sQ + qr * LDH + c), st[u]);
+                    dpt[u] = Fa<E>::mfma(*reinterpret_cast<const v8*>(sV + (k0 + r) * LDH + c), *reinterpret_cast<const v8*>(sD + qr * LDH + c), dpt[u]);
                 }
             }
 #pragma unroll
@@ -258,17 +283,17 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
                 for (int e = 0; e < 4; ++e) {
                     const int key = k0 + 4 * g + e;
                     const float p = (q < T && key < T) ? __expf(scale * st[u][e] - lq) : 0.f;
-                    scrP[(4 * g + e) * kFaScr + 16 * u + r] = (_Float16)p;
-                    scrS[(4 * g + e) * kFaScr + 16 * u + r] = (_Float16)(p * (f16r(dpt[u][e]) - dq));
+                    scrP[(4 * g + e) * kFaScr + 16 * u + r] = (E)p;
+                    scrS[(4 * g + e) * kFaScr + 16 * u + r] = (E)(p * (Fa<E>::r(dpt[u][e]) - dq));
                 }
             }
             fa_wave_lds_fence();
-            const fa_f16x8 ap = *reinterpret_cast<const fa_f16x8*>(scrP + r * kFaScr + 8 * g);
-            const fa_f16x8 as = *reinterpret_cast<const fa_f16x8*>(scrS + r * kFaScr + 8 * g);
+            const v8 ap = *reinterpret_cast<const v8*>(scrP + r * kFaScr + 8 * g);
+            const v8 as = *reinterpret_cast<const v8*>(scrS + r * kFaScr + 8 * g);
 #pragma unroll
             for (int jd = 0; jd < ND; ++jd) {
-                dV[jd] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ap, fa_col8<HD>(sD, qc + 8 * g, 16 * jd + r), dV[jd], 0, 0, 0);
-                dK[jd] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as, fa_col8<HD>(sQ, qc + 8 * g, 16 * jd + r), dK[jd], 0, 0, 0);
+                dV[jd] = Fa<E>::mfma(ap, fa_col8<HD>(sD, qc + 8 * g, 16 * jd + r), dV[jd]);
+                dK[jd] = Fa<E>::mfma(as, fa_col8<HD>(sQ, qc + 8 * g, 16 * jd + r), dK[jd]);
             }
             fa_wave_lds_fence();
         }
@@ -278,9 +303,9 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
             for (int e = 0; e < 4; ++e) {
                 const int key = k0 + 4 * g + e;
                 if (key < T) {
-                    _Float16* o = dqkv + (row0 + key) * ld + h * HD + 16 * jd + r;
-                    o[D] = (_Float16)(scale * dK[jd][e]);
-                    o[2 * D] = (_Float16)dV[jd][e];
+                    E* o = dqkv + (row0 + key) * ld + h * HD + 16 * jd + r;
+                    o[D] = (E)(scale * dK[jd][e]);
+                    o[2 * D] = (E)dV[jd][e];
                 }
             }
     }
@@ -301,10 +326,8 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
 #pragma unroll
                 for (int kk = 0; kk < KK; ++kk) {
                     const int c = 32 * kk + 8 * g, kr = kc + 16 * u + r;
-                    s[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sQ + (q0 + r) * LDH + c),
-                                                                  *reinterpret_cast<const fa_f16x8*>(sK + kr * LDH + c), s[u], 0, 0, 0);
-                    dp[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const fa_f16x8*>(sD + (q0 + r) * LDH + c),
-                                                                   *reinterpret_cast<const fa_f16x8*>(sV + kr * LDH + c), dp[u], 0, 0, 0);
+                    s[u] = Fa<E>::mfma(*reinterpret_cast<const v8*>(sQ + (q0 + r) * LDH + c), *reinterpret_cast<const v8*>(sK + kr * LDH + c), s[u]);
+                    dp[u] = Fa<E>::mfma(*reinterpret_cast<const v8*>(sD + (q0 + r) * LDH + c), *reinterpret_cast<const v8*>(sV + kr * LDH + c), dp[u]);
                 }
             }
 #pragma unroll
@@ -314,14 +337,14 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
                 for (int e = 0; e < 4; ++e) {
                     const int q = q0 + 4 * g + e;
                     const float p = (q < T && key < T) ? __expf(scale * s[u][e] - lq[e]) : 0.f;
-                    scrS[(4 * g + e) * kFaScr + 16 * u + r] = (_Float16)(p * (f16r(dp[u][e]) - dq[e]));
+                    scrS[(4 * g + e) * kFaScr + 16 * u + r] = (E)(p * (Fa<E>::r(dp[u][e]) - dq[e]));
                 }
             }
             fa_wave_lds_fence();
-            const fa_f16x8 as = *reinterpret_cast<const fa_f16x8*>(scrS + r * kFaScr + 8 * g);
+            const v8 as = *reinterpret_cast<const v8*>(scrS + r * kFaScr + 8 * g);
 #pragma unroll
             for (int jd = 0; jd < ND; ++jd)
-                dQ[jd] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as, fa_col8<HD>(sK, kc + 8 * g, 16 * jd + r), dQ[jd], 0, 0, 0);
+                dQ[jd] = Fa<E>::mfma(as, fa_col8<HD>(sK, kc + 8 * g, 16 * jd + r), dQ[jd]);
             fa_wave_lds_fence();
         }
 #pragma unroll
@@ -329,7 +352,7 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int q = q0 + 4 * g + e;
-                if (q < T) dqkv[(row0 + q) * ld + h * HD + 16 * jd + r] = (_Float16)(scale * dQ[jd][e]);
+                if (q < T) dqkv[(row0 + q) * ld + h * HD + 16 * jd + r] = (E)(scale * dQ[jd][e]);
             }
     }
 }
@@ -338,66 +361,85 @@ static size_t fa_attn_lds_bytes(int T, int HD) {
     const size_t Tp = (size_t)((T + 31) & ~31);
     return 4 * Tp * (HD + 8) * 2 + 2 * Tp * 4 + (size_t)kFaWaves * 2 * 16 * kFaScr * 2;
 }
-template <int HD>
+template <int HD, typename E>
 static void launch_fa_attn_fused(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st) {
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_fa_attn_bwd_fused<HD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_fa_attn_bwd_fused<HD, E>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                   (int)fa_attn_lds_bytes(224, HD)),
                         true);
     (void)once;
-    k_fa_attn_bwd_fused<HD><<<B * H, kFaWaves * 64, fa_attn_lds_bytes(T, HD), st>>>(qkv, reinterpret_cast<const _Float16*>(O16), lse, dO, T, H, D,
-                                                                                    1.0f / sqrtf((float)HD), reinterpret_cast<_Float16*>(dqkv16));
+    k_fa_attn_bwd_fused<HD, E><<<B * H, kFaWaves * 64, fa_attn_lds_bytes(T, HD), st>>>(qkv, reinterpret_cast<const E*>(O16), lse, dO, T, H, D,
+                                                                                       1.0f / sqrtf((float)HD), reinterpret_cast<E*>(dqkv16));
 }
 
-int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st) {
+int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st, bool bf16) {
     const int hd = H > 0 ? D / H : 0;
     if (B < 1 || H < 1 || D % H != 0 || (hd != 64 && hd != 32) || T < 1 || T > 224 || !qkv || !O16 || !lse || !dO || !dqkv16) {
-        set_error("attn_bwd_f16: unsupported arguments B=%d T=%d H=%d D=%d (head_dim 32 or 64, T <= 224)", B, T, H, D);
+        set_error("attn_bwd_%s: unsupported arguments B=%d T=%d H=%d D=%d (head_dim 32 or 64, T <= 224)", bf16 ? "bf16" : "f16", B, T, H, D);
         return 1;
     }
-    if (hd == 64) launch_fa_attn_fused<64>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
-    else launch_fa_attn_fused<32>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
+    if (bf16) {
+        if (hd == 64) launch_fa_attn_fused<64, __bf16>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
+        else launch_fa_attn_fused<32, __bf16>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
+    } else if (hd == 64) launch_fa_attn_fused<64, _Float16>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
+    else launch_fa_attn_fused<32, _Float16>(qkv, O16, lse, dO, B, T, H, D, dqkv16, st);
     return 0;
 }
 
-// ---------------------------------------------------------------- launchers (the host driver of both forms is float_step.hip)
-int launch_fa_wcast(int n, const float* const* W, void* const* w16, void* const* w16T, const int* N, const int* K, const int* blk0, hipStream_t st) {
-    FaWTab t{};
+// ---------------------------------------------------------------- launchers (the host driver of every form is float_step.hip); bf16: the bf16 form
+template <typename E>
+static void fa_wcast(int n, const float* const* W, void* const* w16, void* const* w16T, const int* N, const int* K, const int* blk0, hipStream_t st) {
+    FaWTab<E> t{};
     t.n = n;
     for (int wi = 0; wi < n; ++wi) {
         t.W[wi] = W[wi];
-        t.w[wi] = reinterpret_cast<_Float16*>(w16[wi]);
-        t.wT[wi] = reinterpret_cast<_Float16*>(w16T[wi]);
+        t.w[wi] = reinterpret_cast<E*>(w16[wi]);
+        t.wT[wi] = reinterpret_cast<E*>(w16T[wi]);
         t.N[wi] = N[wi]; t.K[wi] = K[wi]; t.blk0[wi] = blk0[wi];
     }
     t.blk0[n] = blk0[n];
-    k_fa_wcast<<<blk0[n], 256, 0, st>>>(t);
+    k_fa_wcast<E><<<blk0[n], 256, 0, st>>>(t);
+}
+int launch_fa_wcast(int n, const float* const* W, void* const* w16, void* const* w16T, const int* N, const int* K, const int* blk0, hipStream_t st, bool bf16) {
+    if (bf16) fa_wcast<__bf16>(n, W, w16, w16T, N, K, blk0, st);
+    else fa_wcast<_Float16>(n, W, w16, w16T, N, K, blk0, st);
     return 0;
 }
 
+template <typename E>
+static void fa_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias, float* hn,
+                        void* logits16, int B, int D, int T, int C, hipStream_t st) {
+    k_fa_head_fwd<E><<<B, 256, D * sizeof(float), st>>>(x, mean, rstd, gamma, beta, W, bias, hn, reinterpret_cast<E*>(logits16), D, T, C);
+}
 int launch_fa_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias, float* hn,
-                       void* logits16, int B, int D, int T, int C, hipStream_t st) {
-    k_fa_head_fwd<<<B, 256, D * sizeof(float), st>>>(x, mean, rstd, gamma, beta, W, bias, hn, reinterpret_cast<_Float16*>(logits16), D, T, C);
+                       void* logits16, int B, int D, int T, int C, hipStream_t st, bool bf16) {
+    if (bf16) fa_head_fwd<__bf16>(x, mean, rstd, gamma, beta, W, bias, hn, logits16, B, D, T, C, st);
+    else fa_head_fwd<_Float16>(x, mean, rstd, gamma, beta, W, bias, hn, logits16, B, D, T, C, st);
     return 0;
 }
 
-int launch_fa_head_bwd(const void* dl16, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st) {
+int launch_fa_head_bwd(const void* dl16, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st, bool bf16) {
     const int64_t n = (int64_t)C * D + (int64_t)B * D + C;
-    k_fa_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const _Float16*>(dl16), hn, W, dW, dbias, dhn, B, D, C);
+    if (bf16) k_fa_head_bwd<__bf16><<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const __bf16*>(dl16), hn, W, dW, dbias, dhn, B, D, C);
+    else k_fa_head_bwd<_Float16><<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const _Float16*>(dl16), hn, W, dW, dbias, dhn, B, D, C);
     return 0;
 }
 
-int launch_fa_gelu(const float* Y, void* G16, int64_t n, hipStream_t st) {
-    k_fa_gelu<<<flat_grid_fs(n / 4), 256, 0, st>>>(Y, reinterpret_cast<_Float16*>(G16), n / 4);
+int launch_fa_gelu(const float* Y, void* G16, int64_t n, hipStream_t st, bool bf16) {
+    if (bf16) k_fa_gelu<__bf16><<<flat_grid_fs(n / 4), 256, 0, st>>>(Y, reinterpret_cast<__bf16*>(G16), n / 4);
+    else k_fa_gelu<_Float16><<<flat_grid_fs(n / 4), 256, 0, st>>>(Y, reinterpret_cast<_Float16*>(G16), n / 4);
     return 0;
 }
 
-int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, hipStream_t st) {
-    k_fa_gelu_bwd<<<flat_grid_fs(n / 4), 256, 0, st>>>(dG, Y, reinterpret_cast<_Float16*>(dY16), n / 4);
+int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, hipStream_t st, bool bf16) {
+    if (bf16) k_fa_gelu_bwd<__bf16><<<flat_grid_fs(n / 4), 256, 0, st>>>(dG, Y, reinterpret_cast<__bf16*>(dY16), n / 4);
+    else k_fa_gelu_bwd<_Float16><<<flat_grid_fs(n / 4), 256, 0, st>>>(dG, Y, reinterpret_cast<_Float16*>(dY16), n / 4);
     return 0;
 }
 
-int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16, int B, int T, int D, hipStream_t st) {
-    k_fa_embed_bwd<<<(int)(((int64_t)T * (D / 4) + 63) / 64), 64, 0, st>>>(dx, dpos, dcls, reinterpret_cast<_Float16*>(dY0_16), B, T, D);
+int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16, int B, int T, int D, hipStream_t st, bool bf16) {
+    const int grid = (int)(((int64_t)T * (D / 4) + 63) / 64);
+    if (bf16) k_fa_embed_bwd<__bf16><<<grid, 64, 0, st>>>(dx, dpos, dcls, reinterpret_cast<__bf16*>(dY0_16), B, T, D);
+    else k_fa_embed_bwd<_Float16><<<grid, 64, 0, st>>>(dx, dpos, dcls, reinterpret_cast<_Float16*>(dY0_16), B, T, D);
     return 0;
 }
 
@@ -419,6 +461,13 @@ int qatvit_float_student_amp_attn_backward(const float* qkv, const void* O16, co
                                            void* dqkv16, void* stream) {
     if (launch_attn_bwd_f16(qkv, O16, lse, dO, B, T, H, D, dqkv16, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_float_student_amp_attn_backward");
+    return 0;
+}
+
+int qatvit_float_student_bf16_attn_backward(const float* qkv, const void* O16, const float* lse, const float* dO, int32_t B, int32_t T, int32_t H, int32_t D,
+                                            void* dqkv16, void* stream) {
+    if (launch_attn_bwd_f16(qkv, O16, lse, dO, B, T, H, D, dqkv16, (hipStream_t)stream, true)) return 1;
+    QV_CHECK_LAUNCH("qatvit_float_student_bf16_attn_backward");
     return 0;
 }
 

@@ -296,11 +296,13 @@ using namespace qv;
 
 extern "C" {
 
-// The host driver of both forms of the step: the pair form (bf16 (hi, lo) pairs, three MFMA passes) and the fp16 form (f16: one fp16 plane per
-// GEMM operand, one pass; its device code and launchers are float_amp.hip's).  The fp16 form keeps each plane at the _hi offset.
+// The host driver of every form of the step: the pair form (bf16 (hi, lo) pairs, three MFMA passes), the fp16 form (one fp16 plane per GEMM
+// operand, one pass; its device code and launchers are float_amp.hip's) and the bf16 form (the fp16 form on bf16 planes and bf16 MFMA).  The
+// one-plane forms keep each plane at the _hi offset.
 // Workspace: a batch-independent head (constants, the weight planes, the weight-gradient scratch) and the batch-sized rest.  The _lo planes and the
 // fp32 attention-backward scratch (Pm, dS, delta) are the pair form's only, amax (the fp16 residual gradient's maximum) the fp16 form's; a plane a
 // form does not take has offset -1.
+enum class FsForm { pair, f16, bf16 };
 struct FsBlock { int64_t x, xm, h1_hi, h1_lo, h2_hi, h2_lo, mean1, rstd1, mean2, rstd2, qkv, O_hi, O_lo, lse, Y1, G_hi, G_lo; };
 struct FsPlan {
     int64_t qp_off, amax, w_hi[kMaxW], w_lo[kMaxW], w_hiT[kMaxW], w_loT[kMaxW], tn_partial;
@@ -309,16 +311,18 @@ struct FsPlan {
     int64_t Y, dx, dx2, dp_hi, dp_lo, dG, dY1_hi, dY1_lo, dh, dO, dqkv_hi, dqkv_lo, Pm, dS, delta, dhn, dY0_hi, dY0_lo;
     int64_t ones_words, total;
 };
-static int fs_check(const qatvit_cfg& c, bool f16) {
+static const char* fs_form_name(FsForm form) { return form == FsForm::f16 ? " amp" : form == FsForm::bf16 ? " bf16" : ""; }
+static int fs_check(const qatvit_cfg& c, FsForm form) {
+    const bool one = form != FsForm::pair;
     const int hd = c.num_heads > 0 ? c.embed_dim / c.num_heads : 0;
     const int np = c.patch_size > 0 ? (c.img_size / c.patch_size) * (c.img_size / c.patch_size) : 0;
-    const int mult = f16 ? 384 : 128;
+    const int mult = one ? 384 : 128;
     if (c.batch < 1 || c.depth < 1 || c.depth > 12 || c.embed_dim % mult != 0 || c.embed_dim > 768 || c.mlp_hidden % mult != 0 || c.num_heads < 1 ||
         c.embed_dim % c.num_heads != 0 || (hd != 32 && hd != 64) || c.patch_size % 4 != 0 || c.img_size % c.patch_size != 0 || np + 1 > 224 ||
         (c.in_chans * c.patch_size * c.patch_size) % 128 != 0 || c.num_classes < 1) {
         set_error("float student%s: unsupported config (batch %d depth %d dim %d hidden %d heads %d img %d patch %d): needs %s, head_dim 32 or 64, "
-                  "<= 224 tokens, depth <= 12", f16 ? " amp" : "", c.batch, c.depth, c.embed_dim, c.mlp_hidden, c.num_heads, c.img_size, c.patch_size,
-                  f16 ? "dim and hidden multiples of 384, dim <= 768" : "dim % 128 == 0 and <= 768");
+                  "<= 224 tokens, depth <= 12", fs_form_name(form), c.batch, c.depth, c.embed_dim, c.mlp_hidden, c.num_heads, c.img_size, c.patch_size,
+                  one ? "dim and hidden multiples of 384, dim <= 768" : "dim % 128 == 0 and <= 768");
         return 1;
     }
     return 0;
@@ -339,15 +343,15 @@ static int fs_weight_param(const qatvit_cfg& c, int wi) {   // its index in the 
     static const int kW[4] = {2, 4, 8, 10};                  // qkv, proj, fc1, fc2 weights within a block's 12 parameters
     return wi == 0 ? 0 : wi == 1 + 4 * c.depth ? 4 + 12 * c.depth + 2 : 4 + 12 * ((wi - 1) / 4) + kW[(wi - 1) % 4];
 }
-static FsPlan fs_plan(const qatvit_cfg& c, bool f16) {
+static FsPlan fs_plan(const qatvit_cfg& c, FsForm form) {
     FsPlan p{};
     int64_t o = 0;
     auto take = [&](int64_t b) { int64_t r = o; o += (b + 255) & ~(int64_t)255; return r; };
-    auto pair = [&](int64_t b) { return f16 ? (int64_t)-1 : take(b); };   // taken by the pair form only
+    auto pair = [&](int64_t b) { return form != FsForm::pair ? (int64_t)-1 : take(b); };   // taken by the pair form only
     const int64_t np = (int64_t)(c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, B = c.batch, M = B * T, D = c.embed_dim,
                   Hd = c.mlp_hidden, H = c.num_heads, Kpe = (int64_t)c.in_chans * c.patch_size * c.patch_size;
     p.qp_off = take(16);
-    p.amax = f16 ? take((int64_t)kDyAmaxSlots * kDyAmaxStride * 4) : -1;
+    p.amax = form == FsForm::f16 ? take((int64_t)kDyAmaxSlots * kDyAmaxStride * 4) : -1;
     for (int wi = 0; wi < 1 + 4 * c.depth; ++wi) {
         int N, K;
         fs_weight_shape(c, wi, &N, &K);
@@ -390,20 +394,20 @@ static FsPlan fs_plan(const qatvit_cfg& c, bool f16) {
     return p;
 }
 
-static int64_t fs_workspace_bytes(const char* fn, bool f16, const qatvit_cfg* cfg) {
+static int64_t fs_workspace_bytes(const char* fn, FsForm form, const qatvit_cfg* cfg) {
     if (!cfg) { set_error("%s: null argument", fn); return -1; }
-    if (fs_check(*cfg, f16)) return -1;
-    return fs_plan(*cfg, f16).total;
+    if (fs_check(*cfg, form)) return -1;
+    return fs_plan(*cfg, form).total;
 }
 
 static void fs_consts(const FsPlan& p, char* ws, hipStream_t st) {
     k_fs_consts<<<flat_grid_fs(p.ones_words), 256, 0, st>>>(reinterpret_cast<float*>(ws + p.qp_off), reinterpret_cast<uint32_t*>(ws + p.ones), p.ones_words);
 }
 
-static int fs_init(const char* fn, bool f16, const qatvit_cfg* cfg, void* workspace, void* stream) {
+static int fs_init(const char* fn, FsForm form, const qatvit_cfg* cfg, void* workspace, void* stream) {
     QV_CHECK_ARG(cfg && workspace, "%s: null argument", fn);
-    if (fs_check(*cfg, f16)) return 1;
-    fs_consts(fs_plan(*cfg, f16), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
+    if (fs_check(*cfg, form)) return 1;
+    fs_consts(fs_plan(*cfg, form), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
     QV_CHECK_LAUNCH(fn);
     return 0;
 }
@@ -446,14 +450,15 @@ struct FsObs {
     uint32_t* w(int wi) const { return stats + p->w_stats[wi]; }
 };
 
-// params: fp32 tensors in the student's order (include/qatvit.h).  Leaves in the workspace everything fs_backward reads.  logits: fp32, or fp16 (f16).
-// observe (the pair form only): also every observer's step (qatvit_float_student_forward_observe).
-static int fs_forward(const char* fn, bool f16, const qatvit_cfg* cfg, void* const* params, const float* images, void* logits, void* workspace,
+// params: fp32 tensors in the student's order (include/qatvit.h).  Leaves in the workspace everything fs_backward reads.  logits: fp32, fp16 (the
+// fp16 form) or bf16 (the bf16 form).  observe (the pair form only): also every observer's step (qatvit_float_student_forward_observe).
+static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* const* params, const float* images, void* logits, void* workspace,
                       void* observe, void* stream) {
     QV_CHECK_ARG(cfg && params && images && logits && workspace, "%s: null argument", fn);
-    if (fs_check(*cfg, f16)) return 1;
+    if (fs_check(*cfg, form)) return 1;
     const qatvit_cfg& c = *cfg;
-    const FsPlan p = fs_plan(c, f16);
+    const FsPlan p = fs_plan(c, form);
+    const bool f16 = form == FsForm::f16, bf16 = form == FsForm::bf16, one = f16 || bf16;
     ObsPlan op{};
     FsObs ob;
     if (observe) {
@@ -471,7 +476,7 @@ static int fs_forward(const char* fn, bool f16, const qatvit_cfg* cfg, void* con
     auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
     auto bprm = [&](int blk, int k) { return prm(4 + 12 * blk + k); };
     // ---- the form's steps
-    auto weight_planes = [&] {   // the weights' (hi, lo) pairs or fp16 planes, as stored and transposed, in one launch
+    auto weight_planes = [&] {   // the weights' (hi, lo) pairs or fp16 / bf16 planes, as stored and transposed, in one launch
         FsWTab t{};
         t.n = 1 + 4 * L;
         int blocks = 0;
@@ -484,21 +489,22 @@ static int fs_forward(const char* fn, bool f16, const qatvit_cfg* cfg, void* con
             blocks += ((t.N[wi] + 31) / 32) * ((t.K[wi] + 31) / 32);
         }
         t.blk0[t.n] = blocks;
-        if (f16) launch_fa_wcast(t.n, t.W, reinterpret_cast<void* const*>(t.hi), reinterpret_cast<void* const*>(t.hiT), t.N, t.K, t.blk0, st);
+        if (one) launch_fa_wcast(t.n, t.W, reinterpret_cast<void* const*>(t.hi), reinterpret_cast<void* const*>(t.hiT), t.N, t.K, t.blk0, st, bf16);
         else k_fs_wsplit<<<blocks, 256, 0, st>>>(t);
     };
     // (act_fq order: 0 quant, 1 patch_embed.proj, per block 2 + 6 i + {norm1, qkv, proj, norm2, fc1, fc2}, then norm, head)
+    // (the bf16 form: no lo planes and not f16 - launch_gemm_nt's one-plane bf16 path)
     auto gemm = [&](int64_t ah, int64_t al, int wi, const float* bias, float* C, int N, int K, int Mrows, int ai) {
         return launch_gemm_nt(V(ah), V(al), V(p.w_hi[wi]), C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, ob.act(ai), ob.stats ? kStatSlots : 1, st,
                               V(p.w_lo[wi]), nullptr, f16);
     };
     auto gelu = [&](const FsBlock& k) {
-        if (f16) launch_fa_gelu(F(k.Y1), V(k.G_hi), M * Hd, st);
+        if (one) launch_fa_gelu(F(k.Y1), V(k.G_hi), M * Hd, st, bf16);
         else launch_gelu_split(F(k.Y1), V(k.G_hi), V(k.G_lo), M * Hd, st);
     };
     auto head = [&](const float* gamma, const float* beta, const float* W, const float* bias) {
-        if (f16)
-            launch_fa_head_fwd(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn), logits, c.batch, D, T, c.num_classes, st);
+        if (one)
+            launch_fa_head_fwd(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn), logits, c.batch, D, T, c.num_classes, st, bf16);
         else if (ob.stats)
             k_fs_head_fwd<true><<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn),
                                                                         reinterpret_cast<float*>(logits), D, T, c.num_classes, ob.act(3 + 6 * L));
@@ -551,14 +557,15 @@ static int fs_forward(const char* fn, bool f16, const qatvit_cfg* cfg, void* con
     return 0;
 }
 
-// dlogits [B, C]: fp32, or fp16 (f16); grads: fp32 tensors in the params order, ZERO on entry (weight / bias / LayerNorm gradients are accumulated
-// into them).  Reads what the last fs_forward of the same form on this workspace (same cfg) left there.
-static int fs_backward(const char* fn, bool f16, const qatvit_cfg* cfg, void* const* params, const void* dlogits, void* const* grads, void* workspace,
+// dlogits [B, C]: fp32, fp16 (the fp16 form) or bf16 (the bf16 form); grads: fp32 tensors in the params order, ZERO on entry (weight / bias /
+// LayerNorm gradients are accumulated into them).  Reads what the last fs_forward of the same form on this workspace (same cfg) left there.
+static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* const* params, const void* dlogits, void* const* grads, void* workspace,
                        void* stream) {
     QV_CHECK_ARG(cfg && params && dlogits && grads && workspace, "%s: null argument", fn);
-    if (fs_check(*cfg, f16)) return 1;
+    if (fs_check(*cfg, form)) return 1;
     const qatvit_cfg& c = *cfg;
-    const FsPlan p = fs_plan(c, f16);
+    const FsPlan p = fs_plan(c, form);
+    const bool f16 = form == FsForm::f16, bf16 = form == FsForm::bf16, one = f16 || bf16;
     char* ws = reinterpret_cast<char*>(workspace);
     hipStream_t st = (hipStream_t)stream;
     const int np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size), T = np + 1, D = c.embed_dim, Hd = c.mlp_hidden, H = c.num_heads;
@@ -569,25 +576,25 @@ static int fs_backward(const char* fn, bool f16, const qatvit_cfg* cfg, void* co
     auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
     auto grd = [&](int i) { return reinterpret_cast<float*>(grads[i]); };
     const float* qp_off = F(p.qp_off);
-    const float* one = qp_off;   // 1.0f: the unit scale of the one-plane GEMMs
+    const float* unit = qp_off;   // 1.0f: the unit scale of the one-plane GEMMs
     float* partial = F(p.tn_partial);
     // ---- the form's steps
     // dgrad: C[M, N] = A[M, K] . W[K, N]  with the transposed weight's planes as the B operand ([N, K] row-major)
     auto dgrad = [&](int64_t ah, int64_t al, int wi, float* C, int N, int K) {
-        if (f16) return launch_gemm_nt_dy16(V(ah), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, one, one, st);
+        if (one) return launch_gemm_nt_dy16(V(ah), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, unit, unit, st, nullptr, bf16);
         return launch_gemm_nt(V(ah), V(al), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st, V(p.w_loT[wi]), nullptr);
     };
     // wgrad: dW[N, Kw] += dY[Mr, N]^T . X[Mr, Kw], dbias[N] += column sums of dY
     auto wgrad = [&](int64_t ph, int64_t pl, int64_t qh, int64_t ql, float* dW, float* db, int N, int Kw, int Mr) {
-        if (f16)
-            return launch_gemm_tn_dy16(V(ph), V(qh), nullptr, dW, Mr, N, Kw, N, Kw, Kw, one, one, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
-                                       kTnScratchBytes);
+        if (one)
+            return launch_gemm_tn_dy16(V(ph), V(qh), nullptr, dW, Mr, N, Kw, N, Kw, Kw, unit, unit, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
+                                       kTnScratchBytes, bf16);
         return launch_gemm_tn(V(ph), V(pl), V(qh), V(ql), dW, Mr, N, Kw, N, Kw, Kw, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
                               kTnScratchBytes);
     };
     auto head = [&] {   // dhn, and the head's weight / bias gradients
-        if (f16) {
-            launch_fa_head_bwd(dlogits, F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), c.batch, D, c.num_classes, st);
+        if (one) {
+            launch_fa_head_bwd(dlogits, F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), c.batch, D, c.num_classes, st, bf16);
             return;
         }
         const int64_t n = (int64_t)c.num_classes * D + (int64_t)c.batch * D + c.num_classes;
@@ -595,19 +602,19 @@ static int fs_backward(const char* fn, bool f16, const qatvit_cfg* cfg, void* co
                                                               c.batch, D, c.num_classes);
     };
     auto gelu_bwd = [&](const FsBlock& k) {   // dY1 = dG * gelu'(Y1)
-        if (f16) return launch_fa_gelu_bwd(F(p.dG), F(k.Y1), V(p.dY1_hi), M * Hd, st);
+        if (one) return launch_fa_gelu_bwd(F(p.dG), F(k.Y1), V(p.dY1_hi), M * Hd, st, bf16);
         return launch_mask_bwd(1, F(p.dG), F(k.Y1), qp_off, 0, 255, nullptr, Hd, V(p.dY1_hi), V(p.dY1_lo), M * Hd, st);
     };
     auto attn_bwd = [&](const FsBlock& k) {   // dqkv from dO
-        if (f16) return launch_attn_bwd_f16(F(k.qkv), V(k.O_hi), F(k.lse), F(p.dO), c.batch, T, H, D, V(p.dqkv_hi), st);
+        if (one) return launch_attn_bwd_f16(F(k.qkv), V(k.O_hi), F(k.lse), F(p.dO), c.batch, T, H, D, V(p.dqkv_hi), st, bf16);
         return launch_attn_bwd_float(F(k.qkv), V(k.O_hi), V(k.O_lo), F(k.lse), F(p.dO), c.batch, T, H, D, F(p.Pm), F(p.dS), F(p.delta), V(p.dqkv_hi),
                                      V(p.dqkv_lo), st);
     };
     auto embed_bwd = [&] {   // pos / cls gradients and dY0 (the patch rows of dx)
-        if (f16) launch_fa_embed_bwd(F(p.dx), grd(3), grd(2), V(p.dY0_hi), c.batch, T, D, st);
+        if (one) launch_fa_embed_bwd(F(p.dx), grd(3), grd(2), V(p.dY0_hi), c.batch, T, D, st, bf16);
         else launch_embed_bwd(F(p.dx), F(p.Y0), qp_off, 0, 255, grd(3), grd(2), V(p.dY0_hi), V(p.dY0_lo), c.batch, T, D, st);
     };
-    auto fp16_overflow = [&] {   // the fp16 form: the overflow rule of the fp16 Linear / Conv2d weight and bias gradients
+    auto fp16_overflow = [&] {   // the fp16 form: the overflow rule of the fp16 Linear / Conv2d weight and bias gradients (bf16 has fp32's range)
         if (!f16) return;
         float* g[2 * kMaxW];
         int64_t n[2 * kMaxW];
@@ -621,8 +628,9 @@ static int fs_backward(const char* fn, bool f16, const qatvit_cfg* cfg, void* co
         }
         launch_fa_inf_rule(g, n, count, st);
     };
-    // the LayerNorm backward's second output: the residual gradient as the next branch's GEMM operand dp (mask all ones; the fp16 form: unit multiplier)
-    LnBwdNext next{V(p.ones), nullptr, V(p.dp_hi), V(p.dp_lo), f16 ? one : nullptr, reinterpret_cast<uint32_t*>(V(p.amax))};
+    // the LayerNorm backward's second output: the residual gradient as the next branch's GEMM operand dp (mask all ones; the fp16 form: unit multiplier;
+    // the bf16 form: no lo plane, so one bf16 plane)
+    LnBwdNext next{V(p.ones), nullptr, V(p.dp_hi), V(p.dp_lo), f16 ? unit : nullptr, reinterpret_cast<uint32_t*>(V(p.amax))};
     // head, then the final norm on the cls rows (dx of every other row = 0); the residual gradient leaves as fp32 (dx) and as dp
     head();
     if (launch_ln_bwd_fq(0, F(p.dhn), F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), qp_off, 0, 255, nullptr, F(p.dx), grd(hb), grd(hb + 1), M, D, T,
@@ -660,43 +668,61 @@ static int fs_backward(const char* fn, bool f16, const qatvit_cfg* cfg, void* co
 }
 
 // ---------------------------------------------------------------- the C ABI (include/qatvit.h)
-int64_t qatvit_float_student_workspace_bytes(const qatvit_cfg* cfg) { return fs_workspace_bytes("qatvit_float_student_workspace_bytes", false, cfg); }
+int64_t qatvit_float_student_workspace_bytes(const qatvit_cfg* cfg) { return fs_workspace_bytes("qatvit_float_student_workspace_bytes", FsForm::pair, cfg); }
 
 int qatvit_float_student_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
-    return fs_init("qatvit_float_student_init", false, cfg, workspace, stream);
+    return fs_init("qatvit_float_student_init", FsForm::pair, cfg, workspace, stream);
 }
 
 int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream) {
-    return fs_forward("qatvit_float_student_forward", false, cfg, params, images, logits, workspace, nullptr, stream);
+    return fs_forward("qatvit_float_student_forward", FsForm::pair, cfg, params, images, logits, workspace, nullptr, stream);
 }
 
 int qatvit_float_student_backward(const qatvit_cfg* cfg, void* const* params, const float* dlogits, void* const* grads, void* workspace, void* stream) {
-    return fs_backward("qatvit_float_student_backward", false, cfg, params, dlogits, grads, workspace, stream);
+    return fs_backward("qatvit_float_student_backward", FsForm::pair, cfg, params, dlogits, grads, workspace, stream);
 }
 
-int64_t qatvit_float_student_amp_workspace_bytes(const qatvit_cfg* cfg) { return fs_workspace_bytes("qatvit_float_student_amp_workspace_bytes", true, cfg); }
+int64_t qatvit_float_student_amp_workspace_bytes(const qatvit_cfg* cfg) {
+    return fs_workspace_bytes("qatvit_float_student_amp_workspace_bytes", FsForm::f16, cfg);
+}
 
 int qatvit_float_student_amp_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
-    return fs_init("qatvit_float_student_amp_init", true, cfg, workspace, stream);
+    return fs_init("qatvit_float_student_amp_init", FsForm::f16, cfg, workspace, stream);
 }
 
 int qatvit_float_student_amp_forward(const qatvit_cfg* cfg, void* const* params, const float* images, void* logits_f16, void* workspace, void* stream) {
-    return fs_forward("qatvit_float_student_amp_forward", true, cfg, params, images, logits_f16, workspace, nullptr, stream);
+    return fs_forward("qatvit_float_student_amp_forward", FsForm::f16, cfg, params, images, logits_f16, workspace, nullptr, stream);
 }
 
 int qatvit_float_student_amp_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_f16, void* const* grads, void* workspace, void* stream) {
-    return fs_backward("qatvit_float_student_amp_backward", true, cfg, params, dlogits_f16, grads, workspace, stream);
+    return fs_backward("qatvit_float_student_amp_backward", FsForm::f16, cfg, params, dlogits_f16, grads, workspace, stream);
+}
+
+int64_t qatvit_float_student_bf16_workspace_bytes(const qatvit_cfg* cfg) {
+    return fs_workspace_bytes("qatvit_float_student_bf16_workspace_bytes", FsForm::bf16, cfg);
+}
+
+int qatvit_float_student_bf16_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
+    return fs_init("qatvit_float_student_bf16_init", FsForm::bf16, cfg, workspace, stream);
+}
+
+int qatvit_float_student_bf16_forward(const qatvit_cfg* cfg, void* const* params, const float* images, void* logits_bf16, void* workspace, void* stream) {
+    return fs_forward("qatvit_float_student_bf16_forward", FsForm::bf16, cfg, params, images, logits_bf16, workspace, nullptr, stream);
+}
+
+int qatvit_float_student_bf16_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_bf16, void* const* grads, void* workspace, void* stream) {
+    return fs_backward("qatvit_float_student_bf16_backward", FsForm::bf16, cfg, params, dlogits_bf16, grads, workspace, stream);
 }
 
 int64_t qatvit_float_student_observe_bytes(const qatvit_cfg* cfg) {
     if (!cfg) { set_error("qatvit_float_student_observe_bytes: null argument"); return -1; }
-    if (fs_check(*cfg, false)) return -1;
+    if (fs_check(*cfg, FsForm::pair)) return -1;
     return obs_plan(*cfg).total;
 }
 
 int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* act_fq, const qatvit_fq* weight_fq, void* observe, void* stream) {
     QV_CHECK_ARG(cfg && act_fq && weight_fq && observe, "qatvit_float_student_observe_init: null argument");
-    if (fs_check(*cfg, false)) return 1;
+    if (fs_check(*cfg, FsForm::pair)) return 1;
     const qatvit_cfg& c = *cfg;
     const ObsPlan p = obs_plan(c);
     char* ob = reinterpret_cast<char*>(observe);
@@ -731,7 +757,7 @@ int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* ac
 int qatvit_float_student_forward_observe(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* observe,
                                          void* stream) {
     QV_CHECK_ARG(observe, "qatvit_float_student_forward_observe: null argument");
-    return fs_forward("qatvit_float_student_forward_observe", false, cfg, params, images, logits, workspace, observe, stream);
+    return fs_forward("qatvit_float_student_forward_observe", FsForm::pair, cfg, params, images, logits, workspace, observe, stream);
 }
 
 }  // extern "C"

@@ -1255,7 +1255,11 @@ int launch_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, 
 }
 
 int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1, const float* s2,
-                        hipStream_t st, const NTPost* post) {
+                        hipStream_t st, const NTPost* post, bool bf16) {
+    if (bf16 && post) {
+        set_error("gemm_nt_dy16: the bf16 form has the plain epilogue only");
+        return 1;
+    }
     if (M < 1 || N % 384 != 0 || K % 32 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0 || !A16 || !B16) {
         set_error("gemm_nt_dy16: unsupported arguments M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (need N%%384==0, K%%32==0)", M, N, K, lda, ldb, ldc);
         return 1;
@@ -1293,7 +1297,8 @@ int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N
     // BK = 64, two stages: every LDS-DMA request is a whole 128-byte line of a gradient / weight row (BK = 32: half lines, each line requested by two k-steps).
     // Same box, same step: dgrad + LayerNorm backward 108.8 -> 103.8 us, + GELU backward 135.4 -> 131.9, plain 29.8 -> 28.5 (three stages of BK = 32; a fourth changed
     // nothing: 105.1 vs 104.5).  The k-values enter the accumulators in the same order: the same bits.
-    nt_launch<1, 2, 1, 13, 1, 8, 3, 64, false, true>(a, cdiv(M, 208) * (N / 384), post ? lds : (size_t)2 * (208 + 384) * 128, st);
+    if (bf16) nt_launch<1, 2, 1, 13, 1, 8, 3, 64>(a, cdiv(M, 208) * (N / 384), lds, st);   // the same tile and ring on bf16 MFMA
+    else nt_launch<1, 2, 1, 13, 1, 8, 3, 64, false, true>(a, cdiv(M, 208) * (N / 384), post ? lds : (size_t)2 * (208 + 384) * 128, st);
     return 0;
 }
 
@@ -1423,9 +1428,10 @@ __device__ inline bf16x8 tr_frag(const char* img, int row0, int col0, int lane) 
 // into the hi / lo images in the layout the LDS-DMA of the plane form produces), the MFMAs of step s+1 read them: same fragments, same bits.
 // TP = 1, F16: the one-plane backward - P is ONE fp16 plane (the gradient scaled by a power of two, its inverse in *s2), Q holds fp16 bit patterns too
 // (grid integers as fp16, or an fp16 (hi, lo) pair / a table of fp16 pairs): v_mfma_f32_16x16x32_f16, one pass per Q plane instead of two.
+// TP = 1, !F16: the same with bf16 planes on v_mfma_f32_16x16x32_bf16 (the float step's bf16 form).
 template <int TQ, int NSTAGE, int WM, int WNK, int TNT, int BK, bool QC = false, int TP = 2, bool F16 = false>
 __global__ __launch_bounds__(WM * WNK * 64) void k_gemm_tn(const TNArgs p) {
-    static_assert((TP == 2 && !F16) || (TP == 1 && F16), "bf16 pair or one fp16 plane");
+    static_assert(TP == 1 || !F16, "bf16 pair, one fp16 plane or one bf16 plane");
     auto mm = [](const bf16x8& a, const bf16x8& b, const f32x4& c) -> f32x4 {
         if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
         else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
@@ -2031,8 +2037,8 @@ static TNArgs tn_args(const void* P_hi, const void* P_lo, const void* Q_hi, cons
     return a;
 }
 
-// DY16: P_hi is the one fp16 plane (P_lo unused), Q holds fp16 bit patterns, *s2 the plane's inverse scale
-template <bool DY16>
+// DY16: P_hi is the one fp16 plane (P_lo unused), Q holds fp16 bit patterns, *s2 the plane's inverse scale; F16 = false with DY16: bf16 bit patterns instead
+template <bool DY16, bool F16 = DY16>
 static int gemm_tn_impl(const void* P_hi, const void* P_lo, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
                         const float* s1, const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
                         float* dbias, const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
@@ -2059,9 +2065,9 @@ static int gemm_tn_impl(const void* P_hi, const void* P_lo, const void* Q_hi, co
         const int64_t tile_f4 = (int64_t)WM_ * WNK_ * tm * TNT_ * 64;                                              \
         const bool two_phase = partial && splits > 1 && (int64_t)grid * tile_f4 * 16 <= partial_bytes;             \
         a.partial = two_phase ? partial : nullptr;                                                                 \
-        static bool once = (allow_lds(k_gemm_tn<TQ_, NS_, WM_, WNK_, TNT_, BK_, false, TP, DY16>, lds), true);     \
+        static bool once = (allow_lds(k_gemm_tn<TQ_, NS_, WM_, WNK_, TNT_, BK_, false, TP, F16>, lds), true);      \
         (void)once;                                                                                                \
-        k_gemm_tn<TQ_, NS_, WM_, WNK_, TNT_, BK_, false, TP, DY16><<<grid, WM_ * WNK_ * 64, lds, st>>>(a);         \
+        k_gemm_tn<TQ_, NS_, WM_, WNK_, TNT_, BK_, false, TP, F16><<<grid, WM_ * WNK_ * 64, lds, st>>>(a);          \
         if (two_phase) k_tn_reduce<<<(int)cdiv((int64_t)tiles * tile_f4, 256), 256, 0, st>>>(a, splits, WM_, WNK_, tm, TNT_); \
     } while (0)
     if constexpr (DY16) {   // one P plane: the stages are 8 KiB (wide) / 16 KiB (narrow) smaller, the rings one stage deeper
@@ -2091,7 +2097,10 @@ int launch_gemm_tn(const void* P_hi, const void* P_lo, const void* Q_hi, const v
 }
 int launch_gemm_tn_dy16(const void* P16, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
                         const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                        const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
+                        const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes, bool bf16) {
+    if (bf16)
+        return gemm_tn_impl<true, false>(P16, nullptr, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias,
+                                         row_div, st, partial, partial_bytes);
     return gemm_tn_impl<true>(P16, nullptr, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div, st,
                               partial, partial_bytes);
 }

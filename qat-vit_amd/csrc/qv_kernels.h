@@ -116,9 +116,9 @@ int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
 // operand A16 as ONE fp16 plane pre-scaled by a power of two (its inverse arrives in *s2) and the transposed weight integers B16 as fp16 (exact):
 // one v_mfma_f32_16x16x32_f16 pass, 2 B per gradient element.  post: nullptr (plain fp32 output: proj dgrad), mode 8 (fused LayerNorm backward)
 // or mode 9 (fused GELU backward) with o16_mul / o16_amax set - the masked gradient for the next layer then leaves as one fp16 plane too.
-// N % 384 == 0, K % 32 == 0.
+// N % 384 == 0, K % 32 == 0.  bf16 (plain output only): both operands hold bf16 bit patterns, v_mfma_f32_16x16x32_bf16 (the float step's bf16 form).
 int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1, const float* s2,
-                        hipStream_t st, const NTPost* post = nullptr);
+                        hipStream_t st, const NTPost* post = nullptr, bool bf16 = false);
 // ---- f16strip.hip: the fc2 dgrad + GELU backward of the one-plane backward, A-stationary (K = 384, N = 1536); B16f = the transposed weight integers as fp16 in
 // fragment order (w8f_offset on their 768-byte rows).  true when it took the request; false -> launch_gemm_nt_dy16 with epilogue mode 9
 bool launch_f16_strip_gelu_bwd(const void* A16, const void* B16f, float* unused, int M, int N, int K, int lda, int ldc, const float* s1, const float* s2, hipStream_t st,
@@ -148,10 +148,11 @@ int launch_gemm_tn_codes(const void* P_hi, const void* P_lo, const void* Qc, con
                          const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
                          const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
 // the one-plane forms of the two weight-gradient launchers: P16 = the gradient as ONE fp16 plane scaled by a power of two (*s2 = its inverse; the bias
-// gradient is multiplied by it too), Q = fp16 bit patterns (grid integers, an fp16 (hi, lo) pair, or codes + a table of fp16 pairs); *s1 = Q's scale
+// gradient is multiplied by it too), Q = fp16 bit patterns (grid integers, an fp16 (hi, lo) pair, or codes + a table of fp16 pairs); *s1 = Q's scale.
+// bf16: P16 and Q hold bf16 bit patterns instead, v_mfma_f32_16x16x32_bf16 (the float step's bf16 form)
 int launch_gemm_tn_dy16(const void* P16, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
                         const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                        const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
+                        const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0, bool bf16 = false);
 int launch_gemm_tn_codes_dy16(const void* P16, const void* Qc, const uint32_t* lutQ16, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
                               const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
                               const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
@@ -177,7 +178,8 @@ int launch_resid_fq_lnstats(int mode, const float* x_prev, const float* Y, const
                             int64_t M, int D, int T, hipStream_t st, void* maskbits = nullptr, const QpLate* late = nullptr);   // late: Y's qparams are resolved inside (QpLate)
 // STE mask of an [M, D] tensor as wave ballots: ceil(D / 256) * 4 64-bit words per row (written by launch_resid_fq_lnstats mode 1)
 inline int64_t ln_maskbits_bytes(int64_t M, int D) { return M * ((D + 255) / 256) * 32; }
-// optional second output of launch_ln_bwd_fq: split(dx_out * mask * colscale) for the next branch's GEMMs
+// optional second output of launch_ln_bwd_fq: split(dx_out * mask * colscale) for the next branch's GEMMs (out_lo == nullptr without o16_*: its hi part
+// only, ONE bf16 plane)
 struct LnBwdNext { const void* maskbits; const float* colscale; void* out_hi; void* out_lo; const float* o16_mul = nullptr; uint32_t* o16_amax = nullptr; };   // o16_*: out_hi is ONE fp16 plane (dy16.hip)
 int launch_ln_apply_quant(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp, int qmin,
                           int qmax, void* out_bf16, int64_t M, int D, hipStream_t st, void* out8 = nullptr, int center = 0,
@@ -263,7 +265,8 @@ bool attn_bwd_is_fused(int T, int H, int D, bool codes);
 // ---- teacher.hip: the float forward pieces (bf16 (hi, lo) pairs; the float student step shares them)
 // lse (optional): log-sum-exp of the scaled scores per query, [B][H][T]
 int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16 = 0, float* lse = nullptr);
-// f16 != 0: fp16 bit patterns instead of bf16 (lo == nullptr: the one-plane form keeps the hi part only; the same for launch_resid_ln_split_save)
+// f16 != 0: fp16 bit patterns instead of bf16.  lo == nullptr: the one-plane form keeps the hi part only (fp16 or bf16); the same for
+// launch_resid_ln_split_save and launch_attn_fwd_float
 int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st, int f16 = 0);
 // mode 0: x = [cls; Y] + pos, mode 1: x = x_prev + Y; then LayerNorm(x) as a (hi, lo) pair, mean / rstd per row (optional); stats (optional):
 // kStatSlots {min, max} accumulator pairs that take the min / max of the fp32 LayerNorm outputs (the observe-only forward)
@@ -271,20 +274,23 @@ int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, co
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
                                uint32_t* stats = nullptr, int f16 = 0);
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st);   // n % 4 == 0
-// ---- float_amp.hip: the fp16 (autocast) form of the float student step (its host driver is float_step.hip's).  Fused attention backward on
-// v_mfma_f32_16x16x32_f16, one workgroup per (image, head): qkv / dO fp32 [B*T, 3D] / [B*T, D] (rounded to fp16 on load), O16 fp16 [B*T, D],
-// lse [B][H][T] -> dqkv16 fp16 [B*T, 3D]
-int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st);
+// ---- float_amp.hip: the fp16 (autocast) form of the float student step, and (bf16 = true) its bf16 form: the same pieces on bf16 planes and
+// v_mfma_f32_16x16x32_bf16 (the host driver of both is float_step.hip's).  Fused attention backward on v_mfma_f32_16x16x32_f16, one workgroup per
+// (image, head): qkv / dO fp32 [B*T, 3D] / [B*T, D] (rounded to fp16 on load), O16 fp16 [B*T, D], lse [B][H][T] -> dqkv16 fp16 [B*T, 3D]
+int launch_attn_bwd_f16(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st,
+                        bool bf16 = false);
 // the n weights as fp16, as stored [N, K] and transposed, in one launch (blk0[wi]: first workgroup of weight wi, 32 x 32 tiles; blk0[n]: the total)
-int launch_fa_wcast(int n, const float* const* W, void* const* w16, void* const* w16T, const int* N, const int* K, const int* blk0, hipStream_t st);
+int launch_fa_wcast(int n, const float* const* W, void* const* w16, void* const* w16T, const int* N, const int* K, const int* blk0, hipStream_t st,
+                    bool bf16 = false);
 // head: hn = fp16(LN(cls rows)) kept as fp32 values, fp16 logits [B, C]; backward from fp16 dlogits (fixed summation order)
 int launch_fa_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias, float* hn,
-                       void* logits16, int B, int D, int T, int C, hipStream_t st);
-int launch_fa_head_bwd(const void* dl16, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st);
-int launch_fa_gelu(const float* Y, void* G16, int64_t n, hipStream_t st);                          // G16 = fp16(gelu(Y)), n % 4 == 0
-int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, hipStream_t st);     // dY16 = fp16(fp16(dG) gelu'(Y)), n % 4 == 0
+                       void* logits16, int B, int D, int T, int C, hipStream_t st, bool bf16 = false);
+int launch_fa_head_bwd(const void* dl16, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st,
+                       bool bf16 = false);
+int launch_fa_gelu(const float* Y, void* G16, int64_t n, hipStream_t st, bool bf16 = false);                        // G16 = fp16(gelu(Y)), n % 4 == 0
+int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, hipStream_t st, bool bf16 = false);   // dY16 = fp16(fp16(dG) gelu'(Y)), n % 4 == 0
 // dpos / dcls from dx [B*T, D] (fixed order), dY0_16 = fp16 of dx's patch rows
-int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16, int B, int T, int D, hipStream_t st);
+int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16, int B, int T, int D, hipStream_t st, bool bf16 = false);
 // the overflow rule of the fp16 Linear / Conv2d gradients on count <= 100 fp32 tensors g[k] of n[k] elements: g -> fp16(g) where that is +-inf
 int launch_fa_inf_rule(float* const* g, const int64_t* n, int count, hipStream_t st);
 // grid of the float step's flat elementwise kernels (float_step.hip, float_amp.hip)

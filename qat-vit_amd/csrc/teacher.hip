@@ -26,6 +26,8 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // (hi, lo) pair of four values: bf16 (8 + 8 significant bits) or, f16 != 0 (uniform), fp16 (11 + 11; unscaled: the teacher's GEMM inputs - LayerNorm
 // outputs, attention outputs, GELU outputs, image patches - are far inside fp16's range).  lo == nullptr: the one-pass form keeps the hi part only.
+// BF1: the bf16 one-plane form (the float step's bf16 form; f16 == 0, lo unused): bf16(v) only.
+template <bool BF1 = false>
 __device__ inline void st_split4(__bf16* hi, __bf16* lo, int64_t off, float a, float b, float c, float d, int f16 = 0) {
     if (f16) {
         f16x4 h, l;
@@ -39,12 +41,17 @@ __device__ inline void st_split4(__bf16* hi, __bf16* lo, int64_t off, float a, f
     }
     bf16x4 h, l;
     h[0] = (__bf16)a; h[1] = (__bf16)b; h[2] = (__bf16)c; h[3] = (__bf16)d;
+    if constexpr (BF1) {
+        *reinterpret_cast<bf16x4*>(hi + off) = h;
+        return;
+    }
     l[0] = (__bf16)(a - (float)h[0]); l[1] = (__bf16)(b - (float)h[1]); l[2] = (__bf16)(c - (float)h[2]); l[3] = (__bf16)(d - (float)h[3]);
     *reinterpret_cast<bf16x4*>(hi + off) = h;
     *reinterpret_cast<bf16x4*>(lo + off) = l;
 }
 
 // image [B,C,H,W] fp32 -> patch rows [B*np, C*P*P] as a (hi, lo) pair
+template <bool BF1 = false>
 __global__ __launch_bounds__(256) void k_patches_split(const float* __restrict__ img, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int B, int C,
                                                        int H, int W, int P, int f16) {
     const int gw = W / P, gh = H / P, K = C * P * P;
@@ -56,7 +63,7 @@ __global__ __launch_bounds__(256) void k_patches_split(const float* __restrict__
         const int px = (int)(prow % gw), py = (int)((prow / gw) % gh), b = (int)(prow / ((int64_t)gw * gh));
         const int j = col % P, i = (col / P) % P, c = col / (P * P);
         const float4 v = *reinterpret_cast<const float4*>(img + (((int64_t)b * C + c) * H + py * P + i) * W + px * P + j);
-        st_split4(hi, lo, e, v.x, v.y, v.z, v.w, f16);
+        st_split4<BF1>(hi, lo, e, v.x, v.y, v.z, v.w, f16);
     }
 }
 
@@ -67,8 +74,8 @@ __device__ inline void t_pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y
 // and is masked out): one `if (c < D)` region per group let LLVM sink each group's loads to its uses - three dependent HBM round trips
 // per row at D = 768.  gamma / beta once per thread.
 // STATS (the observe-only student forward): min / max of the fp32 LayerNorm outputs, one wave reduction and one accumulator atomic per wave
-// (kStatSlots pairs); the instantiations without it are the teacher's and the float step's, unchanged.
-template <int MODE, int NV, bool STATS = false>
+// (kStatSlots pairs); the instantiations without it are the teacher's and the float step's, unchanged.  BF1: h as ONE bf16 plane (st_split4).
+template <int MODE, int NV, bool STATS = false, bool BF1 = false>
 __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict__ x_prev, const float* __restrict__ Y, const float* __restrict__ cls,
                                                         const float* __restrict__ pos, float* __restrict__ x_new, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, __bf16* __restrict__ h_hi,
@@ -127,13 +134,13 @@ __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict_
                                 o3 = v[j].w * rs * g[j].w + bb[j].w;
                     smn = fminf(smn, fminf(fminf(o0, o1), fminf(o2, o3)));
                     smx = fmaxf(smx, fmaxf(fmaxf(o0, o1), fmaxf(o2, o3)));
-                    st_split4(h_hi, h_lo, row * D + cc[j], o0, o1, o2, o3, f16);
+                    st_split4<BF1>(h_hi, h_lo, row * D + cc[j], o0, o1, o2, o3, f16);
                 }
         } else {
 #pragma unroll
             for (int j = 0; j < NV; ++j)
                 if (act[j])
-                    st_split4(h_hi, h_lo, row * D + cc[j], v[j].x * rs * g[j].x + bb[j].x, v[j].y * rs * g[j].y + bb[j].y, v[j].z * rs * g[j].z + bb[j].z,
+                    st_split4<BF1>(h_hi, h_lo, row * D + cc[j], v[j].x * rs * g[j].x + bb[j].x, v[j].y * rs * g[j].y + bb[j].y, v[j].z * rs * g[j].z + bb[j].z,
                               v[j].w * rs * g[j].w + bb[j].w, f16);
         }
     }
@@ -143,12 +150,12 @@ __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict_
         if (lane == 0) stat_atomic(stats, kStatSlots, smn, smx);
     }
 }
-template <int MODE, bool STATS = false, typename... A>
+template <int MODE, bool STATS = false, bool BF1 = false, typename... A>
 static void launch_resid_ln_split(int grid, hipStream_t st, int D, A... a) {
     const int nv = (D + 255) / 256;
-    if (nv == 1) k_resid_ln_split<MODE, 1, STATS><<<grid, 256, 0, st>>>(a...);
-    else if (nv == 2) k_resid_ln_split<MODE, 2, STATS><<<grid, 256, 0, st>>>(a...);
-    else k_resid_ln_split<MODE, 3, STATS><<<grid, 256, 0, st>>>(a...);
+    if (nv == 1) k_resid_ln_split<MODE, 1, STATS, BF1><<<grid, 256, 0, st>>>(a...);
+    else if (nv == 2) k_resid_ln_split<MODE, 2, STATS, BF1><<<grid, 256, 0, st>>>(a...);
+    else k_resid_ln_split<MODE, 3, STATS, BF1><<<grid, 256, 0, st>>>(a...);
 }
 
 __device__ inline float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
@@ -239,7 +246,7 @@ __device__ inline bool t_wave_retile8(float* sO, const f32x4 (&acc)[HD / 16], fl
 }
 
 constexpr int kTW = 8;  // waves per workgroup
-template <int HD, int NKT>
+template <int HD, int NKT, bool BF1 = false>   // BF1: O as ONE bf16 plane (the float step's bf16 form)
 __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __restrict__ qkv, int B, int T, int H, int D, float scale,
                                                              __bf16* __restrict__ O_hi, __bf16* __restrict__ O_lo, int f16,
                                                              float* __restrict__ lse = nullptr) {
@@ -367,7 +374,7 @@ __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __rest
 #pragma unroll
                     for (int j = 0; j < 8; ++j) { hv[j] = (__bf16)ov[j]; lv[j] = (__bf16)(ov[j] - (float)hv[j]); }
                     *reinterpret_cast<bf16x8*>(O_hi + off) = hv;
-                    *reinterpret_cast<bf16x8*>(O_lo + off) = lv;
+                    if constexpr (!BF1) *reinterpret_cast<bf16x8*>(O_lo + off) = lv;
                 }
             }
         }
@@ -383,13 +390,19 @@ static int rows_grid_t(int64_t rows) {
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
+template <int HD, int NKT, bool BF1>
+static void launch_attn_float_k(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16, float* lse) {
+    const size_t lds = (size_t)4 * NKT * 16 * HD * 2 + (size_t)kTW * 8 * (HD + 4) * sizeof(float);
+    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_fwd_float<HD, NKT, BF1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                        true);
+    (void)once;
+    k_attn_fwd_float<HD, NKT, BF1><<<B * H, kTW * 64, lds, st>>>(qkv, B, T, H, D, 1.0f / sqrtf((float)HD), reinterpret_cast<__bf16*>(O_hi),
+                                                                 reinterpret_cast<__bf16*>(O_lo), f16, lse);
+}
 template <int HD, int NKT>
 static void launch_attn_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16, float* lse) {
-    const size_t lds = (size_t)4 * NKT * 16 * HD * 2 + (size_t)kTW * 8 * (HD + 4) * sizeof(float);
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_fwd_float<HD, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)once;
-    k_attn_fwd_float<HD, NKT><<<B * H, kTW * 64, lds, st>>>(qkv, B, T, H, D, 1.0f / sqrtf((float)HD), reinterpret_cast<__bf16*>(O_hi),
-                                                            reinterpret_cast<__bf16*>(O_lo), f16, lse);
+    if (!f16 && !O_lo) launch_attn_float_k<HD, NKT, true>(qkv, B, T, H, D, O_hi, O_lo, st, f16, lse);   // one bf16 plane
+    else launch_attn_float_k<HD, NKT, false>(qkv, B, T, H, D, O_hi, O_lo, st, f16, lse);
 }
 
 int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16, float* lse) {
@@ -402,10 +415,12 @@ int launch_attn_fwd_float(const float* qkv, int B, int T, int H, int D, void* O_
     return 0;
 }
 
-// the forward pieces the float student step (float_step.hip) shares: the bf16-pair form, or (f16, float_amp.hip) one fp16 plane
+// the forward pieces the float student step (float_step.hip) shares: the bf16-pair form, or (f16, float_amp.hip) one fp16 plane, or (neither f16
+// nor a lo plane) one bf16 plane
 int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int H, int W, int P, hipStream_t st, int f16) {
     const int64_t n = (int64_t)B * (H / P) * (W / P) * C * P * P;
-    k_patches_split<<<flat_grid_t(n / 4), 256, 0, st>>>(img, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), B, C, H, W, P, f16);
+    if (!f16 && !lo) k_patches_split<true><<<flat_grid_t(n / 4), 256, 0, st>>>(img, reinterpret_cast<__bf16*>(hi), nullptr, B, C, H, W, P, 0);
+    else k_patches_split<<<flat_grid_t(n / 4), 256, 0, st>>>(img, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), B, C, H, W, P, f16);
     return 0;
 }
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
@@ -416,6 +431,11 @@ int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, co
     if (stats) {
         if (mode == 0) launch_resid_ln_split<0, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats);
         else launch_resid_ln_split<1, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats);
+        return 0;
+    }
+    if (!f16 && !hl) {   // one bf16 plane
+        if (mode == 0) launch_resid_ln_split<0, false, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
+        else launch_resid_ln_split<1, false, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd);
         return 0;
     }
     if (mode == 0) launch_resid_ln_split<0>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, f16, mean, rstd);

@@ -7,7 +7,9 @@ unprepared ``QATWrapper(vit_*_patch16_224)`` into the native step: its ``forward
 MFMA passes per product) whatever autocast says.  ``native_float(wrapper, amp=True)`` adds the fp16 form
 (``qatvit_float_student_amp_*``): a forward inside ``torch.autocast("cuda", dtype=torch.float16)`` then follows stock autocast - fp16 GEMM
 operands, fp32 residual / LayerNorm / softmax, fp16 logits - and outside autocast runs the fp32-accurate form above; the choice is made per
-forward.  Without the opt-in nothing changes: the float tree is ordinary ``nn.Module`` code.
+forward.  ``amp=torch.bfloat16`` adds the bf16 form (``qatvit_float_student_bf16_*``) the same way for
+``torch.autocast("cuda", dtype=torch.bfloat16)`` (bf16 planes and MFMA, bf16 logits), and ``amp=(torch.float16, torch.bfloat16)`` follows both
+autocast dtypes.  Without the opt-in nothing changes: the float tree is ordinary ``nn.Module`` code.
 
 Engines live in a ``WeakKeyDictionary`` keyed by the wrapper, never on the module, so ``copy.deepcopy`` / ``prepare_qat(inplace=False)``
 copy no ctypes state; a copy is not opted in.  A prepared wrapper always takes the QAT engine (engine.py) first.
@@ -26,8 +28,8 @@ from . import native
 _OPTED = weakref.WeakKeyDictionary()   # wrapper -> FloatStudentEngine (or None until its first CUDA forward)
 
 
-def check_shape(model: nn.Module, amp: bool = False) -> None:
-    """Raise unless the native float step covers this tree (the QAT engine's limits; amp: also the fp16 form's)."""
+def check_shape(model: nn.Module, amp=False) -> None:
+    """Raise unless the native float step covers this tree (the QAT engine's limits; amp: also the fp16 / bf16 forms')."""
     from .vit import VisionTransformer
 
     if not isinstance(model, VisionTransformer):
@@ -61,14 +63,28 @@ def check_shape(model: nn.Module, amp: bool = False) -> None:
             why.append("layer scale / drop-path")
             break
     if amp and (D % 384 or model.blocks[0].mlp.fc1.weight.shape[0] % 384):
-        why.append(f"amp=True: embed_dim {D} and mlp hidden {model.blocks[0].mlp.fc1.weight.shape[0]} (multiples of 384 for the fp16 form)")
+        why.append(f"amp=True: embed_dim {D} and mlp hidden {model.blocks[0].mlp.fc1.weight.shape[0]} (multiples of 384 for the fp16 / bf16 forms)")
     if why:
         raise RuntimeError("native float step: unsupported model: " + "; ".join(why))
 
 
-# the two forms: (prefix of the C symbols, dtype of the logits and dlogits)
+# the forms: (prefix of the C symbols, dtype of the logits and dlogits)
 FP32 = ("qatvit_float_student", torch.float32)        # fp32-accurate: bf16 (hi, lo) pairs, three MFMA passes
 FP16 = ("qatvit_float_student_amp", torch.float16)    # stock fp16 autocast
+BF16 = ("qatvit_float_student_bf16", torch.bfloat16)  # stock bf16 autocast
+
+
+def autocast_dtypes(amp) -> tuple:
+    """native_float's ``amp`` as the autocast dtypes the engine follows: False -> (), True -> (fp16,), a dtype or several."""
+    if amp is None or amp is False:
+        return ()
+    if amp is True:
+        return (torch.float16,)
+    dts = (amp,) if isinstance(amp, torch.dtype) else tuple(amp)
+    for dt in dts:
+        if dt not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"native_float: amp={amp!r}: the native forms follow autocast dtypes torch.float16 and torch.bfloat16")
+    return dts
 
 
 class Form:
@@ -102,10 +118,10 @@ class Form:
 
 
 class FloatStudentEngine:
-    def __init__(self, wrapper: nn.Module, amp: bool = False):
+    def __init__(self, wrapper: nn.Module, amp=False):
         model = wrapper.model
-        check_shape(model, amp)
-        self.amp = amp
+        self.amp = autocast_dtypes(amp)   # the autocast dtypes this engine follows (empty: the fp32-accurate form always)
+        check_shape(model, bool(self.amp))
         self.lib = native.lib()
         self.params = native.vit_params(model)
         dev = self.params[0].device
@@ -116,8 +132,8 @@ class FloatStudentEngine:
         self._cfg_kw = dict(native.vit_shape(model), act_qmin=0, act_qmax=255, w_qmin=-128, w_qmax=127, w_per_channel=0, averaging_const=0.01)
         self._ptrs_key = tuple(p.data_ptr() for p in self.params)
         self._ptr_params = (ctypes.c_void_p * len(self.params))(*self._ptrs_key)
-        self.fp32, self.fp16 = Form(*FP32), Form(*FP16)   # each workspace allocated by the first forward of its form
-        self.generation = 0         # bumped by every forward of either form: the workspaces hold the activations of exactly one forward
+        self.fp32, self.fp16, self.bf16 = Form(*FP32), Form(*FP16), Form(*BF16)   # each workspace allocated by the first forward of its form
+        self.generation = 0         # bumped by every forward of any form: the workspaces hold the activations of exactly one forward
         self.grad_numel = sum(p.numel() for p in self.params)
 
     def cfg_for(self, batch: int) -> native.Cfg:
@@ -134,14 +150,22 @@ class FloatStudentEngine:
     def stale(self) -> bool:
         return tuple(p.data_ptr() for p in self.params) != self._ptrs_key
 
-    def forward(self, images: torch.Tensor, f16: bool = False) -> torch.Tensor:
+    def autocast_form(self, dt: torch.dtype) -> Form:
+        """The form that follows autocast dtype dt, or RuntimeError when this engine does not follow it."""
+        if dt not in self.amp:
+            names = " / ".join(f"torch.autocast('cuda', dtype={d})" for d in self.amp)
+            raise RuntimeError(f"native float step (amp=True): autocast dtype {dt} is not supported; this engine follows {names} only "
+                               "(native_float(..., amp=...) selects the autocast dtypes)")
+        return self.fp16 if dt == torch.float16 else self.bf16
+
+    def forward(self, images: torch.Tensor, form: Optional[Form] = None) -> torch.Tensor:
         k = self._cfg_kw
         if images.dim() != 4 or images.shape[0] < 1 or tuple(images.shape[1:]) != (k["in_chans"], k["img_size"], k["img_size"]):
             raise RuntimeError(f"expected images of shape (B, {k['in_chans']}, {k['img_size']}, {k['img_size']}), got {tuple(images.shape)}")
         if not images.is_cuda or images.device != self.device:
             raise RuntimeError(f"native float step: images on {images.device}, parameters on {self.device}")
         images = images.to(torch.float32).contiguous()
-        form = self.fp16 if f16 else self.fp32
+        form = form or self.fp32
         c = self.cfg_for(images.shape[0])
         form.reserve(c, self.device)
         logits = torch.empty(c.batch, c.num_classes, dtype=form.dtype, device=self.device)
@@ -149,8 +173,8 @@ class FloatStudentEngine:
         form.call("forward", ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr())
         return logits
 
-    def backward(self, dlogits: torch.Tensor, batch: int, f16: bool = False) -> List[torch.Tensor]:
-        form = self.fp16 if f16 else self.fp32
+    def backward(self, dlogits: torch.Tensor, batch: int, form: Optional[Form] = None) -> List[torch.Tensor]:
+        form = form or self.fp32
         c = self.cfg_for(batch)
         dlogits = dlogits.to(form.dtype).contiguous()
         flat = torch.zeros(self.grad_numel, dtype=torch.float32, device=self.device)
@@ -163,12 +187,12 @@ class FloatStudentEngine:
         return views
 
 
-def _step_forward(ctx, images, engine, f16: bool):
+def _step_forward(ctx, images, engine, form: Form):
     ctx.engine = engine
-    out = engine.forward(images, f16)
+    out = engine.forward(images, form)
     ctx.generation = engine.generation
     ctx.batch = images.shape[0]
-    ctx.f16 = f16
+    ctx.form = form
     return out
 
 
@@ -182,21 +206,21 @@ def _step_backward(ctx, dlogits):
             "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
             "forward/backward per micro-batch)."
         )
-    grads = eng.backward(dlogits, ctx.batch, ctx.f16)
+    grads = eng.backward(dlogits, ctx.batch, ctx.form)
     for p, g in zip(eng.params, grads):
         if p.grad is None:
             p.grad = g
         else:
             p.grad.add_(g)
-    return (None, None) + (None,) * len(grads)
+    return (None, None, None) + (None,) * len(grads)
 
 
 class _FloatStudentStep(torch.autograd.Function):
     # cast_inputs=float32: inside torch.autocast("cuda") the step keeps its own (fp32-accurate) arithmetic and returns fp32 logits
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, images, engine, *params):
-        return _step_forward(ctx, images, engine, False)
+    def forward(ctx, images, engine, form, *params):
+        return _step_forward(ctx, images, engine, form)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -205,12 +229,12 @@ class _FloatStudentStep(torch.autograd.Function):
 
 
 class _FloatStudentAmpStep(torch.autograd.Function):
-    # the fp16 form (native_float(..., amp=True) inside fp16 autocast): fp16 logits as stock autocast's head Linear returns; ctx.f16 records
-    # the form for the backward
+    # the fp16 / bf16 form (native_float(..., amp=...) inside fp16 / bf16 autocast): fp16 / bf16 logits as stock autocast's head Linear returns;
+    # ctx.form records the form for the backward
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
-    def forward(ctx, images, engine, *params):
-        return _step_forward(ctx, images, engine, True)
+    def forward(ctx, images, engine, form, *params):
+        return _step_forward(ctx, images, engine, form)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -218,14 +242,15 @@ class _FloatStudentAmpStep(torch.autograd.Function):
         return _step_backward(ctx, dlogits)
 
 
-def native_float(wrapper: nn.Module, amp: bool = False) -> nn.Module:
+def native_float(wrapper: nn.Module, amp=False) -> nn.Module:
     """Opt an unprepared ``QATWrapper(vit_*_patch16_224)`` into the native float step; returns the wrapper.
 
     The parameters must already be on the GPU; the shape is checked here.  Afterwards ``wrapper(x)`` on a CUDA tensor runs the native
     forward (and its backward), a CPU tensor raises; ``prepare_qat`` of the wrapper is unaffected (a prepared wrapper takes the QAT engine).
     amp=True: a forward inside ``torch.autocast("cuda", dtype=torch.float16)`` runs the fp16 form (fp16 logits, stock autocast's numerics and
-    overflow behaviour, for GradScaler); outside autocast the fp32-accurate form; bf16 autocast raises.  Needs embed_dim and mlp_hidden
-    multiples of 384."""
+    overflow behaviour, for GradScaler); outside autocast the fp32-accurate form; bf16 autocast raises.  amp=torch.bfloat16: the same for
+    ``torch.autocast("cuda", dtype=torch.bfloat16)`` with the bf16 form (bf16 logits; no GradScaler needed); fp16 autocast raises.
+    amp=(torch.float16, torch.bfloat16): both, chosen per forward.  Any amp needs embed_dim and mlp_hidden multiples of 384."""
     from .model_registry import QATWrapper
 
     if not isinstance(wrapper, QATWrapper):
@@ -234,7 +259,7 @@ def native_float(wrapper: nn.Module, amp: bool = False) -> nn.Module:
         raise RuntimeError("native_float: the wrapper is already prepared for QAT (it runs the native QAT step)")
     if any(not p.is_cuda for p in wrapper.parameters()):
         raise RuntimeError("native_float: move the model to the GPU first (model.cuda()); the native float step runs on MI355X only")
-    _OPTED[wrapper] = FloatStudentEngine(wrapper, amp=bool(amp))
+    _OPTED[wrapper] = FloatStudentEngine(wrapper, amp=amp)
     return wrapper
 
 
@@ -251,9 +276,5 @@ def float_forward(wrapper, images: torch.Tensor) -> torch.Tensor:
     if eng is None or eng.stale():   # parameters re-allocated (e.g. .to()): the float step keeps no state, rebuild
         eng = _OPTED[wrapper] = FloatStudentEngine(wrapper, amp=eng.amp if eng is not None else False)
     if eng.amp and torch.is_autocast_enabled("cuda"):   # decided per forward
-        dt = torch.get_autocast_dtype("cuda")
-        if dt != torch.float16:
-            raise RuntimeError(f"native float step (amp=True): autocast dtype {dt} is not supported; the fp16 form follows "
-                               "torch.autocast('cuda', dtype=torch.float16) only")
-        return _FloatStudentAmpStep.apply(images, eng, *eng.params)
-    return _FloatStudentStep.apply(images, eng, *eng.params)
+        return _FloatStudentAmpStep.apply(images, eng, eng.autocast_form(torch.get_autocast_dtype("cuda")), *eng.params)
+    return _FloatStudentStep.apply(images, eng, eng.fp32, *eng.params)

@@ -77,6 +77,11 @@ SIGNATURES = {
     "qatvit_float_student_amp_forward": (c_int, [c_void_p] * 6),
     "qatvit_float_student_amp_backward": (c_int, [c_void_p] * 6),
     "qatvit_float_student_amp_attn_backward": (c_int, [c_void_p] * 4 + [c_int32] * 4 + [c_void_p] * 2),
+    "qatvit_float_student_bf16_workspace_bytes": (c_int64, [c_void_p]),
+    "qatvit_float_student_bf16_init": (c_int, [c_void_p] * 3),
+    "qatvit_float_student_bf16_forward": (c_int, [c_void_p] * 6),
+    "qatvit_float_student_bf16_backward": (c_int, [c_void_p] * 6),
+    "qatvit_float_student_bf16_attn_backward": (c_int, [c_void_p] * 4 + [c_int32] * 4 + [c_void_p] * 2),
     "qatvit_infer_workspace_bytes": (c_int64, [c_void_p]),
     "qatvit_infer_prepare": (c_int, [c_void_p] * 6),
     "qatvit_infer_forward": (c_int, [c_void_p] * 8),
