@@ -443,6 +443,29 @@ int qatvit_optim_adamw(const void* param_ptrs, const void* grad_ptrs, const void
                        int64_t chunk_elems, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                        const float* clip_out2, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Input pipeline: uint8 images resident on the device -> the normalised fp32 batch.
+ * Replaces: the per-image host transform of the loaders (qat_trainer.py:209-254, evaluator.py:22-41): Resize(D, BICUBIC) through Pillow,
+ *   ToTensor(), Normalize(mean, std), and the host-to-device copy of the fp32 batch.  The result is EQUAL to theirs, element for element.
+ *
+ * Arithmetic (Pillow's 8-bit resample, square source S <= D, so the bicubic filter keeps support 2.0): per axis and output position xx,
+ *   center = (xx + 0.5) * S / D, xmin = max(0, (int)(center - 1.5)), xmax = min(S, (int)(center + 2.5)), at most 4 taps
+ *   w_i = cubic(i + xmin - center + 0.5) (a = -0.5), divided by their sum, coef_i = (int)(w_i * 2^22 +- 0.5), all in double;
+ *   horizontal pass over the source rows, then vertical pass over its uint8 result, each clamp((2^21 + sum_i u8 * coef_i) >> 22, 0, 255) in int32;
+ *   out[b][c][y][x] = table[c][byte], table[c][v] = ((float)v / 255 - mean[c]) / std[c] with IEEE fp32 divisions.
+ *
+ * qatvit_image_resize_coeffs / qatvit_image_table run on the HOST and make no HIP call: xmin[D], ntaps[D], coef[D][4] (unused taps 0) and
+ *   table[3][256] are host arrays.  8 <= S <= D, D % 4 == 0, D <= 384.
+ * qatvit_image_batch: one launch.  data uint8 [N, S, S, 3] (HWC, contiguous); index int64 [B] or NULL (images 0 .. B-1; then B <= N) - an
+ *   index outside 0 .. N-1 is the caller's error (it reads image 0 or N-1, never outside data); coeffs int32 [6 * D] = the three arrays
+ *   of qatvit_image_resize_coeffs(S, D) one after the other (xmin, ntaps, coef), table fp32 [768], both on the device;
+ *   out fp32 [B, 3, D, D] contiguous, 16-byte aligned.  B <= 65535.
+ */
+int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
+int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
+int qatvit_image_batch(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                       const float* table, float* out, void* stream);
+
 /* Measurement hooks (bench.py): bracket every launch of one GEMM class inside the steps of ONE engine - identified by its workspace
  * pointer, so engines in the same process do not see each other's sessions - with HIP events on the launch stream.
  * kind: 1 = NT with split (hi+lo) A operand and the plain epilogue (proj / fc2 forward, proj dgrad), 2 = NT with grid A operand on int8 MFMA, plain

@@ -266,4 +266,35 @@ int qatvit_attn_backward(const float* qkv, const float* qp, int32_t qmin, int32_
     return 0;
 }
 
+static int image_shape_ok(const char* who, int32_t S, int32_t D) {
+    QV_CHECK_ARG(S >= 8 && S <= D, "%s: source size %d is outside 8 .. output size %d (downscaling is not supported)", who, S, D);
+    QV_CHECK_ARG(D % 4 == 0 && D <= kImgMaxD, "%s: output size %d must be a multiple of 4, at most %d", who, D, kImgMaxD);
+    return 0;
+}
+
+int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host) {
+    QV_CHECK_ARG(xmin_host && ntaps_host && coef_host, "qatvit_image_resize_coeffs: null pointer argument");
+    if (image_shape_ok("qatvit_image_resize_coeffs", src, dst)) return 1;
+    return image_resize_coeffs(src, dst, xmin_host, ntaps_host, coef_host);
+}
+
+int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host) {
+    QV_CHECK_ARG(mean_host && std_host && table_host, "qatvit_image_table: null pointer argument");
+    for (int c = 0; c < 3; ++c) QV_CHECK_ARG(std_host[c] != 0.0f, "qatvit_image_table: std[%d] is zero", c);
+    image_table(mean_host, std_host, table_host);
+    return 0;
+}
+
+int qatvit_image_batch(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                       const float* table, float* out, void* stream) {
+    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch: null pointer argument");
+    if (image_shape_ok("qatvit_image_batch", S, D)) return 1;
+    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
+    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch: batch %d of a data set of %d images needs an index", B, N);
+    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0, "qatvit_image_batch: misaligned pointer");
+    launch_image_batch(data, index, B, N, S, D, coeffs, table, out, (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_image_batch");
+    return 0;
+}
+
 }  // extern "C"

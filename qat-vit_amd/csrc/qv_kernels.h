@@ -293,6 +293,12 @@ int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, h
 int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16, int B, int T, int D, hipStream_t st, bool bf16 = false);
 // the overflow rule of the fp16 Linear / Conv2d gradients on count <= 100 fp32 tensors g[k] of n[k] elements: g -> fp16(g) where that is +-inf
 int launch_fa_inf_rule(float* const* g, const int64_t* n, int count, hipStream_t st);
+// image.hip: the input pipeline.  coeffs = int32 {xmin[D], ntaps[D], coef[D][kImgTaps]} and table = fp32 [3][256], both as the two host functions write them
+constexpr int kImgTaps = 4, kImgBits = 22, kImgBand = 16, kImgMaxD = 384;
+int image_resize_coeffs(int src, int dst, int32_t* xmin, int32_t* ntaps, int32_t* coef);   // host only; nonzero + set_error when the kernel's bounds do not hold
+void image_table(const float* mean, const float* stdv, float* table);                      // host only
+int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table, float* out,
+                       hipStream_t st);
 // grid of the float step's flat elementwise kernels (float_step.hip, float_amp.hip)
 inline int flat_grid_fs(int64_t n) {
     int64_t b = (n + 255) / 256;

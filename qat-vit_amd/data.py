@@ -1,0 +1,142 @@
+"""Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch).
+
+Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
+``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
+writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced, equal to it element for element.
+There is no CPU path: CPU tensors raise."""
+import os
+import pickle
+
+import numpy as np
+import torch
+from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
+
+from . import native
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+def resize_tables(src_size: int, out_size: int):
+    """int32 CPU tensors xmin [D], ntaps [D], coef [D, 4] of Pillow's 8-bit bicubic resample from src_size to out_size (host only, no GPU)."""
+    xmin, ntaps = torch.empty(out_size, dtype=torch.int32), torch.empty(out_size, dtype=torch.int32)
+    coef = torch.empty(out_size, 4, dtype=torch.int32)
+    native.check(native.lib().qatvit_image_resize_coeffs(int(src_size), int(out_size), xmin.data_ptr(), ntaps.data_ptr(), coef.data_ptr()),
+                 "qatvit_image_resize_coeffs")
+    return xmin, ntaps, coef
+
+
+def value_table(mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """fp32 CPU tensor [3, 256]: what ToTensor() + Normalize(mean, std) make of each byte value, per channel (host only, no GPU)."""
+    m, s = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+    if m.shape != (3,) or s.shape != (3,):
+        raise ValueError("mean and std must have three entries")
+    table = torch.empty(3, 256, dtype=torch.float32)
+    native.check(native.lib().qatvit_image_table(m.data_ptr(), s.data_ptr(), table.data_ptr()), "qatvit_image_table")
+    return table
+
+
+class GpuResizeNormalize:
+    """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch."""
+
+    def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
+        self.src_size, self.out_size = int(src_size), int(out_size)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GpuResizeNormalize runs on MI355X only: device must be a CUDA device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.coeffs = torch.cat([t.flatten() for t in resize_tables(self.src_size, self.out_size)]).to(self.device)
+        self.table = value_table(mean, std).to(self.device)
+
+    def __call__(self, data_u8, index=None, out=None):
+        S, D = self.src_size, self.out_size
+        if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
+            raise RuntimeError("GpuResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
+        if data_u8.dtype != torch.uint8:
+            raise TypeError(f"images must be uint8, got {data_u8.dtype}")
+        if data_u8.dim() != 4 or tuple(data_u8.shape[1:]) != (S, S, 3):
+            raise ValueError(f"images must be [N, {S}, {S}, 3] (HWC), got {tuple(data_u8.shape)}")
+        if not data_u8.is_contiguous() or data_u8.device != self.device:
+            raise ValueError(f"images must be contiguous and on {self.device}")
+        N = data_u8.shape[0]
+        if index is None:
+            B, ip = N, None
+        else:
+            if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != self.device:
+                raise ValueError(f"index must be a contiguous 1-D int64 tensor on {self.device}")
+            B, ip = index.shape[0], index.data_ptr()
+        if out is None:
+            out = torch.empty(B, 3, D, D, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, D, D) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous fp32 [{B}, 3, {D}, {D}] tensor on {self.device}")
+        if B:
+            with torch.cuda.device(self.device):
+                native.check(native.lib().qatvit_image_batch(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
+                                                             out.data_ptr(), native.stream_ptr()), "qatvit_image_batch")
+        return out
+
+
+def epoch_batches(n, batch_size, shuffle=False, sampler=None, drop_last=False, generator=None):
+    """The plan of one epoch, on the host: a list of 1-D int64 CPU tensors, batch by batch, with DataLoader's meaning of every argument (its own
+    sampler classes draw the order; shuffle is RandomSampler's permutation from `generator`).  `sampler` is any iterable of indices."""
+    if sampler is not None and shuffle:
+        raise ValueError("sampler option is mutually exclusive with shuffle")
+    if sampler is None:
+        sampler = RandomSampler(range(n), generator=generator) if shuffle else SequentialSampler(range(n))
+    return [torch.tensor(b, dtype=torch.int64) for b in BatchSampler(sampler, batch_size, drop_last)]
+
+
+class GpuImageLoader:
+    """Iterates ``(images, labels)`` device batches of a uint8 data set that lives on the device; stands where a ``DataLoader`` over the
+    transformed data set stood.  An epoch's indices go to the device once; drawing a batch is one gather of labels and one launch, with no host
+    synchronisation, and every batch is a fresh tensor."""
+
+    def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda"):
+        if sampler is not None and shuffle:
+            raise ValueError("sampler option is mutually exclusive with shuffle")
+        data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
+        if data_u8.dtype != torch.uint8 or data_u8.dim() != 4 or data_u8.shape[1] != data_u8.shape[2] or data_u8.shape[3] != 3:
+            raise ValueError(f"images must be uint8 [N, S, S, 3] (HWC), got {data_u8.dtype} {tuple(data_u8.shape)}")
+        if labels.dim() != 1 or labels.shape[0] != data_u8.shape[0]:
+            raise ValueError("labels must be one integer per image")
+        self.transform = transform if transform is not None else GpuResizeNormalize(data_u8.shape[1], device=device)
+        self.device = self.transform.device
+        self.data = data_u8.to(self.device).contiguous()
+        self.labels = labels.to(self.device, torch.int64).contiguous()
+        self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator = int(batch_size), shuffle, sampler, drop_last, generator
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
+        if not plan:
+            return
+        flat = torch.cat(plan)
+        # from pinned memory the copy is asynchronous (the caching host allocator keeps the block until the copy has run)
+        order = torch.empty(flat.shape, dtype=torch.int64, pin_memory=True).copy_(flat).to(self.device, non_blocking=True)
+        o = 0
+        for b in plan:
+            idx = order[o:o + b.shape[0]]
+            o += b.shape[0]
+            yield self.transform(self.data, idx), self.labels.index_select(0, idx)
+
+
+def cifar10_arrays(root, train=True):
+    """(uint8 [N, 32, 32, 3], int64 [N]) of the ``cifar-10-batches-py`` directory under `root`, as torchvision's ``CIFAR10(root, train).data`` /
+    ``.targets`` hold them.  Never downloads: FileNotFoundError if the directory or one of its batch files is missing."""
+    base = os.path.join(root, "cifar-10-batches-py")
+    names = [f"data_batch_{i}" for i in range(1, 6)] if train else ["test_batch"]
+    data, labels = [], []
+    for name in names:
+        path = os.path.join(base, name)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path} is missing: put the extracted CIFAR-10 python archive under {root} (nothing is downloaded)")
+        with open(path, "rb") as f:
+            entry = pickle.load(f, encoding="latin1")
+        data.append(np.asarray(entry["data"], dtype=np.uint8))
+        labels.extend(entry["labels"] if "labels" in entry else entry["fine_labels"])
+    data = np.vstack(data).reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
+    return np.ascontiguousarray(data), np.asarray(labels, dtype=np.int64)
