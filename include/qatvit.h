@@ -88,6 +88,16 @@ int qatvit_kd_ce_loss(const float* student, const float* teacher, const int64_t*
                       int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
                       float label_smoothing, float* out3, float* dlogits, void* stream);
 
+/* The same loss, statement for statement, with the teacher row of sample b read from a table of
+ * per-sample teacher logits: teacher[b] = table[index[b]].
+ *  table [table_rows, C] fp32; index int64 [B].  An index outside [0, table_rows) reads nothing:
+ *  out3 and that row of dlogits become NaN (no fault, no host synchronisation).
+ */
+int qatvit_kd_ce_loss_table(const float* student, const float* table, int64_t table_rows,
+                            const int64_t* index, const int64_t* labels, int64_t batch,
+                            int64_t classes, float kd_temp, float kd_alpha, float label_smoothing,
+                            float* out3, float* dlogits, void* stream);
+
 /* ===========================================================================
  * Building blocks of the step, exported for kernel-level parity tests.
  * All matrices row-major; "bf16" = IEEE bfloat16 bit patterns (uint16).

@@ -95,6 +95,20 @@ int qatvit_kd_ce_loss(const float* student, const float* teacher, const int64_t*
     return 0;
 }
 
+int qatvit_kd_ce_loss_table(const float* student, const float* table, int64_t table_rows, const int64_t* index, const int64_t* labels,
+                            int64_t batch, int64_t classes, float kd_temp, float kd_alpha, float label_smoothing, float* out3, float* dlogits,
+                            void* stream) {
+    QV_CHECK_ARG(student && table && index && labels && out3 && dlogits, "qatvit_kd_ce_loss_table: null pointer argument");
+    QV_CHECK_ARG(batch >= 1 && classes >= 2 && classes <= 4096, "qatvit_kd_ce_loss_table: bad shape B=%lld C=%lld", (long long)batch,
+                 (long long)classes);
+    QV_CHECK_ARG(table_rows >= 1, "qatvit_kd_ce_loss_table: table_rows %lld (at least 1)", (long long)table_rows);
+    QV_CHECK_ARG(kd_temp > 0.f, "qatvit_kd_ce_loss_table: kd_temp must be > 0");
+    launch_kd_ce_loss_table(student, table, table_rows, index, labels, batch, classes, kd_temp, kd_alpha, label_smoothing, out3, dlogits,
+                            (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_kd_ce_loss_table");
+    return 0;
+}
+
 int qatvit_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                    int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, void* stream) {
     QV_CHECK_ARG(A_hi && B && C, "qatvit_gemm_nt: null pointer argument");

@@ -46,6 +46,7 @@ class GpuResizeNormalize:
             raise RuntimeError("GpuResizeNormalize runs on MI355X only: device must be a CUDA device")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self.coeffs = torch.cat([t.flatten() for t in resize_tables(self.src_size, self.out_size)]).to(self.device)
         self.table = value_table(mean, std).to(self.device)
 
@@ -90,9 +91,11 @@ def epoch_batches(n, batch_size, shuffle=False, sampler=None, drop_last=False, g
 class GpuImageLoader:
     """Iterates ``(images, labels)`` device batches of a uint8 data set that lives on the device; stands where a ``DataLoader`` over the
     transformed data set stood.  An epoch's indices go to the device once; drawing a batch is one gather of labels and one launch, with no host
-    synchronisation, and every batch is a fresh tensor."""
+    synchronisation, and every batch is a fresh tensor.  ``return_index=True`` yields ``(images, labels, index)``: ``index`` is the batch's slice of
+    the epoch plan on the device (int64), the row numbers a per-sample table such as ``TeacherLogitTable`` is read with."""
 
-    def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda"):
+    def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
+                 return_index=False):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -105,6 +108,7 @@ class GpuImageLoader:
         self.data = data_u8.to(self.device).contiguous()
         self.labels = labels.to(self.device, torch.int64).contiguous()
         self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator = int(batch_size), shuffle, sampler, drop_last, generator
+        self.return_index = bool(return_index)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -121,7 +125,10 @@ class GpuImageLoader:
         for b in plan:
             idx = order[o:o + b.shape[0]]
             o += b.shape[0]
-            yield self.transform(self.data, idx), self.labels.index_select(0, idx)
+            if self.return_index:
+                yield self.transform(self.data, idx), self.labels.index_select(0, idx), idx
+            else:
+                yield self.transform(self.data, idx), self.labels.index_select(0, idx)
 
 
 def cifar10_arrays(root, train=True):

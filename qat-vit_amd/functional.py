@@ -156,3 +156,42 @@ def kd_ce_loss(student, teacher, labels, kd_temp=4.0, kd_alpha=0.5, label_smooth
     """Returns (loss, [loss, ce, kd*T^2]).  ``teacher=None`` -> CE only
     (the reference's step at /root/reference/src/training/qat_trainer.py:343-349)."""
     return _KDCELossFn.apply(student, teacher, labels, kd_temp, kd_alpha, label_smoothing)
+
+
+class _KDCELossTableFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, student, table, index, labels, kd_temp, kd_alpha, label_smoothing):
+        _need_cuda(student, "kd_ce_loss_table")
+        _need_cuda(table, "kd_ce_loss_table")
+        student = student.contiguous()
+        B, C = student.shape
+        if table.dim() != 2 or table.shape[1] != C or table.shape[0] < 1 or not table.is_contiguous() or table.device != student.device:
+            raise RuntimeError(f"kd_ce_loss_table: the table must be a contiguous [rows, {C}] tensor on {student.device}, got {tuple(table.shape)} on {table.device}")
+        index, labels = index.contiguous(), labels.contiguous()
+        if index.dtype != torch.int64 or labels.dtype != torch.int64:
+            raise RuntimeError("kd_ce_loss_table: index and labels must be int64")
+        if index.shape != (B,) or labels.shape != (B,) or index.device != student.device or labels.device != student.device:
+            raise RuntimeError(f"kd_ce_loss_table: index and labels must be [{B}] tensors on {student.device}")
+        out3 = torch.empty(3, dtype=torch.float32, device=student.device)
+        dlogits = torch.empty_like(student)
+        native.check(
+            native.lib().qatvit_kd_ce_loss_table(student.data_ptr(), table.data_ptr(), table.shape[0], index.data_ptr(), labels.data_ptr(), B, C,
+                                                 float(kd_temp), float(kd_alpha), float(label_smoothing), out3.data_ptr(), dlogits.data_ptr(),
+                                                 native.stream_ptr()),
+            "qatvit_kd_ce_loss_table",
+        )
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(out3)
+        return out3[0], out3
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * dloss, None, None, None, None, None, None
+
+
+def kd_ce_loss_table(student, table, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+    """``kd_ce_loss(student, table[index], labels, ...)`` in one launch, without the gathered tensor: returns (loss, [loss, ce, kd*T^2]).
+    ``table`` is fp32 ``[rows, C]`` (per-sample teacher logits, distill.TeacherLogitTable), ``index`` int64 ``[B]``.  An index outside the table
+    makes the loss and that row of the gradient NaN; it is not an error on the host (nothing here synchronises)."""
+    return _KDCELossTableFn.apply(student, table, index, labels, kd_temp, kd_alpha, label_smoothing)

@@ -41,16 +41,7 @@ class TeacherEngine:
         self.cfg = native.Cfg(batch=batch, act_qmin=0, act_qmax=255, w_qmin=-128, w_qmax=127, w_per_channel=0, averaging_const=0.01,
                               **native.vit_shape(model))
         self.weights = [pe.weight] + [w for b in blocks for w in (b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight)]
-        self.passes = int(os.environ.get("QATVIT_TEACHER_PASSES", str(DEFAULT_PASSES)))
-        if self.passes not in (1, 2, 3):
-            raise RuntimeError(f"QATVIT_TEACHER_PASSES={self.passes}: 1, 2 or 3")
-        if self.passes < 3 and (model.embed_dim % 384 or blocks[0].mlp.fc1.weight.shape[0] % 384):
-            self.passes = 3   # the fp16 forms run on the tall 208 x 384 tile only
-        if self.passes < 3 and not self._fp16_range_ok(model, blocks):
-            import warnings
-            warnings.warn("qat-vit_amd: a teacher activation could leave fp16's range with these weights (bound from the LayerNorm / Linear parameters); "
-                          "the frozen teacher runs in the three-pass bf16-pair form instead of the fp16 form", RuntimeWarning)
-            self.passes = 3
+        self.passes = self.resolve_passes(model)
         self._split_weights()
         nbytes = self.lib.qatvit_teacher_workspace_bytes(ctypes.byref(self.cfg))
         if nbytes <= 0:
@@ -58,6 +49,23 @@ class TeacherEngine:
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._ptr_params = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
         self._key = tuple(p.data_ptr() for p in ps)
+
+    @classmethod
+    def resolve_passes(cls, model, warn: bool = True) -> int:
+        """The arithmetic form an engine built now for `model` runs in: ``QATVIT_TEACHER_PASSES`` after the engine's own fall-backs."""
+        blocks = list(model.blocks)
+        passes = int(os.environ.get("QATVIT_TEACHER_PASSES", str(DEFAULT_PASSES)))
+        if passes not in (1, 2, 3):
+            raise RuntimeError(f"QATVIT_TEACHER_PASSES={passes}: 1, 2 or 3")
+        if passes < 3 and (model.embed_dim % 384 or blocks[0].mlp.fc1.weight.shape[0] % 384):
+            passes = 3   # the fp16 forms run on the tall 208 x 384 tile only
+        if passes < 3 and not cls._fp16_range_ok(model, blocks):
+            if warn:
+                import warnings
+                warnings.warn("qat-vit_amd: a teacher activation could leave fp16's range with these weights (bound from the LayerNorm / Linear parameters); "
+                              "the frozen teacher runs in the three-pass bf16-pair form instead of the fp16 form", RuntimeWarning)
+            passes = 3
+        return passes
 
     @staticmethod
     @torch.no_grad()
@@ -99,14 +107,20 @@ class TeacherEngine:
         self._ptr_hi = (ctypes.c_void_p * len(self.w_hi))(*[t.data_ptr() for t in self.w_hi])
         self._ptr_lo = (ctypes.c_void_p * len(self.w_lo))(*[t.data_ptr() for t in self.w_lo])
 
-    def forward(self, images: torch.Tensor) -> torch.Tensor:
+    def forward(self, images: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """Logits of `images`; `out` (contiguous fp32 [batch, num_classes] on the engine's device, e.g. rows of a logit table) receives them in place."""
         c = self.cfg
         if images.shape != (c.batch, c.in_chans, c.img_size, c.img_size) or images.dtype != torch.float32:
             raise RuntimeError(f"expected fp32 images {(c.batch, c.in_chans, c.img_size, c.img_size)}, got {tuple(images.shape)} {images.dtype}")
         if tuple((w.data_ptr(), w._version) for w in self.weights) != self._versions:
             self._split_weights()  # a checkpoint was loaded into the teacher after the first call
         images = images.contiguous()
-        logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
+        if out is None:
+            logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
+        else:
+            if out.shape != (c.batch, c.num_classes) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+                raise RuntimeError(f"out must be a contiguous fp32 {(c.batch, c.num_classes)} tensor on {self.device}")
+            logits = out
         if self.passes == 3:
             native.check(self.lib.qatvit_teacher_forward(ctypes.byref(c), self._ptr_params, self._ptr_hi, self._ptr_lo, images.data_ptr(),
                                                          logits.data_ptr(), self.workspace.data_ptr(), native.stream_ptr()), "qatvit_teacher_forward")
@@ -121,9 +135,9 @@ class TeacherEngine:
 _ENGINES = weakref.WeakKeyDictionary()
 
 
-def teacher_forward(model, images):
+def teacher_forward(model, images, out=None):
     eng = _ENGINES.get(model)
     if eng is None or eng.cfg.batch != images.shape[0] or eng.device != images.device or tuple(p.data_ptr() for p in eng.params) != eng._key:
         eng = TeacherEngine(model, images.shape[0])
         _ENGINES[model] = eng
-    return eng.forward(images)
+    return eng.forward(images, out)
