@@ -150,6 +150,21 @@ int qatvit_i8_strip(int32_t mode, const void* A8, const void* B8f, const int32_t
                     int32_t qmin, int32_t qmax, void* out8, void* out8_mask, int32_t code_T, uint32_t* lut_out, uint32_t* lutq_out,
                     float* out16_scale, void* stream);
 
+/* The LayerNorm apply + fake-quant of norm1 / norm2 as the launch of its own the training forward runs where qatvit_i8_strip_ln does not apply (byte plane only):
+ * out8[m,d] = clamp(rint(y / scale) + zero_point, qmin, qmax) - center as int8, y = ((x[m,d] - mean[m]) * rstd[m]) * gamma[d] + beta[d], qp = {scale, 1/scale,
+ * zero_point, enabled}.  x, out8 [M,D] dense; D % 4 == 0. */
+int qatvit_ln_apply_quant8(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp, int32_t qmin, int32_t qmax,
+                           void* out8, int32_t center, int64_t M, int32_t D, void* stream);
+
+/* The statistics pass (mode 3) of qatvit_i8_strip with the LayerNorm in front of it (nn.LayerNorm + the activation_post_process fake-quant of norm1 / norm2) in its
+ * prologue: every workgroup quantises its own rows - out8[m,k] = clamp(rint(y / scale) + zero_point) - center with y = ((x[m,k] - mean[m]) * rstd[m]) * gamma[k] + beta[k],
+ * a_qp = {scale, 1/scale, zero_point, enabled} of that quantizer - keeps them in LDS as its A strip and stores them to out8 [M,lda] (int8), the A8 of the code pass.
+ * *s1 of qatvit_i8_strip is a_qp[0].  The plane and the statistics are bit-identical to the LayerNorm-apply kernel followed by qatvit_i8_strip(mode 3).
+ * x [M,K] fp32, K = 384: N = 1152 or 1536; K = 768: N = 2304 or 3072; lda % 16 == 0, lda >= K; M < 2^22. */
+int qatvit_i8_strip_ln(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int32_t ln_qmin, int32_t ln_qmax, void* out8,
+                       const void* B8f, const int32_t* wsum, const float* a_qp, int32_t center, int32_t M, int32_t N, int32_t K, int32_t lda, const float* s2,
+                       const float* col_scale, const float* bias, uint32_t* stats, void* stream);
+
 /* qatvit_gemm_nt_f16 for an A operand that takes at most 256 distinct values (mlp.fc2: A = gelu(fq(fc1 output))): A8 uint8 [M,lda] = table
  * index per element (lda in bytes), lut[256] = the fp16 (hi | lo << 16) pair per index.  The kernel expands the codes through the table on their
  * way into LDS: bit-identical to qatvit_gemm_nt_f16 on the expanded planes, 1 B instead of 4 B of HBM traffic per A element.
@@ -309,6 +324,9 @@ int qatvit_student_backward(const qatvit_cfg* cfg, void* const* params, const qa
 #define QATVIT_BWD_DY16 2       /* backward: the one-plane form (the forward ran with QATVIT_FWD_X16, the workspace is calibrated) */
 #define QATVIT_BWD_CALIBRATE 4  /* backward: the pair form, recording the maxima the next one-plane backward scales by (the forward ran WITHOUT QATVIT_FWD_X16) */
 int32_t qatvit_student_dy16_supported(const qatvit_cfg* cfg);
+/* Which LayerNorms of a forward with `flags` run inside the statistics pass that follows them (qatvit_i8_strip_ln) instead of as a launch of their own:
+ * bit 0 = norm1 (attn.qkv), bit 1 = norm2 (mlp.fc1), of every block.  QATVIT_LN_STRIP=0 in the environment: 0. */
+int32_t qatvit_student_ln_in_strip(const qatvit_cfg* cfg, int32_t flags);
 /* h1q / h2q of every block from fp16 integers back to bf16 integers, in place (fallback after an overflow: the pair form reads bf16) */
 /* Host mirror of the one-plane backward's overflow flag: host_pinned = int32[2] in pinned host memory (hipHostMalloc / torch pin_memory), NULL to remove it.  Every
  * backward call then writes {overflow flag, generation} there - the generation (a counter that changes with every call) after the flag, system scope - as soon as the

@@ -24,7 +24,7 @@ static bool knob(const char* name) {
 const Knobs& knobs() {
     static const Knobs k{knob("QATVIT_I8"), knob("QATVIT_F16"), knob("QATVIT_FC2_CODES"), knob("QATVIT_FC1_BITS"), knob("QATVIT_FC2W_CODES"),
                          knob("QATVIT_WBATCH"), knob("QATVIT_ATTN_CODES"), knob("QATVIT_QKV_2PASS"), knob("QATVIT_LNB_FUSE"), knob("QATVIT_QP_LATE"),
-                         knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP")};
+                         knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP"), knob("QATVIT_LN_STRIP")};
     return k;
 }
 }  // namespace qv
@@ -159,6 +159,29 @@ int qatvit_i8_strip(int32_t mode, const void* A8, const void* B8f, const int32_t
         return 1;
     }
     QV_CHECK_LAUNCH("qatvit_i8_strip");
+    return 0;
+}
+
+int qatvit_ln_apply_quant8(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp, int32_t qmin, int32_t qmax,
+                           void* out8, int32_t center, int64_t M, int32_t D, void* stream) {
+    QV_CHECK_ARG(x && mean && rstd && gamma && beta && qp && out8, "qatvit_ln_apply_quant8: null pointer argument");
+    QV_CHECK_ARG(M >= 1 && D >= 4 && D % 4 == 0, "qatvit_ln_apply_quant8: M=%lld D=%d (D %% 4 == 0)", (long long)M, D);
+    if (launch_ln_apply_quant(x, mean, rstd, gamma, beta, qp, qmin, qmax, nullptr, M, D, (hipStream_t)stream, out8, center)) return 1;
+    QV_CHECK_LAUNCH("qatvit_ln_apply_quant8");
+    return 0;
+}
+
+int qatvit_i8_strip_ln(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int32_t ln_qmin, int32_t ln_qmax, void* out8,
+                       const void* B8f, const int32_t* wsum, const float* a_qp, int32_t center, int32_t M, int32_t N, int32_t K, int32_t lda, const float* s2,
+                       const float* col_scale, const float* bias, uint32_t* stats, void* stream) {
+    QV_CHECK_ARG(x && mean && rstd && gamma && beta && out8 && B8f && wsum && a_qp && stats, "qatvit_i8_strip_ln: null pointer argument");
+    if (!launch_i8_strip_ln(x, mean, rstd, gamma, beta, ln_qmin, ln_qmax, out8, B8f, wsum, a_qp, center, M, N, K, lda, s2, col_scale, bias, stats, 1,
+                            (hipStream_t)stream, true)) {
+        set_error("qatvit_i8_strip_ln: unsupported arguments (M=%d N=%d K=%d lda=%d: need K = 384 with N = 1152 or 1536, or K = 768 with N = 2304 or 3072; "
+                  "lda %% 16 == 0, lda >= K, 0 < M < 2^22)", M, N, K, lda);
+        return 1;
+    }
+    QV_CHECK_LAUNCH("qatvit_i8_strip_ln");
     return 0;
 }
 

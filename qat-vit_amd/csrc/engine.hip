@@ -82,6 +82,7 @@ struct Forms {
     bool x_plane_from_q8;    // the one-plane qkv / fc1 weight gradients read the int8 plane of the LayerNorm outputs (q - center) instead of the fp16 one
     bool tn_stream;          // the per-block gradient planes + stream-K scratch exist (the one-plane weight gradients then run at the end of the call)
     bool dy16;               // the one-plane backward covers this configuration
+    bool ln_in_strip;        // norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln) where the forward writes the byte plane only (ln_in_strip_of)
 };
 static Forms forms_of(const qatvit_cfg& c, const Dims& d) {
     const Knobs& k = knobs();
@@ -102,6 +103,7 @@ static Forms forms_of(const qatvit_cfg& c, const Dims& d) {
     f.x_plane_from_q8 = f.i8 && k.tn_q8 && d.D % 384 == 0;
     f.tn_stream = k.tn_stream && d.D % 384 == 0 && d.Hd % 384 == 0;
     f.dy16 = f.i8 && f.w_batched && d.D % 384 == 0 && d.Hd % 384 == 0 && f.qkv_2pass && f.attn_bwd_fused && f.f16_proj && f.fc2w_codes;
+    f.ln_in_strip = k.ln_strip && f.i8 && f.late && f.x_plane_from_q8;
     return f;
 }
 
@@ -224,6 +226,18 @@ static int make_plan(const qatvit_cfg& c, Plan* p) {
     return 0;
 }
 
+// Does the statistics pass of layer `kind` (WB_QKV / WB_FC1) build its own strip from the fp32 rows (the LayerNorm in front of it then launches nothing)?  Only where
+// the forward writes no 2-byte plane of the LayerNorm output (QATVIT_FWD_X16 with the byte-X weight gradients), the quantizer is resolved late, and the
+// strip kernel takes the statistics pass with one workgroup per strip; qkv only in its two-pass form.  All blocks share the answer.
+static bool ln_in_strip_of(const Plan& p, const Dims& d, int flags, int kind) {
+    const Forms& F = p.form;
+    if (!F.ln_in_strip || !(flags & QATVIT_FWD_X16) || (kind == WB_QKV && !F.qkv_2pass) || d.depth < 1) return false;
+    const int wi = 1 + kind;
+    int N, K; wshape(d, wi, &N, &K);
+    if (!(F.w_batched && p.w8f_off[wi] >= 0) || K != d.D) return false;
+    return i8_strip_ln_covers(&p /* (any non-null pointer: the weight in fragment order exists) */, (int)d.M, N, K, K);
+}
+
 static int check_cfg(const qatvit_cfg& c) {
     if (c.batch < 1 || c.depth < 1 || c.embed_dim % 128 != 0 || c.mlp_hidden % 128 != 0 || c.embed_dim % c.num_heads != 0 ||
         c.img_size % c.patch_size != 0 || (c.in_chans * c.patch_size * c.patch_size) % 128 != 0 || c.embed_dim > 768) {
@@ -309,7 +323,7 @@ struct Ctx {
     int a_head() const { return a_norm() + 1; }
     int widx(int blk_i, int k) const { return 1 + WB_COUNT * blk_i + k; }
     // ---- late qparams (qv_kernels.h QpLate, Forms::late): the quantizers whose consumer kernel resolves the observer / qparams update itself - the
-    // LayerNorm outputs (k_ln_apply_quant), the proj / fc2 outputs (k_resid_fq_lnstats) of every block always, the qkv / fc1 outputs where the strip
+    // LayerNorm outputs (k_ln_apply_quant, or the statistics pass that has the LayerNorm in its prologue: ln_in_strip_of), the proj / fc2 outputs (k_resid_fq_lnstats) of every block always, the qkv / fc1 outputs where the strip
     // kernel's code pass is their consumer (decided by the caller: late_strip) - need no k_qparams launch behind the producer of their statistics
     bool late_kind(int ai) const {
         if (!p.form.late || ai < A_BLOCK0 || ai >= A_BLOCK0 + AB_COUNT * d.depth) return false;
@@ -353,6 +367,25 @@ struct Ctx {
         const bool x16 = (flags & QATVIT_FWD_X16) != 0;
         return launch_ln_apply_quant(xrow, mean, rstd, gamma, beta, act_qp(ai), c.act_qmin, c.act_qmax, x16 && p.form.x_plane_from_q8 ? nullptr : out16, d.M, d.D,
                                      st, p.form.i8 ? out8 : nullptr, center(), x16, lt ? &L : nullptr);
+    }
+    // the same LayerNorm as the prologue of the statistics pass of layer wi (ln_in_strip_of): the pass builds the int8 plane out8 and reads it from its own LDS
+    struct LnRows { const float* x; const float* mean; const float* rstd; const float* gamma; const float* beta; int ai; };
+    bool ln_in_strip(int kind) const { return ln_in_strip_of(p, d, flags, kind); }
+    int linear_stats_ln(const LnRows& r, void* out8, int M, int wi, const float* bias, int ai_out, bool late_strip) const {
+        int N, K; wshape(d, wi, &N, &K);
+        const qatvit_fq& f = wfq[wi];
+        {
+            ProfScope ps(prof, 7, 0.0, st);
+            const QpLate L = late(r.ai);
+            if (!late_kind(r.ai) ||
+                !launch_i8_strip_ln(r.x, r.mean, r.rstd, r.gamma, r.beta, c.act_qmin, c.act_qmax, out8, w8f(wi), at<int32_t>(p.wsum_off[wi]), act_qp(r.ai), center(), M, N, K, K,
+                                    c.w_per_channel ? nullptr : f.scale, c.w_per_channel ? f.scale : nullptr, bias, act_stats(ai_out), kStatSlots, st, false, &L)) {
+                set_error("engine: the statistics pass with the LayerNorm prologue does not cover layer %d (M=%d N=%d K=%d)", wi, M, N, K);
+                return 1;
+            }
+        }
+        qparams_after(ai_out, true, late_strip);
+        return 0;
     }
     void qparams_act(int ai) const {
         const qatvit_fq& f = act[ai];
@@ -474,16 +507,21 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
         float* xin = x.blk<float>(p.x_in, i);
         float* xmid = x.blk<float>(p.x_mid, i);
         if (parts & 1) {   // ---- part 0: norm1 -> qkv   (every quantizer's observer / qparams update runs behind the producer of its statistics)
-        x.ln_apply(xin, x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.aidx(i, AB_N1), x.blk<void>(p.h1q, i),
-                   x.blk<void>(p.h1q8, i));
+        const bool ln1 = x.ln_in_strip(WB_QKV);   // norm1's apply + quantise runs inside qkv's statistics pass
+        if (!ln1)
+            x.ln_apply(xin, x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.aidx(i, AB_N1), x.blk<void>(p.h1q, i),
+                       x.blk<void>(p.h1q8, i));
         if (F.qkv_2pass) {
             NTPost p2{};
             p2.mode = 7; p2.qp = x.act_qp(x.aidx(i, AB_QKV)); p2.qmin = qa; p2.qmax = qb;
             p2.out8 = x.blk<void>(p.qkv8, i); p2.out8_mask = x.blk<void>(p.qkvm, i); p2.code_T = (int)d.T; p2.code_hd = (int)(d.D / d.H);
             const bool lt = x.late_in_strip(M, x.widx(i, WB_QKV), &p2);   // the code pass resolves the qkv quantizer's qparams itself: no k_qparams launch between the passes
             const NTPost p1{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 3, nullptr};
-            if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(x.aidx(i, AB_N1)), x.bprm(i, B_QKVB), nullptr,
-                                  x.aidx(i, AB_QKV), &p1, true, lt))
+            if (ln1) {
+                const Ctx::LnRows r{xin, x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.aidx(i, AB_N1)};
+                if (x.linear_stats_ln(r, x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.bprm(i, B_QKVB), x.aidx(i, AB_QKV), lt)) return 1;
+            } else if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(x.aidx(i, AB_N1)), x.bprm(i, B_QKVB), nullptr,
+                                         x.aidx(i, AB_QKV), &p1, true, lt))
                 return 1;
             if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(x.aidx(i, AB_N1)), x.bprm(i, B_QKVB), nullptr,
                                   x.aidx(i, AB_QKV), &p2, false, lt))
@@ -512,8 +550,10 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
             return 1;
         }
         if (parts & 4) {   // ---- part 2: norm2 -> fc1 (both passes) -> GELU
-        x.ln_apply(xmid, x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.aidx(i, AB_N2), x.blk<void>(p.h2q, i),
-                   x.blk<void>(p.h2q8, i));
+        const bool ln2 = x.ln_in_strip(WB_FC1);   // norm2's apply + quantise runs inside fc1's statistics pass
+        if (!ln2)
+            x.ln_apply(xmid, x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.aidx(i, AB_N2), x.blk<void>(p.h2q, i),
+                       x.blk<void>(p.h2q8, i));
         {
             // fc1 is a K = D GEMM whose [M, 4D] fp32 output would be written once and read twice: run it TWICE instead.  Pass 1 only
             // feeds the observer (min/max, nothing stored); pass 2 - the same kernel on the same operands, so the same bits - quantises
@@ -527,8 +567,11 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
             else if (F.f16_fc2) { p2.out16_hi = x.at<void>(p.G16_hi); p2.out16_lo = x.at<void>(p.G16_lo); p2.out16_scale = scal16 + 1; }
             const bool lt = x.late_in_strip(M, x.widx(i, WB_FC1), &p2);   // (as for qkv: the code pass resolves the fc1 quantizer's qparams)
             const NTPost p1{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 3, nullptr};
-            if (x.linear_fwd_grid(x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.act_qp(x.aidx(i, AB_N2)), x.bprm(i, B_FC1B), nullptr,
-                             x.aidx(i, AB_FC1), &p1, true, lt))
+            if (ln2) {
+                const Ctx::LnRows r{xmid, x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.aidx(i, AB_N2)};
+                if (x.linear_stats_ln(r, x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.bprm(i, B_FC1B), x.aidx(i, AB_FC1), lt)) return 1;
+            } else if (x.linear_fwd_grid(x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.act_qp(x.aidx(i, AB_N2)), x.bprm(i, B_FC1B), nullptr,
+                                         x.aidx(i, AB_FC1), &p1, true, lt))
                 return 1;
             if (x.linear_fwd_grid(x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.act_qp(x.aidx(i, AB_N2)), x.bprm(i, B_FC1B), nullptr,
                              x.aidx(i, AB_FC1), &p2, false, lt))
@@ -1066,6 +1109,14 @@ int qatvit_student_backward_stages(const qatvit_cfg* cfg, void* const* params, c
                                    const float* dlogits, void* const* grads, void* workspace, int32_t stage_from, int32_t stage_to, int32_t flags,
                                    void* stream) {
     return run_backward(cfg, params, act_fq, weight_fq, dlogits, grads, workspace, stage_from, stage_to, flags, stream, "qatvit_student_backward_stages");
+}
+
+int32_t qatvit_student_ln_in_strip(const qatvit_cfg* cfg, int32_t flags) {
+    if (!cfg || check_cfg(*cfg)) return 0;
+    Plan p;
+    if (make_plan(*cfg, &p)) return 0;
+    const Dims d = dims_of(*cfg);
+    return (ln_in_strip_of(p, d, flags, WB_QKV) ? 1 : 0) | (ln_in_strip_of(p, d, flags, WB_FC1) ? 2 : 0);
 }
 
 int32_t qatvit_student_dy16_supported(const qatvit_cfg* cfg) {

@@ -25,6 +25,9 @@
 //     wave's MFMAs run under the other's quantise / store phase;
 //   * statistics pass: min / max over the 13 row fragments in the INTEGER domain (the affine map to the stored value is monotone per
 //     column: ca > 0), the float map once per column - 2 instead of 12 VALU instructions per element, the same bits.
+//   * LN form of the statistics pass (template parameter LN, launch_i8_strip_ln): the strip does not come from the int8 plane but from the fp32 rows of the
+//     residual stream - the workgroup applies the LayerNorm and quantises its own 208 rows (k_ln_apply_quant's arithmetic, elt.hip), writes the codes into the
+//     LDS image and to the plane for the code pass; the LayerNorm in front of qkv / fc1 then is no launch of its own (tests/test_gpu_ln_strip.py: the same bits).
 // Every arithmetic step on an element is the one the general tall kernel (gemm.hip, k_gemm_nt<.., I8>) performs, in the same order:
 // tests/test_gpu_knobs.py compares the two (QATVIT_I8_STRIP=0) bit for bit.
 #include <stdlib.h>
@@ -66,6 +69,16 @@ struct I8StripArgs {
     float* out16_scale;
     unsigned long long* dbg;   // experiments only: s_memtime stamps of workgroups 0 and 100 ([2][8 waves][32])
     QpLate late;               // code passes: late.stats set -> the output quantizer's qparams are resolved in the prologue (qv_qparams.h) instead of read from qp
+    // LN form of the statistics pass (k_i8_strip<3, .., LN = true>): the workgroup builds its strip itself from the fp32 residual rows - the work of
+    // k_ln_apply_quant (elt.hip), operation for operation - and stores the codes to the plane A for the code pass and the weight gradients
+    const float* ln_x;         // [M, K] fp32 rows (K == the LayerNorm width)
+    const float* ln_mean;      // [M]
+    const float* ln_rstd;      // [M]
+    const float* ln_gamma;     // [K]
+    const float* ln_beta;      // [K]
+    int8_t* ln_out8;           // [M, lda] = A of the passes that follow
+    int ln_qmin, ln_qmax;
+    QpLate ln_late;            // ln_late.stats set -> the LayerNorm-output quantizer is resolved here (workgroup 0 publishes it); else its ready values are read from aqp
 };
 
 // LDS image of one [208][64 B] k-tile of A: two 64-B tile rows share one 128-B LDS row; chunk ((row & 1) * 4 + k-chunk) XOR (LDS row & 7)
@@ -85,8 +98,10 @@ __device__ inline void strip_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\
 // NTL column tiles of 384 per workgroup: N == gridDim.y * NTL * 384; NWV waves, each 16 TM rows x WC = 384 / NWV columns; K = 64 KT.
 // (TM, KT) = (13, 6): 208-row strips of K = 384 (ViT-S: 243 strips at batch 256, one round); (7, 12): 112-row strips of K = 768 (ViT-B: 226 strips at
 // batch 128, all 6 / 8 column tiles in one workgroup) - the strip has to fit LDS next to the constants and the staging patches.
-template <int MODE, int NTL, int NWV = 8, bool R255 = false, int TM_ = 13, int KT_ = 6>
+// LN (statistics pass only): the A strip is not fetched from the int8 plane but produced here from the fp32 rows of the residual stream (I8StripArgs::ln_*)
+template <int MODE, int NTL, int NWV = 8, bool R255 = false, int TM_ = 13, int KT_ = 6, bool LN = false>
 __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArgs p) {
+    static_assert(!LN || MODE == 3, "the LayerNorm prologue exists in the statistics pass only");
     constexpr int TM = TM_, TNT = 24 / NWV, WC = 16 * TNT, BM = 16 * TM, BN = 384, KT = KT_, PF = 3, NT_ = NWV * 64;
     static_assert(TM <= 2 * NWV, "the strip's 1-KiB DMA pieces are dealt in two rounds");
     static_assert(NWV == 8 || NWV == 12, "8 waves x 48 columns or 12 waves x 32 columns");
@@ -117,7 +132,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
     QV_STAMP();   // entry
 
     // ---- A strip: KT k-tiles x TM pieces of 1 KiB, dealt to the waves; the swizzle goes on the SOURCE address (the DMA destination is lane-linear)
-    {
+    if constexpr (!LN) {
         const int64_t abytes = (int64_t)p.M * p.lda;   // wave-uniform raw-buffer descriptor: lanes past the end read zero
         const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t*>(p.A), 0, abytes > 0xffffffffll ? 0xffffffffu : (uint32_t)abytes, 0x00020000);
         const int lR = lane >> 3, lL = (lane & 7) ^ lR;
@@ -149,15 +164,86 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
     i32x4 bb[2][TNT];
     load_b(0, 0, bb[0]);
 
+    float* sQp = reinterpret_cast<float*>(sStage + (MODE == 3 ? 512 : NWV * WSTG));   // {scale, 1 / scale, zp} of a quantizer this workgroup resolves (below)
+
+    // ---- LN form: the strip from the fp32 rows.  Thread -> (16-B code chunk kc of a row, row lane rg): a thread keeps its 16 columns for all rows
+    // it converts (gamma / beta in registers), consecutive lanes take consecutive chunks (64 B of x each, 16 B of codes) of rows that follow each
+    // other in memory.  Rows are converted NIT sweeps of RG rows at a time, U sweeps per batch, the next batch's loads in flight under the arithmetic.
+    constexpr int CPR = KT * 4, RG = NT_ / CPR, NIT = (BM + RG - 1) / RG, LU = 2, LNB = (NIT + LU - 1) / LU;
+    const int kc = tid % CPR, rg = tid / CPR;
+    float4 xv[LN ? 2 : 1][LN ? LU : 1][4], lg[4], lb[4];
+    float xmu[LN ? 2 : 1][LN ? LU : 1], xrs[LN ? 2 : 1][LN ? LU : 1];
+    // sweep it: row rg + RG it of the strip.  Rows past the strip or past M load row m0 (always valid) and are masked where they are written
+    auto ln_load = [&](int it, float4 (&v)[4], float& mu, float& rs) {
+        const int rl = rg + RG * it;
+        const bool ok = rg < RG && rl < BM && m0 + rl < p.M;
+        const int64_t row = ok ? m0 + rl : m0;
+        const float4* src = reinterpret_cast<const float4*>(p.ln_x + row * (KT * 64) + kc * 16);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = src[c];
+        mu = p.ln_mean[row];
+        rs = p.ln_rstd[row];
+    };
+    if constexpr (LN) {
+#pragma unroll
+        for (int u = 0; u < LU; ++u) ln_load(u, xv[0][u], xmu[0][u], xrs[0][u]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            lg[c] = reinterpret_cast<const float4*>(p.ln_gamma + kc * 16)[c];
+            lb[c] = reinterpret_cast<const float4*>(p.ln_beta + kc * 16)[c];
+        }
+        // the LayerNorm-output quantizer: resolved by this workgroup's first wave under the loads above (workgroup 0 publishes it, as k_ln_apply_quant
+        // did), or ready in aqp.  Everything below takes scale and zero point from sQp - never from global memory workgroup 0 may be writing
+        if (p.ln_late.stats) qp_late_compute(p.ln_late, sQp);
+        else if (tid == 0) { sQp[0] = p.aqp[0]; sQp[1] = p.aqp[1]; sQp[2] = p.aqp[2]; }
+        strip_lds_barrier();
+        QV_STAMP();   // quantizer resolved
+    }
+    const float a_s = LN ? sQp[0] : *p.s1, a_inv = LN ? sQp[1] : 0.f, a_zp = LN ? sQp[2] : p.aqp[2];
+
     // per-column constants v = (float)(acc + corr[n]) * ca[n] + cb[n], once per workgroup into LDS (published by the barrier below): in the swapped
     // accumulator layout a lane needs 3 x 4 columns x 3 constants per column tile - as registers next to 156 accumulators they spill
     {
-        const float alpha = *p.s1 * (p.s2 ? *p.s2 : 1.0f);
-        const int zc = p.center - (int)p.aqp[2];
+        const float alpha = a_s * (p.s2 ? *p.s2 : 1.0f);
+        const int zc = p.center - (int)a_zp;
         for (int c = tid; c < NC; c += NT_) {
             sCorr[c] = zc * p.wsum[nbase + c];
             sCa[c] = alpha * (p.col_scale ? p.col_scale[nbase + c] : 1.0f);
             sCb[c] = p.bias ? p.bias[nbase + c] : 0.0f;
+        }
+    }
+    if constexpr (LN) {
+        // k_ln_apply_quant's arithmetic on every element: y = ((x - mu) * rs) * g + b;  q - zp = clamp(rint(y / s) + zp) - zp;  code = (q - zp) + (zp - center)
+        // (its bf16 round trip of q - zp, an integer of at most 9 bits, changes nothing)
+        const float fqmin = (float)p.ln_qmin, fqmax = (float)p.ln_qmax, sh = a_zp - (float)p.center;
+        auto ln_code = [&](float x, float mu, float rs, float g, float b) {
+            const float y = (x - mu) * rs * g + b;
+            const float qi = fminf(fmaxf(rintf(y * a_inv) + a_zp, fqmin), fqmax) - a_zp;
+            return (uint32_t)(uint8_t)(signed char)(qi + sh);
+        };
+        auto ln_put = [&](int it, const float4 (&v)[4], float mu, float rs) {
+            const int rl = rg + RG * it;
+            const bool in_strip = rg < RG && rl < BM, ok = in_strip && m0 + rl < p.M;
+            uint32_t w[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                w[c] = ln_code(v[c].x, mu, rs, lg[c].x, lb[c].x) | (ln_code(v[c].y, mu, rs, lg[c].y, lb[c].y) << 8) |
+                       (ln_code(v[c].z, mu, rs, lg[c].z, lb[c].z) << 16) | (ln_code(v[c].w, mu, rs, lg[c].w, lb[c].w) << 24);
+            const uint4 pk = ok ? make_uint4(w[0], w[1], w[2], w[3]) : make_uint4(0u, 0u, 0u, 0u);   // rows past M: zero codes, as the zero-filling DMA leaves them
+            if (in_strip) *reinterpret_cast<uint4*>(sA + (kc >> 2) * IMGA + strip_off(rl, kc & 3)) = pk;
+            if (ok) *reinterpret_cast<uint4*>(p.ln_out8 + (int64_t)(m0 + rl) * p.lda + kc * 16) = pk;
+        };
+#pragma unroll
+        for (int b = 0; b < LNB; ++b) {
+            if (b + 1 < LNB) {
+#pragma unroll
+                for (int u = 0; u < LU; ++u)
+                    if ((b + 1) * LU + u < NIT) ln_load((b + 1) * LU + u, xv[(b + 1) & 1][u], xmu[(b + 1) & 1][u], xrs[(b + 1) & 1][u]);
+            }
+            __builtin_amdgcn_sched_barrier(0);           // (the next batch's loads stay in front of this batch's arithmetic)
+#pragma unroll
+            for (int u = 0; u < LU; ++u)
+                if (b * LU + u < NIT) ln_put(b * LU + u, xv[b & 1][u], xmu[b & 1][u], xrs[b & 1][u]);
         }
     }
     struct Consts { float4 ca, cb; };
@@ -167,14 +253,13 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
     };
 
     // code passes: {scale, 1 / scale, zp} of the OUTPUT's quantizer - ready in p.qp, or resolved here from the statistics pass' accumulators (QpLate)
-    float* sQp = reinterpret_cast<float*>(sStage + (MODE == 3 ? 512 : NWV * WSTG));
     if constexpr (MODE != 3) {
         if (p.late.stats) qp_late_compute(p.late, sQp);
         else if (tid == 0) { sQp[0] = p.qp[0]; sQp[1] = p.qp[1]; sQp[2] = p.qp[2]; }
     }
 
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's A pieces have landed, its constants are written ...
-    QV_STAMP();   // own DMA landed
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's A pieces have landed (LN: are written), its constants are written ...
+    QV_STAMP();   // own DMA landed (LN: own rows converted)
     __builtin_amdgcn_s_barrier();                        // ... and everybody else's: the ONLY workgroup barrier of the code passes
     asm volatile("" ::: "memory");
     QV_STAMP();   // strip complete
@@ -416,6 +501,21 @@ static void strip_launch(const I8StripArgs& a0, hipStream_t st) {
     else strip_launch_w<MODE, NTL, 12, TM, KT>(a, st);
 }
 
+// the LN form of the statistics pass (8 waves, as the plain one)
+template <int NTL, int TM = 13, int KT = 6>
+static void strip_launch_ln(const I8StripArgs& a0, hipStream_t st) {
+    I8StripArgs a = a0;
+#ifdef QV_STRIP_EXPERIMENTS
+    const char* d = getenv("QATVIT_STRIP_DBG");
+    a.dbg = d ? reinterpret_cast<unsigned long long*>(strtoull(d, nullptr, 0)) : nullptr;
+#endif
+    constexpr int kLds = KT * 16 * TM * 64 + 3 * NTL * 384 * 4 + 512 + 16;
+    static_assert(kLds <= 160 * 1024, "strip + constants exceed the LDS");
+    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_i8_strip<3, NTL, 8, false, TM, KT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds), true);
+    (void)once;
+    k_i8_strip<3, NTL, 8, false, TM, KT, true><<<dim3(cdiv(a.M, 16 * TM), 1), 8 * 64, kLds, st>>>(a);
+}
+
 // true when the strip kernel covers the request (the caller then launched it); false -> the general tall kernel
 static int strip_ntl(int N, int K) {   // K = 384: 3 or 4 column tiles per workgroup (qkv 1152 / fc1 1536 of ViT-S); K = 768: all 6 or 8 of them (qkv 2304 / fc1 3072 of ViT-B)
     return K == 384 ? (N % (4 * 384) == 0 ? 4 : N % (3 * 384) == 0 ? 3 : 0) : (N == 6 * 384 ? 6 : N == 8 * 384 ? 8 : 0);
@@ -435,6 +535,34 @@ bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, con
     if (post->mode == 7) return post->code_hd == 64 && (N / 3) % 384 == 0 && post->code_T >= 1 && post->code_T < 1024;
     if (post->mode == 4) return !(post->out_hi || post->out_lo || post->code || post->out16_hi || post->out16_lo || !post->lut_out || !post->lutq_out || ldc % 128 != 0);
     return false;
+}
+
+// The LN form takes the requests the statistics pass takes whose workgroups own ALL columns of their rows (one workgroup per strip: nobody else
+// would write the same codes again) - qkv / fc1 of ViT-S (K = 384, N = 1152 / 1536) and of ViT-B (K = 768, N = 2304 / 3072)
+bool i8_strip_ln_covers(const void* B8f, int M, int N, int K, int lda) {
+    NTPost p1{};
+    p1.mode = 3;
+    return knobs().ln_strip && lda >= K && i8_strip_covers(B8f, M, N, K, lda, N, &p1) && N == strip_ntl(N, K) * 384 && (int64_t)M * K < (1ll << 31);
+}
+bool launch_i8_strip_ln(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int ln_qmin, int ln_qmax, void* out8,
+                        const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, const float* s2,
+                        const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, bool force, const QpLate* ln_late) {
+    if ((!(knobs().i8_strip && knobs().ln_strip) && !force) || !x || !mean || !rstd || !gamma || !beta || !out8 || !B8f || !wsum || !stats || (K != 384 && K != 768) ||
+        lda % 16 != 0 || lda < K || M < 1 || !strip_addressable(M, N, lda, N, 3) || (int64_t)M * K >= (1ll << 31))
+        return false;
+    const int ntl = strip_ntl(N, K);
+    if (!ntl || N != ntl * 384) return false;
+    if (!(ln_late && ln_late->stats) && !a_qp) return false;
+    I8StripArgs a{};
+    a.A = reinterpret_cast<const int8_t*>(out8); a.Bf = reinterpret_cast<const i32x4*>(B8f); a.M = M; a.N = N; a.lda = lda;
+    a.s1 = nullptr; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.wsum = wsum; a.aqp = a_qp; a.center = center;
+    a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
+    a.ln_x = x; a.ln_mean = mean; a.ln_rstd = rstd; a.ln_gamma = gamma; a.ln_beta = beta; a.ln_out8 = reinterpret_cast<int8_t*>(out8);
+    a.ln_qmin = ln_qmin; a.ln_qmax = ln_qmax;
+    if (ln_late) a.ln_late = *ln_late;
+    if (K == 768) { if (ntl == 8) strip_launch_ln<8, 7, 12>(a, st); else strip_launch_ln<6, 7, 12>(a, st); }
+    else if (ntl == 4) strip_launch_ln<4>(a, st); else strip_launch_ln<3>(a, st);
+    return true;
 }
 
 bool launch_i8_strip(const void* A8, const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, int ldc,

@@ -29,6 +29,7 @@ struct Knobs {
     bool attn_bwd_fused;  // QATVIT_ATTN_BWD_FUSED: one fused attention backward kernel where its shape holds; 0: k_attn_bwd_dq + k_attn_bwd_dkv
     bool f16_strip;       // QATVIT_F16_STRIP: the one-plane fc2 dgrad on the A-stationary strip kernel; 0: the general tall tile
     bool i8_strip;        // QATVIT_I8_STRIP: the K = 384 / 768 int8 GEMMs on the A-stationary strip kernel; 0: the general tall kernel
+    bool ln_strip;        // QATVIT_LN_STRIP: norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln); 0: k_ln_apply_quant in front of it
 };
 const Knobs& knobs();
 

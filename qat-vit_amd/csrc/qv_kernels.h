@@ -131,6 +131,15 @@ bool launch_i8_strip(const void* A8, const void* B8f, const int32_t* wsum, const
                      const NTPost* post, bool force = false, const QpLate* late = nullptr);   // late (code passes): the output quantizer's qparams are resolved inside
 // would launch_i8_strip take this request?  (the engine decides on it BEFORE the statistics pass whether a k_qparams launch has to follow it)
 bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post);
+// The statistics pass with the LayerNorm apply + quantise in its prologue (k_ln_apply_quant's work, the same bits): every workgroup builds its strip from the
+// fp32 rows x [M, K] (mean / rstd [M], gamma / beta [K]), keeps it in LDS and stores it to out8 [M, lda] (q - center), the plane the code pass and the weight
+// gradients read.  The A operand's quantizer is ln_late (resolved inside; workgroup 0 publishes it) or, without it, the ready a_qp; *s1 of launch_i8_strip is
+// that quantizer's scale.  i8_strip_ln_covers: would it take the request (QATVIT_LN_STRIP, one workgroup per strip: N == 3 / 4 (K = 768: 6 / 8) x 384)?
+bool launch_i8_strip_ln(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int ln_qmin, int ln_qmax, void* out8,
+                        const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, const float* s2,
+                        const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, bool force = false,
+                        const QpLate* ln_late = nullptr);
+bool i8_strip_ln_covers(const void* B8f, int M, int N, int K, int lda);
 // byte offset of element (n, k) of an [N, K] int8 weight in fragment order: [48-column group][64-deep k-step][16-column fragment][lane = 16 (k % 64 / 16) + n % 16][k % 16]
 __host__ __device__ inline int64_t w8f_offset(int n, int k, int K) {
     const int cg = n / 48, cr = n % 48, j = cr / 16, r = cr % 16, kt = k / 64, kk = k % 64;

@@ -316,6 +316,7 @@ class StudentEngine:
         self.dy16 = dy16_default() and bool(self.lib.qatvit_student_dy16_supported(ctypes.byref(self.cfg)))
         self._dy16_calibrated = False
         self._fwd_x16 = False                    # how the most recent forward wrote h1q / h2q
+        self.ln_in_strip = 0                     # ... and which of its LayerNorms ran inside a statistics pass (forward())
         self.dy16_fallbacks = 0                  # backward passes repeated in the pair form after an overflow
         # host mirror of the overflow flag (include/qatvit.h, qatvit_student_dy16_set_mirror): pinned int32 {flag, generation} the backward writes before its deferred
         # weight gradients; the single-GPU backward polls it instead of synchronising with the stream.  QATVIT_DY16_MIRROR=0: the stream synchronisation.
@@ -508,6 +509,8 @@ class StudentEngine:
         self.generation += 1
         # a training forward of a calibrated engine leaves the X operands of the qkv / fc1 weight gradients as fp16 integers: its backward is one-plane
         self._fwd_x16 = self.dy16 and self._dy16_calibrated and self.sync_state
+        # which LayerNorms of this forward run inside the statistics pass that follows them (bit 0: norm1 / qkv, bit 1: norm2 / fc1; QATVIT_LN_STRIP)
+        self.ln_in_strip = int(self.lib.qatvit_student_ln_in_strip(ctypes.byref(c), FWD_X16 if self._fwd_x16 else 0))
         native.check(self.lib.qatvit_student_forward_stages(ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, images.data_ptr(),
                                                             logits.data_ptr(), self.workspace.data_ptr(), 0, c.depth + 1, FWD_X16 if self._fwd_x16 else 0,
                                                             native.stream_ptr()), "qatvit_student_forward")

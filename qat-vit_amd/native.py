@@ -35,6 +35,8 @@ SIGNATURES = {
     "qatvit_gemm_nt_i8_minmax": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_w8_fragment_order": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "qatvit_i8_strip": (c_int, [c_int32] + [c_void_p] * 4 + [c_int32] * 5 + [c_void_p] * 6 + [c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 4),
+    "qatvit_ln_apply_quant8": (c_int, [c_void_p] * 6 + [c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p]),
+    "qatvit_i8_strip_ln": (c_int, [c_void_p] * 5 + [c_int32, c_int32] + [c_void_p] * 4 + [c_int32] * 5 + [c_void_p] * 5),
     "qatvit_gemm_nt_codes": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_gemm_nt_i8": (c_int, [c_void_p] * 4 + [c_int32, c_void_p] + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_gemm_tn_scratch_bytes": (c_int64, []),
@@ -61,6 +63,7 @@ SIGNATURES = {
     "qatvit_student_backward_stages": (c_int, [c_void_p] * 7 + [c_int32, c_int32, c_int32, c_void_p]),
     "qatvit_student_tensor_offset": (c_int64, [c_void_p, c_char_p, c_int32]),
     "qatvit_student_dy16_supported": (c_int32, [c_void_p]),
+    "qatvit_student_ln_in_strip": (c_int32, [c_void_p, c_int32]),
     "qatvit_student_dy16_to_pair": (c_int, [c_void_p, c_void_p, c_void_p]),
     "qatvit_student_dy16_set_mirror": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "qatvit_teacher_workspace_bytes": (c_int64, [c_void_p]),

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """s_memtime stamps of the int8 strip kernel (experiment build, QATVIT_STRIP_VAR=1024): where one workgroup's waves spend their cycles.
-Prints, for workgroups 0 and 100, wave 0 / wave 4 / the slowest wave: cycles between consecutive stamps."""
+Prints, for workgroups 0 and 100, wave 0 / wave 4 / the slowest wave: cycles between consecutive stamps.  Mode "3 ln" is the statistics pass with the
+LayerNorm apply + quantise in its prologue (qatvit_i8_strip_ln) on fp32 rows; QATVIT_STAMP_N=1536 stamps the fc1 shape instead of qkv's."""
 import os
 import sys
 
@@ -19,7 +20,8 @@ torch.manual_seed(0)
 A8 = (torch.randint(0, 256, (M, K), device=dev) - 128).to(torch.int8)
 aqp = torch.tensor([0.0173, 1 / 0.0173, 131.0, 1.0], device=dev)
 s1, s2 = torch.tensor([0.0173], device=dev), torch.tensor([0.0041], device=dev)
-N = 1152
+N = int(os.environ.get("QATVIT_STAMP_N", "1152"))
+NTL = N // 384
 W = torch.randint(-128, 128, (N, K), device=dev)
 B8 = W.to(torch.int8)
 B8f = torch.empty_like(B8)
@@ -32,11 +34,21 @@ out8 = torch.empty(M * N, dtype=torch.uint8, device=dev)
 mask = torch.empty(M * N // 8, dtype=torch.uint8, device=dev)
 dbg = torch.zeros(2 * 8 * 32, dtype=torch.int64, device=dev)
 os.environ["QATVIT_STRIP_DBG"] = hex(dbg.data_ptr())
-names = {3: ["entry", "own DMA", "strip ready"] + [f"t{t} k-loop" for t in range(3)] + ["end"],
-         7: ["entry", "own DMA", "strip ready"] + sum([[f"t{t} k-loop", f"t{t} epilogue"] for t in range(3)], []) + ["end"]}
-for mode in (3, 7):
+x = torch.randn(M, K, device=dev)
+mean, rstd = x.mean(1).contiguous(), torch.rsqrt(x.var(1, unbiased=False) + 1e-6).contiguous()
+gamma, beta = torch.ones(K, device=dev), torch.zeros(K, device=dev)
+ln8 = torch.empty(M, K, dtype=torch.int8, device=dev)
+names = {3: ["entry", "own DMA", "strip ready"] + [f"t{t} k-loop" for t in range(NTL)] + ["end"],
+         "3 ln": ["entry", "quantizer", "own rows", "strip ready"] + [f"t{t} k-loop" for t in range(NTL)] + ["end"],
+         7: ["entry", "own DMA", "strip ready"] + sum([[f"t{t} k-loop", f"t{t} epilogue"] for t in range(NTL)], []) + ["end"]}
+for mode in (3, "3 ln") + ((7,) if N == 1152 else ()):
     for _ in range(5):   # warm
         dbg.zero_()
+        if mode == "3 ln":
+            native.check(L.qatvit_i8_strip_ln(x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 0, 255, ln8.data_ptr(), B8f.data_ptr(),
+                                              wsum.data_ptr(), aqp.data_ptr(), 128, M, N, K, K, s2.data_ptr(), None, bias.data_ptr(), stats.data_ptr(), st), "strip ln")
+            torch.cuda.synchronize()
+            continue
         native.check(L.qatvit_i8_strip(mode, A8.data_ptr(), B8f.data_ptr(), wsum.data_ptr(), aqp.data_ptr(), 128, M, N, K, K, s1.data_ptr(), s2.data_ptr(), None,
                                        bias.data_ptr(), stats.data_ptr() if mode == 3 else None, qp.data_ptr(), 0, 255, out8.data_ptr(), mask.data_ptr(), T,
                                        None, None, None, st), "strip")
