@@ -14,21 +14,12 @@
 #include <stdlib.h>
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 
 namespace qv {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kAW = 8;  // waves per attention workgroup (two per SIMD)
-// workgroup barrier that waits for this wave's LDS traffic only (__syncthreads also drains vmcnt: every global store's round trip)
-__device__ inline void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
 
 // (pk_bf16 / split_pair: qv_common.h)
@@ -121,29 +112,7 @@ __device__ inline bf16x8 decode8(const uint2& codes, float off /* qmin - zp */) 
     return __builtin_bit_cast(bf16x8, (u32x4){w[0], w[1], w[2], w[3]});
 }
 
-// ---- LDS images of a [tokens][HD] bf16 tile
-template <int HD> __device__ inline int row_off(int row, int chunk) {   // for ds_read_b128 row fragments
-    if constexpr (HD == 64) return row * 128 + ((chunk ^ (row & 7)) << 4);
-    else return row * (HD * 2) + (chunk << 4);
-}
-template <int HD> __device__ inline int tr_off(int row, int chunk) {    // for ds_read_b64_tr_b16 blocks of 4 rows
-    if constexpr (HD == 64) return row * 128 + ((chunk ^ (((row >> 1) & 3) << 1)) << 4);
-    else return row * (HD * 2) + (chunk << 4);
-}
-
-// fragment whose k-slots (g, j) are tokens tokA + 4g + (0..3) [j<4] and tokB + 4g + (0..3) [j>=4],
-// and whose row/col index is feature col0 + (lane & 15)
-template <int HD> __device__ inline bf16x8 tr_frag2(const char* img, int tokA, int tokB, int col0, int lane) {
-    const int g = lane >> 4, idx = lane & 15, q = idx >> 2, pp = idx & 3;
-    const int chunk = (col0 >> 3) + (pp >> 1);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + tr_off<HD>(tokA + 4 * g + q, chunk) + (pp & 1) * 8));
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + tr_off<HD>(tokB + 4 * g + q, chunk) + (pp & 1) * 8));
-    // whole-vector bit cast: per-element short->__bf16 inserts are miscompiled by hipcc 7.2 (every element becomes a[0])
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
+// (LDS images of a [tokens][HD] bf16 tile - row_off / tr_off / tr_frag2: qv_device.h)
 
 // 8 consecutive features of one token row -> quantized-integer bf16 fragment
 __device__ inline bf16x8 load_q8(const float* p, const AQP& q) {
@@ -193,7 +162,7 @@ __device__ inline void store_split8_h(_Float16* hi, _Float16* lo, int64_t off, c
 
 // Re-tile one wave's 16 x HD fp32 accumulator block (MFMA layout: column on the lane, 4 rows per register group) through a
 // private LDS scratch into row-major runs: afterwards lane (row = lane / (HD/16), c16 = lane % (HD/16)) holds 16 consecutive
-// features of one token row -> 32-B bf16 stores instead of 2-B scatters.  LDS is in-order per wave; the asm fences stop the
+// features of one token row -> 32-B bf16 stores instead of 2-B scatters.  LDS is in-order per wave; the fences stop the
 // compiler from reordering across the hand-off.
 template <int HD>
 __device__ inline bool wave_retile(float* sO, const f32x4 (&acc)[HD / 16], float scale, int lane, float (&out)[16], int& row, int& c16) {
@@ -203,7 +172,7 @@ __device__ inline bool wave_retile(float* sO, const f32x4 (&acc)[HD / 16], float
     for (int jd = 0; jd < HD / 16; ++jd)
 #pragma unroll
         for (int e = 0; e < 4; ++e) sO[(4 * g + e) * LDO + 16 * jd + r] = acc[jd][e] * scale;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
     row = lane / (HD / 16);
     c16 = lane % (HD / 16);
     const bool active = row < 16;
@@ -214,7 +183,7 @@ __device__ inline bool wave_retile(float* sO, const f32x4 (&acc)[HD / 16], float
             out[4 * k] = v.x; out[4 * k + 1] = v.y; out[4 * k + 2] = v.z; out[4 * k + 3] = v.w;
         }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
     return active;
 }
 __device__ inline void store_split16(__bf16* hi, __bf16* lo, int64_t off, const float (&v)[16]) {
@@ -228,31 +197,7 @@ __device__ inline void store_split16(__bf16* hi, __bf16* lo, int64_t off, const 
     *reinterpret_cast<bf16x8*>(lo + off) = l0; *reinterpret_cast<bf16x8*>(lo + off + 8) = l1;
 }
 
-// Half-tile variant (8 token rows at a time, 2.1 KiB of scratch per wave instead of 4.3 KiB): with it the forward and dQ kernels fit
-// TWO workgroups per CU (LDS <= 80 KiB, <= 128 VGPRs), so one workgroup's staging phase overlaps the other's compute.
-// half = 0: rows 0..7 (lanes with g < 2 hold them), half = 1: rows 8..15.  Afterwards lane (row = lane / (HD/8), c8 = lane % (HD/8))
-// holds 8 consecutive features of token row 8*half + row.
-template <int HD>
-__device__ inline bool wave_retile8(float* sO, const f32x4 (&acc)[HD / 16], float scale, int lane, int half, float (&out)[8], int& row, int& c8) {
-    constexpr int LDO = HD + 4;
-    const int r = lane & 15, g = lane >> 4;
-    if ((g >> 1) == half) {
-#pragma unroll
-        for (int jd = 0; jd < HD / 16; ++jd)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sO[(4 * (g & 1) + e) * LDO + 16 * jd + r] = acc[jd][e] * scale;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    row = lane / (HD / 8);
-    c8 = lane % (HD / 8);
-    const bool active = row < 8;
-    if (active) {
-        const float4 v0 = *reinterpret_cast<const float4*>(sO + row * LDO + 8 * c8), v1 = *reinterpret_cast<const float4*>(sO + row * LDO + 8 * c8 + 4);
-        out[0] = v0.x; out[1] = v0.y; out[2] = v0.z; out[3] = v0.w; out[4] = v1.x; out[5] = v1.y; out[6] = v1.z; out[7] = v1.w;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return active;
-}
+// (half-tile variant, 8 token rows at a time - wave_retile8: qv_device.h)
 __device__ inline void store_split8(__bf16* hi, __bf16* lo, int64_t off, const float (&v)[8]) {
     uint32_t H[4], L[4];
 #pragma unroll
@@ -298,9 +243,8 @@ __device__ inline bf16x8 quant8(const float4& a, const float4& b, const AQP& q) 
     f[4] = (__bf16)qint(b.x, q); f[5] = (__bf16)qint(b.y, q); f[6] = (__bf16)qint(b.z, q); f[7] = (__bf16)qint(b.w, q);
     return f;
 }
-// (pins: an empty asm that "uses" the loaded values right after the load loop - left alone, LLVM sinks half of the loads below the first
-//  half's conversions, two memory round trips per image instead of one)
-__device__ inline void pin4(const float4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
+// (pin4_in, qv_device.h, right after the load loop: left alone, LLVM sinks half of the loads below the first half's conversions, two memory
+//  round trips per image instead of one)
 __device__ inline f16x8 quant8_h(const float4& a, const float4& b, const AQP& q) {
     f16x8 f;
     f[0] = (_Float16)qint(a.x, q); f[1] = (_Float16)qint(a.y, q); f[2] = (_Float16)qint(a.z, q); f[3] = (_Float16)qint(a.w, q);
@@ -322,7 +266,7 @@ __device__ inline void stage_tokens(char* img, const float* base, int T, int ld,
         a[it] = p[0]; b[it] = p[1];
     }
 #pragma unroll
-    for (int it = 0; it < ITERS; ++it) { pin4(a[it]); pin4(b[it]); }
+    for (int it = 0; it < ITERS; ++it) { pin4_in(a[it]); pin4_in(b[it]); }
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int i = threadIdx.x + it * NWV * 64, tok = i / CH, ch = i % CH;
@@ -382,7 +326,7 @@ __device__ inline void stage_split_tr(char* img_hi, char* img_lo, const float* b
         a[it] = p[0]; b[it] = p[1];
     }
 #pragma unroll
-    for (int it = 0; it < ITERS; ++it) { pin4(a[it]); pin4(b[it]); }
+    for (int it = 0; it < ITERS; ++it) { pin4_in(a[it]); pin4_in(b[it]); }
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int i = threadIdx.x + it * NWV * 64, tok = i / CH, ch = i % CH;
@@ -636,7 +580,7 @@ __global__ __launch_bounds__(kAW * 64) void k_attn_bwd_dq(const AttnArgs p) {
             csq[1] = *reinterpret_cast<const float4*>(p.col_scale + h * HD + 8 * ec8 + 4);
         }
 #pragma unroll
-        for (int half = 0; half < 2; ++half) { pin4(xq[half][0]); pin4(xq[half][1]); }
+        for (int half = 0; half < 2; ++half) { pin4_in(xq[half][0]); pin4_in(xq[half][1]); }
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             float gv[8];
@@ -752,7 +696,7 @@ __global__ __launch_bounds__(NWV * 64) void k_attn_bwd_dkv(const AttnArgs p) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
-            for (int kk = 0; kk < KK; ++kk) { pin4(kr[u][kk][0]); pin4(kr[u][kk][1]); pin4(vr[u][kk][0]); pin4(vr[u][kk][1]); }
+            for (int kk = 0; kk < KK; ++kk) { pin4_in(kr[u][kk][0]); pin4_in(kr[u][kk][1]); pin4_in(vr[u][kk][0]); pin4_in(vr[u][kk][1]); }
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -866,7 +810,7 @@ __global__ __launch_bounds__(NWV * 64) void k_attn_bwd_dkv(const AttnArgs p) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int id = 0; id < ND; ++id) { pin4(xk[u][id]); pin4(xv[u][id]); }
+        for (int id = 0; id < ND; ++id) { pin4_in(xk[u][id]); pin4_in(xv[u][id]); }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (!kvalid[u]) continue;
@@ -911,11 +855,9 @@ __global__ __launch_bounds__(NWV * 64) void k_attn_bwd_dkv(const AttnArgs p) {
 constexpr int kSRow = 32;
 __device__ inline bf16x8 tr_frag_ds(const char* img_vq, int tokA, int tokB, int lane) {
     const int g = lane >> 4, idx = lane & 15, q = idx >> 2, pp = idx & 3;
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     // rows tokA + 4g + q, tokA a multiple of 16: (row >> 2) & 3 == g
     const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img_vq + (tokA + 4 * g + q) * kSRow + ((pp ^ g) << 3)));
     const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img_vq + (tokB + 4 * g + q) * kSRow + ((pp ^ g) << 3)));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
     const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, v);
 }
@@ -999,7 +941,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
     for (int i = threadIdx.x; i < 2 * SIMG / 16; i += NWV * 64) reinterpret_cast<uint4*>(sSh)[i] = make_uint4(0u, 0u, 0u, 0u);   // key tiles nobody owns stay zero
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
-        pin4(da4[it]); pin4(db4[it]);
+        pin4_in(da4[it]); pin4_in(db4[it]);
         asm volatile("" ::"v"(oh[it].x), "v"(oh[it].y), "v"(oh[it].z), "v"(oh[it].w), "v"(ol[it].x), "v"(ol[it].y), "v"(ol[it].z), "v"(ol[it].w));
         asm volatile("" ::"v"(cq[it].x), "v"(cq[it].y), "v"(ck[it].x), "v"(ck[it].y));
     }
@@ -1125,7 +1067,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
                 split_acc2(ds2[0], ds2[1], sh, sl2);
             }
             // the dS image is free again once every wave has finished the previous pair's dQ^T tile
-            if (u == 0) lds_only_barrier();
+            if (u == 0) lds_barrier();
             if (has[u]) {
                 // this lane: key 16 jt + r, queries 4g .. 4g+3 of tile v in elements 4v .. 4v+3 -> 8-byte runs of the [key][32 queries] image
                 const uint4 wh = __builtin_bit_cast(uint4, sh), wl = __builtin_bit_cast(uint4, sl2);
@@ -1144,7 +1086,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
                 }
             }
         }
-        lds_only_barrier();   // every owned key tile's dS of this query pair is in the image
+        lds_barrier();   // every owned key tile's dS of this query pair is in the image
         f32x4 dq = {0.f, 0.f, 0.f, 0.f}, dq1 = {0.f, 0.f, 0.f, 0.f};   // (two chains: the hi and the lo products)
 #pragma unroll
         for (int ks = 0; ks < NKT / 2; ++ks) {
@@ -1188,7 +1130,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
         mkr[u] = sM[T + krow];
         mvr[u] = sM[2 * T + krow];
     }
-    lds_only_barrier();
+    lds_barrier();
     constexpr int kERow = 144;
     char* const sE = smem + wave * (4 * 16 * kERow);   // [k hi | k lo | v hi | v lo][16 keys][144 B]
     const int erow = lane >> 3, ech = lane & 7;       // read-back: 8 lanes per key row, two passes of 8 rows
@@ -1221,7 +1163,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
                 *reinterpret_cast<uint2*>(e + 48 * kERow) = vl;
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (wave-private: LDS is in order per wave, no barrier)
+        wave_lds_fence();   // (wave-private: LDS is in order per wave, no barrier)
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int key = 16 * jt[u] + 8 * half + erow;
@@ -1243,7 +1185,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the tile is read before the next key tile overwrites it
+        wave_lds_fence();   // the tile is read before the next key tile overwrites it
     }
     if constexpr (O16) {
         am16 = wave_max(am16);
@@ -1265,9 +1207,8 @@ template <int HD, int NKT>
 static void launch3(int which, const AttnArgs& a, hipStream_t st) {
     const size_t img = (size_t)NKT * 16 * HD * 2;
     const int grid = a.B * a.H;
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_fwd<HD, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * img + kAW * 8 * (HD + 4) * 4)),
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_dq<HD, NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * img + kAW * 8 * (HD + 4) * 4)),
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_dkv<HD, NKT, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * img + NKT * 128)), true);
+    static bool once = (allow_lds(k_attn_fwd<HD, NKT>, 2 * img + kAW * 8 * (HD + 4) * 4), allow_lds(k_attn_bwd_dq<HD, NKT>, 2 * img + kAW * 8 * (HD + 4) * 4),
+                        allow_lds(k_attn_bwd_dkv<HD, NKT, 8>, 3 * img + NKT * 128), true);
     (void)once;
     const size_t scratch = (size_t)kAW * 8 * (HD + 4) * sizeof(float);   // half-tile re-tiling scratch: 2 workgroups per CU (fwd, dQ)
     if (which == 0) k_attn_fwd<HD, NKT><<<grid, kAW * 64, 2 * img + scratch, st>>>(a);
@@ -1319,8 +1260,7 @@ int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B
     if (check_shape(T, D, H, &nkt)) return 1;
     if (attn_bwd_is_fused(T, H, D, codes != nullptr)) {
         constexpr int kLds = 4 * 14 * 16 * 64 * 2 + 2 * 2 * 14 * 16 * kSRow + 2 * 14 * 16 * 4 + 3 * 14 * 16 * 8 + 3 * 64 * 4;   // 151,296 B
-        static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_fused<14>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds),
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bwd_fused<14, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds), true);
+        static bool once = (allow_lds(k_attn_bwd_fused<14>, kLds), allow_lds(k_attn_bwd_fused<14, true>, kLds), true);
         (void)once;
         if (o16_mul) {
             if (!o16_amax) { set_error("attention backward: o16_mul needs o16_amax"); return 1; }

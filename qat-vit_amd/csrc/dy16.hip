@@ -6,6 +6,7 @@
 // every gradient by that factor).  The producers record this step's maximum; a maximum that did not fit raises the overflow flag and the host
 // repeats the backward in the pair form (engine.py) - the result is then bit-identical to a pair-form step.  Layout: qv_kernels.h.
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 
 namespace qv {
@@ -93,8 +94,6 @@ __global__ __launch_bounds__(256) void k_absmax_bf16(const uint4* __restrict__ h
 }
 
 __global__ __launch_bounds__(256) void k_f16int_to_bf16int(uint4* __restrict__ p, int64_t n8) {
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
         const f16x8 v = __builtin_bit_cast(f16x8, p[i]);
         bf16x8 o;
@@ -106,7 +105,6 @@ __global__ __launch_bounds__(256) void k_f16int_to_bf16int(uint4* __restrict__ p
 
 // plane[i] = q8[i] + center - zero point as bf16 (|.| <= 255: exact): the pair-form weight gradient's X operand rebuilt from the forward's int8 plane
 __global__ __launch_bounds__(256) void k_q8_to_bf16int(const uint2* __restrict__ q8, const float* __restrict__ qp, int center, uint4* __restrict__ out, int64_t n8) {
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     const float off = (float)center - qp[2];
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
         const uint2 b = q8[i];

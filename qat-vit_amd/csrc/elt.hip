@@ -11,13 +11,11 @@
 #include <stdlib.h>
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 #include "qv_qparams.h"
 
 namespace qv {
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct QP { float s, inv, zp, on; };
 __device__ inline QP load_qp(const float* qp) { return QP{qp[0], qp[1], qp[2], qp[3]}; }
@@ -33,7 +31,7 @@ __device__ inline float fqi(float x, const QP& q, float fqmin, float fqmax) {
     return fminf(fmaxf(rintf(x * q.inv) + q.zp, fqmin), fqmax) - q.zp;
 }
 
-// float operand of a later GEMM -> (hi, lo) bf16 pair, 4 elements
+// float operand of a later GEMM -> (hi, lo) bf16 pair, 4 elements (through split_pair; teacher.hip's st_split4 casts per element and has an fp16 branch)
 __device__ inline void store_split4(__bf16* hi, __bf16* lo, int64_t off, float a, float b, float c, float d) {
     uint2 h, l;
     split_pair(a, b, h.x, l.x);
@@ -100,8 +98,7 @@ __global__ __launch_bounds__(256) void k_img_patches(const float* __restrict__ i
 // MODE 2: x_new = x_prev, nothing is stored (statistics of a residual-stream tensor the caller wrote: stage-level parity tests)
 // then: mean/rstd of the x_new row and min/max of LN(x_new)*gamma+beta (the next aFQ's observer input).
 constexpr int kMaxV = 3;  // float4 per lane per row: D <= 768
-__device__ inline void pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
-// NV = column groups per lane (ceil(D / 256)).  All of a row's global loads are issued before anything is used, without branches
+// NV = column groups per lane (ceil(D / 256)).  All of a row's global loads are issued before anything is used (pin4, qv_device.h), without branches
 // (a lane whose column is >= D loads column 0 and is masked out of the sums and stores): one `if (c < D)` region per column group made
 // the compiler serialise the groups, i.e. two or three dependent HBM round trips per row.  gamma / beta are loaded once per thread.
 template <int MODE, int NV>
@@ -306,10 +303,7 @@ __global__ __launch_bounds__(256) void k_cls_rows(const float* __restrict__ cls,
     }
 }
 
-// ---------------------------------------------------------------- GELU(fq(Y)) forward / backward
-__device__ inline float gelu(float x) { return gelu_fwd(x); }
-__device__ inline float dgelu(float x) { return gelu_bwd(x); }
-
+// ---------------------------------------------------------------- GELU(fq(Y)) forward / backward (gelu_fwd / gelu_bwd: qv_common.h)
 // GELU_BWD=0: dY = d * mask(Y);  GELU_BWD=1: dY = d * gelu'(fq(Y)) * mask(Y); optionally * col_scale[col]
 // (per-channel weight scale of the consuming layer, folded here because dgrad's reduction runs over that axis).
 // Output: the (hi, lo) bf16 pair both the dgrad and the wgrad GEMM read.
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(256) void k_mask_bwd(const float* __restrict__ d, c
         for (int e = 0; e < 4; ++e) {
             bool in;
             const float f = fqv(in4[e], q, qmin, qmax, in);
-            o[e] = in ? (GELU_BWD ? g4[e] * dgelu(f) : g4[e]) * cs[e] : 0.f;
+            o[e] = in ? (GELU_BWD ? g4[e] * gelu_bwd(f) : g4[e]) * cs[e] : 0.f;
         }
         if constexpr (O16) store_f16x4(dst_hi, i * 4, o[0], o[1], o[2], o[3], mul, am);
         else store_split4(dst_hi, dst_lo, i * 4, o[0], o[1], o[2], o[3]);

@@ -19,14 +19,10 @@
 #include <stdlib.h>
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 
 namespace qv {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct F16StripArgs {
     const _Float16* A;      // [M, lda] the gradient plane (value * 2^e)
@@ -45,27 +41,8 @@ struct F16StripArgs {
     uint32_t* o16_amax;
 };
 
-// LDS-DMA through inline asm (gemm.hip dma16_asm): hipcc waits vmcnt(0) in front of every LDS read that follows a __builtin_amdgcn_raw_ptr_buffer_load_lds it cannot
-// prove disjoint - here every fragment read of the next column tile's k-loop.  An asm DMA is invisible to that bookkeeping; completion is counted by hand.
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-__device__ inline v4i32 fs_rsrc(const void* base, int64_t bytes) {
-    const uint64_t b = reinterpret_cast<uint64_t>(base);
-    const uint32_t n = bytes > 0xffffffffll ? 0xffffffffu : (uint32_t)bytes;
-    return (v4i32){(int)(uint32_t)b, (int)(uint32_t)(b >> 32), (int)n, 0x00020000};
-}
-__device__ inline void fs_dma16(v4i32 rsrc, const char* lds_dst, uint32_t voff) {
-    const uint32_t m = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>((lds_void*)lds_dst));
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(m), "s"(rsrc)
-                 : "memory");
-}
-
-__device__ inline int fstrip_off(int row, int chunk) {   // (strip_off of i8strip.hip)
-    const int R = row >> 1;
-    return R * 128 + (((((row & 1) << 2) | chunk) ^ (R & 7)) << 4);
-}
+// The codes come in by LDS-DMA through inline asm (make_rsrc_v / dma16_asm, qv_device.h): hipcc waits vmcnt(0) in front of every LDS read that follows a
+// __builtin_amdgcn_raw_ptr_buffer_load_lds it cannot prove disjoint - here every fragment read of the next column tile's k-loop.  The k-tile images are strip_off's.
 
 // 12 waves x 32 columns (three per SIMD, 56 accumulator registers), TM = 7 row fragments (112 rows; 104 of them this strip's), KT = 12 k-tiles of 64 B
 template <int NTL>
@@ -114,7 +91,7 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
     i32x4 bb[2][TNT];
     load_b(0, 0, bb[0]);
     // the codes of this wave's sub-tile of column tile nt: 112 rows x 32 B = 3.5 pieces of 1 KiB by LDS-DMA (lane -> row l / 2, half l % 2), wave-private
-    const v4i32 rC = fs_rsrc(p.code8, (int64_t)p.M * p.ldc);
+    const v4i32 rC = make_rsrc_v(p.code8, (int64_t)p.M * p.ldc);
     char* const sCode = sCodeAll + wave * WCODE;
     auto load_codes = [&](int nt) {
 #pragma unroll
@@ -122,7 +99,7 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
             const int row = pc * 32 + (lane >> 1);
             if (pc < 3 || lane < 32) {   // (the fourth piece is half a piece: rows 96 .. 111)
                 const uint32_t off = (uint32_t)((int64_t)(m0 + row) * p.ldc + nt * BN + wave * WC + (lane & 1) * 16);
-                fs_dma16(rC, sCode + pc * 1024, off);
+                dma16_asm(rC, sCode + pc * 1024, off);
             }
         }
     };
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
             __builtin_amdgcn_sched_barrier(0);
             int opaque = 0;
             asm volatile("" : "+v"(opaque));             // (keeps the loop-invariant fragment reads inside the column-tile loop: i8strip.hip)
-            const char* st = sA + opaque + kt * IMGA + fstrip_off(r, g);
+            const char* st = sA + opaque + kt * IMGA + strip_off(r, g);
             i32x4 af[PF];
 #pragma unroll
             for (int i = 0; i < PF - 1; ++i) af[i] = *reinterpret_cast<const i32x4*>(st + 1024 * i);
@@ -180,7 +157,7 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
             const int row = m0 + 16 * i + r2;
             mword[i] = row < p.M ? *reinterpret_cast<const uint32_t*>(p.mask + ((int64_t)row * p.ldc + colbase) / 8) : 0u;
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this tile's codes (DMA) and mask words have landed; the next tile's first weight fragments too
+        wait_vmcnt<0>();   // this tile's codes (DMA) and mask words have landed; the next tile's first weight fragments too
 #pragma unroll
         for (int c0 = 0; c0 < TM; c0 += CH) {
             const int nf = TM - c0 < CH ? TM - c0 : CH;
@@ -205,7 +182,7 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
                     *reinterpret_cast<uint2*>(sOut + rl * OROW + (16 * j + 4 * g2) * 2) = make_uint2(pk_f16(o[0] * mul, o[1] * mul), pk_f16(o[2] * mul, o[3] * mul));
                 }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (wave-private: the wave's own LDS operations execute in order)
+            wave_lds_fence();   // (wave-private: the wave's own LDS operations execute in order)
             // read the patch back: 16 rows x four 16-byte pieces = one piece per lane
             {
                 const int rl = lane2 >> 2, c = lane2 & 3;
@@ -216,7 +193,7 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
             asm volatile("" ::: "memory");
         }
         if (nt + 1 < NTL) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every read of this tile's codes is done: the next tile's may land in the same patch
+            wave_lds_fence();   // every read of this tile's codes is done: the next tile's may land in the same patch
             load_codes(nt + 1);
         }
     }
@@ -238,7 +215,7 @@ bool launch_f16_strip_gelu_bwd(const void* A16, const void* B16f, float* /*unuse
     a.out = reinterpret_cast<_Float16*>(post->out_hi); a.o16_mul = post->o16_mul; a.o16_amax = post->o16_amax;
     constexpr int kLds = 12 * 16 * 7 * 64 + 4 * 384 * 4 + 1024 + 12 * (16 * 7 * 32) + 12 * (16 * 80);   // 86,016 + 6,144 + 1,024 + 43,008 + 15,360 = 151,552 B
     static_assert(kLds <= 160 * 1024, "LDS");
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_f16_strip_gelu_bwd<4>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds), true);
+    static bool once = (allow_lds(k_f16_strip_gelu_bwd<4>, kLds), true);
     (void)once;
     k_f16_strip_gelu_bwd<4><<<cdiv(M, 104), 768, kLds, st>>>(a);
     return true;

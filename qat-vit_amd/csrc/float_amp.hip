@@ -17,26 +17,23 @@
 #include "../../include/qatvit.h"
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 
 namespace qv {
-
-typedef _Float16 fa_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 fa_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float fa_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline float f16r(float v) { return (float)(_Float16)v; }   // round to fp16 and back (RNE: beyond 65520 -> inf)
 // the element type's pieces: 8-element MFMA fragment, the 16x16x32 MFMA, two floats packed (one v_cvt_pk), round and back
 template <typename E> struct Fa;
 template <> struct Fa<_Float16> {
-    typedef fa_f16x8 v8;
-    static __device__ __attribute__((always_inline)) fa_f32x4 mfma(v8 a, v8 b, fa_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+    typedef f16x8 v8;
+    static __device__ __attribute__((always_inline)) f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
     static __device__ __attribute__((always_inline)) uint32_t pk(float a, float b) { return pk_f16(a, b); }
     static __device__ __attribute__((always_inline)) float r(float v) { return f16r(v); }
 };
 template <> struct Fa<__bf16> {
-    typedef fa_bf16x8 v8;
-    static __device__ __attribute__((always_inline)) fa_f32x4 mfma(v8 a, v8 b, fa_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+    typedef bf16x8 v8;
+    static __device__ __attribute__((always_inline)) f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
     static __device__ __attribute__((always_inline)) uint32_t pk(float a, float b) { return pk_bf16(a, b); }
     static __device__ __attribute__((always_inline)) float r(float v) { return (float)(__bf16)v; }
 };
@@ -139,7 +136,7 @@ __global__ __launch_bounds__(256) void k_fa_gelu(const float* __restrict__ Y, E*
         *reinterpret_cast<uint2*>(G + i * 4) = make_uint2(Fa<E>::pk(gelu_fwd(v.x), gelu_fwd(v.y)), Fa<E>::pk(gelu_fwd(v.z), gelu_fwd(v.w)));
     }
 }
-// dY1_16 = fp16(fp16(dG) * gelu'(Y1)),  gelu'(x) = Phi(x) + x phi(x)
+// dY1_16 = fp16(fp16(dG) * gelu'(Y1)),  gelu'(x) = Phi(x) + x phi(x)   (not gelu_bwd of qv_common.h: __expf here, expf there)
 __device__ inline float gelu_grad(float x) {
     return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * __expf(-0.5f * x * x);
 }
@@ -196,7 +193,6 @@ __global__ __launch_bounds__(256) void k_fa_inf_rule(const FaInfTab t) {
 // at a fixed feature: eight 2-byte LDS reads each.  MFMA 16x16x32 layout: A fragment lane l = row l % 16, k 8 (l / 16) .. + 7; B the same with the
 // column; accumulator e of lane l = row 4 (l / 16) + e, column l % 16.
 constexpr int kFaWaves = 8, kFaScr = 40;   // scratch row stride in fp16 (32 + 8: 16-B aligned rows)
-__device__ inline void fa_wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }   // LDS is in order per wave; stop the compiler reordering
 template <int HD, typename E>
 __device__ inline typename Fa<E>::v8 fa_col8(const E* s, int row0, int col) {   // s[(row0 + j) * (HD + 8) + col], j = 0..7
     typename Fa<E>::v8 v;
@@ -260,14 +256,14 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
     // ---- dK, dV: 16 keys per wave tile, the queries in chunks of 32
     for (int kt = wave; kt < ntile; kt += kFaWaves) {
         const int k0 = kt * 16;
-        fa_f32x4 dV[ND], dK[ND];
+        f32x4 dV[ND], dK[ND];
 #pragma unroll
-        for (int jd = 0; jd < ND; ++jd) dV[jd] = dK[jd] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int jd = 0; jd < ND; ++jd) dV[jd] = dK[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int qc = 0; qc < Tp; qc += 32) {
-            fa_f32x4 st[2], dpt[2];
+            f32x4 st[2], dpt[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                st[u] = dpt[u] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+                st[u] = dpt[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kk = 0; kk < KK; ++kk) {
                     const int c = 32 * kk + 8 * g, qr = qc + 16 * u + r;
@@ -287,7 +283,7 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
                     scrS[(4 * g + e) * kFaScr + 16 * u + r] = (E)(p * (Fa<E>::r(dpt[u][e]) - dq));
                 }
             }
-            fa_wave_lds_fence();
+            wave_lds_fence();
             const v8 ap = *reinterpret_cast<const v8*>(scrP + r * kFaScr + 8 * g);
             const v8 as = *reinterpret_cast<const v8*>(scrS + r * kFaScr + 8 * g);
 #pragma unroll
@@ -295,7 +291,7 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
                 dV[jd] = Fa<E>::mfma(ap, fa_col8<HD>(sD, qc + 8 * g, 16 * jd + r), dV[jd]);
                 dK[jd] = Fa<E>::mfma(as, fa_col8<HD>(sQ, qc + 8 * g, 16 * jd + r), dK[jd]);
             }
-            fa_wave_lds_fence();
+            wave_lds_fence();
         }
 #pragma unroll
         for (int jd = 0; jd < ND; ++jd)
@@ -312,17 +308,17 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
     // ---- dQ: 16 queries per wave tile, S / dP / dS recomputed with the queries on the rows, the keys in chunks of 32
     for (int qt = wave; qt < ntile; qt += kFaWaves) {
         const int q0 = qt * 16;
-        fa_f32x4 dQ[ND];
+        f32x4 dQ[ND];
 #pragma unroll
-        for (int jd = 0; jd < ND; ++jd) dQ[jd] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int jd = 0; jd < ND; ++jd) dQ[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
         float lq[4], dq[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) { lq[e] = sL[q0 + 4 * g + e]; dq[e] = sDel[q0 + 4 * g + e]; }
         for (int kc = 0; kc < Tp; kc += 32) {
-            fa_f32x4 s[2], dp[2];
+            f32x4 s[2], dp[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                s[u] = dp[u] = (fa_f32x4){0.f, 0.f, 0.f, 0.f};
+                s[u] = dp[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kk = 0; kk < KK; ++kk) {
                     const int c = 32 * kk + 8 * g, kr = kc + 16 * u + r;
@@ -340,12 +336,12 @@ __global__ __launch_bounds__(kFaWaves * 64) void k_fa_attn_bwd_fused(const float
                     scrS[(4 * g + e) * kFaScr + 16 * u + r] = (E)(p * (Fa<E>::r(dp[u][e]) - dq[e]));
                 }
             }
-            fa_wave_lds_fence();
+            wave_lds_fence();
             const v8 as = *reinterpret_cast<const v8*>(scrS + r * kFaScr + 8 * g);
 #pragma unroll
             for (int jd = 0; jd < ND; ++jd)
                 dQ[jd] = Fa<E>::mfma(as, fa_col8<HD>(sK, kc + 8 * g, 16 * jd + r), dQ[jd]);
-            fa_wave_lds_fence();
+            wave_lds_fence();
         }
 #pragma unroll
         for (int jd = 0; jd < ND; ++jd)
@@ -363,9 +359,7 @@ static size_t fa_attn_lds_bytes(int T, int HD) {
 }
 template <int HD, typename E>
 static void launch_fa_attn_fused(const float* qkv, const void* O16, const float* lse, const float* dO, int B, int T, int H, int D, void* dqkv16, hipStream_t st) {
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_fa_attn_bwd_fused<HD, E>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)fa_attn_lds_bytes(224, HD)),
-                        true);
+    static bool once = (allow_lds(k_fa_attn_bwd_fused<HD, E>, fa_attn_lds_bytes(224, HD)), true);
     (void)once;
     k_fa_attn_bwd_fused<HD, E><<<B * H, kFaWaves * 64, fa_attn_lds_bytes(T, HD), st>>>(qkv, reinterpret_cast<const E*>(O16), lse, dO, T, H, D,
                                                                                        1.0f / sqrtf((float)HD), reinterpret_cast<E*>(dqkv16));

@@ -13,11 +13,10 @@
 #include "../../include/qatvit.h"
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 
 namespace qv {
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- weight (hi, lo) pairs, as stored and transposed
 // (the weights change every optimizer step: rebuilt by every forward; hiT / loT are the B operands of the dgrad GEMMs)

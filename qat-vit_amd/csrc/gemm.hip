@@ -21,66 +21,15 @@
 #include <stdlib.h>
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 #include "qv_qparams.h"
 
 namespace qv {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-// XCD-aware, bijective block-id remap: blocks b and b+8 share an XCD (and its L2), so give each
-// XCD a contiguous run of tiles (neighbouring tiles share an A row panel).
-__device__ inline int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-__device__ inline __amdgpu_buffer_rsrc_t make_rsrc(const void* base, int64_t bytes) {
-    // wave-uniform descriptor: raw buffer, out-of-range (>= bytes) lanes load 0
-    const uint32_t n = bytes > 0xffffffffll ? 0xffffffffu : (uint32_t)bytes;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt: between epilogue slabs that is a wait for every
-// global store of the slab just written to be acknowledged (and for LDS-DMA that was deliberately started early).
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int N> __device__ inline void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 20, "vmcnt immediate");
-#define QV_W(n) if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-    QV_W(0); QV_W(1); QV_W(2); QV_W(3); QV_W(4); QV_W(5); QV_W(6); QV_W(7); QV_W(8); QV_W(9); QV_W(10);
-    QV_W(11); QV_W(12); QV_W(13); QV_W(14); QV_W(15); QV_W(16); QV_W(17); QV_W(18); QV_W(19); QV_W(20);
-#undef QV_W
-}
-
-// LDS-DMA through inline asm.  The TN kernel reads its fragments with the ds_read_tr16_b64 builtin; hipcc 7.2 cannot prove that such a
-// read does not alias the LDS destination of a __builtin_amdgcn_raw_ptr_buffer_load_lds still in flight (another ring stage) and puts
-// an s_waitcnt vmcnt(0) between every DMA issue and the next fragment read: no prefetch overlap at all.  An asm DMA is invisible to
-// that bookkeeping; completion is counted by hand (wait_vmcnt + s_barrier), exactly as the ring protocol requires anyway.
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-__device__ inline v4i32 make_rsrc_v(const void* base, int64_t bytes) {
-    const uint64_t b = reinterpret_cast<uint64_t>(base);
-    const uint32_t n = bytes > 0xffffffffll ? 0xffffffffu : (uint32_t)bytes;
-    return (v4i32){(int)(uint32_t)b, (int)(uint32_t)(b >> 32), (int)n, 0x00020000};
-}
-__device__ inline void dma16_asm(v4i32 rsrc, const char* lds_dst, uint32_t voff) {
-    const uint32_t m = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>((lds_void*)lds_dst));
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(m), "s"(rsrc)
-                 : "memory");
-}
+// (vector types, lds_barrier / wait_vmcnt, make_rsrc / make_rsrc_v / dma16_asm / load16_asm, xcd_remap and the LDS image offsets nt_off / nt_off32 / tn_off: qv_device.h)
 
 // ============================================================================ NT
-// LDS image of a [128 rows][64 bf16] tile: 128-B rows, 16-B chunk index XOR (row & 7).
-__device__ inline int nt_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
 struct NTArgs {
     const __bf16* A0;     // [M,lda] hi part (or the only part)
     const __bf16* A1;     // [M,lda] lo part (TA == 2)
@@ -655,7 +604,6 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                     if (p.post_colscale) cs = *reinterpret_cast<const float4*>(p.post_colscale + n0 + 4 * c4);
                     const uint32_t cd[4] = {c2.x & 0xffffu, c2.x >> 16, c2.y & 0xffffu, c2.y >> 16};
                     const float cv[4] = {v.x, v.y, v.z, v.w}, sv[4] = {cs.x, cs.y, cs.z, cs.w};
-                    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
                     bf16x4 oh, ol;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -701,7 +649,6 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                 } else if constexpr (PM == 2) {
                     const float cv[4] = {v.x, v.y, v.z, v.w};
                     if (p.out_f16) {   // (uniform) the fp16 teacher forward: the pair (or, out_lo == NULL, the hi part alone) in fp16
-                        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
                         f16x4 oh, ol;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -712,7 +659,6 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                         *reinterpret_cast<f16x4*>(p.out_hi + off) = oh;
                         if (p.out_lo) *reinterpret_cast<f16x4*>(p.out_lo + off) = ol;
                     } else {
-                        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
                         bf16x4 oh, ol;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -768,12 +714,6 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
             stat_atomic(p.stats, p.stat_slots, mn, mx);
         }
     }
-}
-
-// LDS image of a BK = 32 tile: two 64-B tile rows share one 128-B LDS row; chunk index ((row & 1) * 4 + k-chunk) XOR (LDS row & 7).
-__device__ inline int nt_off32(int row, int chunk) {
-    const int R = row >> 1;
-    return R * 128 + (((((row & 1) << 2) | chunk) ^ (R & 7)) << 4);
 }
 
 // F16: both operands hold fp16 bit patterns (a float A operand as an fp16 (hi, lo) pair pre-scaled by a power of two, the weight integers
@@ -953,20 +893,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void k_gemm_nt(
 #endif
 }
 
-// register-destination loads beside LDS-DMA: inline asm (hipcc waits vmcnt(0) for every ordinary load result while a DMA is in flight), counted by hand
-__device__ inline v4i32 load16_asm(v4i32 rsrc, uint32_t voff) {
-    v4i32 v;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(v) : "v"(voff), "s"(rsrc) : "memory");
-    return v;
-}
-// the wait that makes the asm-loaded fragments valid: nothing may be scheduled across it (hipcc moves register-only MFMAs past an asm
-// s_waitcnt despite the memory clobber; sched_barrier(0) is the fence - cdna_hip_programming.md rule 18)
-template <int N> __device__ inline void wait_vmcnt_b() {
-    wait_vmcnt<N>();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-
 // ============================================================================ NT, A operand from uint8 codes through a table
 // fc2 forward: its A operand gelu(fq(fc1 output)) takes at most 256 values, so fc1's storing pass writes ONE byte per element (the grid
 // index) and a 256-entry table of packed fp16 (hi | lo << 16) pairs instead of the two 2-byte planes; here every k-step's [208][32] code tile
@@ -1057,7 +983,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_ac(const NTArgs p) {
     auto step = [&](int kt, v4i32& ccur, v4i32& cnext) {   // ccur = codes(kt+1), cnext receives codes(kt+2)
         if (kt + 1 < nk) wait_vmcnt_b<NPW>();
         else wait_vmcnt_b<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // tile kt: B landed, A expanded by everyone; everyone left stage (kt-1)%3
+        lds_barrier();   // tile kt: B landed, A expanded by everyone; everyone left stage (kt-1)%3
         const bool more = kt + 2 < nk, conv = carrier && kt + 1 < nk;
         if (more && carrier) cnext = load_codes(kt + 2);
         const char* st = smem + (kt % NSTAGE) * STAGE;
@@ -1106,11 +1032,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_ac(const NTArgs p) {
     nt_epilogue<1, WN, TM, TNT, 64, PM, LDSB, false>(p, acc, smem, m0, n0, tid, lane, wave, 0, wave, r, g);
 }
 
-
-template <typename K>
-static void allow_lds(K kernel, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 // one kernel instantiation per epilogue variant (NTArgs::pm)
 template <int TA, int NS, int WM, int TM, int TB, int WN, int TNT, int BK, bool I8 = false, bool F16 = false>
@@ -1376,9 +1297,7 @@ int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
 }
 
 // ============================================================================ TN (wgrad)
-// LDS image of a [64 rows (tokens)][128 bf16] tile for ds_read_b64_tr_b16: 256-B rows, chunk XOR.
-__device__ inline int tn_sw(int row) { return ((row & 3) << 1) | (((row >> 3) & 1) << 3); }
-__device__ inline int tn_off(int row, int chunk) { return row * 256 + ((chunk ^ tn_sw(row)) << 4); }
+// (LDS image of a [64 rows (tokens)][128 bf16] tile for ds_read_b64_tr_b16 - tn_sw / tn_off: qv_device.h)
 
 struct TNArgs {
     const __bf16* P0;   // [M, ldp] hi part of dY
@@ -1413,7 +1332,6 @@ __device__ inline bf16x8 tr_frag(const char* img, int row0, int col0, int lane) 
     const int g = lane >> 4, idx = lane & 15, q = idx >> 2, pp = idx & 3;
     const int row = row0 + 8 * g + q;
     const int chunk = (col0 >> 3) + (pp >> 1);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + row * ROWB + ((chunk ^ tn_sw(row)) << 4) + (pp & 1) * 8));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (row + 4) * ROWB + ((chunk ^ tn_sw(row + 4)) << 4) + (pp & 1) * 8));
     // whole-vector bit cast: per-element short->__bf16 inserts are miscompiled by hipcc 7.2 (every element becomes lo[0])
@@ -1593,7 +1511,7 @@ __global__ __launch_bounds__(WM * WNK * 64) void k_gemm_tn(const TNArgs p) {
             else if (young == 2) wait_vmcnt<2>();
             else if (young == 1) wait_vmcnt<1>();
             else wait_vmcnt<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // A: ... and everyone's share of the images of tile s is written
+            lds_barrier();   // A: ... and everyone's share of the images of tile s is written
             if (s + 2 < nsteps) issue_p(s + 2);          // into the P stage step s-1 read
             if (s + 3 < nsteps) issue_c(s + 3);          // into the code buffer the expansion of step s-1 consumed
             const char* st = smem + (s % 3) * QC_PST;
@@ -1603,7 +1521,7 @@ __global__ __launch_bounds__(WM * WNK * 64) void k_gemm_tn(const TNArgs p) {
             for (int t = 0; t < TQ; ++t)
 #pragma unroll
                 for (int j = 0; j < TNT; ++j) qf[t][j] = tr_frag<QROWB>(sq + t * IMGQ, 0, wn * (16 * TNT) + 16 * j, lane);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // B: every wave holds its Q fragments: the images are free
+            lds_barrier();   // B: every wave holds its Q fragments: the images are free
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 if (s + 1 < nsteps) {   // tile s+1's images, between the MFMA groups: round i's gathers here, its pack + stores one group later
@@ -1873,7 +1791,6 @@ __global__ __launch_bounds__(512) void k_gemm_tn_q8(const TNArgs p) {
         for (int k = 0; k < 16; ++k) tab[(tid & 255) * 32 + 16 * (tid >> 8) + k] = ent;
     }
     const uint32_t tab_lane = (uint32_t)(TAB + (lane & 31) * 4);
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     // One 32-token substep's operands in registers: TM P fragments + the bias fragment + TNT raw byte fragments (Ops), expanded to fp16 by x1 / x2.
     // The loop is software-pipelined by hand over two register sets: the LDS reads of substep t + 1 are issued in front of the MFMAs of substep t, the table
     // gathers (MODE 1) in the middle of them - the hipcc schedule of the plain loop kept ONE fragment in flight (2 reads per 3 MFMAs, every fragment a stall).
@@ -1938,7 +1855,7 @@ __global__ __launch_bounds__(512) void k_gemm_tn_q8(const TNArgs p) {
         if (NSTAGE >= 3 && s + NSTAGE - 2 < nsteps) wait_vmcnt<(NSTAGE - 2) * NDMA>();
         else wait_vmcnt<0>();
         // (every LDS read of the stage this step's DMA overwrites has returned: they were issued a substep of MFMAs ago.  MODE 1: the first barrier publishes the table)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         if (s + NSTAGE - 1 < nsteps) issue(s + NSTAGE - 1);
         if (s == 1) QV_NT_STAMP(100 + MODE, 1);
         const char* st = smem + (s % NSTAGE) * STAGE;
@@ -2223,7 +2140,6 @@ __global__ __launch_bounds__(512) void k_tn_stream(const TNStreamArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave;
     const int w = xcd_remap(blockIdx.x, gridDim.x);
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     f16x8 ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (_Float16)1.0f;
@@ -2266,7 +2182,7 @@ __global__ __launch_bounds__(512) void k_tn_stream(const TNStreamArgs a) {
             }
         };
         // every wave has left the previous segment's images (and table) before this segment's DMA / table fill overwrites them
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
 #pragma unroll
         for (int s = 0; s < NSTAGE - 1; ++s)
             if (s < nsteps) issue(s);
@@ -2359,7 +2275,7 @@ __global__ __launch_bounds__(512) void k_tn_stream(const TNStreamArgs a) {
         for (int s = 0; s < nsteps; ++s) {
             if (NSTAGE >= 3 && s + NSTAGE - 2 < nsteps) wait_vmcnt<(NSTAGE - 2) * NDMA>();
             else wait_vmcnt<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            lds_barrier();
             if (s + NSTAGE - 1 < nsteps) issue(s + NSTAGE - 1);
             if (s == 1 && u == u_begin) QV_NT_STAMP(200 + MODE, 1);
             const char* st = smem + (s % NSTAGE) * STAGE;

@@ -35,13 +35,11 @@
 #include <type_traits>
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 #include "qv_qparams.h"
 
 namespace qv {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct I8StripArgs {
     const int8_t* A;        // [M, lda] q - center
@@ -81,12 +79,7 @@ struct I8StripArgs {
     QpLate ln_late;            // ln_late.stats set -> the LayerNorm-output quantizer is resolved here (workgroup 0 publishes it); else its ready values are read from aqp
 };
 
-// LDS image of one [208][64 B] k-tile of A: two 64-B tile rows share one 128-B LDS row; chunk ((row & 1) * 4 + k-chunk) XOR (LDS row & 7)
-__device__ inline int strip_off(int row, int chunk) {
-    const int R = row >> 1;
-    return R * 128 + (((((row & 1) << 2) | chunk) ^ (R & 7)) << 4);
-}
-__device__ inline void strip_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (LDS image of one [208][64 B] k-tile of A: strip_off, qv_device.h)
 
 #ifdef QV_STRIP_EXPERIMENTS
 #define QV_STAMP() stamp()
@@ -196,7 +189,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
         // did), or ready in aqp.  Everything below takes scale and zero point from sQp - never from global memory workgroup 0 may be writing
         if (p.ln_late.stats) qp_late_compute(p.ln_late, sQp);
         else if (tid == 0) { sQp[0] = p.aqp[0]; sQp[1] = p.aqp[1]; sQp[2] = p.aqp[2]; }
-        strip_lds_barrier();
+        lds_barrier();
         QV_STAMP();   // quantizer resolved
     }
     const float a_s = LN ? sQp[0] : *p.s1, a_inv = LN ? sQp[1] : 0.f, a_zp = LN ? sQp[2] : p.aqp[2];
@@ -421,7 +414,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
                 }
                 // the wave's own LDS operations execute in order: the reads below see the writes above without a barrier (the wait + clobber keeps
                 // the compiler from reordering them)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wave_lds_fence();
                 const int row0 = m0 + 16 * c0;
 #pragma unroll
                 for (int k3 = 0; k3 < TNT; ++k3) {
@@ -465,7 +458,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
         mn = wave_min(mn);
         mx = wave_max(mx);
         if (lane == 0) { sRed[wave] = mn; sRed[16 + wave] = mx; }
-        strip_lds_barrier();
+        lds_barrier();
         if (tid == 0) {
 #pragma unroll
             for (int w = 1; w < NWV; ++w) { mn = fminf(mn, sRed[w]); mx = fmaxf(mx, sRed[16 + w]); }
@@ -478,7 +471,7 @@ template <int MODE, int NTL, int NWV, bool R255, int TM, int KT>
 static void strip_launch_r(const I8StripArgs& a, hipStream_t st) {
     constexpr int kLds = KT * 16 * TM * 64 + 3 * NTL * 384 * 4 + (MODE == 3 ? 512 : NWV * (64 * (384 / NWV) + 64 * 16)) + 16;   // (+ the output quantizer's {scale, 1 / scale, zp})
     static_assert(kLds <= 160 * 1024, "strip + constants + staging patches exceed the LDS");
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_i8_strip<MODE, NTL, NWV, R255, TM, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds), true);
+    static bool once = (allow_lds(k_i8_strip<MODE, NTL, NWV, R255, TM, KT>, kLds), true);
     (void)once;
     k_i8_strip<MODE, NTL, NWV, R255, TM, KT><<<dim3(cdiv(a.M, 16 * TM), a.N / (NTL * 384)), NWV * 64, kLds, st>>>(a);
 }
@@ -511,7 +504,7 @@ static void strip_launch_ln(const I8StripArgs& a0, hipStream_t st) {
 #endif
     constexpr int kLds = KT * 16 * TM * 64 + 3 * NTL * 384 * 4 + 512 + 16;
     static_assert(kLds <= 160 * 1024, "strip + constants exceed the LDS");
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_i8_strip<3, NTL, 8, false, TM, KT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds), true);
+    static bool once = (allow_lds(k_i8_strip<3, NTL, 8, false, TM, KT, true>, kLds), true);
     (void)once;
     k_i8_strip<3, NTL, 8, false, TM, KT, true><<<dim3(cdiv(a.M, 16 * TM), 1), 8 * 64, kLds, st>>>(a);
 }

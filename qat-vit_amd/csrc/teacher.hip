@@ -12,18 +12,11 @@
 #include <stdlib.h>
 
 #include "qv_common.h"
+#include "qv_device.h"
 #include "qv_kernels.h"
 
 namespace qv {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // (hi, lo) pair of four values: bf16 (8 + 8 significant bits) or, f16 != 0 (uniform), fp16 (11 + 11; unscaled: the teacher's GEMM inputs - LayerNorm
 // outputs, attention outputs, GELU outputs, image patches - are far inside fp16's range).  lo == nullptr: the one-pass form keeps the hi part only.
 // BF1: the bf16 one-plane form (the float step's bf16 form; f16 == 0, lo unused): bf16(v) only.
@@ -69,8 +62,7 @@ __global__ __launch_bounds__(256) void k_patches_split(const float* __restrict__
 
 // MODE 0: x[b,0,:] = cls + pos[0]; x[b,1+p,:] = Y[b*np+p,:] + pos[1+p,:]     MODE 1: x = x_prev + Y
 // then h = LayerNorm(x) written as a (hi, lo) pair (one wave per row, row kept in registers: single pass over HBM)
-__device__ inline void t_pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
-// NV = ceil(D / 256) column groups per lane.  All loads of the row are issued first, branch-free and pinned (a lane past D reads column 0
+// NV = ceil(D / 256) column groups per lane.  All loads of the row are issued first, branch-free and pinned (pin4; a lane past D reads column 0
 // and is masked out): one `if (c < D)` region per group let LLVM sink each group's loads to its uses - three dependent HBM round trips
 // per row at D = 768.  gamma / beta once per thread.
 // STATS (the observe-only student forward): min / max of the fp32 LayerNorm outputs, one wave reduction and one accumulator atomic per wave
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict_
             y[j] = *reinterpret_cast<const float4*>(ysrc + cc[j]);
         }
 #pragma unroll
-        for (int j = 0; j < NV; ++j) { t_pin4(v[j]); t_pin4(y[j]); }
+        for (int j = 0; j < NV; ++j) { pin4(v[j]); pin4(y[j]); }
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -158,11 +150,10 @@ static void launch_resid_ln_split(int grid, hipStream_t st, int D, A... a) {
     else k_resid_ln_split<MODE, 3, STATS, BF1><<<grid, 256, 0, st>>>(a...);
 }
 
-__device__ inline float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __global__ __launch_bounds__(256) void k_gelu_split(const float* __restrict__ Y, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const float4 v = reinterpret_cast<const float4*>(Y)[i];
-        st_split4(hi, lo, i * 4, gelu_f(v.x), gelu_f(v.y), gelu_f(v.z), gelu_f(v.w));
+        st_split4(hi, lo, i * 4, gelu_fwd(v.x), gelu_fwd(v.y), gelu_fwd(v.z), gelu_fwd(v.w));
     }
 }
 
@@ -198,51 +189,13 @@ __global__ __launch_bounds__(256) void k_teacher_head(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------- float attention (no quantisation): 3-pass products
-template <int HD> __device__ inline int t_row_off(int row, int chunk) {
-    if constexpr (HD == 64) return row * 128 + ((chunk ^ (row & 7)) << 4);
-    else return row * (HD * 2) + (chunk << 4);
-}
-template <int HD> __device__ inline int t_tr_off(int row, int chunk) {
-    if constexpr (HD == 64) return row * 128 + ((chunk ^ (((row >> 1) & 3) << 1)) << 4);
-    else return row * (HD * 2) + (chunk << 4);
-}
-template <int HD> __device__ inline bf16x8 t_tr_frag2(const char* img, int tokA, int tokB, int col0, int lane) {
-    const int g = lane >> 4, idx = lane & 15, q = idx >> 2, pp = idx & 3;
-    const int chunk = (col0 >> 3) + (pp >> 1);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + t_tr_off<HD>(tokA + 4 * g + q, chunk) + (pp & 1) * 8));
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + t_tr_off<HD>(tokB + 4 * g + q, chunk) + (pp & 1) * 8));
-    const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
+// (K as a row_off image, V as a tr_off image read with tr_frag2, the output re-tiled with wave_retile8: qv_device.h)
+// (per-element casts; attn.hip's load_split8 forms the same bits through split_pair, with other instructions)
 __device__ inline void t_load_split8(const float* p, bf16x8& hi, bf16x8& lo) {
     const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
     for (int j = 0; j < 8; ++j) { hi[j] = (__bf16)v[j]; lo[j] = (__bf16)(v[j] - (float)hi[j]); }
-}
-
-// half-tile output re-tiling through a private LDS scratch (same scheme as attn.hip: 16-B row-major bf16 stores instead of 2-B scatters)
-template <int HD>
-__device__ inline bool t_wave_retile8(float* sO, const f32x4 (&acc)[HD / 16], float scale, int lane, int half, float (&out)[8], int& row, int& c8) {
-    constexpr int LDO = HD + 4;
-    const int r = lane & 15, g = lane >> 4;
-    if ((g >> 1) == half) {
-#pragma unroll
-        for (int jd = 0; jd < HD / 16; ++jd)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sO[(4 * (g & 1) + e) * LDO + 16 * jd + r] = acc[jd][e] * scale;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    row = lane / (HD / 8);
-    c8 = lane % (HD / 8);
-    const bool active = row < 8;
-    if (active) {
-        const float4 v0 = *reinterpret_cast<const float4*>(sO + row * LDO + 8 * c8), v1 = *reinterpret_cast<const float4*>(sO + row * LDO + 8 * c8 + 4);
-        out[0] = v0.x; out[1] = v0.y; out[2] = v0.z; out[3] = v0.w; out[4] = v1.x; out[5] = v1.y; out[6] = v1.z; out[7] = v1.w;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return active;
 }
 
 constexpr int kTW = 8;  // waves per workgroup
@@ -271,7 +224,7 @@ __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __rest
             ka[it] = pk[0]; kb[it] = pk[1]; va[it] = pv[0]; vb[it] = pv[1];
         }
 #pragma unroll
-        for (int it = 0; it < ITERS; ++it) { t_pin4(ka[it]); t_pin4(kb[it]); t_pin4(va[it]); t_pin4(vb[it]); }
+        for (int it = 0; it < ITERS; ++it) { pin4(ka[it]); pin4(kb[it]); pin4(va[it]); pin4(vb[it]); }
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int i = threadIdx.x + it * kTW * 64, tok = i / CH, ch = i % CH;
@@ -286,10 +239,10 @@ __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __rest
                     kh[j] = (__bf16)k1; kl[j] = (__bf16)(k1 - (float)kh[j]);
                     vh[j] = (__bf16)v1; vl[j] = (__bf16)(v1 - (float)vh[j]);
                 }
-                *reinterpret_cast<bf16x8*>(sKh + t_row_off<HD>(tok, ch)) = kh;
-                *reinterpret_cast<bf16x8*>(sKl + t_row_off<HD>(tok, ch)) = kl;
-                *reinterpret_cast<bf16x8*>(sVh + t_tr_off<HD>(tok, ch)) = vh;
-                *reinterpret_cast<bf16x8*>(sVl + t_tr_off<HD>(tok, ch)) = vl;
+                *reinterpret_cast<bf16x8*>(sKh + row_off<HD>(tok, ch)) = kh;
+                *reinterpret_cast<bf16x8*>(sKl + row_off<HD>(tok, ch)) = kl;
+                *reinterpret_cast<bf16x8*>(sVh + tr_off<HD>(tok, ch)) = vh;
+                *reinterpret_cast<bf16x8*>(sVl + tr_off<HD>(tok, ch)) = vl;
             }
         }
     }
@@ -307,8 +260,8 @@ __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __rest
             s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
-                const bf16x8 kh = *reinterpret_cast<const bf16x8*>(sKh + t_row_off<HD>(16 * j + r, 4 * kk + g));
-                const bf16x8 kl = *reinterpret_cast<const bf16x8*>(sKl + t_row_off<HD>(16 * j + r, 4 * kk + g));
+                const bf16x8 kh = *reinterpret_cast<const bf16x8*>(sKh + row_off<HD>(16 * j + r, 4 * kk + g));
+                const bf16x8 kl = *reinterpret_cast<const bf16x8*>(sKl + row_off<HD>(16 * j + r, 4 * kk + g));
                 s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh[kk], s[j], 0, 0, 0);
                 s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[kk], s[j], 0, 0, 0);
                 s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[kk], s[j], 0, 0, 0);
@@ -348,8 +301,8 @@ __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __rest
             }
 #pragma unroll
             for (int jd = 0; jd < ND; ++jd) {
-                const bf16x8 vh = t_tr_frag2<HD>(sVh, 32 * ks, 32 * ks + 16, 16 * jd, lane);
-                const bf16x8 vl = t_tr_frag2<HD>(sVl, 32 * ks, 32 * ks + 16, 16 * jd, lane);
+                const bf16x8 vh = tr_frag2<HD>(sVh, 32 * ks, 32 * ks + 16, 16 * jd, lane);
+                const bf16x8 vl = tr_frag2<HD>(sVl, 32 * ks, 32 * ks + 16, 16 * jd, lane);
                 o[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vh, o[jd], 0, 0, 0);
                 o[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl, vh, o[jd], 0, 0, 0);
                 o[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vl, o[jd], 0, 0, 0);
@@ -359,7 +312,7 @@ __global__ __launch_bounds__(kTW * 64) void k_attn_fwd_float(const float* __rest
         for (int half = 0; half < 2; ++half) {
             float ov[8];
             int orow, oc;
-            const bool act = t_wave_retile8<HD>(sO, o, 1.0f, lane, half, ov, orow, oc);
+            const bool act = wave_retile8<HD>(sO, o, 1.0f, lane, half, ov, orow, oc);
             const int qq = qt * 16 + 8 * half + orow;
             if (act && qq < T) {
                 const int64_t off = ((int64_t)b * T + qq) * D + h * HD + 8 * oc;
@@ -393,8 +346,7 @@ static int rows_grid_t(int64_t rows) {
 template <int HD, int NKT, bool BF1>
 static void launch_attn_float_k(const float* qkv, int B, int T, int H, int D, void* O_hi, void* O_lo, hipStream_t st, int f16, float* lse) {
     const size_t lds = (size_t)4 * NKT * 16 * HD * 2 + (size_t)kTW * 8 * (HD + 4) * sizeof(float);
-    static bool once = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_fwd_float<HD, NKT, BF1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        true);
+    static bool once = (allow_lds(k_attn_fwd_float<HD, NKT, BF1>, lds), true);
     (void)once;
     k_attn_fwd_float<HD, NKT, BF1><<<B * H, kTW * 64, lds, st>>>(qkv, B, T, H, D, 1.0f / sqrtf((float)HD), reinterpret_cast<__bf16*>(O_hi),
                                                                  reinterpret_cast<__bf16*>(O_lo), f16, lse);
