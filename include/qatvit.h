@@ -494,6 +494,37 @@ int qatvit_image_table(const float* mean_host, const float* std_host, float* tab
 int qatvit_image_batch(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                        const float* table, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.
+ * Replaces: evaluate_fp32 (qat_trainer.py:49-61: argmax, ==, .sum().item() per batch), _eval_acc_limited of the Optuna objective,
+ *   evaluate_model (evaluator.py) and the accuracy the comparator reports per checkpoint.
+ *
+ * logits [B, C] of `dtype` (QATVIT_EVAL_F32 / _F16 / _BF16), row stride `ld` >= C in elements (elements past C in a row are never read);
+ * labels int64 [B].  Per row:
+ *   pred = torch.argmax's answer: the index of the first NaN if the row has one, otherwise of the first maximum (+0 == -0); compared on the
+ *     stored values (widening fp16 / bf16 to fp32 is exact and monotone).
+ *   A label outside [0, C) is counted in bad_labels and takes no part in correct, the loss, the matrix or other_correct; nothing is read or
+ *     written through it.
+ *   CE = logsumexp(row) - row[label] in fp32, max-subtracted (no smoothing): finite -> added to loss_sum and counted in loss_rows,
+ *     otherwise counted in nonfinite_rows.
+ *   confusion (int64 [C, C], or NULL): confusion[label * C + pred] += 1.
+ *   other (fp32, row stride other_ld >= C, or NULL): a second model's logits for the same samples - row b of [B, C] when other_index is NULL,
+ *     else row other_index[b] of a per-sample table [other_rows, C] (the layout of a teacher logit table).  An index outside [0, other_rows)
+ *     is counted in bad_index and reads nothing; every other row counts in other_rows_seen, in agree when the two argmaxes are equal (labels
+ *     play no part in that) and in other_correct when the label is valid and other's argmax equals it.
+ * state: QATVIT_EVAL_STATE_WORDS 8-byte words, 8-byte aligned, that the caller zeroes once per evaluation and every call ADDS to:
+ *   int64 [0] total [1] correct [2] bad_labels [3] nonfinite_rows [4] other_rows_seen [5] agree [6] other_correct [7] bad_index [8] loss_rows,
+ *   double [9] loss_sum.  The integer counts are exact and do not depend on launch or block order; loss_sum is accumulated in double in arrival
+ *   order, so its last bits can differ between runs.  Nothing synchronises with the host.  1 <= B < 2^30, 2 <= C < 2^30.
+ */
+#define QATVIT_EVAL_F32 0
+#define QATVIT_EVAL_F16 1
+#define QATVIT_EVAL_BF16 2
+#define QATVIT_EVAL_STATE_WORDS 10
+int qatvit_eval_accumulate(const void* logits, int32_t dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes,
+                           const float* other, int64_t other_ld, const int64_t* other_index, int64_t other_rows, void* state,
+                           int64_t* confusion, void* stream);
+
 /* Measurement hooks (bench.py): bracket every launch of one GEMM class inside the steps of ONE engine - identified by its workspace
  * pointer, so engines in the same process do not see each other's sessions - with HIP events on the launch stream.
  * kind: 1 = NT with split (hi+lo) A operand and the plain epilogue (proj / fc2 forward, proj dgrad), 2 = NT with grid A operand on int8 MFMA, plain

@@ -303,6 +303,26 @@ int qatvit_attn_backward(const float* qkv, const float* qp, int32_t qmin, int32_
     return 0;
 }
 
+int qatvit_eval_accumulate(const void* logits, int32_t dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes, const float* other,
+                           int64_t other_ld, const int64_t* other_index, int64_t other_rows, void* state, int64_t* confusion, void* stream) {
+    static_assert(sizeof(EvalState) == 8 * QATVIT_EVAL_STATE_WORDS, "QATVIT_EVAL_STATE_WORDS mirrors EvalState");
+    QV_CHECK_ARG(logits && labels && state, "qatvit_eval_accumulate: null pointer argument");
+    QV_CHECK_ARG(batch >= 1 && batch < (1ll << 30), "qatvit_eval_accumulate: batch %lld (1 .. 2^30 - 1)", (long long)batch);
+    QV_CHECK_ARG(classes >= 2 && classes < (1ll << 30), "qatvit_eval_accumulate: classes %lld (2 .. 2^30 - 1)", (long long)classes);
+    QV_CHECK_ARG(ld >= classes, "qatvit_eval_accumulate: ld %lld is less than classes %lld", (long long)ld, (long long)classes);
+    QV_CHECK_ARG(dtype == QATVIT_EVAL_F32 || dtype == QATVIT_EVAL_F16 || dtype == QATVIT_EVAL_BF16,
+                 "qatvit_eval_accumulate: unknown dtype code %d (0 = fp32, 1 = fp16, 2 = bf16)", dtype);
+    QV_CHECK_ARG(other || !other_index, "qatvit_eval_accumulate: other_index given without other");
+    QV_CHECK_ARG(!other || other_ld >= classes, "qatvit_eval_accumulate: other_ld %lld is less than classes %lld", (long long)other_ld, (long long)classes);
+    QV_CHECK_ARG(!other_index || other_rows >= 1, "qatvit_eval_accumulate: other_rows %lld (at least 1 with an index)", (long long)other_rows);
+    QV_CHECK_ARG(((uintptr_t)state & 7) == 0 && ((uintptr_t)confusion & 7) == 0, "qatvit_eval_accumulate: misaligned state or confusion pointer");
+    if (launch_eval_accumulate(logits, dtype, ld, labels, batch, classes, other, other_ld, other_index, other_rows, static_cast<EvalState*>(state), confusion,
+                               (hipStream_t)stream))
+        return 1;
+    QV_CHECK_LAUNCH("qatvit_eval_accumulate");
+    return 0;
+}
+
 static int image_shape_ok(const char* who, int32_t S, int32_t D) {
     QV_CHECK_ARG(S >= 8 && S <= D, "%s: source size %d is outside 8 .. output size %d (downscaling is not supported)", who, S, D);
     QV_CHECK_ARG(D % 4 == 0 && D <= kImgMaxD, "%s: output size %d must be a multiple of 4, at most %d", who, D, kImgMaxD);

@@ -310,6 +310,26 @@ int image_resize_coeffs(int src, int dst, int32_t* xmin, int32_t* ntaps, int32_t
 void image_table(const float* mean, const float* stdv, float* table);                      // host only
 int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table, float* out,
                        hipStream_t st);
+// eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
+// (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
+// launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.
+struct EvalState {
+    int64_t total;            // rows seen
+    int64_t correct;          // label in [0, C) and argmax == label
+    int64_t bad_labels;       // label outside [0, C): no part in correct / loss / confusion / other_correct
+    int64_t nonfinite_rows;   // valid label, but the row's cross-entropy is NaN or +-inf: not added to loss_sum
+    int64_t other_rows_seen;  // rows whose second-opinion row was read
+    int64_t agree;            // of those: argmax == argmax of the second opinion
+    int64_t other_correct;    // of those: label in [0, C) and the second opinion's argmax == label
+    int64_t bad_index;        // other_index outside [0, other_rows): nothing read through it
+    int64_t loss_rows;        // rows added to loss_sum
+    double loss_sum;
+};
+constexpr int kEvalCounters = 9;
+static_assert(sizeof(EvalState) == 8 * (kEvalCounters + 1), "EvalState is ten 8-byte words");
+// dtype: 0 fp32, 1 fp16, 2 bf16 (anything else returns 1 without a launch); other / other_index / confusion may be null
+int launch_eval_accumulate(const void* logits, int dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes, const float* other,
+                           int64_t other_ld, const int64_t* other_index, int64_t other_rows, EvalState* state, int64_t* confusion, hipStream_t st);
 // grid of the float step's flat elementwise kernels (float_step.hip, float_amp.hip)
 inline int flat_grid_fs(int64_t n) {
     int64_t b = (n + 255) / 256;
