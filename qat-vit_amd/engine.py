@@ -22,7 +22,7 @@ import os
 import time
 import warnings
 import weakref
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -91,6 +91,20 @@ class FlatGradLayout:
         return out
 
 
+def mean_op(pg):
+    """(reduce op, divisor or None) of an average over the group: AVG on nccl; gloo has no AVG: SUM, then divide by the group size."""
+    if dist.get_backend(pg) == "nccl":
+        return dist.ReduceOp.AVG, None
+    return dist.ReduceOp.SUM, dist.get_world_size(pg)
+
+
+def allreduce_mean(tensor: torch.Tensor, pg) -> None:
+    op, div = mean_op(pg)
+    dist.all_reduce(tensor, op=op, group=pg)
+    if div:
+        tensor.div_(div)
+
+
 def staged_backward_allreduce(flat: torch.Tensor, layout: FlatGradLayout, bucket_bytes: int, pg,
                               run_stages: Callable[[int, int], None], exposed: Optional[list] = None) -> None:
     """Run the backward stage by stage; as soon as a bucket's stages have been enqueued, start its all-reduce
@@ -98,21 +112,20 @@ def staged_backward_allreduce(flat: torch.Tensor, layout: FlatGradLayout, bucket
     with every slice averaged over the group (the caller's stream waits on the collectives).
 
     Replaces the Reducer of ``DDP(prepared)`` (qat_trainer.py:311; bucketing of torch/nn/parallel/distributed.py:828-834)."""
-    world = dist.get_world_size(pg)
-    avg = dist.get_backend(pg) == "nccl"          # gloo has no AVG: sum, then divide
+    op, div = mean_op(pg)
     works = []
     for s0, s1, a, b in layout.buckets(bucket_bytes):
         run_stages(s0, s1)
         seg = flat[a:b]
-        works.append((dist.all_reduce(seg, op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, group=pg, async_op=True), seg))
+        works.append((dist.all_reduce(seg, op=op, group=pg, async_op=True), seg))
     ev = None
     if exposed is not None and flat.is_cuda:   # (bench.py) the stream time between the last backward kernel and the join of the last collective
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
     for w, seg in works:
         w.wait()
-        if not avg:
-            seg.div_(world)
+        if div:
+            seg.div_(div)
     if ev is not None:
         ev[1].record()
         exposed.append(ev)
@@ -260,6 +273,141 @@ def broadcast_fq_state(arena: torch.Tensor, pg) -> None:
     dist.broadcast(arena, src=0, group=pg)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The overflow protocol of the one-plane backward (include/qatvit.h, QATVIT_BWD_DY16): did the backward just issued meet a gradient that did not fit
+# its fp16 plane, and does the data-parallel group agree?  mirror_wait and store_agree are pure host logic (no native library, no GPU).
+
+def mirror_wait(mirror, want: int, limit: float = 10.0) -> Optional[bool]:
+    """mirror: int32 {flag, generation}.  Wait until the device has written generation `want` (mod 2^32) or a later one, then the flag; None if it
+    does not show up within `limit` seconds (the caller synchronises instead)."""
+    want, t0 = want & 0xffffffff, time.perf_counter()
+    while ((int(mirror[1]) - want) & 0xffffffff) >= 0x80000000:      # generation still behind the one this call writes
+        if time.perf_counter() - t0 > limit:
+            return None
+        time.sleep(0)
+    return bool(int(mirror[0]))
+
+
+def store_agree(st, k: int, rank: int, world: int, local: bool) -> bool:
+    """MAX over the group's ranks of the local overflow flags, through a key-value store (host only; every rank calls it once per round k)."""
+    if local:
+        st.add(f"o{k}", 1)
+    n = st.add(f"a{k}", 1)                    # (after this rank's overflow count: once all have arrived every count is in)
+    t0 = time.perf_counter()
+    while n < world:
+        if time.perf_counter() - t0 > 60.0:
+            raise RuntimeError("one-plane backward: a rank of the data-parallel group did not report its overflow flag within 60 s")
+        time.sleep(0)
+        n = st.add(f"a{k}", 0)
+    over = st.add(f"o{k}", 0) > 0
+    if k >= 2 and rank == 0:                  # round k - 2 is behind every rank (each passed round k - 1 to get here)
+        for key in (f"a{k - 2}", f"o{k - 2}"):
+            try:
+                st.delete_key(key)
+            except Exception:  # noqa: BLE001
+                pass
+    return over
+
+
+class OverflowProtocol:
+    """One per StudentEngine.  `calibrated`: the workspace holds a scale history (a fresh one starts with one calibrating, pair-form, step);
+    `fallbacks`: backward passes repeated in the pair form after an overflow."""
+
+    def __init__(self):
+        self.calibrated, self.fallbacks = False, 0
+        self.flag = None                         # int32 view of the overflow word in the workspace
+        # host mirror of the flag (qatvit_student_dy16_set_mirror): pinned int32 {flag, generation} the backward writes before its deferred weight
+        # gradients; polled instead of synchronising with the stream.  QATVIT_DY16_MIRROR=0: the stream synchronisation.
+        self.mirror = self.mirror_np = None
+        self.mirror_on = os.environ.get("QATVIT_DY16_MIRROR", "1") != "0"
+        self.gen = 0                             # backward calls issued since the mirror was installed: the generation the device will have written after them
+        self.pg, self.store, self.round, self.epoch = None, None, 0, 0   # (data-parallel: setup_agreement)
+
+    def attach(self, workspace: torch.Tensor, cfg: native.Cfg, mirror: bool) -> None:
+        """A fresh workspace: its flag word, no scale history yet and, if asked for (the one-plane form is on), a mirror installed in it."""
+        L, cp = native.lib(), ctypes.byref(cfg)
+        off = L.qatvit_student_tensor_offset(cp, b"dy16", 0)
+        self.flag = workspace[off + 8:off + 12].view(torch.int32)   # header word 2: overflow
+        self.calibrated, self.gen = False, 0
+        if not (self.mirror_on and mirror):
+            return
+        try:
+            m = torch.zeros(2, dtype=torch.int32).pin_memory()
+        except RuntimeError:
+            return
+        if L.qatvit_student_dy16_set_mirror(cp, workspace.data_ptr(), m.data_ptr(), native.stream_ptr()) == 0:
+            self.mirror, self.mirror_np = m, m.numpy()   # (non-zero: not device-addressable here, the stream synchronisation stays)
+
+    def detach(self) -> None:
+        """Before the workspace is released: nothing here may keep its storage alive, and no kernel may still hold the mirror's address."""
+        self.flag = None
+        if self.mirror is not None:
+            torch.cuda.current_stream().synchronize()
+            self.mirror = self.mirror_np = None
+
+    def issued(self) -> None:   # a backward call with BWD_DY16 or BWD_CALIBRATE was enqueued (a captured one counts when replayed): it ends with k_dy16_end, one generation
+        self.gen += 1
+
+    def setup_agreement(self, pg, device) -> None:
+        """The ranks must agree on the overflow flag of a one-plane backward (all repeat it, with its collectives, or none does).  A one-element MAX
+        all-reduce on the stream is known only when the whole backward is over - the host would come back to an idle GPU (0.6 ms per step).  With the
+        pinned mirror every rank knows its own flag 2 - 3 ms earlier; they agree through the c10d key-value store the group was set up with (two
+        counters per step: arrivals, overflows) while the GPUs still run the weight gradients.  QATVIT_DY16_STORE_AGREE=0 (or a store that is not
+        reachable): the all-reduce."""
+        self.pg, self.store, self.round = pg, None, 0
+        ranks = dist.get_process_group_ranks(pg)
+        self.epoch += 1                                                     # (a second setup on this object must not meet the first one's counters)
+        tag = torch.tensor([id(self) & 0x7fffffff, self.epoch], dtype=torch.int64, device=device)
+        dist.broadcast(tag, src=ranks[0], group=pg)                         # one name for this engine's keys on every rank
+        if os.environ.get("QATVIT_DY16_STORE_AGREE", "1") != "0":
+            try:
+                from torch.distributed.distributed_c10d import _get_default_store
+                self.store = dist.PrefixStore(f"qatvit_dy16/{int(tag[0].item())}.{int(tag[1].item())}/{'-'.join(map(str, ranks))}", _get_default_store())
+                self.store.add("probe", 0)
+            except Exception:  # noqa: BLE001
+                self.store = None
+        can = torch.tensor([1 if self.store is not None else 0], dtype=torch.int32, device=device)
+        dist.all_reduce(can, op=dist.ReduceOp.MIN, group=pg)            # the store path on every rank or on none
+        if int(can.item()) == 0:
+            self.store = None
+
+    def overflowed(self) -> bool:
+        """Did the last one-plane backward meet a gradient that did not fit its fp16 plane?  Blocks on the stream; in a data-parallel group the
+        answer is agreed on (MAX over the ranks) so that every rank repeats the backward, and its collectives, or none does."""
+        flag = self.flag
+        if self.pg is not None:
+            flag = flag.clone()
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.pg)
+        over = bool(flag.item())
+        if self.mirror_np is not None:           # the stream is drained: whatever wrote generations without this object counting is accounted for
+            self.gen = int(self.mirror_np[1]) & 0xffffffff
+        return over
+
+    def resolve(self, replayed: bool = False) -> bool:
+        """Did the one-plane backward just issued overflow, anywhere in the group?  Every rank calls it once per such backward (all repeat the backward,
+        with its collectives, or none does).  replayed: a hipGraph replay issued it, so the host has not counted its generation yet."""
+        if replayed:
+            self.gen += 1
+        over = None
+        if self.pg is None or self.store is not None:   # (the store: agreed on by the whole group in setup_agreement, every rank comes here or none)
+            # the flag as soon as the device knows it: the deferred weight gradients are still running, the host goes on
+            over = mirror_wait(self.mirror_np, self.gen) if self.mirror_np is not None else None
+            if self.pg is not None:
+                self.round += 1
+                over = store_agree(self.store, self.round - 1, dist.get_rank(self.pg), dist.get_world_size(self.pg),
+                                   bool(self.flag.item()) if over is None else over)
+        return self.overflowed() if over is None else over
+
+
+class Step(NamedTuple):
+    """What a forward was: it travels with the step (autograd's ctx, a captured hipGraph) to the backward of exactly that forward."""
+    cfg: native.Cfg
+    generation: int        # the engine's count of forwards: the workspace holds the activations of exactly one
+    x16: bool              # the forward wrote h1q / h2q as fp16 integers: its backward is the one-plane form
+    fq_mode: Optional[str]
+    ln_in_strip: int       # which of its LayerNorms ran inside the statistics pass that follows them (bit 0: norm1 / qkv, bit 1: norm2 / fc1; QATVIT_LN_STRIP)
+
+
 class StudentEngine:
     """One per prepared wrapper (created lazily at the first CUDA forward)."""
 
@@ -290,7 +438,6 @@ class StudentEngine:
         # everywhere (the observe-only step); every forward decides which (decide_mode)
         self._fq_flags, self._fq_names = fq_flags_and_names(wrapper)
         self._fq_state = FqModeState()
-        self.fq_mode: Optional[str] = None       # the mode of the most recent forward
         # observe-only resources, allocated by the first observe-only forward beside the QAT workspace (which keeps the dy16 scale history and the
         # addresses a captured hipGraph is bound to)
         self.float_form = float_engine.Form(*float_engine.FP32)
@@ -302,7 +449,7 @@ class StudentEngine:
             averaging_const=float(a0.activation_post_process.averaging_constant),
         )
         self._cfgs: Dict[int, native.Cfg] = {}
-        self.cfg = self.cfg_for(batch)           # the configuration of the most recent forward (tests read .cfg of the last step)
+        self.last_step = Step(self.cfg_for(batch), 0, False, None, 0)   # the record of the most recent forward (before the first: the bound batch)
         if hd * self.cfg.num_heads != self.cfg.embed_dim:
             raise RuntimeError("embed_dim must equal num_heads * head_dim")
         L, cp = self.lib, ctypes.byref(self.cfg)
@@ -314,16 +461,8 @@ class StudentEngine:
         # the one-plane backward (include/qatvit.h, QATVIT_BWD_DY16): on when the configuration allows it; the scale history lives in the
         # workspace, so a fresh workspace starts with one calibrating (pair-form) step
         self.dy16 = dy16_default() and bool(self.lib.qatvit_student_dy16_supported(ctypes.byref(self.cfg)))
-        self._dy16_calibrated = False
-        self._fwd_x16 = False                    # how the most recent forward wrote h1q / h2q
-        self.ln_in_strip = 0                     # ... and which of its LayerNorms ran inside a statistics pass (forward())
-        self.dy16_fallbacks = 0                  # backward passes repeated in the pair form after an overflow
-        # host mirror of the overflow flag (include/qatvit.h, qatvit_student_dy16_set_mirror): pinned int32 {flag, generation} the backward writes before its deferred
-        # weight gradients; the single-GPU backward polls it instead of synchronising with the stream.  QATVIT_DY16_MIRROR=0: the stream synchronisation.
-        self._mirror = self._mirror_np = None
-        self._mirror_on = os.environ.get("QATVIT_DY16_MIRROR", "1") != "0"
-        self._gen_issued = 0                     # backward calls issued since the mirror was (re)installed: the generation the device will have written after them
-        self._agree_store, self._agree_round = None, 0   # (data-parallel: enable_data_parallel)
+        self.overflow = OverflowProtocol()
+        self.dy16_overflowed = self.overflow.overflowed
         self._reserve(batch)
         # ---- flat gradient buffer, laid out in backward-stage order so that finished buckets are contiguous
         self.layout = FlatGradLayout([p.numel() for p in ps], self.cfg.depth)
@@ -331,13 +470,21 @@ class StudentEngine:
         self._ptr_params = (ctypes.c_void_p * len(ps))(*[p.data_ptr() for p in ps])
         self._param_ptrs_key = tuple(p.data_ptr() for p in ps)
         self.pg = None
-        self.sync_state = True      # set per call by student_forward: grad mode of the caller (False under no_grad)
         self.bucket_bytes = 16 << 20
         self.exposed_events: Optional[list] = None   # bench.py sets a list: (start, end) event pairs of the exposed collective time, one per backward
-        self.generation = 0         # bumped by every forward: the workspace holds the activations of exactly one forward
         self._build_fq_structs()
 
     # ------------------------------------------------------------------ configuration / workspace
+    # the most recent forward, field by field, and the protocol's counter, store and mirror, by the names callers and tests read
+    cfg = property(lambda self: self.last_step.cfg)
+    generation = property(lambda self: self.last_step.generation)
+    _fwd_x16 = property(lambda self: self.last_step.x16)
+    fq_mode = property(lambda self: self.last_step.fq_mode)
+    ln_in_strip = property(lambda self: self.last_step.ln_in_strip)
+    dy16_fallbacks = property(lambda self: self.overflow.fallbacks)
+    _agree_store = property(lambda self: self.overflow.store)
+    _mirror_np = property(lambda self: self.overflow.mirror_np)
+
     def cfg_for(self, batch: int) -> native.Cfg:
         c = self._cfgs.get(batch)
         if c is None:
@@ -361,40 +508,17 @@ class StudentEngine:
             return
         if self.frozen:
             raise RuntimeError(f"batch {batch} exceeds the workspace ({self.capacity}) a captured hipGraph is bound to")
-        L, cp = self.lib, ctypes.byref(self.cfg_for(batch))
+        c = self.cfg_for(batch)
+        L, cp = self.lib, ctypes.byref(c)
         nbytes = L.qatvit_student_workspace_bytes(cp)
         if nbytes <= 0:
             raise RuntimeError("qatvit_student_workspace_bytes: " + L.qatvit_last_error().decode())
+        self.overflow.detach()
         self.workspace = None                    # release the smaller one first
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         native.check(L.qatvit_student_init(cp, self.workspace.data_ptr(), native.stream_ptr()), "qatvit_student_init")
         self.capacity = batch
-        self._dy16_calibrated = False
-        off = L.qatvit_student_tensor_offset(cp, b"dy16", 0)
-        self._dy16_flag = self.workspace[off + 8:off + 12].view(torch.int32)   # header word 2: overflow
-        self._install_mirror(cp)
-
-    def _install_mirror(self, cp) -> None:
-        self._mirror = self._mirror_np = None
-        self._gen_issued = 0
-        if not (self._mirror_on and self.dy16):
-            return
-        try:
-            m = torch.zeros(2, dtype=torch.int32).pin_memory()
-        except RuntimeError:
-            return
-        if self.lib.qatvit_student_dy16_set_mirror(cp, self.workspace.data_ptr(), m.data_ptr(), native.stream_ptr()) != 0:
-            return                               # (not device-addressable here: the stream synchronisation stays)
-        self._mirror, self._mirror_np = m, m.numpy()
-
-    def _mirror_wait(self) -> Optional[bool]:
-        """Wait until the device has written the flag of the last issued backward call; None if it does not show up (the caller synchronises instead)."""
-        m, want, t0 = self._mirror_np, self._gen_issued & 0xffffffff, time.perf_counter()
-        while ((int(m[1]) - want) & 0xffffffff) >= 0x80000000:      # generation still behind the one this call writes
-            if time.perf_counter() - t0 > 10.0:
-                return None
-            time.sleep(0)
-        return bool(int(m[0]))
+        self.overflow.attach(self.workspace, c, self.dy16)
 
     # ------------------------------------------------------------------ FQ state arena
     def _rehome_fq_state(self):
@@ -418,51 +542,7 @@ class StudentEngine:
         self.bucket_bytes = bucket_bytes
         for p in self.params:  # replicas start identical (DDP's constructor broadcast)
             dist.broadcast(p.data, src=0, group=self.pg)
-        # The ranks must agree on the overflow flag of a one-plane backward (all repeat it, with its collectives, or none does).  A one-element MAX all-reduce on the
-        # stream is known only when the whole backward is over - the host would come back to an idle GPU (0.6 ms per step).  With the pinned mirror every rank knows its
-        # own flag 2 - 3 ms earlier; they agree through the c10d key-value store the group was set up with (two counters per step: arrivals, overflows) while the GPUs
-        # still run the weight gradients.  QATVIT_DY16_STORE_AGREE=0 (or a store that is not reachable): the all-reduce.
-        self._agree_store, self._agree_round = None, 0
-        ranks = dist.get_process_group_ranks(self.pg)
-        self._dp_epoch = getattr(self, "_dp_epoch", 0) + 1                  # (a second enable_data_parallel on this engine must not meet the first one's counters)
-        tag = torch.tensor([id(self) & 0x7fffffff, self._dp_epoch], dtype=torch.int64, device=self.device)
-        dist.broadcast(tag, src=ranks[0], group=self.pg)                    # one name for this engine's keys on every rank
-        if os.environ.get("QATVIT_DY16_STORE_AGREE", "1") != "0":
-            try:
-                from torch.distributed.distributed_c10d import _get_default_store
-                self._agree_store = dist.PrefixStore(f"qatvit_dy16/{int(tag[0].item())}.{int(tag[1].item())}/{'-'.join(map(str, ranks))}", _get_default_store())
-                self._agree_store.add("probe", 0)
-            except Exception:  # noqa: BLE001
-                self._agree_store = None
-        can = torch.tensor([1 if self._agree_store is not None else 0], dtype=torch.int32, device=self.device)
-        dist.all_reduce(can, op=dist.ReduceOp.MIN, group=self.pg)       # the store path on every rank or on none
-        if int(can.item()) == 0:
-            self._agree_store = None
-
-    def _agree_overflow(self, local: bool) -> bool:
-        """MAX over the group's ranks of the local overflow flags, through the key-value store (host only; every rank calls it once per one-plane backward)."""
-        st, k, world = self._agree_store, self._agree_round, dist.get_world_size(self.pg)
-        self._agree_round += 1
-        if local:
-            st.add(f"o{k}", 1)
-        n = st.add(f"a{k}", 1)                    # (after this rank's overflow count: once all have arrived every count is in)
-        t0 = time.perf_counter()
-        while n < world:
-            if time.perf_counter() - t0 > 60.0:
-                raise RuntimeError("one-plane backward: a rank of the data-parallel group did not report its overflow flag within 60 s")
-            time.sleep(0)
-            n = st.add(f"a{k}", 0)
-        over = st.add(f"o{k}", 0) > 0
-        if k >= 2 and dist.get_rank(self.pg) == 0:   # round k - 2 is behind every rank (each passed round k - 1 to get here)
-            for key in (f"a{k - 2}", f"o{k - 2}"):
-                try:
-                    st.delete_key(key)
-                except Exception:  # noqa: BLE001
-                    pass
-        return over
-
-    def _broadcast_fq_state(self):
-        broadcast_fq_state(self.fq_arena, self.pg)
+        self.overflow.setup_agreement(self.pg, self.device)
 
     # ------------------------------------------------------------------ step
     def _check_ptrs(self):
@@ -489,31 +569,29 @@ class StudentEngine:
         prev = self._fq_state.mode
         mode = decide_fq_mode(self._fq_state, self._fq_flags, self._fq_names)
         if mode == QAT and prev == OBSERVE:
-            self._dy16_calibrated = False
+            self.overflow.calibrated = False
         return mode
 
-    def forward(self, images: torch.Tensor) -> torch.Tensor:
+    def forward(self, images: torch.Tensor, training: bool) -> torch.Tensor:
+        """training: the caller's grad mode (False under no_grad).  Leaves the record of this forward in `last_step`."""
         mode = self.decide_mode()                # (a mix of flags raises here, before any launch or collective)
-        self.fq_mode = mode
         if mode == OBSERVE:
-            return self._forward_observe(images)
+            return self._forward_observe(images, training)
         c = self._check_images(images)
-        self.cfg = c
         # Rank 0's fake-quant state is authoritative at the start of every TRAINING forward (what DDP's buffer broadcast does
         # for the reference).  A forward under no_grad - the reference's evaluate_fp32 runs on rank 0 only
         # (qat_trainer.py:370-371) - issues no collective, whatever its batch size, so a one-rank evaluation cannot dead-lock the group.
-        if self.pg is not None and self.sync_state:
-            self._broadcast_fq_state()
+        if self.pg is not None and training:
+            broadcast_fq_state(self.fq_arena, self.pg)
         images = images.contiguous()
         logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
-        self.generation += 1
         # a training forward of a calibrated engine leaves the X operands of the qkv / fc1 weight gradients as fp16 integers: its backward is one-plane
-        self._fwd_x16 = self.dy16 and self._dy16_calibrated and self.sync_state
-        # which LayerNorms of this forward run inside the statistics pass that follows them (bit 0: norm1 / qkv, bit 1: norm2 / fc1; QATVIT_LN_STRIP)
-        self.ln_in_strip = int(self.lib.qatvit_student_ln_in_strip(ctypes.byref(c), FWD_X16 if self._fwd_x16 else 0))
+        x16 = self.dy16 and self.overflow.calibrated and training
+        flags = FWD_X16 if x16 else 0
+        self.last_step = Step(c, self.generation + 1, x16, mode, int(self.lib.qatvit_student_ln_in_strip(ctypes.byref(c), flags)))
         native.check(self.lib.qatvit_student_forward_stages(ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, images.data_ptr(),
-                                                            logits.data_ptr(), self.workspace.data_ptr(), 0, c.depth + 1, FWD_X16 if self._fwd_x16 else 0,
-                                                            native.stream_ptr()), "qatvit_student_forward")
+                                                            logits.data_ptr(), self.workspace.data_ptr(), 0, c.depth + 1, flags, native.stream_ptr()),
+                     "qatvit_student_forward")
         return logits
 
     # ------------------------------------------------------------------ observe-only step (fake-quant off everywhere)
@@ -529,42 +607,33 @@ class StudentEngine:
             self.observe_buf = buf
         self.float_form.reserve(c, self.device)
 
-    def _forward_observe(self, images: torch.Tensor) -> torch.Tensor:
+    def _forward_observe(self, images: torch.Tensor, training: bool) -> torch.Tensor:
         """Stock semantics with fake_quant_enabled = 0 everywhere: the float network, whose observers (where observer_enabled = 1) still take their
         EMA step; scale / zero_point stay.  The data-parallel state broadcast of a training forward is the QAT step's."""
         self._check_shape(images)
         c = self.cfg_for(images.shape[0])
         self._reserve_observe(c)
-        self.cfg = c
-        if self.pg is not None and self.sync_state:
-            self._broadcast_fq_state()
+        if self.pg is not None and training:
+            broadcast_fq_state(self.fq_arena, self.pg)
         images = images.contiguous()
         logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
-        self.generation += 1
-        self._fwd_x16 = False
+        self.last_step = Step(c, self.generation + 1, False, OBSERVE, 0)
         native.check(self.lib.qatvit_float_student_forward_observe(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
                                                                    self.float_form.workspace.data_ptr(), self.observe_buf.data_ptr(), native.stream_ptr()),
                      "qatvit_float_student_forward_observe")
         return logits
 
-    def backward_observe(self, dlogits: torch.Tensor, c: native.Cfg) -> List[torch.Tensor]:
+    def backward_observe(self, dlogits: torch.Tensor, step: Step) -> List[torch.Tensor]:
         """The float step's backward (every STE mask is 1: the gradient stock computes); in a data-parallel group one average of the whole flat
         gradient afterwards."""
         flat, views, gptr = self._grad_buffers()
-        self.float_form.call("backward", ctypes.byref(c), self._ptr_params, dlogits.contiguous().data_ptr(), gptr)
+        self.float_form.call("backward", ctypes.byref(step.cfg), self._ptr_params, dlogits.contiguous().data_ptr(), gptr)
         if self.pg is not None:
-            if dist.get_backend(self.pg) == "nccl":
-                dist.all_reduce(flat, op=dist.ReduceOp.AVG, group=self.pg)
-            else:                                # gloo has no AVG
-                dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.pg)
-                flat.div_(dist.get_world_size(self.pg))
+            allreduce_mean(flat, self.pg)
         return views
 
     def _grad_buffers(self):
-        flat = torch.zeros(self.grad_numel, dtype=torch.float32, device=self.device)
-        views = self.layout.views(flat, [p.shape for p in self.params])
-        gptr = (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
-        return flat, views, gptr
+        return native.flat_grad_buffers(self.params, self.layout.offset, self.grad_numel)
 
     def _run_backward(self, dlogits: torch.Tensor, c: native.Cfg, flags: int):
         flat, views, gptr = self._grad_buffers()
@@ -574,7 +643,7 @@ class StudentEngine:
             native.check(L.qatvit_student_backward_stages(cp, self._ptr_params, self._act_structs, self._w_structs, dlogits.data_ptr(), gptr,
                                                           self.workspace.data_ptr(), s0, s1, flags, st), "qatvit_student_backward")
             if flags & (BWD_DY16 | BWD_CALIBRATE) and not torch.cuda.is_current_stream_capturing():
-                self._gen_issued += 1            # (every such call ends with k_dy16_end: one generation of the mirror; a captured call counts when it is replayed)
+                self.overflow.issued()
 
         if self.pg is None:
             run(0, self.layout.last_stage)
@@ -582,57 +651,33 @@ class StudentEngine:
             staged_backward_allreduce(flat, self.layout, self.bucket_bytes, self.pg, run, self.exposed_events)
         return views
 
-    def dy16_overflowed(self) -> bool:
-        """Did the last one-plane backward meet a gradient that did not fit its fp16 plane?  Blocks on the stream; in a data-parallel group the
-        answer is agreed on (MAX over the ranks) so that every rank repeats the backward, and its collectives, or none does."""
-        flag = self._dy16_flag
-        if self.pg is not None:
-            flag = flag.clone()
-            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.pg)
-        over = bool(flag.item())
-        if self._mirror_np is not None:          # the stream is drained: whatever wrote generations without this object counting (a hipGraph replay) is accounted for
-            self._gen_issued = int(self._mirror_np[1]) & 0xffffffff
-        return over
-
-    def backward(self, dlogits: torch.Tensor, cfg: Optional[native.Cfg] = None, x16: Optional[bool] = None):
-        c = cfg if cfg is not None else self.cfg
+    def backward(self, dlogits: torch.Tensor, step: Step):
+        """The backward of the forward that left `step`."""
         dlogits = dlogits.contiguous()
-        x16 = self._fwd_x16 if x16 is None else x16
         if not self.dy16:
-            return self._run_backward(dlogits, c, 0)
-        if not x16:                                     # first step on this workspace: the pair form, recording every gradient tensor's maximum
-            views = self._run_backward(dlogits, c, BWD_CALIBRATE)
-            self._dy16_calibrated = True
+            return self._run_backward(dlogits, step.cfg, 0)
+        if not step.x16:                                # first step on this workspace: the pair form, recording every gradient tensor's maximum
+            views = self._run_backward(dlogits, step.cfg, BWD_CALIBRATE)
+            self.overflow.calibrated = True
             return views
-        views = self._run_backward(dlogits, c, BWD_DY16)
+        views = self._run_backward(dlogits, step.cfg, BWD_DY16)
         if torch.cuda.is_current_stream_capturing():    # a hipGraph capture cannot ask: GraphedStudentStep checks after each replay
             return views
-        over = None
-        if self.pg is None:
-            if self._mirror_np is not None:
-                over = self._mirror_wait()       # the flag as soon as the device knows it: the deferred weight gradients are still running, the host goes on
-        elif self._agree_store is not None:      # (agreed on by the whole group in enable_data_parallel: every rank comes here or none)
-            local = self._mirror_wait() if self._mirror_np is not None else None
-            over = self._agree_overflow(bool(self._dy16_flag.item()) if local is None else local)
-        if over is None:
-            over = self.dy16_overflowed()
-        if over:
-            views = self.dy16_fallback(dlogits, c)
-        return views
+        return self.dy16_fallback(dlogits, step) if self.overflow.resolve() else views
 
-    def dy16_fallback(self, dlogits: torch.Tensor, c: native.Cfg):
+    def dy16_fallback(self, dlogits: torch.Tensor, step: Step):
         """The scales predicted from the previous step did not hold (the flag is raised when max |value| * 2^e > 65504): the same backward again in
         the pair form - bit-identical to a step that never left it - which also re-records the maxima."""
-        self.dy16_fallbacks += 1
+        self.overflow.fallbacks += 1
         if self.dy16_fallbacks == 1:
             warnings.warn("qat-vit_amd: a gradient outgrew its fp16 plane (scale predicted from the previous step); this backward was repeated in the "
                           "bf16-pair form. Harmless if rare (engine.dy16_fallbacks counts them); QATVIT_DY16=0 keeps the pair form throughout.",
                           RuntimeWarning, stacklevel=3)
-        native.check(self.lib.qatvit_student_dy16_to_pair(ctypes.byref(c), self.workspace.data_ptr(), native.stream_ptr()), "qatvit_student_dy16_to_pair")
-        self._fwd_x16 = False
-        return self._run_backward(dlogits, c, BWD_CALIBRATE)
+        native.check(self.lib.qatvit_student_dy16_to_pair(ctypes.byref(step.cfg), self.workspace.data_ptr(), native.stream_ptr()), "qatvit_student_dy16_to_pair")
+        return self._run_backward(dlogits.contiguous(), step.cfg, BWD_CALIBRATE)
 
     # ------------------------------------------------------------------ stage-level access (parity tests, include/qatvit.h "stages")
+    # Test infrastructure: these four work on "the configuration of the most recent forward or bind" (self.cfg) by design.
     def tensor(self, name: str, block: int, shape, dtype=torch.float32, cfg: Optional[native.Cfg] = None) -> torch.Tensor:
         """View of a named intermediate tensor inside the workspace (layout of the given / most recent batch size)."""
         c = cfg if cfg is not None else self.cfg
@@ -649,7 +694,7 @@ class StudentEngine:
         c = self.cfg
         if stage_to == c.depth + 1 and logits is None:
             logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
-        self.generation += 1
+        self.last_step = self.last_step._replace(generation=self.generation + 1)   # (it overwrites the workspace: a forward)
         native.check(self.lib.qatvit_student_forward_stages(
             ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, images.data_ptr() if images is not None else None,
             logits.data_ptr() if logits is not None else None, self.workspace.data_ptr(), stage_from, stage_to,
@@ -658,7 +703,7 @@ class StudentEngine:
 
     def forward_part(self, block: int, part: int, inject: bool = False, x16: bool = False) -> None:
         """qatvit_student_forward_part: part 0 / 1 / 2 of one block (inputs: x_in / pre-FQ qkv / x_mid of that block)."""
-        self.generation += 1
+        self.last_step = self.last_step._replace(generation=self.generation + 1)   # (it overwrites the workspace: a forward)
         native.check(self.lib.qatvit_student_forward_part(ctypes.byref(self.cfg), self._ptr_params, self._act_structs, self._w_structs,
                                                           self.workspace.data_ptr(), block, part, (STAGE_INJECT if inject else 0) | (FWD_X16 if x16 else 0),
                                                           native.stream_ptr()),
@@ -672,48 +717,25 @@ class StudentEngine:
             ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, dlogits.contiguous().data_ptr() if dlogits is not None else None,
             gptr, self.workspace.data_ptr(), stage_from, stage_to, (STAGE_INJECT if inject else 0) | mode, native.stream_ptr()), "qatvit_student_backward_stages")
         if mode & (BWD_DY16 | BWD_CALIBRATE):
-            self._gen_issued += 1
+            self.overflow.issued()
         return views
 
 
 class _StudentStep(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, images, engine, *params):
+    def forward(ctx, images, engine, training, *params):
         ctx.engine = engine
-        out = engine.forward(images)
-        ctx.generation = engine.generation
-        ctx.step_cfg = engine.cfg
-        ctx.x16 = engine._fwd_x16
-        ctx.mode = engine.fq_mode
+        out = engine.forward(images, training)
+        ctx.step = engine.last_step
         return out
 
     @staticmethod
     def backward(ctx, dlogits):
-        # The native backward writes every parameter gradient into one flat buffer; hand the views to the parameters
-        # directly (what `zero_grad(set_to_none=True)` + autograd would end up with) instead of returning them, so
-        # autograd's AccumulateGrad does not clone 152 tensors per step.  Stock ``DDP(prepared)`` keeps working on top of
-        # this because DDP's reducer is driven by post-accumulate-grad hooks that fire when ``.grad`` is assigned here
-        # (tests/test_gpu_dp.py); the native bucketed path (``enable_data_parallel``) is the one bench.py measures.
-        eng = ctx.engine
-        if eng.generation != ctx.generation:
-            # The activations, STE masks and qparams of a step live in the engine's one workspace, not in autograd's graph:
-            # a later forward (an evaluation under no_grad, a second micro-batch) has overwritten them.  Stock autograd
-            # would keep both alive; here the second backward would silently differentiate the wrong step - refuse.
-            raise RuntimeError(
-                "qat-vit_amd: another forward of this model ran between this forward and its backward; the native step keeps the "
-                "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
-                "forward/backward per micro-batch)."
-            )
-        if ctx.mode == OBSERVE:
-            grads = eng.backward_observe(dlogits, ctx.step_cfg)
-        else:
-            grads = eng.backward(dlogits, ctx.step_cfg, ctx.x16)
-        for p, g in zip(eng.params, grads):
-            if p.grad is None:
-                p.grad = g
-            else:
-                p.grad.add_(g)
-        return (None, None) + (None,) * len(grads)
+        eng, step = ctx.engine, ctx.step
+        native.check_generation(eng, step.generation)
+        grads = eng.backward_observe(dlogits, step) if step.fq_mode == OBSERVE else eng.backward(dlogits, step)
+        native.assign_grads(eng.params, grads)
+        return (None, None, None) + (None,) * len(grads)
 
 
 # engines live outside the module (a ctypes pointer table must not be deep-copied or pickled with it)
@@ -735,5 +757,5 @@ def bind(wrapper, batch: int) -> "StudentEngine":
 
 def student_forward(wrapper, images: torch.Tensor) -> torch.Tensor:
     eng = bind(wrapper, images.shape[0])
-    eng.sync_state = torch.is_grad_enabled()   # read here: inside autograd.Function.forward grad mode is always off
-    return _StudentStep.apply(images, eng, *eng.params)
+    # (grad mode is read here: inside autograd.Function.forward it is always off)
+    return _StudentStep.apply(images, eng, torch.is_grad_enabled(), *eng.params)

@@ -135,6 +135,7 @@ class FloatStudentEngine:
         self.fp32, self.fp16, self.bf16 = Form(*FP32), Form(*FP16), Form(*BF16)   # each workspace allocated by the first forward of its form
         self.generation = 0         # bumped by every forward of any form: the workspaces hold the activations of exactly one forward
         self.grad_numel = sum(p.numel() for p in self.params)
+        self._grad_offsets = [sum(p.numel() for p in self.params[:i]) for i in range(len(self.params))]   # dense, in parameter order
 
     def cfg_for(self, batch: int) -> native.Cfg:
         return native.Cfg(batch=batch, **self._cfg_kw)
@@ -177,12 +178,7 @@ class FloatStudentEngine:
         form = form or self.fp32
         c = self.cfg_for(batch)
         dlogits = dlogits.to(form.dtype).contiguous()
-        flat = torch.zeros(self.grad_numel, dtype=torch.float32, device=self.device)
-        views, o = [], 0
-        for p in self.params:
-            views.append(flat[o:o + p.numel()].view(p.shape))
-            o += p.numel()
-        gptr = (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
+        _, views, gptr = native.flat_grad_buffers(self.params, self._grad_offsets, self.grad_numel)
         form.call("backward", ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr)
         return views
 
@@ -197,21 +193,10 @@ def _step_forward(ctx, images, engine, form: Form):
 
 
 def _step_backward(ctx, dlogits):
-    # as engine._StudentStep: the gradients are views of one flat buffer assigned to .grad directly (DDP's post-accumulate-grad hooks
-    # fire on that assignment)
     eng = ctx.engine
-    if eng.generation != ctx.generation:
-        raise RuntimeError(
-            "qat-vit_amd: another forward of this model ran between this forward and its backward; the native step keeps the "
-            "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
-            "forward/backward per micro-batch)."
-        )
+    native.check_generation(eng, ctx.generation)
     grads = eng.backward(dlogits, ctx.batch, ctx.form)
-    for p, g in zip(eng.params, grads):
-        if p.grad is None:
-            p.grad = g
-        else:
-            p.grad.add_(g)
+    native.assign_grads(eng.params, grads)
     return (None, None, None) + (None,) * len(grads)
 
 

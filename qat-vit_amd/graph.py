@@ -46,7 +46,6 @@ class GraphedStudentStep:
         # the graph records raw addresses of the engine's workspace and fake-quant arena: keep the engine alive and pin its workspace
         # (a later, larger batch would otherwise re-allocate it under the graph)
         self.engine = eng
-        eng._reserve(images.shape[0])             # (already true after the warm-up; explicit: the graph is bound to THIS workspace)
         for p in model.parameters():
             p.grad = None
         self.graph = torch.cuda.CUDAGraph()
@@ -60,7 +59,7 @@ class GraphedStudentStep:
             self.engine = None
             raise
         self._grads = [p.grad for p in model.parameters()]   # from here on the pin lasts as long as this object (close() / __del__ release it)
-        self._x16 = eng._fwd_x16                   # the captured backward is the one-plane form: its overflow flag is read after every replay
+        self.step = eng.last_step                  # the record of the captured forward; x16: its backward is the one-plane form, whose overflow flag is read after every replay
 
     def close(self) -> None:
         """Drops the graph and releases THIS object's pin on the engine's workspace (idempotent).  The pin is a count on the engine: a
@@ -105,21 +104,13 @@ class GraphedStudentStep:
         for p, g in zip(self.model.parameters(), self._grads):   # zero_grad(set_to_none=True) in the loop must not drop the static buffers
             p.grad = g
         self.graph.replay()
-        over = False
-        if self._x16:
-            eng = self.engine
-            got = None
-            if eng._mirror_np is not None and eng.pg is None:     # the replayed backward wrote one more generation of the flag mirror, before its weight gradients
-                eng._gen_issued += 1
-                got = eng._mirror_wait()
-            over = eng.dy16_overflowed() if got is None else got
-        if over:
+        if self.step.x16 and self.engine.overflow.resolve(replayed=True):
             # a gradient outgrew its fp16 plane (engine.backward asks this itself in eager mode; a capture cannot): the backward again, eagerly, in the
             # pair form, from the logits the replay left - into the buffers .grad points at
             out = self.out.detach().requires_grad_(True)
             with torch.enable_grad():
                 loss, _ = F.kd_ce_loss(out, self.t, self.y, *self.hp)
                 (dlogits,) = torch.autograd.grad(loss, out)
-            for g, v in zip(self._grads, self.engine.dy16_fallback(dlogits, self.engine.cfg)):
-                g.copy_(v)
+            for p, v in zip(self.engine.params, self.engine.dy16_fallback(dlogits, self.step)):   # (the views come in the engine's parameter order)
+                p.grad.copy_(v)
         return self.out, self.loss, self.parts

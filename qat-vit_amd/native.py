@@ -171,3 +171,39 @@ def stream_ptr() -> int:
     import torch
 
     return torch.cuda.current_stream().cuda_stream
+
+
+# ---- what the autograd functions of the QAT engine (engine.py) and the float engine (float_engine.py) share
+
+def check_generation(engine, generation: int) -> None:
+    """The activations, STE masks and qparams of a step live in the engine's one workspace, not in autograd's graph: a later forward (an evaluation
+    under no_grad, a second micro-batch) has overwritten them.  Stock autograd would keep both alive; here the backward would silently differentiate
+    the wrong step - refuse."""
+    if engine.generation != generation:
+        raise RuntimeError(
+            "qat-vit_amd: another forward of this model ran between this forward and its backward; the native step keeps the "
+            "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
+            "forward/backward per micro-batch)."
+        )
+
+
+def assign_grads(params, grads) -> None:
+    """The native backward writes every parameter gradient into one flat buffer; hand the views to the parameters directly (what
+    `zero_grad(set_to_none=True)` + autograd would end up with) instead of returning them, so autograd's AccumulateGrad does not clone 152 tensors
+    per step.  Stock ``DDP(prepared)`` keeps working on top of this because DDP's reducer is driven by post-accumulate-grad hooks that fire when
+    ``.grad`` is assigned here (tests/test_gpu_dp.py); the native bucketed path (``enable_data_parallel``) is the one bench.py measures."""
+    for p, g in zip(params, grads):
+        if p.grad is None:
+            p.grad = g
+        else:
+            p.grad.add_(g)
+
+
+def flat_grad_buffers(params, offsets, numel: int):
+    """(flat, views, pointer table): one zeroed fp32 buffer of `numel` elements, a view of parameter i's shape at offsets[i], and the views'
+    addresses as the `void**` the native backward takes."""
+    import torch
+
+    flat = torch.zeros(numel, dtype=torch.float32, device=params[0].device)
+    views = [flat[offsets[i]:offsets[i] + p.numel()].view(p.shape) for i, p in enumerate(params)]
+    return flat, views, (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
