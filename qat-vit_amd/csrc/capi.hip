@@ -130,7 +130,7 @@ int qatvit_gemm_nt_i8_minmax(const void* A8, const void* B8, const int32_t* wsum
                              void* stream) {
     QV_CHECK_ARG(A8 && B8 && wsum && a_qp && stats, "qatvit_gemm_nt_i8_minmax: null pointer argument");
     NTPost post{};
-    post.mode = 3;
+    post.mode = kEpiStats;
     if (launch_gemm_nt_i8(A8, B8, wsum, a_qp, center, nullptr, M, N, K, lda, ldb, N, s1, s2, col_scale, bias, stats, 1, (hipStream_t)stream, &post)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_nt_i8_minmax");
     return 0;
@@ -147,7 +147,7 @@ int qatvit_i8_strip(int32_t mode, const void* A8, const void* B8f, const int32_t
                     int32_t qmin, int32_t qmax, void* out8, void* out8_mask, int32_t code_T, uint32_t* lut_out, uint32_t* lutq_out,
                     float* out16_scale, void* stream) {
     QV_CHECK_ARG(A8 && B8f && wsum && a_qp && s1, "qatvit_i8_strip: null pointer argument");
-    QV_CHECK_ARG(mode == 3 || mode == 4 || mode == 7, "qatvit_i8_strip: mode %d (3 = statistics, 7 = qkv codes, 4 = fc1 codes)", mode);
+    QV_CHECK_ARG(mode == kEpiStats || mode == kEpiCodes || mode == kEpiQkvCodes, "qatvit_i8_strip: mode %d (3 = statistics, 7 = qkv codes, 4 = fc1 codes)", mode);
     NTPost post{};
     post.mode = mode;
     post.qp = out_qp; post.qmin = qmin; post.qmax = qmax; post.out8 = out8; post.out8_mask = out8_mask; post.code_T = code_T; post.code_hd = 64;

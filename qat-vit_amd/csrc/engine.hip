@@ -288,6 +288,12 @@ struct ProfScope {
         if (on) (void)hipEventRecord(pr->ev[slot + 1], st);
     }
 };
+// the ProfScope kind of an NT GEMM by its epilogue (qv_kernels.h NTEpi).  Forward on grid operands: 2 plain | 7 statistics pass | 8 fc1 storing pass | 9 qkv code
+// pass; dgrad: 1 plain | 4 + fused LayerNorm backward | 5 + fused GELU' (fc2 dgrad).  A statistics-only pass is issued, not algorithmic, work: it counts no flops
+static bool stats_only(const NTPost* post) { return post && post->mode == kEpiStats; }
+static int prof_kind_fwd(const NTPost* post) { return !post ? 2 : post->mode == kEpiStats ? 7 : post->mode == kEpiCodes ? 8 : post->mode == kEpiQkvCodes ? 9 : 2; }
+static int prof_kind_dgrad(const NTPost* post) { return !post ? 1 : post->mode == kEpiLnBwd ? 4 : 5; }
+static NTPost nt_post_stats() { NTPost p{}; p.mode = kEpiStats; return p; }
 
 struct Ctx {
     const qatvit_cfg& c;
@@ -399,7 +405,7 @@ struct Ctx {
         int N, K; wshape(d, wi, &N, &K);
         const qatvit_fq& f = wfq[wi];
         {
-            ProfScope ps(prof, A_lo ? 1 : 2, (post && post->mode == 3) ? 0.0 : 2.0 * M * N * K, st);   // a statistics-only pass is issued, not algorithmic, work
+            ProfScope ps(prof, A_lo ? 1 : 2, stats_only(post) ? 0.0 : 2.0 * M * N * K, st);   // a statistics-only pass is issued, not algorithmic, work
             if (launch_gemm_nt(A_hi, A_lo, at<void>(p.w_off[wi]), C, M, N, K, K, K, N, s_act, c.w_per_channel ? nullptr : f.scale,
                                c.w_per_channel ? f.scale : nullptr, bias, with_stats ? act_stats(ai_out) : nullptr, kStatSlots, st, nullptr, post, false))
                 return 1;
@@ -445,8 +451,8 @@ struct Ctx {
         if (!p.form.i8 || N % 384 != 0 || K % 64 != 0) return linear_fwd(A16, nullptr, M, wi, a_qp, bias, C, ai_out, post, with_stats);
         const qatvit_fq& f = wfq[wi];
         {
-            ProfScope ps(prof, !post ? 2 : post->mode == 3 ? 7 : post->mode == 4 ? 8 : post->mode == 7 ? 9 : 2, (post && post->mode == 3) ? 0.0 : 2.0 * M * N * K, st);
-            const bool code_pass = late_strip && post && post->mode != 3;
+            ProfScope ps(prof, prof_kind_fwd(post), stats_only(post) ? 0.0 : 2.0 * M * N * K, st);
+            const bool code_pass = late_strip && post && !stats_only(post);
             const QpLate L = code_pass ? late(ai_out) : QpLate{};
             if (launch_gemm_nt_i8(A8, at<void>(p.w8_off[wi]), at<int32_t>(p.wsum_off[wi]), a_qp, center(), C, M, N, K, K, K, N, a_qp,
                                   c.w_per_channel ? nullptr : f.scale, c.w_per_channel ? f.scale : nullptr, bias,
@@ -469,7 +475,7 @@ struct Ctx {
     int linear_dgrad(const void* dY_hi, const void* dY_lo, int M, int wi, float* dX, const NTPost* post = nullptr) const {
         int N, K; wshape(d, wi, &N, &K);
         const qatvit_fq& f = wfq[wi];
-        ProfScope ps(prof, !post ? 1 : post->mode == 8 ? 4 : 5, 2.0 * M * N * K, st);   // plain | + fused LayerNorm backward | + fused GELU' (fc2 dgrad)
+        ProfScope ps(prof, prof_kind_dgrad(post), 2.0 * M * N * K, st);
         return launch_gemm_nt(dY_hi, dY_lo, at<void>(p.wT_off[wi]), dX, M, K, N, N, N, K, c.w_per_channel ? nullptr : f.scale, nullptr, nullptr,
                               nullptr, nullptr, 1, st, nullptr, post);
     }
@@ -513,10 +519,10 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
                        x.blk<void>(p.h1q8, i));
         if (F.qkv_2pass) {
             NTPost p2{};
-            p2.mode = 7; p2.qp = x.act_qp(x.aidx(i, AB_QKV)); p2.qmin = qa; p2.qmax = qb;
+            p2.mode = kEpiQkvCodes; p2.qp = x.act_qp(x.aidx(i, AB_QKV)); p2.qmin = qa; p2.qmax = qb;
             p2.out8 = x.blk<void>(p.qkv8, i); p2.out8_mask = x.blk<void>(p.qkvm, i); p2.code_T = (int)d.T; p2.code_hd = (int)(d.D / d.H);
             const bool lt = x.late_in_strip(M, x.widx(i, WB_QKV), &p2);   // the code pass resolves the qkv quantizer's qparams itself: no k_qparams launch between the passes
-            const NTPost p1{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 3, nullptr};
+            const NTPost p1 = nt_post_stats();
             if (ln1) {
                 const Ctx::LnRows r{xin, x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.aidx(i, AB_N1)};
                 if (x.linear_stats_ln(r, x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.bprm(i, B_QKVB), x.aidx(i, AB_QKV), lt)) return 1;
@@ -559,14 +565,15 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
             // feeds the observer (min/max, nothing stored); pass 2 - the same kernel on the same operands, so the same bits - quantises
             // with the fresh qparams and stores gelu(fq(.)) as the (hi, lo) pair fc2 reads plus a uint16 code (grid index | in-range
             // bit) for the backward.  The fp32 pre-FQ tensor and the separate fq+gelu pass (620 MB per block) disappear.
-            NTPost p2{nullptr, x.act_qp(x.aidx(i, AB_FC1)), qa, qb, nullptr, x.blk<void>(p.G_hi, i), x.blk<void>(p.G_lo, i), 4,
-                      x.blk<void>(p.Y1, i)};
+            NTPost p2{};
+            p2.mode = kEpiCodes; p2.qp = x.act_qp(x.aidx(i, AB_FC1)); p2.qmin = qa; p2.qmax = qb;
+            p2.out_hi = x.blk<void>(p.G_hi, i); p2.out_lo = x.blk<void>(p.G_lo, i); p2.code = x.blk<void>(p.Y1, i);
             if (F.fc2_codes) { p2.out8 = x.blk<void>(p.G8, i); p2.lut_out = x.blk<uint32_t>(p.glut, i); p2.out16_scale = scal16 + 1; }
             if (F.fc1_code_bits) { p2.code = nullptr; p2.out8_mask = x.blk<void>(p.Y1m, i); }   // the backward reads the byte plane + mask bits: no uint16 plane
             if (F.fc2w_codes) { p2.out_hi = p2.out_lo = nullptr; p2.lutq_out = x.blk<uint32_t>(p.glutq, i); }   // no 4-byte plane of gelu(fq(fc1)) at all
             else if (F.f16_fc2) { p2.out16_hi = x.at<void>(p.G16_hi); p2.out16_lo = x.at<void>(p.G16_lo); p2.out16_scale = scal16 + 1; }
             const bool lt = x.late_in_strip(M, x.widx(i, WB_FC1), &p2);   // (as for qkv: the code pass resolves the fc1 quantizer's qparams)
-            const NTPost p1{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 3, nullptr};
+            const NTPost p1 = nt_post_stats();
             if (ln2) {
                 const Ctx::LnRows r{xmid, x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.aidx(i, AB_N2)};
                 if (x.linear_stats_ln(r, x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.bprm(i, B_FC1B), x.aidx(i, AB_FC1), lt)) return 1;
@@ -762,7 +769,7 @@ struct Bwd {
     NTPost lnb_post(int i, bool n2, const float* dx_in, const LnBwdNext& nx) const {
         const Plan& p = x.p;
         NTPost post{};
-        post.mode = 8; post.qp = x.act_qp(x.aidx(i, n2 ? AB_N2 : AB_N1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax;
+        post.mode = kEpiLnBwd; post.qp = x.act_qp(x.aidx(i, n2 ? AB_N2 : AB_N1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax;
         post.lnb_x = x.blk<float>(n2 ? p.x_mid : p.x_in, i); post.lnb_mean = x.blk<float>(n2 ? p.mean2 : p.mean1, i); post.lnb_rstd = x.blk<float>(n2 ? p.rstd2 : p.rstd1, i);
         post.lnb_gamma = x.bprm(i, n2 ? B_N2W : B_N1W); post.lnb_beta = x.bprm(i, n2 ? B_N2B : B_N1B); post.lnb_dx_in = dx_in;
         post.lnb_dgamma = BG(i, n2 ? B_N2W : B_N1W); post.lnb_dbeta = BG(i, n2 ? B_N2B : B_N1B);
@@ -773,7 +780,7 @@ struct Bwd {
     // NTPost mode 9: the fc2 dgrad of block i applies the GELU backward and fc1's STE mask from the forward's byte codes + mask bits: the fc1 output gradient
     NTPost gelu_post(int i, void* out_hi, void* out_lo) const {
         NTPost post{};
-        post.mode = 9; post.qp = x.act_qp(x.aidx(i, AB_FC1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax; post.colscale = x.dy_colscale(x.widx(i, WB_FC1));
+        post.mode = kEpiGeluBwdU8; post.qp = x.act_qp(x.aidx(i, AB_FC1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax; post.colscale = x.dy_colscale(x.widx(i, WB_FC1));
         post.out_hi = out_hi; post.out_lo = out_lo; post.code8 = x.blk<void>(x.p.G8, i); post.code_mask = x.blk<void>(x.p.Y1m, i);
         return post;
     }
@@ -842,7 +849,7 @@ int Bwd::block_one_plane(int i, bool injected) {
     };
     auto dgrad16 = [&](const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
         int N, K; wshape(d, wi, &N, &K);
-        ProfScope ps(x.prof, !post ? 1 : post->mode == 8 ? 4 : 5, 2.0 * M * N * K, st);
+        ProfScope ps(x.prof, prof_kind_dgrad(post), 2.0 * M * N * K, st);
         return launch_gemm_nt_dy16(P16, x.wT16(wi), dX, M, K, N, N, N, K, wscale1(wi), x.dy_inv(i, k), st, post);
     };
     // ---- MLP branch
@@ -917,7 +924,7 @@ int Bwd::block_pair(int i, bool injected) {
     } else if (x.linear_wgrad(dYh, dYl, M, w_fc2, x.blk<void>(p.G_hi, i), x.blk<void>(p.G_lo, i), nullptr, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
     {   // fc2 dgrad with the GELU backward + fc1's STE mask fused into its epilogue: dY1 = (dYs . W_fc2) * gelu'(fq(Y1)) * mask(Y1)
         NTPost post = gelu_post(i, x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo));
-        if (!F.fc1_code_bits) { post.mode = 5; post.code = x.blk<void>(p.Y1, i); post.code8 = post.code_mask = nullptr; }   // the Y1 slot holds the uint16 codes
+        if (!F.fc1_code_bits) { post.mode = kEpiGeluBwdU16; post.code = x.blk<void>(p.Y1, i); post.code8 = post.code_mask = nullptr; }   // the Y1 slot holds the uint16 codes
         if (x.linear_dgrad(dYh, dYl, M, w_fc2, nullptr, &post)) return 1;
     }
     calib(x.at<void>(p.dY1_hi), d.M * d.Hd, i, DS_FC1);

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
 // true when the strip kernel took the request (K = 384, N = 1536: ViT-S's fc2 dgrad); false -> launch_gemm_nt_dy16 with epilogue mode 9
 bool launch_f16_strip_gelu_bwd(const void* A16, const void* B16f, float* /*unused*/, int M, int N, int K, int lda, int ldc, const float* s1, const float* s2, hipStream_t st,
                                const NTPost* post) {
-    if (!knobs().f16_strip || !A16 || !B16f || !post || post->mode != 9 || K != 384 || N != 4 * 384 || lda % 8 != 0 || ldc % 128 != 0 || !post->qp || !post->out_hi ||
+    if (!knobs().f16_strip || !A16 || !B16f || !post || post->mode != kEpiGeluBwdU8 || K != 384 || N != 4 * 384 || lda % 8 != 0 || ldc % 128 != 0 || !post->qp || !post->out_hi ||
         !post->code8 || !post->code_mask || !post->o16_mul || !post->o16_amax || post->qmax - post->qmin >= 256)
         return false;
     if ((int64_t)M * lda * 2 >= (1ll << 32) || (int64_t)M * ldc >= (1ll << 32)) return false;   // the 32-bit DMA offsets

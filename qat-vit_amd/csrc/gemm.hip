@@ -43,41 +43,30 @@ struct NTArgs {
     const float* bias;       // optional [N]
     uint32_t* stats;         // optional {ordered-min, ordered-max} accumulator of the stored values
     int stat_slots;          // number of 128-B-spaced accumulator pairs (power of two; 1 = a single pair)
-    // Optional fused consumer (fc2 dgrad -> GELU backward): instead of storing C, store the (hi, lo) bf16 pair of
-    //   C * gelu'(fq(Y)) * mask(Y) * post_colscale[col],  Y = the pre-FQ fc1 output [M,ldc], post_qp = {scale, 1/scale, zp, enabled}
-    int post_gelu_fwd;       // 1: store (hi, lo) of gelu(C) to out_hi / out_lo instead of C (no Y, no mask)
-    int out_f16;             // with post_gelu_fwd: the pair in fp16 (out_lo may be NULL) - the fp16 teacher forward
-    int post_mode;           // NTPost::mode 3 / 4 / 5 (0 otherwise)
+    // ---- the epilogue's operands: nt_set_post copies them from the NTPost record, whose table (qv_kernels.h, NTEpi) says which mode reads which.
+    // post_gelu_fwd, post_mode and pm are HOST-ONLY (no kernel reads them: the kernel's epilogue is its template parameter PM); they stay because
+    // removing them would shift every NT kernel's argument offsets ("NT epilogues": follow-up)
+    int post_gelu_fwd;       // host only: mode == kEpiGeluFwd
+    int out_f16;
+    int post_mode;           // host only: NTPost::mode
     // int8 operands (template flag I8): A holds q - center, B the weight integers; the k extent / strides are then counted in 2-byte units
     const int32_t* i8_wsum;  // [N] row sums of the int8 weight: C = (acc + (center - zp) * wsum[n]) * alpha + bias
     const float* i8_aqp;     // qparams {s, 1/s, zp, on} of the A operand's quantizer (zp enters the correction)
     int i8_center;
-    int pm;                  // which epilogue the kernel instantiation contains (template parameter PM): 0 plain, 2 = gelu fwd, 3 / 4 / 5
-    uint16_t* post_code;     // mode 4: out, mode 5: in
+    int pm;                  // host only: the instantiation nt_launch picks (PM): an NTEpi value or one of the kPm* ids below
+    uint16_t* post_code;     // NTPost::code
     const float* post_qp;
     int post_qmin, post_qmax;
     const float* post_colscale;
     __bf16* out_hi;
     __bf16* out_lo;
-    // mode 4 (optional): the same gelu(fq(C)) a second time as an fp16 (hi, lo) pair pre-scaled by a power of two (the A operand of the fc2
-    // FORWARD GEMM); *out16_scale receives the factor that takes the pair back to real units
     _Float16* out16_hi;
     _Float16* out16_lo;
     float* out16_scale;
-    // inference epilogues (frozen qparams in post_qp; no statistics, no pre-FQ tensor):
-    //   mode 6: C[orow] = resid[rrow] + fq(acc)        residual stream update (proj / fc2); embed_np > 0: patch-embedding form, input row
-    //           m = b * np + p goes to token row b * (np + 1) + 1 + p and resid = pos[1 + p]
-    //   mode 7: out8 = clamp(q) - qmin as uint8 in the attention code-plane layout [b][h][which][t][d] (qkv)
     const float* resid;
     int embed_np;
     uint8_t* out8;
     int code_T, code_hd;
-    // mode 8 (N == BN == D: the tile holds whole rows): the LayerNorm BACKWARD of the tensor this dgrad differentiates, fused - the fp32
-    // gradient w.r.t. the fake-quantised LayerNorm output never goes to memory.  With dH = acc * alpha:
-    //   g = dH * mask(LN(x)) ; dx_out = dx_in + LNbwd(g) ; dgamma += sum_rows g * xhat ; dbeta += sum_rows g ;
-    //   out_hi / out_lo (optional) = split(dx_out * nmask * post_colscale): the masked gradient of the NEXT (earlier) branch output
-    // (what k_ln_bwd_fq<1, NV, 8, true> computes from a dH it reads back from memory).  post_qp / post_qmin / post_qmax = the LayerNorm
-    // output's quantizer; C = dx_out.
     const float* lnb_x;
     const float* lnb_mean;
     const float* lnb_rstd;
@@ -87,24 +76,18 @@ struct NTArgs {
     float* lnb_dgamma;
     float* lnb_dbeta;
     const unsigned long long* lnb_nmask;
-    // mode 4 (optional): out8 = the grid index (q - qmin) of every element as uint8 [M, ldc] and lut_out[256] = the packed fp16 (hi | lo << 16)
-    // pair of 2^k * gelu(grid value) per index - together the A operand of k_gemm_nt_ac (fc2 forward from codes: 1 B instead of 4 B per element)
     uint32_t* lut_out;
     const uint32_t* a_lut;   // k_gemm_nt_ac: the table its uint8 A operand (A0, lda in BYTES) is expanded through
-    // mode 7 (optional, training): the STE mask bit of every element (t = rint(v / s) + zp inside [qmin, qmax]) next to the codes, one bit per
-    // element in the same [b][h][which][t][d] order (bit d % 8 of byte (... * hd + d) / 8) - what the attention forward writes when it quantises itself
     uint8_t* out8_mask;
-    // mode 9 = mode 5 with the fc1 codes as ONE byte per element (the plane fc2's forward reads: post_code8 [M, ldc]) + the STE mask as one bit per
-    // element (post_mask: bit c % 8 of byte (row * ldc + c) / 8) instead of the uint16 plane: 1.125 instead of 2 B per element read here, and the
-    // fc1 storing pass (mode 4 with out8_mask) writes 0.125 instead of 2 B per element for the backward
-    const uint8_t* post_code8;
-    const uint8_t* post_mask;
-    uint32_t* lutq_out;      // mode 4 (optional): the 256-entry table of bf16 (hi | lo << 16) pairs of gelu(grid value) - the table the fc2 weight gradient expands the codes through
-    // modes 18 / 19 (= 8 / 9 of the one-plane backward, launch_gemm_nt_dy16): the gradient pair out_hi / out_lo becomes ONE fp16 plane (out_hi) of
-    // value * (*o16_mul), a power of two chosen before the step (dy16.hip); max |value| goes into o16_amax (8 sub-slots, 32 B apart) for the next step's choice
+    const uint8_t* post_code8;   // NTPost::code8
+    const uint8_t* post_mask;    // NTPost::code_mask
+    uint32_t* lutq_out;
     const float* o16_mul;
     uint32_t* o16_amax;
 };
+// instantiation ids beyond the NTEpi values (NTArgs::pm / PM only; no caller names them)
+constexpr int kPmCodesF16 = 10;                        // kEpiCodes that also (or only) writes the fp16 (hi, lo) planes
+constexpr int kPmLnBwdO16 = 18, kPmGeluBwdO16 = 19;   // kEpiLnBwd / kEpiGeluBwdU8 + 10: the masked gradient leaves as ONE scaled fp16 plane (launch_gemm_nt_dy16)
 
 constexpr int kStandIn = 512;
 struct OnesTab { float v[kStandIn]; constexpr OnesTab() : v() { for (int i = 0; i < kStandIn; ++i) v[i] = 1.f; } };
@@ -113,7 +96,7 @@ __device__ const OnesTab kOnes{};
 __device__ const ZerosTab kZeros{};
 
 // ---- shared epilogue of the NT kernels.  WM x WN waves, wave (wm, wn) holds a (16*TM) x (16*TNT) sub-tile in acc[][].
-// PM: the epilogue variant compiled into this instantiation (one per kernel: a monolithic epilogue with every mode selected at run time
+// PM: the epilogue variant compiled into this instantiation - an NTEpi value (the table in qv_kernels.h says what each stores and reads) or a kPm* id (one per kernel: a monolithic epilogue with every mode selected at run time
 // needs 100 more registers than the accumulators leave and spills them)
 #ifdef QV_NT_EXPERIMENTS   // development builds only (-DQV_NT_EXPERIMENTS=<epilogue mode>): s_memtime stamps of that mode's phases, workgroups 0 and 100, every
 __device__ unsigned long long g_nt_stamps[2 * 8 * 16];   // wave; read back with qatvit_debug_nt_stamps (tools/stamp_nt.py).  The shipped library has none.
@@ -139,8 +122,8 @@ template <int WM, int WN, int TM, int TNT, int SLAB = 64, int PM = 0, int RING =
 __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4, f32x4> (&acc)[TM][TNT], char* smem, int m0, int n0, int tid, int lane, int wave, int wm, int wn,
                                    int r, int g) {
     constexpr int WR = 16 * TM, WC = 16 * TNT, BM = WR * WM, BN = WC * WN, NW = WN * WM;
-    constexpr bool O16 = PM == 18 || PM == 19;             // the masked gradient leaves as one scaled fp16 plane instead of a bf16 (hi, lo) pair
-    constexpr int PMB = PM == 18 ? 8 : PM == 19 ? 9 : PM;  // the epilogue this instantiation contains
+    constexpr bool O16 = PM == kPmLnBwdO16 || PM == kPmGeluBwdO16;             // the masked gradient leaves as one scaled fp16 plane instead of a bf16 (hi, lo) pair
+    constexpr int PMB = PM == kPmLnBwdO16 ? kEpiLnBwd : PM == kPmGeluBwdO16 ? kEpiGeluBwdU8 : PM;  // the epilogue this instantiation contains
     float o16_mul = 1.f, o16_am = 0.f;
     if constexpr (O16) o16_mul = *p.o16_mul;
     // ---- epilogue: C = acc * alpha[col] + bias[col]; min/max of what is stored.
@@ -158,7 +141,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
     float* sC = reinterpret_cast<float*>(smem); // [SLAB][LDC]
     // fused GELU backward: fq(Y) only takes qmax-qmin+1 (<= 256) values, so gelu'(fq(Y)) is a table (no erf/exp per element)
     float* sLut = sC + SLAB * LDC;
-    constexpr bool P5 = PMB == 5 || PMB == 9;   // fc2 dgrad + GELU backward; 9: codes as uint8 + mask bits
+    constexpr bool P5 = PMB == kEpiGeluBwdU16 || PMB == kEpiGeluBwdU8;   // fc2 dgrad + GELU backward; 9: codes as uint8 + mask bits
     if constexpr (P5) {
         if (tid <= p.post_qmax - p.post_qmin) sLut[tid] = gelu_bwd(((float)(tid + p.post_qmin) - p.post_qp[2]) * p.post_qp[0]);
         // (published by the __syncthreads() between staging and the store loop below)
@@ -166,9 +149,9 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
     uint32_t* sLutF = reinterpret_cast<uint32_t*>(sLut);   // mode 4: packed (hi | lo << 16) bf16 pair of gelu(grid value)
     // mode 5: the slab's uint16 codes come in by LDS-DMA next to the staged tile while the accumulators are being staged (a global load
     // per store-loop iteration is a load-use chain at 8 waves per CU: fc2 dgrad took 296 us against 160 us for the plain store)
-    constexpr int CODE_BYTES = PMB == 9 ? SLAB * BN + SLAB * BN / 8 : SLAB * BN * 2;   // (mode 9: the slab's codes, then its mask bits)
+    constexpr int CODE_BYTES = PMB == kEpiGeluBwdU8 ? SLAB * BN + SLAB * BN / 8 : SLAB * BN * 2;   // (mode 9: the slab's codes, then its mask bits)
     constexpr bool CODE_LDS = P5 && RING >= SLAB * LDC * 4 + 1024 + CODE_BYTES && CODE_BYTES % 1024 == 0;
-    static_assert(PMB != 9 || (CODE_LDS && (SLAB * BN) % 1024 == 0 && (SLAB * BN / 8) % 1024 == 0), "mode 9: whole 1-KiB pieces of codes and of mask bits");
+    static_assert(PMB != kEpiGeluBwdU8 || (CODE_LDS && (SLAB * BN) % 1024 == 0 && (SLAB * BN / 8) % 1024 == 0), "mode 9: whole 1-KiB pieces of codes and of mask bits");
     // two code buffers when they fit: slab h + 1's codes are requested before slab h is staged and arrive under its store loop (one
     // buffer exposes most of a 37-49 KB fetch per slab: a CU fills at ~20-30 GB/s)
     constexpr bool CODE_DB = CODE_LDS && RING >= SLAB * LDC * 4 + 1024 + 2 * CODE_BYTES;
@@ -183,7 +166,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
     }
     auto code_dma = [&](int h, char* dst) -> int {   // returns the number of DMA instructions this wave issued
         int n = 0;
-        if constexpr (PMB == 9) {
+        if constexpr (PMB == kEpiGeluBwdU8) {
             const __amdgpu_buffer_rsrc_t rC8 = make_rsrc(p.post_code8, (int64_t)p.M * p.ldc);
             const __amdgpu_buffer_rsrc_t rMk = make_rsrc(p.post_mask, (int64_t)p.M * p.ldc / 8);
             constexpr int PC = SLAB * BN / 1024, PMK = SLAB * BN / 8 / 1024;
@@ -209,7 +192,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
         return n;
     };
     uint32_t* sLutH = sLutF + 256;   // mode 4: packed fp16 (hi | lo << 16) pair of 2^k * gelu(grid value)
-    constexpr bool P4 = PM == 4 || PM == 10;   // fc1 storing pass; 10: the form that also (or only) writes the fp16 (hi, lo) planes
+    constexpr bool P4 = PM == kEpiCodes || PM == kPmCodesF16;   // fc1 storing pass; 10: the form that also (or only) writes the fp16 (hi, lo) planes
     if constexpr (P4) {
         static_assert(RING == 0 || RING >= SLAB * LDC * 4 + 2048, "ring too small for the two mode-4 tables");
         // |gelu(x)| <= |x|, so the largest grid magnitude bounds the table: 2^k maps it into [2^13, 2^14) - inside fp16's range with
@@ -260,7 +243,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
         return (t >= fmin_ && t <= fmax_) || qq.on == 0.f;
     };
     float4 lnb_ag[2], lnb_ab[2];
-    if constexpr (PMB == 8) {
+    if constexpr (PMB == kEpiLnBwd) {
         static_assert(RING == 0 || RING >= SLAB * LDC * 4 + 2048 + 3 * BN * 4, "ring too small for the mode-8 row operands");
         float* sRow = sC + SLAB * LDC + 512;   // published by the first slab's staging barrier
         for (int c = tid; c < BN; c += NW * 64) {
@@ -270,7 +253,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
         }
         lnb_ag[0] = lnb_ag[1] = lnb_ab[0] = lnb_ab[1] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    if constexpr (PM == 3) {   // statistics only: no staging, no stores
+    if constexpr (PM == kEpiStats) {   // statistics only: no staging, no stores
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -305,7 +288,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                     const int rl = rt - SLAB * h + 4 * g + e;
                     const float v = accv(i, j, e) * ca[j] + cb[j];
                     sC[rl * LDC + cl] = v;
-                    if constexpr (PM != 6 && PM != 7 && PMB != 8) {   // (the inference epilogues and the fused LayerNorm backward feed no observer)
+                    if constexpr (PM != kEpiResidFq && PM != kEpiQkvCodes && PMB != kEpiLnBwd) {   // (the inference epilogues and the fused LayerNorm backward feed no observer)
                         if (m0 + SLAB * h + rl < p.M) { mn = fminf(mn, v); mx = fmaxf(mx, v); }
                     }
                 }
@@ -327,7 +310,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
         QV_NT_STAMP(PM, 5 + 2 * h);   // slab h staged (and its codes arrived)
         constexpr int C4 = BN / 4;              // float4 per staged row
         const int rows_h = BM - SLAB * h < SLAB ? BM - SLAB * h : SLAB;
-        if constexpr (PMB == 8) {
+        if constexpr (PMB == kEpiLnBwd) {
             // one wave per staged row (k_ln_bwd_fq's lane -> column map: lane * 4 + 256 j), the next row's global operands requested one row ahead
             static_assert(BN == 384, "the fused LayerNorm backward needs the whole 384-column row in the tile");
             constexpr int NVL = 2;
@@ -412,11 +395,11 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
             }
             continue;   // next slab (the lds_barrier at its top orders these reads of sC before the next staging)
         }
-        if constexpr (PM == 0 || P4 || P5 || PM == 7) {
+        if constexpr (PM == kEpiPlain || P4 || P5 || PM == kEpiQkvCodes) {
             // Software-pipelined store loop: U iterations' LDS reads (staged values, codes), then their table lookups, then the stores.
             // The rolled loop below is one LDS round trip (two with a table) per 16 B stored at two waves per SIMD; the row guard moves
             // onto the stores so that no branch separates the reads.
-            constexpr int U = PM == 10 ? 2 : 4, NT_ = NW * 64;   // (the fp16-plane form keeps three lookups per element live: four iterations in flight spill)
+            constexpr int U = PM == kPmCodesF16 ? 2 : 4, NT_ = NW * 64;   // (the fp16-plane form keeps three lookups per element live: four iterations in flight spill)
             const int limit = rows_h * C4;
             for (int base = tid; base < limit; base += U * NT_) {
                 float4 v[U];
@@ -432,22 +415,22 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                     off[u] = (int64_t)row * p.ldc + n0 + 4 * c4;
                     const int rls = idx < limit ? rl : 0;      // (stay inside the staged slab)
                     v[u] = *reinterpret_cast<const float4*>(sC + rls * LDC + 4 * c4);
-                    if constexpr (PMB == 9) {   // .x = the four codes, .y = their four mask bits
+                    if constexpr (PMB == kEpiGeluBwdU8) {   // .x = the four codes, .y = their four mask bits
                         c2[u].x = *reinterpret_cast<const uint32_t*>(sCodeH + rls * BN + 4 * c4);
                         c2[u].y = ((uint32_t) reinterpret_cast<const uint8_t*>(sCodeH)[SLAB * BN + ((rls * BN + 4 * c4) >> 3)] >> (4 * (c4 & 1))) & 0xfu;
-                    } else if constexpr (PMB == 5) {
+                    } else if constexpr (PMB == kEpiGeluBwdU16) {
                         if constexpr (CODE_LDS) c2[u] = *reinterpret_cast<const uint2*>(sCodeH + (rls * BN + 4 * c4) * 2);
                         else c2[u] = ok[u] ? *reinterpret_cast<const uint2*>(p.post_code + off[u]) : make_uint2(0u, 0u);
                     }
                 }
-                if constexpr (PM == 0) {
+                if constexpr (PM == kEpiPlain) {
 #pragma unroll
                     for (int u = 0; u < U; ++u)
                         if (ok[u]) *reinterpret_cast<float4*>(p.C + off[u]) = v[u];
                 } else if constexpr (P4) {
                     const float qinv = p.post_qp[1], qzp = p.post_qp[2], fmin_ = (float)p.post_qmin, fmax_ = (float)p.post_qmax;
-                    const bool w16 = PM == 10 && p.out16_hi != nullptr, wbf = p.out_hi != nullptr, w8 = p.out8 != nullptr;   // uniform
-                    uint32_t w[U][4], wh[PM == 10 ? U : 1][4], cd[U][4];
+                    const bool w16 = PM == kPmCodesF16 && p.out16_hi != nullptr, wbf = p.out_hi != nullptr, w8 = p.out8 != nullptr;   // uniform
+                    uint32_t w[U][4], wh[PM == kPmCodesF16 ? U : 1][4], cd[U][4];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const float cv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
@@ -456,7 +439,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                             const float t = rintf(cv[e] * qinv) + qzp;
                             const uint32_t ix = (uint32_t)(int)(fminf(fmaxf(t, fmin_), fmax_) - fmin_);
                             w[u][e] = wbf ? sLutF[ix] : 0u;   // (uniform: the codes-only form of the pass looks nothing up)
-                            if constexpr (PM == 10) wh[u][e] = sLutH[ix];
+                            if constexpr (PM == kPmCodesF16) wh[u][e] = sLutH[ix];
                             cd[u][e] = ix | ((t >= fmin_ && t <= fmax_) ? 0x8000u : 0u);
                         }
                     }
@@ -465,7 +448,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                         uint2 hi2, lo2, cc, h16, l16;
                         hi2.x = (w[u][0] & 0xffffu) | (w[u][1] << 16); hi2.y = (w[u][2] & 0xffffu) | (w[u][3] << 16);
                         lo2.x = (w[u][0] >> 16) | (w[u][1] & 0xffff0000u); lo2.y = (w[u][2] >> 16) | (w[u][3] & 0xffff0000u);
-                        if constexpr (PM == 10) {
+                        if constexpr (PM == kPmCodesF16) {
                             h16.x = (wh[u][0] & 0xffffu) | (wh[u][1] << 16); h16.y = (wh[u][2] & 0xffffu) | (wh[u][3] << 16);
                             l16.x = (wh[u][0] >> 16) | (wh[u][1] & 0xffff0000u); l16.y = (wh[u][2] >> 16) | (wh[u][3] & 0xffff0000u);
                         } else h16 = l16 = make_uint2(0u, 0u);
@@ -489,7 +472,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                         if (ok[u] && w8)
                             *reinterpret_cast<uint32_t*>(p.out8 + off[u]) = (cd[u][0] & 0xffu) | ((cd[u][1] & 0xffu) << 8) | ((cd[u][2] & 0xffu) << 16) | (cd[u][3] << 24);
                     }
-                } else if constexpr (PM == 7) {
+                } else if constexpr (PM == kEpiQkvCodes) {
                     const float qinv = p.post_qp[1], qzp = p.post_qp[2], fmin_ = (float)p.post_qmin, fmax_ = (float)p.post_qmax;
                     // element offset in the [b][h][which][t][d] plane without integer divisions: (x + 0.5) * (1 / n) floors exactly for x < 2^22, n < 2^10
                     // (the error of the product stays far below the 0.5 / n distance to the next integer); head_dim is a power of two
@@ -521,12 +504,12 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                             if (p.out8_mask && (lane & 7) == 0) *reinterpret_cast<uint32_t*>(p.out8_mask + (eo >> 3)) = mk;
                         }
                     }
-                } else {   // PM == 5 / 9
+                } else {   // PM == kEpiGeluBwdU16 / 9
                     float dg[U][4];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
-                        const uint32_t cd[4] = {PMB == 9 ? c2[u].x : c2[u].x & 0xffffu, PMB == 9 ? c2[u].x >> 8 : c2[u].x >> 16,
-                                                PMB == 9 ? c2[u].x >> 16 : c2[u].y & 0xffffu, PMB == 9 ? c2[u].x >> 24 : c2[u].y >> 16};
+                        const uint32_t cd[4] = {PMB == kEpiGeluBwdU8 ? c2[u].x : c2[u].x & 0xffffu, PMB == kEpiGeluBwdU8 ? c2[u].x >> 8 : c2[u].x >> 16,
+                                                PMB == kEpiGeluBwdU8 ? c2[u].x >> 16 : c2[u].y & 0xffffu, PMB == kEpiGeluBwdU8 ? c2[u].x >> 24 : c2[u].y >> 16};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) dg[u][e] = sLut[cd[e] & 0xffu];   // (unconditional: no branch between the lookups)
                     }
@@ -540,7 +523,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const uint32_t cde = (e & 1) ? ((e & 2) ? c2[u].y : c2[u].x) >> 16 : ((e & 2) ? c2[u].y : c2[u].x);
-                            const bool in_range = PMB == 9 ? ((c2[u].y >> e) & 1u) != 0 : (cde & 0x8000u) != 0;
+                            const bool in_range = PMB == kEpiGeluBwdU8 ? ((c2[u].y >> e) & 1u) != 0 : (cde & 0x8000u) != 0;
                             o[e] = in_range ? cv[e] * dg[u][e] * sv[e] : 0.f;
                         }
                         if constexpr (O16) {
@@ -596,7 +579,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                         *reinterpret_cast<uint2*>(p.out16_lo + off) = l16;
                     }
                     if (p.out8) *reinterpret_cast<uint32_t*>(p.out8 + off) = (cd[0] & 0xffu) | ((cd[1] & 0xffu) << 8) | ((cd[2] & 0xffu) << 16) | (cd[3] << 24);
-                } else if constexpr (PM == 5) {
+                } else if constexpr (PM == kEpiGeluBwdU16) {
                     uint2 c2;
                     if constexpr (CODE_LDS) c2 = *reinterpret_cast<const uint2*>(sCodeH + (rl * BN + 4 * c4) * 2);
                     else c2 = *reinterpret_cast<const uint2*>(p.post_code + off);
@@ -613,7 +596,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                     }
                     *reinterpret_cast<bf16x4*>(p.out_hi + off) = oh;
                     *reinterpret_cast<bf16x4*>(p.out_lo + off) = ol;
-                } else if constexpr (PM == 6) {
+                } else if constexpr (PM == kEpiResidFq) {
                     const float qs = p.post_qp[0], qinv = p.post_qp[1], qzp = p.post_qp[2], fmin_ = (float)p.post_qmin, fmax_ = (float)p.post_qmax;
                     int64_t orow = row, rrow = row;
                     if (p.embed_np > 0) { orow = row + row / p.embed_np + 1; rrow = 1 + row % p.embed_np; }
@@ -625,7 +608,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                     o.z = rs.z + fq_one(v.z, qinv, qs, qzp, fmin_, fmax_, in);
                     o.w = rs.w + fq_one(v.w, qinv, qs, qzp, fmin_, fmax_, in);
                     *reinterpret_cast<float4*>(p.C + orow * p.ldc + n0 + 4 * c4) = o;
-                } else if constexpr (PM == 7) {
+                } else if constexpr (PM == kEpiQkvCodes) {
                     const float qinv = p.post_qp[1], qzp = p.post_qp[2], fmin_ = (float)p.post_qmin, fmax_ = (float)p.post_qmax;
                     const float cv[4] = {v.x, v.y, v.z, v.w};
                     uint32_t pk = 0, mk = 0;
@@ -646,7 +629,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                         for (int k = 1; k < 8; ++k) mk |= ((uint32_t)__shfl_down((int)(mk & 0xfu), k, 64) & 0xfu) << (4 * k);
                         if ((lane & 7) == 0) *reinterpret_cast<uint32_t*>(p.out8_mask + eo / 8) = mk;
                     }
-                } else if constexpr (PM == 2) {
+                } else if constexpr (PM == kEpiGeluFwd) {
                     const float cv[4] = {v.x, v.y, v.z, v.w};
                     if (p.out_f16) {   // (uniform) the fp16 teacher forward: the pair (or, out_lo == NULL, the hi part alone) in fp16
                         f16x4 oh, ol;
@@ -675,7 +658,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
             }
         }
     }
-    if constexpr (PMB == 8) {   // dgamma / dbeta: the tile's column sums meet in LDS, one atomic per column per tile
+    if constexpr (PMB == kEpiLnBwd) {   // dgamma / dbeta: the tile's column sums meet in LDS, one atomic per column per tile
         lds_barrier();
         float* sg = reinterpret_cast<float*>(smem);          // [NW][BN]
         float* sb = sg + NW * BN;
@@ -879,12 +862,12 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64) / 256) void k_gemm_nt(
     QV_NT_STAMP(PM, 3);   // k-loop done
     // the staging slab (+ LUT, + the codes of mode 5) must fit inside the ring; mode 5 prefers 48 rows with two code buffers to 64 with one
     constexpr int RING_ = NSTAGE * STAGE;
-    constexpr bool PM5_48 = PM == 5 && RING_ >= 48 * (BN + 4) * 4 + 1024 + 2 * 48 * BN * 2 && RING_ < 64 * (BN + 4) * 4 + 1024 + 2 * 64 * BN * 2;
+    constexpr bool PM5_48 = PM == kEpiGeluBwdU16 && RING_ >= 48 * (BN + 4) * 4 + 1024 + 2 * 48 * BN * 2 && RING_ < 64 * (BN + 4) * 4 + 1024 + 2 * 64 * BN * 2;
     // mode 8 (fused LayerNorm backward) stages 96 rows at a time in 160 KiB of LDS (the launch asks for it): 84 instead of 108 accumulator
     // registers are still live while the first slab's rows are processed
     // mode 9: 64 rows + two (codes + mask bits) buffers of 27 KiB need 154 KiB: the launch asks for 160 like mode 8
-    constexpr int SLAB = (PM == 8 || PM == 18) ? 96 : (PM == 9 || PM == 19) ? 64 : PM5_48 ? 48 : RING_ >= 64 * (BN + 4) * 4 + 1024 ? 64 : 32;
-    constexpr int EPI_LDS = (PM == 8 || PM == 9 || PM == 18 || PM == 19) ? 160 * 1024 : NSTAGE * STAGE;
+    constexpr int SLAB = (PM == kEpiLnBwd || PM == kPmLnBwdO16) ? 96 : (PM == kEpiGeluBwdU8 || PM == kPmGeluBwdO16) ? 64 : PM5_48 ? 48 : RING_ >= 64 * (BN + 4) * 4 + 1024 ? 64 : 32;
+    constexpr int EPI_LDS = (PM == kEpiLnBwd || PM == kEpiGeluBwdU8 || PM == kPmLnBwdO16 || PM == kPmGeluBwdO16) ? 160 * 1024 : NSTAGE * STAGE;
     static_assert(EPI_LDS >= SLAB * (BN + 4) * 4 + 1024, "ring too small for the epilogue slab");
     nt_epilogue<WM, WN, TM, TNT, SLAB, PM, EPI_LDS, I8>(p, acc, smem, m0, n0, tid, lane, wave, wm, wn, r, g);
     QV_NT_STAMP(PM, 12);   // stores issued
@@ -1033,54 +1016,75 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_ac(const NTArgs p) {
 }
 
 
-// one kernel instantiation per epilogue variant (NTArgs::pm)
+// one kernel instantiation per epilogue variant (NTArgs::pm); a (operand form, pm, tile) combination that has none is an error, never a silent no-op
 template <int TA, int NS, int WM, int TM, int TB, int WN, int TNT, int BK, bool I8 = false, bool F16 = false>
-static void nt_launch(const NTArgs& a, int grid, size_t lds, hipStream_t st) {
+static int nt_launch(const NTArgs& a, int grid, size_t lds, hipStream_t st) {
 #define QV_PM(PM_)                                                                                             \
     do {                                                                                                       \
         static bool once = (allow_lds(k_gemm_nt<TA, NS, WM, TM, TB, WN, TNT, BK, PM_, I8, F16>, lds), true);   \
         (void)once;                                                                                            \
         k_gemm_nt<TA, NS, WM, TM, TB, WN, TNT, BK, PM_, I8, F16><<<grid, WM * WN * 64, lds, st>>>(a);          \
+        return 0;                                                                                              \
     } while (0)
-    if constexpr (F16) {   // proj / fc2 forward: plain epilogue (training: the observer needs the pre-FQ tensor) or the fused residual update (inference)
-        if (a.pm == 6) QV_PM(6);
-        else if (a.pm == 2) QV_PM(2);
-        else if (a.pm == 18 || a.pm == 19) {   // the one-plane backward: dgrad + fused LayerNorm backward / GELU backward (launch_gemm_nt_dy16)
-            if constexpr (TA == 1 && TB == 1 && WM == 1 && WN * TNT == 24 && TM == 13) { if (a.pm == 18) QV_PM(18); else QV_PM(19); }
-        } else QV_PM(0);
+    constexpr bool tall1 = TB == 1 && WM == 1 && WN * TNT == 24 && TM == 13;   // the 208 x 384 tile (whole 384-column rows), one B part
+    if constexpr (F16) {   // proj / fc2 forward: plain (training: the observer needs the pre-FQ tensor) or the fused residual update (inference); the teacher's fc1
+        switch (a.pm) {
+            case kEpiResidFq: QV_PM(kEpiResidFq);   // (case order = instantiation order = the functions' order in the object file: keep it, tools/isa_digest.py listings stay comparable)
+            case kEpiGeluFwd: QV_PM(kEpiGeluFwd);
+            case kPmLnBwdO16: if constexpr (TA == 1 && tall1) QV_PM(kPmLnBwdO16); break;       // the one-plane backward (launch_gemm_nt_dy16)
+            case kPmGeluBwdO16: if constexpr (TA == 1 && tall1) QV_PM(kPmGeluBwdO16); break;
+            case kEpiPlain: QV_PM(kEpiPlain);
+        }
     } else if constexpr (I8) {   // the grid x grid forward GEMMs
         switch (a.pm) {
-            case 3: QV_PM(3); break;
-            case 4: QV_PM(4); break;
-            case 10: QV_PM(10); break;
-            case 6: QV_PM(6); break;
-            case 7: QV_PM(7); break;
-            default: QV_PM(0); break;
+            case kEpiStats: QV_PM(kEpiStats);
+            case kEpiCodes: QV_PM(kEpiCodes);
+            case kPmCodesF16: QV_PM(kPmCodesF16);
+            case kEpiResidFq: QV_PM(kEpiResidFq);
+            case kEpiQkvCodes: QV_PM(kEpiQkvCodes);
+            case kEpiPlain: QV_PM(kEpiPlain);
         }
     } else {
         switch (a.pm) {
-            case 2: QV_PM(2); break;
-            case 3: QV_PM(3); break;
-            case 4: QV_PM(4); break;
-            case 10: QV_PM(10); break;
-            case 5: QV_PM(5); break;
-            case 8:
-                if constexpr (TA == 2 && TB == 1 && WM == 1 && WN * TNT == 24 && TM == 13) QV_PM(8);   // (whole 384-column rows per tile only)
-                break;
-            case 9:
-                if constexpr (TA == 2 && TB == 1 && WM == 1 && WN * TNT == 24 && TM == 13) QV_PM(9);   // (the tall tile only)
-                break;
-            default: QV_PM(0); break;
+            case kEpiGeluFwd: QV_PM(kEpiGeluFwd);
+            case kEpiStats: QV_PM(kEpiStats);
+            case kEpiCodes: QV_PM(kEpiCodes);
+            case kPmCodesF16: QV_PM(kPmCodesF16);
+            case kEpiGeluBwdU16: QV_PM(kEpiGeluBwdU16);
+            case kEpiLnBwd: if constexpr (TA == 2 && tall1) QV_PM(kEpiLnBwd); break;
+            case kEpiGeluBwdU8: if constexpr (TA == 2 && tall1) QV_PM(kEpiGeluBwdU8); break;
+            case kEpiPlain: QV_PM(kEpiPlain);
         }
     }
 #undef QV_PM
+    set_error("gemm_nt: no kernel for epilogue id %d on %s operands (%d A parts, %d B parts) with the %d x %d tile", a.pm, F16 ? "fp16" : I8 ? "int8" : "bf16", TA, TB,
+              16 * TM * WM, 16 * TNT * WN);
+    return 1;
 }
+
+// THE copy NTPost -> NTArgs: every epilogue operand, and the instantiation id.  o16: launch_gemm_nt_dy16's one-plane forms of modes 8 / 9.  A kernel reads
+// only the fields of its own PM (nt_epilogue: every access sits under that mode's `if constexpr`), so a field its mode does not use travels unread.
+static void nt_set_post(NTArgs& a, const NTPost& p, bool o16 = false) {
+    a.post_mode = p.mode; a.post_gelu_fwd = p.mode == kEpiGeluFwd; a.out_f16 = p.out_f16;
+    a.pm = o16 ? p.mode + 10 : (p.mode == kEpiCodes && p.out16_hi) ? kPmCodesF16 : p.mode;
+    a.post_qp = p.qp; a.post_qmin = p.qmin; a.post_qmax = p.qmax; a.post_colscale = p.colscale;
+    a.out_hi = reinterpret_cast<__bf16*>(p.out_hi); a.out_lo = reinterpret_cast<__bf16*>(p.out_lo); a.post_code = reinterpret_cast<uint16_t*>(p.code);
+    a.out16_hi = reinterpret_cast<_Float16*>(p.out16_hi); a.out16_lo = reinterpret_cast<_Float16*>(p.out16_lo); a.out16_scale = p.out16_scale;
+    a.resid = p.resid; a.embed_np = p.embed_np; a.out8 = reinterpret_cast<uint8_t*>(p.out8); a.out8_mask = reinterpret_cast<uint8_t*>(p.out8_mask);
+    a.code_T = p.code_T; a.code_hd = p.code_hd; a.lut_out = p.lut_out; a.lutq_out = p.lutq_out;
+    a.post_code8 = reinterpret_cast<const uint8_t*>(p.code8); a.post_mask = reinterpret_cast<const uint8_t*>(p.code_mask);
+    a.lnb_x = p.lnb_x; a.lnb_mean = p.lnb_mean; a.lnb_rstd = p.lnb_rstd; a.lnb_gamma = p.lnb_gamma; a.lnb_beta = p.lnb_beta;
+    a.lnb_dx_in = p.lnb_dx_in; a.lnb_dgamma = p.lnb_dgamma; a.lnb_dbeta = p.lnb_dbeta; a.lnb_nmask = reinterpret_cast<const unsigned long long*>(p.lnb_nmask);
+    a.o16_mul = p.o16_mul; a.o16_amax = p.o16_amax;
+}
+// the mode a launcher switches on: kEpiPlain without a record; a record that names kEpiPlain is an unknown mode (-1) like any other number
+static int nt_mode(const NTPost* post) { return !post ? kEpiPlain : post->mode == kEpiPlain ? -1 : post->mode; }
 
 int launch_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1,
                    const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
                    const void* B_lo, const NTPost* post, bool f16) {
-    const bool f16_gelu = f16 && post && post->mode == 0 && !post->Y && post->out_f16;   // the teacher's fc1: fp16 gelu pair out
-    if (f16 && (B_lo || (post && post->mode != 6 && !f16_gelu) || (!A_lo && post && !f16_gelu) || N % 384 != 0 || K % 32 != 0)) {
+    const bool f16_gelu = f16 && post && post->mode == kEpiGeluFwd && post->out_f16;   // the teacher's fc1: fp16 gelu pair out
+    if (f16 && (B_lo || (post && post->mode != kEpiResidFq && !f16_gelu) || (!A_lo && post && !f16_gelu) || N % 384 != 0 || K % 32 != 0)) {
         set_error("gemm_nt: the fp16 form takes N %% 384 == 0 and the plain, the residual (mode 6) or the fp16 GELU epilogue (N=%d K=%d)", N, K);
         return 1;
     }
@@ -1093,86 +1097,62 @@ int launch_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, 
     a.A0 = reinterpret_cast<const __bf16*>(A_hi); a.A1 = reinterpret_cast<const __bf16*>(A_lo); a.B = reinterpret_cast<const __bf16*>(B);
     a.B1 = reinterpret_cast<const __bf16*>(B_lo); a.C = C; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
     a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
-    if (post && post->mode >= 3) {
-        a.post_mode = post->mode;
-        a.pm = post->mode;
-        a.post_qp = post->qp; a.post_qmin = post->qmin; a.post_qmax = post->qmax; a.post_colscale = post->colscale;
-        a.out_hi = reinterpret_cast<__bf16*>(post->out_hi); a.out_lo = reinterpret_cast<__bf16*>(post->out_lo);
-        a.post_code = reinterpret_cast<uint16_t*>(post->code);
-        a.out16_hi = reinterpret_cast<_Float16*>(post->out16_hi); a.out16_lo = reinterpret_cast<_Float16*>(post->out16_lo); a.out16_scale = post->out16_scale;
-        a.resid = post->resid; a.embed_np = post->embed_np; a.out8 = reinterpret_cast<uint8_t*>(post->out8); a.code_T = post->code_T; a.code_hd = post->code_hd;
-        a.lut_out = post->lut_out; a.out8_mask = reinterpret_cast<uint8_t*>(post->out8_mask);
-        if (post->mode == 4 && a.out16_hi) a.pm = 10;
-        a.lutq_out = post->lutq_out;
-        a.lnb_x = post->lnb_x; a.lnb_mean = post->lnb_mean; a.lnb_rstd = post->lnb_rstd; a.lnb_gamma = post->lnb_gamma; a.lnb_beta = post->lnb_beta;
-        a.lnb_dx_in = post->lnb_dx_in; a.lnb_dgamma = post->lnb_dgamma; a.lnb_dbeta = post->lnb_dbeta;
-        a.lnb_nmask = reinterpret_cast<const unsigned long long*>(post->lnb_nmask);
-        if (post->mode == 9) {
-            a.post_code8 = reinterpret_cast<const uint8_t*>(post->code8); a.post_mask = reinterpret_cast<const uint8_t*>(post->code_mask);
-            if (!(A_lo && !f16 && !B_lo && N % 384 == 0 && K % 32 == 0 && ldc % 128 == 0 && a.post_qp && a.out_hi && a.out_lo && a.post_code8 && a.post_mask &&
-                  a.post_qmax - a.post_qmin < 256)) {
-                set_error("gemm_nt: epilogue mode 9 needs a split A operand, N %% 384 == 0, ldc %% 128 == 0, the uint8 codes and the mask bits");
-                return 1;
-            }
-            nt_launch<2, 3, 1, 13, 1, 8, 3, 32>(a, cdiv(M, 208) * (N / 384), (size_t)160 * 1024, st);
-            return 0;
-        }
-        if (post->mode == 8) {
-            if (!(A_lo && !f16 && !B_lo && N == 384 && K % 32 == 0 && ldc == 384 && C && a.post_qp && a.lnb_x && a.lnb_mean && a.lnb_rstd && a.lnb_gamma && a.lnb_beta &&
-                  a.lnb_dx_in && a.lnb_dgamma && a.lnb_dbeta && (!a.out_hi || (a.out_lo && a.lnb_nmask)))) {
+    if (post) nt_set_post(a, *post);
+    const int mode = nt_mode(post);
+    const bool split_tall = A_lo && !f16 && !B_lo && K % 32 == 0;   // modes 8 / 9: the split-A 208 x 384 tile only
+    switch (mode) {
+        case kEpiPlain:
+            if (!C) { set_error("gemm_nt: null output"); return 1; }
+            break;
+        case kEpiGeluFwd:
+            if (!a.out_hi || (!a.out_lo && !f16_gelu)) { set_error("gemm_nt: fused GELU epilogue needs out_hi / out_lo"); return 1; }
+            if (post->out_f16 && !f16) { set_error("gemm_nt: the fp16 GELU pair is written by the fp16 form only"); return 1; }
+            break;
+        case kEpiStats: break;
+        case kEpiCodes:
+        case kEpiGeluBwdU16:
+            if (!(a.post_qp && a.out_hi && a.out_lo && a.post_code && a.post_qmax - a.post_qmin < 256)) { set_error("gemm_nt: incomplete arguments for epilogue mode %d", mode); return 1; }
+            break;
+        case kEpiResidFq:
+            if (!(f16 && a.post_qp && a.resid && C)) { set_error("gemm_nt: incomplete arguments for epilogue mode %d", mode); return 1; }
+            break;
+        case kEpiLnBwd:
+            if (!(split_tall && N == 384 && ldc == 384 && C && a.post_qp && a.lnb_x && a.lnb_mean && a.lnb_rstd && a.lnb_gamma && a.lnb_beta && a.lnb_dx_in &&
+                  a.lnb_dgamma && a.lnb_dbeta && (!a.out_hi || (a.out_lo && a.lnb_nmask)))) {
                 set_error("gemm_nt: epilogue mode 8 needs a split A operand, N == ldc == 384 and the LayerNorm operands");
                 return 1;
             }
-            constexpr size_t lds8 = 160 * 1024;   // ring 150 KiB; the epilogue's 96-row slab + row operands need 156 KiB
-            nt_launch<2, 3, 1, 13, 1, 8, 3, 32>(a, cdiv(M, 208), lds8, st);
-            return 0;
-        }
-        const bool ok6 = post->mode == 6 && f16 && a.post_qp && a.resid && C;
-        const bool ok345 = post->mode <= 5 && (post->mode == 3 || (a.post_qp && a.out_hi && a.out_lo && a.post_code && a.post_qmax - a.post_qmin < 256));
-        if (!ok6 && !ok345) {
-            set_error("gemm_nt: incomplete arguments for epilogue mode %d", post->mode);
-            return 1;
-        }
-    } else if (post && !post->Y) {
-        a.post_gelu_fwd = 1;
-        a.pm = 2;
-        a.out_f16 = post->out_f16;
-        a.out_hi = reinterpret_cast<__bf16*>(post->out_hi); a.out_lo = reinterpret_cast<__bf16*>(post->out_lo);
-        if (!a.out_hi || (!a.out_lo && !f16_gelu)) { set_error("gemm_nt: fused GELU epilogue needs out_hi / out_lo"); return 1; }
-        if (post->out_f16 && !f16) { set_error("gemm_nt: the fp16 GELU pair is written by the fp16 form only"); return 1; }
-    } else if (post) {
-        set_error("gemm_nt: the GELU-backward epilogue reads fc1's codes (mode 5 or 9); the form that re-quantised a stored fp32 tensor is gone");
-        return 1;
-    } else if (!C) {
-        set_error("gemm_nt: null output");
-        return 1;
+            break;
+        case kEpiGeluBwdU8:
+            if (!(split_tall && N % 384 == 0 && ldc % 128 == 0 && a.post_qp && a.out_hi && a.out_lo && a.post_code8 && a.post_mask && a.post_qmax - a.post_qmin < 256)) {
+                set_error("gemm_nt: epilogue mode 9 needs a split A operand, N %% 384 == 0, ldc %% 128 == 0, the uint8 codes and the mask bits");
+                return 1;
+            }
+            break;
+        default: set_error("gemm_nt: epilogue mode %d not available", post->mode); return 1;
     }
     // Tiles.  M = B * 197 token rows over 256 CUs is 197 rows per CU, so the main tile is 208 rows x the whole 384-column weight panel (every N of
     // ViT-S / B is a multiple of 384): 243 tiles fill the chip in ONE round for N = 384 and the A operand is streamed into LDS exactly once;
     // 1 x 8 waves each 208 x 48, BK 32, 3-stage ring, DMA issue spread between the MFMA groups.  128 x 128 tiles cover the other shapes.
+    const int tall = cdiv(M, 208) * (N / 384), square = cdiv(M, 128) * (N / 128);
+    if (mode == kEpiLnBwd || mode == kEpiGeluBwdU8)   // ring 150 KiB; the epilogue's slab + row operands / code buffers need up to 156 KiB
+        return nt_launch<2, 3, 1, 13, 1, 8, 3, 32>(a, tall, (size_t)160 * 1024, st);
     if (B_lo) {  // float x float (teacher): both operands split
         if (!A_lo) { set_error("gemm_nt: a split B operand needs a split A operand"); return 1; }
-        if (N % 384 == 0) {   // 2 stages x (2 x 208 + 2 x 384) x 64 B = 148 KiB
-            nt_launch<2, 2, 1, 13, 2, 8, 3, 32>(a, cdiv(M, 208) * (N / 384), (size_t)2 * (2 * 208 + 2 * 384) * 64, st);
-            return 0;
-        }
-        nt_launch<2, 2, 4, 2, 2, 2, 4, 64>(a, cdiv(M, 128) * (N / 128), (size_t)2 * 4 * 16384, st);   // 128 x 128, 8 waves, 2 stages x 64 KiB
-        return 0;
+        if (N % 384 == 0) return nt_launch<2, 2, 1, 13, 2, 8, 3, 32>(a, tall, (size_t)2 * (2 * 208 + 2 * 384) * 64, st);   // 2 stages x (2 x 208 + 2 x 384) x 64 B = 148 KiB
+        return nt_launch<2, 2, 4, 2, 2, 2, 4, 64>(a, square, (size_t)2 * 4 * 16384, st);   // 128 x 128, 8 waves, 2 stages x 64 KiB
     }
     if (f16) {
-        if (A_lo) nt_launch<2, 3, 1, 13, 1, 8, 3, 32, false, true>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (2 * 208 + 384) * 64, st);   // 150 KiB
-        else nt_launch<1, 3, 1, 13, 1, 8, 3, 32, false, true>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (208 + 384) * 64, st);        // 111 KiB (one-pass teacher)
-        return 0;
+        if (A_lo) return nt_launch<2, 3, 1, 13, 1, 8, 3, 32, false, true>(a, tall, (size_t)3 * (2 * 208 + 384) * 64, st);   // 150 KiB
+        return nt_launch<1, 3, 1, 13, 1, 8, 3, 32, false, true>(a, tall, (size_t)3 * (208 + 384) * 64, st);                // 111 KiB (one-pass teacher)
     }
     if (N % 384 == 0) {
-        if (A_lo) nt_launch<2, 3, 1, 13, 1, 8, 3, 32>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (2 * 208 + 384) * 64, st);   // 150 KiB
-        else nt_launch<1, 3, 1, 13, 1, 8, 3, 32>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (208 + 384) * 64, st);            // 111 KiB
-        return 0;
+        if (A_lo) return nt_launch<2, 3, 1, 13, 1, 8, 3, 32>(a, tall, (size_t)3 * (2 * 208 + 384) * 64, st);   // 150 KiB
+        return nt_launch<1, 3, 1, 13, 1, 8, 3, 32>(a, tall, (size_t)3 * (208 + 384) * 64, st);                // 111 KiB
     }
     // 128 x 128 tiles, 8 waves x (32 x 64) (measured best of three wave layouts at B = 256: profiles/round1_gemm_configs.txt)
-    if (A_lo) nt_launch<2, 3, 4, 2, 1, 2, 4, 64>(a, cdiv(M, 128) * (N / 128), (size_t)3 * (2 * 16384 + 16384), st);   // 3 stages, 144 KiB
-    else nt_launch<1, 2, 4, 2, 1, 2, 4, 64>(a, cdiv(M, 128) * (N / 128), (size_t)2 * (16384 + 16384), st);           // 2 stages, 64 KiB: two workgroups per CU
-    return 0;
+    if (A_lo) return nt_launch<2, 3, 4, 2, 1, 2, 4, 64>(a, square, (size_t)3 * (2 * 16384 + 16384), st);   // 3 stages, 144 KiB
+    return nt_launch<1, 2, 4, 2, 1, 2, 4, 64>(a, square, (size_t)2 * (16384 + 16384), st);                // 2 stages, 64 KiB: two workgroups per CU
 }
 
 int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1, const float* s2,
@@ -1188,39 +1168,33 @@ int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N
     NTArgs a{};
     a.A0 = reinterpret_cast<const __bf16*>(A16); a.B = reinterpret_cast<const __bf16*>(B16); a.C = C; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
     a.s1 = s1; a.s2 = s2; a.stat_slots = 1;
-    size_t lds = (size_t)2 * (208 + 384) * 128;   // 148 KiB ring
-    if (post) {
-        if ((post->mode != 8 && post->mode != 9) || !post->o16_mul || !post->o16_amax || !post->qp) {
-            set_error("gemm_nt_dy16: epilogue mode %d (8 or 9 with o16_mul / o16_amax)", post->mode);
-            return 1;
-        }
-        a.post_mode = post->mode; a.pm = post->mode + 10;
-        a.post_qp = post->qp; a.post_qmin = post->qmin; a.post_qmax = post->qmax; a.post_colscale = post->colscale;
-        a.out_hi = reinterpret_cast<__bf16*>(post->out_hi); a.o16_mul = post->o16_mul; a.o16_amax = post->o16_amax;
-        a.lnb_x = post->lnb_x; a.lnb_mean = post->lnb_mean; a.lnb_rstd = post->lnb_rstd; a.lnb_gamma = post->lnb_gamma; a.lnb_beta = post->lnb_beta;
-        a.lnb_dx_in = post->lnb_dx_in; a.lnb_dgamma = post->lnb_dgamma; a.lnb_dbeta = post->lnb_dbeta;
-        a.lnb_nmask = reinterpret_cast<const unsigned long long*>(post->lnb_nmask);
-        a.post_code8 = reinterpret_cast<const uint8_t*>(post->code8); a.post_mask = reinterpret_cast<const uint8_t*>(post->code_mask);
-        if (post->mode == 9 && !(ldc % 128 == 0 && a.out_hi && a.post_code8 && a.post_mask && a.post_qmax - a.post_qmin < 256)) {
-            set_error("gemm_nt_dy16: epilogue mode 9 needs ldc %% 128 == 0, the fp16 output plane, the uint8 codes and the mask bits");
-            return 1;
-        }
-        if (post->mode == 8 && !(N == 384 && ldc == 384 && C && a.lnb_x && a.lnb_mean && a.lnb_rstd && a.lnb_gamma && a.lnb_beta && a.lnb_dx_in && a.lnb_dgamma &&
-                                 a.lnb_dbeta && (!a.out_hi || a.lnb_nmask))) {
-            set_error("gemm_nt_dy16: epilogue mode 8 needs N == ldc == 384 and the LayerNorm operands");
-            return 1;
-        }
-        lds = (size_t)160 * 1024;
-    } else if (!C) {
-        set_error("gemm_nt_dy16: null output");
-        return 1;
+    if (post) nt_set_post(a, *post, true);
+    const bool o16 = post && post->o16_mul && post->o16_amax && post->qp;
+    switch (o16 || !post ? nt_mode(post) : -1) {
+        case kEpiPlain:
+            if (!C) { set_error("gemm_nt_dy16: null output"); return 1; }
+            break;
+        case kEpiLnBwd:
+            if (!(N == 384 && ldc == 384 && C && a.lnb_x && a.lnb_mean && a.lnb_rstd && a.lnb_gamma && a.lnb_beta && a.lnb_dx_in && a.lnb_dgamma && a.lnb_dbeta &&
+                  (!a.out_hi || a.lnb_nmask))) {
+                set_error("gemm_nt_dy16: epilogue mode 8 needs N == ldc == 384 and the LayerNorm operands");
+                return 1;
+            }
+            break;
+        case kEpiGeluBwdU8:
+            if (!(ldc % 128 == 0 && a.out_hi && a.post_code8 && a.post_mask && a.post_qmax - a.post_qmin < 256)) {
+                set_error("gemm_nt_dy16: epilogue mode 9 needs ldc %% 128 == 0, the fp16 output plane, the uint8 codes and the mask bits");
+                return 1;
+            }
+            break;
+        default: set_error("gemm_nt_dy16: epilogue mode %d (8 or 9 with o16_mul / o16_amax)", post->mode); return 1;
     }
     // BK = 64, two stages: every LDS-DMA request is a whole 128-byte line of a gradient / weight row (BK = 32: half lines, each line requested by two k-steps).
     // Same box, same step: dgrad + LayerNorm backward 108.8 -> 103.8 us, + GELU backward 135.4 -> 131.9, plain 29.8 -> 28.5 (three stages of BK = 32; a fourth changed
     // nothing: 105.1 vs 104.5).  The k-values enter the accumulators in the same order: the same bits.
-    if (bf16) nt_launch<1, 2, 1, 13, 1, 8, 3, 64>(a, cdiv(M, 208) * (N / 384), lds, st);   // the same tile and ring on bf16 MFMA
-    else nt_launch<1, 2, 1, 13, 1, 8, 3, 64, false, true>(a, cdiv(M, 208) * (N / 384), post ? lds : (size_t)2 * (208 + 384) * 128, st);
-    return 0;
+    const size_t lds = post ? (size_t)160 * 1024 : (size_t)2 * (208 + 384) * 128;   // 148 KiB ring; the fused epilogues ask for 160
+    if (bf16) return nt_launch<1, 2, 1, 13, 1, 8, 3, 64>(a, cdiv(M, 208) * (N / 384), lds, st);   // the same tile and ring on bf16 MFMA
+    return nt_launch<1, 2, 1, 13, 1, 8, 3, 64, false, true>(a, cdiv(M, 208) * (N / 384), lds, st);
 }
 
 // fc2 forward from codes: A8 [M, lda] uint8 grid indices, lut[256] packed fp16 (hi | lo << 16) pairs, B16 [N, ldb] the weight integers as fp16
@@ -1235,20 +1209,25 @@ int launch_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, f
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
     a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
     a.a_lut = lut;
+    if (post) nt_set_post(a, *post);
     constexpr int kLds = 3 * (2 * 208 + 384) * 64 + 1024;   // 151 KiB
-    if (post) {   // inference: the residual update C[orow] = resid + fq(acc) in the epilogue (mode 6), frozen qparams
-        if (post->mode != 6 || !post->qp || !post->resid) { set_error("gemm_nt_codes: only the residual epilogue (mode 6: qp, resid) is available"); return 1; }
-        a.post_mode = a.pm = 6;
-        a.post_qp = post->qp; a.post_qmin = post->qmin; a.post_qmax = post->qmax; a.resid = post->resid; a.embed_np = post->embed_np;
-        static bool once6 = (allow_lds(k_gemm_nt_ac<3, 6, kLds>, (size_t)kLds), true);
-        (void)once6;
-        k_gemm_nt_ac<3, 6, kLds><<<cdiv(M, 208) * (N / 384), 512, kLds, st>>>(a);
-        return 0;
+    switch (nt_mode(post)) {
+        case kEpiResidFq: {   // inference: the residual update C[orow] = resid + fq(acc) in the epilogue, frozen qparams
+            if (!post->qp || !post->resid) break;
+            static bool once6 = (allow_lds(k_gemm_nt_ac<3, kEpiResidFq, kLds>, (size_t)kLds), true);
+            (void)once6;
+            k_gemm_nt_ac<3, kEpiResidFq, kLds><<<cdiv(M, 208) * (N / 384), 512, kLds, st>>>(a);
+            return 0;
+        }
+        case kEpiPlain: {
+            static bool once = (allow_lds(k_gemm_nt_ac<3, kEpiPlain, kLds>, (size_t)kLds), true);
+            (void)once;
+            k_gemm_nt_ac<3, kEpiPlain, kLds><<<cdiv(M, 208) * (N / 384), 512, kLds, st>>>(a);
+            return 0;
+        }
     }
-    static bool once = (allow_lds(k_gemm_nt_ac<3, 0, kLds>, (size_t)kLds), true);
-    (void)once;
-    k_gemm_nt_ac<3, 0, kLds><<<cdiv(M, 208) * (N / 384), 512, kLds, st>>>(a);
-    return 0;
+    set_error("gemm_nt_codes: only the residual epilogue (mode 6: qp, resid) is available");
+    return 1;
 }
 
 // Grid x grid forward GEMM on int8 MFMA (v_mfma_i32_16x16x64_i8: twice the k per instruction and per LDS-DMA byte of the bf16 form).
@@ -1265,35 +1244,34 @@ int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
     a.A0 = reinterpret_cast<const __bf16*>(A8); a.B = reinterpret_cast<const __bf16*>(B8); a.C = C; a.M = M; a.N = N; a.K = K / 2; a.lda = lda / 2; a.ldb = ldb / 2;
     a.ldc = ldc; a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
     a.i8_wsum = wsum; a.i8_aqp = a_qp; a.i8_center = center;
-    if (post) {
-        if (post->mode != 3 && post->mode != 4 && post->mode != 6 && post->mode != 7) { set_error("gemm_nt_i8: epilogue mode %d not available", post->mode); return 1; }
-        a.post_mode = a.pm = post->mode;
-        a.post_qp = post->qp; a.post_qmin = post->qmin; a.post_qmax = post->qmax;
-        a.out_hi = reinterpret_cast<__bf16*>(post->out_hi); a.out_lo = reinterpret_cast<__bf16*>(post->out_lo);
-        a.post_code = reinterpret_cast<uint16_t*>(post->code);
-        a.out16_hi = reinterpret_cast<_Float16*>(post->out16_hi); a.out16_lo = reinterpret_cast<_Float16*>(post->out16_lo); a.out16_scale = post->out16_scale;
-        a.resid = post->resid; a.embed_np = post->embed_np; a.out8 = reinterpret_cast<uint8_t*>(post->out8); a.code_T = post->code_T; a.code_hd = post->code_hd;
-        a.lut_out = post->lut_out; a.out8_mask = reinterpret_cast<uint8_t*>(post->out8_mask);
-        if (post->mode == 4 && a.out16_hi) a.pm = 10;   // the instantiation that also looks up / stores the fp16 planes
-        a.lutq_out = post->lutq_out;
-        const bool codes4 = post->mode == 4 && a.out8 && a.out8_mask && a.lut_out && a.lutq_out && !a.out_hi && !a.out_lo && !a.post_code && ldc % 32 == 0;   // codes + mask bits + the two tables only
-        const bool full4 = codes4 || (a.out_hi && a.out_lo && (a.post_code || (post->mode == 4 && a.out8 && a.out8_mask && ldc % 32 == 0))), half4 = !a.out_hi && !a.out_lo && !a.post_code && a.out16_hi && a.out16_lo && a.out16_scale;
-        if ((post->mode == 4 && (!a.post_qp || !(full4 || half4) || a.post_qmax - a.post_qmin >= 256)) ||
-            (post->mode == 6 && (!a.post_qp || !a.resid || !C)) ||
-            (post->mode == 7 && (!a.post_qp || !a.out8 || a.code_T < 1 || a.code_hd < 8 || (a.out8_mask && a.code_hd % 32 != 0) || (a.code_hd & (a.code_hd - 1)) != 0 || M >= (1 << 22) || N / 3 >= 1024 || a.code_T >= 1024 || (N / 3) % a.code_hd != 0 || a.post_qmax - a.post_qmin >= 256))) {
-            set_error("gemm_nt_i8: incomplete arguments for epilogue mode %d", post->mode);
-            return 1;
+    if (post) nt_set_post(a, *post);
+    const int mode = nt_mode(post);
+    bool ok = true;
+    switch (mode) {
+        case kEpiPlain:
+            if (!C) { set_error("gemm_nt_i8: null output"); return 1; }
+            break;
+        case kEpiStats: break;
+        case kEpiCodes: {
+            const bool bytes = a.out8 && a.out8_mask && ldc % 32 == 0, none = !a.out_hi && !a.out_lo && !a.post_code;
+            const bool codes4 = bytes && a.lut_out && a.lutq_out && none;   // codes + mask bits + the two tables only
+            const bool full4 = codes4 || (a.out_hi && a.out_lo && (a.post_code || bytes)), half4 = none && a.out16_hi && a.out16_lo && a.out16_scale;
+            ok = a.post_qp && (full4 || half4) && a.post_qmax - a.post_qmin < 256;
+            break;
         }
-    } else if (!C) {
-        set_error("gemm_nt_i8: null output");
-        return 1;
+        case kEpiResidFq: ok = a.post_qp && a.resid && C; break;
+        case kEpiQkvCodes:
+            ok = a.post_qp && a.out8 && a.code_T >= 1 && a.code_hd >= 8 && !(a.out8_mask && a.code_hd % 32 != 0) && (a.code_hd & (a.code_hd - 1)) == 0 && M < (1 << 22) &&
+                 N / 3 < 1024 && a.code_T < 1024 && (N / 3) % a.code_hd == 0 && a.post_qmax - a.post_qmin < 256;
+            break;
+        default: set_error("gemm_nt_i8: epilogue mode %d not available", post->mode); return 1;
     }
+    if (!ok) { set_error("gemm_nt_i8: incomplete arguments for epilogue mode %d", mode); return 1; }
     // the K = 384 two-pass GEMMs (qkv, fc1: statistics pass, code passes) on the A-stationary strip kernel (i8strip.hip) when the weight came in
     // fragment order too; everything else (plain fp32 output, K != 384, the inference epilogues) on the general tall tile below
     if (post && launch_i8_strip(A8, B8f, wsum, a_qp, center, M, N, K, lda, ldc, s1, s2, col_scale, bias, stats, stat_slots, st, post, false, late)) return 0;
     if (late) { set_error("gemm_nt_i8: late qparams exist in the strip kernel only (i8_strip_covers)"); return 1; }
-    nt_launch<1, 3, 1, 13, 1, 8, 3, 32, true>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (208 + 384) * 64, st);
-    return 0;
+    return nt_launch<1, 3, 1, 13, 1, 8, 3, 32, true>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (208 + 384) * 64, st);
 }
 
 // ============================================================================ TN (wgrad)

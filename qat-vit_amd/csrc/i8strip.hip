@@ -94,7 +94,7 @@ struct I8StripArgs {
 // LN (statistics pass only): the A strip is not fetched from the int8 plane but produced here from the fp32 rows of the residual stream (I8StripArgs::ln_*)
 template <int MODE, int NTL, int NWV = 8, bool R255 = false, int TM_ = 13, int KT_ = 6, bool LN = false>
 __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArgs p) {
-    static_assert(!LN || MODE == 3, "the LayerNorm prologue exists in the statistics pass only");
+    static_assert(!LN || MODE == kEpiStats, "the LayerNorm prologue exists in the statistics pass only");
     constexpr int TM = TM_, TNT = 24 / NWV, WC = 16 * TNT, BM = 16 * TM, BN = 384, KT = KT_, PF = 3, NT_ = NWV * 64;
     static_assert(TM <= 2 * NWV, "the strip's 1-KiB DMA pieces are dealt in two rounds");
     static_assert(NWV == 8 || NWV == 12, "8 waves x 48 columns or 12 waves x 32 columns");
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
     i32x4 bb[2][TNT];
     load_b(0, 0, bb[0]);
 
-    float* sQp = reinterpret_cast<float*>(sStage + (MODE == 3 ? 512 : NWV * WSTG));   // {scale, 1 / scale, zp} of a quantizer this workgroup resolves (below)
+    float* sQp = reinterpret_cast<float*>(sStage + (MODE == kEpiStats ? 512 : NWV * WSTG));   // {scale, 1 / scale, zp} of a quantizer this workgroup resolves (below)
 
     // ---- LN form: the strip from the fp32 rows.  Thread -> (16-B code chunk kc of a row, row lane rg): a thread keeps its 16 columns for all rows
     // it converts (gamma / beta in registers), consecutive lanes take consecutive chunks (64 B of x each, 16 B of codes) of rows that follow each
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
     };
 
     // code passes: {scale, 1 / scale, zp} of the OUTPUT's quantizer - ready in p.qp, or resolved here from the statistics pass' accumulators (QpLate)
-    if constexpr (MODE != 3) {
+    if constexpr (MODE != kEpiStats) {
         if (p.late.stats) qp_late_compute(p.late, sQp);
         else if (tid == 0) { sQp[0] = p.qp[0]; sQp[1] = p.qp[1]; sQp[2] = p.qp[2]; }
     }
@@ -256,8 +256,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
     __builtin_amdgcn_s_barrier();                        // ... and everybody else's: the ONLY workgroup barrier of the code passes
     asm volatile("" ::: "memory");
     QV_STAMP();   // strip complete
-    const float qp_s = MODE != 3 ? sQp[0] : 0.f, qp_inv = MODE != 3 ? sQp[1] : 0.f, qp_zp = MODE != 3 ? sQp[2] : 0.f;
-    if constexpr (MODE == 4) {   // the two 256-entry tables of gelu(grid value) and the fp16 pair's scale: data-independent, one workgroup writes them
+    const float qp_s = MODE != kEpiStats ? sQp[0] : 0.f, qp_inv = MODE != kEpiStats ? sQp[1] : 0.f, qp_zp = MODE != kEpiStats ? sQp[2] : 0.f;
+    if constexpr (MODE == kEpiCodes) {   // the two 256-entry tables of gelu(grid value) and the fp16 pair's scale: data-independent, one workgroup writes them
         if (blockIdx.x == 0 && blockIdx.y == 0 && tid < 256) {
             const float ga = fabsf(((float)p.qmin - qp_zp) * qp_s), gb = fabsf(((float)p.qmax - qp_zp) * qp_s);
             int ex;
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
         // wave priorities (code passes): MFMA phase above every quantise phase, so a wave's k-loop runs dense under its SIMD partner's epilogue; between
         // two waves that are both quantising, the one favoured alternates per column tile (at equal priority the older wave always wins and finishes
         // ~20 k cycles before its partner, which then runs alone at the one-wave VALU rate): 45.1 -> 42.0 us (qkv), 57.0 -> 54.7 us (fc1)
-        if constexpr (MODE != 3) __builtin_amdgcn_s_setprio(2);
+        if constexpr (MODE != kEpiStats) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
             // request k-step kt + 1 (of this column tile or the next: the next tile's first fragments are then in flight BEFORE the epilogue's
@@ -329,12 +329,12 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
             kstep(kt, bb[kt & 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MODE != 3) {
+        if constexpr (MODE != kEpiStats) {
             if (((wave >> 2) + nt) % (NWV / 4) == 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);   // (wave is an SGPR: a scalar branch)
         }
         QV_STAMP();   // k-loop done
 
-        if constexpr (MODE == 3) {
+        if constexpr (MODE == kEpiStats) {
             // integer min / max per column over this lane's 13 tokens, then the (monotone: ca > 0) float map once per column
             int tid3 = threadIdx.x;                      // (opaque copy: the ragged strip's 13 row predicates are otherwise computed up front and spilled)
             asm volatile("" : "+v"(tid3));
@@ -383,8 +383,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
             char* sW = sStage + wave * WSTG;             // this wave's staging area: [64][48 B] codes, then [64][16 B]: the 4 mask bits of fragment j, lane group g in byte 4 j + g
             char* sWm = sW + 16 * CH * WC;
             // output geometry of this wave's 48 columns
-            const int which = MODE == 7 ? tilebase / p.D : 0, cm0 = MODE == 7 ? tilebase % p.D + wave * WC : 0, Hh = MODE == 7 ? p.D >> 6 : 0;
-            const float invT = MODE == 7 ? 1.0f / (float)p.code_T : 0.f;
+            const int which = MODE == kEpiQkvCodes ? tilebase / p.D : 0, cm0 = MODE == kEpiQkvCodes ? tilebase % p.D + wave * WC : 0, Hh = MODE == kEpiQkvCodes ? p.D >> 6 : 0;
+            const float invT = MODE == kEpiQkvCodes ? 1.0f / (float)p.code_T : 0.f;
 #pragma unroll
             for (int c0 = 0; c0 < TM; c0 += CH) {        // chunks of 4 row fragments (64 rows); the last one holds 1 (16 rows)
                 const int nf = TM - c0 < CH ? TM - c0 : CH;
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
                     uint32_t mx4 = *reinterpret_cast<const uint32_t*>(sWm + rl * 16 + 4 * c) & 0x0f0f0f0fu;
                     mx4 = (mx4 | (mx4 >> 4)) & 0x00ff00ffu;
                     const uint16_t mv = (uint16_t)((mx4 | (mx4 >> 8)) & 0xffffu);
-                    if constexpr (MODE == 4) {
+                    if constexpr (MODE == kEpiCodes) {
                         // (24-bit multiplies: row < 2^22 and ldc < 2^24 are checked by the launcher; the 32-bit forms run at a quarter of the rate)
                         const uint32_t eo = __umul24((uint32_t)row, (uint32_t)p.ldc) + (uint32_t)(tilebase + wave * WC + 16 * c);
                         if (ok) {
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
     }
 
     QV_STAMP();   // end
-    if constexpr (MODE == 3) {
+    if constexpr (MODE == kEpiStats) {
         float* sRed = reinterpret_cast<float*>(sStage);
         mn = wave_min(mn);
         mx = wave_max(mx);
@@ -469,7 +469,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_i8_strip(const I8StripArg
 
 template <int MODE, int NTL, int NWV, bool R255, int TM, int KT>
 static void strip_launch_r(const I8StripArgs& a, hipStream_t st) {
-    constexpr int kLds = KT * 16 * TM * 64 + 3 * NTL * 384 * 4 + (MODE == 3 ? 512 : NWV * (64 * (384 / NWV) + 64 * 16)) + 16;   // (+ the output quantizer's {scale, 1 / scale, zp})
+    constexpr int kLds = KT * 16 * TM * 64 + 3 * NTL * 384 * 4 + (MODE == kEpiStats ? 512 : NWV * (64 * (384 / NWV) + 64 * 16)) + 16;   // (+ the output quantizer's {scale, 1 / scale, zp})
     static_assert(kLds <= 160 * 1024, "strip + constants + staging patches exceed the LDS");
     static bool once = (allow_lds(k_i8_strip<MODE, NTL, NWV, R255, TM, KT>, kLds), true);
     (void)once;
@@ -477,7 +477,7 @@ static void strip_launch_r(const I8StripArgs& a, hipStream_t st) {
 }
 template <int MODE, int NTL, int NWV, int TM, int KT>
 static void strip_launch_w(const I8StripArgs& a, hipStream_t st) {
-    if (MODE != 3 && a.qmax - a.qmin == 255) strip_launch_r<MODE, NTL, NWV, true, TM, KT>(a, st);
+    if (MODE != kEpiStats && a.qmax - a.qmin == 255) strip_launch_r<MODE, NTL, NWV, true, TM, KT>(a, st);
     else strip_launch_r<MODE, NTL, NWV, false, TM, KT>(a, st);
 }
 template <int MODE, int NTL, int TM = 13, int KT = 6>
@@ -490,7 +490,7 @@ static void strip_launch(const I8StripArgs& a0, hipStream_t st) {
     // statistics pass: 8 waves x 48 columns (two per SIMD); code passes: 12 waves x 32 columns (three per SIMD, 104 accumulator registers) - their
     // quantise phase is VALU-issue-bound per wave, and a third wave per SIMD fills it: qkv 45.5 -> 42.9 us, fc1 54.4 -> 50.4 us (the statistics
     // pass does not gain: 27.4 -> 28.0)
-    if constexpr (MODE == 3) strip_launch_w<MODE, NTL, 8, TM, KT>(a, st);
+    if constexpr (MODE == kEpiStats) strip_launch_w<MODE, NTL, 8, TM, KT>(a, st);
     else strip_launch_w<MODE, NTL, 12, TM, KT>(a, st);
 }
 
@@ -504,12 +504,11 @@ static void strip_launch_ln(const I8StripArgs& a0, hipStream_t st) {
 #endif
     constexpr int kLds = KT * 16 * TM * 64 + 3 * NTL * 384 * 4 + 512 + 16;
     static_assert(kLds <= 160 * 1024, "strip + constants exceed the LDS");
-    static bool once = (allow_lds(k_i8_strip<3, NTL, 8, false, TM, KT, true>, kLds), true);
+    static bool once = (allow_lds(k_i8_strip<kEpiStats, NTL, 8, false, TM, KT, true>, kLds), true);
     (void)once;
-    k_i8_strip<3, NTL, 8, false, TM, KT, true><<<dim3(cdiv(a.M, 16 * TM), 1), 8 * 64, kLds, st>>>(a);
+    k_i8_strip<kEpiStats, NTL, 8, false, TM, KT, true><<<dim3(cdiv(a.M, 16 * TM), 1), 8 * 64, kLds, st>>>(a);
 }
 
-// true when the strip kernel covers the request (the caller then launched it); false -> the general tall kernel
 static int strip_ntl(int N, int K) {   // K = 384: 3 or 4 column tiles per workgroup (qkv 1152 / fc1 1536 of ViT-S); K = 768: all 6 or 8 of them (qkv 2304 / fc1 3072 of ViT-B)
     return K == 384 ? (N % (4 * 384) == 0 ? 4 : N % (3 * 384) == 0 ? 3 : 0) : (N == 6 * 384 ? 6 : N == 8 * 384 ? 8 : 0);
 }
@@ -517,31 +516,38 @@ static int strip_ntl(int N, int K) {   // K = 384: 3 or 4 column tiles per workg
 // uint32; mode 7 floors (row + 0.5) * (1 / T) in fp32 (exact with margin for row < 2^20, T < 2^10)
 static bool strip_addressable(int M, int N, int lda, int ldc, int mode) {
     if ((int64_t)M * lda >= (1ll << 32) || M >= (1 << 22) || (int64_t)M * N >= (1ll << 32) || N >= (1 << 24)) return false;
-    if (mode == 4 && (ldc >= (1 << 24) || (int64_t)M * ldc >= (1ll << 32))) return false;
-    if (mode == 7 && M >= (1 << 20)) return false;
+    if (mode == kEpiCodes && (ldc >= (1 << 24) || (int64_t)M * ldc >= (1ll << 32))) return false;
+    if (mode == kEpiQkvCodes && M >= (1 << 20)) return false;
     return true;
 }
-bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post) {
-    if (!knobs().i8_strip || !B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !strip_addressable(M, N, lda, ldc, post->mode) || !strip_ntl(N, K)) return false;
-    if (post->mode == 3) return true;
-    if (!post->out8 || !post->out8_mask || post->qmax - post->qmin >= 256) return false;
-    if (post->mode == 7) return post->code_hd == 64 && (N / 3) % 384 == 0 && post->code_T >= 1 && post->code_T < 1024;
-    if (post->mode == 4) return !(post->out_hi || post->out_lo || post->code || post->out16_hi || post->out16_lo || !post->lut_out || !post->lutq_out || ldc % 128 != 0);
+// THE statement of what the strip kernel takes, the knob aside: i8_strip_covers answers with it before the statistics pass, launch_i8_strip launches by it.
+// has_s1 / has_stats / has_qp: the launch carries *s1, the accumulator (statistics pass), the output quantizer's qparams - ready or late (code passes)
+static bool strip_covered(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post, bool has_s1, bool has_stats, bool has_qp) {
+    if (!B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !has_s1 || !strip_addressable(M, N, lda, ldc, post->mode) || !strip_ntl(N, K)) return false;
+    if (post->mode == kEpiStats) return has_stats;
+    if (!has_qp || !post->out8 || !post->out8_mask || post->qmax - post->qmin >= 256) return false;
+    if (post->mode == kEpiQkvCodes) return post->code_hd == 64 && (N / 3) % 384 == 0 && post->code_T >= 1 && post->code_T < 1024;
+    // the codes-only form of the storing pass: grid indices + mask bits + the two tables, no 2- or 4-byte plane
+    if (post->mode == kEpiCodes) return !(post->out_hi || post->out_lo || post->code || post->out16_hi || post->out16_lo || !post->lut_out || !post->lutq_out || ldc % 128 != 0);
     return false;
+}
+// (the engine's question concerns a launch that will carry s1, the accumulator and - late_in_strip - the late record)
+bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post) {
+    return knobs().i8_strip && strip_covered(B8f, M, N, K, lda, ldc, post, true, true, true);
 }
 
 // The LN form takes the requests the statistics pass takes whose workgroups own ALL columns of their rows (one workgroup per strip: nobody else
 // would write the same codes again) - qkv / fc1 of ViT-S (K = 384, N = 1152 / 1536) and of ViT-B (K = 768, N = 2304 / 3072)
 bool i8_strip_ln_covers(const void* B8f, int M, int N, int K, int lda) {
     NTPost p1{};
-    p1.mode = 3;
+    p1.mode = kEpiStats;
     return knobs().ln_strip && lda >= K && i8_strip_covers(B8f, M, N, K, lda, N, &p1) && N == strip_ntl(N, K) * 384 && (int64_t)M * K < (1ll << 31);
 }
 bool launch_i8_strip_ln(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int ln_qmin, int ln_qmax, void* out8,
                         const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, const float* s2,
                         const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, bool force, const QpLate* ln_late) {
     if ((!(knobs().i8_strip && knobs().ln_strip) && !force) || !x || !mean || !rstd || !gamma || !beta || !out8 || !B8f || !wsum || !stats || (K != 384 && K != 768) ||
-        lda % 16 != 0 || lda < K || M < 1 || !strip_addressable(M, N, lda, N, 3) || (int64_t)M * K >= (1ll << 31))
+        lda % 16 != 0 || lda < K || M < 1 || !strip_addressable(M, N, lda, N, kEpiStats) || (int64_t)M * K >= (1ll << 31))
         return false;
     const int ntl = strip_ntl(N, K);
     if (!ntl || N != ntl * 384) return false;
@@ -558,44 +564,37 @@ bool launch_i8_strip_ln(const float* x, const float* mean, const float* rstd, co
     return true;
 }
 
+template <int MODE>
+static void strip_launch_shape(const I8StripArgs& a, int N, int K, hipStream_t st) {
+    const int ntl = strip_ntl(N, K);
+    if (K == 768) { if (ntl == 8) strip_launch<MODE, 8, 7, 12>(a, st); else strip_launch<MODE, 6, 7, 12>(a, st); }
+    else if (ntl == 4) strip_launch<MODE, 4>(a, st); else strip_launch<MODE, 3>(a, st);
+}
+// true when the strip kernel covers the request (it then launched it); false -> the general tall kernel.  force: ignore the knob, nothing else
 bool launch_i8_strip(const void* A8, const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, int ldc,
                      const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
                      const NTPost* post, bool force, const QpLate* late) {
-    if ((!knobs().i8_strip && !force) || !B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !s1 || !strip_addressable(M, N, lda, ldc, post->mode)) return false;
-    const int ntl = strip_ntl(N, K);
-    if (!ntl) return false;
-    const bool wide = K == 768;
+    if (!knobs().i8_strip && !force) return false;
+    if (!strip_covered(B8f, M, N, K, lda, ldc, post, s1 != nullptr, stats != nullptr, (post && post->qp) || (late && late->stats))) return false;
     I8StripArgs a{};
     a.A = reinterpret_cast<const int8_t*>(A8); a.Bf = reinterpret_cast<const i32x4*>(B8f); a.M = M; a.N = N; a.lda = lda;
     a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.wsum = wsum; a.aqp = a_qp; a.center = center;
-    if (post->mode == 3) {
-        if (!stats) return false;
+    if (post->mode == kEpiStats) {
         a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
-        if (wide) { if (ntl == 8) strip_launch<3, 8, 7, 12>(a, st); else strip_launch<3, 6, 7, 12>(a, st); }
-        else if (ntl == 4) strip_launch<3, 4>(a, st); else strip_launch<3, 3>(a, st);
+        strip_launch_shape<kEpiStats>(a, N, K, st);
         return true;
     }
     a.qp = post->qp; a.qmin = post->qmin; a.qmax = post->qmax;
     if (late) a.late = *late;
     a.out8 = reinterpret_cast<uint8_t*>(post->out8); a.out8_mask = reinterpret_cast<uint8_t*>(post->out8_mask);
-    if ((!a.qp && !a.late.stats) || !a.out8 || !a.out8_mask || a.qmax - a.qmin >= 256) return false;
-    if (post->mode == 7) {
-        const int D = N / 3;
-        if (post->code_hd != 64 || D % 384 != 0 || post->code_T < 1 || post->code_T >= 1024) return false;
-        a.code_T = post->code_T; a.D = D;
-        if (wide) { if (ntl == 8) strip_launch<7, 8, 7, 12>(a, st); else strip_launch<7, 6, 7, 12>(a, st); }
-        else if (ntl == 4) strip_launch<7, 4>(a, st); else strip_launch<7, 3>(a, st);
-        return true;
-    }
-    if (post->mode == 4) {
-        // the codes-only form of the storing pass: grid indices + mask bits + the two tables, no 2- or 4-byte plane
-        if (post->out_hi || post->out_lo || post->code || post->out16_hi || post->out16_lo || !post->lut_out || !post->lutq_out || ldc % 128 != 0) return false;
+    if (post->mode == kEpiQkvCodes) {
+        a.code_T = post->code_T; a.D = N / 3;
+        strip_launch_shape<kEpiQkvCodes>(a, N, K, st);
+    } else {   // kEpiCodes
         a.ldc = ldc; a.lut_out = post->lut_out; a.lutq_out = post->lutq_out; a.out16_scale = post->out16_scale;
-        if (wide) { if (ntl == 8) strip_launch<4, 8, 7, 12>(a, st); else strip_launch<4, 6, 7, 12>(a, st); }
-        else if (ntl == 4) strip_launch<4, 4>(a, st); else strip_launch<4, 3>(a, st);
-        return true;
+        strip_launch_shape<kEpiCodes>(a, N, K, st);
     }
-    return false;
+    return true;
 }
 
 }  // namespace qv

@@ -192,7 +192,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
     launch_cls_rows(prm(2), prm(3), xA, d.B, d.T, d.D, st);
     {
         NTPost post{};
-        post.mode = 6; post.qp = qp(1); post.qmin = qa; post.qmax = qb; post.resid = prm(3); post.embed_np = d.np;
+        post.mode = kEpiResidFq; post.qp = qp(1); post.qmin = qa; post.qmax = qb; post.resid = prm(3); post.embed_np = d.np;
         scal(0, &s2, &cs);
         if (launch_gemm_nt_i8(ws + p.imgq8, w8[0], wsum(0), qp(0), center, xA, d.B * d.np, d.D, d.Kpe, d.Kpe, d.Kpe, d.D, qp(0), s2, cs, prm(1), nullptr, 1, st,
                               &post))
@@ -203,7 +203,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
         if (launch_ln_quant8(xA, bprm(i, 0), bprm(i, 1), c.ln_eps, qp(aidx(i, 0)), qa, qb, center, h8, nullptr, nullptr, d.M, 1, d.D, st)) return 1;
         {
             NTPost post{};
-            post.mode = 7; post.qp = qp(aidx(i, 1)); post.qmin = qa; post.qmax = qb; post.out8 = codes; post.code_T = d.T; post.code_hd = hd;
+            post.mode = kEpiQkvCodes; post.qp = qp(aidx(i, 1)); post.qmin = qa; post.qmax = qb; post.out8 = codes; post.code_T = d.T; post.code_hd = hd;
             // (with the weight in fragment order and a place for the mask bits nobody reads here, the launcher takes the A-stationary strip kernel:
             //  the same codes bit for bit - head_dim 64, K = 384 / 768; the general tile otherwise)
             const int wq = widx(i, 0);
@@ -219,7 +219,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
             return 1;
         {
             NTPost post{};
-            post.mode = 6; post.qp = qp(aidx(i, 2)); post.qmin = qa; post.qmax = qb; post.resid = xA;
+            post.mode = kEpiResidFq; post.qp = qp(aidx(i, 2)); post.qmin = qa; post.qmax = qb; post.resid = xA;
             scal(widx(i, 1), &s2, &cs);
             if (launch_gemm_nt(ws + p.O16_hi, ws + p.O16_lo, ws + p.w16[widx(i, 1)], xB, M, d.D, d.D, d.D, d.D, d.D, scal16, s2, cs, bprm(i, 5), nullptr, 1, st,
                                nullptr, &post, true))
@@ -234,7 +234,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
             const int w1 = widx(i, 2), w2 = widx(i, 3);
             const bool strip = p.w8f[w1] >= 0 && d.Hd % 128 == 0;
             NTPost post{};
-            post.mode = 4; post.qp = qp(aidx(i, 4)); post.qmin = qa; post.qmax = qb; post.out16_scale = scal16 + 1;
+            post.mode = kEpiCodes; post.qp = qp(aidx(i, 4)); post.qmin = qa; post.qmax = qb; post.out16_scale = scal16 + 1;
             uint32_t* const glut = reinterpret_cast<uint32_t*>(ws + p.glut);
             if (strip) { post.out8 = ws + p.G8; post.out8_mask = ws + p.Gm; post.lut_out = glut; post.lutq_out = glut + 256; }
             else { post.out16_hi = ws + p.G16_hi; post.out16_lo = ws + p.G16_lo; }
@@ -243,7 +243,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
                                   bprm(i, 9), nullptr, 1, st, &post, strip ? ws + p.w8f[w1] : nullptr))
                 return 1;
             NTPost post2{};
-            post2.mode = 6; post2.qp = qp(aidx(i, 5)); post2.qmin = qa; post2.qmax = qb; post2.resid = xB;
+            post2.mode = kEpiResidFq; post2.qp = qp(aidx(i, 5)); post2.qmin = qa; post2.qmax = qb; post2.resid = xB;
             scal(w2, &s2, &cs);
             if (strip) {
                 if (launch_gemm_nt_codes(ws + p.G8, glut, ws + p.w16[w2], xA, M, d.D, d.Hd, d.Hd, d.Hd, d.D, scal16 + 1, s2, cs, bprm(i, 11), nullptr, 1, st, &post2))

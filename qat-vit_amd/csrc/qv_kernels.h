@@ -43,51 +43,54 @@ struct QpLate {
 };
 constexpr int kQpStagedWords = 8;
 
-// fused consumers of an NT GEMM's accumulators (epilogue modes)
+// ---- the epilogues of the NT GEMMs: NTPost::mode, and the kernels' template parameter (PM of k_gemm_nt, MODE of k_i8_strip).  post == nullptr is kEpiPlain; a
+// post record names one of the others.  THE table (launchers: nt = launch_gemm_nt on bf16, nt16 = its fp16 form, i8 = launch_gemm_nt_i8, strip = launch_i8_strip,
+// codes = launch_gemm_nt_codes, dy16 = launch_gemm_nt_dy16, f16strip = launch_f16_strip_gelu_bwd); qp / qmin / qmax = the quantizer every mode but 0 / 2 / 3 applies:
+//   mode               stores                                                                          NTPost fields read                              launchers
+//   kEpiPlain      0   C fp32; min / max of C -> stats                                                 -                                               all
+//   kEpiGeluFwd    2   (hi, lo) of gelu(C): bf16, or (out_f16) fp16, where out_lo may be NULL          out_hi out_lo out_f16                           nt, nt16 (teacher fc1)
+//   kEpiStats      3   nothing; min / max -> stats (first pass of a recomputed K = 384 / 768 GEMM)     -                                               nt, i8, strip
+//   kEpiCodes      4   gelu(fq(C)), whichever planes are set: bf16 (hi, lo) + uint16 code              out_hi out_lo code | out16_hi out16_lo           nt (bf16 pair + code), i8,
+//                      (q - qmin) | in_range << 15; fp16 (hi, lo) * 2^k with *out16_scale = 2^-k;      out16_scale | out8 out8_mask lut_out lutq_out    strip (out8 + out8_mask +
+//                      uint8 grid index [M, ldc] + STE mask bits [M, ldc / 8] + the 256-entry tables                                                    both tables only)
+//                      of fp16 / bf16 (hi | lo << 16) pairs of gelu(grid value) (fc1 second pass)
+//   kEpiGeluBwdU16 5   (hi, lo) of C * gelu'(grid value) * in_range * colscale, from uint16 codes      code colscale out_hi out_lo                     nt
+//   kEpiResidFq    6   C[orow] = resid[rrow] + fq(acc), frozen qp (embed_np > 0: input row b * np + p  resid embed_np                                  nt16, i8, codes
+//                      -> token row b * (np + 1) + 1 + p, resid = pos_embed rows 1 + p)
+//   kEpiQkvCodes   7   out8 = clamp(q) - qmin as uint8 in the attention layout [b][h][which][t][d];    out8 out8_mask code_T code_hd                   i8, strip
+//                      out8_mask (optional; head_dim % 32 == 0): the STE mask bits in the same order
+//   kEpiLnBwd      8   C = dx_out = dx_in + LNbwd(acc * alpha * mask(LN(x))), dgamma / dbeta += ;      lnb_* colscale out_hi out_lo                    nt (split A), dy16
+//                      (out_hi set) the (hi, lo) of dx_out * nmask * colscale for the next branch.     (dy16: o16_mul o16_amax, no out_lo)
+//                      N == ldc == 384: the tile holds whole LayerNorm rows; qp = the LN output's
+//   kEpiGeluBwdU8  9   as 5, from one byte per code + one mask bit per element                         code8 code_mask colscale out_hi out_lo          nt (split A), dy16, f16strip
+//                      (bit c % 8 of byte (row * ldc + c) / 8): what mode 4 leaves in out8 / out8_mask (dy16 / f16strip: o16_mul o16_amax, no out_lo)
+//   dy16 / f16strip emit the gradient as ONE fp16 plane (out_hi) of value * (*o16_mul) and accumulate max |value| into o16_amax (dy16.hip: Dy16Slot::amax).
+// The numbers are fixed: qatvit_i8_strip takes 3 / 4 / 7 (include/qatvit.h), -DQV_NT_EXPERIMENTS=<mode> and tools/stamp_nt.py / stamp_i8strip.py pass them.
+enum NTEpi : int {
+    kEpiPlain = 0, kEpiGeluFwd = 2, kEpiStats = 3, kEpiCodes = 4, kEpiGeluBwdU16 = 5, kEpiResidFq = 6, kEpiQkvCodes = 7, kEpiLnBwd = 8, kEpiGeluBwdU8 = 9
+};
+static_assert(kEpiStats == 3 && kEpiCodes == 4 && kEpiQkvCodes == 7, "the modes of qatvit_i8_strip (include/qatvit.h)");
 struct NTPost {
-    // mode 1 (Y != nullptr): store (hi, lo) of C * gelu'(fq(Y)) * mask(Y) * colscale   (fc2 dgrad -> GELU backward)
-    // mode 2 (Y == nullptr): store (hi, lo) of gelu(C)                                  (teacher fc1 -> GELU forward)
-    const float* Y;         // pre-FQ tensor, same [M, ldc] geometry as C
-    const float* qp;        // {scale, 1/scale, zp, enabled}
-    int qmin, qmax;
-    const float* colscale;  // optional [N]
-    void* out_hi;
-    void* out_lo;
-    // explicit modes (0 = infer 1 / 2 from Y as above):
-    //   3: statistics only - nothing is stored, the min/max accumulator is updated (first pass of a recomputed K=384 GEMM)
-    //   4: store (hi, lo) of gelu(fq(C)) and the uint16 code  (q - qmin) | in_range << 15  of every element (fc1 second pass: the fp32
-    //      pre-FQ tensor never exists; qp = the qparams the first pass' statistics produced)
-    //   5: like 1, with the mask and the grid index taken from `code` instead of recomputed from Y
-    int mode = 0;
-    void* code = nullptr;   // uint16 [M, ldc]
-    // mode 4, optional: gelu(fq(C)) once more as an fp16 (hi, lo) pair scaled by a power of two chosen from qp (the operand of the fc2
-    // FORWARD GEMM: 2^-23 per element instead of the bf16 pair's 2^-17); *out16_scale = what the pair has to be multiplied by
+    int mode = kEpiPlain;           // an NTEpi other than kEpiPlain
+    const float* qp = nullptr;      // {scale, 1/scale, zp, enabled}
+    int qmin = 0, qmax = 0;
+    const float* colscale = nullptr;   // optional [N]
+    void* out_hi = nullptr;
+    void* out_lo = nullptr;
+    int out_f16 = 0;
+    void* code = nullptr;           // uint16 [M, ldc]
     void* out16_hi = nullptr;
     void* out16_lo = nullptr;
     float* out16_scale = nullptr;
-    // inference epilogues (qp = FROZEN qparams of the output's quantizer; no statistics, the pre-FQ tensor never exists):
-    //   6: C[orow] = resid[rrow] + fq(acc)   the residual-stream update of proj / fc2 (embed_np > 0: the patch-embedding form - input row
-    //      b * np + p goes to token row b * (np + 1) + 1 + p, resid = pos_embed rows 1 + p)
-    //   7: out8 = clamp(q) - qmin as uint8 in the attention code-plane layout [b][h][which][t][d]   (qkv; code_T tokens, code_hd = head_dim)
-    // (mode 4 with out_hi / out_lo / code all NULL writes the fp16 pair only: fc1 of the inference forward)
     const float* resid = nullptr;
     int embed_np = 0;
     void* out8 = nullptr;
+    void* out8_mask = nullptr;
     int code_T = 0, code_hd = 0;
-    // mode 4, optional: out8 = the grid index (q - qmin) of every element as uint8 [M, ldc] and lut_out[256] = packed fp16 (hi | lo << 16) pair of
-    // 2^k * gelu(grid value) per index (with out16_scale): the A operand of launch_gemm_nt_codes - fc2 forward from 1 B per element
-    uint32_t* lut_out = nullptr;
-    uint32_t* lutq_out = nullptr;   // mode 4, optional: the same table as bf16 (hi | lo << 16) pairs (launch_gemm_tn_codes: the fc2 weight gradient)
-    // mode 9 (= mode 5 with the codes as one byte per element + the STE mask as one bit per element): code8 uint8 [M, ldc], code_mask bit c % 8 of
-    // byte (row * ldc + c) / 8.  Mode 4 writes that mask plane when out8_mask is set (then `code`, the uint16 plane, may be NULL).
+    uint32_t* lut_out = nullptr;    // fp16 pairs: the A operand of launch_gemm_nt_codes with out8 (fc2 forward from 1 B per element)
+    uint32_t* lutq_out = nullptr;   // bf16 pairs: launch_gemm_tn_codes (the fc2 weight gradient)
     const void* code8 = nullptr;
     const void* code_mask = nullptr;
-    // mode 7, optional (training): the STE mask bit of every element in the same order as the codes, one bit per element (head_dim % 32 == 0)
-    void* out8_mask = nullptr;
-    // mode 8 (split-A dgrad whose output rows are whole LayerNorm rows, N == 384): the LayerNorm backward fused into the epilogue -
-    // C = dx_out = dx_in + LNbwd(acc * alpha * mask(LN(x))), dgamma / dbeta accumulated, and (out_hi / out_lo non-null) the masked (hi, lo)
-    // copy of dx_out for the next branch: nmask = that branch output's STE mask words, colscale = its per-channel weight scale.
-    // qp / qmin / qmax = the LayerNorm output's quantizer.
     const float* lnb_x = nullptr;
     const float* lnb_mean = nullptr;
     const float* lnb_rstd = nullptr;
@@ -96,11 +99,7 @@ struct NTPost {
     const float* lnb_dx_in = nullptr;
     float* lnb_dgamma = nullptr;
     float* lnb_dbeta = nullptr;
-    const void* lnb_nmask = nullptr;
-    // mode 2 only: the gelu(C) pair as fp16 instead of bf16 (the fp16 teacher forward); out_lo may then be NULL (one-pass form)
-    int out_f16 = 0;
-    // launch_gemm_nt_dy16 with mode 8 / 9: the gradient the epilogue emits is ONE fp16 plane (out_hi; out_lo unused) of value * (*o16_mul),
-    // and max |value| is accumulated into o16_amax (dy16.hip: Dy16Slot::amax)
+    const void* lnb_nmask = nullptr;   // the next branch output's STE mask words
     const float* o16_mul = nullptr;
     uint32_t* o16_amax = nullptr;
 };
@@ -129,7 +128,8 @@ bool launch_f16_strip_gelu_bwd(const void* A16, const void* B16f, float* unused,
 bool launch_i8_strip(const void* A8, const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, int ldc,
                      const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
                      const NTPost* post, bool force = false, const QpLate* late = nullptr);   // late (code passes): the output quantizer's qparams are resolved inside
-// would launch_i8_strip take this request?  (the engine decides on it BEFORE the statistics pass whether a k_qparams launch has to follow it)
+// would launch_i8_strip take this request, given s1, the accumulator (statistics pass) and ready or late qparams (code passes)?  The same predicate as the
+// launcher's; the knob applies (the engine decides on it BEFORE the statistics pass whether a k_qparams launch has to follow it)
 bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post);
 // The statistics pass with the LayerNorm apply + quantise in its prologue (k_ln_apply_quant's work, the same bits): every workgroup builds its strip from the
 // fp32 rows x [M, K] (mean / rstd [M], gamma / beta [K]), keeps it in LDS and stores it to out8 [M, lda] (q - center), the plane the code pass and the weight

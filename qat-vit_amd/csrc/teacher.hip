@@ -485,8 +485,8 @@ static int teacher_forward_impl(const qatvit_cfg* cfg, void* const* params, void
         launch_resid_ln_split<1>(rows_grid_t(M), st, D, (const float*)x, (const float*)F(p.Y), (const float*)nullptr, (const float*)nullptr, x2, bprm(i, 6), bprm(i, 7), c.ln_eps, H16(p.h_hi),
                                                             LO(p.h_lo), M, D, T, f16);
         {   // fc1 with GELU + hi/lo split in the GEMM epilogue (the fp32 [M, Hd] tensor never exists)
-            NTPost post{nullptr, nullptr, 0, 0, nullptr, V(p.G_hi), passes == 1 ? nullptr : V(p.G_lo)};
-            post.out_f16 = f16;
+            NTPost post{};
+            post.mode = kEpiGeluFwd; post.out_hi = V(p.G_hi); post.out_lo = passes == 1 ? nullptr : V(p.G_lo); post.out_f16 = f16;
             if (gemm(V(p.h_hi), V(p.h_lo), w0 + 2, bprm(i, 9), nullptr, (int)M, Hd, D, &post)) return 1;
         }
         if (gemm(V(p.G_hi), V(p.G_lo), w0 + 3, bprm(i, 11), F(p.Y), (int)M, D, Hd)) return 1;
