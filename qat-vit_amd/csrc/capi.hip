@@ -202,14 +202,21 @@ int qatvit_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
     return 0;
 }
 
+// The weight gradients: a wrapper checks its own pointers, writes its parameters into a TNGemm + TNCall and names the operand form; launch_gemm_tn checks the
+// request itself (gemm.hip tn_request_ok).  QV_TN_REQUEST: the parameters all five entry points share, by name
+#define QV_TN_REQUEST(g, c)                                                                                                                                  \
+    TNGemm g;                                                                                                                                                \
+    g.C = C; g.N = N; g.Kw = Kw; g.ldp = ldp; g.ldq = ldq; g.ldc = ldc; g.W = W; g.w_scale = w_scale; g.w_zp = w_zp; g.dbias = dbias; g.row_div = row_div;  \
+    TNCall c;                                                                                                                                                \
+    c.M = M; c.w_per_channel = w_per_channel; c.w_qmin = w_qmin; c.w_qmax = w_qmax; c.scratch = scratch; c.scratch_bytes = scratch_bytes
+
 int qatvit_gemm_tn(const void* P_hi, const void* P_lo, const void* Q_hi, const void* Q_lo, float* C, int32_t M, int32_t N, int32_t Kw, int32_t ldp,
                    int32_t ldq, int32_t ldc, const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int32_t w_per_channel,
                    int32_t w_qmin, int32_t w_qmax, float* dbias, const float* row_div, float* scratch, int64_t scratch_bytes, void* stream) {
     QV_CHECK_ARG(P_hi && P_lo && Q_hi && C, "qatvit_gemm_tn: null pointer argument");
-    QV_CHECK_ARG(!W || (w_scale && w_zp), "qatvit_gemm_tn: weight mask needs w_scale and w_zp");
-    if (launch_gemm_tn(P_hi, P_lo, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
-                       (hipStream_t)stream, scratch, scratch_bytes))
-        return 1;
+    QV_TN_REQUEST(g, c);
+    g.P = P_hi; g.P_lo = P_lo; g.Q = Q_hi; g.Q_lo = Q_lo; g.s1 = s1;
+    if (launch_gemm_tn(kTNPair, g, c, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_tn");
     return 0;
 }
@@ -227,12 +234,9 @@ int qatvit_gemm_tn_dy16(const void* P16, const void* Q_hi, const void* Q_lo, con
                         int32_t w_per_channel, int32_t w_qmin, int32_t w_qmax, float* dbias, const float* row_div, float* scratch, int64_t scratch_bytes,
                         void* stream) {
     QV_CHECK_ARG(P16 && C && ((Q_hi && !Qc) || (Qc && lutQ16 && !Q_hi && !Q_lo)), "qatvit_gemm_tn_dy16: Q is either planes (Q_hi, optional Q_lo) or codes + table");
-    QV_CHECK_ARG(!W || (w_scale && w_zp), "qatvit_gemm_tn_dy16: weight mask needs w_scale and w_zp");
-    const int rc = Qc ? launch_gemm_tn_codes_dy16(P16, Qc, lutQ16, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
-                                                  (hipStream_t)stream, scratch, scratch_bytes)
-                      : launch_gemm_tn_dy16(P16, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
-                                            (hipStream_t)stream, scratch, scratch_bytes);
-    if (rc) return 1;
+    QV_TN_REQUEST(g, c);
+    g.P = P16; g.Q = Qc ? Qc : Q_hi; g.Q_lo = Q_lo; g.lut = lutQ16; g.s1 = s1; g.s2 = s2;
+    if (launch_gemm_tn(Qc ? kTNPlaneCodes : kTNPlaneF16, g, c, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_tn_dy16");
     return 0;
 }
@@ -241,10 +245,9 @@ int qatvit_gemm_tn_q8_dy16(const void* P16, const void* Q8, const float* a_qp, i
                            int32_t ldc, const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int32_t w_per_channel, int32_t w_qmin,
                            int32_t w_qmax, float* dbias, const float* row_div, float* scratch, int64_t scratch_bytes, void* stream) {
     QV_CHECK_ARG(P16 && Q8 && a_qp && C, "qatvit_gemm_tn_q8_dy16: null pointer argument");
-    QV_CHECK_ARG(!W || (w_scale && w_zp), "qatvit_gemm_tn_q8_dy16: weight mask needs w_scale and w_zp");
-    if (launch_gemm_tn_q8_dy16(P16, Q8, a_qp, center, C, M, N, Kw, ldp, ldq, ldc, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
-                               (hipStream_t)stream, scratch, scratch_bytes))
-        return 1;
+    QV_TN_REQUEST(g, c);
+    g.P = P16; g.Q = Q8; g.s1 = a_qp; g.s2 = s2; c.center = center;
+    if (launch_gemm_tn(kTNPlaneQ8, g, c, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_tn_q8_dy16");
     return 0;
 }
@@ -253,8 +256,17 @@ int64_t qatvit_gemm_tn_stream_scratch_bytes(void) { return tn_stream_scratch_byt
 int qatvit_gemm_tn_stream_dy16(int32_t mode, const struct qatvit_tn_item* items, int32_t n, int32_t M, int32_t center, int32_t w_per_channel, int32_t w_qmin, int32_t w_qmax,
                                float* scratch, int64_t scratch_bytes, void* stream) {
     QV_CHECK_ARG(items && scratch && n >= 1, "qatvit_gemm_tn_stream_dy16: null / empty argument");
-    static_assert(sizeof(qatvit_tn_item) == sizeof(TNStreamGemm), "qatvit_tn_item mirrors TNStreamGemm");
-    if (launch_tn_stream(mode, reinterpret_cast<const TNStreamGemm*>(items), n, M, center, w_per_channel, w_qmin, w_qmax, scratch, scratch_bytes, (hipStream_t)stream)) return 1;
+    QV_CHECK_ARG(n <= kTnStreamMax, "tn_stream: bad arguments (n=%d, mode=%d)", n, mode);
+    TNGemm g[kTnStreamMax];   // qatvit_tn_item is the C caller's layout, TNGemm the library's: copied, not cast
+    for (int i = 0; i < n; ++i) {
+        const qatvit_tn_item& t = items[i];
+        g[i].P = t.P; g[i].Q = t.Q; g[i].lut = t.lut; g[i].s1 = t.s1; g[i].s2 = t.s2; g[i].C = t.C; g[i].W = t.W; g[i].w_scale = t.w_scale; g[i].w_zp = t.w_zp;
+        g[i].dbias = t.dbias; g[i].row_div = t.row_div; g[i].N = t.N; g[i].Kw = t.Kw; g[i].ldp = t.ldp; g[i].ldq = t.ldq; g[i].ldc = t.ldc;
+    }
+    TNCall c;
+    c.M = M; c.center = center; c.w_per_channel = w_per_channel; c.w_qmin = w_qmin; c.w_qmax = w_qmax; c.scratch = scratch; c.scratch_bytes = scratch_bytes;
+    // mode 0 / 1 / 2 are kTNPlaneQ8 / kTNPlaneCodes / kTNPlaneF16 by value (the static_assert at enum TNForm); launch_tn_stream refuses every other number
+    if (launch_tn_stream((TNForm)mode, g, n, c, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_tn_stream_dy16");
     return 0;
 }
@@ -263,13 +275,13 @@ int qatvit_gemm_tn_codes(const void* P_hi, const void* P_lo, const void* Qc, con
                          int32_t ldq, int32_t ldc, const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int32_t w_per_channel,
                          int32_t w_qmin, int32_t w_qmax, float* dbias, const float* row_div, float* scratch, int64_t scratch_bytes, void* stream) {
     QV_CHECK_ARG(P_hi && P_lo && Qc && lutQ && C, "qatvit_gemm_tn_codes: null pointer argument");
-    QV_CHECK_ARG(!W || (w_scale && w_zp), "qatvit_gemm_tn_codes: weight mask needs w_scale and w_zp");
-    if (launch_gemm_tn_codes(P_hi, P_lo, Qc, lutQ, C, M, N, Kw, ldp, ldq, ldc, s1, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
-                             (hipStream_t)stream, scratch, scratch_bytes))
-        return 1;
+    QV_TN_REQUEST(g, c);
+    g.P = P_hi; g.P_lo = P_lo; g.Q = Qc; g.lut = lutQ; g.s1 = s1;
+    if (launch_gemm_tn(kTNPairCodes, g, c, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_tn_codes");
     return 0;
 }
+#undef QV_TN_REQUEST
 
 int64_t qatvit_gemm_tn_scratch_bytes(void) { return kTnScratchBytes; }
 

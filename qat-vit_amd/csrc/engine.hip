@@ -479,22 +479,38 @@ struct Ctx {
         return launch_gemm_nt(dY_hi, dY_lo, at<void>(p.wT_off[wi]), dX, M, K, N, N, N, K, c.w_per_channel ? nullptr : f.scale, nullptr, nullptr,
                               nullptr, nullptr, 1, st, nullptr, post);
     }
-    // the same with X as uint8 table indices + a 256-entry bf16-pair table (fc2: X = gelu(fq(fc1 output)))
-    int linear_wgrad_codes(const void* dY_hi, const void* dY_lo, int M, int wi, const void* X8, const uint32_t* lutq, float* dW, float* db) const {
-        int N, K; wshape(d, wi, &N, &K);
+    // The weight-gradient request of layer wi without its operands: dW[N,K] += sum_m dY[m,N] X[m,K] * s_x under the weight FQ's STE mask, db[N] += sum_m dY;
+    // dy_scaled: dY carries the per-channel weight scale s_w[n] (folded in for the dgrad), row_div takes it out again
+    TNGemm wgrad_request(int wi, float* dW, float* db, bool dy_scaled = true) const {
         const qatvit_fq& f = wfq[wi];
-        ProfScope ps(prof, 6, 2.0 * M * N * K, st);
-        return launch_gemm_tn_codes(dY_hi, dY_lo, X8, lutq, dW, M, N, K, N, K, K, nullptr, prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel, c.w_qmin,
-                                    c.w_qmax, db, c.w_per_channel ? f.scale : nullptr, st, at<float>(p.tn_scratch), kTnScratchBytes);
+        TNGemm g;
+        wshape(d, wi, &g.N, &g.Kw);
+        g.ldp = g.N; g.ldq = g.Kw; g.ldc = g.Kw; g.C = dW; g.dbias = db;
+        g.W = prm(wparam(d, wi)); g.w_scale = f.scale; g.w_zp = f.zero_point;
+        g.row_div = (c.w_per_channel && dy_scaled) ? f.scale : nullptr;
+        return g;
     }
-    // wgrad: dW[N,K] += sum_m dY[m,N] X[m,K] * s_x, masked by the weight FQ; db[N] += sum_m dY
+    // ... and what the weight gradients over M token rows share; the per-GEMM launches split through tn_scratch (two-phase, bit-reproducible)
+    TNCall wgrad_call(int M) const {
+        TNCall k;
+        k.M = M; k.center = center(); k.w_per_channel = c.w_per_channel; k.w_qmin = c.w_qmin; k.w_qmax = c.w_qmax;
+        k.scratch = at<float>(p.tn_scratch); k.scratch_bytes = kTnScratchBytes;
+        return k;
+    }
+    // X as uint8 table indices + a 256-entry bf16-pair table (fc2: X = gelu(fq(fc1 output)))
+    int linear_wgrad_codes(const void* dY_hi, const void* dY_lo, int M, int wi, const void* X8, const uint32_t* lutq, float* dW, float* db) const {
+        TNGemm g = wgrad_request(wi, dW, db);
+        g.P = dY_hi; g.P_lo = dY_lo; g.Q = X8; g.lut = lutq;
+        ProfScope ps(prof, 6, 2.0 * M * g.N * g.Kw, st);
+        return launch_gemm_tn(kTNPairCodes, g, wgrad_call(M), st);
+    }
+    // X as a bf16 grid plane (qkv / fc1 / patch-embed wgrad), or with X_lo a split float operand (proj / fc2 wgrad)
     int linear_wgrad(const void* dY_hi, const void* dY_lo, int M, int wi, const void* X_hi, const void* X_lo, const float* s_x, float* dW, float* db,
                      bool dy_scaled = true) const {
-        int N, K; wshape(d, wi, &N, &K);
-        const qatvit_fq& f = wfq[wi];
-        ProfScope ps(prof, X_lo ? 6 : 3, 2.0 * M * N * K, st);   // grid X (qkv / fc1 / patch-embed wgrad) | split X (proj / fc2 wgrad)
-        return launch_gemm_tn(dY_hi, dY_lo, X_hi, X_lo, dW, M, N, K, N, K, K, s_x, prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel,
-                              c.w_qmin, c.w_qmax, db, (c.w_per_channel && dy_scaled) ? f.scale : nullptr, st, at<float>(p.tn_scratch), kTnScratchBytes);
+        TNGemm g = wgrad_request(wi, dW, db, dy_scaled);
+        g.P = dY_hi; g.P_lo = dY_lo; g.Q = X_hi; g.Q_lo = X_lo; g.s1 = s_x;
+        ProfScope ps(prof, X_lo ? 6 : 3, 2.0 * M * g.N * g.Kw, st);
+        return launch_gemm_tn(kTNPair, g, wgrad_call(M), st);
     }
 };
 
@@ -751,7 +767,7 @@ struct Bwd {
     bool stream;   // deferred weight gradients (k_tn_stream): every block's gradient planes stay in the workspace, the GEMMs are collected here and run at the end of the call
     float* dxA;    // the gradient w.r.t. the current block's OUTPUT at stage entry
     float* dxB;    // ... w.r.t. x_mid inside a block
-    std::vector<TNStreamGemm> sg[3];
+    std::vector<TNGemm> sg[3];   // by TNForm: kTNPlaneQ8, kTNPlaneCodes, kTNPlaneF16
     double sflops[3] = {0.0, 0.0, 0.0};
 
     float* G(int i) const { return reinterpret_cast<float*>(grads[i]); }
@@ -828,24 +844,17 @@ int Bwd::block_one_plane(int i, bool injected) {
     // of fp16 pairs (X8: the same grid integers as q - center, one byte each - the forward's int8 operand; taken instead of the fp16 plane where k_gemm_tn_q8 applies)
     auto wgrad16 = [&](const void* P16, int k, int wi, const void* X, const void* Xc, const uint32_t* lut, const float* s_x, float* dW, float* db,
                        const void* X8 = nullptr) -> int {
-        int N, K; wshape(d, wi, &N, &K);
-        const qatvit_fq& f = x.wfq[wi];
-        const float* rdiv = c.w_per_channel ? f.scale : nullptr;
+        const TNForm form = (X8 && F.x_plane_from_q8) ? kTNPlaneQ8 : Xc ? kTNPlaneCodes : kTNPlaneF16;
+        TNGemm g = x.wgrad_request(wi, dW, db);
+        g.P = P16; g.Q = form == kTNPlaneQ8 ? X8 : Xc ? Xc : X; g.lut = lut; g.s1 = s_x; g.s2 = x.dy_inv(i, k);
+        const double flops = 2.0 * M * g.N * g.Kw;
         if (stream) {   // collected: one persistent launch per X form at the end of the call
-            const int m = X8 ? 0 : Xc ? 1 : 2;
-            sg[m].push_back(TNStreamGemm{P16, X8 ? X8 : Xc ? Xc : X, lut, s_x, x.dy_inv(i, k), dW, x.prm(wparam(d, wi)), f.scale, f.zero_point, db, rdiv, N, K, N, K, K});
-            sflops[m] += 2.0 * M * N * K;
+            sg[form].push_back(g);
+            sflops[form] += flops;
             return 0;
         }
-        ProfScope ps(x.prof, (wi == w_proj || Xc) ? 6 : 3, 2.0 * M * N * K, st);
-        if (X8 && F.x_plane_from_q8)
-            return launch_gemm_tn_q8_dy16(P16, X8, s_x, x.center(), dW, M, N, K, N, K, K, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point,
-                                          c.w_per_channel, c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
-        if (Xc)
-            return launch_gemm_tn_codes_dy16(P16, Xc, lut, dW, M, N, K, N, K, K, s_x, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel,
-                                             c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
-        return launch_gemm_tn_dy16(P16, X, nullptr, dW, M, N, K, N, K, K, s_x, x.dy_inv(i, k), x.prm(wparam(d, wi)), f.scale, f.zero_point, c.w_per_channel,
-                                   c.w_qmin, c.w_qmax, db, rdiv, st, x.at<float>(p.tn_scratch), kTnScratchBytes);
+        ProfScope ps(x.prof, (wi == w_proj || Xc) ? 6 : 3, flops, st);
+        return launch_gemm_tn(form, g, x.wgrad_call(M), st);
     };
     auto dgrad16 = [&](const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
         int N, K; wshape(d, wi, &N, &K);
@@ -976,14 +985,13 @@ int Bwd::embed() {
 
 // the collected weight gradients: one persistent launch (+ its fix-up) per X form and <= 24 GEMMs
 int Bwd::flush() {
-    const qatvit_cfg& c = x.c;
-    for (int m = 0; m < 3; ++m) {
-        for (size_t o = 0; o < sg[m].size(); o += 24) {
-            const int n = (int)std::min<size_t>(24, sg[m].size() - o);
-            ProfScope ps(x.prof, m == 0 ? 3 : 6, sflops[m] * n / (double)sg[m].size(), x.st);
-            if (launch_tn_stream(m, sg[m].data() + o, n, (int)x.d.M, x.center(), c.w_per_channel, c.w_qmin, c.w_qmax, x.at<float>(x.p.tn_stream),
-                                 tn_stream_scratch_bytes(), x.st))
-                return 1;
+    TNCall call = x.wgrad_call((int)x.d.M);
+    call.scratch = x.at<float>(x.p.tn_stream); call.scratch_bytes = tn_stream_scratch_bytes();
+    for (int m = kTNPlaneQ8; m <= kTNPlaneF16; ++m) {
+        for (size_t o = 0; o < sg[m].size(); o += kTnStreamMax) {
+            const int n = (int)std::min<size_t>(kTnStreamMax, sg[m].size() - o);
+            ProfScope ps(x.prof, m == kTNPlaneQ8 ? 3 : 6, sflops[m] * n / (double)sg[m].size(), x.st);
+            if (launch_tn_stream((TNForm)m, sg[m].data() + o, n, call, x.st)) return 1;
         }
     }
     return 0;

@@ -3,7 +3,7 @@
 // Replaces: `student_out = model(images)` ... `loss.backward()` of the reference's float epochs (qat_trainer.py:295-361 before
 // prepare_qat), the unprepared QATWrapper(vit_*_patch16_224) in fp32.  Every GEMM operand is a float tensor held as a bf16 (hi, lo)
 // pair and every product takes three MFMA passes (hi.hi + lo.hi + hi.lo, fp32 accumulate): the teacher's 3-pass form (teacher.hip),
-// here on both sides of the backward too - dgrad = launch_gemm_nt with the transposed weight pair, wgrad = launch_gemm_tn with
+// here on both sides of the backward too - dgrad = launch_gemm_nt with the transposed weight pair, wgrad = launch_gemm_tn (kTNPair) with
 // pairs on both sides.  The forward is the teacher's (patches, fused residual + LayerNorm, float attention, GELU) with the extra
 // outputs a backward needs: LayerNorm mean / rstd, attention log-sum-exp, the fc1 pre-activation, the residual stream.
 // Of the QAT engine's backward kernels the LayerNorm backward (elt.hip k_ln_bwd_fq), the GELU' pass (k_mask_bwd) and the
@@ -585,11 +585,13 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
     };
     // wgrad: dW[N, Kw] += dY[Mr, N]^T . X[Mr, Kw], dbias[N] += column sums of dY
     auto wgrad = [&](int64_t ph, int64_t pl, int64_t qh, int64_t ql, float* dW, float* db, int N, int Kw, int Mr) {
-        if (one)
-            return launch_gemm_tn_dy16(V(ph), V(qh), nullptr, dW, Mr, N, Kw, N, Kw, Kw, unit, unit, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
-                                       kTnScratchBytes, bf16);
-        return launch_gemm_tn(V(ph), V(pl), V(qh), V(ql), dW, Mr, N, Kw, N, Kw, Kw, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, db, nullptr, st, partial,
-                              kTnScratchBytes);
+        TNGemm g;
+        g.P = V(ph); g.Q = V(qh); g.C = dW; g.dbias = db; g.N = N; g.Kw = Kw; g.ldp = N; g.ldq = Kw; g.ldc = Kw;
+        if (one) g.s1 = g.s2 = unit;
+        else { g.P_lo = V(pl); g.Q_lo = V(ql); }
+        TNCall call;
+        call.M = Mr; call.scratch = partial; call.scratch_bytes = kTnScratchBytes;
+        return launch_gemm_tn(!one ? kTNPair : bf16 ? kTNPlaneBf16 : kTNPlaneF16, g, call, st);
     };
     auto head = [&] {   // dhn, and the head's weight / bias gradients
         if (one) {

@@ -1605,10 +1605,7 @@ __global__ __launch_bounds__(WM * WNK * 64) void k_gemm_tn(const TNArgs p) {
             for (int j = 0; j < TNT; ++j) {
                 const int kw = k0 + wn * (16 * TNT) + 16 * j + r;
                 float v = acc[i][j][e] * (alpha * rdiv);
-                if (p.W) {
-                    const float q = rintf(p.W[(int64_t)n * p.ldc + kw] * inv) + fzp;
-                    if (!(q >= (float)p.w_qmin && q <= (float)p.w_qmax)) v = 0.f;
-                }
+                if (p.W && ste_clips(p.W[(int64_t)n * p.ldc + kw], inv, fzp, p.w_qmin, p.w_qmax)) v = 0.f;
                 atomicAdd(&p.C[(int64_t)n * p.ldc + kw], v);
             }
         }
@@ -1673,8 +1670,7 @@ __global__ __launch_bounds__(256) void k_tn_reduce(const TNArgs p, int splits, i
     for (int e = 0; e < 4; ++e) {
         const float rdiv = __fdiv_rn(1.0f, rdv[e]);                       // (stand-in 1.0 without row_div: exactly 1)
         const float v = av[e] * (alpha * rdiv);
-        const float q = rintf(wv[e] * __fdiv_rn(1.0f, wsc[e])) + (float)wzp[e];
-        const bool clipped = p.W != nullptr && !(q >= (float)p.w_qmin && q <= (float)p.w_qmax);
+        const bool clipped = p.W != nullptr && ste_clips(wv[e], __fdiv_rn(1.0f, wsc[e]), (float)wzp[e], p.w_qmin, p.w_qmax);
         outv[e] = cv[e] + (clipped ? 0.f : v);
     }
 #pragma unroll
@@ -1900,10 +1896,7 @@ __global__ __launch_bounds__(512) void k_gemm_tn_q8(const TNArgs p) {
             for (int j = 0; j < TNT; ++j) {
                 const int kw = k0 + wn * (16 * TNT) + 16 * j + r;
                 float v = acc[i][j][e] * (alpha * rdiv);
-                if (p.W) {
-                    const float q = rintf(p.W[(int64_t)n * p.ldc + kw] * inv) + fzp;
-                    if (!(q >= (float)p.w_qmin && q <= (float)p.w_qmax)) v = 0.f;
-                }
+                if (p.W && ste_clips(p.W[(int64_t)n * p.ldc + kw], inv, fzp, p.w_qmin, p.w_qmax)) v = 0.f;
                 atomicAdd(&p.C[(int64_t)n * p.ldc + kw], v);
             }
         }
@@ -1922,162 +1915,131 @@ static int tn_plan(TNArgs& a, int M, int bk, int tiles) {
     a.tiles = tiles;
     return (steps + a.steps_per_split - 1) / a.steps_per_split;
 }
-static TNArgs tn_args(const void* P_hi, const void* P_lo, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                      const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                      const float* row_div) {
+
+// what a TNForm requires of a request beyond P, Q, C, N % 128 == 0 and ldp % 8 == 0 (the table at enum TNForm, qv_kernels.h), and how its refusal reads
+struct TNRule { const char* name; const char* what; int kw_mod, ldq_mod; bool p_lo, lut, s1; const char* need; };
+static const TNRule kTNRules[kTNForms] = {
+    /* kTNPlaneQ8    */ {"gemm_tn_q8", "arguments", 384, 16, false, false, true, "N%128==0, Kw%384==0, ldp%8==0, ldq%16==0, s1"},
+    /* kTNPlaneCodes */ {"gemm_tn_codes", "arguments", 384, 16, false, true, true, "N%128==0, Kw%384==0, ldp%8==0, ldq%16==0, s1"},
+    /* kTNPlaneF16   */ {"gemm_tn", "shape", 128, 8, false, false, false, "N%128==0, Kw%128==0, ld%8==0"},
+    /* kTNPlaneBf16  */ {"gemm_tn", "shape", 128, 8, false, false, false, "N%128==0, Kw%128==0, ld%8==0"},
+    /* kTNPair       */ {"gemm_tn", "shape", 128, 8, true, false, false, "N%128==0, Kw%128==0, ld%8==0"},
+    /* kTNPairCodes  */ {"gemm_tn_codes", "arguments", 384, 16, true, true, false, "N%128==0, Kw%384==0, ldp%8==0, ldq%16==0"},
+};
+// THE check of a weight-gradient request.  item >= 0: item `item` of a launch_tn_stream batch - k_tn_stream has the 128 x 384 tile only and reads s1 in every form
+static bool tn_request_ok(TNForm form, const TNGemm& g, int M, int item = -1) {
+    const TNRule& r = kTNRules[form];
+    const bool shape = M >= 1 && g.N >= 128 && g.N % 128 == 0 && g.Kw > 0 && g.Kw % (item >= 0 ? 384 : r.kw_mod) == 0 && g.ldp % 8 == 0 && g.ldq % r.ldq_mod == 0;
+    const bool operands = g.P && g.Q && g.C && (!r.p_lo || g.P_lo) && (!r.lut || g.lut) && (!(r.s1 || item >= 0) || g.s1) && (item < 0 || !g.Q_lo);
+    const bool mask = !g.W || (g.w_scale && g.w_zp);
+    if (shape && operands && mask) return true;
+    if (item >= 0) set_error("tn_stream: unsupported item %d (N=%d Kw=%d ldp=%d ldq=%d)", item, g.N, g.Kw, g.ldp, g.ldq);
+    else if (shape && operands) set_error("%s: weight mask needs w_scale and w_zp", r.name);
+    else set_error("%s: unsupported %s M=%d N=%d Kw=%d ldp=%d ldq=%d (need %s)", r.name, r.what, M, g.N, g.Kw, g.ldp, g.ldq, r.need);
+    return false;
+}
+// THE copy of a request into the kernels' argument record (tn_plan and tn_launch fill the launch plan in)
+static TNArgs tn_args(TNForm form, const TNGemm& g, const TNCall& call) {
+    const bool one_plane = form != kTNPair && form != kTNPairCodes, byte_q = form == kTNPlaneQ8 || form == kTNPlaneCodes || form == kTNPairCodes;
     TNArgs a{};
-    a.P0 = reinterpret_cast<const __bf16*>(P_hi); a.P1 = reinterpret_cast<const __bf16*>(P_lo); a.Q0 = reinterpret_cast<const __bf16*>(Q_hi);
-    a.Q1 = reinterpret_cast<const __bf16*>(Q_lo); a.C = C; a.M = M; a.N = N; a.Kw = Kw; a.ldp = ldp; a.ldq = ldq; a.ldc = ldc; a.s1 = s1;
-    a.W = W; a.w_scale = w_scale; a.w_zp = w_zp; a.w_per_channel = w_per_channel; a.w_qmin = w_qmin; a.w_qmax = w_qmax; a.dbias = dbias; a.row_div = row_div;
+    a.P0 = reinterpret_cast<const __bf16*>(g.P);
+    a.P1 = reinterpret_cast<const __bf16*>(one_plane ? g.P : g.P_lo);
+    if (byte_q) a.Qc = reinterpret_cast<const uint8_t*>(g.Q);
+    else { a.Q0 = reinterpret_cast<const __bf16*>(g.Q); a.Q1 = reinterpret_cast<const __bf16*>(g.Q_lo); }
+    a.lutQ = g.lut; a.s1 = g.s1; a.s2 = g.s2; a.q8_center = call.center;
+    a.C = g.C; a.M = call.M; a.N = g.N; a.Kw = g.Kw; a.ldp = g.ldp; a.ldq = g.ldq; a.ldc = g.ldc;
+    a.W = g.W; a.w_scale = g.w_scale; a.w_zp = g.w_zp; a.w_per_channel = call.w_per_channel; a.w_qmin = call.w_qmin; a.w_qmax = call.w_qmax;
+    a.dbias = g.dbias; a.row_div = g.row_div;
     return a;
 }
+// THE launch of a planned TN kernel: a.tiles x splits workgroups of WM x WNK waves, TM x TNT accumulator fragments each.  Two-phase - raw split tiles to the
+// call's scratch, summed in split order by k_tn_reduce: no atomics on C, bit-reproducible - when there is more than one split and the scratch holds them all;
+// otherwise the kernel's own tail adds into C with atomics.
+static int tn_launch(void (*kernel)(const TNArgs), size_t lds, TNArgs& a, int splits, int WM, int WNK, int TM, int TNT, const TNCall& call, hipStream_t st) {
+    const int grid = a.tiles * splits;
+    const int64_t tile_f4 = (int64_t)WM * WNK * TM * TNT * 64;
+    const bool two_phase = call.scratch && splits > 1 && (int64_t)grid * tile_f4 * 16 <= call.scratch_bytes;
+    a.partial = two_phase ? call.scratch : nullptr;
+    kernel<<<grid, WM * WNK * 64, lds, st>>>(a);
+    if (two_phase) k_tn_reduce<<<(int)cdiv((int64_t)a.tiles * tile_f4, 256), 256, 0, st>>>(a, splits, WM, WNK, TM, TNT);
+    return 0;
+}
 
-// DY16: P_hi is the one fp16 plane (P_lo unused), Q holds fp16 bit patterns, *s2 the plane's inverse scale; F16 = false with DY16: bf16 bit patterns instead
+// The plane forms.  DY16: P is the one fp16 plane, Q holds fp16 bit patterns, *s2 the plane's inverse scale; F16 = false with DY16: bf16 bit patterns instead
 template <bool DY16, bool F16 = DY16>
-static int gemm_tn_impl(const void* P_hi, const void* P_lo, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                        const float* s1, const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
-                        float* dbias, const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
-    if (M < 1 || N % 128 != 0 || Kw % 128 != 0 || ldp % 8 != 0 || ldq % 8 != 0) {
-        set_error("gemm_tn: unsupported shape M=%d N=%d Kw=%d ldp=%d ldq=%d (need N%%128==0, Kw%%128==0, ld%%8==0)", M, N, Kw, ldp, ldq);
-        return 1;
-    }
+static int tn_planes(TNArgs& a, const TNCall& call, hipStream_t st) {
     constexpr int TP = DY16 ? 1 : 2;
-    TNArgs a = tn_args(P_hi, DY16 ? P_hi : P_lo, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div);
-    a.s2 = s2;
     // Kw-panel-wide tiles (128 x 384) read the heavy operand P = dY (hi, lo) once per N tile when Kw = 384; every Kw of ViT-S/B (384, 1536, 768, 3072)
     // is a multiple of 384.  (Measured at B=256: wide wins for a grid Q operand, 110/133 us vs 113/148; with a split Q (32-row steps) it wins when
     // there are enough wide tiles - fc2 wgrad, 12 tiles: 169 vs 181 us - and loses when few tiles mean many splits - proj wgrad, 3 tiles: 84 vs 56 us)
-    const bool wide = (Kw % 384 == 0) && (!Q_lo || (N / 128) * (Kw / 384) >= 8);
+    const bool wide = (a.Kw % 384 == 0) && (!a.Q1 || (a.N / 128) * (a.Kw / 384) >= 8);
     const int bk = wide ? 32 : 64;                  // wide tiles: 32-token steps (split Q: the stage only fits that way; grid Q: a 4-deep ring)
-    const int tiles = (N / 128) * (Kw / (wide ? 384 : 128));
-    const int splits = tn_plan(a, M, bk, tiles);
-    const int grid = tiles * splits;
+    const int splits = tn_plan(a, a.M, bk, (a.N / 128) * (a.Kw / (wide ? 384 : 128)));
 #define QV_TN_LAUNCH(TQ_, NS_, WM_, WNK_, TNT_, BK_)                                                               \
     do {                                                                                                           \
         constexpr size_t lds = (size_t)NS_ * (TP * BK_ * 256 + TQ_ * BK_ * (WNK_ * TNT_ * 32));                     \
         static_assert(lds <= 160 * 1024, "LDS");                                                                   \
-        constexpr int tm = 128 / WM_ / 16;                                                                         \
-        const int64_t tile_f4 = (int64_t)WM_ * WNK_ * tm * TNT_ * 64;                                              \
-        const bool two_phase = partial && splits > 1 && (int64_t)grid * tile_f4 * 16 <= partial_bytes;             \
-        a.partial = two_phase ? partial : nullptr;                                                                 \
         static bool once = (allow_lds(k_gemm_tn<TQ_, NS_, WM_, WNK_, TNT_, BK_, false, TP, F16>, lds), true);      \
         (void)once;                                                                                                \
-        k_gemm_tn<TQ_, NS_, WM_, WNK_, TNT_, BK_, false, TP, F16><<<grid, WM_ * WNK_ * 64, lds, st>>>(a);          \
-        if (two_phase) k_tn_reduce<<<(int)cdiv((int64_t)tiles * tile_f4, 256), 256, 0, st>>>(a, splits, WM_, WNK_, tm, TNT_); \
+        return tn_launch(k_gemm_tn<TQ_, NS_, WM_, WNK_, TNT_, BK_, false, TP, F16>, lds, a, splits, WM_, WNK_, 128 / WM_ / 16, TNT_, call, st); \
     } while (0)
     if constexpr (DY16) {   // one P plane: the stages are 8 KiB (wide) / 16 KiB (narrow) smaller, the rings one stage deeper
         if (wide) {
-            if (Q_lo) QV_TN_LAUNCH(2, 2, 2, 4, 6, 32);   // 2 x (8 + 48) KiB = 112 KiB
+            if (a.Q1) QV_TN_LAUNCH(2, 2, 2, 4, 6, 32);   // 2 x (8 + 48) KiB = 112 KiB
             else QV_TN_LAUNCH(1, 5, 2, 4, 6, 32);        // 5 x (8 + 24) KiB = 160 KiB
         } else {
-            if (Q_lo) QV_TN_LAUNCH(2, 3, 4, 2, 4, 64);   // 3 x 48 KiB
+            if (a.Q1) QV_TN_LAUNCH(2, 3, 4, 2, 4, 64);   // 3 x 48 KiB
             else QV_TN_LAUNCH(1, 4, 4, 2, 4, 64);        // 4 x 32 KiB
         }
     } else if (wide) {
-        if (Q_lo) QV_TN_LAUNCH(2, 2, 2, 4, 6, 32);   // 2 x (16 + 48) KiB = 128 KiB
+        if (a.Q1) QV_TN_LAUNCH(2, 2, 2, 4, 6, 32);   // 2 x (16 + 48) KiB = 128 KiB
         else QV_TN_LAUNCH(1, 4, 2, 4, 6, 32);        // 4 x (16 + 24) KiB = 160 KiB: three 32-token tiles in flight (2 x 64-token stages: 117.5 -> 109 us)
     } else {
-        if (Q_lo) QV_TN_LAUNCH(2, 2, 4, 2, 4, 64);   // 2 x 64 KiB
+        if (a.Q1) QV_TN_LAUNCH(2, 2, 4, 2, 4, 64);   // 2 x 64 KiB
         else QV_TN_LAUNCH(1, 3, 4, 2, 4, 64);        // 3 x 48 KiB
     }
 #undef QV_TN_LAUNCH
-    return 0;
 }
 
-int launch_gemm_tn(const void* P_hi, const void* P_lo, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                   const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
-                   float* dbias, const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
-    return gemm_tn_impl<false>(P_hi, P_lo, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, nullptr, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
-                               st, partial, partial_bytes);
-}
-int launch_gemm_tn_dy16(const void* P16, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
-                        const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                        const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes, bool bf16) {
-    if (bf16)
-        return gemm_tn_impl<true, false>(P16, nullptr, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias,
-                                         row_div, st, partial, partial_bytes);
-    return gemm_tn_impl<true>(P16, nullptr, Q_hi, Q_lo, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div, st,
-                              partial, partial_bytes);
-}
-
-// The byte-Q forms of the one-plane weight gradient (k_gemm_tn_q8).  QATVIT_TN_Q8=0: the fp16-plane / expand-through-LDS kernels instead.
+// The byte-Q forms of the one-plane weight gradient (k_gemm_tn_q8): MODE 0 = kTNPlaneQ8, MODE 1 = kTNPlaneCodes.  QATVIT_TN_Q8=0: the fp16-plane /
+// expand-through-LDS kernels instead.
 template <int MODE>
-static int gemm_tn_q8_impl(const void* P16, const void* Q8, const uint32_t* lutQ16, int center, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                           const float* s1, const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
-                           float* dbias, const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
-    if (M < 1 || N % 128 != 0 || Kw % 384 != 0 || ldp % 8 != 0 || ldq % 16 != 0 || !P16 || !Q8 || !C || !s1 || (MODE == 1 && !lutQ16)) {
-        set_error("gemm_tn_q8: unsupported arguments M=%d N=%d Kw=%d ldp=%d ldq=%d (need N%%128==0, Kw%%384==0, ldp%%8==0, ldq%%16==0, s1)", M, N, Kw, ldp, ldq);
-        return 1;
-    }
-    TNArgs a = tn_args(P16, P16, nullptr, nullptr, C, M, N, Kw, ldp, ldq, ldc, s1, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div);
-    a.Qc = reinterpret_cast<const uint8_t*>(Q8); a.lutQ = lutQ16; a.s2 = s2; a.q8_center = center;
-    const int tiles = (N / 128) * (Kw / 384);
-    const int splits = tn_plan(a, M, 64, tiles);
-    const int grid = tiles * splits;
+static int tn_bytes(TNArgs& a, const TNCall& call, hipStream_t st) {
+    const int splits = tn_plan(a, a.M, 64, (a.N / 128) * (a.Kw / 384));
     // one wave row of eight waves (128 x 48 per wave): every Q fragment is expanded by exactly one wave
     constexpr int WM = 1, WNK = 8, TM = 8, TNT = 3;
     constexpr int NS = MODE == 0 ? 4 : 3;
     constexpr size_t lds = (size_t)NS * (64 * 256 + 64 * 384) + (MODE == 1 ? 256 * 32 * 4 : 0);   // 160 KiB / 152 KiB
     static_assert(lds <= 160 * 1024, "LDS");
-    const int64_t tile_f4 = (int64_t)WM * WNK * TM * TNT * 64;
-    const bool two_phase = partial && splits > 1 && (int64_t)grid * tile_f4 * 16 <= partial_bytes;
-    a.partial = two_phase ? partial : nullptr;
     static bool once = (allow_lds(k_gemm_tn_q8<MODE, NS, WM>, lds), true);
     (void)once;
-    k_gemm_tn_q8<MODE, NS, WM><<<grid, 512, lds, st>>>(a);
-    if (two_phase) k_tn_reduce<<<(int)cdiv((int64_t)tiles * tile_f4, 256), 256, 0, st>>>(a, splits, WM, WNK, TM, TNT);
-    return 0;
-}
-// grid X operand of the one-plane weight gradient as int8: Q8[m][k] = q - center, a_qp = the activation's {scale, 1/scale, zero point, enabled}
-int launch_gemm_tn_q8_dy16(const void* P16, const void* Q8, const float* a_qp, int center, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s2,
-                           const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias, const float* row_div,
-                           hipStream_t st, float* partial, int64_t partial_bytes) {
-    return gemm_tn_q8_impl<0>(P16, Q8, nullptr, center, C, M, N, Kw, ldp, ldq, ldc, a_qp, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div, st,
-                              partial, partial_bytes);
+    return tn_launch(k_gemm_tn_q8<MODE, NS, WM>, lds, a, splits, WM, WNK, TM, TNT, call, st);
 }
 
-// Weight gradient with the Q operand as uint8 table indices + a 256-entry table of bf16 (hi | lo << 16) pairs (fc2: Q = gelu(fq(fc1 output))): the
-// 128 x 384 tile of launch_gemm_tn's split-Q form, the same MFMAs in the same order - bit-identical to it on the expanded planes.
-template <bool DY16>   // DY16 (the one-plane form): the hi half of every table entry alone - X rounded to fp16, one MFMA pass (TQ = 1)
-static int gemm_tn_codes_impl(const void* P_hi, const void* P_lo, const void* Qc, const uint32_t* lutQ, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                              const float* s1, const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
-                              float* dbias, const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
-    if (M < 1 || N % 128 != 0 || Kw % 384 != 0 || ldp % 8 != 0 || ldq % 16 != 0 || !P_hi || (!DY16 && !P_lo) || !Qc || !lutQ || !C) {
-        set_error("gemm_tn_codes: unsupported arguments M=%d N=%d Kw=%d ldp=%d ldq=%d (need N%%128==0, Kw%%384==0, ldp%%8==0, ldq%%16==0)", M, N, Kw, ldp, ldq);
-        return 1;
-    }
+// The Q operand as uint8 table indices + a 256-entry table of (hi | lo << 16) pairs, expanded through LDS (fc2: Q = gelu(fq(fc1 output))): the 128 x 384 tile
+// of the split-Q plane form, the same MFMAs in the same order - kTNPairCodes is bit-identical to kTNPair on the expanded planes.
+template <bool DY16>   // DY16 (kTNPlaneCodes): the hi half of every table entry alone - X rounded to fp16, one MFMA pass (TQ = 1)
+static int tn_codes(TNArgs& a, const TNCall& call, hipStream_t st) {
     constexpr int TP = DY16 ? 1 : 2, TQ = DY16 ? 1 : 2;
-    TNArgs a = tn_args(P_hi, DY16 ? P_hi : P_lo, nullptr, nullptr, C, M, N, Kw, ldp, ldq, ldc, s1, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div);
-    a.Qc = reinterpret_cast<const uint8_t*>(Qc); a.lutQ = lutQ; a.s2 = s2;
-    const int tiles = (N / 128) * (Kw / 384);
-    const int splits = tn_plan(a, M, 32, tiles);
-    const int grid = tiles * splits;
+    const int splits = tn_plan(a, a.M, 32, (a.N / 128) * (a.Kw / 384));
     constexpr size_t lds = 3 * (TP * 32 * 256) + (TQ * 32 * 768) + 3 * (32 * 384) + 1024;   // 133 KiB (one P plane: 109 KiB; one Q plane too: 85 KiB)
-    constexpr int tm = 4;
-    const int64_t tile_f4 = (int64_t)2 * 4 * tm * 6 * 64;
-    const bool two_phase = partial && splits > 1 && (int64_t)grid * tile_f4 * 16 <= partial_bytes;
-    a.partial = two_phase ? partial : nullptr;
     static bool once = (allow_lds(k_gemm_tn<TQ, 2, 2, 4, 6, 32, true, TP, DY16>, lds), true);
     (void)once;
-    k_gemm_tn<TQ, 2, 2, 4, 6, 32, true, TP, DY16><<<grid, 512, lds, st>>>(a);
-    if (two_phase) k_tn_reduce<<<(int)cdiv((int64_t)tiles * tile_f4, 256), 256, 0, st>>>(a, splits, 2, 4, tm, 6);
-    return 0;
+    return tn_launch(k_gemm_tn<TQ, 2, 2, 4, 6, 32, true, TP, DY16>, lds, a, splits, 2, 4, 4, 6, call, st);
 }
-int launch_gemm_tn_codes(const void* P_hi, const void* P_lo, const void* Qc, const uint32_t* lutQ, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                         const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                         const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
-    return gemm_tn_codes_impl<false>(P_hi, P_lo, Qc, lutQ, C, M, N, Kw, ldp, ldq, ldc, s1, nullptr, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias,
-                                     row_div, st, partial, partial_bytes);
-}
-// the one-plane form: P16 = the gradient as one fp16 plane, lutQ16 = the table of fp16 (hi | lo << 16) pairs (what fc2's FORWARD expands the same codes through)
-int launch_gemm_tn_codes_dy16(const void* P16, const void* Qc, const uint32_t* lutQ16, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
-                              const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                              const float* row_div, hipStream_t st, float* partial, int64_t partial_bytes) {
-    if (knobs().tn_q8 && ldq % 16 == 0 && Kw % 384 == 0)
-        return gemm_tn_q8_impl<1>(P16, Qc, lutQ16, 0, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div, st, partial,
-                                  partial_bytes);
-    return gemm_tn_codes_impl<true>(P16, nullptr, Qc, lutQ16, C, M, N, Kw, ldp, ldq, ldc, s1, s2, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dbias, row_div,
-                                    st, partial, partial_bytes);
+
+int launch_gemm_tn(TNForm form, const TNGemm& g, const TNCall& call, hipStream_t st) {
+    if (form < 0 || form >= kTNForms) { set_error("gemm_tn: no operand form %d", (int)form); return 1; }
+    if (!tn_request_ok(form, g, call.M)) return 1;
+    TNArgs a = tn_args(form, g, call);
+    switch (form) {   // (in the order the kernel templates were always instantiated in: it numbers the labels of the generated code)
+    case kTNPair: return tn_planes<false>(a, call, st);
+    case kTNPlaneBf16: return tn_planes<true, false>(a, call, st);
+    case kTNPlaneF16: return tn_planes<true>(a, call, st);
+    case kTNPlaneQ8: return tn_bytes<0>(a, call, st);
+    case kTNPairCodes: return tn_codes<false>(a, call, st);
+    default: return knobs().tn_q8 ? tn_bytes<1>(a, call, st) : tn_codes<true>(a, call, st);   // kTNPlaneCodes
+    }
 }
 
 
@@ -2089,7 +2051,6 @@ int launch_gemm_tn_codes_dy16(const void* P16, const void* Qc, const uint32_t* l
 // about one tile per CU (252 / 144 / 36 tiles), so almost nothing is split: where the per-GEMM launches wrote and re-read 50 MB of raw partial tiles each (2.4 GB per step,
 // 94 launches), only the <= 2 tiles a span cuts are written raw ([2 slots per workgroup]) and summed in workgroup order by k_tn_stream_fixup - fixed order, bit-reproducible.
 // A complete tile's owner applies scale / STE mask and adds into dW itself (exclusive: no atomics).  Loop body: k_gemm_tn_q8's.
-constexpr int kTnStreamMax = 24;
 struct TNStreamItem {
     const void* P;          // fp16 gradient plane [M, ldp]
     const void* Q;          // MODE 0: int8 q - center [M, ldq]; MODE 1: uint8 codes [M, ldq]; MODE 2: fp16 plane [M, ldq] (ldq in elements)
@@ -2314,10 +2275,7 @@ __global__ __launch_bounds__(512) void k_tn_stream(const TNStreamArgs a) {
                     for (int j = 0; j < TNT; ++j) {
                         const int kw = k0 + wn * (16 * TNT) + 16 * j + r;
                         float v = acc[i][j][e] * (alpha * rdiv);
-                        if (it.W) {
-                            const float q = rintf(it.W[(int64_t)n * it.ldc + kw] * inv) + fzp;
-                            if (!(q >= (float)a.w_qmin && q <= (float)a.w_qmax)) v = 0.f;
-                        }
+                        if (it.W && ste_clips(it.W[(int64_t)n * it.ldc + kw], inv, fzp, a.w_qmin, a.w_qmax)) v = 0.f;
                         it.C[(int64_t)n * it.ldc + kw] += v;
                     }
                 }
@@ -2363,8 +2321,7 @@ __global__ __launch_bounds__(256) void k_tn_stream_fixup(const TNStreamArgs a, i
         float v = av[e] * (alpha * rdiv);
         if (it.W) {
             const int ci = a.w_per_channel ? n : 0;
-            const float qq = rintf(it.W[(int64_t)n * it.ldc + kw] * __fdiv_rn(1.0f, it.w_scale[ci])) + (float)it.w_zp[ci];
-            if (!(qq >= (float)a.w_qmin && qq <= (float)a.w_qmax)) v = 0.f;
+            if (ste_clips(it.W[(int64_t)n * it.ldc + kw], __fdiv_rn(1.0f, it.w_scale[ci]), (float)it.w_zp[ci], a.w_qmin, a.w_qmax)) v = 0.f;
         }
         it.C[(int64_t)n * it.ldc + kw] += v;
     }
@@ -2372,17 +2329,18 @@ __global__ __launch_bounds__(256) void k_tn_stream_fixup(const TNStreamArgs a, i
 
 int64_t tn_stream_scratch_bytes() { return (int64_t)2 * 256 * 128 * 384 * 4; }   // two raw tiles per workgroup, at most 256 workgroups (one per CU of an MI355X)
 
-// items[0..n): the weight-gradient GEMMs of one X form (mode 0 / 1 / 2 as above), all over the same M token rows.  N % 128 == 0, Kw % 384 == 0.
-int launch_tn_stream(int mode, const TNStreamGemm* items, int n, int M, int center, int w_per_channel, int w_qmin, int w_qmax, float* partial, int64_t partial_bytes,
-                     hipStream_t st) {
-    if (n < 1 || n > kTnStreamMax || M < 1 || mode < 0 || mode > 2 || !partial) { set_error("tn_stream: bad arguments (n=%d, mode=%d)", n, mode); return 1; }
+// items[0..n): the weight-gradient GEMMs of one X form (kTNPlaneQ8 / kTNPlaneCodes / kTNPlaneF16 = MODE 0 / 1 / 2 above), all over the same call.M token rows.
+int launch_tn_stream(TNForm form, const TNGemm* items, int n, const TNCall& call, hipStream_t st) {
+    const int M = call.M;
+    if (n < 1 || n > kTnStreamMax || M < 1 || form < kTNPlaneQ8 || form > kTNPlaneF16 || !call.scratch) { set_error("tn_stream: bad arguments (n=%d, mode=%d)", n, (int)form); return 1; }
     static int cus = 0;
     if (!cus) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 || cus > 256) cus = 256;
     }
     TNStreamArgs a{};
-    a.n = n; a.M = M; a.steps = (M + 63) / 64; a.center = center; a.w_per_channel = w_per_channel; a.w_qmin = w_qmin; a.w_qmax = w_qmax; a.partial = partial;
+    a.n = n; a.M = M; a.steps = (M + 63) / 64; a.center = call.center; a.w_per_channel = call.w_per_channel; a.w_qmin = call.w_qmin; a.w_qmax = call.w_qmax;
+    a.partial = call.scratch;
     int tiles = 0;
     for (int i = 0; i < n; ++i) tiles += (items[i].N / 128) * (items[i].Kw / 384);
     {   // A batch whose tiles do not tile the chip in lockstep (144 fc2 tiles on 256 CUs) as TWO aligned launches where a cut exists: free spans share nothing through L2
@@ -2393,8 +2351,8 @@ int launch_tn_stream(int mode, const TNStreamGemm* items, int n, int M, int cent
             for (int k = 1; k < n; ++k) {
                 t1 += (items[k - 1].N / 128) * (items[k - 1].Kw / 384);
                 if (fill_ok(t1) && fill_ok(tiles - t1)) {
-                    if (launch_tn_stream(mode, items, k, M, center, w_per_channel, w_qmin, w_qmax, partial, partial_bytes, st)) return 1;
-                    return launch_tn_stream(mode, items + k, n - k, M, center, w_per_channel, w_qmin, w_qmax, partial, partial_bytes, st);
+                    if (launch_tn_stream(form, items, k, call, st)) return 1;
+                    return launch_tn_stream(form, items + k, n - k, call, st);
                 }
             }
         }
@@ -2413,12 +2371,8 @@ int launch_tn_stream(int mode, const TNStreamGemm* items, int n, int M, int cent
     int units = 0;
     tiles = 0;
     for (int i = 0; i < n; ++i) {
-        const TNStreamGemm& s = items[i];
-        const int qal = mode == 2 ? 8 : 16;
-        if (!s.P || !s.Q || !s.C || !s.s1 || (mode == 1 && !s.lut) || s.N % 128 != 0 || s.Kw % 384 != 0 || s.ldp % 8 != 0 || s.ldq % qal != 0 || (s.W && (!s.w_scale || !s.w_zp))) {
-            set_error("tn_stream: unsupported item %d (N=%d Kw=%d ldp=%d ldq=%d)", i, s.N, s.Kw, s.ldp, s.ldq);
-            return 1;
-        }
+        const TNGemm& s = items[i];
+        if (!tn_request_ok(form, s, M, i)) return 1;
         TNStreamItem& d = a.it[i];
         d.P = s.P; d.Q = s.Q; d.lut = s.lut; d.s1 = s.s1; d.s2 = s.s2; d.C = s.C; d.W = s.W; d.w_scale = s.w_scale; d.w_zp = s.w_zp; d.dbias = s.dbias; d.row_div = s.row_div;
         d.N = s.N; d.Kw = s.Kw; d.ldp = s.ldp; d.ldq = s.ldq; d.ldc = s.ldc; d.tiles = (s.N / 128) * (s.Kw / 384); d.unit0 = units;
@@ -2429,12 +2383,12 @@ int launch_tn_stream(int mode, const TNStreamGemm* items, int n, int M, int cent
     a.units_total = units;
     a.units_per_wg = aligned ? upw_al : (units + grid - 1) / grid;
     a.rounds = rr ? rr_rounds : 1;
-    if ((int64_t)2 * grid * 128 * 384 * 4 > partial_bytes) { set_error("tn_stream: scratch too small (%lld bytes)", (long long)partial_bytes); return 1; }
+    if ((int64_t)2 * grid * 128 * 384 * 4 > call.scratch_bytes) { set_error("tn_stream: scratch too small (%lld bytes)", (long long)call.scratch_bytes); return 1; }
     constexpr size_t lds0 = 4 * (64 * 256 + 64 * 384), lds1 = 3 * (64 * 256 + 64 * 384) + 256 * 32 * 4, lds2 = 2 * (64 * 256 + 64 * 768);
     static bool once = (allow_lds(k_tn_stream<0>, lds0), allow_lds(k_tn_stream<1>, lds1), allow_lds(k_tn_stream<2>, lds2), true);
     (void)once;
-    if (mode == 0) k_tn_stream<0><<<grid, 512, lds0, st>>>(a);
-    else if (mode == 1) k_tn_stream<1><<<grid, 512, lds1, st>>>(a);
+    if (form == kTNPlaneQ8) k_tn_stream<0><<<grid, 512, lds0, st>>>(a);
+    else if (form == kTNPlaneCodes) k_tn_stream<1><<<grid, 512, lds1, st>>>(a);
     else k_tn_stream<2><<<grid, 512, lds2, st>>>(a);
     k_tn_stream_fixup<<<tiles * (8 * 24 * 64 / 256), 256, 0, st>>>(a, tiles);
     return 0;

@@ -152,6 +152,13 @@ __device__ inline bool wave_retile8(float* sO, const f32x4 (&acc)[HD / 16], floa
 __device__ inline void pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 __device__ inline void pin4_in(const float4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
 
+// The weight fake-quant's straight-through rule, for every kernel that recomputes the STE mask from the fp32 weight: the gradient of weight value w is dropped unless
+// its grid index rint(w * (1 / scale)) + zero point lies inside [qmin, qmax] (a NaN index is outside).
+__device__ inline bool ste_clips(float w, float inv_scale, float fzp, int qmin, int qmax) {
+    const float q = rintf(w * inv_scale) + fzp;
+    return !(q >= (float)qmin && q <= (float)qmax);
+}
+
 // ---------------------------------------------------------------- host
 // Raise a kernel's dynamic LDS limit above the 64 KiB default.  Once per kernel instantiation: call it from the initialiser of a function-local
 // static next to the launch, `static bool once = (allow_lds(kernel<...>, bytes), true);`.

@@ -88,7 +88,7 @@ struct NTPost {
     void* out8_mask = nullptr;
     int code_T = 0, code_hd = 0;
     uint32_t* lut_out = nullptr;    // fp16 pairs: the A operand of launch_gemm_nt_codes with out8 (fc2 forward from 1 B per element)
-    uint32_t* lutq_out = nullptr;   // bf16 pairs: launch_gemm_tn_codes (the fc2 weight gradient)
+    uint32_t* lutq_out = nullptr;   // bf16 pairs: the kTNPairCodes weight gradient (fc2)
     const void* code8 = nullptr;
     const void* code_mask = nullptr;
     const float* lnb_x = nullptr;
@@ -149,38 +149,50 @@ int launch_w8_fragment_order(const void* B8, void* B8f, int N, int K, hipStream_
 // A operand = uint8 grid indices [M, lda] expanded through lut[256] (packed fp16 hi | lo << 16 pairs) inside the kernel; B16 = weight integers as fp16
 int launch_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1,
                          const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, const NTPost* post = nullptr);
-// scratch that lets every wgrad shape take the two-phase (non-atomic, bit-reproducible) reduction: 256 workgroups x the largest tile
-constexpr int64_t kTnScratchBytes = 256ll * 128 * 384 * 4;
-int launch_gemm_tn(const void* P_hi, const void* P_lo, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                   const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax,
-                   float* dbias, const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
-// Q operand = uint8 table indices [M, ldq bytes] + lutQ[256] packed bf16 (hi | lo << 16) pairs, expanded inside the kernel (fc2 weight gradient)
-int launch_gemm_tn_codes(const void* P_hi, const void* P_lo, const void* Qc, const uint32_t* lutQ, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc,
-                         const float* s1, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                         const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
-// the one-plane forms of the two weight-gradient launchers: P16 = the gradient as ONE fp16 plane scaled by a power of two (*s2 = its inverse; the bias
-// gradient is multiplied by it too), Q = fp16 bit patterns (grid integers, an fp16 (hi, lo) pair, or codes + a table of fp16 pairs); *s1 = Q's scale.
-// bf16: P16 and Q hold bf16 bit patterns instead, v_mfma_f32_16x16x32_bf16 (the float step's bf16 form)
-int launch_gemm_tn_dy16(const void* P16, const void* Q_hi, const void* Q_lo, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
-                        const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                        const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0, bool bf16 = false);
-int launch_gemm_tn_codes_dy16(const void* P16, const void* Qc, const uint32_t* lutQ16, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s1,
-                              const float* s2, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias,
-                              const float* row_div, hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
-// ... with the grid X operand as ONE byte per element: Q8 = q - center as int8 (the forward's int8-MFMA operand), a_qp = that activation's {scale, 1/scale,
-// zero point, enabled}: X = Q8 + center - zero point, expanded to fp16 in registers (k_gemm_tn_q8).  Kw % 384 == 0, ldq % 16 == 0 (bytes).
-int launch_gemm_tn_q8_dy16(const void* P16, const void* Q8, const float* a_qp, int center, float* C, int M, int N, int Kw, int ldp, int ldq, int ldc, const float* s2,
-                           const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dbias, const float* row_div,
-                           hipStream_t st, float* partial = nullptr, int64_t partial_bytes = 0);
-// the weight gradients of one backward call, one persistent stream-K launch per X form (gemm.hip k_tn_stream): mode 0 = X as int8 grid plane (s1 = the activation's
-// qparams, `center`), 1 = uint8 codes + table (lut), 2 = fp16 plane.  All items share M.  partial: >= tn_stream_scratch_bytes().
-struct TNStreamGemm {
-    const void* P; const void* Q; const uint32_t* lut; const float* s1; const float* s2; float* C; const float* W; const float* w_scale; const int32_t* w_zp; float* dbias;
-    const float* row_div; int N, Kw, ldp, ldq, ldc;
+// ---- the weight gradients (TN GEMMs of gemm.hip): one request record, six named operand forms, two launchers.  A request computes
+//   C[n, kw] += mask(W)[n, kw] * sum_m P[m, n] * X[m, kw] * (*s1) * (*s2) / row_div[n]        dbias[n] += sum_m P[m, n] * (*s2) / row_div[n]
+// with the gradient P [M, ldp] and the layer input X [M, Kw] given by Q.  THE table (every form: N % 128 == 0, ldp % 8 == 0; ldq counts elements of Q as stored;
+// s2, W, dbias, row_div optional; a "pair" is (hi, lo) planes whose sum is the value; launch_tn_stream takes the first three forms, with Kw % 384 == 0 and s1):
+//   form              P, P_lo            Q, Q_lo                                     lut                      s1                            center   Kw %, ldq %
+//   kTNPlaneQ8     0  fp16 plane, -      int8 grid plane q - center, -               -                        the activation's {scale,      read     384, 16
+//                                                                                                             1 / scale, zero point, ..}
+//   kTNPlaneCodes  1  fp16 plane, -      uint8 table indices, -                      256 fp16 (hi | lo << 16) X's scale                     -        384, 16
+//                                                                                    pairs, hi half used
+//   kTNPlaneF16    2  fp16 plane, -      fp16 plane (grid integers), optional lo     -                        X's scale, optional           -        128, 8
+//                                        plane of an fp16 pair (per-GEMM launch only)
+//   kTNPlaneBf16   3  bf16 plane, -      bf16 plane, optional lo plane               -                        optional                      -        128, 8
+//   kTNPair        4  bf16 pair          bf16 plane (grid integers), optional lo     -                        optional                      -        128, 8
+//   kTNPairCodes   5  bf16 pair          uint8 table indices, -                      256 bf16 (hi | lo << 16) optional                      -        384, 16
+//                                                                                    pairs
+// The one-plane forms (0 - 3; DESIGN.md section 4, "dY as one fp16 plane"): P = the gradient * 2^e, *s2 = 2^-e.  X of kTNPlaneQ8 = Q + center - s1[2], expanded to
+// fp16 in registers (k_gemm_tn_q8); the byte forms read ldq in bytes.  The numbers 0 / 1 / 2 are the `mode` of qatvit_gemm_tn_stream_dy16 (include/qatvit.h).
+enum TNForm : int { kTNPlaneQ8 = 0, kTNPlaneCodes = 1, kTNPlaneF16 = 2, kTNPlaneBf16 = 3, kTNPair = 4, kTNPairCodes = 5, kTNForms = 6 };
+static_assert(kTNPlaneQ8 == 0 && kTNPlaneCodes == 1 && kTNPlaneF16 == 2, "the modes of qatvit_gemm_tn_stream_dy16 (include/qatvit.h)");
+struct TNGemm {   // one weight gradient
+    const void* P = nullptr; const void* P_lo = nullptr;
+    const void* Q = nullptr; const void* Q_lo = nullptr;
+    const uint32_t* lut = nullptr;
+    const float* s1 = nullptr; const float* s2 = nullptr;
+    float* C = nullptr;                // fp32 [N, ldc], accumulated into
+    // fp32 [N, ldc]: the weight whose fake-quant STE mask applies, with its scale and zero point ([1], or [N] with TNCall::w_per_channel)
+    const float* W = nullptr; const float* w_scale = nullptr; const int32_t* w_zp = nullptr;
+    float* dbias = nullptr;            // [N]
+    const float* row_div = nullptr;    // [N]: P was pre-multiplied by the per-channel weight scale
+    int N = 0, Kw = 0, ldp = 0, ldq = 0, ldc = 0;
 };
+struct TNCall {   // what the weight gradients of one call share
+    int M = 0;                         // token rows
+    int center = 0;                    // kTNPlaneQ8
+    int w_per_channel = 0, w_qmin = 0, w_qmax = 0;
+    float* scratch = nullptr;          // launch_gemm_tn: optional, kTnScratchBytes let every shape take the two-phase (non-atomic, bit-reproducible) split reduction;
+    int64_t scratch_bytes = 0;         // launch_tn_stream: required, >= tn_stream_scratch_bytes()
+};
+constexpr int64_t kTnScratchBytes = 256ll * 128 * 384 * 4;   // 256 workgroups x the largest tile
 int64_t tn_stream_scratch_bytes();
-int launch_tn_stream(int mode, const TNStreamGemm* items, int n, int M, int center, int w_per_channel, int w_qmin, int w_qmax, float* partial, int64_t partial_bytes,
-                     hipStream_t st);
+int launch_gemm_tn(TNForm form, const TNGemm& g, const TNCall& call, hipStream_t st);
+// n <= kTnStreamMax weight gradients of one form over the same token rows as one persistent stream-K launch (gemm.hip k_tn_stream) + its fix-up
+constexpr int kTnStreamMax = 24;
+int launch_tn_stream(TNForm form, const TNGemm* items, int n, const TNCall& call, hipStream_t st);
 // ---- elt.hip
 int launch_img_patches(const float* img, void* out_bf16, const float* qp, int qmin, int qmax, int B, int C, int H, int W, int P, hipStream_t st,
                        void* out8 = nullptr, int center = 0);

@@ -121,6 +121,77 @@ def test_wgrad_one_plane_byte_grid_vs_fp64(native_lib, M, N, Kw, center, zp):
     assert rel_l2((dW2.double() - 1e-4).cpu().numpy(), ref.cpu().numpy()) < 1e-4      # (fp32 atomics onto 1e-4: ~1e-5)
 
 
+@pytest.mark.parametrize("M", [70, 640])   # one split and the in-kernel tail | two splits for every form: k_tn_reduce with scratch, atomics without
+@pytest.mark.parametrize("kind", ["grid", "pair", "codes", "q8"])
+def test_wgrad_one_plane_mask_row_div_per_channel(native_lib, M, kind):
+    """The four per-GEMM one-plane forms with the request fields no other per-GEMM test sets: W with per-channel w_scale / w_zp, row_div and dbias, on
+    a non-zero dW.  fp64 on the rounded plane, divided by row_div, under the STE mask in the kernel's own fp32 arithmetic (rint(W * (1 / scale)) + zp).
+    row_div, w_scale and w_zp are three different vectors, so a launcher that swaps two of them fails.  N = 256, Kw = 384: the pair form takes the
+    narrow tile (2 wide tiles < 8), the others the wide one."""
+    N, Kw = 256, 384
+    g = torch.Generator(device="cuda").manual_seed(1000 + M + len(kind))
+    dy = torch.randn(M, N, generator=g, device="cuda") * 2e-6 * torch.exp(torch.randn(M, N, generator=g, device="cuda"))
+    e = 8 - int(np.floor(np.log2(dy.abs().max().item())) + 1)
+    plane = (dy * 2.0 ** e).to(torch.float16)
+    sx, center, zp = 0.0371, 128, 131
+    qh = ql = qc = lut = q8 = None
+    if kind == "grid":
+        xv = torch.randint(-255, 256, (M, Kw), generator=g, device="cuda").float()
+        qh = xv.to(torch.float16)
+    elif kind == "pair":
+        xv = torch.randn(M, Kw, generator=g, device="cuda") * 300.0
+        qh = xv.to(torch.float16)
+        ql = (xv - qh.float()).to(torch.float16)
+        xv = qh.float() + ql.float()
+    elif kind == "codes":
+        tab = torch.randn(256, generator=g, device="cuda") * 400.0
+        th = tab.to(torch.float16)
+        tl = (tab - th.float()).to(torch.float16)
+        lut = ((th.view(torch.int16).int() & 0xffff) | (tl.view(torch.int16).int() << 16)).contiguous()
+        qc = torch.randint(0, 256, (M, Kw), generator=g, device="cuda").to(torch.uint8)
+        xv = th.float()[qc.long()]
+    else:
+        q = torch.randint(0, 256, (M, Kw), generator=g, device="cuda")
+        q8 = (q - center).to(torch.int8)
+        xv = (q - zp).float()
+    W = torch.randn(N, Kw, generator=g, device="cuda")
+    wsc = 0.012 + 0.004 * torch.rand(N, generator=g, device="cuda")            # clips |W + zp * scale| > 1.5 .. 2.0: 4 - 13 % of a standard normal
+    wzp = torch.randint(-8, 9, (N,), generator=g, device="cuda").to(torch.int32)
+    rdiv = 0.5 + torch.rand(N, generator=g, device="cuda")
+    C0 = torch.randn(N, Kw, generator=g, device="cuda") * 1e-5
+    s1, s2 = _scalar(sx), _scalar(2.0 ** -e)
+    a_qp = torch.tensor([sx, 1.0 / sx, float(zp), 1.0], dtype=torch.float32, device="cuda")
+    scratch = torch.empty(native_lib.qatvit_gemm_tn_scratch_bytes(), dtype=torch.uint8, device="cuda")
+
+    def run(dW, db, sc):
+        tail = (_ptr(W), _ptr(wsc), _ptr(wzp), 1, -128, 127, _ptr(db), _ptr(rdiv), _ptr(sc), sc.numel() if sc is not None else 0, P(native.stream_ptr()))
+        if kind == "q8":
+            rc = native_lib.qatvit_gemm_tn_q8_dy16(_ptr(plane), _ptr(q8), _ptr(a_qp), center, _ptr(dW), M, N, Kw, N, Kw, Kw, _ptr(s2), *tail)
+        else:
+            rc = native_lib.qatvit_gemm_tn_dy16(_ptr(plane), _ptr(qh), _ptr(ql), _ptr(qc), _ptr(lut), _ptr(dW), M, N, Kw, N, Kw, Kw, _ptr(s1), _ptr(s2), *tail)
+        native.check(rc, "tn_dy16 " + kind)
+
+    qq = torch.round(W * (1.0 / wsc)[:, None]) + wzp.float()[:, None]
+    keep = (qq >= -128) & (qq <= 127)
+    clipped = 1.0 - keep.double().mean().item()
+    ref = (plane.double().T @ xv.double()) * (sx * 2.0 ** -e) / rdiv.double()[:, None]
+    ref = torch.where(keep, ref, torch.zeros_like(ref))
+    bref = plane.double().sum(0) * 2.0 ** -e / rdiv.double()
+    dW, db = C0.clone(), torch.zeros(N, device="cuda")
+    run(dW, db, scratch)
+    err_w, err_b = rel_l2((dW.double() - C0.double()).cpu().numpy(), ref.cpu().numpy()), rel_l2(db.cpu().numpy(), bref.cpu().numpy())
+    dW2, db2 = C0.clone(), torch.zeros(N, device="cuda")
+    run(dW2, db2, scratch)
+    dW3, db3 = torch.full((N, Kw), 1e-4, device="cuda"), torch.zeros(N, device="cuda")
+    run(dW3, db3, None)
+    err_wa, err_ba = rel_l2((dW3.double() - 1e-4).cpu().numpy(), ref.cpu().numpy()), rel_l2(db3.cpu().numpy(), bref.cpu().numpy())
+    print(f"{kind} M={M}: clipped {clipped:.4f}; scratch dW {err_w:.2e} db {err_b:.2e}; atomics dW {err_wa:.2e} db {err_ba:.2e}")
+    assert 0.01 < clipped < 0.2
+    assert err_w < 2e-5 and err_b < 2e-5
+    assert torch.equal(dW, dW2), "with scratch the splits are summed in a fixed order: same bits on a second run"
+    assert err_wa < 1e-4 and err_ba < 1e-4      # (fp32 atomics onto 1e-4: ~1e-5)
+
+
 @pytest.mark.parametrize("mode", [0, 1, 2])
 @pytest.mark.parametrize("M,shapes", [(640, [(1536, 384)] * 12 + [(1152, 384)] * 10 + [(384, 768)] * 2),      # 282 tiles of 10 steps: whole tiles in registers AND cut tiles
                                       (640, [(1536, 384)] * 24),                                                # 288 tiles: more tiles than CUs, last round 12 % full - free spans over one workgroup per CU
