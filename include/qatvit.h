@@ -471,6 +471,22 @@ int qatvit_optim_adamw(const void* param_ptrs, const void* grad_ptrs, const void
                        int64_t chunk_elems, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
                        const float* clip_out2, void* stream);
 
+/* adamw_groups: the same update for the tensors of up to QATVIT_OPTIM_MAX_GROUPS param groups in ONE launch (with grad_norm over the same tables:
+ *            one global norm, one update, whatever the number of groups).  The tables span all groups; tensor_group is a DEVICE int32 array with
+ *            one entry per tensor, the index of that tensor's row in `groups`; a tensor whose entry is outside [0, n_groups) is left untouched.
+ *            `groups` is HOST memory, read during the call only: each row's hyper-parameters become the prefactors qatvit_optim_adamw forms (in
+ *            double, narrowed once) and travel in the kernel-argument block, so a changed lr costs no copy.  step is 1-based and per group.
+ *            A tensor is updated to the same bits as by qatvit_optim_adamw with its group's values. */
+#define QATVIT_OPTIM_MAX_GROUPS 64
+typedef struct qatvit_adamw_group {
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t step;
+} qatvit_adamw_group;
+int qatvit_optim_adamw_groups(const void* param_ptrs, const void* grad_ptrs, const void* exp_avg_ptrs, const void* exp_avg_sq_ptrs,
+                              const int64_t* numel, const int32_t* tensor_group, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                              int32_t n_chunks, int64_t chunk_elems, const qatvit_adamw_group* groups, int32_t n_groups,
+                              const float* clip_out2, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Input pipeline: uint8 images resident on the device -> the normalised fp32 batch.
  * Replaces: the per-image host transform of the loaders (qat_trainer.py:209-254, evaluator.py:22-41): Resize(D, BICUBIC) through Pillow,

@@ -124,6 +124,70 @@ __global__ __launch_bounds__(kOptThreads) void k_adamw(const AdamArgs a) {
     }
 }
 
+// ---- several param groups in one launch: the seven prefactors of every group travel by value in the kernel-argument block (no host-to-device
+// copy, nothing to keep alive), and a workgroup picks its tensor's row once
+struct AdamGroup {
+    float decay, w1, beta2, w2, step_size, bc2_sqrt, eps;   // as in AdamArgs
+};
+
+struct AdamGroupsArgs {
+    float* const* params;
+    const float* const* grads;
+    float* const* exp_avg;
+    float* const* exp_avg_sq;
+    const int64_t* numel;
+    const int32_t* tensor_group;
+    const int32_t* chunk_tensor;
+    const int32_t* chunk_index;
+    int64_t chunk;
+    const float* coef;
+    int32_t n_groups;
+    AdamGroup group[QATVIT_OPTIM_MAX_GROUPS];
+};
+
+// k_adamw with AdamArgs assembled per workgroup: the same adam_one on the same operands in the same order, so a tensor is updated to the same bits
+// whichever of the two kernels it goes through (tests/test_gpu_optim_groups.py: identity).  A tensor of no group (the host cannot see that table) gets an
+// empty range instead of an early exit, so that the row - the last link of the chain chunk -> tensor -> group -> row - is fetched while the first
+// vector loads are in flight rather than in front of them.
+__global__ __launch_bounds__(kOptThreads) void k_adamw_groups(const AdamGroupsArgs ga) {
+    const int t = ga.chunk_tensor[blockIdx.x];
+    const int gi = __builtin_amdgcn_readfirstlane(ga.tensor_group[t]);   // uniform: the row is read into scalars, once
+    const bool in_group = (unsigned)gi < (unsigned)ga.n_groups;
+    const AdamGroup h = ga.group[in_group ? gi : 0];
+    const AdamArgs a{ga.params, ga.grads, ga.exp_avg, ga.exp_avg_sq, ga.numel, ga.chunk_tensor, ga.chunk_index, ga.chunk,
+                     h.decay, h.w1, h.beta2, h.w2, h.step_size, h.bc2_sqrt, h.eps, ga.coef};
+    const int64_t lo = (int64_t)a.chunk_index[blockIdx.x] * a.chunk;
+    const int64_t n = a.numel[t];
+    const int64_t hi = !in_group ? lo : lo + a.chunk < n ? lo + a.chunk : n;   // no group: both loops are empty
+    float* p = a.params[t];
+    const float* g = a.grads[t];
+    float* m = a.exp_avg[t];
+    float* v = a.exp_avg_sq[t];
+    const float coef = a.coef ? a.coef[1] : 1.0f;
+    const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    int64_t tail = lo;
+    if (al) {
+        const int64_t hi4 = lo + ((hi - lo) & ~(int64_t)3);
+        for (int64_t i = lo + 4 * threadIdx.x; i < hi4; i += 4 * kOptThreads) {
+            float4 P = *reinterpret_cast<float4*>(p + i), M = *reinterpret_cast<float4*>(m + i), V = *reinterpret_cast<float4*>(v + i);
+            const float4 G = *reinterpret_cast<const float4*>(g + i);
+            adam_one(P.x, G.x, M.x, V.x, a, coef);
+            adam_one(P.y, G.y, M.y, V.y, a, coef);
+            adam_one(P.z, G.z, M.z, V.z, a, coef);
+            adam_one(P.w, G.w, M.w, V.w, a, coef);
+            *reinterpret_cast<float4*>(p + i) = P;
+            *reinterpret_cast<float4*>(m + i) = M;
+            *reinterpret_cast<float4*>(v + i) = V;
+        }
+        tail = hi4;
+    }
+    for (int64_t i = tail + threadIdx.x; i < hi; i += kOptThreads) {
+        float P = p[i], M = m[i], V = v[i];
+        adam_one(P, g[i], M, V, a, coef);
+        p[i] = P; m[i] = M; v[i] = V;
+    }
+}
+
 }  // namespace qv
 
 using namespace qv;
@@ -162,6 +226,33 @@ int qatvit_optim_adamw(const void* param_ptrs, const void* grad_ptrs, const void
                (float)(lr / bc1), (float)sqrt(bc2), (float)eps, clip_out2};
     k_adamw<<<n_chunks, kOptThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
     QV_CHECK_LAUNCH("k_adamw");
+    return 0;
+}
+
+int qatvit_optim_adamw_groups(const void* param_ptrs, const void* grad_ptrs, const void* exp_avg_ptrs, const void* exp_avg_sq_ptrs, const int64_t* numel,
+                              const int32_t* tensor_group, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks,
+                              int64_t chunk_elems, const qatvit_adamw_group* groups, int32_t n_groups, const float* clip_out2, void* stream) {
+    QV_CHECK_ARG(param_ptrs && grad_ptrs && exp_avg_ptrs && exp_avg_sq_ptrs && numel && tensor_group && chunk_tensor && chunk_index && groups,
+                 "qatvit_optim_adamw_groups: null pointer");
+    QV_CHECK_ARG(n_chunks > 0 && chunk_elems > 0 && chunk_elems % 4 == 0, "qatvit_optim_adamw_groups: bad chunking (n_chunks=%d chunk=%lld)", n_chunks,
+                 (long long)chunk_elems);
+    QV_CHECK_ARG(n_groups >= 1 && n_groups <= QATVIT_OPTIM_MAX_GROUPS, "qatvit_optim_adamw_groups: n_groups %d outside [1, %d]", n_groups,
+                 QATVIT_OPTIM_MAX_GROUPS);
+    AdamGroupsArgs a{reinterpret_cast<float* const*>(param_ptrs), reinterpret_cast<const float* const*>(grad_ptrs),
+                     reinterpret_cast<float* const*>(exp_avg_ptrs), reinterpret_cast<float* const*>(exp_avg_sq_ptrs), numel, tensor_group, chunk_tensor,
+                     chunk_index, chunk_elems, clip_out2, n_groups, {}};
+    for (int i = 0; i < n_groups; ++i) {
+        const qatvit_adamw_group& g = groups[i];
+        QV_CHECK_ARG(g.step >= 1 && g.lr >= 0. && g.beta1 >= 0. && g.beta1 < 1. && g.beta2 >= 0. && g.beta2 < 1. && g.eps >= 0. && g.weight_decay >= 0.,
+                     "qatvit_optim_adamw_groups: bad hyper-parameters in group %d (step=%lld lr=%g betas=(%g, %g) eps=%g weight_decay=%g)", i,
+                     (long long)g.step, g.lr, g.beta1, g.beta2, g.eps, g.weight_decay);
+        // the prefactors of qatvit_optim_adamw, formed the same way (doubles, narrowed once)
+        const double bc1 = 1.0 - pow(g.beta1, (double)g.step), bc2 = 1.0 - pow(g.beta2, (double)g.step);
+        a.group[i] = AdamGroup{(float)(1.0 - g.lr * g.weight_decay), (float)(1.0 - g.beta1), (float)g.beta2, (float)(1.0 - g.beta2),
+                               (float)(g.lr / bc1), (float)sqrt(bc2), (float)g.eps};
+    }
+    k_adamw_groups<<<n_chunks, kOptThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
+    QV_CHECK_LAUNCH("k_adamw_groups");
     return 0;
 }
 

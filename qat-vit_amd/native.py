@@ -30,6 +30,7 @@ SIGNATURES = {
     "qatvit_kd_ce_loss_table": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "qatvit_optim_grad_norm": (c_int, [c_void_p] * 4 + [c_int32, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "qatvit_optim_adamw": (c_int, [c_void_p] * 7 + [c_int32, c_int64] + [c_double] * 5 + [c_int64, c_void_p, c_void_p]),
+    "qatvit_optim_adamw_groups": (c_int, [c_void_p] * 8 + [c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     "qatvit_gemm_nt": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_gemm_nt_f16": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_gemm_nt_i8_minmax": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
@@ -127,6 +128,11 @@ def vit_shape(model) -> dict:
 class TNItem(ctypes.Structure):
     """struct qatvit_tn_item (include/qatvit.h)."""
     _fields_ = [(n, c_void_p) for n in ("P", "Q", "lut", "s1", "s2", "C", "W", "w_scale", "w_zp", "dbias", "row_div")] + [(n, c_int32) for n in ("N", "Kw", "ldp", "ldq", "ldc")]
+
+
+class AdamWGroup(ctypes.Structure):
+    """struct qatvit_adamw_group (include/qatvit.h)."""
+    _fields_ = [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("step", c_int64)]
 
 
 class FQ(ctypes.Structure):
