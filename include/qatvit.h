@@ -504,11 +504,28 @@ int qatvit_optim_adamw_groups(const void* param_ptrs, const void* grad_ptrs, con
  *   index outside 0 .. N-1 is the caller's error (it reads image 0 or N-1, never outside data); coeffs int32 [6 * D] = the three arrays
  *   of qatvit_image_resize_coeffs(S, D) one after the other (xmin, ntaps, coef), table fp32 [768], both on the device;
  *   out fp32 [B, 3, D, D] contiguous, 16-byte aligned.  B <= 65535.
+ *
+ * qatvit_image_batch_aug: the same launch with a random crop and a horizontal flip of the uint8 SOURCE image in front of the resize, where
+ *   Compose([RandomCrop(S, padding=p), RandomHorizontalFlip(), Resize(D, BICUBIC), ToTensor(), Normalize()]) has them.  aug int32 [B] on the
+ *   device, 4-byte aligned, one word per batch POSITION b (not per image number index[b]):
+ *     bits 0..7 oy (signed), bits 8..15 ox (signed), bit 16 flip, all other bits zero.
+ *   The augmented image A of the source I (S x S x 3) is
+ *     A[y][x][c] = E[y + oy][xf + ox][c],  xf = flip ? S-1-x : x
+ *   where E extends I beyond its borders:
+ *     padding_mode 0 (constant): a coordinate outside [0, S) gives the byte `fill` (0 .. 255, the same for all channels);
+ *     padding_mode 1 (reflect, the edge not repeated, as np.pad(mode="reflect") and torchvision): u < 0 -> -u, u > S-1 -> 2(S-1) - u, the
+ *       result then clamped to [0, S-1].
+ *   This is torchvision's hflip(crop(pad(I, p), top = i, left = j)) with oy = i - p, ox = j - p.  The resize, the rounding, the value table and
+ *   the output layout are qatvit_image_batch's: the result EQUALS qatvit_image_batch's on the uint8 image A.  Every word is safe: in constant
+ *   mode an offset that moves the whole window off the image gives an all-`fill` source; in reflect mode the clamp keeps every read inside
+ *   the image (one reflection is exact for |oy|, |ox| <= S-1).  aug == NULL launches qatvit_image_batch's kernel: no augmentation.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
 int qatvit_image_batch(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                        const float* table, float* out, void* stream);
+int qatvit_image_batch_aug(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                           const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

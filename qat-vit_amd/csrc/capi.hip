@@ -366,4 +366,19 @@ int qatvit_image_batch(const uint8_t* data, const int64_t* index, int32_t B, int
     return 0;
 }
 
+int qatvit_image_batch_aug(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                           const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, float* out, void* stream) {
+    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch_aug: null pointer argument");
+    if (image_shape_ok("qatvit_image_batch_aug", S, D)) return 1;
+    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_aug: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
+    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_aug: batch %d of a data set of %d images needs an index", B, N);
+    QV_CHECK_ARG(padding_mode == 0 || padding_mode == 1, "qatvit_image_batch_aug: unknown padding_mode %d (0 = constant, 1 = reflect)", padding_mode);
+    QV_CHECK_ARG(fill >= 0 && fill <= 255, "qatvit_image_batch_aug: fill %d is outside 0 .. 255", fill);
+    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)aug & 3) == 0,
+                 "qatvit_image_batch_aug: misaligned pointer");
+    launch_image_batch_aug(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, out, (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_image_batch_aug");
+    return 0;
+}
+
 }  // extern "C"

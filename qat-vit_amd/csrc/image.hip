@@ -85,93 +85,13 @@ __device__ inline int img_round_clip(int acc) {
     return acc < 0 ? 0 : (acc > 255 ? 255 : acc);
 }
 
-// DT = the output size as a constant (its divisions become multiplications), or 0: taken from D_rt.
-template <int DT>
-__global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
-                                                             int max_rows, const int32_t* __restrict__ coeffs, const float* __restrict__ table,
-                                                             float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int D = DT ? DT : D_rt;
-    const int row_bytes = S * 3, src_bytes = (max_rows * row_bytes + 15) & ~15;
-    int32_t* s_xmin = (int32_t*)smem;                    // [D]
-    int32_t* s_coef = s_xmin + D;                        // [D][4]
-    float* s_table = (float*)(s_coef + D * kImgTaps);    // [3][256]
-    uint8_t* s_src = (uint8_t*)(s_table + 768);          // [max_rows][S][3]
-    uint8_t* s_tmp = s_src + src_bytes;                  // [max_rows][3][D]
-
-    const int tid = threadIdx.x, b = blockIdx.y;
-    const int y0 = blockIdx.x * kImgBand, y1 = min(y0 + kImgBand, D);
-    int64_t img = index ? index[b] : b;
-    img = img < 0 ? 0 : (img >= N ? N - 1 : img);        // the range is the caller's contract; a bad index must still not read outside data
-
-    // rows of the source this band reads; clamped so that tables other than qatvit_image_resize_coeffs' cannot send a read outside the image
-    int r0 = coeffs[y0], r1 = coeffs[y1 - 1] + coeffs[D + y1 - 1];
-    r0 = max(0, min(r0, S - 1));
-    r1 = max(r0 + 1, min(r1, min(S, r0 + max_rows)));
-    const int nrows = r1 - r0;
-
-    for (int i = tid; i < D; i += kImgThreads) s_xmin[i] = coeffs[i];
-    for (int i = tid; i < D * kImgTaps; i += kImgThreads) s_coef[i] = coeffs[2 * D + i];
-    for (int i = tid; i < 768; i += kImgThreads) s_table[i] = table[i];
-    const uint8_t* src = data + (img * S + r0) * (int64_t)row_bytes;
-    const int nbytes = nrows * row_bytes;
-    if ((((uintptr_t)src | (uintptr_t)nbytes) & 3) == 0) {
-        for (int i = tid; i < nbytes / 4; i += kImgThreads) ((uint32_t*)s_src)[i] = ((const uint32_t*)src)[i];
-    } else {
-        for (int i = tid; i < nbytes; i += kImgThreads) s_src[i] = src[i];
-    }
-    __syncthreads();
-
-    // horizontal pass: one item = four neighbouring outputs of one (row, channel), written as one dword.  Taps past a short window have coefficient 0,
-    // so all four are always taken, from a clamped position.
-    const int D4 = D / 4;
-    for (int it = tid; it < nrows * 3 * D4; it += kImgThreads) {
-        const int x4 = it % D4, rc = it / D4, c = rc % 3, r = rc / 3;
-        const uint8_t* line = s_src + r * row_bytes + c;
-        const int4 xm = ((const int4*)s_xmin)[x4];
-        const int xms[4] = {xm.x, xm.y, xm.z, xm.w};
-        int px[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int4 k = ((const int4*)s_coef)[x4 * 4 + j];
-            const int p = max(0, xms[j]);
-            int acc = 1 << (kImgBits - 1);
-            acc += __mul24((int)line[min(p, S - 1) * 3], k.x);
-            acc += __mul24((int)line[min(p + 1, S - 1) * 3], k.y);
-            acc += __mul24((int)line[min(p + 2, S - 1) * 3], k.z);
-            acc += __mul24((int)line[min(p + 3, S - 1) * 3], k.w);
-            px[j] = img_round_clip(acc);
-        }
-        // packed through v_perm_b32: hipcc turns the plain (shift, clamp, | << 8) pair into v_ashr_pk_u8_i32 and then takes the upper half of its
-        // result for zero, which on the MI355X it is not (bytes 2 and 3 of the dword came out wrong)
-        ((uint32_t*)s_tmp)[rc * D4 + x4] = __builtin_amdgcn_perm((uint32_t)(px[2] | px[3] << 16), (uint32_t)(px[0] | px[1] << 16), 0x06040200u);
-    }
-    __syncthreads();
-
-    // vertical pass + value table + store
-    const int band4 = (y1 - y0) * D4;
-    float* obase = out + (int64_t)b * 3 * D * D + (int64_t)y0 * D;
-    for (int it = tid; it < 3 * band4; it += kImgThreads) {
-        const int c = it / band4, e = it % band4, y = y0 + e / D4, x4 = e % D4;
-        const int4 k = ((const int4*)s_coef)[y];
-        const int rel = s_xmin[y] - r0, last = nrows - 1;
-        const uint32_t* plane = (const uint32_t*)s_tmp + c * D4 + x4;
-        const uint32_t t0 = plane[max(0, min(rel, last)) * 3 * D4], t1 = plane[max(0, min(rel + 1, last)) * 3 * D4];
-        const uint32_t t2 = plane[max(0, min(rel + 2, last)) * 3 * D4], t3 = plane[max(0, min(rel + 3, last)) * 3 * D4];
-        const float* tab = s_table + c * 256;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int acc = 1 << (kImgBits - 1);
-            acc += __mul24((int)((t0 >> (8 * j)) & 255), k.x);
-            acc += __mul24((int)((t1 >> (8 * j)) & 255), k.y);
-            acc += __mul24((int)((t2 >> (8 * j)) & 255), k.z);
-            acc += __mul24((int)((t3 >> (8 * j)) & 255), k.w);
-            v[j] = tab[img_round_clip(acc)];
-        }
-        *(float4*)(obase + (int64_t)c * D * D + (int64_t)e * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
+// the kernel, once per form (image_kernel.h)
+#define QV_IMAGE_AUG 0
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#define QV_IMAGE_AUG 1
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
 
 int64_t image_lds_bytes(int S, int D) {
     const int mr = image_max_rows(S, D);
@@ -183,6 +103,16 @@ int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, 
     const dim3 grid((D + kImgBand - 1) / kImgBand, B);
     auto kern = D == 224 ? k_image_batch<224> : k_image_batch<0>;
     hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)image_lds_bytes(S, D), st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out);
+    return 0;
+}
+
+int launch_image_batch_aug(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                           const int32_t* aug, int padding_mode, int fill, float* out, hipStream_t st) {
+    if (!aug) return launch_image_batch(data, index, B, N, S, D, coeffs, table, out, st);
+    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
+    auto kern = D == 224 ? k_image_batch_aug<224> : k_image_batch_aug<0>;
+    hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)image_lds_bytes(S, D), st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out,
+                       aug, padding_mode, fill);
     return 0;
 }
 

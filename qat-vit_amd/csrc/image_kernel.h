@@ -1,0 +1,119 @@
+// The kernel of image.hip, which includes this text twice: QV_IMAGE_AUG 0 gives k_image_batch<DT>, QV_IMAGE_AUG 1 gives k_image_batch_aug<DT>, whose
+// staged source rows are rows of the augmented image A (include/qatvit.h), fetched through the word aug[b].  Everything behind the staging is the
+// same text for both.  Text, not a shared __device__ function: inlined into two kernels, the common body changed the instruction schedule of
+// k_image_batch<0>, and the non-augmenting kernels are to stay the machine code they were (profiles/augment_bench.txt).  No include guard.
+// DT = the output size as a constant (its divisions become multiplications), or 0: taken from D_rt.
+template <int DT>
+#if QV_IMAGE_AUG
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_aug(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                 int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
+                                                                 const float* __restrict__ table, float* __restrict__ out,
+                                                                 const int32_t* __restrict__ aug, int reflect, int fill) {
+#else
+__global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
+                                                             int max_rows, const int32_t* __restrict__ coeffs, const float* __restrict__ table,
+                                                             float* __restrict__ out) {
+#endif
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int D = DT ? DT : D_rt;
+    const int row_bytes = S * 3, src_bytes = (max_rows * row_bytes + 15) & ~15;
+    int32_t* s_xmin = (int32_t*)smem;                    // [D]
+    int32_t* s_coef = s_xmin + D;                        // [D][4]
+    float* s_table = (float*)(s_coef + D * kImgTaps);    // [3][256]
+    uint8_t* s_src = (uint8_t*)(s_table + 768);          // [max_rows][S][3]
+    uint8_t* s_tmp = s_src + src_bytes;                  // [max_rows][3][D]
+
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int y0 = blockIdx.x * kImgBand, y1 = min(y0 + kImgBand, D);
+    int64_t img = index ? index[b] : b;
+    img = img < 0 ? 0 : (img >= N ? N - 1 : img);        // the range is the caller's contract; a bad index must still not read outside data
+
+    // rows of the source this band reads; clamped so that tables other than qatvit_image_resize_coeffs' cannot send a read outside the image
+    int r0 = coeffs[y0], r1 = coeffs[y1 - 1] + coeffs[D + y1 - 1];
+    r0 = max(0, min(r0, S - 1));
+    r1 = max(r0 + 1, min(r1, min(S, r0 + max_rows)));
+    const int nrows = r1 - r0;
+
+    for (int i = tid; i < D; i += kImgThreads) s_xmin[i] = coeffs[i];
+    for (int i = tid; i < D * kImgTaps; i += kImgThreads) s_coef[i] = coeffs[2 * D + i];
+    for (int i = tid; i < 768; i += kImgThreads) s_table[i] = table[i];
+#if QV_IMAGE_AUG
+    // one item = one pixel of the rows r0 .. r1-1 of A.  The word is the workgroup's (blockIdx.y): one scalar load.  Both coordinates are clamped
+    // after the reflection, so the three byte loads stay inside the image whatever the word holds; in constant mode their result is replaced.
+    const int w = aug[b];
+    const int oy = (int)(int8_t)(w & 255), ox = (int)(int8_t)((w >> 8) & 255), flip = (w >> 16) & 1;
+    const uint8_t* image = data + img * S * (int64_t)row_bytes;
+    for (int i = tid; i < nrows * S; i += kImgThreads) {
+        const int r = i / S, x = i - r * S;
+        int sy = r0 + r + oy, sx = (flip ? S - 1 - x : x) + ox;
+        const bool outside = !reflect && ((unsigned)sy >= (unsigned)S || (unsigned)sx >= (unsigned)S);
+        sy = sy < 0 ? -sy : sy, sx = sx < 0 ? -sx : sx;
+        sy = sy > S - 1 ? 2 * (S - 1) - sy : sy, sx = sx > S - 1 ? 2 * (S - 1) - sx : sx;
+        sy = max(0, min(sy, S - 1)), sx = max(0, min(sx, S - 1));
+        const uint8_t* px = image + (sy * S + sx) * 3;
+        uint8_t* dst = s_src + i * 3;
+        dst[0] = outside ? (uint8_t)fill : px[0];
+        dst[1] = outside ? (uint8_t)fill : px[1];
+        dst[2] = outside ? (uint8_t)fill : px[2];
+    }
+#else
+    const uint8_t* src = data + (img * S + r0) * (int64_t)row_bytes;
+    const int nbytes = nrows * row_bytes;
+    if ((((uintptr_t)src | (uintptr_t)nbytes) & 3) == 0) {
+        for (int i = tid; i < nbytes / 4; i += kImgThreads) ((uint32_t*)s_src)[i] = ((const uint32_t*)src)[i];
+    } else {
+        for (int i = tid; i < nbytes; i += kImgThreads) s_src[i] = src[i];
+    }
+#endif
+    __syncthreads();
+
+    // horizontal pass: one item = four neighbouring outputs of one (row, channel), written as one dword.  Taps past a short window have coefficient 0,
+    // so all four are always taken, from a clamped position.
+    const int D4 = D / 4;
+    for (int it = tid; it < nrows * 3 * D4; it += kImgThreads) {
+        const int x4 = it % D4, rc = it / D4, c = rc % 3, r = rc / 3;
+        const uint8_t* line = s_src + r * row_bytes + c;
+        const int4 xm = ((const int4*)s_xmin)[x4];
+        const int xms[4] = {xm.x, xm.y, xm.z, xm.w};
+        int px[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int4 k = ((const int4*)s_coef)[x4 * 4 + j];
+            const int p = max(0, xms[j]);
+            int acc = 1 << (kImgBits - 1);
+            acc += __mul24((int)line[min(p, S - 1) * 3], k.x);
+            acc += __mul24((int)line[min(p + 1, S - 1) * 3], k.y);
+            acc += __mul24((int)line[min(p + 2, S - 1) * 3], k.z);
+            acc += __mul24((int)line[min(p + 3, S - 1) * 3], k.w);
+            px[j] = img_round_clip(acc);
+        }
+        // packed through v_perm_b32: hipcc turns the plain (shift, clamp, | << 8) pair into v_ashr_pk_u8_i32 and then takes the upper half of its
+        // result for zero, which on the MI355X it is not (bytes 2 and 3 of the dword came out wrong)
+        ((uint32_t*)s_tmp)[rc * D4 + x4] = __builtin_amdgcn_perm((uint32_t)(px[2] | px[3] << 16), (uint32_t)(px[0] | px[1] << 16), 0x06040200u);
+    }
+    __syncthreads();
+
+    // vertical pass + value table + store
+    const int band4 = (y1 - y0) * D4;
+    float* obase = out + (int64_t)b * 3 * D * D + (int64_t)y0 * D;
+    for (int it = tid; it < 3 * band4; it += kImgThreads) {
+        const int c = it / band4, e = it % band4, y = y0 + e / D4, x4 = e % D4;
+        const int4 k = ((const int4*)s_coef)[y];
+        const int rel = s_xmin[y] - r0, last = nrows - 1;
+        const uint32_t* plane = (const uint32_t*)s_tmp + c * D4 + x4;
+        const uint32_t t0 = plane[max(0, min(rel, last)) * 3 * D4], t1 = plane[max(0, min(rel + 1, last)) * 3 * D4];
+        const uint32_t t2 = plane[max(0, min(rel + 2, last)) * 3 * D4], t3 = plane[max(0, min(rel + 3, last)) * 3 * D4];
+        const float* tab = s_table + c * 256;
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int acc = 1 << (kImgBits - 1);
+            acc += __mul24((int)((t0 >> (8 * j)) & 255), k.x);
+            acc += __mul24((int)((t1 >> (8 * j)) & 255), k.y);
+            acc += __mul24((int)((t2 >> (8 * j)) & 255), k.z);
+            acc += __mul24((int)((t3 >> (8 * j)) & 255), k.w);
+            v[j] = tab[img_round_clip(acc)];
+        }
+        *(float4*)(obase + (int64_t)c * D * D + (int64_t)e * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}

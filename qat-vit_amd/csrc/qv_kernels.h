@@ -322,6 +322,10 @@ int image_resize_coeffs(int src, int dst, int32_t* xmin, int32_t* ntaps, int32_t
 void image_table(const float* mean, const float* stdv, float* table);                      // host only
 int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table, float* out,
                        hipStream_t st);
+// the same with a crop offset and a flip of the source per batch position (aug int32 [B]: oy | ox << 8 | flip << 16; include/qatvit.h); aug == nullptr:
+// launch_image_batch.  padding_mode 0 = constant (fill), 1 = reflect
+int launch_image_batch_aug(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                           const int32_t* aug, int padding_mode, int fill, float* out, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

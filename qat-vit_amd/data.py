@@ -1,8 +1,9 @@
-"""Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch).
+"""Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug).
 
 Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
 ``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
 writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced, equal to it element for element.
+``RandomCropFlip`` adds ``RandomCrop(S, padding=p)`` + ``RandomHorizontalFlip()`` in front of the resize, inside the same launch (section 7l).
 There is no CPU path: CPU tensors raise."""
 import os
 import pickle
@@ -36,8 +37,43 @@ def value_table(mean=IMAGENET_MEAN, std=IMAGENET_STD):
     return table
 
 
+PADDING_MODES = {"constant": 0, "reflect": 1}
+
+
+def _padding_mode_and_fill(padding_mode, fill):
+    if padding_mode not in PADDING_MODES:
+        raise ValueError(f"padding_mode must be one of {sorted(PADDING_MODES)}, got {padding_mode!r}")
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
+        raise ValueError(f"fill must be an integer byte value 0 .. 255 (the same for all channels), got {fill!r}")
+    return PADDING_MODES[padding_mode], fill
+
+
+class RandomCropFlip:
+    """``RandomCrop(S, padding=padding, padding_mode=..., fill=...)`` + ``RandomHorizontalFlip(flip)`` of the uint8 source image as one int32 word
+    per sample (include/qatvit.h): bits 0..7 the row offset ``oy``, bits 8..15 the column offset ``ox`` (both signed, in ``[-padding, padding]``:
+    torchvision's ``top - padding`` / ``left - padding``), bit 16 the flip, all other bits zero.  Built and drawn on the host; needs no GPU."""
+
+    def __init__(self, padding=4, flip=0.5, padding_mode="constant", fill=0):
+        if isinstance(padding, bool) or not isinstance(padding, int) or not 0 <= padding <= 127:
+            raise ValueError(f"padding must be an integer 0 .. 127, got {padding!r}")
+        if isinstance(flip, bool) or not isinstance(flip, (int, float)) or not 0 <= flip <= 1:
+            raise ValueError(f"flip must be a probability 0 .. 1, got {flip!r}")
+        _, self.fill = _padding_mode_and_fill(padding_mode, fill)
+        self.padding, self.flip, self.padding_mode = padding, float(flip), padding_mode
+
+    def draw(self, n, generator=None):
+        """int32 CPU tensor [n].  The rule: ``off = torch.randint(0, 2 * padding + 1, (n, 2), generator=g) - padding`` (row k is ``[oy, ox]``), then
+        ``flip_k = torch.rand(n, generator=g) < flip``.  Both draws are always made, so the generator ends where it ends for any setting."""
+        off = torch.randint(0, 2 * self.padding + 1, (n, 2), generator=generator) - self.padding
+        flip = torch.rand(n, generator=generator) < self.flip
+        return ((off[:, 0] & 255) | (off[:, 1] & 255) << 8 | flip.to(torch.int64) << 16).to(torch.int32)
+
+
 class GpuResizeNormalize:
-    """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch."""
+    """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch.
+    With ``aug`` (int32 ``[B]`` on the device, the words of ``RandomCropFlip.draw``; word b belongs to batch position b) the source of sample b is
+    cropped at its offset out of the image extended by ``padding_mode`` / ``fill`` and flipped first, in the same launch.  ``padding`` states the
+    bound of the offsets in ``aug`` where the caller knows it: reflect mode is exact for offsets up to ``S - 1`` and a larger bound is refused."""
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
         self.src_size, self.out_size = int(src_size), int(out_size)
@@ -50,7 +86,7 @@ class GpuResizeNormalize:
         self.coeffs = torch.cat([t.flatten() for t in resize_tables(self.src_size, self.out_size)]).to(self.device)
         self.table = value_table(mean, std).to(self.device)
 
-    def __call__(self, data_u8, index=None, out=None):
+    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None):
         S, D = self.src_size, self.out_size
         if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
             raise RuntimeError("GpuResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
@@ -71,7 +107,19 @@ class GpuResizeNormalize:
             out = torch.empty(B, 3, D, D, dtype=torch.float32, device=self.device)
         elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, D, D) or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"out must be a contiguous fp32 [{B}, 3, {D}, {D}] tensor on {self.device}")
-        if B:
+        mode, fill = _padding_mode_and_fill(padding_mode, fill)
+        if aug is not None:
+            if not isinstance(aug, torch.Tensor) or aug.dtype != torch.int32 or tuple(aug.shape) != (B,) or not aug.is_contiguous() \
+                    or aug.device != self.device:
+                raise ValueError(f"aug must be a contiguous int32 [{B}] tensor on {self.device}")
+            if mode == PADDING_MODES["reflect"] and padding is not None and padding > S - 1:
+                raise ValueError(f"reflect padding reflects once: offsets up to {padding} exceed S - 1 = {S - 1}")
+        if B and aug is not None:
+            with torch.cuda.device(self.device):
+                native.check(native.lib().qatvit_image_batch_aug(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
+                                                                 aug.data_ptr(), mode, fill, out.data_ptr(), native.stream_ptr()),
+                             "qatvit_image_batch_aug")
+        elif B:
             with torch.cuda.device(self.device):
                 native.check(native.lib().qatvit_image_batch(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
                                                              out.data_ptr(), native.stream_ptr()), "qatvit_image_batch")
@@ -92,10 +140,12 @@ class GpuImageLoader:
     """Iterates ``(images, labels)`` device batches of a uint8 data set that lives on the device; stands where a ``DataLoader`` over the
     transformed data set stood.  An epoch's indices go to the device once; drawing a batch is one gather of labels and one launch, with no host
     synchronisation, and every batch is a fresh tensor.  ``return_index=True`` yields ``(images, labels, index)``: ``index`` is the batch's slice of
-    the epoch plan on the device (int64), the row numbers a per-sample table such as ``TeacherLogitTable`` is read with."""
+    the epoch plan on the device (int64), the row numbers a per-sample table such as ``TeacherLogitTable`` is read with.  ``augment`` (a
+    ``RandomCropFlip``) crops and flips every drawn sample inside the same launch: an epoch's words are drawn right after its plan, from the same
+    ``generator``, and travel to the device with the indices in the one copy; the yielded tuples are the same."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
-                 return_index=False):
+                 return_index=False, augment=None):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -109,6 +159,12 @@ class GpuImageLoader:
         self.labels = labels.to(self.device, torch.int64).contiguous()
         self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator = int(batch_size), shuffle, sampler, drop_last, generator
         self.return_index = bool(return_index)
+        if augment is not None:
+            if not isinstance(augment, RandomCropFlip):
+                raise TypeError(f"augment must be a RandomCropFlip, got {type(augment).__name__}")
+            if augment.padding > self.data.shape[1] - 1:
+                raise ValueError(f"augment.padding {augment.padding} exceeds S - 1 = {self.data.shape[1] - 1}")
+        self.augment = augment
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -117,6 +173,9 @@ class GpuImageLoader:
     def __iter__(self):
         plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
         if not plan:
+            return
+        if self.augment is not None:
+            yield from self._iter_augmented(plan)
             return
         flat = torch.cat(plan)
         # from pinned memory the copy is asynchronous (the caching host allocator keeps the block until the copy has run)
@@ -129,6 +188,25 @@ class GpuImageLoader:
                 yield self.transform(self.data, idx), self.labels.index_select(0, idx), idx
             else:
                 yield self.transform(self.data, idx), self.labels.index_select(0, idx)
+
+    def _iter_augmented(self, plan):
+        a, flat = self.augment, torch.cat(plan)
+        n = flat.shape[0]
+        # one pinned block and one asynchronous copy for both: n int64 indices, then the n int32 words in the int64 elements behind them
+        host = torch.empty(n + (n + 1) // 2, dtype=torch.int64, pin_memory=True)
+        host[:n].copy_(flat)
+        host[n:].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
+        dev = host.to(self.device, non_blocking=True)
+        order, words = dev[:n], dev[n:].view(torch.int32)[:n]
+        o = 0
+        for b in plan:
+            idx, w = order[o:o + b.shape[0]], words[o:o + b.shape[0]]
+            o += b.shape[0]
+            x = self.transform(self.data, idx, aug=w, padding_mode=a.padding_mode, fill=a.fill, padding=a.padding)
+            if self.return_index:
+                yield x, self.labels.index_select(0, idx), idx
+            else:
+                yield x, self.labels.index_select(0, idx)
 
 
 def cifar10_arrays(root, train=True):

@@ -11,7 +11,13 @@
    shuffle=True, interleaved a, b, a, b, ... five times in this process, each window a host clock between two device synchronisations.
    (b) may exceed (a) by the kernel's time per batch plus the spread (max - min) of (a), and no more; the exit status says whether it held.
 
-usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE]"""
+With --augment it measures only the augmenting form of the kernel and writes profiles/augment_bench.txt: three arms with
+the method of 2., interleaved a, b, c, a, b, c, ... over the five repetitions - (a) qatvit_image_batch, (b) qatvit_image_batch_aug with the words of
+RandomCropFlip(4) and constant padding, (c) the same with reflect padding.  (b) and (c) may exceed (a) by (a)'s own spread over its repetitions
+plus 1 % of (a) - the extra bytes moved are at most the source bytes once more and 4 B per sample, against 154 MB written - and no more; the exit
+status says whether it held.
+
+usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment]"""
 import argparse
 import multiprocessing
 import os
@@ -90,6 +96,46 @@ def kernel_time(lines, data, tr):
     return ms
 
 
+def augment_arms(lines, data, tr):
+    import qat_vit_amd
+
+    g = torch.Generator(device="cuda").manual_seed(1)
+    idx = torch.randint(0, data.shape[0], (256,), device="cuda", generator=g)
+    words = qat_vit_amd.RandomCropFlip(4).draw(256, torch.Generator().manual_seed(1)).cuda()
+    outs = [torch.empty(256, 3, 224, 224, device="cuda") for _ in range(4)]
+    arms = {"a": ("qatvit_image_batch", {}),
+            "b": ("qatvit_image_batch_aug, constant padding, p = 4", {"aug": words, "padding_mode": "constant", "padding": 4}),
+            "c": ("qatvit_image_batch_aug, reflect padding, p = 4", {"aug": words, "padding_mode": "reflect", "padding": 4})}
+    for _, kw in arms.values():
+        for i in range(20):
+            tr(data, idx, out=outs[i % 4], **kw)
+    reps = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (_, kw) in arms.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            for i in range(200):
+                tr(data, idx, out=outs[i % 4], **kw)
+            ev[1].record()
+            torch.cuda.synchronize()
+            reps[k].append(ev[0].elapsed_time(ev[1]) / 200 * 1e3)
+    med = {k: statistics.median(v) for k, v in reps.items()}
+    spread = {k: max(v) - min(v) for k, v in reps.items()}
+    allowed = med["a"] + spread["a"] + 0.01 * med["a"]
+    lines.append("kernel with augmentation (batch 256, S = 32 -> 224, random index into 50,000 resident images, one word per sample), us per batch; "
+                 "HIP events around 200 launches after 20 warm-up launches per arm, five repetitions interleaved a, b, c, output rotating over 616 MB:")
+    for k, (name, _) in arms.items():
+        lines.append(f"  ({k}) {name + ':':<52} median {med[k]:.1f}  ({', '.join(f'{r:.1f}' for r in reps[k])}); spread {spread[k]:.1f}")
+    ok = True
+    for k in ("b", "c"):
+        held = med[k] <= allowed
+        ok = ok and held
+        lines.append(f"  ({k}) / (a) = {med[k] / med['a']:.3f}; ({k}) - (a) = {med[k] - med['a']:+.1f} us; allowed: (a) {med['a']:.1f} + spread of (a) "
+                     f"{spread['a']:.1f} + 1 % of (a) {0.01 * med['a']:.1f} = {allowed:.1f} us -> {'holds' if held else 'DOES NOT HOLD'}")
+    return ok
+
+
 def step_condition(lines, data, labels, tr, kernel_ms, steps, warmup):
     import qat_vit_amd
     from qat_vit_amd import functional as F
@@ -149,10 +195,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "input_pipeline_bench.txt"))
+    ap.add_argument("--out", default=None, help="profiles/input_pipeline_bench.txt, or profiles/augment_bench.txt with --augment")
+    ap.add_argument("--augment", action="store_true", help="only the three arms of the augmenting kernel")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
     lines = []
-    host_path(lines)                      # before the first CUDA call: the pool's processes are forked from a process without a GPU context
+    if not args.augment:
+        host_path(lines)                  # before the first CUDA call: the pool's processes are forked from a process without a GPU context
     if not torch.cuda.is_available():
         raise SystemExit("bench_input_pipeline.py needs an MI355X: there is no CPU form of the pipeline to time")
     import qat_vit_amd
@@ -162,8 +212,11 @@ def main():
     labels = torch.randint(0, 10, (50000,), device="cuda", generator=g)
     tr = qat_vit_amd.GpuResizeNormalize(32)
     lines.insert(0, f"input pipeline on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
-    kernel_ms = kernel_time(lines, data, tr)
-    ok = step_condition(lines, data, labels, tr, kernel_ms, args.steps, args.warmup)
+    if args.augment:
+        ok = augment_arms(lines, data, tr)
+    else:
+        kernel_ms = kernel_time(lines, data, tr)
+        ok = step_condition(lines, data, labels, tr, kernel_ms, args.steps, args.warmup)
     lines.append(CLOCK_NOTE)
     text = "\n".join(lines) + "\n"
     print(text, end="")
