@@ -98,6 +98,22 @@ int qatvit_kd_ce_loss_table(const float* student, const float* table, int64_t ta
                             int64_t classes, float kd_temp, float kd_alpha, float label_smoothing,
                             float* out3, float* dlogits, void* stream);
 
+/* Both losses with the mixed targets of mixup / cutmix: mix int32 [B][6], the record of qatvit_image_batch_mix (below), of which the loss
+ * reads word 0 (partner p; outside [0, B) means p = b) and word 5 (lam, fp32 bits).  teacher [B,C] and table [table_rows,C] are mutually
+ * exclusive (both given: an argument error); both NULL: CE only; a table needs index.  Per row b, with oml = 1 - lam formed in fp32:
+ *   hard target      t[c] = lam * [c == labels[b]] + oml * [c == labels[p]],  smoothed (1 - eps) * t[c] + eps / C;
+ *   teacher tensor:  the KD part is qatvit_kd_ce_loss's (the teacher saw the mixed images);
+ *   teacher table:   q = lam * softmax(table[index[b]] / T) + oml * softmax(table[index[p]] / T), KD = sum_c q (log q - log_softmax(s / T))
+ *                    with 0 log 0 = 0, gradient term alpha * T * (softmax(s / T) - q) / B.  This is the usual mixed soft label, NOT the
+ *                    teacher's output on the mixed image.
+ * The partner's label weight and table row take part only where lam != 1: a row with lam == 1 gives the bits of the two entries above, and
+ * an index[p] outside the table makes NaN only where lam != 1; index[b] outside the table makes NaN as in qatvit_kd_ce_loss_table.
+ * mix == NULL: qatvit_kd_ce_loss_table (table given) or qatvit_kd_ce_loss.  mix 4-byte aligned.  One single-block launch.
+ */
+int qatvit_kd_ce_loss_mix(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                          const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                          float label_smoothing, float* out3, float* dlogits, void* stream);
+
 /* ===========================================================================
  * Building blocks of the step, exported for kernel-level parity tests.
  * All matrices row-major; "bf16" = IEEE bfloat16 bit patterns (uint16).
@@ -519,6 +535,22 @@ int qatvit_optim_adamw_groups(const void* param_ptrs, const void* grad_ptrs, con
  *   the output layout are qatvit_image_batch's: the result EQUALS qatvit_image_batch's on the uint8 image A.  Every word is safe: in constant
  *   mode an offset that moves the whole window off the image gives an all-`fill` source; in reflect mode the clamp keeps every read inside
  *   the image (one reflection is exact for |oy|, |ox| <= S-1).  aug == NULL launches qatvit_image_batch's kernel: no augmentation.
+ *
+ * qatvit_image_batch_mix: the same launch with mixup / cutmix behind the per-sample transforms, where timm's Mixup and torchvision's
+ *   MixUp / CutMix have them.  mix int32 [B][6] on the device, contiguous, 4-byte aligned, one record per batch POSITION b:
+ *     word 0  partner: batch position p of the second image; a value outside [0, B) means p = b (never an out-of-range read)
+ *     word 1  w_self, fp32 bits            word 2  w_partner, fp32 bits
+ *     word 3  y0 | y1 << 16: output rows y0 .. y1-1 of the box, each clamped to [0, D]
+ *     word 4  x0 | x1 << 16: output columns x0 .. x1-1, clamped likewise; the box is empty if y1 <= y0 or x1 <= x0
+ *     word 5  lam, fp32 bits: the weight of the sample's own label in qatvit_kd_ce_loss_mix (the partner's gets 1 - lam); unused here
+ *   With X[b] = what qatvit_image_batch_aug writes for position b with word aug[b] (aug == NULL: what qatvit_image_batch writes), and the
+ *   partner taken with its own word aug[p] - X[p], never a mixed row:
+ *     out[b][c][y][x] = X[p][c][y][x]                                       inside the box,
+ *                     = fl(fl(w_self * X[b]) + fl(w_partner * X[p]))        elsewhere: fp32, three roundings, no fused multiply-add
+ *   (x * w_self + xp * w_partner as separate torch ops).  Mixup: an empty box, (w_self, w_partner) = (lam, 1 - lam).  Cutmix: a box, weights
+ *   (1, 0), lam = 1 - area / D^2 of the clamped box.  Identity: weights (1, 0), an empty box, lam = 1: the result is X[b].
+ *   The kernel keeps a second set of resampled planes in LDS: a shape whose request exceeds 64 KB (S and D both near 384) is refused with an
+ *   error string before any HIP call.  mix == NULL: qatvit_image_batch_aug.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -526,6 +558,9 @@ int qatvit_image_batch(const uint8_t* data, const int64_t* index, int32_t B, int
                        const float* table, float* out, void* stream);
 int qatvit_image_batch_aug(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                            const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, float* out, void* stream);
+int qatvit_image_batch_mix(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                           const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix, float* out,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

@@ -109,6 +109,23 @@ int qatvit_kd_ce_loss_table(const float* student, const float* table, int64_t ta
     return 0;
 }
 
+int qatvit_kd_ce_loss_mix(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                          const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                          float label_smoothing, float* out3, float* dlogits, void* stream) {
+    QV_CHECK_ARG(student && labels && out3 && dlogits, "qatvit_kd_ce_loss_mix: null pointer argument");
+    QV_CHECK_ARG(!(teacher && table), "qatvit_kd_ce_loss_mix: a teacher tensor and a teacher table are mutually exclusive");
+    QV_CHECK_ARG(!table || index, "qatvit_kd_ce_loss_mix: a teacher table needs an index");
+    QV_CHECK_ARG(batch >= 1 && classes >= 2 && classes <= 4096, "qatvit_kd_ce_loss_mix: bad shape B=%lld C=%lld", (long long)batch,
+                 (long long)classes);
+    QV_CHECK_ARG(!table || table_rows >= 1, "qatvit_kd_ce_loss_mix: table_rows %lld (at least 1)", (long long)table_rows);
+    QV_CHECK_ARG(kd_temp > 0.f, "qatvit_kd_ce_loss_mix: kd_temp must be > 0");
+    QV_CHECK_ARG(((uintptr_t)mix & 3) == 0, "qatvit_kd_ce_loss_mix: misaligned mix pointer");
+    launch_kd_ce_loss_mix(student, teacher, table, table_rows, index, labels, mix, batch, classes, kd_temp, kd_alpha, label_smoothing, out3, dlogits,
+                          (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_kd_ce_loss_mix");
+    return 0;
+}
+
 int qatvit_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                    int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, void* stream) {
     QV_CHECK_ARG(A_hi && B && C, "qatvit_gemm_nt: null pointer argument");
@@ -378,6 +395,24 @@ int qatvit_image_batch_aug(const uint8_t* data, const int64_t* index, int32_t B,
                  "qatvit_image_batch_aug: misaligned pointer");
     launch_image_batch_aug(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, out, (hipStream_t)stream);
     QV_CHECK_LAUNCH("qatvit_image_batch_aug");
+    return 0;
+}
+
+int qatvit_image_batch_mix(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                           const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix, float* out,
+                           void* stream) {
+    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch_mix: null pointer argument");
+    if (image_shape_ok("qatvit_image_batch_mix", S, D)) return 1;
+    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_mix: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
+    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_mix: batch %d of a data set of %d images needs an index", B, N);
+    QV_CHECK_ARG(padding_mode == 0 || padding_mode == 1, "qatvit_image_batch_mix: unknown padding_mode %d (0 = constant, 1 = reflect)", padding_mode);
+    QV_CHECK_ARG(fill >= 0 && fill <= 255, "qatvit_image_batch_mix: fill %d is outside 0 .. 255", fill);
+    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)aug & 3) == 0 &&
+                     ((uintptr_t)mix & 3) == 0,
+                 "qatvit_image_batch_mix: misaligned pointer");
+    // the shape's LDS request is checked here, before any HIP call
+    if (launch_image_batch_mix(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, out, (hipStream_t)stream)) return 1;
+    QV_CHECK_LAUNCH("qatvit_image_batch_mix");
     return 0;
 }
 

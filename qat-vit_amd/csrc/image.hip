@@ -86,17 +86,25 @@ __device__ inline int img_round_clip(int acc) {
 }
 
 // the kernel, once per form (image_kernel.h)
+#define QV_IMAGE_MIX 0
 #define QV_IMAGE_AUG 0
 #include "image_kernel.h"
 #undef QV_IMAGE_AUG
 #define QV_IMAGE_AUG 1
 #include "image_kernel.h"
+#undef QV_IMAGE_MIX
+#define QV_IMAGE_MIX 1
+#include "image_kernel.h"
 #undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
 
 int64_t image_lds_bytes(int S, int D) {
     const int mr = image_max_rows(S, D);
     return (int64_t)D * (1 + kImgTaps) * 4 + 768 * 4 + ((mr * S * 3 + 15) & ~15) + (int64_t)mr * 3 * D;
 }
+
+// the mix kernel keeps the partner's planes behind the sample's
+int64_t image_mix_lds_bytes(int S, int D) { return image_lds_bytes(S, D) + (int64_t)image_max_rows(S, D) * 3 * D; }
 
 int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table, float* out,
                        hipStream_t st) {
@@ -113,6 +121,22 @@ int launch_image_batch_aug(const uint8_t* data, const int64_t* index, int B, int
     auto kern = D == 224 ? k_image_batch_aug<224> : k_image_batch_aug<0>;
     hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)image_lds_bytes(S, D), st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out,
                        aug, padding_mode, fill);
+    return 0;
+}
+
+int launch_image_batch_mix(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                           const int32_t* aug, int padding_mode, int fill, const int32_t* mix, float* out, hipStream_t st) {
+    if (!mix) return launch_image_batch_aug(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, out, st);
+    const int64_t lds = image_mix_lds_bytes(S, D);
+    if (lds > kImgMixMaxLds) {
+        set_error("qatvit_image_batch_mix: source %d -> output %d needs %lld bytes of LDS for two plane sets, more than %d", S, D, (long long)lds,
+                  kImgMixMaxLds);
+        return 1;
+    }
+    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
+    auto kern = D == 224 ? k_image_batch_mix<224> : k_image_batch_mix<0>;
+    hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug, padding_mode,
+                       fill, mix);
     return 0;
 }
 

@@ -2,9 +2,18 @@
 // staged source rows are rows of the augmented image A (include/qatvit.h), fetched through the word aug[b].  Everything behind the staging is the
 // same text for both.  Text, not a shared __device__ function: inlined into two kernels, the common body changed the instruction schedule of
 // k_image_batch<0>, and the non-augmenting kernels are to stay the machine code they were (profiles/augment_bench.txt).  No include guard.
+// QV_IMAGE_AUG 1 with QV_IMAGE_MIX 1 gives k_image_batch_mix<DT>: the staging and the horizontal pass run once for the sample and, where the
+// workgroup's band needs it, once more for the partner of its mix record (include/qatvit.h) into a second plane set; the vertical pass then forms
+// both values of an element and blends or selects them.  QV_IMAGE_MIX must be defined (0 or 1) by the including file.
 // DT = the output size as a constant (its divisions become multiplications), or 0: taken from D_rt.
 template <int DT>
-#if QV_IMAGE_AUG
+#if QV_IMAGE_MIX
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_mix(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                 int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
+                                                                 const float* __restrict__ table, float* __restrict__ out,
+                                                                 const int32_t* __restrict__ aug, int reflect, int fill,
+                                                                 const int32_t* __restrict__ mix) {
+#elif QV_IMAGE_AUG
 __global__ __launch_bounds__(kImgThreads) void k_image_batch_aug(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
                                                                  int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
                                                                  const float* __restrict__ table, float* __restrict__ out,
@@ -21,10 +30,29 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     int32_t* s_coef = s_xmin + D;                        // [D][4]
     float* s_table = (float*)(s_coef + D * kImgTaps);    // [3][256]
     uint8_t* s_src = (uint8_t*)(s_table + 768);          // [max_rows][S][3]
+#if QV_IMAGE_MIX
+    uint8_t* s_planes = s_src + src_bytes;               // [2][max_rows][3][D]: the sample's planes, then its partner's
+    const int plane_bytes = max_rows * 3 * D;
+#else
     uint8_t* s_tmp = s_src + src_bytes;                  // [max_rows][3][D]
+#endif
 
     const int tid = threadIdx.x, b = blockIdx.y;
     const int y0 = blockIdx.x * kImgBand, y1 = min(y0 + kImgBand, D);
+#if QV_IMAGE_MIX
+    // the record is the workgroup's: six scalar loads.  A partner outside the batch is the sample itself; the box is clamped to the output.
+    const int32_t* rec = mix + b * 6;
+    const int p = (unsigned)rec[0] < gridDim.y ? rec[0] : b;
+    const float w_self = __int_as_float(rec[1]), w_partner = __int_as_float(rec[2]);
+    const int by0 = min(rec[3] & 0xffff, D), by1 = min((rec[3] >> 16) & 0xffff, D);
+    const int bx0 = min(rec[4] & 0xffff, D), bx1 = min((rec[4] >> 16) & 0xffff, D);
+    const bool box = by1 > by0 && bx1 > bx0;
+    // one plane set serves both operands unless this band takes something from another position
+    const bool partner = w_partner != 0.0f || (box && by0 < y1 && by1 > y0);
+    const int sides = partner && p != b ? 2 : 1;
+    // nothing of the partner and the sample's weight 1: fl(1 * v) + fl(0 * v) is v, and the band stores what the aug kernel stores
+    const bool as_is = !partner && w_self == 1.0f;
+#endif
     int64_t img = index ? index[b] : b;
     img = img < 0 ? 0 : (img >= N ? N - 1 : img);        // the range is the caller's contract; a bad index must still not read outside data
 
@@ -37,10 +65,21 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     for (int i = tid; i < D; i += kImgThreads) s_xmin[i] = coeffs[i];
     for (int i = tid; i < D * kImgTaps; i += kImgThreads) s_coef[i] = coeffs[2 * D + i];
     for (int i = tid; i < 768; i += kImgThreads) s_table[i] = table[i];
+#if QV_IMAGE_MIX
+    for (int side = 0; side < sides; ++side) {
+    uint8_t* s_tmp = s_planes + side * plane_bytes;
+    if (side) {
+        __syncthreads();                                 // the sample's horizontal pass has read s_src
+        img = index ? index[p] : p;
+        img = img < 0 ? 0 : (img >= N ? N - 1 : img);
+    }
+    const int w = aug ? aug[side ? p : b] : 0;           // no words: the zero word, which is the plain image
+#elif QV_IMAGE_AUG
+    const int w = aug[b];
+#endif
 #if QV_IMAGE_AUG
     // one item = one pixel of the rows r0 .. r1-1 of A.  The word is the workgroup's (blockIdx.y): one scalar load.  Both coordinates are clamped
     // after the reflection, so the three byte loads stay inside the image whatever the word holds; in constant mode their result is replaced.
-    const int w = aug[b];
     const int oy = (int)(int8_t)(w & 255), ox = (int)(int8_t)((w >> 8) & 255), flip = (w >> 16) & 1;
     const uint8_t* image = data + img * S * (int64_t)row_bytes;
     for (int i = tid; i < nrows * S; i += kImgThreads) {
@@ -91,6 +130,12 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
         // result for zero, which on the MI355X it is not (bytes 2 and 3 of the dword came out wrong)
         ((uint32_t*)s_tmp)[rc * D4 + x4] = __builtin_amdgcn_perm((uint32_t)(px[2] | px[3] << 16), (uint32_t)(px[0] | px[1] << 16), 0x06040200u);
     }
+#if QV_IMAGE_MIX
+    }
+    const int D4 = D / 4;
+    const uint8_t* s_tmp = s_planes;
+    const int partner4 = (sides - 1) * (plane_bytes / 4);
+#endif
     __syncthreads();
 
     // vertical pass + value table + store
@@ -114,6 +159,34 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
             acc += __mul24((int)((t3 >> (8 * j)) & 255), k.w);
             v[j] = tab[img_round_clip(acc)];
         }
+#if QV_IMAGE_MIX
+        // the partner's value of the same element (the sample's own where one plane set serves both), then
+        // out = inside the box ? partner : fl(fl(w_self * own) + fl(w_partner * partner)), the products and the sum rounded one by one
+        if (!as_is) {
+            float u[4] = {v[0], v[1], v[2], v[3]};
+            if (sides == 2) {
+                const uint32_t* pp = plane + partner4;
+                const uint32_t p0 = pp[max(0, min(rel, last)) * 3 * D4], p1 = pp[max(0, min(rel + 1, last)) * 3 * D4];
+                const uint32_t p2 = pp[max(0, min(rel + 2, last)) * 3 * D4], p3 = pp[max(0, min(rel + 3, last)) * 3 * D4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int acc = 1 << (kImgBits - 1);
+                    acc += __mul24((int)((p0 >> (8 * j)) & 255), k.x);
+                    acc += __mul24((int)((p1 >> (8 * j)) & 255), k.y);
+                    acc += __mul24((int)((p2 >> (8 * j)) & 255), k.z);
+                    acc += __mul24((int)((p3 >> (8 * j)) & 255), k.w);
+                    u[j] = tab[img_round_clip(acc)];
+                }
+            }
+            const bool row_in = box && y >= by0 && y < by1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = x4 * 4 + j;
+                const float a = w_self * v[j], c2 = w_partner * u[j];
+                v[j] = row_in && x >= bx0 && x < bx1 ? u[j] : a + c2;
+            }
+        }
+#endif
         *(float4*)(obase + (int64_t)c * D * D + (int64_t)e * 4) = make_float4(v[0], v[1], v[2], v[3]);
     }
 }

@@ -19,6 +19,10 @@ int launch_kd_ce_loss(const float* student, const float* teacher, const int64_t*
                       float kd_alpha, float label_smoothing, float* out3, float* dlogits, hipStream_t st);
 int launch_kd_ce_loss_table(const float* student, const float* table, int64_t table_rows, const int64_t* index, const int64_t* labels, int64_t batch,
                             int64_t classes, float kd_temp, float kd_alpha, float label_smoothing, float* out3, float* dlogits, hipStream_t st);
+// the same two with mixed targets (mix int32 [B][6], include/qatvit.h): teacher [B, C], or table + index, or neither; mix == nullptr: the launchers above
+int launch_kd_ce_loss_mix(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                          const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                          float label_smoothing, float* out3, float* dlogits, hipStream_t st);
 
 // ---- fq.hip (engine pieces)
 int launch_minmax(const float* x, int64_t channels, int64_t inner, int per_channel, uint32_t* ws, int nslots, hipStream_t st);
@@ -326,6 +330,12 @@ int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, 
 // launch_image_batch.  padding_mode 0 = constant (fill), 1 = reflect
 int launch_image_batch_aug(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
                            const int32_t* aug, int padding_mode, int fill, float* out, hipStream_t st);
+// the same with a partner position, two blend weights and a box per batch position (mix int32 [B][6]; include/qatvit.h); mix == nullptr:
+// launch_image_batch_aug.  Keeps two plane sets in LDS: nonzero + set_error, before any launch, where image_mix_lds_bytes exceeds kImgMixMaxLds
+constexpr int kImgMixMaxLds = 64 * 1024;
+int64_t image_mix_lds_bytes(int S, int D);
+int launch_image_batch_mix(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                           const int32_t* aug, int padding_mode, int fill, const int32_t* mix, float* out, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

@@ -1,9 +1,11 @@
-"""Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug).
+"""Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug /
+qatvit_image_batch_mix).
 
 Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
 ``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
 writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced, equal to it element for element.
 ``RandomCropFlip`` adds ``RandomCrop(S, padding=p)`` + ``RandomHorizontalFlip()`` in front of the resize, inside the same launch (section 7l).
+``MixupCutmix`` adds mixup / cutmix behind them, still inside that launch (section 7m); ``functional.kd_ce_loss_mix`` takes the same records.
 There is no CPU path: CPU tensors raise."""
 import os
 import pickle
@@ -69,11 +71,83 @@ class RandomCropFlip:
         return ((off[:, 0] & 255) | (off[:, 1] & 255) << 8 | flip.to(torch.int64) << 16).to(torch.int32)
 
 
+MIX_WORDS = 6
+
+
+class MixupCutmix:
+    """Mixup (arXiv:1710.09412) and cutmix (arXiv:1905.04899) as one six-word int32 record per batch position (include/qatvit.h): partner
+    position, ``w_self`` and ``w_partner`` (fp32 bits), the box rows ``y0 | y1 << 16`` and columns ``x0 | x1 << 16``, and ``lam`` (fp32 bits), the
+    weight of the sample's own label.  The arguments have timm's ``Mixup`` meaning.  Built and drawn on the host; needs no GPU."""
+
+    MODES = ("batch", "elem")
+
+    def __init__(self, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch"):
+        for name, v in (("mixup_alpha", mixup_alpha), ("cutmix_alpha", cutmix_alpha)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf"):
+                raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+        for name, v in (("prob", prob), ("switch_prob", switch_prob)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+                raise ValueError(f"{name} must be a probability 0 .. 1, got {v!r}")
+        if mode not in self.MODES:
+            raise ValueError(f"mode must be one of {list(self.MODES)}, got {mode!r}")
+        self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob, self.mode = float(mixup_alpha), float(cutmix_alpha), float(prob), \
+            float(switch_prob), mode
+
+    def _draw_one(self, D, generator):
+        """(w_self, w_partner, y0, y1, x0, x1, lam) of one decision; the weights and lam are np.float32."""
+        u = torch.rand(2, dtype=torch.float64, generator=generator)
+        mixing = bool(u[0] < self.prob) and (self.mixup_alpha > 0 or self.cutmix_alpha > 0)
+        cut = bool(u[1] < self.switch_prob) if self.mixup_alpha > 0 and self.cutmix_alpha > 0 else self.cutmix_alpha > 0
+        alpha = (self.cutmix_alpha if cut else self.mixup_alpha) if mixing else 1.0
+        g = torch._standard_gamma(torch.full((2,), alpha, dtype=torch.float64), generator=generator)
+        lam = float(g[0] / (g[0] + g[1]))
+        one, zero = np.float32(1), np.float32(0)
+        if not mixing or not 0 <= lam <= 1:      # both gamma draws underflowed to 0: no mix
+            return one, zero, 0, 0, 0, 0, one
+        if not cut:
+            lam = np.float32(lam)
+            return lam, one - lam, 0, 0, 0, 0, lam
+        cy, cx = (int(v) for v in torch.randint(0, D, (2,), generator=generator))
+        h = int(D * float(np.sqrt(1.0 - lam)))
+        y0, y1 = min(max(cy - h // 2, 0), D), min(max(cy + h // 2, 0), D)
+        x0, x1 = min(max(cx - h // 2, 0), D), min(max(cx + h // 2, 0), D)
+        return one, zero, y0, y1, x0, x1, np.float32(1.0 - (y1 - y0) * (x1 - x0) / float(D * D))
+
+    def draw(self, batch_sizes, out_size, generator=None):
+        """int32 CPU tensor ``[sum(batch_sizes), 6]``, the records of the batches one after the other.  The rule (timm's, restated: timm is not a
+        dependency).  The partner of position b in a batch of m is ``m - 1 - b`` (the batch flipped).  One decision per batch, or per sample in
+        ``mode="elem"``, all from `generator`, in this order:
+        ``u = torch.rand(2, dtype=float64)``: ``u[0] < prob`` means mix; ``u[1] < switch_prob`` means cutmix when both alphas are positive,
+        otherwise whichever alpha is positive is used;
+        ``X, Y = torch._standard_gamma(torch.full((2,), alpha, dtype=float64))``, ``lam = X / (X + Y)`` (a Beta(alpha, alpha) draw), with the
+        chosen alpha, or 1 when not mixing (so ``u`` and the gamma pair are always drawn);
+        mixup: an empty box, ``w_self = fp32(lam)``, ``w_partner = fp32(1) - w_self``, the record's lam ``= w_self``;
+        cutmix: ``cy, cx = torch.randint(0, D, (2,))``, ``h = int(D * sqrt(1 - lam))``, ``y0 = clip(cy - h // 2, 0, D)``,
+        ``y1 = clip(cy + h // 2, 0, D)``, the columns likewise from ``cx``; weights (1, 0); lam ``= fp32(1 - (y1 - y0) * (x1 - x0) / D^2)``;
+        not mixing: the identity record: weights (1, 0), an empty box, lam 1."""
+        D = int(out_size)
+        if not 1 <= D <= 0xffff:
+            raise ValueError(f"out_size must be 1 .. 65535, got {out_size!r}")
+        sizes = [int(m) for m in batch_sizes]
+        rec = np.zeros((sum(sizes), MIX_WORDS), dtype=np.int32)
+        bits = lambda v: np.float32(v).view(np.int32)
+        o = 0
+        for m in sizes:
+            one = None if self.mode == "elem" else self._draw_one(D, generator)
+            for b in range(m):
+                ws, wp, y0, y1, x0, x1, lam = one if one is not None else self._draw_one(D, generator)
+                rec[o + b] = (m - 1 - b, bits(ws), bits(wp), y0 | y1 << 16, x0 | x1 << 16, bits(lam))
+            o += m
+        return torch.from_numpy(rec)
+
+
 class GpuResizeNormalize:
     """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch.
     With ``aug`` (int32 ``[B]`` on the device, the words of ``RandomCropFlip.draw``; word b belongs to batch position b) the source of sample b is
     cropped at its offset out of the image extended by ``padding_mode`` / ``fill`` and flipped first, in the same launch.  ``padding`` states the
-    bound of the offsets in ``aug`` where the caller knows it: reflect mode is exact for offsets up to ``S - 1`` and a larger bound is refused."""
+    bound of the offsets in ``aug`` where the caller knows it: reflect mode is exact for offsets up to ``S - 1`` and a larger bound is refused.
+    With ``mix`` (int32 ``[B, 6]`` on the device, the records of ``MixupCutmix.draw``) sample b is blended with, or takes a box from, what this
+    call produces for its partner position, in the same launch."""
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
         self.src_size, self.out_size = int(src_size), int(out_size)
@@ -86,7 +160,7 @@ class GpuResizeNormalize:
         self.coeffs = torch.cat([t.flatten() for t in resize_tables(self.src_size, self.out_size)]).to(self.device)
         self.table = value_table(mean, std).to(self.device)
 
-    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None):
+    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None):
         S, D = self.src_size, self.out_size
         if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
             raise RuntimeError("GpuResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
@@ -114,6 +188,16 @@ class GpuResizeNormalize:
                 raise ValueError(f"aug must be a contiguous int32 [{B}] tensor on {self.device}")
             if mode == PADDING_MODES["reflect"] and padding is not None and padding > S - 1:
                 raise ValueError(f"reflect padding reflects once: offsets up to {padding} exceed S - 1 = {S - 1}")
+        if mix is not None:
+            if not isinstance(mix, torch.Tensor) or mix.dtype != torch.int32 or tuple(mix.shape) != (B, MIX_WORDS) or not mix.is_contiguous() \
+                    or mix.device != self.device:
+                raise ValueError(f"mix must be a contiguous int32 [{B}, {MIX_WORDS}] tensor on {self.device}")
+            if B:
+                with torch.cuda.device(self.device):
+                    native.check(native.lib().qatvit_image_batch_mix(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
+                                                                     None if aug is None else aug.data_ptr(), mode, fill, mix.data_ptr(),
+                                                                     out.data_ptr(), native.stream_ptr()), "qatvit_image_batch_mix")
+            return out
         if B and aug is not None:
             with torch.cuda.device(self.device):
                 native.check(native.lib().qatvit_image_batch_aug(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
@@ -142,10 +226,12 @@ class GpuImageLoader:
     synchronisation, and every batch is a fresh tensor.  ``return_index=True`` yields ``(images, labels, index)``: ``index`` is the batch's slice of
     the epoch plan on the device (int64), the row numbers a per-sample table such as ``TeacherLogitTable`` is read with.  ``augment`` (a
     ``RandomCropFlip``) crops and flips every drawn sample inside the same launch: an epoch's words are drawn right after its plan, from the same
-    ``generator``, and travel to the device with the indices in the one copy; the yielded tuples are the same."""
+    ``generator``, and travel to the device with the indices in the one copy; the yielded tuples are the same.  ``mix`` (a ``MixupCutmix``) mixes
+    every batch inside the same launch: an epoch's records are drawn after the plan and after the words, travel in the same copy, and the batch's
+    device slice (int32 ``[B, 6]``, what ``kd_ce_loss_mix`` / ``TeacherLogitTable.loss(mix=...)`` take) is the last element of every tuple."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
-                 return_index=False, augment=None):
+                 return_index=False, augment=None, mix=None):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -165,6 +251,9 @@ class GpuImageLoader:
             if augment.padding > self.data.shape[1] - 1:
                 raise ValueError(f"augment.padding {augment.padding} exceeds S - 1 = {self.data.shape[1] - 1}")
         self.augment = augment
+        if mix is not None and not isinstance(mix, MixupCutmix):
+            raise TypeError(f"mix must be a MixupCutmix, got {type(mix).__name__}")
+        self.mix = mix
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -173,6 +262,9 @@ class GpuImageLoader:
     def __iter__(self):
         plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
         if not plan:
+            return
+        if self.mix is not None:
+            yield from self._iter_mixed(plan)
             return
         if self.augment is not None:
             yield from self._iter_augmented(plan)
@@ -207,6 +299,34 @@ class GpuImageLoader:
                 yield x, self.labels.index_select(0, idx), idx
             else:
                 yield x, self.labels.index_select(0, idx)
+
+
+    def _iter_mixed(self, plan):
+        a, flat = self.augment, torch.cat(plan)
+        n = flat.shape[0]
+        nw = (n + 1) // 2 if a is not None else 0
+        # one pinned block and one asynchronous copy: n int64 indices, the n int32 words (with augment), then the n six-word int32 records
+        host = torch.empty(n + nw + 3 * n, dtype=torch.int64, pin_memory=True)
+        host[:n].copy_(flat)
+        if a is not None:
+            host[n:n + nw].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
+        host[n + nw:].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], self.transform.out_size, self.generator))
+        dev = host.to(self.device, non_blocking=True)
+        order, records = dev[:n], dev[n + nw:].view(torch.int32).view(n, MIX_WORDS)
+        words = dev[n:n + nw].view(torch.int32)[:n] if a is not None else None
+        o = 0
+        for b in plan:
+            m = b.shape[0]
+            idx, r = order[o:o + m], records[o:o + m]
+            if a is not None:
+                x = self.transform(self.data, idx, aug=words[o:o + m], padding_mode=a.padding_mode, fill=a.fill, padding=a.padding, mix=r)
+            else:
+                x = self.transform(self.data, idx, mix=r)
+            o += m
+            if self.return_index:
+                yield x, self.labels.index_select(0, idx), idx, r
+            else:
+                yield x, self.labels.index_select(0, idx), r
 
 
 def cifar10_arrays(root, train=True):

@@ -161,10 +161,14 @@ class TeacherLogitTable:
         self.check_fresh()
         return self.logits.index_select(0, index)
 
-    def loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
-        """``F.kd_ce_loss(student_logits, teacher(images of index), labels, ...)`` without the teacher forward: (loss, [loss, ce, kd*T^2])."""
+    def loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None):
+        """``F.kd_ce_loss(student_logits, teacher(images of index), labels, ...)`` without the teacher forward: (loss, [loss, ce, kd*T^2]).
+        ``mix`` (the int32 ``[B, 6]`` records a mixing loader yields) mixes the labels and the teacher's rows of each sample and its partner
+        (``F.kd_ce_loss_table_mix``)."""
         self._need_device("loss")
         self.check_fresh()
+        if mix is not None:
+            return F.kd_ce_loss_table_mix(student_logits, self.logits, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
         return F.kd_ce_loss_table(student_logits, self.logits, index, labels, kd_temp, kd_alpha, label_smoothing)
 
     def save(self, path) -> None:

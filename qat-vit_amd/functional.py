@@ -195,3 +195,66 @@ def kd_ce_loss_table(student, table, index, labels, kd_temp=4.0, kd_alpha=0.5, l
     ``table`` is fp32 ``[rows, C]`` (per-sample teacher logits, distill.TeacherLogitTable), ``index`` int64 ``[B]``.  An index outside the table
     makes the loss and that row of the gradient NaN; it is not an error on the host (nothing here synchronises)."""
     return _KDCELossTableFn.apply(student, table, index, labels, kd_temp, kd_alpha, label_smoothing)
+
+
+class _KDCELossMixFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing):
+        who = "kd_ce_loss_mix" if table is None else "kd_ce_loss_table_mix"
+        _need_cuda(student, who)
+        student = student.contiguous()
+        B, C = student.shape
+        dev = student.device
+        tptr = bptr = iptr = None
+        rows = 0
+        if teacher is not None:
+            teacher = teacher.contiguous().float()
+            if teacher.shape != (B, C) or teacher.device != dev:
+                raise RuntimeError(f"{who}: the teacher must be a [{B}, {C}] tensor on {dev}, got {tuple(teacher.shape)} on {teacher.device}")
+            tptr = teacher.data_ptr()
+        if table is not None:
+            _need_cuda(table, who)
+            if table.dim() != 2 or table.shape[1] != C or table.shape[0] < 1 or not table.is_contiguous() or table.device != dev:
+                raise RuntimeError(f"{who}: the table must be a contiguous [rows, {C}] tensor on {dev}, got {tuple(table.shape)} on {table.device}")
+            index = index.contiguous()
+            if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev:
+                raise RuntimeError(f"{who}: index must be an int64 [{B}] tensor on {dev}")
+            bptr, iptr, rows = table.data_ptr(), index.data_ptr(), table.shape[0]
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64 or labels.shape != (B,) or labels.device != dev:
+            raise RuntimeError(f"{who}: labels must be an int64 [{B}] tensor on {dev}")
+        mptr = None
+        if mix is not None:
+            if mix.dtype != torch.int32 or tuple(mix.shape) != (B, 6) or not mix.is_contiguous() or mix.device != dev:
+                raise RuntimeError(f"{who}: mix must be a contiguous int32 [{B}, 6] tensor on {dev}")
+            mptr = mix.data_ptr()
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        dlogits = torch.empty_like(student)
+        native.check(
+            native.lib().qatvit_kd_ce_loss_mix(student.data_ptr(), tptr, bptr, rows, iptr, labels.data_ptr(), mptr, B, C, float(kd_temp),
+                                               float(kd_alpha), float(label_smoothing), out3.data_ptr(), dlogits.data_ptr(), native.stream_ptr()),
+            "qatvit_kd_ce_loss_mix",
+        )
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(out3)
+        return out3[0], out3
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * dloss,) + (None,) * 8
+
+
+def kd_ce_loss_mix(student, teacher, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+    """``kd_ce_loss`` on a mixed batch: returns (loss, [loss, ce, kd*T^2]).  ``mix`` is the int32 ``[B, 6]`` record tensor the images were mixed
+    with (data.MixupCutmix): row b's hard target is ``lam`` on ``labels[b]`` and ``1 - lam`` on the partner's label.  ``teacher`` (``[B, C]`` or
+    None) is the teacher's output on the mixed images, so the KD part is ``kd_ce_loss``'s.  ``mix=None`` is ``kd_ce_loss``."""
+    return _KDCELossMixFn.apply(student, teacher, None, None, labels, mix, kd_temp, kd_alpha, label_smoothing)
+
+
+def kd_ce_loss_table_mix(student, table, index, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+    """``kd_ce_loss_table`` on a mixed batch: the hard target as in ``kd_ce_loss_mix``, the KD target
+    ``lam * softmax(table[index[b]] / T) + (1 - lam) * softmax(table[index[p]] / T)`` - the usual mixed soft label, not the teacher's output on
+    the mixed image.  An index outside the table, of the row or (where ``lam != 1``) of its partner, makes the loss and that row of the gradient
+    NaN.  ``mix=None`` is ``kd_ce_loss_table``."""
+    return _KDCELossMixFn.apply(student, None, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing)

@@ -28,6 +28,8 @@ SIGNATURES = {
     "qatvit_ln_backward": (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_void_p]),
     "qatvit_kd_ce_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "qatvit_kd_ce_loss_table": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "qatvit_kd_ce_loss_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float,
+                                      c_void_p, c_void_p, c_void_p]),
     "qatvit_optim_grad_norm": (c_int, [c_void_p] * 4 + [c_int32, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "qatvit_optim_adamw": (c_int, [c_void_p] * 7 + [c_int32, c_int64] + [c_double] * 5 + [c_int64, c_void_p, c_void_p]),
     "qatvit_optim_adamw_groups": (c_int, [c_void_p] * 8 + [c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
@@ -94,6 +96,7 @@ SIGNATURES = {
     "qatvit_image_table": (c_int, [c_void_p] * 3),
     "qatvit_image_batch": (c_int, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 4),
     "qatvit_image_batch_aug": (c_int, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 3 + [c_int32, c_int32, c_void_p, c_void_p]),
+    "qatvit_image_batch_mix": (c_int, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 3 + [c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "qatvit_eval_accumulate": (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "qatvit_profile_start": (c_int, [c_void_p, c_int32, c_int32]),
     "qatvit_profile_stop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

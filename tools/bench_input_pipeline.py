@@ -17,7 +17,14 @@ RandomCropFlip(4) and constant padding, (c) the same with reflect padding.  (b) 
 plus 1 % of (a) - the extra bytes moved are at most the source bytes once more and 4 B per sample, against 154 MB written - and no more; the exit
 status says whether it held.
 
-usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment]"""
+With --mix it measures only the mixing form of the kernel and writes profiles/mix_bench.txt: five arms with the method of
+2., interleaved over the five repetitions - (a) qatvit_image_batch_aug alone, (b) what a user composes for mixup without the entry: (a) +
+index_select of the partners + two mul + add, (c) qatvit_image_batch_mix with mixup records, every partner another position, (d) the same with
+cutmix records whose box is about half the area, (e) the same with identity records.  The condition: (c) and (d) no slower than (b)'s median; the
+exit status says whether it held.  (e) against (a) is reported.  --note FILE appends that file's text (the machine-code comparison, the register
+report) to the output.
+
+usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix [--note FILE]]"""
 import argparse
 import multiprocessing
 import os
@@ -136,6 +143,77 @@ def augment_arms(lines, data, tr):
     return ok
 
 
+def mix_arms(lines, data, tr):
+    import qat_vit_amd
+
+    B, D = 256, 224
+    g = torch.Generator(device="cuda").manual_seed(1)
+    idx = torch.randint(0, data.shape[0], (B,), device="cuda", generator=g)
+    words = qat_vit_amd.RandomCropFlip(4).draw(B, torch.Generator().manual_seed(1)).cuda()
+    kw = {"aug": words, "padding_mode": "constant", "padding": 4}
+    bits = lambda v: int(np.float32(v).view(np.int32))   # noqa: E731
+    lam = np.random.default_rng(1).beta(0.8, 0.8, B).astype(np.float32)
+    partner = [B - 1 - b for b in range(B)]              # the flip: every partner is another position
+    mixup = torch.tensor([[p, bits(l), bits(np.float32(1) - l), 0, 0, bits(l)] for p, l in zip(partner, lam)], dtype=torch.int32).cuda()
+    y0, y1, x0, x1 = 33, 191, 33, 192                    # 158 x 159 of 224 x 224: 0.5007 of the area, edges off the band and float4 grids
+    area = (y1 - y0) * (x1 - x0) / float(D * D)
+    cutmix = torch.tensor([[p, bits(1), 0, y0 | y1 << 16, x0 | x1 << 16, bits(1 - area)] for p in partner], dtype=torch.int32).cuda()
+    ident = torch.tensor([[p, bits(1), 0, 0, 0, bits(1)] for p in partner], dtype=torch.int32).cuda()
+    part = torch.tensor(partner, device="cuda")
+    ws, wp = torch.from_numpy(lam).cuda().view(B, 1, 1, 1), torch.from_numpy(np.float32(1) - lam).cuda().view(B, 1, 1, 1)
+    outs = [torch.empty(B, 3, D, D, device="cuda") for _ in range(4)]
+
+    def composed(i):
+        x = tr(data, idx, out=outs[i % 4], **kw)
+        return torch.add(x.mul(ws), x.index_select(0, part).mul(wp))
+
+    arms = {"a": ("qatvit_image_batch_aug alone", lambda i: tr(data, idx, out=outs[i % 4], **kw)),
+            "b": ("(a) + index_select + two mul + add (mixup today)", composed),
+            "c": ("qatvit_image_batch_mix, mixup records", lambda i: tr(data, idx, out=outs[i % 4], mix=mixup, **kw)),
+            "d": (f"qatvit_image_batch_mix, cutmix, box {area:.3f} of the area", lambda i: tr(data, idx, out=outs[i % 4], mix=cutmix, **kw)),
+            "e": ("qatvit_image_batch_mix, identity records", lambda i: tr(data, idx, out=outs[i % 4], mix=ident, **kw))}
+    assert torch.equal(arms["c"][1](0), composed(1)) and torch.equal(arms["e"][1](2), arms["a"][1](3))
+    for _, run in arms.values():
+        for i in range(20):
+            run(i)
+    reps = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (_, run) in arms.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            for i in range(200):
+                run(i)
+            ev[1].record()
+            torch.cuda.synchronize()
+            reps[k].append(ev[0].elapsed_time(ev[1]) / 200 * 1e3)
+    med = {k: statistics.median(v) for k, v in reps.items()}
+    spread = {k: max(v) - min(v) for k, v in reps.items()}
+    lines.append("kernel with mixup / cutmix (batch 256, S = 32 -> 224, random index into 50,000 resident images, words of RandomCropFlip(4), constant "
+                 "padding), us per batch; HIP events around 200 launches after 20 warm-up launches per arm, five repetitions interleaved a .. e, output "
+                 "rotating over 616 MB:")
+    for k, (name, _) in arms.items():
+        lines.append(f"  ({k}) {name + ':':<58} median {med[k]:.1f}  ({', '.join(f'{r:.1f}' for r in reps[k])}); spread {spread[k]:.1f}")
+    ok = True
+    for k in ("c", "d"):
+        held = med[k] <= med["b"]
+        ok = ok and held
+        lines.append(f"  ({k}) / (b) = {med[k] / med['b']:.3f}; ({k}) / (a) = {med[k] / med['a']:.3f}; the condition ({k}) <= (b)'s median {med['b']:.1f} us -> "
+                     f"{'holds' if held else 'DOES NOT HOLD'}")
+    allowed = med["a"] + spread["a"] + 0.01 * med["a"]
+    lines.append(f"  reported, not required: (e) / (a) = {med['e'] / med['a']:.3f}; (e) - (a) = {med['e'] - med['a']:+.1f} us; (a) + spread of (a) "
+                 f"{spread['a']:.1f} + 1 % of (a) = {allowed:.1f} us -> {'within' if med['e'] <= allowed else 'NOT within'}")
+    lines.append(f"  LDS per workgroup: aug kernel {lds_bytes(32, D)[0]} B, mix kernel {lds_bytes(32, D)[1]} B")
+    return ok
+
+
+def lds_bytes(S, D):
+    """(aug kernel, mix kernel) dynamic LDS of one workgroup, as csrc/image.hip sizes them: tables, source rows, one or two plane sets."""
+    mr = (16 * S + D - 1) // D + 5
+    one = D * 5 * 4 + 768 * 4 + ((mr * S * 3 + 15) & ~15) + mr * 3 * D
+    return one, one + mr * 3 * D
+
+
 def step_condition(lines, data, labels, tr, kernel_ms, steps, warmup):
     import qat_vit_amd
     from qat_vit_amd import functional as F
@@ -197,11 +275,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None, help="profiles/input_pipeline_bench.txt, or profiles/augment_bench.txt with --augment")
     ap.add_argument("--augment", action="store_true", help="only the three arms of the augmenting kernel")
+    ap.add_argument("--mix", action="store_true", help="only the five arms of the mixing kernel")
+    ap.add_argument("--note", default=None, help="with --mix: a text file appended to the output")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
+        args.out = os.path.join(ROOT, "profiles", "mix_bench.txt" if args.mix else "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
     lines = []
-    if not args.augment:
+    if not args.augment and not args.mix:
         host_path(lines)                  # before the first CUDA call: the pool's processes are forked from a process without a GPU context
     if not torch.cuda.is_available():
         raise SystemExit("bench_input_pipeline.py needs an MI355X: there is no CPU form of the pipeline to time")
@@ -212,12 +292,17 @@ def main():
     labels = torch.randint(0, 10, (50000,), device="cuda", generator=g)
     tr = qat_vit_amd.GpuResizeNormalize(32)
     lines.insert(0, f"input pipeline on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
-    if args.augment:
+    if args.mix:
+        ok = mix_arms(lines, data, tr)
+    elif args.augment:
         ok = augment_arms(lines, data, tr)
     else:
         kernel_ms = kernel_time(lines, data, tr)
         ok = step_condition(lines, data, labels, tr, kernel_ms, args.steps, args.warmup)
     lines.append(CLOCK_NOTE)
+    if args.mix and args.note:
+        lines.append("")
+        lines.append(open(args.note).read().rstrip("\n"))
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
