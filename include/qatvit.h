@@ -134,7 +134,7 @@ int qatvit_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, 
 /* The same product with fp16 bit patterns in all three matrices: A = (A16_hi + A16_lo), an fp16 (hi, lo) pair of a float tensor pre-scaled
  * by a power of two that the caller folds into *s1 (22 significant bits, 2^-23 relative, against 2^-17 for a bf16 pair); B16 = the weight
  * integers as fp16 (exact).  v_mfma_f32_16x16x32_f16, fp32 accumulate.  Used for the two forward GEMMs with a float operand (attn.proj, mlp.fc2),
- * whose outputs are fake-quantized next.  N % 384 == 0, K % 32 == 0. */
+ * whose outputs are fake-quantized next.  N % 384 == 0, K % 64 == 0. */
 int qatvit_gemm_nt_f16(const void* A16_hi, const void* A16_lo, const void* B16, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                        int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, void* stream);
 

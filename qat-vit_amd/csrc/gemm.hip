@@ -1193,6 +1193,11 @@ int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N
     // Same box, same step: dgrad + LayerNorm backward 108.8 -> 103.8 us, + GELU backward 135.4 -> 131.9, plain 29.8 -> 28.5 (three stages of BK = 32; a fourth changed
     // nothing: 105.1 vs 104.5).  The k-values enter the accumulators in the same order: the same bits.
     const size_t lds = post ? (size_t)160 * 1024 : (size_t)2 * (208 + 384) * 128;   // 148 KiB ring; the fused epilogues ask for 160
+    if (K % 64 != 0) {   // an odd number of 32-wide k-steps: 64-wide steps would drop the last one (K = 32: all of it).  The three-stage BK = 32 ring, plain epilogue only
+        if (post) { set_error("gemm_nt_dy16: the fused epilogues need K %% 64 == 0 (K=%d)", K); return 1; }
+        if (bf16) return nt_launch<1, 3, 1, 13, 1, 8, 3, 32>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (208 + 384) * 64, st);
+        return nt_launch<1, 3, 1, 13, 1, 8, 3, 32, false, true>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (208 + 384) * 64, st);
+    }
     if (bf16) return nt_launch<1, 2, 1, 13, 1, 8, 3, 64>(a, cdiv(M, 208) * (N / 384), lds, st);   // the same tile and ring on bf16 MFMA
     return nt_launch<1, 2, 1, 13, 1, 8, 3, 64, false, true>(a, cdiv(M, 208) * (N / 384), lds, st);
 }

@@ -121,7 +121,7 @@ int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
 // operand A16 as ONE fp16 plane pre-scaled by a power of two (its inverse arrives in *s2) and the transposed weight integers B16 as fp16 (exact):
 // one v_mfma_f32_16x16x32_f16 pass, 2 B per gradient element.  post: nullptr (plain fp32 output: proj dgrad), mode 8 (fused LayerNorm backward)
 // or mode 9 (fused GELU backward) with o16_mul / o16_amax set - the masked gradient for the next layer then leaves as one fp16 plane too.
-// N % 384 == 0, K % 32 == 0.  bf16 (plain output only): both operands hold bf16 bit patterns, v_mfma_f32_16x16x32_bf16 (the float step's bf16 form).
+// N % 384 == 0, K % 32 == 0 (the fused modes 8 / 9: K % 64 == 0 - they exist on the 64-wide ring only).  bf16 (plain output only): both operands hold bf16 bit patterns, v_mfma_f32_16x16x32_bf16 (the float step's bf16 form).
 int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1, const float* s2,
                         hipStream_t st, const NTPost* post = nullptr, bool bf16 = false);
 // ---- f16strip.hip: the fc2 dgrad + GELU backward of the one-plane backward, A-stationary (K = 384, N = 1536); B16f = the transposed weight integers as fp16 in

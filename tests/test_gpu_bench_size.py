@@ -20,6 +20,8 @@ pytestmark = pytest.mark.gpu
 import qat_vit_amd  # noqa: E402
 from oracle import step_ref  # noqa: E402
 from qat_vit_amd import functional as F  # noqa: E402
+from tests.kernel_check import assert_tiles_close, guarded  # noqa: E402
+from tests.test_gpu_attn import _backward_tile_bounds  # noqa: E402
 from tests.util import cosine, fq_modules, prepare, rel_l2  # noqa: E402
 
 M256 = 256 * 197
@@ -58,16 +60,24 @@ def test_split_a_nt_at_m50432(native_lib, name, K, N):
     s1 = torch.tensor([0.0123], device=dev)
     bias = torch.randn(N, device=dev)
     stats = torch.tensor([0xFF800000 - (1 << 32), 0x007FFFFF], dtype=torch.int32, device=dev)
-    C = torch.full((M, N), float("nan"), device=dev)
+    C, canary = guarded(M, N, torch.float32, dev)
     assert native_lib.qatvit_gemm_nt(Ah.data_ptr(), Al.data_ptr(), Bh.data_ptr(), C.data_ptr(), M, N, K, K, K, N, s1.data_ptr(), None, None,
                                      bias.data_ptr(), stats.data_ptr(), _st()) == 0, native_lib.qatvit_last_error()
     assert not torch.isnan(C).any()                                     # every row of every tile was written
+    canary(name)
     rows = _sample_rows(M)
     ref = ((Ah[rows].double() + Al[rows].double()) @ B.double().t()) * s1.double() + bias.double()
     assert rel_l2(C[rows].cpu(), ref.cpu()) < 2e-5, name
     # the (hi, lo) pair itself is 2^-17 away from fp32: against the unsplit operand
     ref32 = (A[rows].double() @ B.double().t()) * s1.double() + bias.double()
     assert rel_l2(C[rows].cpu(), ref32.cpu()) < 2e-5, name
+    # ... and every row of all 243 row tiles, per 16 x 16 tile, in blocks of 32 row tiles (the fp64 operand of a block stays small)
+    for r0 in range(0, M, 208 * 32):
+        r1 = min(M, r0 + 208 * 32)
+        full = ((Ah[r0:r1].double() + Al[r0:r1].double()) @ B.double().t()) * s1.double() + bias.double()
+        assert_tiles_close(C[r0:r1], full, 2e-5, what=f"{name}, rows {r0}..{r1 - 1}, against the pair")
+        full32 = (A[r0:r1].double() @ B.double().t()) * s1.double() + bias.double()
+        assert_tiles_close(C[r0:r1], full32, 2e-5, what=f"{name}, rows {r0}..{r1 - 1}, against the unsplit operand")
     u = stats.cpu().numpy().view(np.uint32)
 
     def ord2f(k):
@@ -97,8 +107,9 @@ def test_tn_wgrad_at_m50432(native_lib, name, N, Kw, q_f32):
     W = torch.randn(N, Kw, device=dev)
     w_scale = torch.tensor([2.0 / 127], device=dev)
     w_zp = torch.zeros(1, dtype=torch.int32, device=dev)
-    C = torch.zeros(N, Kw, device=dev)
-    db = torch.zeros(N, device=dev)
+    C, canary = guarded(N, Kw, torch.float32, dev, fill=0.0)
+    db2d, canary_db = guarded(1, N, torch.float32, dev, fill=0.0)
+    db = db2d[0]
     nb = native_lib.qatvit_gemm_tn_scratch_bytes()
     scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
     assert native_lib.qatvit_gemm_tn(Ph.data_ptr(), Pl.data_ptr(), Qh.data_ptr(), None if Ql is None else Ql.data_ptr(), C.data_ptr(), M, N, Kw, N, Kw,
@@ -107,8 +118,11 @@ def test_tn_wgrad_at_m50432(native_lib, name, N, Kw, q_f32):
     qv = torch.round(W * (torch.ones(1, device=dev) / w_scale))
     mask = ((qv >= -128) & (qv <= 127)).double()
     ref = ((Ph.double() + Pl.double()).t() @ Qd) * s1.double() * mask
+    canary(name + " C"), canary_db(name + " dbias")
     assert rel_l2(C.cpu(), ref.cpu()) < 2e-5, name
+    assert_tiles_close(C, ref, 2e-5, what=name + " C")
     assert rel_l2(db.cpu(), (Ph.double() + Pl.double()).sum(0).cpu()) < 2e-5, name
+    assert_tiles_close(db2d, (Ph.double() + Pl.double()).sum(0)[None, :], 2e-5, tile=(1, 16), what=name + " dbias")
 
 
 def test_attention_at_b256(native_lib):
@@ -121,17 +135,24 @@ def test_attention_at_b256(native_lib):
     qp = torch.tensor([scale, 1.0, float(zp), 1.0], device=dev)
     qp[1] = torch.ones(1, device=dev)[0] / qp[0]
     TP = native_lib.qatvit_attn_padded_tokens(T)
-    Oh = torch.zeros(B * T, D, device=dev, dtype=torch.bfloat16)
-    Ol = torch.zeros_like(Oh)
-    lse = torch.zeros(B * H, TP, device=dev)
-    delta = torch.zeros(B * H, TP, device=dev)
+    checks = []
+
+    def out(rows, cols, dtype, fill=None):
+        t, check = guarded(rows, cols, dtype, dev, fill=fill)
+        checks.append(check)
+        return t
+
+    Oh = out(B * T, D, torch.bfloat16, 0.0)
+    Ol = out(B * T, D, torch.bfloat16, 0.0)
+    lse = out(B * H, TP, torch.float32, 0.0)
+    delta = out(B * H, TP, torch.float32, 0.0)
     dO = torch.randn(B * T, D, device=dev)
-    gh = torch.full((B * T, 3 * D), float("nan"), device=dev, dtype=torch.bfloat16)
-    gl = torch.full_like(gh, float("nan"))
+    gh = out(B * T, 3 * D, torch.bfloat16)
+    gl = out(B * T, 3 * D, torch.bfloat16)
     st = _st()
-    O16h = torch.zeros(B * T, D, device=dev, dtype=torch.float16); O16l = torch.zeros_like(O16h); osc = torch.zeros(1, device=dev)
-    codes = torch.zeros(B * T, 3 * D, dtype=torch.uint8, device=dev)
-    cmask = torch.zeros(B * T, 3 * D // 8, dtype=torch.uint8, device=dev)
+    O16h = out(B * T, D, torch.float16, 0.0); O16l = out(B * T, D, torch.float16, 0.0); osc = torch.zeros(1, device=dev)
+    codes = out(B * T, 3 * D, torch.uint8, 0)
+    cmask = out(B * T, 3 * D // 8, torch.uint8, 0)
     # as in the step: the forward saves the quantised qkv, the backward reads only that (qkv = NULL)
     assert native_lib.qatvit_attn_forward_f16(qkv.data_ptr(), qp.data_ptr(), qmin, qmax, B, T, H, D, Oh.data_ptr(), Ol.data_ptr(), lse.data_ptr(),
                                               O16h.data_ptr(), O16l.data_ptr(), osc.data_ptr(), codes.data_ptr(), cmask.data_ptr(), st) == 0
@@ -140,6 +161,8 @@ def test_attention_at_b256(native_lib):
     O = (Oh.float() + Ol.float()).view(B, T, D)
     dqkv = (gh.float() + gl.float()).view(B, T, 3, D)
     assert not torch.isnan(dqkv).any()
+    for c in checks:
+        c("attention at B = 256")
     inv = (torch.ones(1, device=dev) / qp[0]).item()
     for b in (0, 1, 100, 127, 128, 254, 255):                           # first / last / middle images, every head of each
         q = torch.round(qkv[b * T:(b + 1) * T] * inv) + zp
@@ -151,10 +174,15 @@ def test_attention_at_b256(native_lib):
         o.backward(dO[b * T:(b + 1) * T].double())
         rg = (fq.grad * mask).view(T, 3, D)
         assert rel_l2(O[b].cpu(), o.detach().cpu()) < 3e-5, b
+        assert_tiles_close(O[b], o.detach(), 3e-5, what=f"O of image {b}")
         o16 = ((O16h.double() + O16l.double()) * osc.double()).view(B, T, D)[b]
         assert rel_l2(o16.cpu(), o.detach().cpu()) < 2e-6, b
+        assert_tiles_close(o16, o.detach(), 2e-6, what=f"O (fp16 pair) of image {b}")
+        # (per tile: dK and dV at 3e-5, dQ at twice the worst tile of the CPU emulation as in tests/test_gpu_attn.py - a correct kernel's worst dQ tile is just above half of 3e-5)
+        bound = _backward_tile_bounds(qkv[b * T:(b + 1) * T], qp[0].item(), zp, qmin, qmax, 1, T, H, D, dO[b * T:(b + 1) * T], None, rg.reshape(T, 3 * D))
         for k in range(3):
             assert rel_l2(dqkv[b, :, k].cpu(), rg[:, k].cpu()) < 3e-5, (b, k)
+            assert_tiles_close(dqkv[b, :, k], rg[:, k], bound["dQ dK dV".split()[k]], what=f"{'dQ dK dV'.split()[k]} of image {b}")
 
 
 def _step(p, x, y, t):

@@ -22,6 +22,7 @@ import qat_vit_amd  # noqa: E402
 from qat_vit_amd import engine as E  # noqa: E402
 from qat_vit_amd import functional as F  # noqa: E402
 from qat_vit_amd import native  # noqa: E402
+from tests.kernel_check import assert_tiles_close, guarded, tile_errors  # noqa: E402
 from tests.util import prepare, rel_l2  # noqa: E402
 
 P = ctypes.c_void_p
@@ -44,13 +45,21 @@ def test_dgrad_one_plane_vs_fp64(native_lib, M, N, K):
     e = 8 - int(np.floor(np.log2(dy.abs().max().item())) + 1)
     plane = (dy * 2.0 ** e).to(torch.float16)
     assert torch.isfinite(plane).all()
-    C = torch.empty(M, N, device="cuda")
+    C, canary = guarded(M, N, torch.float32, "cuda")
     s1, s2 = _scalar(0.0123), _scalar(2.0 ** -e)
     native.check(native_lib.qatvit_gemm_nt_dy16(_ptr(plane), _ptr(wt.to(torch.float16)), _ptr(C), M, N, K, K, K, N, _ptr(s1), _ptr(s2), P(native.stream_ptr())), "nt_dy16")
     ref_rounded = (plane.double() @ wt.double().T) * (0.0123 * 2.0 ** -e)
     ref_exact = (dy.double() @ wt.double().T) * 0.0123
+    canary("gemm_nt_dy16 C")
     assert rel_l2(C.cpu().numpy(), ref_rounded.cpu().numpy()) < 2e-5
+    assert_tiles_close(C, ref_rounded, 2e-5, what="gemm_nt_dy16 against the rounded plane")
     assert rel_l2(C.cpu().numpy(), ref_exact.cpu().numpy()) < 4e-4
+    # what the form costs, per tile: the gradient is heavy-tailed, a tile that holds one of its largest rows carries that row's fp16 rounding (2^-12 of a value
+    # many times the RMS) - measured 5.4e-4 at M = 50,432 for a correct kernel.  The bound is therefore not 4e-4 but twice the worst tile of the emulation: the
+    # exact fp64 product on the ROUNDED plane (ref_rounded, stock torch) against the same reference - every rounding the kernel is asked to make, and no other
+    cost = tile_errors(ref_rounded, ref_exact)[1]
+    print(f"EMU gemm_nt_dy16 against the unrounded gradient: emulation worst_tile {cost:.3e}")
+    assert_tiles_close(C, ref_exact, 2 * cost, what="gemm_nt_dy16 against the unrounded gradient")
 
 
 @pytest.mark.parametrize("M,N,Kw,kind", [(1576, 1152, 384, "grid"), (50432, 1536, 384, "grid"), (50432, 384, 384, "pair"), (1576, 384, 1536, "codes"),
@@ -79,17 +88,24 @@ def test_wgrad_one_plane_vs_fp64(native_lib, M, N, Kw, kind):
         qc = torch.randint(0, 256, (M, Kw), generator=g, device="cuda").to(torch.uint8)
         # (the table's lo halves are ignored: the float X operand enters the one-plane weight gradient rounded to fp16)
         xv = th.float()[qc.long()]
-    dW = torch.zeros(N, Kw, device="cuda")
-    db = torch.zeros(N, device="cuda")
+    dW, canary = guarded(N, Kw, torch.float32, "cuda", fill=0.0)
+    db2d, canary_db = guarded(1, N, torch.float32, "cuda", fill=0.0)
+    db = db2d[0]
     scratch = torch.empty(native_lib.qatvit_gemm_tn_scratch_bytes(), dtype=torch.uint8, device="cuda")
     s1, s2 = _scalar(sx), _scalar(2.0 ** -e)
     native.check(native_lib.qatvit_gemm_tn_dy16(_ptr(plane), _ptr(qh), _ptr(ql), _ptr(qc), _ptr(lut), _ptr(dW), M, N, Kw, N, Kw, Kw, _ptr(s1), _ptr(s2), None, None, None,
                                                 0, -128, 127, _ptr(db), None, _ptr(scratch), scratch.numel(), P(native.stream_ptr())), "tn_dy16")
     ref_rounded = (plane.double().T @ xv.double()) * (sx * 2.0 ** -e)
     ref_exact = (dy.double().T @ xv.double()) * sx
+    canary("gemm_tn_dy16 dW"), canary_db("gemm_tn_dy16 dbias")
     assert rel_l2(dW.cpu().numpy(), ref_rounded.cpu().numpy()) < 2e-5
+    assert_tiles_close(dW, ref_rounded, 2e-5, what="gemm_tn_dy16 against the rounded plane")
     assert rel_l2(dW.cpu().numpy(), ref_exact.cpu().numpy()) < 4e-4     # (codes: against the table value the kernel is given, hi half)
+    cost = tile_errors(ref_rounded, ref_exact)[1]      # (as in test_dgrad_one_plane_vs_fp64: twice the worst tile of the fp64 product on the rounded plane)
+    print(f"EMU gemm_tn_dy16 against the unrounded gradient: emulation worst_tile {cost:.3e}")
+    assert_tiles_close(dW, ref_exact, 2 * cost, what="gemm_tn_dy16 against the unrounded gradient")
     assert rel_l2(db.cpu().numpy(), (plane.double().sum(0) * 2.0 ** -e).cpu().numpy()) < 2e-5
+    assert_tiles_close(db2d, (plane.double().sum(0) * 2.0 ** -e)[None, :], 2e-5, tile=(1, 16), what="gemm_tn_dy16 dbias")
 
 
 @pytest.mark.parametrize("M,N,Kw,center,zp", [(1576, 1152, 384, 128, 131), (50432, 1536, 384, 128, 0), (50432, 1152, 384, 64, 127), (999, 384, 768, 128, 255)])
@@ -105,20 +121,26 @@ def test_wgrad_one_plane_byte_grid_vs_fp64(native_lib, M, N, Kw, center, zp):
     q8 = (q - center).to(torch.int8)
     sx = 0.0371
     a_qp = torch.tensor([sx, 1.0 / sx, float(zp), 1.0], dtype=torch.float32, device="cuda")
-    dW = torch.zeros(N, Kw, device="cuda")
-    db = torch.zeros(N, device="cuda")
+    dW, canary = guarded(N, Kw, torch.float32, "cuda", fill=0.0)
+    db2d, canary_db = guarded(1, N, torch.float32, "cuda", fill=0.0)
+    db = db2d[0]
     scratch = torch.empty(native_lib.qatvit_gemm_tn_scratch_bytes(), dtype=torch.uint8, device="cuda")
     s2 = _scalar(2.0 ** -e)
     native.check(native_lib.qatvit_gemm_tn_q8_dy16(_ptr(plane), _ptr(q8), _ptr(a_qp), center, _ptr(dW), M, N, Kw, N, Kw, Kw, _ptr(s2), None, None, None, 0, -128, 127,
                                                    _ptr(db), None, _ptr(scratch), scratch.numel(), P(native.stream_ptr())), "tn_q8_dy16")
     ref = (plane.double().T @ (q - zp).double()) * (sx * 2.0 ** -e)
+    canary("gemm_tn_q8_dy16 dW"), canary_db("gemm_tn_q8_dy16 dbias")
     assert rel_l2(dW.cpu().numpy(), ref.cpu().numpy()) < 2e-5
+    assert_tiles_close(dW, ref, 2e-5, what="gemm_tn_q8_dy16 dW")
     assert rel_l2(db.cpu().numpy(), (plane.double().sum(0) * 2.0 ** -e).cpu().numpy()) < 2e-5
+    assert_tiles_close(db2d, (plane.double().sum(0) * 2.0 ** -e)[None, :], 2e-5, tile=(1, 16), what="gemm_tn_q8_dy16 dbias")
     # ... and without the split scratch (atomic accumulation), on top of a non-zero dW
-    dW2 = torch.full((N, Kw), 1e-4, device="cuda")
+    dW2, canary2 = guarded(N, Kw, torch.float32, "cuda", fill=1e-4)
     native.check(native_lib.qatvit_gemm_tn_q8_dy16(_ptr(plane), _ptr(q8), _ptr(a_qp), center, _ptr(dW2), M, N, Kw, N, Kw, Kw, _ptr(s2), None, None, None, 0, -128, 127,
                                                    None, None, None, 0, P(native.stream_ptr())), "tn_q8_dy16")
+    canary2("gemm_tn_q8_dy16 dW (atomics)")
     assert rel_l2((dW2.double() - 1e-4).cpu().numpy(), ref.cpu().numpy()) < 1e-4      # (fp32 atomics onto 1e-4: ~1e-5)
+    assert_tiles_close(dW2.double() - 1e-4, ref, 1e-4, what="gemm_tn_q8_dy16 dW (atomics)")
 
 
 @pytest.mark.parametrize("M", [70, 640])   # one split and the in-kernel tail | two splits for every form: k_tn_reduce with scratch, atomics without
@@ -177,19 +199,27 @@ def test_wgrad_one_plane_mask_row_div_per_channel(native_lib, M, kind):
     ref = (plane.double().T @ xv.double()) * (sx * 2.0 ** -e) / rdiv.double()[:, None]
     ref = torch.where(keep, ref, torch.zeros_like(ref))
     bref = plane.double().sum(0) * 2.0 ** -e / rdiv.double()
-    dW, db = C0.clone(), torch.zeros(N, device="cuda")
+    (dW, canary), (db2d, canary_db) = guarded(N, Kw, torch.float32, "cuda"), guarded(1, N, torch.float32, "cuda", fill=0.0)
+    dW.copy_(C0)
+    db = db2d[0]
     run(dW, db, scratch)
+    canary(f"tn_dy16 {kind} dW"), canary_db(f"tn_dy16 {kind} dbias")
     err_w, err_b = rel_l2((dW.double() - C0.double()).cpu().numpy(), ref.cpu().numpy()), rel_l2(db.cpu().numpy(), bref.cpu().numpy())
     dW2, db2 = C0.clone(), torch.zeros(N, device="cuda")
     run(dW2, db2, scratch)
-    dW3, db3 = torch.full((N, Kw), 1e-4, device="cuda"), torch.zeros(N, device="cuda")
+    (dW3, canary3), db3 = guarded(N, Kw, torch.float32, "cuda", fill=1e-4), torch.zeros(N, device="cuda")
     run(dW3, db3, None)
+    canary3(f"tn_dy16 {kind} dW (atomics)")
     err_wa, err_ba = rel_l2((dW3.double() - 1e-4).cpu().numpy(), ref.cpu().numpy()), rel_l2(db3.cpu().numpy(), bref.cpu().numpy())
     print(f"{kind} M={M}: clipped {clipped:.4f}; scratch dW {err_w:.2e} db {err_b:.2e}; atomics dW {err_wa:.2e} db {err_ba:.2e}")
     assert 0.01 < clipped < 0.2
     assert err_w < 2e-5 and err_b < 2e-5
+    assert_tiles_close(dW.double() - C0.double(), ref, 2e-5, what=f"tn_dy16 {kind} dW")
+    assert_tiles_close(db2d, bref[None, :], 2e-5, tile=(1, 16), what=f"tn_dy16 {kind} dbias")
     assert torch.equal(dW, dW2), "with scratch the splits are summed in a fixed order: same bits on a second run"
     assert err_wa < 1e-4 and err_ba < 1e-4      # (fp32 atomics onto 1e-4: ~1e-5)
+    assert_tiles_close(dW3.double() - 1e-4, ref, 1e-4, what=f"tn_dy16 {kind} dW (atomics)")
+    assert_tiles_close(db3[None, :], bref[None, :], 1e-4, tile=(1, 16), what=f"tn_dy16 {kind} dbias (atomics)")
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
@@ -229,7 +259,8 @@ def test_wgrad_stream_batch_vs_fp64(native_lib, mode, M, shapes):
             s1 = _scalar(sx)
         s2 = _scalar(2.0 ** -e)
         C0 = torch.randn(N, Kw, generator=g, device="cuda") * 1e-5
-        C = C0.clone()
+        C, canary = guarded(N, Kw, torch.float32, "cuda")
+        C.copy_(C0)
         masked, biased, divided = k % 2 == 0, k % 3 != 1, k % 4 == 3
         W = torch.randn(N, Kw, generator=g, device="cuda") if masked else None
         wsc = torch.full((N,), 0.01, device="cuda") if masked else None
@@ -248,7 +279,7 @@ def test_wgrad_stream_batch_vs_fp64(native_lib, mode, M, shapes):
             qq = torch.round(W * (1.0 / wsc)[:, None])
             ref = torch.where((qq >= -128) & (qq <= 127), ref, torch.zeros_like(ref))
         bref = plane.double().sum(0) * 2.0 ** -e / (rdiv.double() if divided else 1.0)
-        keep.append((plane, Q, lut, s1, s2, C, W, wsc, wzp, db, rdiv, C0))
+        keep.append((plane, Q, lut, s1, s2, C, W, wsc, wzp, db, rdiv, C0, canary))
         refs.append((ref, bref))
     scratch = torch.empty(native_lib.qatvit_gemm_tn_stream_scratch_bytes(), dtype=torch.uint8, device="cuda")
 
@@ -257,11 +288,14 @@ def test_wgrad_stream_batch_vs_fp64(native_lib, mode, M, shapes):
                                                            P(native.stream_ptr())), "tn_stream_dy16")
     run()
     first = []
-    for (plane, Q, lut, s1, s2, C, W, wsc, wzp, db, rdiv, C0), (ref, bref) in zip(keep, refs):
+    for k, ((plane, Q, lut, s1, s2, C, W, wsc, wzp, db, rdiv, C0, canary), (ref, bref)) in enumerate(zip(keep, refs)):
+        canary(f"tn_stream item {k} dW")
         got = (C.double() - C0.double())
         assert rel_l2(got.cpu().numpy(), ref.cpu().numpy()) < 3e-5
+        assert_tiles_close(got, ref, 3e-5, what=f"tn_stream item {k} dW")
         if db is not None:
             assert rel_l2(db.cpu().numpy(), bref.cpu().numpy()) < 2e-5
+            assert_tiles_close(db[None, :], bref[None, :], 2e-5, tile=(1, 16), what=f"tn_stream item {k} dbias")
         first.append(C.clone())
         C.copy_(C0)
     run()

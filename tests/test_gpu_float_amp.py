@@ -13,6 +13,7 @@ import qat_vit_amd
 from qat_vit_amd import functional as F
 from qat_vit_amd import native
 from qat_vit_amd.float_engine import engine_of
+from tests.kernel_check import assert_tiles_close, guarded
 
 pytestmark = pytest.mark.gpu
 D2 = dict(depth=2)   # ViT-S width (384, 6 heads), two blocks
@@ -91,7 +92,7 @@ def test_attention_backward_kernel_against_fp64(hd):
     O16 = O.transpose(1, 2).reshape(B * T, D).half().contiguous()
     lse32 = lse.float().contiguous()
     lib = native.lib()
-    dqkv = torch.full((B * T, 3 * D), float("nan"), dtype=torch.float16, device="cuda")
+    dqkv, canary = guarded(B * T, 3 * D, torch.float16, "cuda")
     native.check(lib.qatvit_float_student_amp_attn_backward(qkv.data_ptr(), O16.data_ptr(), lse32.data_ptr(), dO.data_ptr(), B, T, H, D, dqkv.data_ptr(),
                                                             native.stream_ptr()), "qatvit_float_student_amp_attn_backward")
     torch.cuda.synchronize()
@@ -100,6 +101,10 @@ def test_attention_backward_kernel_against_fp64(hd):
     print(f"\nhead_dim {hd}: dQ {errs[0]:.2e} dK {errs[1]:.2e} dV {errs[2]:.2e}")
     assert torch.isfinite(dqkv).all()
     assert max(errs) <= 3e-3, errs
+    canary("dqkv")
+    want2d = torch.stack((dQ, dK, dV)).permute(1, 3, 0, 2, 4).reshape(B * T, 3 * D)      # the qkv layout of the output
+    for name, c0 in (("dQ", 0), ("dK", D), ("dV", 2 * D)):
+        assert_tiles_close(dqkv[:, c0:c0 + D], want2d[:, c0:c0 + D], 3e-3, what=name)
 
 
 def _scaled_grads_finite(model, x, y, scale):

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from tests.kernel_check import assert_tiles_close, guarded  # noqa: E402
 from tests.util import rel_l2  # noqa: E402
 
 
@@ -44,13 +45,15 @@ def test_gemm_nt(native_lib, M, N, K, a_f32):
     cs = torch.rand(N, device=dev) + 0.5
     bias = torch.randn(N, device=dev)
     stats = torch.tensor([-8388608, 8388607], dtype=torch.int32, device=dev)  # bit patterns of ord(+inf), ord(-inf)
-    C = torch.full((M, N), float("nan"), device=dev)
+    C, canary = guarded(M, N, torch.float32, dev)
     st = native_lib.qatvit_gemm_nt(Ah.data_ptr(), _ptr(Al), Bh.data_ptr(), C.data_ptr(), M, N, K, K, K, N, s1.data_ptr(), s2.data_ptr(),
                                    cs.data_ptr(), bias.data_ptr(), stats.data_ptr(), _st())
     assert st == 0, native_lib.qatvit_last_error()
     ref = (A.double() @ B.double().t()) * (s1.double() * s2.double()) * cs.double() + bias.double()
     assert not torch.isnan(C).any()
+    canary("gemm_nt C")
     assert rel_l2(C.cpu(), ref.cpu()) < 2e-5
+    assert_tiles_close(C, ref, 2e-5, what="gemm_nt")
     u = stats.cpu().numpy().view(np.uint32)
 
     def ord2f(k):
@@ -67,10 +70,11 @@ def test_gemm_nt_integer_exact(native_lib):
     M, N, K = 256, 128, 384
     A = torch.randint(-255, 256, (M, K), device=dev).float()
     B = torch.randint(-128, 128, (N, K), device=dev).float()
-    C = torch.empty(M, N, device=dev)
+    C, canary = guarded(M, N, torch.float32, dev)
     Ah, Bh = A.to(torch.bfloat16), B.to(torch.bfloat16)
     st = native_lib.qatvit_gemm_nt(Ah.data_ptr(), None, Bh.data_ptr(), C.data_ptr(), M, N, K, K, K, N, None, None, None, None, None, _st())
     assert st == 0
+    canary("gemm_nt C")
     assert torch.equal(C.double(), A.double() @ B.double().t())  # integers < 2^24: exact
 
 
@@ -92,8 +96,8 @@ def test_gemm_nt_i8_equals_bf16_path(native_lib, M, N, K, zp, center):
     s1 = torch.tensor([0.0173], device=dev)
     s2 = torch.tensor([0.0041], device=dev)
     bias = torch.randn(N, device=dev)
-    C16 = torch.empty(M, N, device=dev)
-    C8 = torch.empty(M, N, device=dev)
+    C16, canary16 = guarded(M, N, torch.float32, dev)
+    C8, canary8 = guarded(M, N, torch.float32, dev)
     st16 = torch.tensor([0xFF800000 - (1 << 32), 0x007FFFFF], dtype=torch.int32, device=dev)
     st8 = st16.clone()
     assert native_lib.qatvit_gemm_nt(A16.data_ptr(), None, B16.data_ptr(), C16.data_ptr(), M, N, K, K, K, N, s1.data_ptr(), s2.data_ptr(), None,
@@ -102,8 +106,10 @@ def test_gemm_nt_i8_equals_bf16_path(native_lib, M, N, K, zp, center):
                                         s1.data_ptr(), s2.data_ptr(), None, bias.data_ptr(), st8.data_ptr(), _st()) == 0, native_lib.qatvit_last_error()
     assert torch.equal(C8, C16)
     assert torch.equal(st8, st16)
+    canary16("gemm_nt C"), canary8("gemm_nt_i8 C")
     ref = ((q - zp).double() @ W.double().t()) * (0.0173 * 0.0041) + bias.double()
     assert rel_l2(C8.cpu(), ref.cpu()) < 1e-6
+    assert_tiles_close(C8, ref, 1e-6, what="gemm_nt_i8")
 
 
 def test_gemm_rejects_bad_shapes(native_lib):
@@ -135,8 +141,9 @@ def test_gemm_tn(native_lib, M, N, Kw, q_f32, two_phase):
     W = torch.randn(N, Kw, device=dev)
     w_scale = torch.tensor([2.0 / 127], device=dev)  # clips |W| > 2
     w_zp = torch.zeros(1, dtype=torch.int32, device=dev)
-    C = torch.zeros(N, Kw, device=dev)
-    db = torch.zeros(N, device=dev)
+    C, canary = guarded(N, Kw, torch.float32, dev, fill=0.0)
+    db2d, canary_db = guarded(1, N, torch.float32, dev, fill=0.0)
+    db = db2d[0]
     nb = native_lib.qatvit_gemm_tn_scratch_bytes()
     scratch = torch.empty(nb if two_phase else 16, dtype=torch.uint8, device=dev)
 
@@ -157,8 +164,11 @@ def test_gemm_tn(native_lib, M, N, Kw, q_f32, two_phase):
     mask = ((qv >= -128) & (qv <= 127)).double()
     ref = (P.double().t() @ Q.double()) * s1.double() * mask
     assert 0.01 < 1 - mask.mean().item() < 0.2
+    canary("gemm_tn C"), canary_db("gemm_tn dbias")
     assert rel_l2(C.cpu(), ref.cpu()) < 2e-5
+    assert_tiles_close(C, ref, 2e-5, what="gemm_tn C")
     assert rel_l2(db.cpu(), P.double().sum(0).cpu()) < 2e-5
+    assert_tiles_close(db2d, P.double().sum(0)[None, :], 2e-5, tile=(1, 16), what="gemm_tn dbias")
 
 
 def test_gemm_tn_per_channel_mask_and_row_div(native_lib):
@@ -170,8 +180,9 @@ def test_gemm_tn_per_channel_mask_and_row_div(native_lib):
     W = torch.randn(N, Kw, device=dev)
     w_scale = (torch.rand(N, device=dev) + 0.5) * 2.0 / 127
     w_zp = torch.zeros(N, dtype=torch.int32, device=dev)
-    C = torch.zeros(N, Kw, device=dev)
-    db = torch.zeros(N, device=dev)
+    C, canary = guarded(N, Kw, torch.float32, dev, fill=0.0)
+    db2d, canary_db = guarded(1, N, torch.float32, dev, fill=0.0)
+    db = db2d[0]
     Ph, Pl = split(P * w_scale[None, :])  # the producer folds the per-channel scale in ...
     Qh = Q.to(torch.bfloat16)
     st = native_lib.qatvit_gemm_tn(Ph.data_ptr(), Pl.data_ptr(), Qh.data_ptr(), None, C.data_ptr(), M, N, Kw, N, Kw, Kw, None, W.data_ptr(),
@@ -179,8 +190,11 @@ def test_gemm_tn_per_channel_mask_and_row_div(native_lib):
     assert st == 0, native_lib.qatvit_last_error()
     qv = torch.round(W * (1.0 / w_scale)[:, None])
     mask = ((qv >= -128) & (qv <= 127)).double()
+    canary("gemm_tn C"), canary_db("gemm_tn dbias")
     assert rel_l2(C.cpu(), ((P.double().t() @ Q.double()) * mask).cpu()) < 2e-5
+    assert_tiles_close(C, (P.double().t() @ Q.double()) * mask, 2e-5, what="gemm_tn C (per-channel mask, row_div)")
     assert rel_l2(db.cpu(), P.double().sum(0).cpu()) < 2e-5
+    assert_tiles_close(db2d, P.double().sum(0)[None, :], 2e-5, tile=(1, 16), what="gemm_tn dbias (row_div)")
 
 
 def split_h(x):
@@ -206,22 +220,29 @@ def test_gemm_nt_f16_pair(native_lib, M, N, K):
     s2 = torch.tensor([0.0045], device=dev)
     bias = torch.randn(N, device=dev)
     stats = torch.tensor([0xFF800000 - (1 << 32), 0x007FFFFF], dtype=torch.int32, device=dev)
-    C = torch.full((M, N), float("nan"), device=dev)
+    C, canary = guarded(M, N, torch.float32, dev)
     assert native_lib.qatvit_gemm_nt_f16(Ah.data_ptr(), Al.data_ptr(), Bh.data_ptr(), C.data_ptr(), M, N, K, K, K, N, s1.data_ptr(), s2.data_ptr(), None,
                                          bias.data_ptr(), stats.data_ptr(), _st()) == 0, native_lib.qatvit_last_error()
+    canary("gemm_nt_f16 C")
     rows = torch.arange(0, M, max(1, M // 1500), device=dev)
     ref = (A[rows].double() @ B.double().t()) * (0.0123 * 0.0045) + bias.double()
     assert not torch.isnan(C).any()
     e16 = rel_l2(C[rows].cpu(), ref.cpu())
     # the bf16-pair form on the same operand, for the record
     Abh, Abl = split(A)
-    Cb = torch.empty_like(C)
+    Cb, canary_b = guarded(M, N, torch.float32, dev)
     s1b = torch.tensor([0.0123], device=dev)
     assert native_lib.qatvit_gemm_nt(Abh.data_ptr(), Abl.data_ptr(), B.to(torch.bfloat16).data_ptr(), Cb.data_ptr(), M, N, K, K, K, N, s1b.data_ptr(),
                                      s2.data_ptr(), None, bias.data_ptr(), None, _st()) == 0
     eb = rel_l2(Cb[rows].cpu(), ref.cpu())
     print(f"nt M={M} N={N} K={K}: fp16 pair {e16:.2e}, bf16 pair {eb:.2e}")
     assert e16 < 1e-6 and e16 < eb
+    canary_b("gemm_nt C")
+    # every row, per tile (the sampled rows above skip most of the ragged last row tile); row blocks keep the fp64 operand small
+    for r0 in range(0, M, 208 * 32):
+        r1 = min(M, r0 + 208 * 32)
+        full = (A[r0:r1].double() @ B.double().t()) * (0.0123 * 0.0045) + bias.double()
+        assert_tiles_close(C[r0:r1], full, 1e-6, what=f"gemm_nt_f16 rows {r0}..{r1 - 1}")
 
 
 @pytest.mark.parametrize("M,N,K", [(1576, 384, 384), (300, 384, 1536), (50432, 384, 1536), (1000, 768, 3072), (207, 384, 64)])
@@ -247,8 +268,8 @@ def test_gemm_nt_codes_equals_planes(native_lib, M, N, K):
         return torch.tensor([0xFF800000 - (1 << 32), 0x007FFFFF], dtype=torch.int32, device=dev)
 
     st_a, st_b = fresh(), fresh()
-    Ca = torch.full((M, N), float("nan"), device=dev)
-    Cb = torch.full((M, N), float("nan"), device=dev)
+    Ca, canary_a = guarded(M, N, torch.float32, dev)
+    Cb, canary_b = guarded(M, N, torch.float32, dev)
     assert native_lib.qatvit_gemm_nt_f16(Ah.data_ptr(), Al.data_ptr(), Bh.data_ptr(), Ca.data_ptr(), M, N, K, K, K, N, s1.data_ptr(), s2.data_ptr(),
                                          cs.data_ptr(), bias.data_ptr(), st_a.data_ptr(), _st()) == 0, native_lib.qatvit_last_error()
     assert native_lib.qatvit_gemm_nt_codes(idx.data_ptr(), lut.data_ptr(), Bh.data_ptr(), Cb.data_ptr(), M, N, K, K, K, N, s1.data_ptr(), s2.data_ptr(),
@@ -257,6 +278,7 @@ def test_gemm_nt_codes_equals_planes(native_lib, M, N, K):
     assert not torch.isnan(Cb).any()
     assert torch.equal(Ca, Cb)
     assert torch.equal(st_a, st_b)
+    canary_a("gemm_nt_f16 C"), canary_b("gemm_nt_codes C")
 
 
 def _ord2f(k):   # qv_common.h: order-preserving uint32 -> float
@@ -302,7 +324,7 @@ def test_i8_strip_kernel_equals_general_kernel(native_lib, B, T, N, K, per_chann
     def fresh():
         return torch.tensor([0xFF800000 - (1 << 32), 0x007FFFFF], dtype=torch.int32, device=dev)
 
-    C = torch.empty(M, N, device=dev)
+    C, canary = guarded(M, N, torch.float32, dev)
     st_full, st_gen, st_strip = fresh(), fresh(), fresh()
     assert native_lib.qatvit_gemm_nt_i8(A8.data_ptr(), B8.data_ptr(), wsum.data_ptr(), aqp.data_ptr(), center, C.data_ptr(), M, N, K, K, K, N, s1.data_ptr(),
                                         s2p, csp, bias.data_ptr(), st_full.data_ptr(), _st()) == 0, native_lib.qatvit_last_error()
@@ -332,8 +354,9 @@ def test_i8_strip_kernel_equals_general_kernel(native_lib, B, T, N, K, per_chann
     assert 0.02 < (~want_mask).float().mean().item() < 0.5
 
     # mode 4: row-major codes + mask bits + the two tables
-    out8 = torch.full((M, N), 0xEE, dtype=torch.uint8, device=dev)
-    mask = torch.full((M, N // 8), 0xEE, dtype=torch.uint8, device=dev)
+    canary("gemm_nt_i8 C")
+    out8, canary_o = guarded(M, N, torch.uint8, dev, fill=0xEE)
+    mask, canary_m = guarded(M, N // 8, torch.uint8, dev, fill=0xEE)
     lut = torch.zeros(256, dtype=torch.int32, device=dev)
     lutq = torch.zeros(256, dtype=torch.int32, device=dev)
     sc = torch.zeros(1, device=dev)
@@ -341,6 +364,7 @@ def test_i8_strip_kernel_equals_general_kernel(native_lib, B, T, N, K, per_chann
     torch.cuda.synchronize()
     assert torch.equal(out8, want_code)
     assert torch.equal(_unpack_bits(mask, M * N).view(M, N), want_mask)
+    canary_o("i8_strip mode 4 codes"), canary_m("i8_strip mode 4 mask bits")
     grid = (torch.arange(qrange[0], qrange[1] + 1, device=dev).float() - zpo) * scale
     g = torch.nn.functional.gelu(grid.double()).float()
     n = grid.numel()
@@ -354,14 +378,16 @@ def test_i8_strip_kernel_equals_general_kernel(native_lib, B, T, N, K, per_chann
     # mode 7: the attention layout [b][head][q|k|v][t][64]
     if (N // 3) % 384 == 0:
         D, H = N // 3, N // 3 // 64
-        out8 = torch.full((B, H, 3, T, 64), 0xEE, dtype=torch.uint8, device=dev)
-        mask = torch.full((B, H, 3, T, 8), 0xEE, dtype=torch.uint8, device=dev)
+        out8, canary_o = guarded(B * H * 3 * T, 64, torch.uint8, dev, fill=0xEE)
+        mask, canary_m = guarded(B * H * 3 * T, 8, torch.uint8, dev, fill=0xEE)
+        out8, mask = out8.view(B, H, 3, T, 64), mask.view(B, H, 3, T, 8)
         strip(7, qp=qp, out8=out8, mask=mask, code_T=T)
         torch.cuda.synchronize()
         want = want_code.view(B, T, 3, H, 64).permute(0, 3, 2, 1, 4).contiguous()
         assert torch.equal(out8, want)
         wm = want_mask.view(B, T, 3, H, 64).permute(0, 3, 2, 1, 4).contiguous()
         assert torch.equal(_unpack_bits(mask, M * N).view(B, H, 3, T, 64), wm)
+        canary_o("i8_strip mode 7 codes"), canary_m("i8_strip mode 7 mask bits")
 
 
 @pytest.mark.parametrize("two_phase", [0, 1])
@@ -386,8 +412,9 @@ def test_gemm_tn_codes_equals_planes(native_lib, M, N, Kw, two_phase):
     w_zp = torch.zeros(1, dtype=torch.int32, device=dev)
     nb = native_lib.qatvit_gemm_tn_scratch_bytes()
     scratch = torch.empty(nb if two_phase else 16, dtype=torch.uint8, device=dev)
-    Ca, Cb = torch.zeros(N, Kw, device=dev), torch.zeros(N, Kw, device=dev)
-    dba, dbb = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+    (Ca, canary_a), (Cb, canary_b) = guarded(N, Kw, torch.float32, dev, fill=0.0), guarded(N, Kw, torch.float32, dev, fill=0.0)
+    (dba2, canary_da), (dbb2, canary_db) = guarded(1, N, torch.float32, dev, fill=0.0), guarded(1, N, torch.float32, dev, fill=0.0)
+    dba, dbb = dba2[0], dbb2[0]
     sp, sn = (scratch.data_ptr(), nb) if two_phase else (None, 0)
     assert native_lib.qatvit_gemm_tn(Ph.data_ptr(), Pl.data_ptr(), Qh.data_ptr(), Ql.data_ptr(), Ca.data_ptr(), M, N, Kw, N, Kw, Kw, s1.data_ptr(), W.data_ptr(),
                                      w_scale.data_ptr(), w_zp.data_ptr(), 0, -128, 127, dba.data_ptr(), None, sp, sn, _st()) == 0, native_lib.qatvit_last_error()
@@ -400,5 +427,9 @@ def test_gemm_tn_codes_equals_planes(native_lib, M, N, Kw, two_phase):
     qv = torch.round(W * (torch.ones(1, device=dev) / w_scale))
     mask = ((qv >= -128) & (qv <= 127)).double()
     ref = (P.double().t() @ (Qh.double() + Ql.double())) * s1.double() * mask
+    canary_a("gemm_tn C"), canary_b("gemm_tn_codes C"), canary_da("gemm_tn dbias"), canary_db("gemm_tn_codes dbias")
     assert rel_l2(Cb.cpu(), ref.cpu()) < 2e-5 and rel_l2(Ca.cpu(), ref.cpu()) < 2e-5
+    assert_tiles_close(Cb, ref, 2e-5, what="gemm_tn_codes C")
+    assert_tiles_close(Ca, ref, 2e-5, what="gemm_tn C")
     assert rel_l2(dbb.cpu(), P.double().sum(0).cpu()) < 2e-5
+    assert_tiles_close(dbb2, P.double().sum(0)[None, :], 2e-5, tile=(1, 16), what="gemm_tn_codes dbias")

@@ -9,6 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from qat_vit_amd import functional as F  # noqa: E402
+from tests.kernel_check import assert_tiles_close  # noqa: E402
 from tests.util import rel_l2  # noqa: E402
 
 
@@ -26,7 +27,9 @@ def test_layer_norm_fwd_bwd(native_lib, rows, D):
     y64.backward(dy.double())
     # fp32 kernel vs fp64 reference: 1e-5 relative L2 (fp32 rounding of a D-term reduction)
     assert rel_l2(y.detach().cpu(), y64.detach().cpu()) < 1e-5
+    assert_tiles_close(y.detach(), y64.detach(), 1e-5, tile=(1, D), what="layer_norm y, per row")
     assert rel_l2(x.grad.cpu(), x64.grad.cpu()) < 1e-5
+    assert_tiles_close(x.grad, x64.grad, 1e-5, tile=(1, D), what="layer_norm dx, per row")
     # column sums over up to 50k rows in fp32 with atomics: 1e-4
     assert rel_l2(g.grad.cpu(), g64.grad.cpu()) < 1e-4
     assert rel_l2(b.grad.cpu(), b64.grad.cpu()) < 1e-4
