@@ -270,6 +270,22 @@ int qatvit_attn_forward_f16(const float* qkv, const float* qp, int32_t qmin, int
 int qatvit_attn_backward(const float* qkv, const float* qp, int32_t qmin, int32_t qmax, int32_t B, int32_t T, int32_t H,
                          int32_t D, const void* O_hi, const void* O_lo, const float* lse, float* delta, const float* dO,
                          void* dqkv_hi, void* dqkv_lo, const float* col_scale, const void* qkv_codes, const void* qkv_mask, void* stream);
+/* The same backward where dO is known to be zero outside the first live_q_tiles 16-query tiles of every image (0: anywhere - qatvit_attn_backward).  The fused
+ * kernel (head_dim 64, 33..224 tokens, saved codes) then sweeps only the query pairs that hold them and stores zeros as the dQ of the others; dK and dV are
+ * complete either way.  The two-kernel form ignores the count.  dO_cls != 0 (fused kernel only, live_q_tiles >= 1): dO is [B, D] - the rows of token 0, the
+ * class token of a cls-pooled model; every other row of dO is zero by definition. */
+int qatvit_attn_backward_live(const float* qkv, const float* qp, int32_t qmin, int32_t qmax, int32_t B, int32_t T, int32_t H,
+                              int32_t D, const void* O_hi, const void* O_lo, const float* lse, float* delta, const float* dO,
+                              void* dqkv_hi, void* dqkv_lo, const float* col_scale, const void* qkv_codes, const void* qkv_mask,
+                              int32_t live_q_tiles, int32_t dO_cls, void* stream);
+
+/* The class-token rows of a [rows * T, width bytes] tensor (the student pools the class token, so the gradient entering the last block lives in rows
+ * b * T only; the one-plane backward runs that block's MLP and proj on those rows - QATVIT_CLS_BWD=0 in the environment: on all rows).
+ * gather: compact[b] = tall[b * T], b < rows; width % 4 == 0, `stride` = bytes between two rows of tall (% 4 == 0, >= width).
+ * scatter: writes ALL of tall [rows * T, width] - row b * T = compact[b], every other row zero; width % 16 == 0, 16-byte aligned pointers.
+ * Replaces: nothing in the reference (its autograd runs every row). */
+int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream);
+int qatvit_rows_scatter(const void* compact, void* tall, int32_t rows, int32_t T, int32_t width, void* stream);
 
 /* ===========================================================================
  * The whole student step.
@@ -335,6 +351,9 @@ int qatvit_student_backward(const qatvit_cfg* cfg, void* const* params, const qa
  * backward with QATVIT_BWD_DY16; a raised flag -> qatvit_student_dy16_to_pair + the same backward again with QATVIT_BWD_CALIBRATE into zeroed gradients:
  * the step is then bit-identical to a pair-form step.  Error of the one-plane form against the pair form: 2^-12 per element, relative L2 1-2e-4 per stage
  * (tests/test_gpu_stage_parity.py runs every stage table in both forms).  qatvit_student_backward (no flags) is always the pair form.
+ * Stage 0 with QATVIT_BWD_DY16 leaves the gradient entering the last block as [B, embed_dim] rows of the class tokens inside the workspace (the student pools the class
+ * token: every other row is zero), not as the full "dxA"; stage 1 of the same or a later call takes it from there and runs its MLP and proj backward on those B rows.
+ * A stage 1 with QATVIT_STAGE_INJECT reads the caller's full "dxA" as before.  QATVIT_CLS_BWD=0 in the environment: the full-height form throughout.
  * Replaces: the same `loss.backward()` (qat_trainer.py:359). */
 #define QATVIT_FWD_X16 2        /* forward: h1q / h2q as fp16 integers (needs qatvit_student_dy16_supported) */
 #define QATVIT_BWD_DY16 2       /* backward: the one-plane form (the forward ran with QATVIT_FWD_X16, the workspace is calibrated) */

@@ -232,6 +232,11 @@ struct AttnArgs {
     // the one-plane backward (k_attn_bwd_fused<NKT, true>): dqkv_hi is ONE fp16 plane of value * (*o16_mul), max |value| goes to o16_amax (dy16.hip)
     const float* o16_mul;
     uint32_t* o16_amax;
+    // k_attn_bwd_fused on the class-token gradient (the last block under a cls-pooled head: dO is zero in every query row but row 0 of each image, so delta, dP
+    // and dS of every other query are zero).  live_q_tiles > 0: only the first live_q_tiles 16-query tiles carry a gradient - the sweep visits the query pairs
+    // that hold them and stores zeros as the dQ of the rest; 0: all of them.  dO_cls != 0: dO is [B, D], the rows of token 0 (every other row reads as zero)
+    int live_q_tiles;
+    int dO_cls;
 };
 
 // stage one [T][HD] slice (q, k or v of head h) into an LDS image; `which`: 0 q, 1 k, 2 v
@@ -861,7 +866,9 @@ __device__ inline bf16x8 tr_frag_ds(const char* img_vq, int tokA, int tokB, int 
     const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, v);
 }
-template <int NKT, bool O16 = false>
+// LIVE: AttnArgs::live_q_tiles / dO_cls apply (an instantiation of its own: the ordinary one keeps its compile-time sweep count and unconditional loads -
+// with both as run-time values every launch measured 2 - 4 us slower)
+template <int NKT, bool O16 = false, bool LIVE = false>
 __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
     constexpr int HD = 64, NWV = 8;
     float mul16 = 1.f, am16 = 0.f;
@@ -916,7 +923,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
     float4 da4[ITERS], db4[ITERS];
     uint4 oh[ITERS], ol[ITERS];
     {
-        const float* const dOb = p.dO + (int64_t)b * T * D + h * HD;
+        const float* const dOb = p.dO + (int64_t)b * (LIVE && p.dO_cls ? 1 : T) * D + h * HD;
         const __bf16* const Ohb = p.O_hi + (int64_t)b * T * D + h * HD;
         const __bf16* const Olb = p.O_lo + (int64_t)b * T * D + h * HD;
 #pragma unroll
@@ -925,10 +932,18 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
             cq[it] = *reinterpret_cast<const uint2*>(cbase + tok * HD + ch * 8);
             ck[it] = *reinterpret_cast<const uint2*>(cbase + sl + tok * HD + ch * 8);
             const int64_t off = (int64_t)tok * D + ch * 8;
-            da4[it] = reinterpret_cast<const float4*>(dOb + off)[0];
-            db4[it] = reinterpret_cast<const float4*>(dOb + off)[1];
-            oh[it] = *reinterpret_cast<const uint4*>(Ohb + off);
-            ol[it] = *reinterpret_cast<const uint4*>(Olb + off);
+            // (the [B, D] form: dO has the rows of token 0 only, and O is needed for delta = rowsum(dO . O) alone - every other token loads neither: a
+            //  quarter of the head's bytes instead of all of them; for it >= 1 the branch is wave-uniform)
+            if constexpr (LIVE) {
+                da4[it] = db4[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+                oh[it] = ol[it] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            if (!LIVE || !p.dO_cls || tok == 0) {
+                da4[it] = reinterpret_cast<const float4*>(dOb + off)[0];
+                db4[it] = reinterpret_cast<const float4*>(dOb + off)[1];
+                oh[it] = *reinterpret_cast<const uint4*>(Ohb + off);
+                ol[it] = *reinterpret_cast<const uint4*>(Olb + off);
+            }
         }
     }
     // the head's three mask slices are one contiguous run of 3 T rows: two 8-byte loads per thread here instead of 23 single-byte loads per
@@ -995,8 +1010,10 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
     for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int id = 0; id < ND; ++id) dk[u][id] = dv[u][id] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // the query pairs that carry a gradient (AttnArgs::live_q_tiles): a pair without one adds exact zeros to dK / dV and its dQ is zero
+    const int nqs = LIVE && p.live_q_tiles > 0 ? min(NKT / 2, (p.live_q_tiles + 1) / 2) : NKT / 2;
 #pragma unroll 1
-    for (int qs = 0; qs < NKT / 2; ++qs) {
+    for (int qs = 0; qs < nqs; ++qs) {
         const int qme = 16 * (2 * qs + vq) + r;
         const uint32_t mqb = reinterpret_cast<const uint8_t*>(sM)[min(qme, T - 1) * 8 + 2 * jd + (g >> 1)];
         // phase 1: S and dP of every owned key tile (the query-row fragments are dead afterwards: 48 registers)
@@ -1112,6 +1129,13 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
                 *reinterpret_cast<uint2*>(p.dqkv_lo + offq) = gl;
             }
         }
+    }
+    // the dQ of the query pairs the sweep skipped: zeros (the qkv dgrad and weight gradient read the whole plane), 16 bytes per thread, whole 128-byte rows
+    if constexpr (LIVE)
+    for (int i = threadIdx.x; i < (T - 32 * nqs) * (HD / 8); i += NWV * 64) {
+        const int64_t offq = ((int64_t)b * T + 32 * nqs + i / (HD / 8)) * ld + h * HD + 8 * (i % (HD / 8));
+        *reinterpret_cast<uint4*>(p.dqkv_hi + offq) = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (!O16) *reinterpret_cast<uint4*>(p.dqkv_lo + offq) = make_uint4(0u, 0u, 0u, 0u);
     }
     // dK / dV: accumulators hold row = feature 16id + 4g + e, col = key 16j + r -> 8-B (4 x bf16) stores along d  (as k_attn_bwd_dkv)
     float4 ckc[ND], cvc[ND];   // (from the LDS copy the prologue made: a global load here is a full round trip with nothing to hide it)
@@ -1248,27 +1272,37 @@ bool attn_bwd_is_fused(int T, int H, int D, bool codes) {
 
 int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B, int T, int H, int D, const void* O_hi, const void* O_lo,
                     const float* lse, float* delta, const float* dO, void* dqkv_hi, void* dqkv_lo, const float* col_scale, hipStream_t st,
-                    const void* codes, const void* cmask, const float* o16_mul, uint32_t* o16_amax) {
+                    const void* codes, const void* cmask, const float* o16_mul, uint32_t* o16_amax, int live_q_tiles, bool dO_cls) {
     if ((codes != nullptr) != (cmask != nullptr)) { set_error("attention backward: codes / cmask go together"); return 1; }
+    if (live_q_tiles < 0) { set_error("attention backward: live_q_tiles %d", live_q_tiles); return 1; }
     AttnArgs a{qkv, qp, qmin, qmax, B, T, H, D, 1.0f / sqrtf((float)(D / H)), reinterpret_cast<__bf16*>(const_cast<void*>(O_hi)),
                reinterpret_cast<__bf16*>(const_cast<void*>(O_lo)), const_cast<float*>(lse), delta, dO, reinterpret_cast<__bf16*>(dqkv_hi),
                reinterpret_cast<__bf16*>(dqkv_lo), col_scale, nullptr, nullptr, nullptr,
-               reinterpret_cast<uint8_t*>(const_cast<void*>(codes)), reinterpret_cast<uint8_t*>(const_cast<void*>(cmask)), o16_mul, o16_amax};
+               reinterpret_cast<uint8_t*>(const_cast<void*>(codes)), reinterpret_cast<uint8_t*>(const_cast<void*>(cmask)), o16_mul, o16_amax,
+               live_q_tiles, dO_cls ? 1 : 0};
     // one fused kernel (dK, dV and dQ from one sweep) where its shape holds: head_dim 64, 33..224 tokens, saved codes; QATVIT_ATTN_BWD_FUSED=0: the
     // two-kernel form (k_attn_bwd_dq + k_attn_bwd_dkv) everything else takes
     int nkt;
     if (check_shape(T, D, H, &nkt)) return 1;
     if (attn_bwd_is_fused(T, H, D, codes != nullptr)) {
         constexpr int kLds = 4 * 14 * 16 * 64 * 2 + 2 * 2 * 14 * 16 * kSRow + 2 * 14 * 16 * 4 + 3 * 14 * 16 * 8 + 3 * 64 * 4;   // 151,296 B
-        static bool once = (allow_lds(k_attn_bwd_fused<14>, kLds), allow_lds(k_attn_bwd_fused<14, true>, kLds), true);
+        static bool once = (allow_lds(k_attn_bwd_fused<14>, kLds), allow_lds(k_attn_bwd_fused<14, true>, kLds), allow_lds(k_attn_bwd_fused<14, false, true>, kLds),
+                            allow_lds(k_attn_bwd_fused<14, true, true>, kLds), true);
         (void)once;
+        if (dO_cls && live_q_tiles < 1) { set_error("attention backward: the [B, D] form of dO needs live_q_tiles >= 1"); return 1; }
+        const bool live = live_q_tiles > 0;
         if (o16_mul) {
             if (!o16_amax) { set_error("attention backward: o16_mul needs o16_amax"); return 1; }
-            k_attn_bwd_fused<14, true><<<B * H, 8 * 64, kLds, st>>>(a);
-        } else k_attn_bwd_fused<14><<<B * H, 8 * 64, kLds, st>>>(a);
+            if (live) k_attn_bwd_fused<14, true, true><<<B * H, 8 * 64, kLds, st>>>(a);
+            else k_attn_bwd_fused<14, true><<<B * H, 8 * 64, kLds, st>>>(a);
+        } else if (live) k_attn_bwd_fused<14, false, true><<<B * H, 8 * 64, kLds, st>>>(a);
+        else k_attn_bwd_fused<14><<<B * H, 8 * 64, kLds, st>>>(a);
         return 0;
     }
     if (o16_mul) { set_error("attention backward: the one-plane output exists in the fused kernel only (head_dim 64, 33..224 tokens, saved codes)"); return 1; }
+    // (live_q_tiles is a licence to skip, not a request: the two-kernel form runs every query - on a full dO)
+    if (dO_cls) { set_error("attention backward: the [B, D] form of dO exists in the fused kernel only (head_dim 64, 33..224 tokens, saved codes)"); return 1; }
+    a.live_q_tiles = 0;
     if (dispatch(1, a, st)) return 1;
     return dispatch(2, a, st);
 }

@@ -24,7 +24,8 @@ static bool knob(const char* name) {
 const Knobs& knobs() {
     static const Knobs k{knob("QATVIT_I8"), knob("QATVIT_F16"), knob("QATVIT_FC2_CODES"), knob("QATVIT_FC1_BITS"), knob("QATVIT_FC2W_CODES"),
                          knob("QATVIT_WBATCH"), knob("QATVIT_ATTN_CODES"), knob("QATVIT_QKV_2PASS"), knob("QATVIT_LNB_FUSE"), knob("QATVIT_QP_LATE"),
-                         knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP"), knob("QATVIT_LN_STRIP")};
+                         knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP"), knob("QATVIT_LN_STRIP"),
+                         knob("QATVIT_CLS_BWD")};
     return k;
 }
 }  // namespace qv
@@ -332,6 +333,18 @@ int qatvit_attn_backward(const float* qkv, const float* qp, int32_t qmin, int32_
     return 0;
 }
 
+int qatvit_attn_backward_live(const float* qkv, const float* qp, int32_t qmin, int32_t qmax, int32_t B, int32_t T, int32_t H, int32_t D,
+                              const void* O_hi, const void* O_lo, const float* lse, float* delta, const float* dO, void* dqkv_hi, void* dqkv_lo,
+                              const float* col_scale, const void* qkv_codes, const void* qkv_mask, int32_t live_q_tiles, int32_t dO_cls, void* stream) {
+    QV_CHECK_ARG((qkv || qkv_codes) && qp && O_hi && O_lo && lse && delta && dO && dqkv_hi && dqkv_lo, "qatvit_attn_backward_live: null pointer argument");
+    QV_CHECK_ARG(live_q_tiles >= 0 && (!dO_cls || live_q_tiles >= 1), "qatvit_attn_backward_live: live_q_tiles %d (>= 0; >= 1 with the [B, D] form of dO)", live_q_tiles);
+    if (launch_attn_bwd(qkv, qp, qmin, qmax, B, T, H, D, O_hi, O_lo, lse, delta, dO, dqkv_hi, dqkv_lo, col_scale, (hipStream_t)stream, qkv_codes, qkv_mask, nullptr,
+                        nullptr, live_q_tiles, dO_cls != 0))
+        return 1;
+    QV_CHECK_LAUNCH("qatvit_attn_backward_live");
+    return 0;
+}
+
 int qatvit_eval_accumulate(const void* logits, int32_t dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes, const float* other,
                            int64_t other_ld, const int64_t* other_index, int64_t other_rows, void* state, int64_t* confusion, void* stream) {
     static_assert(sizeof(EvalState) == 8 * QATVIT_EVAL_STATE_WORDS, "QATVIT_EVAL_STATE_WORDS mirrors EvalState");
@@ -413,6 +426,22 @@ int qatvit_image_batch_mix(const uint8_t* data, const int64_t* index, int32_t B,
     // the shape's LDS request is checked here, before any HIP call
     if (launch_image_batch_mix(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, out, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_image_batch_mix");
+    return 0;
+}
+
+int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {
+    RowMoveTab t;
+    t.n = 1; t.m[0] = RowMove{tall, compact, stride, width};
+    if (launch_rows_gather(t, rows, T, (hipStream_t)stream)) return 1;
+    QV_CHECK_LAUNCH("qatvit_rows_gather");
+    return 0;
+}
+
+int qatvit_rows_scatter(const void* compact, void* tall, int32_t rows, int32_t T, int32_t width, void* stream) {
+    RowMoveTab t;
+    t.n = 1; t.m[0] = RowMove{compact, tall, width, width};
+    if (launch_rows_scatter(t, rows, T, (hipStream_t)stream)) return 1;
+    QV_CHECK_LAUNCH("qatvit_rows_scatter");
     return 0;
 }
 

@@ -10,6 +10,8 @@
 // Row kernels: one wave per row, 16 B per lane per load; all are single-pass over HBM.
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "qv_common.h"
 #include "qv_device.h"
 #include "qv_kernels.h"
@@ -748,9 +750,9 @@ int launch_mask_bwd(int gelu_bwd, const float* d, const float* Y, const float* q
 
 int launch_ln_bwd_fq(int acc, const float* dH, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                      const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T,
-                     int cls_only, hipStream_t st, const LnBwdNext* next) {
+                     int cls_only, hipStream_t st, const LnBwdNext* next, int rows_per_wave) {
     if (D % 4 != 0 || D > 256 * kMaxV) { set_error("ln_bwd_fq: D=%d unsupported", D); return 1; }
-    constexpr int rpw = 16;   // rows per wave (8 waves per block): fewer blocks = fewer same-address dgamma/dbeta atomics (12 ns each, serialised)
+    const int rpw = rows_per_wave > 0 ? rows_per_wave : 16;   // rows per wave (8 waves per block): fewer blocks = fewer same-address dgamma/dbeta atomics (12 ns each, serialised)
     int grid = (int)((M + 8 * rpw - 1) / (8 * rpw));
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
@@ -809,6 +811,62 @@ __global__ void k_zero_i32(int32_t* p, int64_t n) {
 // (a kernel, not hipMemsetAsync: the memset node of a captured hipGraph did not re-zero the buffer on replay)
 int launch_zero_i32(int32_t* p, int64_t n, hipStream_t st) {
     k_zero_i32<<<(int)cdiv(n, 256) > 1024 ? 1024 : (int)cdiv(n, 256), 256, 0, st>>>(p, n);
+    return 0;
+}
+// ---------------------------------------------------------------- the class-token rows of [B * T, .] tensors (the last block's backward on B rows)
+// blockIdx.y = the tensor; 4-byte words, so that one kernel moves a row statistic (4 B), a mask-bit row and a 1536-float row alike
+__global__ __launch_bounds__(256) void k_rows_gather(const RowMoveTab t, int rows, int T) {
+    const RowMove m = t.m[blockIdx.y];
+    const int wpr = m.width / 4;
+    const int64_t tall = (int64_t)T * (m.stride / 4);   // words between two gathered rows
+    const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(m.src);
+    uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(m.dst);
+    const int total = rows * wpr;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int b = i / wpr, j = i - b * wpr;
+        dst[i] = src[b * tall + j];
+    }
+}
+// every 16-byte chunk of the tall tensor is written exactly once: streaming stores at the rate of a fill
+__global__ __launch_bounds__(256) void k_rows_scatter(const RowMoveTab t, int rows, int T) {
+    const RowMove m = t.m[blockIdx.y];
+    const int cpr = m.width / 16;
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(m.src);
+    uint4* __restrict__ dst = reinterpret_cast<uint4*>(m.dst);
+    const int total = rows * T * cpr;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int row = i / cpr, c = i - row * cpr;
+        const int b = row / T;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (row - b * T == 0) v = src[b * cpr + c];
+        dst[i] = v;
+    }
+}
+static int rows_check(const char* who, const RowMoveTab& t, int rows, int T, bool scatter) {
+    if (t.n < 1 || t.n > kRowMoveMax || rows < 1 || T < 1) { set_error("%s: %d tensors, %d rows, T=%d", who, t.n, rows, T); return 1; }
+    for (int k = 0; k < t.n; ++k) {
+        const RowMove& m = t.m[k];
+        const int unit = scatter ? 16 : 4;
+        const bool ok = m.src && m.dst && m.width >= unit && m.width % unit == 0 && m.stride % unit == 0 && (scatter ? m.stride == m.width : m.stride >= m.width) &&
+                        (int64_t)rows * (scatter ? T : 1) * (m.width / unit) < (1ll << 31) &&
+                        (reinterpret_cast<uintptr_t>(m.src) | reinterpret_cast<uintptr_t>(m.dst)) % unit == 0;
+        if (!ok) { set_error("%s: tensor %d: width %d, stride %lld (bytes; need %% %d == 0%s, aligned bases, < 2^31 units)", who, k, m.width, (long long)m.stride, unit,
+                             scatter ? " and stride == width" : ""); return 1; }
+    }
+    return 0;
+}
+int launch_rows_gather(const RowMoveTab& t, int rows, int T, hipStream_t st) {
+    if (rows_check("rows_gather", t, rows, T, false)) return 1;
+    int64_t most = 0;
+    for (int k = 0; k < t.n; ++k) most = std::max<int64_t>(most, (int64_t)rows * (t.m[k].width / 4));
+    k_rows_gather<<<dim3(std::min(cdiv(most, 256), 512), t.n), 256, 0, st>>>(t, rows, T);
+    return 0;
+}
+int launch_rows_scatter(const RowMoveTab& t, int rows, int T, hipStream_t st) {
+    if (rows_check("rows_scatter", t, rows, T, true)) return 1;
+    int64_t most = 0;
+    for (int k = 0; k < t.n; ++k) most = std::max<int64_t>(most, (int64_t)rows * T * (t.m[k].width / 16));
+    k_rows_scatter<<<dim3(std::min(cdiv(most, 256 * 4), 4096), t.n), 256, 0, st>>>(t, rows, T);
     return 0;
 }
 int launch_w_quant_all(WQuantTab& t, hipStream_t st) {

@@ -83,6 +83,7 @@ struct Forms {
     bool tn_stream;          // the per-block gradient planes + stream-K scratch exist (the one-plane weight gradients then run at the end of the call)
     bool dy16;               // the one-plane backward covers this configuration
     bool ln_in_strip;        // norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln) where the forward writes the byte plane only (ln_in_strip_of)
+    bool cls_bwd;            // the one-plane backward of the final norm and of the last block's MLP + proj on the B class-token rows (Plan::ClsRows; bwd() decides per call)
 };
 static Forms forms_of(const qatvit_cfg& c, const Dims& d) {
     const Knobs& k = knobs();
@@ -104,6 +105,7 @@ static Forms forms_of(const qatvit_cfg& c, const Dims& d) {
     f.tn_stream = k.tn_stream && d.D % 384 == 0 && d.Hd % 384 == 0;
     f.dy16 = f.i8 && f.w_batched && d.D % 384 == 0 && d.Hd % 384 == 0 && f.qkv_2pass && f.attn_bwd_fused && f.f16_proj && f.fc2w_codes;
     f.ln_in_strip = k.ln_strip && f.i8 && f.late && f.x_plane_from_q8;
+    f.cls_bwd = k.cls_bwd && f.dy16;
     return f;
 }
 
@@ -124,6 +126,14 @@ struct Plan {
     int64_t dyp, dyp_stride, dyp_p, dyp_h, dyp_q, tn_stream;
     int64_t qp_staged;   // staging records of the late-resolved quantizers (qv_kernels.h QpLate): kQpStagedWords words per activation quantizer
     int64_t dy16;   // scale state of the one-plane backward (dy16.hip): 4 slots per block - the gradients entering fc2, fc1, proj, qkv
+    // The class-token rows ([B, .] instead of [B * T, .]; Forms::cls_bwd, else absent): what the final norm's backward leaves for the last block (dx, dY - they
+    // outlive the call: a staged backward runs stage 0 and stage 1 in different calls), that block's gathered forward operands, and its gradients on those rows
+    struct ClsRows {
+        int64_t dx, dY;                                             // d loss / d x_in[depth] fp32; its masked fc2-in plane fp16
+        int64_t xF, meanF, rstdF, m2;                               // final norm: x_in[depth], row statistics, fc2's mask bits
+        int64_t G8, Y1m, h2q, x_mid, mean2, rstd2, mproj, O16;      // last block (h2q: the int8 plane q - center, or the fp16 one where the weight gradient reads that)
+        int64_t dY1, dYp, dxB, dO, dH;                              // fc1-out / proj-in planes fp16; d x_mid, d attention output, the unfused dgrad's output fp32
+    } cls;
     int64_t total, stats_words;
     int TP;
 };
@@ -221,6 +231,16 @@ static int make_plan(const qatvit_cfg& c, Plan* p) {
         p->dyp_stride = p->dyp_q + al(M * 3 * D * 2);
         p->dyp = take(p->dyp_stride * d.depth);
         p->tn_stream = take(tn_stream_scratch_bytes());
+    }
+    p->cls = Plan::ClsRows{};
+    if (p->form.cls_bwd) {   // (behind everything else: no other offset depends on the knob)
+        const int64_t B = d.B, mrow = ln_maskbits_bytes(1, (int)D);
+        Plan::ClsRows& r = p->cls;
+        r.dx = take(B * D * 4); r.dY = take(B * D * 2);
+        r.xF = take(B * D * 4); r.meanF = take(B * 4); r.rstdF = take(B * 4); r.m2 = take(B * mrow);
+        r.G8 = take(B * Hd); r.Y1m = take(B * Hd / 8); r.h2q = take(B * D * 2); r.x_mid = take(B * D * 4); r.mean2 = take(B * 4); r.rstd2 = take(B * 4);
+        r.mproj = take(B * mrow); r.O16 = take(B * D * 2);
+        r.dY1 = take(B * Hd * 2); r.dYp = take(B * D * 2); r.dxB = take(B * D * 4); r.dO = take(B * D * 4); r.dH = take(B * D * 4);
     }
     p->total = o;
     return 0;
@@ -765,6 +785,10 @@ struct Bwd {
     void* const* grads;
     bool dy, cal;
     bool stream;   // deferred weight gradients (k_tn_stream): every block's gradient planes stay in the workspace, the GEMMs are collected here and run at the end of the call
+    // The student pools the class token: the gradient entering the last block is zero outside the B rows b * T, a zero row of a dgrad operand gives a zero output
+    // row and adds nothing to a weight gradient.  One-plane form with Forms::cls_bwd: head() leaves dx and the masked fc2-in plane as [B, .] (Plan::ClsRows),
+    // and the last block - unless its input gradient was injected, which arrives as the full dxA - runs its MLP and proj backward on those B rows
+    bool cls;
     float* dxA;    // the gradient w.r.t. the current block's OUTPUT at stage entry
     float* dxB;    // ... w.r.t. x_mid inside a block
     std::vector<TNGemm> sg[3];   // by TNForm: kTNPlaneQ8, kTNPlaneCodes, kTNPlaneF16
@@ -815,6 +839,20 @@ int Bwd::head(const float* dlogits) {
     launch_head_bwd(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), c.act_qmin, c.act_qmax, x.at<float>(p.hq), x.act_qp(x.a_norm()),
                     x.at<void>(p.w_off[wh]), x.prm(base + 2), x.wfq[wh].scale, x.wfq[wh].zero_point, c.w_per_channel, c.w_qmin, c.w_qmax,
                     G(base + 2), G(base + 3), x.at<float>(p.dh), d.B, d.D, d.C, x.st);
+    if (cls) {   // the same kernel on the gathered class-token rows ([B, D], T = 1): the same bits in those rows, and neither the full dxA nor the full plane is written
+        const Plan::ClsRows& r = p.cls;
+        const int64_t mrow = ln_maskbits_bytes(1, d.D);
+        RowMoveTab t;
+        t.n = 4;
+        t.m[0] = RowMove{x.blk<void>(p.x_in, d.depth), x.at<void>(r.xF), (int64_t)d.D * 4, d.D * 4};
+        t.m[1] = RowMove{x.at<void>(p.meanF), x.at<void>(r.meanF), 4, 4};
+        t.m[2] = RowMove{x.at<void>(p.rstdF), x.at<void>(r.rstdF), 4, 4};
+        t.m[3] = RowMove{x.blk<void>(p.m2, last), x.at<void>(r.m2), mrow, (int)mrow};
+        if (launch_rows_gather(t, d.B, d.T, x.st)) return 1;
+        const LnBwdNext nx{x.at<void>(r.m2), x.dy_colscale(x.widx(last, WB_FC2)), x.at<void>(r.dY), nullptr, x.dy_mul(last, DS_FC2), x.dy_slot(last, DS_FC2)};
+        return launch_ln_bwd_fq(0, x.at<float>(p.dh), x.at<float>(r.xF), x.at<float>(r.meanF), x.at<float>(r.rstdF), x.prm(base), x.prm(base + 1), x.act_qp(x.a_norm()),
+                                c.act_qmin, c.act_qmax, nullptr, x.at<float>(r.dx), G(base), G(base + 1), d.B, d.D, 1, 0, x.st, &nx, 1);
+    }
     LnBwdNext nx{x.blk<void>(p.m2, last), x.dy_colscale(x.widx(last, WB_FC2)), plane(last, 0), x.at<void>(p.dYs_lo)};
     if (dy) { nx.o16_mul = x.dy_mul(last, DS_FC2); nx.o16_amax = x.dy_slot(last, DS_FC2); }
     if (launch_ln_bwd_fq(0, x.at<float>(p.dh), x.blk<float>(p.x_in, d.depth), x.at<float>(p.meanF), x.at<float>(p.rstdF), x.prm(base), x.prm(base + 1),
@@ -833,69 +871,113 @@ int Bwd::block_one_plane(int i, bool injected) {
     hipStream_t st = x.st;
     const int qa = c.act_qmin, qb = c.act_qmax;
     const int M = (int)d.M;
-    void* dY16 = plane(i, 0);      // the masked gradient entering fc2
-    void* dYp16 = plane(i, 1);     // ... entering proj (the same buffer as dY16 unless the weight gradients are deferred)
-    void* dY1_16 = plane(i, 2);
+    // the MLP and proj part of the last block on the class-token rows (Bwd::cls): the same launchers over Mr = B rows of gathered operands; its three weight
+    // gradients run right here (the deferred batch shares ONE token count); dxB goes back to full height, zeros elsewhere, for the qkv dgrad, and the attention
+    // backward reads dO as [B, D] and sweeps the live query pair alone (dK, dV and the rest of the block are dense: every key and value reaches the class token)
+    const bool rows = cls && i == d.depth - 1 && !injected;
+    const Plan::ClsRows& cr = p.cls;
+    const int Mr = rows ? d.B : M;
+    void* dY16 = rows ? x.at<void>(cr.dY) : plane(i, 0);      // the masked gradient entering fc2
+    void* dYp16 = rows ? x.at<void>(cr.dYp) : plane(i, 1);    // ... entering proj (the same buffer as dY16 unless the weight gradients are deferred)
+    void* dY1_16 = rows ? x.at<void>(cr.dY1) : plane(i, 2);
     void* dqkv16 = plane(i, 3);
+    const void* G8 = rows ? x.at<void>(cr.G8) : x.blk<void>(p.G8, i);
+    const void* Y1m = rows ? x.at<void>(cr.Y1m) : x.blk<void>(p.Y1m, i);
+    const void* h2q = rows ? x.at<void>(cr.h2q) : x.blk<void>(p.h2q, i);      // (rows: ONE buffer holds whichever plane the fc1 weight gradient reads)
+    const void* h2q8 = rows ? x.at<void>(cr.h2q) : x.blk<void>(p.h2q8, i);
+    const void* O16 = rows ? x.at<void>(cr.O16) : x.blk<void>(p.O16_hi, i);
+    const float* x_mid = rows ? x.at<float>(cr.x_mid) : x.blk<float>(p.x_mid, i);
+    const float* mean2 = rows ? x.at<float>(cr.mean2) : x.blk<float>(p.mean2, i);
+    const float* rstd2 = rows ? x.at<float>(cr.rstd2) : x.blk<float>(p.rstd2, i);
+    const void* mproj = rows ? x.at<void>(cr.mproj) : x.blk<void>(p.mproj, i);
+    const float* dx_mlp = rows ? x.at<float>(cr.dx) : dxA;                     // the gradient w.r.t. the block's output
+    float* dxB_mlp = rows ? x.at<float>(cr.dxB) : dxB;
+    float* dO_proj = rows ? x.at<float>(cr.dO) : x.at<float>(p.dO);
+    float* dH_mlp = rows ? x.at<float>(cr.dH) : x.at<float>(p.dH);
     const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
     float* const scal16 = x.blk<float>(p.scal16, i);
     auto wscale1 = [&](int wi) { return c.w_per_channel ? nullptr : x.wfq[wi].scale; };
+    if (rows) {
+        const int64_t mrow = ln_maskbits_bytes(1, d.D);
+        const bool q8 = F.x_plane_from_q8;
+        RowMoveTab t;
+        t.n = 8;
+        t.m[0] = RowMove{x.blk<void>(p.G8, i), x.at<void>(cr.G8), d.Hd, d.Hd};
+        t.m[1] = RowMove{x.blk<void>(p.Y1m, i), x.at<void>(cr.Y1m), d.Hd / 8, d.Hd / 8};
+        t.m[2] = RowMove{q8 ? x.blk<void>(p.h2q8, i) : x.blk<void>(p.h2q, i), x.at<void>(cr.h2q), q8 ? d.D : d.D * 2, q8 ? d.D : d.D * 2};
+        t.m[3] = RowMove{x.blk<void>(p.x_mid, i), x.at<void>(cr.x_mid), (int64_t)d.D * 4, d.D * 4};
+        t.m[4] = RowMove{x.blk<void>(p.mean2, i), x.at<void>(cr.mean2), 4, 4};
+        t.m[5] = RowMove{x.blk<void>(p.rstd2, i), x.at<void>(cr.rstd2), 4, 4};
+        t.m[6] = RowMove{x.blk<void>(p.mproj, i), x.at<void>(cr.mproj), mrow, (int)mrow};
+        t.m[7] = RowMove{x.blk<void>(p.O16_hi, i), x.at<void>(cr.O16), (int64_t)d.D * 2, d.D * 2};
+        if (launch_rows_gather(t, d.B, d.T, st)) return 1;
+    }
     // wgrad of layer wi from the plane P16 (slot k): X as fp16 (grid integers; proj: the attention output rounded to fp16 like dY itself: one pass), or codes + a table
     // of fp16 pairs (X8: the same grid integers as q - center, one byte each - the forward's int8 operand; taken instead of the fp16 plane where k_gemm_tn_q8 applies)
-    auto wgrad16 = [&](const void* P16, int k, int wi, const void* X, const void* Xc, const uint32_t* lut, const float* s_x, float* dW, float* db,
+    // (Mw token rows: M, or Mr for the MLP / proj part)
+    auto wgrad16 = [&](int Mw, const void* P16, int k, int wi, const void* X, const void* Xc, const uint32_t* lut, const float* s_x, float* dW, float* db,
                        const void* X8 = nullptr) -> int {
         const TNForm form = (X8 && F.x_plane_from_q8) ? kTNPlaneQ8 : Xc ? kTNPlaneCodes : kTNPlaneF16;
         TNGemm g = x.wgrad_request(wi, dW, db);
         g.P = P16; g.Q = form == kTNPlaneQ8 ? X8 : Xc ? Xc : X; g.lut = lut; g.s1 = s_x; g.s2 = x.dy_inv(i, k);
-        const double flops = 2.0 * M * g.N * g.Kw;
-        if (stream) {   // collected: one persistent launch per X form at the end of the call
+        const double flops = 2.0 * Mw * g.N * g.Kw;
+        if (stream && Mw == M) {   // collected (M != Mr on class-token rows: T > 1): one persistent launch per X form at the end of the call
             sg[form].push_back(g);
             sflops[form] += flops;
             return 0;
         }
         ProfScope ps(x.prof, (wi == w_proj || Xc) ? 6 : 3, flops, st);
-        return launch_gemm_tn(form, g, x.wgrad_call(M), st);
+        TNCall call = x.wgrad_call(Mw);
+        call.reduce_single = rows && Mw == Mr;   // (B rows: the kernel's serial tail would be the run time)
+        return launch_gemm_tn(form, g, call, st);
     };
-    auto dgrad16 = [&](const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
+    auto dgrad16 = [&](int Md, const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
         int N, K; wshape(d, wi, &N, &K);
-        ProfScope ps(x.prof, prof_kind_dgrad(post), 2.0 * M * N * K, st);
-        return launch_gemm_nt_dy16(P16, x.wT16(wi), dX, M, K, N, N, N, K, wscale1(wi), x.dy_inv(i, k), st, post);
+        ProfScope ps(x.prof, prof_kind_dgrad(post), 2.0 * Md * N * K, st);
+        return launch_gemm_nt_dy16(P16, x.wT16(wi), dX, Md, K, N, N, N, K, wscale1(wi), x.dy_inv(i, k), st, post);
     };
     // ---- MLP branch
     if (injected)
         launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, dY16, nullptr, d.M * d.D, st,
                         x.dy_mul(i, DS_FC2), x.dy_slot(i, DS_FC2));
-    if (wgrad16(dY16, DS_FC2, w_fc2, nullptr, x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glut, i), scal16 + 1, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
+    if (wgrad16(Mr, dY16, DS_FC2, w_fc2, nullptr, G8, x.blk<uint32_t>(p.glut, i), scal16 + 1, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
     {   // fc2 dgrad + GELU backward + fc1's STE mask -> the fc1 output gradient, one plane
         NTPost post = gelu_post(i, dY1_16, nullptr);
+        post.code8 = G8; post.code_mask = Y1m;
         post.o16_mul = x.dy_mul(i, DS_FC1); post.o16_amax = x.dy_slot(i, DS_FC1);
         bool strip = false;
         if (x.wT16f_ok(w_fc2) && knobs().f16_strip) {   // the A-stationary strip form (f16strip.hip): the gradient plane fetched once for all four column tiles
-            ProfScope ps(x.prof, 5, 2.0 * M * d.D * d.Hd, st);
-            strip = launch_f16_strip_gelu_bwd(dY16, x.wT16f(w_fc2), nullptr, M, d.Hd, d.D, d.D, d.Hd, wscale1(w_fc2), x.dy_inv(i, DS_FC2), st, &post);
+            ProfScope ps(x.prof, 5, 2.0 * Mr * d.D * d.Hd, st);
+            strip = launch_f16_strip_gelu_bwd(dY16, x.wT16f(w_fc2), nullptr, Mr, d.Hd, d.D, d.D, d.Hd, wscale1(w_fc2), x.dy_inv(i, DS_FC2), st, &post);
         }
-        if (!strip && dgrad16(dY16, DS_FC2, w_fc2, nullptr, &post)) return 1;
+        if (!strip && dgrad16(Mr, dY16, DS_FC2, w_fc2, nullptr, &post)) return 1;
     }
-    if (wgrad16(dY1_16, DS_FC1, w_fc1, x.blk<void>(p.h2q, i), nullptr, nullptr, x.act_qp(x.aidx(i, AB_N2)), BG(i, B_FC1W), BG(i, B_FC1B), x.blk<void>(p.h2q8, i)))
-        return 1;
-    const LnBwdNext nx_proj{x.blk<void>(p.mproj, i), x.dy_colscale(w_proj), dYp16, nullptr, x.dy_mul(i, DS_PROJ), x.dy_slot(i, DS_PROJ)};
-    if (F.lnb) {
+    if (wgrad16(Mr, dY1_16, DS_FC1, w_fc1, h2q, nullptr, nullptr, x.act_qp(x.aidx(i, AB_N2)), BG(i, B_FC1W), BG(i, B_FC1B), h2q8)) return 1;
+    const LnBwdNext nx_proj{mproj, x.dy_colscale(w_proj), dYp16, nullptr, x.dy_mul(i, DS_PROJ), x.dy_slot(i, DS_PROJ)};
+    if (F.lnb && !rows) {
         const NTPost post = lnb_post(i, true, dxA, nx_proj);
-        if (dgrad16(dY1_16, DS_FC1, w_fc1, dxB, &post)) return 1;
-    } else {
-        if (dgrad16(dY1_16, DS_FC1, w_fc1, x.at<float>(p.dH), nullptr)) return 1;
-        if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_mid, i), x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W),
-                             x.bprm(i, B_N2B), x.act_qp(x.aidx(i, AB_N2)), qa, qb, dxA, dxB, BG(i, B_N2W), BG(i, B_N2B), d.M, d.D, d.T, 0, st, &nx_proj))
+        if (dgrad16(M, dY1_16, DS_FC1, w_fc1, dxB, &post)) return 1;
+    } else {   // (B rows: two tiles of the fused epilogue, one wave per row in sequence, take 70 us; the plain dgrad and k_ln_bwd_fq with one row per wave a third of it)
+        if (dgrad16(Mr, dY1_16, DS_FC1, w_fc1, dH_mlp, nullptr)) return 1;
+        if (launch_ln_bwd_fq(1, dH_mlp, x_mid, mean2, rstd2, x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.act_qp(x.aidx(i, AB_N2)), qa, qb, dx_mlp, dxB_mlp, BG(i, B_N2W),
+                             BG(i, B_N2B), Mr, d.D, d.T, 0, st, &nx_proj, rows ? 1 : 16))
             return 1;
     }
     // ---- attention branch (dxB = gradient w.r.t. x_mid)
-    if (wgrad16(dYp16, DS_PROJ, w_proj, x.blk<void>(p.O16_hi, i), nullptr, nullptr, scal16, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
-    if (dgrad16(dYp16, DS_PROJ, w_proj, x.at<float>(p.dO), nullptr)) return 1;
+    if (wgrad16(Mr, dYp16, DS_PROJ, w_proj, O16, nullptr, nullptr, scal16, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
+    if (dgrad16(Mr, dYp16, DS_PROJ, w_proj, dO_proj, nullptr)) return 1;
+    if (rows) {   // back to full height, zeros elsewhere, for the qkv dgrad's LayerNorm-1 epilogue (its dx_in): ONE streaming pass
+        RowMoveTab t;
+        t.n = 1;
+        t.m[0] = RowMove{dxB_mlp, dxB, (int64_t)d.D * 4, d.D * 4};
+        if (launch_rows_scatter(t, d.B, d.T, st)) return 1;
+    }
+    // (rows: dO stays [B, D] - only query row 0 of every image carries a gradient, so the fused kernel sweeps the one query pair that holds it)
     if (launch_attn_bwd(nullptr, x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i),
-                        x.at<float>(p.delta), x.at<float>(p.dO), dqkv16, nullptr, x.dy_colscale(w_qkv), st, x.blk<void>(p.qkv8, i), x.blk<void>(p.qkvm, i),
-                        x.dy_mul(i, DS_QKV), x.dy_slot(i, DS_QKV)))
+                        x.at<float>(p.delta), dO_proj, dqkv16, nullptr, x.dy_colscale(w_qkv), st, x.blk<void>(p.qkv8, i), x.blk<void>(p.qkvm, i),
+                        x.dy_mul(i, DS_QKV), x.dy_slot(i, DS_QKV), rows ? 1 : 0, rows))
         return 1;
-    if (wgrad16(dqkv16, DS_QKV, w_qkv, x.blk<void>(p.h1q, i), nullptr, nullptr, x.act_qp(x.aidx(i, AB_N1)), BG(i, B_QKVW), BG(i, B_QKVB), x.blk<void>(p.h1q8, i)))
+    if (wgrad16(M, dqkv16, DS_QKV, w_qkv, x.blk<void>(p.h1q, i), nullptr, nullptr, x.act_qp(x.aidx(i, AB_N1)), BG(i, B_QKVW), BG(i, B_QKVB), x.blk<void>(p.h1q8, i)))
         return 1;
     // the next block's fc2-in plane (its own buffer when the weight gradients are deferred).  Block 0 emits no next-branch gradient; the fused epilogue still
     // wants a scale / maximum target: its own qkv slot, which nothing reads afterwards
@@ -904,9 +986,9 @@ int Bwd::block_one_plane(int i, bool injected) {
                                    : LnBwdNext{nullptr, nullptr, nullptr, nullptr, x.dy_mul(0, DS_QKV), x.dy_slot(0, DS_QKV)};
     if (F.lnb) {
         const NTPost post = lnb_post(i, false, dxB, nx_fc2);
-        return dgrad16(dqkv16, DS_QKV, w_qkv, dxA, &post);
+        return dgrad16(M, dqkv16, DS_QKV, w_qkv, dxA, &post);
     }
-    if (dgrad16(dqkv16, DS_QKV, w_qkv, x.at<float>(p.dH), nullptr)) return 1;
+    if (dgrad16(M, dqkv16, DS_QKV, w_qkv, x.at<float>(p.dH), nullptr)) return 1;
     return launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_in, i), x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B),
                             x.act_qp(x.aidx(i, AB_N1)), qa, qb, dxB, dxA, BG(i, B_N1W), BG(i, B_N1B), d.M, d.D, d.T, 0, st, i > 0 ? &nx_fc2 : nullptr);
 }
@@ -1003,7 +1085,7 @@ static int bwd(const Ctx& x, const float* dlogits, void* const* grads, int stage
     const bool dy = (x.flags & QATVIT_BWD_DY16) != 0, cal = (x.flags & QATVIT_BWD_CALIBRATE) != 0;
     if (dy && cal) { set_error("student backward: QATVIT_BWD_DY16 and QATVIT_BWD_CALIBRATE exclude each other"); return 1; }
     if ((dy || cal) && !F.dy16) { set_error("student backward: the one-plane form does not cover this configuration (qatvit_student_dy16_supported)"); return 1; }
-    Bwd b{x, grads, dy, cal, dy && F.tn_stream && F.x_plane_from_q8, x.at<float>(x.p.dxA), x.at<float>(x.p.dxB)};
+    Bwd b{x, grads, dy, cal, dy && F.tn_stream && F.x_plane_from_q8, dy && F.cls_bwd, x.at<float>(x.p.dxA), x.at<float>(x.p.dxB)};
     uint32_t* const dystate = x.at<uint32_t>(x.p.dy16);
     const int nslots = DS_COUNT * d.depth;
     if ((dy || cal) && (stage_from == 0 || inject)) launch_dy16_begin(dystate, nslots, stage_from == 0 ? dlogits : nullptr, d.B * d.C, x.st);

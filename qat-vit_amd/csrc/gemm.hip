@@ -1963,7 +1963,7 @@ static TNArgs tn_args(TNForm form, const TNGemm& g, const TNCall& call) {
 static int tn_launch(void (*kernel)(const TNArgs), size_t lds, TNArgs& a, int splits, int WM, int WNK, int TM, int TNT, const TNCall& call, hipStream_t st) {
     const int grid = a.tiles * splits;
     const int64_t tile_f4 = (int64_t)WM * WNK * TM * TNT * 64;
-    const bool two_phase = call.scratch && splits > 1 && (int64_t)grid * tile_f4 * 16 <= call.scratch_bytes;
+    const bool two_phase = call.scratch && (splits > 1 || call.reduce_single) && (int64_t)grid * tile_f4 * 16 <= call.scratch_bytes;
     a.partial = two_phase ? call.scratch : nullptr;
     kernel<<<grid, WM * WNK * 64, lds, st>>>(a);
     if (two_phase) k_tn_reduce<<<(int)cdiv((int64_t)a.tiles * tile_f4, 256), 256, 0, st>>>(a, splits, WM, WNK, TM, TNT);

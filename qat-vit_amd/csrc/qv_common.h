@@ -30,6 +30,7 @@ struct Knobs {
     bool f16_strip;       // QATVIT_F16_STRIP: the one-plane fc2 dgrad on the A-stationary strip kernel; 0: the general tall tile
     bool i8_strip;        // QATVIT_I8_STRIP: the K = 384 / 768 int8 GEMMs on the A-stationary strip kernel; 0: the general tall kernel
     bool ln_strip;        // QATVIT_LN_STRIP: norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln); 0: k_ln_apply_quant in front of it
+    bool cls_bwd;         // QATVIT_CLS_BWD: the one-plane backward of the last block's MLP and proj on the B class-token rows (the only ones the cls-pooled head reaches); 0: all B * T rows
 };
 const Knobs& knobs();
 

@@ -190,6 +190,9 @@ struct TNCall {   // what the weight gradients of one call share
     int w_per_channel = 0, w_qmin = 0, w_qmax = 0;
     float* scratch = nullptr;          // launch_gemm_tn: optional, kTnScratchBytes let every shape take the two-phase (non-atomic, bit-reproducible) split reduction;
     int64_t scratch_bytes = 0;         // launch_tn_stream: required, >= tn_stream_scratch_bytes()
+    // launch_gemm_tn: the two-phase form for a single split too.  The kernel's own tail is 96 dependent round trips per lane (weight load -> STE mask -> atomic),
+    // about 60 us whatever M is; over a few hundred token rows that is the whole run time, and k_tn_reduce does the same work one element per thread
+    bool reduce_single = false;
 };
 constexpr int64_t kTnScratchBytes = 256ll * 128 * 384 * 4;   // 256 workgroups x the largest tile
 int64_t tn_stream_scratch_bytes();
@@ -221,7 +224,16 @@ int launch_mask_bwd(int gelu_bwd, const float* d, const float* Y, const float* q
                     void* dst_hi, void* dst_lo, int64_t n, hipStream_t st, const float* o16_mul = nullptr, uint32_t* o16_amax = nullptr);
 int launch_ln_bwd_fq(int acc, const float* dH, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                      const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T,
-                     int cls_only, hipStream_t st, const LnBwdNext* next = nullptr);
+                     int cls_only, hipStream_t st, const LnBwdNext* next = nullptr,
+                     int rows_per_wave = 16);   // 16: few blocks, few same-address dgamma / dbeta atomics; 1 for a few hundred rows, where a wave's rows in sequence are the run time
+// Every T-th row of up to kRowMoveMax tensors in one launch (the class-token rows b * T of [B * T, .] operands): `width` bytes per row, % 4 == 0, as is the
+// tall tensor's row stride `stride` (bytes, >= width).  gather: compact[b] = tall[b * T] for b < rows.  scatter: the whole tall tensor is written - row b * T
+// from compact[b], zeros everywhere else (a kernel, as k_zero_i32 is: no memset node in a captured graph) - with width == stride, % 16 == 0, and 16-byte aligned bases
+constexpr int kRowMoveMax = 8;
+struct RowMove { const void* src; void* dst; int64_t stride; int width; };
+struct RowMoveTab { RowMove m[kRowMoveMax]; int n = 0; };
+int launch_rows_gather(const RowMoveTab& t, int rows, int T, hipStream_t st);
+int launch_rows_scatter(const RowMoveTab& t, int rows, int T, hipStream_t st);
 int launch_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp_norm, int qmin,
                     int qmax, const void* wq, const float* w_scale, int w_per_channel, const float* bias, float* hq, float* logits_pre,
                     uint32_t* stats, int stat_slots, int B, int D, int T, int C, hipStream_t st);
@@ -285,7 +297,10 @@ int launch_attn_fwd(const float* qkv, const float* qp, int qmin, int qmax, int B
 int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B, int T, int H, int D, const void* O_hi, const void* O_lo,
                     const float* lse, float* delta, const float* dO, void* dqkv_hi, void* dqkv_lo, const float* col_scale, hipStream_t st,
                     const void* codes = nullptr, const void* cmask = nullptr,   // with the forward's codes the pre-FQ qkv is not read at all
-                    const float* o16_mul = nullptr, uint32_t* o16_amax = nullptr);   // the one-plane form: dqkv_hi = ONE fp16 plane (fused kernel only)
+                    const float* o16_mul = nullptr, uint32_t* o16_amax = nullptr,   // the one-plane form: dqkv_hi = ONE fp16 plane (fused kernel only)
+                    // dO is zero outside the first live_q_tiles 16-query tiles of every image (0: anywhere): the fused kernel sweeps those alone and stores
+                    // zeros as the dQ of the rest.  dO_cls (fused kernel only, with live_q_tiles >= 1): dO is [B, D], the rows of token 0
+                    int live_q_tiles = 0, bool dO_cls = false);
 // true where launch_attn_bwd takes the fused kernel (the only one with the one-plane output)
 bool attn_bwd_is_fused(int T, int H, int D, bool codes);
 
