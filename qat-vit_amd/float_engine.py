@@ -46,6 +46,8 @@ def check_shape(model: nn.Module, amp=False) -> None:
     if depth < 1 or depth > 12:
         why.append(f"depth {depth} (1..12)")
     pe = model.patch_embed.proj
+    if model.patch_embed.img_size % model.patch_embed.patch_size:   # (stock would crop the image to whole patches; the native step reads whole images)
+        why.append(f"img_size {model.patch_embed.img_size} (a multiple of the patch size {model.patch_embed.patch_size})")
     if pe.kernel_size[0] % 4 or (pe.in_channels * pe.kernel_size[0] * pe.kernel_size[1]) % 128:
         why.append("patch embedding (patch size a multiple of 4, in_chans * patch^2 a multiple of 128)")
     if type(model.head) is not nn.Linear or type(pe) is not nn.Conv2d:
@@ -62,8 +64,9 @@ def check_shape(model: nn.Module, amp=False) -> None:
         if not all(isinstance(getattr(b, n), nn.Identity) for n in ("ls1", "ls2", "drop_path1", "drop_path2")):
             why.append("layer scale / drop-path")
             break
-    if amp and (D % 384 or model.blocks[0].mlp.fc1.weight.shape[0] % 384):
-        why.append(f"amp=True: embed_dim {D} and mlp hidden {model.blocks[0].mlp.fc1.weight.shape[0]} (multiples of 384 for the fp16 / bf16 forms)")
+    hidden = model.blocks[0].mlp.fc1.weight.shape[0] if depth else 0
+    if amp and (D % 384 or hidden % 384):
+        why.append(f"amp=True: embed_dim {D} and mlp hidden {hidden} (multiples of 384 for the fp16 / bf16 forms)")
     if why:
         raise RuntimeError("native float step: unsupported model: " + "; ".join(why))
 
