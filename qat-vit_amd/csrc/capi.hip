@@ -127,10 +127,18 @@ int qatvit_kd_ce_loss_mix(const float* student, const float* teacher, const floa
     return 0;
 }
 
+// The NT GEMMs: a wrapper checks its own pointers, writes its parameters into an NTGemm and names the operand form; launch_gemm_nt checks the request itself
+// (gemm.hip nt_request_ok).  QV_NT_REQUEST: the parameters the entry points share, by name (B and ldb: where there are any)
+#define QV_NT_REQUEST(g, a, a_ld, c_ld)                                                                                                         \
+    NTGemm g;                                                                                                                                   \
+    g.A = a; g.M = M; g.N = N; g.K = K; g.lda = a_ld; g.ldc = c_ld; g.s2 = s2; g.col_scale = col_scale; g.bias = bias; g.stats = stats
+
 int qatvit_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                    int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, void* stream) {
     QV_CHECK_ARG(A_hi && B && C, "qatvit_gemm_nt: null pointer argument");
-    if (launch_gemm_nt(A_hi, A_lo, B, C, M, N, K, lda, ldb, ldc, s1, s2, col_scale, bias, stats, 1, (hipStream_t)stream)) return 1;
+    QV_NT_REQUEST(g, A_hi, lda, ldc);
+    g.A_lo = A_lo; g.B = B; g.ldb = ldb; g.C = C; g.s1 = s1;
+    if (launch_gemm_nt(kNTBf16, g, nullptr, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_nt");
     return 0;
 }
@@ -138,7 +146,9 @@ int qatvit_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, 
 int qatvit_gemm_nt_f16(const void* A16_hi, const void* A16_lo, const void* B16, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                        int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, void* stream) {
     QV_CHECK_ARG(A16_hi && A16_lo && B16 && C, "qatvit_gemm_nt_f16: null pointer argument");
-    if (launch_gemm_nt(A16_hi, A16_lo, B16, C, M, N, K, lda, ldb, ldc, s1, s2, col_scale, bias, stats, 1, (hipStream_t)stream, nullptr, nullptr, true)) return 1;
+    QV_NT_REQUEST(g, A16_hi, lda, ldc);
+    g.A_lo = A16_lo; g.B = B16; g.ldb = ldb; g.C = C; g.s1 = s1;
+    if (launch_gemm_nt(kNTF16, g, nullptr, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_nt_f16");
     return 0;
 }
@@ -149,7 +159,9 @@ int qatvit_gemm_nt_i8_minmax(const void* A8, const void* B8, const int32_t* wsum
     QV_CHECK_ARG(A8 && B8 && wsum && a_qp && stats, "qatvit_gemm_nt_i8_minmax: null pointer argument");
     NTPost post{};
     post.mode = kEpiStats;
-    if (launch_gemm_nt_i8(A8, B8, wsum, a_qp, center, nullptr, M, N, K, lda, ldb, N, s1, s2, col_scale, bias, stats, 1, (hipStream_t)stream, &post)) return 1;
+    QV_NT_REQUEST(g, A8, lda, N);
+    g.wsum = wsum; g.a_qp = a_qp; g.center = center; g.s1 = s1; g.B = B8; g.ldb = ldb;
+    if (launch_gemm_nt(kNTI8, g, &post, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_nt_i8_minmax");
     return 0;
 }
@@ -170,7 +182,9 @@ int qatvit_i8_strip(int32_t mode, const void* A8, const void* B8f, const int32_t
     post.mode = mode;
     post.qp = out_qp; post.qmin = qmin; post.qmax = qmax; post.out8 = out8; post.out8_mask = out8_mask; post.code_T = code_T; post.code_hd = 64;
     post.lut_out = lut_out; post.lutq_out = lutq_out; post.out16_scale = out16_scale;
-    if (!launch_i8_strip(A8, B8f, wsum, a_qp, center, M, N, K, lda, N, s1, s2, col_scale, bias, stats, 1, (hipStream_t)stream, &post, true)) {
+    QV_NT_REQUEST(g, A8, lda, N);
+    g.wsum = wsum; g.a_qp = a_qp; g.center = center; g.s1 = s1; g.B_frag = B8f;
+    if (!launch_i8_strip(g, &post, (hipStream_t)stream, true)) {
         set_error("qatvit_i8_strip: unsupported arguments (mode %d M=%d N=%d K=%d lda=%d: need K = 384 with N %% 1152 == 0 or N %% 1536 == 0, or K = 768 with "
                   "N = 2304 or 3072; lda %% 16 == 0, M < 2^22, the mode's output pointers, qmax - qmin < 256; mode 7: (N / 3) %% 384 == 0, 0 < code_T < 1024)",
                   mode, M, N, K, lda);
@@ -193,8 +207,10 @@ int qatvit_i8_strip_ln(const float* x, const float* mean, const float* rstd, con
                        const void* B8f, const int32_t* wsum, const float* a_qp, int32_t center, int32_t M, int32_t N, int32_t K, int32_t lda, const float* s2,
                        const float* col_scale, const float* bias, uint32_t* stats, void* stream) {
     QV_CHECK_ARG(x && mean && rstd && gamma && beta && out8 && B8f && wsum && a_qp && stats, "qatvit_i8_strip_ln: null pointer argument");
-    if (!launch_i8_strip_ln(x, mean, rstd, gamma, beta, ln_qmin, ln_qmax, out8, B8f, wsum, a_qp, center, M, N, K, lda, s2, col_scale, bias, stats, 1,
-                            (hipStream_t)stream, true)) {
+    QV_NT_REQUEST(g, out8, lda, N);
+    g.wsum = wsum; g.a_qp = a_qp; g.center = center; g.B_frag = B8f;
+    const StripLn ln{x, mean, rstd, gamma, beta, ln_qmin, ln_qmax, out8};
+    if (!launch_i8_strip_ln(g, ln, (hipStream_t)stream, true)) {
         set_error("qatvit_i8_strip_ln: unsupported arguments (M=%d N=%d K=%d lda=%d: need K = 384 with N = 1152 or 1536, or K = 768 with N = 2304 or 3072; "
                   "lda %% 16 == 0, lda >= K, 0 < M < 2^22)", M, N, K, lda);
         return 1;
@@ -206,7 +222,9 @@ int qatvit_i8_strip_ln(const float* x, const float* mean, const float* rstd, con
 int qatvit_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                          int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, void* stream) {
     QV_CHECK_ARG(A8 && lut && B16 && C, "qatvit_gemm_nt_codes: null pointer argument");
-    if (launch_gemm_nt_codes(A8, lut, B16, C, M, N, K, lda, ldb, ldc, s1, s2, col_scale, bias, stats, 1, (hipStream_t)stream)) return 1;
+    QV_NT_REQUEST(g, A8, lda, ldc);
+    g.lut = lut; g.B = B16; g.ldb = ldb; g.C = C; g.s1 = s1;
+    if (launch_gemm_nt(kNTCodes, g, nullptr, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_nt_codes");
     return 0;
 }
@@ -215,7 +233,9 @@ int qatvit_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
                       int32_t K, int32_t lda, int32_t ldb, int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias,
                       uint32_t* stats, void* stream) {
     QV_CHECK_ARG(A8 && B8 && wsum && a_qp && C, "qatvit_gemm_nt_i8: null pointer argument");
-    if (launch_gemm_nt_i8(A8, B8, wsum, a_qp, center, C, M, N, K, lda, ldb, ldc, s1, s2, col_scale, bias, stats, 1, (hipStream_t)stream)) return 1;
+    QV_NT_REQUEST(g, A8, lda, ldc);
+    g.wsum = wsum; g.a_qp = a_qp; g.center = center; g.s1 = s1; g.B = B8; g.ldb = ldb; g.C = C;
+    if (launch_gemm_nt(kNTI8, g, nullptr, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_nt_i8");
     return 0;
 }
@@ -242,7 +262,9 @@ int qatvit_gemm_tn(const void* P_hi, const void* P_lo, const void* Q_hi, const v
 int qatvit_gemm_nt_dy16(const void* A16, const void* B16, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, const float* s1,
                         const float* s2, void* stream) {
     QV_CHECK_ARG(A16 && B16 && C, "qatvit_gemm_nt_dy16: null pointer argument");
-    if (launch_gemm_nt_dy16(A16, B16, C, M, N, K, lda, ldb, ldc, s1, s2, (hipStream_t)stream)) return 1;
+    NTGemm g;
+    g.A = A16; g.B = B16; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.s1 = s1; g.s2 = s2;
+    if (launch_gemm_nt(kNTPlaneF16, g, nullptr, (hipStream_t)stream)) return 1;
     QV_CHECK_LAUNCH("qatvit_gemm_nt_dy16");
     return 0;
 }

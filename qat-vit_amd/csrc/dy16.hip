@@ -1,5 +1,5 @@
 // Scale bookkeeping of the one-plane backward: every gradient tensor that feeds a dgrad / wgrad GEMM pair is stored as ONE fp16 plane
-// value * 2^e instead of a bf16 (hi, lo) pair (gemm.hip launch_gemm_nt_dy16 / launch_gemm_tn, forms kTNPlane*).  fp16's precision (2^-12 per element) is
+// value * 2^e instead of a bf16 (hi, lo) pair (gemm.hip launch_gemm_nt, forms kNTPlane* / launch_gemm_tn, forms kTNPlane*).  fp16's precision (2^-12 per element) is
 // inside the 1e-3 bar of `loss.backward()` (/root/reference/src/training/qat_trainer.py:359); its range (2^-14 .. 2^16) is not wide enough for
 // gradients (1e-7 .. 1e-2 at batch 256), so e is chosen per tensor BEFORE the tensor exists: from the maximum the same tensor had in the previous
 // backward, rescaled by the ratio of this backward's max |dlogits| to the previous one's (a different batch size, loss weight or loss scale moves

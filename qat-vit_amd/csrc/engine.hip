@@ -253,9 +253,10 @@ static bool ln_in_strip_of(const Plan& p, const Dims& d, int flags, int kind) {
     const Forms& F = p.form;
     if (!F.ln_in_strip || !(flags & QATVIT_FWD_X16) || (kind == WB_QKV && !F.qkv_2pass) || d.depth < 1) return false;
     const int wi = 1 + kind;
-    int N, K; wshape(d, wi, &N, &K);
-    if (!(F.w_batched && p.w8f_off[wi] >= 0) || K != d.D) return false;
-    return i8_strip_ln_covers(&p /* (any non-null pointer: the weight in fragment order exists) */, (int)d.M, N, K, K);
+    NTGemm g;
+    wshape(d, wi, &g.N, &g.K);
+    g.B_frag = &p; g.M = (int)d.M; g.lda = g.K;   // (B_frag: any non-null pointer - the weight in fragment order exists)
+    return F.w_batched && p.w8f_off[wi] >= 0 && g.K == d.D && i8_strip_ln_covers(g);
 }
 
 static int check_cfg(const qatvit_cfg& c) {
@@ -398,15 +399,13 @@ struct Ctx {
     struct LnRows { const float* x; const float* mean; const float* rstd; const float* gamma; const float* beta; int ai; };
     bool ln_in_strip(int kind) const { return ln_in_strip_of(p, d, flags, kind); }
     int linear_stats_ln(const LnRows& r, void* out8, int M, int wi, const float* bias, int ai_out, bool late_strip) const {
-        int N, K; wshape(d, wi, &N, &K);
-        const qatvit_fq& f = wfq[wi];
+        const NTGemm g = grid_request(M, wi, out8, act_qp(r.ai), bias, ai_out);   // (A: the plane the pass itself writes)
         {
             ProfScope ps(prof, 7, 0.0, st);
             const QpLate L = late(r.ai);
-            if (!late_kind(r.ai) ||
-                !launch_i8_strip_ln(r.x, r.mean, r.rstd, r.gamma, r.beta, c.act_qmin, c.act_qmax, out8, w8f(wi), at<int32_t>(p.wsum_off[wi]), act_qp(r.ai), center(), M, N, K, K,
-                                    c.w_per_channel ? nullptr : f.scale, c.w_per_channel ? f.scale : nullptr, bias, act_stats(ai_out), kStatSlots, st, false, &L)) {
-                set_error("engine: the statistics pass with the LayerNorm prologue does not cover layer %d (M=%d N=%d K=%d)", wi, M, N, K);
+            const StripLn ln{r.x, r.mean, r.rstd, r.gamma, r.beta, c.act_qmin, c.act_qmax, out8, &L};
+            if (!late_kind(r.ai) || !launch_i8_strip_ln(g, ln, st)) {
+                set_error("engine: the statistics pass with the LayerNorm prologue does not cover layer %d (M=%d N=%d K=%d)", wi, M, g.N, g.K);
                 return 1;
             }
         }
@@ -418,47 +417,48 @@ struct Ctx {
         launch_qparams(act_stats(ai), f.min_val, f.max_val, f.scale, f.zero_point, f.observer_on, f.fake_quant_on, c.averaging_const,
                        c.act_qmin, c.act_qmax, 1, 0, act_qp(ai), 1, kStatSlots, st);
     }
-    // forward GEMM against fake-quantized weight wi: C = (A . wq^T) * s_act * s_w + bias, stats -> act FQ `ai_out`
-    // (A_lo == nullptr: A holds grid integers; else A = A_hi + A_lo is a float operand)
+    // The forward product of layer wi over M rows without its operands: C = (A . wq^T) * (*s_act) * s_w + bias, s_w the scalar s2 or (per-channel) the vector col_scale; stats -> act FQ `ai_out`
+    NTGemm fwd_request(int M, int wi, const float* s_act = nullptr, const float* bias = nullptr, int ai_out = -1, float* C = nullptr) const {
+        NTGemm g;
+        wshape(d, wi, &g.N, &g.K);
+        g.M = M; g.lda = g.ldb = g.K; g.ldc = g.N; g.C = C; g.s1 = s_act; g.bias = bias; g.stat_slots = kStatSlots;
+        (c.w_per_channel ? g.col_scale : g.s2) = wfq[wi].scale;
+        if (ai_out >= 0) g.stats = act_stats(ai_out);
+        return g;
+    }
+    // ... on int8 operands (kNTI8): A8 = q - center, the weight integers with their row sums and, where the forward wrote it, their fragment-order copy
+    NTGemm grid_request(int M, int wi, const void* A8, const float* a_qp, const float* bias, int ai_out, float* C = nullptr) const {
+        NTGemm g = fwd_request(M, wi, a_qp, bias, ai_out, C);
+        g.A = A8; g.B = at<void>(p.w8_off[wi]); g.B_frag = w8f(wi); g.wsum = at<int32_t>(p.wsum_off[wi]); g.a_qp = a_qp; g.center = center();
+        return g;
+    }
+    // ... on bf16 operands (A_lo == nullptr: A holds grid integers; else A = A_hi + A_lo is a float operand)
     int linear_fwd(const void* A_hi, const void* A_lo, int M, int wi, const float* s_act, const float* bias, float* C, int ai_out,
                    const NTPost* post = nullptr, bool with_stats = true) const {
-        int N, K; wshape(d, wi, &N, &K);
-        const qatvit_fq& f = wfq[wi];
+        NTGemm g = fwd_request(M, wi, s_act, bias, with_stats ? ai_out : -1, C);
+        g.A = A_hi; g.A_lo = A_lo; g.B = at<void>(p.w_off[wi]);
+        return fwd_launch(kNTBf16, g, post, A_lo ? 1 : 2, ai_out);
+    }
+    // THE launch of a forward request (a statistics-only pass is issued, not algorithmic, work), then the update of the quantizer ai_out that got its statistics
+    int fwd_launch(NTForm form, const NTGemm& g, const NTPost* post, int kind, int ai_out, bool late_strip = false) const {
         {
-            ProfScope ps(prof, A_lo ? 1 : 2, stats_only(post) ? 0.0 : 2.0 * M * N * K, st);   // a statistics-only pass is issued, not algorithmic, work
-            if (launch_gemm_nt(A_hi, A_lo, at<void>(p.w_off[wi]), C, M, N, K, K, K, N, s_act, c.w_per_channel ? nullptr : f.scale,
-                               c.w_per_channel ? f.scale : nullptr, bias, with_stats ? act_stats(ai_out) : nullptr, kStatSlots, st, nullptr, post, false))
-                return 1;
+            ProfScope ps(prof, kind, stats_only(post) ? 0.0 : 2.0 * g.M * g.N * g.K, st);
+            if (launch_gemm_nt(form, g, post, st)) return 1;
         }
-        qparams_after(ai_out, with_stats);
+        qparams_after(ai_out, g.stats != nullptr, late_strip);
         return 0;
     }
-    // the same product with the float A operand as an fp16 (hi, lo) pair scaled by *pair_scale (a device scalar its producer wrote) and the
-    // weight integers as fp16
+    // the same product with the float A operand as an fp16 (hi, lo) pair scaled by *pair_scale (a device scalar its producer wrote) and the weight integers as fp16
     int linear_fwd_f16(const void* A16_hi, const void* A16_lo, const float* pair_scale, int M, int wi, const float* bias, float* C, int ai_out) const {
-        int N, K; wshape(d, wi, &N, &K);
-        const qatvit_fq& f = wfq[wi];
-        {
-            ProfScope ps(prof, 1, 2.0 * M * N * K, st);
-            if (launch_gemm_nt(A16_hi, A16_lo, at<void>(p.w16_off[wi]), C, M, N, K, K, K, N, pair_scale, c.w_per_channel ? nullptr : f.scale,
-                               c.w_per_channel ? f.scale : nullptr, bias, act_stats(ai_out), kStatSlots, st, nullptr, nullptr, true))
-                return 1;
-        }
-        qparams_after(ai_out, true);
-        return 0;
+        NTGemm g = fwd_request(M, wi, pair_scale, bias, ai_out, C);
+        g.A = A16_hi; g.A_lo = A16_lo; g.B = at<void>(p.w16_off[wi]);
+        return fwd_launch(kNTF16, g, nullptr, 1, ai_out);
     }
     // the same product with the A operand as uint8 table indices [M, K] + the 256-entry table of fp16 pairs (fc2: gelu(fq(.)) takes <= 256 values)
     int linear_fwd_codes(const void* A8, const uint32_t* lut, const float* pair_scale, int M, int wi, const float* bias, float* C, int ai_out) const {
-        int N, K; wshape(d, wi, &N, &K);
-        const qatvit_fq& f = wfq[wi];
-        {
-            ProfScope ps(prof, 1, 2.0 * M * N * K, st);
-            if (launch_gemm_nt_codes(A8, lut, at<void>(p.w16_off[wi]), C, M, N, K, K, K, N, pair_scale, c.w_per_channel ? nullptr : f.scale,
-                                     c.w_per_channel ? f.scale : nullptr, bias, act_stats(ai_out), kStatSlots, st))
-                return 1;
-        }
-        qparams_after(ai_out, true);
-        return 0;
+        NTGemm g = fwd_request(M, wi, pair_scale, bias, ai_out, C);
+        g.A = A8; g.lut = lut; g.B = at<void>(p.w16_off[wi]);
+        return fwd_launch(kNTCodes, g, nullptr, 1, ai_out);
     }
     int center() const { return (c.act_qmin + c.act_qmax + 1) / 2; }
     // the same forward product with int8 operands: A8 = q - center written next to the bf16 grid by its producer, weight integers + row sums
@@ -469,35 +469,33 @@ struct Ctx {
                         const NTPost* post = nullptr, bool with_stats = true, bool late_strip = false) const {
         int N, K; wshape(d, wi, &N, &K);
         if (!p.form.i8 || N % 384 != 0 || K % 64 != 0) return linear_fwd(A16, nullptr, M, wi, a_qp, bias, C, ai_out, post, with_stats);
-        const qatvit_fq& f = wfq[wi];
-        {
-            ProfScope ps(prof, prof_kind_fwd(post), stats_only(post) ? 0.0 : 2.0 * M * N * K, st);
-            const bool code_pass = late_strip && post && !stats_only(post);
-            const QpLate L = code_pass ? late(ai_out) : QpLate{};
-            if (launch_gemm_nt_i8(A8, at<void>(p.w8_off[wi]), at<int32_t>(p.wsum_off[wi]), a_qp, center(), C, M, N, K, K, K, N, a_qp,
-                                  c.w_per_channel ? nullptr : f.scale, c.w_per_channel ? f.scale : nullptr, bias,
-                                  with_stats ? act_stats(ai_out) : nullptr, kStatSlots, st, post, w8f(wi), code_pass ? &L : nullptr))
-                return 1;
-        }
-        qparams_after(ai_out, with_stats, late_strip);
-        return 0;
+        NTGemm g = grid_request(M, wi, A8, a_qp, bias, with_stats ? ai_out : -1, C);
+        const bool code_pass = late_strip && post && !stats_only(post);
+        const QpLate L = code_pass ? late(ai_out) : QpLate{};
+        if (code_pass) g.late = &L;
+        return fwd_launch(kNTI8, g, post, prof_kind_fwd(post), ai_out, late_strip);
     }
     // the int8 weight of layer wi in fragment order (the strip kernel's B operand), where the forward wrote it
     void* w8f(int wi) const { return p.form.i8 && p.form.w_batched && p.w8f_off[wi] >= 0 ? at<void>(p.w8f_off[wi]) : nullptr; }
     // will the strip kernel's code pass (post2) be the consumer of quantizer-of-layer-wi's statistics?  (then it resolves the qparams itself)
     bool late_in_strip(int M, int wi, const NTPost* post2) const {
-        int N, K; wshape(d, wi, &N, &K);
-        return p.form.late && i8_strip_covers(w8f(wi), M, N, K, K, N, post2);
+        NTGemm g = fwd_request(M, wi); g.B_frag = w8f(wi);
+        return p.form.late && i8_strip_covers(g, post2);
     }
     // the per-channel weight scale of layer wi, which its dY producer folds in (nullptr for per-tensor)
     const float* dy_colscale(int wi) const { return c.w_per_channel ? wfq[wi].scale : nullptr; }
-    // dgrad: dX[M,K] = dY[M,N] . W_fq[N,K]   (per-channel: dY already carries s_w[n])
+    // dgrad: dX[M,K] = dY[M,N] . W_fq[N,K] from the transposed weight; *s1 = the per-tensor weight scale (per-channel: dY already carries s_w[n]).  The request without its operands:
+    NTGemm dgrad_request(int M, int wi, float* dX = nullptr) const {
+        NTGemm g;
+        wshape(d, wi, &g.K, &g.N);
+        g.M = M; g.lda = g.ldb = g.K; g.ldc = g.N; g.C = dX; if (!c.w_per_channel) g.s1 = wfq[wi].scale;
+        return g;
+    }
     int linear_dgrad(const void* dY_hi, const void* dY_lo, int M, int wi, float* dX, const NTPost* post = nullptr) const {
-        int N, K; wshape(d, wi, &N, &K);
-        const qatvit_fq& f = wfq[wi];
-        ProfScope ps(prof, prof_kind_dgrad(post), 2.0 * M * N * K, st);
-        return launch_gemm_nt(dY_hi, dY_lo, at<void>(p.wT_off[wi]), dX, M, K, N, N, N, K, c.w_per_channel ? nullptr : f.scale, nullptr, nullptr,
-                              nullptr, nullptr, 1, st, nullptr, post);
+        NTGemm g = dgrad_request(M, wi, dX);
+        g.A = dY_hi; g.A_lo = dY_lo; g.B = at<void>(p.wT_off[wi]);
+        ProfScope ps(prof, prof_kind_dgrad(post), 2.0 * M * g.N * g.K, st);
+        return launch_gemm_nt(kNTBf16, g, post, st);
     }
     // The weight-gradient request of layer wi without its operands: dW[N,K] += sum_m dY[m,N] X[m,K] * s_x under the weight FQ's STE mask, db[N] += sum_m dY;
     // dy_scaled: dY carries the per-channel weight scale s_w[n] (folded in for the dgrad), row_div takes it out again
@@ -896,7 +894,6 @@ int Bwd::block_one_plane(int i, bool injected) {
     float* dH_mlp = rows ? x.at<float>(cr.dH) : x.at<float>(p.dH);
     const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
     float* const scal16 = x.blk<float>(p.scal16, i);
-    auto wscale1 = [&](int wi) { return c.w_per_channel ? nullptr : x.wfq[wi].scale; };
     if (rows) {
         const int64_t mrow = ln_maskbits_bytes(1, d.D);
         const bool q8 = F.x_plane_from_q8;
@@ -932,9 +929,10 @@ int Bwd::block_one_plane(int i, bool injected) {
         return launch_gemm_tn(form, g, call, st);
     };
     auto dgrad16 = [&](int Md, const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
-        int N, K; wshape(d, wi, &N, &K);
-        ProfScope ps(x.prof, prof_kind_dgrad(post), 2.0 * Md * N * K, st);
-        return launch_gemm_nt_dy16(P16, x.wT16(wi), dX, Md, K, N, N, N, K, wscale1(wi), x.dy_inv(i, k), st, post);
+        NTGemm g = x.dgrad_request(Md, wi, dX);
+        g.A = P16; g.B = x.wT16(wi); g.s2 = x.dy_inv(i, k);
+        ProfScope ps(x.prof, prof_kind_dgrad(post), 2.0 * Md * g.N * g.K, st);
+        return launch_gemm_nt(kNTPlaneF16, g, post, st);
     };
     // ---- MLP branch
     if (injected)
@@ -948,7 +946,9 @@ int Bwd::block_one_plane(int i, bool injected) {
         bool strip = false;
         if (x.wT16f_ok(w_fc2) && knobs().f16_strip) {   // the A-stationary strip form (f16strip.hip): the gradient plane fetched once for all four column tiles
             ProfScope ps(x.prof, 5, 2.0 * Mr * d.D * d.Hd, st);
-            strip = launch_f16_strip_gelu_bwd(dY16, x.wT16f(w_fc2), nullptr, Mr, d.Hd, d.D, d.D, d.Hd, wscale1(w_fc2), x.dy_inv(i, DS_FC2), st, &post);
+            NTGemm g = x.dgrad_request(Mr, w_fc2);
+            g.A = dY16; g.B_frag = x.wT16f(w_fc2); g.s2 = x.dy_inv(i, DS_FC2);
+            strip = launch_f16_strip_gelu_bwd(g, &post, st);
         }
         if (!strip && dgrad16(Mr, dY16, DS_FC2, w_fc2, nullptr, &post)) return 1;
     }

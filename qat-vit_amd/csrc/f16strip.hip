@@ -201,15 +201,15 @@ __global__ __launch_bounds__(768, 3) void k_f16_strip_gelu_bwd(const F16StripArg
     if (lane == 0) atomicMax(p.o16_amax + (blockIdx.x & (kDyAmaxSlots - 1)) * kDyAmaxStride, __builtin_bit_cast(uint32_t, am));
 }
 
-// true when the strip kernel took the request (K = 384, N = 1536: ViT-S's fc2 dgrad); false -> launch_gemm_nt_dy16 with epilogue mode 9
-bool launch_f16_strip_gelu_bwd(const void* A16, const void* B16f, float* /*unused*/, int M, int N, int K, int lda, int ldc, const float* s1, const float* s2, hipStream_t st,
-                               const NTPost* post) {
-    if (!knobs().f16_strip || !A16 || !B16f || !post || post->mode != kEpiGeluBwdU8 || K != 384 || N != 4 * 384 || lda % 8 != 0 || ldc % 128 != 0 || !post->qp || !post->out_hi ||
-        !post->code8 || !post->code_mask || !post->o16_mul || !post->o16_amax || post->qmax - post->qmin >= 256)
+// true when the strip kernel took the request (K = 384, N = 1536: ViT-S's fc2 dgrad); false -> launch_gemm_nt(kNTPlaneF16, ..) with epilogue mode 9
+bool launch_f16_strip_gelu_bwd(const NTGemm& g, const NTPost* post, hipStream_t st) {
+    const int M = g.M, N = g.N, lda = g.lda, ldc = g.ldc;
+    if (!knobs().f16_strip || !g.A || !g.B_frag || !post || post->mode != kEpiGeluBwdU8 || g.K != 384 || N != 4 * 384 || lda % 8 != 0 || ldc % 128 != 0 || !post->qp ||
+        !post->out_hi || !post->code8 || !post->code_mask || !post->o16_mul || !post->o16_amax || post->qmax - post->qmin >= 256)
         return false;
     if ((int64_t)M * lda * 2 >= (1ll << 32) || (int64_t)M * ldc >= (1ll << 32)) return false;   // the 32-bit DMA offsets
     F16StripArgs a{};
-    a.A = reinterpret_cast<const _Float16*>(A16); a.Bf = reinterpret_cast<const i32x4*>(B16f); a.M = M; a.N = N; a.lda = lda; a.s1 = s1; a.s2 = s2;
+    a.A = reinterpret_cast<const _Float16*>(g.A); a.Bf = reinterpret_cast<const i32x4*>(g.B_frag); a.M = M; a.N = N; a.lda = lda; a.s1 = g.s1; a.s2 = g.s2;
     a.qp = post->qp; a.qmin = post->qmin; a.qmax = post->qmax; a.colscale = post->colscale;
     a.code8 = reinterpret_cast<const uint8_t*>(post->code8); a.mask = reinterpret_cast<const uint8_t*>(post->code_mask); a.ldc = ldc;
     a.out = reinterpret_cast<_Float16*>(post->out_hi); a.o16_mul = post->o16_mul; a.o16_amax = post->o16_amax;

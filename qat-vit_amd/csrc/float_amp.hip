@@ -5,7 +5,7 @@
 // the same with one fp16 plane per GEMM operand and one v_mfma_f32_16x16x32_f16 pass per product:
 //   forward   the teacher's one-pass fp16 pieces (k_patches_split / k_resid_ln_split / k_attn_fwd_float with f16), keeping LayerNorm mean / rstd,
 //             lse, the fc1 pre-activation and the fp16 activation planes the weight gradients read; GEMM outputs stay fp32; fp16 logits.
-//   backward  dgrad = launch_gemm_nt_dy16 and wgrad = launch_gemm_tn (kTNPlaneF16 / kTNPlaneBf16) with unit scales; the LayerNorm backward of the float step (its fused
+//   backward  dgrad = launch_gemm_nt (kNTPlaneF16 / kNTPlaneBf16) and wgrad = launch_gemm_tn (kTNPlaneF16 / kTNPlaneBf16) with unit scales; the LayerNorm backward of the float step (its fused
 //             next-branch output as one fp16 plane); new here: the head, GELU', embedding and attention backward in their fp16 forms.
 // Overflow follows stock (GradScaler must skip the same steps): every tensor stock holds in fp16 is rounded to nearest (fp16 overflow -> +-inf,
 // NaN propagates) where it becomes fp16 - dlogits, dhn, the fc2 dgrad output, dO, dP, dS, dQKV, dY0 - and the

@@ -3,7 +3,7 @@
 // Replaces: `student_out = model(images)` ... `loss.backward()` of the reference's float epochs (qat_trainer.py:295-361 before
 // prepare_qat), the unprepared QATWrapper(vit_*_patch16_224) in fp32.  Every GEMM operand is a float tensor held as a bf16 (hi, lo)
 // pair and every product takes three MFMA passes (hi.hi + lo.hi + hi.lo, fp32 accumulate): the teacher's 3-pass form (teacher.hip),
-// here on both sides of the backward too - dgrad = launch_gemm_nt with the transposed weight pair, wgrad = launch_gemm_tn (kTNPair) with
+// here on both sides of the backward too - dgrad = launch_gemm_nt (kNTBf16) with the transposed weight pair, wgrad = launch_gemm_tn (kTNPair) with
 // pairs on both sides.  The forward is the teacher's (patches, fused residual + LayerNorm, float attention, GELU) with the extra
 // outputs a backward needs: LayerNorm mean / rstd, attention log-sum-exp, the fc1 pre-activation, the residual stream.
 // Of the QAT engine's backward kernels the LayerNorm backward (elt.hip k_ln_bwd_fq), the GELU' pass (k_mask_bwd) and the
@@ -492,10 +492,12 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
         else k_fs_wsplit<<<blocks, 256, 0, st>>>(t);
     };
     // (act_fq order: 0 quant, 1 patch_embed.proj, per block 2 + 6 i + {norm1, qkv, proj, norm2, fc1, fc2}, then norm, head)
-    // (the bf16 form: no lo planes and not f16 - launch_gemm_nt's one-plane bf16 path)
+    // (the bf16 form: kNTBf16 without lo planes - its one-plane path)
     auto gemm = [&](int64_t ah, int64_t al, int wi, const float* bias, float* C, int N, int K, int Mrows, int ai) {
-        return launch_gemm_nt(V(ah), V(al), V(p.w_hi[wi]), C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, ob.act(ai), ob.stats ? kStatSlots : 1, st,
-                              V(p.w_lo[wi]), nullptr, f16);
+        NTGemm g;
+        g.A = V(ah); g.A_lo = V(al); g.B = V(p.w_hi[wi]); g.B_lo = V(p.w_lo[wi]); g.C = C; g.M = Mrows; g.N = N; g.K = g.lda = g.ldb = K; g.ldc = N;
+        g.bias = bias; g.stats = ob.act(ai); g.stat_slots = ob.stats ? kStatSlots : 1;
+        return launch_gemm_nt(f16 ? kNTF16 : kNTBf16, g, nullptr, st);
     };
     auto gelu = [&](const FsBlock& k) {
         if (one) launch_fa_gelu(F(k.Y1), V(k.G_hi), M * Hd, st, bf16);
@@ -580,8 +582,11 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
     // ---- the form's steps
     // dgrad: C[M, N] = A[M, K] . W[K, N]  with the transposed weight's planes as the B operand ([N, K] row-major)
     auto dgrad = [&](int64_t ah, int64_t al, int wi, float* C, int N, int K) {
-        if (one) return launch_gemm_nt_dy16(V(ah), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, unit, unit, st, nullptr, bf16);
-        return launch_gemm_nt(V(ah), V(al), V(p.w_hiT[wi]), C, (int)M, N, K, K, K, N, nullptr, nullptr, nullptr, nullptr, nullptr, 1, st, V(p.w_loT[wi]), nullptr);
+        NTGemm g;
+        g.A = V(ah); g.B = V(p.w_hiT[wi]); g.C = C; g.M = (int)M; g.N = N; g.K = g.lda = g.ldb = K; g.ldc = N;
+        if (one) g.s1 = g.s2 = unit;
+        else { g.A_lo = V(al); g.B_lo = V(p.w_loT[wi]); }
+        return launch_gemm_nt(bf16 ? kNTPlaneBf16 : f16 ? kNTPlaneF16 : kNTBf16, g, nullptr, st);
     };
     // wgrad: dW[N, Kw] += dY[Mr, N]^T . X[Mr, Kw], dbias[N] += column sums of dY
     auto wgrad = [&](int64_t ph, int64_t pl, int64_t qh, int64_t ql, float* dW, float* db, int N, int Kw, int Mr) {

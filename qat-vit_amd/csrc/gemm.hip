@@ -87,7 +87,7 @@ struct NTArgs {
 };
 // instantiation ids beyond the NTEpi values (NTArgs::pm / PM only; no caller names them)
 constexpr int kPmCodesF16 = 10;                        // kEpiCodes that also (or only) writes the fp16 (hi, lo) planes
-constexpr int kPmLnBwdO16 = 18, kPmGeluBwdO16 = 19;   // kEpiLnBwd / kEpiGeluBwdU8 + 10: the masked gradient leaves as ONE scaled fp16 plane (launch_gemm_nt_dy16)
+constexpr int kPmLnBwdO16 = 18, kPmGeluBwdO16 = 19;   // kEpiLnBwd / kEpiGeluBwdU8 + 10: the masked gradient leaves as ONE scaled fp16 plane (kNTPlaneF16)
 
 constexpr int kStandIn = 512;
 struct OnesTab { float v[kStandIn]; constexpr OnesTab() : v() { for (int i = 0; i < kStandIn; ++i) v[i] = 1.f; } };
@@ -1031,7 +1031,7 @@ static int nt_launch(const NTArgs& a, int grid, size_t lds, hipStream_t st) {
         switch (a.pm) {
             case kEpiResidFq: QV_PM(kEpiResidFq);   // (case order = instantiation order = the functions' order in the object file: keep it, tools/isa_digest.py listings stay comparable)
             case kEpiGeluFwd: QV_PM(kEpiGeluFwd);
-            case kPmLnBwdO16: if constexpr (TA == 1 && tall1) QV_PM(kPmLnBwdO16); break;       // the one-plane backward (launch_gemm_nt_dy16)
+            case kPmLnBwdO16: if constexpr (TA == 1 && tall1) QV_PM(kPmLnBwdO16); break;       // the one-plane backward (kNTPlaneF16)
             case kPmGeluBwdO16: if constexpr (TA == 1 && tall1) QV_PM(kPmGeluBwdO16); break;
             case kEpiPlain: QV_PM(kEpiPlain);
         }
@@ -1062,7 +1062,7 @@ static int nt_launch(const NTArgs& a, int grid, size_t lds, hipStream_t st) {
     return 1;
 }
 
-// THE copy NTPost -> NTArgs: every epilogue operand, and the instantiation id.  o16: launch_gemm_nt_dy16's one-plane forms of modes 8 / 9.  A kernel reads
+// THE copy NTPost -> NTArgs: every epilogue operand, and the instantiation id.  o16: kNTPlaneF16's one-plane forms of modes 8 / 9.  A kernel reads
 // only the fields of its own PM (nt_epilogue: every access sits under that mode's `if constexpr`), so a field its mode does not use travels unread.
 static void nt_set_post(NTArgs& a, const NTPost& p, bool o16 = false) {
     a.post_mode = p.mode; a.post_gelu_fwd = p.mode == kEpiGeluFwd; a.out_f16 = p.out_f16;
@@ -1080,25 +1080,46 @@ static void nt_set_post(NTArgs& a, const NTPost& p, bool o16 = false) {
 // the mode a launcher switches on: kEpiPlain without a record; a record that names kEpiPlain is an unknown mode (-1) like any other number
 static int nt_mode(const NTPost* post) { return !post ? kEpiPlain : post->mode == kEpiPlain ? -1 : post->mode; }
 
-int launch_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1,
-                   const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
-                   const void* B_lo, const NTPost* post, bool f16) {
-    const bool f16_gelu = f16 && post && post->mode == kEpiGeluFwd && post->out_f16;   // the teacher's fc1: fp16 gelu pair out
-    if (f16 && (B_lo || (post && post->mode != kEpiResidFq && !f16_gelu) || (!A_lo && post && !f16_gelu) || N % 384 != 0 || K % 32 != 0)) {
-        set_error("gemm_nt: the fp16 form takes N %% 384 == 0 and the plain, the residual (mode 6) or the fp16 GELU epilogue (N=%d K=%d)", N, K);
-        return 1;
+// what an NTForm requires of a request (the table at enum NTForm, qv_kernels.h), and how its refusal reads (its numbers: M N K lda ldb ldc; kNTI8's text stops at ldb)
+struct NTRule { const char* refusal; int n_mod, k_mod, lda_mod, ldb_mod; bool ab, c_lut, i8; };
+static const char kNTShape[] = "gemm_nt: unsupported shape M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (need N%%128==0, K%%64==0, lda/ldb%%8==0, ldc%%4==0)";
+static const char kNTPlane[] = "gemm_nt_dy16: unsupported arguments M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (need N%%384==0, K%%32==0)";
+static const NTRule kNTRules[kNTForms] = {
+    /* kNTBf16      */ {kNTShape, 128, 64, 8, 8, false, false, false},
+    /* kNTF16       */ {kNTShape, 128, 64, 8, 8, false, false, false},   // (after its own rule in nt_request_ok: N % 384)
+    /* kNTI8        */ {"gemm_nt_i8: unsupported shape M=%d N=%d K=%d lda=%d ldb=%d (need N%%384==0, K%%64==0, ld%%16==0)", 384, 64, 16, 16, false, false, true},
+    /* kNTCodes     */ {"gemm_nt_codes: unsupported arguments M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (need N%%384==0, K%%64==0, lda%%16==0)", 384, 64, 16, 8, true, true, false},
+    /* kNTPlaneF16  */ {kNTPlane, 384, 32, 8, 8, true, false, false},
+    /* kNTPlaneBf16 */ {kNTPlane, 384, 32, 8, 8, true, false, false},
+};
+// THE check of an NT request, the epilogue's own operands aside (the mode switch of its form)
+static bool nt_request_ok(NTForm form, const NTGemm& g, const NTPost* post) {
+    const NTRule& r = kNTRules[form];
+    const bool f16_gelu = form == kNTF16 && post && post->mode == kEpiGeluFwd && post->out_f16;   // the teacher's fc1: fp16 gelu pair out
+    if (form == kNTF16 && (g.B_lo || (post && post->mode != kEpiResidFq && !f16_gelu) || (!g.A_lo && post && !f16_gelu) || g.N % 384 != 0 || g.K % 32 != 0)) {
+        set_error("gemm_nt: the fp16 form takes N %% 384 == 0 and the plain, the residual (mode 6) or the fp16 GELU epilogue (N=%d K=%d)", g.N, g.K);
+        return false;
     }
-    if (M < 1 || N % 128 != 0 || K % 64 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0) {
-        set_error("gemm_nt: unsupported shape M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (need N%%128==0, K%%64==0, lda/ldb%%8==0, ldc%%4==0)", M, N, K,
-                  lda, ldb, ldc);
-        return 1;
-    }
+    if (form == kNTPlaneBf16 && post) { set_error("gemm_nt_dy16: the bf16 form has the plain epilogue only"); return false; }
+    const bool ok = g.M >= 1 && g.N % r.n_mod == 0 && g.K % r.k_mod == 0 && g.lda % r.lda_mod == 0 && g.ldb % r.ldb_mod == 0 && g.ldc % 4 == 0 &&
+                    (!r.ab || (g.A && g.B)) && (!r.c_lut || (g.C && g.lut)) && (!r.i8 || (g.wsum && g.a_qp));
+    if (!ok) set_error(r.refusal, g.M, g.N, g.K, g.lda, g.ldb, g.ldc);
+    return ok;
+}
+// THE copy of a request into the kernels' argument record.  int8 operands: the k extent and the operand strides are counted in 2-byte units from here on
+static NTArgs nt_args(NTForm form, const NTGemm& g) {
+    const int unit = form == kNTI8 ? 2 : 1;
     NTArgs a{};
-    a.A0 = reinterpret_cast<const __bf16*>(A_hi); a.A1 = reinterpret_cast<const __bf16*>(A_lo); a.B = reinterpret_cast<const __bf16*>(B);
-    a.B1 = reinterpret_cast<const __bf16*>(B_lo); a.C = C; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-    a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
-    if (post) nt_set_post(a, *post);
-    const int mode = nt_mode(post);
+    a.A0 = reinterpret_cast<const __bf16*>(g.A); a.A1 = reinterpret_cast<const __bf16*>(g.A_lo); a.B = reinterpret_cast<const __bf16*>(g.B);
+    a.B1 = reinterpret_cast<const __bf16*>(g.B_lo); a.C = g.C; a.M = g.M; a.N = g.N; a.K = g.K / unit; a.lda = g.lda / unit; a.ldb = g.ldb / unit; a.ldc = g.ldc;
+    a.s1 = g.s1; a.s2 = g.s2; a.col_scale = g.col_scale; a.bias = g.bias; a.stats = g.stats; a.stat_slots = g.stat_slots < 1 ? 1 : g.stat_slots;
+    a.a_lut = g.lut; a.i8_wsum = g.wsum; a.i8_aqp = g.a_qp; a.i8_center = g.center;
+    return a;
+}
+// kNTBf16 / kNTF16: planes or (hi, lo) pairs
+static int nt_pairs(const NTArgs& a, const NTPost* post, bool f16, hipStream_t st) {
+    const bool A_lo = a.A1, B_lo = a.B1, C = a.C, f16_gelu = f16 && post && post->mode == kEpiGeluFwd && post->out_f16;
+    const int M = a.M, N = a.N, K = a.K, ldc = a.ldc, mode = nt_mode(post);
     const bool split_tall = A_lo && !f16 && !B_lo && K % 32 == 0;   // modes 8 / 9: the split-A 208 x 384 tile only
     switch (mode) {
         case kEpiPlain:
@@ -1155,27 +1176,16 @@ int launch_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, 
     return nt_launch<1, 2, 4, 2, 1, 2, 4, 64>(a, square, (size_t)2 * (16384 + 16384), st);                // 2 stages, 64 KiB: two workgroups per CU
 }
 
-int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1, const float* s2,
-                        hipStream_t st, const NTPost* post, bool bf16) {
-    if (bf16 && post) {
-        set_error("gemm_nt_dy16: the bf16 form has the plain epilogue only");
-        return 1;
-    }
-    if (M < 1 || N % 384 != 0 || K % 32 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0 || !A16 || !B16) {
-        set_error("gemm_nt_dy16: unsupported arguments M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (need N%%384==0, K%%32==0)", M, N, K, lda, ldb, ldc);
-        return 1;
-    }
-    NTArgs a{};
-    a.A0 = reinterpret_cast<const __bf16*>(A16); a.B = reinterpret_cast<const __bf16*>(B16); a.C = C; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-    a.s1 = s1; a.s2 = s2; a.stat_slots = 1;
-    if (post) nt_set_post(a, *post, true);
+// kNTPlaneF16 / kNTPlaneBf16, the one-plane backward: one v_mfma_f32_16x16x32_f16 (bf16) pass, 2 B per gradient element; modes 8 / 9 emit one fp16 plane too
+static int nt_planes(const NTArgs& a, const NTPost* post, bool bf16, hipStream_t st) {
+    const int M = a.M, N = a.N, K = a.K, ldc = a.ldc;
     const bool o16 = post && post->o16_mul && post->o16_amax && post->qp;
     switch (o16 || !post ? nt_mode(post) : -1) {
         case kEpiPlain:
-            if (!C) { set_error("gemm_nt_dy16: null output"); return 1; }
+            if (!a.C) { set_error("gemm_nt_dy16: null output"); return 1; }
             break;
         case kEpiLnBwd:
-            if (!(N == 384 && ldc == 384 && C && a.lnb_x && a.lnb_mean && a.lnb_rstd && a.lnb_gamma && a.lnb_beta && a.lnb_dx_in && a.lnb_dgamma && a.lnb_dbeta &&
+            if (!(N == 384 && ldc == 384 && a.C && a.lnb_x && a.lnb_mean && a.lnb_rstd && a.lnb_gamma && a.lnb_beta && a.lnb_dx_in && a.lnb_dgamma && a.lnb_dbeta &&
                   (!a.out_hi || a.lnb_nmask))) {
                 set_error("gemm_nt_dy16: epilogue mode 8 needs N == ldc == 384 and the LayerNorm operands");
                 return 1;
@@ -1202,32 +1212,21 @@ int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N
     return nt_launch<1, 2, 1, 13, 1, 8, 3, 64, false, true>(a, cdiv(M, 208) * (N / 384), lds, st);
 }
 
-// fc2 forward from codes: A8 [M, lda] uint8 grid indices, lut[256] packed fp16 (hi | lo << 16) pairs, B16 [N, ldb] the weight integers as fp16
-int launch_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1,
-                         const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, const NTPost* post) {
-    if (M < 1 || N % 384 != 0 || K % 64 != 0 || lda % 16 != 0 || ldb % 8 != 0 || ldc % 4 != 0 || !A8 || !lut || !B16 || !C) {
-        set_error("gemm_nt_codes: unsupported arguments M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (need N%%384==0, K%%64==0, lda%%16==0)", M, N, K, lda, ldb, ldc);
-        return 1;
-    }
-    NTArgs a{};
-    a.A0 = reinterpret_cast<const __bf16*>(A8); a.B = reinterpret_cast<const __bf16*>(B16); a.C = C;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-    a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
-    a.a_lut = lut;
-    if (post) nt_set_post(a, *post);
+// kNTCodes, fc2 forward from codes: A [M, lda] uint8 grid indices, lut[256] packed fp16 (hi | lo << 16) pairs, B [N, ldb] the weight integers as fp16
+static int nt_codes(const NTArgs& a, const NTPost* post, hipStream_t st) {
     constexpr int kLds = 3 * (2 * 208 + 384) * 64 + 1024;   // 151 KiB
     switch (nt_mode(post)) {
         case kEpiResidFq: {   // inference: the residual update C[orow] = resid + fq(acc) in the epilogue, frozen qparams
             if (!post->qp || !post->resid) break;
             static bool once6 = (allow_lds(k_gemm_nt_ac<3, kEpiResidFq, kLds>, (size_t)kLds), true);
             (void)once6;
-            k_gemm_nt_ac<3, kEpiResidFq, kLds><<<cdiv(M, 208) * (N / 384), 512, kLds, st>>>(a);
+            k_gemm_nt_ac<3, kEpiResidFq, kLds><<<cdiv(a.M, 208) * (a.N / 384), 512, kLds, st>>>(a);
             return 0;
         }
         case kEpiPlain: {
             static bool once = (allow_lds(k_gemm_nt_ac<3, kEpiPlain, kLds>, (size_t)kLds), true);
             (void)once;
-            k_gemm_nt_ac<3, kEpiPlain, kLds><<<cdiv(M, 208) * (N / 384), 512, kLds, st>>>(a);
+            k_gemm_nt_ac<3, kEpiPlain, kLds><<<cdiv(a.M, 208) * (a.N / 384), 512, kLds, st>>>(a);
             return 0;
         }
     }
@@ -1235,26 +1234,14 @@ int launch_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, f
     return 1;
 }
 
-// Grid x grid forward GEMM on int8 MFMA (v_mfma_i32_16x16x64_i8: twice the k per instruction and per LDS-DMA byte of the bf16 form).
-// A8 [M, lda] = q - center (int8), B8 [N, ldb] = weight integers (int8), wsum [N] = row sums of B8; the result equals the bf16 path's
-// bit for bit (both accumulate the same integers exactly).  Tall 208 x 384 tiles only: N % 384 == 0, K % 64 == 0.
-int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const float* a_qp, int center, float* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots,
-                      hipStream_t st, const NTPost* post, const void* B8f, const QpLate* late) {
-    if (M < 1 || N % 384 != 0 || K % 64 != 0 || lda % 16 != 0 || ldb % 16 != 0 || ldc % 4 != 0 || !wsum || !a_qp) {
-        set_error("gemm_nt_i8: unsupported shape M=%d N=%d K=%d lda=%d ldb=%d (need N%%384==0, K%%64==0, ld%%16==0)", M, N, K, lda, ldb);
-        return 1;
-    }
-    NTArgs a{};   // (int8 operands: the k extent and the operand strides are counted in 2-byte units)
-    a.A0 = reinterpret_cast<const __bf16*>(A8); a.B = reinterpret_cast<const __bf16*>(B8); a.C = C; a.M = M; a.N = N; a.K = K / 2; a.lda = lda / 2; a.ldb = ldb / 2;
-    a.ldc = ldc; a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
-    a.i8_wsum = wsum; a.i8_aqp = a_qp; a.i8_center = center;
-    if (post) nt_set_post(a, *post);
-    const int mode = nt_mode(post);
+// kNTI8, grid x grid forward GEMM on int8 MFMA (v_mfma_i32_16x16x64_i8: twice the k per instruction and per LDS-DMA byte of the bf16 form): the result equals the bf16
+// path's bit for bit (both accumulate the same integers exactly).  Tall 208 x 384 tiles only
+static int nt_i8(const NTArgs& a, const NTGemm& g, const NTPost* post, hipStream_t st) {
+    const int M = a.M, N = a.N, ldc = a.ldc, mode = nt_mode(post);
     bool ok = true;
     switch (mode) {
         case kEpiPlain:
-            if (!C) { set_error("gemm_nt_i8: null output"); return 1; }
+            if (!a.C) { set_error("gemm_nt_i8: null output"); return 1; }
             break;
         case kEpiStats: break;
         case kEpiCodes: {
@@ -1264,7 +1251,7 @@ int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
             ok = a.post_qp && (full4 || half4) && a.post_qmax - a.post_qmin < 256;
             break;
         }
-        case kEpiResidFq: ok = a.post_qp && a.resid && C; break;
+        case kEpiResidFq: ok = a.post_qp && a.resid && a.C; break;
         case kEpiQkvCodes:
             ok = a.post_qp && a.out8 && a.code_T >= 1 && a.code_hd >= 8 && !(a.out8_mask && a.code_hd % 32 != 0) && (a.code_hd & (a.code_hd - 1)) == 0 && M < (1 << 22) &&
                  N / 3 < 1024 && a.code_T < 1024 && (N / 3) % a.code_hd == 0 && a.post_qmax - a.post_qmin < 256;
@@ -1274,9 +1261,22 @@ int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const
     if (!ok) { set_error("gemm_nt_i8: incomplete arguments for epilogue mode %d", mode); return 1; }
     // the K = 384 two-pass GEMMs (qkv, fc1: statistics pass, code passes) on the A-stationary strip kernel (i8strip.hip) when the weight came in
     // fragment order too; everything else (plain fp32 output, K != 384, the inference epilogues) on the general tall tile below
-    if (post && launch_i8_strip(A8, B8f, wsum, a_qp, center, M, N, K, lda, ldc, s1, s2, col_scale, bias, stats, stat_slots, st, post, false, late)) return 0;
-    if (late) { set_error("gemm_nt_i8: late qparams exist in the strip kernel only (i8_strip_covers)"); return 1; }
+    if (post && launch_i8_strip(g, post, st)) return 0;
+    if (g.late) { set_error("gemm_nt_i8: late qparams exist in the strip kernel only (i8_strip_covers)"); return 1; }
     return nt_launch<1, 3, 1, 13, 1, 8, 3, 32, true>(a, cdiv(M, 208) * (N / 384), (size_t)3 * (208 + 384) * 64, st);
+}
+
+int launch_gemm_nt(NTForm form, const NTGemm& g, const NTPost* post, hipStream_t st) {
+    if (form < 0 || form >= kNTForms) { set_error("gemm_nt: no operand form %d", (int)form); return 1; }
+    if (!nt_request_ok(form, g, post)) return 1;
+    NTArgs a = nt_args(form, g);
+    if (post) nt_set_post(a, *post, form == kNTPlaneF16);
+    switch (form) {
+    case kNTBf16: case kNTF16: return nt_pairs(a, post, form == kNTF16, st);
+    case kNTPlaneF16: case kNTPlaneBf16: return nt_planes(a, post, form == kNTPlaneBf16, st);
+    case kNTCodes: return nt_codes(a, post, st);
+    default: return nt_i8(a, g, post, st);   // kNTI8
+    }
 }
 
 // ============================================================================ TN (wgrad)

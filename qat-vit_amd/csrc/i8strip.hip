@@ -522,8 +522,9 @@ static bool strip_addressable(int M, int N, int lda, int ldc, int mode) {
 }
 // THE statement of what the strip kernel takes, the knob aside: i8_strip_covers answers with it before the statistics pass, launch_i8_strip launches by it.
 // has_s1 / has_stats / has_qp: the launch carries *s1, the accumulator (statistics pass), the output quantizer's qparams - ready or late (code passes)
-static bool strip_covered(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post, bool has_s1, bool has_stats, bool has_qp) {
-    if (!B8f || !post || (K != 384 && K != 768) || lda % 16 != 0 || !has_s1 || !strip_addressable(M, N, lda, ldc, post->mode) || !strip_ntl(N, K)) return false;
+static bool strip_covered(const NTGemm& g, const NTPost* post, bool has_s1, bool has_stats, bool has_qp) {
+    const int N = g.N, K = g.K, ldc = g.ldc;
+    if (!g.B_frag || !post || (K != 384 && K != 768) || g.lda % 16 != 0 || !has_s1 || !strip_addressable(g.M, N, g.lda, ldc, post->mode) || !strip_ntl(N, K)) return false;
     if (post->mode == kEpiStats) return has_stats;
     if (!has_qp || !post->out8 || !post->out8_mask || post->qmax - post->qmin >= 256) return false;
     if (post->mode == kEpiQkvCodes) return post->code_hd == 64 && (N / 3) % 384 == 0 && post->code_T >= 1 && post->code_T < 1024;
@@ -532,33 +533,36 @@ static bool strip_covered(const void* B8f, int M, int N, int K, int lda, int ldc
     return false;
 }
 // (the engine's question concerns a launch that will carry s1, the accumulator and - late_in_strip - the late record)
-bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post) {
-    return knobs().i8_strip && strip_covered(B8f, M, N, K, lda, ldc, post, true, true, true);
+bool i8_strip_covers(const NTGemm& g, const NTPost* post) { return knobs().i8_strip && strip_covered(g, post, true, true, true); }
+// THE copy of a request's operands into the kernel's argument record
+static I8StripArgs strip_args(const NTGemm& g) {
+    I8StripArgs a{};
+    a.A = reinterpret_cast<const int8_t*>(g.A); a.Bf = reinterpret_cast<const i32x4*>(g.B_frag); a.M = g.M; a.N = g.N; a.lda = g.lda;
+    a.s1 = g.s1; a.s2 = g.s2; a.col_scale = g.col_scale; a.bias = g.bias; a.wsum = g.wsum; a.aqp = g.a_qp; a.center = g.center;
+    return a;
 }
 
 // The LN form takes the requests the statistics pass takes whose workgroups own ALL columns of their rows (one workgroup per strip: nobody else
 // would write the same codes again) - qkv / fc1 of ViT-S (K = 384, N = 1152 / 1536) and of ViT-B (K = 768, N = 2304 / 3072)
-bool i8_strip_ln_covers(const void* B8f, int M, int N, int K, int lda) {
+bool i8_strip_ln_covers(const NTGemm& g) {
     NTPost p1{};
-    p1.mode = kEpiStats;
-    return knobs().ln_strip && lda >= K && i8_strip_covers(B8f, M, N, K, lda, N, &p1) && N == strip_ntl(N, K) * 384 && (int64_t)M * K < (1ll << 31);
+    p1.mode = kEpiStats;   // (a statistics pass: no check reads ldc)
+    return knobs().ln_strip && g.lda >= g.K && i8_strip_covers(g, &p1) && g.N == strip_ntl(g.N, g.K) * 384 && (int64_t)g.M * g.K < (1ll << 31);
 }
-bool launch_i8_strip_ln(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int ln_qmin, int ln_qmax, void* out8,
-                        const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, const float* s2,
-                        const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, bool force, const QpLate* ln_late) {
-    if ((!(knobs().i8_strip && knobs().ln_strip) && !force) || !x || !mean || !rstd || !gamma || !beta || !out8 || !B8f || !wsum || !stats || (K != 384 && K != 768) ||
-        lda % 16 != 0 || lda < K || M < 1 || !strip_addressable(M, N, lda, N, kEpiStats) || (int64_t)M * K >= (1ll << 31))
+bool launch_i8_strip_ln(const NTGemm& g, const StripLn& ln, hipStream_t st, bool force) {
+    const int M = g.M, N = g.N, K = g.K, lda = g.lda;
+    if ((!(knobs().i8_strip && knobs().ln_strip) && !force) || !ln.x || !ln.mean || !ln.rstd || !ln.gamma || !ln.beta || !ln.out8 || !g.B_frag || !g.wsum || !g.stats ||
+        (K != 384 && K != 768) || lda % 16 != 0 || lda < K || M < 1 || !strip_addressable(M, N, lda, N, kEpiStats) || (int64_t)M * K >= (1ll << 31))
         return false;
     const int ntl = strip_ntl(N, K);
     if (!ntl || N != ntl * 384) return false;
-    if (!(ln_late && ln_late->stats) && !a_qp) return false;
-    I8StripArgs a{};
-    a.A = reinterpret_cast<const int8_t*>(out8); a.Bf = reinterpret_cast<const i32x4*>(B8f); a.M = M; a.N = N; a.lda = lda;
-    a.s1 = nullptr; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.wsum = wsum; a.aqp = a_qp; a.center = center;
-    a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
-    a.ln_x = x; a.ln_mean = mean; a.ln_rstd = rstd; a.ln_gamma = gamma; a.ln_beta = beta; a.ln_out8 = reinterpret_cast<int8_t*>(out8);
-    a.ln_qmin = ln_qmin; a.ln_qmax = ln_qmax;
-    if (ln_late) a.ln_late = *ln_late;
+    if (!(ln.late && ln.late->stats) && !g.a_qp) return false;
+    I8StripArgs a = strip_args(g);
+    a.A = reinterpret_cast<const int8_t*>(ln.out8); a.s1 = nullptr;
+    a.stats = g.stats; a.stat_slots = g.stat_slots < 1 ? 1 : g.stat_slots;
+    a.ln_x = ln.x; a.ln_mean = ln.mean; a.ln_rstd = ln.rstd; a.ln_gamma = ln.gamma; a.ln_beta = ln.beta; a.ln_out8 = reinterpret_cast<int8_t*>(ln.out8);
+    a.ln_qmin = ln.qmin; a.ln_qmax = ln.qmax;
+    if (ln.late) a.ln_late = *ln.late;
     if (K == 768) { if (ntl == 8) strip_launch_ln<8, 7, 12>(a, st); else strip_launch_ln<6, 7, 12>(a, st); }
     else if (ntl == 4) strip_launch_ln<4>(a, st); else strip_launch_ln<3>(a, st);
     return true;
@@ -571,28 +575,24 @@ static void strip_launch_shape(const I8StripArgs& a, int N, int K, hipStream_t s
     else if (ntl == 4) strip_launch<MODE, 4>(a, st); else strip_launch<MODE, 3>(a, st);
 }
 // true when the strip kernel covers the request (it then launched it); false -> the general tall kernel.  force: ignore the knob, nothing else
-bool launch_i8_strip(const void* A8, const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, int ldc,
-                     const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
-                     const NTPost* post, bool force, const QpLate* late) {
+bool launch_i8_strip(const NTGemm& g, const NTPost* post, hipStream_t st, bool force) {
     if (!knobs().i8_strip && !force) return false;
-    if (!strip_covered(B8f, M, N, K, lda, ldc, post, s1 != nullptr, stats != nullptr, (post && post->qp) || (late && late->stats))) return false;
-    I8StripArgs a{};
-    a.A = reinterpret_cast<const int8_t*>(A8); a.Bf = reinterpret_cast<const i32x4*>(B8f); a.M = M; a.N = N; a.lda = lda;
-    a.s1 = s1; a.s2 = s2; a.col_scale = col_scale; a.bias = bias; a.wsum = wsum; a.aqp = a_qp; a.center = center;
+    if (!strip_covered(g, post, g.s1 != nullptr, g.stats != nullptr, (post && post->qp) || (g.late && g.late->stats))) return false;
+    I8StripArgs a = strip_args(g);
     if (post->mode == kEpiStats) {
-        a.stats = stats; a.stat_slots = stat_slots < 1 ? 1 : stat_slots;
-        strip_launch_shape<kEpiStats>(a, N, K, st);
+        a.stats = g.stats; a.stat_slots = g.stat_slots < 1 ? 1 : g.stat_slots;
+        strip_launch_shape<kEpiStats>(a, g.N, g.K, st);
         return true;
     }
     a.qp = post->qp; a.qmin = post->qmin; a.qmax = post->qmax;
-    if (late) a.late = *late;
+    if (g.late) a.late = *g.late;
     a.out8 = reinterpret_cast<uint8_t*>(post->out8); a.out8_mask = reinterpret_cast<uint8_t*>(post->out8_mask);
     if (post->mode == kEpiQkvCodes) {
-        a.code_T = post->code_T; a.D = N / 3;
-        strip_launch_shape<kEpiQkvCodes>(a, N, K, st);
+        a.code_T = post->code_T; a.D = g.N / 3;
+        strip_launch_shape<kEpiQkvCodes>(a, g.N, g.K, st);
     } else {   // kEpiCodes
-        a.ldc = ldc; a.lut_out = post->lut_out; a.lutq_out = post->lutq_out; a.out16_scale = post->out16_scale;
-        strip_launch_shape<kEpiCodes>(a, N, K, st);
+        a.ldc = g.ldc; a.lut_out = post->lut_out; a.lutq_out = post->lutq_out; a.out16_scale = post->out16_scale;
+        strip_launch_shape<kEpiCodes>(a, g.N, g.K, st);
     }
     return true;
 }

@@ -175,17 +175,26 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
     auto aidx = [&](int blk, int k) { return 2 + 6 * blk + k; };                // norm1, qkv, proj, norm2, fc1, fc2
     auto widx = [&](int blk, int k) { return 1 + 4 * blk + k; };                // qkv, proj, fc1, fc2
     auto wsum = [&](int wi) { return reinterpret_cast<const int32_t*>(ws + p.wsum[wi]); };
-    const float* s_pt = nullptr;   // per-tensor weight scale pointer, or the per-channel vector
-    auto scal = [&](int wi, const float** s2, const float** cs) {
-        if (c.w_per_channel) { *s2 = nullptr; *cs = w_scale[wi]; } else { *s2 = w_scale[wi]; *cs = nullptr; }
+    // the product of layer wi over `rows` rows without its operands: C = (A . w^T) * (*s1) * s_w + bias, the weight scale as the scalar s2 (per-tensor) or the
+    // column vector col_scale (per-channel)
+    auto request = [&](int wi, int rows, const float* s1, const float* bias, float* C = nullptr) {
+        NTGemm g;
+        iwshape(d, wi, &g.N, &g.K);
+        g.M = rows; g.lda = g.ldb = g.K; g.ldc = g.N; g.C = C; g.s1 = s1; g.bias = bias;
+        (c.w_per_channel ? g.col_scale : g.s2) = w_scale[wi];
+        return g;
     };
-    (void)s_pt;
+    // ... on int8 operands (kNTI8): A8 = q - center of activation quantizer ai
+    auto request8 = [&](int wi, int rows, const void* A8, int ai, const float* bias, float* C = nullptr) {
+        NTGemm g = request(wi, rows, qp(ai), bias, C);
+        g.A = A8; g.B = w8[wi]; g.wsum = wsum(wi); g.a_qp = qp(ai); g.center = center;
+        return g;
+    };
     float* xA = reinterpret_cast<float*>(ws + p.xA);
     float* xB = reinterpret_cast<float*>(ws + p.xB);
     void* h8 = ws + p.h8;
     void* codes = ws + p.codes;
     float* scal16 = reinterpret_cast<float*>(ws + p.scal16);
-    const float *s2, *cs;
 
     // ---- embedding: input fake-quant -> int8 patches; patch GEMM whose epilogue fake-quantises, adds pos_embed and scatters to token rows
     if (launch_img_patches(images, nullptr, qp(0), qa, qb, d.B, c.in_chans, c.img_size, c.img_size, c.patch_size, st, ws + p.imgq8, center)) return 1;
@@ -193,10 +202,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
     {
         NTPost post{};
         post.mode = kEpiResidFq; post.qp = qp(1); post.qmin = qa; post.qmax = qb; post.resid = prm(3); post.embed_np = d.np;
-        scal(0, &s2, &cs);
-        if (launch_gemm_nt_i8(ws + p.imgq8, w8[0], wsum(0), qp(0), center, xA, d.B * d.np, d.D, d.Kpe, d.Kpe, d.Kpe, d.D, qp(0), s2, cs, prm(1), nullptr, 1, st,
-                              &post))
-            return 1;
+        if (launch_gemm_nt(kNTI8, request8(0, d.B * d.np, ws + p.imgq8, 0, prm(1), xA), &post, st)) return 1;
     }
     for (int i = 0; i < d.depth; ++i) {
         // norm1 -> qkv (codes straight into the attention layout)
@@ -207,12 +213,9 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
             // (with the weight in fragment order and a place for the mask bits nobody reads here, the launcher takes the A-stationary strip kernel:
             //  the same codes bit for bit - head_dim 64, K = 384 / 768; the general tile otherwise)
             const int wq = widx(i, 0);
-            const void* b8f = (p.w8f[wq] >= 0 && hd == 64) ? ws + p.w8f[wq] : nullptr;
-            if (b8f) post.out8_mask = ws + p.qkvm;
-            scal(wq, &s2, &cs);
-            if (launch_gemm_nt_i8(h8, w8[wq], wsum(wq), qp(aidx(i, 0)), center, nullptr, M, 3 * d.D, d.D, d.D, d.D, 3 * d.D, qp(aidx(i, 0)), s2, cs,
-                                  bprm(i, 3), nullptr, 1, st, &post, b8f))
-                return 1;
+            NTGemm g = request8(wq, M, h8, aidx(i, 0), bprm(i, 3));
+            if (p.w8f[wq] >= 0 && hd == 64) { g.B_frag = ws + p.w8f[wq]; post.out8_mask = ws + p.qkvm; }
+            if (launch_gemm_nt(kNTI8, g, &post, st)) return 1;
         }
         // attention from the code plane -> fp16 pair; proj adds fq(.) into the residual stream
         if (launch_attn_fwd(nullptr, qp(aidx(i, 1)), qa, qb, d.B, d.T, d.H, d.D, nullptr, nullptr, nullptr, st, ws + p.O16_hi, ws + p.O16_lo, scal16, codes, nullptr))
@@ -220,10 +223,9 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
         {
             NTPost post{};
             post.mode = kEpiResidFq; post.qp = qp(aidx(i, 2)); post.qmin = qa; post.qmax = qb; post.resid = xA;
-            scal(widx(i, 1), &s2, &cs);
-            if (launch_gemm_nt(ws + p.O16_hi, ws + p.O16_lo, ws + p.w16[widx(i, 1)], xB, M, d.D, d.D, d.D, d.D, d.D, scal16, s2, cs, bprm(i, 5), nullptr, 1, st,
-                               nullptr, &post, true))
-                return 1;
+            NTGemm g = request(widx(i, 1), M, scal16, bprm(i, 5), xB);
+            g.A = ws + p.O16_hi; g.A_lo = ws + p.O16_lo; g.B = ws + p.w16[widx(i, 1)];
+            if (launch_gemm_nt(kNTF16, g, &post, st)) return 1;
         }
         // norm2 -> fc1 (one pass: quantise + GELU table + fp16 pair) -> fc2 adds fq(.) into the residual stream
         if (launch_ln_quant8(xB, bprm(i, 6), bprm(i, 7), c.ln_eps, qp(aidx(i, 3)), qa, qb, center, h8, nullptr, nullptr, d.M, 1, d.D, st)) return 1;
@@ -238,19 +240,16 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
             uint32_t* const glut = reinterpret_cast<uint32_t*>(ws + p.glut);
             if (strip) { post.out8 = ws + p.G8; post.out8_mask = ws + p.Gm; post.lut_out = glut; post.lutq_out = glut + 256; }
             else { post.out16_hi = ws + p.G16_hi; post.out16_lo = ws + p.G16_lo; }
-            scal(w1, &s2, &cs);
-            if (launch_gemm_nt_i8(h8, w8[w1], wsum(w1), qp(aidx(i, 3)), center, nullptr, M, d.Hd, d.D, d.D, d.D, d.Hd, qp(aidx(i, 3)), s2, cs,
-                                  bprm(i, 9), nullptr, 1, st, &post, strip ? ws + p.w8f[w1] : nullptr))
-                return 1;
+            NTGemm g1 = request8(w1, M, h8, aidx(i, 3), bprm(i, 9));
+            if (strip) g1.B_frag = ws + p.w8f[w1];
+            if (launch_gemm_nt(kNTI8, g1, &post, st)) return 1;
             NTPost post2{};
             post2.mode = kEpiResidFq; post2.qp = qp(aidx(i, 5)); post2.qmin = qa; post2.qmax = qb; post2.resid = xB;
-            scal(w2, &s2, &cs);
-            if (strip) {
-                if (launch_gemm_nt_codes(ws + p.G8, glut, ws + p.w16[w2], xA, M, d.D, d.Hd, d.Hd, d.Hd, d.D, scal16 + 1, s2, cs, bprm(i, 11), nullptr, 1, st, &post2))
-                    return 1;
-            } else if (launch_gemm_nt(ws + p.G16_hi, ws + p.G16_lo, ws + p.w16[w2], xA, M, d.D, d.Hd, d.Hd, d.Hd, d.D, scal16 + 1, s2, cs, bprm(i, 11), nullptr, 1, st,
-                                      nullptr, &post2, true))
-                return 1;
+            NTGemm g2 = request(w2, M, scal16 + 1, bprm(i, 11), xA);
+            g2.B = ws + p.w16[w2];
+            if (strip) { g2.A = ws + p.G8; g2.lut = glut; }
+            else { g2.A = ws + p.G16_hi; g2.A_lo = ws + p.G16_lo; }
+            if (launch_gemm_nt(strip ? kNTCodes : kNTF16, g2, &post2, st)) return 1;
         }
     }
     // ---- final norm on the cls rows, head, logits fake-quant

@@ -48,27 +48,27 @@ struct QpLate {
 constexpr int kQpStagedWords = 8;
 
 // ---- the epilogues of the NT GEMMs: NTPost::mode, and the kernels' template parameter (PM of k_gemm_nt, MODE of k_i8_strip).  post == nullptr is kEpiPlain; a
-// post record names one of the others.  THE table (launchers: nt = launch_gemm_nt on bf16, nt16 = its fp16 form, i8 = launch_gemm_nt_i8, strip = launch_i8_strip,
-// codes = launch_gemm_nt_codes, dy16 = launch_gemm_nt_dy16, f16strip = launch_f16_strip_gelu_bwd); qp / qmin / qmax = the quantizer every mode but 0 / 2 / 3 applies:
-//   mode               stores                                                                          NTPost fields read                              launchers
+// post record names one of the others.  THE table (forms: the NTForm of launch_gemm_nt, below - bf16 = kNTBf16, f16 = kNTF16, i8 = kNTI8, codes = kNTCodes,
+// plane = kNTPlaneF16; strip = launch_i8_strip, f16strip = launch_f16_strip_gelu_bwd); qp / qmin / qmax = the quantizer every mode but 0 / 2 / 3 applies:
+//   mode               stores                                                                          NTPost fields read                              forms
 //   kEpiPlain      0   C fp32; min / max of C -> stats                                                 -                                               all
-//   kEpiGeluFwd    2   (hi, lo) of gelu(C): bf16, or (out_f16) fp16, where out_lo may be NULL          out_hi out_lo out_f16                           nt, nt16 (teacher fc1)
-//   kEpiStats      3   nothing; min / max -> stats (first pass of a recomputed K = 384 / 768 GEMM)     -                                               nt, i8, strip
-//   kEpiCodes      4   gelu(fq(C)), whichever planes are set: bf16 (hi, lo) + uint16 code              out_hi out_lo code | out16_hi out16_lo           nt (bf16 pair + code), i8,
+//   kEpiGeluFwd    2   (hi, lo) of gelu(C): bf16, or (out_f16) fp16, where out_lo may be NULL          out_hi out_lo out_f16                           bf16, f16 (teacher fc1)
+//   kEpiStats      3   nothing; min / max -> stats (first pass of a recomputed K = 384 / 768 GEMM)     -                                               bf16, i8, strip
+//   kEpiCodes      4   gelu(fq(C)), whichever planes are set: bf16 (hi, lo) + uint16 code              out_hi out_lo code | out16_hi out16_lo           bf16 (bf16 pair + code), i8,
 //                      (q - qmin) | in_range << 15; fp16 (hi, lo) * 2^k with *out16_scale = 2^-k;      out16_scale | out8 out8_mask lut_out lutq_out    strip (out8 + out8_mask +
 //                      uint8 grid index [M, ldc] + STE mask bits [M, ldc / 8] + the 256-entry tables                                                    both tables only)
 //                      of fp16 / bf16 (hi | lo << 16) pairs of gelu(grid value) (fc1 second pass)
-//   kEpiGeluBwdU16 5   (hi, lo) of C * gelu'(grid value) * in_range * colscale, from uint16 codes      code colscale out_hi out_lo                     nt
-//   kEpiResidFq    6   C[orow] = resid[rrow] + fq(acc), frozen qp (embed_np > 0: input row b * np + p  resid embed_np                                  nt16, i8, codes
+//   kEpiGeluBwdU16 5   (hi, lo) of C * gelu'(grid value) * in_range * colscale, from uint16 codes      code colscale out_hi out_lo                     bf16
+//   kEpiResidFq    6   C[orow] = resid[rrow] + fq(acc), frozen qp (embed_np > 0: input row b * np + p  resid embed_np                                  f16, i8, codes
 //                      -> token row b * (np + 1) + 1 + p, resid = pos_embed rows 1 + p)
 //   kEpiQkvCodes   7   out8 = clamp(q) - qmin as uint8 in the attention layout [b][h][which][t][d];    out8 out8_mask code_T code_hd                   i8, strip
 //                      out8_mask (optional; head_dim % 32 == 0): the STE mask bits in the same order
-//   kEpiLnBwd      8   C = dx_out = dx_in + LNbwd(acc * alpha * mask(LN(x))), dgamma / dbeta += ;      lnb_* colscale out_hi out_lo                    nt (split A), dy16
-//                      (out_hi set) the (hi, lo) of dx_out * nmask * colscale for the next branch.     (dy16: o16_mul o16_amax, no out_lo)
+//   kEpiLnBwd      8   C = dx_out = dx_in + LNbwd(acc * alpha * mask(LN(x))), dgamma / dbeta += ;      lnb_* colscale out_hi out_lo                    bf16 (split A), plane
+//                      (out_hi set) the (hi, lo) of dx_out * nmask * colscale for the next branch.     (plane: o16_mul o16_amax, no out_lo)
 //                      N == ldc == 384: the tile holds whole LayerNorm rows; qp = the LN output's
-//   kEpiGeluBwdU8  9   as 5, from one byte per code + one mask bit per element                         code8 code_mask colscale out_hi out_lo          nt (split A), dy16, f16strip
-//                      (bit c % 8 of byte (row * ldc + c) / 8): what mode 4 leaves in out8 / out8_mask (dy16 / f16strip: o16_mul o16_amax, no out_lo)
-//   dy16 / f16strip emit the gradient as ONE fp16 plane (out_hi) of value * (*o16_mul) and accumulate max |value| into o16_amax (dy16.hip: Dy16Slot::amax).
+//   kEpiGeluBwdU8  9   as 5, from one byte per code + one mask bit per element                         code8 code_mask colscale out_hi out_lo          bf16 (split A), plane, f16strip
+//                      (bit c % 8 of byte (row * ldc + c) / 8): what mode 4 leaves in out8 / out8_mask (plane / f16strip: o16_mul o16_amax, no out_lo)
+//   plane / f16strip emit the gradient as ONE fp16 plane (out_hi) of value * (*o16_mul) and accumulate max |value| into o16_amax (dy16.hip: Dy16Slot::amax).
 // The numbers are fixed: qatvit_i8_strip takes 3 / 4 / 7 (include/qatvit.h), -DQV_NT_EXPERIMENTS=<mode> and tools/stamp_nt.py / stamp_i8strip.py pass them.
 enum NTEpi : int {
     kEpiPlain = 0, kEpiGeluFwd = 2, kEpiStats = 3, kEpiCodes = 4, kEpiGeluBwdU16 = 5, kEpiResidFq = 6, kEpiQkvCodes = 7, kEpiLnBwd = 8, kEpiGeluBwdU8 = 9
@@ -91,7 +91,7 @@ struct NTPost {
     void* out8 = nullptr;
     void* out8_mask = nullptr;
     int code_T = 0, code_hd = 0;
-    uint32_t* lut_out = nullptr;    // fp16 pairs: the A operand of launch_gemm_nt_codes with out8 (fc2 forward from 1 B per element)
+    uint32_t* lut_out = nullptr;    // fp16 pairs: the A operand of kNTCodes with out8 (fc2 forward from 1 B per element)
     uint32_t* lutq_out = nullptr;   // bf16 pairs: the kTNPairCodes weight gradient (fc2)
     const void* code8 = nullptr;
     const void* code_mask = nullptr;
@@ -108,51 +108,51 @@ struct NTPost {
     uint32_t* o16_amax = nullptr;
 };
 
-// ---- gemm.hip  (all operands bf16; a float operand is a (hi, lo) pair, lo == nullptr for a grid operand)
-int launch_gemm_nt(const void* A_hi, const void* A_lo, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1,
-                   const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
-                   const void* B_lo = nullptr, const NTPost* post = nullptr, bool f16 = false);   // f16: A_hi / A_lo / B hold fp16 bit patterns
-int launch_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const float* a_qp, int center, float* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots,
-                      hipStream_t st, const NTPost* post = nullptr,
-                      const void* B8f = nullptr,   // B8f: the same weight integers in fragment order (launch_w8_fragment_order): enables the strip kernel
-                      const QpLate* late = nullptr);
-// The one-plane backward ("dY as one fp16 plane"): the dgrad C[M,N] = A16[M,K] . B16[N,K]^T * (*s1) * (*s2) with the gradient
-// operand A16 as ONE fp16 plane pre-scaled by a power of two (its inverse arrives in *s2) and the transposed weight integers B16 as fp16 (exact):
-// one v_mfma_f32_16x16x32_f16 pass, 2 B per gradient element.  post: nullptr (plain fp32 output: proj dgrad), mode 8 (fused LayerNorm backward)
-// or mode 9 (fused GELU backward) with o16_mul / o16_amax set - the masked gradient for the next layer then leaves as one fp16 plane too.
-// N % 384 == 0, K % 32 == 0 (the fused modes 8 / 9: K % 64 == 0 - they exist on the 64-wide ring only).  bf16 (plain output only): both operands hold bf16 bit patterns, v_mfma_f32_16x16x32_bf16 (the float step's bf16 form).
-int launch_gemm_nt_dy16(const void* A16, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1, const float* s2,
-                        hipStream_t st, const NTPost* post = nullptr, bool bf16 = false);
-// ---- f16strip.hip: the fc2 dgrad + GELU backward of the one-plane backward, A-stationary (K = 384, N = 1536); B16f = the transposed weight integers as fp16 in
-// fragment order (w8f_offset on their 768-byte rows).  true when it took the request; false -> launch_gemm_nt_dy16 with epilogue mode 9
-bool launch_f16_strip_gelu_bwd(const void* A16, const void* B16f, float* unused, int M, int N, int K, int lda, int ldc, const float* s1, const float* s2, hipStream_t st,
-                               const NTPost* post);
-// ---- i8strip.hip: the K = 384 two-pass forward GEMMs (qkv, fc1), A-stationary; returns true when it covered (and launched) the request
-bool launch_i8_strip(const void* A8, const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, int ldc,
-                     const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st,
-                     const NTPost* post, bool force = false, const QpLate* late = nullptr);   // late (code passes): the output quantizer's qparams are resolved inside
-// would launch_i8_strip take this request, given s1, the accumulator (statistics pass) and ready or late qparams (code passes)?  The same predicate as the
-// launcher's; the knob applies (the engine decides on it BEFORE the statistics pass whether a k_qparams launch has to follow it)
-bool i8_strip_covers(const void* B8f, int M, int N, int K, int lda, int ldc, const NTPost* post);
+// ---- the NT GEMMs (gemm.hip): one request record, six named operand forms, one launcher.  A request computes, for the epilogue its NTPost names (NTEpi above),
+//   C[m, n] = (sum_k A[m, k] * B[n, k]) * (*s1) * (*s2) * col_scale[n] + bias[n]        min / max of the stored values -> stats (stat_slots pairs)
+// THE table (every form: M >= 1, ldc % 4 == 0; lda / ldb count elements of A / B as stored; s1, s2, col_scale, bias, stats optional; pair = (hi, lo) planes whose sum is the value; integers = grid values, exact):
+//   form              A, A_lo                         B, B_lo                                 required        N %, K %, lda %, ldb %   epilogues (NTEpi numbers)
+//   kNTBf16       0   bf16 plane (integers) or pair   bf16 plane (integers) or pair (A too)   -               128, 64, 8, 8            0 2 3 4 5; 8 9: A_lo, no B_lo, N % 384 == 0
+//   kNTF16        1   fp16 plane or pair              fp16 plane (integers), -                -               384, 64, 8, 8            0; 6: A_lo; 2: out_f16
+//   kNTI8         2   int8 q - center, -              int8 integers, -                        wsum [N], a_qp  384, 64, 16, 16          0 3 4 6 7
+//   kNTCodes      3   uint8 indices of lut, -         fp16 plane (integers), -                A, B, C, lut    384, 64, 16, 8           0 6
+//   kNTPlaneF16   4   ONE fp16 plane of value * 2^e   fp16 plane (integers), -                A, B            384, 32, 8, 8            0; 8 9: o16_mul / o16_amax, K % 64 == 0
+//   kNTPlaneBf16  5   ONE bf16 plane                  bf16 plane, -                           A, B            384, 32, 8, 8            0
+// lut: 256 packed fp16 (hi | lo << 16) pairs, A is expanded through it inside the kernel.  wsum / a_qp / center: the row sums of B and the A operand's quantizer {scale, 1 / scale,
+// zero point, ..}: C = (acc + (center - zp) * wsum[n]) * ..; with B_frag the strip kernel takes what launch_i8_strip covers, and `late` (the output quantizer's qparams resolved in a
+// code pass) exists there only.  The plane forms are the one-plane backward ("dY as one fp16 plane"): *s2 = 2^-e.  A field a form's row does not name is not read.
+enum NTForm : int { kNTBf16 = 0, kNTF16 = 1, kNTI8 = 2, kNTCodes = 3, kNTPlaneF16 = 4, kNTPlaneBf16 = 5, kNTForms = 6 };
+struct NTGemm {   // one NT GEMM without its epilogue
+    const void* A = nullptr; const void* A_lo = nullptr; const void* B = nullptr; const void* B_lo = nullptr;
+    const void* B_frag = nullptr;      // B once more, in the strip kernels' fragment order (i8strip.hip: int8, w8f_offset; f16strip.hip: fp16 on 768-byte rows)
+    const uint32_t* lut = nullptr; const int32_t* wsum = nullptr; const float* a_qp = nullptr; int center = 0;
+    float* C = nullptr; int M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;   // C: fp32 [M, ldc]
+    const float* s1 = nullptr; const float* s2 = nullptr; const float* col_scale = nullptr; const float* bias = nullptr;   // scalars; [N]
+    uint32_t* stats = nullptr; int stat_slots = 1; const QpLate* late = nullptr;
+};
+int launch_gemm_nt(NTForm form, const NTGemm& g, const NTPost* post, hipStream_t st);
+// ---- f16strip.hip: the fc2 dgrad + GELU backward of the one-plane backward, A-stationary (K = 384, N = 1536): a kNTPlaneF16 request with epilogue mode 9 whose
+// B_frag holds the transposed weight integers as fp16 in fragment order (B, ldb, C unread).  true when it took the request; false -> launch_gemm_nt
+bool launch_f16_strip_gelu_bwd(const NTGemm& g, const NTPost* post, hipStream_t st);
+// ---- i8strip.hip: the K = 384 / 768 two-pass forward GEMMs (qkv, fc1), A-stationary: a kNTI8 request read through B_frag (B, ldb, C unread; the code passes
+// take g.late).  true when it covered (and launched) the request; force: whatever the knob says
+bool launch_i8_strip(const NTGemm& g, const NTPost* post, hipStream_t st, bool force = false);
+// would launch_i8_strip take this request (B_frag, M, N, K, lda, ldc), given s1, the accumulator (statistics pass) and ready or late qparams (code passes)?  The
+// same predicate as the launcher's; the knob applies (the engine decides on it BEFORE the statistics pass whether a k_qparams launch has to follow it)
+bool i8_strip_covers(const NTGemm& g, const NTPost* post);
 // The statistics pass with the LayerNorm apply + quantise in its prologue (k_ln_apply_quant's work, the same bits): every workgroup builds its strip from the
 // fp32 rows x [M, K] (mean / rstd [M], gamma / beta [K]), keeps it in LDS and stores it to out8 [M, lda] (q - center), the plane the code pass and the weight
-// gradients read.  The A operand's quantizer is ln_late (resolved inside; workgroup 0 publishes it) or, without it, the ready a_qp; *s1 of launch_i8_strip is
-// that quantizer's scale.  i8_strip_ln_covers: would it take the request (QATVIT_LN_STRIP, one workgroup per strip: N == 3 / 4 (K = 768: 6 / 8) x 384)?
-bool launch_i8_strip_ln(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int ln_qmin, int ln_qmax, void* out8,
-                        const void* B8f, const int32_t* wsum, const float* a_qp, int center, int M, int N, int K, int lda, const float* s2,
-                        const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, bool force = false,
-                        const QpLate* ln_late = nullptr);
-bool i8_strip_ln_covers(const void* B8f, int M, int N, int K, int lda);
+// gradients read.  The A operand's quantizer is `late` (resolved inside; workgroup 0 publishes it) or, without it, the ready g.a_qp; g.A, g.s1 (that quantizer's
+// scale) and g.ldc are not read.  i8_strip_ln_covers: would it take B_frag, M, N, K, lda (QATVIT_LN_STRIP, one workgroup per strip: N == 3 / 4 (K = 768: 6 / 8) x 384)?
+struct StripLn { const float *x = nullptr, *mean = nullptr, *rstd = nullptr, *gamma = nullptr, *beta = nullptr; int qmin = 0, qmax = 0; void* out8 = nullptr; const QpLate* late = nullptr; };
+bool launch_i8_strip_ln(const NTGemm& g, const StripLn& ln, hipStream_t st, bool force = false);
+bool i8_strip_ln_covers(const NTGemm& g);
 // byte offset of element (n, k) of an [N, K] int8 weight in fragment order: [48-column group][64-deep k-step][16-column fragment][lane = 16 (k % 64 / 16) + n % 16][k % 16]
 __host__ __device__ inline int64_t w8f_offset(int n, int k, int K) {
     const int cg = n / 48, cr = n % 48, j = cr / 16, r = cr % 16, kt = k / 64, kk = k % 64;
     return ((((int64_t)cg * (K / 64) + kt) * 3 + j) * 64 + (kk / 16) * 16 + r) * 16 + (kk % 16);
 }
 int launch_w8_fragment_order(const void* B8, void* B8f, int N, int K, hipStream_t st);   // N % 48 == 0, K % 64 == 0
-// A operand = uint8 grid indices [M, lda] expanded through lut[256] (packed fp16 hi | lo << 16 pairs) inside the kernel; B16 = weight integers as fp16
-int launch_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* s1,
-                         const float* s2, const float* col_scale, const float* bias, uint32_t* stats, int stat_slots, hipStream_t st, const NTPost* post = nullptr);
 // ---- the weight gradients (TN GEMMs of gemm.hip): one request record, six named operand forms, two launchers.  A request computes
 //   C[n, kw] += mask(W)[n, kw] * sum_m P[m, n] * X[m, kw] * (*s1) * (*s2) / row_div[n]        dbias[n] += sum_m P[m, n] * (*s2) / row_div[n]
 // with the gradient P [M, ldp] and the layer input X [M, Kw] given by Q.  THE table (every form: N % 128 == 0, ldp % 8 == 0; ldq counts elements of Q as stored;

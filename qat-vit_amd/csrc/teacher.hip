@@ -467,8 +467,11 @@ static int teacher_forward_impl(const qatvit_cfg* cfg, void* const* params, void
     auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
     auto bprm = [&](int blk, int k) { return prm(4 + 12 * blk + k); };
     auto gemm = [&](const void* Ah, const void* Al, int wi, const float* bias, float* C, int Mrows, int N, int K, const NTPost* post = nullptr) {
-        if (f16) return launch_gemm_nt(Ah, passes == 1 ? nullptr : Al, w_hi[wi], C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, nullptr, 1, st, nullptr, post, true);
-        return launch_gemm_nt(Ah, Al, w_hi[wi], C, Mrows, N, K, K, K, N, nullptr, nullptr, nullptr, bias, nullptr, 1, st, w_lo[wi], post);
+        NTGemm g;
+        g.A = Ah; g.B = w_hi[wi]; g.C = C; g.M = Mrows; g.N = N; g.K = g.lda = g.ldb = K; g.ldc = N; g.bias = bias;
+        if (passes > 1) g.A_lo = Al;
+        if (!f16) g.B_lo = w_lo[wi];
+        return launch_gemm_nt(f16 ? kNTF16 : kNTBf16, g, post, st);
     };
     k_patches_split<<<flat_grid_t((int64_t)c.batch * np * Kpe / 4), 256, 0, st>>>(images, H16(p.p_hi), LO(p.p_lo), c.batch, c.in_chans, c.img_size,
                                                                                c.img_size, c.patch_size, f16);
