@@ -10,6 +10,7 @@
 
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -342,6 +343,7 @@ struct Ctx {
     template <typename T> T* blk(int64_t off, int i) const { return reinterpret_cast<T*>(ws + off + p.blk_stride * i); }
     const float* prm(int i) const { return reinterpret_cast<const float*>(params[i]); }
     const float* bprm(int blk_i, int k) const { return prm(P_BLOCK0 + B_COUNT * blk_i + k); }
+    int p_tail() const { return P_BLOCK0 + B_COUNT * d.depth; }   // the 4 tail parameters: final norm weight, bias, head weight, bias
     uint32_t* act_stats(int ai) const { return at<uint32_t>(p.stats) + (int64_t)ai * kStatSlots * kStatStride; }
     float* act_qp(int ai) const { return at<float>(p.qp_act) + 4 * ai; }
     float* w_qp(int wi) const { return at<float>(p.qp_w) + p.w_qp[wi]; }
@@ -349,6 +351,13 @@ struct Ctx {
     int a_norm() const { return A_BLOCK0 + AB_COUNT * d.depth; }
     int a_head() const { return a_norm() + 1; }
     int widx(int blk_i, int k) const { return 1 + WB_COUNT * blk_i + k; }
+    // One LayerNorm as its callers see it: the rows it normalises, their statistics, the affine parameters and the quantizer of its output.  norm1(depth) is the final norm
+    struct LnRows { float* x; float* mean; float* rstd; const float* gamma; const float* beta; int ai; };
+    LnRows norm1(int i) const {
+        if (i < d.depth) return LnRows{blk<float>(p.x_in, i), blk<float>(p.mean1, i), blk<float>(p.rstd1, i), bprm(i, B_N1W), bprm(i, B_N1B), aidx(i, AB_N1)};
+        return LnRows{blk<float>(p.x_in, d.depth), at<float>(p.meanF), at<float>(p.rstdF), prm(p_tail()), prm(p_tail() + 1), a_norm()};
+    }
+    LnRows norm2(int i) const { return LnRows{blk<float>(p.x_mid, i), blk<float>(p.mean2, i), blk<float>(p.rstd2, i), bprm(i, B_N2W), bprm(i, B_N2B), aidx(i, AB_N2)}; }
     // ---- late qparams (qv_kernels.h QpLate, Forms::late): the quantizers whose consumer kernel resolves the observer / qparams update itself - the
     // LayerNorm outputs (k_ln_apply_quant, or the statistics pass that has the LayerNorm in its prologue: ln_in_strip_of), the proj / fc2 outputs (k_resid_fq_lnstats) of every block always, the qkv / fc1 outputs where the strip
     // kernel's code pass is their consumer (decided by the caller: late_strip) - need no k_qparams launch behind the producer of their statistics
@@ -375,28 +384,28 @@ struct Ctx {
     void qparams_after(int ai, bool produced_stats, bool deferred = false) const {
         if (produced_stats && !deferred && !late_kind(ai)) qparams_act(ai);
     }
-    // launch_resid_fq_lnstats (Y = the output of quantizer ai_Y, -1: none) with the LayerNorm-output quantizer ai_stats updated behind it
-    int resid_lnstats(int mode, const float* x_prev, const float* Y, int ai_Y, const float* cls, const float* pos, float* x_new, float* mean,
-                      float* rstd, const float* gamma, const float* beta, int ai_stats, void* maskbits = nullptr) const {
+    // launch_resid_fq_lnstats (Y = the output of quantizer ai_Y, -1: none; x_new: the rows of `next`, or nullptr where they stand already) leaves the row
+    // statistics of the LayerNorm `next`, whose output quantizer is updated behind it
+    int resid_lnstats(int mode, const float* x_prev, const float* Y, int ai_Y, const float* cls, const float* pos, float* x_new, const LnRows& next,
+                      void* maskbits = nullptr) const {
         const bool lt = ai_Y >= 0 && late_kind(ai_Y);
         const QpLate L = lt ? late(ai_Y) : QpLate{};
-        if (launch_resid_fq_lnstats(mode, x_prev, Y, act_qp(ai_Y >= 0 ? ai_Y : 0), c.act_qmin, c.act_qmax, cls, pos, x_new, mean, rstd, gamma, beta, c.ln_eps,
-                                    act_stats(ai_stats), kStatSlots, d.M, d.D, d.T, st, maskbits, lt ? &L : nullptr))
+        if (launch_resid_fq_lnstats(mode, x_prev, Y, act_qp(ai_Y >= 0 ? ai_Y : 0), c.act_qmin, c.act_qmax, cls, pos, x_new, next.mean, next.rstd, next.gamma, next.beta,
+                                    c.ln_eps, act_stats(next.ai), kStatSlots, d.M, d.D, d.T, st, maskbits, lt ? &L : nullptr))
             return 1;
-        qparams_after(ai_stats, true);
+        qparams_after(next.ai, true);
         return 0;
     }
-    // launch_ln_apply_quant for the LayerNorm-output quantizer ai
-    int ln_apply(const float* xrow, const float* mean, const float* rstd, const float* gamma, const float* beta, int ai, void* out16, void* out8) const {
-        const bool lt = late_kind(ai);
-        const QpLate L = lt ? late(ai) : QpLate{};
+    // launch_ln_apply_quant for the LayerNorm r
+    int ln_apply(const LnRows& r, void* out16, void* out8) const {
+        const bool lt = late_kind(r.ai);
+        const QpLate L = lt ? late(r.ai) : QpLate{};
         // a QATVIT_FWD_X16 forward whose backward takes the byte plane (k_gemm_tn_q8) writes no 2-byte plane at all: the forward GEMM reads out8 too
         const bool x16 = (flags & QATVIT_FWD_X16) != 0;
-        return launch_ln_apply_quant(xrow, mean, rstd, gamma, beta, act_qp(ai), c.act_qmin, c.act_qmax, x16 && p.form.x_plane_from_q8 ? nullptr : out16, d.M, d.D,
-                                     st, p.form.i8 ? out8 : nullptr, center(), x16, lt ? &L : nullptr);
+        return launch_ln_apply_quant(r.x, r.mean, r.rstd, r.gamma, r.beta, act_qp(r.ai), c.act_qmin, c.act_qmax, x16 && p.form.x_plane_from_q8 ? nullptr : out16,
+                                     d.M, d.D, st, p.form.i8 ? out8 : nullptr, center(), x16, lt ? &L : nullptr);
     }
     // the same LayerNorm as the prologue of the statistics pass of layer wi (ln_in_strip_of): the pass builds the int8 plane out8 and reads it from its own LDS
-    struct LnRows { const float* x; const float* mean; const float* rstd; const float* gamma; const float* beta; int ai; };
     bool ln_in_strip(int kind) const { return ln_in_strip_of(p, d, flags, kind); }
     int linear_stats_ln(const LnRows& r, void* out8, int M, int wi, const float* bias, int ai_out, bool late_strip) const {
         const NTGemm g = grid_request(M, wi, out8, act_qp(r.ai), bias, ai_out);   // (A: the plane the pass itself writes)
@@ -482,6 +491,25 @@ struct Ctx {
         NTGemm g = fwd_request(M, wi); g.B_frag = w8f(wi);
         return p.form.late && i8_strip_covers(g, post2);
     }
+    // qkv (kind WB_QKV) or fc1 (WB_FC1) of block i as TWO passes of the same kernel on the same operands, so the same bits: the statistics pass only feeds the
+    // observer (min / max, nothing stored; with the LayerNorm in its prologue where ln_in_strip says so), the code pass quantises with the fresh qparams in its
+    // epilogue post2.  Where the strip kernel's code pass resolves the output quantizer's qparams itself there is no k_qparams launch between the passes
+    int two_pass(int i, int kind, const NTPost& post2) const {
+        const bool fc1 = kind == WB_FC1;
+        const LnRows r = fc1 ? norm2(i) : norm1(i);
+        const void* A16 = blk<void>(fc1 ? p.h2q : p.h1q, i);
+        void* A8 = blk<void>(fc1 ? p.h2q8 : p.h1q8, i);
+        const int M = (int)d.M, wi = widx(i, kind), ai_out = aidx(i, fc1 ? AB_FC1 : AB_QKV);
+        const float* bias = bprm(i, fc1 ? B_FC1B : B_QKVB);
+        const bool lt = late_in_strip(M, wi, &post2);
+        if (ln_in_strip(kind)) {
+            if (linear_stats_ln(r, A8, M, wi, bias, ai_out, lt)) return 1;
+        } else {
+            const NTPost post1 = nt_post_stats();
+            if (linear_fwd_grid(A16, A8, M, wi, act_qp(r.ai), bias, nullptr, ai_out, &post1, true, lt)) return 1;
+        }
+        return linear_fwd_grid(A16, A8, M, wi, act_qp(r.ai), bias, nullptr, ai_out, &post2, false, lt);
+    }
     // the per-channel weight scale of layer wi, which its dY producer folds in (nullptr for per-tensor)
     const float* dy_colscale(int wi) const { return c.w_per_channel ? wfq[wi].scale : nullptr; }
     // dgrad: dX[M,K] = dY[M,N] . W_fq[N,K] from the transposed weight; *s1 = the per-tensor weight scale (per-channel: dY already carries s_w[n]).  The request without its operands:
@@ -490,12 +518,6 @@ struct Ctx {
         wshape(d, wi, &g.K, &g.N);
         g.M = M; g.lda = g.ldb = g.K; g.ldc = g.N; g.C = dX; if (!c.w_per_channel) g.s1 = wfq[wi].scale;
         return g;
-    }
-    int linear_dgrad(const void* dY_hi, const void* dY_lo, int M, int wi, float* dX, const NTPost* post = nullptr) const {
-        NTGemm g = dgrad_request(M, wi, dX);
-        g.A = dY_hi; g.A_lo = dY_lo; g.B = at<void>(p.wT_off[wi]);
-        ProfScope ps(prof, prof_kind_dgrad(post), 2.0 * M * g.N * g.K, st);
-        return launch_gemm_nt(kNTBf16, g, post, st);
     }
     // The weight-gradient request of layer wi without its operands: dW[N,K] += sum_m dY[m,N] X[m,K] * s_x under the weight FQ's STE mask, db[N] += sum_m dY;
     // dy_scaled: dY carries the per-channel weight scale s_w[n] (folded in for the dgrad), row_div takes it out again
@@ -515,21 +537,6 @@ struct Ctx {
         k.scratch = at<float>(p.tn_scratch); k.scratch_bytes = kTnScratchBytes;
         return k;
     }
-    // X as uint8 table indices + a 256-entry bf16-pair table (fc2: X = gelu(fq(fc1 output)))
-    int linear_wgrad_codes(const void* dY_hi, const void* dY_lo, int M, int wi, const void* X8, const uint32_t* lutq, float* dW, float* db) const {
-        TNGemm g = wgrad_request(wi, dW, db);
-        g.P = dY_hi; g.P_lo = dY_lo; g.Q = X8; g.lut = lutq;
-        ProfScope ps(prof, 6, 2.0 * M * g.N * g.Kw, st);
-        return launch_gemm_tn(kTNPairCodes, g, wgrad_call(M), st);
-    }
-    // X as a bf16 grid plane (qkv / fc1 / patch-embed wgrad), or with X_lo a split float operand (proj / fc2 wgrad)
-    int linear_wgrad(const void* dY_hi, const void* dY_lo, int M, int wi, const void* X_hi, const void* X_lo, const float* s_x, float* dW, float* db,
-                     bool dy_scaled = true) const {
-        TNGemm g = wgrad_request(wi, dW, db, dy_scaled);
-        g.P = dY_hi; g.P_lo = dY_lo; g.Q = X_hi; g.Q_lo = X_lo; g.s1 = s_x;
-        ProfScope ps(prof, X_lo ? 6 : 3, 2.0 * M * g.N * g.Kw, st);
-        return launch_gemm_tn(kTNPair, g, wgrad_call(M), st);
-    }
 };
 
 // One transformer block of the forward, in four parts that each start where the stage-level parity tests inject the oracle's tensor (behind
@@ -539,42 +546,25 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
     const Dims& d = x.d;
     const Plan& p = x.p;
     const Forms& F = p.form;
-    const qatvit_cfg& c = x.c;
-    hipStream_t st = x.st;
-    const int qa = c.act_qmin, qb = c.act_qmax;
+    const int qa = x.c.act_qmin, qb = x.c.act_qmax;
     const int M = (int)d.M;
-    {
-        float* xin = x.blk<float>(p.x_in, i);
-        float* xmid = x.blk<float>(p.x_mid, i);
-        if (parts & 1) {   // ---- part 0: norm1 -> qkv   (every quantizer's observer / qparams update runs behind the producer of its statistics)
-        const bool ln1 = x.ln_in_strip(WB_QKV);   // norm1's apply + quantise runs inside qkv's statistics pass
-        if (!ln1)
-            x.ln_apply(xin, x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.aidx(i, AB_N1), x.blk<void>(p.h1q, i),
-                       x.blk<void>(p.h1q8, i));
+    const Ctx::LnRows n1 = x.norm1(i), n2 = x.norm2(i);   // (n1.x = x_in[i], n2.x = x_mid[i])
+    float* const scal16 = x.blk<float>(p.scal16, i);
+    if (parts & 1) {   // ---- part 0: norm1 -> qkv   (every quantizer's observer / qparams update runs behind the producer of its statistics)
+        if (!x.ln_in_strip(WB_QKV)) x.ln_apply(n1, x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i));   // (else norm1's apply + quantise runs inside qkv's statistics pass)
         if (F.qkv_2pass) {
             NTPost p2{};
             p2.mode = kEpiQkvCodes; p2.qp = x.act_qp(x.aidx(i, AB_QKV)); p2.qmin = qa; p2.qmax = qb;
             p2.out8 = x.blk<void>(p.qkv8, i); p2.out8_mask = x.blk<void>(p.qkvm, i); p2.code_T = (int)d.T; p2.code_hd = (int)(d.D / d.H);
-            const bool lt = x.late_in_strip(M, x.widx(i, WB_QKV), &p2);   // the code pass resolves the qkv quantizer's qparams itself: no k_qparams launch between the passes
-            const NTPost p1 = nt_post_stats();
-            if (ln1) {
-                const Ctx::LnRows r{xin, x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B), x.aidx(i, AB_N1)};
-                if (x.linear_stats_ln(r, x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.bprm(i, B_QKVB), x.aidx(i, AB_QKV), lt)) return 1;
-            } else if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(x.aidx(i, AB_N1)), x.bprm(i, B_QKVB), nullptr,
-                                         x.aidx(i, AB_QKV), &p1, true, lt))
-                return 1;
-            if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(x.aidx(i, AB_N1)), x.bprm(i, B_QKVB), nullptr,
-                                  x.aidx(i, AB_QKV), &p2, false, lt))
-                return 1;
-        } else if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(x.aidx(i, AB_N1)), x.bprm(i, B_QKVB),
-                                     x.blk<float>(p.qkv, i), x.aidx(i, AB_QKV)))
+            if (x.two_pass(i, WB_QKV, p2)) return 1;
+        } else if (x.linear_fwd_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), M, x.widx(i, WB_QKV), x.act_qp(n1.ai), x.bprm(i, B_QKVB), x.blk<float>(p.qkv, i),
+                                     x.aidx(i, AB_QKV)))
             return 1;
-        }
-        float* const scal16 = x.blk<float>(p.scal16, i);
-        if (parts & 2) {   // ---- part 1: attention -> proj -> residual (+ statistics of norm2)
+    }
+    if (parts & 2) {   // ---- part 1: attention -> proj -> residual (+ statistics of norm2)
         const bool from_codes = F.qkv_2pass && !qkv_injected;   // part 0 left the code plane (and ran the observer); an injected fp32 qkv takes the one-pass route
         if (launch_attn_fwd(from_codes ? nullptr : x.blk<float>(p.qkv, i), x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i),
-                            x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i), st, F.f16_proj ? x.blk<void>(p.O16_hi, i) : nullptr,
+                            x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i), x.st, F.f16_proj ? x.blk<void>(p.O16_hi, i) : nullptr,
                             F.f16_proj ? x.blk<void>(p.O16_lo, i) : nullptr, F.f16_proj ? scal16 : nullptr, F.attn_codes ? x.blk<void>(p.qkv8, i) : nullptr,
                             F.attn_codes ? x.blk<void>(p.qkvm, i) : nullptr))
             return 1;
@@ -585,41 +575,24 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
         } else if (x.linear_fwd(x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), M, x.widx(i, WB_PROJ), nullptr, x.bprm(i, B_PROJB),
                                 x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ)))
             return 1;
-        if (x.resid_lnstats(1, xin, x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ), nullptr, nullptr, xmid, x.blk<float>(p.mean2, i),
-                            x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.aidx(i, AB_N2), x.blk<void>(p.mproj, i)))
-            return 1;
-        }
-        if (parts & 4) {   // ---- part 2: norm2 -> fc1 (both passes) -> GELU
-        const bool ln2 = x.ln_in_strip(WB_FC1);   // norm2's apply + quantise runs inside fc1's statistics pass
-        if (!ln2)
-            x.ln_apply(xmid, x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.aidx(i, AB_N2), x.blk<void>(p.h2q, i),
-                       x.blk<void>(p.h2q8, i));
-        {
-            // fc1 is a K = D GEMM whose [M, 4D] fp32 output would be written once and read twice: run it TWICE instead.  Pass 1 only
-            // feeds the observer (min/max, nothing stored); pass 2 - the same kernel on the same operands, so the same bits - quantises
-            // with the fresh qparams and stores gelu(fq(.)) as the (hi, lo) pair fc2 reads plus a uint16 code (grid index | in-range
-            // bit) for the backward.  The fp32 pre-FQ tensor and the separate fq+gelu pass (620 MB per block) disappear.
-            NTPost p2{};
-            p2.mode = kEpiCodes; p2.qp = x.act_qp(x.aidx(i, AB_FC1)); p2.qmin = qa; p2.qmax = qb;
-            p2.out_hi = x.blk<void>(p.G_hi, i); p2.out_lo = x.blk<void>(p.G_lo, i); p2.code = x.blk<void>(p.Y1, i);
-            if (F.fc2_codes) { p2.out8 = x.blk<void>(p.G8, i); p2.lut_out = x.blk<uint32_t>(p.glut, i); p2.out16_scale = scal16 + 1; }
-            if (F.fc1_code_bits) { p2.code = nullptr; p2.out8_mask = x.blk<void>(p.Y1m, i); }   // the backward reads the byte plane + mask bits: no uint16 plane
-            if (F.fc2w_codes) { p2.out_hi = p2.out_lo = nullptr; p2.lutq_out = x.blk<uint32_t>(p.glutq, i); }   // no 4-byte plane of gelu(fq(fc1)) at all
-            else if (F.f16_fc2) { p2.out16_hi = x.at<void>(p.G16_hi); p2.out16_lo = x.at<void>(p.G16_lo); p2.out16_scale = scal16 + 1; }
-            const bool lt = x.late_in_strip(M, x.widx(i, WB_FC1), &p2);   // (as for qkv: the code pass resolves the fc1 quantizer's qparams)
-            const NTPost p1 = nt_post_stats();
-            if (ln2) {
-                const Ctx::LnRows r{xmid, x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.aidx(i, AB_N2)};
-                if (x.linear_stats_ln(r, x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.bprm(i, B_FC1B), x.aidx(i, AB_FC1), lt)) return 1;
-            } else if (x.linear_fwd_grid(x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.act_qp(x.aidx(i, AB_N2)), x.bprm(i, B_FC1B), nullptr,
-                                         x.aidx(i, AB_FC1), &p1, true, lt))
-                return 1;
-            if (x.linear_fwd_grid(x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i), M, x.widx(i, WB_FC1), x.act_qp(x.aidx(i, AB_N2)), x.bprm(i, B_FC1B), nullptr,
-                             x.aidx(i, AB_FC1), &p2, false, lt))
-                return 1;
-        }
-        }
-        if (parts & 8) {   // ---- part 3: fc2 -> residual (+ statistics of the next LayerNorm)
+        if (x.resid_lnstats(1, n1.x, x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ), nullptr, nullptr, n2.x, n2, x.blk<void>(p.mproj, i))) return 1;
+    }
+    if (parts & 4) {   // ---- part 2: norm2 -> fc1 (both passes) -> GELU
+        if (!x.ln_in_strip(WB_FC1)) x.ln_apply(n2, x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i));   // (else norm2's apply + quantise runs inside fc1's statistics pass)
+        // fc1 is a K = D GEMM whose [M, 4D] fp32 output would be written once and read twice: run it TWICE instead.  Pass 1 only
+        // feeds the observer (min/max, nothing stored); pass 2 - the same kernel on the same operands, so the same bits - quantises
+        // with the fresh qparams and stores gelu(fq(.)) as the (hi, lo) pair fc2 reads plus a uint16 code (grid index | in-range
+        // bit) for the backward.  The fp32 pre-FQ tensor and the separate fq+gelu pass (620 MB per block) disappear.
+        NTPost p2{};
+        p2.mode = kEpiCodes; p2.qp = x.act_qp(x.aidx(i, AB_FC1)); p2.qmin = qa; p2.qmax = qb;
+        p2.out_hi = x.blk<void>(p.G_hi, i); p2.out_lo = x.blk<void>(p.G_lo, i); p2.code = x.blk<void>(p.Y1, i);
+        if (F.fc2_codes) { p2.out8 = x.blk<void>(p.G8, i); p2.lut_out = x.blk<uint32_t>(p.glut, i); p2.out16_scale = scal16 + 1; }
+        if (F.fc1_code_bits) { p2.code = nullptr; p2.out8_mask = x.blk<void>(p.Y1m, i); }   // the backward reads the byte plane + mask bits: no uint16 plane
+        if (F.fc2w_codes) { p2.out_hi = p2.out_lo = nullptr; p2.lutq_out = x.blk<uint32_t>(p.glutq, i); }   // no 4-byte plane of gelu(fq(fc1)) at all
+        else if (F.f16_fc2) { p2.out16_hi = x.at<void>(p.G16_hi); p2.out16_lo = x.at<void>(p.G16_lo); p2.out16_scale = scal16 + 1; }
+        if (x.two_pass(i, WB_FC1, p2)) return 1;
+    }
+    if (parts & 8) {   // ---- part 3: fc2 -> residual (+ statistics of the next LayerNorm)
         if (F.fc2_codes) {
             if (x.linear_fwd_codes(x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glut, i), scal16 + 1, M, x.widx(i, WB_FC2), x.bprm(i, B_FC2B), x.blk<float>(p.Y2, i),
                                    x.aidx(i, AB_FC2)))
@@ -632,35 +605,18 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
                                 x.aidx(i, AB_FC2)))
             return 1;
         // residual + statistics of the NEXT LayerNorm (block i+1's norm1, or the final norm)
-        const bool last = (i + 1 == d.depth);
-        const float* g = last ? x.prm(P_BLOCK0 + B_COUNT * d.depth) : x.bprm(i + 1, B_N1W);
-        const float* bt = last ? x.prm(P_BLOCK0 + B_COUNT * d.depth + 1) : x.bprm(i + 1, B_N1B);
-        float* mean = last ? x.at<float>(p.meanF) : x.blk<float>(p.mean1, i + 1);
-        float* rstd = last ? x.at<float>(p.rstdF) : x.blk<float>(p.rstd1, i + 1);
-        if (x.resid_lnstats(1, xmid, x.blk<float>(p.Y2, i), x.aidx(i, AB_FC2), nullptr, nullptr, x.blk<float>(p.x_in, i + 1), mean, rstd, g, bt,
-                            last ? x.a_norm() : x.aidx(i + 1, AB_N1), x.blk<void>(p.m2, i)))
-            return 1;
-        }
-        return 0;
+        const Ctx::LnRows next = x.norm1(i + 1);
+        if (x.resid_lnstats(1, n2.x, x.blk<float>(p.Y2, i), x.aidx(i, AB_FC2), nullptr, nullptr, next.x, next, x.blk<void>(p.m2, i))) return 1;
     }
+    return 0;
 }
 
-// x_in[i] (the input of block i, or of the final norm for i == depth) was written into the workspace by the caller (teacher forcing in
-// the stage-level parity tests): compute what the producer of that tensor would have left behind for its consumer - the row mean / rstd
+// x_in[i] (the input of block i, or of the final norm for i == depth) or x_mid[i] - the rows of the LayerNorm r - was written into the workspace by the caller
+// (teacher forcing in the stage-level parity tests): compute what the producer of that tensor would have left behind for its consumer - the row mean / rstd
 // and the min/max of the LayerNorm output that the consumer's first fake-quant observes.
-static int inject_ln_stats_of(const Ctx& x, const float* tensor, const float* g, const float* bt, float* mean, float* rstd, int ai) {
-    launch_ws_init(x.act_stats(ai), kStatSlots * kStatStride / 2, x.st);   // whatever an earlier, unconsumed producer accumulated is stale
-    return x.resid_lnstats(2, tensor, nullptr, -1, nullptr, nullptr, nullptr, mean, rstd, g, bt, ai);
-}
-static int inject_ln_stats(const Ctx& x, int i) {
-    const Dims& d = x.d;
-    const Plan& p = x.p;
-    const bool last = (i == d.depth);
-    const float* g = last ? x.prm(P_BLOCK0 + B_COUNT * d.depth) : x.bprm(i, B_N1W);
-    const float* bt = last ? x.prm(P_BLOCK0 + B_COUNT * d.depth + 1) : x.bprm(i, B_N1B);
-    float* mean = last ? x.at<float>(p.meanF) : x.blk<float>(p.mean1, i);
-    float* rstd = last ? x.at<float>(p.rstdF) : x.blk<float>(p.rstd1, i);
-    return inject_ln_stats_of(x, x.blk<float>(p.x_in, i), g, bt, mean, rstd, last ? x.a_norm() : x.aidx(i, AB_N1));
+static int inject_ln_stats(const Ctx& x, const Ctx::LnRows& r) {
+    launch_ws_init(x.act_stats(r.ai), kStatSlots * kStatStride / 2, x.st);   // whatever an earlier, unconsumed producer accumulated is stale
+    return x.resid_lnstats(2, r.x, nullptr, -1, nullptr, nullptr, nullptr, r);
 }
 // one part of one block (fwd_block); `inject`: the part's input was written by the caller - part 0: x_in[block]; part 1: the pre-fake-quant
 // qkv[block] (x_in[block] is read as it stands); part 2: x_mid[block]; part 3: the GELU output planes (G_hi / G_lo, and G16_hi / G16_lo with
@@ -670,16 +626,14 @@ static int fwd_part(const Ctx& x, int block, int part, bool inject) {
     const Plan& p = x.p;
     if (inject) {
         if (part == 0) {
-            if (inject_ln_stats(x, block)) return 1;
+            if (inject_ln_stats(x, x.norm1(block))) return 1;
         } else if (part == 1) {
             const int ai = x.aidx(block, AB_QKV);
             launch_ws_init(x.act_stats(ai), kStatSlots * kStatStride / 2, x.st);
             launch_minmax(x.blk<float>(p.qkv, block), 1, d.M * 3 * d.D, 0, x.act_stats(ai), kStatSlots, x.st);
             x.qparams_act(ai);
         } else if (part == 2) {
-            if (inject_ln_stats_of(x, x.blk<float>(p.x_mid, block), x.bprm(block, B_N2W), x.bprm(block, B_N2B), x.blk<float>(p.mean2, block),
-                                   x.blk<float>(p.rstd2, block), x.aidx(block, AB_N2)))
-                return 1;
+            if (inject_ln_stats(x, x.norm2(block))) return 1;
         }
     }
     return fwd_block(x, block, 1 << part, inject && part == 1);
@@ -694,7 +648,7 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
     const qatvit_cfg& c = x.c;
     hipStream_t st = x.st;
     const int qa = c.act_qmin, qb = c.act_qmax;
-    if (inject && s_from >= 1 && inject_ln_stats(x, s_from - 1)) return 1;
+    if (inject && s_from >= 1 && inject_ln_stats(x, x.norm1(s_from - 1))) return 1;
     if (s_from == 0) {
     // a forward from the start observes from empty accumulators: statistics a partial call (a stage range) produced for a consumer that never ran do not leak
     // into this step (the late-resolved quantizers' accumulators are re-armed by their consumer's commit, not behind their producer)
@@ -752,19 +706,17 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
                            F.i8 ? x.at<void>(p.imgq8) : nullptr, x.center()))
         return 1;
     if (x.linear_fwd_grid(x.at<void>(p.imgq), x.at<void>(p.imgq8), d.B * d.np, 0, x.act_qp(A_IN), x.prm(P_PE_B), x.at<float>(p.Y0), A_PE)) return 1;
-    if (x.resid_lnstats(0, nullptr, x.at<float>(p.Y0), A_PE, x.prm(P_CLS), x.prm(P_POS), x.blk<float>(p.x_in, 0), x.blk<float>(p.mean1, 0),
-                        x.blk<float>(p.rstd1, 0), x.bprm(0, B_N1W), x.bprm(0, B_N1B), x.aidx(0, AB_N1)))
-        return 1;
+    const Ctx::LnRows n0 = x.norm1(0);
+    if (x.resid_lnstats(0, nullptr, x.at<float>(p.Y0), A_PE, x.prm(P_CLS), x.prm(P_POS), n0.x, n0)) return 1;
     }   // stage 0
     for (int i = (s_from < 1 ? 0 : s_from - 1); i < d.depth && i + 1 <= s_to; ++i)
         if (fwd_block(x, i, 15)) return 1;
     if (s_to < d.depth + 1) return 0;
     // ---- final norm (observer saw all tokens: updated behind the last block's residual kernel), cls pooling, head
-    const int base = P_BLOCK0 + B_COUNT * d.depth;
+    const Ctx::LnRows nf = x.norm1(d.depth);
     const int wh = d.n_w - 1;
-    launch_head_fwd(x.blk<float>(p.x_in, d.depth), x.at<float>(p.meanF), x.at<float>(p.rstdF), x.prm(base), x.prm(base + 1), x.act_qp(x.a_norm()),
-                    qa, qb, x.at<void>(p.w_off[wh]), x.wfq[wh].scale, c.w_per_channel, x.prm(base + 3), x.at<float>(p.hq), x.at<float>(p.logits_pre),
-                    x.act_stats(x.a_head()), kStatSlots, d.B, d.D, d.T, d.C, st);
+    launch_head_fwd(nf.x, nf.mean, nf.rstd, nf.gamma, nf.beta, x.act_qp(nf.ai), qa, qb, x.at<void>(p.w_off[wh]), x.wfq[wh].scale, c.w_per_channel,
+                    x.prm(x.p_tail() + 3), x.at<float>(p.hq), x.at<float>(p.logits_pre), x.act_stats(x.a_head()), kStatSlots, d.B, d.D, d.T, d.C, st);
     x.qparams_act(x.a_head());
     launch_logits_fq(x.at<float>(p.logits_pre), x.act_qp(x.a_head()), qa, qb, logits, d.B * d.C, st);
     return 0;
@@ -778,6 +730,32 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
 // x.flags & QATVIT_BWD_DY16: the one-plane form - every gradient that feeds a dgrad / wgrad pair (the masked residual gradient entering fc2 and proj,
 // the fc1 and qkv output gradients) is ONE fp16 plane scaled by a power of two chosen from the previous backward's maxima (dy16.hip) instead of a bf16
 // (hi, lo) pair: one MFMA pass and 2 B per element in eight GEMMs per block.  QATVIT_BWD_CALIBRATE: the pair form, recording those maxima.
+
+// A gradient that feeds a dgrad / wgrad pair.  lo set: a bf16 (hi, lo) pair.  lo == nullptr: ONE fp16 plane in hi, scaled by the power of two of slot (block, slot)
+// of the scale state (dy16.hip): its mul, amax and inv are Ctx::dy_mul, dy_slot and dy_inv of that slot (Bwd::mul / amax / inv)
+struct Grad { void* hi; void* lo; int slot; };
+// The layer input X of a weight gradient as the form at hand holds it; with the gradient's form it decides the TNForm (Bwd::wgrad)
+struct WX { const void* hi; const void* lo; const void* q8; const void* codes; const uint32_t* lut; const float* scale; };
+// grid integers with their quantizer: a 2-byte plane (bf16, one-plane form fp16) and - taken instead where k_gemm_tn_q8 applies - the same integers as q - center, one
+// byte each (the forward's int8 operand)
+static WX x_grid(const void* plane, const void* q8, const float* qp) { return WX{plane, nullptr, q8, nullptr, nullptr, qp}; }
+// a float operand: split into a bf16 (hi, lo) pair, or (one-plane form, lo == nullptr) rounded to fp16 like dY itself, times *scale
+static WX x_float(const void* hi, const void* lo, const float* scale) { return WX{hi, lo, nullptr, nullptr, nullptr, scale}; }
+// uint8 table indices + a 256-entry table of pairs (fc2: X = gelu(fq(fc1 output))): fp16 pairs times *scale in the one-plane form, bf16 pairs in the pair form
+static WX x_codes(const void* codes, const uint32_t* lut, const float* scale) { return WX{nullptr, nullptr, nullptr, codes, lut, scale}; }
+struct LnGrads { float* dgamma; float* dbeta; };
+// What the MLP and proj part of a block's backward reads and writes, over M rows: the full-height tensors of the Plan or, on the class-token rows (Bwd::cls), the
+// gathered forward operands and [B, .] gradients of Plan::ClsRows.  (The qkv part of a block is full height always.)
+struct BlockOps {
+    bool cls_rows;
+    int M;
+    Grad gy, gh, gp;                                     // the masked gradient entering fc2, the fc1 output gradient, the masked gradient entering proj
+    const void *G8, *Y1m, *h2q, *h2q8, *O16, *mproj;     // forward operands (O16: the attention output's fp16 hi plane)
+    Ctx::LnRows n2;
+    const float* dx;                                     // the gradient w.r.t. the block's output
+    float *dxB, *dO, *dH;                                // ... w.r.t. x_mid, w.r.t. the attention output; the unfused fc1 dgrad's output
+};
+
 struct Bwd {
     const Ctx& x;
     void* const* grads;
@@ -793,266 +771,245 @@ struct Bwd {
     double sflops[3] = {0.0, 0.0, 0.0};
 
     float* G(int i) const { return reinterpret_cast<float*>(grads[i]); }
-    float* BG(int blk_i, int k) const { return G(P_BLOCK0 + B_COUNT * blk_i + k); }
-    // the one-plane gradient planes of block blk_i - 0 fc2-in, 1 proj-in, 2 fc1-out, 3 qkv-out: one set per block where the weight gradients are deferred, else shared
-    void* plane(int blk_i, int which) const {
+    LnGrads dnorm1(int i) const { const int k = i < x.d.depth ? P_BLOCK0 + B_COUNT * i + B_N1W : x.p_tail(); return LnGrads{G(k), G(k + 1)}; }   // (depth: the final norm)
+    LnGrads dnorm2(int i) const { const int k = P_BLOCK0 + B_COUNT * i + B_N2W; return LnGrads{G(k), G(k + 1)}; }
+    // The gradient of slot `slot` (DS_*) of block blk_i in the form this call runs.  Pair form: the shared (hi, lo) buffers (fc2-in and proj-in are one pair).  One-plane
+    // form: the hi buffer of that pair, or - where the weight gradients are deferred - the block's own planes [fc2-in | proj-in | fc1-out | qkv-out]; rows: the [B, .]
+    // plane of the class-token rows
+    Grad grad(int blk_i, int slot, bool rows = false) const {
         const Plan& p = x.p;
-        if (!stream) return x.at<void>(which <= 1 ? p.dYs_hi : which == 2 ? p.dY1_hi : p.dqkv_hi);
-        return x.at<char>(p.dyp) + (int64_t)blk_i * p.dyp_stride + (which == 0 ? 0 : which == 1 ? p.dyp_p : which == 2 ? p.dyp_h : p.dyp_q);
+        if (rows) return Grad{x.at<void>(slot == DS_FC2 ? p.cls.dY : slot == DS_FC1 ? p.cls.dY1 : p.cls.dYp), nullptr, slot};
+        void* hi = x.at<void>(slot == DS_FC1 ? p.dY1_hi : slot == DS_QKV ? p.dqkv_hi : p.dYs_hi);
+        if (!dy) return Grad{hi, x.at<void>(slot == DS_FC1 ? p.dY1_lo : slot == DS_QKV ? p.dqkv_lo : p.dYs_lo), slot};
+        if (stream) hi = x.at<char>(p.dyp) + (int64_t)blk_i * p.dyp_stride + (slot == DS_FC2 ? 0 : slot == DS_PROJ ? p.dyp_p : slot == DS_FC1 ? p.dyp_h : p.dyp_q);
+        return Grad{hi, nullptr, slot};
     }
+    const float* mul(int blk_i, const Grad& g) const { return g.lo ? nullptr : x.dy_mul(blk_i, g.slot); }
+    uint32_t* amax(int blk_i, const Grad& g) const { return g.lo ? nullptr : x.dy_slot(blk_i, g.slot); }
+    const float* inv(int blk_i, const Grad& g) const { return g.lo ? nullptr : x.dy_inv(blk_i, g.slot); }
     // calibration: the maximum of a tensor the pair form just wrote (its hi plane) into the tensor's slot
-    void calib(const void* hi, int64_t n, int blk_i, int k) const { if (cal) launch_absmax_bf16(hi, n, x.dy_slot(blk_i, k), x.st); }
-    // NTPost mode 8: the dgrad GEMM into the output of block i's norm2 (n2) or norm1 runs that LayerNorm's backward in its epilogue (dx_in: the residual
-    // gradient it adds to) and emits nx's masked gradient of the branch output in front of it
-    NTPost lnb_post(int i, bool n2, const float* dx_in, const LnBwdNext& nx) const {
-        const Plan& p = x.p;
+    void calib(const Grad& g, int64_t n, int blk_i) const { if (cal) launch_absmax_bf16(g.hi, n, x.dy_slot(blk_i, g.slot), x.st); }
+    // What a LayerNorm backward leaves for the branch in front of it: g = split(dx_out * mask * colscale), the gradient entering layer wi of block blk_i (maskbits: the
+    // forward's STE bits of that layer's output)
+    LnBwdNext next(int blk_i, const Grad& g, const void* maskbits, int wi) const {
+        return LnBwdNext{maskbits, x.dy_colscale(wi), g.hi, g.lo, mul(blk_i, g), amax(blk_i, g)};
+    }
+    // launch_ln_bwd_fq for the LayerNorm r over M rows (dx_in: the residual gradient it adds to where acc)
+    int ln_bwd(int acc, const float* dH, const Ctx::LnRows& r, const LnGrads& dr, const float* dx_in, float* dx_out, int64_t M, int T, int cls_only,
+               const LnBwdNext* nx, int rows_per_wave = 16) const {
+        return launch_ln_bwd_fq(acc, dH, r.x, r.mean, r.rstd, r.gamma, r.beta, x.act_qp(r.ai), x.c.act_qmin, x.c.act_qmax, dx_in, dx_out, dr.dgamma, dr.dbeta, M, x.d.D, T,
+                                cls_only, x.st, nx, rows_per_wave);
+    }
+    // NTPost mode 8: the dgrad GEMM into the output of the LayerNorm r runs that LayerNorm's backward in its epilogue (dx_in: the residual gradient it adds to) and
+    // emits nx's masked gradient of the branch output in front of it
+    NTPost lnb_post(const Ctx::LnRows& r, const LnGrads& dr, const float* dx_in, const LnBwdNext& nx) const {
         NTPost post{};
-        post.mode = kEpiLnBwd; post.qp = x.act_qp(x.aidx(i, n2 ? AB_N2 : AB_N1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax;
-        post.lnb_x = x.blk<float>(n2 ? p.x_mid : p.x_in, i); post.lnb_mean = x.blk<float>(n2 ? p.mean2 : p.mean1, i); post.lnb_rstd = x.blk<float>(n2 ? p.rstd2 : p.rstd1, i);
-        post.lnb_gamma = x.bprm(i, n2 ? B_N2W : B_N1W); post.lnb_beta = x.bprm(i, n2 ? B_N2B : B_N1B); post.lnb_dx_in = dx_in;
-        post.lnb_dgamma = BG(i, n2 ? B_N2W : B_N1W); post.lnb_dbeta = BG(i, n2 ? B_N2B : B_N1B);
+        post.mode = kEpiLnBwd; post.qp = x.act_qp(r.ai); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax;
+        post.lnb_x = r.x; post.lnb_mean = r.mean; post.lnb_rstd = r.rstd; post.lnb_gamma = r.gamma; post.lnb_beta = r.beta; post.lnb_dx_in = dx_in;
+        post.lnb_dgamma = dr.dgamma; post.lnb_dbeta = dr.dbeta;
         post.lnb_nmask = nx.maskbits; post.colscale = nx.colscale; post.out_hi = nx.out_hi; post.out_lo = nx.out_lo;
         post.o16_mul = nx.o16_mul; post.o16_amax = nx.o16_amax;
         return post;
     }
-    // NTPost mode 9: the fc2 dgrad of block i applies the GELU backward and fc1's STE mask from the forward's byte codes + mask bits: the fc1 output gradient
-    NTPost gelu_post(int i, void* out_hi, void* out_lo) const {
+    // NTPost mode 9: the fc2 dgrad of block i applies the GELU backward and fc1's STE mask from the forward's byte codes + mask bits: the fc1 output gradient gh
+    NTPost gelu_post(int i, const Grad& gh, const void* G8, const void* Y1m) const {
         NTPost post{};
         post.mode = kEpiGeluBwdU8; post.qp = x.act_qp(x.aidx(i, AB_FC1)); post.qmin = x.c.act_qmin; post.qmax = x.c.act_qmax; post.colscale = x.dy_colscale(x.widx(i, WB_FC1));
-        post.out_hi = out_hi; post.out_lo = out_lo; post.code8 = x.blk<void>(x.p.G8, i); post.code_mask = x.blk<void>(x.p.Y1m, i);
+        post.out_hi = gh.hi; post.out_lo = gh.lo; post.code8 = G8; post.code_mask = Y1m;
+        post.o16_mul = mul(i, gh); post.o16_amax = amax(i, gh);
         return post;
     }
+    BlockOps operands(int i, bool rows, RowMoveTab* gather) const;
+    int wgrad(int i, int Mw, const Grad& g, int wi, const WX& X, bool cls_rows = false);
+    int dgrad(int i, int Md, const Grad& g, int wi, float* dX, const NTPost* post) const;
+    int dgrad_ln(int i, bool n2, const Ctx::LnRows& r, const Grad& g, const float* dx_in, float* dx_out, float* dH, const LnBwdNext& nx, int Md, bool cls_rows) const;
     int head(const float* dlogits);
-    int block_one_plane(int i, bool injected);
-    int block_pair(int i, bool injected);
+    int block(int i, bool injected);
     int embed();
     int flush();
 };
+
+// The operand set of block i's MLP and proj backward.  rows: every forward operand moves to its gathered copy and the move is listed in *gather - one list, so
+// what is gathered is what is read
+BlockOps Bwd::operands(int i, bool rows, RowMoveTab* gather) const {
+    const Dims& d = x.d;
+    const Plan& p = x.p;
+    const Plan::ClsRows& cr = p.cls;
+    BlockOps o;
+    o.cls_rows = rows;
+    o.M = rows ? d.B : (int)d.M;
+    o.gy = grad(i, DS_FC2, rows); o.gh = grad(i, DS_FC1, rows); o.gp = grad(i, DS_PROJ, rows);   // (gp: the same buffer as gy unless the weight gradients are deferred)
+    o.G8 = x.blk<void>(p.G8, i); o.Y1m = x.blk<void>(p.Y1m, i); o.h2q = x.blk<void>(p.h2q, i); o.h2q8 = x.blk<void>(p.h2q8, i);
+    o.O16 = x.blk<void>(p.O16_hi, i); o.mproj = x.blk<void>(p.mproj, i); o.n2 = x.norm2(i);
+    o.dx = rows ? x.at<float>(cr.dx) : dxA;
+    o.dxB = rows ? x.at<float>(cr.dxB) : dxB;
+    o.dO = x.at<float>(rows ? cr.dO : p.dO);
+    o.dH = x.at<float>(rows ? cr.dH : p.dH);
+    gather->n = 0;
+    if (!rows) return o;
+    auto to_rows = [&](auto*& ptr, int64_t off, int64_t width) {
+        gather->m[gather->n++] = RowMove{ptr, x.at<void>(off), width, (int)width};
+        ptr = static_cast<std::remove_reference_t<decltype(ptr)>>(x.at<void>(off));
+    };
+    const int64_t mrow = ln_maskbits_bytes(1, d.D);
+    const bool q8 = p.form.x_plane_from_q8;
+    to_rows(o.G8, cr.G8, d.Hd);
+    to_rows(o.Y1m, cr.Y1m, d.Hd / 8);
+    to_rows(q8 ? o.h2q8 : o.h2q, cr.h2q, q8 ? d.D : d.D * 2);   // ONE buffer holds whichever plane the fc1 weight gradient reads
+    o.h2q = o.h2q8 = q8 ? o.h2q8 : o.h2q;
+    to_rows(o.n2.x, cr.x_mid, (int64_t)d.D * 4);
+    to_rows(o.n2.mean, cr.mean2, 4);
+    to_rows(o.n2.rstd, cr.rstd2, 4);
+    to_rows(o.mproj, cr.mproj, mrow);
+    to_rows(o.O16, cr.O16, (int64_t)d.D * 2);
+    return o;
+}
+
+// The weight gradient of layer wi over Mw token rows from the gradient g of its output.  One-plane form: X as fp16 (grid integers; proj: the attention output rounded to
+// fp16 like dY itself: one pass), as q - center bytes where k_gemm_tn_q8 applies, or codes + a table of fp16 pairs; where the weight gradients are deferred it is
+// collected for one persistent launch per X form at the end of the call - unless it runs over the class-token rows: the deferred batch shares ONE token count
+int Bwd::wgrad(int i, int Mw, const Grad& g, int wi, const WX& X, bool cls_rows) {
+    const TNForm form = g.lo ? (X.codes ? kTNPairCodes : kTNPair) : (X.q8 && x.p.form.x_plane_from_q8) ? kTNPlaneQ8 : X.codes ? kTNPlaneCodes : kTNPlaneF16;
+    const int pw = wparam(x.d, wi);
+    TNGemm t = x.wgrad_request(wi, G(pw), G(pw + 1));   // (a layer's bias follows its weight in params[])
+    t.P = g.hi; t.P_lo = g.lo; t.Q = form == kTNPlaneQ8 ? X.q8 : X.codes ? X.codes : X.hi; t.Q_lo = X.lo; t.lut = X.lut; t.s1 = X.scale; t.s2 = inv(i, g);
+    const double flops = 2.0 * Mw * t.N * t.Kw;
+    if (stream && !cls_rows) {
+        sg[form].push_back(t);
+        sflops[form] += flops;
+        return 0;
+    }
+    ProfScope ps(x.prof, (X.codes || X.lo || wi == x.widx(i, WB_PROJ)) ? 6 : 3, flops, x.st);   // 6: X is a float operand, 3: grid integers
+    TNCall call = x.wgrad_call(Mw);
+    call.reduce_single = cls_rows;   // (B rows: the kernel's serial tail would be the run time)
+    return launch_gemm_tn(form, t, call, x.st);
+}
+
+// dgrad of layer wi over Md rows: the fp16 plane against the transposed weight integers as fp16 (s2 undoes the plane's scale), or the bf16 pair against them as bf16
+int Bwd::dgrad(int i, int Md, const Grad& g, int wi, float* dX, const NTPost* post) const {
+    NTGemm r = x.dgrad_request(Md, wi, dX);
+    r.A = g.hi; r.A_lo = g.lo; r.B = g.lo ? x.at<void>(x.p.wT_off[wi]) : x.wT16(wi); r.s2 = inv(i, g);
+    ProfScope ps(x.prof, prof_kind_dgrad(post), 2.0 * Md * r.N * r.K, x.st);
+    return launch_gemm_nt(g.lo ? kNTBf16 : kNTPlaneF16, r, post, x.st);
+}
+
+// THE dgrad into a LayerNorm output + that LayerNorm's backward, for block i's norm2 (n2: g = the fc1 output gradient) or norm1 (g = the qkv output gradient) over the
+// rows r: dx_out = dx_in + the gradient w.r.t. r.x, and nx's masked gradient of the branch output in front of the LayerNorm (a record without an output: none).
+// One GEMM with the LayerNorm backward in its epilogue (Forms::lnb), or the plain dgrad into dH and k_ln_bwd_fq.  On the class-token rows always the latter: two tiles of
+// the fused epilogue, one wave per row in sequence, take 70 us; the plain dgrad and k_ln_bwd_fq with one row per wave a third of it
+int Bwd::dgrad_ln(int i, bool n2, const Ctx::LnRows& r, const Grad& g, const float* dx_in, float* dx_out, float* dH, const LnBwdNext& nx, int Md, bool cls_rows) const {
+    const int wi = x.widx(i, n2 ? WB_FC1 : WB_QKV);
+    const LnGrads dr = n2 ? dnorm2(i) : dnorm1(i);
+    if (x.p.form.lnb && !cls_rows) {
+        const NTPost post = lnb_post(r, dr, dx_in, nx);
+        return dgrad(i, Md, g, wi, dx_out, &post);
+    }
+    if (dgrad(i, Md, g, wi, dH, nullptr)) return 1;
+    return ln_bwd(1, dH, r, dr, dx_in, dx_out, Md, x.d.T, 0, nx.out_hi ? &nx : nullptr, cls_rows ? 1 : 16);
+}
 
 int Bwd::head(const float* dlogits) {
     const Dims& d = x.d;
     const Plan& p = x.p;
     const qatvit_cfg& c = x.c;
-    const int base = P_BLOCK0 + B_COUNT * d.depth, wh = d.n_w - 1, last = d.depth - 1;
-    launch_head_bwd(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), c.act_qmin, c.act_qmax, x.at<float>(p.hq), x.act_qp(x.a_norm()),
+    const int base = x.p_tail(), wh = d.n_w - 1, last = d.depth - 1;
+    Ctx::LnRows nf = x.norm1(d.depth);
+    launch_head_bwd(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), c.act_qmin, c.act_qmax, x.at<float>(p.hq), x.act_qp(nf.ai),
                     x.at<void>(p.w_off[wh]), x.prm(base + 2), x.wfq[wh].scale, x.wfq[wh].zero_point, c.w_per_channel, c.w_qmin, c.w_qmax,
                     G(base + 2), G(base + 3), x.at<float>(p.dh), d.B, d.D, d.C, x.st);
+    const Grad gy = grad(last, DS_FC2, cls);   // the masked gradient entering the last block's fc2
+    const void* m2 = x.blk<void>(p.m2, last);
     if (cls) {   // the same kernel on the gathered class-token rows ([B, D], T = 1): the same bits in those rows, and neither the full dxA nor the full plane is written
         const Plan::ClsRows& r = p.cls;
         const int64_t mrow = ln_maskbits_bytes(1, d.D);
         RowMoveTab t;
         t.n = 4;
-        t.m[0] = RowMove{x.blk<void>(p.x_in, d.depth), x.at<void>(r.xF), (int64_t)d.D * 4, d.D * 4};
-        t.m[1] = RowMove{x.at<void>(p.meanF), x.at<void>(r.meanF), 4, 4};
-        t.m[2] = RowMove{x.at<void>(p.rstdF), x.at<void>(r.rstdF), 4, 4};
-        t.m[3] = RowMove{x.blk<void>(p.m2, last), x.at<void>(r.m2), mrow, (int)mrow};
+        t.m[0] = RowMove{nf.x, x.at<void>(r.xF), (int64_t)d.D * 4, d.D * 4};
+        t.m[1] = RowMove{nf.mean, x.at<void>(r.meanF), 4, 4};
+        t.m[2] = RowMove{nf.rstd, x.at<void>(r.rstdF), 4, 4};
+        t.m[3] = RowMove{m2, x.at<void>(r.m2), mrow, (int)mrow};
         if (launch_rows_gather(t, d.B, d.T, x.st)) return 1;
-        const LnBwdNext nx{x.at<void>(r.m2), x.dy_colscale(x.widx(last, WB_FC2)), x.at<void>(r.dY), nullptr, x.dy_mul(last, DS_FC2), x.dy_slot(last, DS_FC2)};
-        return launch_ln_bwd_fq(0, x.at<float>(p.dh), x.at<float>(r.xF), x.at<float>(r.meanF), x.at<float>(r.rstdF), x.prm(base), x.prm(base + 1), x.act_qp(x.a_norm()),
-                                c.act_qmin, c.act_qmax, nullptr, x.at<float>(r.dx), G(base), G(base + 1), d.B, d.D, 1, 0, x.st, &nx, 1);
+        nf.x = x.at<float>(r.xF); nf.mean = x.at<float>(r.meanF); nf.rstd = x.at<float>(r.rstdF);
+        const LnBwdNext nx = next(last, gy, x.at<void>(r.m2), x.widx(last, WB_FC2));
+        return ln_bwd(0, x.at<float>(p.dh), nf, dnorm1(d.depth), nullptr, x.at<float>(r.dx), d.B, 1, 0, &nx, 1);
     }
-    LnBwdNext nx{x.blk<void>(p.m2, last), x.dy_colscale(x.widx(last, WB_FC2)), plane(last, 0), x.at<void>(p.dYs_lo)};
-    if (dy) { nx.o16_mul = x.dy_mul(last, DS_FC2); nx.o16_amax = x.dy_slot(last, DS_FC2); }
-    if (launch_ln_bwd_fq(0, x.at<float>(p.dh), x.blk<float>(p.x_in, d.depth), x.at<float>(p.meanF), x.at<float>(p.rstdF), x.prm(base), x.prm(base + 1),
-                         x.act_qp(x.a_norm()), c.act_qmin, c.act_qmax, nullptr, dxA, G(base), G(base + 1), d.M, d.D, d.T, 1, x.st, &nx))
-        return 1;
-    calib(nx.out_hi, d.M * d.D, last, DS_FC2);
+    const LnBwdNext nx = next(last, gy, m2, x.widx(last, WB_FC2));
+    if (ln_bwd(0, x.at<float>(p.dh), nf, dnorm1(d.depth), nullptr, dxA, d.M, d.T, 1, &nx)) return 1;
+    calib(gy, d.M * d.D, last);
     return 0;
 }
 
-// one block, one-plane form.  Same dataflow as the pair form below; every dY is one fp16 plane in the hi buffer of the pair.
-int Bwd::block_one_plane(int i, bool injected) {
+// One block: the steps of its backward, once for both gradient forms (Grad).  MLP branch: [the masked fc2-in gradient, if the stage's input was injected]
+// -> fc2 wgrad -> fc2 dgrad + GELU' + fc1's STE mask -> fc1 wgrad -> fc1 dgrad + norm2's backward (leaves dxB and the masked proj-in gradient).  Attention branch:
+// proj wgrad -> proj dgrad -> attention backward -> qkv wgrad -> qkv dgrad + norm1's backward (leaves dxA and the next block's masked fc2-in gradient).  The pair form
+// records the maximum of every gradient right behind its producer when calibrating.
+// The MLP and proj part of the last block runs on the class-token rows (Bwd::cls): the same launchers over B rows of gathered operands (BlockOps); its three weight
+// gradients run right here (the deferred batch shares ONE token count); dxB goes back to full height, zeros elsewhere, for the qkv dgrad, and the attention
+// backward reads dO as [B, D] and sweeps the live query pair alone (dK, dV and the rest of the block are dense: every key and value reaches the class token)
+int Bwd::block(int i, bool injected) {
     const Dims& d = x.d;
     const Plan& p = x.p;
     const Forms& F = p.form;
-    const qatvit_cfg& c = x.c;
     hipStream_t st = x.st;
-    const int qa = c.act_qmin, qb = c.act_qmax;
+    const int qa = x.c.act_qmin, qb = x.c.act_qmax;
     const int M = (int)d.M;
-    // the MLP and proj part of the last block on the class-token rows (Bwd::cls): the same launchers over Mr = B rows of gathered operands; its three weight
-    // gradients run right here (the deferred batch shares ONE token count); dxB goes back to full height, zeros elsewhere, for the qkv dgrad, and the attention
-    // backward reads dO as [B, D] and sweeps the live query pair alone (dK, dV and the rest of the block are dense: every key and value reaches the class token)
     const bool rows = cls && i == d.depth - 1 && !injected;
-    const Plan::ClsRows& cr = p.cls;
-    const int Mr = rows ? d.B : M;
-    void* dY16 = rows ? x.at<void>(cr.dY) : plane(i, 0);      // the masked gradient entering fc2
-    void* dYp16 = rows ? x.at<void>(cr.dYp) : plane(i, 1);    // ... entering proj (the same buffer as dY16 unless the weight gradients are deferred)
-    void* dY1_16 = rows ? x.at<void>(cr.dY1) : plane(i, 2);
-    void* dqkv16 = plane(i, 3);
-    const void* G8 = rows ? x.at<void>(cr.G8) : x.blk<void>(p.G8, i);
-    const void* Y1m = rows ? x.at<void>(cr.Y1m) : x.blk<void>(p.Y1m, i);
-    const void* h2q = rows ? x.at<void>(cr.h2q) : x.blk<void>(p.h2q, i);      // (rows: ONE buffer holds whichever plane the fc1 weight gradient reads)
-    const void* h2q8 = rows ? x.at<void>(cr.h2q) : x.blk<void>(p.h2q8, i);
-    const void* O16 = rows ? x.at<void>(cr.O16) : x.blk<void>(p.O16_hi, i);
-    const float* x_mid = rows ? x.at<float>(cr.x_mid) : x.blk<float>(p.x_mid, i);
-    const float* mean2 = rows ? x.at<float>(cr.mean2) : x.blk<float>(p.mean2, i);
-    const float* rstd2 = rows ? x.at<float>(cr.rstd2) : x.blk<float>(p.rstd2, i);
-    const void* mproj = rows ? x.at<void>(cr.mproj) : x.blk<void>(p.mproj, i);
-    const float* dx_mlp = rows ? x.at<float>(cr.dx) : dxA;                     // the gradient w.r.t. the block's output
-    float* dxB_mlp = rows ? x.at<float>(cr.dxB) : dxB;
-    float* dO_proj = rows ? x.at<float>(cr.dO) : x.at<float>(p.dO);
-    float* dH_mlp = rows ? x.at<float>(cr.dH) : x.at<float>(p.dH);
+    RowMoveTab gather;
+    const BlockOps o = operands(i, rows, &gather);
+    const Grad gq = grad(i, DS_QKV);   // the qkv output gradient
     const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
     float* const scal16 = x.blk<float>(p.scal16, i);
-    if (rows) {
-        const int64_t mrow = ln_maskbits_bytes(1, d.D);
-        const bool q8 = F.x_plane_from_q8;
-        RowMoveTab t;
-        t.n = 8;
-        t.m[0] = RowMove{x.blk<void>(p.G8, i), x.at<void>(cr.G8), d.Hd, d.Hd};
-        t.m[1] = RowMove{x.blk<void>(p.Y1m, i), x.at<void>(cr.Y1m), d.Hd / 8, d.Hd / 8};
-        t.m[2] = RowMove{q8 ? x.blk<void>(p.h2q8, i) : x.blk<void>(p.h2q, i), x.at<void>(cr.h2q), q8 ? d.D : d.D * 2, q8 ? d.D : d.D * 2};
-        t.m[3] = RowMove{x.blk<void>(p.x_mid, i), x.at<void>(cr.x_mid), (int64_t)d.D * 4, d.D * 4};
-        t.m[4] = RowMove{x.blk<void>(p.mean2, i), x.at<void>(cr.mean2), 4, 4};
-        t.m[5] = RowMove{x.blk<void>(p.rstd2, i), x.at<void>(cr.rstd2), 4, 4};
-        t.m[6] = RowMove{x.blk<void>(p.mproj, i), x.at<void>(cr.mproj), mrow, (int)mrow};
-        t.m[7] = RowMove{x.blk<void>(p.O16_hi, i), x.at<void>(cr.O16), (int64_t)d.D * 2, d.D * 2};
-        if (launch_rows_gather(t, d.B, d.T, st)) return 1;
-    }
-    // wgrad of layer wi from the plane P16 (slot k): X as fp16 (grid integers; proj: the attention output rounded to fp16 like dY itself: one pass), or codes + a table
-    // of fp16 pairs (X8: the same grid integers as q - center, one byte each - the forward's int8 operand; taken instead of the fp16 plane where k_gemm_tn_q8 applies)
-    // (Mw token rows: M, or Mr for the MLP / proj part)
-    auto wgrad16 = [&](int Mw, const void* P16, int k, int wi, const void* X, const void* Xc, const uint32_t* lut, const float* s_x, float* dW, float* db,
-                       const void* X8 = nullptr) -> int {
-        const TNForm form = (X8 && F.x_plane_from_q8) ? kTNPlaneQ8 : Xc ? kTNPlaneCodes : kTNPlaneF16;
-        TNGemm g = x.wgrad_request(wi, dW, db);
-        g.P = P16; g.Q = form == kTNPlaneQ8 ? X8 : Xc ? Xc : X; g.lut = lut; g.s1 = s_x; g.s2 = x.dy_inv(i, k);
-        const double flops = 2.0 * Mw * g.N * g.Kw;
-        if (stream && Mw == M) {   // collected (M != Mr on class-token rows: T > 1): one persistent launch per X form at the end of the call
-            sg[form].push_back(g);
-            sflops[form] += flops;
-            return 0;
-        }
-        ProfScope ps(x.prof, (wi == w_proj || Xc) ? 6 : 3, flops, st);
-        TNCall call = x.wgrad_call(Mw);
-        call.reduce_single = rows && Mw == Mr;   // (B rows: the kernel's serial tail would be the run time)
-        return launch_gemm_tn(form, g, call, st);
-    };
-    auto dgrad16 = [&](int Md, const void* P16, int k, int wi, float* dX, const NTPost* post) -> int {
-        NTGemm g = x.dgrad_request(Md, wi, dX);
-        g.A = P16; g.B = x.wT16(wi); g.s2 = x.dy_inv(i, k);
-        ProfScope ps(x.prof, prof_kind_dgrad(post), 2.0 * Md * g.N * g.K, st);
-        return launch_gemm_nt(kNTPlaneF16, g, post, st);
-    };
+    if (rows && launch_rows_gather(gather, d.B, d.T, st)) return 1;
     // ---- MLP branch
-    if (injected)
-        launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, dY16, nullptr, d.M * d.D, st,
-                        x.dy_mul(i, DS_FC2), x.dy_slot(i, DS_FC2));
-    if (wgrad16(Mr, dY16, DS_FC2, w_fc2, nullptr, G8, x.blk<uint32_t>(p.glut, i), scal16 + 1, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
-    {   // fc2 dgrad + GELU backward + fc1's STE mask -> the fc1 output gradient, one plane
-        NTPost post = gelu_post(i, dY1_16, nullptr);
-        post.code8 = G8; post.code_mask = Y1m;
-        post.o16_mul = x.dy_mul(i, DS_FC1); post.o16_amax = x.dy_slot(i, DS_FC1);
+    if (injected) {
+        launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, o.gy.hi, o.gy.lo, d.M * d.D, st, mul(i, o.gy),
+                        amax(i, o.gy));
+        calib(o.gy, d.M * d.D, i);
+    }
+    const WX x_fc2 = dy             ? x_codes(o.G8, x.blk<uint32_t>(p.glut, i), scal16 + 1)
+                     : F.fc2w_codes ? x_codes(o.G8, x.blk<uint32_t>(p.glutq, i), nullptr)
+                                    : x_float(x.blk<void>(p.G_hi, i), x.blk<void>(p.G_lo, i), nullptr);
+    if (wgrad(i, o.M, o.gy, w_fc2, x_fc2, rows)) return 1;
+    {   // fc2 dgrad with the GELU backward + fc1's STE mask fused into its epilogue: dY1 = (dYs . W_fc2) * gelu'(fq(Y1)) * mask(Y1)
+        NTPost post = gelu_post(i, o.gh, o.G8, o.Y1m);
+        if (!F.fc1_code_bits) { post.mode = kEpiGeluBwdU16; post.code = x.blk<void>(p.Y1, i); post.code8 = post.code_mask = nullptr; }   // the Y1 slot holds the uint16 codes (pair form only: the one-plane form needs the code bits)
         bool strip = false;
-        if (x.wT16f_ok(w_fc2) && knobs().f16_strip) {   // the A-stationary strip form (f16strip.hip): the gradient plane fetched once for all four column tiles
-            ProfScope ps(x.prof, 5, 2.0 * Mr * d.D * d.Hd, st);
-            NTGemm g = x.dgrad_request(Mr, w_fc2);
-            g.A = dY16; g.B_frag = x.wT16f(w_fc2); g.s2 = x.dy_inv(i, DS_FC2);
+        if (dy && x.wT16f_ok(w_fc2) && knobs().f16_strip) {   // the A-stationary strip form (f16strip.hip): the gradient plane fetched once for all four column tiles
+            ProfScope ps(x.prof, 5, 2.0 * o.M * d.D * d.Hd, st);
+            NTGemm g = x.dgrad_request(o.M, w_fc2);
+            g.A = o.gy.hi; g.B_frag = x.wT16f(w_fc2); g.s2 = inv(i, o.gy);
             strip = launch_f16_strip_gelu_bwd(g, &post, st);
         }
-        if (!strip && dgrad16(Mr, dY16, DS_FC2, w_fc2, nullptr, &post)) return 1;
+        if (!strip && dgrad(i, o.M, o.gy, w_fc2, nullptr, &post)) return 1;
     }
-    if (wgrad16(Mr, dY1_16, DS_FC1, w_fc1, h2q, nullptr, nullptr, x.act_qp(x.aidx(i, AB_N2)), BG(i, B_FC1W), BG(i, B_FC1B), h2q8)) return 1;
-    const LnBwdNext nx_proj{mproj, x.dy_colscale(w_proj), dYp16, nullptr, x.dy_mul(i, DS_PROJ), x.dy_slot(i, DS_PROJ)};
-    if (F.lnb && !rows) {
-        const NTPost post = lnb_post(i, true, dxA, nx_proj);
-        if (dgrad16(M, dY1_16, DS_FC1, w_fc1, dxB, &post)) return 1;
-    } else {   // (B rows: two tiles of the fused epilogue, one wave per row in sequence, take 70 us; the plain dgrad and k_ln_bwd_fq with one row per wave a third of it)
-        if (dgrad16(Mr, dY1_16, DS_FC1, w_fc1, dH_mlp, nullptr)) return 1;
-        if (launch_ln_bwd_fq(1, dH_mlp, x_mid, mean2, rstd2, x.bprm(i, B_N2W), x.bprm(i, B_N2B), x.act_qp(x.aidx(i, AB_N2)), qa, qb, dx_mlp, dxB_mlp, BG(i, B_N2W),
-                             BG(i, B_N2B), Mr, d.D, d.T, 0, st, &nx_proj, rows ? 1 : 16))
-            return 1;
-    }
+    calib(o.gh, d.M * d.Hd, i);
+    if (wgrad(i, o.M, o.gh, w_fc1, x_grid(o.h2q, o.h2q8, x.act_qp(o.n2.ai)), rows)) return 1;
+    if (dgrad_ln(i, true, o.n2, o.gh, o.dx, o.dxB, o.dH, next(i, o.gp, o.mproj, w_proj), o.M, rows)) return 1;
     // ---- attention branch (dxB = gradient w.r.t. x_mid)
-    if (wgrad16(Mr, dYp16, DS_PROJ, w_proj, O16, nullptr, nullptr, scal16, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
-    if (dgrad16(Mr, dYp16, DS_PROJ, w_proj, dO_proj, nullptr)) return 1;
+    calib(o.gp, d.M * d.D, i);
+    const WX x_proj = dy ? x_float(o.O16, nullptr, scal16) : x_float(x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), nullptr);
+    if (wgrad(i, o.M, o.gp, w_proj, x_proj, rows)) return 1;
+    if (dgrad(i, o.M, o.gp, w_proj, o.dO, nullptr)) return 1;
     if (rows) {   // back to full height, zeros elsewhere, for the qkv dgrad's LayerNorm-1 epilogue (its dx_in): ONE streaming pass
         RowMoveTab t;
         t.n = 1;
-        t.m[0] = RowMove{dxB_mlp, dxB, (int64_t)d.D * 4, d.D * 4};
+        t.m[0] = RowMove{o.dxB, dxB, (int64_t)d.D * 4, d.D * 4};
         if (launch_rows_scatter(t, d.B, d.T, st)) return 1;
     }
-    // (rows: dO stays [B, D] - only query row 0 of every image carries a gradient, so the fused kernel sweeps the one query pair that holds it)
-    if (launch_attn_bwd(nullptr, x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), x.blk<float>(p.lse, i),
-                        x.at<float>(p.delta), dO_proj, dqkv16, nullptr, x.dy_colscale(w_qkv), st, x.blk<void>(p.qkv8, i), x.blk<void>(p.qkvm, i),
-                        x.dy_mul(i, DS_QKV), x.dy_slot(i, DS_QKV), rows ? 1 : 0, rows))
+    // The one-plane form reads the codes its forward saved, never the fp32 qkv.  (rows: dO stays [B, D] - only query row 0 of every image carries a gradient, so the
+    // fused kernel sweeps the one query pair that holds it)
+    if (launch_attn_bwd(dy ? nullptr : x.blk<float>(p.qkv, i), x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i),
+                        x.blk<float>(p.lse, i), x.at<float>(p.delta), o.dO, gq.hi, gq.lo, x.dy_colscale(w_qkv), st, F.attn_codes ? x.blk<void>(p.qkv8, i) : nullptr,
+                        F.attn_codes ? x.blk<void>(p.qkvm, i) : nullptr, mul(i, gq), amax(i, gq), rows ? 1 : 0, rows))
         return 1;
-    if (wgrad16(M, dqkv16, DS_QKV, w_qkv, x.blk<void>(p.h1q, i), nullptr, nullptr, x.act_qp(x.aidx(i, AB_N1)), BG(i, B_QKVW), BG(i, B_QKVB), x.blk<void>(p.h1q8, i)))
-        return 1;
-    // the next block's fc2-in plane (its own buffer when the weight gradients are deferred).  Block 0 emits no next-branch gradient; the fused epilogue still
-    // wants a scale / maximum target: its own qkv slot, which nothing reads afterwards
-    const LnBwdNext nx_fc2 = i > 0 ? LnBwdNext{x.blk<void>(p.m2, i - 1), x.dy_colscale(x.widx(i - 1, WB_FC2)), plane(i - 1, 0), nullptr, x.dy_mul(i - 1, DS_FC2),
-                                               x.dy_slot(i - 1, DS_FC2)}
-                                   : LnBwdNext{nullptr, nullptr, nullptr, nullptr, x.dy_mul(0, DS_QKV), x.dy_slot(0, DS_QKV)};
-    if (F.lnb) {
-        const NTPost post = lnb_post(i, false, dxB, nx_fc2);
-        return dgrad16(M, dqkv16, DS_QKV, w_qkv, dxA, &post);
-    }
-    if (dgrad16(M, dqkv16, DS_QKV, w_qkv, x.at<float>(p.dH), nullptr)) return 1;
-    return launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_in, i), x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B),
-                            x.act_qp(x.aidx(i, AB_N1)), qa, qb, dxB, dxA, BG(i, B_N1W), BG(i, B_N1B), d.M, d.D, d.T, 0, st, i > 0 ? &nx_fc2 : nullptr);
-}
-
-// one block, bf16 (hi, lo) pair form (also the calibrating step of the one-plane form)
-int Bwd::block_pair(int i, bool injected) {
-    const Dims& d = x.d;
-    const Plan& p = x.p;
-    const Forms& F = p.form;
-    const qatvit_cfg& c = x.c;
-    hipStream_t st = x.st;
-    const int qa = c.act_qmin, qb = c.act_qmax;
-    const int M = (int)d.M;
-    void* dYh = x.at<void>(p.dYs_hi);
-    void* dYl = x.at<void>(p.dYs_lo);
-    const int w_fc2 = x.widx(i, WB_FC2), w_fc1 = x.widx(i, WB_FC1), w_proj = x.widx(i, WB_PROJ), w_qkv = x.widx(i, WB_QKV);
-    // ---- MLP branch
-    if (injected) {
-        launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, dYh, dYl, d.M * d.D, st);
-        calib(dYh, d.M * d.D, i, DS_FC2);
-    }
-    if (F.fc2w_codes) {
-        if (x.linear_wgrad_codes(dYh, dYl, M, w_fc2, x.blk<void>(p.G8, i), x.blk<uint32_t>(p.glutq, i), BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
-    } else if (x.linear_wgrad(dYh, dYl, M, w_fc2, x.blk<void>(p.G_hi, i), x.blk<void>(p.G_lo, i), nullptr, BG(i, B_FC2W), BG(i, B_FC2B))) return 1;
-    {   // fc2 dgrad with the GELU backward + fc1's STE mask fused into its epilogue: dY1 = (dYs . W_fc2) * gelu'(fq(Y1)) * mask(Y1)
-        NTPost post = gelu_post(i, x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo));
-        if (!F.fc1_code_bits) { post.mode = kEpiGeluBwdU16; post.code = x.blk<void>(p.Y1, i); post.code8 = post.code_mask = nullptr; }   // the Y1 slot holds the uint16 codes
-        if (x.linear_dgrad(dYh, dYl, M, w_fc2, nullptr, &post)) return 1;
-    }
-    calib(x.at<void>(p.dY1_hi), d.M * d.Hd, i, DS_FC1);
-    if (x.linear_wgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, x.blk<void>(p.h2q, i), nullptr, x.act_qp(x.aidx(i, AB_N2)), BG(i, B_FC1W), BG(i, B_FC1B)))
-        return 1;
-    const LnBwdNext nx_proj{x.blk<void>(p.mproj, i), x.dy_colscale(w_proj), dYh, dYl};
-    if (F.lnb) {
-        const NTPost post = lnb_post(i, true, dxA, nx_proj);
-        if (x.linear_dgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, dxB, &post)) return 1;
-    } else {
-        if (x.linear_dgrad(x.at<void>(p.dY1_hi), x.at<void>(p.dY1_lo), M, w_fc1, x.at<float>(p.dH))) return 1;
-        if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_mid, i), x.blk<float>(p.mean2, i), x.blk<float>(p.rstd2, i), x.bprm(i, B_N2W), x.bprm(i, B_N2B),
-                             x.act_qp(x.aidx(i, AB_N2)), qa, qb, dxA, dxB, BG(i, B_N2W), BG(i, B_N2B), d.M, d.D, d.T, 0, st, &nx_proj))
-            return 1;
-    }
-    // ---- attention branch (dxB = gradient w.r.t. x_mid)
-    calib(dYh, d.M * d.D, i, DS_PROJ);
-    if (x.linear_wgrad(dYh, dYl, M, w_proj, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), nullptr, BG(i, B_PROJW), BG(i, B_PROJB))) return 1;
-    if (x.linear_dgrad(dYh, dYl, M, w_proj, x.at<float>(p.dO))) return 1;
-    if (launch_attn_bwd(x.blk<float>(p.qkv, i), x.act_qp(x.aidx(i, AB_QKV)), qa, qb, d.B, d.T, d.H, d.D, x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i),
-                        x.blk<float>(p.lse, i), x.at<float>(p.delta), x.at<float>(p.dO), x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), x.dy_colscale(w_qkv), st,
-                        F.attn_codes ? x.blk<void>(p.qkv8, i) : nullptr, F.attn_codes ? x.blk<void>(p.qkvm, i) : nullptr))
-        return 1;
-    calib(x.at<void>(p.dqkv_hi), d.M * 3 * d.D, i, DS_QKV);
-    if (x.linear_wgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, x.blk<void>(p.h1q, i), nullptr, x.act_qp(x.aidx(i, AB_N1)), BG(i, B_QKVW), BG(i, B_QKVB)))
-        return 1;
-    const LnBwdNext nx_fc2 = i > 0 ? LnBwdNext{x.blk<void>(p.m2, i - 1), x.dy_colscale(x.widx(i - 1, WB_FC2)), dYh, dYl} : LnBwdNext{nullptr, nullptr, nullptr, nullptr};
-    if (F.lnb) {
-        const NTPost post = lnb_post(i, false, dxB, nx_fc2);
-        if (x.linear_dgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, dxA, &post)) return 1;
-    } else {
-        if (x.linear_dgrad(x.at<void>(p.dqkv_hi), x.at<void>(p.dqkv_lo), M, w_qkv, x.at<float>(p.dH))) return 1;
-        if (launch_ln_bwd_fq(1, x.at<float>(p.dH), x.blk<float>(p.x_in, i), x.blk<float>(p.mean1, i), x.blk<float>(p.rstd1, i), x.bprm(i, B_N1W), x.bprm(i, B_N1B),
-                             x.act_qp(x.aidx(i, AB_N1)), qa, qb, dxB, dxA, BG(i, B_N1W), BG(i, B_N1B), d.M, d.D, d.T, 0, st, i > 0 ? &nx_fc2 : nullptr))
-            return 1;
-    }
-    if (i > 0) calib(dYh, d.M * d.D, i - 1, DS_FC2);
+    calib(gq, d.M * 3 * d.D, i);
+    if (wgrad(i, M, gq, w_qkv, x_grid(x.blk<void>(p.h1q, i), x.blk<void>(p.h1q8, i), x.act_qp(x.aidx(i, AB_N1))))) return 1;
+    // the next block's fc2-in gradient (its own plane when the weight gradients are deferred).  Block 0 emits no next-branch gradient; the one-plane form's fused
+    // epilogue still wants a scale / maximum target: its own qkv slot, which nothing reads afterwards
+    const LnBwdNext nx_fc2 = i > 0 ? next(i - 1, grad(i - 1, DS_FC2), x.blk<void>(p.m2, i - 1), x.widx(i - 1, WB_FC2))
+                                   : LnBwdNext{nullptr, nullptr, nullptr, nullptr, mul(0, gq), amax(0, gq)};
+    if (dgrad_ln(i, false, x.norm1(i), gq, dxB, dxA, x.at<float>(p.dH), nx_fc2, M, false)) return 1;
+    if (i > 0) calib(grad(i - 1, DS_FC2), d.M * d.D, i - 1);
     return 0;
 }
 
@@ -1061,8 +1018,12 @@ int Bwd::embed() {
     const Plan& p = x.p;
     launch_embed_bwd(dxA, x.at<float>(p.Y0), x.act_qp(A_PE), x.c.act_qmin, x.c.act_qmax, G(P_POS), G(P_CLS), x.at<void>(p.dY0_hi), x.at<void>(p.dY0_lo), d.B,
                      d.T, d.D, x.st);
-    // (no dgrad into the image, so dY0 is not pre-scaled by the per-channel weight scale)
-    return x.linear_wgrad(x.at<void>(p.dY0_hi), x.at<void>(p.dY0_lo), d.B * d.np, 0, x.at<void>(p.imgq), nullptr, x.act_qp(A_IN), G(P_PE_W), G(P_PE_B), false);
+    // the patch embedding's weight gradient: a bf16 pair against the bf16 grid plane of the image patches.  No dgrad into the image, so dY0 is not pre-scaled by the
+    // per-channel weight scale (dy_scaled = false)
+    TNGemm g = x.wgrad_request(0, G(P_PE_W), G(P_PE_B), false);
+    g.P = x.at<void>(p.dY0_hi); g.P_lo = x.at<void>(p.dY0_lo); g.Q = x.at<void>(p.imgq); g.s1 = x.act_qp(A_IN);
+    ProfScope ps(x.prof, 3, 2.0 * d.B * d.np * g.N * g.Kw, x.st);
+    return launch_gemm_tn(kTNPair, g, x.wgrad_call(d.B * d.np), x.st);
 }
 
 // the collected weight gradients: one persistent launch (+ its fix-up) per X form and <= 24 GEMMs
@@ -1091,7 +1052,7 @@ static int bwd(const Ctx& x, const float* dlogits, void* const* grads, int stage
     if ((dy || cal) && (stage_from == 0 || inject)) launch_dy16_begin(dystate, nslots, stage_from == 0 ? dlogits : nullptr, d.B * d.C, x.st);
     for (int s = stage_from; s <= stage_to; ++s) {
         const bool injected = inject && s == stage_from;
-        if (s == 0 ? b.head(dlogits) : s > d.depth ? b.embed() : dy ? b.block_one_plane(d.depth - s, injected) : b.block_pair(d.depth - s, injected)) return 1;
+        if (s == 0 ? b.head(dlogits) : s > d.depth ? b.embed() : b.block(d.depth - s, injected)) return 1;
     }
     // (the scale bookkeeping and the overflow flag first: they depend on the producers of the planes only, and the host's mirror of the flag - qatvit_student_dy16_set_mirror -
     //  is written here, 2 - 3 ms before the deferred weight gradients are done)
