@@ -570,6 +570,28 @@ int qatvit_optim_adamw_groups(const void* param_ptrs, const void* grad_ptrs, con
  *   (1, 0), lam = 1 - area / D^2 of the clamped box.  Identity: weights (1, 0), an empty box, lam = 1: the result is X[b].
  *   The kernel keeps a second set of resampled planes in LDS: a shape whose request exceeds 64 KB (S and D both near 384) is refused with an
  *   error string before any HIP call.  mix == NULL: qatvit_image_batch_aug.
+ *
+ * qatvit_image_batch_rrc: the same launch with a resized crop of the uint8 SOURCE image per sample, where
+ *   Compose([RandomResizedCrop(D, scale, ratio, BICUBIC), RandomHorizontalFlip(), ToTensor(), Normalize()]) has it.  rrc int32 [B][2] on the
+ *   device, contiguous, 4-byte aligned, one record per batch POSITION b:
+ *     word 0  top | left << 16            (16 bits each)
+ *     word 1  h | w << 15 | flip << 30    (15 bits each, then one; bit 31 is ignored)
+ *   all fields unsigned, 1 <= h, w <= S, top <= S - h, left <= S - w.  The source of position b is the uint8 window
+ *   I[top : top + h, left : left + w] of its image, mirrored left to right when flip is set; Pillow's 8-bit bicubic resample (above) takes it
+ *   to D x D: the horizontal pass with the table of w -> D, then the vertical pass over its uint8 result with the table of h -> D.  The value
+ *   table and the output layout are qatvit_image_batch's.  The result EQUALS, element for element,
+ *     Normalize(ToTensor(hflip?(crop(I, top, left, h, w)).resize((D, D), BICUBIC)))
+ *   which is torchvision's resized_crop: crop, THEN resize (Pillow's resize(box=...) of the whole image is another function: its filter reads
+ *   pixels outside the box).  The record (0, 0, S, S, flip = 0) gives qatvit_image_batch's result.
+ *   A malformed record is made safe, not trusted: h and w are clamped to [1, S], then top to [0, S - h] and left to [0, S - w]; no read
+ *   leaves the image, and the result is the clamped record's.
+ *   windows int32 [S][6 * D] on the device, 4-byte aligned: table n - 1 (offset (n - 1) * 6 * D) is the three arrays xmin[D], ntaps[D],
+ *   coef[D][4] of an n -> D resample one after the other, n = 1 .. S, as qatvit_image_resize_coeffs_windows(S, D, out_host) writes them on the
+ *   HOST (no HIP call; the builder and the 24-bit / overflow / row-budget checks of qatvit_image_resize_coeffs, whose own refusal of a source
+ *   below 8 stays; table S is qatvit_image_resize_coeffs(S, D)).  8 <= S <= D, D % 4 == 0, D <= 384.
+ *   mix int32 [B][6] or NULL: the record of qatvit_image_batch_mix, with X[b] = what this entry writes for position b without mix, the
+ *   partner taken with its own record rrc[p].  The LDS request (the mix form's two plane sets, plus the band's row-table entries per side) is
+ *   refused above 64 KB with an error string before any HIP call.  rrc == NULL is refused: without records the call is qatvit_image_batch's.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -580,6 +602,9 @@ int qatvit_image_batch_aug(const uint8_t* data, const int64_t* index, int32_t B,
 int qatvit_image_batch_mix(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                            const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix, float* out,
                            void* stream);
+int qatvit_image_resize_coeffs_windows(int32_t src, int32_t dst, int32_t* out_host);
+int qatvit_image_batch_rrc(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
+                           const float* table, const int32_t* rrc, const int32_t* mix, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

@@ -451,6 +451,28 @@ int qatvit_image_batch_mix(const uint8_t* data, const int64_t* index, int32_t B,
     return 0;
 }
 
+int qatvit_image_resize_coeffs_windows(int32_t src, int32_t dst, int32_t* out_host) {
+    QV_CHECK_ARG(out_host, "qatvit_image_resize_coeffs_windows: null pointer argument");
+    if (image_shape_ok("qatvit_image_resize_coeffs_windows", src, dst)) return 1;
+    return image_resize_coeffs_windows(src, dst, out_host);
+}
+
+int qatvit_image_batch_rrc(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
+                           const float* table, const int32_t* rrc, const int32_t* mix, float* out, void* stream) {
+    QV_CHECK_ARG(data && windows && table && out, "qatvit_image_batch_rrc: null pointer argument");
+    QV_CHECK_ARG(rrc, "qatvit_image_batch_rrc: rrc is NULL (the call without records is qatvit_image_batch or qatvit_image_batch_mix)");
+    if (image_shape_ok("qatvit_image_batch_rrc", S, D)) return 1;
+    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_rrc: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
+    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_rrc: batch %d of a data set of %d images needs an index", B, N);
+    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)windows & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)rrc & 3) == 0 &&
+                     ((uintptr_t)mix & 3) == 0,
+                 "qatvit_image_batch_rrc: misaligned pointer");
+    // the shape's LDS request is checked here, before any HIP call
+    if (launch_image_batch_rrc(data, index, B, N, S, D, windows, table, rrc, mix, out, (hipStream_t)stream)) return 1;
+    QV_CHECK_LAUNCH("qatvit_image_batch_rrc");
+    return 0;
+}
+
 int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {
     RowMoveTab t;
     t.n = 1; t.m[0] = RowMove{tall, compact, stride, width};

@@ -74,6 +74,14 @@ void image_table(const float* mean, const float* stdv, float* table) {
         for (int i = 0; i < 256; ++i) table[c * 256 + i] = ((float)i / 255.0f - mean[c]) / stdv[c];   // two IEEE divisions, as torch's div(255) .. div(std)
 }
 
+int image_resize_coeffs_windows(int S, int D, int32_t* out) {
+    for (int n = 1; n <= S; ++n) {
+        int32_t* t = out + (int64_t)(n - 1) * 6 * D;
+        if (image_resize_coeffs(n, D, t, t + D, t + 2 * D)) return 1;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- device
 // One workgroup = kImgBand output rows of one image, all three channels.  LDS: the source rows the band touches (HWC bytes as they lie in memory),
 // their horizontally resampled form as planes [row][c][D] of bytes, the coefficient tables and the value table.  The store loop walks each channel's
@@ -85,7 +93,37 @@ __device__ inline int img_round_clip(int acc) {
     return acc < 0 ? 0 : (acc > 255 ? 255 : acc);
 }
 
+// The rrc forms: one side's window (include/qatvit.h: the record of qatvit_image_batch_rrc) as the workgroup of output rows y0 .. y1-1 needs it.
+// A malformed record is made safe, not trusted: h and w are clamped to 1 .. S, then top to 0 .. S-h and left to 0 .. S-w, so the tables read are
+// among the S tables of `windows` and every pixel read lies inside the image.  r0 and nrows are the source rows of the band inside the window,
+// from the row table of h, clamped as the other forms clamp them; the host builder has checked that nrows <= image_max_rows(h, D) <= max_rows.
+struct ImgWindow {
+    int top, left, w, flip, r0, nrows;
+    const int32_t* ctab;   // the table of w -> D: xmin[D], ntaps[D], coef[D][4]
+    const int32_t* rtab;   // the table of h -> D
+};
+
+__device__ inline ImgWindow img_window(const int32_t* __restrict__ rec, const int32_t* __restrict__ windows, int S, int D, int y0, int y1,
+                                       int max_rows) {
+    const int w0 = rec[0], w1 = rec[1];
+    const int h = max(1, min(w1 & 0x7fff, S)), w = max(1, min((w1 >> 15) & 0x7fff, S));
+    ImgWindow v;
+    v.top = min(w0 & 0xffff, S - h);
+    v.left = min((w0 >> 16) & 0xffff, S - w);
+    v.w = w;
+    v.flip = (w1 >> 30) & 1;
+    v.ctab = windows + (int64_t)(w - 1) * 6 * D;
+    v.rtab = windows + (int64_t)(h - 1) * 6 * D;
+    int r0 = v.rtab[y0], r1 = v.rtab[y1 - 1] + v.rtab[D + y1 - 1];
+    r0 = max(0, min(r0, h - 1));
+    r1 = max(r0 + 1, min(r1, min(h, r0 + max_rows)));
+    v.r0 = r0;
+    v.nrows = r1 - r0;
+    return v;
+}
+
 // the kernel, once per form (image_kernel.h)
+#define QV_IMAGE_RRC 0
 #define QV_IMAGE_MIX 0
 #define QV_IMAGE_AUG 0
 #include "image_kernel.h"
@@ -97,6 +135,17 @@ __device__ inline int img_round_clip(int acc) {
 #include "image_kernel.h"
 #undef QV_IMAGE_AUG
 #undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
+#define QV_IMAGE_RRC 1
+#define QV_IMAGE_AUG 0
+#define QV_IMAGE_MIX 0
+#include "image_kernel.h"
+#undef QV_IMAGE_MIX
+#define QV_IMAGE_MIX 1
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
 
 int64_t image_lds_bytes(int S, int D) {
     const int mr = image_max_rows(S, D);
@@ -105,6 +154,12 @@ int64_t image_lds_bytes(int S, int D) {
 
 // the mix kernel keeps the partner's planes behind the sample's
 int64_t image_mix_lds_bytes(int S, int D) { return image_lds_bytes(S, D) + (int64_t)image_max_rows(S, D) * 3 * D; }
+
+// the rrc forms keep, behind that on the next 16 bytes, the band's entries of the row table per side (one side, or two with mix records)
+int64_t image_rrc_lds_bytes(int S, int D, int mixed) {
+    const int64_t base = mixed ? image_mix_lds_bytes(S, D) : image_lds_bytes(S, D);
+    return ((base + 15) & ~(int64_t)15) + (int64_t)(mixed ? 2 : 1) * kImgBand * (1 + kImgTaps) * 4;
+}
 
 int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table, float* out,
                        hipStream_t st) {
@@ -137,6 +192,25 @@ int launch_image_batch_mix(const uint8_t* data, const int64_t* index, int B, int
     auto kern = D == 224 ? k_image_batch_mix<224> : k_image_batch_mix<0>;
     hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug, padding_mode,
                        fill, mix);
+    return 0;
+}
+
+int launch_image_batch_rrc(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
+                           const int32_t* rrc, const int32_t* mix, float* out, hipStream_t st) {
+    const int64_t lds = image_rrc_lds_bytes(S, D, mix != nullptr);
+    if (lds > kImgMixMaxLds) {
+        set_error("qatvit_image_batch_rrc: source %d -> output %d needs %lld bytes of LDS%s, more than %d", S, D, (long long)lds,
+                  mix ? " for two plane sets" : "", kImgMixMaxLds);
+        return 1;
+    }
+    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
+    if (mix) {
+        auto kern = D == 224 ? k_image_batch_rrc_mix<224> : k_image_batch_rrc_mix<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, mix);
+    } else {
+        auto kern = D == 224 ? k_image_batch_rrc<224> : k_image_batch_rrc<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc);
+    }
     return 0;
 }
 

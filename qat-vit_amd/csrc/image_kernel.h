@@ -5,9 +5,28 @@
 // QV_IMAGE_AUG 1 with QV_IMAGE_MIX 1 gives k_image_batch_mix<DT>: the staging and the horizontal pass run once for the sample and, where the
 // workgroup's band needs it, once more for the partner of its mix record (include/qatvit.h) into a second plane set; the vertical pass then forms
 // both values of an element and blends or selects them.  QV_IMAGE_MIX must be defined (0 or 1) by the including file.
+// QV_IMAGE_RRC 1 (with QV_IMAGE_AUG 0) gives k_image_batch_rrc<DT> and, with QV_IMAGE_MIX 1, k_image_batch_rrc_mix<DT>: the source of a sample is
+// the window h x w at (top, left) of its record rrc[b] (include/qatvit.h), so every side has its own column table (of w), its own entries of the
+// row table (of h) and its own source rows.  The directives of that switch add text for those two forms only: with QV_IMAGE_RRC 0 the other three
+// kernels are compiled from the token sequence they had (profiles/rrc_bench.txt).  QV_IMAGE_RRC must be defined (0 or 1) by the including file.
 // DT = the output size as a constant (its divisions become multiplications), or 0: taken from D_rt.
+#if QV_IMAGE_RRC
+#define QV_IMAGE_XLAST xlast   // the last column of the window
+#else
+#define QV_IMAGE_XLAST S - 1
+#endif
 template <int DT>
-#if QV_IMAGE_MIX
+#if QV_IMAGE_RRC && QV_IMAGE_MIX
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                     int D_rt, int max_rows, const int32_t* __restrict__ windows,
+                                                                     const float* __restrict__ table, float* __restrict__ out,
+                                                                     const int32_t* __restrict__ rrc, const int32_t* __restrict__ mix) {
+#elif QV_IMAGE_RRC
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                 int D_rt, int max_rows, const int32_t* __restrict__ windows,
+                                                                 const float* __restrict__ table, float* __restrict__ out,
+                                                                 const int32_t* __restrict__ rrc) {
+#elif QV_IMAGE_MIX
 __global__ __launch_bounds__(kImgThreads) void k_image_batch_mix(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
                                                                  int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
                                                                  const float* __restrict__ table, float* __restrict__ out,
@@ -36,6 +55,11 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
 #else
     uint8_t* s_tmp = s_src + src_bytes;                  // [max_rows][3][D]
 #endif
+#if QV_IMAGE_RRC
+    // behind what the other forms keep, on the next 16 bytes (image_rrc_lds_bytes): per side, the band's entries of the row table,
+    // xmin [kImgBand] then coef [kImgBand][4].  s_xmin and s_coef hold the column table of the side whose horizontal pass runs.
+    int32_t* s_band = (int32_t*)(s_src + ((src_bytes + (QV_IMAGE_MIX + 1) * max_rows * 3 * D + 15) & ~15));
+#endif
 
     const int tid = threadIdx.x, b = blockIdx.y;
     const int y0 = blockIdx.x * kImgBand, y1 = min(y0 + kImgBand, D);
@@ -56,6 +80,15 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     int64_t img = index ? index[b] : b;
     img = img < 0 ? 0 : (img >= N ? N - 1 : img);        // the range is the caller's contract; a bad index must still not read outside data
 
+#if QV_IMAGE_RRC
+    // the window of the sample (and of its partner, where the band needs it): the record's two scalar loads, clamped, and the source rows of
+    // this band out of the row table of its h (img_window, image.hip)
+    const ImgWindow win_b = img_window(rrc + 2 * b, windows, S, D, y0, y1, max_rows);
+#if QV_IMAGE_MIX
+    const ImgWindow win_p = sides == 2 ? img_window(rrc + 2 * p, windows, S, D, y0, y1, max_rows) : win_b;
+#endif
+    for (int i = tid; i < 768; i += kImgThreads) s_table[i] = table[i];
+#else
     // rows of the source this band reads; clamped so that tables other than qatvit_image_resize_coeffs' cannot send a read outside the image
     int r0 = coeffs[y0], r1 = coeffs[y1 - 1] + coeffs[D + y1 - 1];
     r0 = max(0, min(r0, S - 1));
@@ -65,6 +98,7 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     for (int i = tid; i < D; i += kImgThreads) s_xmin[i] = coeffs[i];
     for (int i = tid; i < D * kImgTaps; i += kImgThreads) s_coef[i] = coeffs[2 * D + i];
     for (int i = tid; i < 768; i += kImgThreads) s_table[i] = table[i];
+#endif
 #if QV_IMAGE_MIX
     for (int side = 0; side < sides; ++side) {
     uint8_t* s_tmp = s_planes + side * plane_bytes;
@@ -73,11 +107,38 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
         img = index ? index[p] : p;
         img = img < 0 ? 0 : (img >= N ? N - 1 : img);
     }
+#if QV_IMAGE_RRC
+    const ImgWindow win = side ? win_p : win_b;
+#else
     const int w = aug ? aug[side ? p : b] : 0;           // no words: the zero word, which is the plain image
+#endif
+#elif QV_IMAGE_RRC
+    const int side = 0;
+    const ImgWindow win = win_b;
 #elif QV_IMAGE_AUG
     const int w = aug[b];
 #endif
-#if QV_IMAGE_AUG
+#if QV_IMAGE_RRC
+    // this side's tables (behind the barrier above where the other side's horizontal pass has read s_xmin and s_coef): the column table of its w,
+    // and of the row table of its h the band's entries only
+    const int r0 = win.r0, nrows = win.nrows, xlast = win.w - 1;
+    for (int i = tid; i < D; i += kImgThreads) s_xmin[i] = win.ctab[i];
+    for (int i = tid; i < D * kImgTaps; i += kImgThreads) s_coef[i] = win.ctab[2 * D + i];
+    int32_t* band = s_band + side * kImgBand * (1 + kImgTaps);
+    for (int i = tid; i < y1 - y0; i += kImgThreads) band[i] = win.rtab[y0 + i];
+    for (int i = tid; i < (y1 - y0) * kImgTaps; i += kImgThreads) band[kImgBand + i] = win.rtab[2 * D + y0 * kImgTaps + i];
+    // one item = one pixel of the window's rows r0 .. r1-1, mirrored where the record says so.  img_window's clamps keep top + r0 + r below
+    // top + h <= S and left + sx below left + w <= S whatever the record holds.
+    const uint8_t* image = data + (img * S + win.top + r0) * (int64_t)row_bytes + win.left * 3;
+    for (int i = tid; i < nrows * win.w; i += kImgThreads) {
+        const int r = i / win.w, x = i - r * win.w;
+        const uint8_t* px = image + r * row_bytes + (win.flip ? xlast - x : x) * 3;
+        uint8_t* dst = s_src + r * row_bytes + x * 3;
+        dst[0] = px[0];
+        dst[1] = px[1];
+        dst[2] = px[2];
+    }
+#elif QV_IMAGE_AUG
     // one item = one pixel of the rows r0 .. r1-1 of A.  The word is the workgroup's (blockIdx.y): one scalar load.  Both coordinates are clamped
     // after the reflection, so the three byte loads stay inside the image whatever the word holds; in constant mode their result is replaced.
     const int oy = (int)(int8_t)(w & 255), ox = (int)(int8_t)((w >> 8) & 255), flip = (w >> 16) & 1;
@@ -120,10 +181,10 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
             const int4 k = ((const int4*)s_coef)[x4 * 4 + j];
             const int p = max(0, xms[j]);
             int acc = 1 << (kImgBits - 1);
-            acc += __mul24((int)line[min(p, S - 1) * 3], k.x);
-            acc += __mul24((int)line[min(p + 1, S - 1) * 3], k.y);
-            acc += __mul24((int)line[min(p + 2, S - 1) * 3], k.z);
-            acc += __mul24((int)line[min(p + 3, S - 1) * 3], k.w);
+            acc += __mul24((int)line[min(p, QV_IMAGE_XLAST) * 3], k.x);
+            acc += __mul24((int)line[min(p + 1, QV_IMAGE_XLAST) * 3], k.y);
+            acc += __mul24((int)line[min(p + 2, QV_IMAGE_XLAST) * 3], k.z);
+            acc += __mul24((int)line[min(p + 3, QV_IMAGE_XLAST) * 3], k.w);
             px[j] = img_round_clip(acc);
         }
         // packed through v_perm_b32: hipcc turns the plain (shift, clamp, | << 8) pair into v_ashr_pk_u8_i32 and then takes the upper half of its
@@ -135,6 +196,9 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     const int D4 = D / 4;
     const uint8_t* s_tmp = s_planes;
     const int partner4 = (sides - 1) * (plane_bytes / 4);
+#if QV_IMAGE_RRC
+    const int r0 = win_b.r0, nrows = win_b.nrows;
+#endif
 #endif
     __syncthreads();
 
@@ -143,8 +207,13 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     float* obase = out + (int64_t)b * 3 * D * D + (int64_t)y0 * D;
     for (int it = tid; it < 3 * band4; it += kImgThreads) {
         const int c = it / band4, e = it % band4, y = y0 + e / D4, x4 = e % D4;
+#if QV_IMAGE_RRC
+        const int4 k = ((const int4*)(s_band + kImgBand))[y - y0];
+        const int rel = s_band[y - y0] - r0, last = nrows - 1;
+#else
         const int4 k = ((const int4*)s_coef)[y];
         const int rel = s_xmin[y] - r0, last = nrows - 1;
+#endif
         const uint32_t* plane = (const uint32_t*)s_tmp + c * D4 + x4;
         const uint32_t t0 = plane[max(0, min(rel, last)) * 3 * D4], t1 = plane[max(0, min(rel + 1, last)) * 3 * D4];
         const uint32_t t2 = plane[max(0, min(rel + 2, last)) * 3 * D4], t3 = plane[max(0, min(rel + 3, last)) * 3 * D4];
@@ -165,6 +234,12 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
         if (!as_is) {
             float u[4] = {v[0], v[1], v[2], v[3]};
             if (sides == 2) {
+#if QV_IMAGE_RRC
+                // the partner's planes came from its own window: within this block k, rel and last are those of its row table and its rows
+                const int32_t* band_p = s_band + kImgBand * (1 + kImgTaps);
+                const int4 k = ((const int4*)(band_p + kImgBand))[y - y0];
+                const int rel = band_p[y - y0] - win_p.r0, last = win_p.nrows - 1;
+#endif
                 const uint32_t* pp = plane + partner4;
                 const uint32_t p0 = pp[max(0, min(rel, last)) * 3 * D4], p1 = pp[max(0, min(rel + 1, last)) * 3 * D4];
                 const uint32_t p2 = pp[max(0, min(rel + 2, last)) * 3 * D4], p3 = pp[max(0, min(rel + 3, last)) * 3 * D4];
@@ -190,3 +265,4 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
         *(float4*)(obase + (int64_t)c * D * D + (int64_t)e * 4) = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
+#undef QV_IMAGE_XLAST

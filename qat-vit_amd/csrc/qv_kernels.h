@@ -351,6 +351,14 @@ constexpr int kImgMixMaxLds = 64 * 1024;
 int64_t image_mix_lds_bytes(int S, int D);
 int launch_image_batch_mix(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
                            const int32_t* aug, int padding_mode, int fill, const int32_t* mix, float* out, hipStream_t st);
+// the resized crop: the source of batch position b is the window of its record (rrc int32 [B][2]: top | left << 16, h | w << 15 | flip << 30;
+// include/qatvit.h), resampled with the tables of w and h out of windows = int32 [S][6 * D], table n - 1 = image_resize_coeffs(n, D) as coeffs has it
+// (image_resize_coeffs_windows writes them on the host, with image_resize_coeffs' checks).  mix as above, or nullptr.  Nonzero + set_error, before
+// any launch, where image_rrc_lds_bytes exceeds kImgMixMaxLds
+int image_resize_coeffs_windows(int S, int D, int32_t* out);   // host only
+int64_t image_rrc_lds_bytes(int S, int D, int mixed);
+int launch_image_batch_rrc(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
+                           const int32_t* rrc, const int32_t* mix, float* out, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

@@ -1,12 +1,14 @@
 """Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug /
-qatvit_image_batch_mix).
+qatvit_image_batch_mix / qatvit_image_resize_coeffs_windows / qatvit_image_batch_rrc).
 
 Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
 ``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
 writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced, equal to it element for element.
 ``RandomCropFlip`` adds ``RandomCrop(S, padding=p)`` + ``RandomHorizontalFlip()`` in front of the resize, inside the same launch (section 7l).
 ``MixupCutmix`` adds mixup / cutmix behind them, still inside that launch (section 7m); ``functional.kd_ce_loss_mix`` takes the same records.
+``RandomResizedCrop`` stands instead of ``RandomCropFlip``: every sample is a window of its image, resized, inside the same launch (section 7n).
 There is no CPU path: CPU tensors raise."""
+import math
 import os
 import pickle
 
@@ -27,6 +29,14 @@ def resize_tables(src_size: int, out_size: int):
     native.check(native.lib().qatvit_image_resize_coeffs(int(src_size), int(out_size), xmin.data_ptr(), ntaps.data_ptr(), coef.data_ptr()),
                  "qatvit_image_resize_coeffs")
     return xmin, ntaps, coef
+
+
+def resize_window_tables(src_size: int, out_size: int):
+    """int32 CPU tensor [S, 6 * D]: row n - 1 holds xmin [D], ntaps [D], coef [D, 4] of the resample from n to out_size one after the other, for
+    every window side n = 1 .. src_size (host only, no GPU).  Row S - 1 is ``resize_tables(S, D)``."""
+    out = torch.empty(max(int(src_size), 0), 6 * max(int(out_size), 0), dtype=torch.int32)
+    native.check(native.lib().qatvit_image_resize_coeffs_windows(int(src_size), int(out_size), out.data_ptr()), "qatvit_image_resize_coeffs_windows")
+    return out
 
 
 def value_table(mean=IMAGENET_MEAN, std=IMAGENET_STD):
@@ -69,6 +79,68 @@ class RandomCropFlip:
         off = torch.randint(0, 2 * self.padding + 1, (n, 2), generator=generator) - self.padding
         flip = torch.rand(n, generator=generator) < self.flip
         return ((off[:, 0] & 255) | (off[:, 1] & 255) << 8 | flip.to(torch.int64) << 16).to(torch.int32)
+
+
+RRC_WORDS = 2
+
+
+def _interval(name, v):
+    """(lo, hi) of a pair of finite numbers 0 < lo <= hi."""
+    ok = isinstance(v, (tuple, list)) and len(v) == 2 and all(not isinstance(t, bool) and isinstance(t, (int, float)) for t in v)
+    if not ok or not 0 < v[0] <= v[1] < float("inf"):
+        raise ValueError(f"{name} must be a pair of finite numbers 0 < low <= high, got {v!r}")
+    return float(v[0]), float(v[1])
+
+
+class RandomResizedCrop:
+    """``RandomResizedCrop(D, scale, ratio, BICUBIC)`` + ``RandomHorizontalFlip(flip)`` of the uint8 source image as one two-word int32 record per
+    sample (include/qatvit.h): word 0 ``top | left << 16``, word 1 ``h | w << 15 | flip << 30``, with ``1 <= h, w <= S``, ``top <= S - h``,
+    ``left <= S - w``: the window that is cropped, mirrored where ``flip`` is set, and resized to the output.  Built and drawn on the host; needs
+    no GPU."""
+
+    def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=0.5):
+        self.scale, self.ratio = _interval("scale", scale), _interval("ratio", ratio)
+        if isinstance(flip, bool) or not isinstance(flip, (int, float)) or not 0 <= flip <= 1:
+            raise ValueError(f"flip must be a probability 0 .. 1, got {flip!r}")
+        self.flip = float(flip)
+
+    def draw(self, n, src_size, generator=None):
+        """int32 CPU tensor [n, 2] for square sources of side S = `src_size`.  The rule (torchvision's ``RandomResizedCrop.get_params``,
+        restated: torchvision is not a dependency), with ``scale = (s0, s1)``, ``ratio = (r0, r1)``, all from `generator`, in this order:
+        ``u = torch.rand(n, 10, 2, dtype=float64)``: ten tries per sample, ``area = S^2 * (s0 + u[..., 0] * (s1 - s0))``,
+        ``aspect = exp(log r0 + u[..., 1] * (log r1 - log r0))``, ``w = torch.round(sqrt(area * aspect))``,
+        ``h = torch.round(sqrt(area / aspect))``; the first try with ``1 <= w <= S`` and ``1 <= h <= S`` is taken;
+        if none of the ten fits, torchvision's fallback for a square image, centred: the whole image if ``r0 <= 1 <= r1``; if ``1 < r0``,
+        ``w = S, h = round(S / r0)``; if ``r1 < 1``, ``h = S, w = round(S * r1)`` (round half to even, at least 1);
+        ``top = (S - h) // 2, left = (S - w) // 2``;
+        ``v = torch.rand(n, 3, dtype=float64)``: ``top = floor(v[:, 0] * (S - h + 1))``, ``left = floor(v[:, 1] * (S - w + 1))`` (both unused by
+        the fallback), ``flip = v[:, 2] < flip``.
+        Both ``rand`` calls are always made, so the generator ends where it ends for any setting."""
+        S = int(src_size)
+        if not 1 <= S <= 0x7fff:
+            raise ValueError(f"src_size must be 1 .. 32767, got {src_size!r}")
+        (s0, s1), (r0, r1) = self.scale, self.ratio
+        u = torch.rand(n, 10, 2, dtype=torch.float64, generator=generator)
+        v = torch.rand(n, 3, dtype=torch.float64, generator=generator)
+        area = float(S * S) * (s0 + u[..., 0] * (s1 - s0))
+        aspect = torch.exp(math.log(r0) + u[..., 1] * (math.log(r1) - math.log(r0)))
+        w, h = torch.round(torch.sqrt(area * aspect)), torch.round(torch.sqrt(area / aspect))
+        fits = (w >= 1) & (w <= S) & (h >= 1) & (h <= S)
+        first = fits.to(torch.int8).argmax(1, keepdim=True)           # the first maximum: the first try that fits (0 where none does)
+        found = fits.any(1)
+        w, h = w.gather(1, first)[:, 0].to(torch.int64), h.gather(1, first)[:, 0].to(torch.int64)
+        if r0 > 1.0:
+            fw, fh = S, max(1, int(round(S / r0)))
+        elif r1 < 1.0:
+            fw, fh = max(1, int(round(S * r1))), S
+        else:
+            fw, fh = S, S
+        w, h = torch.where(found, w, torch.full_like(w, fw)), torch.where(found, h, torch.full_like(h, fh))
+        top = torch.minimum(torch.floor(v[:, 0] * (S - h + 1)).to(torch.int64), S - h)
+        left = torch.minimum(torch.floor(v[:, 1] * (S - w + 1)).to(torch.int64), S - w)
+        top, left = torch.where(found, top, (S - h) // 2), torch.where(found, left, (S - w) // 2)
+        flip = (v[:, 2] < self.flip).to(torch.int64)
+        return torch.stack([top | left << 16, h | w << 15 | flip << 30], 1).to(torch.int32)
 
 
 MIX_WORDS = 6
@@ -147,7 +219,11 @@ class GpuResizeNormalize:
     cropped at its offset out of the image extended by ``padding_mode`` / ``fill`` and flipped first, in the same launch.  ``padding`` states the
     bound of the offsets in ``aug`` where the caller knows it: reflect mode is exact for offsets up to ``S - 1`` and a larger bound is refused.
     With ``mix`` (int32 ``[B, 6]`` on the device, the records of ``MixupCutmix.draw``) sample b is blended with, or takes a box from, what this
-    call produces for its partner position, in the same launch."""
+    call produces for its partner position, in the same launch.
+    With ``rrc`` (int32 ``[B, 2]`` on the device, the records of ``RandomResizedCrop.draw``; record b belongs to batch position b) the source of
+    sample b is the window of its record, mirrored where the record says so, and that window is what is resized to ``D x D``, in the same launch;
+    ``mix`` applies behind it as it does otherwise.  ``rrc`` stands instead of ``aug``: the record carries its own flip, and padding does not
+    apply.  The tables of every window side are built on the first such call and kept on the device."""
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
         self.src_size, self.out_size = int(src_size), int(out_size)
@@ -160,8 +236,16 @@ class GpuResizeNormalize:
         self.coeffs = torch.cat([t.flatten() for t in resize_tables(self.src_size, self.out_size)]).to(self.device)
         self.table = value_table(mean, std).to(self.device)
 
-    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None):
+    def window_tables(self):
+        """The device copy of ``resize_window_tables(S, D)``, built on first use."""
+        if getattr(self, "windows", None) is None:
+            self.windows = resize_window_tables(self.src_size, self.out_size).to(self.device)
+        return self.windows
+
+    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None):
         S, D = self.src_size, self.out_size
+        if rrc is not None and aug is not None:
+            raise ValueError("rrc and aug are mutually exclusive: the rrc record carries its own flip, and padding does not apply to a window")
         if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
             raise RuntimeError("GpuResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
         if data_u8.dtype != torch.uint8:
@@ -192,6 +276,18 @@ class GpuResizeNormalize:
             if not isinstance(mix, torch.Tensor) or mix.dtype != torch.int32 or tuple(mix.shape) != (B, MIX_WORDS) or not mix.is_contiguous() \
                     or mix.device != self.device:
                 raise ValueError(f"mix must be a contiguous int32 [{B}, {MIX_WORDS}] tensor on {self.device}")
+        if rrc is not None:
+            if not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
+                    or rrc.device != self.device:
+                raise ValueError(f"rrc must be a contiguous int32 [{B}, {RRC_WORDS}] tensor on {self.device}")
+            if B:
+                with torch.cuda.device(self.device):
+                    native.check(native.lib().qatvit_image_batch_rrc(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
+                                                                     self.table.data_ptr(), rrc.data_ptr(),
+                                                                     None if mix is None else mix.data_ptr(), out.data_ptr(),
+                                                                     native.stream_ptr()), "qatvit_image_batch_rrc")
+            return out
+        if mix is not None:
             if B:
                 with torch.cuda.device(self.device):
                     native.check(native.lib().qatvit_image_batch_mix(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
@@ -228,10 +324,13 @@ class GpuImageLoader:
     ``RandomCropFlip``) crops and flips every drawn sample inside the same launch: an epoch's words are drawn right after its plan, from the same
     ``generator``, and travel to the device with the indices in the one copy; the yielded tuples are the same.  ``mix`` (a ``MixupCutmix``) mixes
     every batch inside the same launch: an epoch's records are drawn after the plan and after the words, travel in the same copy, and the batch's
-    device slice (int32 ``[B, 6]``, what ``kd_ce_loss_mix`` / ``TeacherLogitTable.loss(mix=...)`` take) is the last element of every tuple."""
+    device slice (int32 ``[B, 6]``, what ``kd_ce_loss_mix`` / ``TeacherLogitTable.loss(mix=...)`` take) is the last element of every tuple.
+    ``crop`` (a ``RandomResizedCrop``) stands instead of ``augment``: every drawn sample is a resized window of its image, inside the same launch;
+    an epoch's records are drawn after the plan and before the mix records, from the same ``generator``, and travel in the same copy; the yielded
+    tuples are the same."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
-                 return_index=False, augment=None, mix=None):
+                 return_index=False, augment=None, mix=None, crop=None):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -254,6 +353,12 @@ class GpuImageLoader:
         if mix is not None and not isinstance(mix, MixupCutmix):
             raise TypeError(f"mix must be a MixupCutmix, got {type(mix).__name__}")
         self.mix = mix
+        if crop is not None:
+            if not isinstance(crop, RandomResizedCrop):
+                raise TypeError(f"crop must be a RandomResizedCrop, got {type(crop).__name__}")
+            if augment is not None:
+                raise ValueError("crop and augment are mutually exclusive: the crop's record carries its own flip, and padding does not apply")
+        self.crop = crop
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -262,6 +367,9 @@ class GpuImageLoader:
     def __iter__(self):
         plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
         if not plan:
+            return
+        if self.crop is not None:
+            yield from self._iter_cropped(plan)
             return
         if self.mix is not None:
             yield from self._iter_mixed(plan)
@@ -327,6 +435,28 @@ class GpuImageLoader:
                 yield x, self.labels.index_select(0, idx), idx, r
             else:
                 yield x, self.labels.index_select(0, idx), r
+
+    def _iter_cropped(self, plan):
+        flat = torch.cat(plan)
+        n = flat.shape[0]
+        nm = 3 * n if self.mix is not None else 0
+        # one pinned block and one asynchronous copy: n int64 indices, the n two-word int32 records, then (with mix) the n six-word int32 records
+        host = torch.empty(2 * n + nm, dtype=torch.int64, pin_memory=True)
+        host[:n].copy_(flat)
+        host[n:2 * n].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.data.shape[1], self.generator))
+        if self.mix is not None:
+            host[2 * n:].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], self.transform.out_size, self.generator))
+        dev = host.to(self.device, non_blocking=True)
+        order, windows = dev[:n], dev[n:2 * n].view(torch.int32).view(n, RRC_WORDS)
+        records = dev[2 * n:].view(torch.int32).view(n, MIX_WORDS) if self.mix is not None else None
+        o = 0
+        for b in plan:
+            m = b.shape[0]
+            idx, r = order[o:o + m], records[o:o + m] if records is not None else None
+            x = self.transform(self.data, idx, rrc=windows[o:o + m], mix=r)
+            o += m
+            tail = (idx,) if self.return_index else ()
+            yield (x, self.labels.index_select(0, idx)) + tail + ((r,) if r is not None else ())
 
 
 def cifar10_arrays(root, train=True):

@@ -24,7 +24,13 @@ cutmix records whose box is about half the area, (e) the same with identity reco
 exit status says whether it held.  (e) against (a) is reported.  --note FILE appends that file's text (the machine-code comparison, the register
 report) to the output.
 
-usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix [--note FILE]]"""
+With --rrc it measures only the resized-crop forms of the kernel and writes profiles/rrc_bench.txt: six arms with the
+method of 2., interleaved over the five repetitions in the one process, the records of the default RandomResizedCrop - (a) qatvit_image_batch,
+(b) qatvit_image_batch_rrc, (c) / (e) qatvit_image_batch_mix with the words of RandomCropFlip(4) and the mixup / cutmix records of --mix,
+(d) / (f) qatvit_image_batch_rrc with the same mix records.  The expectation under test: (b) within 10 % of (a), (d) of (c), (f) of (e); the exit
+status says whether it held.  --note FILE appends that file's text as with --mix.
+
+usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix | --rrc [--note FILE]]"""
 import argparse
 import multiprocessing
 import os
@@ -207,6 +213,73 @@ def mix_arms(lines, data, tr):
     return ok
 
 
+def rrc_arms(lines, data, tr):
+    import qat_vit_amd
+
+    B, D = 256, 224
+    g = torch.Generator(device="cuda").manual_seed(1)
+    idx = torch.randint(0, data.shape[0], (B,), device="cuda", generator=g)
+    host_windows = qat_vit_amd.RandomResizedCrop().draw(B, 32, torch.Generator().manual_seed(1))
+    windows = host_windows.cuda()
+    words = qat_vit_amd.RandomCropFlip(4).draw(B, torch.Generator().manual_seed(1)).cuda()
+    kw = {"aug": words, "padding_mode": "constant", "padding": 4}
+    bits = lambda v: int(np.float32(v).view(np.int32))   # noqa: E731
+    lam = np.random.default_rng(1).beta(0.8, 0.8, B).astype(np.float32)
+    partner = [B - 1 - b for b in range(B)]              # the flip: every partner is another position
+    mixup = torch.tensor([[p, bits(l), bits(np.float32(1) - l), 0, 0, bits(l)] for p, l in zip(partner, lam)], dtype=torch.int32).cuda()
+    y0, y1, x0, x1 = 33, 191, 33, 192                    # the box of --mix: 0.5007 of the area, edges off the band and float4 grids
+    area = (y1 - y0) * (x1 - x0) / float(D * D)
+    cutmix = torch.tensor([[p, bits(1), 0, y0 | y1 << 16, x0 | x1 << 16, bits(1 - area)] for p in partner], dtype=torch.int32).cuda()
+    whole = torch.tensor([[0, 32 | 32 << 15]] * B, dtype=torch.int32).cuda()
+    part = torch.tensor(partner, device="cuda")
+    ws, wp = torch.from_numpy(lam).cuda().view(B, 1, 1, 1), torch.from_numpy(np.float32(1) - lam).cuda().view(B, 1, 1, 1)
+    outs = [torch.empty(B, 3, D, D, device="cuda") for _ in range(4)]
+    arms = {"a": ("qatvit_image_batch", lambda i: tr(data, idx, out=outs[i % 4])),
+            "b": ("qatvit_image_batch_rrc", lambda i: tr(data, idx, out=outs[i % 4], rrc=windows)),
+            "c": ("qatvit_image_batch_mix, words of RandomCropFlip(4), mixup", lambda i: tr(data, idx, out=outs[i % 4], mix=mixup, **kw)),
+            "d": ("qatvit_image_batch_rrc, mixup records", lambda i: tr(data, idx, out=outs[i % 4], rrc=windows, mix=mixup)),
+            "e": (f"qatvit_image_batch_mix, words, cutmix, box {area:.3f}", lambda i: tr(data, idx, out=outs[i % 4], mix=cutmix, **kw)),
+            "f": (f"qatvit_image_batch_rrc, cutmix, box {area:.3f}", lambda i: tr(data, idx, out=outs[i % 4], rrc=windows, mix=cutmix))}
+    # what is timed is what the tests hold: the whole-image record is the plain call, and the mixed call is the composition of the rrc batch
+    assert torch.equal(tr(data, idx, rrc=whole), arms["a"][1](0))
+    x = arms["b"][1](1)
+    assert torch.equal(arms["d"][1](2), torch.add(x.mul(ws), x.index_select(0, part).mul(wp)))
+    for _, run in arms.values():
+        for i in range(20):
+            run(i)
+    reps = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (_, run) in arms.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            for i in range(200):
+                run(i)
+            ev[1].record()
+            torch.cuda.synchronize()
+            reps[k].append(ev[0].elapsed_time(ev[1]) / 200 * 1e3)
+    med = {k: statistics.median(v) for k, v in reps.items()}
+    spread = {k: max(v) - min(v) for k, v in reps.items()}
+    h, w = (host_windows[:, 1] & 0x7fff).double(), (host_windows[:, 1] >> 15 & 0x7fff).double()
+    lines.append("kernel with the resized crop (batch 256, S = 32 -> 224, random index into 50,000 resident images, one record of the default "
+                 "RandomResizedCrop per sample), us per batch; HIP events around 200 launches after 20 warm-up launches per arm, five repetitions "
+                 "interleaved a .. f in this one process, output rotating over 616 MB:")
+    lines.append(f"  windows drawn: h {int(h.min())} .. {int(h.max())} (mean {float(h.mean()):.1f}), w {int(w.min())} .. {int(w.max())} (mean {float(w.mean()):.1f})")
+    for k, (name, _) in arms.items():
+        lines.append(f"  ({k}) {name + ':':<62} median {med[k]:.1f}  ({', '.join(f'{r:.1f}' for r in reps[k])}); spread {spread[k]:.1f}")
+    ok = True
+    for k, base in (("b", "a"), ("d", "c"), ("f", "e")):
+        held = med[k] <= 1.10 * med[base]
+        ok = ok and held
+        lines.append(f"  ({k}) / ({base}) = {med[k] / med[base]:.3f}; ({k}) - ({base}) = {med[k] - med[base]:+.1f} us; the expectation ({k}) <= 1.10 x ({base}) = "
+                     f"{1.10 * med[base]:.1f} us -> {'holds' if held else 'DOES NOT HOLD'}")
+    lines.append(f"  every arm writes {BATCH_BYTES / 1e6:.1f} MB; (b) -> {BATCH_BYTES / (med['b'] * 1e-6) / 1e12:.2f} TB/s, (a) -> "
+                 f"{BATCH_BYTES / (med['a'] * 1e-6) / 1e12:.2f} TB/s")
+    lines.append(f"  LDS per workgroup: plain kernel {lds_bytes(32, D)[0]} B, rrc kernel {lds_bytes(32, D)[0] + 320} B, mix kernel {lds_bytes(32, D)[1]} B, "
+                 f"rrc-mix kernel {lds_bytes(32, D)[1] + 640} B")
+    return ok
+
+
 def lds_bytes(S, D):
     """(aug kernel, mix kernel) dynamic LDS of one workgroup, as csrc/image.hip sizes them: tables, source rows, one or two plane sets."""
     mr = (16 * S + D - 1) // D + 5
@@ -276,12 +349,14 @@ def main():
     ap.add_argument("--out", default=None, help="profiles/input_pipeline_bench.txt, or profiles/augment_bench.txt with --augment")
     ap.add_argument("--augment", action="store_true", help="only the three arms of the augmenting kernel")
     ap.add_argument("--mix", action="store_true", help="only the five arms of the mixing kernel")
-    ap.add_argument("--note", default=None, help="with --mix: a text file appended to the output")
+    ap.add_argument("--rrc", action="store_true", help="only the six arms of the resized-crop kernels")
+    ap.add_argument("--note", default=None, help="with --mix or --rrc: a text file appended to the output")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mix_bench.txt" if args.mix else "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
+        args.out = os.path.join(ROOT, "profiles", "rrc_bench.txt" if args.rrc else "mix_bench.txt" if args.mix else
+                                "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
     lines = []
-    if not args.augment and not args.mix:
+    if not args.augment and not args.mix and not args.rrc:
         host_path(lines)                  # before the first CUDA call: the pool's processes are forked from a process without a GPU context
     if not torch.cuda.is_available():
         raise SystemExit("bench_input_pipeline.py needs an MI355X: there is no CPU form of the pipeline to time")
@@ -292,7 +367,9 @@ def main():
     labels = torch.randint(0, 10, (50000,), device="cuda", generator=g)
     tr = qat_vit_amd.GpuResizeNormalize(32)
     lines.insert(0, f"input pipeline on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
-    if args.mix:
+    if args.rrc:
+        ok = rrc_arms(lines, data, tr)
+    elif args.mix:
         ok = mix_arms(lines, data, tr)
     elif args.augment:
         ok = augment_arms(lines, data, tr)
@@ -300,7 +377,7 @@ def main():
         kernel_ms = kernel_time(lines, data, tr)
         ok = step_condition(lines, data, labels, tr, kernel_ms, args.steps, args.warmup)
     lines.append(CLOCK_NOTE)
-    if args.mix and args.note:
+    if (args.mix or args.rrc) and args.note:
         lines.append("")
         lines.append(open(args.note).read().rstrip("\n"))
     text = "\n".join(lines) + "\n"
