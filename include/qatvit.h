@@ -592,6 +592,32 @@ int qatvit_optim_adamw_groups(const void* param_ptrs, const void* grad_ptrs, con
  *   mix int32 [B][6] or NULL: the record of qatvit_image_batch_mix, with X[b] = what this entry writes for position b without mix, the
  *   partner taken with its own record rrc[p].  The LDS request (the mix form's two plane sets, plus the band's row-table entries per side) is
  *   refused above 64 KB with an error string before any HIP call.  rrc == NULL is refused: without records the call is qatvit_image_batch's.
+ *
+ * qatvit_image_batch_erase / qatvit_image_batch_rrc_erase: the same launches with RandomErasing (arXiv:1708.04896) behind Normalize and in front
+ *   of the mix, where torchvision's reference recipe and timm without its prefetcher have it.  erase int32 [B][8] on the device, contiguous,
+ *   4-byte aligned, one record per batch POSITION b:
+ *     word 0  y0 | y1 << 16: output rows y0 .. y1-1 of the box, each bound clamped to [0, D]
+ *     word 1  x0 | x1 << 16: output columns, clamped likewise; the box is empty if y1 <= y0 or x1 <= x0
+ *     word 2, 3, 4  the fill of channel 0, 1, 2, fp32 bits, in normalised units (what the output holds)
+ *     word 5  mode; only bit 0 is read: 0 = the constant fill of words 2..4, 1 = per-element standard-normal noise (words 2..4 unused)
+ *     word 6, 7  k0, k1: the 64-bit key of the noise (mode 1)
+ *   The all-zero record is the identity (an empty box).  With X[b] = what qatvit_image_batch_mix (without mix) / qatvit_image_batch_rrc
+ *   (without mix) writes for position b with aug[b] / rrc[b]:
+ *     E[b][c][y][x] = X[b][c][y][x] outside the box of erase[b]; inside it the fill of channel c (mode 0) or z(k0, k1, c, y, x) (mode 1).
+ *   Without mix the output is E[b].  With mix it is qatvit_image_batch_mix's expression with E in the place of X: the partner contributes
+ *   E[p], erased by its own record erase[p] - never a mixed row, and never an un-erased one.
+ *   The noise z is a pure function of (key, c, y, x): the same record gives the same values at any batch position, as the sample or as a
+ *   partner.  Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85), key (k0, k1),
+ *   counter (y * (D / 4) + x / 4, c, 0, 0): one call per four neighbouring columns, whose outputs r0 .. r3 give the elements x & 3 = 0 .. 3 by
+ *   Box-Muller on the pairs (r0, r1) and (r2, r3):
+ *     u = ((r_even >> 9) + 1) * 2^-23  in (0, 1],   t = (r_odd >> 8) * 2^-23  in [0, 2),   both exact in fp32,
+ *     R = sqrtf(-2 * logf(u)),   the even element = R * cospif(t),   the odd element = R * sinpif(t)
+ *   with the full-precision fp32 functions and no fused multiply-add.  The integer half is exact; the float half follows the device's math
+ *   library to a few ulp (measured against an fp64 evaluation: profiles/erase_bench.txt).  |z| <= sqrt(46 ln 2) = 5.65.
+ *   A malformed record is made safe, not trusted: the bounds are clamped, the other mode bits are ignored, and nothing is addressed through a
+ *   record, so none can cause a read or a write outside out[b].  The kernels keep nothing more in LDS: the refusals are the siblings'.
+ *   aug, mix may be NULL with their meanings above (no words; no mixing); rrc == NULL is refused.  erase == NULL makes the call
+ *   qatvit_image_batch_mix's / qatvit_image_batch_rrc's: that entry's kernel is launched and the result is bitwise its result.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -605,6 +631,11 @@ int qatvit_image_batch_mix(const uint8_t* data, const int64_t* index, int32_t B,
 int qatvit_image_resize_coeffs_windows(int32_t src, int32_t dst, int32_t* out_host);
 int qatvit_image_batch_rrc(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
                            const float* table, const int32_t* rrc, const int32_t* mix, float* out, void* stream);
+int qatvit_image_batch_erase(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                             const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix,
+                             const int32_t* erase, float* out, void* stream);
+int qatvit_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
+                                 const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

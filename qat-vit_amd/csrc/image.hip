@@ -122,7 +122,69 @@ __device__ inline ImgWindow img_window(const int32_t* __restrict__ rec, const in
     return v;
 }
 
+// The erase forms: one side's record (include/qatvit.h: the record of qatvit_image_batch_erase) as the workgroup of output rows y0 .. y1-1 needs it.
+// A malformed record is made safe, not trusted: the four bounds are clamped to [0, D] and only bit 0 of the mode is read; nothing is addressed
+// through the record, so no record can move a read or a store.  touched = the box is not empty and meets the band's rows (workgroup-uniform).
+struct ImgErase {
+    int y0, y1, x0, x1;
+    bool touched, noise;
+    float f0, f1, f2;
+    uint32_t k0, k1;
+};
+
+__device__ __forceinline__ ImgErase img_erase(const int32_t* __restrict__ rec, int D, int y0, int y1) {
+    ImgErase e;
+    e.y0 = min(rec[0] & 0xffff, D), e.y1 = min((rec[0] >> 16) & 0xffff, D);
+    e.x0 = min(rec[1] & 0xffff, D), e.x1 = min((rec[1] >> 16) & 0xffff, D);
+    e.touched = e.y1 > e.y0 && e.x1 > e.x0 && e.y0 < y1 && e.y1 > y0;
+    e.f0 = __int_as_float(rec[2]), e.f1 = __int_as_float(rec[3]), e.f2 = __int_as_float(rec[4]);
+    e.noise = rec[5] & 1;
+    e.k0 = (uint32_t)rec[6], e.k1 = (uint32_t)rec[7];
+    return e;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11) with the standard constants; the integer half of the noise, exact
+__device__ __forceinline__ void img_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t r[4]) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0, c1 = l1, c2 = h0 ^ c3 ^ k1, c3 = l0;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    r[0] = c0, r[1] = c1, r[2] = c2, r[3] = c3;
+}
+
+// z(key, c, y, 4 * x4 + j), j = 0 .. 3, of include/qatvit.h: one Philox call, Box-Muller on (r0, r1) and (r2, r3) with the full-precision functions
+__device__ __forceinline__ void img_noise4(uint32_t k0, uint32_t k1, int c, int y, int x4, int D4, float z[4]) {
+    uint32_t r[4];
+    img_philox((uint32_t)(y * D4 + x4), (uint32_t)c, 0u, 0u, k0, k1, r);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u = (float)((r[2 * h] >> 9) + 1u) * 0x1p-23f, t = (float)(r[2 * h + 1] >> 8) * 0x1p-23f;
+        const float R = sqrtf(-2.0f * logf(u));
+        z[2 * h] = R * cospif(t);
+        z[2 * h + 1] = R * sinpif(t);
+    }
+}
+
+// One float4 item (channel c, row y, columns 4 * x4 .. + 3) of a band that the box meets: the elements inside the box take the fill of their
+// channel or their noise value; only an item with an element inside the box makes the Philox call.
+__device__ __forceinline__ void img_erase_apply(const ImgErase e, int c, int y, int x4, int D4, float v[4]) {
+    const int x = x4 * 4;
+    if (y < e.y0 || y >= e.y1 || x + 3 < e.x0 || x >= e.x1) return;
+    float z[4];
+    if (e.noise) {
+        img_noise4(e.k0, e.k1, c, y, x4, D4, z);
+    } else {
+        z[0] = z[1] = z[2] = z[3] = c == 0 ? e.f0 : (c == 1 ? e.f1 : e.f2);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = x + j >= e.x0 && x + j < e.x1 ? z[j] : v[j];
+}
+
 // the kernel, once per form (image_kernel.h)
+#define QV_IMAGE_ERASE 0
 #define QV_IMAGE_RRC 0
 #define QV_IMAGE_MIX 0
 #define QV_IMAGE_AUG 0
@@ -146,6 +208,30 @@ __device__ inline ImgWindow img_window(const int32_t* __restrict__ rec, const in
 #undef QV_IMAGE_AUG
 #undef QV_IMAGE_MIX
 #undef QV_IMAGE_RRC
+// the four erasing forms: aug (which also serves the call without words), mix, rrc, rrc-mix
+#undef QV_IMAGE_ERASE
+#define QV_IMAGE_ERASE 1
+#define QV_IMAGE_RRC 0
+#define QV_IMAGE_AUG 1
+#define QV_IMAGE_MIX 0
+#include "image_kernel.h"
+#undef QV_IMAGE_MIX
+#define QV_IMAGE_MIX 1
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
+#define QV_IMAGE_RRC 1
+#define QV_IMAGE_AUG 0
+#define QV_IMAGE_MIX 0
+#include "image_kernel.h"
+#undef QV_IMAGE_MIX
+#define QV_IMAGE_MIX 1
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
+#undef QV_IMAGE_ERASE
 
 int64_t image_lds_bytes(int S, int D) {
     const int mr = image_max_rows(S, D);
@@ -210,6 +296,50 @@ int launch_image_batch_rrc(const uint8_t* data, const int64_t* index, int B, int
     } else {
         auto kern = D == 224 ? k_image_batch_rrc<224> : k_image_batch_rrc<0>;
         hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc);
+    }
+    return 0;
+}
+
+// The erase forms keep nothing more in LDS: the requests and their refusals are those of the forms without erase records.
+int launch_image_batch_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st) {
+    if (!erase) return launch_image_batch_mix(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, out, st);
+    const int64_t lds = mix ? image_mix_lds_bytes(S, D) : image_lds_bytes(S, D);
+    if (mix && lds > kImgMixMaxLds) {
+        set_error("qatvit_image_batch_erase: source %d -> output %d needs %lld bytes of LDS for two plane sets, more than %d", S, D, (long long)lds,
+                  kImgMixMaxLds);
+        return 1;
+    }
+    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
+    if (mix) {
+        auto kern = D == 224 ? k_image_batch_mix_erase<224> : k_image_batch_mix_erase<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
+                           padding_mode, fill, mix, erase);
+    } else {
+        auto kern = D == 224 ? k_image_batch_aug_erase<224> : k_image_batch_aug_erase<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
+                           padding_mode, fill, erase);
+    }
+    return 0;
+}
+
+int launch_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
+                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st) {
+    if (!erase) return launch_image_batch_rrc(data, index, B, N, S, D, windows, table, rrc, mix, out, st);
+    const int64_t lds = image_rrc_lds_bytes(S, D, mix != nullptr);
+    if (lds > kImgMixMaxLds) {
+        set_error("qatvit_image_batch_rrc_erase: source %d -> output %d needs %lld bytes of LDS%s, more than %d", S, D, (long long)lds,
+                  mix ? " for two plane sets" : "", kImgMixMaxLds);
+        return 1;
+    }
+    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
+    if (mix) {
+        auto kern = D == 224 ? k_image_batch_rrc_mix_erase<224> : k_image_batch_rrc_mix_erase<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, mix,
+                           erase);
+    } else {
+        auto kern = D == 224 ? k_image_batch_rrc_erase<224> : k_image_batch_rrc_erase<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, erase);
     }
     return 0;
 }

@@ -9,6 +9,11 @@
 // the window h x w at (top, left) of its record rrc[b] (include/qatvit.h), so every side has its own column table (of w), its own entries of the
 // row table (of h) and its own source rows.  The directives of that switch add text for those two forms only: with QV_IMAGE_RRC 0 the other three
 // kernels are compiled from the token sequence they had (profiles/rrc_bench.txt).  QV_IMAGE_RRC must be defined (0 or 1) by the including file.
+// QV_IMAGE_ERASE 1 gives k_image_batch_aug_erase<DT>, _mix_erase, _rrc_erase and _rrc_mix_erase: the vertical pass replaces the elements inside the box
+// of the side's erase record (include/qatvit.h) right after it has formed them, so what is blended or selected is the erased sample and the erased
+// partner.  The aug form of this switch takes aug == NULL as the zero word.  The directives of the switch add text for those four forms only: with
+// QV_IMAGE_ERASE 0 the five other kernels are compiled from the token sequence they had (profiles/erase_bench.txt).  QV_IMAGE_ERASE must be defined
+// (0 or 1) by the including file.
 // DT = the output size as a constant (its divisions become multiplications), or 0: taken from D_rt.
 #if QV_IMAGE_RRC
 #define QV_IMAGE_XLAST xlast   // the last column of the window
@@ -16,6 +21,32 @@
 #define QV_IMAGE_XLAST S - 1
 #endif
 template <int DT>
+#if QV_IMAGE_ERASE
+#if QV_IMAGE_RRC && QV_IMAGE_MIX
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N,
+                                                                           int S, int D_rt, int max_rows, const int32_t* __restrict__ windows,
+                                                                           const float* __restrict__ table, float* __restrict__ out,
+                                                                           const int32_t* __restrict__ rrc, const int32_t* __restrict__ mix,
+                                                                           const int32_t* __restrict__ erase) {
+#elif QV_IMAGE_RRC
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                       int D_rt, int max_rows, const int32_t* __restrict__ windows,
+                                                                       const float* __restrict__ table, float* __restrict__ out,
+                                                                       const int32_t* __restrict__ rrc, const int32_t* __restrict__ erase) {
+#elif QV_IMAGE_MIX
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_mix_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
+                                                                       const float* __restrict__ table, float* __restrict__ out,
+                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
+                                                                       const int32_t* __restrict__ mix, const int32_t* __restrict__ erase) {
+#else
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_aug_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
+                                                                       const float* __restrict__ table, float* __restrict__ out,
+                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
+                                                                       const int32_t* __restrict__ erase) {
+#endif
+#else
 #if QV_IMAGE_RRC && QV_IMAGE_MIX
 __global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
                                                                      int D_rt, int max_rows, const int32_t* __restrict__ windows,
@@ -41,6 +72,7 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch_aug(const uint8_t* 
 __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
                                                              int max_rows, const int32_t* __restrict__ coeffs, const float* __restrict__ table,
                                                              float* __restrict__ out) {
+#endif
 #endif
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int D = DT ? DT : D_rt;
@@ -115,6 +147,8 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
 #elif QV_IMAGE_RRC
     const int side = 0;
     const ImgWindow win = win_b;
+#elif QV_IMAGE_AUG && QV_IMAGE_ERASE
+    const int w = aug ? aug[b] : 0;                      // no words: the zero word, as the mix form has it
 #elif QV_IMAGE_AUG
     const int w = aug[b];
 #endif
@@ -200,6 +234,14 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     const int r0 = win_b.r0, nrows = win_b.nrows;
 #endif
 #endif
+#if QV_IMAGE_ERASE
+    // the erase record is the workgroup's (and its partner's, where the band takes something from it): eight scalar loads per side, clamped;
+    // `touched` is workgroup-uniform, and a band that no box meets runs what the form without the switch runs (img_erase, image.hip)
+    const ImgErase er_b = img_erase(erase + 8 * b, D, y0, y1);
+#if QV_IMAGE_MIX
+    const ImgErase er_p = sides == 2 ? img_erase(erase + 8 * p, D, y0, y1) : er_b;
+#endif
+#endif
     __syncthreads();
 
     // vertical pass + value table + store
@@ -228,6 +270,10 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
             acc += __mul24((int)((t3 >> (8 * j)) & 255), k.w);
             v[j] = tab[img_round_clip(acc)];
         }
+#if QV_IMAGE_ERASE
+        // E[b] where X[b] stood: the elements inside the sample's box are replaced before anything is mixed
+        if (er_b.touched) img_erase_apply(er_b, c, y, x4, D4, v);
+#endif
 #if QV_IMAGE_MIX
         // the partner's value of the same element (the sample's own where one plane set serves both), then
         // out = inside the box ? partner : fl(fl(w_self * own) + fl(w_partner * partner)), the products and the sum rounded one by one
@@ -252,6 +298,9 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
                     acc += __mul24((int)((p3 >> (8 * j)) & 255), k.w);
                     u[j] = tab[img_round_clip(acc)];
                 }
+#if QV_IMAGE_ERASE
+                if (er_p.touched) img_erase_apply(er_p, c, y, x4, D4, u);   // E[p], by the partner's own record
+#endif
             }
             const bool row_in = box && y >= by0 && y < by1;
 #pragma unroll

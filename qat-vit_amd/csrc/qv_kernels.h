@@ -359,6 +359,13 @@ int image_resize_coeffs_windows(int S, int D, int32_t* out);   // host only
 int64_t image_rrc_lds_bytes(int S, int D, int mixed);
 int launch_image_batch_rrc(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
                            const int32_t* rrc, const int32_t* mix, float* out, hipStream_t st);
+// the same two with an erase box per batch position (erase int32 [B][8]: rows, columns, three fills, mode, a 64-bit noise key; include/qatvit.h),
+// applied to the sample and to its partner before they are mixed.  erase == nullptr: launch_image_batch_mix / launch_image_batch_rrc.  No LDS of
+// their own: the refusals are those of the forms without erase records
+int launch_image_batch_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st);
+int launch_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
+                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

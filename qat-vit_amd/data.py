@@ -1,5 +1,5 @@
 """Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug /
-qatvit_image_batch_mix / qatvit_image_resize_coeffs_windows / qatvit_image_batch_rrc).
+qatvit_image_batch_mix / qatvit_image_resize_coeffs_windows / qatvit_image_batch_rrc / qatvit_image_batch_erase / qatvit_image_batch_rrc_erase).
 
 Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
 ``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
@@ -7,6 +7,7 @@ writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced,
 ``RandomCropFlip`` adds ``RandomCrop(S, padding=p)`` + ``RandomHorizontalFlip()`` in front of the resize, inside the same launch (section 7l).
 ``MixupCutmix`` adds mixup / cutmix behind them, still inside that launch (section 7m); ``functional.kd_ce_loss_mix`` takes the same records.
 ``RandomResizedCrop`` stands instead of ``RandomCropFlip``: every sample is a window of its image, resized, inside the same launch (section 7n).
+``RandomErasing`` erases a box of every sample's normalised output, behind either and in front of the mix, inside the same launch (section 7o).
 There is no CPU path: CPU tensors raise."""
 import math
 import os
@@ -213,6 +214,88 @@ class MixupCutmix:
         return torch.from_numpy(rec)
 
 
+ERASE_WORDS = 8
+
+
+class RandomErasing:
+    """``RandomErasing(p, scale, ratio, value)`` (arXiv:1708.04896) of the normalised output as one eight-word int32 record per sample
+    (include/qatvit.h): the box rows ``y0 | y1 << 16`` and columns ``x0 | x1 << 16``, the fill of each channel (fp32 bits, normalised units), the
+    mode bit and the 64-bit key of the noise.  ``value`` is a number, three numbers (one per channel) or ``"random"``; ``mode`` is ``"const"``
+    (the fill is ``value``; with ``value=0`` timm's ``const``), ``"rand"`` (one standard normal per channel and sample, drawn on the host into the
+    fill words: timm's ``rand``) or ``"pixel"`` (one standard normal per element, formed inside the launch from the record's key).
+    ``value="random"`` is a synonym for ``mode="pixel"``, as torchvision has it; ``mode=None`` follows ``value``.  The erasure stands behind
+    ``Normalize`` and in front of the mix.  Built and drawn on the host; needs no GPU."""
+
+    MODES = ("const", "rand", "pixel")
+
+    def __init__(self, p=0.25, scale=(0.02, 0.33), ratio=(0.3, 3.3), value=0, mode=None):
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 <= p <= 1:
+            raise ValueError(f"p must be a probability 0 .. 1, got {p!r}")
+        self.p, self.scale, self.ratio = float(p), _interval("scale", scale), _interval("ratio", ratio)
+        if mode is not None and mode not in self.MODES:
+            raise ValueError(f"mode must be one of {list(self.MODES)} or None, got {mode!r}")
+        number = lambda t: not isinstance(t, bool) and isinstance(t, (int, float)) and math.isfinite(t)   # noqa: E731
+        if isinstance(value, str):
+            if value != "random":
+                raise ValueError(f"value must be a number, three numbers or 'random', got {value!r}")
+            if mode not in (None, "pixel"):
+                raise ValueError(f"value='random' is mode='pixel'; it cannot go with mode={mode!r}")
+            mode, fill = "pixel", (0.0, 0.0, 0.0)
+        elif number(value):
+            fill = (float(value),) * 3
+        elif isinstance(value, (tuple, list)) and len(value) == 3 and all(number(t) for t in value):
+            fill = tuple(float(t) for t in value)
+        else:
+            raise ValueError(f"value must be a finite number, three finite numbers or 'random', got {value!r}")
+        mode = mode or "const"
+        if mode != "const" and any(t != 0.0 for t in fill):
+            raise ValueError(f"mode={mode!r} draws its own fill: value must stay 0, got {value!r}")
+        self.value, self.mode = fill, mode
+
+    def draw(self, n, out_size, generator=None):
+        """int32 CPU tensor [n, 8] for outputs of side D = `out_size`.  The rule (torchvision's ``RandomErasing.forward`` / ``get_params`` for a
+        square image, restated: torchvision is not a dependency), with ``scale = (s0, s1)``, ``ratio = (r0, r1)``, all from `generator`, in
+        this order:
+        ``g = torch.rand(n, dtype=float64)``: sample k is erased where ``g[k] < p``;
+        ``u = torch.rand(n, 10, 2, dtype=float64)``: ten tries per sample, ``area = D^2 * (s0 + u[..., 0] * (s1 - s0))``,
+        ``aspect = exp(log r0 + u[..., 1] * (log r1 - log r0))``, ``h = torch.round(sqrt(area * aspect))``,
+        ``w = torch.round(sqrt(area / aspect))``; the first try with ``h < D`` and ``w < D`` is taken; if none of the ten fits the sample is not
+        erased;
+        ``v = torch.rand(n, 2, dtype=float64)``: ``top = floor(v[:, 0] * (D - h + 1))``, ``left = floor(v[:, 1] * (D - w + 1))``;
+        ``z = torch.randn(n, 3, dtype=float32)``: the fill of the three channels in ``mode="rand"``;
+        ``k = torch.randint(-2^31, 2^31, (n, 2))``: the key words in ``mode="pixel"``.
+        The box is rows ``top .. top + h - 1``, columns ``left .. left + w - 1``.  A sample that is not erased gets the all-zero record, the
+        identity.  Every draw is always made, so the generator ends where it ends for any setting: its position depends on `n` only."""
+        D = int(out_size)
+        if not 1 <= D <= 0xffff:
+            raise ValueError(f"out_size must be 1 .. 65535, got {out_size!r}")
+        (s0, s1), (r0, r1) = self.scale, self.ratio
+        g = torch.rand(n, dtype=torch.float64, generator=generator)
+        u = torch.rand(n, 10, 2, dtype=torch.float64, generator=generator)
+        v = torch.rand(n, 2, dtype=torch.float64, generator=generator)
+        z = torch.randn(n, 3, dtype=torch.float32, generator=generator)
+        k = torch.randint(-(1 << 31), 1 << 31, (n, 2), dtype=torch.int64, generator=generator)
+        area = float(D * D) * (s0 + u[..., 0] * (s1 - s0))
+        aspect = torch.exp(math.log(r0) + u[..., 1] * (math.log(r1) - math.log(r0)))
+        h, w = torch.round(torch.sqrt(area * aspect)), torch.round(torch.sqrt(area / aspect))
+        fits = (h < D) & (w < D)
+        first = fits.to(torch.int8).argmax(1, keepdim=True)           # the first maximum: the first try that fits (0 where none does)
+        erased = (g < self.p) & fits.any(1)
+        h, w = h.gather(1, first)[:, 0].to(torch.int64), w.gather(1, first)[:, 0].to(torch.int64)
+        h, w = torch.where(erased, h, torch.zeros_like(h)), torch.where(erased, w, torch.zeros_like(w))
+        top = torch.minimum(torch.floor(v[:, 0] * (D - h + 1)).to(torch.int64), D - h)
+        left = torch.minimum(torch.floor(v[:, 1] * (D - w + 1)).to(torch.int64), D - w)
+        rec = torch.zeros(n, ERASE_WORDS, dtype=torch.int64)
+        rec[:, 0], rec[:, 1] = top | (top + h) << 16, left | (left + w) << 16
+        if self.mode == "pixel":
+            rec[:, 5], rec[:, 6:8] = 1, k
+        else:
+            fill = z if self.mode == "rand" else torch.tensor(self.value, dtype=torch.float32).expand(n, 3)
+            rec[:, 2:5] = fill.contiguous().view(torch.int32).to(torch.int64)
+        rec = torch.where(erased[:, None], rec, torch.zeros_like(rec))
+        return ((rec + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32)    # the 32 bits of every word, as int32
+
+
 class GpuResizeNormalize:
     """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch.
     With ``aug`` (int32 ``[B]`` on the device, the words of ``RandomCropFlip.draw``; word b belongs to batch position b) the source of sample b is
@@ -223,7 +306,10 @@ class GpuResizeNormalize:
     With ``rrc`` (int32 ``[B, 2]`` on the device, the records of ``RandomResizedCrop.draw``; record b belongs to batch position b) the source of
     sample b is the window of its record, mirrored where the record says so, and that window is what is resized to ``D x D``, in the same launch;
     ``mix`` applies behind it as it does otherwise.  ``rrc`` stands instead of ``aug``: the record carries its own flip, and padding does not
-    apply.  The tables of every window side are built on the first such call and kept on the device."""
+    apply.  The tables of every window side are built on the first such call and kept on the device.
+    With ``erase`` (int32 ``[B, 8]`` on the device, the records of ``RandomErasing.draw``; record b belongs to batch position b) the box of sample
+    b's record is filled, or set to noise, in its normalised output, in the same launch: behind ``aug`` / ``rrc`` and in front of ``mix``, whose
+    partner is erased by its own record."""
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
         self.src_size, self.out_size = int(src_size), int(out_size)
@@ -242,7 +328,7 @@ class GpuResizeNormalize:
             self.windows = resize_window_tables(self.src_size, self.out_size).to(self.device)
         return self.windows
 
-    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None):
+    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None, erase=None):
         S, D = self.src_size, self.out_size
         if rrc is not None and aug is not None:
             raise ValueError("rrc and aug are mutually exclusive: the rrc record carries its own flip, and padding does not apply to a window")
@@ -276,16 +362,35 @@ class GpuResizeNormalize:
             if not isinstance(mix, torch.Tensor) or mix.dtype != torch.int32 or tuple(mix.shape) != (B, MIX_WORDS) or not mix.is_contiguous() \
                     or mix.device != self.device:
                 raise ValueError(f"mix must be a contiguous int32 [{B}, {MIX_WORDS}] tensor on {self.device}")
+        if erase is not None:
+            if not isinstance(erase, torch.Tensor) or erase.dtype != torch.int32 or tuple(erase.shape) != (B, ERASE_WORDS) \
+                    or not erase.is_contiguous() or erase.device != self.device:
+                raise ValueError(f"erase must be a contiguous int32 [{B}, {ERASE_WORDS}] tensor on {self.device}")
         if rrc is not None:
             if not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
                     or rrc.device != self.device:
                 raise ValueError(f"rrc must be a contiguous int32 [{B}, {RRC_WORDS}] tensor on {self.device}")
+            if B and erase is not None:
+                with torch.cuda.device(self.device):
+                    native.check(native.lib().qatvit_image_batch_rrc_erase(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
+                                                                           self.table.data_ptr(), rrc.data_ptr(),
+                                                                           None if mix is None else mix.data_ptr(), erase.data_ptr(),
+                                                                           out.data_ptr(), native.stream_ptr()), "qatvit_image_batch_rrc_erase")
+                return out
             if B:
                 with torch.cuda.device(self.device):
                     native.check(native.lib().qatvit_image_batch_rrc(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
                                                                      self.table.data_ptr(), rrc.data_ptr(),
                                                                      None if mix is None else mix.data_ptr(), out.data_ptr(),
                                                                      native.stream_ptr()), "qatvit_image_batch_rrc")
+            return out
+        if erase is not None:
+            if B:
+                with torch.cuda.device(self.device):
+                    native.check(native.lib().qatvit_image_batch_erase(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(),
+                                                                       self.table.data_ptr(), None if aug is None else aug.data_ptr(), mode, fill,
+                                                                       None if mix is None else mix.data_ptr(), erase.data_ptr(), out.data_ptr(),
+                                                                       native.stream_ptr()), "qatvit_image_batch_erase")
             return out
         if mix is not None:
             if B:
@@ -327,10 +432,13 @@ class GpuImageLoader:
     device slice (int32 ``[B, 6]``, what ``kd_ce_loss_mix`` / ``TeacherLogitTable.loss(mix=...)`` take) is the last element of every tuple.
     ``crop`` (a ``RandomResizedCrop``) stands instead of ``augment``: every drawn sample is a resized window of its image, inside the same launch;
     an epoch's records are drawn after the plan and before the mix records, from the same ``generator``, and travel in the same copy; the yielded
-    tuples are the same."""
+    tuples are the same.  ``erase`` (a ``RandomErasing``) erases a box of every drawn sample's output inside the same launch, with ``augment`` or
+    ``crop`` and in front of ``mix``: an epoch's records are drawn last, after the plan, the words or windows and the mix records, so that a seed
+    gives the plan, words, windows and mix records it gives without ``erase``; they travel in the same copy, four int64 elements per sample, and the
+    yielded tuples are the same (the loss needs nothing from an erase record)."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
-                 return_index=False, augment=None, mix=None, crop=None):
+                 return_index=False, augment=None, mix=None, crop=None, erase=None):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -359,6 +467,9 @@ class GpuImageLoader:
             if augment is not None:
                 raise ValueError("crop and augment are mutually exclusive: the crop's record carries its own flip, and padding does not apply")
         self.crop = crop
+        if erase is not None and not isinstance(erase, RandomErasing):
+            raise TypeError(f"erase must be a RandomErasing, got {type(erase).__name__}")
+        self.erase = erase
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -367,6 +478,9 @@ class GpuImageLoader:
     def __iter__(self):
         plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
         if not plan:
+            return
+        if self.erase is not None:
+            yield from self._iter_erased(plan)
             return
         if self.crop is not None:
             yield from self._iter_cropped(plan)
@@ -454,6 +568,41 @@ class GpuImageLoader:
             m = b.shape[0]
             idx, r = order[o:o + m], records[o:o + m] if records is not None else None
             x = self.transform(self.data, idx, rrc=windows[o:o + m], mix=r)
+            o += m
+            tail = (idx,) if self.return_index else ()
+            yield (x, self.labels.index_select(0, idx)) + tail + ((r,) if r is not None else ())
+
+    def _iter_erased(self, plan):
+        a, flat = self.augment, torch.cat(plan)
+        n, D = flat.shape[0], self.transform.out_size
+        # one pinned block and one asynchronous copy: n int64 indices; the n int32 words (augment) or the n two-word records (crop); the n six-word
+        # mix records (mix); then the n eight-word erase records.  Drawn in that order, the erase records last
+        nw = (n + 1) // 2 if a is not None else (n if self.crop is not None else 0)
+        nm = 3 * n if self.mix is not None else 0
+        host = torch.empty(n + nw + nm + 4 * n, dtype=torch.int64, pin_memory=True)
+        host[:n].copy_(flat)
+        if a is not None:
+            host[n:n + nw].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
+        elif self.crop is not None:
+            host[n:n + nw].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.data.shape[1], self.generator))
+        if self.mix is not None:
+            host[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], D, self.generator))
+        host[n + nw + nm:].view(torch.int32).view(n, ERASE_WORDS).copy_(self.erase.draw(n, D, self.generator))
+        dev = host.to(self.device, non_blocking=True)
+        order, boxes = dev[:n], dev[n + nw + nm:].view(torch.int32).view(n, ERASE_WORDS)
+        front = dev[n:n + nw].view(torch.int32)
+        records = dev[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS) if self.mix is not None else None
+        o = 0
+        for b in plan:
+            m = b.shape[0]
+            idx, r = order[o:o + m], records[o:o + m] if records is not None else None
+            if a is not None:
+                x = self.transform(self.data, idx, aug=front[:n][o:o + m], padding_mode=a.padding_mode, fill=a.fill, padding=a.padding, mix=r,
+                                   erase=boxes[o:o + m])
+            elif self.crop is not None:
+                x = self.transform(self.data, idx, rrc=front.view(n, RRC_WORDS)[o:o + m], mix=r, erase=boxes[o:o + m])
+            else:
+                x = self.transform(self.data, idx, mix=r, erase=boxes[o:o + m])
             o += m
             tail = (idx,) if self.return_index else ()
             yield (x, self.labels.index_select(0, idx)) + tail + ((r,) if r is not None else ())

@@ -30,7 +30,16 @@ method of 2., interleaved over the five repetitions in the one process, the reco
 (d) / (f) qatvit_image_batch_rrc with the same mix records.  The expectation under test: (b) within 10 % of (a), (d) of (c), (f) of (e); the exit
 status says whether it held.  --note FILE appends that file's text as with --mix.
 
-usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix | --rrc [--note FILE]]"""
+With --erase it measures only the erasing forms of the kernel and writes profiles/erase_bench.txt: twelve arms with the
+method of 2., interleaved over the five repetitions in the one process, the records of the default RandomErasing - (a) qatvit_image_batch_aug,
+(b) / (b') what a user composes today: (a) + a slice assignment / a normal_() on a view per erased sample, (c) / (d) qatvit_image_batch_erase with
+those records, const / pixel noise, (c<), (d<) / (d>) the records of (c), (d) with the erased samples at the first / last
+batch positions, (e) every sample erased over a third of its area with noise, (f) identity records, (g) / (h) rrc + mixup
+without / with the pixel-noise records.  The condition: (c) faster than (b) and (d) than (b'), beyond both arms' spreads; the exit status says
+whether it held.  (c), (d), (f) against (a), (h) against (g) and (e) are reported, and so is the largest deviation of the kernel's noise from the
+fp64 evaluation of its formula.  --note FILE appends that file's text as with --mix.
+
+usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix | --rrc | --erase [--note FILE]]"""
 import argparse
 import multiprocessing
 import os
@@ -280,6 +289,114 @@ def rrc_arms(lines, data, tr):
     return ok
 
 
+def erase_arms(lines, data, tr):
+    import qat_vit_amd
+    from tests import erase_ref
+
+    B, D = 256, 224
+    g = torch.Generator(device="cuda").manual_seed(1)
+    idx = torch.randint(0, data.shape[0], (B,), device="cuda", generator=g)
+    words = qat_vit_amd.RandomCropFlip(4).draw(B, torch.Generator().manual_seed(1)).cuda()
+    kw = {"aug": words, "padding_mode": "constant", "padding": 4}
+    host_const = qat_vit_amd.RandomErasing().draw(B, D, torch.Generator().manual_seed(1))
+    host_pixel = qat_vit_amd.RandomErasing(value="random").draw(B, D, torch.Generator().manual_seed(1))
+    const, pixel, ident = host_const.cuda(), host_pixel.cuda(), torch.zeros(B, 8, dtype=torch.int32, device="cuda")
+    assert torch.equal(host_const[:, :2], host_pixel[:, :2])
+    # the same pixel-noise records with the erased samples at the first / the last batch positions: the workgroups of a launch start in the order
+    # of the positions, so these two arms show what the place of the touched workgroups inside the launch costs
+    hit = host_pixel.any(1)
+    first, last = torch.cat([host_pixel[hit], host_pixel[~hit]]).cuda(), torch.cat([host_pixel[~hit], host_pixel[hit]]).cuda()
+    const_first = torch.cat([host_const[hit], host_const[~hit]]).cuda()
+    # the worst case: every sample erased, a box of one third of the area (129 x 129 of 224 x 224, edges off the band and float4 grids), noise
+    y0, y1, x0, x1 = 47, 176, 46, 175
+    rng = np.random.default_rng(1)
+    third = torch.tensor([erase_ref.pack(y0, y1, x0, x1, mode=1, key=(int(k[0]), int(k[1]))) for k in rng.integers(0, 1 << 32, (B, 2))],
+                         dtype=torch.int32).cuda()
+    boxes = [(b,) + erase_ref.unpack(r)[:4] for b, r in enumerate(host_const.tolist()) if any(r)]
+    fills = [torch.tensor(erase_ref.unpack(r)[4], device="cuda").view(3, 1, 1) for r in host_const.tolist() if any(r)]
+    host_windows = qat_vit_amd.RandomResizedCrop().draw(B, 32, torch.Generator().manual_seed(1)).cuda()
+    bits = lambda v: int(np.float32(v).view(np.int32))   # noqa: E731
+    lam = np.random.default_rng(1).beta(0.8, 0.8, B).astype(np.float32)
+    mixup = torch.tensor([[B - 1 - b, bits(l), bits(np.float32(1) - l), 0, 0, bits(l)] for b, l in enumerate(lam)], dtype=torch.int32).cuda()
+    outs = [torch.empty(B, 3, D, D, device="cuda") for _ in range(4)]
+
+    def loop_fill(i):
+        x = tr(data, idx, out=outs[i % 4], **kw)
+        for (b, r0, r1, c0, c1), f in zip(boxes, fills):
+            x[b, :, r0:r1, c0:c1] = f
+        return x
+
+    def loop_normal(i):
+        x = tr(data, idx, out=outs[i % 4], **kw)
+        for b, r0, r1, c0, c1 in boxes:
+            x[b, :, r0:r1, c0:c1].normal_()
+        return x
+
+    arms = {"a": ("qatvit_image_batch_aug, words of RandomCropFlip(4)", lambda i: tr(data, idx, out=outs[i % 4], **kw)),
+            "b": (f"(a) + a slice assignment per erased sample ({len(boxes)} of 256)", loop_fill),
+            "b'": (f"(a) + normal_() on a view per erased sample ({len(boxes)} of 256)", loop_normal),
+            "c": ("qatvit_image_batch_erase, default records, const", lambda i: tr(data, idx, out=outs[i % 4], erase=const, **kw)),
+            "d": ("qatvit_image_batch_erase, the same boxes, pixel noise", lambda i: tr(data, idx, out=outs[i % 4], erase=pixel, **kw)),
+            "c<": ("(c) with the erased samples at the first positions", lambda i: tr(data, idx, out=outs[i % 4], erase=const_first, **kw)),
+            "d<": ("(d) with the erased samples at the first positions", lambda i: tr(data, idx, out=outs[i % 4], erase=first, **kw)),
+            "d>": ("(d) with the erased samples at the last positions", lambda i: tr(data, idx, out=outs[i % 4], erase=last, **kw)),
+            "e": ("qatvit_image_batch_erase, every sample, 1/3 of the area, noise", lambda i: tr(data, idx, out=outs[i % 4], erase=third, **kw)),
+            "f": ("qatvit_image_batch_erase, identity records", lambda i: tr(data, idx, out=outs[i % 4], erase=ident, **kw)),
+            "g": ("qatvit_image_batch_rrc, mixup records", lambda i: tr(data, idx, out=outs[i % 4], rrc=host_windows, mix=mixup)),
+            "h": ("qatvit_image_batch_rrc_erase, mixup, default pixel noise", lambda i: tr(data, idx, out=outs[i % 4], rrc=host_windows, mix=mixup,
+                                                                                          erase=pixel))}
+    # what is timed is what the tests hold: the entry equals the loop for constant fills, and identity records give the aug call
+    assert torch.equal(arms["c"][1](0), loop_fill(1)) and torch.equal(arms["f"][1](2), arms["a"][1](3))
+    # the noise against the fp64 evaluation of the header's formula: eight whole-image records with keys of their own
+    keys = [(int(k[0]), int(k[1])) for k in rng.integers(0, 1 << 32, (8, 2))]
+    whole = torch.tensor([erase_ref.pack(0, D, 0, D, mode=1, key=k) for k in keys], dtype=torch.int32).cuda()
+    z = tr(data, idx[:8].contiguous(), erase=whole).cpu().numpy().astype(np.float64)
+    ref = np.stack([erase_ref.noise(k, D) for k in keys])
+    dev = np.abs(z - ref)
+    at = np.unravel_index(dev.argmax(), dev.shape)
+    for _, run in arms.values():
+        for i in range(20):
+            run(i)
+    reps = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (_, run) in arms.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            for i in range(200):
+                run(i)
+            ev[1].record()
+            torch.cuda.synchronize()
+            reps[k].append(ev[0].elapsed_time(ev[1]) / 200 * 1e3)
+    med = {k: statistics.median(v) for k, v in reps.items()}
+    spread = {k: max(v) - min(v) for k, v in reps.items()}
+    area = torch.tensor([(r1 - r0) * (c1 - c0) for _, r0, r1, c0, c1 in boxes]).double() / (D * D)
+    lines.append("kernel with RandomErasing (batch 256, S = 32 -> 224, random index into 50,000 resident images, words of RandomCropFlip(4), constant "
+                 "padding; records of the default RandomErasing, p = 0.25, seed 1), us per batch; HIP events around 200 launches after 20 warm-up "
+                 "launches per arm, five repetitions interleaved a .. h in this one process, output rotating over 616 MB:")
+    lines.append(f"  records drawn: {len(boxes)} of 256 erased, box area {float(area.min()):.3f} .. {float(area.max()):.3f} of the image (mean "
+                 f"{float(area.mean()):.3f}); {float(area.sum()) / B:.4f} of all elements erased; (e): {(y1 - y0) * (x1 - x0) / (D * D):.3f} of every sample")
+    for k, (name, _) in arms.items():
+        lines.append(f"  ({k}) {name + ':':<66} median {med[k]:.1f}  ({', '.join(f'{r:.1f}' for r in reps[k])}); spread {spread[k]:.1f}")
+    ok = True
+    for k, base in (("c", "b"), ("d", "b'")):
+        held = med[k] + spread[k] + spread[base] < med[base]
+        ok = ok and held
+        lines.append(f"  ({k}) / ({base}) = {med[k] / med[base]:.3f}; the condition ({k}) + both spreads = {med[k] + spread[k] + spread[base]:.1f} us < ({base}) = "
+                     f"{med[base]:.1f} us -> {'holds' if held else 'DOES NOT HOLD'}")
+    for k, base in (("c", "a"), ("d", "a"), ("f", "a"), ("h", "g")):
+        lines.append(f"  reported, not required: ({k}) / ({base}) = {med[k] / med[base]:.3f}; ({k}) - ({base}) = {med[k] - med[base]:+.1f} us; expected within "
+                     f"10 %: {1.10 * med[base]:.1f} us -> {'within' if med[k] <= 1.10 * med[base] else 'NOT within'}")
+    lines.append(f"  reported: (e) / (a) = {med['e'] / med['a']:.3f}; (e) - (a) = {med['e'] - med['a']:+.1f} us")
+    lines.append(f"  reported: the place of the touched workgroups in the launch: (c<) - (a) = {med['c<'] - med['a']:+.1f} us, (c) - (a) = "
+                 f"{med['c'] - med['a']:+.1f} us; (d<) - (a) = {med['d<'] - med['a']:+.1f} us, (d) - (a) = "
+                 f"{med['d'] - med['a']:+.1f} us, (d>) - (a) = {med['d>'] - med['a']:+.1f} us")
+    lines.append(f"  noise against the fp64 evaluation of the same formula (tests/erase_ref.py), {dev.size} elements of eight whole-image records: largest "
+                 f"deviation {dev.max():.3e} (at z = {ref[at]:+.4f}), mean {dev.mean():.3e}; largest |z| {np.abs(ref).max():.3f}")
+    lines.append(f"  LDS per workgroup: the erase forms request what their siblings request: aug {lds_bytes(32, D)[0]} B, rrc-mix {lds_bytes(32, D)[1] + 640} B")
+    return ok
+
+
 def lds_bytes(S, D):
     """(aug kernel, mix kernel) dynamic LDS of one workgroup, as csrc/image.hip sizes them: tables, source rows, one or two plane sets."""
     mr = (16 * S + D - 1) // D + 5
@@ -350,13 +467,14 @@ def main():
     ap.add_argument("--augment", action="store_true", help="only the three arms of the augmenting kernel")
     ap.add_argument("--mix", action="store_true", help="only the five arms of the mixing kernel")
     ap.add_argument("--rrc", action="store_true", help="only the six arms of the resized-crop kernels")
-    ap.add_argument("--note", default=None, help="with --mix or --rrc: a text file appended to the output")
+    ap.add_argument("--erase", action="store_true", help="only the arms of the erasing kernels")
+    ap.add_argument("--note", default=None, help="with --mix, --rrc or --erase: a text file appended to the output")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "rrc_bench.txt" if args.rrc else "mix_bench.txt" if args.mix else
+        args.out = os.path.join(ROOT, "profiles", "erase_bench.txt" if args.erase else "rrc_bench.txt" if args.rrc else "mix_bench.txt" if args.mix else
                                 "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
     lines = []
-    if not args.augment and not args.mix and not args.rrc:
+    if not args.augment and not args.mix and not args.rrc and not args.erase:
         host_path(lines)                  # before the first CUDA call: the pool's processes are forked from a process without a GPU context
     if not torch.cuda.is_available():
         raise SystemExit("bench_input_pipeline.py needs an MI355X: there is no CPU form of the pipeline to time")
@@ -367,7 +485,9 @@ def main():
     labels = torch.randint(0, 10, (50000,), device="cuda", generator=g)
     tr = qat_vit_amd.GpuResizeNormalize(32)
     lines.insert(0, f"input pipeline on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
-    if args.rrc:
+    if args.erase:
+        ok = erase_arms(lines, data, tr)
+    elif args.rrc:
         ok = rrc_arms(lines, data, tr)
     elif args.mix:
         ok = mix_arms(lines, data, tr)
@@ -377,7 +497,7 @@ def main():
         kernel_ms = kernel_time(lines, data, tr)
         ok = step_condition(lines, data, labels, tr, kernel_ms, args.steps, args.warmup)
     lines.append(CLOCK_NOTE)
-    if (args.mix or args.rrc) and args.note:
+    if (args.mix or args.rrc or args.erase) and args.note:
         lines.append("")
         lines.append(open(args.note).read().rstrip("\n"))
     text = "\n".join(lines) + "\n"
