@@ -522,6 +522,36 @@ int qatvit_optim_adamw_groups(const void* param_ptrs, const void* grad_ptrs, con
                               int32_t n_chunks, int64_t chunk_elems, const qatvit_adamw_group* groups, int32_t n_groups,
                               const float* clip_out2, void* stream);
 
+/* Weight EMA: an exponential moving average of every parameter, kept by the update launch itself, and the in-place exchange that puts it to use.
+ * ema_ptrs is a DEVICE array of n_tensors fp32 device pointers (one average per tensor, the tensor's numel, disjoint from every other operand);
+ * ema_decay is one value for all tensors and groups and travels by value in the kernel arguments, so a scheduled decay costs no copy and no sync.
+ * Arithmetic, exactly: with w = (float)(1.0 - ema_decay) (double on the host, narrowed once), p' the fp32 parameter value the update just produced
+ * (for qatvit_optim_ema: the parameter as it stands) and e the average,
+ *     d  = p' - e
+ *     e' = (w < 0.5f) ? e + w * d : p' - d * (1.0f - w)
+ * every operation rounded to fp32, none fused (the library is built with -ffp-contract=off).  This is ATen's lerp(e, p', w) in both of its
+ * branches; ema_decay = 0 gives e' = p' exactly.
+ * adamw_ema / adamw_groups_ema: qatvit_optim_adamw / qatvit_optim_adamw_groups with the average as one more read-modify-write stream (36 B per
+ *            parameter instead of 28, no extra launch): same tables, same checks; params, exp_avg and exp_avg_sq come out with the same bits as
+ *            through the entries without the average.  All five tensors of a parameter must be 16-byte aligned for the vector path; otherwise
+ *            that tensor takes the scalar path.
+ * ema:       the same average as a launch of its own over (param, ema) pairs, for tensors that take no update in a step; params are read only.
+ * swap:      exchanges the contents of a[t] and b[t] in place, bit for bit (16 B per element); a[t] and b[t] must not overlap.
+ * Errors (before any HIP call): a null pointer, bad chunking, the hyper-parameter errors of the entry without the average, ema_decay outside
+ * [0, 1) or NaN. */
+int qatvit_optim_adamw_ema(const void* param_ptrs, const void* grad_ptrs, const void* exp_avg_ptrs, const void* exp_avg_sq_ptrs,
+                           const void* ema_ptrs, const int64_t* numel, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                           int32_t n_chunks, int64_t chunk_elems, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int64_t step, double ema_decay, const float* clip_out2, void* stream);
+int qatvit_optim_adamw_groups_ema(const void* param_ptrs, const void* grad_ptrs, const void* exp_avg_ptrs, const void* exp_avg_sq_ptrs,
+                                  const void* ema_ptrs, const int64_t* numel, const int32_t* tensor_group, const int32_t* chunk_tensor,
+                                  const int32_t* chunk_index, int32_t n_chunks, int64_t chunk_elems, const qatvit_adamw_group* groups,
+                                  int32_t n_groups, double ema_decay, const float* clip_out2, void* stream);
+int qatvit_optim_ema(const void* param_ptrs, const void* ema_ptrs, const int64_t* numel, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                     int32_t n_chunks, int64_t chunk_elems, double ema_decay, void* stream);
+int qatvit_optim_swap(const void* a_ptrs, const void* b_ptrs, const int64_t* numel, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                      int32_t n_chunks, int64_t chunk_elems, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Input pipeline: uint8 images resident on the device -> the normalised fp32 batch.
  * Replaces: the per-image host transform of the loaders (qat_trainer.py:209-254, evaluator.py:22-41): Resize(D, BICUBIC) through Pillow,

@@ -1,4 +1,5 @@
-"""Fused gradient clipping + AdamW on MI355X (libqatvit.so: qatvit_optim_grad_norm / qatvit_optim_adamw / qatvit_optim_adamw_groups).
+"""Fused gradient clipping + AdamW on MI355X (libqatvit.so: qatvit_optim_grad_norm / qatvit_optim_adamw / qatvit_optim_adamw_groups, and with a
+weight EMA qatvit_optim_adamw_ema / qatvit_optim_adamw_groups_ema / qatvit_optim_ema / qatvit_optim_swap).
 
 Stands where the reference's loop has (``/root/reference/src/training/qat_trainer.py:360-361``, optimizer built at ``:271-276``)::
 
@@ -12,8 +13,15 @@ as ``optimizer.step(max_norm=1.0)`` (or ``optimizer.clip_grad_norm_(1.0); optimi
 Param groups are first-class: the norm is ONE global L2 norm over every group, and the update of up to ``MAX_GROUPS`` groups with their own
 ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` / step count is ONE launch (``qatvit_optim_adamw_groups``); an optimizer with a single group keeps
 calling ``qatvit_optim_adamw``.  ``vit_param_groups`` builds the two usual ViT layouts (no weight decay on biases, norms and embeddings; layer-wise
-learning-rate decay)."""
+learning-rate decay).
 
+``ema_decay=d`` keeps an exponential moving average of every updated parameter in ``state[p]["ema"]``, written by the update launch itself (the
+``_ema`` entries: one more stream, no extra launch): ``e <- lerp(e, p_new, 1 - d)`` in fp32, ATen's formula (include/qatvit.h states it).  The
+averaged model is evaluated by exchanging contents in place - ``with opt.ema_weights(): evaluate(...)`` - so no address changes and nothing that
+reads parameters by address (the engines, ``export_int8``) has to be rebuilt; ``opt.ema_state_dict(model)`` is its checkpoint.  Only parameters are
+averaged: buffers and observer ranges are the live model's, also while swapped."""
+
+import contextlib
 import operator
 import struct
 
@@ -26,23 +34,65 @@ MAX_GROUPS = 64  # QATVIT_OPTIM_MAX_GROUPS (include/qatvit.h): rows of the prefa
 _HYPER = operator.itemgetter("lr", "betas", "eps", "weight_decay")
 
 
+def _checked_ema_decay(decay):
+    if decay is None:
+        return None
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:   # NaN fails too
+        raise ValueError(f"ClipAdamW: ema_decay {decay} outside [0, 1)")
+    return decay
+
+
+def ema_warmup_decay(decay, updates):
+    """The usual warm-up of an EMA decay: ``min(decay, (1 + updates) / (10 + updates))`` after `updates` optimizer steps, so that the average
+    follows the weights closely at first.  A host helper: assign the result to ``opt.ema_decay`` before each step (it costs no copy and no sync)."""
+    return min(decay, (1 + updates) / (10 + updates))
+
+
 class ClipAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_decay=None):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameters")
+        ema_decay = _checked_ema_decay(ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._tables = None
         self._pending = None   # clip out2 of a clip_grad_norm_() not yet consumed by step()
+        self._ema_decay = ema_decay   # not a param-group entry: state_dict()'s groups stay torch.optim.AdamW's
+        self._idle = []               # (p, ema) of the parameters that have an average but no gradient this step
+        self._pairs = {}              # tables of the two pair launches (qatvit_optim_ema, qatvit_optim_swap)
+        self._swapped = False
+
+    @property
+    def ema_decay(self):
+        """None (no average is kept; the default) or the decay in [0, 1) the next step() uses."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, decay):
+        self._ema_decay = _checked_ema_decay(decay)
+
+    @property
+    def ema_swapped(self) -> bool:
+        """True while the parameters hold the averages and ``state[p]["ema"]`` the live weights (between two swap_ema() calls)."""
+        return self._swapped
 
     # ------------------------------------------------------------------ tables
     def _live_tables(self):
         """One table set for the whole optimizer: the parameters that have a gradient, in group order and then parameter order (torch skips the
         others), keyed on their addresses and group membership.  None if no parameter has a gradient.  The per-step cost is one pass over the
         parameters whatever the number of groups."""
-        ps, tg, live = [], [], []
+        ps, tg, live, ema = [], [], [], self._ema_decay is not None
+        self._idle = idle = []
         for group in self.param_groups:
             n0 = len(ps)
-            ps += [p for p in group["params"] if p.grad is not None]
+            if ema:
+                for p in group["params"]:
+                    if p.grad is not None:
+                        ps.append(p)
+                    elif self._has_ema(p):
+                        idle.append((p, self.state[p]["ema"]))
+            else:
+                ps += [p for p in group["params"] if p.grad is not None]
             if len(ps) != n0:
                 tg += [len(live)] * (len(ps) - n0)
                 live.append(group)
@@ -63,12 +113,22 @@ class ClipAdamW(torch.optim.Optimizer):
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             sts.append(st)
-            ptrs.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()))
+            if ema:
+                if "ema" not in st:   # before the first update of p with a decay set (also after a checkpoint without averages)
+                    st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+                ptrs.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["ema"].data_ptr()))
+            else:
+                ptrs.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()))
         key = (ptrs, tg)
         t = self._tables
         if t is None or t["key"] != key:
             i64 = lambda xs: torch.tensor(xs, dtype=torch.int64, device=dev)   # noqa: E731
             i32 = lambda xs: torch.tensor(xs, dtype=torch.int32, device=dev)   # noqa: E731
+            if ema:   # an average may come from a checkpoint: it is written through, so its extent is checked whenever an address is new
+                for p, st in zip(ps, sts):
+                    e = st["ema"]
+                    if e.shape != p.shape or e.dtype != torch.float32 or e.device != dev or not e.is_contiguous():
+                        raise RuntimeError("ClipAdamW: state[p]['ema'] must be a contiguous fp32 tensor of the parameter's shape on its device")
             starts, ct, ci = [tg.index(gi) for gi in range(len(live))], [], []
             for ti, p in enumerate(ps):
                 n = (p.numel() + _CHUNK - 1) // _CHUNK
@@ -76,6 +136,7 @@ class ClipAdamW(torch.optim.Optimizer):
                 ci += list(range(n))
             t = dict(key=key, n=len(ct),
                      params=i64([k[0] for k in ptrs]), grads=i64([k[1] for k in ptrs]), m=i64([k[2] for k in ptrs]), v=i64([k[3] for k in ptrs]),
+                     ema=i64([k[4] for k in ptrs]) if ema else None,
                      tg=i32(tg), numel=i64([p.numel() for p in ps]), ct=i32(ct), ci=i32(ci),
                      starts=starts, first=[starts[gi] for gi in tg],   # the first tensor of each group; per tensor, the first of its group
                      pack=struct.Struct("=" + "5dq" * len(live)).pack,
@@ -83,6 +144,32 @@ class ClipAdamW(torch.optim.Optimizer):
             self._tables = t
         t["live"], t["sts"] = live, sts
         return t
+
+    def _pair_tables(self, slot, pairs):
+        """The tables of a launch over (a, b) tensor pairs (the stand-alone average, the swap), keyed on the addresses; None if there is no element."""
+        key = [(a.data_ptr(), b.data_ptr()) for a, b in pairs]
+        t = self._pairs.get(slot)
+        if t is None or t["key"] != key:
+            dev, ct, ci = pairs[0][0].device, [], []
+            for ti, (a, b) in enumerate(pairs):
+                if not (a.is_cuda and b.device == a.device and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+                        and a.numel() == b.numel()):
+                    raise RuntimeError("ClipAdamW: a parameter and its average must be contiguous fp32 CUDA tensors of one size on one device")
+                n = (a.numel() + _CHUNK - 1) // _CHUNK
+                ct += [ti] * n
+                ci += list(range(n))
+            t = self._pairs[slot] = dict(key=key, n=len(ct), a=torch.tensor([k[0] for k in key], dtype=torch.int64, device=dev),
+                                         b=torch.tensor([k[1] for k in key], dtype=torch.int64, device=dev),
+                                         numel=torch.tensor([a.numel() for a, _ in pairs], dtype=torch.int64, device=dev),
+                                         ct=torch.tensor(ct, dtype=torch.int32, device=dev), ci=torch.tensor(ci, dtype=torch.int32, device=dev))
+        return t if t["n"] else None
+
+    def _average_idle(self):
+        """One qatvit_optim_ema launch for the parameters that have an average but took no update this step (none, normally: nothing is launched)."""
+        t = self._pair_tables("idle", self._idle) if self._idle else None
+        if t is not None:
+            native.check(native.lib().qatvit_optim_ema(t["a"].data_ptr(), t["b"].data_ptr(), t["numel"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(),
+                                                       t["n"], _CHUNK, self._ema_decay, native.stream_ptr()), "qatvit_optim_ema")
 
     def _grad_norm(self, t, max_norm):
         native.check(native.lib().qatvit_optim_grad_norm(t["grads"].data_ptr(), t["numel"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK,
@@ -95,6 +182,7 @@ class ClipAdamW(torch.optim.Optimizer):
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         """Total L2 norm of all gradients of all param groups (one launch pair over one table); the clip coefficient is applied inside the next
         step() instead of re-writing the gradients."""
+        self._refuse_swapped("clip_grad_norm_()")
         t = self._live_tables()
         if t is None:
             return torch.zeros(())
@@ -104,12 +192,14 @@ class ClipAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, max_norm=None):
         loss = None
+        self._refuse_swapped("step()")
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         t = self._live_tables()
         if t is None:
             self._pending = None
+            self._average_idle()
             return loss
         steps = [st["step"] for st in t["sts"]]
         count = torch.stack(steps).tolist()
@@ -119,24 +209,85 @@ class ClipAdamW(torch.optim.Optimizer):
             self._grad_norm(t, max_norm)
         L = native.lib()
         clip = self._pending.data_ptr() if self._pending is not None else None
+        # with a weight EMA the `_ema` entry of the same name: ema_ptrs after exp_avg_sq_ptrs, the decay (by value, as the prefactors) in front of clip
+        ema = t["ema"] is not None
+        sfx, e_ptr, e_decay = ("_ema", (t["ema"].data_ptr(),), (self._ema_decay,)) if ema else ("", (), ())
         if len(self.param_groups) == 1:
             group = t["live"][0]
             b1, b2 = group["betas"]
-            native.check(L.qatvit_optim_adamw(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), t["numel"].data_ptr(),
-                                              t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK, float(group["lr"]), float(b1), float(b2),
-                                              float(group["eps"]), float(group["weight_decay"]), int(count[0]) + 1, clip, native.stream_ptr()),
-                         "qatvit_optim_adamw")
+            name = "qatvit_optim_adamw" + sfx
+            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr, t["numel"].data_ptr(),
+                                      t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK, float(group["lr"]), float(b1), float(b2),
+                                      float(group["eps"]), float(group["weight_decay"]), int(count[0]) + 1, *e_decay, clip, native.stream_ptr())
         else:   # the rows of struct qatvit_adamw_group, packed on the host; they go by value into the kernel arguments: a new lr costs no copy
             rows = []
             for (lr, (b1, b2), eps, wd), i in zip(map(_HYPER, t["live"]), t["starts"]):
                 rows += (lr, b1, b2, eps, wd, int(count[i]) + 1)
-            native.check(L.qatvit_optim_adamw_groups(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(),
-                                                     t["numel"].data_ptr(), t["tg"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK,
-                                                     t["pack"](*rows), len(t["live"]), clip, native.stream_ptr()),
-                         "qatvit_optim_adamw_groups")
+            name = "qatvit_optim_adamw_groups" + sfx
+            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr,
+                                      t["numel"].data_ptr(), t["tg"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK,
+                                      t["pack"](*rows), len(t["live"]), *e_decay, clip, native.stream_ptr())
+        native.check(status, name)
+        if ema:
+            self._average_idle()
         torch._foreach_add_(steps, 1)
         self._pending = None
         return loss
+
+    # ------------------------------------------------------------------ the averaged weights
+    def _refuse_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f"ClipAdamW: the averaged weights are swapped in (swap_ema() / ema_weights()); swap back before {what}")
+
+    def _has_ema(self, p):
+        return "ema" in self.state.get(p, ())   # .get: looking must not create the state of a parameter that has none
+
+    def ema_parameters(self):
+        """Per param group, the tensors that hold the averaged values, aligned with ``group["params"]``: ``state[p]["ema"]`` (the parameter itself
+        while swapped), and the parameter itself where there is no average yet (a parameter that never had a gradient is its own average)."""
+        return [[self.state[p]["ema"] if self._has_ema(p) and not self._swapped else p for p in group["params"]] for group in self.param_groups]
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchanges the contents of every (parameter, average) pair in place, in one launch; no address changes.  ``ema_swapped`` tells which way
+        round they are; while it is True, step() and clip_grad_norm_() raise."""
+        pairs = [(p, self.state[p]["ema"]) for group in self.param_groups for p in group["params"] if self._has_ema(p)]
+        t = self._pair_tables("swap", pairs) if pairs else None
+        if t is not None:
+            native.check(native.lib().qatvit_optim_swap(t["a"].data_ptr(), t["b"].data_ptr(), t["numel"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(),
+                                                        t["n"], _CHUNK, native.stream_ptr()), "qatvit_optim_swap")
+            # the launch wrote through raw addresses: tell torch, so that what is keyed on a weight's `_version` (the native frozen-teacher forward
+            # that a float model in eval() under no_grad runs through keeps fp16 / bf16 copies of the weights) sees the exchange
+            torch.autograd.graph.increment_version([x for pair in pairs for x in pair])
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with opt.ema_weights():`` - the model computes with the averaged weights inside the block (evaluate, export); the live weights are
+        back after it, also when the block raises.  Buffers and observer ranges are not averaged: they are the live model's throughout."""
+        if self._swapped:
+            raise RuntimeError("ClipAdamW: the averaged weights are swapped in already")
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self, model):
+        """``model.state_dict()`` (through DistributedDataParallel's ``.module``) with the entry of every optimised parameter replaced by a clone of
+        its average: the checkpoint of the averaged model, in the format the loaders of the live model read.  Buffers are the live ones."""
+        if isinstance(model, torch.nn.parallel.DistributedDataParallel):
+            model = model.module
+        avg = {id(p): e for group, es in zip(self.param_groups, self.ema_parameters()) for p, e in zip(group["params"], es)}
+        sd = model.state_dict()
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if name in sd and id(p) in avg:
+                sd[name] = avg[id(p)].detach().clone()
+        return sd
+
+    def state_dict(self):
+        self._refuse_swapped("state_dict()")   # "ema" would be saved holding the live weights
+        return super().state_dict()
 
 
 # ---------------------------------------------------------------------- the usual ViT param groups
