@@ -648,6 +648,37 @@ int qatvit_optim_swap(const void* a_ptrs, const void* b_ptrs, const int64_t* num
  *   record, so none can cause a read or a write outside out[b].  The kernels keep nothing more in LDS: the refusals are the siblings'.
  *   aug, mix may be NULL with their meanings above (no words; no mixing); rrc == NULL is refused.  erase == NULL makes the call
  *   qatvit_image_batch_mix's / qatvit_image_batch_rrc's: that entry's kernel is launched and the result is bitwise its result.
+ *
+ * qatvit_image_batch_color / qatvit_image_batch_rrc_color: the same launches with the colour augmentations of the fine-tuning recipes
+ *   (torchvision's ColorJitter without hue, RandomGrayscale with three output channels, RandomSolarize) where those recipes have them: on the
+ *   uint8 RGB D x D image behind the resize (what Pillow's resize returns) and in front of ToTensor() + Normalize(), so in front of the erase
+ *   and of the mix.  color int32 [B][4] on the device, contiguous, 4-byte aligned, one record per batch POSITION b:
+ *     word 0  bits 0-1, 2-3, 4-5: the jitter op of slot 0, 1, 2 (0 = none, 1 = brightness, 2 = contrast, 3 = saturation), applied in slot
+ *             order; an op code that an earlier slot held is skipped.  Bit 8: grayscale.  Bit 9: solarize, with the threshold 0 .. 255 in
+ *             bits 16-23.  All other bits are ignored.
+ *     word 1, 2, 3  the factor of brightness, contrast, saturation, fp32 bits.  A factor that is negative or not finite makes its op the
+ *             identity; factor 1 is the identity by the formula.
+ *   The all-zero record is the identity.  Per sample, in this order: grayscale, solarize, the jitter ops.  For a pixel (R, G, B), with
+ *   L(R, G, B) = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 (Pillow's convert("L")):
+ *     grayscale      R = G = B = L
+ *     solarize(t)    v < t ? v : 255 - v, per channel (ImageOps.solarize)
+ *     blend(in1, in2, a), per channel: t = fl32(fl32(in1) + fl32(a * fl32(in2 - in1))) with a in fp32, THE PRODUCT AND THE SUM ROUNDED ONE BY
+ *                    ONE: a fused multiply-add is forbidden here (it changes 2 bytes in 1.5 million against Pillow's Image.blend);
+ *                    0 <= a <= 1: out = (uint8) trunc(t); otherwise out = t <= 0 ? 0 : t >= 255 ? 255 : trunc(t)
+ *     brightness(f)  blend(0, v, f)
+ *     contrast(f)    blend(m, v, f), m = (2 * s + D * D) / (2 * D * D) in integers (Python's int(s / (D * D) + 0.5)), s = the sum of L over ALL
+ *                    D x D pixels of this sample's image as it stands right in front of the contrast op: behind grayscale, solarize and the
+ *                    jitter ops of the earlier slots.  s <= 255 * 384 * 384 < 2^26.
+ *     saturation(f)  blend(L, v, f), L of the pixel as it stands
+ *   The result EQUALS, byte for byte, what Pillow's ImageOps / ImageEnhance give (tests/golden/color_kat.npz).  The partner of a mix record is
+ *   coloured by ITS OWN record color[p] with its own sum, as it is erased by its own record.  erase == NULL here means all-zero erase records.
+ *   sums uint32 [B] on the device, 4-byte aligned: a workspace whose contents on entry are ignored.  The entry zeroes it on the stream and runs
+ *   a statistics launch in front of the batch launch; on return sums[b] = s of position b, and 0 where record b holds no contrast op (after the
+ *   cleaning above).  sums == NULL IS THE CALLER'S PROMISE THAT NO RECORD HOLDS A CONTRAST OP: no statistics launch runs, and a contrast op
+ *   met anyway is the identity.
+ *   A malformed record gives exactly the result of the cleaned record, and nothing is addressed through a record.  The kernels keep nothing
+ *   more in LDS: the refusals are the siblings'.  color == NULL makes the call qatvit_image_batch_erase's / qatvit_image_batch_rrc_erase's:
+ *   that entry's kernel is launched and the result is bitwise its result (sums is then not touched).
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -666,6 +697,12 @@ int qatvit_image_batch_erase(const uint8_t* data, const int64_t* index, int32_t 
                              const int32_t* erase, float* out, void* stream);
 int qatvit_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
                                  const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, void* stream);
+int qatvit_image_batch_color(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                             const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix,
+                             const int32_t* erase, const int32_t* color, uint32_t* sums, float* out, void* stream);
+int qatvit_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
+                                 const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color,
+                                 uint32_t* sums, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

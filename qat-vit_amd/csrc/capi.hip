@@ -508,6 +508,45 @@ int qatvit_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int3
     return 0;
 }
 
+int qatvit_image_batch_color(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                             const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix,
+                             const int32_t* erase, const int32_t* color, uint32_t* sums, float* out, void* stream) {
+    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch_color: null pointer argument");
+    if (image_shape_ok("qatvit_image_batch_color", S, D)) return 1;
+    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_color: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
+    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_color: batch %d of a data set of %d images needs an index", B, N);
+    QV_CHECK_ARG(padding_mode == 0 || padding_mode == 1, "qatvit_image_batch_color: unknown padding_mode %d (0 = constant, 1 = reflect)", padding_mode);
+    QV_CHECK_ARG(fill >= 0 && fill <= 255, "qatvit_image_batch_color: fill %d is outside 0 .. 255", fill);
+    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)aug & 3) == 0 &&
+                     ((uintptr_t)mix & 3) == 0 && ((uintptr_t)erase & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)sums & 3) == 0,
+                 "qatvit_image_batch_color: misaligned pointer");
+    // the shape's LDS request is checked here, before any HIP call
+    if (int rc = launch_image_batch_color(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, erase, color, sums, out,
+                                          (hipStream_t)stream))
+        return rc;
+    QV_CHECK_LAUNCH("qatvit_image_batch_color");
+    return 0;
+}
+
+int qatvit_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
+                                 const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color,
+                                 uint32_t* sums, float* out, void* stream) {
+    QV_CHECK_ARG(data && windows && table && out, "qatvit_image_batch_rrc_color: null pointer argument");
+    QV_CHECK_ARG(rrc, "qatvit_image_batch_rrc_color: rrc is NULL (the call without window records is qatvit_image_batch_color)");
+    if (image_shape_ok("qatvit_image_batch_rrc_color", S, D)) return 1;
+    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_rrc_color: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B,
+                 N);
+    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_rrc_color: batch %d of a data set of %d images needs an index", B, N);
+    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)windows & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)rrc & 3) == 0 &&
+                     ((uintptr_t)mix & 3) == 0 && ((uintptr_t)erase & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)sums & 3) == 0,
+                 "qatvit_image_batch_rrc_color: misaligned pointer");
+    // the shape's LDS request is checked here, before any HIP call
+    if (int rc = launch_image_batch_rrc_color(data, index, B, N, S, D, windows, table, rrc, mix, erase, color, sums, out, (hipStream_t)stream))
+        return rc;
+    QV_CHECK_LAUNCH("qatvit_image_batch_rrc_color");
+    return 0;
+}
+
 int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {
     RowMoveTab t;
     t.n = 1; t.m[0] = RowMove{tall, compact, stride, width};

@@ -183,7 +183,119 @@ __device__ __forceinline__ void img_erase_apply(const ImgErase e, int c, int y, 
     for (int j = 0; j < 4; ++j) v[j] = x + j >= e.x0 && x + j < e.x1 ? z[j] : v[j];
 }
 
+// The colour forms: an all-zero erase record, for erase == NULL
+__device__ __forceinline__ ImgErase img_erase_none() {
+    ImgErase e;
+    e.y0 = e.y1 = e.x0 = e.x1 = 0;
+    e.touched = e.noise = false;
+    e.f0 = e.f1 = e.f2 = 0.0f;
+    e.k0 = e.k1 = 0u;
+    return e;
+}
+
+// The colour forms: one side's record (include/qatvit.h: the record of qatvit_image_batch_color) as the workgroup needs it.  A malformed record
+// is cleaned, not trusted, and nothing is addressed through it: an op code that an earlier slot held, and an op whose factor is negative or not
+// finite, become "none"; so does contrast where the caller passed no sums.  before_contrast (the statistics launch) drops the contrast op and
+// the slots behind it.  mean = Python's int(s / (D * D) + 0.5) of the sum s that the statistics launch left in sums[b].
+enum { kColNone = 0, kColBrightness = 1, kColContrast = 2, kColSaturation = 3 };
+
+struct ImgColor {
+    int op0, op1, op2;
+    bool gray, solarize, contrast, any;
+    int threshold, mean;
+    float fb, fc, fs;
+};
+
+__device__ __forceinline__ ImgColor img_color(const int32_t* __restrict__ rec, const uint32_t* __restrict__ sums, int b, int D, bool before_contrast) {
+    ImgColor c;
+    const int w0 = rec[0];
+    c.fb = __int_as_float(rec[1]), c.fc = __int_as_float(rec[2]), c.fs = __int_as_float(rec[3]);
+    // f >= 0 && f < inf is false for a NaN
+    const bool ok_b = c.fb >= 0.0f && c.fb < INFINITY, ok_c = c.fc >= 0.0f && c.fc < INFINITY, ok_s = c.fs >= 0.0f && c.fs < INFINITY;
+    const int s0 = w0 & 3, s1 = (w0 >> 2) & 3, s2 = (w0 >> 4) & 3;
+    const int d1 = s1 == s0 ? kColNone : s1, d2 = s2 == s0 || s2 == s1 ? kColNone : s2;
+    c.contrast = ok_c && (s0 == kColContrast || d1 == kColContrast || d2 == kColContrast);
+    const bool keep_c = c.contrast && !before_contrast && sums != nullptr;
+    auto cleaned = [&](int op) { return op == kColBrightness ? (ok_b ? op : kColNone) : op == kColContrast ? (keep_c ? op : kColNone) : op == kColSaturation ? (ok_s ? op : kColNone) : kColNone; };
+    c.op0 = cleaned(s0), c.op1 = cleaned(d1), c.op2 = cleaned(d2);
+    if (before_contrast) {
+        if (s0 == kColContrast) c.op1 = c.op2 = kColNone;
+        if (d1 == kColContrast) c.op2 = kColNone;
+    }
+    c.gray = (w0 >> 8) & 1, c.solarize = (w0 >> 9) & 1;
+    c.threshold = (w0 >> 16) & 255;
+    c.mean = 0;
+    if (keep_c) {
+        const uint32_t dd = (uint32_t)(D * D);
+        c.mean = (int)((2u * sums[b] + dd) / (2u * dd));   // s <= 255 * 384 * 384 < 2^26
+    }
+    c.any = c.gray || c.solarize || c.op0 != kColNone || c.op1 != kColNone || c.op2 != kColNone;
+    return c;
+}
+
+// Pillow's convert("L")
+__device__ __forceinline__ int img_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
+
+// Pillow's Image.blend as ImageEnhance calls it: fl(in1 + fl(a * (v - in1))), the product and the sum rounded one by one (never fused: a fused
+// multiply-add changes bytes), truncated and clipped to 0 .. 255.  For 0 <= a <= 1 the sum lies between in1 and v, where the clip does nothing.
+// t is finite (a is finite, the operands are bytes), so the clip is one median: v_med3_f32 in place of two compares and two selects.
+__device__ __forceinline__ int img_blend(int in1, int v, float a) {
+    const float t = __fadd_rn((float)in1, __fmul_rn(a, (float)(v - in1)));
+    return (int)__builtin_amdgcn_fmed3f(t, 0.0f, 255.0f);
+}
+
+// in1 = 0: fl(0 + x) is x (a -0.0 product, from a = -0.0 or v = 0, clips to 0 like +0.0), so the sum is left out
+__device__ __forceinline__ int img_blend0(int v, float a) { return (int)__builtin_amdgcn_fmed3f(__fmul_rn(a, (float)v), 0.0f, 255.0f); }
+
+__device__ __forceinline__ void img_color_op(int op, const ImgColor c, int& r, int& g, int& b) {
+    if (op == kColBrightness) {
+        r = img_blend0(r, c.fb), g = img_blend0(g, c.fb), b = img_blend0(b, c.fb);
+    } else if (op == kColContrast) {
+        r = img_blend(c.mean, r, c.fc), g = img_blend(c.mean, g, c.fc), b = img_blend(c.mean, b, c.fc);
+    } else if (op == kColSaturation) {
+        const int l = img_luma(r, g, b);
+        r = img_blend(l, r, c.fs), g = img_blend(l, g, c.fs), b = img_blend(l, b, c.fs);
+    }
+}
+
+// The chain on the four pixels of an item: grayscale, solarize, then the record's ops in slot order.  Every branch is workgroup-uniform.
+__device__ __forceinline__ void img_color_apply(const ImgColor c, int px[3][4]) {
+    if (!c.any) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int r = px[0][j], g = px[1][j], b = px[2][j];
+        if (c.gray) r = g = b = img_luma(r, g, b);
+        if (c.solarize) {
+            r = r < c.threshold ? r : 255 - r, g = g < c.threshold ? g : 255 - g, b = b < c.threshold ? b : 255 - b;
+        }
+        img_color_op(c.op0, c, r, g, b);
+        img_color_op(c.op1, c, r, g, b);
+        img_color_op(c.op2, c, r, g, b);
+        px[0][j] = r, px[1][j] = g, px[2][j] = b;
+    }
+}
+
+// The colour forms' vertical pass of one item: four neighbouring pixels of one output row in all three channels, as bytes 0 .. 255
+__device__ __forceinline__ void img_vertical4(const uint32_t* plane, int D4, int rel, int last, const int4 k, int px[3][4]) {
+    const int o0 = max(0, min(rel, last)) * 3 * D4, o1 = max(0, min(rel + 1, last)) * 3 * D4;
+    const int o2 = max(0, min(rel + 2, last)) * 3 * D4, o3 = max(0, min(rel + 3, last)) * 3 * D4;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t t0 = plane[o0 + c * D4], t1 = plane[o1 + c * D4], t2 = plane[o2 + c * D4], t3 = plane[o3 + c * D4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int acc = 1 << (kImgBits - 1);
+            acc += __mul24((int)((t0 >> (8 * j)) & 255), k.x);
+            acc += __mul24((int)((t1 >> (8 * j)) & 255), k.y);
+            acc += __mul24((int)((t2 >> (8 * j)) & 255), k.z);
+            acc += __mul24((int)((t3 >> (8 * j)) & 255), k.w);
+            px[c][j] = img_round_clip(acc);
+        }
+    }
+}
+
 // the kernel, once per form (image_kernel.h)
+#define QV_IMAGE_COLOR 0
 #define QV_IMAGE_ERASE 0
 #define QV_IMAGE_RRC 0
 #define QV_IMAGE_MIX 0
@@ -231,6 +343,44 @@ __device__ __forceinline__ void img_erase_apply(const ImgErase e, int c, int y, 
 #undef QV_IMAGE_AUG
 #undef QV_IMAGE_MIX
 #undef QV_IMAGE_RRC
+// the four colour forms (the erasing forms with a colour record per side; erase == NULL: no boxes), then the two statistics forms
+#undef QV_IMAGE_COLOR
+#define QV_IMAGE_COLOR 1
+#define QV_IMAGE_RRC 0
+#define QV_IMAGE_AUG 1
+#define QV_IMAGE_MIX 0
+#include "image_kernel.h"
+#undef QV_IMAGE_MIX
+#define QV_IMAGE_MIX 1
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
+#define QV_IMAGE_RRC 1
+#define QV_IMAGE_AUG 0
+#define QV_IMAGE_MIX 0
+#include "image_kernel.h"
+#undef QV_IMAGE_MIX
+#define QV_IMAGE_MIX 1
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
+#undef QV_IMAGE_COLOR
+#define QV_IMAGE_COLOR 2
+#define QV_IMAGE_RRC 0
+#define QV_IMAGE_AUG 1
+#define QV_IMAGE_MIX 0
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_RRC
+#define QV_IMAGE_RRC 1
+#define QV_IMAGE_AUG 0
+#include "image_kernel.h"
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
+#undef QV_IMAGE_COLOR
 #undef QV_IMAGE_ERASE
 
 int64_t image_lds_bytes(int S, int D) {
@@ -340,6 +490,74 @@ int launch_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int 
     } else {
         auto kern = D == 224 ? k_image_batch_rrc_erase<224> : k_image_batch_rrc_erase<0>;
         hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, erase);
+    }
+    return 0;
+}
+
+// The colour forms keep nothing more in LDS either (the statistics launch keeps one plane set): the requests and their refusals are those of the
+// forms without colour records.  With sums, the workspace is zeroed and the statistics launch runs first, both on the stream.
+int launch_image_batch_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, const int32_t* color,
+                             uint32_t* sums, float* out, hipStream_t st) {
+    if (!color) return launch_image_batch_erase(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, erase, out, st);
+    const int64_t lds = mix ? image_mix_lds_bytes(S, D) : image_lds_bytes(S, D);
+    if (mix && lds > kImgMixMaxLds) {
+        set_error("qatvit_image_batch_color: source %d -> output %d needs %lld bytes of LDS for two plane sets, more than %d", S, D, (long long)lds,
+                  kImgMixMaxLds);
+        return 1;
+    }
+    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
+    if (sums) {
+        const hipError_t e = hipMemsetAsync(sums, 0, (size_t)B * sizeof(uint32_t), st);
+        if (e != hipSuccess) {
+            set_error("qatvit_image_batch_color: zeroing sums failed: %s", hipGetErrorString(e));
+            return 2;
+        }
+        auto stat = D == 224 ? k_image_stat_aug<224> : k_image_stat_aug<0>;
+        hipLaunchKernelGGL(stat, grid, dim3(kImgThreads), (size_t)image_lds_bytes(S, D), st, data, index, N, S, D, image_max_rows(S, D), coeffs, aug,
+                           padding_mode, fill, color, sums);
+    }
+    if (mix) {
+        auto kern = D == 224 ? k_image_batch_mix_color<224> : k_image_batch_mix_color<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
+                           padding_mode, fill, mix, erase, color, (const uint32_t*)sums);
+    } else {
+        auto kern = D == 224 ? k_image_batch_aug_color<224> : k_image_batch_aug_color<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
+                           padding_mode, fill, erase, color, (const uint32_t*)sums);
+    }
+    return 0;
+}
+
+int launch_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
+                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color, uint32_t* sums, float* out,
+                                 hipStream_t st) {
+    if (!color) return launch_image_batch_rrc_erase(data, index, B, N, S, D, windows, table, rrc, mix, erase, out, st);
+    const int64_t lds = image_rrc_lds_bytes(S, D, mix != nullptr);
+    if (lds > kImgMixMaxLds) {
+        set_error("qatvit_image_batch_rrc_color: source %d -> output %d needs %lld bytes of LDS%s, more than %d", S, D, (long long)lds,
+                  mix ? " for two plane sets" : "", kImgMixMaxLds);
+        return 1;
+    }
+    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
+    if (sums) {
+        const hipError_t e = hipMemsetAsync(sums, 0, (size_t)B * sizeof(uint32_t), st);
+        if (e != hipSuccess) {
+            set_error("qatvit_image_batch_rrc_color: zeroing sums failed: %s", hipGetErrorString(e));
+            return 2;
+        }
+        auto stat = D == 224 ? k_image_stat_rrc<224> : k_image_stat_rrc<0>;
+        hipLaunchKernelGGL(stat, grid, dim3(kImgThreads), (size_t)image_rrc_lds_bytes(S, D, 0), st, data, index, N, S, D, image_max_rows(S, D), windows,
+                           rrc, color, sums);
+    }
+    if (mix) {
+        auto kern = D == 224 ? k_image_batch_rrc_mix_color<224> : k_image_batch_rrc_mix_color<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, mix,
+                           erase, color, (const uint32_t*)sums);
+    } else {
+        auto kern = D == 224 ? k_image_batch_rrc_color<224> : k_image_batch_rrc_color<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, erase,
+                           color, (const uint32_t*)sums);
     }
     return 0;
 }

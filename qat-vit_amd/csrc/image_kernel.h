@@ -14,6 +14,13 @@
 // partner.  The aug form of this switch takes aug == NULL as the zero word.  The directives of the switch add text for those four forms only: with
 // QV_IMAGE_ERASE 0 the five other kernels are compiled from the token sequence they had (profiles/erase_bench.txt).  QV_IMAGE_ERASE must be defined
 // (0 or 1) by the including file.
+// QV_IMAGE_COLOR 1 (with QV_IMAGE_ERASE 1) gives k_image_batch_aug_color<DT>, _mix_color, _rrc_color and _rrc_mix_color: the erasing forms with the
+// colour record of the side (include/qatvit.h) applied to the uint8 pixels between the vertical pass and the value table, so their vertical pass
+// has another item, four pixels in all three channels, and erase == NULL stands for all-zero erase records.  QV_IMAGE_COLOR 2 gives
+// k_image_stat_aug<DT> and k_image_stat_rrc<DT>, the statistics launch in front of them: the same staging and passes, the chain up to the
+// contrast op, and the sum of the luma into sums[b]; no table, no output.  The directives of the switch add text for those six forms only: with
+// QV_IMAGE_COLOR 0 the nine other kernels are compiled from the token sequence they had (profiles/color_bench.txt).  QV_IMAGE_COLOR must be
+// defined (0, 1 or 2) by the including file.
 // DT = the output size as a constant (its divisions become multiplications), or 0: taken from D_rt.
 #if QV_IMAGE_RRC
 #define QV_IMAGE_XLAST xlast   // the last column of the window
@@ -21,7 +28,47 @@
 #define QV_IMAGE_XLAST S - 1
 #endif
 template <int DT>
-#if QV_IMAGE_ERASE
+#if QV_IMAGE_COLOR == 2
+#if QV_IMAGE_RRC
+__global__ __launch_bounds__(kImgThreads) void k_image_stat_rrc(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
+                                                                int max_rows, const int32_t* __restrict__ windows, const int32_t* __restrict__ rrc,
+                                                                const int32_t* __restrict__ color, uint32_t* __restrict__ sums) {
+#else
+__global__ __launch_bounds__(kImgThreads) void k_image_stat_aug(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
+                                                                int max_rows, const int32_t* __restrict__ coeffs, const int32_t* __restrict__ aug,
+                                                                int reflect, int fill, const int32_t* __restrict__ color,
+                                                                uint32_t* __restrict__ sums) {
+#endif
+#elif QV_IMAGE_COLOR
+#if QV_IMAGE_RRC && QV_IMAGE_MIX
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N,
+                                                                           int S, int D_rt, int max_rows, const int32_t* __restrict__ windows,
+                                                                           const float* __restrict__ table, float* __restrict__ out,
+                                                                           const int32_t* __restrict__ rrc, const int32_t* __restrict__ mix,
+                                                                           const int32_t* __restrict__ erase, const int32_t* __restrict__ color,
+                                                                           const uint32_t* __restrict__ sums) {
+#elif QV_IMAGE_RRC
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                       int D_rt, int max_rows, const int32_t* __restrict__ windows,
+                                                                       const float* __restrict__ table, float* __restrict__ out,
+                                                                       const int32_t* __restrict__ rrc, const int32_t* __restrict__ erase,
+                                                                       const int32_t* __restrict__ color, const uint32_t* __restrict__ sums) {
+#elif QV_IMAGE_MIX
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_mix_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
+                                                                       const float* __restrict__ table, float* __restrict__ out,
+                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
+                                                                       const int32_t* __restrict__ mix, const int32_t* __restrict__ erase,
+                                                                       const int32_t* __restrict__ color, const uint32_t* __restrict__ sums) {
+#else
+__global__ __launch_bounds__(kImgThreads) void k_image_batch_aug_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
+                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
+                                                                       const float* __restrict__ table, float* __restrict__ out,
+                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
+                                                                       const int32_t* __restrict__ erase, const int32_t* __restrict__ color,
+                                                                       const uint32_t* __restrict__ sums) {
+#endif
+#elif QV_IMAGE_ERASE
 #if QV_IMAGE_RRC && QV_IMAGE_MIX
 __global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N,
                                                                            int S, int D_rt, int max_rows, const int32_t* __restrict__ windows,
@@ -109,6 +156,18 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     // nothing of the partner and the sample's weight 1: fl(1 * v) + fl(0 * v) is v, and the band stores what the aug kernel stores
     const bool as_is = !partner && w_self == 1.0f;
 #endif
+#if QV_IMAGE_COLOR == 2
+    // the statistics form: the chain of the workgroup's record up to its contrast op; a record without one asks for nothing
+    const ImgColor col_b = img_color(color + 4 * b, nullptr, b, D, true);
+    if (!col_b.contrast) return;
+#elif QV_IMAGE_COLOR
+    // the colour record is the workgroup's (and its partner's, where the band takes something from it): four scalar loads per side, cleaned,
+    // and the side's sum of the statistics launch (img_color, image.hip)
+    const ImgColor col_b = img_color(color + 4 * b, sums, b, D, false);
+#if QV_IMAGE_MIX
+    const ImgColor col_p = sides == 2 ? img_color(color + 4 * p, sums, p, D, false) : col_b;
+#endif
+#endif
     int64_t img = index ? index[b] : b;
     img = img < 0 ? 0 : (img >= N ? N - 1 : img);        // the range is the caller's contract; a bad index must still not read outside data
 
@@ -119,7 +178,9 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
 #if QV_IMAGE_MIX
     const ImgWindow win_p = sides == 2 ? img_window(rrc + 2 * p, windows, S, D, y0, y1, max_rows) : win_b;
 #endif
+#if QV_IMAGE_COLOR != 2
     for (int i = tid; i < 768; i += kImgThreads) s_table[i] = table[i];
+#endif
 #else
     // rows of the source this band reads; clamped so that tables other than qatvit_image_resize_coeffs' cannot send a read outside the image
     int r0 = coeffs[y0], r1 = coeffs[y1 - 1] + coeffs[D + y1 - 1];
@@ -129,7 +190,9 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
 
     for (int i = tid; i < D; i += kImgThreads) s_xmin[i] = coeffs[i];
     for (int i = tid; i < D * kImgTaps; i += kImgThreads) s_coef[i] = coeffs[2 * D + i];
+#if QV_IMAGE_COLOR != 2
     for (int i = tid; i < 768; i += kImgThreads) s_table[i] = table[i];
+#endif
 #endif
 #if QV_IMAGE_MIX
     for (int side = 0; side < sides; ++side) {
@@ -234,7 +297,13 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
     const int r0 = win_b.r0, nrows = win_b.nrows;
 #endif
 #endif
-#if QV_IMAGE_ERASE
+#if QV_IMAGE_COLOR == 1
+    // the erase records as below; no records (erase == NULL) are all-zero records
+    const ImgErase er_b = erase ? img_erase(erase + 8 * b, D, y0, y1) : img_erase_none();
+#if QV_IMAGE_MIX
+    const ImgErase er_p = sides == 2 && erase ? img_erase(erase + 8 * p, D, y0, y1) : er_b;
+#endif
+#elif QV_IMAGE_ERASE && !QV_IMAGE_COLOR
     // the erase record is the workgroup's (and its partner's, where the band takes something from it): eight scalar loads per side, clamped;
     // `touched` is workgroup-uniform, and a band that no box meets runs what the form without the switch runs (img_erase, image.hip)
     const ImgErase er_b = img_erase(erase + 8 * b, D, y0, y1);
@@ -244,6 +313,96 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
 #endif
     __syncthreads();
 
+#if QV_IMAGE_COLOR
+    // vertical pass of the colour forms: one item = four neighbouring pixels of one output row in ALL THREE channels (grayscale, saturation and
+    // the luma need them together).  The chain runs on the integers the vertical pass has formed; behind it stand the three lookups in the
+    // value table, the erase, the mix and three float4 stores - or, in the statistics forms, nothing but the luma sum.
+    const int band4 = (y1 - y0) * D4;
+#if QV_IMAGE_COLOR == 2
+    uint32_t lsum = 0;
+#else
+    float* obase = out + (int64_t)b * 3 * D * D + (int64_t)y0 * D;
+#endif
+    for (int it = tid; it < band4; it += kImgThreads) {
+        const int y = y0 + it / D4, x4 = it % D4;
+#if QV_IMAGE_RRC
+        const int4 k = ((const int4*)(s_band + kImgBand))[y - y0];
+        const int rel = s_band[y - y0] - r0, last = nrows - 1;
+#else
+        const int4 k = ((const int4*)s_coef)[y];
+        const int rel = s_xmin[y] - r0, last = nrows - 1;
+#endif
+        const uint32_t* plane = (const uint32_t*)s_tmp + x4;
+        int px[3][4];
+        img_vertical4(plane, D4, rel, last, k, px);
+        img_color_apply(col_b, px);
+#if QV_IMAGE_COLOR == 2
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lsum += (uint32_t)img_luma(px[0][j], px[1][j], px[2][j]);
+#else
+        float v[3][4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[c][j] = s_table[c * 256 + px[c][j]];
+            if (er_b.touched) img_erase_apply(er_b, c, y, x4, D4, v[c]);
+        }
+#if QV_IMAGE_MIX
+        // as the forms without colour: the partner's value of the same elements, coloured by the partner's record with the partner's sum
+        // and erased by the partner's record, then the blend or the box
+        if (!as_is) {
+            float u[3][4];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) u[c][j] = v[c][j];
+            if (sides == 2) {
+#if QV_IMAGE_RRC
+                const int32_t* band_p = s_band + kImgBand * (1 + kImgTaps);
+                const int4 k = ((const int4*)(band_p + kImgBand))[y - y0];
+                const int rel = band_p[y - y0] - win_p.r0, last = win_p.nrows - 1;
+#endif
+                img_vertical4(plane + partner4, D4, rel, last, k, px);
+                img_color_apply(col_p, px);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) u[c][j] = s_table[c * 256 + px[c][j]];
+                    if (er_p.touched) img_erase_apply(er_p, c, y, x4, D4, u[c]);
+                }
+            }
+            const bool row_in = box && y >= by0 && y < by1;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int x = x4 * 4 + j;
+                    const float a = w_self * v[c][j], c2 = w_partner * u[c][j];
+                    v[c][j] = row_in && x >= bx0 && x < bx1 ? u[c][j] : a + c2;
+                }
+        }
+#endif
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            *(float4*)(obase + (int64_t)c * D * D + (int64_t)it * 4) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+#endif
+    }
+#if QV_IMAGE_COLOR == 2
+    // the workgroup's sum: the waves by shuffles, the four wave sums through the first words of s_src (dead behind the horizontal pass), and one
+    // integer atomic per workgroup - integer adds commute, so sums[b] is exact whatever the order of the workgroups
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lsum += __shfl_down(lsum, off);
+    uint32_t* s_part = (uint32_t*)s_src;
+    if ((tid & 63) == 0) s_part[tid >> 6] = lsum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (int i = 0; i < kImgThreads / 64; ++i) total += s_part[i];
+        atomicAdd(sums + b, total);
+    }
+#endif
+}
+#else
     // vertical pass + value table + store
     const int band4 = (y1 - y0) * D4;
     float* obase = out + (int64_t)b * 3 * D * D + (int64_t)y0 * D;
@@ -314,4 +473,5 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
         *(float4*)(obase + (int64_t)c * D * D + (int64_t)e * 4) = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
+#endif
 #undef QV_IMAGE_XLAST

@@ -366,6 +366,16 @@ int launch_image_batch_erase(const uint8_t* data, const int64_t* index, int B, i
                              const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st);
 int launch_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
                                  const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st);
+// the same two with a colour record per batch position (color int32 [B][4]: jitter ops in order, grayscale, solarize, three factors;
+// include/qatvit.h), applied to the uint8 pixels of the sample and of its partner in front of the value table.  erase == nullptr here: all-zero
+// erase records.  sums uint32 [B] (or nullptr: contrast is the identity): zeroed, then filled by a statistics launch in front of the batch launch,
+// all on st.  color == nullptr: launch_image_batch_erase / launch_image_batch_rrc_erase.  No LDS of their own
+int launch_image_batch_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
+                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, const int32_t* color,
+                             uint32_t* sums, float* out, hipStream_t st);
+int launch_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
+                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color, uint32_t* sums, float* out,
+                                 hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

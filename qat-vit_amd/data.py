@@ -1,5 +1,6 @@
 """Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug /
-qatvit_image_batch_mix / qatvit_image_resize_coeffs_windows / qatvit_image_batch_rrc / qatvit_image_batch_erase / qatvit_image_batch_rrc_erase).
+qatvit_image_batch_mix / qatvit_image_resize_coeffs_windows / qatvit_image_batch_rrc / qatvit_image_batch_erase / qatvit_image_batch_rrc_erase /
+qatvit_image_batch_color / qatvit_image_batch_rrc_color).
 
 Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
 ``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
@@ -8,6 +9,8 @@ writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced,
 ``MixupCutmix`` adds mixup / cutmix behind them, still inside that launch (section 7m); ``functional.kd_ce_loss_mix`` takes the same records.
 ``RandomResizedCrop`` stands instead of ``RandomCropFlip``: every sample is a window of its image, resized, inside the same launch (section 7n).
 ``RandomErasing`` erases a box of every sample's normalised output, behind either and in front of the mix, inside the same launch (section 7o).
+``ColorJitter`` applies grayscale, solarize, brightness, contrast and saturation to the uint8 image behind the resize, equal to Pillow's, inside
+the same launch; contrast takes the sample's mean luma from a statistics launch in front of it (section 7q).
 There is no CPU path: CPU tensors raise."""
 import math
 import os
@@ -296,6 +299,73 @@ class RandomErasing:
         return ((rec + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32)    # the 32 bits of every word, as int32
 
 
+COLOR_WORDS = 4
+COLOR_OPS = {"brightness": 1, "contrast": 2, "saturation": 3}
+
+
+def _jitter_range(name, v):
+    """torchvision's ColorJitter._check_input: a number x >= 0 means [max(0, 1 - x), 1 + x], a pair means [lo, hi] with 0 <= lo <= hi, both
+    finite.  None where the range is [1, 1]: the op is not enabled."""
+    number = lambda t: not isinstance(t, bool) and isinstance(t, (int, float)) and math.isfinite(t)   # noqa: E731
+    if number(v):
+        if v < 0:
+            raise ValueError(f"{name} must be a number >= 0 or a pair 0 <= low <= high, got {v!r}")
+        lo, hi = max(0.0, 1.0 - float(v)), 1.0 + float(v)
+    elif isinstance(v, (tuple, list)) and len(v) == 2 and all(number(t) for t in v) and 0 <= v[0] <= v[1]:
+        lo, hi = float(v[0]), float(v[1])
+    else:
+        raise ValueError(f"{name} must be a number >= 0 or a pair of finite numbers 0 <= low <= high, got {v!r}")
+    return None if lo == hi == 1.0 else (lo, hi)
+
+
+class ColorJitter:
+    """torchvision's ``ColorJitter(brightness, contrast, saturation)`` + ``RandomGrayscale(grayscale)`` (three output channels) +
+    ``RandomSolarize(solarize_threshold, solarize)`` of the uint8 image behind the resize as one four-word int32 record per sample
+    (include/qatvit.h): word 0 the jitter ops in the order they are applied (two bits per slot: 1 brightness, 2 contrast, 3 saturation), bit 8
+    grayscale, bit 9 solarize with the threshold in bits 16..23; words 1..3 the factors of brightness, contrast, saturation (fp32 bits).  Per
+    sample the order is grayscale, solarize, the jitter ops; the result equals Pillow's.  ``brightness`` / ``contrast`` / ``saturation`` have
+    torchvision's meaning: a number x is the range ``[max(0, 1 - x), 1 + x]``, a pair is ``[low, high]``; 0 disables the op.  ``hue`` is not
+    supported (neither timm's default recipe nor DeiT-III's 3-Augment uses it) and anything but 0 raises; so is Gaussian blur.  Built and drawn
+    on the host; needs no GPU."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, grayscale=0.0, solarize=0.0, solarize_threshold=128):
+        if isinstance(hue, bool) or not isinstance(hue, (int, float)) or hue != 0:
+            raise ValueError(f"hue is not supported by the native pipeline (Pillow's HSV round trip is not restated): it must stay 0, got {hue!r}")
+        self.brightness, self.contrast = _jitter_range("brightness", brightness), _jitter_range("contrast", contrast)
+        self.saturation = _jitter_range("saturation", saturation)
+        for name, v in (("grayscale", grayscale), ("solarize", solarize)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+                raise ValueError(f"{name} must be a probability 0 .. 1, got {v!r}")
+        if isinstance(solarize_threshold, bool) or not isinstance(solarize_threshold, int) or not 0 <= solarize_threshold <= 255:
+            raise ValueError(f"solarize_threshold must be an integer byte value 0 .. 255, got {solarize_threshold!r}")
+        self.grayscale, self.solarize, self.solarize_threshold = float(grayscale), float(solarize), solarize_threshold
+
+    def draw(self, n, generator=None):
+        """int32 CPU tensor [n, 4].  The rule, all from `generator`, in this order:
+        ``o = torch.rand(n, 3, dtype=float64).argsort(1)``: row k is a uniformly random order of (brightness, contrast, saturation); the
+        enabled ops of that order, kept in it, fill the slots from slot 0 - a uniformly random order of the enabled ops;
+        ``f = torch.rand(n, 3, dtype=float64)``: the factor of op j is ``fp32(low_j + f[:, j] * (high_j - low_j))``;
+        ``p = torch.rand(n, 2, dtype=float64)``: grayscale where ``p[:, 0] < grayscale``, solarize where ``p[:, 1] < solarize``.
+        The factor word of a disabled op and the threshold of a sample that is not solarized are 0.  Every draw is always made, so the
+        generator ends where it ends for any setting: its position depends on `n` only."""
+        order = torch.rand(n, 3, dtype=torch.float64, generator=generator).argsort(1)
+        f = torch.rand(n, 3, dtype=torch.float64, generator=generator)
+        p = torch.rand(n, 2, dtype=torch.float64, generator=generator)
+        ranges = (self.brightness, self.contrast, self.saturation)
+        enabled = torch.tensor([r is not None for r in ranges])
+        on = enabled[order]                                            # [n, 3]: is the op at this place of the order enabled
+        slot = on.to(torch.int64).cumsum(1) - 1
+        rec = torch.zeros(n, COLOR_WORDS, dtype=torch.int64)
+        rec[:, 0] = torch.where(on, (order + 1) << (2 * slot).clamp_min(0), torch.zeros_like(order)).sum(1)
+        rec[:, 0] |= (p[:, 0] < self.grayscale).to(torch.int64) << 8
+        rec[:, 0] |= (p[:, 1] < self.solarize).to(torch.int64) * (1 << 9 | self.solarize_threshold << 16)
+        for j, r in enumerate(ranges):
+            if r is not None:
+                factor = (r[0] + f[:, j] * (r[1] - r[0])).to(torch.float32)
+                rec[:, 1 + j] = factor.view(torch.int32).to(torch.int64)
+        return rec.to(torch.int32)
+
+
 class GpuResizeNormalize:
     """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch.
     With ``aug`` (int32 ``[B]`` on the device, the words of ``RandomCropFlip.draw``; word b belongs to batch position b) the source of sample b is
@@ -309,7 +379,12 @@ class GpuResizeNormalize:
     apply.  The tables of every window side are built on the first such call and kept on the device.
     With ``erase`` (int32 ``[B, 8]`` on the device, the records of ``RandomErasing.draw``; record b belongs to batch position b) the box of sample
     b's record is filled, or set to noise, in its normalised output, in the same launch: behind ``aug`` / ``rrc`` and in front of ``mix``, whose
-    partner is erased by its own record."""
+    partner is erased by its own record.
+    With ``color`` (int32 ``[B, 4]`` on the device, the records of ``ColorJitter.draw``; record b belongs to batch position b) the uint8 image
+    behind the resize goes through grayscale, solarize and the jitter ops of its record, in the same launch: behind ``aug`` / ``rrc``, in front
+    of ``Normalize``, ``erase`` and ``mix``, whose partner is coloured by its own record.  The contrast op needs the mean luma of the whole
+    sample, which a statistics launch in front of the batch launch sums into ``color_sums(B)``; ``contrast=False`` is the caller's promise that
+    no record holds a contrast op, and leaves that launch out."""
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
         self.src_size, self.out_size = int(src_size), int(out_size)
@@ -328,7 +403,17 @@ class GpuResizeNormalize:
             self.windows = resize_window_tables(self.src_size, self.out_size).to(self.device)
         return self.windows
 
-    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None, erase=None):
+    def color_sums(self, B):
+        """The uint32 ``[B]`` workspace (as int32) that the calls with ``color`` records of a batch of B hand to the library, one per batch size,
+        made on first use: behind such a call element b holds the luma sum that the contrast op of record b used (0: no contrast op)."""
+        if getattr(self, "_sums", None) is None:
+            self._sums = {}
+        if B not in self._sums:
+            self._sums[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
+        return self._sums[B]
+
+    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None, erase=None,
+                 color=None, contrast=True):
         S, D = self.src_size, self.out_size
         if rrc is not None and aug is not None:
             raise ValueError("rrc and aug are mutually exclusive: the rrc record carries its own flip, and padding does not apply to a window")
@@ -366,10 +451,32 @@ class GpuResizeNormalize:
             if not isinstance(erase, torch.Tensor) or erase.dtype != torch.int32 or tuple(erase.shape) != (B, ERASE_WORDS) \
                     or not erase.is_contiguous() or erase.device != self.device:
                 raise ValueError(f"erase must be a contiguous int32 [{B}, {ERASE_WORDS}] tensor on {self.device}")
+        if color is not None:
+            if not isinstance(color, torch.Tensor) or color.dtype != torch.int32 or tuple(color.shape) != (B, COLOR_WORDS) \
+                    or not color.is_contiguous() or color.device != self.device:
+                raise ValueError(f"color must be a contiguous int32 [{B}, {COLOR_WORDS}] tensor on {self.device}")
         if rrc is not None:
             if not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
                     or rrc.device != self.device:
                 raise ValueError(f"rrc must be a contiguous int32 [{B}, {RRC_WORDS}] tensor on {self.device}")
+        if color is not None:
+            # the colour entries: every other record may be absent; without `contrast` no workspace is passed and no statistics launch runs
+            if B:
+                opt = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+                sums = self.color_sums(B).data_ptr() if contrast else None
+                with torch.cuda.device(self.device):
+                    if rrc is not None:
+                        native.check(native.lib().qatvit_image_batch_rrc_color(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
+                                                                               self.table.data_ptr(), rrc.data_ptr(), opt(mix), opt(erase),
+                                                                               color.data_ptr(), sums, out.data_ptr(), native.stream_ptr()),
+                                     "qatvit_image_batch_rrc_color")
+                    else:
+                        native.check(native.lib().qatvit_image_batch_color(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(),
+                                                                           self.table.data_ptr(), opt(aug), mode, fill, opt(mix), opt(erase),
+                                                                           color.data_ptr(), sums, out.data_ptr(), native.stream_ptr()),
+                                     "qatvit_image_batch_color")
+            return out
+        if rrc is not None:
             if B and erase is not None:
                 with torch.cuda.device(self.device):
                     native.check(native.lib().qatvit_image_batch_rrc_erase(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
@@ -435,10 +542,14 @@ class GpuImageLoader:
     tuples are the same.  ``erase`` (a ``RandomErasing``) erases a box of every drawn sample's output inside the same launch, with ``augment`` or
     ``crop`` and in front of ``mix``: an epoch's records are drawn last, after the plan, the words or windows and the mix records, so that a seed
     gives the plan, words, windows and mix records it gives without ``erase``; they travel in the same copy, four int64 elements per sample, and the
-    yielded tuples are the same (the loss needs nothing from an erase record)."""
+    yielded tuples are the same (the loss needs nothing from an erase record).  ``color`` (a ``ColorJitter``) applies grayscale, solarize and
+    the colour jitter to every drawn sample inside the same launch (behind a statistics launch where contrast is enabled), with ``augment`` or
+    ``crop``, with or without ``mix`` / ``erase``: an epoch's colour records are drawn last of all, after the erase records, so that a seed
+    gives the plan, words, windows, mix and erase records it gives without ``color``; they travel in the same copy, two int64 elements per
+    sample, and the yielded tuples are the same (the loss needs nothing from a colour record)."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
-                 return_index=False, augment=None, mix=None, crop=None, erase=None):
+                 return_index=False, augment=None, mix=None, crop=None, erase=None, color=None):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -470,6 +581,9 @@ class GpuImageLoader:
         if erase is not None and not isinstance(erase, RandomErasing):
             raise TypeError(f"erase must be a RandomErasing, got {type(erase).__name__}")
         self.erase = erase
+        if color is not None and not isinstance(color, ColorJitter):
+            raise TypeError(f"color must be a ColorJitter, got {type(color).__name__}")
+        self.color = color
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -479,7 +593,7 @@ class GpuImageLoader:
         plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
         if not plan:
             return
-        if self.erase is not None:
+        if self.erase is not None or self.color is not None:
             yield from self._iter_erased(plan)
             return
         if self.crop is not None:
@@ -576,10 +690,12 @@ class GpuImageLoader:
         a, flat = self.augment, torch.cat(plan)
         n, D = flat.shape[0], self.transform.out_size
         # one pinned block and one asynchronous copy: n int64 indices; the n int32 words (augment) or the n two-word records (crop); the n six-word
-        # mix records (mix); then the n eight-word erase records.  Drawn in that order, the erase records last
+        # mix records (mix); the n eight-word erase records (erase); then the n four-word colour records (color).  Drawn in that order
         nw = (n + 1) // 2 if a is not None else (n if self.crop is not None else 0)
         nm = 3 * n if self.mix is not None else 0
-        host = torch.empty(n + nw + nm + 4 * n, dtype=torch.int64, pin_memory=True)
+        ne = 4 * n if self.erase is not None else 0
+        nc = 2 * n if self.color is not None else 0
+        host = torch.empty(n + nw + nm + ne + nc, dtype=torch.int64, pin_memory=True)
         host[:n].copy_(flat)
         if a is not None:
             host[n:n + nw].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
@@ -587,9 +703,19 @@ class GpuImageLoader:
             host[n:n + nw].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.data.shape[1], self.generator))
         if self.mix is not None:
             host[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], D, self.generator))
-        host[n + nw + nm:].view(torch.int32).view(n, ERASE_WORDS).copy_(self.erase.draw(n, D, self.generator))
+        if self.erase is not None:
+            host[n + nw + nm:n + nw + nm + ne].view(torch.int32).view(n, ERASE_WORDS).copy_(self.erase.draw(n, D, self.generator))
+        if self.color is not None:
+            host[n + nw + nm + ne:].view(torch.int32).view(n, COLOR_WORDS).copy_(self.color.draw(n, self.generator))
         dev = host.to(self.device, non_blocking=True)
-        order, boxes = dev[:n], dev[n + nw + nm:].view(torch.int32).view(n, ERASE_WORDS)
+        order = dev[:n]
+        boxes = dev[n + nw + nm:n + nw + nm + ne].view(torch.int32).view(n, ERASE_WORDS) if self.erase is not None else None
+        colors = dev[n + nw + nm + ne:].view(torch.int32).view(n, COLOR_WORDS) if self.color is not None else None
+        wants_sums = self.color is not None and self.color.contrast is not None   # the statistics launch runs only where contrast is enabled
+
+        def late(o, m):
+            return {"erase": None if boxes is None else boxes[o:o + m], "color": None if colors is None else colors[o:o + m], "contrast": wants_sums}
+
         front = dev[n:n + nw].view(torch.int32)
         records = dev[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS) if self.mix is not None else None
         o = 0
@@ -598,11 +724,11 @@ class GpuImageLoader:
             idx, r = order[o:o + m], records[o:o + m] if records is not None else None
             if a is not None:
                 x = self.transform(self.data, idx, aug=front[:n][o:o + m], padding_mode=a.padding_mode, fill=a.fill, padding=a.padding, mix=r,
-                                   erase=boxes[o:o + m])
+                                   **late(o, m))
             elif self.crop is not None:
-                x = self.transform(self.data, idx, rrc=front.view(n, RRC_WORDS)[o:o + m], mix=r, erase=boxes[o:o + m])
+                x = self.transform(self.data, idx, rrc=front.view(n, RRC_WORDS)[o:o + m], mix=r, **late(o, m))
             else:
-                x = self.transform(self.data, idx, mix=r, erase=boxes[o:o + m])
+                x = self.transform(self.data, idx, mix=r, **late(o, m))
             o += m
             tail = (idx,) if self.return_index else ()
             yield (x, self.labels.index_select(0, idx)) + tail + ((r,) if r is not None else ())

@@ -39,7 +39,14 @@ without / with the pixel-noise records.  The condition: (c) faster than (b) and 
 whether it held.  (c), (d), (f) against (a), (h) against (g) and (e) are reported, and so is the largest deviation of the kernel's noise from the
 fp64 evaluation of its formula.  --note FILE appends that file's text as with --mix.
 
-usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix | --rrc | --erase [--note FILE]]"""
+With --color it measures only the colour forms of the kernel and writes profiles/color_bench.txt: eight arms with the method
+of 2., interleaved over the five repetitions in the one process - (a) the erase entry of the parent with the default erase records, (b) the colour
+entry with the records of ColorJitter(0.4, 0.4, 0.4) and the same erase records, (b-) the same records without the workspace (no statistics
+launch), (c) jitter(0.4, 0, 0.4), (d) / (d-) identity colour records with / without the workspace, (e) the 3-Augment records, (f) the same chain
+as torch ops on the float batch (time only).  Every comparison is against (a), the parent's entry; nothing is required, the figures are
+reported.  --note FILE appends that file's text as with --mix.
+
+usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix | --rrc | --erase | --color [--note FILE]]"""
 import argparse
 import multiprocessing
 import os
@@ -397,6 +404,90 @@ def erase_arms(lines, data, tr):
     return ok
 
 
+def color_arms(lines, data, tr):
+    import qat_vit_amd
+    from tests import color_ref
+
+    B, D = 256, 224
+    g = torch.Generator(device="cuda").manual_seed(1)
+    idx = torch.randint(0, data.shape[0], (B,), device="cuda", generator=g)
+    words = qat_vit_amd.RandomCropFlip(4).draw(B, torch.Generator().manual_seed(1)).cuda()
+    kw = {"aug": words, "padding_mode": "constant", "padding": 4}
+    boxes = qat_vit_amd.RandomErasing().draw(B, D, torch.Generator().manual_seed(1)).cuda()
+    host_full = qat_vit_amd.ColorJitter(0.4, 0.4, 0.4).draw(B, torch.Generator().manual_seed(1))
+    host_two = qat_vit_amd.ColorJitter(0.4, 0, 0.4).draw(B, torch.Generator().manual_seed(1))
+    host_aug3 = qat_vit_amd.ColorJitter(0.3, 0.3, 0.3, grayscale=1 / 3, solarize=1 / 3).draw(B, torch.Generator().manual_seed(1))
+    full, two, aug3, ident = host_full.cuda(), host_two.cuda(), host_aug3.cuda(), torch.zeros(B, 4, dtype=torch.int32, device="cuda")
+    outs = [torch.empty(B, 3, D, D, device="cuda") for _ in range(4)]
+    # the same chain as torch ops on a float batch in [0, 255] (brightness, contrast, saturation in that order; for time only: no rounding to
+    # bytes between the ops, so its values are not Pillow's)
+    fac = host_full[:, 1:].contiguous().view(torch.float32).cuda()
+    fb, fc, fs = (fac[:, k].view(B, 1, 1, 1) for k in range(3))
+    lw = torch.tensor([0.299, 0.587, 0.114], device="cuda").view(1, 3, 1, 1)
+    mean, std = torch.tensor(MEAN, device="cuda").view(1, 3, 1, 1), torch.tensor(STD, device="cuda").view(1, 3, 1, 1)
+
+    def composed(i):
+        x = tr(data, idx, out=outs[i % 4], **kw)
+        x = (x * std + mean) * 255.0                                 # back to the byte range
+        x = (x * fb).clamp_(0, 255)
+        m = (x * lw).sum(1, keepdim=True).mean((2, 3), keepdim=True)
+        x = (m + fc * (x - m)).clamp_(0, 255)
+        l = (x * lw).sum(1, keepdim=True)
+        x = (l + fs * (x - l)).clamp_(0, 255)
+        return (x / 255.0 - mean) / std
+
+    arms = {"a": ("qatvit_image_batch_erase, default erase records (the parent's entry)", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, **kw)),
+            "b": ("qatvit_image_batch_color, jitter(0.4, 0.4, 0.4), the same erase records", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes,
+                                                                                                       color=full, **kw)),
+            "b-": ("(b)'s records without a workspace: contrast the identity, no statistics launch", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes,
+                                                                                                            color=full, contrast=False, **kw)),
+            "c": ("qatvit_image_batch_color, jitter(0.4, 0, 0.4): contrast left out", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=two,
+                                                                                                contrast=False, **kw)),
+            "d": ("qatvit_image_batch_color, identity records, with the workspace", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=ident,
+                                                                                              **kw)),
+            "d-": ("qatvit_image_batch_color, identity records, no workspace", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=ident,
+                                                                                        contrast=False, **kw)),
+            "e": ("3-Augment: gray 1/3, solarize 1/3, jitter(0.3, 0.3, 0.3)", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=aug3, **kw)),
+            "f": ("qatvit_image_batch_aug + the chain as torch ops on the float batch (time only)", composed)}
+    # what is timed is what the tests hold: identity records give the erase entry's batch, and the sums are those of the host restatement
+    assert torch.equal(arms["d"][1](0), arms["a"][1](1)) and torch.equal(arms["d-"][1](2), arms["a"][1](3))
+    arms["b"][1](0)
+    sums = (tr.color_sums(B).cpu().to(torch.int64) & 0xffffffff)
+    assert int((sums > 0).sum()) == B
+    for _, run in arms.values():
+        for i in range(20):
+            run(i)
+    reps = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (_, run) in arms.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            for i in range(200):
+                run(i)
+            ev[1].record()
+            torch.cuda.synchronize()
+            reps[k].append(ev[0].elapsed_time(ev[1]) / 200 * 1e3)
+    med = {k: statistics.median(v) for k, v in reps.items()}
+    spread = {k: max(v) - min(v) for k, v in reps.items()}
+    n_gray = sum(color_ref.unpack(r)[1] for r in host_aug3.tolist())
+    n_sol = sum(color_ref.unpack(r)[2] for r in host_aug3.tolist())
+    lines.append("kernel with the colour augmentations (batch 256, S = 32 -> 224, random index into 50,000 resident images, words of RandomCropFlip(4), "
+                 "constant padding, erase records of the default RandomErasing, colour records of ColorJitter drawn once with seed 1), us per batch; "
+                 "HIP events around 200 launches after 20 warm-up launches per arm, five repetitions interleaved a .. f in this one process, output "
+                 "rotating over 616 MB.  (b), (d), (e) are three stream operations per batch: the zeroing of sums, the statistics launch, the batch launch:")
+    lines.append(f"  records drawn: (b) every sample holds three ops in a random order; (e) {n_gray} of 256 grayscale, {n_sol} of 256 solarized")
+    for k, (name, _) in arms.items():
+        lines.append(f"  ({k}) {name + ':':<84} median {med[k]:.1f}  ({', '.join(f'{r:.1f}' for r in reps[k])}); spread {spread[k]:.1f}")
+    for k, base in (("b", "a"), ("b-", "a"), ("c", "a"), ("d", "a"), ("d-", "a"), ("e", "a"), ("b", "f")):
+        lines.append(f"  reported: ({k}) / ({base}) = {med[k] / med[base]:.3f}; ({k}) - ({base}) = {med[k] - med[base]:+.1f} us")
+    lines.append(f"  the statistics launch and the zeroing, by difference: (b) - (b-) = {med['b'] - med['b-']:+.1f} us (this also holds the contrast op's own "
+                 f"arithmetic in the batch launch); with records that ask for nothing (every workgroup returns at once): (d) - (d-) = "
+                 f"{med['d'] - med['d-']:+.1f} us")
+    lines.append(f"  LDS per workgroup: the colour forms request what their siblings request: aug {lds_bytes(32, D)[0]} B; the statistics launch the same")
+    return True
+
+
 def lds_bytes(S, D):
     """(aug kernel, mix kernel) dynamic LDS of one workgroup, as csrc/image.hip sizes them: tables, source rows, one or two plane sets."""
     mr = (16 * S + D - 1) // D + 5
@@ -468,13 +559,14 @@ def main():
     ap.add_argument("--mix", action="store_true", help="only the five arms of the mixing kernel")
     ap.add_argument("--rrc", action="store_true", help="only the six arms of the resized-crop kernels")
     ap.add_argument("--erase", action="store_true", help="only the arms of the erasing kernels")
-    ap.add_argument("--note", default=None, help="with --mix, --rrc or --erase: a text file appended to the output")
+    ap.add_argument("--color", action="store_true", help="only the arms of the colour kernels")
+    ap.add_argument("--note", default=None, help="with --mix, --rrc, --erase or --color: a text file appended to the output")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "erase_bench.txt" if args.erase else "rrc_bench.txt" if args.rrc else "mix_bench.txt" if args.mix else
+        args.out = os.path.join(ROOT, "profiles", "color_bench.txt" if args.color else "erase_bench.txt" if args.erase else "rrc_bench.txt" if args.rrc else "mix_bench.txt" if args.mix else
                                 "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
     lines = []
-    if not args.augment and not args.mix and not args.rrc and not args.erase:
+    if not args.augment and not args.mix and not args.rrc and not args.erase and not args.color:
         host_path(lines)                  # before the first CUDA call: the pool's processes are forked from a process without a GPU context
     if not torch.cuda.is_available():
         raise SystemExit("bench_input_pipeline.py needs an MI355X: there is no CPU form of the pipeline to time")
@@ -485,7 +577,9 @@ def main():
     labels = torch.randint(0, 10, (50000,), device="cuda", generator=g)
     tr = qat_vit_amd.GpuResizeNormalize(32)
     lines.insert(0, f"input pipeline on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
-    if args.erase:
+    if args.color:
+        ok = color_arms(lines, data, tr)
+    elif args.erase:
         ok = erase_arms(lines, data, tr)
     elif args.rrc:
         ok = rrc_arms(lines, data, tr)
@@ -497,7 +591,7 @@ def main():
         kernel_ms = kernel_time(lines, data, tr)
         ok = step_condition(lines, data, labels, tr, kernel_ms, args.steps, args.warmup)
     lines.append(CLOCK_NOTE)
-    if (args.mix or args.rrc or args.erase) and args.note:
+    if (args.mix or args.rrc or args.erase or args.color) and args.note:
         lines.append("")
         lines.append(open(args.note).read().rstrip("\n"))
     text = "\n".join(lines) + "\n"
