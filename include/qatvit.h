@@ -369,6 +369,22 @@ int32_t qatvit_student_ln_in_strip(const qatvit_cfg* cfg, int32_t flags);
  * queue the next step 2 - 3 ms earlier.  qatvit_student_init clears the mirror. */
 int qatvit_student_dy16_set_mirror(const qatvit_cfg* cfg, void* workspace, void* host_pinned, void* stream);
 int qatvit_student_dy16_to_pair(const qatvit_cfg* cfg, void* workspace, void* stream);
+/* Stochastic depth (drop-path): a per-sample multiplier on each residual branch, x = x + fq(branch) * s - behind the activation fake-quant of the proj / fc2
+ * output and in front of the add, where the DropPath module stands in the prepared tree.
+ *  scale_table: DEVICE float [2 * depth][batch] for the cfg->batch of the calls that follow, indexed [branch][sample]; row 2 i = block i's attention branch,
+ *  row 2 i + 1 = its MLP branch.  Any finite multipliers (timm's DropPath: 0 or 1 / keep).  NULL unbinds.
+ * Host-side binding only (no launch, no stream): every forward / backward entry on this workspace - qatvit_student_forward, _backward and the staged / part
+ * entries qatvit_student_forward_stages, _forward_part, _backward_stages - reads the table bound at the time of the call.  Contract: a forward and the
+ * backward that follows it read the SAME table at the SAME address (bind once, rewrite its contents between steps); nothing bound - the state after
+ * qatvit_student_init, which unbinds - is the step without drop-path, with the same launches as before this entry existed.
+ * Lifetime: the binding is keyed by the workspace ADDRESS and outlives the memory.  Unbind (NULL) before freeing a workspace or its table, or call the
+ * workspace's _init entry on whatever is placed at that address next; the library never dereferences a table outside a forward / backward call.
+ * Forward: product and sum are rounded separately (no fused multiply-add), as the two stock ops round them, so equal fq(branch) gives bit-equal x and an
+ * all-ones table gives the bits of the step without one.  Backward: the gradient entering the branch is (d loss / d x) * STE mask * s[sample], in the pair and
+ * the one-plane form (whose recorded maxima include s) and on the class-token rows of the last block.
+ * Two limits.  With a table bound, the LayerNorm backward runs as its own kernel behind the plain fc1 / qkv dgrad, not in the dgrad's epilogue (that epilogue
+ * does not know the multipliers).  The GEMMs of a dropped sample (s = 0) are not skipped: it costs what a kept one costs, as in stock torch. */
+int qatvit_student_set_drop_path(const qatvit_cfg* cfg, void* workspace, const float* scale_table);
 int qatvit_student_forward_stages(const qatvit_cfg* cfg, void* const* params, const qatvit_fq* act_fq, const qatvit_fq* weight_fq,
                                   const float* images, float* logits, void* workspace, int32_t stage_from, int32_t stage_to, int32_t flags,
                                   void* stream);
@@ -410,7 +426,8 @@ int qatvit_teacher_forward_f16(const qatvit_cfg* cfg, void* const* params, void*
  * Replaces: `student_out = model(images)` ... `loss.backward()` of the reference's float epochs (qat_trainer.py:295-361 before
  * prepare_qat; train_final.sh runs them in fp32, the Optuna objective under autocast + GradScaler).
  *  cfg: same struct (the quantisation fields are ignored); cfg->batch is a run-time argument - a workspace sized for batch B serves
- *  every batch <= B.  Limits: embed_dim % 128 == 0 and <= 768, head_dim 32 or 64, <= 224 tokens, depth <= 12, no dropout / drop-path.
+ *  every batch <= B.  Limits: embed_dim % 128 == 0 and <= 768, head_dim 32 or 64, <= 224 tokens, depth <= 12, no dropout, no LayerScale
+ *  (drop-path: qatvit_float_student_set_drop_path below).
  *  params / grads: fp32 tensors in the student's order above.  grads must be ZERO on entry: the backward accumulates into them.
  *  Every GEMM operand is a bf16 (hi, lo) pair, three MFMA passes per product (hi.hi + lo.hi + hi.lo), fp32 accumulate; the attention
  *  backward runs in fp32 FMA.  The forward leaves in the workspace what the backward reads (one forward per workspace at a time). */
@@ -419,6 +436,16 @@ int qatvit_float_student_init(const qatvit_cfg* cfg, void* workspace, void* stre
 int qatvit_float_student_forward(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* stream);
 int qatvit_float_student_backward(const qatvit_cfg* cfg, void* const* params, const float* dlogits, void* const* grads, void* workspace,
                                   void* stream);
+/* Stochastic depth (drop-path) for a float-step workspace of ANY of the three forms (fp32-accurate, fp16, bf16 - each has its own workspace; the observe-only
+ * forward runs on the fp32 form's): x = x + branch * s[sample].  scale_table, its indexing, the host-side binding and the contract are those of
+ * qatvit_student_set_drop_path: DEVICE float [2 * depth][batch], row 2 i = block i's attention branch, row 2 i + 1 = its MLP branch; the forward and the
+ * backward that follows read the same table at the same address; NULL, or nothing bound (the state after the form's _init), is the step without drop-path
+ * with the same launches as before.  fp32-accurate form: the product in fp32.  fp16 / bf16 forms: as stock autocast - the branch output and s are values
+ * of the 16-bit type, their product is rounded to that type, the add is fp32.  Backward: the gradient entering the branch is (d loss / d x) * s[sample],
+ * with s as the table holds it: the forward of the 16-bit forms rounds s to the type, the backward does not, so a caller that wants stock autocast's
+ * gradient (one 16-bit mask in both directions) stores multipliers that the type represents (qat_vit_amd's engine stores the table rounded).
+ * The GEMMs of a dropped sample are not skipped. */
+int qatvit_float_student_set_drop_path(const qatvit_cfg* cfg, void* workspace, const float* scale_table);
 /* Observe-only form: the PREPARED student with fake_quant_enabled = 0 on every fake-quant module (torch.ao.quantization.disable_fake_quant).  Stock
  * FusedMovingAvgObsFakeQuantize then passes every tensor through unchanged (gradient: the identity) and, where observer_enabled = 1, still moves
  * running_min / running_max by the EMA (c = cfg->averaging_const); scale / zero_point are not written.  The forward is qatvit_float_student_forward

@@ -4,6 +4,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #include "../../include/qatvit.h"
 #include "qv_common.h"
 #include "qv_kernels.h"
@@ -28,6 +31,22 @@ const Knobs& knobs() {
                          knob("QATVIT_CLS_BWD")};
     return k;
 }
+
+// The drop-path scale table bound to a step workspace (qatvit_student_set_drop_path / qatvit_float_student_set_drop_path): host state keyed by the workspace
+// address, read by every forward / backward entry on that workspace - a backward runs on autograd's worker thread, hence the lock.  The init entries of both
+// workspaces unbind (an address that is bound anew must not inherit a table).
+static std::mutex g_drop_mu;
+static std::unordered_map<const void*, const float*> g_drop;
+void drop_path_bind(const void* workspace, const float* table) {
+    std::lock_guard<std::mutex> lk(g_drop_mu);
+    if (table) g_drop[workspace] = table;
+    else g_drop.erase(workspace);
+}
+const float* drop_path_of(const void* workspace) {
+    std::lock_guard<std::mutex> lk(g_drop_mu);
+    auto it = g_drop.find(workspace);
+    return it == g_drop.end() ? nullptr : it->second;
+}
 }  // namespace qv
 
 using namespace qv;
@@ -35,6 +54,17 @@ using namespace qv;
 extern "C" {
 
 int qatvit_abi_version(void) { return QATVIT_ABI_VERSION; }
+
+int qatvit_student_set_drop_path(const qatvit_cfg* cfg, void* workspace, const float* scale_table) {
+    QV_CHECK_ARG(cfg && workspace, "qatvit_student_set_drop_path: null argument");
+    drop_path_bind(workspace, scale_table);
+    return 0;
+}
+int qatvit_float_student_set_drop_path(const qatvit_cfg* cfg, void* workspace, const float* scale_table) {
+    QV_CHECK_ARG(cfg && workspace, "qatvit_float_student_set_drop_path: null argument");
+    drop_path_bind(workspace, scale_table);
+    return 0;
+}
 const char* qatvit_last_error(void) { return qv::g_err; }
 const char* qatvit_target_arch(void) { return "gfx950"; }
 

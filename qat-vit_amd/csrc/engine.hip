@@ -86,7 +86,8 @@ struct Forms {
     bool ln_in_strip;        // norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln) where the forward writes the byte plane only (ln_in_strip_of)
     bool cls_bwd;            // the one-plane backward of the final norm and of the last block's MLP + proj on the B class-token rows (Plan::ClsRows; bwd() decides per call)
 };
-static Forms forms_of(const qatvit_cfg& c, const Dims& d) {
+// drop_path: a drop-path scale table is bound to the workspace of the call (qatvit_student_set_drop_path)
+static Forms forms_of(const qatvit_cfg& c, const Dims& d, bool drop_path) {
     const Knobs& k = knobs();
     const bool byte_codes = c.act_qmax - c.act_qmin <= 255;
     Forms f{};
@@ -101,7 +102,7 @@ static Forms forms_of(const qatvit_cfg& c, const Dims& d) {
     f.attn_codes = k.attn_codes && byte_codes;
     f.qkv_2pass = k.qkv_2pass && f.attn_codes && f.i8 && (3 * d.D) % 384 == 0 && d.D % 64 == 0 && (d.D / d.H) % 32 == 0;
     f.attn_bwd_fused = attn_bwd_is_fused(d.T, d.H, d.D, f.attn_codes);
-    f.lnb = k.lnb_fuse && d.D == 384;
+    f.lnb = k.lnb_fuse && d.D == 384 && !drop_path;   // (the fused epilogue does not know the drop-path multipliers: k_ln_bwd_fq behind the plain dgrad does)
     f.x_plane_from_q8 = f.i8 && k.tn_q8 && d.D % 384 == 0;
     f.tn_stream = k.tn_stream && d.D % 384 == 0 && d.Hd % 384 == 0;
     f.dy16 = f.i8 && f.w_batched && d.D % 384 == 0 && d.Hd % 384 == 0 && f.qkv_2pass && f.attn_bwd_fused && f.f16_proj && f.fc2w_codes;
@@ -142,10 +143,10 @@ enum { DS_FC2 = 0, DS_FC1, DS_PROJ, DS_QKV, DS_COUNT };
 
 static int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
-static int make_plan(const qatvit_cfg& c, Plan* p) {
+static int make_plan(const qatvit_cfg& c, Plan* p, bool drop_path = false) {   // (no offset depends on drop_path)
     const Dims d = dims_of(c);
     if (d.depth > 64) { set_error("engine: depth %d > 64", d.depth); return 1; }
-    p->form = forms_of(c, d);
+    p->form = forms_of(c, d, drop_path);
     int64_t o = 0;
     auto take = [&](int64_t bytes) { int64_t r = o; o += al(bytes); return r; };
     const int64_t M = d.M, D = d.D, Hd = d.Hd;
@@ -328,6 +329,9 @@ struct Ctx {
     hipStream_t st;
     std::shared_ptr<Prof> prof;
     int flags = 0;   // QATVIT_FWD_X16 (forward) / QATVIT_BWD_DY16, QATVIT_BWD_CALIBRATE (backward)
+    // drop-path: the scale table bound to the workspace ([2 * depth][batch] floats), nullptr: none.  Row of block i's attention (mlp = 0) / MLP (1) branch:
+    const float* drop = nullptr;
+    const float* drop_row(int i, int mlp) const { return drop ? drop + (int64_t)(2 * i + mlp) * d.B : nullptr; }
     // ---- the one-plane backward (dy16.hip): slot k (DS_*) of block i
     uint32_t* dy_slot(int i, int k) const { return at<uint32_t>(p.dy16) + kDyHdrWords + (int64_t)(DS_COUNT * i + k) * kDySlotWords; }
     const float* dy_mul(int i, int k) const { return reinterpret_cast<const float*>(dy_slot(i, k) + 1); }
@@ -387,11 +391,11 @@ struct Ctx {
     // launch_resid_fq_lnstats (Y = the output of quantizer ai_Y, -1: none; x_new: the rows of `next`, or nullptr where they stand already) leaves the row
     // statistics of the LayerNorm `next`, whose output quantizer is updated behind it
     int resid_lnstats(int mode, const float* x_prev, const float* Y, int ai_Y, const float* cls, const float* pos, float* x_new, const LnRows& next,
-                      void* maskbits = nullptr) const {
+                      void* maskbits = nullptr, const float* drop_scale_rows = nullptr) const {
         const bool lt = ai_Y >= 0 && late_kind(ai_Y);
         const QpLate L = lt ? late(ai_Y) : QpLate{};
         if (launch_resid_fq_lnstats(mode, x_prev, Y, act_qp(ai_Y >= 0 ? ai_Y : 0), c.act_qmin, c.act_qmax, cls, pos, x_new, next.mean, next.rstd, next.gamma, next.beta,
-                                    c.ln_eps, act_stats(next.ai), kStatSlots, d.M, d.D, d.T, st, maskbits, lt ? &L : nullptr))
+                                    c.ln_eps, act_stats(next.ai), kStatSlots, d.M, d.D, d.T, st, maskbits, lt ? &L : nullptr, drop_scale_rows))
             return 1;
         qparams_after(next.ai, true);
         return 0;
@@ -575,7 +579,7 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
         } else if (x.linear_fwd(x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), M, x.widx(i, WB_PROJ), nullptr, x.bprm(i, B_PROJB),
                                 x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ)))
             return 1;
-        if (x.resid_lnstats(1, n1.x, x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ), nullptr, nullptr, n2.x, n2, x.blk<void>(p.mproj, i))) return 1;
+        if (x.resid_lnstats(1, n1.x, x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ), nullptr, nullptr, n2.x, n2, x.blk<void>(p.mproj, i), x.drop_row(i, 0))) return 1;
     }
     if (parts & 4) {   // ---- part 2: norm2 -> fc1 (both passes) -> GELU
         if (!x.ln_in_strip(WB_FC1)) x.ln_apply(n2, x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i));   // (else norm2's apply + quantise runs inside fc1's statistics pass)
@@ -606,7 +610,7 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
             return 1;
         // residual + statistics of the NEXT LayerNorm (block i+1's norm1, or the final norm)
         const Ctx::LnRows next = x.norm1(i + 1);
-        if (x.resid_lnstats(1, n2.x, x.blk<float>(p.Y2, i), x.aidx(i, AB_FC2), nullptr, nullptr, next.x, next, x.blk<void>(p.m2, i))) return 1;
+        if (x.resid_lnstats(1, n2.x, x.blk<float>(p.Y2, i), x.aidx(i, AB_FC2), nullptr, nullptr, next.x, next, x.blk<void>(p.m2, i), x.drop_row(i, 1))) return 1;
     }
     return 0;
 }
@@ -791,8 +795,13 @@ struct Bwd {
     void calib(const Grad& g, int64_t n, int blk_i) const { if (cal) launch_absmax_bf16(g.hi, n, x.dy_slot(blk_i, g.slot), x.st); }
     // What a LayerNorm backward leaves for the branch in front of it: g = split(dx_out * mask * colscale), the gradient entering layer wi of block blk_i (maskbits: the
     // forward's STE bits of that layer's output)
-    LnBwdNext next(int blk_i, const Grad& g, const void* maskbits, int wi) const {
-        return LnBwdNext{maskbits, x.dy_colscale(wi), g.hi, g.lo, mul(blk_i, g), amax(blk_i, g)};
+    // Under drop-path that gradient also carries the multipliers of the branch layer wi closes (proj: attention, fc2: MLP), one per sample: T rows each, or - rows -
+    // one each on the compact class-token rows
+    LnBwdNext next(int blk_i, const Grad& g, const void* maskbits, int wi, bool rows = false) const {
+        LnBwdNext nx{maskbits, x.dy_colscale(wi), g.hi, g.lo, mul(blk_i, g), amax(blk_i, g)};
+        nx.drop_scale = x.drop_row(blk_i, wi == x.widx(blk_i, WB_FC2) ? 1 : 0);
+        nx.drop_rows = rows ? 1 : x.d.T;
+        return nx;
     }
     // launch_ln_bwd_fq for the LayerNorm r over M rows (dx_in: the residual gradient it adds to where acc)
     int ln_bwd(int acc, const float* dH, const Ctx::LnRows& r, const LnGrads& dr, const float* dx_in, float* dx_out, int64_t M, int T, int cls_only,
@@ -930,7 +939,7 @@ int Bwd::head(const float* dlogits) {
         t.m[3] = RowMove{m2, x.at<void>(r.m2), mrow, (int)mrow};
         if (launch_rows_gather(t, d.B, d.T, x.st)) return 1;
         nf.x = x.at<float>(r.xF); nf.mean = x.at<float>(r.meanF); nf.rstd = x.at<float>(r.rstdF);
-        const LnBwdNext nx = next(last, gy, x.at<void>(r.m2), x.widx(last, WB_FC2));
+        const LnBwdNext nx = next(last, gy, x.at<void>(r.m2), x.widx(last, WB_FC2), true);
         return ln_bwd(0, x.at<float>(p.dh), nf, dnorm1(d.depth), nullptr, x.at<float>(r.dx), d.B, 1, 0, &nx, 1);
     }
     const LnBwdNext nx = next(last, gy, m2, x.widx(last, WB_FC2));
@@ -962,8 +971,9 @@ int Bwd::block(int i, bool injected) {
     if (rows && launch_rows_gather(gather, d.B, d.T, st)) return 1;
     // ---- MLP branch
     if (injected) {
-        launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, o.gy.hi, o.gy.lo, d.M * d.D, st, mul(i, o.gy),
-                        amax(i, o.gy));
+        if (launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, o.gy.hi, o.gy.lo, d.M * d.D, st, mul(i, o.gy),
+                            amax(i, o.gy), x.drop_row(i, 1), d.T))
+            return 1;
         calib(o.gy, d.M * d.D, i);
     }
     const WX x_fc2 = dy             ? x_codes(o.G8, x.blk<uint32_t>(p.glut, i), scal16 + 1)
@@ -984,7 +994,7 @@ int Bwd::block(int i, bool injected) {
     }
     calib(o.gh, d.M * d.Hd, i);
     if (wgrad(i, o.M, o.gh, w_fc1, x_grid(o.h2q, o.h2q8, x.act_qp(o.n2.ai)), rows)) return 1;
-    if (dgrad_ln(i, true, o.n2, o.gh, o.dx, o.dxB, o.dH, next(i, o.gp, o.mproj, w_proj), o.M, rows)) return 1;
+    if (dgrad_ln(i, true, o.n2, o.gh, o.dx, o.dxB, o.dH, next(i, o.gp, o.mproj, w_proj, rows), o.M, rows)) return 1;
     // ---- attention branch (dxB = gradient w.r.t. x_mid)
     calib(o.gp, d.M * d.D, i);
     const WX x_proj = dy ? x_float(o.O16, nullptr, scal16) : x_float(x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), nullptr);
@@ -1088,6 +1098,7 @@ int qatvit_student_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
         if (it != g_profs.end()) { std::lock_guard<std::mutex> l2(it->second->mu); it->second->closed = true; }
         g_profs.erase(workspace);
     }
+    drop_path_bind(workspace, nullptr);   // ... and so does a drop-path table
     launch_ws_init(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + p.stats), p.stats_words / 2, (hipStream_t)stream);
     // the one-plane backward's scale history starts empty (the first backward on a workspace calibrates); no late-resolved quantizer state is pending
     launch_zero_i32(reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + p.dy16), dy16_state_bytes(DS_COUNT * cfg->depth) / 4, (hipStream_t)stream);
@@ -1105,7 +1116,8 @@ static int run_forward(const qatvit_cfg* cfg, void* const* params, const qatvit_
     QV_CHECK_ARG(stage_to <= cfg->depth || logits, "%s: the last stage needs the logits buffer", who);
     QV_CHECK_ARG((flags & ~(QATVIT_STAGE_INJECT | QATVIT_FWD_X16)) == 0 && !((flags & QATVIT_STAGE_INJECT) && stage_from == 0), "%s: bad flags %d", who, flags);
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
-    if (make_plan(*cfg, &x.p)) return 1;
+    x.drop = drop_path_of(workspace);
+    if (make_plan(*cfg, &x.p, x.drop != nullptr)) return 1;
     x.flags = flags & QATVIT_FWD_X16;
     QV_CHECK_ARG(!x.flags || x.p.form.dy16, "%s: QATVIT_FWD_X16 needs a configuration the one-plane backward covers (qatvit_student_dy16_supported)", who);
     if (fwd(x, images, logits, stage_from, stage_to, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
@@ -1133,7 +1145,8 @@ int qatvit_student_forward_part(const qatvit_cfg* cfg, void* const* params, cons
     QV_CHECK_ARG(block >= 0 && block < cfg->depth && part >= 0 && part <= 3 && (flags & ~(QATVIT_STAGE_INJECT | QATVIT_FWD_X16)) == 0,
                  "qatvit_student_forward_part: bad block %d / part %d / flags %d", block, part, flags);
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
-    if (make_plan(*cfg, &x.p)) return 1;
+    x.drop = drop_path_of(workspace);
+    if (make_plan(*cfg, &x.p, x.drop != nullptr)) return 1;
     x.flags = flags & QATVIT_FWD_X16;
     QV_CHECK_ARG(!x.flags || x.p.form.dy16, "qatvit_student_forward_part: QATVIT_FWD_X16 needs a configuration the one-plane backward covers");
     if (fwd_part(x, block, part, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
@@ -1151,7 +1164,8 @@ static int run_backward(const qatvit_cfg* cfg, void* const* params, const qatvit
     QV_CHECK_ARG((flags & ~(QATVIT_STAGE_INJECT | QATVIT_BWD_DY16 | QATVIT_BWD_CALIBRATE)) == 0 && !((flags & QATVIT_STAGE_INJECT) && stage_from == 0),
                  "%s: bad flags %d", who, flags);
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
-    if (make_plan(*cfg, &x.p)) return 1;
+    x.drop = drop_path_of(workspace);
+    if (make_plan(*cfg, &x.p, x.drop != nullptr)) return 1;
     x.flags = flags & (QATVIT_BWD_DY16 | QATVIT_BWD_CALIBRATE);
     if (bwd(x, dlogits, grads, stage_from, stage_to, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
     QV_CHECK_LAUNCH(who);

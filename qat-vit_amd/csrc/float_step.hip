@@ -406,6 +406,7 @@ static void fs_consts(const FsPlan& p, char* ws, hipStream_t st) {
 static int fs_init(const char* fn, FsForm form, const qatvit_cfg* cfg, void* workspace, void* stream) {
     QV_CHECK_ARG(cfg && workspace, "%s: null argument", fn);
     if (fs_check(*cfg, form)) return 1;
+    drop_path_bind(workspace, nullptr);   // (a drop-path table bound to this address belongs to whatever stood here before)
     fs_consts(fs_plan(*cfg, form), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
     QV_CHECK_LAUNCH(fn);
     return 0;
@@ -474,6 +475,9 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
     auto V = [&](int64_t off) { return off < 0 ? nullptr : reinterpret_cast<void*>(ws + off); };
     auto prm = [&](int i) { return reinterpret_cast<const float*>(params[i]); };
     auto bprm = [&](int blk, int k) { return prm(4 + 12 * blk + k); };
+    // drop-path (qatvit_float_student_set_drop_path): the per-sample multipliers of block i's attention (mlp = 0) or MLP (1) branch, nullptr without a table
+    const float* const drop = drop_path_of(workspace);
+    auto drop_row = [&](int i, int mlp) { return drop ? drop + (int64_t)(2 * i + mlp) * c.batch : nullptr; };
     // ---- the form's steps
     auto weight_planes = [&] {   // the weights' (hi, lo) pairs or fp16 / bf16 planes, as stored and transposed, in one launch
         FsWTab t{};
@@ -540,7 +544,7 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
         if (launch_attn_fwd_float(F(k.qkv), c.batch, T, c.num_heads, D, V(k.O_hi), V(k.O_lo), st, f16, F(k.lse))) return 1;
         if (gemm(k.O_hi, k.O_lo, w0 + 1, bprm(i, 5), F(p.Y), D, D, (int)M, a0 + 2)) return 1;
         launch_resid_ln_split_save(1, F(k.x), F(p.Y), nullptr, nullptr, F(k.xm), bprm(i, 6), bprm(i, 7), c.ln_eps, V(k.h2_hi), V(k.h2_lo), F(k.mean2),
-                                   F(k.rstd2), M, D, T, st, ob.act(a0 + 3), f16);
+                                   F(k.rstd2), M, D, T, st, ob.act(a0 + 3), f16, drop_row(i, 0));
         if (gemm(k.h2_hi, k.h2_lo, w0 + 2, bprm(i, 9), F(k.Y1), Hd, D, (int)M, a0 + 4)) return 1;
         gelu(k);
         if (gemm(k.G_hi, k.G_lo, w0 + 3, bprm(i, 11), F(p.Y), D, Hd, (int)M, a0 + 5)) return 1;
@@ -548,7 +552,8 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
         const FsBlock* nx = last ? nullptr : &p.blk[i + 1];
         launch_resid_ln_split_save(1, F(k.xm), F(p.Y), nullptr, nullptr, last ? F(p.x_last) : F(nx->x), last ? prm(4 + 12 * L) : bprm(i + 1, 0),
                                    last ? prm(4 + 12 * L + 1) : bprm(i + 1, 1), c.ln_eps, last ? V(p.hf_hi) : V(nx->h1_hi), last ? V(p.hf_lo) : V(nx->h1_lo),
-                                   last ? F(p.meanf) : F(nx->mean1), last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, ob.act(last ? 2 + 6 * L : a0 + 6), f16);
+                                   last ? F(p.meanf) : F(nx->mean1), last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, ob.act(last ? 2 + 6 * L : a0 + 6), f16,
+                                   drop_row(i, 1));
     }
     const int hb = 4 + 12 * L;
     head(prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3));
@@ -637,10 +642,17 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
     // the LayerNorm backward's second output: the residual gradient as the next branch's GEMM operand dp (mask all ones; the fp16 form: unit multiplier;
     // the bf16 form: no lo plane, so one bf16 plane)
     LnBwdNext next{V(p.ones), nullptr, V(p.dp_hi), V(p.dp_lo), f16 ? unit : nullptr, reinterpret_cast<uint32_t*>(V(p.amax))};
+    // drop-path (the table the forward read): dp also carries the multipliers of the branch it enters - block i's attention (mlp = 0) or MLP (1) branch
+    const float* const drop = drop_path_of(workspace);
+    auto next_of = [&](int i, int mlp) {
+        next.drop_scale = drop ? drop + (int64_t)(2 * i + mlp) * c.batch : nullptr;
+        next.drop_rows = T;
+        return &next;
+    };
     // head, then the final norm on the cls rows (dx of every other row = 0); the residual gradient leaves as fp32 (dx) and as dp
     head();
     if (launch_ln_bwd_fq(0, F(p.dhn), F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), qp_off, 0, 255, nullptr, F(p.dx), grd(hb), grd(hb + 1), M, D, T,
-                         1, st, &next))
+                         1, st, next_of(L - 1, 1)))
         return 1;
     for (int i = L - 1; i >= 0; --i) {
         const FsBlock& k = p.blk[i];
@@ -653,7 +665,7 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
         if (wgrad(p.dY1_hi, p.dY1_lo, k.h2_hi, k.h2_lo, grd(g0 + 8), grd(g0 + 9), Hd, D, (int)M)) return 1;
         if (dgrad(p.dY1_hi, p.dY1_lo, w0 + 2, F(p.dh), D, Hd)) return 1;
         if (launch_ln_bwd_fq(1, F(p.dh), F(k.xm), F(k.mean2), F(k.rstd2), prm(g0 + 6), prm(g0 + 7), qp_off, 0, 255, F(p.dx), F(p.dx2), grd(g0 + 6), grd(g0 + 7), M,
-                             D, T, 0, st, &next))
+                             D, T, 0, st, next_of(i, 0)))
             return 1;
         // proj (input O), attention, qkv (input h1 = norm1(x)); norm1 backward: dx = dx2 + LNbwd(dh1), the gradient of the block's input
         if (wgrad(p.dp_hi, p.dp_lo, k.O_hi, k.O_lo, grd(g0 + 4), grd(g0 + 5), D, D, (int)M)) return 1;
@@ -662,7 +674,7 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
         if (wgrad(p.dqkv_hi, p.dqkv_lo, k.h1_hi, k.h1_lo, grd(g0 + 2), grd(g0 + 3), 3 * D, D, (int)M)) return 1;
         if (dgrad(p.dqkv_hi, p.dqkv_lo, w0 + 0, F(p.dh), D, 3 * D)) return 1;
         if (launch_ln_bwd_fq(1, F(p.dh), F(k.x), F(k.mean1), F(k.rstd1), prm(g0 + 0), prm(g0 + 1), qp_off, 0, 255, F(p.dx2), F(p.dx), grd(g0 + 0), grd(g0 + 1), M,
-                             D, T, 0, st, i > 0 ? &next : nullptr))
+                             D, T, 0, st, i > 0 ? next_of(i - 1, 1) : nullptr))
             return 1;
     }
     // embedding, then the patch-embedding weight gradient over the saved patches

@@ -9,6 +9,9 @@ namespace qv {
 constexpr int kWave = 64;
 
 void set_error(const char* fmt, ...);
+// the drop-path scale table bound to a step workspace, nullptr: none (capi.hip; include/qatvit.h qatvit_student_set_drop_path)
+void drop_path_bind(const void* workspace, const float* table);
+const float* drop_path_of(const void* workspace);
 
 // The QATVIT_* knobs of the library, read from the environment once per process on first use (capi.hip).  Each one switches a form off for an
 // A/B or bit-identity comparison (tests/test_gpu_knobs.py); unset = on, set = atoi(value) != 0.  Which form a configuration runs is decided from

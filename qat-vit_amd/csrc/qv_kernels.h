@@ -205,12 +205,18 @@ int launch_img_patches(const float* img, void* out_bf16, const float* qp, int qm
                        void* out8 = nullptr, int center = 0);
 int launch_resid_fq_lnstats(int mode, const float* x_prev, const float* Y, const float* qpY, int qmin, int qmax, const float* cls, const float* pos,
                             float* x_new, float* mean, float* rstd, const float* gamma, const float* beta, float eps, uint32_t* stats, int stat_slots,
-                            int64_t M, int D, int T, hipStream_t st, void* maskbits = nullptr, const QpLate* late = nullptr);   // late: Y's qparams are resolved inside (QpLate)
+                            int64_t M, int D, int T, hipStream_t st, void* maskbits = nullptr, const QpLate* late = nullptr,   // late: Y's qparams are resolved inside (QpLate)
+                            const float* drop_scale_rows = nullptr);   // mode 1, optional: x_new = x_prev + fq(Y) * drop_scale_rows[row / T] (drop-path; [M / T] floats)
 // STE mask of an [M, D] tensor as wave ballots: ceil(D / 256) * 4 64-bit words per row (written by launch_resid_fq_lnstats mode 1)
 inline int64_t ln_maskbits_bytes(int64_t M, int D) { return M * ((D + 255) / 256) * 32; }
 // optional second output of launch_ln_bwd_fq: split(dx_out * mask * colscale) for the next branch's GEMMs (out_lo == nullptr without o16_*: its hi part
 // only, ONE bf16 plane)
-struct LnBwdNext { const void* maskbits; const float* colscale; void* out_hi; void* out_lo; const float* o16_mul = nullptr; uint32_t* o16_amax = nullptr; };   // o16_*: out_hi is ONE fp16 plane (dy16.hip)
+struct LnBwdNext {
+    const void* maskbits; const float* colscale; void* out_hi; void* out_lo; const float* o16_mul = nullptr; uint32_t* o16_amax = nullptr;   // o16_*: out_hi is ONE fp16 plane (dy16.hip)
+    // drop-path: that branch's per-sample multipliers, also a factor of its gradient - drop_scale[row / drop_rows], drop_rows = rows per sample (T over [B * T, D]
+    // rows, 1 over the compact class-token rows [B, D])
+    const float* drop_scale = nullptr; int drop_rows = 0;
+};
 int launch_ln_apply_quant(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp, int qmin,
                           int qmax, void* out_bf16, int64_t M, int D, hipStream_t st, void* out8 = nullptr, int center = 0,
                           bool out_f16 = false,   // out_f16: the integers as fp16 bit patterns (X operand of the one-plane weight gradient)
@@ -221,7 +227,8 @@ int launch_ln_quant8(const float* x, const float* gamma, const float* beta, floa
                      float* mean, float* rstd, int64_t nrows, int64_t row_stride, int D, hipStream_t st);
 int launch_cls_rows(const float* cls, const float* pos, float* x, int B, int T, int D, hipStream_t st);
 int launch_mask_bwd(int gelu_bwd, const float* d, const float* Y, const float* qp, int qmin, int qmax, const float* col_scale, int ncols,
-                    void* dst_hi, void* dst_lo, int64_t n, hipStream_t st, const float* o16_mul = nullptr, uint32_t* o16_amax = nullptr);
+                    void* dst_hi, void* dst_lo, int64_t n, hipStream_t st, const float* o16_mul = nullptr, uint32_t* o16_amax = nullptr,
+                    const float* drop_scale_rows = nullptr, int T = 0);   // plain mask, optional: also * drop_scale_rows[row / T] (a residual branch under drop-path)
 int launch_ln_bwd_fq(int acc, const float* dH, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                      const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T,
                      int cls_only, hipStream_t st, const LnBwdNext* next = nullptr,
@@ -314,7 +321,8 @@ int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int
 // kStatSlots {min, max} accumulator pairs that take the min / max of the fp32 LayerNorm outputs (the observe-only forward)
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
-                               uint32_t* stats = nullptr, int f16 = 0);
+                               uint32_t* stats = nullptr, int f16 = 0,
+                               const float* drop_scale_rows = nullptr);   // mode 1, optional: x = x_prev + Y * drop_scale_rows[row / T] (drop-path; [M / T] floats)
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st);   // n % 4 == 0
 // ---- float_amp.hip: the fp16 (autocast) form of the float student step, and (bf16 = true) its bf16 form: the same pieces on bf16 planes and
 // v_mfma_f32_16x16x32_bf16 (the host driver of both is float_step.hip's).  Fused attention backward on v_mfma_f32_16x16x32_f16, one workgroup per

@@ -60,88 +60,12 @@ __global__ __launch_bounds__(256) void k_patches_split(const float* __restrict__
     }
 }
 
-// MODE 0: x[b,0,:] = cls + pos[0]; x[b,1+p,:] = Y[b*np+p,:] + pos[1+p,:]     MODE 1: x = x_prev + Y
-// then h = LayerNorm(x) written as a (hi, lo) pair (one wave per row, row kept in registers: single pass over HBM)
-// NV = ceil(D / 256) column groups per lane.  All loads of the row are issued first, branch-free and pinned (pin4; a lane past D reads column 0
-// and is masked out): one `if (c < D)` region per group let LLVM sink each group's loads to its uses - three dependent HBM round trips
-// per row at D = 768.  gamma / beta once per thread.
-// STATS (the observe-only student forward): min / max of the fp32 LayerNorm outputs, one wave reduction and one accumulator atomic per wave
-// (kStatSlots pairs); the instantiations without it are the teacher's and the float step's, unchanged.  BF1: h as ONE bf16 plane (st_split4).
-template <int MODE, int NV, bool STATS = false, bool BF1 = false>
-__global__ __launch_bounds__(256) void k_resid_ln_split(const float* __restrict__ x_prev, const float* __restrict__ Y, const float* __restrict__ cls,
-                                                        const float* __restrict__ pos, float* __restrict__ x_new, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, float eps, __bf16* __restrict__ h_hi,
-                                                        __bf16* __restrict__ h_lo, int64_t M, int D, int T, int f16,
-                                                        float* __restrict__ mean_out = nullptr, float* __restrict__ rstd_out = nullptr,
-                                                        uint32_t* __restrict__ stats = nullptr) {
-    const int lane = threadIdx.x & 63;
-    float smn = INFINITY, smx = -INFINITY;
-    bool act[NV];
-    int cc[NV];
-    float4 g[NV], bb[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c = lane * 4 + 256 * j;
-        act[j] = c < D;
-        cc[j] = act[j] ? c : 0;
-        g[j] = *reinterpret_cast<const float4*>(gamma + cc[j]);
-        bb[j] = *reinterpret_cast<const float4*>(beta + cc[j]);
-    }
-    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * 4) {
-        const int t = (int)(row % T);
-        const int64_t b = row / T;
-        const float* ysrc = MODE == 0 ? (t == 0 ? cls : Y + (b * (T - 1) + (t - 1)) * D) : Y + row * D;   // (wave-uniform select)
-        const float* bsrc = MODE == 0 ? pos + (int64_t)t * D : x_prev + row * D;
-        float4 v[NV], y[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            v[j] = *reinterpret_cast<const float4*>(bsrc + cc[j]);
-            y[j] = *reinterpret_cast<const float4*>(ysrc + cc[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) { pin4(v[j]); pin4(y[j]); }
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            v[j] = make_float4(v[j].x + y[j].x, v[j].y + y[j].y, v[j].z + y[j].z, v[j].w + y[j].w);
-            if (act[j]) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-            if (act[j]) *reinterpret_cast<float4*>(x_new + row * D + cc[j]) = v[j];
-        const float mu = wave_sum(s) / (float)D;
-        float qq = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            v[j].x -= mu; v[j].y -= mu; v[j].z -= mu; v[j].w -= mu;
-            if (act[j]) qq += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
-        }
-        const float rs = rsqrtf(wave_sum(qq) / (float)D + eps);
-        if (mean_out && lane == 0) { mean_out[row] = mu; rstd_out[row] = rs; }   // (the float student step's LayerNorm backward; the teacher passes nullptr)
-        if constexpr (STATS) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                if (act[j]) {
-                    const float o0 = v[j].x * rs * g[j].x + bb[j].x, o1 = v[j].y * rs * g[j].y + bb[j].y, o2 = v[j].z * rs * g[j].z + bb[j].z,
-                                o3 = v[j].w * rs * g[j].w + bb[j].w;
-                    smn = fminf(smn, fminf(fminf(o0, o1), fminf(o2, o3)));
-                    smx = fmaxf(smx, fmaxf(fmaxf(o0, o1), fmaxf(o2, o3)));
-                    st_split4<BF1>(h_hi, h_lo, row * D + cc[j], o0, o1, o2, o3, f16);
-                }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                if (act[j])
-                    st_split4<BF1>(h_hi, h_lo, row * D + cc[j], v[j].x * rs * g[j].x + bb[j].x, v[j].y * rs * g[j].y + bb[j].y, v[j].z * rs * g[j].z + bb[j].z,
-                              v[j].w * rs * g[j].w + bb[j].w, f16);
-        }
-    }
-    if constexpr (STATS) {
-        smn = wave_min(smn);
-        smx = wave_max(smx);
-        if (lane == 0) stat_atomic(stats, kStatSlots, smn, smx);
-    }
-}
+// v rounded to the type a 16-bit form holds it in (kind 1: fp16, 2: bf16; 0: fp32, unchanged), as an fp32 value
+__device__ inline float round_as(float v, int kind) { return kind == 1 ? (float)(_Float16)v : kind == 2 ? (float)(__bf16)v : v; }
+
+#define QV_DP 0
+#include "teacher_rows.inc"
+#undef QV_DP
 template <int MODE, bool STATS = false, bool BF1 = false, typename... A>
 static void launch_resid_ln_split(int grid, hipStream_t st, int D, A... a) {
     const int nv = (D + 255) / 256;
@@ -375,11 +299,19 @@ int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int
     else k_patches_split<<<flat_grid_t(n / 4), 256, 0, st>>>(img, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), B, C, H, W, P, f16);
     return 0;
 }
+// mode 1 under drop-path (teacher_rows.inc): defined at the end of this namespace, behind the second inclusion - k_resid_ln_split_dp is instantiated after every
+// other kernel of the file, which keeps those where they stood in the object
+static int resid_ln_split_dp(const float* x_prev, const float* Y, float* x_new, const float* gamma, const float* beta, float eps, __bf16* hh, __bf16* hl, float* mean,
+                             float* rstd, int64_t M, int D, int T, hipStream_t st, uint32_t* stats, int f16, const float* dps);
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
-                               uint32_t* stats, int f16) {
+                               uint32_t* stats, int f16, const float* drop_scale_rows) {
     __bf16* hh = reinterpret_cast<__bf16*>(h_hi);
     __bf16* hl = reinterpret_cast<__bf16*>(h_lo);
+    if (drop_scale_rows) {
+        if (mode != 1) { set_error("resid_ln_split: drop-path multipliers belong to a residual branch (mode 1)"); return 1; }
+        return resid_ln_split_dp(x_prev, Y, x_new, gamma, beta, eps, hh, hl, mean, rstd, M, D, T, st, stats, f16, drop_scale_rows);
+    }
     if (stats) {
         if (mode == 0) launch_resid_ln_split<0, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats);
         else launch_resid_ln_split<1, true>(rows_grid_t(M), st, D, x_prev, Y, cls, pos, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats);
@@ -396,6 +328,26 @@ int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, co
 }
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st) {
     k_gelu_split<<<flat_grid_t(n / 4), 256, 0, st>>>(Y, reinterpret_cast<__bf16*>(hi), reinterpret_cast<__bf16*>(lo), n / 4);
+    return 0;
+}
+
+// ---------------------------------------------------------------- the residual + LayerNorm row kernel under drop-path (k_resid_ln_split_dp) and its launch
+#define QV_DP 1
+#include "teacher_rows.inc"
+#undef QV_DP
+// (the output forms of launch_resid_ln_split_save: the pair with the observe-only statistics, one bf16 plane, the pair or one fp16 plane)
+static int resid_ln_split_dp(const float* x_prev, const float* Y, float* x_new, const float* gamma, const float* beta, float eps, __bf16* hh, __bf16* hl, float* mean,
+                             float* rstd, int64_t M, int D, int T, hipStream_t st, uint32_t* stats, int f16, const float* dps) {
+    const int grid = rows_grid_t(M), nv = (D + 255) / 256;
+    const float* const none = nullptr;
+#define QV_RESID_DP(NV_)                                                                                                                                    \
+    do {                                                                                                                                                    \
+        if (stats) k_resid_ln_split_dp<1, NV_, true><<<grid, 256, 0, st>>>(x_prev, Y, none, none, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats, dps); \
+        else if (!f16 && !hl) k_resid_ln_split_dp<1, NV_, false, true><<<grid, 256, 0, st>>>(x_prev, Y, none, none, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, nullptr, dps); \
+        else k_resid_ln_split_dp<1, NV_><<<grid, 256, 0, st>>>(x_prev, Y, none, none, x_new, gamma, beta, eps, hh, hl, M, D, T, f16, mean, rstd, nullptr, dps); \
+    } while (0)
+    if (nv == 1) QV_RESID_DP(1); else if (nv == 2) QV_RESID_DP(2); else QV_RESID_DP(3);
+#undef QV_RESID_DP
     return 0;
 }
 

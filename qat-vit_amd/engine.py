@@ -463,6 +463,8 @@ class StudentEngine:
         self.dy16 = dy16_default() and bool(self.lib.qatvit_student_dy16_supported(ctypes.byref(self.cfg)))
         self.overflow = OverflowProtocol()
         self.dy16_overflowed = self.overflow.overflowed
+        # stochastic depth: the per-sample multipliers of a training-mode step (the QAT step's and the observe-only step's alike)
+        self.drop = native.DropPathTable(m, dev)
         self._reserve(batch)
         # ---- flat gradient buffer, laid out in backward-stage order so that finished buckets are contiguous
         self.layout = FlatGradLayout([p.numel() for p in ps], self.cfg.depth)
@@ -588,6 +590,8 @@ class StudentEngine:
         # a training forward of a calibrated engine leaves the X operands of the qkv / fc1 weight gradients as fp16 integers: its backward is one-plane
         x16 = self.dy16 and self.overflow.calibrated and training
         flags = FWD_X16 if x16 else 0
+        # drop-path (module in training mode): filled here, read by this forward and by its backward - the binding stays until the next forward
+        self.drop.bind("qatvit_student_set_drop_path", c, self.workspace, self.drop.step(c.batch, self.capacity, self.frozen))
         self.last_step = Step(c, self.generation + 1, x16, mode, int(self.lib.qatvit_student_ln_in_strip(ctypes.byref(c), flags)))
         native.check(self.lib.qatvit_student_forward_stages(ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, images.data_ptr(),
                                                             logits.data_ptr(), self.workspace.data_ptr(), 0, c.depth + 1, flags, native.stream_ptr()),
@@ -617,6 +621,7 @@ class StudentEngine:
             broadcast_fq_state(self.fq_arena, self.pg)
         images = images.contiguous()
         logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
+        self.drop.bind("qatvit_float_student_set_drop_path", c, self.float_form.workspace, self.drop.step(c.batch, max(self.capacity, self.float_form.capacity), self.frozen))
         self.last_step = Step(c, self.generation + 1, False, OBSERVE, 0)
         native.check(self.lib.qatvit_float_student_forward_observe(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
                                                                    self.float_form.workspace.data_ptr(), self.observe_buf.data_ptr(), native.stream_ptr()),

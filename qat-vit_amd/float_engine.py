@@ -30,7 +30,7 @@ _OPTED = weakref.WeakKeyDictionary()   # wrapper -> FloatStudentEngine (or None 
 
 def check_shape(model: nn.Module, amp=False) -> None:
     """Raise unless the native float step covers this tree (the QAT engine's limits; amp: also the fp16 / bf16 forms')."""
-    from .vit import VisionTransformer
+    from .vit import DropPath, VisionTransformer
 
     if not isinstance(model, VisionTransformer):
         raise RuntimeError(f"native float step: expected the ViT student tree, got {type(model).__name__}")
@@ -61,8 +61,12 @@ def check_shape(model: nn.Module, amp=False) -> None:
             why.append("dropout != 0")
             break
     for b in model.blocks:
-        if not all(isinstance(getattr(b, n), nn.Identity) for n in ("ls1", "ls2", "drop_path1", "drop_path2")):
-            why.append("layer scale / drop-path")
+        if not all(isinstance(getattr(b, n), nn.Identity) for n in ("ls1", "ls2")):
+            why.append("layer scale")
+            break
+    for b in model.blocks:   # stochastic depth: this package's DropPath (its multipliers travel to the residual kernels), or none
+        if not all(isinstance(getattr(b, n), (nn.Identity, DropPath)) for n in ("drop_path1", "drop_path2")):
+            why.append("drop_path1 / drop_path2 are neither Identity nor qat_vit_amd.DropPath")
             break
     hidden = model.blocks[0].mlp.fc1.weight.shape[0] if depth else 0
     if amp and (D % 384 or hidden % 384):
@@ -139,6 +143,7 @@ class FloatStudentEngine:
         self.generation = 0         # bumped by every forward of any form: the workspaces hold the activations of exactly one forward
         self.grad_numel = sum(p.numel() for p in self.params)
         self._grad_offsets = [sum(p.numel() for p in self.params[:i]) for i in range(len(self.params))]   # dense, in parameter order
+        self.drop = native.DropPathTable(model, dev)   # stochastic depth: the per-sample multipliers of a training-mode step, one buffer for all three forms
 
     def cfg_for(self, batch: int) -> native.Cfg:
         return native.Cfg(batch=batch, **self._cfg_kw)
@@ -172,6 +177,8 @@ class FloatStudentEngine:
         form = form or self.fp32
         c = self.cfg_for(images.shape[0])
         form.reserve(c, self.device)
+        # drop-path: filled here, read by this forward and by its backward (the binding stays until the next forward of this form)
+        self.drop.bind("qatvit_float_student_set_drop_path", c, form.workspace, self.drop.step(c.batch, form.capacity, round_to=None if form is self.fp32 else form.dtype))
         logits = torch.empty(c.batch, c.num_classes, dtype=form.dtype, device=self.device)
         self.generation += 1
         form.call("forward", ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr())

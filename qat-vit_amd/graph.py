@@ -58,6 +58,9 @@ class GraphedStudentStep:
             self.graph = None
             self.engine = None
             raise
+        # stochastic depth: the captured kernels read the engine's static drop-path table; the capture itself drew nothing (a draw inside the graph would be
+        # replayed as the same launch, and a forced table is the caller's to change) - __call__ refills the table before every replay
+        self._drop_path = eng.drop.active()
         self._grads = [p.grad for p in model.parameters()]   # from here on the pin lasts as long as this object (close() / __del__ release it)
         self.step = eng.last_step                  # the record of the captured forward; x16: its backward is the one-plane form, whose overflow flag is read after every replay
 
@@ -103,6 +106,12 @@ class GraphedStudentStep:
             self.t.copy_(teacher_out)
         for p, g in zip(self.model.parameters(), self._grads):   # zero_grad(set_to_none=True) in the loop must not drop the static buffers
             p.grad = g
+        if self._drop_path:   # this step's masks: a fresh draw, or the table of the forced_drop_path context the call is in
+            drop = self.engine.drop
+            drop.refill(self.x.shape[0])
+            # The captured kernels carry the table's address; the eager repeat of an overflowed backward below reads the workspace's binding instead, which
+            # an evaluation forward since the capture has removed: bind again what the replay reads
+            drop.bind("qatvit_student_set_drop_path", self.step.cfg, self.engine.workspace, drop.view(self.x.shape[0]))
         self.graph.replay()
         if self.step.x16 and self.engine.overflow.resolve(replayed=True):
             # a gradient outgrew its fp16 plane (engine.backward asks this itself in eager mode; a capture cannot): the backward again, eagerly, in the

@@ -76,6 +76,8 @@ SIGNATURES = {
     "qatvit_student_ln_in_strip": (c_int32, [c_void_p, c_int32]),
     "qatvit_student_dy16_to_pair": (c_int, [c_void_p, c_void_p, c_void_p]),
     "qatvit_student_dy16_set_mirror": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "qatvit_student_set_drop_path": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "qatvit_float_student_set_drop_path": (c_int, [c_void_p, c_void_p, c_void_p]),
     "qatvit_teacher_workspace_bytes": (c_int64, [c_void_p]),
     "qatvit_teacher_forward": (c_int, [c_void_p] * 8),
     "qatvit_teacher_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -208,6 +210,97 @@ def check_generation(engine, generation: int) -> None:
             "saved activations of ONE forward per model. Call backward() before the next forward (gradient accumulation: "
             "forward/backward per micro-batch)."
         )
+
+
+class DropPathTable:
+    """The drop-path scale table of one engine (include/qatvit.h, qatvit_student_set_drop_path): ONE static fp32 buffer per capacity, so the address a
+    workspace is bound to - and a captured hipGraph replays - is the same every step; the step at batch B uses its front as [2 * depth, B].
+
+    ``step(batch, capacity)``: the table of the forward about to run, or None when that forward has no drop-path (eval mode, or a tree without
+    stochastic depth outside ``forced_drop_path``).  Filled here: the caller's table inside ``forced_drop_path``, else ONE draw for the whole step -
+    ``bernoulli`` over [2 * depth, B] with each branch's keep probability, times its 1 / keep - on the device, without a synchronisation.  The draw has
+    the modules' distribution but does not consume the generator as their 2 * depth separate calls would.  While the stream is being captured nothing is
+    filled: the owner of the graph refills before every replay (``refill``)."""
+
+    def __init__(self, model, device):
+        self.model, self.device = model, device
+        self.rows = 2 * len(model.blocks)
+        self.plan = self.keep = self.mult = None   # the modules' rates as last read, and their device copies
+        self.round_to = None                       # the 16-bit type of the float form the table was last filled for (None: fp32 as given)
+        self.buf = None
+        self.capacity = 0
+        self.bound = set()   # addresses of the workspaces a table was handed to (those a forward without a table has to unbind)
+        self.read_plan()
+
+    def read_plan(self) -> None:
+        """The modules' rates are read before every step (a drop-path schedule changes ``drop_prob`` between epochs): host work, and a host-to-device
+        copy only when a rate moved."""
+        import torch
+        from .vit import drop_path_plan
+
+        plan = drop_path_plan(self.model)
+        if plan == self.plan:
+            return
+        self.plan = plan
+        self.keep = self.mult = None
+        if plan is not None:
+            self.keep = torch.tensor(plan[0], dtype=torch.float32, device=self.device).view(-1, 1)
+            self.mult = torch.tensor(plan[1], dtype=torch.float32, device=self.device).view(-1, 1)
+
+    def active(self) -> bool:
+        from .vit import forced_table
+
+        if not self.model.training:
+            return False
+        self.read_plan()
+        return self.plan is not None or forced_table(self.model) is not None
+
+    def view(self, batch: int):
+        return self.buf[:self.rows * batch].view(self.rows, batch)
+
+    def refill(self, batch: int) -> None:
+        import torch
+        from .vit import forced_table
+
+        t, forced = self.view(batch), forced_table(self.model)
+        if forced is not None:
+            if tuple(forced.shape) != (self.rows, batch):
+                raise RuntimeError(f"forced_drop_path: the table is {tuple(forced.shape)}, this step needs [{self.rows}, {batch}]")
+            t.copy_(forced)
+        elif self.keep is not None:
+            torch.bernoulli(self.keep.expand(self.rows, batch), out=t)
+            t.mul_(self.mult)
+        else:
+            t.fill_(1.0)
+        if self.round_to is not None:   # stock autocast holds the mask in the 16-bit type, forward and backward alike: the table holds those values
+            t.copy_(t.to(self.round_to))
+
+    def step(self, batch: int, capacity: int, frozen: bool = False, round_to=None):
+        """round_to: torch.float16 / torch.bfloat16 for the float step's 16-bit forms - the multipliers are stored rounded to that type."""
+        import torch
+
+        if not self.active():
+            return None
+        self.round_to = round_to
+        if max(batch, capacity) > self.capacity:
+            if frozen and self.buf is not None:
+                raise RuntimeError(f"batch {batch} exceeds the drop-path table ({self.capacity}) a captured hipGraph is bound to")
+            self.capacity = max(batch, capacity)
+            self.buf = torch.ones(self.rows * self.capacity, dtype=torch.float32, device=self.device)
+        if not torch.cuda.is_current_stream_capturing():
+            self.refill(batch)
+        return self.view(batch)
+
+    def bind(self, setter: str, cfg, workspace, table) -> None:
+        """Hand `table` (None: no drop-path) to the library for the calls on `workspace` that follow; a workspace that never saw a table is never touched."""
+        ws = workspace.data_ptr()
+        if table is None and ws not in self.bound:
+            return
+        check(getattr(lib(), setter)(ctypes.byref(cfg), ws, table.data_ptr() if table is not None else None), setter)
+        if table is None:
+            self.bound.discard(ws)
+        else:
+            self.bound.add(ws)
 
 
 def assign_grads(params, grads) -> None:

@@ -12,6 +12,10 @@ these modules' ``forward``.
 """
 from __future__ import annotations
 
+import contextlib
+import weakref
+from typing import Optional
+
 import torch
 import torch.nn as nn
 
@@ -69,15 +73,52 @@ class Mlp(nn.Module):
         return self.drop2(self.fc2(self.norm(self.drop1(self.act(self.fc1(x))))))
 
 
+class DropPath(nn.Module):
+    """Stochastic depth per sample, on the branch of a residual block - timm's ``DropPath`` (timm/layers/drop.py): in eval mode or with
+    ``drop_prob == 0`` the identity, otherwise ``x * m`` with ``m = x.new_empty(B, 1, .., 1).bernoulli_(keep)``, divided by ``keep`` when
+    ``keep > 0 and scale_by_keep``.  No parameters, no buffers; ``prepare_qat`` leaves it where it is and gives it no observer.
+
+    Inside ``forced_drop_path`` a training-mode forward multiplies by the caller's per-sample multipliers instead of drawing (whatever
+    ``drop_prob`` is).  On an MI355X the native steps (engine.py, float_engine.py) apply the multipliers in their residual kernels; this
+    ``forward`` is the stock path."""
+
+    def __init__(self, drop_prob: float = 0.0, scale_by_keep: bool = True):
+        super().__init__()
+        self.drop_prob, self.scale_by_keep = float(drop_prob), bool(scale_by_keep)
+        self._forced = None   # forced_drop_path: this branch's [B] multipliers
+
+    def forward(self, x):
+        if not self.training:
+            return x
+        shape = (x.shape[0],) + (1,) * (x.dim() - 1)
+        if self._forced is not None:
+            if self._forced.numel() != x.shape[0]:
+                raise RuntimeError(f"forced_drop_path: the table holds {self._forced.numel()} samples, the batch {x.shape[0]}")
+            return x * self._forced.to(device=x.device, dtype=x.dtype).view(shape)
+        if self.drop_prob == 0.0:
+            return x
+        keep = 1.0 - self.drop_prob
+        m = x.new_empty(shape).bernoulli_(keep)
+        if keep > 0.0 and self.scale_by_keep:
+            m.div_(keep)
+        return x * m
+
+    def extra_repr(self):
+        return f"drop_prob={round(self.drop_prob, 3):0.3f}"
+
+
 class Block(nn.Module):
-    def __init__(self, dim: int, num_heads: int, mlp_ratio: float):
+    def __init__(self, dim: int, num_heads: int, mlp_ratio: float, drop_path: Optional[float] = None):
+        """drop_path: None - no stochastic depth in this model (``nn.Identity``, the tree as it always was); a rate - ``DropPath(rate)`` on
+        both branches (also for the rate 0.0 of the first block, where timm puts an Identity: it is one in effect, and every branch of the
+        model then follows a ``forced_drop_path`` table)."""
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
         self.attn = Attention(dim, num_heads)
-        self.ls1, self.drop_path1 = nn.Identity(), nn.Identity()
+        self.ls1, self.drop_path1 = nn.Identity(), nn.Identity() if drop_path is None else DropPath(drop_path)
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
         self.mlp = Mlp(dim, int(dim * mlp_ratio))
-        self.ls2, self.drop_path2 = nn.Identity(), nn.Identity()
+        self.ls2, self.drop_path2 = nn.Identity(), nn.Identity() if drop_path is None else DropPath(drop_path)
 
     def forward(self, x):
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
@@ -88,7 +129,9 @@ class VisionTransformer(nn.Module):
     """``global_pool='token'``, ``class_token=True``, no dist token, ``fc_norm`` identity."""
 
     def __init__(self, embed_dim=384, depth=12, num_heads=6, num_classes=10, img_size=224, patch_size=16,
-                 in_chans=3, mlp_ratio=4.0):
+                 in_chans=3, mlp_ratio=4.0, drop_path_rate=0.0):
+        """drop_path_rate: stochastic depth by timm's linear rule - block i drops each of its two branches with probability
+        ``torch.linspace(0, drop_path_rate, depth)[i]``; 0 builds the tree without any ``DropPath`` module."""
         super().__init__()
         self.embed_dim = self.num_features = embed_dim
         self.num_classes, self.depth, self.num_heads = num_classes, depth, num_heads
@@ -97,7 +140,10 @@ class VisionTransformer(nn.Module):
         self.pos_embed = nn.Parameter(torch.randn(1, self.patch_embed.num_patches + 1, embed_dim) * 0.02)
         self.pos_drop = nn.Dropout(0.0)
         self.norm_pre = nn.Identity()
-        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio) for _ in range(depth)])
+        if not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate {drop_path_rate}: expected a probability in [0, 1)")
+        rates = [r.item() for r in torch.linspace(0, drop_path_rate, depth)] if drop_path_rate > 0 else [None] * depth
+        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio, rates[i]) for i in range(depth)])
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
         self.fc_norm = nn.Identity()
         self.head_drop = nn.Dropout(0.0)
@@ -137,6 +183,64 @@ def _native_teacher_ok(m: "VisionTransformer") -> bool:
 
 def x_dtype_ok(m) -> bool:
     return m.cls_token.dtype == torch.float32
+
+
+def _vit_of(wrapper) -> "VisionTransformer":
+    m = wrapper if isinstance(wrapper, VisionTransformer) else getattr(wrapper, "model", None)
+    if not isinstance(m, VisionTransformer):
+        raise TypeError(f"expected a VisionTransformer or a QATWrapper around one, got {type(wrapper).__name__}")
+    return m
+
+
+def drop_path_branches(model: "VisionTransformer") -> list:
+    """The 2 * depth branch modules in table order: row 2 i = block i's ``drop_path1`` (attention), row 2 i + 1 = its ``drop_path2`` (MLP)."""
+    return [m for b in model.blocks for m in (b.drop_path1, b.drop_path2)]
+
+
+def drop_path_plan(model: "VisionTransformer"):
+    """None for a tree without stochastic depth (no ``DropPath`` with a rate > 0); else per branch (keep probability, multiplier of a kept
+    sample) - what one draw of the whole [2 * depth, B] table needs."""
+    br = drop_path_branches(model)
+    if not any(isinstance(m, DropPath) and m.drop_prob > 0.0 for m in br):
+        return None
+    keep = [1.0 - m.drop_prob if isinstance(m, DropPath) else 1.0 for m in br]
+    mult = [1.0 / k if (isinstance(m, DropPath) and m.scale_by_keep and k > 0.0) else 1.0 for m, k in zip(br, keep)]
+    return keep, mult
+
+
+_FORCED = weakref.WeakKeyDictionary()   # VisionTransformer -> the table of the forced_drop_path context it is in
+
+
+def forced_table(model: "VisionTransformer") -> Optional[torch.Tensor]:
+    """The [2 * depth, B] table of the ``forced_drop_path`` context this model is in, or None."""
+    return _FORCED.get(model)
+
+
+@contextlib.contextmanager
+def forced_drop_path(wrapper, table: torch.Tensor):
+    """Inside the context every training-mode forward of ``wrapper`` (a ``QATWrapper`` or its ``VisionTransformer``) - the stock module
+    forward, the native QAT step and the native float step alike - uses ``table`` instead of drawing its drop-path masks.
+
+    ``table``: fp32 ``[2 * depth, B]``; row ``2 i`` multiplies block ``i``'s attention branch, row ``2 i + 1`` its MLP branch, per sample.
+    Any finite multipliers (a draw holds 0 and ``1 / keep``).  The model must have been built with ``drop_path_rate > 0`` (every branch then
+    is a ``DropPath``).  For tests, and for a caller that owns its masks the way the augmentation records own theirs."""
+    model = _vit_of(wrapper)
+    br = drop_path_branches(model)
+    if not all(isinstance(m, DropPath) for m in br):
+        raise ValueError("forced_drop_path: the model has no DropPath modules (build it with drop_path_rate > 0)")
+    if table.dim() != 2 or table.shape[0] != len(br) or table.dtype != torch.float32:
+        raise ValueError(f"forced_drop_path: expected an fp32 table of shape [{len(br)}, B], got {tuple(table.shape)} {table.dtype}")
+    if model in _FORCED:
+        raise RuntimeError("forced_drop_path: already inside a forced_drop_path context of this model")
+    _FORCED[model] = table
+    for m, row in zip(br, table):
+        m._forced = row
+    try:
+        yield table
+    finally:
+        del _FORCED[model]
+        for m in br:
+            m._forced = None
 
 
 def create_vit(name: str, pretrained: bool = False, num_classes: int = 10, **kwargs) -> VisionTransformer:
