@@ -385,6 +385,22 @@ int qatvit_student_dy16_to_pair(const qatvit_cfg* cfg, void* workspace, void* st
  * Two limits.  With a table bound, the LayerNorm backward runs as its own kernel behind the plain fc1 / qkv dgrad, not in the dgrad's epilogue (that epilogue
  * does not know the multipliers).  The GEMMs of a dropped sample (s = 0) are not skipped: it costs what a kept one costs, as in stock torch. */
 int qatvit_student_set_drop_path(const qatvit_cfg* cfg, void* workspace, const float* scale_table);
+/* LayerScale (timm's init_values): a learnable per-channel gamma on each residual branch, x = x + (fq(branch) * gamma[c]) * s[sample] - behind the activation
+ * fake-quant of the proj / fc2 output and in front of DropPath, where the LayerScale module stands in the prepared tree (it has no observer).
+ *  gammas: HOST array of 2 * depth DEVICE pointers to fp32 gamma[embed_dim]; entry 2 i = block i's attention branch (ls1), 2 i + 1 = its MLP branch (ls2).
+ *  grads: HOST array of 2 * depth DEVICE pointers to fp32 [embed_dim] gradient buffers, ZERO on entry of a backward and accumulated into, as `grads` of the
+ *  backward entries; NULL for a binding that serves forwards only (a backward on it is refused).  Both arrays are copied.  gammas == NULL unbinds.
+ * The parameter order of params / grads (8 + 12 * depth) does not change: the gammas travel through this binding alone.
+ * Host-side binding keyed by the workspace address, with the rules of qatvit_student_set_drop_path: every forward / backward / staged / part entry reads the
+ * binding of the time of the call; nothing bound - the state after qatvit_student_init, which unbinds - is the step without LayerScale with the same launches.
+ * Arithmetic.  Forward: each product and the sum are rounded separately (no fused multiply-add); without a drop-path table there is no "* s".  gamma == 1
+ * everywhere therefore gives the bits of the step without LayerScale.  Backward: the gradient entering the branch is (d loss / d x) * STE mask * s * gamma[c], in
+ * the pair form, the one-plane form (recorded maxima: of the scaled value) and on the class-token rows of the last block; gamma's own gradient is
+ * sum over rows of (d loss / d x)[row, c] * s[sample] * fq(branch)[row, c] WITHOUT the STE mask (d (fq(Y) * g) / dg = fq(Y) whether or not Y clamped): the
+ * LayerNorm-backward kernel reads the block's pre-FQ proj / fc2 output again and re-applies that quantizer.  gamma == 0 is fine: nothing divides by gamma.
+ * Limit: with a binding the LayerNorm backward runs as its own kernel behind the plain fc1 / qkv dgrad, as under drop-path (the fused epilogue does not know
+ * gamma). */
+int qatvit_student_set_layer_scale(const qatvit_cfg* cfg, void* workspace, const float* const* gammas, float* const* grads);
 int qatvit_student_forward_stages(const qatvit_cfg* cfg, void* const* params, const qatvit_fq* act_fq, const qatvit_fq* weight_fq,
                                   const float* images, float* logits, void* workspace, int32_t stage_from, int32_t stage_to, int32_t flags,
                                   void* stream);
@@ -426,8 +442,8 @@ int qatvit_teacher_forward_f16(const qatvit_cfg* cfg, void* const* params, void*
  * Replaces: `student_out = model(images)` ... `loss.backward()` of the reference's float epochs (qat_trainer.py:295-361 before
  * prepare_qat; train_final.sh runs them in fp32, the Optuna objective under autocast + GradScaler).
  *  cfg: same struct (the quantisation fields are ignored); cfg->batch is a run-time argument - a workspace sized for batch B serves
- *  every batch <= B.  Limits: embed_dim % 128 == 0 and <= 768, head_dim 32 or 64, <= 224 tokens, depth <= 12, no dropout, no LayerScale
- *  (drop-path: qatvit_float_student_set_drop_path below).
+ *  every batch <= B.  Limits: embed_dim % 128 == 0 and <= 768, head_dim 32 or 64, <= 224 tokens, depth <= 12, no dropout
+ *  (drop-path: qatvit_float_student_set_drop_path, LayerScale: qatvit_float_student_set_layer_scale, both below).
  *  params / grads: fp32 tensors in the student's order above.  grads must be ZERO on entry: the backward accumulates into them.
  *  Every GEMM operand is a bf16 (hi, lo) pair, three MFMA passes per product (hi.hi + lo.hi + hi.lo), fp32 accumulate; the attention
  *  backward runs in fp32 FMA.  The forward leaves in the workspace what the backward reads (one forward per workspace at a time). */
@@ -446,6 +462,23 @@ int qatvit_float_student_backward(const qatvit_cfg* cfg, void* const* params, co
  * gradient (one 16-bit mask in both directions) stores multipliers that the type represents (qat_vit_amd's engine stores the table rounded).
  * The GEMMs of a dropped sample are not skipped. */
 int qatvit_float_student_set_drop_path(const qatvit_cfg* cfg, void* workspace, const float* scale_table);
+/* LayerScale for a float-step workspace of ANY of the three forms: x = x + (B * gamma[c]) * s[sample].  gammas / grads, their indexing, the host-side binding and
+ * its rules are those of qatvit_student_set_layer_scale.
+ *  saved: DEVICE buffer of qatvit_float_student_layer_scale_bytes(cfg) bytes (cfg->batch = the largest batch of the calls that follow): fp32
+ *  [2 * depth][batch * tokens, embed_dim], and 256 bytes of per-branch scales behind them (the fp16 form's backward, below).  The float forms keep ONE shared branch-output tensor, not one per block; with a binding each forward writes every
+ *  branch output to its own rows of `saved` instead, and the backward reads them for gamma's gradient.  Required with grads; NULL serves forwards only.  No
+ *  existing workspace changes its size.
+ * fp32-accurate form: B = the branch output, every product and the sum rounded separately in fp32.  fp16 / bf16 forms: as stock autocast - B is the branch output
+ * rounded to the 16-bit type, gamma is an fp32 parameter, so type promotion makes B * gamma an fp32 tensor and DropPath multiplies it in fp32:
+ * x = x + fl32(fl32(B * gamma) * s) with NEITHER the product NOR s rounded to the 16-bit type (without LayerScale the drop-path kernel rounds both: a caller that
+ * binds both binds the table unrounded).  Backward: the gradient entering the branch is (d loss / d x) * s * gamma[c]; gamma's gradient is
+ * sum over rows of (d loss / d x)[row, c] * s[sample] * B[row, c].
+ * fp16 form: stock autocast holds every gradient inside a branch in fp16, each carrying the branch's gamma - at gamma = 1e-5 in or under fp16's subnormal range.
+ * The backward carries them multiplied by K = 2^-e (max |gamma| = m * 2^e, m in [0.5, 1); clamped to [1, 2^24], so K = 1 for max |gamma| >= 0.5), computed on the
+ * device per branch and step, and undoes K exactly in the weight gradients and in the dgrad that leaves the branch: more digits than stock autocast for small
+ * gammas, the same arithmetic otherwise.  The overflow rule of the fp16 weight / bias gradients applies to the unscaled values, as before. */
+int qatvit_float_student_set_layer_scale(const qatvit_cfg* cfg, void* workspace, const float* const* gammas, float* const* grads, void* saved);
+int64_t qatvit_float_student_layer_scale_bytes(const qatvit_cfg* cfg);
 /* Observe-only form: the PREPARED student with fake_quant_enabled = 0 on every fake-quant module (torch.ao.quantization.disable_fake_quant).  Stock
  * FusedMovingAvgObsFakeQuantize then passes every tensor through unchanged (gradient: the identity) and, where observer_enabled = 1, still moves
  * running_min / running_max by the EMA (c = cfg->averaging_const); scale / zero_point are not written.  The forward is qatvit_float_student_forward

@@ -47,6 +47,37 @@ const float* drop_path_of(const void* workspace) {
     auto it = g_drop.find(workspace);
     return it == g_drop.end() ? nullptr : it->second;
 }
+// The LayerScale binding of a step workspace (qatvit_student_set_layer_scale / qatvit_float_student_set_layer_scale): as the drop-path table, host state keyed by
+// the workspace address under the same lock; the pointer lists are copied, a call holds its own reference while it runs
+static std::unordered_map<const void*, std::shared_ptr<const LayerScale>> g_ls;
+void layer_scale_bind(const void* workspace, int branches, const float* const* gammas, float* const* grads, void* saved) {
+    std::shared_ptr<LayerScale> b;
+    if (gammas) {
+        b = std::make_shared<LayerScale>();
+        b->gamma.assign(gammas, gammas + branches);
+        if (grads) b->grad.assign(grads, grads + branches);
+        b->saved = reinterpret_cast<float*>(saved);
+    }
+    std::lock_guard<std::mutex> lk(g_drop_mu);
+    if (b) g_ls[workspace] = b;
+    else g_ls.erase(workspace);
+}
+std::shared_ptr<const LayerScale> layer_scale_of(const void* workspace) {
+    std::lock_guard<std::mutex> lk(g_drop_mu);
+    auto it = g_ls.find(workspace);
+    return it == g_ls.end() ? nullptr : it->second;
+}
+static int layer_scale_set(const char* fn, const qatvit_cfg* cfg, void* workspace, const float* const* gammas, float* const* grads, void* saved, bool need_saved) {
+    if (!cfg || !workspace) { set_error("%s: null argument", fn); return 1; }
+    if (gammas) {
+        if (cfg->depth < 1 || cfg->embed_dim % 4 != 0) { set_error("%s: depth %d, embed_dim %d", fn, cfg->depth, cfg->embed_dim); return 1; }
+        for (int k = 0; k < 2 * cfg->depth; ++k)
+            if (!gammas[k] || (grads && !grads[k])) { set_error("%s: branch %d has a null gamma or gradient", fn, k); return 1; }
+        if (need_saved && grads && !saved) { set_error("%s: a binding with gradients needs the saved-branch buffer (qatvit_float_student_layer_scale_bytes)", fn); return 1; }
+    }
+    layer_scale_bind(workspace, gammas ? 2 * cfg->depth : 0, gammas, grads, saved);
+    return 0;
+}
 }  // namespace qv
 
 using namespace qv;
@@ -64,6 +95,18 @@ int qatvit_float_student_set_drop_path(const qatvit_cfg* cfg, void* workspace, c
     QV_CHECK_ARG(cfg && workspace, "qatvit_float_student_set_drop_path: null argument");
     drop_path_bind(workspace, scale_table);
     return 0;
+}
+int qatvit_student_set_layer_scale(const qatvit_cfg* cfg, void* workspace, const float* const* gammas, float* const* grads) {
+    return layer_scale_set("qatvit_student_set_layer_scale", cfg, workspace, gammas, grads, nullptr, false);
+}
+int qatvit_float_student_set_layer_scale(const qatvit_cfg* cfg, void* workspace, const float* const* gammas, float* const* grads, void* saved) {
+    return layer_scale_set("qatvit_float_student_set_layer_scale", cfg, workspace, gammas, grads, saved, true);
+}
+int64_t qatvit_float_student_layer_scale_bytes(const qatvit_cfg* cfg) {
+    if (!cfg || cfg->depth < 1 || cfg->batch < 1) return -1;
+    const int64_t np = (int64_t)(cfg->img_size / cfg->patch_size) * (cfg->img_size / cfg->patch_size);
+    // fp32 [2 * depth][batch * tokens, embed_dim], then [2 * depth] {K, 1 / K}: the fp16 form's per-branch gradient scales (float_step.hip)
+    return 2 * (int64_t)cfg->depth * cfg->batch * (np + 1) * cfg->embed_dim * 4 + 256;
 }
 const char* qatvit_last_error(void) { return qv::g_err; }
 const char* qatvit_target_arch(void) { return "gfx950"; }

@@ -435,13 +435,26 @@ static int ln_bwd_fq_dp(int acc, int grid, const float* dH, const float* x, cons
                         const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T, int cls_only,
                         hipStream_t st, const unsigned long long* nm, const float* ncs, __bf16* nh, __bf16* nl, const float* m16, uint32_t* a16, const float* dps,
                         int dp_rows);
+// ... and their LayerScale forms (the third inclusion)
+static int resid_fq_lnstats_ls(const float* x_prev, const float* Y, const float* qpY, int qmin, int qmax, float* x_new, float* mean, float* rstd,
+                               const float* gamma, const float* beta, float eps, uint32_t* stats, int stat_slots, int64_t M, int D, int T, hipStream_t st,
+                               unsigned long long* mbits, const QpLate& lt, const float* dps, const float* lsg);
+static int mask_bwd_ls(const float* d, const float* Y, const float* qp, int qmin, int qmax, const float* col_scale, int ncols4, __bf16* h, __bf16* l, int64_t n4,
+                       hipStream_t st, const float* o16_mul, uint32_t* o16_amax, const float* dps, int T, const float* lsg);
+static int ln_bwd_fq_ls(int acc, int grid, const float* dH, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T, int cls_only,
+                        hipStream_t st, const unsigned long long* nm, const float* ncs, __bf16* nh, __bf16* nl, const float* m16, uint32_t* a16, const LnBwdNext& nx);
 
 int launch_resid_fq_lnstats(int mode, const float* x_prev, const float* Y, const float* qpY, int qmin, int qmax, const float* cls, const float* pos,
                             float* x_new, float* mean, float* rstd, const float* gamma, const float* beta, float eps, uint32_t* stats, int stat_slots,
-                            int64_t M, int D, int T, hipStream_t st, void* maskbits, const QpLate* late, const float* drop_scale_rows) {
+                            int64_t M, int D, int T, hipStream_t st, void* maskbits, const QpLate* late, const float* drop_scale_rows, const float* ls_gamma) {
     if (D % 4 != 0 || D > 256 * kMaxV) { set_error("resid_fq_lnstats: D=%d unsupported (need D%%4==0, D<=768)", D); return 1; }
     unsigned long long* mbits = mode != 1 ? nullptr : reinterpret_cast<unsigned long long*>(maskbits);
     const QpLate lt = late ? *late : QpLate{};
+    if (ls_gamma) {
+        if (mode != 1) { set_error("resid_fq_lnstats: LayerScale belongs to a residual branch (mode 1)"); return 1; }
+        return resid_fq_lnstats_ls(x_prev, Y, qpY, qmin, qmax, x_new, mean, rstd, gamma, beta, eps, stats, stat_slots, M, D, T, st, mbits, lt, drop_scale_rows, ls_gamma);
+    }
     if (drop_scale_rows) {
         if (mode != 1) { set_error("resid_fq_lnstats: drop-path multipliers belong to a residual branch (mode 1)"); return 1; }
         return resid_fq_lnstats_dp(x_prev, Y, qpY, qmin, qmax, x_new, mean, rstd, gamma, beta, eps, stats, stat_slots, M, D, T, st, mbits, lt, drop_scale_rows);
@@ -478,9 +491,13 @@ int launch_cls_rows(const float* cls, const float* pos, float* x, int B, int T, 
 }
 
 int launch_mask_bwd(int gelu_bwd, const float* d, const float* Y, const float* qp, int qmin, int qmax, const float* col_scale, int ncols,
-                    void* dst_hi, void* dst_lo, int64_t n, hipStream_t st, const float* o16_mul, uint32_t* o16_amax, const float* drop_scale_rows, int T) {
+                    void* dst_hi, void* dst_lo, int64_t n, hipStream_t st, const float* o16_mul, uint32_t* o16_amax, const float* drop_scale_rows, int T, const float* ls_gamma) {
     __bf16* h = reinterpret_cast<__bf16*>(dst_hi);
     __bf16* l = reinterpret_cast<__bf16*>(dst_lo);
+    if (ls_gamma) {   // Y: a residual branch's output under LayerScale (and, drop_scale_rows, drop-path)
+        if (gelu_bwd || T < 1 || ncols < 4 || (o16_mul && !o16_amax)) { set_error("mask_bwd: LayerScale goes with the plain mask, ncols and T"); return 1; }
+        return mask_bwd_ls(d, Y, qp, qmin, qmax, col_scale, ncols / 4, h, l, n / 4, st, o16_mul, o16_amax, drop_scale_rows, T, ls_gamma);
+    }
     if (drop_scale_rows) {   // Y: a residual branch's output, [n / ncols rows, T per sample] x ncols, under drop-path
         if (gelu_bwd || T < 1 || ncols < 4 || (o16_mul && !o16_amax)) { set_error("mask_bwd: drop-path multipliers go with the plain mask, ncols and T"); return 1; }
         return mask_bwd_dp(d, Y, qp, qmin, qmax, col_scale, ncols / 4, h, l, n / 4, st, o16_mul, o16_amax, drop_scale_rows, T);
@@ -510,6 +527,13 @@ int launch_ln_bwd_fq(int acc, const float* dH, const float* x, const float* mean
     const float* m16 = next ? next->o16_mul : nullptr;
     uint32_t* a16 = next ? next->o16_amax : nullptr;
     if (m16 && !a16) { set_error("ln_bwd_fq: o16_mul needs o16_amax"); return 1; }
+    if (next && next->ls_gamma) {   // the next branch ran under LayerScale: its gamma goes into the fused store, and gamma's gradient is formed here
+        if (next->drop_rows < 1 || !nh || !next->ls_dgamma || !next->ls_Y || next->ls_ymul < 1) {
+            set_error("ln_bwd_fq: LayerScale needs the rows per sample, an output plane, the branch output and the gradient buffer");
+            return 1;
+        }
+        return ln_bwd_fq_ls(acc, grid, dH, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, st, nm, ncs, nh, nl, m16, a16, *next);
+    }
     if (next && next->drop_scale) {   // the next branch ran under drop-path: its multipliers go into the fused store
         if (next->drop_rows < 1 || !nh) { set_error("ln_bwd_fq: drop-path multipliers need the rows per sample and an output plane"); return 1; }
         return ln_bwd_fq_dp(acc, grid, dH, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, st, nm, ncs, nh, nl, m16, a16,
@@ -672,6 +696,45 @@ static int ln_bwd_fq_dp(int acc, int grid, const float* dH, const float* x, cons
     if (acc) { if (nv == 1) QV_LNB_DP(1, 1); else if (nv == 2) QV_LNB_DP(1, 2); else QV_LNB_DP(1, 3); }
     else { if (nv == 1) QV_LNB_DP(0, 1); else if (nv == 2) QV_LNB_DP(0, 2); else QV_LNB_DP(0, 3); }
 #undef QV_LNB_DP
+    return 0;
+}
+
+// ============================================================================ the row kernels under LayerScale (k_*_ls) and their launches
+#define QV_DP 2
+#include "elt_rows.inc"
+#undef QV_DP
+
+static int resid_fq_lnstats_ls(const float* x_prev, const float* Y, const float* qpY, int qmin, int qmax, float* x_new, float* mean, float* rstd,
+                               const float* gamma, const float* beta, float eps, uint32_t* stats, int stat_slots, int64_t M, int D, int T, hipStream_t st,
+                               unsigned long long* mbits, const QpLate& lt, const float* dps, const float* lsg) {
+#define QV_RESID_LS(NV_) k_resid_fq_lnstats_ls<1, NV_><<<rows_grid(M), 256, 0, st>>>(x_prev, Y, qpY, qmin, qmax, nullptr, nullptr, x_new, mean, rstd, gamma, beta, eps, stats, stat_slots, M, D, T, mbits, lt, dps, T, lsg)
+    const int nv = (D + 255) / 256;
+    if (nv == 1) QV_RESID_LS(1); else if (nv == 2) QV_RESID_LS(2); else QV_RESID_LS(3);
+#undef QV_RESID_LS
+    return 0;
+}
+static int mask_bwd_ls(const float* d, const float* Y, const float* qp, int qmin, int qmax, const float* col_scale, int ncols4, __bf16* h, __bf16* l, int64_t n4,
+                       hipStream_t st, const float* o16_mul, uint32_t* o16_amax, const float* dps, int T, const float* lsg) {
+    if (o16_mul) k_mask_bwd_ls<0, true><<<flat_grid(n4), 256, 0, st>>>(d, Y, qp, qmin, qmax, col_scale, ncols4, h, l, n4, o16_mul, o16_amax, dps, T, lsg);
+    else k_mask_bwd_ls<0><<<flat_grid(n4), 256, 0, st>>>(d, Y, qp, qmin, qmax, col_scale, ncols4, h, l, n4, nullptr, nullptr, dps, T, lsg);
+    return 0;
+}
+// (the output forms of launch_ln_bwd_fq's fused store: one fp16 plane, one bf16 plane, the bf16 pair)
+static int ln_bwd_fq_ls(int acc, int grid, const float* dH, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T, int cls_only,
+                        hipStream_t st, const unsigned long long* nm, const float* ncs, __bf16* nh, __bf16* nl, const float* m16, uint32_t* a16, const LnBwdNext& nx) {
+#define QV_LS_TAIL nx.drop_scale, nx.drop_rows, nx.ls_gamma, nx.ls_Y, nx.ls_ymul, nx.ls_qp, nx.ls_kind, nx.ls_dgamma
+#define QV_LNB_LS(ACC_, NV_)                                                                                                                       \
+    do {                                                                                                                                           \
+        if (m16) k_ln_bwd_fq_ls<ACC_, NV_, 8, true, true><<<grid, 512, 0, st>>>(dH, 0, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, nm, ncs, nh, nl, m16, a16, QV_LS_TAIL); \
+        else if (!nl) k_ln_bwd_fq_ls<ACC_, NV_, 8, true, false, true><<<grid, 512, 0, st>>>(dH, 0, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, nm, ncs, nh, nullptr, nullptr, nullptr, QV_LS_TAIL); \
+        else k_ln_bwd_fq_ls<ACC_, NV_, 8, true><<<grid, 512, 0, st>>>(dH, 0, x, mean, rstd, gamma, beta, qp, qmin, qmax, dx_in, dx_out, dgamma, dbeta, M, D, T, cls_only, nm, ncs, nh, nl, nullptr, nullptr, QV_LS_TAIL); \
+    } while (0)
+    const int nv = (D + 255) / 256;
+    if (acc) { if (nv == 1) QV_LNB_LS(1, 1); else if (nv == 2) QV_LNB_LS(1, 2); else QV_LNB_LS(1, 3); }
+    else { if (nv == 1) QV_LNB_LS(0, 1); else if (nv == 2) QV_LNB_LS(0, 2); else QV_LNB_LS(0, 3); }
+#undef QV_LNB_LS
+#undef QV_LS_TAIL
     return 0;
 }
 

@@ -5,12 +5,27 @@
 // drop-path keep their names, their arguments and, instruction for instruction, their machine code (profiles/drop_path_bench.txt): a shared __device__ body
 // inlined into both changed the existing kernels' code, a further template flag with a trailing argument their names and kernel-argument layout.
 // The multiplier is wave-uniform; it is requested with the row's other loads, before anything is used.
-#if QV_DP
+// QV_DP 2: a third inclusion, k_<name>_ls - LayerScale.  The branch is also multiplied by lsg[column], the learnable per-channel gamma that stands between the
+// branch's fake-quant and DropPath: x_new = x_prev + (fq(Y) * lsg[c]) * dps[sample], every product and the sum rounded separately.  lsg is required and loaded
+// once per thread, like the LayerNorm gamma; dps may be null here (LayerScale without drop-path: multiplier 1, a wave-uniform select), so one variant serves
+// both.  k_ln_bwd_fq_ls takes five more arguments (QV_LS_BWD_ARGS): it also produces lsg's gradient, see there.
+#if QV_DP == 2
+#define QV_LS 1
+#define QV_ROWK(name) name##_ls
+#define QV_DP_ARGS , const float* __restrict__ dps, int dp_rows, const float* __restrict__ lsg
+#define QV_LS_BWD_ARGS , const float* __restrict__ lsY, int ls_ymul, const float* __restrict__ lsqp, int ls_kind, float* __restrict__ dls
+#define QV_DP_LOAD(idx) (dps ? dps[idx] : 1.f)
+#elif QV_DP
+#define QV_LS 0
 #define QV_ROWK(name) name##_dp
 #define QV_DP_ARGS , const float* __restrict__ dps, int dp_rows
+#define QV_LS_BWD_ARGS
+#define QV_DP_LOAD(idx) dps[idx]
 #else
+#define QV_LS 0
 #define QV_ROWK(name) name
 #define QV_DP_ARGS
+#define QV_LS_BWD_ARGS
 #endif
 
 // ---------------------------------------------------------------- residual + FQ + LN statistics
@@ -44,6 +59,9 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_fq_lnstats)(const float* 
     bool act[NV];
     int cc[NV];
     float4 g[NV], bb[NV];
+#if QV_LS
+    float4 lsv[NV];   // the branch's LayerScale gamma: once per thread
+#endif
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int c = lane * 4 + 256 * j;
@@ -51,6 +69,9 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_fq_lnstats)(const float* 
         cc[j] = act[j] ? c : 0;
         g[j] = *reinterpret_cast<const float4*>(gamma + cc[j]);
         bb[j] = *reinterpret_cast<const float4*>(beta + cc[j]);
+#if QV_LS
+        lsv[j] = *reinterpret_cast<const float4*>(lsg + cc[j]);
+#endif
     }
     float mn = INFINITY, mx = -INFINITY;
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * 4) {
@@ -66,7 +87,7 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_fq_lnstats)(const float* 
             yr[j] = *reinterpret_cast<const float4*>(ysrc + cc[j]);
         }
 #if QV_DP
-        float sc = dps[row / dp_rows];
+        float sc = QV_DP_LOAD(row / dp_rows);
 #endif
         // (pin the loaded values here: LLVM otherwise sinks each column group's loads down to its uses, one memory round trip per group)
 #pragma unroll
@@ -87,6 +108,9 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_fq_lnstats)(const float* 
                 mb[j][0] = __ballot(act[j] && i0); mb[j][1] = __ballot(act[j] && i1);
                 mb[j][2] = __ballot(act[j] && i2); mb[j][3] = __ballot(act[j] && i3);
             }
+#if QV_LS
+            y = make_float4(__fmul_rn(y.x, lsv[j].x), __fmul_rn(y.y, lsv[j].y), __fmul_rn(y.z, lsv[j].z), __fmul_rn(y.w, lsv[j].w));
+#endif
 #if QV_DP
             y = make_float4(__fmul_rn(y.x, sc), __fmul_rn(y.y, sc), __fmul_rn(y.z, sc), __fmul_rn(y.w, sc));
 #endif
@@ -136,6 +160,7 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_fq_lnstats)(const float* 
 // Output: the (hi, lo) bf16 pair both the dgrad and the wgrad GEMM read.
 // QV_DP (GELU_BWD = 0): Y is a residual branch's output [rows, 4 * ncols4] under drop-path, and its gradient also carries dps[row / dp_rows] - what
 // k_ln_bwd_fq's fused store computes on the paths that do not pass through here.
+// QV_LS: ... and lsg[column], the branch's LayerScale gamma (gamma's own gradient is k_ln_bwd_fq_ls's, which produced d).
 template <int GELU_BWD, bool O16 = false>
 __global__ __launch_bounds__(256) void QV_ROWK(k_mask_bwd)(const float* __restrict__ d, const float* __restrict__ Y, const float* __restrict__ qp,
                                                   int qmin, int qmax, const float* __restrict__ col_scale, int ncols4,
@@ -162,9 +187,15 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_mask_bwd)(const float* __restri
             o[e] = in ? (GELU_BWD ? g4[e] * gelu_bwd(f) : g4[e]) * cs[e] : 0.f;
         }
 #if QV_DP
-        const float sc = dps[(i / ncols4) / dp_rows];
+        const float sc = QV_DP_LOAD((i / ncols4) / dp_rows);
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] *= sc;
+#endif
+#if QV_LS
+        {
+            const float4 lg = reinterpret_cast<const float4*>(lsg)[i % ncols4];
+            o[0] *= lg.x; o[1] *= lg.y; o[2] *= lg.z; o[3] *= lg.w;
+        }
 #endif
         if constexpr (O16) store_f16x4(dst_hi, i * 4, o[0], o[1], o[2], o[3], mul, am);
         else store_split4(dst_hi, dst_lo, i * 4, o[0], o[1], o[2], o[3]);
@@ -181,6 +212,12 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_mask_bwd)(const float* __restri
 // k_resid_fq_lnstats wrote in the forward) and the optional per-channel weight scale: what k_mask_bwd<0> would compute from a second
 // read of dx_out and of the fp32 pre-FQ tensor.
 // BF1: the fused next-branch gradient as ONE bf16 plane (nhi; the float step's bf16 form)
+// QV_LS: the next branch was scaled by its LayerScale gamma lsg, so its gradient is dx_out * mask * colscale * dps[sample] * lsg[c] - and this kernel is where
+// lsg's own gradient is complete: dls[c] += sum over rows of dx_out[row, c] * dps[sample] * B[row, c], B the branch output the forward scaled, WITHOUT the STE
+// mask (d (fq(Y) * g) / dg = fq(Y) whether or not Y clamped).  B is read again from lsY (row `row * ls_ymul`: 1 over full-height rows, T over the compact
+// class-token rows, whose Y stays where the forward left it): fq(Y) with the qparams lsqp (the QAT step keeps the pre-FQ Y of every block), or - lsqp null,
+// the float forms - Y rounded as ls_kind says (0: fp32, 1: fp16, 2: bf16, the type stock autocast holds it in).  A dead row (cls_only) that carries a
+// gradient (ACC) contributes too.  The sums travel through the sg staging array once dgamma / dbeta have left it: no LDS beyond the kernel without LayerScale.
 template <int ACC, int NV, int WPB = 8, bool FUSE = false, bool O16 = false, bool BF1 = false>   // WPB waves per block: column sums meet in LDS, so more waves per block = same atomics, more rows in flight
 __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __restrict__ dH, int64_t dH_row_stride_rows, const float* __restrict__ x,
                                                    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
@@ -189,7 +226,7 @@ __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __
                                                    float* __restrict__ dbeta, int64_t M, int D, int T, int cls_only,
                                                    const unsigned long long* __restrict__ nmask, const float* __restrict__ ncs,
                                                    __bf16* __restrict__ nhi, __bf16* __restrict__ nlo, const float* __restrict__ o16_mul,
-                                                   uint32_t* __restrict__ o16_amax QV_DP_ARGS) {
+                                                   uint32_t* __restrict__ o16_amax QV_DP_ARGS QV_LS_BWD_ARGS) {
     static_assert((!O16 && !BF1) || (FUSE && !(O16 && BF1)), "the one-plane output is the fused next-branch gradient");
     static_assert(!QV_DP || FUSE, "drop-path scales the fused next-branch gradient");
 #if QV_DP
@@ -212,10 +249,31 @@ __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __
         bt[j] = *reinterpret_cast<const float4*>(beta + cc[j]);
         csn[j] = FUSE && ncs ? *reinterpret_cast<const float4*>(ncs + cc[j]) : make_float4(1.f, 1.f, 1.f, 1.f);
     }
+#if QV_LS
+    float4 lsv[NV], al[NV];   // the next branch's LayerScale gamma (once per thread) and this lane's share of its gradient
+    QP lq{};
+    if (lsqp) lq = load_qp(lsqp);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        lsv[j] = *reinterpret_cast<const float4*>(lsg + cc[j]);
+        al[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    auto ls_branch = [&](float y) {   // B of one element
+        bool in;
+        return lsqp ? fqv(y, lq, qmin, qmax, in) : ls_kind == 1 ? (float)(_Float16)y : ls_kind == 2 ? (float)(__bf16)y : y;
+    };
+    auto ls_acc = [&](int j, const float4& o, const float4& y) {
+        al[j].x += o.x * sc * ls_branch(y.x); al[j].y += o.y * sc * ls_branch(y.y); al[j].z += o.z * sc * ls_branch(y.z); al[j].w += o.w * sc * ls_branch(y.w);
+    };
+#endif
     auto fuse_store = [&](int64_t row, int j, int c, const float4& o) {
         const unsigned long long m0 = mk[j][0], m1 = mk[j][1], m2 = mk[j][2], m3 = mk[j][3];
         const float4 cs = csn[j];
-#if QV_DP
+#if QV_LS
+        const float4 lg = lsv[j];
+        const float f0 = ((m0 >> lane) & 1 ? o.x * cs.x : 0.f) * sc * lg.x, f1 = ((m1 >> lane) & 1 ? o.y * cs.y : 0.f) * sc * lg.y,
+                    f2 = ((m2 >> lane) & 1 ? o.z * cs.z : 0.f) * sc * lg.z, f3 = ((m3 >> lane) & 1 ? o.w * cs.w : 0.f) * sc * lg.w;
+#elif QV_DP
         const float f0 = ((m0 >> lane) & 1 ? o.x * cs.x : 0.f) * sc, f1 = ((m1 >> lane) & 1 ? o.y * cs.y : 0.f) * sc, f2 = ((m2 >> lane) & 1 ? o.z * cs.z : 0.f) * sc,
                     f3 = ((m3 >> lane) & 1 ? o.w * cs.w : 0.f) * sc;
 #else
@@ -239,7 +297,7 @@ __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __
                 for (int e = 0; e < 4; ++e) mk[j][e] = nmask[(row * NV + j) * 4 + e];
         }
 #if QV_DP
-        sc = dps[row / dp_rows];
+        sc = QV_DP_LOAD(row / dp_rows);
 #endif
         if (!live) {
             // no gradient reaches this token through the (cls-pooled) head
@@ -249,6 +307,9 @@ __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __
                     const float4 o = ACC ? *reinterpret_cast<const float4*>(dx_in + row * D + cc[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
                     *reinterpret_cast<float4*>(dx_out + row * D + cc[j]) = o;
                     if (FUSE) fuse_store(row, j, cc[j], o);
+#if QV_LS
+                    if (ACC) ls_acc(j, o, *reinterpret_cast<const float4*>(lsY + row * ls_ymul * D + cc[j]));
+#endif
                 }
             }
             continue;
@@ -264,11 +325,19 @@ __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __
             dvv[j] = *reinterpret_cast<const float4*>(dH + drow * D + cc[j]);
             if (ACC) pv[j] = *reinterpret_cast<const float4*>(dx_in + row * D + cc[j]);
         }
+#if QV_LS
+        float4 yv[NV];   // the next branch's output row
+#pragma unroll
+        for (int j = 0; j < NV; ++j) yv[j] = *reinterpret_cast<const float4*>(lsY + row * ls_ymul * D + cc[j]);
+#endif
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             pin4(xv[j]);
             pin4(dvv[j]);
             if (ACC) pin4(pv[j]);
+#if QV_LS
+            pin4(yv[j]);
+#endif
         }
         float4 xh[NV], gy[NV];
         float s1 = 0.f, s2 = 0.f;
@@ -300,6 +369,9 @@ __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __
             if (act[j]) {
                 *reinterpret_cast<float4*>(dx_out + row * D + cc[j]) = o;
                 if (FUSE) fuse_store(row, j, cc[j], o);
+#if QV_LS
+                ls_acc(j, o, yv[j]);
+#endif
             }
         }
     }
@@ -322,7 +394,27 @@ __global__ __launch_bounds__(WPB * 64) void QV_ROWK(k_ln_bwd_fq)(const float* __
         atomicAdd(&dgamma[c], a);
         atomicAdd(&dbeta[c], b);
     }
+#if QV_LS
+    __syncthreads();   // dgamma has left sg: the LayerScale sums take its place
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = lane * 4 + 256 * j;
+        if (j < nv && c < D) { sg[wave][c] = al[j].x; sg[wave][c + 1] = al[j].y; sg[wave][c + 2] = al[j].z; sg[wave][c + 3] = al[j].w; }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += WPB * 64) {
+        float a = 0.f;
+#pragma unroll
+        for (int w = 0; w < WPB; ++w) a += sg[w][c];
+        atomicAdd(&dls[c], a);
+    }
+#endif
 }
 
 #undef QV_ROWK
 #undef QV_DP_ARGS
+#undef QV_LS_BWD_ARGS
+#undef QV_LS
+#ifdef QV_DP_LOAD
+#undef QV_DP_LOAD
+#endif

@@ -86,7 +86,7 @@ struct Forms {
     bool ln_in_strip;        // norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln) where the forward writes the byte plane only (ln_in_strip_of)
     bool cls_bwd;            // the one-plane backward of the final norm and of the last block's MLP + proj on the B class-token rows (Plan::ClsRows; bwd() decides per call)
 };
-// drop_path: a drop-path scale table is bound to the workspace of the call (qatvit_student_set_drop_path)
+// drop_path: a drop-path scale table or a LayerScale binding is bound to the workspace of the call (qatvit_student_set_drop_path, _set_layer_scale)
 static Forms forms_of(const qatvit_cfg& c, const Dims& d, bool drop_path) {
     const Knobs& k = knobs();
     const bool byte_codes = c.act_qmax - c.act_qmin <= 255;
@@ -102,7 +102,7 @@ static Forms forms_of(const qatvit_cfg& c, const Dims& d, bool drop_path) {
     f.attn_codes = k.attn_codes && byte_codes;
     f.qkv_2pass = k.qkv_2pass && f.attn_codes && f.i8 && (3 * d.D) % 384 == 0 && d.D % 64 == 0 && (d.D / d.H) % 32 == 0;
     f.attn_bwd_fused = attn_bwd_is_fused(d.T, d.H, d.D, f.attn_codes);
-    f.lnb = k.lnb_fuse && d.D == 384 && !drop_path;   // (the fused epilogue does not know the drop-path multipliers: k_ln_bwd_fq behind the plain dgrad does)
+    f.lnb = k.lnb_fuse && d.D == 384 && !drop_path;   // (the fused epilogue knows neither the drop-path multipliers nor a LayerScale gamma: k_ln_bwd_fq behind the plain dgrad does)
     f.x_plane_from_q8 = f.i8 && k.tn_q8 && d.D % 384 == 0;
     f.tn_stream = k.tn_stream && d.D % 384 == 0 && d.Hd % 384 == 0;
     f.dy16 = f.i8 && f.w_batched && d.D % 384 == 0 && d.Hd % 384 == 0 && f.qkv_2pass && f.attn_bwd_fused && f.f16_proj && f.fc2w_codes;
@@ -332,6 +332,10 @@ struct Ctx {
     // drop-path: the scale table bound to the workspace ([2 * depth][batch] floats), nullptr: none.  Row of block i's attention (mlp = 0) / MLP (1) branch:
     const float* drop = nullptr;
     const float* drop_row(int i, int mlp) const { return drop ? drop + (int64_t)(2 * i + mlp) * d.B : nullptr; }
+    // LayerScale: the binding of the workspace (qatvit_student_set_layer_scale), null: none.  gamma / gradient of block i's attention (mlp = 0) / MLP (1) branch:
+    std::shared_ptr<const LayerScale> ls;
+    const float* ls_gamma(int i, int mlp) const { return ls ? ls->gamma[2 * i + mlp] : nullptr; }
+    float* ls_grad(int i, int mlp) const { return ls && !ls->grad.empty() ? ls->grad[2 * i + mlp] : nullptr; }
     // ---- the one-plane backward (dy16.hip): slot k (DS_*) of block i
     uint32_t* dy_slot(int i, int k) const { return at<uint32_t>(p.dy16) + kDyHdrWords + (int64_t)(DS_COUNT * i + k) * kDySlotWords; }
     const float* dy_mul(int i, int k) const { return reinterpret_cast<const float*>(dy_slot(i, k) + 1); }
@@ -391,11 +395,11 @@ struct Ctx {
     // launch_resid_fq_lnstats (Y = the output of quantizer ai_Y, -1: none; x_new: the rows of `next`, or nullptr where they stand already) leaves the row
     // statistics of the LayerNorm `next`, whose output quantizer is updated behind it
     int resid_lnstats(int mode, const float* x_prev, const float* Y, int ai_Y, const float* cls, const float* pos, float* x_new, const LnRows& next,
-                      void* maskbits = nullptr, const float* drop_scale_rows = nullptr) const {
+                      void* maskbits = nullptr, const float* drop_scale_rows = nullptr, const float* ls_gamma_cols = nullptr) const {
         const bool lt = ai_Y >= 0 && late_kind(ai_Y);
         const QpLate L = lt ? late(ai_Y) : QpLate{};
         if (launch_resid_fq_lnstats(mode, x_prev, Y, act_qp(ai_Y >= 0 ? ai_Y : 0), c.act_qmin, c.act_qmax, cls, pos, x_new, next.mean, next.rstd, next.gamma, next.beta,
-                                    c.ln_eps, act_stats(next.ai), kStatSlots, d.M, d.D, d.T, st, maskbits, lt ? &L : nullptr, drop_scale_rows))
+                                    c.ln_eps, act_stats(next.ai), kStatSlots, d.M, d.D, d.T, st, maskbits, lt ? &L : nullptr, drop_scale_rows, ls_gamma_cols))
             return 1;
         qparams_after(next.ai, true);
         return 0;
@@ -579,7 +583,7 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
         } else if (x.linear_fwd(x.blk<void>(p.O_hi, i), x.blk<void>(p.O_lo, i), M, x.widx(i, WB_PROJ), nullptr, x.bprm(i, B_PROJB),
                                 x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ)))
             return 1;
-        if (x.resid_lnstats(1, n1.x, x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ), nullptr, nullptr, n2.x, n2, x.blk<void>(p.mproj, i), x.drop_row(i, 0))) return 1;
+        if (x.resid_lnstats(1, n1.x, x.blk<float>(p.Yproj, i), x.aidx(i, AB_PROJ), nullptr, nullptr, n2.x, n2, x.blk<void>(p.mproj, i), x.drop_row(i, 0), x.ls_gamma(i, 0))) return 1;
     }
     if (parts & 4) {   // ---- part 2: norm2 -> fc1 (both passes) -> GELU
         if (!x.ln_in_strip(WB_FC1)) x.ln_apply(n2, x.blk<void>(p.h2q, i), x.blk<void>(p.h2q8, i));   // (else norm2's apply + quantise runs inside fc1's statistics pass)
@@ -610,7 +614,7 @@ static int fwd_block(const Ctx& x, int i, int parts, bool qkv_injected = false) 
             return 1;
         // residual + statistics of the NEXT LayerNorm (block i+1's norm1, or the final norm)
         const Ctx::LnRows next = x.norm1(i + 1);
-        if (x.resid_lnstats(1, n2.x, x.blk<float>(p.Y2, i), x.aidx(i, AB_FC2), nullptr, nullptr, next.x, next, x.blk<void>(p.m2, i), x.drop_row(i, 1))) return 1;
+        if (x.resid_lnstats(1, n2.x, x.blk<float>(p.Y2, i), x.aidx(i, AB_FC2), nullptr, nullptr, next.x, next, x.blk<void>(p.m2, i), x.drop_row(i, 1), x.ls_gamma(i, 1))) return 1;
     }
     return 0;
 }
@@ -801,6 +805,14 @@ struct Bwd {
         LnBwdNext nx{maskbits, x.dy_colscale(wi), g.hi, g.lo, mul(blk_i, g), amax(blk_i, g)};
         nx.drop_scale = x.drop_row(blk_i, wi == x.widx(blk_i, WB_FC2) ? 1 : 0);
         nx.drop_rows = rows ? 1 : x.d.T;
+        // Under LayerScale it carries that branch's gamma too, and the kernel that writes it completes gamma's gradient: from the residual gradient, the multipliers
+        // and fq of the branch's pre-FQ output, which every block keeps (the compact class-token rows read it in place, every T-th row)
+        const int mlp = wi == x.widx(blk_i, WB_FC2) ? 1 : 0;
+        nx.ls_gamma = x.ls_gamma(blk_i, mlp);
+        nx.ls_dgamma = x.ls_grad(blk_i, mlp);
+        nx.ls_Y = x.blk<float>(mlp ? x.p.Y2 : x.p.Yproj, blk_i);
+        nx.ls_ymul = rows ? x.d.T : 1;
+        nx.ls_qp = x.act_qp(x.aidx(blk_i, mlp ? AB_FC2 : AB_PROJ));
         return nx;
     }
     // launch_ln_bwd_fq for the LayerNorm r over M rows (dx_in: the residual gradient it adds to where acc)
@@ -972,7 +984,7 @@ int Bwd::block(int i, bool injected) {
     // ---- MLP branch
     if (injected) {
         if (launch_mask_bwd(0, dxA, x.blk<float>(p.Y2, i), x.act_qp(x.aidx(i, AB_FC2)), qa, qb, x.dy_colscale(w_fc2), d.D, o.gy.hi, o.gy.lo, d.M * d.D, st, mul(i, o.gy),
-                            amax(i, o.gy), x.drop_row(i, 1), d.T))
+                            amax(i, o.gy), x.drop_row(i, 1), d.T, x.ls_gamma(i, 1)))
             return 1;
         calib(o.gy, d.M * d.D, i);
     }
@@ -1098,7 +1110,8 @@ int qatvit_student_init(const qatvit_cfg* cfg, void* workspace, void* stream) {
         if (it != g_profs.end()) { std::lock_guard<std::mutex> l2(it->second->mu); it->second->closed = true; }
         g_profs.erase(workspace);
     }
-    drop_path_bind(workspace, nullptr);   // ... and so does a drop-path table
+    drop_path_bind(workspace, nullptr);   // ... and so do a drop-path table and a LayerScale binding
+    layer_scale_bind(workspace, 0, nullptr, nullptr, nullptr);
     launch_ws_init(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + p.stats), p.stats_words / 2, (hipStream_t)stream);
     // the one-plane backward's scale history starts empty (the first backward on a workspace calibrates); no late-resolved quantizer state is pending
     launch_zero_i32(reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + p.dy16), dy16_state_bytes(DS_COUNT * cfg->depth) / 4, (hipStream_t)stream);
@@ -1117,7 +1130,9 @@ static int run_forward(const qatvit_cfg* cfg, void* const* params, const qatvit_
     QV_CHECK_ARG((flags & ~(QATVIT_STAGE_INJECT | QATVIT_FWD_X16)) == 0 && !((flags & QATVIT_STAGE_INJECT) && stage_from == 0), "%s: bad flags %d", who, flags);
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
     x.drop = drop_path_of(workspace);
-    if (make_plan(*cfg, &x.p, x.drop != nullptr)) return 1;
+    x.ls = layer_scale_of(workspace);
+    QV_CHECK_ARG(!x.ls || (int)x.ls->gamma.size() == 2 * cfg->depth, "student step: the LayerScale binding holds %d branches, depth is %d", (int)x.ls->gamma.size(), cfg->depth);
+    if (make_plan(*cfg, &x.p, x.drop != nullptr || x.ls != nullptr)) return 1;
     x.flags = flags & QATVIT_FWD_X16;
     QV_CHECK_ARG(!x.flags || x.p.form.dy16, "%s: QATVIT_FWD_X16 needs a configuration the one-plane backward covers (qatvit_student_dy16_supported)", who);
     if (fwd(x, images, logits, stage_from, stage_to, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
@@ -1146,7 +1161,9 @@ int qatvit_student_forward_part(const qatvit_cfg* cfg, void* const* params, cons
                  "qatvit_student_forward_part: bad block %d / part %d / flags %d", block, part, flags);
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
     x.drop = drop_path_of(workspace);
-    if (make_plan(*cfg, &x.p, x.drop != nullptr)) return 1;
+    x.ls = layer_scale_of(workspace);
+    QV_CHECK_ARG(!x.ls || (int)x.ls->gamma.size() == 2 * cfg->depth, "student step: the LayerScale binding holds %d branches, depth is %d", (int)x.ls->gamma.size(), cfg->depth);
+    if (make_plan(*cfg, &x.p, x.drop != nullptr || x.ls != nullptr)) return 1;
     x.flags = flags & QATVIT_FWD_X16;
     QV_CHECK_ARG(!x.flags || x.p.form.dy16, "qatvit_student_forward_part: QATVIT_FWD_X16 needs a configuration the one-plane backward covers");
     if (fwd_part(x, block, part, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
@@ -1165,8 +1182,11 @@ static int run_backward(const qatvit_cfg* cfg, void* const* params, const qatvit
                  "%s: bad flags %d", who, flags);
     Ctx x{*cfg, dims_of(*cfg), Plan(), reinterpret_cast<char*>(workspace), params, act_fq, weight_fq, (hipStream_t)stream, prof_of(workspace)};
     x.drop = drop_path_of(workspace);
-    if (make_plan(*cfg, &x.p, x.drop != nullptr)) return 1;
+    x.ls = layer_scale_of(workspace);
+    QV_CHECK_ARG(!x.ls || (int)x.ls->gamma.size() == 2 * cfg->depth, "student step: the LayerScale binding holds %d branches, depth is %d", (int)x.ls->gamma.size(), cfg->depth);
+    if (make_plan(*cfg, &x.p, x.drop != nullptr || x.ls != nullptr)) return 1;
     x.flags = flags & (QATVIT_BWD_DY16 | QATVIT_BWD_CALIBRATE);
+    QV_CHECK_ARG(!x.ls || !x.ls->grad.empty(), "%s: the LayerScale binding has no gradient buffers", who);
     if (bwd(x, dlogits, grads, stage_from, stage_to, (flags & QATVIT_STAGE_INJECT) != 0)) return 1;
     QV_CHECK_LAUNCH(who);
     return 0;

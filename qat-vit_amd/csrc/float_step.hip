@@ -406,7 +406,8 @@ static void fs_consts(const FsPlan& p, char* ws, hipStream_t st) {
 static int fs_init(const char* fn, FsForm form, const qatvit_cfg* cfg, void* workspace, void* stream) {
     QV_CHECK_ARG(cfg && workspace, "%s: null argument", fn);
     if (fs_check(*cfg, form)) return 1;
-    drop_path_bind(workspace, nullptr);   // (a drop-path table bound to this address belongs to whatever stood here before)
+    drop_path_bind(workspace, nullptr);   // (a drop-path table bound to this address belongs to whatever stood here before; a LayerScale binding too)
+    layer_scale_bind(workspace, 0, nullptr, nullptr, nullptr);
     fs_consts(fs_plan(*cfg, form), reinterpret_cast<char*>(workspace), (hipStream_t)stream);
     QV_CHECK_LAUNCH(fn);
     return 0;
@@ -478,6 +479,11 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
     // drop-path (qatvit_float_student_set_drop_path): the per-sample multipliers of block i's attention (mlp = 0) or MLP (1) branch, nullptr without a table
     const float* const drop = drop_path_of(workspace);
     auto drop_row = [&](int i, int mlp) { return drop ? drop + (int64_t)(2 * i + mlp) * c.batch : nullptr; };
+    // LayerScale (qatvit_float_student_set_layer_scale): the branch's gamma, and where its output goes - its own rows of the binding's saved buffer, which the
+    // backward reads for gamma's gradient, instead of the one shared Y (a binding without that buffer serves a forward alone)
+    const std::shared_ptr<const LayerScale> ls = layer_scale_of(workspace);
+    QV_CHECK_ARG(!ls || (int)ls->gamma.size() == 2 * c.depth, "%s: the LayerScale binding holds %d branches, depth is %d", fn, (int)ls->gamma.size(), c.depth);
+    auto ls_gamma = [&](int i, int mlp) { return ls ? ls->gamma[2 * i + mlp] : nullptr; };
     // ---- the form's steps
     auto weight_planes = [&] {   // the weights' (hi, lo) pairs or fp16 / bf16 planes, as stored and transposed, in one launch
         FsWTab t{};
@@ -542,18 +548,20 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
         const int w0 = 1 + 4 * i, a0 = 2 + 6 * i;
         if (gemm(k.h1_hi, k.h1_lo, w0 + 0, bprm(i, 3), F(k.qkv), 3 * D, D, (int)M, a0 + 1)) return 1;
         if (launch_attn_fwd_float(F(k.qkv), c.batch, T, c.num_heads, D, V(k.O_hi), V(k.O_lo), st, f16, F(k.lse))) return 1;
-        if (gemm(k.O_hi, k.O_lo, w0 + 1, bprm(i, 5), F(p.Y), D, D, (int)M, a0 + 2)) return 1;
-        launch_resid_ln_split_save(1, F(k.x), F(p.Y), nullptr, nullptr, F(k.xm), bprm(i, 6), bprm(i, 7), c.ln_eps, V(k.h2_hi), V(k.h2_lo), F(k.mean2),
-                                   F(k.rstd2), M, D, T, st, ob.act(a0 + 3), f16, drop_row(i, 0));
+        float* const Ya = ls && ls->saved ? ls->saved + (int64_t)(2 * i) * M * D : F(p.Y);
+        float* const Ym = ls && ls->saved ? ls->saved + (int64_t)(2 * i + 1) * M * D : F(p.Y);
+        if (gemm(k.O_hi, k.O_lo, w0 + 1, bprm(i, 5), Ya, D, D, (int)M, a0 + 2)) return 1;
+        launch_resid_ln_split_save(1, F(k.x), Ya, nullptr, nullptr, F(k.xm), bprm(i, 6), bprm(i, 7), c.ln_eps, V(k.h2_hi), V(k.h2_lo), F(k.mean2),
+                                   F(k.rstd2), M, D, T, st, ob.act(a0 + 3), f16, drop_row(i, 0), ls_gamma(i, 0));
         if (gemm(k.h2_hi, k.h2_lo, w0 + 2, bprm(i, 9), F(k.Y1), Hd, D, (int)M, a0 + 4)) return 1;
         gelu(k);
-        if (gemm(k.G_hi, k.G_lo, w0 + 3, bprm(i, 11), F(p.Y), D, Hd, (int)M, a0 + 5)) return 1;
+        if (gemm(k.G_hi, k.G_lo, w0 + 3, bprm(i, 11), Ym, D, Hd, (int)M, a0 + 5)) return 1;
         const bool last = i + 1 == L;
         const FsBlock* nx = last ? nullptr : &p.blk[i + 1];
-        launch_resid_ln_split_save(1, F(k.xm), F(p.Y), nullptr, nullptr, last ? F(p.x_last) : F(nx->x), last ? prm(4 + 12 * L) : bprm(i + 1, 0),
+        launch_resid_ln_split_save(1, F(k.xm), Ym, nullptr, nullptr, last ? F(p.x_last) : F(nx->x), last ? prm(4 + 12 * L) : bprm(i + 1, 0),
                                    last ? prm(4 + 12 * L + 1) : bprm(i + 1, 1), c.ln_eps, last ? V(p.hf_hi) : V(nx->h1_hi), last ? V(p.hf_lo) : V(nx->h1_lo),
                                    last ? F(p.meanf) : F(nx->mean1), last ? F(p.rstdf) : F(nx->rstd1), M, D, T, st, ob.act(last ? 2 + 6 * L : a0 + 6), f16,
-                                   drop_row(i, 1));
+                                   drop_row(i, 1), ls_gamma(i, 1));
     }
     const int hb = 4 + 12 * L;
     head(prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3));
@@ -586,18 +594,19 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
     float* partial = F(p.tn_partial);
     // ---- the form's steps
     // dgrad: C[M, N] = A[M, K] . W[K, N]  with the transposed weight's planes as the B operand ([N, K] row-major)
-    auto dgrad = [&](int64_t ah, int64_t al, int wi, float* C, int N, int K) {
+    // (s2: the one-plane forms' second scalar - 1 / K where the fp16 form carries a branch's gradients scaled by K, see below; else the unit)
+    auto dgrad = [&](int64_t ah, int64_t al, int wi, float* C, int N, int K, const float* s2 = nullptr) {
         NTGemm g;
         g.A = V(ah); g.B = V(p.w_hiT[wi]); g.C = C; g.M = (int)M; g.N = N; g.K = g.lda = g.ldb = K; g.ldc = N;
-        if (one) g.s1 = g.s2 = unit;
+        if (one) { g.s1 = unit; g.s2 = s2 ? s2 : unit; }
         else { g.A_lo = V(al); g.B_lo = V(p.w_loT[wi]); }
         return launch_gemm_nt(bf16 ? kNTPlaneBf16 : f16 ? kNTPlaneF16 : kNTBf16, g, nullptr, st);
     };
     // wgrad: dW[N, Kw] += dY[Mr, N]^T . X[Mr, Kw], dbias[N] += column sums of dY
-    auto wgrad = [&](int64_t ph, int64_t pl, int64_t qh, int64_t ql, float* dW, float* db, int N, int Kw, int Mr) {
+    auto wgrad = [&](int64_t ph, int64_t pl, int64_t qh, int64_t ql, float* dW, float* db, int N, int Kw, int Mr, const float* s2 = nullptr) {
         TNGemm g;
         g.P = V(ph); g.Q = V(qh); g.C = dW; g.dbias = db; g.N = N; g.Kw = Kw; g.ldp = N; g.ldq = Kw; g.ldc = Kw;
-        if (one) g.s1 = g.s2 = unit;
+        if (one) { g.s1 = unit; g.s2 = s2 ? s2 : unit; }
         else { g.P_lo = V(pl); g.Q_lo = V(ql); }
         TNCall call;
         call.M = Mr; call.scratch = partial; call.scratch_bytes = kTnScratchBytes;
@@ -644,9 +653,30 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
     LnBwdNext next{V(p.ones), nullptr, V(p.dp_hi), V(p.dp_lo), f16 ? unit : nullptr, reinterpret_cast<uint32_t*>(V(p.amax))};
     // drop-path (the table the forward read): dp also carries the multipliers of the branch it enters - block i's attention (mlp = 0) or MLP (1) branch
     const float* const drop = drop_path_of(workspace);
+    const std::shared_ptr<const LayerScale> ls = layer_scale_of(workspace);
+    QV_CHECK_ARG(!ls || ((int)ls->gamma.size() == 2 * c.depth && ls->grad.size() == ls->gamma.size() && ls->saved),
+                 "%s: the LayerScale binding needs 2 * depth gammas, their gradient buffers and the saved-branch buffer", fn);
+    // The fp16 form under LayerScale.  Stock autocast holds every gradient inside a branch in fp16, and each of them carries the branch's gamma: at
+    // gamma = 1e-5, timm's initial value, they lie in or under fp16's subnormal range, and every gradient in front of a branch loses its digits (stock
+    // autocast without a loss scale: 5e-2 - 7e-2 relative).  Here the branch's gradients travel multiplied by K, a power of two of the order of
+    // 1 / max |gamma| (launch_fs_ls_scales: exact to apply and to undo): the LayerNorm backward writes dp * K, the GEMMs, the GELU backward and the attention
+    // backward are linear in it, and the four weight gradients and the dgrad that leaves the branch undo it through the GEMMs' scalar (1 / K).  K = 1 for
+    // max |gamma| >= 0.5 (ls_scales.hip).  {K, 1 / K} per branch stand behind the branch outputs in the binding's saved buffer.
+    float* const lsK = f16 && ls ? ls->saved + (int64_t)2 * L * M * D : nullptr;
+    if (lsK) {
+        QV_CHECK_ARG(2 * L <= 24, "%s: LayerScale scales cover depth <= 12", fn);
+        if (launch_fs_ls_scales(ls->gamma.data(), 2 * L, D, lsK, st)) return 1;
+    }
+    auto inv_of = [&](int i, int mlp) -> const float* { return lsK ? lsK + 2 * (2 * i + mlp) + 1 : nullptr; };
     auto next_of = [&](int i, int mlp) {
         next.drop_scale = drop ? drop + (int64_t)(2 * i + mlp) * c.batch : nullptr;
         next.drop_rows = T;
+        if (lsK) next.o16_mul = lsK + 2 * (2 * i + mlp);
+        if (ls) {   // LayerScale: dp also carries the branch's gamma, and the kernel that writes it completes gamma's gradient from the branch output the forward kept
+            const int k = 2 * i + mlp;
+            next.ls_gamma = ls->gamma[k]; next.ls_dgamma = ls->grad[k]; next.ls_Y = ls->saved + (int64_t)k * M * D; next.ls_ymul = 1;
+            next.ls_qp = nullptr; next.ls_kind = f16 ? 1 : bf16 ? 2 : 0;
+        }
         return &next;
     };
     // head, then the final norm on the cls rows (dx of every other row = 0); the residual gradient leaves as fp32 (dx) and as dp
@@ -658,28 +688,32 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
         const FsBlock& k = p.blk[i];
         const int w0 = 1 + 4 * i, g0 = 4 + 12 * i;
         // fc2 (input G = gelu(Y1)), then GELU' on the fc1 pre-activation
-        if (wgrad(p.dp_hi, p.dp_lo, k.G_hi, k.G_lo, grd(g0 + 10), grd(g0 + 11), D, Hd, (int)M)) return 1;
+        const float* const im = inv_of(i, 1), * const ia = inv_of(i, 0);   // (1 / K of the MLP and of the attention branch, nullptr: the unit)
+        if (wgrad(p.dp_hi, p.dp_lo, k.G_hi, k.G_lo, grd(g0 + 10), grd(g0 + 11), D, Hd, (int)M, im)) return 1;
         if (dgrad(p.dp_hi, p.dp_lo, w0 + 3, F(p.dG), Hd, D)) return 1;
         if (gelu_bwd(k)) return 1;
         // fc1 (input h2 = norm2(xm)), norm2 backward + the residual: dx2 = dx + LNbwd(dh2), and its dp for proj
-        if (wgrad(p.dY1_hi, p.dY1_lo, k.h2_hi, k.h2_lo, grd(g0 + 8), grd(g0 + 9), Hd, D, (int)M)) return 1;
-        if (dgrad(p.dY1_hi, p.dY1_lo, w0 + 2, F(p.dh), D, Hd)) return 1;
+        if (wgrad(p.dY1_hi, p.dY1_lo, k.h2_hi, k.h2_lo, grd(g0 + 8), grd(g0 + 9), Hd, D, (int)M, im)) return 1;
+        if (dgrad(p.dY1_hi, p.dY1_lo, w0 + 2, F(p.dh), D, Hd, im)) return 1;
         if (launch_ln_bwd_fq(1, F(p.dh), F(k.xm), F(k.mean2), F(k.rstd2), prm(g0 + 6), prm(g0 + 7), qp_off, 0, 255, F(p.dx), F(p.dx2), grd(g0 + 6), grd(g0 + 7), M,
                              D, T, 0, st, next_of(i, 0)))
             return 1;
         // proj (input O), attention, qkv (input h1 = norm1(x)); norm1 backward: dx = dx2 + LNbwd(dh1), the gradient of the block's input
-        if (wgrad(p.dp_hi, p.dp_lo, k.O_hi, k.O_lo, grd(g0 + 4), grd(g0 + 5), D, D, (int)M)) return 1;
+        if (wgrad(p.dp_hi, p.dp_lo, k.O_hi, k.O_lo, grd(g0 + 4), grd(g0 + 5), D, D, (int)M, ia)) return 1;
         if (dgrad(p.dp_hi, p.dp_lo, w0 + 1, F(p.dO), D, D)) return 1;
         if (attn_bwd(k)) return 1;
-        if (wgrad(p.dqkv_hi, p.dqkv_lo, k.h1_hi, k.h1_lo, grd(g0 + 2), grd(g0 + 3), 3 * D, D, (int)M)) return 1;
-        if (dgrad(p.dqkv_hi, p.dqkv_lo, w0 + 0, F(p.dh), D, 3 * D)) return 1;
+        if (wgrad(p.dqkv_hi, p.dqkv_lo, k.h1_hi, k.h1_lo, grd(g0 + 2), grd(g0 + 3), 3 * D, D, (int)M, ia)) return 1;
+        if (dgrad(p.dqkv_hi, p.dqkv_lo, w0 + 0, F(p.dh), D, 3 * D, ia)) return 1;
         if (launch_ln_bwd_fq(1, F(p.dh), F(k.x), F(k.mean1), F(k.rstd1), prm(g0 + 0), prm(g0 + 1), qp_off, 0, 255, F(p.dx2), F(p.dx), grd(g0 + 0), grd(g0 + 1), M,
                              D, T, 0, st, i > 0 ? next_of(i - 1, 1) : nullptr))
             return 1;
     }
     // embedding, then the patch-embedding weight gradient over the saved patches
     embed_bwd();
-    if (wgrad(p.dY0_hi, p.dY0_lo, p.p_hi, p.p_lo, grd(0), grd(1), D, Kpe, c.batch * np)) return 1;
+    if (lsK) {   // (the fp16 form under LayerScale: the patch-embedding gradient's operand at the branches' scale, see above)
+        if (launch_fs_ls_dy0(F(p.dx), V(p.dY0_hi), c.batch, T, D, lsK, 2 * L, st)) return 1;
+    }
+    if (wgrad(p.dY0_hi, p.dY0_lo, p.p_hi, p.p_lo, grd(0), grd(1), D, Kpe, c.batch * np, lsK ? lsK + 4 * L + 1 : nullptr)) return 1;
     fp16_overflow();
     QV_CHECK_LAUNCH(fn);
     return 0;

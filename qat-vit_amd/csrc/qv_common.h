@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <memory>
+#include <vector>
+
 namespace qv {
 
 constexpr int kWave = 64;
@@ -12,6 +15,15 @@ void set_error(const char* fmt, ...);
 // the drop-path scale table bound to a step workspace, nullptr: none (capi.hip; include/qatvit.h qatvit_student_set_drop_path)
 void drop_path_bind(const void* workspace, const float* table);
 const float* drop_path_of(const void* workspace);
+// the LayerScale binding of a step workspace, null: none (capi.hip; include/qatvit.h qatvit_student_set_layer_scale): per branch (row 2 i = block i's attention
+// branch, 2 i + 1 = its MLP branch) the device address of gamma [embed_dim] and of its gradient; saved: the float forms' retained branch outputs
+struct LayerScale {
+    std::vector<const float*> gamma;
+    std::vector<float*> grad;   // (empty: a forward-only binding)
+    float* saved = nullptr;
+};
+void layer_scale_bind(const void* workspace, int branches, const float* const* gammas, float* const* grads, void* saved);
+std::shared_ptr<const LayerScale> layer_scale_of(const void* workspace);
 
 // The QATVIT_* knobs of the library, read from the environment once per process on first use (capi.hip).  Each one switches a form off for an
 // A/B or bit-identity comparison (tests/test_gpu_knobs.py); unset = on, set = atoi(value) != 0.  Which form a configuration runs is decided from

@@ -206,7 +206,8 @@ int launch_img_patches(const float* img, void* out_bf16, const float* qp, int qm
 int launch_resid_fq_lnstats(int mode, const float* x_prev, const float* Y, const float* qpY, int qmin, int qmax, const float* cls, const float* pos,
                             float* x_new, float* mean, float* rstd, const float* gamma, const float* beta, float eps, uint32_t* stats, int stat_slots,
                             int64_t M, int D, int T, hipStream_t st, void* maskbits = nullptr, const QpLate* late = nullptr,   // late: Y's qparams are resolved inside (QpLate)
-                            const float* drop_scale_rows = nullptr);   // mode 1, optional: x_new = x_prev + fq(Y) * drop_scale_rows[row / T] (drop-path; [M / T] floats)
+                            const float* drop_scale_rows = nullptr,   // mode 1, optional: x_new = x_prev + fq(Y) * drop_scale_rows[row / T] (drop-path; [M / T] floats)
+                            const float* ls_gamma = nullptr);   // mode 1, optional: LayerScale - x_new = x_prev + (fq(Y) * ls_gamma[column]) * multiplier (k_*_ls, with or without drop-path)
 // STE mask of an [M, D] tensor as wave ballots: ceil(D / 256) * 4 64-bit words per row (written by launch_resid_fq_lnstats mode 1)
 inline int64_t ln_maskbits_bytes(int64_t M, int D) { return M * ((D + 255) / 256) * 32; }
 // optional second output of launch_ln_bwd_fq: split(dx_out * mask * colscale) for the next branch's GEMMs (out_lo == nullptr without o16_*: its hi part
@@ -216,6 +217,10 @@ struct LnBwdNext {
     // drop-path: that branch's per-sample multipliers, also a factor of its gradient - drop_scale[row / drop_rows], drop_rows = rows per sample (T over [B * T, D]
     // rows, 1 over the compact class-token rows [B, D])
     const float* drop_scale = nullptr; int drop_rows = 0;
+    // LayerScale: that branch's gamma [D], also a factor of its gradient, and what gamma's own gradient needs - ls_dgamma [D] (accumulated into), the branch output
+    // ls_Y (row r of this call is its row r * ls_ymul: 1, or T over the compact class-token rows), taken as fq(ls_Y) under the qparams ls_qp or, ls_qp null, rounded
+    // as ls_kind says (0: fp32, 1: fp16, 2: bf16).  With ls_gamma set, drop_scale may be null (drop_rows is still needed)
+    const float* ls_gamma = nullptr; float* ls_dgamma = nullptr; const float* ls_Y = nullptr; int ls_ymul = 1; const float* ls_qp = nullptr; int ls_kind = 0;
 };
 int launch_ln_apply_quant(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp, int qmin,
                           int qmax, void* out_bf16, int64_t M, int D, hipStream_t st, void* out8 = nullptr, int center = 0,
@@ -228,7 +233,8 @@ int launch_ln_quant8(const float* x, const float* gamma, const float* beta, floa
 int launch_cls_rows(const float* cls, const float* pos, float* x, int B, int T, int D, hipStream_t st);
 int launch_mask_bwd(int gelu_bwd, const float* d, const float* Y, const float* qp, int qmin, int qmax, const float* col_scale, int ncols,
                     void* dst_hi, void* dst_lo, int64_t n, hipStream_t st, const float* o16_mul = nullptr, uint32_t* o16_amax = nullptr,
-                    const float* drop_scale_rows = nullptr, int T = 0);   // plain mask, optional: also * drop_scale_rows[row / T] (a residual branch under drop-path)
+                    const float* drop_scale_rows = nullptr, int T = 0,   // plain mask, optional: also * drop_scale_rows[row / T] (a residual branch under drop-path)
+                    const float* ls_gamma = nullptr);   // ... and * ls_gamma[column] (LayerScale; needs T, drop_scale_rows may then be null)
 int launch_ln_bwd_fq(int acc, const float* dH, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                      const float* qp, int qmin, int qmax, const float* dx_in, float* dx_out, float* dgamma, float* dbeta, int64_t M, int D, int T,
                      int cls_only, hipStream_t st, const LnBwdNext* next = nullptr,
@@ -322,8 +328,14 @@ int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
                                uint32_t* stats = nullptr, int f16 = 0,
-                               const float* drop_scale_rows = nullptr);   // mode 1, optional: x = x_prev + Y * drop_scale_rows[row / T] (drop-path; [M / T] floats)
+                               const float* drop_scale_rows = nullptr,   // mode 1, optional: x = x_prev + Y * drop_scale_rows[row / T] (drop-path; [M / T] floats)
+                               const float* ls_gamma = nullptr);   // mode 1, optional: LayerScale - x = x_prev + (Y * ls_gamma[column]) * multiplier, nothing rounded to a 16-bit type
 int launch_gelu_split(const float* Y, void* hi, void* lo, int64_t n, hipStream_t st);   // n % 4 == 0
+// ---- ls_scales.hip: the fp16 float form under LayerScale - scales[2 k] = K, [2 k + 1] = 1 / K of branch k, a power of two of the order of 1 / max |gamma_k|
+// in [1, 2^24] (gammas: HOST array of device pointers, at most 24); then the patch rows of dx as the fp16 plane dY0 * Ke, Ke = the smallest branch scale,
+// with {Ke, 1 / Ke} left at scales[2 * branches], [2 * branches + 1]
+int launch_fs_ls_scales(const float* const* gammas, int branches, int D, float* scales, hipStream_t st);
+int launch_fs_ls_dy0(const float* dx, void* dY0_f16, int B, int T, int D, float* scales, int branches, hipStream_t st);
 // ---- float_amp.hip: the fp16 (autocast) form of the float student step, and (bf16 = true) its bf16 form: the same pieces on bf16 planes and
 // v_mfma_f32_16x16x32_bf16 (the host driver of both is float_step.hip's).  Fused attention backward on v_mfma_f32_16x16x32_f16, one workgroup per
 // (image, head): qkv / dO fp32 [B*T, 3D] / [B*T, D] (rounded to fp16 on load), O16 fp16 [B*T, D], lse [B][H][T] -> dqkv16 fp16 [B*T, 3D]

@@ -303,11 +303,17 @@ int launch_patches_split(const float* img, void* hi, void* lo, int B, int C, int
 // other kernel of the file, which keeps those where they stood in the object
 static int resid_ln_split_dp(const float* x_prev, const float* Y, float* x_new, const float* gamma, const float* beta, float eps, __bf16* hh, __bf16* hl, float* mean,
                              float* rstd, int64_t M, int D, int T, hipStream_t st, uint32_t* stats, int f16, const float* dps);
+static int resid_ln_split_ls(const float* x_prev, const float* Y, float* x_new, const float* gamma, const float* beta, float eps, __bf16* hh, __bf16* hl, float* mean,
+                             float* rstd, int64_t M, int D, int T, hipStream_t st, uint32_t* stats, int f16, const float* dps, const float* lsg);
 int launch_resid_ln_split_save(int mode, const float* x_prev, const float* Y, const float* cls, const float* pos, float* x_new, const float* gamma,
                                const float* beta, float eps, void* h_hi, void* h_lo, float* mean, float* rstd, int64_t M, int D, int T, hipStream_t st,
-                               uint32_t* stats, int f16, const float* drop_scale_rows) {
+                               uint32_t* stats, int f16, const float* drop_scale_rows, const float* ls_gamma) {
     __bf16* hh = reinterpret_cast<__bf16*>(h_hi);
     __bf16* hl = reinterpret_cast<__bf16*>(h_lo);
+    if (ls_gamma) {
+        if (mode != 1) { set_error("resid_ln_split: LayerScale belongs to a residual branch (mode 1)"); return 1; }
+        return resid_ln_split_ls(x_prev, Y, x_new, gamma, beta, eps, hh, hl, mean, rstd, M, D, T, st, stats, f16, drop_scale_rows, ls_gamma);
+    }
     if (drop_scale_rows) {
         if (mode != 1) { set_error("resid_ln_split: drop-path multipliers belong to a residual branch (mode 1)"); return 1; }
         return resid_ln_split_dp(x_prev, Y, x_new, gamma, beta, eps, hh, hl, mean, rstd, M, D, T, st, stats, f16, drop_scale_rows);
@@ -348,6 +354,25 @@ static int resid_ln_split_dp(const float* x_prev, const float* Y, float* x_new, 
     } while (0)
     if (nv == 1) QV_RESID_DP(1); else if (nv == 2) QV_RESID_DP(2); else QV_RESID_DP(3);
 #undef QV_RESID_DP
+    return 0;
+}
+
+// ---------------------------------------------------------------- ... and under LayerScale (k_resid_ln_split_ls), with or without drop-path
+#define QV_DP 2
+#include "teacher_rows.inc"
+#undef QV_DP
+static int resid_ln_split_ls(const float* x_prev, const float* Y, float* x_new, const float* gamma, const float* beta, float eps, __bf16* hh, __bf16* hl, float* mean,
+                             float* rstd, int64_t M, int D, int T, hipStream_t st, uint32_t* stats, int f16, const float* dps, const float* lsg) {
+    const int grid = rows_grid_t(M), nv = (D + 255) / 256;
+    const float* const none = nullptr;
+#define QV_RESID_LS(NV_)                                                                                                                                    \
+    do {                                                                                                                                                    \
+        if (stats) k_resid_ln_split_ls<1, NV_, true><<<grid, 256, 0, st>>>(x_prev, Y, none, none, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, stats, dps, lsg); \
+        else if (!f16 && !hl) k_resid_ln_split_ls<1, NV_, false, true><<<grid, 256, 0, st>>>(x_prev, Y, none, none, x_new, gamma, beta, eps, hh, hl, M, D, T, 0, mean, rstd, nullptr, dps, lsg); \
+        else k_resid_ln_split_ls<1, NV_><<<grid, 256, 0, st>>>(x_prev, Y, none, none, x_new, gamma, beta, eps, hh, hl, M, D, T, f16, mean, rstd, nullptr, dps, lsg); \
+    } while (0)
+    if (nv == 1) QV_RESID_LS(1); else if (nv == 2) QV_RESID_LS(2); else QV_RESID_LS(3);
+#undef QV_RESID_LS
     return 0;
 }
 

@@ -4,7 +4,13 @@
 // QV_DP (MODE 1): x = x_prev + Y * dps[row / T].  The pair form (and its STATS form): the product in fp32.  The fp16 form (f16) and the bf16 form (BF1): as stock
 // autocast - Y and the multiplier are values of the 16-bit type, their product is rounded to that type (the fp32 product of two such values is exact: ONE
 // rounding), the add is fp32.  The multiplier is wave-uniform and is requested with the row's other loads.
-#if QV_DP
+// QV_DP 2: a third inclusion, k_resid_ln_split_ls - LayerScale: x = x_prev + (B * lsg[column]) * dps[row / T], B = Y in the pair forms and Y rounded to the
+// 16-bit type in the fp16 / bf16 forms.  lsg is the fp32 parameter, so stock type promotion makes the product fp32 and DropPath runs in fp32: neither the product
+// nor the multiplier is rounded to the 16-bit type here (with the multiplier alone, above, both are).  dps may be null: LayerScale without drop-path.
+#if QV_DP == 2
+#define QV_ROWK(name) name##_ls
+#define QV_DP_ARGS , const float* __restrict__ dps = nullptr, const float* __restrict__ lsg = nullptr
+#elif QV_DP
 #define QV_ROWK(name) name##_dp
 #define QV_DP_ARGS , const float* __restrict__ dps = nullptr
 #else
@@ -32,6 +38,9 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_ln_split)(const float* __
     bool act[NV];
     int cc[NV];
     float4 g[NV], bb[NV];
+#if QV_DP == 2
+    float4 lsv[NV];   // the branch's LayerScale gamma: once per thread
+#endif
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int c = lane * 4 + 256 * j;
@@ -39,6 +48,9 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_ln_split)(const float* __
         cc[j] = act[j] ? c : 0;
         g[j] = *reinterpret_cast<const float4*>(gamma + cc[j]);
         bb[j] = *reinterpret_cast<const float4*>(beta + cc[j]);
+#if QV_DP == 2
+        lsv[j] = *reinterpret_cast<const float4*>(lsg + cc[j]);
+#endif
     }
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += (int64_t)gridDim.x * 4) {
         const int t = (int)(row % T);
@@ -51,12 +63,21 @@ __global__ __launch_bounds__(256) void QV_ROWK(k_resid_ln_split)(const float* __
             v[j] = *reinterpret_cast<const float4*>(bsrc + cc[j]);
             y[j] = *reinterpret_cast<const float4*>(ysrc + cc[j]);
         }
-#if QV_DP
+#if QV_DP == 2
+        float sc = dps ? dps[b] : 1.f;
+#elif QV_DP
         float sc = dps[b];
 #endif
 #pragma unroll
         for (int j = 0; j < NV; ++j) { pin4(v[j]); pin4(y[j]); }
-#if QV_DP
+#if QV_DP == 2
+        asm volatile("" : "+v"(sc));
+        const int kind = BF1 ? 2 : f16 ? 1 : 0;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            y[j] = make_float4(__fmul_rn(__fmul_rn(round_as(y[j].x, kind), lsv[j].x), sc), __fmul_rn(__fmul_rn(round_as(y[j].y, kind), lsv[j].y), sc),
+                               __fmul_rn(__fmul_rn(round_as(y[j].z, kind), lsv[j].z), sc), __fmul_rn(__fmul_rn(round_as(y[j].w, kind), lsv[j].w), sc));
+#elif QV_DP
         asm volatile("" : "+v"(sc));
         const int kind = BF1 ? 2 : f16 ? 1 : 0;   // (uniform) the type stock autocast holds the branch output in: bf16, fp16, or fp32
         sc = round_as(sc, kind);

@@ -21,6 +21,7 @@ import torch
 from . import functional as F
 from . import native
 from .data import GpuResizeNormalize
+from .vit import layer_scale_params
 
 FORMAT = 1
 FIELDS = ("N", "C", "teacher_form", "transform", "data_digest", "param_digest")
@@ -51,7 +52,7 @@ def data_digest(data_u8, labels=None) -> str:
 def param_digest(teacher) -> str:
     """SHA-256 of the teacher's parameters in the order of the C ABI (native.vit_params); computed on the host."""
     h = hashlib.sha256()
-    for p in native.vit_params(teacher):
+    for p in native.vit_params(teacher) + layer_scale_params(teacher):   # (LayerScale gammas, where the teacher has them, behind the ABI's parameters)
         h.update(repr((tuple(p.shape), str(p.dtype))).encode())
         h.update(p.detach().cpu().contiguous().numpy().tobytes())
     return h.hexdigest()
@@ -65,7 +66,7 @@ def teacher_form(teacher) -> int:
 
 
 def _versions(teacher) -> tuple:
-    return tuple((p.data_ptr(), p._version) for p in native.vit_params(teacher))
+    return tuple((p.data_ptr(), p._version) for p in native.vit_params(teacher) + layer_scale_params(teacher))
 
 
 class TeacherLogitTable:
@@ -113,6 +114,8 @@ class TeacherLogitTable:
         if not data_u8.is_cuda:
             raise RuntimeError("TeacherLogitTable.build runs on MI355X only: move the uint8 images to the GPU (there is no CPU fallback)")
         params = native.vit_params(teacher)
+        if layer_scale_params(teacher):
+            raise RuntimeError("TeacherLogitTable.build: the native teacher forward does not cover a LayerScale teacher (its stock module forward does)")
         if any(not p.is_cuda for p in params):
             raise RuntimeError("TeacherLogitTable.build runs on MI355X only: move the teacher to the GPU (there is no CPU fallback)")
         if any(p.requires_grad for p in teacher.parameters()):

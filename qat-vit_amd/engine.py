@@ -51,19 +51,22 @@ class FlatGradLayout:
     (stage 0 = final norm + head, stages 1..depth = blocks depth-1..0, stage depth+1 = embedding), so that the
     gradients finished by a prefix of the stages are a contiguous slice - the unit of the bucketed all-reduce.
 
-    ``numels``: parameter sizes in the C-ABI order of include/qatvit.h (4 embedding tensors, 12 per block, 4 tail)."""
+    ``numels``: parameter sizes in the C-ABI order of include/qatvit.h (4 embedding tensors, 12 per block, 4 tail), optionally followed by the
+    2 * depth LayerScale gammas (block i's ``ls1`` / ``ls2`` at 8 + 12 * depth + 2 i, + 1): they lie at the end of block i's stage, so the bucketed
+    all-reduce carries them with that block.  Without them the layout is what it always was."""
 
     ALIGN = 64  # elements: every tensor starts on a 256-byte boundary
 
     def __init__(self, numels: Sequence[int], depth: int):
-        n_par = len(numels)
-        if n_par != 8 + 12 * depth:
-            raise ValueError(f"expected {8 + 12 * depth} parameters for depth {depth}, got {n_par}")
+        n_par = 8 + 12 * depth
+        if len(numels) not in (n_par, n_par + 2 * depth):
+            raise ValueError(f"expected {n_par} parameters for depth {depth} (or {n_par + 2 * depth} with LayerScale), got {len(numels)}")
+        ls = 2 if len(numels) > n_par else 0
         order = [n_par - 4 + k for k in range(4)]                       # stage 0: norm, head
         for i in reversed(range(depth)):
-            order += [4 + 12 * i + k for k in range(12)]                # stages 1..depth
+            order += [4 + 12 * i + k for k in range(12)] + [n_par + 2 * i + k for k in range(ls)]   # stages 1..depth
         order += [0, 1, 2, 3]                                           # stage depth+1: embedding
-        stage_of_slot = [0] * 4 + sum(([s] * 12 for s in range(1, depth + 1)), []) + [depth + 1] * 4
+        stage_of_slot = [0] * 4 + sum(([s] * (12 + ls) for s in range(1, depth + 1)), []) + [depth + 1] * 4
         self.order = order
         self.offset: Dict[int, int] = {}
         self.stage_end: List[int] = [0] * (depth + 2)
@@ -420,6 +423,11 @@ class StudentEngine:
         self.lib = native.lib()
         blocks = list(m.blocks)
         ps, act, wfq = collect_student(wrapper)
+        # LayerScale: the 2 * depth gammas stand BEHIND the parameters of the C ABI (every existing index keeps its meaning); the library learns their
+        # addresses through qatvit_student_set_layer_scale
+        self.n_abi = len(ps)
+        self.ls = native.LayerScaleBinding(m, dev)
+        ps = ps + self.ls.gammas
         for p in ps:
             if p is None or p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("every student parameter must be a contiguous fp32 tensor (bias=True everywhere)")
@@ -453,7 +461,7 @@ class StudentEngine:
         if hd * self.cfg.num_heads != self.cfg.embed_dim:
             raise RuntimeError("embed_dim must equal num_heads * head_dim")
         L, cp = self.lib, ctypes.byref(self.cfg)
-        assert L.qatvit_student_num_params(cp) == len(ps) and L.qatvit_student_num_act_fq(cp) == len(act) and L.qatvit_student_num_weight_fq(cp) == len(wfq)
+        assert L.qatvit_student_num_params(cp) == self.n_abi and L.qatvit_student_num_act_fq(cp) == len(act) and L.qatvit_student_num_weight_fq(cp) == len(wfq)
         self._rehome_fq_state()
         self.capacity = 0
         self.workspace: Optional[torch.Tensor] = None
@@ -524,7 +532,7 @@ class StudentEngine:
 
     # ------------------------------------------------------------------ FQ state arena
     def _rehome_fq_state(self):
-        self.fq_f32, self.fq_i32, self.fq_arena, self.fq_total = rehome_fq_state(self.params, self.act_fq, self.w_fq, self.device)
+        self.fq_f32, self.fq_i32, self.fq_arena, self.fq_total = rehome_fq_state(self.params[:self.n_abi], self.act_fq, self.w_fq, self.device)
 
     def _build_fq_structs(self):
         def arr(fqs):
@@ -592,6 +600,7 @@ class StudentEngine:
         flags = FWD_X16 if x16 else 0
         # drop-path (module in training mode): filled here, read by this forward and by its backward - the binding stays until the next forward
         self.drop.bind("qatvit_student_set_drop_path", c, self.workspace, self.drop.step(c.batch, self.capacity, self.frozen))
+        self.ls.bind(c, self.workspace)
         self.last_step = Step(c, self.generation + 1, x16, mode, int(self.lib.qatvit_student_ln_in_strip(ctypes.byref(c), flags)))
         native.check(self.lib.qatvit_student_forward_stages(ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, images.data_ptr(),
                                                             logits.data_ptr(), self.workspace.data_ptr(), 0, c.depth + 1, flags, native.stream_ptr()),
@@ -622,6 +631,7 @@ class StudentEngine:
         images = images.contiguous()
         logits = torch.empty(c.batch, c.num_classes, dtype=torch.float32, device=self.device)
         self.drop.bind("qatvit_float_student_set_drop_path", c, self.float_form.workspace, self.drop.step(c.batch, max(self.capacity, self.float_form.capacity), self.frozen))
+        self.ls.bind_float(c, self.float_form.workspace)
         self.last_step = Step(c, self.generation + 1, False, OBSERVE, 0)
         native.check(self.lib.qatvit_float_student_forward_observe(ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr(),
                                                                    self.float_form.workspace.data_ptr(), self.observe_buf.data_ptr(), native.stream_ptr()),
@@ -632,6 +642,7 @@ class StudentEngine:
         """The float step's backward (every STE mask is 1: the gradient stock computes); in a data-parallel group one average of the whole flat
         gradient afterwards."""
         flat, views, gptr = self._grad_buffers()
+        self.ls.bind_float(step.cfg, self.float_form.workspace, views[self.n_abi:])
         self.float_form.call("backward", ctypes.byref(step.cfg), self._ptr_params, dlogits.contiguous().data_ptr(), gptr)
         if self.pg is not None:
             allreduce_mean(flat, self.pg)
@@ -643,6 +654,7 @@ class StudentEngine:
     def _run_backward(self, dlogits: torch.Tensor, c: native.Cfg, flags: int):
         flat, views, gptr = self._grad_buffers()
         L, cp, st = self.lib, ctypes.byref(c), native.stream_ptr()
+        self.ls.bind(c, self.workspace, views[self.n_abi:])   # (the gammas' gradients are accumulated into this backward's buffer)
 
         def run(s0, s1):
             native.check(L.qatvit_student_backward_stages(cp, self._ptr_params, self._act_structs, self._w_structs, dlogits.data_ptr(), gptr,
@@ -718,6 +730,7 @@ class StudentEngine:
         """Returns per-parameter gradient views (zero for the stages that did not run).  mode: 0 (pair form), BWD_CALIBRATE or BWD_DY16."""
         c = self.cfg
         flat, views, gptr = self._grad_buffers()
+        self.ls.bind(c, self.workspace, views[self.n_abi:])
         native.check(self.lib.qatvit_student_backward_stages(
             ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, dlogits.contiguous().data_ptr() if dlogits is not None else None,
             gptr, self.workspace.data_ptr(), stage_from, stage_to, (STAGE_INJECT if inject else 0) | mode, native.stream_ptr()), "qatvit_student_backward_stages")

@@ -19,6 +19,11 @@ from .model_registry import create_student
 FORMAT = "qatvit-int8-v1"
 
 
+def _has_layer_scale(export: Dict) -> bool:
+    """The LayerScale gammas travel as fp32 among the export's "float" tensors (``model.blocks.i.ls1.gamma`` / ``ls2.gamma``)."""
+    return any(n.endswith((".ls1.gamma", ".ls2.gamma")) for n in export["float"])
+
+
 def _fq_items(prepared):
     return {n: m for n, m in prepared.named_modules() if hasattr(m, "activation_post_process") and hasattr(m, "scale") and hasattr(m, "zero_point")}
 
@@ -66,7 +71,8 @@ def import_int8(export: Dict, device="cuda"):
     """Rebuilds a prepared QATWrapper (observers frozen, eval mode) from export_int8's dict."""
     if export.get("format") != FORMAT:
         raise ValueError("not a qatvit int8 export")
-    stu = create_student("vit", qat_wrapper=True, **export["arch"])
+    # (a LayerScale export: the tree is built with LayerScale modules, whose gammas the "float" tensors below overwrite)
+    stu = create_student("vit", qat_wrapper=True, **export["arch"], **(dict(init_values=1.0) if _has_layer_scale(export) else {}))
     stu.train()
     stu.qconfig = get_default_qat_qconfig(export["backend"])
     prepared = prepare_qat(stu, inplace=False).to(device)
@@ -110,6 +116,9 @@ class Int8Student:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Int8Student executes on MI355X only (no CPU fallback exists)")
+        if _has_layer_scale(export):
+            raise NotImplementedError("Int8Student: the export holds LayerScale gammas; the integer forward adds the residual in a GEMM epilogue that does not "
+                                      "know them yet - evaluate import_int8(export) (the native QAT forward) instead")
         self.lib = native.lib()
         a = export["arch"]
         depth = a["depth"]

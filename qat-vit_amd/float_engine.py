@@ -30,7 +30,7 @@ _OPTED = weakref.WeakKeyDictionary()   # wrapper -> FloatStudentEngine (or None 
 
 def check_shape(model: nn.Module, amp=False) -> None:
     """Raise unless the native float step covers this tree (the QAT engine's limits; amp: also the fp16 / bf16 forms')."""
-    from .vit import DropPath, VisionTransformer
+    from .vit import DropPath, LayerScale, VisionTransformer
 
     if not isinstance(model, VisionTransformer):
         raise RuntimeError(f"native float step: expected the ViT student tree, got {type(model).__name__}")
@@ -61,8 +61,10 @@ def check_shape(model: nn.Module, amp=False) -> None:
             why.append("dropout != 0")
             break
     for b in model.blocks:
-        if not all(isinstance(getattr(b, n), nn.Identity) for n in ("ls1", "ls2")):
-            why.append("layer scale")
+        # LayerScale: this package's module (its gamma travels to the residual kernels, which also form its gradient), or none - both branches alike
+        kinds = {type(getattr(b, n)) for n in ("ls1", "ls2")}
+        if not (kinds == {nn.Identity} or (kinds == {LayerScale} and not (b.ls1.inplace or b.ls2.inplace))):
+            why.append("ls1 / ls2 are neither both Identity nor both qat_vit_amd.LayerScale (inplace=False)")
             break
     for b in model.blocks:   # stochastic depth: this package's DropPath (its multipliers travel to the residual kernels), or none
         if not all(isinstance(getattr(b, n), (nn.Identity, DropPath)) for n in ("drop_path1", "drop_path2")):
@@ -132,6 +134,10 @@ class FloatStudentEngine:
         self.lib = native.lib()
         self.params = native.vit_params(model)
         dev = self.params[0].device
+        # LayerScale: the 2 * depth gammas behind the parameters of the C ABI, bound to a form's workspace with qatvit_float_student_set_layer_scale
+        self.n_abi = len(self.params)
+        self.ls = native.LayerScaleBinding(model, dev)
+        self.params = self.params + self.ls.gammas
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or not p.is_cuda:
                 raise RuntimeError("native float step: the parameters must be contiguous fp32 tensors on one CUDA device")
@@ -178,7 +184,10 @@ class FloatStudentEngine:
         c = self.cfg_for(images.shape[0])
         form.reserve(c, self.device)
         # drop-path: filled here, read by this forward and by its backward (the binding stays until the next forward of this form)
-        self.drop.bind("qatvit_float_student_set_drop_path", c, form.workspace, self.drop.step(c.batch, form.capacity, round_to=None if form is self.fp32 else form.dtype))
+        # (with LayerScale the branch is an fp32 tensor when DropPath meets it - 16-bit branch times fp32 gamma - so the multipliers stay fp32 in every form)
+        self.drop.bind("qatvit_float_student_set_drop_path", c, form.workspace,
+                       self.drop.step(c.batch, form.capacity, round_to=None if form is self.fp32 or self.ls else form.dtype))
+        self.ls.bind_float(c, form.workspace)
         logits = torch.empty(c.batch, c.num_classes, dtype=form.dtype, device=self.device)
         self.generation += 1
         form.call("forward", ctypes.byref(c), self._ptr_params, images.data_ptr(), logits.data_ptr())
@@ -189,6 +198,7 @@ class FloatStudentEngine:
         c = self.cfg_for(batch)
         dlogits = dlogits.to(form.dtype).contiguous()
         _, views, gptr = native.flat_grad_buffers(self.params, self._grad_offsets, self.grad_numel)
+        self.ls.bind_float(c, form.workspace, views[self.n_abi:])
         form.call("backward", ctypes.byref(c), self._ptr_params, dlogits.data_ptr(), gptr)
         return views
 

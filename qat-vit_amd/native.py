@@ -78,6 +78,9 @@ SIGNATURES = {
     "qatvit_student_dy16_set_mirror": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "qatvit_student_set_drop_path": (c_int, [c_void_p, c_void_p, c_void_p]),
     "qatvit_float_student_set_drop_path": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "qatvit_student_set_layer_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "qatvit_float_student_set_layer_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "qatvit_float_student_layer_scale_bytes": (c_int64, [c_void_p]),
     "qatvit_teacher_workspace_bytes": (c_int64, [c_void_p]),
     "qatvit_teacher_forward": (c_int, [c_void_p] * 8),
     "qatvit_teacher_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -301,6 +304,56 @@ class DropPathTable:
             self.bound.discard(ws)
         else:
             self.bound.add(ws)
+
+
+class LayerScaleBinding:
+    """The LayerScale gammas of one engine's model (include/qatvit.h, qatvit_student_set_layer_scale): the 2 * depth parameters in branch order, which the
+    engine keeps BEHIND the 8 + 12 * depth parameters of the C ABI, and the host-side binding of their addresses to a step workspace.  A forward binds the
+    gammas alone (and, float forms, the buffer that keeps the branch outputs for the backward); a backward binds them again together with its gradient
+    views - the gradient buffer of a step is allocated by its backward.  Parameter addresses are static, so a captured hipGraph replays them as it is."""
+
+    def __init__(self, model, device):
+        import torch
+        from .vit import layer_scale_params
+
+        self.gammas = layer_scale_params(model)
+        self.device = device
+        for g in self.gammas:
+            if g.dtype != torch.float32 or not g.is_contiguous() or g.device != device:
+                raise RuntimeError("every LayerScale gamma must be a contiguous fp32 tensor on the model's device")
+        self._gptr = (ctypes.c_void_p * len(self.gammas))(*[g.data_ptr() for g in self.gammas]) if self.gammas else None
+        self.saved = None   # the float forms' retained branch outputs (qatvit_float_student_layer_scale_bytes), grown on demand
+
+    def __bool__(self) -> bool:
+        return bool(self.gammas)
+
+    def _grads(self, views):
+        if views is None:
+            return None
+        assert len(views) == len(self.gammas)
+        return (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
+
+    def bind(self, cfg, workspace, grad_views=None) -> None:
+        """The QAT step's workspace.  grad_views: the zeroed gradient views of the gammas (a backward), None: a forward."""
+        if self.gammas:
+            check(lib().qatvit_student_set_layer_scale(ctypes.byref(cfg), workspace.data_ptr(), self._gptr, self._grads(grad_views)), "qatvit_student_set_layer_scale")
+
+    def bind_float(self, cfg, workspace, grad_views=None) -> None:
+        """A float-step workspace of any form; the branch outputs of the forward go to (and its backward reads them from) the engine's one saved buffer."""
+        import torch
+
+        if not self.gammas:
+            return
+        n = lib().qatvit_float_student_layer_scale_bytes(ctypes.byref(cfg))
+        if n <= 0:
+            raise RuntimeError("qatvit_float_student_layer_scale_bytes failed")
+        if self.saved is None or self.saved.numel() < n:
+            if grad_views is not None:
+                raise RuntimeError("LayerScale: the saved-branch buffer of this backward's forward is gone")
+            self.saved = None
+            self.saved = torch.empty(n, dtype=torch.uint8, device=self.device)
+        check(lib().qatvit_float_student_set_layer_scale(ctypes.byref(cfg), workspace.data_ptr(), self._gptr, self._grads(grad_views), self.saved.data_ptr()),
+              "qatvit_float_student_set_layer_scale")
 
 
 def assign_grads(params, grads) -> None:

@@ -107,18 +107,40 @@ class DropPath(nn.Module):
         return f"drop_prob={round(self.drop_prob, 3):0.3f}"
 
 
+class LayerScale(nn.Module):
+    """A learnable per-channel scale on the branch of a residual block - timm's ``LayerScale`` (``init_values=`` of its ViTs; the DeiT-III / BEiT /
+    DINOv2 checkpoints carry it as ``blocks.i.ls1.gamma`` / ``ls2.gamma``): ``gamma = init_values * ones(dim)``, ``forward`` is ``x * gamma``
+    (``x.mul_(gamma)`` with ``inplace``).  ``prepare_qat`` leaves it where it is and gives it no observer, so in the prepared tree it stands behind the
+    activation fake-quant of the proj / fc2 output and in front of ``DropPath``.  On an MI355X the native steps apply ``gamma`` - and form its
+    gradient - in their residual kernels; this ``forward`` is the stock path."""
+
+    def __init__(self, dim: int, init_values: float = 1e-5, inplace: bool = False):
+        super().__init__()
+        self.inplace = bool(inplace)
+        self.gamma = nn.Parameter(init_values * torch.ones(dim))
+
+    def forward(self, x):
+        return x.mul_(self.gamma) if self.inplace else x * self.gamma
+
+    def extra_repr(self):
+        return f"dim={self.gamma.numel()}, inplace={self.inplace}"
+
+
 class Block(nn.Module):
-    def __init__(self, dim: int, num_heads: int, mlp_ratio: float, drop_path: Optional[float] = None):
-        """drop_path: None - no stochastic depth in this model (``nn.Identity``, the tree as it always was); a rate - ``DropPath(rate)`` on
+    def __init__(self, dim: int, num_heads: int, mlp_ratio: float, drop_path: Optional[float] = None, init_values: Optional[float] = None):
+        """init_values: falsy - no LayerScale (``nn.Identity``, the tree as it always was); else ``LayerScale(dim, init_values)`` on both branches.
+        drop_path: None - no stochastic depth in this model (``nn.Identity``, the tree as it always was); a rate - ``DropPath(rate)`` on
         both branches (also for the rate 0.0 of the first block, where timm puts an Identity: it is one in effect, and every branch of the
         model then follows a ``forced_drop_path`` table)."""
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
         self.attn = Attention(dim, num_heads)
-        self.ls1, self.drop_path1 = nn.Identity(), nn.Identity() if drop_path is None else DropPath(drop_path)
+        self.ls1 = LayerScale(dim, init_values) if init_values else nn.Identity()
+        self.drop_path1 = nn.Identity() if drop_path is None else DropPath(drop_path)
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
         self.mlp = Mlp(dim, int(dim * mlp_ratio))
-        self.ls2, self.drop_path2 = nn.Identity(), nn.Identity() if drop_path is None else DropPath(drop_path)
+        self.ls2 = LayerScale(dim, init_values) if init_values else nn.Identity()
+        self.drop_path2 = nn.Identity() if drop_path is None else DropPath(drop_path)
 
     def forward(self, x):
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
@@ -129,8 +151,10 @@ class VisionTransformer(nn.Module):
     """``global_pool='token'``, ``class_token=True``, no dist token, ``fc_norm`` identity."""
 
     def __init__(self, embed_dim=384, depth=12, num_heads=6, num_classes=10, img_size=224, patch_size=16,
-                 in_chans=3, mlp_ratio=4.0, drop_path_rate=0.0):
-        """drop_path_rate: stochastic depth by timm's linear rule - block i drops each of its two branches with probability
+                 in_chans=3, mlp_ratio=4.0, drop_path_rate=0.0, init_values=None):
+        """init_values: LayerScale as in timm - a falsy value builds the tree without it (``ls1`` / ``ls2`` stay ``nn.Identity``: the same ``state_dict``
+        keys as ever); otherwise every block gets ``LayerScale(embed_dim, init_values)`` on both branches (keys ``blocks.i.ls1.gamma``, ``blocks.i.ls2.gamma``).
+        drop_path_rate: stochastic depth by timm's linear rule - block i drops each of its two branches with probability
         ``torch.linspace(0, drop_path_rate, depth)[i]``; 0 builds the tree without any ``DropPath`` module."""
         super().__init__()
         self.embed_dim = self.num_features = embed_dim
@@ -143,7 +167,7 @@ class VisionTransformer(nn.Module):
         if not 0.0 <= drop_path_rate < 1.0:
             raise ValueError(f"drop_path_rate {drop_path_rate}: expected a probability in [0, 1)")
         rates = [r.item() for r in torch.linspace(0, drop_path_rate, depth)] if drop_path_rate > 0 else [None] * depth
-        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio, rates[i]) for i in range(depth)])
+        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio, rates[i], init_values) for i in range(depth)])
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
         self.fc_norm = nn.Identity()
         self.head_drop = nn.Dropout(0.0)
@@ -178,7 +202,18 @@ def _native_teacher_ok(m: "VisionTransformer") -> bool:
     """Shapes the native teacher covers, and an un-prepared (float) tree."""
     return (m.embed_dim % 128 == 0 and m.embed_dim <= 768 and type(m.head) is nn.Linear and type(m.patch_embed.proj) is nn.Conv2d
             and m.blocks[0].mlp.fc1.weight.shape[0] % 128 == 0 and m.blocks[0].attn.head_dim in (32, 64) and m.patch_embed.num_patches < 224
-            and x_dtype_ok(m))
+            and x_dtype_ok(m) and not layer_scale_params(m))   # (a LayerScale teacher: the stock module forward)
+
+
+def layer_scale_params(model: "VisionTransformer") -> list:
+    """The 2 * depth LayerScale gammas in branch order (row 2 i = block i's ``ls1``, 2 i + 1 = its ``ls2``), [] for a tree without LayerScale; a tree
+    with LayerScale on some branches only, or a foreign module in its place, is refused."""
+    mods = [m for b in model.blocks for m in (b.ls1, b.ls2)]
+    if all(isinstance(m, nn.Identity) for m in mods):
+        return []
+    if not all(type(m) is LayerScale and not m.inplace for m in mods):
+        raise RuntimeError("ls1 / ls2: expected nn.Identity on every branch or qat_vit_amd.LayerScale (inplace=False) on every branch")
+    return [m.gamma for m in mods]
 
 
 def x_dtype_ok(m) -> bool:
