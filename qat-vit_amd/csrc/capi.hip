@@ -479,49 +479,58 @@ int qatvit_image_table(const float* mean_host, const float* std_host, float* tab
     return 0;
 }
 
+// The eight batch entries: each fills an ImageBatch (qv_kernels.h) with its own arguments and runs it.  The part of the record that all of them have:
+static ImageBatch image_request(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* tab,
+                                const float* table, float* out) {
+    ImageBatch r;
+    r.data = data, r.index = index, r.B = B, r.N = N, r.S = S, r.D = D, r.tab = tab, r.table = table, r.out = out;
+    return r;
+}
+
+// Every argument check, once; who = the entry that was called.  no_rrc = what an entry of the window family says of the call without window records,
+// which it refuses; nullptr in the other family, the one with padding_mode and fill.  A record pointer that is null is aligned.
+static int image_request_ok(const char* who, const ImageBatch& r, const char* no_rrc) {
+    QV_CHECK_ARG(r.data && r.tab && r.table && r.out, "%s: null pointer argument", who);
+    QV_CHECK_ARG(!no_rrc || r.rrc, "%s: rrc is NULL (%s)", who, no_rrc);
+    if (image_shape_ok(who, r.S, r.D)) return 1;
+    QV_CHECK_ARG(r.B >= 1 && r.B <= 65535 && r.N >= 1, "%s: batch %d must be 1 .. 65535 and the data set (%d images) not empty", who, r.B, r.N);
+    QV_CHECK_ARG(r.index || r.B <= r.N, "%s: batch %d of a data set of %d images needs an index", who, r.B, r.N);
+    if (!no_rrc) {
+        QV_CHECK_ARG(r.padding_mode == 0 || r.padding_mode == 1, "%s: unknown padding_mode %d (0 = constant, 1 = reflect)", who, r.padding_mode);
+        QV_CHECK_ARG(r.fill >= 0 && r.fill <= 255, "%s: fill %d is outside 0 .. 255", who, r.fill);
+    }
+    const uintptr_t words = (uintptr_t)r.tab | (uintptr_t)r.table | (uintptr_t)r.aug | (uintptr_t)r.rrc | (uintptr_t)r.mix | (uintptr_t)r.erase |
+                            (uintptr_t)r.color | (uintptr_t)r.sums;
+    QV_CHECK_ARG(((uintptr_t)r.out & 15) == 0 && (words & 3) == 0, "%s: misaligned pointer", who);
+    return 0;
+}
+
+// the check, the launch (which refuses a form's LDS request before any HIP call, under the form's own name), the launch check
+static int image_run(const char* who, const ImageBatch& r, void* stream, const char* no_rrc = nullptr) {
+    if (image_request_ok(who, r, no_rrc)) return 1;
+    if (int rc = launch_image_batch(r, (hipStream_t)stream)) return rc;
+    QV_CHECK_LAUNCH(who);
+    return 0;
+}
+
 int qatvit_image_batch(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                        const float* table, float* out, void* stream) {
-    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch: null pointer argument");
-    if (image_shape_ok("qatvit_image_batch", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0, "qatvit_image_batch: misaligned pointer");
-    launch_image_batch(data, index, B, N, S, D, coeffs, table, out, (hipStream_t)stream);
-    QV_CHECK_LAUNCH("qatvit_image_batch");
-    return 0;
+    return image_run("qatvit_image_batch", image_request(data, index, B, N, S, D, coeffs, table, out), stream);
 }
 
 int qatvit_image_batch_aug(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                            const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, float* out, void* stream) {
-    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch_aug: null pointer argument");
-    if (image_shape_ok("qatvit_image_batch_aug", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_aug: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_aug: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(padding_mode == 0 || padding_mode == 1, "qatvit_image_batch_aug: unknown padding_mode %d (0 = constant, 1 = reflect)", padding_mode);
-    QV_CHECK_ARG(fill >= 0 && fill <= 255, "qatvit_image_batch_aug: fill %d is outside 0 .. 255", fill);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)aug & 3) == 0,
-                 "qatvit_image_batch_aug: misaligned pointer");
-    launch_image_batch_aug(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, out, (hipStream_t)stream);
-    QV_CHECK_LAUNCH("qatvit_image_batch_aug");
-    return 0;
+    ImageBatch r = image_request(data, index, B, N, S, D, coeffs, table, out);
+    r.aug = aug, r.padding_mode = padding_mode, r.fill = fill;
+    return image_run("qatvit_image_batch_aug", r, stream);
 }
 
 int qatvit_image_batch_mix(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                            const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix, float* out,
                            void* stream) {
-    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch_mix: null pointer argument");
-    if (image_shape_ok("qatvit_image_batch_mix", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_mix: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_mix: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(padding_mode == 0 || padding_mode == 1, "qatvit_image_batch_mix: unknown padding_mode %d (0 = constant, 1 = reflect)", padding_mode);
-    QV_CHECK_ARG(fill >= 0 && fill <= 255, "qatvit_image_batch_mix: fill %d is outside 0 .. 255", fill);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)aug & 3) == 0 &&
-                     ((uintptr_t)mix & 3) == 0,
-                 "qatvit_image_batch_mix: misaligned pointer");
-    // the shape's LDS request is checked here, before any HIP call
-    if (launch_image_batch_mix(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, out, (hipStream_t)stream)) return 1;
-    QV_CHECK_LAUNCH("qatvit_image_batch_mix");
-    return 0;
+    ImageBatch r = image_request(data, index, B, N, S, D, coeffs, table, out);
+    r.aug = aug, r.padding_mode = padding_mode, r.fill = fill, r.mix = mix;
+    return image_run("qatvit_image_batch_mix", r, stream);
 }
 
 int qatvit_image_resize_coeffs_windows(int32_t src, int32_t dst, int32_t* out_host) {
@@ -532,92 +541,40 @@ int qatvit_image_resize_coeffs_windows(int32_t src, int32_t dst, int32_t* out_ho
 
 int qatvit_image_batch_rrc(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
                            const float* table, const int32_t* rrc, const int32_t* mix, float* out, void* stream) {
-    QV_CHECK_ARG(data && windows && table && out, "qatvit_image_batch_rrc: null pointer argument");
-    QV_CHECK_ARG(rrc, "qatvit_image_batch_rrc: rrc is NULL (the call without records is qatvit_image_batch or qatvit_image_batch_mix)");
-    if (image_shape_ok("qatvit_image_batch_rrc", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_rrc: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_rrc: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)windows & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)rrc & 3) == 0 &&
-                     ((uintptr_t)mix & 3) == 0,
-                 "qatvit_image_batch_rrc: misaligned pointer");
-    // the shape's LDS request is checked here, before any HIP call
-    if (launch_image_batch_rrc(data, index, B, N, S, D, windows, table, rrc, mix, out, (hipStream_t)stream)) return 1;
-    QV_CHECK_LAUNCH("qatvit_image_batch_rrc");
-    return 0;
+    ImageBatch r = image_request(data, index, B, N, S, D, windows, table, out);
+    r.rrc = rrc, r.mix = mix;
+    return image_run("qatvit_image_batch_rrc", r, stream, "the call without records is qatvit_image_batch or qatvit_image_batch_mix");
 }
 
 int qatvit_image_batch_erase(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                              const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix,
                              const int32_t* erase, float* out, void* stream) {
-    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch_erase: null pointer argument");
-    if (image_shape_ok("qatvit_image_batch_erase", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_erase: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_erase: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(padding_mode == 0 || padding_mode == 1, "qatvit_image_batch_erase: unknown padding_mode %d (0 = constant, 1 = reflect)", padding_mode);
-    QV_CHECK_ARG(fill >= 0 && fill <= 255, "qatvit_image_batch_erase: fill %d is outside 0 .. 255", fill);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)aug & 3) == 0 &&
-                     ((uintptr_t)mix & 3) == 0 && ((uintptr_t)erase & 3) == 0,
-                 "qatvit_image_batch_erase: misaligned pointer");
-    // the shape's LDS request is checked here, before any HIP call
-    if (launch_image_batch_erase(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, erase, out, (hipStream_t)stream)) return 1;
-    QV_CHECK_LAUNCH("qatvit_image_batch_erase");
-    return 0;
+    ImageBatch r = image_request(data, index, B, N, S, D, coeffs, table, out);
+    r.aug = aug, r.padding_mode = padding_mode, r.fill = fill, r.mix = mix, r.erase = erase;
+    return image_run("qatvit_image_batch_erase", r, stream);
 }
 
 int qatvit_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
                                  const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, void* stream) {
-    QV_CHECK_ARG(data && windows && table && out, "qatvit_image_batch_rrc_erase: null pointer argument");
-    QV_CHECK_ARG(rrc, "qatvit_image_batch_rrc_erase: rrc is NULL (the call without window records is qatvit_image_batch_erase)");
-    if (image_shape_ok("qatvit_image_batch_rrc_erase", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_rrc_erase: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B,
-                 N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_rrc_erase: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)windows & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)rrc & 3) == 0 &&
-                     ((uintptr_t)mix & 3) == 0 && ((uintptr_t)erase & 3) == 0,
-                 "qatvit_image_batch_rrc_erase: misaligned pointer");
-    // the shape's LDS request is checked here, before any HIP call
-    if (launch_image_batch_rrc_erase(data, index, B, N, S, D, windows, table, rrc, mix, erase, out, (hipStream_t)stream)) return 1;
-    QV_CHECK_LAUNCH("qatvit_image_batch_rrc_erase");
-    return 0;
+    ImageBatch r = image_request(data, index, B, N, S, D, windows, table, out);
+    r.rrc = rrc, r.mix = mix, r.erase = erase;
+    return image_run("qatvit_image_batch_rrc_erase", r, stream, "the call without window records is qatvit_image_batch_erase");
 }
 
 int qatvit_image_batch_color(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
                              const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix,
                              const int32_t* erase, const int32_t* color, uint32_t* sums, float* out, void* stream) {
-    QV_CHECK_ARG(data && coeffs && table && out, "qatvit_image_batch_color: null pointer argument");
-    if (image_shape_ok("qatvit_image_batch_color", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_color: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B, N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_color: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(padding_mode == 0 || padding_mode == 1, "qatvit_image_batch_color: unknown padding_mode %d (0 = constant, 1 = reflect)", padding_mode);
-    QV_CHECK_ARG(fill >= 0 && fill <= 255, "qatvit_image_batch_color: fill %d is outside 0 .. 255", fill);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)coeffs & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)aug & 3) == 0 &&
-                     ((uintptr_t)mix & 3) == 0 && ((uintptr_t)erase & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)sums & 3) == 0,
-                 "qatvit_image_batch_color: misaligned pointer");
-    // the shape's LDS request is checked here, before any HIP call
-    if (int rc = launch_image_batch_color(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, erase, color, sums, out,
-                                          (hipStream_t)stream))
-        return rc;
-    QV_CHECK_LAUNCH("qatvit_image_batch_color");
-    return 0;
+    ImageBatch r = image_request(data, index, B, N, S, D, coeffs, table, out);
+    r.aug = aug, r.padding_mode = padding_mode, r.fill = fill, r.mix = mix, r.erase = erase, r.color = color, r.sums = sums;
+    return image_run("qatvit_image_batch_color", r, stream);
 }
 
 int qatvit_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
                                  const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color,
                                  uint32_t* sums, float* out, void* stream) {
-    QV_CHECK_ARG(data && windows && table && out, "qatvit_image_batch_rrc_color: null pointer argument");
-    QV_CHECK_ARG(rrc, "qatvit_image_batch_rrc_color: rrc is NULL (the call without window records is qatvit_image_batch_color)");
-    if (image_shape_ok("qatvit_image_batch_rrc_color", S, D)) return 1;
-    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "qatvit_image_batch_rrc_color: batch %d must be 1 .. 65535 and the data set (%d images) not empty", B,
-                 N);
-    QV_CHECK_ARG(index || B <= N, "qatvit_image_batch_rrc_color: batch %d of a data set of %d images needs an index", B, N);
-    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)windows & 3) == 0 && ((uintptr_t)table & 3) == 0 && ((uintptr_t)rrc & 3) == 0 &&
-                     ((uintptr_t)mix & 3) == 0 && ((uintptr_t)erase & 3) == 0 && ((uintptr_t)color & 3) == 0 && ((uintptr_t)sums & 3) == 0,
-                 "qatvit_image_batch_rrc_color: misaligned pointer");
-    // the shape's LDS request is checked here, before any HIP call
-    if (int rc = launch_image_batch_rrc_color(data, index, B, N, S, D, windows, table, rrc, mix, erase, color, sums, out, (hipStream_t)stream))
-        return rc;
-    QV_CHECK_LAUNCH("qatvit_image_batch_rrc_color");
-    return 0;
+    ImageBatch r = image_request(data, index, B, N, S, D, windows, table, out);
+    r.rrc = rrc, r.mix = mix, r.erase = erase, r.color = color, r.sums = sums;
+    return image_run("qatvit_image_batch_rrc_color", r, stream, "the call without window records is qatvit_image_batch_color");
 }
 
 int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {

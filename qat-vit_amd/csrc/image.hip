@@ -294,270 +294,119 @@ __device__ __forceinline__ void img_vertical4(const uint32_t* plane, int D4, int
     }
 }
 
-// the kernel, once per form (image_kernel.h)
-#define QV_IMAGE_COLOR 0
-#define QV_IMAGE_ERASE 0
-#define QV_IMAGE_RRC 0
-#define QV_IMAGE_MIX 0
-#define QV_IMAGE_AUG 0
+// the kernel, once per form (image_kernel.h): every inclusion states the kernel's name and all five switches
+//                    (name,                        AUG, MIX, RRC, ERASE, COLOR)
+#define QV_IMAGE_FORM (k_image_batch,                 0,   0,   0,   0,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#define QV_IMAGE_AUG 1
+#define QV_IMAGE_FORM (k_image_batch_aug,             1,   0,   0,   0,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_MIX
-#define QV_IMAGE_MIX 1
+#define QV_IMAGE_FORM (k_image_batch_mix,             1,   1,   0,   0,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_MIX
-#undef QV_IMAGE_RRC
-#define QV_IMAGE_RRC 1
-#define QV_IMAGE_AUG 0
-#define QV_IMAGE_MIX 0
+#define QV_IMAGE_FORM (k_image_batch_rrc,             0,   0,   1,   0,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_MIX
-#define QV_IMAGE_MIX 1
+#define QV_IMAGE_FORM (k_image_batch_rrc_mix,         0,   1,   1,   0,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_MIX
-#undef QV_IMAGE_RRC
-// the four erasing forms: aug (which also serves the call without words), mix, rrc, rrc-mix
-#undef QV_IMAGE_ERASE
-#define QV_IMAGE_ERASE 1
-#define QV_IMAGE_RRC 0
-#define QV_IMAGE_AUG 1
-#define QV_IMAGE_MIX 0
+// the four erasing forms; the aug form also serves the call without aug words
+#define QV_IMAGE_FORM (k_image_batch_aug_erase,       1,   0,   0,   1,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_MIX
-#define QV_IMAGE_MIX 1
+#define QV_IMAGE_FORM (k_image_batch_mix_erase,       1,   1,   0,   1,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_MIX
-#undef QV_IMAGE_RRC
-#define QV_IMAGE_RRC 1
-#define QV_IMAGE_AUG 0
-#define QV_IMAGE_MIX 0
+#define QV_IMAGE_FORM (k_image_batch_rrc_erase,       0,   0,   1,   1,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_MIX
-#define QV_IMAGE_MIX 1
+#define QV_IMAGE_FORM (k_image_batch_rrc_mix_erase,   0,   1,   1,   1,   0)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_MIX
-#undef QV_IMAGE_RRC
 // the four colour forms (the erasing forms with a colour record per side; erase == NULL: no boxes), then the two statistics forms
-#undef QV_IMAGE_COLOR
-#define QV_IMAGE_COLOR 1
-#define QV_IMAGE_RRC 0
-#define QV_IMAGE_AUG 1
-#define QV_IMAGE_MIX 0
+#define QV_IMAGE_FORM (k_image_batch_aug_color,       1,   0,   0,   1,   1)
 #include "image_kernel.h"
-#undef QV_IMAGE_MIX
-#define QV_IMAGE_MIX 1
+#define QV_IMAGE_FORM (k_image_batch_mix_color,       1,   1,   0,   1,   1)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_MIX
-#undef QV_IMAGE_RRC
-#define QV_IMAGE_RRC 1
-#define QV_IMAGE_AUG 0
-#define QV_IMAGE_MIX 0
+#define QV_IMAGE_FORM (k_image_batch_rrc_color,       0,   0,   1,   1,   1)
 #include "image_kernel.h"
-#undef QV_IMAGE_MIX
-#define QV_IMAGE_MIX 1
+#define QV_IMAGE_FORM (k_image_batch_rrc_mix_color,   0,   1,   1,   1,   1)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_MIX
-#undef QV_IMAGE_RRC
-#undef QV_IMAGE_COLOR
-#define QV_IMAGE_COLOR 2
-#define QV_IMAGE_RRC 0
-#define QV_IMAGE_AUG 1
-#define QV_IMAGE_MIX 0
+#define QV_IMAGE_FORM (k_image_stat_aug,              1,   0,   0,   1,   2)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_RRC
-#define QV_IMAGE_RRC 1
-#define QV_IMAGE_AUG 0
+#define QV_IMAGE_FORM (k_image_stat_rrc,              0,   0,   1,   1,   2)
 #include "image_kernel.h"
-#undef QV_IMAGE_AUG
-#undef QV_IMAGE_MIX
-#undef QV_IMAGE_RRC
-#undef QV_IMAGE_COLOR
-#undef QV_IMAGE_ERASE
 
-int64_t image_lds_bytes(int S, int D) {
+// One plane set, or the partner's planes behind the sample's (mixed); the window forms keep, behind that on the next 16 bytes, the band's entries of
+// the row table per side (one side, or two with mix records)
+int64_t image_lds_bytes(int S, int D, bool mixed, bool rrc) {
     const int mr = image_max_rows(S, D);
-    return (int64_t)D * (1 + kImgTaps) * 4 + 768 * 4 + ((mr * S * 3 + 15) & ~15) + (int64_t)mr * 3 * D;
+    const int64_t base = (int64_t)D * (1 + kImgTaps) * 4 + 768 * 4 + ((mr * S * 3 + 15) & ~15) + (int64_t)(mixed ? 2 : 1) * mr * 3 * D;
+    return rrc ? ((base + 15) & ~(int64_t)15) + (int64_t)(mixed ? 2 : 1) * kImgBand * (1 + kImgTaps) * 4 : base;
 }
 
-// the mix kernel keeps the partner's planes behind the sample's
-int64_t image_mix_lds_bytes(int S, int D) { return image_lds_bytes(S, D) + (int64_t)image_max_rows(S, D) * 3 * D; }
+// The forms.  The erase and colour records add nothing to LDS, so a form's request is that of its family with or without mix, and `who`, the name
+// in its refusal, is the narrowest C entry that serves the records present.  The window forms are always checked, the others only with mix.
+enum ImageForm { kImgPlain, kImgAug, kImgMix, kImgAugErase, kImgMixErase, kImgAugColor, kImgMixColor,
+                 kImgRrc, kImgRrcMix, kImgRrcErase, kImgRrcMixErase, kImgRrcColor, kImgRrcMixColor };
+static const struct { const char* who; bool mixed, rrc; } kImageForms[] = {
+    {"qatvit_image_batch", false, false},           {"qatvit_image_batch_aug", false, false},       {"qatvit_image_batch_mix", true, false},
+    {"qatvit_image_batch_erase", false, false},     {"qatvit_image_batch_erase", true, false},      {"qatvit_image_batch_color", false, false},
+    {"qatvit_image_batch_color", true, false},      {"qatvit_image_batch_rrc", false, true},        {"qatvit_image_batch_rrc", true, true},
+    {"qatvit_image_batch_rrc_erase", false, true},  {"qatvit_image_batch_rrc_erase", true, true},   {"qatvit_image_batch_rrc_color", false, true},
+    {"qatvit_image_batch_rrc_color", true, true}};
+static_assert(sizeof(kImageForms) / sizeof(kImageForms[0]) == kImgRrcMixColor + 1, "one row per form, in the enum's order");
 
-// the rrc forms keep, behind that on the next 16 bytes, the band's entries of the row table per side (one side, or two with mix records)
-int64_t image_rrc_lds_bytes(int S, int D, int mixed) {
-    const int64_t base = mixed ? image_mix_lds_bytes(S, D) : image_lds_bytes(S, D);
-    return ((base + 15) & ~(int64_t)15) + (int64_t)(mixed ? 2 : 1) * kImgBand * (1 + kImgTaps) * 4;
+// per family: no records, erase, colour (which takes erase as it comes), each without and with mix, as the enum lists them
+static ImageForm image_form(const ImageBatch& r) {
+    const int records = r.color ? 2 : (r.erase ? 1 : 0), mixed = r.mix != nullptr;
+    if (r.rrc) return ImageForm(kImgRrc + 2 * records + mixed);
+    if (records) return ImageForm(kImgAugErase + 2 * (records - 1) + mixed);
+    return mixed ? kImgMix : (r.aug ? kImgAug : kImgPlain);
 }
 
-int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table, float* out,
-                       hipStream_t st) {
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    auto kern = D == 224 ? k_image_batch<224> : k_image_batch<0>;
-    hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)image_lds_bytes(S, D), st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out);
-    return 0;
+// the one launch site: the grid, the constant-D choice and the head that every kernel takes
+template <typename K, typename... Tail>
+static void image_launch(const ImageBatch& r, K k224, K k0, int64_t lds, hipStream_t st, Tail... tail) {
+    const dim3 grid((r.D + kImgBand - 1) / kImgBand, r.B);
+    hipLaunchKernelGGL(r.D == 224 ? k224 : k0, grid, dim3(kImgThreads), (size_t)lds, st, r.data, r.index, r.N, r.S, r.D, image_max_rows(r.S, r.D), r.tab,
+                       tail...);
 }
+#define QV_IMAGE_K(name) name<224>, name<0>
 
-int launch_image_batch_aug(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                           const int32_t* aug, int padding_mode, int fill, float* out, hipStream_t st) {
-    if (!aug) return launch_image_batch(data, index, B, N, S, D, coeffs, table, out, st);
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    auto kern = D == 224 ? k_image_batch_aug<224> : k_image_batch_aug<0>;
-    hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)image_lds_bytes(S, D), st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out,
-                       aug, padding_mode, fill);
-    return 0;
-}
-
-int launch_image_batch_mix(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                           const int32_t* aug, int padding_mode, int fill, const int32_t* mix, float* out, hipStream_t st) {
-    if (!mix) return launch_image_batch_aug(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, out, st);
-    const int64_t lds = image_mix_lds_bytes(S, D);
-    if (lds > kImgMixMaxLds) {
-        set_error("qatvit_image_batch_mix: source %d -> output %d needs %lld bytes of LDS for two plane sets, more than %d", S, D, (long long)lds,
-                  kImgMixMaxLds);
+int launch_image_batch(const ImageBatch& r, hipStream_t st) {
+    const ImageForm form = image_form(r);
+    const auto& f = kImageForms[form];
+    const int64_t lds = image_lds_bytes(r.S, r.D, f.mixed, f.rrc);
+    if ((f.rrc || f.mixed) && lds > kImgMixMaxLds) {
+        set_error("%s: source %d -> output %d needs %lld bytes of LDS%s, more than %d", f.who, r.S, r.D, (long long)lds,
+                  f.mixed ? " for two plane sets" : "", kImgMixMaxLds);
         return 1;
     }
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    auto kern = D == 224 ? k_image_batch_mix<224> : k_image_batch_mix<0>;
-    hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug, padding_mode,
-                       fill, mix);
-    return 0;
-}
-
-int launch_image_batch_rrc(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
-                           const int32_t* rrc, const int32_t* mix, float* out, hipStream_t st) {
-    const int64_t lds = image_rrc_lds_bytes(S, D, mix != nullptr);
-    if (lds > kImgMixMaxLds) {
-        set_error("qatvit_image_batch_rrc: source %d -> output %d needs %lld bytes of LDS%s, more than %d", S, D, (long long)lds,
-                  mix ? " for two plane sets" : "", kImgMixMaxLds);
-        return 1;
-    }
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    if (mix) {
-        auto kern = D == 224 ? k_image_batch_rrc_mix<224> : k_image_batch_rrc_mix<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, mix);
-    } else {
-        auto kern = D == 224 ? k_image_batch_rrc<224> : k_image_batch_rrc<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc);
-    }
-    return 0;
-}
-
-// The erase forms keep nothing more in LDS: the requests and their refusals are those of the forms without erase records.
-int launch_image_batch_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st) {
-    if (!erase) return launch_image_batch_mix(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, out, st);
-    const int64_t lds = mix ? image_mix_lds_bytes(S, D) : image_lds_bytes(S, D);
-    if (mix && lds > kImgMixMaxLds) {
-        set_error("qatvit_image_batch_erase: source %d -> output %d needs %lld bytes of LDS for two plane sets, more than %d", S, D, (long long)lds,
-                  kImgMixMaxLds);
-        return 1;
-    }
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    if (mix) {
-        auto kern = D == 224 ? k_image_batch_mix_erase<224> : k_image_batch_mix_erase<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
-                           padding_mode, fill, mix, erase);
-    } else {
-        auto kern = D == 224 ? k_image_batch_aug_erase<224> : k_image_batch_aug_erase<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
-                           padding_mode, fill, erase);
-    }
-    return 0;
-}
-
-int launch_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
-                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st) {
-    if (!erase) return launch_image_batch_rrc(data, index, B, N, S, D, windows, table, rrc, mix, out, st);
-    const int64_t lds = image_rrc_lds_bytes(S, D, mix != nullptr);
-    if (lds > kImgMixMaxLds) {
-        set_error("qatvit_image_batch_rrc_erase: source %d -> output %d needs %lld bytes of LDS%s, more than %d", S, D, (long long)lds,
-                  mix ? " for two plane sets" : "", kImgMixMaxLds);
-        return 1;
-    }
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    if (mix) {
-        auto kern = D == 224 ? k_image_batch_rrc_mix_erase<224> : k_image_batch_rrc_mix_erase<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, mix,
-                           erase);
-    } else {
-        auto kern = D == 224 ? k_image_batch_rrc_erase<224> : k_image_batch_rrc_erase<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, erase);
-    }
-    return 0;
-}
-
-// The colour forms keep nothing more in LDS either (the statistics launch keeps one plane set): the requests and their refusals are those of the
-// forms without colour records.  With sums, the workspace is zeroed and the statistics launch runs first, both on the stream.
-int launch_image_batch_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, const int32_t* color,
-                             uint32_t* sums, float* out, hipStream_t st) {
-    if (!color) return launch_image_batch_erase(data, index, B, N, S, D, coeffs, table, aug, padding_mode, fill, mix, erase, out, st);
-    const int64_t lds = mix ? image_mix_lds_bytes(S, D) : image_lds_bytes(S, D);
-    if (mix && lds > kImgMixMaxLds) {
-        set_error("qatvit_image_batch_color: source %d -> output %d needs %lld bytes of LDS for two plane sets, more than %d", S, D, (long long)lds,
-                  kImgMixMaxLds);
-        return 1;
-    }
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    if (sums) {
-        const hipError_t e = hipMemsetAsync(sums, 0, (size_t)B * sizeof(uint32_t), st);
+    const bool stats = r.color && r.sums;   // the statistics launch in front of a colour form: one plane set, into the zeroed workspace
+    if (stats) {
+        const hipError_t e = hipMemsetAsync(r.sums, 0, (size_t)r.B * sizeof(uint32_t), st);
         if (e != hipSuccess) {
-            set_error("qatvit_image_batch_color: zeroing sums failed: %s", hipGetErrorString(e));
+            set_error("%s: zeroing sums failed: %s", f.who, hipGetErrorString(e));
             return 2;
         }
-        auto stat = D == 224 ? k_image_stat_aug<224> : k_image_stat_aug<0>;
-        hipLaunchKernelGGL(stat, grid, dim3(kImgThreads), (size_t)image_lds_bytes(S, D), st, data, index, N, S, D, image_max_rows(S, D), coeffs, aug,
-                           padding_mode, fill, color, sums);
     }
-    if (mix) {
-        auto kern = D == 224 ? k_image_batch_mix_color<224> : k_image_batch_mix_color<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
-                           padding_mode, fill, mix, erase, color, (const uint32_t*)sums);
-    } else {
-        auto kern = D == 224 ? k_image_batch_aug_color<224> : k_image_batch_aug_color<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), coeffs, table, out, aug,
-                           padding_mode, fill, erase, color, (const uint32_t*)sums);
-    }
-    return 0;
-}
-
-int launch_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
-                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color, uint32_t* sums, float* out,
-                                 hipStream_t st) {
-    if (!color) return launch_image_batch_rrc_erase(data, index, B, N, S, D, windows, table, rrc, mix, erase, out, st);
-    const int64_t lds = image_rrc_lds_bytes(S, D, mix != nullptr);
-    if (lds > kImgMixMaxLds) {
-        set_error("qatvit_image_batch_rrc_color: source %d -> output %d needs %lld bytes of LDS%s, more than %d", S, D, (long long)lds,
-                  mix ? " for two plane sets" : "", kImgMixMaxLds);
-        return 1;
-    }
-    const dim3 grid((D + kImgBand - 1) / kImgBand, B);
-    if (sums) {
-        const hipError_t e = hipMemsetAsync(sums, 0, (size_t)B * sizeof(uint32_t), st);
-        if (e != hipSuccess) {
-            set_error("qatvit_image_batch_rrc_color: zeroing sums failed: %s", hipGetErrorString(e));
-            return 2;
-        }
-        auto stat = D == 224 ? k_image_stat_rrc<224> : k_image_stat_rrc<0>;
-        hipLaunchKernelGGL(stat, grid, dim3(kImgThreads), (size_t)image_rrc_lds_bytes(S, D, 0), st, data, index, N, S, D, image_max_rows(S, D), windows,
-                           rrc, color, sums);
-    }
-    if (mix) {
-        auto kern = D == 224 ? k_image_batch_rrc_mix_color<224> : k_image_batch_rrc_mix_color<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, mix,
-                           erase, color, (const uint32_t*)sums);
-    } else {
-        auto kern = D == 224 ? k_image_batch_rrc_color<224> : k_image_batch_rrc_color<0>;
-        hipLaunchKernelGGL(kern, grid, dim3(kImgThreads), (size_t)lds, st, data, index, N, S, D, image_max_rows(S, D), windows, table, out, rrc, erase,
-                           color, (const uint32_t*)sums);
+    // The compiler emits the kernels in the order in which this text names them, and their labels are numbered in that order: the cases stand in the
+    // order of the launchers this one replaced, so that the machine code stays what it was (profiles/image_request_record_isa_identity.txt).
+    switch (form) {
+    case kImgPlain: image_launch(r, QV_IMAGE_K(k_image_batch), lds, st, r.table, r.out); break;
+    case kImgAug: image_launch(r, QV_IMAGE_K(k_image_batch_aug), lds, st, r.table, r.out, r.aug, r.padding_mode, r.fill); break;
+    case kImgMix: image_launch(r, QV_IMAGE_K(k_image_batch_mix), lds, st, r.table, r.out, r.aug, r.padding_mode, r.fill, r.mix); break;
+    case kImgRrcMix: image_launch(r, QV_IMAGE_K(k_image_batch_rrc_mix), lds, st, r.table, r.out, r.rrc, r.mix); break;
+    case kImgRrc: image_launch(r, QV_IMAGE_K(k_image_batch_rrc), lds, st, r.table, r.out, r.rrc); break;
+    case kImgMixErase: image_launch(r, QV_IMAGE_K(k_image_batch_mix_erase), lds, st, r.table, r.out, r.aug, r.padding_mode, r.fill, r.mix, r.erase); break;
+    case kImgAugErase: image_launch(r, QV_IMAGE_K(k_image_batch_aug_erase), lds, st, r.table, r.out, r.aug, r.padding_mode, r.fill, r.erase); break;
+    case kImgRrcMixErase: image_launch(r, QV_IMAGE_K(k_image_batch_rrc_mix_erase), lds, st, r.table, r.out, r.rrc, r.mix, r.erase); break;
+    case kImgRrcErase: image_launch(r, QV_IMAGE_K(k_image_batch_rrc_erase), lds, st, r.table, r.out, r.rrc, r.erase); break;
+    case kImgMixColor:
+    case kImgAugColor:
+        if (stats) image_launch(r, QV_IMAGE_K(k_image_stat_aug), image_lds_bytes(r.S, r.D, false, false), st, r.aug, r.padding_mode, r.fill, r.color, r.sums);
+        if (f.mixed) image_launch(r, QV_IMAGE_K(k_image_batch_mix_color), lds, st, r.table, r.out, r.aug, r.padding_mode, r.fill, r.mix, r.erase, r.color, r.sums);
+        else image_launch(r, QV_IMAGE_K(k_image_batch_aug_color), lds, st, r.table, r.out, r.aug, r.padding_mode, r.fill, r.erase, r.color, r.sums);
+        break;
+    case kImgRrcMixColor:
+    case kImgRrcColor:
+        if (stats) image_launch(r, QV_IMAGE_K(k_image_stat_rrc), image_lds_bytes(r.S, r.D, false, true), st, r.rrc, r.color, r.sums);
+        if (f.mixed) image_launch(r, QV_IMAGE_K(k_image_batch_rrc_mix_color), lds, st, r.table, r.out, r.rrc, r.mix, r.erase, r.color, r.sums);
+        else image_launch(r, QV_IMAGE_K(k_image_batch_rrc_color), lds, st, r.table, r.out, r.rrc, r.erase, r.color, r.sums);
+        break;
     }
     return 0;
 }

@@ -1,125 +1,73 @@
-// The kernel of image.hip, which includes this text twice: QV_IMAGE_AUG 0 gives k_image_batch<DT>, QV_IMAGE_AUG 1 gives k_image_batch_aug<DT>, whose
-// staged source rows are rows of the augmented image A (include/qatvit.h), fetched through the word aug[b].  Everything behind the staging is the
-// same text for both.  Text, not a shared __device__ function: inlined into two kernels, the common body changed the instruction schedule of
-// k_image_batch<0>, and the non-augmenting kernels are to stay the machine code they were (profiles/augment_bench.txt).  No include guard.
-// QV_IMAGE_AUG 1 with QV_IMAGE_MIX 1 gives k_image_batch_mix<DT>: the staging and the horizontal pass run once for the sample and, where the
-// workgroup's band needs it, once more for the partner of its mix record (include/qatvit.h) into a second plane set; the vertical pass then forms
-// both values of an element and blends or selects them.  QV_IMAGE_MIX must be defined (0 or 1) by the including file.
-// QV_IMAGE_RRC 1 (with QV_IMAGE_AUG 0) gives k_image_batch_rrc<DT> and, with QV_IMAGE_MIX 1, k_image_batch_rrc_mix<DT>: the source of a sample is
-// the window h x w at (top, left) of its record rrc[b] (include/qatvit.h), so every side has its own column table (of w), its own entries of the
-// row table (of h) and its own source rows.  The directives of that switch add text for those two forms only: with QV_IMAGE_RRC 0 the other three
-// kernels are compiled from the token sequence they had (profiles/rrc_bench.txt).  QV_IMAGE_RRC must be defined (0 or 1) by the including file.
-// QV_IMAGE_ERASE 1 gives k_image_batch_aug_erase<DT>, _mix_erase, _rrc_erase and _rrc_mix_erase: the vertical pass replaces the elements inside the box
-// of the side's erase record (include/qatvit.h) right after it has formed them, so what is blended or selected is the erased sample and the erased
-// partner.  The aug form of this switch takes aug == NULL as the zero word.  The directives of the switch add text for those four forms only: with
-// QV_IMAGE_ERASE 0 the five other kernels are compiled from the token sequence they had (profiles/erase_bench.txt).  QV_IMAGE_ERASE must be defined
-// (0 or 1) by the including file.
-// QV_IMAGE_COLOR 1 (with QV_IMAGE_ERASE 1) gives k_image_batch_aug_color<DT>, _mix_color, _rrc_color and _rrc_mix_color: the erasing forms with the
-// colour record of the side (include/qatvit.h) applied to the uint8 pixels between the vertical pass and the value table, so their vertical pass
-// has another item, four pixels in all three channels, and erase == NULL stands for all-zero erase records.  QV_IMAGE_COLOR 2 gives
-// k_image_stat_aug<DT> and k_image_stat_rrc<DT>, the statistics launch in front of them: the same staging and passes, the chain up to the
-// contrast op, and the sum of the luma into sums[b]; no table, no output.  The directives of the switch add text for those six forms only: with
-// QV_IMAGE_COLOR 0 the nine other kernels are compiled from the token sequence they had (profiles/color_bench.txt).  QV_IMAGE_COLOR must be
-// defined (0, 1 or 2) by the including file.
+// The kernel of image.hip, which includes this text once per form: fifteen times, each behind one line
+//     #define QV_IMAGE_FORM (name, AUG, MIX, RRC, ERASE, COLOR)
+// that names the kernel and states all five switches.  This text reads them as QV_IMAGE_NAME and QV_IMAGE_AUG .. QV_IMAGE_COLOR and undefines all of
+// it at its end, so no inclusion inherits anything from the one before.  No include guard.
+//   AUG 1            the staged source rows are rows of the augmented image A (include/qatvit.h), fetched through the word aug[b]; everything behind
+//                    the staging is the same text.  AUG 0, RRC 0 is the plain k_image_batch<DT>.
+//   MIX 1            the staging and the horizontal pass run once for the sample and, where the workgroup's band needs it, once more for the partner of
+//                    its mix record into a second plane set; the vertical pass then forms both values of an element and blends or selects them.
+//   RRC 1 (AUG 0)    the source of a sample is the window h x w at (top, left) of its record rrc[b], so every side has its own column table (of w),
+//                    its own entries of the row table (of h) and its own source rows.
+//   ERASE 1          the vertical pass replaces the elements inside the box of the side's erase record right after it has formed them, so what is
+//                    blended or selected is the erased sample and the erased partner.  The aug form of this switch takes aug == NULL as the zero word.
+//   COLOR 1 (ERASE 1) the erasing forms with the colour record of the side applied to the uint8 pixels between the vertical pass and the value table,
+//                    so their vertical pass has another item, four pixels in all three channels, and erase == NULL stands for all-zero erase records.
+//   COLOR 2          k_image_stat_aug<DT> / k_image_stat_rrc<DT>, the statistics launch in front of the colour forms: the same staging and passes, the
+//                    chain up to the contrast op, and the sum of the luma into sums[b]; no table, no output.
+// The forms built: (AUG, MIX) = (0, 0), (1, 0), (1, 1) without RRC and MIX = 0, 1 with it, each with ERASE = COLOR = 0; the same without the plain one
+// at ERASE 1, COLOR 0 and at ERASE 1, COLOR 1; the two statistics forms.
+// Text, not a shared __device__ function: inlined into two kernels, the common body changed the instruction schedule of k_image_batch<0>, and the
+// older kernels are to stay the machine code they were.  The directives of a switch add text for its own forms only: with the switch at 0 the other
+// kernels are compiled from the token sequence they had (profiles/augment_bench.txt, rrc_bench.txt, erase_bench.txt, color_bench.txt).
 // DT = the output size as a constant (its divisions become multiplications), or 0: taken from D_rt.
+#define QV_IMAGE_PICK(field, form) field form
+#define QV_IMAGE_FIELD_NAME(name, aug, mix, rrc, erase, color) name
+#define QV_IMAGE_FIELD_AUG(name, aug, mix, rrc, erase, color) aug
+#define QV_IMAGE_FIELD_MIX(name, aug, mix, rrc, erase, color) mix
+#define QV_IMAGE_FIELD_RRC(name, aug, mix, rrc, erase, color) rrc
+#define QV_IMAGE_FIELD_ERASE(name, aug, mix, rrc, erase, color) erase
+#define QV_IMAGE_FIELD_COLOR(name, aug, mix, rrc, erase, color) color
+#define QV_IMAGE_NAME QV_IMAGE_PICK(QV_IMAGE_FIELD_NAME, QV_IMAGE_FORM)
+#define QV_IMAGE_AUG QV_IMAGE_PICK(QV_IMAGE_FIELD_AUG, QV_IMAGE_FORM)
+#define QV_IMAGE_MIX QV_IMAGE_PICK(QV_IMAGE_FIELD_MIX, QV_IMAGE_FORM)
+#define QV_IMAGE_RRC QV_IMAGE_PICK(QV_IMAGE_FIELD_RRC, QV_IMAGE_FORM)
+#define QV_IMAGE_ERASE QV_IMAGE_PICK(QV_IMAGE_FIELD_ERASE, QV_IMAGE_FORM)
+#define QV_IMAGE_COLOR QV_IMAGE_PICK(QV_IMAGE_FIELD_COLOR, QV_IMAGE_FORM)
 #if QV_IMAGE_RRC
 #define QV_IMAGE_XLAST xlast   // the last column of the window
 #else
 #define QV_IMAGE_XLAST S - 1
 #endif
+// the signature: one head, then the tail of the source (coeffs or windows) and the tail of the records; the statistics forms have their own tails
 template <int DT>
-#if QV_IMAGE_COLOR == 2
+__global__ __launch_bounds__(kImgThreads) void QV_IMAGE_NAME(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
+                                                             int max_rows,
+#if QV_IMAGE_COLOR == 2 && QV_IMAGE_RRC
+                                                             const int32_t* __restrict__ windows, const int32_t* __restrict__ rrc,
+                                                             const int32_t* __restrict__ color, uint32_t* __restrict__ sums) {
+#elif QV_IMAGE_COLOR == 2
+                                                             const int32_t* __restrict__ coeffs, const int32_t* __restrict__ aug, int reflect, int fill,
+                                                             const int32_t* __restrict__ color, uint32_t* __restrict__ sums) {
+#else
 #if QV_IMAGE_RRC
-__global__ __launch_bounds__(kImgThreads) void k_image_stat_rrc(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
-                                                                int max_rows, const int32_t* __restrict__ windows, const int32_t* __restrict__ rrc,
-                                                                const int32_t* __restrict__ color, uint32_t* __restrict__ sums) {
+                                                             const int32_t* __restrict__ windows, const float* __restrict__ table,
+                                                             float* __restrict__ out, const int32_t* __restrict__ rrc
 #else
-__global__ __launch_bounds__(kImgThreads) void k_image_stat_aug(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
-                                                                int max_rows, const int32_t* __restrict__ coeffs, const int32_t* __restrict__ aug,
-                                                                int reflect, int fill, const int32_t* __restrict__ color,
-                                                                uint32_t* __restrict__ sums) {
+                                                             const int32_t* __restrict__ coeffs, const float* __restrict__ table, float* __restrict__ out
+#if QV_IMAGE_AUG
+                                                             , const int32_t* __restrict__ aug, int reflect, int fill
 #endif
-#elif QV_IMAGE_COLOR
-#if QV_IMAGE_RRC && QV_IMAGE_MIX
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N,
-                                                                           int S, int D_rt, int max_rows, const int32_t* __restrict__ windows,
-                                                                           const float* __restrict__ table, float* __restrict__ out,
-                                                                           const int32_t* __restrict__ rrc, const int32_t* __restrict__ mix,
-                                                                           const int32_t* __restrict__ erase, const int32_t* __restrict__ color,
-                                                                           const uint32_t* __restrict__ sums) {
-#elif QV_IMAGE_RRC
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                       int D_rt, int max_rows, const int32_t* __restrict__ windows,
-                                                                       const float* __restrict__ table, float* __restrict__ out,
-                                                                       const int32_t* __restrict__ rrc, const int32_t* __restrict__ erase,
-                                                                       const int32_t* __restrict__ color, const uint32_t* __restrict__ sums) {
-#elif QV_IMAGE_MIX
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_mix_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
-                                                                       const float* __restrict__ table, float* __restrict__ out,
-                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
-                                                                       const int32_t* __restrict__ mix, const int32_t* __restrict__ erase,
-                                                                       const int32_t* __restrict__ color, const uint32_t* __restrict__ sums) {
-#else
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_aug_color(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
-                                                                       const float* __restrict__ table, float* __restrict__ out,
-                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
-                                                                       const int32_t* __restrict__ erase, const int32_t* __restrict__ color,
-                                                                       const uint32_t* __restrict__ sums) {
 #endif
-#elif QV_IMAGE_ERASE
-#if QV_IMAGE_RRC && QV_IMAGE_MIX
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N,
-                                                                           int S, int D_rt, int max_rows, const int32_t* __restrict__ windows,
-                                                                           const float* __restrict__ table, float* __restrict__ out,
-                                                                           const int32_t* __restrict__ rrc, const int32_t* __restrict__ mix,
-                                                                           const int32_t* __restrict__ erase) {
-#elif QV_IMAGE_RRC
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                       int D_rt, int max_rows, const int32_t* __restrict__ windows,
-                                                                       const float* __restrict__ table, float* __restrict__ out,
-                                                                       const int32_t* __restrict__ rrc, const int32_t* __restrict__ erase) {
-#elif QV_IMAGE_MIX
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_mix_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
-                                                                       const float* __restrict__ table, float* __restrict__ out,
-                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
-                                                                       const int32_t* __restrict__ mix, const int32_t* __restrict__ erase) {
-#else
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_aug_erase(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                       int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
-                                                                       const float* __restrict__ table, float* __restrict__ out,
-                                                                       const int32_t* __restrict__ aug, int reflect, int fill,
-                                                                       const int32_t* __restrict__ erase) {
+#if QV_IMAGE_MIX
+                                                             , const int32_t* __restrict__ mix
 #endif
-#else
-#if QV_IMAGE_RRC && QV_IMAGE_MIX
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc_mix(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                     int D_rt, int max_rows, const int32_t* __restrict__ windows,
-                                                                     const float* __restrict__ table, float* __restrict__ out,
-                                                                     const int32_t* __restrict__ rrc, const int32_t* __restrict__ mix) {
-#elif QV_IMAGE_RRC
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_rrc(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                 int D_rt, int max_rows, const int32_t* __restrict__ windows,
-                                                                 const float* __restrict__ table, float* __restrict__ out,
-                                                                 const int32_t* __restrict__ rrc) {
-#elif QV_IMAGE_MIX
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_mix(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                 int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
-                                                                 const float* __restrict__ table, float* __restrict__ out,
-                                                                 const int32_t* __restrict__ aug, int reflect, int fill,
-                                                                 const int32_t* __restrict__ mix) {
-#elif QV_IMAGE_AUG
-__global__ __launch_bounds__(kImgThreads) void k_image_batch_aug(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S,
-                                                                 int D_rt, int max_rows, const int32_t* __restrict__ coeffs,
-                                                                 const float* __restrict__ table, float* __restrict__ out,
-                                                                 const int32_t* __restrict__ aug, int reflect, int fill) {
-#else
-__global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __restrict__ data, const int64_t* __restrict__ index, int N, int S, int D_rt,
-                                                             int max_rows, const int32_t* __restrict__ coeffs, const float* __restrict__ table,
-                                                             float* __restrict__ out) {
+#if QV_IMAGE_ERASE
+                                                             , const int32_t* __restrict__ erase
 #endif
+#if QV_IMAGE_COLOR
+                                                             , const int32_t* __restrict__ color, const uint32_t* __restrict__ sums
+#endif
+                                                             ) {
 #endif
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int D = DT ? DT : D_rt;
@@ -475,3 +423,10 @@ __global__ __launch_bounds__(kImgThreads) void k_image_batch(const uint8_t* __re
 }
 #endif
 #undef QV_IMAGE_XLAST
+#undef QV_IMAGE_NAME
+#undef QV_IMAGE_AUG
+#undef QV_IMAGE_MIX
+#undef QV_IMAGE_RRC
+#undef QV_IMAGE_ERASE
+#undef QV_IMAGE_COLOR
+#undef QV_IMAGE_FORM

@@ -357,45 +357,32 @@ int launch_fa_embed_bwd(const float* dx, float* dpos, float* dcls, void* dY0_16,
 int launch_fa_inf_rule(float* const* g, const int64_t* n, int count, hipStream_t st);
 // image.hip: the input pipeline.  coeffs = int32 {xmin[D], ntaps[D], coef[D][kImgTaps]} and table = fp32 [3][256], both as the two host functions write them
 constexpr int kImgTaps = 4, kImgBits = 22, kImgBand = 16, kImgMaxD = 384;
+constexpr int kImgMixMaxLds = 64 * 1024;
 int image_resize_coeffs(int src, int dst, int32_t* xmin, int32_t* ntaps, int32_t* coef);   // host only; nonzero + set_error when the kernel's bounds do not hold
 void image_table(const float* mean, const float* stdv, float* table);                      // host only
-int launch_image_batch(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table, float* out,
-                       hipStream_t st);
-// the same with a crop offset and a flip of the source per batch position (aug int32 [B]: oy | ox << 8 | flip << 16; include/qatvit.h); aug == nullptr:
-// launch_image_batch.  padding_mode 0 = constant (fill), 1 = reflect
-int launch_image_batch_aug(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                           const int32_t* aug, int padding_mode, int fill, float* out, hipStream_t st);
-// the same with a partner position, two blend weights and a box per batch position (mix int32 [B][6]; include/qatvit.h); mix == nullptr:
-// launch_image_batch_aug.  Keeps two plane sets in LDS: nonzero + set_error, before any launch, where image_mix_lds_bytes exceeds kImgMixMaxLds
-constexpr int kImgMixMaxLds = 64 * 1024;
-int64_t image_mix_lds_bytes(int S, int D);
-int launch_image_batch_mix(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                           const int32_t* aug, int padding_mode, int fill, const int32_t* mix, float* out, hipStream_t st);
-// the resized crop: the source of batch position b is the window of its record (rrc int32 [B][2]: top | left << 16, h | w << 15 | flip << 30;
-// include/qatvit.h), resampled with the tables of w and h out of windows = int32 [S][6 * D], table n - 1 = image_resize_coeffs(n, D) as coeffs has it
-// (image_resize_coeffs_windows writes them on the host, with image_resize_coeffs' checks).  mix as above, or nullptr.  Nonzero + set_error, before
-// any launch, where image_rrc_lds_bytes exceeds kImgMixMaxLds
-int image_resize_coeffs_windows(int S, int D, int32_t* out);   // host only
-int64_t image_rrc_lds_bytes(int S, int D, int mixed);
-int launch_image_batch_rrc(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
-                           const int32_t* rrc, const int32_t* mix, float* out, hipStream_t st);
-// the same two with an erase box per batch position (erase int32 [B][8]: rows, columns, three fills, mode, a 64-bit noise key; include/qatvit.h),
-// applied to the sample and to its partner before they are mixed.  erase == nullptr: launch_image_batch_mix / launch_image_batch_rrc.  No LDS of
-// their own: the refusals are those of the forms without erase records
-int launch_image_batch_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st);
-int launch_image_batch_rrc_erase(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
-                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, float* out, hipStream_t st);
-// the same two with a colour record per batch position (color int32 [B][4]: jitter ops in order, grayscale, solarize, three factors;
-// include/qatvit.h), applied to the uint8 pixels of the sample and of its partner in front of the value table.  erase == nullptr here: all-zero
-// erase records.  sums uint32 [B] (or nullptr: contrast is the identity): zeroed, then filled by a statistics launch in front of the batch launch,
-// all on st.  color == nullptr: launch_image_batch_erase / launch_image_batch_rrc_erase.  No LDS of their own
-int launch_image_batch_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* coeffs, const float* table,
-                             const int32_t* aug, int padding_mode, int fill, const int32_t* mix, const int32_t* erase, const int32_t* color,
-                             uint32_t* sums, float* out, hipStream_t st);
-int launch_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int B, int N, int S, int D, const int32_t* windows, const float* table,
-                                 const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color, uint32_t* sums, float* out,
-                                 hipStream_t st);
+int image_resize_coeffs_windows(int S, int D, int32_t* out);                               // host only: int32 [S][6 * D], table n - 1 = image_resize_coeffs(n, D)
+// One batch request: out fp32 [B, 3, D, D] from data uint8 [N, S, S, 3] through index int64 [B] (nullptr: image b).  The records are device arrays with one
+// entry per batch position (include/qatvit.h states every word); a null pointer means "no such records", and the records present alone decide the kernel
+// (kImageForms, image.hip).  sums != nullptr with colour records: zeroed, then filled by a statistics launch in front of the batch launch, all on st.
+struct ImageBatch {
+    const uint8_t* data = nullptr;
+    const int64_t* index = nullptr;
+    int B = 0, N = 0, S = 0, D = 0;
+    const int32_t* tab = nullptr;     // coeffs; with rrc, windows (image_resize_coeffs_windows)
+    const float* table = nullptr;
+    const int32_t* aug = nullptr;     // [B]: oy | ox << 8 | flip << 16, a crop offset and a flip of the padded source.  Absent: none (with erase / color: the zero word)
+    int padding_mode = 0, fill = 0;   // of aug: 0 = constant (fill), 1 = reflect
+    const int32_t* rrc = nullptr;     // [B][2]: top | left << 16, h | w << 15 | flip << 30, the source window.  Present: the window family, which has no aug
+    const int32_t* mix = nullptr;     // [B][6]: a partner position, two blend weights and a box.  Present: two plane sets in LDS, refused above kImgMixMaxLds
+    const int32_t* erase = nullptr;   // [B][8]: rows, columns, three fills, mode, a 64-bit noise key, on the sample and on its partner before they are mixed.
+                                      // Absent with color: all-zero records
+    const int32_t* color = nullptr;   // [B][4]: jitter ops in order, grayscale, solarize, three factors, on the uint8 pixels in front of the value table
+    uint32_t* sums = nullptr;         // [B], read with color only: the luma sums of the contrast op.  Absent: contrast is the identity, no statistics launch
+    float* out = nullptr;
+};
+int64_t image_lds_bytes(int S, int D, bool mixed, bool rrc);
+// nonzero + set_error: 1 before any HIP call where the form's LDS request exceeds kImgMixMaxLds (the window forms, and the others with mix), 2 where zeroing sums fails
+int launch_image_batch(const ImageBatch& r, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

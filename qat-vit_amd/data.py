@@ -459,62 +459,27 @@ class GpuResizeNormalize:
             if not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
                     or rrc.device != self.device:
                 raise ValueError(f"rrc must be a contiguous int32 [{B}, {RRC_WORDS}] tensor on {self.device}")
+        if not B:
+            return out
+        # The narrowest entry that takes the records present, and its arguments between D and out.  An entry takes the records in front of its own as
+        # they are, absent ones as NULL; without `contrast` the colour entries get no workspace and no statistics launch runs.
+        opt = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         if color is not None:
-            # the colour entries: every other record may be absent; without `contrast` no workspace is passed and no statistics launch runs
-            if B:
-                opt = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-                sums = self.color_sums(B).data_ptr() if contrast else None
-                with torch.cuda.device(self.device):
-                    if rrc is not None:
-                        native.check(native.lib().qatvit_image_batch_rrc_color(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
-                                                                               self.table.data_ptr(), rrc.data_ptr(), opt(mix), opt(erase),
-                                                                               color.data_ptr(), sums, out.data_ptr(), native.stream_ptr()),
-                                     "qatvit_image_batch_rrc_color")
-                    else:
-                        native.check(native.lib().qatvit_image_batch_color(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(),
-                                                                           self.table.data_ptr(), opt(aug), mode, fill, opt(mix), opt(erase),
-                                                                           color.data_ptr(), sums, out.data_ptr(), native.stream_ptr()),
-                                     "qatvit_image_batch_color")
-            return out
+            level, records = "_color", (opt(erase), color.data_ptr(), self.color_sums(B).data_ptr() if contrast else None)
+        elif erase is not None:
+            level, records = "_erase", (erase.data_ptr(),)
+        else:
+            level, records = "", ()
         if rrc is not None:
-            if B and erase is not None:
-                with torch.cuda.device(self.device):
-                    native.check(native.lib().qatvit_image_batch_rrc_erase(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
-                                                                           self.table.data_ptr(), rrc.data_ptr(),
-                                                                           None if mix is None else mix.data_ptr(), erase.data_ptr(),
-                                                                           out.data_ptr(), native.stream_ptr()), "qatvit_image_batch_rrc_erase")
-                return out
-            if B:
-                with torch.cuda.device(self.device):
-                    native.check(native.lib().qatvit_image_batch_rrc(data_u8.data_ptr(), ip, B, N, S, D, self.window_tables().data_ptr(),
-                                                                     self.table.data_ptr(), rrc.data_ptr(),
-                                                                     None if mix is None else mix.data_ptr(), out.data_ptr(),
-                                                                     native.stream_ptr()), "qatvit_image_batch_rrc")
-            return out
-        if erase is not None:
-            if B:
-                with torch.cuda.device(self.device):
-                    native.check(native.lib().qatvit_image_batch_erase(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(),
-                                                                       self.table.data_ptr(), None if aug is None else aug.data_ptr(), mode, fill,
-                                                                       None if mix is None else mix.data_ptr(), erase.data_ptr(), out.data_ptr(),
-                                                                       native.stream_ptr()), "qatvit_image_batch_erase")
-            return out
-        if mix is not None:
-            if B:
-                with torch.cuda.device(self.device):
-                    native.check(native.lib().qatvit_image_batch_mix(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
-                                                                     None if aug is None else aug.data_ptr(), mode, fill, mix.data_ptr(),
-                                                                     out.data_ptr(), native.stream_ptr()), "qatvit_image_batch_mix")
-            return out
-        if B and aug is not None:
-            with torch.cuda.device(self.device):
-                native.check(native.lib().qatvit_image_batch_aug(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
-                                                                 aug.data_ptr(), mode, fill, out.data_ptr(), native.stream_ptr()),
-                             "qatvit_image_batch_aug")
-        elif B:
-            with torch.cuda.device(self.device):
-                native.check(native.lib().qatvit_image_batch(data_u8.data_ptr(), ip, B, N, S, D, self.coeffs.data_ptr(), self.table.data_ptr(),
-                                                             out.data_ptr(), native.stream_ptr()), "qatvit_image_batch")
+            name, args = "qatvit_image_batch_rrc" + level, (self.window_tables().data_ptr(), self.table.data_ptr(), rrc.data_ptr(), opt(mix)) + records
+        elif level or mix is not None:
+            name, args = "qatvit_image_batch" + (level or "_mix"), (self.coeffs.data_ptr(), self.table.data_ptr(), opt(aug), mode, fill, opt(mix)) + records
+        elif aug is not None:
+            name, args = "qatvit_image_batch_aug", (self.coeffs.data_ptr(), self.table.data_ptr(), aug.data_ptr(), mode, fill)
+        else:
+            name, args = "qatvit_image_batch", (self.coeffs.data_ptr(), self.table.data_ptr())
+        with torch.cuda.device(self.device):
+            native.check(getattr(native.lib(), name)(data_u8.data_ptr(), ip, B, N, S, D, *args, out.data_ptr(), native.stream_ptr()), name)
         return out
 
 
