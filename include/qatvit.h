@@ -278,6 +278,19 @@ int qatvit_attn_backward_live(const float* qkv, const float* qp, int32_t qmin, i
                               int32_t D, const void* O_hi, const void* O_lo, const float* lse, float* delta, const float* dO,
                               void* dqkv_hi, void* dqkv_lo, const float* col_scale, const void* qkv_codes, const void* qkv_mask,
                               int32_t live_q_tiles, int32_t dO_cls, void* stream);
+/* The same backward (full sweep) with the launch form named, so that one process can compare the forms (the library itself chooses by shape and
+ * QATVIT_ATTN_BWD_PIPE).  form 0: one workgroup per (image, head) - at every shape what qatvit_attn_backward launches under QATVIT_ATTN_BWD_PIPE=0;
+ * form 1: the persistent kernel, min(B * H, CU count) workgroups that each walk several heads and fetch the next one under the sweep; form 2: the
+ * same on 5 workgroups (tests).  Forms 1 and 2 exist for head_dim 64, 33..224 tokens and saved codes only: an error elsewhere, nothing is launched.
+ * Every form writes the same bits.  o16_mul / o16_amax (optional, together; fused shapes only): the one-plane output - dqkv_hi is ONE fp16 plane
+ * of value * (*o16_mul), dqkv_lo is not written (may be NULL), max |value| is folded into the QATVIT_DY16_AMAX_SLOTS slots of o16_amax (uint32
+ * bit patterns, QATVIT_DY16_AMAX_STRIDE words apart) with atomicMax. */
+#define QATVIT_DY16_AMAX_SLOTS 8
+#define QATVIT_DY16_AMAX_STRIDE 32
+int qatvit_attn_backward_form(const float* qkv, const float* qp, int32_t qmin, int32_t qmax, int32_t B, int32_t T, int32_t H,
+                              int32_t D, const void* O_hi, const void* O_lo, const float* lse, float* delta, const float* dO,
+                              void* dqkv_hi, void* dqkv_lo, const float* col_scale, const void* qkv_codes, const void* qkv_mask,
+                              const float* o16_mul, uint32_t* o16_amax, int32_t form, void* stream);
 
 /* The class-token rows of a [rows * T, width bytes] tensor (the student pools the class token, so the gradient entering the last block lives in rows
  * b * T only; the one-plane backward runs that block's MLP and proj on those rows - QATVIT_CLS_BWD=0 in the environment: on all rows).

@@ -1217,6 +1217,427 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
     }
 }
 
+// ============================================================================ backward, fused and persistent: the next head fetched under the sweep
+// k_attn_bwd_fused<NKT, O16> (not LIVE) as gridDim.x <= CU count workgroups that each walk the (image, head) items w, w + gridDim.x, ...: per head the same
+// conversion, sweep and epilogue, instruction order and summation order included - the same bits.  What changes is when the global loads are requested: the
+// per-head launch has all 256 resident workgroups stage at the same moment (HBM-paced, MFMAs idle), sweep at the same moment (HBM idle) and store at the same
+// moment; here the loads of the NEXT head are requested as early as there are registers for them and waited for only at the next conversion, and the
+// epilogue's stores stay in flight under that conversion.
+// Two waves per SIMD leave 256 registers per lane, the sweep holds about 230 of them and the conversion all of them, so the 98 registers of a head's loads
+// cannot be in flight under the sweep (requested there, 72 of them spill - and a scratch reload is a vmcnt(0) in front of the loads in flight).  What fits:
+// the first of the four dO / O hi / O lo chunks (kEarly, 24 registers) right behind the conversion; everything else in front of the epilogue's LAST key tile,
+// when the sweep's fragments and half of the accumulators are dead.  The dS image is zeroed once (tile ownership does not change between heads), am16 is
+// published once per workgroup (atomicMax: order-independent).  profiles/attn_bwd_pipe_c2_b256_per_step.txt has the variants that lost.
+template <int NKT, bool O16>
+__global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, const int nitems) {
+    constexpr int HD = 64, NWV = 8;
+    float mul16 = 1.f, am16 = 0.f;
+    if constexpr (O16) mul16 = *p.o16_mul;
+    constexpr int U = (NKT + NWV - 1) / NWV;   // key tiles per wave
+    constexpr int IMG = NKT * 16 * HD * 2, SVQ = NKT * 16 * kSRow, SIMG = 2 * SVQ;
+    constexpr int KK = HD / 32, ND = HD / 16;
+    static_assert(2 * ND == NWV, "one dQ^T tile (16 features x 16 queries of a query pair) per wave");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // (the layout of k_attn_bwd_fused)
+    char* sQt = smem;
+    char* sDh = smem + IMG;
+    char* sDl = smem + 2 * IMG;
+    char* sKt = smem + 3 * IMG;
+    char* sSh = smem + 4 * IMG;
+    char* sSl = sSh + SIMG;
+    float* sLse = reinterpret_cast<float*>(sSl + SIMG);
+    float* sDlt = sLse + NKT * 16;
+    uint2* sM = reinterpret_cast<uint2*>(sDlt + NKT * 16);
+    float* sCs = reinterpret_cast<float*>(sM + 3 * NKT * 16);
+    const AQP q = make_aqp(p.qp, p.qmin, p.qmax);
+    const int T = p.T, D = p.D, ld = 3 * D;
+    static_assert(NKT * 16 <= NWV * 64, "one softmax constant per thread");
+    const int64_t sl = (int64_t)T * HD;
+    const float coff = q.fqmin - q.zp;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nkt = (T + 15) / 16;
+    int jt[U];
+    bool has[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        jt[u] = wave + u * NWV;
+        has[u] = jt[u] < nkt;
+    }
+    constexpr int CH = HD / 8, TOTAL = NKT * 16 * CH, ITERS = (TOTAL + NWV * 64 - 1) / (NWV * 64);
+    constexpr int kEarly = 1;   // dO / O chunks requested under the sweep
+    static_assert(U == 2 && kEarly <= ITERS, "the rest of the loads goes in front of the second (last) key tile of the epilogue");
+    // one head's loads (the registers of k_attn_bwd_fused's prologue; lse and the column scale raw, converted where they are written to LDS)
+    uint2 vc[U][KK], cq[ITERS], ck[ITERS], mrow[2];
+    float4 da4[ITERS], db4[ITERS];
+    uint4 oh[ITERS], ol[ITERS];
+    float lse_raw, cs_raw;
+    auto load_codes = [&](int item, int tid) {
+        const uint8_t* const cbase = p.codes + (int64_t)item * 3 * sl;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int i = tid + it * NWV * 64, tok = min(i / CH, T - 1), ch = i % CH;   // (branch-free: a padded token reads the last real one)
+            cq[it] = *reinterpret_cast<const uint2*>(cbase + tok * HD + ch * 8);
+            ck[it] = *reinterpret_cast<const uint2*>(cbase + sl + tok * HD + ch * 8);
+        }
+    };
+    auto load_grad = [&](int item, int tid, int it0, int it1) {   // dO, O hi / lo of chunks it0 .. it1 - 1
+        const int b = item / p.H, h = item % p.H;
+        const float* const dOb = p.dO + (int64_t)b * T * D + h * HD;
+        const __bf16* const Ohb = p.O_hi + (int64_t)b * T * D + h * HD;
+        const __bf16* const Olb = p.O_lo + (int64_t)b * T * D + h * HD;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            if (it < it0 || it >= it1) continue;
+            const int i = tid + it * NWV * 64, tok = min(i / CH, T - 1), ch = i % CH;
+            const int64_t off = (int64_t)tok * D + ch * 8;
+            da4[it] = reinterpret_cast<const float4*>(dOb + off)[0];
+            db4[it] = reinterpret_cast<const float4*>(dOb + off)[1];
+            oh[it] = *reinterpret_cast<const uint4*>(Ohb + off);
+            ol[it] = *reinterpret_cast<const uint4*>(Olb + off);
+        }
+    };
+    auto load_small = [&](int item, int tid) {   // the owned V rows' codes, the head's mask rows, lse, column scales
+        const uint8_t* const cbase = p.codes + (int64_t)item * 3 * sl;
+        const uint8_t* const mbase = p.cmask + (int64_t)item * 3 * (sl / 8);
+        const int r = tid & 15, g = (tid & 63) >> 4;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk)
+                vc[u][kk] = *reinterpret_cast<const uint2*>(cbase + 2 * sl + min(16 * jt[u] + r, T - 1) * HD + 32 * kk + 8 * g);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) mrow[k] = reinterpret_cast<const uint2*>(mbase)[min(tid + k * NWV * 64, 3 * T - 1)];
+        lse_raw = p.lse[(int64_t)item * (NKT * 16) + min(tid, NKT * 16 - 1)];   // (the row is NKT * 16 long: in bounds past T too)
+        // (without col_scale: any valid float, replaced by 1.0 at the conversion - a conditional load is merged with its alternative, i.e. waited for, right here)
+        const int cc = min(tid, 3 * HD - 1);
+        cs_raw = *(p.col_scale ? p.col_scale + (cc / HD) * D + (item % p.H) * HD + (cc % HD) : p.qp);
+    };
+    auto load_rest = [&](int item, int tid) {   // what is not requested under the sweep
+        load_small(item, tid);
+        load_codes(item, tid);
+        load_grad(item, tid, kEarly, ITERS);
+    };
+    // The last head requests nothing.  On that path the registers must not keep the current head's values either (the compiler does not see that the loop
+    // ends there: they would be live across the sweep): an empty asm "writes" them.
+    auto drop_codes = [&]() {
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) asm volatile("" : "=v"(cq[it].x), "=v"(cq[it].y), "=v"(ck[it].x), "=v"(ck[it].y));
+    };
+    auto drop_grad = [&](int it0, int it1) {
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            if (it < it0 || it >= it1) continue;
+            asm volatile("" : "=v"(da4[it].x), "=v"(da4[it].y), "=v"(da4[it].z), "=v"(da4[it].w), "=v"(db4[it].x), "=v"(db4[it].y), "=v"(db4[it].z), "=v"(db4[it].w));
+            asm volatile("" : "=v"(oh[it].x), "=v"(oh[it].y), "=v"(oh[it].z), "=v"(oh[it].w), "=v"(ol[it].x), "=v"(ol[it].y), "=v"(ol[it].z), "=v"(ol[it].w));
+        }
+    };
+    auto drop_small = [&]() {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) asm volatile("" : "=v"(vc[u][kk].x), "=v"(vc[u][kk].y));
+        asm volatile("" : "=v"(mrow[0].x), "=v"(mrow[0].y), "=v"(mrow[1].x), "=v"(mrow[1].y), "=v"(lse_raw), "=v"(cs_raw));
+    };
+    for (int i = threadIdx.x; i < 2 * SIMG / 16; i += NWV * 64) reinterpret_cast<uint4*>(sSh)[i] = make_uint4(0u, 0u, 0u, 0u);   // key tiles nobody owns stay zero
+    const int jd = wave & (ND - 1), vq = wave / ND;   // this wave's dQ^T tile of every query pair: features 16 jd .. + 15, queries 16 (2 qs + vq) .. + 15
+    const float c = q.s * q.s * p.softmax_scale, c2 = c * kLog2e;
+    load_grad(blockIdx.x, threadIdx.x, 0, kEarly);
+    load_rest(blockIdx.x, threadIdx.x);
+#pragma unroll 1
+    for (int item = blockIdx.x;;) {
+        const int b = item / p.H, h = item % p.H;
+        // (the thread index behind an empty asm, once per head and once more for the early loads: everything derived from it is then computed inside this
+        //  loop, where it is used - hoisted out of the loop, the sweep's and the epilogue's offsets are live during the conversion and the conversion's during
+        //  the sweep, and neither has a register to spare)
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int lane = tid & 63, r = lane & 15, g = lane >> 4;
+        uint32_t zr = 0u;   // (the zero rows of the images, likewise: as a hoisted 16-byte constant they were the one spill of this kernel)
+        asm volatile("" : "+v"(zr));
+        int krow[U];
+        bool kvalid[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            krow[u] = min(16 * jt[u] + r, T - 1);
+            kvalid[u] = has[u] && 16 * jt[u] + r < T;
+        }
+        // ---- the conversion of k_attn_bwd_fused
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            pin4_in(da4[it]); pin4_in(db4[it]);
+            asm volatile("" ::"v"(oh[it].x), "v"(oh[it].y), "v"(oh[it].z), "v"(oh[it].w), "v"(ol[it].x), "v"(ol[it].y), "v"(ol[it].z), "v"(ol[it].w));
+            asm volatile("" ::"v"(cq[it].x), "v"(cq[it].y), "v"(ck[it].x), "v"(ck[it].y));
+        }
+        if (tid < NKT * 16) sLse[tid] = tid < T ? -lse_raw * kLog2e : -INFINITY;   // (see k_attn_bwd_dkv)
+        if (tid < 3 * HD) sCs[tid] = p.col_scale ? cs_raw : 1.f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (tid + k * NWV * 64 < 3 * T) sM[tid + k * NWV * 64] = mrow[k];
+        float* const gdelta = p.delta ? p.delta + (int64_t)item * (NKT * 16) : nullptr;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int i = tid + it * NWV * 64, tok = i / CH, ch = i % CH;
+            const bool real = tok < T;   // padded token rows are zero in every image
+            const float v[8] = {da4[it].x, da4[it].y, da4[it].z, da4[it].w, db4[it].x, db4[it].y, db4[it].z, db4[it].w};
+            const uint32_t wh[4] = {oh[it].x, oh[it].y, oh[it].z, oh[it].w}, wl[4] = {ol[it].x, ol[it].y, ol[it].z, ol[it].w};
+            float d = 0.f;   // delta = sum_d dO . O over the row: 8 features here, the row's 8 chunks on consecutive lanes
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                d += v[2 * j] * (__builtin_bit_cast(float, wh[j] << 16) + __builtin_bit_cast(float, wl[j] << 16));
+                d += v[2 * j + 1] * (__builtin_bit_cast(float, wh[j] & 0xffff0000u) + __builtin_bit_cast(float, wl[j] & 0xffff0000u));
+            }
+            d += __shfl_xor(d, 1, 64);
+            d += __shfl_xor(d, 2, 64);
+            d += __shfl_xor(d, 4, 64);
+            if (i < TOTAL) {
+                const uint4 z = make_uint4(zr, zr, zr, zr);
+                *reinterpret_cast<uint4*>(sQt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(cq[it], coff)) : z;
+                *reinterpret_cast<uint4*>(sKt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(ck[it], coff)) : z;
+                uint32_t H[4], L[4];
+                split_pair(v[0], v[1], H[0], L[0]); split_pair(v[2], v[3], H[1], L[1]);
+                split_pair(v[4], v[5], H[2], L[2]); split_pair(v[6], v[7], H[3], L[3]);
+                *reinterpret_cast<uint4*>(sDh + tr_off<HD>(tok, ch)) = real ? make_uint4(H[0], H[1], H[2], H[3]) : z;
+                *reinterpret_cast<uint4*>(sDl + tr_off<HD>(tok, ch)) = real ? make_uint4(L[0], L[1], L[2], L[3]) : z;
+                if (ch == 0) {
+                    sDlt[tok] = d * q.inv;
+                    if (real && gdelta) gdelta[tok] = d;
+                }
+            }
+        }
+        bf16x8 vf[U][KK];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) vf[u][kk] = decode8(vc[u][kk], coff);
+        lds_barrier();   // (LDS only: the previous head's dK / dV stores stay in flight)
+        // ---- the next head's loads, into the registers the conversion has freed: waited for behind the epilogue
+        const int next = item + gridDim.x;
+        if (next < nitems) {
+            int tid2 = threadIdx.x;
+            asm volatile("" : "+v"(tid2));
+            load_grad(next, tid2, 0, kEarly);
+        } else {
+            drop_grad(0, kEarly);
+        }
+        // (the query column scales from the LDS copy - 1.0 without col_scale, the same product: a global load consumed inside the sweep would be a wait
+        //  behind the loads just requested, vmcnt retires in order)
+        const float4 ckq = *reinterpret_cast<const float4*>(sCs + 16 * jd + 4 * g);
+        // ---- the sweep of k_attn_bwd_fused
+        f32x4 dk[U][ND], dv[U][ND];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int id = 0; id < ND; ++id) dk[u][id] = dv[u][id] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int qs = 0; qs < NKT / 2; ++qs) {
+            const int qme = 16 * (2 * qs + vq) + r;
+            const uint32_t mqb = reinterpret_cast<const uint8_t*>(sM)[min(qme, T - 1) * 8 + 2 * jd + (g >> 1)];
+            // phase 1: S and dP of every owned key tile (the query-row fragments are dead afterwards: 48 registers)
+            f32x4 sacc[U][2], dpv[U][2];
+            {
+                bf16x8 qa[2][KK], da[2][KK], db[2][KK];
+#pragma unroll
+                for (int v = 0; v < 2; ++v)
+#pragma unroll
+                    for (int kk = 0; kk < KK; ++kk) {
+                        qa[v][kk] = *reinterpret_cast<const bf16x8*>(sQt + tr_off<HD>(16 * (2 * qs + v) + r, 4 * kk + g));
+                        da[v][kk] = *reinterpret_cast<const bf16x8*>(sDh + tr_off<HD>(16 * (2 * qs + v) + r, 4 * kk + g));
+                        db[v][kk] = *reinterpret_cast<const bf16x8*>(sDl + tr_off<HD>(16 * (2 * qs + v) + r, 4 * kk + g));
+                    }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (!has[u]) continue;   // wave-uniform
+                    bf16x8 kf[KK];           // (rows >= T of the image are zero)
+#pragma unroll
+                    for (int kk = 0; kk < KK; ++kk) kf[kk] = *reinterpret_cast<const bf16x8*>(sKt + tr_off<HD>(16 * jt[u] + r, 4 * kk + g));
+#pragma unroll
+                    for (int v = 0; v < 2; ++v) {
+                        sacc[u][v] = dpv[u][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int kk = 0; kk < KK; ++kk) {
+                            sacc[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[v][kk], kf[kk], sacc[u][v], 0, 0, 0);
+                            dpv[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[v][kk], vf[u][kk], dpv[u][v], 0, 0, 0);
+                            dpv[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(db[v][kk], vf[u][kk], dpv[u][v], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // phase 2: the transposed fragments (their LDS latency runs under the exp / split arithmetic), P and dS, dV / dK
+            bf16x8 dth[ND], dtl[ND], qtf[ND];
+#pragma unroll
+            for (int id = 0; id < ND; ++id) {
+                dth[id] = tr_frag2<HD>(sDh, 32 * qs, 32 * qs + 16, 16 * id, lane);
+                dtl[id] = tr_frag2<HD>(sDl, 32 * qs, 32 * qs + 16, 16 * id, lane);
+                qtf[id] = tr_frag2<HD>(sQt, 32 * qs, 32 * qs + 16, 16 * id, lane);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                bf16x8 ph, pl, sh, sl2;
+                if (has[u]) {
+                    f32x4 p2[2], ds2[2];
+#pragma unroll
+                    for (int v = 0; v < 2; ++v) {
+                        // S orientation: this lane's key = 16 jt + r, query = 16 (2qs + v) + 4g + e: the four softmax constants are one 16-byte read
+                        const float4 nl = *reinterpret_cast<const float4*>(sLse + 16 * (2 * qs + v) + 4 * g);
+                        const float4 dl = *reinterpret_cast<const float4*>(sDlt + 16 * (2 * qs + v) + 4 * g);
+                        const float nlv[4] = {nl.x, nl.y, nl.z, nl.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[u][v][e], c2, nlv[e]));
+                            p2[v][e] = pr;
+                            ds2[v][e] = pr * (dpv[u][v][e] - dlv[e]);
+                        }
+                    }
+                    if (16 * jt[u] + 15 >= T) {   // (wave-uniform) the tile with padded keys: their dS goes into the image as zero - their P is e^-lse, which
+                        asm volatile("");         // may overflow, and dQ^T multiplies it with the zero rows of the K image (inf * 0 = NaN)
+#pragma unroll
+                        for (int v = 0; v < 2; ++v)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) ds2[v][e] = kvalid[u] ? ds2[v][e] : 0.f;
+                    }
+                    split_acc2(p2[0], p2[1], ph, pl);
+                    split_acc2(ds2[0], ds2[1], sh, sl2);
+                }
+                // the dS image is free again once every wave has finished the previous pair's dQ^T tile
+                if (u == 0) lds_barrier();
+                if (has[u]) {
+                    // this lane: key 16 jt + r, queries 4g .. 4g+3 of tile v in elements 4v .. 4v+3 -> 8-byte runs of the [key][32 queries] image
+                    const uint4 wh = __builtin_bit_cast(uint4, sh), wl = __builtin_bit_cast(uint4, sl2);
+                    const int so = (16 * jt[u] + r) * kSRow + ((g ^ ((r >> 2) & 3)) << 3);   // slot g of the key's row, XORed with (key >> 2) & 3
+                    *reinterpret_cast<uint2*>(sSh + so) = make_uint2(wh.x, wh.y);
+                    *reinterpret_cast<uint2*>(sSh + SVQ + so) = make_uint2(wh.z, wh.w);
+                    *reinterpret_cast<uint2*>(sSl + so) = make_uint2(wl.x, wl.y);
+                    *reinterpret_cast<uint2*>(sSl + SVQ + so) = make_uint2(wl.z, wl.w);
+#pragma unroll
+                    for (int id = 0; id < ND; ++id) {
+                        dv[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dth[id], ph, dv[u][id], 0, 0, 0);
+                        dv[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dth[id], pl, dv[u][id], 0, 0, 0);
+                        dv[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dtl[id], ph, dv[u][id], 0, 0, 0);
+                        dk[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf[id], sh, dk[u][id], 0, 0, 0);
+                        dk[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf[id], sl2, dk[u][id], 0, 0, 0);
+                    }
+                }
+            }
+            lds_barrier();   // every owned key tile's dS of this query pair is in the image
+            f32x4 dq = {0.f, 0.f, 0.f, 0.f}, dq1 = {0.f, 0.f, 0.f, 0.f};   // (two chains: the hi and the lo products)
+#pragma unroll
+            for (int ks = 0; ks < NKT / 2; ++ks) {
+                const bf16x8 kt = tr_frag2<HD>(sKt, 32 * ks, 32 * ks + 16, 16 * jd, lane);   // A: row = feature, k-slots = keys
+                const bf16x8 bh = tr_frag_ds(sSh + vq * SVQ, 32 * ks, 32 * ks + 16, lane);     // B: col = query, the same k-slots
+                const bf16x8 bl = tr_frag_ds(sSl + vq * SVQ, 32 * ks, 32 * ks + 16, lane);
+                dq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt, bh, dq, 0, 0, 0);
+                dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt, bl, dq1, 0, 0, 0);
+            }
+            dq += dq1;
+            if (qme < T) {   // rows: features 16 jd + 4g + e, column: query qme -> 8-byte (4 x bf16) stores along d
+                const uint32_t mb = mqb >> (4 * (g & 1));
+                const float gq[4] = {(mb & 1u) ? dq[0] * c * ckq.x : 0.f, (mb & 2u) ? dq[1] * c * ckq.y : 0.f, (mb & 4u) ? dq[2] * c * ckq.z : 0.f,
+                                     (mb & 8u) ? dq[3] * c * ckq.w : 0.f};
+                const int64_t offq = ((int64_t)b * T + qme) * ld + h * HD + 16 * jd + 4 * g;
+                if constexpr (O16) {
+                    am16 = fmaxf(fmaxf(am16, fmaxf(fabsf(gq[0]), fabsf(gq[1]))), fmaxf(fabsf(gq[2]), fabsf(gq[3])));
+                    *reinterpret_cast<uint2*>(p.dqkv_hi + offq) = make_uint2(pk_f16(gq[0] * mul16, gq[1] * mul16), pk_f16(gq[2] * mul16, gq[3] * mul16));
+                } else {
+                    uint2 gh, gl;
+                    split_pair(gq[0], gq[1], gh.x, gl.x); split_pair(gq[2], gq[3], gh.y, gl.y);
+                    *reinterpret_cast<uint2*>(p.dqkv_hi + offq) = gh;
+                    *reinterpret_cast<uint2*>(p.dqkv_lo + offq) = gl;
+                }
+            }
+        }
+        // ---- the rest of the next head's loads: the sweep's fragments are dead, the accumulators drain - the epilogue has the registers the sweep has not
+        auto rest_early = [&]() {
+            if (next < nitems) {
+                int tid3 = threadIdx.x;
+                asm volatile("" : "+v"(tid3));
+                load_rest(next, tid3);
+            } else {
+                drop_small();
+                drop_codes();
+                drop_grad(kEarly, ITERS);
+            }
+        };
+        // ---- the dK / dV epilogue of k_attn_bwd_fused, through wave-private LDS tiles over the (dead) images
+        float4 ckc[ND], cvc[ND];
+#pragma unroll
+        for (int id = 0; id < ND; ++id) {
+            ckc[id] = *reinterpret_cast<const float4*>(sCs + HD + 16 * id + 4 * g);
+            cvc[id] = *reinterpret_cast<const float4*>(sCs + 2 * HD + 16 * id + 4 * g);
+        }
+        uint2 mkr[U], mvr[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            mkr[u] = sM[T + krow[u]];
+            mvr[u] = sM[2 * T + krow[u]];
+        }
+        lds_barrier();
+        constexpr int kERow = 144;
+        char* const sE = smem + wave * (4 * 16 * kERow);   // [k hi | k lo | v hi | v lo][16 keys][144 B]
+        const int erow = lane >> 3, ech = lane & 7;       // read-back: 8 lanes per key row, two passes of 8 rows
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (u == U - 1) rest_early();
+            if (!has[u]) continue;   // wave-uniform
+#pragma unroll
+            for (int id = 0; id < ND; ++id) {
+                const float4 ck4 = ckc[id], cv = cvc[id];
+                const uint32_t bk = (id < 2 ? mkr[u].x : mkr[u].y) >> (16 * (id & 1) + 4 * g), bv = (id < 2 ? mvr[u].x : mvr[u].y) >> (16 * (id & 1) + 4 * g);
+                const float vk[4] = {(bk & 1u) ? dk[u][id][0] * c * ck4.x : 0.f, (bk & 2u) ? dk[u][id][1] * c * ck4.y : 0.f,
+                                     (bk & 4u) ? dk[u][id][2] * c * ck4.z : 0.f, (bk & 8u) ? dk[u][id][3] * c * ck4.w : 0.f};
+                const float vv[4] = {(bv & 1u) ? dv[u][id][0] * cv.x : 0.f, (bv & 2u) ? dv[u][id][1] * cv.y : 0.f,
+                                     (bv & 4u) ? dv[u][id][2] * cv.z : 0.f, (bv & 8u) ? dv[u][id][3] * cv.w : 0.f};
+                uint2 kh, kl, vh, vl;
+                char* const e = sE + r * kERow + (16 * id + 4 * g) * 2;
+                if constexpr (O16) {   // (padded keys hold zero accumulators: P = 0 and dS = 0 for them)
+                    am16 = fmaxf(fmaxf(am16, fmaxf(fmaxf(fabsf(vk[0]), fabsf(vk[1])), fmaxf(fabsf(vk[2]), fabsf(vk[3])))),
+                                 fmaxf(fmaxf(fabsf(vv[0]), fabsf(vv[1])), fmaxf(fabsf(vv[2]), fabsf(vv[3]))));
+                    kh = make_uint2(pk_f16(vk[0] * mul16, vk[1] * mul16), pk_f16(vk[2] * mul16, vk[3] * mul16));
+                    vh = make_uint2(pk_f16(vv[0] * mul16, vv[1] * mul16), pk_f16(vv[2] * mul16, vv[3] * mul16));
+                    *reinterpret_cast<uint2*>(e) = kh;
+                    *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
+                } else {
+                    split_pair(vk[0], vk[1], kh.x, kl.x); split_pair(vk[2], vk[3], kh.y, kl.y);
+                    split_pair(vv[0], vv[1], vh.x, vl.x); split_pair(vv[2], vv[3], vh.y, vl.y);
+                    *reinterpret_cast<uint2*>(e) = kh;
+                    *reinterpret_cast<uint2*>(e + 16 * kERow) = kl;
+                    *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
+                    *reinterpret_cast<uint2*>(e + 48 * kERow) = vl;
+                }
+            }
+            wave_lds_fence();   // (wave-private: LDS is in order per wave, no barrier)
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const int key = 16 * jt[u] + 8 * half + erow;
+                const char* const e = sE + (8 * half + erow) * kERow + ech * 16;
+                const uint4 kh = *reinterpret_cast<const uint4*>(e), vh = *reinterpret_cast<const uint4*>(e + 32 * kERow);
+                const int64_t offk = ((int64_t)b * T + key) * ld + D + h * HD + 8 * ech;
+                if constexpr (O16) {
+                    if (key < T) {
+                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
+                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
+                    }
+                } else {
+                    const uint4 kl = *reinterpret_cast<const uint4*>(e + 16 * kERow), vl = *reinterpret_cast<const uint4*>(e + 48 * kERow);
+                    if (key < T) {
+                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
+                        *reinterpret_cast<uint4*>(p.dqkv_lo + offk) = kl;
+                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
+                        *reinterpret_cast<uint4*>(p.dqkv_lo + offk + D) = vl;
+                    }
+                }
+            }
+            wave_lds_fence();   // the tile is read before the next key tile overwrites it
+        }
+        if (next >= nitems) break;
+        item = next;
+        lds_barrier();   // the epilogue tiles overlay the images the next conversion writes
+    }
+    if constexpr (O16) {
+        am16 = wave_max(am16);
+        if ((threadIdx.x & 63) == 0) atomicMax(p.o16_amax + (blockIdx.x & (kDyAmaxSlots - 1)) * kDyAmaxStride, __builtin_bit_cast(uint32_t, am16));
+    }
+}
+
 // ============================================================================ launchers
 static int check_shape(int T, int D, int H, int* nkt) {
     const int hd = D / H;
@@ -1270,16 +1691,39 @@ bool attn_bwd_is_fused(int T, int H, int D, bool codes) {
     return knobs().attn_bwd_fused && codes && H > 0 && D % H == 0 && D / H == 64 && T > 32 && T <= 224;
 }
 
+static void launch_pipe(const AttnArgs& a, int max_grid, hipStream_t st);   // (defined last: the kernel templates are instantiated in their old order)
+static int cu_count() {   // (as launch_tn_stream)
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 || cus > 256) cus = 256;
+    }
+    return cus;
+}
+
 int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B, int T, int H, int D, const void* O_hi, const void* O_lo,
                     const float* lse, float* delta, const float* dO, void* dqkv_hi, void* dqkv_lo, const float* col_scale, hipStream_t st,
-                    const void* codes, const void* cmask, const float* o16_mul, uint32_t* o16_amax, int live_q_tiles, bool dO_cls) {
+                    const void* codes, const void* cmask, const float* o16_mul, uint32_t* o16_amax, int live_q_tiles, bool dO_cls, int form) {
     if ((codes != nullptr) != (cmask != nullptr)) { set_error("attention backward: codes / cmask go together"); return 1; }
     if (live_q_tiles < 0) { set_error("attention backward: live_q_tiles %d", live_q_tiles); return 1; }
+    if (form < kAttnBwdAuto || form > kAttnBwdPipe5) { set_error("attention backward: form %d (0 per-head launches, 1 persistent, 2 persistent on 5 workgroups)", form); return 1; }
+    if (o16_mul && !o16_amax) { set_error("attention backward: o16_mul needs o16_amax"); return 1; }
+    // The persistent form (k_attn_bwd_pipe) for the ordinary full sweep of the fused kernel's shapes: asked for by name, or - QATVIT_ATTN_BWD_PIPE, default on -
+    // where there are more (image, head) items than workgroups.  Everything else keeps its kernels.
+    const bool pipe_ok = attn_bwd_is_fused(T, H, D, codes != nullptr) && live_q_tiles == 0 && !dO_cls && B >= 1 && T >= 1;
+    if (form >= kAttnBwdPipe && !pipe_ok) {
+        set_error("attention backward: the persistent form needs head_dim 64, 33..224 tokens, saved codes and the full sweep (T=%d, head_dim %d)", T, H > 0 ? D / H : 0);
+        return 1;
+    }
     AttnArgs a{qkv, qp, qmin, qmax, B, T, H, D, 1.0f / sqrtf((float)(D / H)), reinterpret_cast<__bf16*>(const_cast<void*>(O_hi)),
                reinterpret_cast<__bf16*>(const_cast<void*>(O_lo)), const_cast<float*>(lse), delta, dO, reinterpret_cast<__bf16*>(dqkv_hi),
                reinterpret_cast<__bf16*>(dqkv_lo), col_scale, nullptr, nullptr, nullptr,
                reinterpret_cast<uint8_t*>(const_cast<void*>(codes)), reinterpret_cast<uint8_t*>(const_cast<void*>(cmask)), o16_mul, o16_amax,
                live_q_tiles, dO_cls ? 1 : 0};
+    if (pipe_ok && (form >= kAttnBwdPipe || (form == kAttnBwdAuto && knobs().attn_bwd_pipe && (int64_t)B * H > cu_count()))) {
+        launch_pipe(a, form == kAttnBwdPipe5 ? 5 : cu_count(), st);
+        return 0;
+    }
     // one fused kernel (dK, dV and dQ from one sweep) where its shape holds: head_dim 64, 33..224 tokens, saved codes; QATVIT_ATTN_BWD_FUSED=0: the
     // two-kernel form (k_attn_bwd_dq + k_attn_bwd_dkv) everything else takes
     int nkt;
@@ -1305,6 +1749,15 @@ int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B
     a.live_q_tiles = 0;
     if (dispatch(1, a, st)) return 1;
     return dispatch(2, a, st);
+}
+
+static void launch_pipe(const AttnArgs& a, int max_grid, hipStream_t st) {
+    constexpr int kLds = 4 * 14 * 16 * 64 * 2 + 2 * 2 * 14 * 16 * kSRow + 2 * 14 * 16 * 4 + 3 * 14 * 16 * 8 + 3 * 64 * 4;   // 151,296 B, as the per-head kernel
+    static bool once = (allow_lds(k_attn_bwd_pipe<14, false>, kLds), allow_lds(k_attn_bwd_pipe<14, true>, kLds), true);
+    (void)once;
+    const int items = a.B * a.H, grid = items < max_grid ? items : max_grid;
+    if (a.o16_mul) k_attn_bwd_pipe<14, true><<<grid, 8 * 64, kLds, st>>>(a, items);
+    else k_attn_bwd_pipe<14, false><<<grid, 8 * 64, kLds, st>>>(a, items);
 }
 
 }  // namespace qv

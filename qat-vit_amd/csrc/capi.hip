@@ -28,7 +28,7 @@ const Knobs& knobs() {
     static const Knobs k{knob("QATVIT_I8"), knob("QATVIT_F16"), knob("QATVIT_FC2_CODES"), knob("QATVIT_FC1_BITS"), knob("QATVIT_FC2W_CODES"),
                          knob("QATVIT_WBATCH"), knob("QATVIT_ATTN_CODES"), knob("QATVIT_QKV_2PASS"), knob("QATVIT_LNB_FUSE"), knob("QATVIT_QP_LATE"),
                          knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP"), knob("QATVIT_LN_STRIP"),
-                         knob("QATVIT_CLS_BWD")};
+                         knob("QATVIT_CLS_BWD"), knob("QATVIT_ATTN_BWD_PIPE")};
     return k;
 }
 
@@ -437,6 +437,21 @@ int qatvit_attn_backward_live(const float* qkv, const float* qp, int32_t qmin, i
                         nullptr, live_q_tiles, dO_cls != 0))
         return 1;
     QV_CHECK_LAUNCH("qatvit_attn_backward_live");
+    return 0;
+}
+
+int qatvit_attn_backward_form(const float* qkv, const float* qp, int32_t qmin, int32_t qmax, int32_t B, int32_t T, int32_t H, int32_t D,
+                              const void* O_hi, const void* O_lo, const float* lse, float* delta, const float* dO, void* dqkv_hi, void* dqkv_lo,
+                              const float* col_scale, const void* qkv_codes, const void* qkv_mask, const float* o16_mul, uint32_t* o16_amax, int32_t form,
+                              void* stream) {
+    static_assert(QATVIT_DY16_AMAX_SLOTS == kDyAmaxSlots && QATVIT_DY16_AMAX_STRIDE == kDyAmaxStride, "qatvit.h mirrors the amax slot layout");
+    QV_CHECK_ARG((qkv || qkv_codes) && qp && O_hi && O_lo && lse && delta && dO && dqkv_hi && (dqkv_lo || o16_mul), "qatvit_attn_backward_form: null pointer argument");
+    QV_CHECK_ARG(form >= kAttnBwdPerHead && form <= kAttnBwdPipe5, "qatvit_attn_backward_form: form %d (0 per-head launches, 1 persistent, 2 persistent on 5 workgroups)", form);
+    QV_CHECK_ARG(B >= 1 && T >= 1 && H >= 1, "qatvit_attn_backward_form: empty shape");
+    if (launch_attn_bwd(qkv, qp, qmin, qmax, B, T, H, D, O_hi, O_lo, lse, delta, dO, dqkv_hi, dqkv_lo, col_scale, (hipStream_t)stream, qkv_codes, qkv_mask, o16_mul,
+                        o16_amax, 0, false, form))
+        return 1;
+    QV_CHECK_LAUNCH("qatvit_attn_backward_form");
     return 0;
 }
 

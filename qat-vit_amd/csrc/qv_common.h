@@ -46,6 +46,7 @@ struct Knobs {
     bool i8_strip;        // QATVIT_I8_STRIP: the K = 384 / 768 int8 GEMMs on the A-stationary strip kernel; 0: the general tall kernel
     bool ln_strip;        // QATVIT_LN_STRIP: norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln); 0: k_ln_apply_quant in front of it
     bool cls_bwd;         // QATVIT_CLS_BWD: the one-plane backward of the last block's MLP and proj on the B class-token rows (the only ones the cls-pooled head reaches); 0: all B * T rows
+    bool attn_bwd_pipe;   // QATVIT_ATTN_BWD_PIPE: the fused attention backward as one persistent workgroup per CU that fetches its next head under the sweep (more heads than CUs); 0: one workgroup per head
 };
 const Knobs& knobs();
 

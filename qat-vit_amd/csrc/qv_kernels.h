@@ -313,7 +313,16 @@ int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B
                     const float* o16_mul = nullptr, uint32_t* o16_amax = nullptr,   // the one-plane form: dqkv_hi = ONE fp16 plane (fused kernel only)
                     // dO is zero outside the first live_q_tiles 16-query tiles of every image (0: anywhere): the fused kernel sweeps those alone and stores
                     // zeros as the dQ of the rest.  dO_cls (fused kernel only, with live_q_tiles >= 1): dO is [B, D], the rows of token 0
-                    int live_q_tiles = 0, bool dO_cls = false);
+                    int live_q_tiles = 0, bool dO_cls = false,
+                    // which kernels run the fused kernel's ordinary full sweep: kAttnBwdAuto by shape and QATVIT_ATTN_BWD_PIPE; a named form that has no
+                    // kernel for the shape is an error
+                    int form = -1);
+enum AttnBwdForm : int {
+    kAttnBwdAuto = -1,
+    kAttnBwdPerHead = 0,   // one workgroup per (image, head): what QATVIT_ATTN_BWD_PIPE=0 launches, at every shape
+    kAttnBwdPipe = 1,      // k_attn_bwd_pipe: min(B * H, CU count) persistent workgroups, the next head's loads under the sweep
+    kAttnBwdPipe5 = 2,     // the same on 5 workgroups (tests: several heads per workgroup at small B * H)
+};
 // true where launch_attn_bwd takes the fused kernel (the only one with the one-plane output)
 bool attn_bwd_is_fused(int T, int H, int D, bool codes);
 

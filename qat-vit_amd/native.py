@@ -61,6 +61,7 @@ SIGNATURES = {
     "qatvit_attn_forward_f16": (c_int, [c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p] * 9),
     "qatvit_attn_backward": (c_int, [c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p] * 11),
     "qatvit_attn_backward_live": (c_int, [c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p] * 10 + [c_int32, c_int32, c_void_p]),
+    "qatvit_attn_backward_form": (c_int, [c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p] * 12 + [c_int32, c_void_p]),
     "qatvit_student_num_params": (c_int32, [c_void_p]),
     "qatvit_student_num_act_fq": (c_int32, [c_void_p]),
     "qatvit_student_num_weight_fq": (c_int32, [c_void_p]),
