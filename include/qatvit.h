@@ -625,6 +625,50 @@ int qatvit_optim_ema(const void* param_ptrs, const void* ema_ptrs, const int64_t
 int qatvit_optim_swap(const void* a_ptrs, const void* b_ptrs, const int64_t* numel, const int32_t* chunk_tensor, const int32_t* chunk_index,
                       int32_t n_chunks, int64_t chunk_elems, void* stream);
 
+/* LAMB with per-tensor trust ratios: two launches behind qatvit_optim_grad_norm, over the same tables (all param groups in each launch; the groups
+ * form with n_groups >= 1 is the only one).  Arithmetic, exactly - timm's Lamb with that class's defaults - for every tensor p with gradient g, the
+ * row lr, (b1, b2), eps, weight_decay = wd, step = t (1-based) of its group, and coef = clip_out2[1] (1 where clip_out2 is NULL):
+ *     g   <- g * coef
+ *     m   <- b1 * m + (1 - b1) * g                       (grad_averaging = 0: m <- b1 * m + g)
+ *     v   <- b2 * v + (1 - b2) * g * g
+ *     r    = (m / (1 - b1^t)) / (sqrt(v) / sqrt(1 - b2^t) + eps) + wd * p
+ *     trust = ||p||_2 / ||r||_2  if (wd != 0 or always_adapt) and ||p|| > 0 and ||r|| > 0, else 1;   trust_clip: min(trust, 1)
+ *     p   <- p - lr * trust * r
+ * ||p|| is the norm of the weight before the update; both norms are per tensor, never per group.  Every fp32 operation is rounded on its own, in
+ * the order written (-ffp-contract=off); 1 - b1, 1 - b2, 1 - b1^t and sqrt(1 - b2^t) are formed in double and narrowed once; lr * trust is one
+ * product per tensor.  coef is qatvit_optim_grad_norm's min(1, max_norm / (total + 1e-6)) over ALL groups (timm divides by max(total / max_norm,
+ * 1): a stated deviation).  The squares are added in fp32 inside a chunk and in double across the chunks of a tensor, in a fixed order: no
+ * atomics, bit-reproducible run to run.
+ * lamb_moments: reads params, grads, exp_avg, exp_avg_sq; writes exp_avg, exp_avg_sq and partials2 = device fp32 [n_chunks][2] = per chunk
+ *            {sum r^2, sum p^2}.  params are NOT written (16 B read + 8 B written per parameter).
+ * lamb_apply: adds up each tensor's partials (tensor_first_chunk = device int32 [n_tensors], the index in the chunk tables of the tensor's chunk 0;
+ *            a tensor's chunks are contiguous and ascending there), forms trust, forms r again from the exp_avg / exp_avg_sq that lamb_moments
+ *            wrote and the untouched params - the same expression, the same bits - and writes params (12 B + 4 B per parameter).  ema_ptrs = NULL
+ *            or the averages of the weight EMA above, e <- lerp(e, p_new, 1 - ema_decay), 8 B per parameter more; ema_decay is read only then.
+ *            The branches are those stated there, each with its multiply-add as ONE fused operation: with d = p_new - e,
+ *                e' = (w < 0.5f) ? fma(w, d, e) : fma(-d, 1.0f - w, p_new)
+ *            which is how stock torch.lerp rounds (CPU and GPU): the average is torch.equal to torch.lerp(e, p_new, 1 - ema_decay) applied after
+ *            the step, and within one rounding of the two-rounding form of qatvit_optim_ema, which still averages the tensors a step leaves out.
+ *            trust_out = NULL or device fp32 [n_tensors]: the trust each tensor was updated with.
+ * Both take the same `groups` (HOST memory, read during the call; the prefactors travel in the kernel arguments) and the same tensor_group; a tensor
+ * whose entry is outside [0, n_groups) is left untouched by both (its partials are zeros, its trust_out entry is not written).
+ * Errors (before any HIP call): a null table, n_chunks <= 0, chunk_elems <= 0 or not a multiple of 4, n_groups outside [1,
+ * QATVIT_OPTIM_MAX_GROUPS], a row with lr < 0, eps < 0, a beta outside [0, 1), weight_decay < 0 or step < 1, and with ema_ptrs an ema_decay
+ * outside [0, 1) or NaN. */
+typedef struct qatvit_lamb_group {
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t step;
+    int32_t grad_averaging, always_adapt, trust_clip, reserved;   /* flags: 0 / non-zero; reserved = 0 */
+} qatvit_lamb_group;
+int qatvit_optim_lamb_moments(const void* param_ptrs, const void* grad_ptrs, const void* exp_avg_ptrs, const void* exp_avg_sq_ptrs,
+                              const int64_t* numel, const int32_t* tensor_group, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                              int32_t n_chunks, int64_t chunk_elems, const qatvit_lamb_group* groups, int32_t n_groups,
+                              const float* clip_out2, float* partials2, void* stream);
+int qatvit_optim_lamb_apply(const void* param_ptrs, const void* exp_avg_ptrs, const void* exp_avg_sq_ptrs, const void* ema_ptrs,
+                            const int64_t* numel, const int32_t* tensor_group, const int32_t* tensor_first_chunk, const int32_t* chunk_tensor,
+                            const int32_t* chunk_index, int32_t n_chunks, int64_t chunk_elems, const qatvit_lamb_group* groups, int32_t n_groups,
+                            double ema_decay, const float* partials2, float* trust_out, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Input pipeline: uint8 images resident on the device -> the normalised fp32 batch.
  * Replaces: the per-image host transform of the loaders (qat_trainer.py:209-254, evaluator.py:22-41): Resize(D, BICUBIC) through Pillow,

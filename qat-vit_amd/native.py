@@ -37,6 +37,8 @@ SIGNATURES = {
     "qatvit_optim_adamw_groups_ema": (c_int, [c_void_p] * 9 + [c_int32, c_int64, c_void_p, c_int32, c_double, c_void_p, c_void_p]),
     "qatvit_optim_ema": (c_int, [c_void_p] * 5 + [c_int32, c_int64, c_double, c_void_p]),
     "qatvit_optim_swap": (c_int, [c_void_p] * 5 + [c_int32, c_int64, c_void_p]),
+    "qatvit_optim_lamb_moments": (c_int, [c_void_p] * 8 + [c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "qatvit_optim_lamb_apply": (c_int, [c_void_p] * 9 + [c_int32, c_int64, c_void_p, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
     "qatvit_gemm_nt": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_gemm_nt_f16": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_gemm_nt_i8_minmax": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
@@ -156,6 +158,12 @@ class TNItem(ctypes.Structure):
 class AdamWGroup(ctypes.Structure):
     """struct qatvit_adamw_group (include/qatvit.h)."""
     _fields_ = [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("step", c_int64)]
+
+
+class LambGroup(ctypes.Structure):
+    """struct qatvit_lamb_group (include/qatvit.h)."""
+    _fields_ = [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("step", c_int64)] + \
+               [(n, c_int32) for n in ("grad_averaging", "always_adapt", "trust_clip", "reserved")]
 
 
 class FQ(ctypes.Structure):

@@ -1,5 +1,6 @@
 """Fused gradient clipping + AdamW on MI355X (libqatvit.so: qatvit_optim_grad_norm / qatvit_optim_adamw / qatvit_optim_adamw_groups, and with a
-weight EMA qatvit_optim_adamw_ema / qatvit_optim_adamw_groups_ema / qatvit_optim_ema / qatvit_optim_swap).
+weight EMA qatvit_optim_adamw_ema / qatvit_optim_adamw_groups_ema / qatvit_optim_ema / qatvit_optim_swap), and LAMB with per-tensor trust ratios on
+the same tables (qatvit_optim_lamb_moments / qatvit_optim_lamb_apply): ``ClipAdamW`` and ``ClipLamb``.
 
 Stands where the reference's loop has (``/root/reference/src/training/qat_trainer.py:360-361``, optimizer built at ``:271-276``)::
 
@@ -19,7 +20,16 @@ learning-rate decay).
 ``_ema`` entries: one more stream, no extra launch): ``e <- lerp(e, p_new, 1 - d)`` in fp32, ATen's formula (include/qatvit.h states it).  The
 averaged model is evaluated by exchanging contents in place - ``with opt.ema_weights(): evaluate(...)`` - so no address changes and nothing that
 reads parameters by address (the engines, ``export_int8``) has to be rebuilt; ``opt.ema_state_dict(model)`` is its checkpoint.  Only parameters are
-averaged: buffers and observer ranges are the live model's, also while swapped."""
+averaged: buffers and observer ranges are the live model's, also while swapped.
+
+``ClipLamb`` is LAMB - the optimizer of the DeiT-III-style ViT recipes - on the same footing (qatvit_optim_lamb_moments / qatvit_optim_lamb_apply behind
+the same qatvit_optim_grad_norm): timm's ``Lamb`` arithmetic with that class's defaults, one trust ratio ``||p|| / ||r||`` per tensor.  The two norms of a
+tensor are needed between forming the update and applying it, so the update is two launches: the first writes both moments and, per 16384-element chunk, the
+partial sums of ``r^2`` and ``p^2``; the second adds up its tensor's partials (double, fixed order, no atomics), forms the ratio, forms ``r`` again from the new
+moments and writes the parameters - and the weight average, from the same register.  Everything else is shared with ``ClipAdamW`` (``_ClipOptimizer``): one
+table set and one clip coefficient over all param groups, the rows of up to ``MAX_GROUPS`` groups by value in the kernel arguments, ``ema_decay``,
+``swap_ema`` / ``ema_weights`` / ``ema_parameters`` / ``ema_state_dict``, ``vit_param_groups`` output as is.  ``opt.trust_ratios()`` is the device tensor of the
+ratios the last step used, for logging.  ``step()`` reads nothing back from the device.  State keys ``step``, ``exp_avg``, ``exp_avg_sq`` (and ``ema``)."""
 
 import contextlib
 import operator
@@ -34,12 +44,12 @@ MAX_GROUPS = 64  # QATVIT_OPTIM_MAX_GROUPS (include/qatvit.h): rows of the prefa
 _HYPER = operator.itemgetter("lr", "betas", "eps", "weight_decay")
 
 
-def _checked_ema_decay(decay):
+def _checked_ema_decay(decay, name="ClipAdamW"):
     if decay is None:
         return None
     decay = float(decay)
     if not 0.0 <= decay < 1.0:   # NaN fails too
-        raise ValueError(f"ClipAdamW: ema_decay {decay} outside [0, 1)")
+        raise ValueError(f"{name}: ema_decay {decay} outside [0, 1)")
     return decay
 
 
@@ -49,15 +59,19 @@ def ema_warmup_decay(decay, updates):
     return min(decay, (1 + updates) / (10 + updates))
 
 
-class ClipAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_decay=None):
-        if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
-            raise ValueError("invalid AdamW hyper-parameters")
-        ema_decay = _checked_ema_decay(ema_decay)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+class _ClipOptimizer(torch.optim.Optimizer):
+    """What ClipAdamW and ClipLamb share: the table set over the live tensors of all param groups, the global-norm launch pair, the weight EMA's
+    state, its idle launch and the in-place swap, and the frame of step().  A subclass gives its name (the prefix of every message), validates its
+    hyper-parameters and launches its update (``_update``)."""
+    _NAME = None
+    MAX_GROUPS = MAX_GROUPS   # live param groups one update launch takes
+
+    def __init__(self, params, defaults, ema_decay):
+        ema_decay = _checked_ema_decay(ema_decay, self._NAME)
+        super().__init__(params, defaults)
         self._tables = None
         self._pending = None   # clip out2 of a clip_grad_norm_() not yet consumed by step()
-        self._ema_decay = ema_decay   # not a param-group entry: state_dict()'s groups stay torch.optim.AdamW's
+        self._ema_decay = ema_decay   # not a param-group entry: state_dict()'s groups stay the stock optimizer's
         self._idle = []               # (p, ema) of the parameters that have an average but no gradient this step
         self._pairs = {}              # tables of the two pair launches (qatvit_optim_ema, qatvit_optim_swap)
         self._swapped = False
@@ -69,7 +83,7 @@ class ClipAdamW(torch.optim.Optimizer):
 
     @ema_decay.setter
     def ema_decay(self, decay):
-        self._ema_decay = _checked_ema_decay(decay)
+        self._ema_decay = _checked_ema_decay(decay, self._NAME)
 
     @property
     def ema_swapped(self) -> bool:
@@ -99,14 +113,14 @@ class ClipAdamW(torch.optim.Optimizer):
         if not ps:
             return None
         if len(live) > MAX_GROUPS:
-            raise RuntimeError(f"ClipAdamW: {len(live)} param groups with gradients; one launch updates at most {MAX_GROUPS} groups")
+            raise RuntimeError(f"{self._NAME}: {len(live)} param groups with gradients; one launch updates at most {MAX_GROUPS} groups")
         dev, state, sts, ptrs = ps[0].device, self.state, [], []
         for p in ps:
             if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("ClipAdamW runs on MI355X only: parameters must be contiguous fp32 CUDA tensors")
+                raise RuntimeError(f"{self._NAME} runs on MI355X only: parameters must be contiguous fp32 CUDA tensors")
             g = p.grad
             if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
-                raise RuntimeError("ClipAdamW: gradients must be contiguous fp32 tensors on the one device all parameters live on")
+                raise RuntimeError(f"{self._NAME}: gradients must be contiguous fp32 tensors on the one device all parameters live on")
             st = state[p]
             if not st:
                 st["step"] = torch.tensor(0.0)
@@ -128,7 +142,7 @@ class ClipAdamW(torch.optim.Optimizer):
                 for p, st in zip(ps, sts):
                     e = st["ema"]
                     if e.shape != p.shape or e.dtype != torch.float32 or e.device != dev or not e.is_contiguous():
-                        raise RuntimeError("ClipAdamW: state[p]['ema'] must be a contiguous fp32 tensor of the parameter's shape on its device")
+                        raise RuntimeError(f"{self._NAME}: state[p]['ema'] must be a contiguous fp32 tensor of the parameter's shape on its device")
             starts, ct, ci = [tg.index(gi) for gi in range(len(live))], [], []
             for ti, p in enumerate(ps):
                 n = (p.numel() + _CHUNK - 1) // _CHUNK
@@ -141,9 +155,13 @@ class ClipAdamW(torch.optim.Optimizer):
                      starts=starts, first=[starts[gi] for gi in tg],   # the first tensor of each group; per tensor, the first of its group
                      pack=struct.Struct("=" + "5dq" * len(live)).pack,
                      partials=torch.empty(len(ct), dtype=torch.float32, device=dev), out2=torch.empty(2, dtype=torch.float32, device=dev))
+            self._more_tables(t, ct, len(ps), dev)
             self._tables = t
         t["live"], t["sts"] = live, sts
         return t
+
+    def _more_tables(self, t, ct, n_tensors, dev):
+        """What a subclass's update needs in the table set beyond the common entries (called when the set is rebuilt)."""
 
     def _pair_tables(self, slot, pairs):
         """The tables of a launch over (a, b) tensor pairs (the stand-alone average, the swap), keyed on the addresses; None if there is no element."""
@@ -154,7 +172,7 @@ class ClipAdamW(torch.optim.Optimizer):
             for ti, (a, b) in enumerate(pairs):
                 if not (a.is_cuda and b.device == a.device and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
                         and a.numel() == b.numel()):
-                    raise RuntimeError("ClipAdamW: a parameter and its average must be contiguous fp32 CUDA tensors of one size on one device")
+                    raise RuntimeError(f"{self._NAME}: a parameter and its average must be contiguous fp32 CUDA tensors of one size on one device")
                 n = (a.numel() + _CHUNK - 1) // _CHUNK
                 ct += [ti] * n
                 ci += list(range(n))
@@ -204,40 +222,25 @@ class ClipAdamW(torch.optim.Optimizer):
         steps = [st["step"] for st in t["sts"]]
         count = torch.stack(steps).tolist()
         if count != [count[i] for i in t["first"]]:
-            raise RuntimeError("ClipAdamW: parameters of one group must share their step count")
+            raise RuntimeError(f"{self._NAME}: parameters of one group must share their step count")
         if max_norm is not None:
             self._grad_norm(t, max_norm)
-        L = native.lib()
-        clip = self._pending.data_ptr() if self._pending is not None else None
-        # with a weight EMA the `_ema` entry of the same name: ema_ptrs after exp_avg_sq_ptrs, the decay (by value, as the prefactors) in front of clip
-        ema = t["ema"] is not None
-        sfx, e_ptr, e_decay = ("_ema", (t["ema"].data_ptr(),), (self._ema_decay,)) if ema else ("", (), ())
-        if len(self.param_groups) == 1:
-            group = t["live"][0]
-            b1, b2 = group["betas"]
-            name = "qatvit_optim_adamw" + sfx
-            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr, t["numel"].data_ptr(),
-                                      t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK, float(group["lr"]), float(b1), float(b2),
-                                      float(group["eps"]), float(group["weight_decay"]), int(count[0]) + 1, *e_decay, clip, native.stream_ptr())
-        else:   # the rows of struct qatvit_adamw_group, packed on the host; they go by value into the kernel arguments: a new lr costs no copy
-            rows = []
-            for (lr, (b1, b2), eps, wd), i in zip(map(_HYPER, t["live"]), t["starts"]):
-                rows += (lr, b1, b2, eps, wd, int(count[i]) + 1)
-            name = "qatvit_optim_adamw_groups" + sfx
-            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr,
-                                      t["numel"].data_ptr(), t["tg"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK,
-                                      t["pack"](*rows), len(t["live"]), *e_decay, clip, native.stream_ptr())
-        native.check(status, name)
-        if ema:
+        self._update(t, count, self._pending.data_ptr() if self._pending is not None else None)
+        if t["ema"] is not None:
             self._average_idle()
         torch._foreach_add_(steps, 1)
         self._pending = None
         return loss
 
+    def _update(self, t, count, clip):
+        """The update launch(es) of one step over the table set `t`; count[i] = the step count of live tensor i before this step, clip = the address
+        of the pending {norm, coefficient} pair or None."""
+        raise NotImplementedError
+
     # ------------------------------------------------------------------ the averaged weights
     def _refuse_swapped(self, what):
         if self._swapped:
-            raise RuntimeError(f"ClipAdamW: the averaged weights are swapped in (swap_ema() / ema_weights()); swap back before {what}")
+            raise RuntimeError(f"{self._NAME}: the averaged weights are swapped in (swap_ema() / ema_weights()); swap back before {what}")
 
     def _has_ema(self, p):
         return "ema" in self.state.get(p, ())   # .get: looking must not create the state of a parameter that has none
@@ -266,7 +269,7 @@ class ClipAdamW(torch.optim.Optimizer):
         """``with opt.ema_weights():`` - the model computes with the averaged weights inside the block (evaluate, export); the live weights are
         back after it, also when the block raises.  Buffers and observer ranges are not averaged: they are the live model's throughout."""
         if self._swapped:
-            raise RuntimeError("ClipAdamW: the averaged weights are swapped in already")
+            raise RuntimeError(f"{self._NAME}: the averaged weights are swapped in already")
         self.swap_ema()
         try:
             yield self
@@ -288,6 +291,92 @@ class ClipAdamW(torch.optim.Optimizer):
     def state_dict(self):
         self._refuse_swapped("state_dict()")   # "ema" would be saved holding the live weights
         return super().state_dict()
+
+
+class ClipAdamW(_ClipOptimizer):
+    _NAME = "ClipAdamW"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_decay=None):
+        if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
+            raise ValueError("invalid AdamW hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), ema_decay)
+
+    def _update(self, t, count, clip):
+        L = native.lib()
+        # with a weight EMA the `_ema` entry of the same name: ema_ptrs after exp_avg_sq_ptrs, the decay (by value, as the prefactors) in front of clip
+        ema = t["ema"] is not None
+        sfx, e_ptr, e_decay = ("_ema", (t["ema"].data_ptr(),), (self._ema_decay,)) if ema else ("", (), ())
+        if len(self.param_groups) == 1:
+            group = t["live"][0]
+            b1, b2 = group["betas"]
+            name = "qatvit_optim_adamw" + sfx
+            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr, t["numel"].data_ptr(),
+                                      t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK, float(group["lr"]), float(b1), float(b2),
+                                      float(group["eps"]), float(group["weight_decay"]), int(count[0]) + 1, *e_decay, clip, native.stream_ptr())
+        else:   # the rows of struct qatvit_adamw_group, packed on the host; they go by value into the kernel arguments: a new lr costs no copy
+            rows = []
+            for (lr, (b1, b2), eps, wd), i in zip(map(_HYPER, t["live"]), t["starts"]):
+                rows += (lr, b1, b2, eps, wd, int(count[i]) + 1)
+            name = "qatvit_optim_adamw_groups" + sfx
+            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr,
+                                      t["numel"].data_ptr(), t["tg"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK,
+                                      t["pack"](*rows), len(t["live"]), *e_decay, clip, native.stream_ptr())
+        native.check(status, name)
+
+
+_LAMB_FLAGS = operator.itemgetter("grad_averaging", "always_adapt", "trust_clip")
+
+
+class ClipLamb(_ClipOptimizer):
+    """LAMB with per-tensor trust ratios (timm's ``Lamb`` with that class's defaults; include/qatvit.h states the arithmetic), with ClipAdamW's surface:
+    ``step(max_norm=...)`` / ``clip_grad_norm_`` apply ONE global clip coefficient inside the update, all param groups go through the same launches,
+    ``ema_decay`` keeps the weight average inside the apply launch, ``ema_weights()`` swaps it in place.  A step is the norm launch pair (with a
+    ``max_norm``), ``qatvit_optim_lamb_moments`` and ``qatvit_optim_lamb_apply``; nothing is read back from the device.
+
+    Differences from timm: the clip coefficient is ``min(1, max_norm / (total + 1e-6))`` (ClipAdamW's, torch's ``clip_grad_norm_``) rather than a
+    division by ``max(total / max_norm, 1)``, and it is asked for per step instead of through a ``max_grad_norm`` group entry; a fused GradScaler
+    unscale is not part of it (``scaler.step(opt)`` goes through the stock path).  State keys: ``step``, ``exp_avg``, ``exp_avg_sq`` (and ``ema``)."""
+    _NAME = "ClipLamb"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, grad_averaging=True, always_adapt=False, trust_clip=False,
+                 ema_decay=None):
+        if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
+            raise ValueError("invalid LAMB hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_averaging=bool(grad_averaging),
+                                      always_adapt=bool(always_adapt), trust_clip=bool(trust_clip)), ema_decay)
+        self._trust = None
+
+    def _more_tables(self, t, ct, n_tensors, dev):
+        first = [0] * n_tensors   # a tensor's chunks are contiguous: where each tensor's begin (an empty tensor has none and is never looked up)
+        for c in range(len(ct) - 1, -1, -1):
+            first[ct[c]] = c
+        t["first_chunk"] = torch.tensor(first, dtype=torch.int32, device=dev)
+        t["partials2"] = torch.empty(2 * len(ct), dtype=torch.float32, device=dev)
+        t["trust"] = torch.ones(n_tensors, dtype=torch.float32, device=dev)
+        t["pack"] = struct.Struct("=" + "5dq4i" * len(t["starts"])).pack   # rows of struct qatvit_lamb_group
+
+    def _update(self, t, count, clip):
+        L, st = native.lib(), native.stream_ptr()
+        rows = []
+        for group, i in zip(t["live"], t["starts"]):
+            lr, (b1, b2), eps, wd = _HYPER(group)
+            rows += (lr, b1, b2, eps, wd, int(count[i]) + 1, *map(int, _LAMB_FLAGS(group)), 0)
+        rows = t["pack"](*rows)   # by value into the kernel arguments of both launches: a scheduled lr costs no copy
+        native.check(L.qatvit_optim_lamb_moments(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), t["numel"].data_ptr(),
+                                                 t["tg"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK, rows, len(t["live"]), clip,
+                                                 t["partials2"].data_ptr(), st), "qatvit_optim_lamb_moments")
+        ema = t["ema"] is not None
+        native.check(L.qatvit_optim_lamb_apply(t["params"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), t["ema"].data_ptr() if ema else None,
+                                               t["numel"].data_ptr(), t["tg"].data_ptr(), t["first_chunk"].data_ptr(), t["ct"].data_ptr(),
+                                               t["ci"].data_ptr(), t["n"], _CHUNK, rows, len(t["live"]), self._ema_decay if ema else 0.0,
+                                               t["partials2"].data_ptr(), t["trust"].data_ptr(), st), "qatvit_optim_lamb_apply")
+        self._trust = t["trust"]
+
+    def trust_ratios(self):
+        """The trust ratio each tensor was updated with in the last step: a device fp32 tensor with one entry per tensor that had a gradient, in
+        group order and then parameter order (exactly 1 where the group neither decays nor always adapts, or a norm was zero).  For logging: it is
+        the buffer the step wrote, returned without a synchronisation - clone it to keep it past the next step.  None before the first step."""
+        return self._trust
 
 
 # ---------------------------------------------------------------------- the usual ViT param groups
