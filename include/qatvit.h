@@ -114,6 +114,33 @@ int qatvit_kd_ce_loss_mix(const float* student, const float* teacher, const floa
                           const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
                           float label_smoothing, float* out3, float* dlogits, void* stream);
 
+/* KD + BINARY cross-entropy with logits on the same targets (timm's BinaryCrossEntropy on the output of its Mixup; the DeiT-III criterion), forward
+ * and d/dlogits.  One entry for every form: teacher / table / index / mix are optional under qatvit_kd_ce_loss_mix's rules (tensor and table
+ * mutually exclusive, a table needs index and table_rows >= 1, both NULL: the hard part only and alpha ignored; mix 4-byte aligned).
+ * 1 <= B < 2^30, 2 <= C <= 4096, kd_temp > 0, label_smoothing eps in [0, 1).  partials: fp32 [2 * B] workspace, contents on entry ignored.
+ * Per row b, with p and lam from words 0 and 5 of the row's record (p outside [0, B): p = b; mix == NULL or lam == 1: p = b, lam = 1),
+ * oml = 1 - lam formed in fp32, x = student[b][c], all in fp32, every operation rounded on its own:
+ *   target     t[c] = (1 - eps) * (lam * [c == labels[b]] + oml * [c == labels[p]]) + eps / C
+ *              then, if target_threshold >= 0:  t[c] = t[c] > target_threshold ? 1 : 0   (after smoothing and mixing; negative: off)
+ *   hard part  l[c] = max(x, 0) - x * t[c] + log1pf(e),  e = expf(-|x|);   sigma = x >= 0 ? 1 / (1 + e) : e / (1 + e)
+ *              gradient term  w_hard * (sigma - t[c]) * scale,  scale = 1 / (B * C), or 1 / B where sum_classes != 0
+ *   KD part    qatvit_kd_ce_loss_mix's, term for term: teacher tensor q = softmax(teacher[b] / T); teacher table
+ *              q = softmax(table[index[b]] / T), and where lam != 1  q = lam * q + oml * softmax(table[index[p]] / T);
+ *              KD = sum_c q (log q - log_softmax(x / T)) with 0 log 0 = 0, gradient term w_kd * T * (softmax(x / T) - q) / B.
+ *              w_kd = alpha, w_hard = 1 - alpha with a teacher of either kind, else 0 and 1.
+ *   An index[b], or where lam != 1 an index[p], outside [0, table_rows) reads nothing: that row of dlogits and all of out3 become NaN
+ *   (no fault, no host synchronisation).  The partner's label and row are read only where lam != 1.
+ * Two launches on `stream`: one wave of 64 lanes per row (4 rows per workgroup) writes dlogits[b] and the row's {sum_c l[c], KD} to
+ * partials[2 * b]; one workgroup then adds the partials up in double in a fixed order and writes
+ *   out3 = {w_kd * kd + w_hard * bce, bce, kd},  bce = scale * sum_b sum_c l,  kd = T^2 / B * sum_b KD.
+ * No atomics: the same inputs give the same bits.  The lanes of a row add in parallel, so the KD number agrees with the CE entries' to
+ * rounding, not bit for bit.
+ */
+int qatvit_kd_bce_loss(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                       const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                       float label_smoothing, float target_threshold, int32_t sum_classes, float* partials, float* out3, float* dlogits,
+                       void* stream);
+
 /* ===========================================================================
  * Building blocks of the step, exported for kernel-level parity tests.
  * All matrices row-major; "bf16" = IEEE bfloat16 bit patterns (uint16).

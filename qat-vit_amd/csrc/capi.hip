@@ -200,6 +200,25 @@ int qatvit_kd_ce_loss_mix(const float* student, const float* teacher, const floa
     return 0;
 }
 
+int qatvit_kd_bce_loss(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                       const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                       float label_smoothing, float target_threshold, int32_t sum_classes, float* partials, float* out3, float* dlogits,
+                       void* stream) {
+    QV_CHECK_ARG(student && labels && partials && out3 && dlogits, "qatvit_kd_bce_loss: null pointer argument");
+    QV_CHECK_ARG(!(teacher && table), "qatvit_kd_bce_loss: a teacher tensor and a teacher table are mutually exclusive");
+    QV_CHECK_ARG(!table || index, "qatvit_kd_bce_loss: a teacher table needs an index");
+    QV_CHECK_ARG(batch >= 1 && batch <= INT32_MAX / 2 && classes >= 2 && classes <= 4096, "qatvit_kd_bce_loss: bad shape B=%lld C=%lld",
+                 (long long)batch, (long long)classes);
+    QV_CHECK_ARG(!table || table_rows >= 1, "qatvit_kd_bce_loss: table_rows %lld (at least 1)", (long long)table_rows);
+    QV_CHECK_ARG(kd_temp > 0.f, "qatvit_kd_bce_loss: kd_temp must be > 0");
+    QV_CHECK_ARG(label_smoothing >= 0.f && label_smoothing < 1.f, "qatvit_kd_bce_loss: label_smoothing %g is outside [0, 1)", (double)label_smoothing);
+    QV_CHECK_ARG(((uintptr_t)mix & 3) == 0, "qatvit_kd_bce_loss: misaligned mix pointer");
+    launch_kd_bce_loss(student, teacher, table, table_rows, index, labels, mix, batch, classes, kd_temp, kd_alpha, label_smoothing, target_threshold,
+                       sum_classes != 0, partials, out3, dlogits, (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_kd_bce_loss");
+    return 0;
+}
+
 // The NT GEMMs: a wrapper checks its own pointers, writes its parameters into an NTGemm and names the operand form; launch_gemm_nt checks the request itself
 // (gemm.hip nt_request_ok).  QV_NT_REQUEST: the parameters the entry points share, by name (B and ldb: where there are any)
 #define QV_NT_REQUEST(g, a, a_ld, c_ld)                                                                                                         \

@@ -24,6 +24,12 @@ int launch_kd_ce_loss_mix(const float* student, const float* teacher, const floa
                           const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
                           float label_smoothing, float* out3, float* dlogits, hipStream_t st);
 
+// ---- bce.hip: KD + binary cross-entropy on the same targets, one wave per row and a fixed-order reduction of partials[2 * batch] (two launches)
+int launch_kd_bce_loss(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                       const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                       float label_smoothing, float target_threshold, bool sum_classes, float* partials, float* out3, float* dlogits,
+                       hipStream_t st);
+
 // ---- fq.hip (engine pieces)
 int launch_minmax(const float* x, int64_t channels, int64_t inner, int per_channel, uint32_t* ws, int nslots, hipStream_t st);
 int launch_ws_init(uint32_t* ws, int64_t slots, hipStream_t st);

@@ -174,6 +174,15 @@ class TeacherLogitTable:
             return F.kd_ce_loss_table_mix(student_logits, self.logits, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
         return F.kd_ce_loss_table(student_logits, self.logits, index, labels, kd_temp, kd_alpha, label_smoothing)
 
+    def bce_loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None, target_threshold=None,
+                 sum_classes=False):
+        """``loss`` with the binary cross-entropy of ``F.kd_bce_loss`` as the hard part: (loss, [loss, bce, kd*T^2]).  The KD part and what ``mix``
+        does to the labels and the teacher's rows are ``loss``'s."""
+        self._need_device("bce_loss")
+        self.check_fresh()
+        return F.kd_bce_loss(student_logits, labels, table=self.logits, index=index, mix=mix, kd_temp=kd_temp, kd_alpha=kd_alpha,
+                             label_smoothing=label_smoothing, target_threshold=target_threshold, sum_classes=sum_classes)
+
     def save(self, path) -> None:
         torch.save({"logits": self.logits.detach().cpu(), "meta": self.meta}, path)
 

@@ -258,3 +258,73 @@ def kd_ce_loss_table_mix(student, table, index, labels, mix, kd_temp=4.0, kd_alp
     the mixed image.  An index outside the table, of the row or (where ``lam != 1``) of its partner, makes the loss and that row of the gradient
     NaN.  ``mix=None`` is ``kd_ce_loss_table``."""
     return _KDCELossMixFn.apply(student, None, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
+
+
+class _KDBCELossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes):
+        who = "kd_bce_loss"
+        _need_cuda(student, who)
+        if student.dim() != 2:
+            raise RuntimeError(f"{who}: the student logits must be [B, C], got {tuple(student.shape)}")
+        student = student.contiguous()
+        B, C = student.shape
+        dev = student.device
+        if teacher is not None and table is not None:
+            raise RuntimeError(f"{who}: a teacher tensor and a teacher table are mutually exclusive")
+        tptr = bptr = iptr = None
+        rows = 0
+        if teacher is not None:
+            teacher = teacher.contiguous().float()
+            if teacher.shape != (B, C) or teacher.device != dev:
+                raise RuntimeError(f"{who}: the teacher must be a [{B}, {C}] tensor on {dev}, got {tuple(teacher.shape)} on {teacher.device}")
+            tptr = teacher.data_ptr()
+        if table is not None:
+            _need_cuda(table, who)
+            if table.dim() != 2 or table.shape[1] != C or table.shape[0] < 1 or not table.is_contiguous() or table.device != dev:
+                raise RuntimeError(f"{who}: the table must be a contiguous [rows, {C}] tensor on {dev}, got {tuple(table.shape)} on {table.device}")
+            if index is None:
+                raise RuntimeError(f"{who}: a teacher table needs an index")
+            index = index.contiguous()
+            if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev:
+                raise RuntimeError(f"{who}: index must be an int64 [{B}] tensor on {dev}")
+            bptr, iptr, rows = table.data_ptr(), index.data_ptr(), table.shape[0]
+        labels = labels.contiguous()
+        if labels.dtype != torch.int64 or labels.shape != (B,) or labels.device != dev:
+            raise RuntimeError(f"{who}: labels must be an int64 [{B}] tensor on {dev}")
+        mptr = None
+        if mix is not None:
+            if mix.dtype != torch.int32 or tuple(mix.shape) != (B, 6) or not mix.is_contiguous() or mix.device != dev:
+                raise RuntimeError(f"{who}: mix must be a contiguous int32 [{B}, 6] tensor on {dev}")
+            mptr = mix.data_ptr()
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        partials = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        dlogits = torch.empty_like(student)
+        native.check(
+            native.lib().qatvit_kd_bce_loss(student.data_ptr(), tptr, bptr, rows, iptr, labels.data_ptr(), mptr, B, C, float(kd_temp), float(kd_alpha),
+                                            float(label_smoothing), -1.0 if target_threshold is None else float(target_threshold),
+                                            int(bool(sum_classes)), partials.data_ptr(), out3.data_ptr(), dlogits.data_ptr(), native.stream_ptr()),
+            "qatvit_kd_bce_loss",
+        )
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(out3)
+        return out3[0], out3
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * dloss,) + (None,) * 10
+
+
+def kd_bce_loss(student, labels, teacher=None, table=None, index=None, mix=None, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1,
+                target_threshold=None, sum_classes=False):
+    """KD + binary cross-entropy with logits on smoothed, mixed targets (timm's ``BinaryCrossEntropy`` behind its ``Mixup``; the DeiT-III
+    criterion): returns (loss, [loss, bce, kd*T^2]).  The hard target of row b is ``kd_ce_loss_mix``'s - ``lam`` on ``labels[b]``, ``1 - lam`` on
+    the partner's label, smoothed to ``(1 - eps) * t + eps / C`` - used per class; ``target_threshold`` (None or negative: off) then turns it into
+    ``t > threshold``.  The hard part is the mean over all ``B * C`` elements (``BCEWithLogitsLoss()``), or with ``sum_classes`` the sum over the
+    classes and the mean over the batch.  ``teacher`` (``[B, C]``: its output on the mixed images) or ``table`` + ``index`` (the mixed soft label of
+    ``kd_ce_loss_table_mix``) add the KD part with weight ``kd_alpha``, the hard part then has ``1 - kd_alpha``; with neither, the loss is the hard
+    part.  An index outside the table makes the loss and that row of the gradient NaN; nothing here synchronises."""
+    if target_threshold is not None and not isinstance(target_threshold, (int, float)):
+        raise RuntimeError("kd_bce_loss: target_threshold must be None or a Python number (a tensor would have to be read on the host)")
+    return _KDBCELossFn.apply(student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes)

@@ -30,6 +30,8 @@ SIGNATURES = {
     "qatvit_kd_ce_loss_table": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "qatvit_kd_ce_loss_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float,
                                       c_void_p, c_void_p, c_void_p]),
+    "qatvit_kd_bce_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float,
+                                   c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "qatvit_optim_grad_norm": (c_int, [c_void_p] * 4 + [c_int32, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "qatvit_optim_adamw": (c_int, [c_void_p] * 7 + [c_int32, c_int64] + [c_double] * 5 + [c_int64, c_void_p, c_void_p]),
     "qatvit_optim_adamw_groups": (c_int, [c_void_p] * 8 + [c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
