@@ -866,110 +866,79 @@ __device__ inline bf16x8 tr_frag_ds(const char* img_vq, int tokA, int tokB, int 
     const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, v);
 }
-// LIVE: AttnArgs::live_q_tiles / dO_cls apply (an instantiation of its own: the ordinary one keeps its compile-time sweep count and unconditional loads -
-// with both as run-time values every launch measured 2 - 4 us slower)
-template <int NKT, bool O16 = false, bool LIVE = false>
-__global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
-    constexpr int HD = 64, NWV = 8;
-    float mul16 = 1.f, am16 = 0.f;
-    if constexpr (O16) mul16 = *p.o16_mul;
-    constexpr int U = (NKT + NWV - 1) / NWV;   // key tiles per wave
-    constexpr int IMG = NKT * 16 * HD * 2, SVQ = NKT * 16 * kSRow, SIMG = 2 * SVQ;   // (SVQ: one 16-query tile's plane)
-    constexpr int KK = HD / 32, ND = HD / 16;
+
+// ---- one head of the fused backward: shape, LDS layout and the per-head body (conversion, sweep, dK / dV epilogue) that k_attn_bwd_fused and its
+// persistent form k_attn_bwd_pipe both call.  Every piece is force-inlined: the kernels differ in when a head's loads are requested, not in what is done
+// with them - instruction order and summation order per head are one text.
+template <int NKT>
+struct BwdHead {
+    static constexpr int HD = 64, NWV = 8;
+    static constexpr int U = (NKT + NWV - 1) / NWV;   // key tiles per wave
+    static constexpr int KK = HD / 32, ND = HD / 16;
+    static constexpr int CH = HD / 8, TOTAL = NKT * 16 * CH, ITERS = (TOTAL + NWV * 64 - 1) / (NWV * 64);   // staging: 16-byte chunks, per thread
+    static constexpr int IMG = NKT * 16 * HD * 2, SVQ = NKT * 16 * kSRow, SIMG = 2 * SVQ;   // (SVQ: one 16-query tile's plane)
     static_assert(2 * ND == NWV, "one dQ^T tile (16 features x 16 queries of a query pair) per wave");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* sQt = smem;               // [token][d] images for transposed reads: Q and K integers, dO hi / lo
-    char* sDh = smem + IMG;
-    char* sDl = smem + 2 * IMG;
-    char* sKt = smem + 3 * IMG;
-    char* sSh = smem + 4 * IMG;     // [query tile of the pair][key][16 queries] image of the current query pair's dS, hi / lo
-    char* sSl = sSh + SIMG;
-    float* sLse = reinterpret_cast<float*>(sSl + SIMG);
-    float* sDlt = sLse + NKT * 16;
-    uint2* sM = reinterpret_cast<uint2*>(sDlt + NKT * 16);   // STE mask bits of this head's q | k | v slices: [3][T] rows of HD / 8 = 8 bytes
-    float* sCs = reinterpret_cast<float*>(sM + 3 * NKT * 16);   // this head's 3 x 64 per-column scales (q | k | v), 1.0 without col_scale
-    const AQP q = make_aqp(p.qp, p.qmin, p.qmax);
-    const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
-    const int T = p.T, D = p.D, ld = 3 * D;
     static_assert(NKT * 16 <= NWV * 64, "one softmax constant per thread");
-    const int ci = min((int)threadIdx.x, NKT * 16 - 1);
-    const float lse_i = ci < T ? -p.lse[(int64_t)blockIdx.x * (NKT * 16) + ci] * kLog2e : -INFINITY;   // (see k_attn_bwd_dkv)
-    const int64_t sl = (int64_t)T * HD;
-    const uint8_t* const cbase = p.codes + (int64_t)blockIdx.x * 3 * sl;
-    const uint8_t* const mbase = p.cmask + (int64_t)blockIdx.x * 3 * (sl / 8);
-    const float coff = q.fqmin - q.zp;
-    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nkt = (T + 15) / 16;
-    int jt[U];
-    bool has[U], kvalid[U];
-    // the owned V row fragments from the saved codes, requested first (the K fragments are re-read from the K image every sweep step: 16 registers)
-    uint2 vc[U][KK];
+    // dK / dV leave through a wave-private LDS tile ([key][64 features] bf16, rows 144 B apart: 16-byte aligned, 2-way conflicts at most) so that the global
+    // stores are 16 bytes per lane in whole 128-byte row segments - straight from the accumulator layout they would be 8-byte pieces, 32 bytes
+    // per row and instruction: twice the store instructions, half-used lines.  The images are dead: one barrier, then each wave has its own 9 KiB.
+    static constexpr int kERow = 144;
+    static constexpr int kBytes = 4 * IMG + 2 * SIMG + 2 * NKT * 16 * 4 + 3 * NKT * 16 * 8 + 3 * HD * 4;   // NKT = 14: 151,296 B
+    static_assert(NWV * 4 * 16 * kERow <= 4 * IMG, "the epilogue tiles overlay the images");
+    char* sQt;     // [token][d] images for transposed reads: Q and K integers, dO hi / lo
+    char* sDh;
+    char* sDl;
+    char* sKt;
+    char* sSh;     // [query tile of the pair][key][16 queries] image of the current query pair's dS, hi / lo
+    char* sSl;
+    float* sLse;
+    float* sDlt;
+    uint2* sM;     // STE mask bits of this head's q | k | v slices: [3][T] rows of HD / 8 = 8 bytes
+    float* sCs;    // this head's 3 x 64 per-column scales (q | k | v), 1.0 without col_scale
+    __device__ __forceinline__ explicit BwdHead(char* smem)
+        : sQt(smem), sDh(smem + IMG), sDl(smem + 2 * IMG), sKt(smem + 3 * IMG), sSh(smem + 4 * IMG), sSl(sSh + SIMG),
+          sLse(reinterpret_cast<float*>(sSl + SIMG)), sDlt(sLse + NKT * 16), sM(reinterpret_cast<uint2*>(sDlt + NKT * 16)),
+          sCs(reinterpret_cast<float*>(sM + 3 * NKT * 16)) {}
+    __device__ __forceinline__ char* tile(int wave) const { return sQt + wave * (4 * 16 * kERow); }   // [k hi | k lo | v hi | v lo][16 keys][144 B]
+
+    // one head's loads: the owned V rows' codes, per 16-byte chunk the Q and K codes, dO and O hi / lo (20 registers per chunk, four chunks per thread), and
+    // the head's mask rows (two 8-byte rows per thread).  (The member order is the order in which k_attn_bwd_pipe's loop carries them: with the mask rows
+    // behind ol the register allocator split two dwords of the last O chunk off their load tuple - a copy, i.e. a vmcnt(0), right behind the late loads.)
+    struct Loads {
+        uint2 vc[U][KK], cq[ITERS], ck[ITERS], mrow[2];
+        float4 da4[ITERS], db4[ITERS];
+        uint4 oh[ITERS], ol[ITERS];
+        __device__ __forceinline__ void pin() const {   // (qv_device.h pin4_in: in front of the first use of any of them, or part of the loads sinks to its use)
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        jt[u] = wave + u * NWV;
-        has[u] = jt[u] < nkt;
-        const int krow = min(16 * jt[u] + r, T - 1);
-        kvalid[u] = has[u] && 16 * jt[u] + r < T;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) {
-            vc[u][kk] = *reinterpret_cast<const uint2*>(cbase + 2 * sl + krow * HD + 32 * kk + 8 * g);
-        }
-    }
-    // Staging: EVERY global load of the workgroup is requested before anything is converted (Q and K codes, dO, O hi / lo: 20 registers per
-    // 16-byte chunk, four chunks per thread) - with one workgroup per CU each dependent round trip is exposed in full.
-    constexpr int CH = HD / 8, TOTAL = NKT * 16 * CH, ITERS = (TOTAL + NWV * 64 - 1) / (NWV * 64);
-    uint2 cq[ITERS], ck[ITERS];
-    float4 da4[ITERS], db4[ITERS];
-    uint4 oh[ITERS], ol[ITERS];
-    {
-        const float* const dOb = p.dO + (int64_t)b * (LIVE && p.dO_cls ? 1 : T) * D + h * HD;
-        const __bf16* const Ohb = p.O_hi + (int64_t)b * T * D + h * HD;
-        const __bf16* const Olb = p.O_lo + (int64_t)b * T * D + h * HD;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int i = threadIdx.x + it * NWV * 64, tok = min(i / CH, T - 1), ch = i % CH;   // (branch-free: a padded token reads the last real one)
-            cq[it] = *reinterpret_cast<const uint2*>(cbase + tok * HD + ch * 8);
-            ck[it] = *reinterpret_cast<const uint2*>(cbase + sl + tok * HD + ch * 8);
-            const int64_t off = (int64_t)tok * D + ch * 8;
-            // (the [B, D] form: dO has the rows of token 0 only, and O is needed for delta = rowsum(dO . O) alone - every other token loads neither: a
-            //  quarter of the head's bytes instead of all of them; for it >= 1 the branch is wave-uniform)
-            if constexpr (LIVE) {
-                da4[it] = db4[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-                oh[it] = ol[it] = make_uint4(0u, 0u, 0u, 0u);
-            }
-            if (!LIVE || !p.dO_cls || tok == 0) {
-                da4[it] = reinterpret_cast<const float4*>(dOb + off)[0];
-                db4[it] = reinterpret_cast<const float4*>(dOb + off)[1];
-                oh[it] = *reinterpret_cast<const uint4*>(Ohb + off);
-                ol[it] = *reinterpret_cast<const uint4*>(Olb + off);
+            for (int it = 0; it < ITERS; ++it) {
+                pin4_in(da4[it]); pin4_in(db4[it]);
+                asm volatile("" ::"v"(oh[it].x), "v"(oh[it].y), "v"(oh[it].z), "v"(oh[it].w), "v"(ol[it].x), "v"(ol[it].y), "v"(ol[it].z), "v"(ol[it].w));
+                asm volatile("" ::"v"(cq[it].x), "v"(cq[it].y), "v"(ck[it].x), "v"(ck[it].y));
             }
         }
-    }
-    // the head's three mask slices are one contiguous run of 3 T rows: two 8-byte loads per thread here instead of 23 single-byte loads per
-    // thread for the epilogues (each a full 64-lane address instruction)
-    uint2 mrow[2];
+    };
+    struct DkvConsts {   // what the dK / dV epilogue reads from the images before they die
+        float4 ckc[ND], cvc[ND];
+        uint2 mkr[U], mvr[U];
+        char* sE;          // this wave's tile
+        int erow, ech;     // read-back: 8 lanes per key row, two passes of 8 rows
+    };
+};
+
+// Conversion: a head's loaded registers -> the Q / K / dO hi / dO lo images, sDlt (delta / scale), the global delta and the decoded V fragments.
+// Loads::pin() is its first step; it is a call of its own because the small LDS writes of a kernel (mask rows, softmax constants) sit between the two.
+// zr: the zero of a padded row (a constant, or a register the caller made opaque), tid: the thread index likewise.
+template <int NKT>
+__device__ __forceinline__ void bwd_convert(const BwdHead<NKT>& s, const typename BwdHead<NKT>::Loads& ld, int tid, int T, uint32_t zr, float coff, float inv_scale,
+                             float* gdelta, bf16x8 (&vf)[BwdHead<NKT>::U][BwdHead<NKT>::KK]) {
+    using S = BwdHead<NKT>;
+    constexpr int HD = S::HD, NWV = S::NWV, CH = S::CH;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) mrow[k] = reinterpret_cast<const uint2*>(mbase)[min((int)threadIdx.x + k * NWV * 64, 3 * T - 1)];
-    if (threadIdx.x < NKT * 16) sLse[threadIdx.x] = lse_i;
-    if (threadIdx.x < 3 * HD) sCs[threadIdx.x] = p.col_scale ? p.col_scale[(threadIdx.x / HD) * D + h * HD + (threadIdx.x % HD)] : 1.f;
-    for (int i = threadIdx.x; i < 2 * SIMG / 16; i += NWV * 64) reinterpret_cast<uint4*>(sSh)[i] = make_uint4(0u, 0u, 0u, 0u);   // key tiles nobody owns stay zero
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        pin4_in(da4[it]); pin4_in(db4[it]);
-        asm volatile("" ::"v"(oh[it].x), "v"(oh[it].y), "v"(oh[it].z), "v"(oh[it].w), "v"(ol[it].x), "v"(ol[it].y), "v"(ol[it].z), "v"(ol[it].w));
-        asm volatile("" ::"v"(cq[it].x), "v"(cq[it].y), "v"(ck[it].x), "v"(ck[it].y));
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-        if ((int)threadIdx.x + k * NWV * 64 < 3 * T) sM[threadIdx.x + k * NWV * 64] = mrow[k];
-    float* const gdelta = p.delta ? p.delta + (int64_t)blockIdx.x * (NKT * 16) : nullptr;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const int i = threadIdx.x + it * NWV * 64, tok = i / CH, ch = i % CH;
+    for (int it = 0; it < S::ITERS; ++it) {
+        const int i = tid + it * NWV * 64, tok = i / CH, ch = i % CH;
         const bool real = tok < T;   // padded token rows are zero in every image
-        const float v[8] = {da4[it].x, da4[it].y, da4[it].z, da4[it].w, db4[it].x, db4[it].y, db4[it].z, db4[it].w};
-        const uint32_t wh[4] = {oh[it].x, oh[it].y, oh[it].z, oh[it].w}, wl[4] = {ol[it].x, ol[it].y, ol[it].z, ol[it].w};
+        const float v[8] = {ld.da4[it].x, ld.da4[it].y, ld.da4[it].z, ld.da4[it].w, ld.db4[it].x, ld.db4[it].y, ld.db4[it].z, ld.db4[it].w};
+        const uint32_t wh[4] = {ld.oh[it].x, ld.oh[it].y, ld.oh[it].z, ld.oh[it].w}, wl[4] = {ld.ol[it].x, ld.ol[it].y, ld.ol[it].z, ld.ol[it].w};
         float d = 0.f;   // delta = sum_d dO . O over the row: 8 features here, the row's 8 chunks on consecutive lanes
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -979,43 +948,44 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
         d += __shfl_xor(d, 1, 64);
         d += __shfl_xor(d, 2, 64);
         d += __shfl_xor(d, 4, 64);
-        if (i < TOTAL) {
-            const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-            *reinterpret_cast<uint4*>(sQt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(cq[it], coff)) : z;
-            *reinterpret_cast<uint4*>(sKt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(ck[it], coff)) : z;
+        if (i < S::TOTAL) {
+            const uint4 z = make_uint4(zr, zr, zr, zr);
+            *reinterpret_cast<uint4*>(s.sQt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(ld.cq[it], coff)) : z;
+            *reinterpret_cast<uint4*>(s.sKt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(ld.ck[it], coff)) : z;
             uint32_t H[4], L[4];
             split_pair(v[0], v[1], H[0], L[0]); split_pair(v[2], v[3], H[1], L[1]);
             split_pair(v[4], v[5], H[2], L[2]); split_pair(v[6], v[7], H[3], L[3]);
-            *reinterpret_cast<uint4*>(sDh + tr_off<HD>(tok, ch)) = real ? make_uint4(H[0], H[1], H[2], H[3]) : z;
-            *reinterpret_cast<uint4*>(sDl + tr_off<HD>(tok, ch)) = real ? make_uint4(L[0], L[1], L[2], L[3]) : z;
+            *reinterpret_cast<uint4*>(s.sDh + tr_off<HD>(tok, ch)) = real ? make_uint4(H[0], H[1], H[2], H[3]) : z;
+            *reinterpret_cast<uint4*>(s.sDl + tr_off<HD>(tok, ch)) = real ? make_uint4(L[0], L[1], L[2], L[3]) : z;
             if (ch == 0) {
-                sDlt[tok] = d * q.inv;
+                s.sDlt[tok] = d * inv_scale;
                 if (real && gdelta) gdelta[tok] = d;
             }
         }
     }
-    bf16x8 vf[U][KK];
 #pragma unroll
-    for (int u = 0; u < U; ++u)
+    for (int u = 0; u < S::U; ++u)
 #pragma unroll
-        for (int kk = 0; kk < KK; ++kk) vf[u][kk] = decode8(vc[u][kk], coff);
-    // this wave's dQ^T tile of every query pair: features 16 jd .. + 15, queries 16 (2 qs + vq) .. + 15
+        for (int kk = 0; kk < S::KK; ++kk) vf[u][kk] = decode8(ld.vc[u][kk], coff);
+}
+
+// Sweep: nqs query pairs (NKT / 2 for the full sweep; fewer under AttnArgs::live_q_tiles) against this wave's key tiles jt[]: dK / dV accumulate in
+// dk / dv (zeroed by the kernel: zeroed in here, the LIVE instantiations spill 50 registers), each pair's dQ^T tile - features 16 jd .. + 15, queries 16 (2 qs + vq) .. + 15 for this wave - is finished over all keys and stored.
+// ckq: the query column scales of this lane's four features (1.0 without col_scale); c, c2: scale^2 / sqrt(d), and that times log2(e).
+template <int NKT, bool O16>
+__device__ __forceinline__ void bwd_sweep(const AttnArgs& p, const BwdHead<NKT>& s, int nqs, int lane, int wave, int b, int h, float c, float c2, const float4& ckq,
+                           float mul16, float& am16, const int (&jt)[BwdHead<NKT>::U], const bool (&has)[BwdHead<NKT>::U],
+                           const bool (&kvalid)[BwdHead<NKT>::U], const bf16x8 (&vf)[BwdHead<NKT>::U][BwdHead<NKT>::KK],
+                           f32x4 (&dk)[BwdHead<NKT>::U][BwdHead<NKT>::ND], f32x4 (&dv)[BwdHead<NKT>::U][BwdHead<NKT>::ND]) {
+    using S = BwdHead<NKT>;
+    constexpr int HD = S::HD, U = S::U, KK = S::KK, ND = S::ND, SVQ = S::SVQ;
+    const int T = p.T, ld = 3 * p.D, r = lane & 15, g = lane >> 4;
     const int jd = wave & (ND - 1), vq = wave / ND;
-    float4 ckq = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (p.col_scale) ckq = *reinterpret_cast<const float4*>(p.col_scale + h * HD + 16 * jd + 4 * g);
-    __syncthreads();
-    const float c = q.s * q.s * p.softmax_scale, c2 = c * kLog2e;
-    f32x4 dk[U][ND], dv[U][ND];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int id = 0; id < ND; ++id) dk[u][id] = dv[u][id] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // the query pairs that carry a gradient (AttnArgs::live_q_tiles): a pair without one adds exact zeros to dK / dV and its dQ is zero
-    const int nqs = LIVE && p.live_q_tiles > 0 ? min(NKT / 2, (p.live_q_tiles + 1) / 2) : NKT / 2;
+    char* const sQt = s.sQt; char* const sDh = s.sDh; char* const sDl = s.sDl; char* const sKt = s.sKt; char* const sSh = s.sSh; char* const sSl = s.sSl;
 #pragma unroll 1
     for (int qs = 0; qs < nqs; ++qs) {
         const int qme = 16 * (2 * qs + vq) + r;
-        const uint32_t mqb = reinterpret_cast<const uint8_t*>(sM)[min(qme, T - 1) * 8 + 2 * jd + (g >> 1)];
+        const uint32_t mqb = reinterpret_cast<const uint8_t*>(s.sM)[min(qme, T - 1) * 8 + 2 * jd + (g >> 1)];
         // phase 1: S and dP of every owned key tile (the query-row fragments are dead afterwards: 48 registers)
         f32x4 sacc[U][2], dpv[U][2];
         {
@@ -1063,8 +1033,8 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
 #pragma unroll
                 for (int v = 0; v < 2; ++v) {
                     // S orientation: this lane's key = 16 jt + r, query = 16 (2qs + v) + 4g + e: the four softmax constants are one 16-byte read
-                    const float4 nl = *reinterpret_cast<const float4*>(sLse + 16 * (2 * qs + v) + 4 * g);
-                    const float4 dl = *reinterpret_cast<const float4*>(sDlt + 16 * (2 * qs + v) + 4 * g);
+                    const float4 nl = *reinterpret_cast<const float4*>(s.sLse + 16 * (2 * qs + v) + 4 * g);
+                    const float4 dl = *reinterpret_cast<const float4*>(s.sDlt + 16 * (2 * qs + v) + 4 * g);
                     const float nlv[4] = {nl.x, nl.y, nl.z, nl.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -1130,6 +1100,182 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
             }
         }
     }
+}
+
+// dK / dV epilogue: accumulators hold row = feature 16id + 4g + e, col = key 16j + r -> 8-B (4 x bf16) stores along d  (as k_attn_bwd_dkv).
+// bwd_dkv_consts reads what the epilogue needs from the images - the k | v column scales (from the LDS copy: a global load here is a full round trip with
+// nothing to hide it) and the mask rows of this lane's keys krow[] - and ends with the barrier behind which the images are dead; bwd_dkv_tile then
+// scales, masks and stores one owned key tile jt through the wave-private tile (BwdHead::kERow), 16 bytes per lane.
+template <int NKT>
+__device__ __forceinline__ void bwd_dkv_consts(const BwdHead<NKT>& s, int T, int lane, int wave, const int (&krow)[BwdHead<NKT>::U], typename BwdHead<NKT>::DkvConsts& k) {
+    using S = BwdHead<NKT>;
+    const int g = lane >> 4;
+#pragma unroll
+    for (int id = 0; id < S::ND; ++id) {
+        k.ckc[id] = *reinterpret_cast<const float4*>(s.sCs + S::HD + 16 * id + 4 * g);
+        k.cvc[id] = *reinterpret_cast<const float4*>(s.sCs + 2 * S::HD + 16 * id + 4 * g);
+    }
+#pragma unroll
+    for (int u = 0; u < S::U; ++u) {   // (before the barrier: the epilogue tiles overwrite the front of the LDS only, but keep the read next to the other image reads)
+        k.mkr[u] = s.sM[T + krow[u]];
+        k.mvr[u] = s.sM[2 * T + krow[u]];
+    }
+    lds_barrier();
+    k.sE = s.tile(wave);
+    k.erow = lane >> 3;
+    k.ech = lane & 7;
+}
+template <int NKT, bool O16>
+__device__ __forceinline__ void bwd_dkv_tile(const AttnArgs& p, int lane, int b, int h, int jt, float c,
+                              const typename BwdHead<NKT>::DkvConsts& k, int u, const f32x4 (&dk)[BwdHead<NKT>::ND], const f32x4 (&dv)[BwdHead<NKT>::ND],
+                              float mul16, float& am16) {
+    using S = BwdHead<NKT>;
+    constexpr int HD = S::HD, kERow = S::kERow;
+    const int T = p.T, D = p.D, ld = 3 * D, r = lane & 15, g = lane >> 4;
+    char* const sE = k.sE;
+    const int erow = k.erow, ech = k.ech;   // (computed once, behind the barrier of bwd_dkv_consts)
+#pragma unroll
+    for (int id = 0; id < S::ND; ++id) {
+        const float4 ck = k.ckc[id], cv = k.cvc[id];
+        const uint32_t bk = (id < 2 ? k.mkr[u].x : k.mkr[u].y) >> (16 * (id & 1) + 4 * g), bv = (id < 2 ? k.mvr[u].x : k.mvr[u].y) >> (16 * (id & 1) + 4 * g);
+        const float vk[4] = {(bk & 1u) ? dk[id][0] * c * ck.x : 0.f, (bk & 2u) ? dk[id][1] * c * ck.y : 0.f,
+                             (bk & 4u) ? dk[id][2] * c * ck.z : 0.f, (bk & 8u) ? dk[id][3] * c * ck.w : 0.f};
+        const float vv[4] = {(bv & 1u) ? dv[id][0] * cv.x : 0.f, (bv & 2u) ? dv[id][1] * cv.y : 0.f,
+                             (bv & 4u) ? dv[id][2] * cv.z : 0.f, (bv & 8u) ? dv[id][3] * cv.w : 0.f};
+        uint2 kh, kl, vh, vl;
+        char* const e = sE + r * kERow + (16 * id + 4 * g) * 2;
+        if constexpr (O16) {   // (padded keys hold zero accumulators: P = 0 and dS = 0 for them)
+            am16 = fmaxf(fmaxf(am16, fmaxf(fmaxf(fabsf(vk[0]), fabsf(vk[1])), fmaxf(fabsf(vk[2]), fabsf(vk[3])))),
+                         fmaxf(fmaxf(fabsf(vv[0]), fabsf(vv[1])), fmaxf(fabsf(vv[2]), fabsf(vv[3]))));
+            kh = make_uint2(pk_f16(vk[0] * mul16, vk[1] * mul16), pk_f16(vk[2] * mul16, vk[3] * mul16));
+            vh = make_uint2(pk_f16(vv[0] * mul16, vv[1] * mul16), pk_f16(vv[2] * mul16, vv[3] * mul16));
+            *reinterpret_cast<uint2*>(e) = kh;
+            *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
+        } else {
+            split_pair(vk[0], vk[1], kh.x, kl.x); split_pair(vk[2], vk[3], kh.y, kl.y);
+            split_pair(vv[0], vv[1], vh.x, vl.x); split_pair(vv[2], vv[3], vh.y, vl.y);
+            *reinterpret_cast<uint2*>(e) = kh;
+            *reinterpret_cast<uint2*>(e + 16 * kERow) = kl;
+            *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
+            *reinterpret_cast<uint2*>(e + 48 * kERow) = vl;
+        }
+    }
+    wave_lds_fence();   // (wave-private: LDS is in order per wave, no barrier)
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int key = 16 * jt + 8 * half + erow;
+        const char* const e = sE + (8 * half + erow) * kERow + ech * 16;
+        const uint4 kh = *reinterpret_cast<const uint4*>(e), vh = *reinterpret_cast<const uint4*>(e + 32 * kERow);
+        const int64_t offk = ((int64_t)b * T + key) * ld + D + h * HD + 8 * ech;
+        if constexpr (O16) {
+            if (key < T) {
+                *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
+                *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
+            }
+        } else {
+            const uint4 kl = *reinterpret_cast<const uint4*>(e + 16 * kERow), vl = *reinterpret_cast<const uint4*>(e + 48 * kERow);
+            if (key < T) {
+                *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
+                *reinterpret_cast<uint4*>(p.dqkv_lo + offk) = kl;
+                *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
+                *reinterpret_cast<uint4*>(p.dqkv_lo + offk + D) = vl;
+            }
+        }
+    }
+    wave_lds_fence();   // the tile is read before the next key tile overwrites it
+}
+
+// LIVE: AttnArgs::live_q_tiles / dO_cls apply (an instantiation of its own: the ordinary one keeps its compile-time sweep count and unconditional loads -
+// with both as run-time values every launch measured 2 - 4 us slower)
+template <int NKT, bool O16 = false, bool LIVE = false>
+__global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
+    using S = BwdHead<NKT>;
+    constexpr int HD = S::HD, NWV = S::NWV, U = S::U, KK = S::KK, ND = S::ND, CH = S::CH, ITERS = S::ITERS;
+    float mul16 = 1.f, am16 = 0.f;
+    if constexpr (O16) mul16 = *p.o16_mul;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const S s(smem);
+    const AQP q = make_aqp(p.qp, p.qmin, p.qmax);
+    const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
+    const int T = p.T, D = p.D, ld = 3 * D;
+    const int ci = min((int)threadIdx.x, NKT * 16 - 1);
+    const float lse_i = ci < T ? -p.lse[(int64_t)blockIdx.x * (NKT * 16) + ci] * kLog2e : -INFINITY;   // (see k_attn_bwd_dkv)
+    const int64_t sl = (int64_t)T * HD;
+    const uint8_t* const cbase = p.codes + (int64_t)blockIdx.x * 3 * sl;
+    const uint8_t* const mbase = p.cmask + (int64_t)blockIdx.x * 3 * (sl / 8);
+    const float coff = q.fqmin - q.zp;
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nkt = (T + 15) / 16;
+    int jt[U];
+    bool has[U], kvalid[U];
+    typename S::Loads in;
+    // the owned V row fragments from the saved codes, requested first (the K fragments are re-read from the K image every sweep step: 16 registers)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        jt[u] = wave + u * NWV;
+        has[u] = jt[u] < nkt;
+        const int krow = min(16 * jt[u] + r, T - 1);
+        kvalid[u] = has[u] && 16 * jt[u] + r < T;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+            in.vc[u][kk] = *reinterpret_cast<const uint2*>(cbase + 2 * sl + krow * HD + 32 * kk + 8 * g);
+        }
+    }
+    // Staging: EVERY global load of the workgroup is requested before anything is converted (Q and K codes, dO, O hi / lo: 20 registers per
+    // 16-byte chunk, four chunks per thread) - with one workgroup per CU each dependent round trip is exposed in full.
+    {
+        const float* const dOb = p.dO + (int64_t)b * (LIVE && p.dO_cls ? 1 : T) * D + h * HD;
+        const __bf16* const Ohb = p.O_hi + (int64_t)b * T * D + h * HD;
+        const __bf16* const Olb = p.O_lo + (int64_t)b * T * D + h * HD;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int i = threadIdx.x + it * NWV * 64, tok = min(i / CH, T - 1), ch = i % CH;   // (branch-free: a padded token reads the last real one)
+            in.cq[it] = *reinterpret_cast<const uint2*>(cbase + tok * HD + ch * 8);
+            in.ck[it] = *reinterpret_cast<const uint2*>(cbase + sl + tok * HD + ch * 8);
+            const int64_t off = (int64_t)tok * D + ch * 8;
+            // (the [B, D] form: dO has the rows of token 0 only, and O is needed for delta = rowsum(dO . O) alone - every other token loads neither: a
+            //  quarter of the head's bytes instead of all of them; for it >= 1 the branch is wave-uniform)
+            if constexpr (LIVE) {
+                in.da4[it] = in.db4[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+                in.oh[it] = in.ol[it] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            if (!LIVE || !p.dO_cls || tok == 0) {
+                in.da4[it] = reinterpret_cast<const float4*>(dOb + off)[0];
+                in.db4[it] = reinterpret_cast<const float4*>(dOb + off)[1];
+                in.oh[it] = *reinterpret_cast<const uint4*>(Ohb + off);
+                in.ol[it] = *reinterpret_cast<const uint4*>(Olb + off);
+            }
+        }
+    }
+    // the head's three mask slices are one contiguous run of 3 T rows: two 8-byte loads per thread here instead of 23 single-byte loads per
+    // thread for the epilogues (each a full 64-lane address instruction)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) in.mrow[k] = reinterpret_cast<const uint2*>(mbase)[min((int)threadIdx.x + k * NWV * 64, 3 * T - 1)];
+    if (threadIdx.x < NKT * 16) s.sLse[threadIdx.x] = lse_i;
+    if (threadIdx.x < 3 * HD) s.sCs[threadIdx.x] = p.col_scale ? p.col_scale[(threadIdx.x / HD) * D + h * HD + (threadIdx.x % HD)] : 1.f;
+    for (int i = threadIdx.x; i < 2 * S::SIMG / 16; i += NWV * 64) reinterpret_cast<uint4*>(s.sSh)[i] = make_uint4(0u, 0u, 0u, 0u);   // key tiles nobody owns stay zero
+    in.pin();
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if ((int)threadIdx.x + k * NWV * 64 < 3 * T) s.sM[threadIdx.x + k * NWV * 64] = in.mrow[k];
+    float* const gdelta = p.delta ? p.delta + (int64_t)blockIdx.x * (NKT * 16) : nullptr;
+    bf16x8 vf[U][KK];
+    bwd_convert(s, in, threadIdx.x, T, 0u, coff, q.inv, gdelta, vf);
+    // the query column scales of this wave's dQ^T tile (features 16 jd .. + 15), straight from global: requested here, they arrive under the barrier
+    const int jd = wave & (ND - 1);
+    float4 ckq = make_float4(1.f, 1.f, 1.f, 1.f);
+    if (p.col_scale) ckq = *reinterpret_cast<const float4*>(p.col_scale + h * HD + 16 * jd + 4 * g);
+    __syncthreads();
+    const float c = q.s * q.s * p.softmax_scale, c2 = c * kLog2e;
+    f32x4 dk[U][ND], dv[U][ND];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int id = 0; id < ND; ++id) dk[u][id] = dv[u][id] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // the query pairs that carry a gradient (AttnArgs::live_q_tiles): a pair without one adds exact zeros to dK / dV and its dQ is zero
+    const int nqs = LIVE && p.live_q_tiles > 0 ? min(NKT / 2, (p.live_q_tiles + 1) / 2) : NKT / 2;
+    bwd_sweep<NKT, O16>(p, s, nqs, lane, wave, b, h, c, c2, ckq, mul16, am16, jt, has, kvalid, vf, dk, dv);
     // the dQ of the query pairs the sweep skipped: zeros (the qkv dgrad and weight gradient read the whole plane), 16 bytes per thread, whole 128-byte rows
     if constexpr (LIVE)
     for (int i = threadIdx.x; i < (T - 32 * nqs) * (HD / 8); i += NWV * 64) {
@@ -1137,79 +1283,15 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
         *reinterpret_cast<uint4*>(p.dqkv_hi + offq) = make_uint4(0u, 0u, 0u, 0u);
         if constexpr (!O16) *reinterpret_cast<uint4*>(p.dqkv_lo + offq) = make_uint4(0u, 0u, 0u, 0u);
     }
-    // dK / dV: accumulators hold row = feature 16id + 4g + e, col = key 16j + r -> 8-B (4 x bf16) stores along d  (as k_attn_bwd_dkv)
-    float4 ckc[ND], cvc[ND];   // (from the LDS copy the prologue made: a global load here is a full round trip with nothing to hide it)
+    int krow[U];   // (recomputed: two registers less across the sweep)
 #pragma unroll
-    for (int id = 0; id < ND; ++id) {
-        ckc[id] = *reinterpret_cast<const float4*>(sCs + HD + 16 * id + 4 * g);
-        cvc[id] = *reinterpret_cast<const float4*>(sCs + 2 * HD + 16 * id + 4 * g);
-    }
-    // Through a wave-private LDS tile ([key][64 features] bf16, rows 144 B apart: 16-byte aligned, 2-way conflicts at most) so that the global
-    // stores are 16 bytes per lane in whole 128-byte row segments - straight from the accumulator layout they would be 8-byte pieces, 32 bytes
-    // per row and instruction: twice the store instructions, half-used lines.  The images are dead: one barrier, then each wave has its own 9 KiB.
-    uint2 mkr[U], mvr[U];   // the mask rows of this lane's keys (before the barrier: the epilogue tiles overwrite the front of the LDS only, but
-#pragma unroll              // keep the read next to the other image reads)
-    for (int u = 0; u < U; ++u) {
-        const int krow = min(16 * jt[u] + r, T - 1);
-        mkr[u] = sM[T + krow];
-        mvr[u] = sM[2 * T + krow];
-    }
-    lds_barrier();
-    constexpr int kERow = 144;
-    char* const sE = smem + wave * (4 * 16 * kERow);   // [k hi | k lo | v hi | v lo][16 keys][144 B]
-    const int erow = lane >> 3, ech = lane & 7;       // read-back: 8 lanes per key row, two passes of 8 rows
+    for (int u = 0; u < U; ++u) krow[u] = min(16 * jt[u] + r, T - 1);
+    typename S::DkvConsts kc;
+    bwd_dkv_consts(s, T, lane, wave, krow, kc);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (!has[u]) continue;   // wave-uniform
-#pragma unroll
-        for (int id = 0; id < ND; ++id) {
-            const float4 ck = ckc[id], cv = cvc[id];
-            const uint32_t bk = (id < 2 ? mkr[u].x : mkr[u].y) >> (16 * (id & 1) + 4 * g), bv = (id < 2 ? mvr[u].x : mvr[u].y) >> (16 * (id & 1) + 4 * g);
-            const float vk[4] = {(bk & 1u) ? dk[u][id][0] * c * ck.x : 0.f, (bk & 2u) ? dk[u][id][1] * c * ck.y : 0.f,
-                                 (bk & 4u) ? dk[u][id][2] * c * ck.z : 0.f, (bk & 8u) ? dk[u][id][3] * c * ck.w : 0.f};
-            const float vv[4] = {(bv & 1u) ? dv[u][id][0] * cv.x : 0.f, (bv & 2u) ? dv[u][id][1] * cv.y : 0.f,
-                                 (bv & 4u) ? dv[u][id][2] * cv.z : 0.f, (bv & 8u) ? dv[u][id][3] * cv.w : 0.f};
-            uint2 kh, kl, vh, vl;
-            char* const e = sE + r * kERow + (16 * id + 4 * g) * 2;
-            if constexpr (O16) {   // (padded keys hold zero accumulators: P = 0 and dS = 0 for them)
-                am16 = fmaxf(fmaxf(am16, fmaxf(fmaxf(fabsf(vk[0]), fabsf(vk[1])), fmaxf(fabsf(vk[2]), fabsf(vk[3])))),
-                             fmaxf(fmaxf(fabsf(vv[0]), fabsf(vv[1])), fmaxf(fabsf(vv[2]), fabsf(vv[3]))));
-                kh = make_uint2(pk_f16(vk[0] * mul16, vk[1] * mul16), pk_f16(vk[2] * mul16, vk[3] * mul16));
-                vh = make_uint2(pk_f16(vv[0] * mul16, vv[1] * mul16), pk_f16(vv[2] * mul16, vv[3] * mul16));
-                *reinterpret_cast<uint2*>(e) = kh;
-                *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
-            } else {
-                split_pair(vk[0], vk[1], kh.x, kl.x); split_pair(vk[2], vk[3], kh.y, kl.y);
-                split_pair(vv[0], vv[1], vh.x, vl.x); split_pair(vv[2], vv[3], vh.y, vl.y);
-                *reinterpret_cast<uint2*>(e) = kh;
-                *reinterpret_cast<uint2*>(e + 16 * kERow) = kl;
-                *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
-                *reinterpret_cast<uint2*>(e + 48 * kERow) = vl;
-            }
-        }
-        wave_lds_fence();   // (wave-private: LDS is in order per wave, no barrier)
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const int key = 16 * jt[u] + 8 * half + erow;
-            const char* const e = sE + (8 * half + erow) * kERow + ech * 16;
-            const uint4 kh = *reinterpret_cast<const uint4*>(e), vh = *reinterpret_cast<const uint4*>(e + 32 * kERow);
-            const int64_t offk = ((int64_t)b * T + key) * ld + D + h * HD + 8 * ech;
-            if constexpr (O16) {
-                if (key < T) {
-                    *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
-                    *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
-                }
-            } else {
-                const uint4 kl = *reinterpret_cast<const uint4*>(e + 16 * kERow), vl = *reinterpret_cast<const uint4*>(e + 48 * kERow);
-                if (key < T) {
-                    *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
-                    *reinterpret_cast<uint4*>(p.dqkv_lo + offk) = kl;
-                    *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
-                    *reinterpret_cast<uint4*>(p.dqkv_lo + offk + D) = vl;
-                }
-            }
-        }
-        wave_lds_fence();   // the tile is read before the next key tile overwrites it
+        bwd_dkv_tile<NKT, O16>(p, lane, b, h, jt[u], c, kc, u, dk[u], dv[u], mul16, am16);
     }
     if constexpr (O16) {
         am16 = wave_max(am16);
@@ -1219,7 +1301,7 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
 
 // ============================================================================ backward, fused and persistent: the next head fetched under the sweep
 // k_attn_bwd_fused<NKT, O16> (not LIVE) as gridDim.x <= CU count workgroups that each walk the (image, head) items w, w + gridDim.x, ...: per head the same
-// conversion, sweep and epilogue, instruction order and summation order included - the same bits.  What changes is when the global loads are requested: the
+// conversion, sweep and epilogue (bwd_convert, bwd_sweep, bwd_dkv_consts / bwd_dkv_tile above) - the same bits.  What changes is when the global loads are requested: the
 // per-head launch has all 256 resident workgroups stage at the same moment (HBM-paced, MFMAs idle), sweep at the same moment (HBM idle) and store at the same
 // moment; here the loads of the NEXT head are requested as early as there are registers for them and waited for only at the next conversion, and the
 // epilogue's stores stay in flight under that conversion.
@@ -1230,27 +1312,14 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_fused(const AttnArgs p) {
 // published once per workgroup (atomicMax: order-independent).  profiles/attn_bwd_pipe_c2_b256_per_step.txt has the variants that lost.
 template <int NKT, bool O16>
 __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, const int nitems) {
-    constexpr int HD = 64, NWV = 8;
+    using S = BwdHead<NKT>;
+    constexpr int HD = S::HD, NWV = S::NWV, U = S::U, KK = S::KK, ND = S::ND, CH = S::CH, ITERS = S::ITERS;
     float mul16 = 1.f, am16 = 0.f;
     if constexpr (O16) mul16 = *p.o16_mul;
-    constexpr int U = (NKT + NWV - 1) / NWV;   // key tiles per wave
-    constexpr int IMG = NKT * 16 * HD * 2, SVQ = NKT * 16 * kSRow, SIMG = 2 * SVQ;
-    constexpr int KK = HD / 32, ND = HD / 16;
-    static_assert(2 * ND == NWV, "one dQ^T tile (16 features x 16 queries of a query pair) per wave");
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // (the layout of k_attn_bwd_fused)
-    char* sQt = smem;
-    char* sDh = smem + IMG;
-    char* sDl = smem + 2 * IMG;
-    char* sKt = smem + 3 * IMG;
-    char* sSh = smem + 4 * IMG;
-    char* sSl = sSh + SIMG;
-    float* sLse = reinterpret_cast<float*>(sSl + SIMG);
-    float* sDlt = sLse + NKT * 16;
-    uint2* sM = reinterpret_cast<uint2*>(sDlt + NKT * 16);
-    float* sCs = reinterpret_cast<float*>(sM + 3 * NKT * 16);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const S s(smem);
     const AQP q = make_aqp(p.qp, p.qmin, p.qmax);
-    const int T = p.T, D = p.D, ld = 3 * D;
-    static_assert(NKT * 16 <= NWV * 64, "one softmax constant per thread");
+    const int T = p.T, D = p.D;
     const int64_t sl = (int64_t)T * HD;
     const float coff = q.fqmin - q.zp;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1262,21 +1331,18 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, cons
         jt[u] = wave + u * NWV;
         has[u] = jt[u] < nkt;
     }
-    constexpr int CH = HD / 8, TOTAL = NKT * 16 * CH, ITERS = (TOTAL + NWV * 64 - 1) / (NWV * 64);
     constexpr int kEarly = 1;   // dO / O chunks requested under the sweep
     static_assert(U == 2 && kEarly <= ITERS, "the rest of the loads goes in front of the second (last) key tile of the epilogue");
-    // one head's loads (the registers of k_attn_bwd_fused's prologue; lse and the column scale raw, converted where they are written to LDS)
-    uint2 vc[U][KK], cq[ITERS], ck[ITERS], mrow[2];
-    float4 da4[ITERS], db4[ITERS];
-    uint4 oh[ITERS], ol[ITERS];
+    // one head's loads (lse and the column scale raw, converted where they are written to LDS)
+    typename S::Loads in;
     float lse_raw, cs_raw;
     auto load_codes = [&](int item, int tid) {
         const uint8_t* const cbase = p.codes + (int64_t)item * 3 * sl;
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int i = tid + it * NWV * 64, tok = min(i / CH, T - 1), ch = i % CH;   // (branch-free: a padded token reads the last real one)
-            cq[it] = *reinterpret_cast<const uint2*>(cbase + tok * HD + ch * 8);
-            ck[it] = *reinterpret_cast<const uint2*>(cbase + sl + tok * HD + ch * 8);
+            in.cq[it] = *reinterpret_cast<const uint2*>(cbase + tok * HD + ch * 8);
+            in.ck[it] = *reinterpret_cast<const uint2*>(cbase + sl + tok * HD + ch * 8);
         }
     };
     auto load_grad = [&](int item, int tid, int it0, int it1) {   // dO, O hi / lo of chunks it0 .. it1 - 1
@@ -1289,10 +1355,10 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, cons
             if (it < it0 || it >= it1) continue;
             const int i = tid + it * NWV * 64, tok = min(i / CH, T - 1), ch = i % CH;
             const int64_t off = (int64_t)tok * D + ch * 8;
-            da4[it] = reinterpret_cast<const float4*>(dOb + off)[0];
-            db4[it] = reinterpret_cast<const float4*>(dOb + off)[1];
-            oh[it] = *reinterpret_cast<const uint4*>(Ohb + off);
-            ol[it] = *reinterpret_cast<const uint4*>(Olb + off);
+            in.da4[it] = reinterpret_cast<const float4*>(dOb + off)[0];
+            in.db4[it] = reinterpret_cast<const float4*>(dOb + off)[1];
+            in.oh[it] = *reinterpret_cast<const uint4*>(Ohb + off);
+            in.ol[it] = *reinterpret_cast<const uint4*>(Olb + off);
         }
     };
     auto load_small = [&](int item, int tid) {   // the owned V rows' codes, the head's mask rows, lse, column scales
@@ -1303,9 +1369,9 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, cons
         for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk)
-                vc[u][kk] = *reinterpret_cast<const uint2*>(cbase + 2 * sl + min(16 * jt[u] + r, T - 1) * HD + 32 * kk + 8 * g);
+                in.vc[u][kk] = *reinterpret_cast<const uint2*>(cbase + 2 * sl + min(16 * jt[u] + r, T - 1) * HD + 32 * kk + 8 * g);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) mrow[k] = reinterpret_cast<const uint2*>(mbase)[min(tid + k * NWV * 64, 3 * T - 1)];
+        for (int k = 0; k < 2; ++k) in.mrow[k] = reinterpret_cast<const uint2*>(mbase)[min(tid + k * NWV * 64, 3 * T - 1)];
         lse_raw = p.lse[(int64_t)item * (NKT * 16) + min(tid, NKT * 16 - 1)];   // (the row is NKT * 16 long: in bounds past T too)
         // (without col_scale: any valid float, replaced by 1.0 at the conversion - a conditional load is merged with its alternative, i.e. waited for, right here)
         const int cc = min(tid, 3 * HD - 1);
@@ -1320,25 +1386,25 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, cons
     // ends there: they would be live across the sweep): an empty asm "writes" them.
     auto drop_codes = [&]() {
 #pragma unroll
-        for (int it = 0; it < ITERS; ++it) asm volatile("" : "=v"(cq[it].x), "=v"(cq[it].y), "=v"(ck[it].x), "=v"(ck[it].y));
+        for (int it = 0; it < ITERS; ++it) asm volatile("" : "=v"(in.cq[it].x), "=v"(in.cq[it].y), "=v"(in.ck[it].x), "=v"(in.ck[it].y));
     };
     auto drop_grad = [&](int it0, int it1) {
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             if (it < it0 || it >= it1) continue;
-            asm volatile("" : "=v"(da4[it].x), "=v"(da4[it].y), "=v"(da4[it].z), "=v"(da4[it].w), "=v"(db4[it].x), "=v"(db4[it].y), "=v"(db4[it].z), "=v"(db4[it].w));
-            asm volatile("" : "=v"(oh[it].x), "=v"(oh[it].y), "=v"(oh[it].z), "=v"(oh[it].w), "=v"(ol[it].x), "=v"(ol[it].y), "=v"(ol[it].z), "=v"(ol[it].w));
+            asm volatile("" : "=v"(in.da4[it].x), "=v"(in.da4[it].y), "=v"(in.da4[it].z), "=v"(in.da4[it].w), "=v"(in.db4[it].x), "=v"(in.db4[it].y), "=v"(in.db4[it].z), "=v"(in.db4[it].w));
+            asm volatile("" : "=v"(in.oh[it].x), "=v"(in.oh[it].y), "=v"(in.oh[it].z), "=v"(in.oh[it].w), "=v"(in.ol[it].x), "=v"(in.ol[it].y), "=v"(in.ol[it].z), "=v"(in.ol[it].w));
         }
     };
     auto drop_small = [&]() {
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
-            for (int kk = 0; kk < KK; ++kk) asm volatile("" : "=v"(vc[u][kk].x), "=v"(vc[u][kk].y));
-        asm volatile("" : "=v"(mrow[0].x), "=v"(mrow[0].y), "=v"(mrow[1].x), "=v"(mrow[1].y), "=v"(lse_raw), "=v"(cs_raw));
+            for (int kk = 0; kk < KK; ++kk) asm volatile("" : "=v"(in.vc[u][kk].x), "=v"(in.vc[u][kk].y));
+        asm volatile("" : "=v"(in.mrow[0].x), "=v"(in.mrow[0].y), "=v"(in.mrow[1].x), "=v"(in.mrow[1].y), "=v"(lse_raw), "=v"(cs_raw));
     };
-    for (int i = threadIdx.x; i < 2 * SIMG / 16; i += NWV * 64) reinterpret_cast<uint4*>(sSh)[i] = make_uint4(0u, 0u, 0u, 0u);   // key tiles nobody owns stay zero
-    const int jd = wave & (ND - 1), vq = wave / ND;   // this wave's dQ^T tile of every query pair: features 16 jd .. + 15, queries 16 (2 qs + vq) .. + 15
+    for (int i = threadIdx.x; i < 2 * S::SIMG / 16; i += NWV * 64) reinterpret_cast<uint4*>(s.sSh)[i] = make_uint4(0u, 0u, 0u, 0u);   // key tiles nobody owns stay zero
+    const int jd = wave & (ND - 1);   // this wave's dQ^T tile of every query pair holds features 16 jd .. + 15
     const float c = q.s * q.s * p.softmax_scale, c2 = c * kLog2e;
     load_grad(blockIdx.x, threadIdx.x, 0, kEarly);
     load_rest(blockIdx.x, threadIdx.x);
@@ -1353,61 +1419,23 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, cons
         const int lane = tid & 63, r = lane & 15, g = lane >> 4;
         uint32_t zr = 0u;   // (the zero rows of the images, likewise: as a hoisted 16-byte constant they were the one spill of this kernel)
         asm volatile("" : "+v"(zr));
-        int krow[U];
+        int krow[U];   // (kept for the epilogue)
         bool kvalid[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             krow[u] = min(16 * jt[u] + r, T - 1);
             kvalid[u] = has[u] && 16 * jt[u] + r < T;
         }
-        // ---- the conversion of k_attn_bwd_fused
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            pin4_in(da4[it]); pin4_in(db4[it]);
-            asm volatile("" ::"v"(oh[it].x), "v"(oh[it].y), "v"(oh[it].z), "v"(oh[it].w), "v"(ol[it].x), "v"(ol[it].y), "v"(ol[it].z), "v"(ol[it].w));
-            asm volatile("" ::"v"(cq[it].x), "v"(cq[it].y), "v"(ck[it].x), "v"(ck[it].y));
-        }
-        if (tid < NKT * 16) sLse[tid] = tid < T ? -lse_raw * kLog2e : -INFINITY;   // (see k_attn_bwd_dkv)
-        if (tid < 3 * HD) sCs[tid] = p.col_scale ? cs_raw : 1.f;
+        // ---- the conversion
+        in.pin();
+        if (tid < NKT * 16) s.sLse[tid] = tid < T ? -lse_raw * kLog2e : -INFINITY;   // (see k_attn_bwd_dkv)
+        if (tid < 3 * HD) s.sCs[tid] = p.col_scale ? cs_raw : 1.f;
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            if (tid + k * NWV * 64 < 3 * T) sM[tid + k * NWV * 64] = mrow[k];
+            if (tid + k * NWV * 64 < 3 * T) s.sM[tid + k * NWV * 64] = in.mrow[k];
         float* const gdelta = p.delta ? p.delta + (int64_t)item * (NKT * 16) : nullptr;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int i = tid + it * NWV * 64, tok = i / CH, ch = i % CH;
-            const bool real = tok < T;   // padded token rows are zero in every image
-            const float v[8] = {da4[it].x, da4[it].y, da4[it].z, da4[it].w, db4[it].x, db4[it].y, db4[it].z, db4[it].w};
-            const uint32_t wh[4] = {oh[it].x, oh[it].y, oh[it].z, oh[it].w}, wl[4] = {ol[it].x, ol[it].y, ol[it].z, ol[it].w};
-            float d = 0.f;   // delta = sum_d dO . O over the row: 8 features here, the row's 8 chunks on consecutive lanes
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                d += v[2 * j] * (__builtin_bit_cast(float, wh[j] << 16) + __builtin_bit_cast(float, wl[j] << 16));
-                d += v[2 * j + 1] * (__builtin_bit_cast(float, wh[j] & 0xffff0000u) + __builtin_bit_cast(float, wl[j] & 0xffff0000u));
-            }
-            d += __shfl_xor(d, 1, 64);
-            d += __shfl_xor(d, 2, 64);
-            d += __shfl_xor(d, 4, 64);
-            if (i < TOTAL) {
-                const uint4 z = make_uint4(zr, zr, zr, zr);
-                *reinterpret_cast<uint4*>(sQt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(cq[it], coff)) : z;
-                *reinterpret_cast<uint4*>(sKt + tr_off<HD>(tok, ch)) = real ? __builtin_bit_cast(uint4, decode8(ck[it], coff)) : z;
-                uint32_t H[4], L[4];
-                split_pair(v[0], v[1], H[0], L[0]); split_pair(v[2], v[3], H[1], L[1]);
-                split_pair(v[4], v[5], H[2], L[2]); split_pair(v[6], v[7], H[3], L[3]);
-                *reinterpret_cast<uint4*>(sDh + tr_off<HD>(tok, ch)) = real ? make_uint4(H[0], H[1], H[2], H[3]) : z;
-                *reinterpret_cast<uint4*>(sDl + tr_off<HD>(tok, ch)) = real ? make_uint4(L[0], L[1], L[2], L[3]) : z;
-                if (ch == 0) {
-                    sDlt[tok] = d * q.inv;
-                    if (real && gdelta) gdelta[tok] = d;
-                }
-            }
-        }
         bf16x8 vf[U][KK];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) vf[u][kk] = decode8(vc[u][kk], coff);
+        bwd_convert(s, in, tid, T, zr, coff, q.inv, gdelta, vf);
         lds_barrier();   // (LDS only: the previous head's dK / dV stores stay in flight)
         // ---- the next head's loads, into the registers the conversion has freed: waited for behind the epilogue
         const int next = item + gridDim.x;
@@ -1420,131 +1448,14 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, cons
         }
         // (the query column scales from the LDS copy - 1.0 without col_scale, the same product: a global load consumed inside the sweep would be a wait
         //  behind the loads just requested, vmcnt retires in order)
-        const float4 ckq = *reinterpret_cast<const float4*>(sCs + 16 * jd + 4 * g);
-        // ---- the sweep of k_attn_bwd_fused
+        const float4 ckq = *reinterpret_cast<const float4*>(s.sCs + 16 * jd + 4 * g);
+        // ---- the sweep
         f32x4 dk[U][ND], dv[U][ND];
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int id = 0; id < ND; ++id) dk[u][id] = dv[u][id] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int qs = 0; qs < NKT / 2; ++qs) {
-            const int qme = 16 * (2 * qs + vq) + r;
-            const uint32_t mqb = reinterpret_cast<const uint8_t*>(sM)[min(qme, T - 1) * 8 + 2 * jd + (g >> 1)];
-            // phase 1: S and dP of every owned key tile (the query-row fragments are dead afterwards: 48 registers)
-            f32x4 sacc[U][2], dpv[U][2];
-            {
-                bf16x8 qa[2][KK], da[2][KK], db[2][KK];
-#pragma unroll
-                for (int v = 0; v < 2; ++v)
-#pragma unroll
-                    for (int kk = 0; kk < KK; ++kk) {
-                        qa[v][kk] = *reinterpret_cast<const bf16x8*>(sQt + tr_off<HD>(16 * (2 * qs + v) + r, 4 * kk + g));
-                        da[v][kk] = *reinterpret_cast<const bf16x8*>(sDh + tr_off<HD>(16 * (2 * qs + v) + r, 4 * kk + g));
-                        db[v][kk] = *reinterpret_cast<const bf16x8*>(sDl + tr_off<HD>(16 * (2 * qs + v) + r, 4 * kk + g));
-                    }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (!has[u]) continue;   // wave-uniform
-                    bf16x8 kf[KK];           // (rows >= T of the image are zero)
-#pragma unroll
-                    for (int kk = 0; kk < KK; ++kk) kf[kk] = *reinterpret_cast<const bf16x8*>(sKt + tr_off<HD>(16 * jt[u] + r, 4 * kk + g));
-#pragma unroll
-                    for (int v = 0; v < 2; ++v) {
-                        sacc[u][v] = dpv[u][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int kk = 0; kk < KK; ++kk) {
-                            sacc[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[v][kk], kf[kk], sacc[u][v], 0, 0, 0);
-                            dpv[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[v][kk], vf[u][kk], dpv[u][v], 0, 0, 0);
-                            dpv[u][v] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(db[v][kk], vf[u][kk], dpv[u][v], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // phase 2: the transposed fragments (their LDS latency runs under the exp / split arithmetic), P and dS, dV / dK
-            bf16x8 dth[ND], dtl[ND], qtf[ND];
-#pragma unroll
-            for (int id = 0; id < ND; ++id) {
-                dth[id] = tr_frag2<HD>(sDh, 32 * qs, 32 * qs + 16, 16 * id, lane);
-                dtl[id] = tr_frag2<HD>(sDl, 32 * qs, 32 * qs + 16, 16 * id, lane);
-                qtf[id] = tr_frag2<HD>(sQt, 32 * qs, 32 * qs + 16, 16 * id, lane);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                bf16x8 ph, pl, sh, sl2;
-                if (has[u]) {
-                    f32x4 p2[2], ds2[2];
-#pragma unroll
-                    for (int v = 0; v < 2; ++v) {
-                        // S orientation: this lane's key = 16 jt + r, query = 16 (2qs + v) + 4g + e: the four softmax constants are one 16-byte read
-                        const float4 nl = *reinterpret_cast<const float4*>(sLse + 16 * (2 * qs + v) + 4 * g);
-                        const float4 dl = *reinterpret_cast<const float4*>(sDlt + 16 * (2 * qs + v) + 4 * g);
-                        const float nlv[4] = {nl.x, nl.y, nl.z, nl.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[u][v][e], c2, nlv[e]));
-                            p2[v][e] = pr;
-                            ds2[v][e] = pr * (dpv[u][v][e] - dlv[e]);
-                        }
-                    }
-                    if (16 * jt[u] + 15 >= T) {   // (wave-uniform) the tile with padded keys: their dS goes into the image as zero - their P is e^-lse, which
-                        asm volatile("");         // may overflow, and dQ^T multiplies it with the zero rows of the K image (inf * 0 = NaN)
-#pragma unroll
-                        for (int v = 0; v < 2; ++v)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) ds2[v][e] = kvalid[u] ? ds2[v][e] : 0.f;
-                    }
-                    split_acc2(p2[0], p2[1], ph, pl);
-                    split_acc2(ds2[0], ds2[1], sh, sl2);
-                }
-                // the dS image is free again once every wave has finished the previous pair's dQ^T tile
-                if (u == 0) lds_barrier();
-                if (has[u]) {
-                    // this lane: key 16 jt + r, queries 4g .. 4g+3 of tile v in elements 4v .. 4v+3 -> 8-byte runs of the [key][32 queries] image
-                    const uint4 wh = __builtin_bit_cast(uint4, sh), wl = __builtin_bit_cast(uint4, sl2);
-                    const int so = (16 * jt[u] + r) * kSRow + ((g ^ ((r >> 2) & 3)) << 3);   // slot g of the key's row, XORed with (key >> 2) & 3
-                    *reinterpret_cast<uint2*>(sSh + so) = make_uint2(wh.x, wh.y);
-                    *reinterpret_cast<uint2*>(sSh + SVQ + so) = make_uint2(wh.z, wh.w);
-                    *reinterpret_cast<uint2*>(sSl + so) = make_uint2(wl.x, wl.y);
-                    *reinterpret_cast<uint2*>(sSl + SVQ + so) = make_uint2(wl.z, wl.w);
-#pragma unroll
-                    for (int id = 0; id < ND; ++id) {
-                        dv[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dth[id], ph, dv[u][id], 0, 0, 0);
-                        dv[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dth[id], pl, dv[u][id], 0, 0, 0);
-                        dv[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dtl[id], ph, dv[u][id], 0, 0, 0);
-                        dk[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf[id], sh, dk[u][id], 0, 0, 0);
-                        dk[u][id] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf[id], sl2, dk[u][id], 0, 0, 0);
-                    }
-                }
-            }
-            lds_barrier();   // every owned key tile's dS of this query pair is in the image
-            f32x4 dq = {0.f, 0.f, 0.f, 0.f}, dq1 = {0.f, 0.f, 0.f, 0.f};   // (two chains: the hi and the lo products)
-#pragma unroll
-            for (int ks = 0; ks < NKT / 2; ++ks) {
-                const bf16x8 kt = tr_frag2<HD>(sKt, 32 * ks, 32 * ks + 16, 16 * jd, lane);   // A: row = feature, k-slots = keys
-                const bf16x8 bh = tr_frag_ds(sSh + vq * SVQ, 32 * ks, 32 * ks + 16, lane);     // B: col = query, the same k-slots
-                const bf16x8 bl = tr_frag_ds(sSl + vq * SVQ, 32 * ks, 32 * ks + 16, lane);
-                dq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt, bh, dq, 0, 0, 0);
-                dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt, bl, dq1, 0, 0, 0);
-            }
-            dq += dq1;
-            if (qme < T) {   // rows: features 16 jd + 4g + e, column: query qme -> 8-byte (4 x bf16) stores along d
-                const uint32_t mb = mqb >> (4 * (g & 1));
-                const float gq[4] = {(mb & 1u) ? dq[0] * c * ckq.x : 0.f, (mb & 2u) ? dq[1] * c * ckq.y : 0.f, (mb & 4u) ? dq[2] * c * ckq.z : 0.f,
-                                     (mb & 8u) ? dq[3] * c * ckq.w : 0.f};
-                const int64_t offq = ((int64_t)b * T + qme) * ld + h * HD + 16 * jd + 4 * g;
-                if constexpr (O16) {
-                    am16 = fmaxf(fmaxf(am16, fmaxf(fabsf(gq[0]), fabsf(gq[1]))), fmaxf(fabsf(gq[2]), fabsf(gq[3])));
-                    *reinterpret_cast<uint2*>(p.dqkv_hi + offq) = make_uint2(pk_f16(gq[0] * mul16, gq[1] * mul16), pk_f16(gq[2] * mul16, gq[3] * mul16));
-                } else {
-                    uint2 gh, gl;
-                    split_pair(gq[0], gq[1], gh.x, gl.x); split_pair(gq[2], gq[3], gh.y, gl.y);
-                    *reinterpret_cast<uint2*>(p.dqkv_hi + offq) = gh;
-                    *reinterpret_cast<uint2*>(p.dqkv_lo + offq) = gl;
-                }
-            }
-        }
+        bwd_sweep<NKT, O16>(p, s, NKT / 2, lane, wave, b, h, c, c2, ckq, mul16, am16, jt, has, kvalid, vf, dk, dv);
         // ---- the rest of the next head's loads: the sweep's fragments are dead, the accumulators drain - the epilogue has the registers the sweep has not
         auto rest_early = [&]() {
             if (next < nitems) {
@@ -1557,76 +1468,14 @@ __global__ __launch_bounds__(8 * 64) void k_attn_bwd_pipe(const AttnArgs p, cons
                 drop_grad(kEarly, ITERS);
             }
         };
-        // ---- the dK / dV epilogue of k_attn_bwd_fused, through wave-private LDS tiles over the (dead) images
-        float4 ckc[ND], cvc[ND];
-#pragma unroll
-        for (int id = 0; id < ND; ++id) {
-            ckc[id] = *reinterpret_cast<const float4*>(sCs + HD + 16 * id + 4 * g);
-            cvc[id] = *reinterpret_cast<const float4*>(sCs + 2 * HD + 16 * id + 4 * g);
-        }
-        uint2 mkr[U], mvr[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            mkr[u] = sM[T + krow[u]];
-            mvr[u] = sM[2 * T + krow[u]];
-        }
-        lds_barrier();
-        constexpr int kERow = 144;
-        char* const sE = smem + wave * (4 * 16 * kERow);   // [k hi | k lo | v hi | v lo][16 keys][144 B]
-        const int erow = lane >> 3, ech = lane & 7;       // read-back: 8 lanes per key row, two passes of 8 rows
+        // ---- the dK / dV epilogue, through wave-private LDS tiles over the (dead) images
+        typename S::DkvConsts kc;
+        bwd_dkv_consts(s, T, lane, wave, krow, kc);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (u == U - 1) rest_early();
             if (!has[u]) continue;   // wave-uniform
-#pragma unroll
-            for (int id = 0; id < ND; ++id) {
-                const float4 ck4 = ckc[id], cv = cvc[id];
-                const uint32_t bk = (id < 2 ? mkr[u].x : mkr[u].y) >> (16 * (id & 1) + 4 * g), bv = (id < 2 ? mvr[u].x : mvr[u].y) >> (16 * (id & 1) + 4 * g);
-                const float vk[4] = {(bk & 1u) ? dk[u][id][0] * c * ck4.x : 0.f, (bk & 2u) ? dk[u][id][1] * c * ck4.y : 0.f,
-                                     (bk & 4u) ? dk[u][id][2] * c * ck4.z : 0.f, (bk & 8u) ? dk[u][id][3] * c * ck4.w : 0.f};
-                const float vv[4] = {(bv & 1u) ? dv[u][id][0] * cv.x : 0.f, (bv & 2u) ? dv[u][id][1] * cv.y : 0.f,
-                                     (bv & 4u) ? dv[u][id][2] * cv.z : 0.f, (bv & 8u) ? dv[u][id][3] * cv.w : 0.f};
-                uint2 kh, kl, vh, vl;
-                char* const e = sE + r * kERow + (16 * id + 4 * g) * 2;
-                if constexpr (O16) {   // (padded keys hold zero accumulators: P = 0 and dS = 0 for them)
-                    am16 = fmaxf(fmaxf(am16, fmaxf(fmaxf(fabsf(vk[0]), fabsf(vk[1])), fmaxf(fabsf(vk[2]), fabsf(vk[3])))),
-                                 fmaxf(fmaxf(fabsf(vv[0]), fabsf(vv[1])), fmaxf(fabsf(vv[2]), fabsf(vv[3]))));
-                    kh = make_uint2(pk_f16(vk[0] * mul16, vk[1] * mul16), pk_f16(vk[2] * mul16, vk[3] * mul16));
-                    vh = make_uint2(pk_f16(vv[0] * mul16, vv[1] * mul16), pk_f16(vv[2] * mul16, vv[3] * mul16));
-                    *reinterpret_cast<uint2*>(e) = kh;
-                    *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
-                } else {
-                    split_pair(vk[0], vk[1], kh.x, kl.x); split_pair(vk[2], vk[3], kh.y, kl.y);
-                    split_pair(vv[0], vv[1], vh.x, vl.x); split_pair(vv[2], vv[3], vh.y, vl.y);
-                    *reinterpret_cast<uint2*>(e) = kh;
-                    *reinterpret_cast<uint2*>(e + 16 * kERow) = kl;
-                    *reinterpret_cast<uint2*>(e + 32 * kERow) = vh;
-                    *reinterpret_cast<uint2*>(e + 48 * kERow) = vl;
-                }
-            }
-            wave_lds_fence();   // (wave-private: LDS is in order per wave, no barrier)
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int key = 16 * jt[u] + 8 * half + erow;
-                const char* const e = sE + (8 * half + erow) * kERow + ech * 16;
-                const uint4 kh = *reinterpret_cast<const uint4*>(e), vh = *reinterpret_cast<const uint4*>(e + 32 * kERow);
-                const int64_t offk = ((int64_t)b * T + key) * ld + D + h * HD + 8 * ech;
-                if constexpr (O16) {
-                    if (key < T) {
-                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
-                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
-                    }
-                } else {
-                    const uint4 kl = *reinterpret_cast<const uint4*>(e + 16 * kERow), vl = *reinterpret_cast<const uint4*>(e + 48 * kERow);
-                    if (key < T) {
-                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk) = kh;
-                        *reinterpret_cast<uint4*>(p.dqkv_lo + offk) = kl;
-                        *reinterpret_cast<uint4*>(p.dqkv_hi + offk + D) = vh;
-                        *reinterpret_cast<uint4*>(p.dqkv_lo + offk + D) = vl;
-                    }
-                }
-            }
-            wave_lds_fence();   // the tile is read before the next key tile overwrites it
+            bwd_dkv_tile<NKT, O16>(p, lane, b, h, jt[u], c, kc, u, dk[u], dv[u], mul16, am16);
         }
         if (next >= nitems) break;
         item = next;
@@ -1691,14 +1540,19 @@ bool attn_bwd_is_fused(int T, int H, int D, bool codes) {
     return knobs().attn_bwd_fused && codes && H > 0 && D % H == 0 && D / H == 64 && T > 32 && T <= 224;
 }
 
-static void launch_pipe(const AttnArgs& a, int max_grid, hipStream_t st);   // (defined last: the kernel templates are instantiated in their old order)
-static int cu_count() {   // (as launch_tn_stream)
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 || cus > 256) cus = 256;
-    }
-    return cus;
+// the fused backward (head_dim 64, 33..224 tokens: 14 key tiles), one workgroup per (image, head) or max_grid persistent ones; LDS: BwdHead<14>::kBytes
+template <bool O16, bool LIVE>
+static void launch_fused(const AttnArgs& a, hipStream_t st) {
+    static bool once = (allow_lds(k_attn_bwd_fused<14, O16, LIVE>, BwdHead<14>::kBytes), true);
+    (void)once;
+    k_attn_bwd_fused<14, O16, LIVE><<<a.B * a.H, 8 * 64, BwdHead<14>::kBytes, st>>>(a);
+}
+template <bool O16>
+static void launch_pipe(const AttnArgs& a, int max_grid, hipStream_t st) {
+    static bool once = (allow_lds(k_attn_bwd_pipe<14, O16>, BwdHead<14>::kBytes), true);
+    (void)once;
+    const int items = a.B * a.H, grid = items < max_grid ? items : max_grid;
+    k_attn_bwd_pipe<14, O16><<<grid, 8 * 64, BwdHead<14>::kBytes, st>>>(a, items);
 }
 
 int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B, int T, int H, int D, const void* O_hi, const void* O_lo,
@@ -1721,7 +1575,7 @@ int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B
                reinterpret_cast<uint8_t*>(const_cast<void*>(codes)), reinterpret_cast<uint8_t*>(const_cast<void*>(cmask)), o16_mul, o16_amax,
                live_q_tiles, dO_cls ? 1 : 0};
     if (pipe_ok && (form >= kAttnBwdPipe || (form == kAttnBwdAuto && knobs().attn_bwd_pipe && (int64_t)B * H > cu_count()))) {
-        launch_pipe(a, form == kAttnBwdPipe5 ? 5 : cu_count(), st);
+        (o16_mul ? launch_pipe<true> : launch_pipe<false>)(a, form == kAttnBwdPipe5 ? 5 : cu_count(), st);
         return 0;
     }
     // one fused kernel (dK, dV and dQ from one sweep) where its shape holds: head_dim 64, 33..224 tokens, saved codes; QATVIT_ATTN_BWD_FUSED=0: the
@@ -1729,18 +1583,10 @@ int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B
     int nkt;
     if (check_shape(T, D, H, &nkt)) return 1;
     if (attn_bwd_is_fused(T, H, D, codes != nullptr)) {
-        constexpr int kLds = 4 * 14 * 16 * 64 * 2 + 2 * 2 * 14 * 16 * kSRow + 2 * 14 * 16 * 4 + 3 * 14 * 16 * 8 + 3 * 64 * 4;   // 151,296 B
-        static bool once = (allow_lds(k_attn_bwd_fused<14>, kLds), allow_lds(k_attn_bwd_fused<14, true>, kLds), allow_lds(k_attn_bwd_fused<14, false, true>, kLds),
-                            allow_lds(k_attn_bwd_fused<14, true, true>, kLds), true);
-        (void)once;
         if (dO_cls && live_q_tiles < 1) { set_error("attention backward: the [B, D] form of dO needs live_q_tiles >= 1"); return 1; }
-        const bool live = live_q_tiles > 0;
-        if (o16_mul) {
-            if (!o16_amax) { set_error("attention backward: o16_mul needs o16_amax"); return 1; }
-            if (live) k_attn_bwd_fused<14, true, true><<<B * H, 8 * 64, kLds, st>>>(a);
-            else k_attn_bwd_fused<14, true><<<B * H, 8 * 64, kLds, st>>>(a);
-        } else if (live) k_attn_bwd_fused<14, false, true><<<B * H, 8 * 64, kLds, st>>>(a);
-        else k_attn_bwd_fused<14><<<B * H, 8 * 64, kLds, st>>>(a);
+        static constexpr void (*kFused[2][2])(const AttnArgs&, hipStream_t) = {{launch_fused<false, false>, launch_fused<false, true>},
+                                                                               {launch_fused<true, false>, launch_fused<true, true>}};   // [O16][LIVE]
+        kFused[o16_mul != nullptr][live_q_tiles > 0](a, st);
         return 0;
     }
     if (o16_mul) { set_error("attention backward: the one-plane output exists in the fused kernel only (head_dim 64, 33..224 tokens, saved codes)"); return 1; }
@@ -1749,15 +1595,6 @@ int launch_attn_bwd(const float* qkv, const float* qp, int qmin, int qmax, int B
     a.live_q_tiles = 0;
     if (dispatch(1, a, st)) return 1;
     return dispatch(2, a, st);
-}
-
-static void launch_pipe(const AttnArgs& a, int max_grid, hipStream_t st) {
-    constexpr int kLds = 4 * 14 * 16 * 64 * 2 + 2 * 2 * 14 * 16 * kSRow + 2 * 14 * 16 * 4 + 3 * 14 * 16 * 8 + 3 * 64 * 4;   // 151,296 B, as the per-head kernel
-    static bool once = (allow_lds(k_attn_bwd_pipe<14, false>, kLds), allow_lds(k_attn_bwd_pipe<14, true>, kLds), true);
-    (void)once;
-    const int items = a.B * a.H, grid = items < max_grid ? items : max_grid;
-    if (a.o16_mul) k_attn_bwd_pipe<14, true><<<grid, 8 * 64, kLds, st>>>(a, items);
-    else k_attn_bwd_pipe<14, false><<<grid, 8 * 64, kLds, st>>>(a, items);
 }
 
 }  // namespace qv

@@ -31,6 +31,14 @@ const Knobs& knobs() {
                          knob("QATVIT_CLS_BWD"), knob("QATVIT_ATTN_BWD_PIPE")};
     return k;
 }
+int cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1 || n > 256) n = 256;
+        return n;
+    }();
+    return cus;
+}
 
 // The drop-path scale table bound to a step workspace (qatvit_student_set_drop_path / qatvit_float_student_set_drop_path): host state keyed by the workspace
 // address, read by every forward / backward entry on that workspace - a backward runs on autograd's worker thread, hence the lock.  The init entries of both

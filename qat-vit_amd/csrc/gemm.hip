@@ -2338,11 +2338,7 @@ int64_t tn_stream_scratch_bytes() { return (int64_t)2 * 256 * 128 * 384 * 4; }  
 int launch_tn_stream(TNForm form, const TNGemm* items, int n, const TNCall& call, hipStream_t st) {
     const int M = call.M;
     if (n < 1 || n > kTnStreamMax || M < 1 || form < kTNPlaneQ8 || form > kTNPlaneF16 || !call.scratch) { set_error("tn_stream: bad arguments (n=%d, mode=%d)", n, (int)form); return 1; }
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 || cus > 256) cus = 256;
-    }
+    const int cus = cu_count();
     TNStreamArgs a{};
     a.n = n; a.M = M; a.steps = (M + 63) / 64; a.center = call.center; a.w_per_channel = call.w_per_channel; a.w_qmin = call.w_qmin; a.w_qmax = call.w_qmax;
     a.partial = call.scratch;

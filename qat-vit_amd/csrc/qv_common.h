@@ -49,6 +49,8 @@ struct Knobs {
     bool attn_bwd_pipe;   // QATVIT_ATTN_BWD_PIPE: the fused attention backward as one persistent workgroup per CU that fetches its next head under the sweep (more heads than CUs); 0: one workgroup per head
 };
 const Knobs& knobs();
+// compute units of the current device, asked once per process (capi.hip); 256 where the runtime does not say or says more: the size of persistent grids
+int cu_count();
 
 #define QV_CHECK_ARG(cond, ...)                 \
     do {                                        \

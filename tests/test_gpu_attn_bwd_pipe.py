@@ -15,8 +15,9 @@ from tests.test_gpu_attn_live import _setup  # noqa: E402
 DEV = "cuda"
 AMAX_SLOTS, AMAX_STRIDE = 8, 32      # include/qatvit.h QATVIT_DY16_AMAX_SLOTS / _STRIDE
 MUL16 = 64.0                         # the one-plane form's scale (a power of two, as dy16 chooses them)
-# (B, H, T): 12 heads; three key tiles, so five of the eight waves own none; fewer heads than CUs or than 2 x 5: form 1 fetches no successor
-CASES = [(2, 6, 197), (3, 6, 40), (1, 6, 197)]
+# (B, H, T): 12 heads; three key tiles, so five of the eight waves own none; fewer heads than CUs or than 2 x 5: form 1 fetches no successor;
+# every key tile full (no padded-key branch, all 14 tiles owned); three key tiles, the last with ONE real key (12 items on 5 workgroups: an uneven tail)
+CASES = [(2, 6, 197), (3, 6, 40), (1, 6, 197), (2, 6, 224), (2, 6, 33)]
 
 
 def _run(native_lib, s, B, T, H, D, dO, cs, one_plane, form, what):
