@@ -823,6 +823,33 @@ int qatvit_optim_lamb_apply(const void* param_ptrs, const void* exp_avg_ptrs, co
  *   A malformed record gives exactly the result of the cleaned record, and nothing is addressed through a record.  The kernels keep nothing
  *   more in LDS: the refusals are the siblings'.  color == NULL makes the call qatvit_image_batch_erase's / qatvit_image_batch_rrc_erase's:
  *   that entry's kernel is launched and the result is bitwise its result (sums is then not touched).
+ *
+ * qatvit_image_batch_blur / qatvit_image_batch_rrc_blur: the same launches with Gaussian blur, as DeiT-III's 3-Augment and timm apply it
+ *   (img.filter(ImageFilter.GaussianBlur(radius))), on the uint8 RGB D x D image behind the resize.  Per sample the order is: grayscale,
+ *   solarize, BLUR, the jitter ops of the colour record, then Normalize, the erase, the mix.  The sum s of a contrast op is taken of the image
+ *   as it stands in front of that op, so behind the blur.  The partner of a mix record is blurred by ITS OWN record blur[p].
+ *   blur int32 [B][4] on the device, contiguous, 4-byte aligned, one record per batch POSITION b:
+ *     word 0  bit 0: blur on.  Bits 8-15: the integer box radius, at most 1.  All other bits are ignored.
+ *     word 1  ww, the weight of the 2 * radius + 1 pixels around the centre, 1 .. 2^24
+ *     word 2  fw, the weight of the two pixels at distance radius + 1, >= 0
+ *     word 3  0 (ignored)
+ *   Pillow computes the filter as three box passes along the rows, then three along the columns, every pass rounded to uint8, in integers.
+ *   One pass over a line in[0 .. n-1], per channel, with clamp to 0 .. n-1 (the edge pixel is replicated):
+ *     out[x] = (ww * SUM(|d| <= radius) in[clamp(x + d)] + fw * (in[clamp(x - radius - 1)] + in[clamp(x + radius + 1)]) + 2^23) >> 24
+ *   in 32 unsigned bits.  The host forms the record from the Gaussian radius r in C float arithmetic, with passes = 3:
+ *     sigma2 = r * r / passes, L = sqrt(12 * sigma2 + 1), l = floor((L - 1) / 2),
+ *     a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2) / (6 * (sigma2 - (l + 1)^2)), box = l + a, radius = (int)box,
+ *     ww = (uint32)((float)(1 << 24) / (box * 2 + 1)), fw = ((1 << 24) - (2 * radius + 1) * ww) / 2
+ *   e.g. r = 0.1: (0, 16721291, 27962); r = 2.0: (1, 4473924, 1677722).  The integer radius is at most 1 for Gaussian radii below sqrt(6);
+ *   larger ones are not offered.  The device does no float arithmetic for the blur.  The result EQUALS Pillow's, byte for byte
+ *   (tests/golden/blur_kat.npz).
+ *   A record is cleaned, not trusted: it counts as "no blur" unless bit 0 is set, radius <= 1, 1 <= ww <= 2^24, fw >= 0 and
+ *   (2 * radius + 1) * ww + 2 * fw <= 2^24; then every pass result is at most 255 and nothing overflows.  Nothing is addressed through a
+ *   record.  A sample whose record is "no blur" goes through the colour entry's arithmetic and gets bitwise its result.
+ *   The other records are qatvit_image_batch_color's; color == NULL here means all-zero colour records, erase == NULL all-zero erase records.
+ *   The kernels keep a band of 8 output rows with up to 6 halo rows on each side, per side of a mix record, and one more such buffer in LDS:
+ *   above 64 KB the call is refused with an error string before any HIP call (32 -> 224 with mix is served).  blur == NULL makes the call
+ *   qatvit_image_batch_color's / qatvit_image_batch_rrc_color's: the result is bitwise its result.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -847,6 +874,12 @@ int qatvit_image_batch_color(const uint8_t* data, const int64_t* index, int32_t 
 int qatvit_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
                                  const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color,
                                  uint32_t* sums, float* out, void* stream);
+int qatvit_image_batch_blur(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                            const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix,
+                            const int32_t* erase, const int32_t* color, uint32_t* sums, const int32_t* blur, float* out, void* stream);
+int qatvit_image_batch_rrc_blur(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
+                                const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color,
+                                uint32_t* sums, const int32_t* blur, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

@@ -521,7 +521,7 @@ int qatvit_image_table(const float* mean_host, const float* std_host, float* tab
     return 0;
 }
 
-// The eight batch entries: each fills an ImageBatch (qv_kernels.h) with its own arguments and runs it.  The part of the record that all of them have:
+// The ten batch entries: each fills an ImageBatch (qv_kernels.h) with its own arguments and runs it.  The part of the record that all of them have:
 static ImageBatch image_request(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* tab,
                                 const float* table, float* out) {
     ImageBatch r;
@@ -542,7 +542,7 @@ static int image_request_ok(const char* who, const ImageBatch& r, const char* no
         QV_CHECK_ARG(r.fill >= 0 && r.fill <= 255, "%s: fill %d is outside 0 .. 255", who, r.fill);
     }
     const uintptr_t words = (uintptr_t)r.tab | (uintptr_t)r.table | (uintptr_t)r.aug | (uintptr_t)r.rrc | (uintptr_t)r.mix | (uintptr_t)r.erase |
-                            (uintptr_t)r.color | (uintptr_t)r.sums;
+                            (uintptr_t)r.color | (uintptr_t)r.sums | (uintptr_t)r.blur;
     QV_CHECK_ARG(((uintptr_t)r.out & 15) == 0 && (words & 3) == 0, "%s: misaligned pointer", who);
     return 0;
 }
@@ -617,6 +617,22 @@ int qatvit_image_batch_rrc_color(const uint8_t* data, const int64_t* index, int3
     ImageBatch r = image_request(data, index, B, N, S, D, windows, table, out);
     r.rrc = rrc, r.mix = mix, r.erase = erase, r.color = color, r.sums = sums;
     return image_run("qatvit_image_batch_rrc_color", r, stream, "the call without window records is qatvit_image_batch_color");
+}
+
+int qatvit_image_batch_blur(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* coeffs,
+                            const float* table, const int32_t* aug, int32_t padding_mode, int32_t fill, const int32_t* mix, const int32_t* erase,
+                            const int32_t* color, uint32_t* sums, const int32_t* blur, float* out, void* stream) {
+    ImageBatch r = image_request(data, index, B, N, S, D, coeffs, table, out);
+    r.aug = aug, r.padding_mode = padding_mode, r.fill = fill, r.mix = mix, r.erase = erase, r.color = color, r.sums = sums, r.blur = blur;
+    return image_run("qatvit_image_batch_blur", r, stream);
+}
+
+int qatvit_image_batch_rrc_blur(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
+                                const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color,
+                                uint32_t* sums, const int32_t* blur, float* out, void* stream) {
+    ImageBatch r = image_request(data, index, B, N, S, D, windows, table, out);
+    r.rrc = rrc, r.mix = mix, r.erase = erase, r.color = color, r.sums = sums, r.blur = blur;
+    return image_run("qatvit_image_batch_rrc_blur", r, stream, "the call without window records is qatvit_image_batch_blur");
 }
 
 int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {

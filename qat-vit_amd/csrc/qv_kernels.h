@@ -373,6 +373,8 @@ int launch_fa_inf_rule(float* const* g, const int64_t* n, int count, hipStream_t
 // image.hip: the input pipeline.  coeffs = int32 {xmin[D], ntaps[D], coef[D][kImgTaps]} and table = fp32 [3][256], both as the two host functions write them
 constexpr int kImgTaps = 4, kImgBits = 22, kImgBand = 16, kImgMaxD = 384;
 constexpr int kImgMixMaxLds = 64 * 1024;
+// the blur forms: the integer box radius a record may hold, the halo rows its three column passes need on each side of a band, the band without and with mix records
+constexpr int kImgBlurMaxRadius = 1, kImgBlurHalo = 3 * (kImgBlurMaxRadius + 1), kImgBlurBand = 16, kImgBlurMixBand = 8;
 int image_resize_coeffs(int src, int dst, int32_t* xmin, int32_t* ntaps, int32_t* coef);   // host only; nonzero + set_error when the kernel's bounds do not hold
 void image_table(const float* mean, const float* stdv, float* table);                      // host only
 int image_resize_coeffs_windows(int S, int D, int32_t* out);                               // host only: int32 [S][6 * D], table n - 1 = image_resize_coeffs(n, D)
@@ -393,9 +395,15 @@ struct ImageBatch {
                                       // Absent with color: all-zero records
     const int32_t* color = nullptr;   // [B][4]: jitter ops in order, grayscale, solarize, three factors, on the uint8 pixels in front of the value table
     uint32_t* sums = nullptr;         // [B], read with color only: the luma sums of the contrast op.  Absent: contrast is the identity, no statistics launch
+    const int32_t* blur = nullptr;    // [B][4]: bit 0 on and the integer box radius in bits 8..15, ww, fw, 0: Pillow's GaussianBlur between grayscale / solarize
+                                      // and the jitter ops.  Present: the blur forms (image_blur.h), which take every other record as it comes; color absent:
+                                      // all-zero records
     float* out = nullptr;
 };
 int64_t image_lds_bytes(int S, int D, bool mixed, bool rrc);
+// image_blur.hip: the blur forms' request, always checked against kImgMixMaxLds, and their launcher, which launch_image_batch calls where r.blur is present
+int64_t image_blur_lds_bytes(int S, int D, bool mixed, bool rrc);
+int launch_image_blur(const ImageBatch& r, hipStream_t st);
 // nonzero + set_error: 1 before any HIP call where the form's LDS request exceeds kImgMixMaxLds (the window forms, and the others with mix), 2 where zeroing sums fails
 int launch_image_batch(const ImageBatch& r, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses

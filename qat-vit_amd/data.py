@@ -1,6 +1,6 @@
 """Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug /
 qatvit_image_batch_mix / qatvit_image_resize_coeffs_windows / qatvit_image_batch_rrc / qatvit_image_batch_erase / qatvit_image_batch_rrc_erase /
-qatvit_image_batch_color / qatvit_image_batch_rrc_color).
+qatvit_image_batch_color / qatvit_image_batch_rrc_color / qatvit_image_batch_blur / qatvit_image_batch_rrc_blur).
 
 Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
 ``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
@@ -11,6 +11,8 @@ writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced,
 ``RandomErasing`` erases a box of every sample's normalised output, behind either and in front of the mix, inside the same launch (section 7o).
 ``ColorJitter`` applies grayscale, solarize, brightness, contrast and saturation to the uint8 image behind the resize, equal to Pillow's, inside
 the same launch; contrast takes the sample's mean luma from a statistics launch in front of it (section 7q).
+``GaussianBlur`` blurs the uint8 image behind the resize as Pillow's ``ImageFilter.GaussianBlur`` does, between grayscale / solarize and the jitter
+ops, inside the same launch; ``ThreeAugment`` draws DeiT-III's one-of-three choice with its colour jitter (section 7v).
 There is no CPU path: CPU tensors raise."""
 import math
 import os
@@ -325,8 +327,8 @@ class ColorJitter:
     grayscale, bit 9 solarize with the threshold in bits 16..23; words 1..3 the factors of brightness, contrast, saturation (fp32 bits).  Per
     sample the order is grayscale, solarize, the jitter ops; the result equals Pillow's.  ``brightness`` / ``contrast`` / ``saturation`` have
     torchvision's meaning: a number x is the range ``[max(0, 1 - x), 1 + x]``, a pair is ``[low, high]``; 0 disables the op.  ``hue`` is not
-    supported (neither timm's default recipe nor DeiT-III's 3-Augment uses it) and anything but 0 raises; so is Gaussian blur.  Built and drawn
-    on the host; needs no GPU."""
+    supported (neither timm's default recipe nor DeiT-III's 3-Augment uses it) and anything but 0 raises.  Built and drawn on the host; needs
+    no GPU."""
 
     def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, grayscale=0.0, solarize=0.0, solarize_threshold=128):
         if isinstance(hue, bool) or not isinstance(hue, (int, float)) or hue != 0:
@@ -366,6 +368,98 @@ class ColorJitter:
         return rec.to(torch.int32)
 
 
+BLUR_WORDS = 4
+BLUR_MAX_BOX_RADIUS = 1
+
+
+def blur_weights(radius):
+    """``(box radius, ww, fw)`` of Pillow's ``ImageFilter.GaussianBlur(radius)``: its three box passes' integer radius and 24-bit fixed-point
+    weights, in ``np.float32`` arithmetic as Pillow's C ``float`` code forms them (include/qatvit.h).  A number gives three ints, an array three
+    int64 arrays of its shape.  Host only, no GPU."""
+    f = np.float32
+    r, passes = np.asarray(radius, dtype=f), f(3)
+    sigma2 = r * r / passes
+    L = np.sqrt(f(12) * sigma2 + f(1))
+    l = np.floor((L - f(1)) / f(2))
+    a = (f(2) * l + f(1)) * (l * (l + f(1)) - f(3) * sigma2) / (f(6) * (sigma2 - (l + f(1)) * (l + f(1))))
+    box = l + a
+    assert box.dtype == f
+    rad = box.astype(np.int64)                                       # (int)box and (uint32)(...): truncation of non-negative values
+    ww = (f(1 << 24) / (box * f(2) + f(1))).astype(np.int64)
+    fw = ((1 << 24) - (2 * rad + 1) * ww) // 2
+    return (int(rad), int(ww), int(fw)) if r.ndim == 0 else (rad, ww, fw)
+
+
+def _blur_radius_range(radius):
+    number = lambda t: not isinstance(t, bool) and isinstance(t, (int, float)) and math.isfinite(t)   # noqa: E731
+    if number(radius):
+        radius = (radius, radius)
+    if not (isinstance(radius, (tuple, list)) and len(radius) == 2 and all(number(t) for t in radius) and 0 <= radius[0] <= radius[1]):
+        raise ValueError(f"radius must be a number >= 0 or a pair of finite numbers 0 <= low <= high, got {radius!r}")
+    lo, hi = float(radius[0]), float(radius[1])
+    if blur_weights(hi)[0] > BLUR_MAX_BOX_RADIUS:
+        raise ValueError(f"radius up to {hi!r} gives the box radius {blur_weights(hi)[0]}: the native blur serves box radii up to "
+                         f"{BLUR_MAX_BOX_RADIUS}, which is a Gaussian radius below sqrt(6) = 2.449...")
+    return lo, hi
+
+
+def _blur_records(on, radius):
+    """int32 [n, 4] of a bool tensor `on` and a float64 tensor `radius`: the record of a sample that is not blurred is all zero."""
+    rad, ww, fw = blur_weights(radius.numpy().astype(np.float32))
+    rec = np.stack([1 | rad << 8, ww, fw, np.zeros_like(ww)], 1) * on.numpy()[:, None]
+    return torch.from_numpy(rec.astype(np.int32))
+
+
+class GaussianBlur:
+    """DeiT-III's / timm's ``GaussianBlur(p)``: with probability ``p``, ``img.filter(ImageFilter.GaussianBlur(radius=uniform(*radius)))`` of the
+    uint8 image behind the resize, as one four-word int32 record per sample (include/qatvit.h): word 0 bit 0 "on" and the integer box radius
+    in bits 8..15, word 1 ``ww``, word 2 ``fw`` (``blur_weights``), word 3 zero.  The blur stands behind grayscale / solarize and in front of
+    the jitter ops of a ``ColorJitter`` record; the result equals Pillow's.  A ``radius`` range whose upper end gives a box radius above 1
+    (a Gaussian radius of sqrt(6) or more) is refused.  Built and drawn on the host; needs no GPU."""
+
+    def __init__(self, p=1.0, radius=(0.1, 2.0)):
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 <= p <= 1:
+            raise ValueError(f"p must be a probability 0 .. 1, got {p!r}")
+        self.p, self.radius = float(p), _blur_radius_range(radius)
+
+    def draw(self, n, generator=None):
+        """int32 CPU tensor [n, 4].  The rule, all from `generator`, in this order: ``c = torch.rand(n, dtype=float64)``: sample k is blurred
+        where ``c[k] < p``; ``u = torch.rand(n, dtype=float64)``: its Gaussian radius is ``fp32(low + u[k] * (high - low))``.  A sample that is
+        not blurred gets the all-zero record.  Both draws are always made, so the generator's position depends on `n` only."""
+        c = torch.rand(n, dtype=torch.float64, generator=generator)
+        u = torch.rand(n, dtype=torch.float64, generator=generator)
+        return _blur_records(c < self.p, self.radius[0] + u * (self.radius[1] - self.radius[0]))
+
+
+class ThreeAugment:
+    """DeiT-III's 3-Augment (arXiv:2204.07118): per sample exactly one of grayscale, solarize and Gaussian blur, chosen uniformly, then
+    ``ColorJitter(color_jitter, color_jitter, color_jitter)``.  ``draw`` returns the colour records and the blur records of the same samples;
+    ``ColorJitter``'s two independent coins cannot express the choice.  Built and drawn on the host; needs no GPU."""
+
+    def __init__(self, color_jitter=0.3, radius=(0.1, 2.0), solarize_threshold=128):
+        # the jitter part: ColorJitter's validation and its draw; its own coins are off and the choice below sets the bits
+        self.jitter = ColorJitter(color_jitter, color_jitter, color_jitter, solarize_threshold=solarize_threshold)
+        self.radius = _blur_radius_range(radius)
+        self.solarize_threshold = solarize_threshold
+
+    @property
+    def contrast(self):
+        return self.jitter.contrast
+
+    def draw(self, n, generator=None):
+        """``(color int32 [n, 4], blur int32 [n, 4])`` CPU tensors.  The rule, all from `generator`, in this order: ``ColorJitter.draw(n)`` of
+        the jitter (a random order of the enabled ops and their factors); ``c = torch.rand(n, dtype=float64)``: the choice
+        ``floor(3 * c)`` - 0 grayscale, 1 solarize (with the threshold), 2 blur; ``u = torch.rand(n, dtype=float64)``: the Gaussian radius
+        ``fp32(low + u * (high - low))`` of a blurred sample.  Every draw is always made: the generator's position depends on `n` only."""
+        color = self.jitter.draw(n, generator).to(torch.int64)
+        c = torch.rand(n, dtype=torch.float64, generator=generator)
+        u = torch.rand(n, dtype=torch.float64, generator=generator)
+        choice = torch.clamp((3.0 * c).floor().to(torch.int64), max=2)
+        color[:, 0] |= (choice == 0).to(torch.int64) << 8
+        color[:, 0] |= (choice == 1).to(torch.int64) * (1 << 9 | self.solarize_threshold << 16)
+        return color.to(torch.int32), _blur_records(choice == 2, self.radius[0] + u * (self.radius[1] - self.radius[0]))
+
+
 class GpuResizeNormalize:
     """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch.
     With ``aug`` (int32 ``[B]`` on the device, the words of ``RandomCropFlip.draw``; word b belongs to batch position b) the source of sample b is
@@ -384,7 +478,11 @@ class GpuResizeNormalize:
     behind the resize goes through grayscale, solarize and the jitter ops of its record, in the same launch: behind ``aug`` / ``rrc``, in front
     of ``Normalize``, ``erase`` and ``mix``, whose partner is coloured by its own record.  The contrast op needs the mean luma of the whole
     sample, which a statistics launch in front of the batch launch sums into ``color_sums(B)``; ``contrast=False`` is the caller's promise that
-    no record holds a contrast op, and leaves that launch out."""
+    no record holds a contrast op, and leaves that launch out.
+    With ``blur`` (int32 ``[B, 4]`` on the device, the records of ``GaussianBlur.draw`` or the second result of ``ThreeAugment.draw``; record b
+    belongs to batch position b) the uint8 image behind the resize is blurred as Pillow's ``ImageFilter.GaussianBlur`` blurs it, in the same
+    launch: behind grayscale / solarize and in front of the jitter ops of ``color``, whose contrast mean is then that of the blurred image;
+    the partner of a mix record is blurred by its own record.  A workgroup whose record says "no blur" runs no pass."""
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
         self.src_size, self.out_size = int(src_size), int(out_size)
@@ -413,7 +511,7 @@ class GpuResizeNormalize:
         return self._sums[B]
 
     def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None, erase=None,
-                 color=None, contrast=True):
+                 color=None, contrast=True, blur=None):
         S, D = self.src_size, self.out_size
         if rrc is not None and aug is not None:
             raise ValueError("rrc and aug are mutually exclusive: the rrc record carries its own flip, and padding does not apply to a window")
@@ -455,6 +553,10 @@ class GpuResizeNormalize:
             if not isinstance(color, torch.Tensor) or color.dtype != torch.int32 or tuple(color.shape) != (B, COLOR_WORDS) \
                     or not color.is_contiguous() or color.device != self.device:
                 raise ValueError(f"color must be a contiguous int32 [{B}, {COLOR_WORDS}] tensor on {self.device}")
+        if blur is not None:
+            if not isinstance(blur, torch.Tensor) or blur.dtype != torch.int32 or tuple(blur.shape) != (B, BLUR_WORDS) \
+                    or not blur.is_contiguous() or blur.device != self.device:
+                raise ValueError(f"blur must be a contiguous int32 [{B}, {BLUR_WORDS}] tensor on {self.device}")
         if rrc is not None:
             if not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
                     or rrc.device != self.device:
@@ -464,7 +566,10 @@ class GpuResizeNormalize:
         # The narrowest entry that takes the records present, and its arguments between D and out.  An entry takes the records in front of its own as
         # they are, absent ones as NULL; without `contrast` the colour entries get no workspace and no statistics launch runs.
         opt = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        if color is not None:
+        if blur is not None:
+            level = "_blur"
+            records = (opt(erase), opt(color), self.color_sums(B).data_ptr() if color is not None and contrast else None, blur.data_ptr())
+        elif color is not None:
             level, records = "_color", (opt(erase), color.data_ptr(), self.color_sums(B).data_ptr() if contrast else None)
         elif erase is not None:
             level, records = "_erase", (erase.data_ptr(),)
@@ -511,10 +616,14 @@ class GpuImageLoader:
     the colour jitter to every drawn sample inside the same launch (behind a statistics launch where contrast is enabled), with ``augment`` or
     ``crop``, with or without ``mix`` / ``erase``: an epoch's colour records are drawn last of all, after the erase records, so that a seed
     gives the plan, words, windows, mix and erase records it gives without ``color``; they travel in the same copy, two int64 elements per
-    sample, and the yielded tuples are the same (the loss needs nothing from a colour record)."""
+    sample, and the yielded tuples are the same (the loss needs nothing from a colour record).  ``blur`` (a ``GaussianBlur``) blurs the drawn
+    samples its coin picks inside the same launch: an epoch's blur records are drawn last of all, after the colour records, so that a seed
+    gives the plan, words, windows, mix, erase and colour records it gives without ``blur``; they travel in the same copy, two int64 elements
+    per sample.  ``three_augment`` (a ``ThreeAugment``) stands instead of ``color`` and ``blur`` and draws both kinds of record, where they
+    stand: DeiT-III's one-of-three choice and its colour jitter."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
-                 return_index=False, augment=None, mix=None, crop=None, erase=None, color=None):
+                 return_index=False, augment=None, mix=None, crop=None, erase=None, color=None, blur=None, three_augment=None):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -549,6 +658,14 @@ class GpuImageLoader:
         if color is not None and not isinstance(color, ColorJitter):
             raise TypeError(f"color must be a ColorJitter, got {type(color).__name__}")
         self.color = color
+        if three_augment is not None:
+            if not isinstance(three_augment, ThreeAugment):
+                raise TypeError(f"three_augment must be a ThreeAugment, got {type(three_augment).__name__}")
+            if color is not None or blur is not None:
+                raise ValueError("three_augment is exclusive with color and blur: it draws both records itself")
+        if blur is not None and not isinstance(blur, GaussianBlur):
+            raise TypeError(f"blur must be a GaussianBlur, got {type(blur).__name__}")
+        self.blur, self.three_augment = blur, three_augment
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -558,7 +675,7 @@ class GpuImageLoader:
         plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
         if not plan:
             return
-        if self.erase is not None or self.color is not None:
+        if self.erase is not None or self.color is not None or self.blur is not None or self.three_augment is not None:
             yield from self._iter_erased(plan)
             return
         if self.crop is not None:
@@ -655,12 +772,15 @@ class GpuImageLoader:
         a, flat = self.augment, torch.cat(plan)
         n, D = flat.shape[0], self.transform.out_size
         # one pinned block and one asynchronous copy: n int64 indices; the n int32 words (augment) or the n two-word records (crop); the n six-word
-        # mix records (mix); the n eight-word erase records (erase); then the n four-word colour records (color).  Drawn in that order
+        # mix records (mix); the n eight-word erase records (erase); the n four-word colour records (color); then the n four-word blur records (blur).
+        # Drawn in that order; three_augment draws the colour and the blur records together, where they stand
         nw = (n + 1) // 2 if a is not None else (n if self.crop is not None else 0)
         nm = 3 * n if self.mix is not None else 0
         ne = 4 * n if self.erase is not None else 0
-        nc = 2 * n if self.color is not None else 0
-        host = torch.empty(n + nw + nm + ne + nc, dtype=torch.int64, pin_memory=True)
+        three = self.three_augment
+        nc = 2 * n if self.color is not None or three is not None else 0
+        nb = 2 * n if self.blur is not None or three is not None else 0
+        host = torch.empty(n + nw + nm + ne + nc + nb, dtype=torch.int64, pin_memory=True)
         host[:n].copy_(flat)
         if a is not None:
             host[n:n + nw].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
@@ -670,16 +790,26 @@ class GpuImageLoader:
             host[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], D, self.generator))
         if self.erase is not None:
             host[n + nw + nm:n + nw + nm + ne].view(torch.int32).view(n, ERASE_WORDS).copy_(self.erase.draw(n, D, self.generator))
+        oc = n + nw + nm + ne
         if self.color is not None:
-            host[n + nw + nm + ne:].view(torch.int32).view(n, COLOR_WORDS).copy_(self.color.draw(n, self.generator))
+            host[oc:oc + nc].view(torch.int32).view(n, COLOR_WORDS).copy_(self.color.draw(n, self.generator))
+        if self.blur is not None:
+            host[oc + nc:].view(torch.int32).view(n, BLUR_WORDS).copy_(self.blur.draw(n, self.generator))
+        if three is not None:
+            c3, b3 = three.draw(n, self.generator)
+            host[oc:oc + nc].view(torch.int32).view(n, COLOR_WORDS).copy_(c3)
+            host[oc + nc:].view(torch.int32).view(n, BLUR_WORDS).copy_(b3)
         dev = host.to(self.device, non_blocking=True)
         order = dev[:n]
-        boxes = dev[n + nw + nm:n + nw + nm + ne].view(torch.int32).view(n, ERASE_WORDS) if self.erase is not None else None
-        colors = dev[n + nw + nm + ne:].view(torch.int32).view(n, COLOR_WORDS) if self.color is not None else None
-        wants_sums = self.color is not None and self.color.contrast is not None   # the statistics launch runs only where contrast is enabled
+        boxes = dev[n + nw + nm:oc].view(torch.int32).view(n, ERASE_WORDS) if self.erase is not None else None
+        colors = dev[oc:oc + nc].view(torch.int32).view(n, COLOR_WORDS) if nc else None
+        blurs = dev[oc + nc:].view(torch.int32).view(n, BLUR_WORDS) if nb else None
+        jitter = self.color if self.color is not None else three
+        wants_sums = jitter is not None and jitter.contrast is not None   # the statistics launch runs only where contrast is enabled
 
         def late(o, m):
-            return {"erase": None if boxes is None else boxes[o:o + m], "color": None if colors is None else colors[o:o + m], "contrast": wants_sums}
+            return {"erase": None if boxes is None else boxes[o:o + m], "color": None if colors is None else colors[o:o + m], "contrast": wants_sums,
+                    "blur": None if blurs is None else blurs[o:o + m]}
 
         front = dev[n:n + nw].view(torch.int32)
         records = dev[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS) if self.mix is not None else None

@@ -39,6 +39,9 @@ without / with the pixel-noise records.  The condition: (c) faster than (b) and 
 whether it held.  (c), (d), (f) against (a), (h) against (g) and (e) are reported, and so is the largest deviation of the kernel's noise from the
 fp64 evaluation of its formula.  --note FILE appends that file's text as with --mix.
 
+With --blur it measures only the blur forms against the colour entry on records without blur and writes
+profiles/blur_bench.txt: the colour entry, the blur entry with "no blur" records, ThreeAugment records, every sample blurred at radius 0.1 and at
+2.0, and box convolutions as torch ops for scale.
 With --color it measures only the colour forms of the kernel and writes profiles/color_bench.txt: eight arms with the method
 of 2., interleaved over the five repetitions in the one process - (a) the erase entry of the parent with the default erase records, (b) the colour
 entry with the records of ColorJitter(0.4, 0.4, 0.4) and the same erase records, (b-) the same records without the workspace (no statistics
@@ -46,7 +49,7 @@ launch), (c) jitter(0.4, 0, 0.4), (d) / (d-) identity colour records with / with
 as torch ops on the float batch (time only).  Every comparison is against (a), the parent's entry; nothing is required, the figures are
 reported.  --note FILE appends that file's text as with --mix.
 
-usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix | --rrc | --erase | --color [--note FILE]]"""
+usage: python3 tools/bench_input_pipeline.py [--steps K] [--warmup W] [--out FILE] [--augment | --mix | --rrc | --erase | --color | --blur [--note FILE]]"""
 import argparse
 import multiprocessing
 import os
@@ -488,6 +491,82 @@ def color_arms(lines, data, tr):
     return True
 
 
+def blur_arms(lines, data, tr):
+    import qat_vit_amd
+    from tests import blur_ref
+
+    B, D = 256, 224
+    g = torch.Generator(device="cuda").manual_seed(1)
+    idx = torch.randint(0, data.shape[0], (B,), device="cuda", generator=g)
+    words = qat_vit_amd.RandomCropFlip(4).draw(B, torch.Generator().manual_seed(1)).cuda()
+    kw = {"aug": words, "padding_mode": "constant", "padding": 4}
+    boxes = qat_vit_amd.RandomErasing().draw(B, D, torch.Generator().manual_seed(1)).cuda()
+    # (a): the colour bench's 3-Augment-style records (two independent coins, no blur); (c): ThreeAugment's one-of-three choice
+    aug3 = qat_vit_amd.ColorJitter(0.3, 0.3, 0.3, grayscale=1 / 3, solarize=1 / 3).draw(B, torch.Generator().manual_seed(1)).cuda()
+    col3, blur3 = qat_vit_amd.ThreeAugment().draw(B, torch.Generator().manual_seed(1))
+    n_blur = int((blur3[:, 0] & 1).sum())
+    col3, blur3 = col3.cuda(), blur3.cuda()
+    none = torch.zeros(B, 4, dtype=torch.int32, device="cuda")
+    all01 = torch.tensor([blur_ref.pack(0.1)] * B, dtype=torch.int32).cuda()      # box radius 0: 3 halo rows on each side
+    all20 = torch.tensor([blur_ref.pack(2.0)] * B, dtype=torch.int32).cuda()      # box radius 1: 6 halo rows on each side
+    outs = [torch.empty(B, 3, D, D, device="cuda") for _ in range(4)]
+    mean, std = torch.tensor(MEAN, device="cuda").view(1, 3, 1, 1), torch.tensor(STD, device="cuda").view(1, 3, 1, 1)
+    box3 = torch.full((3, 1, 3, 3), 1.0 / 9.0, device="cuda")
+
+    def composed(i):
+        # three 3 x 3 box passes as one depthwise convolution each on the float batch, replicated edge (time only: not Pillow's values)
+        x = tr(data, idx, out=outs[i % 4], erase=boxes, color=aug3, **kw)
+        x = (x * std + mean) * 255.0
+        for _ in range(3):
+            x = torch.nn.functional.conv2d(torch.nn.functional.pad(x, (1, 1, 1, 1), mode="replicate"), box3, groups=3)
+        return (x / 255.0 - mean) / std
+
+    arms = {"a": ("qatvit_image_batch_color, 3-Augment-style records without blur (the parent's entry)",
+                  lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=aug3, **kw)),
+            "b": ("qatvit_image_batch_blur, the same colour records, every blur record \"no blur\"",
+                  lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=aug3, blur=none, **kw)),
+            "c": ("qatvit_image_batch_blur, ThreeAugment records", lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=col3, blur=blur3, **kw)),
+            "d1": ("qatvit_image_batch_blur, (a)'s colour records, every sample blurred at radius 0.1",
+                   lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=aug3, blur=all01, **kw)),
+            "d2": ("qatvit_image_batch_blur, (a)'s colour records, every sample blurred at radius 2.0",
+                   lambda i: tr(data, idx, out=outs[i % 4], erase=boxes, color=aug3, blur=all20, **kw)),
+            "e": ("(a) + three 3 x 3 box convolutions as torch ops on the float batch (time only)", composed)}
+    # what is timed is what the tests hold: "no blur" records give the colour entry's batch
+    assert torch.equal(arms["b"][1](0), arms["a"][1](1)) and not torch.equal(arms["d2"][1](2), arms["a"][1](3))
+    for _, run in arms.values():
+        for i in range(20):
+            run(i)
+    reps = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (_, run) in arms.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            for i in range(200):
+                run(i)
+            ev[1].record()
+            torch.cuda.synchronize()
+            reps[k].append(ev[0].elapsed_time(ev[1]) / 200 * 1e3)
+    med = {k: statistics.median(v) for k, v in reps.items()}
+    spread = {k: max(v) - min(v) for k, v in reps.items()}
+    lines.append("kernel with Gaussian blur (batch 256, S = 32 -> 224, random index into 50,000 resident images, words of RandomCropFlip(4), constant "
+                 "padding, erase records of the default RandomErasing, records drawn once with seed 1), us per batch; HIP events around 200 launches "
+                 "after 20 warm-up launches per arm, five repetitions interleaved a .. e in this one process, output rotating over 616 MB.  Every arm "
+                 "is three stream operations per batch: the zeroing of sums, the statistics launch, the batch launch:")
+    lines.append(f"  records drawn: (c) {n_blur} of 256 blurred, the others grayscale or solarized; every sample holds three jitter ops")
+    for k, (name, _) in arms.items():
+        lines.append(f"  ({k}) {name + ':':<92} median {med[k]:.1f}  ({', '.join(f'{r:.1f}' for r in reps[k])}); spread {spread[k]:.1f}")
+    for k, base in (("b", "a"), ("c", "a"), ("d1", "a"), ("d2", "a"), ("d2", "e")):
+        lines.append(f"  reported: ({k}) / ({base}) = {med[k] / med[base]:.3f}; ({k}) - ({base}) = {med[k] - med[base]:+.1f} us")
+    lines.append(f"  expectation (b) within the run-to-run spread of (a), {spread['a']:.1f} us: (b) - (a) = {med['b'] - med['a']:+.1f} us -> "
+                 f"{'confirmed' if abs(med['b'] - med['a']) <= spread['a'] else 'REFUTED'} (reported, not a gate)")
+    mr = (28 * 32 + D - 1) // D + 5
+    one = D * 5 * 4 + 768 * 4 + ((mr * 32 * 3 + 15) & ~15) + mr * 3 * D
+    lines.append(f"  LDS per workgroup: the blur forms request {((one + 15) & ~15) + 2 * 28 * 3 * D} B without mix records (aug), bands of 16 rows (8 with mix records); "
+                 f"the colour forms {lds_bytes(32, D)[0]} B, bands of 16 rows")
+    return True
+
+
 def lds_bytes(S, D):
     """(aug kernel, mix kernel) dynamic LDS of one workgroup, as csrc/image.hip sizes them: tables, source rows, one or two plane sets."""
     mr = (16 * S + D - 1) // D + 5
@@ -560,13 +639,14 @@ def main():
     ap.add_argument("--rrc", action="store_true", help="only the six arms of the resized-crop kernels")
     ap.add_argument("--erase", action="store_true", help="only the arms of the erasing kernels")
     ap.add_argument("--color", action="store_true", help="only the arms of the colour kernels")
+    ap.add_argument("--blur", action="store_true", help="only the arms of the blur kernels")
     ap.add_argument("--note", default=None, help="with --mix, --rrc, --erase or --color: a text file appended to the output")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "color_bench.txt" if args.color else "erase_bench.txt" if args.erase else "rrc_bench.txt" if args.rrc else "mix_bench.txt" if args.mix else
+        args.out = os.path.join(ROOT, "profiles", "blur_bench.txt" if args.blur else "color_bench.txt" if args.color else "erase_bench.txt" if args.erase else "rrc_bench.txt" if args.rrc else "mix_bench.txt" if args.mix else
                                 "augment_bench.txt" if args.augment else "input_pipeline_bench.txt")
     lines = []
-    if not args.augment and not args.mix and not args.rrc and not args.erase and not args.color:
+    if not args.augment and not args.mix and not args.rrc and not args.erase and not args.color and not args.blur:
         host_path(lines)                  # before the first CUDA call: the pool's processes are forked from a process without a GPU context
     if not torch.cuda.is_available():
         raise SystemExit("bench_input_pipeline.py needs an MI355X: there is no CPU form of the pipeline to time")
@@ -577,7 +657,9 @@ def main():
     labels = torch.randint(0, 10, (50000,), device="cuda", generator=g)
     tr = qat_vit_amd.GpuResizeNormalize(32)
     lines.insert(0, f"input pipeline on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
-    if args.color:
+    if args.blur:
+        ok = blur_arms(lines, data, tr)
+    elif args.color:
         ok = color_arms(lines, data, tr)
     elif args.erase:
         ok = erase_arms(lines, data, tr)
@@ -591,7 +673,7 @@ def main():
         kernel_ms = kernel_time(lines, data, tr)
         ok = step_condition(lines, data, labels, tr, kernel_ms, args.steps, args.warmup)
     lines.append(CLOCK_NOTE)
-    if (args.mix or args.rrc or args.erase or args.color) and args.note:
+    if (args.mix or args.rrc or args.erase or args.color or args.blur) and args.note:
         lines.append("")
         lines.append(open(args.note).read().rstrip("\n"))
     text = "\n".join(lines) + "\n"
