@@ -14,13 +14,11 @@
 //                   weight average from the register that holds the new p where ema_ptrs is given.  12 B + 4 B per parameter (+ 8 B with the average).
 // No atomics, nothing kept per parameter beyond m and v: 40 B of traffic per parameter against AdamW's 28.  (r as a fourth stream would move the same
 // 40 B and cost 4 B per parameter of state; it would save launch 2's divisions and square root, which a kernel bound by HBM does not wait for.)
-#include "../../include/qatvit.h"
-#include "qv_common.h"
 #include "qv_kernels.h"
+#include "qv_optim.h"
 
 namespace qv {
 
-constexpr int kLambThreads = 256;
 constexpr uint32_t kLambAdapt = 1, kLambTrustClip = 2;
 
 struct LambRow {
@@ -63,37 +61,26 @@ __device__ inline float lamb_moments_one(float p, float g, float& m, float& v, c
     return lamb_r(p, m, v, h);
 }
 
-// The weight average: optim.hip's ema_one - ATen's lerp(e, p, w), both branches - with each branch's multiply-add as ONE fused operation.  That is
-// how stock torch.lerp rounds, on this GPU and on the CPU alike (its kernels are built with contraction on: of 200,000 normal samples at w = 0.1
-// 22,503 differ from the two-rounding form and none from this one), and state[p]["ema"] is specified as torch.equal to torch.lerp applied after the
-// step.  The library is built with -ffp-contract=off, so the fusion is written out; d and 1 - w are rounded on their own, as there.  Against
-// ema_one's two roundings the result differs by at most one rounding of the product; w = 1 gives p exactly in both.
-__device__ inline float lamb_ema_one(float e, float p, float w) {
-    const float d = p - e;
-    return w < 0.5f ? fmaf(w, d, e) : fmaf(-d, 1.0f - w, p);
-}
-
-// chunk -> tensor -> group -> row as in k_adamw_groups: the row is read into scalars once, and a tensor of no group gets an empty range (its partials
-// are written as zeros, its trust is not written)
-__global__ __launch_bounds__(kLambThreads) void k_lamb_moments(const LambArgs a) {
-    const int t = a.chunk_tensor[blockIdx.x];
-    const int gi = __builtin_amdgcn_readfirstlane(a.tensor_group[t]);
-    const bool in_group = (unsigned)gi < (unsigned)a.n_groups;
-    const LambRow h = a.group[in_group ? gi : 0];
-    const int64_t lo = (int64_t)a.chunk_index[blockIdx.x] * a.chunk;
-    const int64_t n = a.numel[t];
-    const int64_t hi = !in_group ? lo : lo + a.chunk < n ? lo + a.chunk : n;
-    const float* p = a.params[t];
-    const float* g = a.grads[t];
-    float* m = a.exp_avg[t];
-    float* v = a.exp_avg_sq[t];
+// The row of the tensor's group and the range as in k_adamw_groups (qv_optim.h: group_row, chunk_range); a tensor of no group has its partials written as
+// zeros, its trust is not written.  The two kernels keep their float4 body and scalar tail written out instead of calling walk_range: a closure carries
+// the stream pointers through memory at the point where the compiler decides that they are global addresses, and both kernels came out with flat
+// loads and stores, other scalar-register counts and another schedule ([&] and [=] captures alike; profiles/optim_one_walker_identity.txt).
+__global__ __launch_bounds__(kOptThreads) void k_lamb_moments(const LambArgs a) {
+    bool in_group;
+    const LambRow h = a.group[group_row(a.chunk_tensor, a.tensor_group, a.n_groups, in_group)];
+    const ChunkRange r = chunk_range(a.numel, a.chunk_tensor, a.chunk_index, a.chunk, in_group);
+    const float* p = a.params[r.t];
+    const float* g = a.grads[r.t];
+    float* m = a.exp_avg[r.t];
+    float* v = a.exp_avg_sq[r.t];
     const float coef = a.coef ? a.coef[1] : 1.0f;
-    const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    const bool al = aligned16(p, g, m, v);
+    const int64_t lo = r.lo, hi = r.hi;
     float sr = 0.f, sp = 0.f;
     int64_t tail = lo;
     if (al) {
         const int64_t hi4 = lo + ((hi - lo) & ~(int64_t)3);
-        for (int64_t i = lo + 4 * threadIdx.x; i < hi4; i += 4 * kLambThreads) {
+        for (int64_t i = lo + 4 * threadIdx.x; i < hi4; i += 4 * kOptThreads) {
             const float4 P = *reinterpret_cast<const float4*>(p + i), G = *reinterpret_cast<const float4*>(g + i);
             float4 M = *reinterpret_cast<float4*>(m + i), V = *reinterpret_cast<float4*>(v + i);
             const float rx = lamb_moments_one(P.x, G.x, M.x, V.x, h, coef);
@@ -107,7 +94,7 @@ __global__ __launch_bounds__(kLambThreads) void k_lamb_moments(const LambArgs a)
         }
         tail = hi4;
     }
-    for (int64_t i = tail + threadIdx.x; i < hi; i += kLambThreads) {
+    for (int64_t i = tail + threadIdx.x; i < hi; i += kOptThreads) {
         const float P = p[i];
         float M = m[i], V = v[i];
         const float r = lamb_moments_one(P, g[i], M, V, h, coef);
@@ -115,7 +102,7 @@ __global__ __launch_bounds__(kLambThreads) void k_lamb_moments(const LambArgs a)
         sr += r * r;
         sp += P * P;
     }
-    __shared__ float sw[2][kLambThreads / 64];
+    __shared__ float sw[2][kOptThreads / 64];
     sr = wave_sum(sr);
     sp = wave_sum(sp);
     if ((threadIdx.x & 63) == 0) { sw[0][threadIdx.x >> 6] = sr; sw[1][threadIdx.x >> 6] = sp; }
@@ -133,19 +120,14 @@ __device__ inline double wave_sum_f64(double v) {
 }
 
 template <bool EMA>
-__global__ __launch_bounds__(kLambThreads) void k_lamb_apply(const LambArgs a) {
-    const int t = a.chunk_tensor[blockIdx.x];
-    const int gi = __builtin_amdgcn_readfirstlane(a.tensor_group[t]);
-    const bool in_group = (unsigned)gi < (unsigned)a.n_groups;
-    const LambRow h = a.group[in_group ? gi : 0];
-    const int ck = a.chunk_index[blockIdx.x];
-    const int64_t lo = (int64_t)ck * a.chunk;
-    const int64_t n = a.numel[t];
-    const int64_t hi = !in_group ? lo : lo + a.chunk < n ? lo + a.chunk : n;
+__global__ __launch_bounds__(kOptThreads) void k_lamb_apply(const LambArgs a) {
+    bool in_group;
+    const LambRow h = a.group[group_row(a.chunk_tensor, a.tensor_group, a.n_groups, in_group)];
+    const ChunkRange r = chunk_range(a.numel, a.chunk_tensor, a.chunk_index, a.chunk, in_group);
     // the tensor's two norms: lane l of every wave takes partials l, l + 64, ... of the tensor in double, then one butterfly - the same order in every
     // wave of every workgroup of the tensor, so they all apply the same trust
-    const int64_t first = a.tensor_first_chunk[t];
-    const int64_t nc = in_group ? (n + a.chunk - 1) / a.chunk : 0;
+    const int64_t first = a.tensor_first_chunk[r.t];
+    const int64_t nc = in_group ? (r.n + a.chunk - 1) / a.chunk : 0;
     double sr = 0.0, sp = 0.0;
     for (int64_t c = threadIdx.x & 63; c < nc; c += 64) {
         sr += (double)a.partials[2 * (first + c)];
@@ -160,19 +142,20 @@ __global__ __launch_bounds__(kLambThreads) void k_lamb_apply(const LambArgs a) {
         if (h.flags & kLambTrustClip) trust = fminf(trust, 1.0f);
     }
     trust = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, trust)));
-    if (a.trust_out && in_group && ck == 0 && threadIdx.x == 0) a.trust_out[t] = trust;
+    if (a.trust_out && in_group && r.ck == 0 && threadIdx.x == 0) a.trust_out[r.t] = trust;
     const float step = h.lr * trust;
 
-    float* p = a.params[t];
-    const float* m = a.exp_avg[t];
-    const float* v = a.exp_avg_sq[t];
-    float* e = EMA ? a.ema[t] : nullptr;
+    float* p = a.params[r.t];
+    const float* m = a.exp_avg[r.t];
+    const float* v = a.exp_avg_sq[r.t];
+    float* e = EMA ? a.ema[r.t] : nullptr;
     const float w = a.ema_w;
-    const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(e)) & 15) == 0;
+    const bool al = aligned16(p, m, v, e);
+    const int64_t lo = r.lo, hi = r.hi;
     int64_t tail = lo;
     if (al) {
         const int64_t hi4 = lo + ((hi - lo) & ~(int64_t)3);
-        for (int64_t i = lo + 4 * threadIdx.x; i < hi4; i += 4 * kLambThreads) {
+        for (int64_t i = lo + 4 * threadIdx.x; i < hi4; i += 4 * kOptThreads) {
             float4 P = *reinterpret_cast<float4*>(p + i);
             const float4 M = *reinterpret_cast<const float4*>(m + i), V = *reinterpret_cast<const float4*>(v + i);
             P.x = P.x - step * lamb_r(P.x, M.x, V.x, h);
@@ -191,7 +174,7 @@ __global__ __launch_bounds__(kLambThreads) void k_lamb_apply(const LambArgs a) {
         }
         tail = hi4;
     }
-    for (int64_t i = tail + threadIdx.x; i < hi; i += kLambThreads) {
+    for (int64_t i = tail + threadIdx.x; i < hi; i += kOptThreads) {
         float P = p[i];
         P = P - step * lamb_r(P, m[i], v[i], h);
         p[i] = P;
@@ -199,22 +182,18 @@ __global__ __launch_bounds__(kLambThreads) void k_lamb_apply(const LambArgs a) {
     }
 }
 
-// the rows of `groups` as the kernels' prefactors: formed in double, narrowed once (as qatvit_optim_adamw_groups forms its own)
-static int lamb_rows(const char* fn, const qatvit_lamb_group* groups, int32_t n_groups, LambArgs& a) {
+// the rows of `groups` as the kernels' prefactors, checked in ascending order: formed in double, narrowed once (as adam_prefactors forms AdamW's)
+static bool lamb_rows(const char* fn, const qatvit_lamb_group* groups, int32_t n_groups, LambArgs& a) {
     for (int i = 0; i < n_groups; ++i) {
         const qatvit_lamb_group& g = groups[i];
-        if (!(g.step >= 1 && g.lr >= 0. && g.beta1 >= 0. && g.beta1 < 1. && g.beta2 >= 0. && g.beta2 < 1. && g.eps >= 0. && g.weight_decay >= 0.)) {
-            set_error("%s: bad hyper-parameters in group %d (step=%lld lr=%g betas=(%g, %g) eps=%g weight_decay=%g)", fn, i, (long long)g.step, g.lr,
-                      g.beta1, g.beta2, g.eps, g.weight_decay);
-            return 1;
-        }
+        if (!hyper_ok(fn, i, g.step, g.lr, g.beta1, g.beta2, g.eps, g.weight_decay)) return false;
         const double bc1 = 1.0 - pow(g.beta1, (double)g.step), bc2 = 1.0 - pow(g.beta2, (double)g.step);
         a.group[i] = LambRow{(float)g.beta1, g.grad_averaging ? (float)(1.0 - g.beta1) : 1.0f, (float)g.beta2, (float)(1.0 - g.beta2),
                              (float)bc1, (float)sqrt(bc2), (float)g.eps, (float)g.weight_decay, (float)g.lr,
                              ((g.weight_decay != 0. || g.always_adapt) ? kLambAdapt : 0u) | (g.trust_clip ? kLambTrustClip : 0u)};
     }
     a.n_groups = n_groups;
-    return 0;
+    return true;
 }
 
 }  // namespace qv
@@ -226,17 +205,17 @@ extern "C" {
 int qatvit_optim_lamb_moments(const void* param_ptrs, const void* grad_ptrs, const void* exp_avg_ptrs, const void* exp_avg_sq_ptrs, const int64_t* numel,
                               const int32_t* tensor_group, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks, int64_t chunk_elems,
                               const qatvit_lamb_group* groups, int32_t n_groups, const float* clip_out2, float* partials2, void* stream) {
-    QV_CHECK_ARG(param_ptrs && grad_ptrs && exp_avg_ptrs && exp_avg_sq_ptrs && numel && tensor_group && chunk_tensor && chunk_index && groups && partials2,
-                 "qatvit_optim_lamb_moments: null pointer");
-    QV_CHECK_ARG(n_chunks > 0 && chunk_elems > 0 && chunk_elems % 4 == 0, "qatvit_optim_lamb_moments: bad chunking (n_chunks=%d chunk=%lld)", n_chunks,
-                 (long long)chunk_elems);
-    QV_CHECK_ARG(n_groups >= 1 && n_groups <= QATVIT_OPTIM_MAX_GROUPS, "qatvit_optim_lamb_moments: n_groups %d outside [1, %d]", n_groups,
-                 QATVIT_OPTIM_MAX_GROUPS);
+    const char* fn = "qatvit_optim_lamb_moments";
+    if (!tables_ok(fn, param_ptrs && grad_ptrs && exp_avg_ptrs && exp_avg_sq_ptrs && numel && tensor_group && chunk_tensor && chunk_index && groups &&
+                           partials2,
+                   n_chunks, chunk_elems) ||
+        !n_groups_ok(fn, n_groups))
+        return 1;
     LambArgs a{};
-    a.params = reinterpret_cast<float* const*>(param_ptrs);
-    a.grads = reinterpret_cast<const float* const*>(grad_ptrs);
-    a.exp_avg = reinterpret_cast<float* const*>(exp_avg_ptrs);
-    a.exp_avg_sq = reinterpret_cast<float* const*>(exp_avg_sq_ptrs);
+    a.params = ptr_table<float>(param_ptrs);
+    a.grads = ptr_table<const float>(grad_ptrs);
+    a.exp_avg = ptr_table<float>(exp_avg_ptrs);
+    a.exp_avg_sq = ptr_table<float>(exp_avg_sq_ptrs);
     a.numel = numel;
     a.tensor_group = tensor_group;
     a.chunk_tensor = chunk_tensor;
@@ -244,8 +223,8 @@ int qatvit_optim_lamb_moments(const void* param_ptrs, const void* grad_ptrs, con
     a.chunk = chunk_elems;
     a.coef = clip_out2;
     a.partials = partials2;
-    if (lamb_rows("qatvit_optim_lamb_moments", groups, n_groups, a)) return 1;
-    k_lamb_moments<<<n_chunks, kLambThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
+    if (!lamb_rows(fn, groups, n_groups, a)) return 1;
+    k_lamb_moments<<<n_chunks, kOptThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
     QV_CHECK_LAUNCH("k_lamb_moments");
     return 0;
 }
@@ -254,18 +233,17 @@ int qatvit_optim_lamb_apply(const void* param_ptrs, const void* exp_avg_ptrs, co
                             const int32_t* tensor_group, const int32_t* tensor_first_chunk, const int32_t* chunk_tensor, const int32_t* chunk_index,
                             int32_t n_chunks, int64_t chunk_elems, const qatvit_lamb_group* groups, int32_t n_groups, double ema_decay,
                             const float* partials2, float* trust_out, void* stream) {
-    QV_CHECK_ARG(param_ptrs && exp_avg_ptrs && exp_avg_sq_ptrs && numel && tensor_group && tensor_first_chunk && chunk_tensor && chunk_index && groups &&
-                     partials2,
-                 "qatvit_optim_lamb_apply: null pointer");
-    QV_CHECK_ARG(n_chunks > 0 && chunk_elems > 0 && chunk_elems % 4 == 0, "qatvit_optim_lamb_apply: bad chunking (n_chunks=%d chunk=%lld)", n_chunks,
-                 (long long)chunk_elems);
-    QV_CHECK_ARG(n_groups >= 1 && n_groups <= QATVIT_OPTIM_MAX_GROUPS, "qatvit_optim_lamb_apply: n_groups %d outside [1, %d]", n_groups,
-                 QATVIT_OPTIM_MAX_GROUPS);
+    const char* fn = "qatvit_optim_lamb_apply";
+    if (!tables_ok(fn, param_ptrs && exp_avg_ptrs && exp_avg_sq_ptrs && numel && tensor_group && tensor_first_chunk && chunk_tensor && chunk_index &&
+                           groups && partials2,
+                   n_chunks, chunk_elems) ||
+        !n_groups_ok(fn, n_groups))
+        return 1;
     LambArgs a{};
-    a.params = reinterpret_cast<float* const*>(param_ptrs);
-    a.exp_avg = reinterpret_cast<float* const*>(exp_avg_ptrs);
-    a.exp_avg_sq = reinterpret_cast<float* const*>(exp_avg_sq_ptrs);
-    a.ema = reinterpret_cast<float* const*>(ema_ptrs);
+    a.params = ptr_table<float>(param_ptrs);
+    a.exp_avg = ptr_table<float>(exp_avg_ptrs);
+    a.exp_avg_sq = ptr_table<float>(exp_avg_sq_ptrs);
+    a.ema = ptr_table<float>(ema_ptrs);
     a.numel = numel;
     a.tensor_group = tensor_group;
     a.tensor_first_chunk = tensor_first_chunk;
@@ -274,13 +252,13 @@ int qatvit_optim_lamb_apply(const void* param_ptrs, const void* exp_avg_ptrs, co
     a.chunk = chunk_elems;
     a.partials = const_cast<float*>(partials2);
     a.trust_out = trust_out;
-    if (lamb_rows("qatvit_optim_lamb_apply", groups, n_groups, a)) return 1;
-    if (ema_ptrs) {
-        QV_CHECK_ARG(ema_decay >= 0. && ema_decay < 1., "qatvit_optim_lamb_apply: ema_decay %g outside [0, 1)", ema_decay);   // NaN fails both comparisons
+    if (!lamb_rows(fn, groups, n_groups, a)) return 1;
+    if (ema_ptrs) {   // the decay is looked at only with averages
+        if (!ema_decay_ok(fn, ema_decay)) return 1;
         a.ema_w = (float)(1.0 - ema_decay);
-        k_lamb_apply<true><<<n_chunks, kLambThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
+        k_lamb_apply<true><<<n_chunks, kOptThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
     } else {
-        k_lamb_apply<false><<<n_chunks, kLambThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
+        k_lamb_apply<false><<<n_chunks, kOptThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
     }
     QV_CHECK_LAUNCH("k_lamb_apply");
     return 0;

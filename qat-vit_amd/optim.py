@@ -44,6 +44,19 @@ MAX_GROUPS = 64  # QATVIT_OPTIM_MAX_GROUPS (include/qatvit.h): rows of the prefa
 _HYPER = operator.itemgetter("lr", "betas", "eps", "weight_decay")
 
 
+def _chunk_table(numels):
+    """The (tensor, chunk) table of the multi-tensor launches over tensors of `numels` elements: one row per `_CHUNK` elements of a tensor, a tensor's
+    rows contiguous and in order.  (chunk_tensor, chunk_index, first_chunk): per row its tensor and which of its chunks, per tensor its first row
+    (an empty tensor has none and is never looked up: 0)."""
+    ct, ci, first = [], [], []
+    for ti, numel in enumerate(numels):
+        n = (numel + _CHUNK - 1) // _CHUNK
+        first.append(len(ct) if n else 0)
+        ct += [ti] * n
+        ci += list(range(n))
+    return ct, ci, first
+
+
 def _checked_ema_decay(decay, name="ClipAdamW"):
     if decay is None:
         return None
@@ -143,42 +156,39 @@ class _ClipOptimizer(torch.optim.Optimizer):
                     e = st["ema"]
                     if e.shape != p.shape or e.dtype != torch.float32 or e.device != dev or not e.is_contiguous():
                         raise RuntimeError(f"{self._NAME}: state[p]['ema'] must be a contiguous fp32 tensor of the parameter's shape on its device")
-            starts, ct, ci = [tg.index(gi) for gi in range(len(live))], [], []
-            for ti, p in enumerate(ps):
-                n = (p.numel() + _CHUNK - 1) // _CHUNK
-                ct += [ti] * n
-                ci += list(range(n))
+            starts, numel = [tg.index(gi) for gi in range(len(live))], [p.numel() for p in ps]
+            ct, ci, first_chunk = _chunk_table(numel)
             t = dict(key=key, n=len(ct),
                      params=i64([k[0] for k in ptrs]), grads=i64([k[1] for k in ptrs]), m=i64([k[2] for k in ptrs]), v=i64([k[3] for k in ptrs]),
                      ema=i64([k[4] for k in ptrs]) if ema else None,
-                     tg=i32(tg), numel=i64([p.numel() for p in ps]), ct=i32(ct), ci=i32(ci),
+                     tg=i32(tg), numel=i64(numel), ct=i32(ct), ci=i32(ci),
                      starts=starts, first=[starts[gi] for gi in tg],   # the first tensor of each group; per tensor, the first of its group
                      pack=struct.Struct("=" + "5dq" * len(live)).pack,
                      partials=torch.empty(len(ct), dtype=torch.float32, device=dev), out2=torch.empty(2, dtype=torch.float32, device=dev))
-            self._more_tables(t, ct, len(ps), dev)
+            self._more_tables(t, first_chunk, dev)
             self._tables = t
         t["live"], t["sts"] = live, sts
         return t
 
-    def _more_tables(self, t, ct, n_tensors, dev):
-        """What a subclass's update needs in the table set beyond the common entries (called when the set is rebuilt)."""
+    def _more_tables(self, t, first_chunk, dev):
+        """What a subclass's update needs in the table set beyond the common entries (called when the set is rebuilt); first_chunk: per tensor, where
+        its rows begin in the chunk table."""
 
     def _pair_tables(self, slot, pairs):
         """The tables of a launch over (a, b) tensor pairs (the stand-alone average, the swap), keyed on the addresses; None if there is no element."""
         key = [(a.data_ptr(), b.data_ptr()) for a, b in pairs]
         t = self._pairs.get(slot)
         if t is None or t["key"] != key:
-            dev, ct, ci = pairs[0][0].device, [], []
-            for ti, (a, b) in enumerate(pairs):
+            dev = pairs[0][0].device
+            for a, b in pairs:
                 if not (a.is_cuda and b.device == a.device and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
                         and a.numel() == b.numel()):
                     raise RuntimeError(f"{self._NAME}: a parameter and its average must be contiguous fp32 CUDA tensors of one size on one device")
-                n = (a.numel() + _CHUNK - 1) // _CHUNK
-                ct += [ti] * n
-                ci += list(range(n))
+            numel = [a.numel() for a, _ in pairs]
+            ct, ci, _ = _chunk_table(numel)
             t = self._pairs[slot] = dict(key=key, n=len(ct), a=torch.tensor([k[0] for k in key], dtype=torch.int64, device=dev),
                                          b=torch.tensor([k[1] for k in key], dtype=torch.int64, device=dev),
-                                         numel=torch.tensor([a.numel() for a, _ in pairs], dtype=torch.int64, device=dev),
+                                         numel=torch.tensor(numel, dtype=torch.int64, device=dev),
                                          ct=torch.tensor(ct, dtype=torch.int32, device=dev), ci=torch.tensor(ci, dtype=torch.int32, device=dev))
         return t if t["n"] else None
 
@@ -302,26 +312,23 @@ class ClipAdamW(_ClipOptimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), ema_decay)
 
     def _update(self, t, count, clip):
-        L = native.lib()
-        # with a weight EMA the `_ema` entry of the same name: ema_ptrs after exp_avg_sq_ptrs, the decay (by value, as the prefactors) in front of clip
-        ema = t["ema"] is not None
-        sfx, e_ptr, e_decay = ("_ema", (t["ema"].data_ptr(),), (self._ema_decay,)) if ema else ("", (), ())
-        if len(self.param_groups) == 1:
+        """One launch: qatvit_optim_adamw for an optimizer of one group, qatvit_optim_adamw_groups for several; with a weight EMA the `_ema` entry of the
+        same name, which takes ema_ptrs after exp_avg_sq_ptrs and the decay (by value, as the prefactors) in front of clip."""
+        one, ema = len(self.param_groups) == 1, t["ema"] is not None
+        name = "qatvit_optim_adamw" + ("" if one else "_groups") + ("_ema" if ema else "")
+        if one:
             group = t["live"][0]
             b1, b2 = group["betas"]
-            name = "qatvit_optim_adamw" + sfx
-            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr, t["numel"].data_ptr(),
-                                      t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK, float(group["lr"]), float(b1), float(b2),
-                                      float(group["eps"]), float(group["weight_decay"]), int(count[0]) + 1, *e_decay, clip, native.stream_ptr())
+            hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), int(count[0]) + 1)
         else:   # the rows of struct qatvit_adamw_group, packed on the host; they go by value into the kernel arguments: a new lr costs no copy
             rows = []
             for (lr, (b1, b2), eps, wd), i in zip(map(_HYPER, t["live"]), t["starts"]):
                 rows += (lr, b1, b2, eps, wd, int(count[i]) + 1)
-            name = "qatvit_optim_adamw_groups" + sfx
-            status = getattr(L, name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), *e_ptr,
-                                      t["numel"].data_ptr(), t["tg"].data_ptr(), t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK,
-                                      t["pack"](*rows), len(t["live"]), *e_decay, clip, native.stream_ptr())
-        native.check(status, name)
+            hyper = (t["pack"](*rows), len(t["live"]))
+        native.check(getattr(native.lib(), name)(t["params"].data_ptr(), t["grads"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(),
+                                                 *((t["ema"].data_ptr(),) if ema else ()), t["numel"].data_ptr(), *(() if one else (t["tg"].data_ptr(),)),
+                                                 t["ct"].data_ptr(), t["ci"].data_ptr(), t["n"], _CHUNK, *hyper, *((self._ema_decay,) if ema else ()), clip,
+                                                 native.stream_ptr()), name)
 
 
 _LAMB_FLAGS = operator.itemgetter("grad_averaging", "always_adapt", "trust_clip")
@@ -346,13 +353,10 @@ class ClipLamb(_ClipOptimizer):
                                       always_adapt=bool(always_adapt), trust_clip=bool(trust_clip)), ema_decay)
         self._trust = None
 
-    def _more_tables(self, t, ct, n_tensors, dev):
-        first = [0] * n_tensors   # a tensor's chunks are contiguous: where each tensor's begin (an empty tensor has none and is never looked up)
-        for c in range(len(ct) - 1, -1, -1):
-            first[ct[c]] = c
-        t["first_chunk"] = torch.tensor(first, dtype=torch.int32, device=dev)
-        t["partials2"] = torch.empty(2 * len(ct), dtype=torch.float32, device=dev)
-        t["trust"] = torch.ones(n_tensors, dtype=torch.float32, device=dev)
+    def _more_tables(self, t, first_chunk, dev):
+        t["first_chunk"] = torch.tensor(first_chunk, dtype=torch.int32, device=dev)
+        t["partials2"] = torch.empty(2 * t["n"], dtype=torch.float32, device=dev)
+        t["trust"] = torch.ones(len(first_chunk), dtype=torch.float32, device=dev)
         t["pack"] = struct.Struct("=" + "5dq4i" * len(t["starts"])).pack   # rows of struct qatvit_lamb_group
 
     def _update(self, t, count, clip):
