@@ -850,6 +850,37 @@ int qatvit_optim_lamb_apply(const void* param_ptrs, const void* exp_avg_ptrs, co
  *   The kernels keep a band of 8 output rows with up to 6 halo rows on each side, per side of a mix record, and one more such buffer in LDS:
  *   above 64 KB the call is refused with an error string before any HIP call (32 -> 224 with mix is served).  blur == NULL makes the call
  *   qatvit_image_batch_color's / qatvit_image_batch_rrc_color's: the result is bitwise its result.
+ *
+ * qatvit_image_window_u8: the window stage, a launch of its own IN FRONT of the batch launch, for sources that are not square or are larger
+ *   than the output (the entries above refuse both).  data uint8 [N][H][W][3] (HWC, contiguous, on the device); index int64 [B] or NULL with
+ *   the rule above (an index outside 0 .. N-1 is clamped and never reads outside data); rrc int32 [B][2], the record of
+ *   qatvit_image_batch_rrc with S read as H for top / h and as W for left / w; out uint8 [B][D][D][3] (HWC, contiguous, 4-byte aligned).
+ *   out[b] EQUALS, byte for byte,
+ *     Image.fromarray(I).crop(window)[.transpose(FLIP_LEFT_RIGHT)].resize((D, D), BICUBIC)
+ *   of image index[b] and record b: torchvision's resized_crop + hflip.  The batch launch at S = D on these bytes is the identity resize (the
+ *   cubic at integer offsets is 0, 1, 0, 0), so qatvit_image_batch* (D, D) on out, with index == NULL and without rrc, applies colour, erase,
+ *   mix and Normalize to it at batch positions.
+ *   Pillow stretches its filter when it shrinks.  One axis n -> D, all in double on the host:
+ *     scale = n / D, fs = max(scale, 1.0), support = 2.0 * fs, ss = 1.0 / fs; per output xx:
+ *     center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), ntaps = min((int)(center + support + 0.5), n) - xmin,
+ *     w[i] = cubic((i + xmin - center + 0.5) * ss) with the cubic above (a = -0.5), ww = their sum in index order, w[i] /= ww unless ww == 0,
+ *     k[i] = (int)(+-0.5 + w[i] * 2^22) with the sign of w[i].
+ *   A pass is clip8((2^21 + SUM k[i] * px[xmin + i]) >> 22) in int32: the horizontal pass over the window (table of w) rounds to uint8, the
+ *   vertical pass runs over those bytes (table of h).  Edges are the window's edges: no pixel outside the window enters the result.
+ *   For n <= D this is qatvit_image_resize_coeffs' table (support 2, up to 4 taps) wherever that entry builds one; for n <= 4 D, support <= 8
+ *   and ntaps <= 17.  Where center -+ support + 0.5 falls on an integer, the rounding of the doubles gives some outputs one tap more than
+ *   ceil(2 * support) - five at n = 12 -> D = 44, which qatvit_image_resize_coeffs refuses.  That tap lies at the distance of the support,
+ *   its coefficient is 0, and this builder keeps it (ntaps is Pillow's) after checking that it is 0: every admitted (n, D) is built.
+ *   tables int32 [max_side][D * 19] on the device, 4-byte aligned: table n - 1 is xmin[D], ntaps[D], coef[D][17] of n -> D one after the other
+ *   (coefficients past ntaps are 0), n = 1 .. max_side, as qatvit_image_window_coeffs(max_side, D, out_host) writes them on the HOST (no HIP
+ *   call) into qatvit_image_window_coeffs_bytes(max_side, D) bytes (-1 + error string for a refused shape); max_side >= max(H, W).  The
+ *   builder applies qatvit_image_resize_coeffs' checks: every coefficient fits 24 bits, no int32 accumulator overflows, and a band of 8
+ *   output rows reads no more rows than the kernel keeps.
+ *   D % 4 == 0, 8 <= D <= 384, 8 <= H, W <= 4 * D, 8 <= max_side <= 4 * D, 1 <= B <= 65535: anything else is refused with an error string
+ *   before any HIP call, and so is a shape whose LDS request (the band's resampled rows and a staging buffer of source rows) exceeds 64 KB -
+ *   none within these limits does.
+ *   A malformed record is made safe, not trusted, as the rrc entries do it: h is clamped to [1, H] and w to [1, W], then top to [0, H - h]
+ *   and left to [0, W - w]; any two words are safe, and the result is the clamped record's.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -880,6 +911,10 @@ int qatvit_image_batch_blur(const uint8_t* data, const int64_t* index, int32_t B
 int qatvit_image_batch_rrc_blur(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t S, int32_t D, const int32_t* windows,
                                 const float* table, const int32_t* rrc, const int32_t* mix, const int32_t* erase, const int32_t* color,
                                 uint32_t* sums, const int32_t* blur, float* out, void* stream);
+int64_t qatvit_image_window_coeffs_bytes(int32_t max_side, int32_t D);
+int qatvit_image_window_coeffs(int32_t max_side, int32_t D, int32_t* out_host);
+int qatvit_image_window_u8(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t H, int32_t W, int32_t D,
+                           const int32_t* tables, int32_t max_side, const int32_t* rrc, uint8_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

@@ -635,6 +635,41 @@ int qatvit_image_batch_rrc_blur(const uint8_t* data, const int64_t* index, int32
     return image_run("qatvit_image_batch_rrc_blur", r, stream, "the call without window records is qatvit_image_batch_blur");
 }
 
+// The window stage (image_window.hip): the output size and a side of the source, every check before any HIP call
+static int window_shape_ok(const char* who, const char* what, int32_t side, int32_t D) {
+    QV_CHECK_ARG(D % 4 == 0 && D >= 8 && D <= kImgMaxD, "%s: output size %d must be a multiple of 4 in 8 .. %d", who, D, kImgMaxD);
+    QV_CHECK_ARG(side >= 8 && side <= kWinMaxScale * D, "%s: %s %d is outside 8 .. %d (%d times the output size %d)", who, what, side,
+                 kWinMaxScale * D, kWinMaxScale, D);
+    return 0;
+}
+
+int64_t qatvit_image_window_coeffs_bytes(int32_t max_side, int32_t D) {
+    if (window_shape_ok("qatvit_image_window_coeffs_bytes", "max_side", max_side, D)) return -1;
+    return image_window_coeffs_words(max_side, D) * 4;
+}
+
+int qatvit_image_window_coeffs(int32_t max_side, int32_t D, int32_t* out_host) {
+    QV_CHECK_ARG(out_host, "qatvit_image_window_coeffs: null pointer argument");
+    if (window_shape_ok("qatvit_image_window_coeffs", "max_side", max_side, D)) return 1;
+    return image_window_coeffs(max_side, D, out_host);
+}
+
+int qatvit_image_window_u8(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t H, int32_t W, int32_t D, const int32_t* tables,
+                           int32_t max_side, const int32_t* rrc, uint8_t* out, void* stream) {
+    const char* who = "qatvit_image_window_u8";
+    QV_CHECK_ARG(data && tables && rrc && out, "%s: null pointer argument", who);
+    if (window_shape_ok(who, "source height", H, D) || window_shape_ok(who, "source width", W, D)) return 1;
+    QV_CHECK_ARG(max_side >= H && max_side >= W, "%s: tables of %d sides do not serve a %d x %d source", who, max_side, H, W);
+    QV_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "%s: batch %d must be 1 .. 65535 and the data set (%d images) not empty", who, B, N);
+    QV_CHECK_ARG(index || B <= N, "%s: batch %d of a data set of %d images needs an index", who, B, N);
+    QV_CHECK_ARG((((uintptr_t)tables | (uintptr_t)rrc | (uintptr_t)out) & 3) == 0 && ((uintptr_t)index & 7) == 0, "%s: misaligned pointer", who);
+    ImageWindow r;
+    r.data = data, r.index = index, r.B = B, r.N = N, r.H = H, r.W = W, r.D = D, r.tables = tables, r.rrc = rrc, r.out = out;
+    if (int rc = launch_image_window(r, (hipStream_t)stream)) return rc;
+    QV_CHECK_LAUNCH(who);
+    return 0;
+}
+
 int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {
     RowMoveTab t;
     t.n = 1; t.m[0] = RowMove{tall, compact, stride, width};

@@ -406,6 +406,24 @@ int64_t image_blur_lds_bytes(int S, int D, bool mixed, bool rrc);
 int launch_image_blur(const ImageBatch& r, hipStream_t st);
 // nonzero + set_error: 1 before any HIP call where the form's LDS request exceeds kImgMixMaxLds (the window forms, and the others with mix), 2 where zeroing sums fails
 int launch_image_batch(const ImageBatch& r, hipStream_t st);
+// image_window.hip: the window stage in front of the batch launch, for sources larger than the output.  A side n -> D has up to kWinTaps taps
+// (n <= 4 D: support <= 8); tables = int32 [sides][D * (2 + kWinTaps)], table n - 1 = {xmin[D], ntaps[D], coef[D][kWinTaps]} of n -> D
+constexpr int kWinTaps = 17, kWinBand = 8, kWinMaxScale = 4, kWinStageBytes = 16 * 1024;
+int64_t image_window_coeffs_words(int max_side, int D);
+int image_window_coeffs(int max_side, int D, int32_t* out);   // host only; nonzero + set_error when the kernel's bounds do not hold
+int image_window_max_rows(int n, int D);
+int64_t image_window_lds_bytes(int H, int W, int D);
+// out uint8 [B, D, D, 3] from the windows rrc [B][2] of data uint8 [N, H, W, 3] through index int64 [B] (nullptr: image b)
+struct ImageWindow {
+    const uint8_t* data = nullptr;
+    const int64_t* index = nullptr;
+    int B = 0, N = 0, H = 0, W = 0, D = 0;
+    const int32_t* tables = nullptr;
+    const int32_t* rrc = nullptr;
+    uint8_t* out = nullptr;
+};
+// nonzero + set_error: 1 before any HIP call where the LDS request exceeds kImgMixMaxLds
+int launch_image_window(const ImageWindow& r, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

@@ -13,6 +13,9 @@ writes the fp32 ``[B, 3, 224, 224]`` batch those transforms would have produced,
 the same launch; contrast takes the sample's mean luma from a statistics launch in front of it (section 7q).
 ``GaussianBlur`` blurs the uint8 image behind the resize as Pillow's ``ImageFilter.GaussianBlur`` does, between grayscale / solarize and the jitter
 ops, inside the same launch; ``ThreeAugment`` draws DeiT-III's one-of-three choice with its colour jitter (section 7v).
+``GpuWindowResize`` / ``GpuWideResizeNormalize`` serve sources that are rectangles or larger than the output: a window stage of its own
+(``qatvit_image_window_u8``, Pillow's stretched filter, up to 17 taps) writes the resized uint8 windows, and the batch launch at S = D applies the
+rest to them (section 7x).
 There is no CPU path: CPU tensors raise."""
 import math
 import os
@@ -111,7 +114,11 @@ class RandomResizedCrop:
         self.flip = float(flip)
 
     def draw(self, n, src_size, generator=None):
-        """int32 CPU tensor [n, 2] for square sources of side S = `src_size`.  The rule (torchvision's ``RandomResizedCrop.get_params``,
+        """int32 CPU tensor [n, 2] for square sources of side S = `src_size`, or for ``H x W`` sources where `src_size` is a pair ``(H, W)``:
+        then ``area = H * W * ...``, a try fits when ``1 <= w <= W`` and ``1 <= h <= H``, the fallback compares ``in_ratio = W / H`` with the
+        ratio range (``in_ratio < r0``: ``w = W, h = round(W / r0)``; ``in_ratio > r1``: ``h = H, w = round(H * r1)``; otherwise the whole
+        image), ``top`` is drawn in ``H - h + 1`` and ``left`` in ``W - w + 1`` values, and the fallback window is centred on both axes.  For
+        a number S the tensor is what ``(S, S)`` gives.  The rule (torchvision's ``RandomResizedCrop.get_params``,
         restated: torchvision is not a dependency), with ``scale = (s0, s1)``, ``ratio = (r0, r1)``, all from `generator`, in this order:
         ``u = torch.rand(n, 10, 2, dtype=float64)``: ten tries per sample, ``area = S^2 * (s0 + u[..., 0] * (s1 - s0))``,
         ``aspect = exp(log r0 + u[..., 1] * (log r1 - log r0))``, ``w = torch.round(sqrt(area * aspect))``,
@@ -122,29 +129,35 @@ class RandomResizedCrop:
         ``v = torch.rand(n, 3, dtype=float64)``: ``top = floor(v[:, 0] * (S - h + 1))``, ``left = floor(v[:, 1] * (S - w + 1))`` (both unused by
         the fallback), ``flip = v[:, 2] < flip``.
         Both ``rand`` calls are always made, so the generator ends where it ends for any setting."""
-        S = int(src_size)
-        if not 1 <= S <= 0x7fff:
-            raise ValueError(f"src_size must be 1 .. 32767, got {src_size!r}")
+        if isinstance(src_size, (tuple, list)):
+            if len(src_size) != 2 or not all(1 <= int(t) <= 0x7fff for t in src_size):
+                raise ValueError(f"src_size must be 1 .. 32767 or a pair (H, W) of such numbers, got {src_size!r}")
+            H, W = int(src_size[0]), int(src_size[1])
+        else:
+            H = W = int(src_size)
+            if not 1 <= H <= 0x7fff:
+                raise ValueError(f"src_size must be 1 .. 32767, got {src_size!r}")
         (s0, s1), (r0, r1) = self.scale, self.ratio
         u = torch.rand(n, 10, 2, dtype=torch.float64, generator=generator)
         v = torch.rand(n, 3, dtype=torch.float64, generator=generator)
-        area = float(S * S) * (s0 + u[..., 0] * (s1 - s0))
+        area = float(H * W) * (s0 + u[..., 0] * (s1 - s0))
         aspect = torch.exp(math.log(r0) + u[..., 1] * (math.log(r1) - math.log(r0)))
         w, h = torch.round(torch.sqrt(area * aspect)), torch.round(torch.sqrt(area / aspect))
-        fits = (w >= 1) & (w <= S) & (h >= 1) & (h <= S)
+        fits = (w >= 1) & (w <= W) & (h >= 1) & (h <= H)
         first = fits.to(torch.int8).argmax(1, keepdim=True)           # the first maximum: the first try that fits (0 where none does)
         found = fits.any(1)
         w, h = w.gather(1, first)[:, 0].to(torch.int64), h.gather(1, first)[:, 0].to(torch.int64)
-        if r0 > 1.0:
-            fw, fh = S, max(1, int(round(S / r0)))
-        elif r1 < 1.0:
-            fw, fh = max(1, int(round(S * r1))), S
+        in_ratio = float(W) / float(H)
+        if in_ratio < r0:
+            fw, fh = W, min(H, max(1, int(round(W / r0))))
+        elif in_ratio > r1:
+            fw, fh = min(W, max(1, int(round(H * r1)))), H
         else:
-            fw, fh = S, S
+            fw, fh = W, H
         w, h = torch.where(found, w, torch.full_like(w, fw)), torch.where(found, h, torch.full_like(h, fh))
-        top = torch.minimum(torch.floor(v[:, 0] * (S - h + 1)).to(torch.int64), S - h)
-        left = torch.minimum(torch.floor(v[:, 1] * (S - w + 1)).to(torch.int64), S - w)
-        top, left = torch.where(found, top, (S - h) // 2), torch.where(found, left, (S - w) // 2)
+        top = torch.minimum(torch.floor(v[:, 0] * (H - h + 1)).to(torch.int64), H - h)
+        left = torch.minimum(torch.floor(v[:, 1] * (W - w + 1)).to(torch.int64), W - w)
+        top, left = torch.where(found, top, (H - h) // 2), torch.where(found, left, (W - w) // 2)
         flip = (v[:, 2] < self.flip).to(torch.int64)
         return torch.stack([top | left << 16, h | w << 15 | flip << 30], 1).to(torch.int32)
 
@@ -588,6 +601,159 @@ class GpuResizeNormalize:
         return out
 
 
+WINDOW_TAPS = 17
+WINDOW_MAX_SCALE = 4
+BLUR_LDS_CAP = 64 * 1024
+
+
+def window_stage_tables(max_side: int, out_size: int):
+    """int32 CPU tensor [max_side, 19 * D]: row n - 1 holds xmin [D], ntaps [D], coef [D, 17] of Pillow's 8-bit bicubic resample from n to
+    out_size one after the other, for every window side n = 1 .. max_side <= 4 * D, with the filter stretched where n > D (host only, no GPU).
+    For n <= D the first four coefficients, xmin and ntaps are ``resize_tables(n, D)``.  4 * 19 * D * max_side bytes: 15.3 MB at D = 224
+    with max_side = 896, 4.4 MB for 256 x 256 sources."""
+    nbytes = native.lib().qatvit_image_window_coeffs_bytes(int(max_side), int(out_size))
+    if nbytes < 0:
+        native.check(1, "qatvit_image_window_coeffs_bytes")
+    out = torch.empty(int(max_side), nbytes // (4 * int(max_side)), dtype=torch.int32)
+    native.check(native.lib().qatvit_image_window_coeffs(int(max_side), int(out_size), out.data_ptr()), "qatvit_image_window_coeffs")
+    return out
+
+
+def center_crop_window(H, W, frac=1.0):
+    """``(top, left, side, side)`` of torchvision's ``CenterCrop(side)`` on an ``H x W`` image, ``side = max(1, round(frac * min(H, W)))``:
+    ``top = int(round((H - side) / 2.0))``, ``left = int(round((W - side) / 2.0))`` with Python's round.  As the default window of a
+    ``GpuWindowResize`` / ``GpuWideResizeNormalize`` this is crop-THEN-resize: the central square of the source resized to the output, not
+    ``Resize(256)`` + ``CenterCrop(224)``, which resizes first and whose crop is then not resampled again."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or not 0 < frac <= 1:
+        raise ValueError(f"center_crop_window needs H, W >= 1 and 0 < frac <= 1, got {H}, {W}, {frac!r}")
+    side = max(1, int(round(frac * min(H, W))))
+    return int(round((H - side) / 2.0)), int(round((W - side) / 2.0)), side, side
+
+
+def _pair(src_size):
+    if not isinstance(src_size, (tuple, list)) or len(src_size) != 2:
+        raise ValueError(f"src_size must be a pair (H, W), got {src_size!r}")
+    return int(src_size[0]), int(src_size[1])
+
+
+class GpuWindowResize:
+    """uint8 ``[N, H, W, 3]`` images on the device -> uint8 ``[B, D, D, 3]``: per batch position the window of its record, mirrored where the
+    record says so, resized as ``Image.crop(window).resize((D, D), BICUBIC)`` resizes it, in one launch (``qatvit_image_window_u8``; DESIGN.md
+    section 7x).  The source may be a rectangle and larger than the output, up to ``4 * D`` on a side: Pillow's filter is stretched where a
+    window side exceeds D, up to 17 taps.  ``rrc`` (int32 ``[B, 2]`` on the device) holds ``RandomResizedCrop.draw(n, (H, W))``'s records,
+    record b for batch position b; ``rrc=None`` takes the default window for every sample: the whole image, or ``window = (top, left, h, w)``
+    (e.g. ``center_crop_window(H, W)``).  The tables of every window side are built at construction and kept on the device."""
+
+    def __init__(self, src_size, out_size=224, device="cuda", window=None):
+        self.src_size, self.out_size = _pair(src_size), int(out_size)
+        H, W = self.src_size
+        if window is None:
+            window = (0, 0, H, W)
+        if not isinstance(window, (tuple, list)) or len(window) != 4 or not all(isinstance(t, int) and not isinstance(t, bool) for t in window):
+            raise ValueError(f"window must be four integers (top, left, h, w), got {window!r}")
+        top, left, h, w = window
+        if not (1 <= h <= H and 1 <= w <= W and 0 <= top <= H - h and 0 <= left <= W - w):
+            raise ValueError(f"window {window!r} does not lie inside the {H} x {W} source")
+        self.window = (top, left, h, w)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GpuWindowResize runs on MI355X only: device must be a CUDA device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if min(H, W) < 8:
+            raise ValueError(f"the source {H} x {W} has a side below 8")
+        self.max_side = max(H, W)
+        self.tables = window_stage_tables(self.max_side, self.out_size).to(self.device)   # (refuses a bad D and a side above 4 * D)
+        self._default = {}
+
+    def default_records(self, B):
+        """int32 ``[B, 2]`` on the device: the default window's record at every position; one tensor per distinct batch size, made on first
+        use and kept for the life of the transform."""
+        if B not in self._default:
+            top, left, h, w = self.window
+            self._default[B] = torch.tensor([[top | left << 16, h | w << 15]] * B, dtype=torch.int32).reshape(B, RRC_WORDS).to(self.device)
+        return self._default[B]
+
+    def __call__(self, data_u8, index=None, rrc=None, out=None):
+        (H, W), D = self.src_size, self.out_size
+        if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
+            raise RuntimeError("GpuWindowResize runs on MI355X only: move the uint8 images to the GPU")
+        if data_u8.dtype != torch.uint8:
+            raise TypeError(f"images must be uint8, got {data_u8.dtype}")
+        if data_u8.dim() != 4 or tuple(data_u8.shape[1:]) != (H, W, 3):
+            raise ValueError(f"images must be [N, {H}, {W}, 3] (HWC), got {tuple(data_u8.shape)}")
+        if not data_u8.is_contiguous() or data_u8.device != self.device:
+            raise ValueError(f"images must be contiguous and on {self.device}")
+        N = data_u8.shape[0]
+        if index is None:
+            B, ip = N, None
+        else:
+            if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != self.device:
+                raise ValueError(f"index must be a contiguous 1-D int64 tensor on {self.device}")
+            B, ip = index.shape[0], index.data_ptr()
+        if out is None:
+            out = torch.empty(B, D, D, 3, dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (B, D, D, 3) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous uint8 [{B}, {D}, {D}, 3] tensor on {self.device}")
+        if rrc is None:
+            rrc = self.default_records(B)
+        elif not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
+                or rrc.device != self.device:
+            raise ValueError(f"rrc must be a contiguous int32 [{B}, {RRC_WORDS}] tensor on {self.device}")
+        if not B:
+            return out
+        with torch.cuda.device(self.device):
+            native.check(native.lib().qatvit_image_window_u8(data_u8.data_ptr(), ip, B, N, H, W, D, self.tables.data_ptr(), self.max_side,
+                                                             rrc.data_ptr(), out.data_ptr(), native.stream_ptr()), "qatvit_image_window_u8")
+        return out
+
+
+class GpuWideResizeNormalize:
+    """Stands where a ``GpuResizeNormalize`` stands, for uint8 ``[N, H, W, 3]`` sources that are rectangles or larger than the output (up to
+    ``4 * D`` on a side): two launches per batch.  Stage 1 (``GpuWindowResize``) writes the uint8 ``[B, D, D, 3]`` bytes of every sample's
+    resized window into a staging buffer this object owns, one per batch size (no allocation per step, and static addresses, so a captured
+    graph replays); stage 2 is a ``GpuResizeNormalize(D, D)`` on those bytes at batch positions, whose resize is the identity and which
+    applies ``color``, ``erase``, ``mix`` and ``Normalize`` as it does for a small source.  ``__call__`` has ``GpuResizeNormalize``'s
+    keywords; ``rrc`` records are ``RandomResizedCrop.draw(n, (H, W))``'s, ``rrc=None`` is the default ``window`` (the whole image, or e.g.
+    ``center_crop_window(H, W)``).  ``aug`` is refused: padding applies to CIFAR-style sources.  ``blur`` is refused: the blur forms keep
+    source rows and planes in LDS, and at S = D = 224 that is 89,536 bytes (98,272 with mix records), above the 65,536-byte cap."""
+
+    def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda", window=None):
+        self.stage = GpuWindowResize(src_size, out_size, device, window)
+        self.src_size, self.out_size, self.device, self.window = self.stage.src_size, self.stage.out_size, self.stage.device, self.stage.window
+        self.inner = GpuResizeNormalize(self.out_size, self.out_size, mean, std, self.device)
+        self.mean, self.std = self.inner.mean, self.inner.std
+        self._staged = {}
+
+    def staged(self, B):
+        """The uint8 ``[B, D, D, 3]`` staging buffer of a batch of B, made on first use: behind a call it holds stage 1's bytes.  One buffer
+        per distinct batch size (a loader has two: the full and the last batch), kept for the life of the transform, never released."""
+        if B not in self._staged:
+            self._staged[B] = torch.empty(B, self.out_size, self.out_size, 3, dtype=torch.uint8, device=self.device)
+        return self._staged[B]
+
+    def color_sums(self, B):
+        return self.inner.color_sums(B)
+
+    @staticmethod
+    def refuse(aug=None, blur=None):
+        if aug is not None:
+            raise ValueError("aug does not apply to a wide source: RandomCrop's padding is for CIFAR-style sources; use rrc records")
+        if blur is not None:
+            raise NotImplementedError(f"blur is not served on a wide source: the blur forms stage source rows plus planes in LDS, and at S = D = 224 "
+                                      f"they ask for 89,536 bytes, above the cap of {BLUR_LDS_CAP} bytes")
+
+    def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None, erase=None,
+                 color=None, contrast=True, blur=None):
+        self.refuse(aug, blur)                                       # padding_mode, fill and padding describe aug, which is refused: nothing reads them
+        if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
+            raise RuntimeError("GpuWideResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
+        B = data_u8.shape[0] if index is None else index.shape[0]
+        staged = self.stage(data_u8, index, rrc, out=self.staged(B))
+        return self.inner(staged, None, out=out, mix=mix, erase=erase, color=color, contrast=contrast)
+
+
 def epoch_batches(n, batch_size, shuffle=False, sampler=None, drop_last=False, generator=None):
     """The plan of one epoch, on the host: a list of 1-D int64 CPU tensors, batch by batch, with DataLoader's meaning of every argument (its own
     sampler classes draw the order; shuffle is RandomSampler's permutation from `generator`).  `sampler` is any iterable of indices."""
@@ -627,8 +793,16 @@ class GpuImageLoader:
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
-        if data_u8.dtype != torch.uint8 or data_u8.dim() != 4 or data_u8.shape[1] != data_u8.shape[2] or data_u8.shape[3] != 3:
+        wide = isinstance(transform, GpuWideResizeNormalize)
+        if wide:
+            H, W = transform.src_size
+            if data_u8.dtype != torch.uint8 or data_u8.dim() != 4 or tuple(data_u8.shape[1:]) != (H, W, 3):
+                raise ValueError(f"images must be uint8 [N, {H}, {W}, 3] (HWC) for this transform, got {data_u8.dtype} {tuple(data_u8.shape)}")
+            transform.refuse(augment, blur if blur is not None else three_augment)
+        elif data_u8.dtype != torch.uint8 or data_u8.dim() != 4 or data_u8.shape[1] != data_u8.shape[2] or data_u8.shape[3] != 3:
             raise ValueError(f"images must be uint8 [N, S, S, 3] (HWC), got {data_u8.dtype} {tuple(data_u8.shape)}")
+        # what crop.draw takes: the side of a square source, or (H, W) of a wide transform's
+        self.crop_size = tuple(transform.src_size) if wide else data_u8.shape[1]
         if labels.dim() != 1 or labels.shape[0] != data_u8.shape[0]:
             raise ValueError("labels must be one integer per image")
         self.transform = transform if transform is not None else GpuResizeNormalize(data_u8.shape[1], device=device)
@@ -753,7 +927,7 @@ class GpuImageLoader:
         # one pinned block and one asynchronous copy: n int64 indices, the n two-word int32 records, then (with mix) the n six-word int32 records
         host = torch.empty(2 * n + nm, dtype=torch.int64, pin_memory=True)
         host[:n].copy_(flat)
-        host[n:2 * n].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.data.shape[1], self.generator))
+        host[n:2 * n].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.crop_size, self.generator))
         if self.mix is not None:
             host[2 * n:].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], self.transform.out_size, self.generator))
         dev = host.to(self.device, non_blocking=True)
@@ -785,7 +959,7 @@ class GpuImageLoader:
         if a is not None:
             host[n:n + nw].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
         elif self.crop is not None:
-            host[n:n + nw].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.data.shape[1], self.generator))
+            host[n:n + nw].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.crop_size, self.generator))
         if self.mix is not None:
             host[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], D, self.generator))
         if self.erase is not None:

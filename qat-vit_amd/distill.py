@@ -28,12 +28,20 @@ FIELDS = ("N", "C", "teacher_form", "transform", "data_digest", "param_digest")
 
 
 def transform_tuple(transform) -> tuple:
-    """``(src_size, out_size, mean, std)`` of a ``GpuResizeNormalize`` (or of such a tuple itself), in plain Python numbers."""
+    """``(src_size, out_size, mean, std)`` of a ``GpuResizeNormalize`` (or of such a tuple itself), in plain Python numbers; of a
+    ``GpuWideResizeNormalize``, ``((H, W), out_size, mean, std, (top, left, h, w))`` with its default window."""
     if isinstance(transform, (tuple, list)):
-        src, out, mean, std = transform
+        src, out, mean, std = transform[:4]
+        window = transform[4] if len(transform) > 4 else None
     else:
         src, out, mean, std = transform.src_size, transform.out_size, transform.mean, transform.std
-    return int(src), int(out), tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        window = getattr(transform, "window", None)
+    plain = (int(out), tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    if isinstance(src, (tuple, list)):
+        # a GpuWideResizeNormalize: (H, W) in the place of the side, and behind the rest the default window, which decides what the teacher saw
+        H, W = (int(v) for v in src)
+        return ((H, W),) + plain + (tuple(int(v) for v in (window if window is not None else (0, 0, H, W))),)
+    return (int(src),) + plain
 
 
 def data_digest(data_u8, labels=None) -> str:
