@@ -8,65 +8,13 @@
 namespace qv {
 
 // ---------------------------------------------------------------------------------------------------------------- host: the two tables
-static double cubic(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
+#include "image_tables.h"
 
 int image_max_rows(int S, int D) { return (kImgBand * S + D - 1) / D + kImgTaps + 1; }
 
+// src <= dst: the filter is not stretched, and the kernel takes all kImgTaps taps
 int image_resize_coeffs(int src, int dst, int32_t* xmin_out, int32_t* ntaps_out, int32_t* coef) {
-    const double scale = (double)src / (double)dst, support = 2.0;   // src <= dst: the filter is not stretched
-    for (int xx = 0; xx < dst; ++xx) {
-        const double center = (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > src) xmax = src;
-        const int n = xmax - xmin;
-        if (n < 1 || n > kImgTaps) {
-            set_error("qatvit_image_resize_coeffs: %d taps at output %d (src %d, dst %d)", n, xx, src, dst);
-            return 1;
-        }
-        double w[kImgTaps], ww = 0.0;
-        for (int i = 0; i < n; ++i) {
-            w[i] = cubic(i + xmin - center + 0.5);
-            ww += w[i];
-        }
-        int64_t pos = 0;
-        for (int i = 0; i < kImgTaps; ++i) {
-            int32_t k = 0;
-            if (i < n) {
-                const double v = ww != 0.0 ? w[i] / ww : w[i];
-                k = v < 0 ? (int32_t)(-0.5 + v * (double)(1 << kImgBits)) : (int32_t)(0.5 + v * (double)(1 << kImgBits));
-            }
-            // the kernel multiplies with v_mad_i32_i24 and accumulates in int32, as Pillow does
-            if (k <= -(1 << 23) || k >= (1 << 23)) {
-                set_error("qatvit_image_resize_coeffs: coefficient %d at output %d does not fit 24 bits", k, xx);
-                return 1;
-            }
-            if (k > 0) pos += k;
-            coef[xx * kImgTaps + i] = k;
-        }
-        if (255 * pos + (1 << (kImgBits - 1)) >= ((int64_t)1 << 31)) {
-            set_error("qatvit_image_resize_coeffs: int32 accumulator overflow at output %d", xx);
-            return 1;
-        }
-        xmin_out[xx] = xmin;
-        ntaps_out[xx] = n;
-    }
-    // the kernel keeps image_max_rows source rows per band of kImgBand output rows
-    for (int y0 = 0; y0 < dst; y0 += kImgBand) {
-        const int y1 = (y0 + kImgBand < dst ? y0 + kImgBand : dst) - 1;
-        if (xmin_out[y1] + ntaps_out[y1] - xmin_out[y0] > image_max_rows(src, dst)) {
-            set_error("qatvit_image_resize_coeffs: output rows %d..%d read more than %d source rows", y0, y1, image_max_rows(src, dst));
-            return 1;
-        }
-    }
-    return 0;
+    return pillow_coeffs<kImgTaps>("qatvit_image_resize_coeffs", false, kImgTaps, kImgBand, image_max_rows, src, dst, xmin_out, ntaps_out, coef);
 }
 
 void image_table(const float* mean, const float* stdv, float* table) {

@@ -473,6 +473,45 @@ class ThreeAugment:
         return color.to(torch.int32), _blur_records(choice == 2, self.radius[0] + u * (self.radius[1] - self.radius[0]))
 
 
+def _cuda_device(who, device):
+    """The device of a transform: a CUDA device with its index resolved."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{who} runs on MI355X only: device must be a CUDA device")
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def _source_batch(who, data_u8, index, h, w, device):
+    """``(N, B, index pointer)`` of the uint8 ``[N, h, w, 3]`` source of a transform named `who` and the batch's ``index`` (or None)."""
+    if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
+        raise RuntimeError(f"{who} runs on MI355X only: move the uint8 images to the GPU")
+    if data_u8.dtype != torch.uint8:
+        raise TypeError(f"images must be uint8, got {data_u8.dtype}")
+    if data_u8.dim() != 4 or tuple(data_u8.shape[1:]) != (h, w, 3):
+        raise ValueError(f"images must be [N, {h}, {w}, 3] (HWC), got {tuple(data_u8.shape)}")
+    if not data_u8.is_contiguous() or data_u8.device != device:
+        raise ValueError(f"images must be contiguous and on {device}")
+    if index is None:
+        return data_u8.shape[0], data_u8.shape[0], None
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != device:
+        raise ValueError(f"index must be a contiguous 1-D int64 tensor on {device}")
+    return data_u8.shape[0], index.shape[0], index.data_ptr()
+
+
+def _out_batch(out, dtype, shape, device):
+    """`out`, or a fresh tensor where it is None."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"out must be a contiguous {'fp32' if dtype == torch.float32 else 'uint8'} {list(shape)} tensor on {device}")
+    return out
+
+
+def _check_records(name, t, shape, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {device}")
+
+
 class GpuResizeNormalize:
     """uint8 ``[N, S, S, 3]`` images on the device -> fp32 ``[B, 3, D, D]``: Resize(D, BICUBIC) + ToTensor() + Normalize(mean, std) in one launch.
     With ``aug`` (int32 ``[B]`` on the device, the words of ``RandomCropFlip.draw``; word b belongs to batch position b) the source of sample b is
@@ -499,11 +538,7 @@ class GpuResizeNormalize:
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
         self.src_size, self.out_size = int(src_size), int(out_size)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("GpuResizeNormalize runs on MI355X only: device must be a CUDA device")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device("GpuResizeNormalize", device)
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self.coeffs = torch.cat([t.flatten() for t in resize_tables(self.src_size, self.out_size)]).to(self.device)
         self.table = value_table(mean, std).to(self.device)
@@ -528,52 +563,17 @@ class GpuResizeNormalize:
         S, D = self.src_size, self.out_size
         if rrc is not None and aug is not None:
             raise ValueError("rrc and aug are mutually exclusive: the rrc record carries its own flip, and padding does not apply to a window")
-        if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
-            raise RuntimeError("GpuResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
-        if data_u8.dtype != torch.uint8:
-            raise TypeError(f"images must be uint8, got {data_u8.dtype}")
-        if data_u8.dim() != 4 or tuple(data_u8.shape[1:]) != (S, S, 3):
-            raise ValueError(f"images must be [N, {S}, {S}, 3] (HWC), got {tuple(data_u8.shape)}")
-        if not data_u8.is_contiguous() or data_u8.device != self.device:
-            raise ValueError(f"images must be contiguous and on {self.device}")
-        N = data_u8.shape[0]
-        if index is None:
-            B, ip = N, None
-        else:
-            if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != self.device:
-                raise ValueError(f"index must be a contiguous 1-D int64 tensor on {self.device}")
-            B, ip = index.shape[0], index.data_ptr()
-        if out is None:
-            out = torch.empty(B, 3, D, D, dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, D, D) or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"out must be a contiguous fp32 [{B}, 3, {D}, {D}] tensor on {self.device}")
+        N, B, ip = _source_batch("GpuResizeNormalize", data_u8, index, S, S, self.device)
+        out = _out_batch(out, torch.float32, (B, 3, D, D), self.device)
         mode, fill = _padding_mode_and_fill(padding_mode, fill)
         if aug is not None:
-            if not isinstance(aug, torch.Tensor) or aug.dtype != torch.int32 or tuple(aug.shape) != (B,) or not aug.is_contiguous() \
-                    or aug.device != self.device:
-                raise ValueError(f"aug must be a contiguous int32 [{B}] tensor on {self.device}")
+            _check_records("aug", aug, (B,), self.device)
             if mode == PADDING_MODES["reflect"] and padding is not None and padding > S - 1:
                 raise ValueError(f"reflect padding reflects once: offsets up to {padding} exceed S - 1 = {S - 1}")
-        if mix is not None:
-            if not isinstance(mix, torch.Tensor) or mix.dtype != torch.int32 or tuple(mix.shape) != (B, MIX_WORDS) or not mix.is_contiguous() \
-                    or mix.device != self.device:
-                raise ValueError(f"mix must be a contiguous int32 [{B}, {MIX_WORDS}] tensor on {self.device}")
-        if erase is not None:
-            if not isinstance(erase, torch.Tensor) or erase.dtype != torch.int32 or tuple(erase.shape) != (B, ERASE_WORDS) \
-                    or not erase.is_contiguous() or erase.device != self.device:
-                raise ValueError(f"erase must be a contiguous int32 [{B}, {ERASE_WORDS}] tensor on {self.device}")
-        if color is not None:
-            if not isinstance(color, torch.Tensor) or color.dtype != torch.int32 or tuple(color.shape) != (B, COLOR_WORDS) \
-                    or not color.is_contiguous() or color.device != self.device:
-                raise ValueError(f"color must be a contiguous int32 [{B}, {COLOR_WORDS}] tensor on {self.device}")
-        if blur is not None:
-            if not isinstance(blur, torch.Tensor) or blur.dtype != torch.int32 or tuple(blur.shape) != (B, BLUR_WORDS) \
-                    or not blur.is_contiguous() or blur.device != self.device:
-                raise ValueError(f"blur must be a contiguous int32 [{B}, {BLUR_WORDS}] tensor on {self.device}")
-        if rrc is not None:
-            if not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
-                    or rrc.device != self.device:
-                raise ValueError(f"rrc must be a contiguous int32 [{B}, {RRC_WORDS}] tensor on {self.device}")
+        for name, t, words in (("mix", mix, MIX_WORDS), ("erase", erase, ERASE_WORDS), ("color", color, COLOR_WORDS), ("blur", blur, BLUR_WORDS),
+                               ("rrc", rrc, RRC_WORDS)):
+            if t is not None:
+                _check_records(name, t, (B, words), self.device)
         if not B:
             return out
         # The narrowest entry that takes the records present, and its arguments between D and out.  An entry takes the records in front of its own as
@@ -656,11 +656,7 @@ class GpuWindowResize:
         if not (1 <= h <= H and 1 <= w <= W and 0 <= top <= H - h and 0 <= left <= W - w):
             raise ValueError(f"window {window!r} does not lie inside the {H} x {W} source")
         self.window = (top, left, h, w)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("GpuWindowResize runs on MI355X only: device must be a CUDA device")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device("GpuWindowResize", device)
         if min(H, W) < 8:
             raise ValueError(f"the source {H} x {W} has a side below 8")
         self.max_side = max(H, W)
@@ -677,30 +673,12 @@ class GpuWindowResize:
 
     def __call__(self, data_u8, index=None, rrc=None, out=None):
         (H, W), D = self.src_size, self.out_size
-        if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
-            raise RuntimeError("GpuWindowResize runs on MI355X only: move the uint8 images to the GPU")
-        if data_u8.dtype != torch.uint8:
-            raise TypeError(f"images must be uint8, got {data_u8.dtype}")
-        if data_u8.dim() != 4 or tuple(data_u8.shape[1:]) != (H, W, 3):
-            raise ValueError(f"images must be [N, {H}, {W}, 3] (HWC), got {tuple(data_u8.shape)}")
-        if not data_u8.is_contiguous() or data_u8.device != self.device:
-            raise ValueError(f"images must be contiguous and on {self.device}")
-        N = data_u8.shape[0]
-        if index is None:
-            B, ip = N, None
-        else:
-            if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != self.device:
-                raise ValueError(f"index must be a contiguous 1-D int64 tensor on {self.device}")
-            B, ip = index.shape[0], index.data_ptr()
-        if out is None:
-            out = torch.empty(B, D, D, 3, dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (B, D, D, 3) or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"out must be a contiguous uint8 [{B}, {D}, {D}, 3] tensor on {self.device}")
+        N, B, ip = _source_batch("GpuWindowResize", data_u8, index, H, W, self.device)
+        out = _out_batch(out, torch.uint8, (B, D, D, 3), self.device)
         if rrc is None:
             rrc = self.default_records(B)
-        elif not isinstance(rrc, torch.Tensor) or rrc.dtype != torch.int32 or tuple(rrc.shape) != (B, RRC_WORDS) or not rrc.is_contiguous() \
-                or rrc.device != self.device:
-            raise ValueError(f"rrc must be a contiguous int32 [{B}, {RRC_WORDS}] tensor on {self.device}")
+        else:
+            _check_records("rrc", rrc, (B, RRC_WORDS), self.device)
         if not B:
             return out
         with torch.cuda.device(self.device):
@@ -811,196 +789,80 @@ class GpuImageLoader:
         self.labels = labels.to(self.device, torch.int64).contiguous()
         self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator = int(batch_size), shuffle, sampler, drop_last, generator
         self.return_index = bool(return_index)
-        if augment is not None:
-            if not isinstance(augment, RandomCropFlip):
-                raise TypeError(f"augment must be a RandomCropFlip, got {type(augment).__name__}")
-            if augment.padding > self.data.shape[1] - 1:
-                raise ValueError(f"augment.padding {augment.padding} exceeds S - 1 = {self.data.shape[1] - 1}")
-        self.augment = augment
-        if mix is not None and not isinstance(mix, MixupCutmix):
-            raise TypeError(f"mix must be a MixupCutmix, got {type(mix).__name__}")
-        self.mix = mix
-        if crop is not None:
-            if not isinstance(crop, RandomResizedCrop):
-                raise TypeError(f"crop must be a RandomResizedCrop, got {type(crop).__name__}")
-            if augment is not None:
+        for name, v, cls in (("augment", augment, RandomCropFlip), ("mix", mix, MixupCutmix), ("crop", crop, RandomResizedCrop),
+                             ("erase", erase, RandomErasing), ("color", color, ColorJitter), ("three_augment", three_augment, ThreeAugment),
+                             ("blur", blur, GaussianBlur)):
+            if v is None:
+                continue
+            if not isinstance(v, cls):
+                raise TypeError(f"{name} must be a {cls.__name__}, got {type(v).__name__}")
+            if name == "augment" and v.padding > self.data.shape[1] - 1:
+                raise ValueError(f"augment.padding {v.padding} exceeds S - 1 = {self.data.shape[1] - 1}")
+            if name == "crop" and augment is not None:
                 raise ValueError("crop and augment are mutually exclusive: the crop's record carries its own flip, and padding does not apply")
-        self.crop = crop
-        if erase is not None and not isinstance(erase, RandomErasing):
-            raise TypeError(f"erase must be a RandomErasing, got {type(erase).__name__}")
-        self.erase = erase
-        if color is not None and not isinstance(color, ColorJitter):
-            raise TypeError(f"color must be a ColorJitter, got {type(color).__name__}")
-        self.color = color
-        if three_augment is not None:
-            if not isinstance(three_augment, ThreeAugment):
-                raise TypeError(f"three_augment must be a ThreeAugment, got {type(three_augment).__name__}")
-            if color is not None or blur is not None:
+            if name == "three_augment" and (color is not None or blur is not None):
                 raise ValueError("three_augment is exclusive with color and blur: it draws both records itself")
-        if blur is not None and not isinstance(blur, GaussianBlur):
-            raise TypeError(f"blur must be a GaussianBlur, got {type(blur).__name__}")
-        self.blur, self.three_augment = blur, three_augment
+        self.augment, self.mix, self.crop, self.erase, self.color, self.blur, self.three_augment = augment, mix, crop, erase, color, blur, three_augment
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
-        plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, self.generator)
+        g = self.generator
+        plan = epoch_batches(self.data.shape[0], self.batch_size, self.shuffle, self.sampler, self.drop_last, g)
         if not plan:
             return
-        if self.erase is not None or self.color is not None or self.blur is not None or self.three_augment is not None:
-            yield from self._iter_erased(plan)
-            return
+        flat = torch.cat(plan)
+        n, a, three = flat.shape[0], self.augment, self.three_augment
+        size = lambda: self.transform.out_size   # noqa: E731   (read only where a record kind needs it: a loader without options takes any callable)
+        # The record kinds in drawing order, which is the order of their sections behind the n indices: (option, the keywords the transform takes
+        # the records under, int32 words per sample of each, the draw: one tensor per keyword).  A seed gives the plan and the records of every
+        # kind it gives without the later kinds
+        kinds = [(a, ("aug",), (1,), lambda: (a.draw(n, g),)),
+                 (self.crop, ("rrc",), (RRC_WORDS,), lambda: (self.crop.draw(n, self.crop_size, g),)),
+                 (self.mix, ("mix",), (MIX_WORDS,), lambda: (self.mix.draw([b.shape[0] for b in plan], size(), g),)),
+                 (self.erase, ("erase",), (ERASE_WORDS,), lambda: (self.erase.draw(n, size(), g),)),
+                 (self.color, ("color",), (COLOR_WORDS,), lambda: (self.color.draw(n, g),)),
+                 (self.blur, ("blur",), (BLUR_WORDS,), lambda: (self.blur.draw(n, g),)),
+                 (three, ("color", "blur"), (COLOR_WORDS, BLUR_WORDS), lambda: three.draw(n, g))]
+        kinds = [k[1:] for k in kinds if k[0] is not None]
+        # one pinned block and one asynchronous copy (the caching host allocator keeps the block until the copy has run): n int64 indices, then
+        # every section's n * words int32 in whole int64 elements
+        bounds = [n]
+        for _, words, _ in kinds:
+            for w in words:
+                bounds.append(bounds[-1] + (n * w + 1) // 2)
+        host = torch.empty(bounds[-1], dtype=torch.int64, pin_memory=True)
+
+        def sections(block):
+            """{keyword: the int32 [n, words] view ([n] for the one-word kind) of its section of `block`}, in drawing order."""
+            keys = [(key, w) for keywords, words, _ in kinds for key, w in zip(keywords, words)]
+            return {key: block[lo:hi].view(torch.int32)[:n * w].view((n, w) if w > 1 else (n,)) for (key, w), lo, hi in zip(keys, bounds, bounds[1:])}
+
+        host[:n].copy_(flat)
+        into = sections(host)
+        for keywords, _, draw in kinds:
+            for key, records in zip(keywords, draw()):
+                into[key].copy_(records)
+        dev = host.to(self.device, non_blocking=True)
+        order, records = dev[:n], sections(dev)
+        # what every call of the epoch gets besides its slices: the augment's padding with its words; behind a crop, absent mix records as None;
+        # and with any of the late kinds (erase, colour, blur) all of them, absent ones as None, and whether contrast needs the statistics launch
+        fixed = {} if a is None else {"padding_mode": a.padding_mode, "fill": a.fill, "padding": a.padding}
         if self.crop is not None:
-            yield from self._iter_cropped(plan)
-            return
-        if self.mix is not None:
-            yield from self._iter_mixed(plan)
-            return
-        if self.augment is not None:
-            yield from self._iter_augmented(plan)
-            return
-        flat = torch.cat(plan)
-        # from pinned memory the copy is asynchronous (the caching host allocator keeps the block until the copy has run)
-        order = torch.empty(flat.shape, dtype=torch.int64, pin_memory=True).copy_(flat).to(self.device, non_blocking=True)
-        o = 0
-        for b in plan:
-            idx = order[o:o + b.shape[0]]
-            o += b.shape[0]
-            if self.return_index:
-                yield self.transform(self.data, idx), self.labels.index_select(0, idx), idx
-            else:
-                yield self.transform(self.data, idx), self.labels.index_select(0, idx)
-
-    def _iter_augmented(self, plan):
-        a, flat = self.augment, torch.cat(plan)
-        n = flat.shape[0]
-        # one pinned block and one asynchronous copy for both: n int64 indices, then the n int32 words in the int64 elements behind them
-        host = torch.empty(n + (n + 1) // 2, dtype=torch.int64, pin_memory=True)
-        host[:n].copy_(flat)
-        host[n:].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
-        dev = host.to(self.device, non_blocking=True)
-        order, words = dev[:n], dev[n:].view(torch.int32)[:n]
-        o = 0
-        for b in plan:
-            idx, w = order[o:o + b.shape[0]], words[o:o + b.shape[0]]
-            o += b.shape[0]
-            x = self.transform(self.data, idx, aug=w, padding_mode=a.padding_mode, fill=a.fill, padding=a.padding)
-            if self.return_index:
-                yield x, self.labels.index_select(0, idx), idx
-            else:
-                yield x, self.labels.index_select(0, idx)
-
-
-    def _iter_mixed(self, plan):
-        a, flat = self.augment, torch.cat(plan)
-        n = flat.shape[0]
-        nw = (n + 1) // 2 if a is not None else 0
-        # one pinned block and one asynchronous copy: n int64 indices, the n int32 words (with augment), then the n six-word int32 records
-        host = torch.empty(n + nw + 3 * n, dtype=torch.int64, pin_memory=True)
-        host[:n].copy_(flat)
-        if a is not None:
-            host[n:n + nw].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
-        host[n + nw:].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], self.transform.out_size, self.generator))
-        dev = host.to(self.device, non_blocking=True)
-        order, records = dev[:n], dev[n + nw:].view(torch.int32).view(n, MIX_WORDS)
-        words = dev[n:n + nw].view(torch.int32)[:n] if a is not None else None
+            fixed["mix"] = None
+        if records.keys() & {"erase", "color", "blur"}:
+            jitter = self.color if self.color is not None else three
+            fixed.update(mix=None, erase=None, color=None, contrast=jitter is not None and jitter.contrast is not None, blur=None)
         o = 0
         for b in plan:
             m = b.shape[0]
-            idx, r = order[o:o + m], records[o:o + m]
-            if a is not None:
-                x = self.transform(self.data, idx, aug=words[o:o + m], padding_mode=a.padding_mode, fill=a.fill, padding=a.padding, mix=r)
-            else:
-                x = self.transform(self.data, idx, mix=r)
+            idx, kw = order[o:o + m], dict(fixed, **{key: r[o:o + m] for key, r in records.items()})
             o += m
-            if self.return_index:
-                yield x, self.labels.index_select(0, idx), idx, r
-            else:
-                yield x, self.labels.index_select(0, idx), r
-
-    def _iter_cropped(self, plan):
-        flat = torch.cat(plan)
-        n = flat.shape[0]
-        nm = 3 * n if self.mix is not None else 0
-        # one pinned block and one asynchronous copy: n int64 indices, the n two-word int32 records, then (with mix) the n six-word int32 records
-        host = torch.empty(2 * n + nm, dtype=torch.int64, pin_memory=True)
-        host[:n].copy_(flat)
-        host[n:2 * n].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.crop_size, self.generator))
-        if self.mix is not None:
-            host[2 * n:].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], self.transform.out_size, self.generator))
-        dev = host.to(self.device, non_blocking=True)
-        order, windows = dev[:n], dev[n:2 * n].view(torch.int32).view(n, RRC_WORDS)
-        records = dev[2 * n:].view(torch.int32).view(n, MIX_WORDS) if self.mix is not None else None
-        o = 0
-        for b in plan:
-            m = b.shape[0]
-            idx, r = order[o:o + m], records[o:o + m] if records is not None else None
-            x = self.transform(self.data, idx, rrc=windows[o:o + m], mix=r)
-            o += m
+            x = self.transform(self.data, idx, **kw)
             tail = (idx,) if self.return_index else ()
-            yield (x, self.labels.index_select(0, idx)) + tail + ((r,) if r is not None else ())
-
-    def _iter_erased(self, plan):
-        a, flat = self.augment, torch.cat(plan)
-        n, D = flat.shape[0], self.transform.out_size
-        # one pinned block and one asynchronous copy: n int64 indices; the n int32 words (augment) or the n two-word records (crop); the n six-word
-        # mix records (mix); the n eight-word erase records (erase); the n four-word colour records (color); then the n four-word blur records (blur).
-        # Drawn in that order; three_augment draws the colour and the blur records together, where they stand
-        nw = (n + 1) // 2 if a is not None else (n if self.crop is not None else 0)
-        nm = 3 * n if self.mix is not None else 0
-        ne = 4 * n if self.erase is not None else 0
-        three = self.three_augment
-        nc = 2 * n if self.color is not None or three is not None else 0
-        nb = 2 * n if self.blur is not None or three is not None else 0
-        host = torch.empty(n + nw + nm + ne + nc + nb, dtype=torch.int64, pin_memory=True)
-        host[:n].copy_(flat)
-        if a is not None:
-            host[n:n + nw].view(torch.int32)[:n].copy_(a.draw(n, self.generator))
-        elif self.crop is not None:
-            host[n:n + nw].view(torch.int32).view(n, RRC_WORDS).copy_(self.crop.draw(n, self.crop_size, self.generator))
-        if self.mix is not None:
-            host[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS).copy_(self.mix.draw([b.shape[0] for b in plan], D, self.generator))
-        if self.erase is not None:
-            host[n + nw + nm:n + nw + nm + ne].view(torch.int32).view(n, ERASE_WORDS).copy_(self.erase.draw(n, D, self.generator))
-        oc = n + nw + nm + ne
-        if self.color is not None:
-            host[oc:oc + nc].view(torch.int32).view(n, COLOR_WORDS).copy_(self.color.draw(n, self.generator))
-        if self.blur is not None:
-            host[oc + nc:].view(torch.int32).view(n, BLUR_WORDS).copy_(self.blur.draw(n, self.generator))
-        if three is not None:
-            c3, b3 = three.draw(n, self.generator)
-            host[oc:oc + nc].view(torch.int32).view(n, COLOR_WORDS).copy_(c3)
-            host[oc + nc:].view(torch.int32).view(n, BLUR_WORDS).copy_(b3)
-        dev = host.to(self.device, non_blocking=True)
-        order = dev[:n]
-        boxes = dev[n + nw + nm:oc].view(torch.int32).view(n, ERASE_WORDS) if self.erase is not None else None
-        colors = dev[oc:oc + nc].view(torch.int32).view(n, COLOR_WORDS) if nc else None
-        blurs = dev[oc + nc:].view(torch.int32).view(n, BLUR_WORDS) if nb else None
-        jitter = self.color if self.color is not None else three
-        wants_sums = jitter is not None and jitter.contrast is not None   # the statistics launch runs only where contrast is enabled
-
-        def late(o, m):
-            return {"erase": None if boxes is None else boxes[o:o + m], "color": None if colors is None else colors[o:o + m], "contrast": wants_sums,
-                    "blur": None if blurs is None else blurs[o:o + m]}
-
-        front = dev[n:n + nw].view(torch.int32)
-        records = dev[n + nw:n + nw + nm].view(torch.int32).view(n, MIX_WORDS) if self.mix is not None else None
-        o = 0
-        for b in plan:
-            m = b.shape[0]
-            idx, r = order[o:o + m], records[o:o + m] if records is not None else None
-            if a is not None:
-                x = self.transform(self.data, idx, aug=front[:n][o:o + m], padding_mode=a.padding_mode, fill=a.fill, padding=a.padding, mix=r,
-                                   **late(o, m))
-            elif self.crop is not None:
-                x = self.transform(self.data, idx, rrc=front.view(n, RRC_WORDS)[o:o + m], mix=r, **late(o, m))
-            else:
-                x = self.transform(self.data, idx, mix=r, **late(o, m))
-            o += m
-            tail = (idx,) if self.return_index else ()
-            yield (x, self.labels.index_select(0, idx)) + tail + ((r,) if r is not None else ())
+            yield (x, self.labels.index_select(0, idx)) + tail + ((kw["mix"],) if self.mix is not None else ())
 
 
 def cifar10_arrays(root, train=True):
