@@ -881,6 +881,27 @@ int qatvit_optim_lamb_apply(const void* param_ptrs, const void* exp_avg_ptrs, co
  *   none within these limits does.
  *   A malformed record is made safe, not trusted, as the rrc entries do it: h is clamped to [1, H] and w to [1, W], then top to [0, H - h]
  *   and left to [0, W - w]; any two words are safe, and the result is the clamped record's.
+ *
+ * qatvit_image_bytes_blur: the second stage behind qatvit_image_window_u8 WITH Gaussian blur, a launch that takes the resized bytes as they are.
+ *   bytes uint8 [B][D][D][3] (HWC, contiguous, 4-byte aligned, on the device) at batch POSITIONS: no index, no N, no table of coefficients.
+ *   out fp32 [B][3][D][D], 16-byte aligned.  mix, erase, color, sums and blur are qatvit_image_batch_blur's arguments with its records, its
+ *   cleaning rules and its order (grayscale, solarize, BLUR, the jitter ops with the contrast sum taken behind the blur, Normalize, the erase,
+ *   the mix; the partner of a mix record is coloured, blurred and erased by its own records): mix, erase, color and sums may be NULL
+ *   (color == NULL: all-zero colour records; sums == NULL: the caller's promise that no record holds a contrast op); blur is REQUIRED -
+ *   without blur records the second stage is qatvit_image_batch_color at S = D.  With color and sums a statistics launch runs in front, and
+ *   on return sums[b] is what qatvit_image_batch_blur leaves there.
+ *   out[b] is BITWISE what
+ *     qatvit_image_batch_blur(bytes, NULL, B, B, D, D, qatvit_image_resize_coeffs(D, D), table, NULL, 0, 0, mix, erase, color, sums, blur, ..)
+ *   defines: the resize D -> D is the identity, so the image that entry blurs is `bytes`.  That definition holds at the sizes at which that
+ *   entry is refused for its LDS request as well (D = 224 among them: 89,536 bytes there): this entry is how those sizes are served.  A
+ *   sample whose cleaned record is "no blur" gets bitwise qatvit_image_batch_color's result on the same bytes; nothing is addressed through a
+ *   record.
+ *   LDS: the value table (3072 bytes) and (sides + 1) image buffers of (band + 12) * 3 * D bytes, sides = 2 with mix records, else 1; the
+ *   band is 16 rows without mix records where that stays within 64 KB (D <= 368), else 8 rows (D = 372 .. 384), and 8 rows with them.
+ *   D = 224: 40,704 bytes, 43,392 with mix records; D = 384: 49,152 bytes.  With mix records D <= 344 is served (64,992 bytes); above, the
+ *   request exceeds 64 KB and the call is refused with an error string that states the byte count, before any HIP call.
+ *   D % 4 == 0, 8 <= D <= 384, 1 <= B <= 65535, bytes / table / blur / out not NULL: anything else is refused with an error string before
+ *   any HIP call.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -915,6 +936,8 @@ int64_t qatvit_image_window_coeffs_bytes(int32_t max_side, int32_t D);
 int qatvit_image_window_coeffs(int32_t max_side, int32_t D, int32_t* out_host);
 int qatvit_image_window_u8(const uint8_t* data, const int64_t* index, int32_t B, int32_t N, int32_t H, int32_t W, int32_t D,
                            const int32_t* tables, int32_t max_side, const int32_t* rrc, uint8_t* out, void* stream);
+int qatvit_image_bytes_blur(const uint8_t* bytes, int32_t B, int32_t D, const float* table, const int32_t* mix, const int32_t* erase,
+                            const int32_t* color, uint32_t* sums, const int32_t* blur, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

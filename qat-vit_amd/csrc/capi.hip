@@ -670,6 +670,22 @@ int qatvit_image_window_u8(const uint8_t* data, const int64_t* index, int32_t B,
     return 0;
 }
 
+// The bytes-in blur form (image_bytes_blur.hip): every check before any HIP call; the launcher refuses the LDS request under the same name
+int qatvit_image_bytes_blur(const uint8_t* bytes, int32_t B, int32_t D, const float* table, const int32_t* mix, const int32_t* erase,
+                            const int32_t* color, uint32_t* sums, const int32_t* blur, float* out, void* stream) {
+    const char* who = "qatvit_image_bytes_blur";
+    QV_CHECK_ARG(bytes && table && blur && out, "%s: null pointer argument (without blur records the call is qatvit_image_batch_color at S = D)", who);
+    QV_CHECK_ARG(D % 4 == 0 && D >= 8 && D <= kImgMaxD, "%s: output size %d must be a multiple of 4 in 8 .. %d", who, D, kImgMaxD);
+    QV_CHECK_ARG(B >= 1 && B <= 65535, "%s: batch %d must be 1 .. 65535", who, B);
+    const uintptr_t words = (uintptr_t)bytes | (uintptr_t)table | (uintptr_t)mix | (uintptr_t)erase | (uintptr_t)color | (uintptr_t)sums | (uintptr_t)blur;
+    QV_CHECK_ARG(((uintptr_t)out & 15) == 0 && (words & 3) == 0, "%s: misaligned pointer", who);
+    ImageBytesBlur r;
+    r.bytes = bytes, r.B = B, r.D = D, r.table = table, r.mix = mix, r.erase = erase, r.color = color, r.sums = sums, r.blur = blur, r.out = out;
+    if (int rc = launch_image_bytes_blur(r, (hipStream_t)stream)) return rc;
+    QV_CHECK_LAUNCH(who);
+    return 0;
+}
+
 int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {
     RowMoveTab t;
     t.n = 1; t.m[0] = RowMove{tall, compact, stride, width};

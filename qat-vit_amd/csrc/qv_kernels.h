@@ -424,6 +424,23 @@ struct ImageWindow {
 };
 // nonzero + set_error: 1 before any HIP call where the LDS request exceeds kImgMixMaxLds
 int launch_image_window(const ImageWindow& r, hipStream_t st);
+// image_bytes_blur.hip: the blur forms' chain on bytes that are the resized image already (the window stage's output, at batch positions): out fp32
+// [B, 3, D, D] from bytes uint8 [B, D, D, 3].  The records are ImageBatch's; blur is required.  LDS: the value table and (sides + 1) image buffers
+struct ImageBytesBlur {
+    const uint8_t* bytes = nullptr;
+    int B = 0, D = 0;
+    const float* table = nullptr;
+    const int32_t* mix = nullptr;
+    const int32_t* erase = nullptr;
+    const int32_t* color = nullptr;
+    uint32_t* sums = nullptr;
+    const int32_t* blur = nullptr;
+    float* out = nullptr;
+};
+int image_bytes_blur_band(int D, bool mixed);          // 16 rows without mix records where two buffers of 28 rows fit, else 8
+int64_t image_bytes_blur_lds_bytes(int D, bool mixed);
+// nonzero + set_error: 1 before any HIP call where the LDS request exceeds kImgMixMaxLds (mix records above D = 344), 2 where zeroing sums fails
+int launch_image_bytes_blur(const ImageBytesBlur& r, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

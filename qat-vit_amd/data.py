@@ -1,6 +1,7 @@
 """Input pipeline on MI355X (libqatvit.so: qatvit_image_resize_coeffs / qatvit_image_table / qatvit_image_batch / qatvit_image_batch_aug /
 qatvit_image_batch_mix / qatvit_image_resize_coeffs_windows / qatvit_image_batch_rrc / qatvit_image_batch_erase / qatvit_image_batch_rrc_erase /
-qatvit_image_batch_color / qatvit_image_batch_rrc_color / qatvit_image_batch_blur / qatvit_image_batch_rrc_blur).
+qatvit_image_batch_color / qatvit_image_batch_rrc_color / qatvit_image_batch_blur / qatvit_image_batch_rrc_blur / qatvit_image_window_u8 /
+qatvit_image_bytes_blur).
 
 Stands where the reference's loaders have, per image on DataLoader workers, ``Resize(224, BICUBIC)`` through Pillow, ``ToTensor()`` and
 ``Normalize(mean, std)``, followed by the copy of the fp32 batch to the device: the uint8 data set lives on the device, and one launch per batch
@@ -16,6 +17,8 @@ ops, inside the same launch; ``ThreeAugment`` draws DeiT-III's one-of-three choi
 ``GpuWindowResize`` / ``GpuWideResizeNormalize`` serve sources that are rectangles or larger than the output: a window stage of its own
 (``qatvit_image_window_u8``, Pillow's stretched filter, up to 17 taps) writes the resized uint8 windows, and the batch launch at S = D applies the
 rest to them (section 7x).
+``GpuBytesBlurNormalize`` / ``GpuWideResizeNormalize(..., blur=True)`` serve ``GaussianBlur`` and ``ThreeAugment`` on such sources: the second stage
+of a call with blur records is a launch that takes the staged bytes as the image to blur (``qatvit_image_bytes_blur``, section 7z).
 There is no CPU path: CPU tensors raise."""
 import math
 import os
@@ -687,6 +690,48 @@ class GpuWindowResize:
         return out
 
 
+class GpuBytesBlurNormalize:
+    """uint8 ``[B, D, D, 3]`` bytes on the device, at batch positions (what ``GpuWindowResize`` writes) -> fp32 ``[B, 3, D, D]``: the chain of
+    ``GpuResizeNormalize``'s ``blur`` form behind its resize, in one launch that takes the bytes as the resized image
+    (``qatvit_image_bytes_blur``).  ``blur`` (int32 ``[B, 4]``) is required; ``mix``, ``erase``, ``color`` and
+    ``contrast`` have ``GpuResizeNormalize``'s meaning.  The result is bitwise what ``GpuResizeNormalize(D, D)(bytes, blur=...)`` defines,
+    also at the sizes which that form refuses for its LDS request (D = 224); a record of "no blur" gives bitwise the colour form's result.
+    LDS holds the value table and the image buffers only: 40,704 bytes at D = 224, 43,392 with ``mix``.  With ``mix`` an output above 344 is
+    refused by the library."""
+
+    def __init__(self, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
+        self.out_size = int(out_size)
+        self.device = _cuda_device("GpuBytesBlurNormalize", device)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        self.table = value_table(mean, std).to(self.device)
+        self._sums = {}
+
+    def color_sums(self, B):
+        """The uint32 ``[B]`` workspace (as int32) of the calls with ``color`` records of a batch of B, one per batch size, made on first use:
+        behind such a call element b holds the luma sum that the contrast op of record b used (0: no contrast op)."""
+        if B not in self._sums:
+            self._sums[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
+        return self._sums[B]
+
+    def __call__(self, bytes_u8, out=None, mix=None, erase=None, color=None, contrast=True, blur=None):
+        D = self.out_size
+        _, B, _ = _source_batch("GpuBytesBlurNormalize", bytes_u8, None, D, D, self.device)
+        out = _out_batch(out, torch.float32, (B, 3, D, D), self.device)
+        if blur is None:
+            raise ValueError("blur records are required: without them the second stage is GpuResizeNormalize(D, D)")
+        for name, t, words in (("mix", mix, MIX_WORDS), ("erase", erase, ERASE_WORDS), ("color", color, COLOR_WORDS), ("blur", blur, BLUR_WORDS)):
+            if t is not None:
+                _check_records(name, t, (B, words), self.device)
+        if not B:
+            return out
+        opt = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        sums = self.color_sums(B).data_ptr() if color is not None and contrast else None
+        with torch.cuda.device(self.device):
+            native.check(native.lib().qatvit_image_bytes_blur(bytes_u8.data_ptr(), B, D, self.table.data_ptr(), opt(mix), opt(erase), opt(color), sums,
+                                                              blur.data_ptr(), out.data_ptr(), native.stream_ptr()), "qatvit_image_bytes_blur")
+        return out
+
+
 class GpuWideResizeNormalize:
     """Stands where a ``GpuResizeNormalize`` stands, for uint8 ``[N, H, W, 3]`` sources that are rectangles or larger than the output (up to
     ``4 * D`` on a side): two launches per batch.  Stage 1 (``GpuWindowResize``) writes the uint8 ``[B, D, D, 3]`` bytes of every sample's
@@ -694,15 +739,23 @@ class GpuWideResizeNormalize:
     graph replays); stage 2 is a ``GpuResizeNormalize(D, D)`` on those bytes at batch positions, whose resize is the identity and which
     applies ``color``, ``erase``, ``mix`` and ``Normalize`` as it does for a small source.  ``__call__`` has ``GpuResizeNormalize``'s
     keywords; ``rrc`` records are ``RandomResizedCrop.draw(n, (H, W))``'s, ``rrc=None`` is the default ``window`` (the whole image, or e.g.
-    ``center_crop_window(H, W)``).  ``aug`` is refused: padding applies to CIFAR-style sources.  ``blur`` is refused: the blur forms keep
-    source rows and planes in LDS, and at S = D = 224 that is 89,536 bytes (98,272 with mix records), above the 65,536-byte cap."""
+    ``center_crop_window(H, W)``).  ``aug`` is refused: padding applies to CIFAR-style sources.
+    ``blur`` records are served where the object was made with ``blur=True``: stage 2 of a call with ``blur=records`` is then a
+    ``GpuBytesBlurNormalize`` on the staged bytes (still two launches, plus the statistics launch that colour records with contrast bring),
+    which is what ``GpuImageLoader(..., blur=GaussianBlur(...))`` and ``three_augment=ThreeAugment(...)`` need; ``mix`` with ``blur`` is
+    refused by the library above D = 344.  Without the switch ``blur`` is refused as before: the one-launch blur forms keep source rows and
+    planes in LDS, and at S = D = 224 that is 89,536 bytes (98,272 with mix records), above the 65,536-byte cap."""
 
-    def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda", window=None):
+    def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda", window=None, blur=False):
         self.stage = GpuWindowResize(src_size, out_size, device, window)
         self.src_size, self.out_size, self.device, self.window = self.stage.src_size, self.stage.out_size, self.stage.device, self.stage.window
         self.inner = GpuResizeNormalize(self.out_size, self.out_size, mean, std, self.device)
         self.mean, self.std = self.inner.mean, self.inner.std
         self._staged = {}
+        self.blur = bool(blur)
+        self.inner_blur = GpuBytesBlurNormalize(self.out_size, mean, std, self.device) if self.blur else None
+        if self.blur:
+            self.inner._sums = self.inner_blur._sums                  # one workspace per batch size, whichever second stage a call takes
 
     def staged(self, B):
         """The uint8 ``[B, D, D, 3]`` staging buffer of a batch of B, made on first use: behind a call it holds stage 1's bytes.  One buffer
@@ -714,11 +767,12 @@ class GpuWideResizeNormalize:
     def color_sums(self, B):
         return self.inner.color_sums(B)
 
-    @staticmethod
-    def refuse(aug=None, blur=None):
+    def refuse(self, aug=None, blur=None):
+        """Raises for what this object does not serve: ``aug`` always, ``blur`` unless it was made with ``blur=True`` (an object that never ran
+        the constructor has the switch off)."""
         if aug is not None:
             raise ValueError("aug does not apply to a wide source: RandomCrop's padding is for CIFAR-style sources; use rrc records")
-        if blur is not None:
+        if blur is not None and not getattr(self, "blur", False):
             raise NotImplementedError(f"blur is not served on a wide source: the blur forms stage source rows plus planes in LDS, and at S = D = 224 "
                                       f"they ask for 89,536 bytes, above the cap of {BLUR_LDS_CAP} bytes")
 
@@ -729,6 +783,8 @@ class GpuWideResizeNormalize:
             raise RuntimeError("GpuWideResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
         B = data_u8.shape[0] if index is None else index.shape[0]
         staged = self.stage(data_u8, index, rrc, out=self.staged(B))
+        if blur is not None:
+            return self.inner_blur(staged, out=out, mix=mix, erase=erase, color=color, contrast=contrast, blur=blur)
         return self.inner(staged, None, out=out, mix=mix, erase=erase, color=color, contrast=contrast)
 
 

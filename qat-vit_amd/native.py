@@ -125,6 +125,7 @@ SIGNATURES = {
     "qatvit_image_window_coeffs_bytes": (c_int64, [c_int32, c_int32]),
     "qatvit_image_window_coeffs": (c_int, [c_int32, c_int32, c_void_p]),
     "qatvit_image_window_u8": (c_int, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "qatvit_image_bytes_blur": (c_int, [c_void_p, c_int32, c_int32] + [c_void_p] * 8),
     "qatvit_eval_accumulate": (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "qatvit_profile_start": (c_int, [c_void_p, c_int32, c_int32]),
     "qatvit_profile_stop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
