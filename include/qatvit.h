@@ -215,6 +215,20 @@ int qatvit_i8_strip_ln(const float* x, const float* mean, const float* rstd, con
 int qatvit_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, float* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb,
                          int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias, uint32_t* stats, void* stream);
 
+/* The residual epilogue of the inference forward (attn.proj, mlp.fc2 of qatvit_infer_forward / qatvit_infer_forward_ls) on one GEMM of its own: with
+ *   v[m,n] = the value qatvit_gemm_nt_f16 (form 1) / qatvit_gemm_nt_codes (form 3) stores for the same operands, bit for bit, and
+ *   fq(v)  = (clamp(rint(v * out_qp[1]) + out_qp[2], qmin, qmax) - out_qp[2]) * out_qp[0],  out_qp = {scale, 1/scale, zero_point, enabled} (device),
+ *   ls_gamma == NULL:  C[m,n] = resid[m,n] + fq(v[m,n])
+ *   ls_gamma fp32 [N]: C[m,n] = resid[m,n] + fl(fq(v[m,n]) * ls_gamma[n])        (LayerScale)
+ * where fl() rounds the product to fp32 before the sum is formed and rounded: two roundings, never a fused multiply-add - what the training forward's
+ * residual kernel computes - so a gamma of exactly 1 gives the bits of the NULL form.  resid and C are fp32 [M,ldc] (one leading dimension), rows >= M are not
+ * touched.
+ *  form 1: A = the hi plane and A_lo_or_lut = the lo plane of an fp16 pair (lda in elements);  form 3: A = uint8 codes (lda in bytes), A_lo_or_lut = their
+ *  256-entry table of fp16 (hi | lo << 16) pairs.  Every other form is refused.  N % 384 == 0, K % 64 == 0, ldc % 4 == 0 (form 3: lda % 16 == 0). */
+int qatvit_gemm_nt_resid_fq(int32_t form, const void* A, const void* A_lo_or_lut, const void* B16, const float* resid, float* C, int32_t M, int32_t N,
+                            int32_t K, int32_t lda, int32_t ldb, int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias,
+                            const float* out_qp, int32_t qmin, int32_t qmax, const float* ls_gamma, void* stream);
+
 /* The same product for two operands that both sit on a quantisation grid (qkv / fc1 / patch-embed forward), on int8 MFMA:
  *   A8 int8 [M,lda] = q - center (center = (qmin+qmax+1)/2 of the activation range), B8 int8 [N,ldb] = weight integers,
  *   wsum int32 [N] = row sums of B8, a_qp = {scale, 1/scale, zero_point, enabled} of A's quantizer (device):
@@ -584,6 +598,14 @@ int qatvit_infer_prepare(const qatvit_cfg* cfg, const void* const* w8, const flo
                          void* stream);
 int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void* const* w8, const float* const* w_scale, const float* images,
                          float* logits, void* workspace, void* stream);
+/* The same forward for a student with LayerScale (init_values): ls_gamma = 2 * depth device pointers, entry 2 i = block i's ls1 (attention branch), entry
+ * 2 i + 1 = its ls2 (MLP branch), fp32 [embed_dim] each.  attn.proj and mlp.fc2 of every block then update the residual stream as
+ *   x[m,n] = x[m,n] + fl(fq(v[m,n]) * gamma[n])      (the ls_gamma form of qatvit_gemm_nt_resid_fq: product and sum rounded separately)
+ * and nothing else changes: the same workspace, qatvit_infer_prepare and qatvit_infer_workspace_bytes.  ls_gamma == NULL is qatvit_infer_forward (one body
+ * serves both); a non-null array with a null entry is refused before any HIP call.  Logits are bit-identical to qatvit_student_forward of the LayerScale
+ * model with the observers switched off. */
+int qatvit_infer_forward_ls(const qatvit_cfg* cfg, void* const* params, const void* const* w8, const float* const* w_scale, const float* const* ls_gamma,
+                            const float* images, float* logits, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Gradient clipping + AdamW: the two statements that follow the hot path in the reference's loop.

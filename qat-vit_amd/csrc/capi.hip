@@ -329,6 +329,22 @@ int qatvit_gemm_nt_codes(const void* A8, const uint32_t* lut, const void* B16, f
     return 0;
 }
 
+// the residual epilogue of one GEMM on its own: the request as it comes, checked by launch_gemm_nt alone (a form that has no residual epilogue, a shape, a null
+// resid / C / out_qp / operand: its refusals, its texts)
+int qatvit_gemm_nt_resid_fq(int32_t form, const void* A, const void* A_lo_or_lut, const void* B16, const float* resid, float* C, int32_t M, int32_t N, int32_t K,
+                            int32_t lda, int32_t ldb, int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias,
+                            const float* out_qp, int32_t qmin, int32_t qmax, const float* ls_gamma, void* stream) {
+    uint32_t* const stats = nullptr;   // (the residual epilogue feeds no observer)
+    QV_NT_REQUEST(g, A, lda, ldc);
+    if (form == kNTCodes) g.lut = reinterpret_cast<const uint32_t*>(A_lo_or_lut); else g.A_lo = A_lo_or_lut;
+    g.B = B16; g.ldb = ldb; g.C = C; g.s1 = s1;
+    NTPost post{};
+    post.mode = ls_gamma ? kEpiResidFqLs : kEpiResidFq; post.qp = out_qp; post.qmin = qmin; post.qmax = qmax; post.resid = resid; post.ls_gamma = ls_gamma;
+    if (launch_gemm_nt((NTForm)form, g, &post, (hipStream_t)stream)) return 1;
+    QV_CHECK_LAUNCH("qatvit_gemm_nt_resid_fq");
+    return 0;
+}
+
 int qatvit_gemm_nt_i8(const void* A8, const void* B8, const int32_t* wsum, const float* a_qp, int32_t center, float* C, int32_t M, int32_t N,
                       int32_t K, int32_t lda, int32_t ldb, int32_t ldc, const float* s1, const float* s2, const float* col_scale, const float* bias,
                       uint32_t* stats, void* stream) {

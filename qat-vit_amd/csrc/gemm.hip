@@ -57,7 +57,7 @@ struct NTArgs {
     uint16_t* post_code;     // NTPost::code
     const float* post_qp;
     int post_qmin, post_qmax;
-    const float* post_colscale;
+    const float* post_colscale;   // NTPost::colscale; kEpiResidFqLs, which has no colscale: NTPost::ls_gamma (so the record keeps its size and every kernel its argument layout)
     __bf16* out_hi;
     __bf16* out_lo;
     _Float16* out16_hi;
@@ -118,6 +118,17 @@ __device__ unsigned long long g_wg_rt[2048 * 2];   // per workgroup: s_memrealti
 #define QV_NT_STAMP(PM_, k_)
 #define QV_WG_RT(PM_, k_)
 #endif
+// The branch output of the residual epilogue: as it is, or (LS, kEpiResidFqLs) times element E of its column group's four LayerScale gammas, the product rounded
+// on its own.  The four calls of a group name the same address and the compiler loads it once (global_load_dwordx4).  In this shape - no new local in the caller,
+// an ordinary inline function - the kEpiResidFq kernels compile to the machine code they had; a float4 of gammas declared beside `rs` in the epilogue changes their
+// register allocation although nothing reads it there (tools/isa_digest.py, profiles/infer_layer_scale_isa_identity.txt)
+template <bool LS, int E>
+__device__ inline float ls_branch(float y, const float* gamma4) {
+    if constexpr (LS) {
+        const float4 g = *reinterpret_cast<const float4*>(gamma4);
+        return __fmul_rn(y, E == 0 ? g.x : E == 1 ? g.y : E == 2 ? g.z : g.w);
+    } else return y;
+}
 template <int WM, int WN, int TM, int TNT, int SLAB = 64, int PM = 0, int RING = 0, bool I8 = false>   // SLAB: rows staged through LDS at a time; RING: LDS bytes
 __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4, f32x4> (&acc)[TM][TNT], char* smem, int m0, int n0, int tid, int lane, int wave, int wm, int wn,
                                    int r, int g) {
@@ -288,7 +299,7 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                     const int rl = rt - SLAB * h + 4 * g + e;
                     const float v = accv(i, j, e) * ca[j] + cb[j];
                     sC[rl * LDC + cl] = v;
-                    if constexpr (PM != kEpiResidFq && PM != kEpiQkvCodes && PMB != kEpiLnBwd) {   // (the inference epilogues and the fused LayerNorm backward feed no observer)
+                    if constexpr (PM != kEpiResidFq && PM != kEpiResidFqLs && PM != kEpiQkvCodes && PMB != kEpiLnBwd) {   // (the inference epilogues and the fused LayerNorm backward feed no observer)
                         if (m0 + SLAB * h + rl < p.M) { mn = fminf(mn, v); mx = fmaxf(mx, v); }
                     }
                 }
@@ -596,17 +607,22 @@ __device__ inline void nt_epilogue(const NTArgs& p, std::conditional_t<I8, i32x4
                     }
                     *reinterpret_cast<bf16x4*>(p.out_hi + off) = oh;
                     *reinterpret_cast<bf16x4*>(p.out_lo + off) = ol;
-                } else if constexpr (PM == kEpiResidFq) {
+                } else if constexpr (PM == kEpiResidFq || PM == kEpiResidFqLs) {
+                    // LS (LayerScale): the branch output times its column's gamma before the add.  Product and sum are rounded one after the other, as the
+                    // training forward rounds them (elt_rows.inc, k_resid_fq_lnstats_ls) - never one fused multiply-add - so gamma == 1 gives the bits of mode 6.
+                    // The gammas are read here, beside the residual: a thread's column group moves by 32 float4 with every step of this loop (NW * 64 = 512
+                    // threads over C4 = 96 groups per row), so there is no one group per thread to load in front of it
+                    constexpr bool LS = PM == kEpiResidFqLs;
                     const float qs = p.post_qp[0], qinv = p.post_qp[1], qzp = p.post_qp[2], fmin_ = (float)p.post_qmin, fmax_ = (float)p.post_qmax;
                     int64_t orow = row, rrow = row;
                     if (p.embed_np > 0) { orow = row + row / p.embed_np + 1; rrow = 1 + row % p.embed_np; }
                     const float4 rs = *reinterpret_cast<const float4*>(p.resid + rrow * p.ldc + n0 + 4 * c4);
                     bool in;
-                    float4 o;
-                    o.x = rs.x + fq_one(v.x, qinv, qs, qzp, fmin_, fmax_, in);
-                    o.y = rs.y + fq_one(v.y, qinv, qs, qzp, fmin_, fmax_, in);
-                    o.z = rs.z + fq_one(v.z, qinv, qs, qzp, fmin_, fmax_, in);
-                    o.w = rs.w + fq_one(v.w, qinv, qs, qzp, fmin_, fmax_, in);
+                    float4 o;   // (p.post_colscale: NTPost::ls_gamma under LS - nt_set_post)
+                    o.x = rs.x + ls_branch<LS, 0>(fq_one(v.x, qinv, qs, qzp, fmin_, fmax_, in), p.post_colscale + n0 + 4 * c4);
+                    o.y = rs.y + ls_branch<LS, 1>(fq_one(v.y, qinv, qs, qzp, fmin_, fmax_, in), p.post_colscale + n0 + 4 * c4);
+                    o.z = rs.z + ls_branch<LS, 2>(fq_one(v.z, qinv, qs, qzp, fmin_, fmax_, in), p.post_colscale + n0 + 4 * c4);
+                    o.w = rs.w + ls_branch<LS, 3>(fq_one(v.w, qinv, qs, qzp, fmin_, fmax_, in), p.post_colscale + n0 + 4 * c4);
                     *reinterpret_cast<float4*>(p.C + orow * p.ldc + n0 + 4 * c4) = o;
                 } else if constexpr (PM == kEpiQkvCodes) {
                     const float qinv = p.post_qp[1], qzp = p.post_qp[2], fmin_ = (float)p.post_qmin, fmax_ = (float)p.post_qmax;
@@ -1016,6 +1032,10 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_ac(const NTArgs p) {
 }
 
 
+// the two kernels of kEpiResidFqLs (the fp16-pair tall tile; codes = the kNTCodes kernel), launched from the END of this file (see there)
+constexpr int kNtCodesLds = 3 * (2 * 208 + 384) * 64 + 1024;   // k_gemm_nt_ac: 151 KiB
+static int nt_launch_resid_ls(const NTArgs& a, bool codes, int grid, size_t lds, hipStream_t st);
+
 // one kernel instantiation per epilogue variant (NTArgs::pm); a (operand form, pm, tile) combination that has none is an error, never a silent no-op
 template <int TA, int NS, int WM, int TM, int TB, int WN, int TNT, int BK, bool I8 = false, bool F16 = false>
 static int nt_launch(const NTArgs& a, int grid, size_t lds, hipStream_t st) {
@@ -1034,6 +1054,7 @@ static int nt_launch(const NTArgs& a, int grid, size_t lds, hipStream_t st) {
             case kPmLnBwdO16: if constexpr (TA == 1 && tall1) QV_PM(kPmLnBwdO16); break;       // the one-plane backward (kNTPlaneF16)
             case kPmGeluBwdO16: if constexpr (TA == 1 && tall1) QV_PM(kPmGeluBwdO16); break;
             case kEpiPlain: QV_PM(kEpiPlain);
+            case kEpiResidFqLs: if constexpr (TA == 2 && tall1 && NS == 3 && BK == 32) return nt_launch_resid_ls(a, false, grid, lds, st); break;   // inference under LayerScale: proj, and fc2 from planes (an fp16 pair)
         }
     } else if constexpr (I8) {   // the grid x grid forward GEMMs
         switch (a.pm) {
@@ -1076,9 +1097,12 @@ static void nt_set_post(NTArgs& a, const NTPost& p, bool o16 = false) {
     a.lnb_x = p.lnb_x; a.lnb_mean = p.lnb_mean; a.lnb_rstd = p.lnb_rstd; a.lnb_gamma = p.lnb_gamma; a.lnb_beta = p.lnb_beta;
     a.lnb_dx_in = p.lnb_dx_in; a.lnb_dgamma = p.lnb_dgamma; a.lnb_dbeta = p.lnb_dbeta; a.lnb_nmask = reinterpret_cast<const unsigned long long*>(p.lnb_nmask);
     a.o16_mul = p.o16_mul; a.o16_amax = p.o16_amax;
+    if (p.mode == kEpiResidFqLs) a.post_colscale = p.ls_gamma;   // (the gammas travel in colscale's slot: NTArgs)
 }
 // the mode a launcher switches on: kEpiPlain without a record; a record that names kEpiPlain is an unknown mode (-1) like any other number
 static int nt_mode(const NTPost* post) { return !post ? kEpiPlain : post->mode == kEpiPlain ? -1 : post->mode; }
+// a record of the residual epilogue: mode 6, or its LayerScale form with the gammas it reads
+static bool nt_resid_post(const NTPost* post) { return post && (post->mode == kEpiResidFq || (post->mode == kEpiResidFqLs && post->ls_gamma)); }
 
 // what an NTForm requires of a request (the table at enum NTForm, qv_kernels.h), and how its refusal reads (its numbers: M N K lda ldb ldc; kNTI8's text stops at ldb)
 struct NTRule { const char* refusal; int n_mod, k_mod, lda_mod, ldb_mod; bool ab, c_lut, i8; };
@@ -1096,8 +1120,8 @@ static const NTRule kNTRules[kNTForms] = {
 static bool nt_request_ok(NTForm form, const NTGemm& g, const NTPost* post) {
     const NTRule& r = kNTRules[form];
     const bool f16_gelu = form == kNTF16 && post && post->mode == kEpiGeluFwd && post->out_f16;   // the teacher's fc1: fp16 gelu pair out
-    if (form == kNTF16 && (g.B_lo || (post && post->mode != kEpiResidFq && !f16_gelu) || (!g.A_lo && post && !f16_gelu) || g.N % 384 != 0 || g.K % 32 != 0)) {
-        set_error("gemm_nt: the fp16 form takes N %% 384 == 0 and the plain, the residual (mode 6) or the fp16 GELU epilogue (N=%d K=%d)", g.N, g.K);
+    if (form == kNTF16 && (g.B_lo || (post && !nt_resid_post(post) && !f16_gelu) || (!g.A_lo && post && !f16_gelu) || g.N % 384 != 0 || g.K % 32 != 0)) {
+        set_error("gemm_nt: the fp16 form takes N %% 384 == 0 and the plain, the residual (mode 6; mode 11 with ls_gamma) or the fp16 GELU epilogue (N=%d K=%d)", g.N, g.K);
         return false;
     }
     if (form == kNTPlaneBf16 && post) { set_error("gemm_nt_dy16: the bf16 form has the plain epilogue only"); return false; }
@@ -1149,6 +1173,9 @@ static int nt_pairs(const NTArgs& a, const NTPost* post, bool f16, hipStream_t s
                 set_error("gemm_nt: epilogue mode 9 needs a split A operand, N %% 384 == 0, ldc %% 128 == 0, the uint8 codes and the mask bits");
                 return 1;
             }
+            break;
+        case kEpiResidFqLs:
+            if (!(f16 && a.post_qp && a.resid && C && post->ls_gamma)) { set_error("gemm_nt: incomplete arguments for epilogue mode %d", mode); return 1; }
             break;
         default: set_error("gemm_nt: epilogue mode %d not available", post->mode); return 1;
     }
@@ -1214,7 +1241,7 @@ static int nt_planes(const NTArgs& a, const NTPost* post, bool bf16, hipStream_t
 
 // kNTCodes, fc2 forward from codes: A [M, lda] uint8 grid indices, lut[256] packed fp16 (hi | lo << 16) pairs, B [N, ldb] the weight integers as fp16
 static int nt_codes(const NTArgs& a, const NTPost* post, hipStream_t st) {
-    constexpr int kLds = 3 * (2 * 208 + 384) * 64 + 1024;   // 151 KiB
+    constexpr int kLds = kNtCodesLds;   // 151 KiB
     switch (nt_mode(post)) {
         case kEpiResidFq: {   // inference: the residual update C[orow] = resid + fq(acc) in the epilogue, frozen qparams
             if (!post->qp || !post->resid) break;
@@ -1229,8 +1256,12 @@ static int nt_codes(const NTArgs& a, const NTPost* post, hipStream_t st) {
             k_gemm_nt_ac<3, kEpiPlain, kLds><<<cdiv(a.M, 208) * (a.N / 384), 512, kLds, st>>>(a);
             return 0;
         }
+        case kEpiResidFqLs: {   // ... under LayerScale: C[orow] = resid + fq(acc) * ls_gamma[column]
+            if (!post->qp || !post->resid || !post->ls_gamma) break;
+            return nt_launch_resid_ls(a, true, cdiv(a.M, 208) * (a.N / 384), (size_t)kLds, st);
+        }
     }
-    set_error("gemm_nt_codes: only the residual epilogue (mode 6: qp, resid) is available");
+    set_error("gemm_nt_codes: only the residual epilogue (mode 6: qp, resid; mode 11: and ls_gamma) is available");
     return 1;
 }
 
@@ -1256,6 +1287,7 @@ static int nt_i8(const NTArgs& a, const NTGemm& g, const NTPost* post, hipStream
             ok = a.post_qp && a.out8 && a.code_T >= 1 && a.code_hd >= 8 && !(a.out8_mask && a.code_hd % 32 != 0) && (a.code_hd & (a.code_hd - 1)) == 0 && M < (1 << 22) &&
                  N / 3 < 1024 && a.code_T < 1024 && (N / 3) % a.code_hd == 0 && a.post_qmax - a.post_qmin < 256;
             break;
+        case kEpiResidFqLs: set_error("gemm_nt_i8: the int8 form (the patch embedding) has no LayerScale, so no epilogue mode %d", mode); return 1;
         default: set_error("gemm_nt_i8: epilogue mode %d not available", post->mode); return 1;
     }
     if (!ok) { set_error("gemm_nt_i8: incomplete arguments for epilogue mode %d", mode); return 1; }
@@ -2392,6 +2424,24 @@ int launch_tn_stream(TNForm form, const TNGemm* items, int n, const TNCall& call
     else if (form == kTNPlaneCodes) k_tn_stream<1><<<grid, 512, lds1, st>>>(a);
     else k_tn_stream<2><<<grid, 512, lds2, st>>>(a);
     k_tn_stream_fixup<<<tiles * (8 * 24 * 64 / 256), 256, 0, st>>>(a, tiles);
+    return 0;
+}
+
+// ============================================================================ NT, the residual epilogue under LayerScale
+// The launches - and with them the instantiations - of the two kEpiResidFqLs kernels stand behind every other function of this file on purpose.  The compiler
+// emits a kernel where its first launch stands and numbers the labels of the generated code by function, so an instantiation in nt_launch / nt_codes, where the
+// mode-6 siblings are, renumbers every kernel that follows it: the tools/isa_digest.py listing of this file then differs from its parent's in every such line, at the
+// same machine code.  From here the listing gains two lines and loses none (profiles/infer_layer_scale_isa_identity.txt).
+static int nt_launch_resid_ls(const NTArgs& a, bool codes, int grid, size_t lds, hipStream_t st) {
+    if (codes) {
+        static bool once = (allow_lds(k_gemm_nt_ac<3, kEpiResidFqLs, kNtCodesLds>, lds), true);
+        (void)once;
+        k_gemm_nt_ac<3, kEpiResidFqLs, kNtCodesLds><<<grid, 512, lds, st>>>(a);
+        return 0;
+    }
+    static bool once = (allow_lds(k_gemm_nt<2, 3, 1, 13, 1, 8, 3, 32, kEpiResidFqLs, false, true>, lds), true);
+    (void)once;
+    k_gemm_nt<2, 3, 1, 13, 1, 8, 3, 32, kEpiResidFqLs, false, true><<<grid, 512, lds, st>>>(a);
     return 0;
 }
 

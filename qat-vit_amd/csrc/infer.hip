@@ -121,47 +121,15 @@ __global__ __launch_bounds__(256) void k_infer_wprep(const int8_t* __restrict__ 
     if (threadIdx.x == 0 && wsum) wsum[n] = s[0];
 }
 
-}  // namespace
-}  // namespace qv
-
-using namespace qv;
-
-extern "C" {
-
-int64_t qatvit_infer_workspace_bytes(const qatvit_cfg* cfg) {
-    if (!cfg || icheck(*cfg)) return -1;
-    IPlan p;
-    if (iplan(*cfg, &p)) return -1;
-    return p.total;
-}
-
-int qatvit_infer_prepare(const qatvit_cfg* cfg, const void* const* w8, const float* act_scale, const int32_t* act_zero_point, void* workspace,
-                         void* stream) {
-    QV_CHECK_ARG(cfg && w8 && act_scale && act_zero_point && workspace, "qatvit_infer_prepare: null argument");
+// THE forward.  ls_gamma: nullptr, or 2 * depth device pointers - entry 2 i = block i's ls1 (attention branch), 2 i + 1 = its ls2 (MLP branch), fp32 [D] each;
+// proj and fc2 then post the residual epilogue's LayerScale form (kEpiResidFqLs) with their branch's gamma, and nothing else differs
+int infer_forward(const char* who, const qatvit_cfg* cfg, void* const* params, const void* const* w8, const float* const* w_scale, const float* const* ls_gamma,
+                  const float* images, float* logits, void* workspace, void* stream) {
+    QV_CHECK_ARG(cfg && params && w8 && w_scale && images && logits && workspace, "%s: null argument", who);
     if (icheck(*cfg)) return 1;
-    IPlan p;
-    if (iplan(*cfg, &p)) return 1;
-    const IDims d = idims(*cfg);
-    char* ws = reinterpret_cast<char*>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    k_infer_qp<<<cdiv(d.n_act, 64), 64, 0, st>>>(act_scale, act_zero_point, reinterpret_cast<float*>(ws + p.qp), d.n_act);
-    launch_ws_init(reinterpret_cast<uint32_t*>(ws + p.stats), kStatSlots * kStatStride / 2, st);
-    for (int wi = 0; wi < d.n_w; ++wi) {
-        int N, K; iwshape(d, wi, &N, &K);
-        QV_CHECK_ARG(w8[wi], "qatvit_infer_prepare: weight %d is null", wi);
-        k_infer_wprep<<<N, 256, 0, st>>>(reinterpret_cast<const int8_t*>(w8[wi]), K, reinterpret_cast<int32_t*>(ws + p.wsum[wi]),
-                                         p.w16[wi] >= 0 ? reinterpret_cast<_Float16*>(ws + p.w16[wi]) : nullptr,
-                                         wi == d.n_w - 1 ? reinterpret_cast<__bf16*>(ws + p.head_bf16) : nullptr);
-        if (p.w8f[wi] >= 0 && launch_w8_fragment_order(w8[wi], ws + p.w8f[wi], N, K, st)) return 1;
-    }
-    QV_CHECK_LAUNCH("qatvit_infer_prepare");
-    return 0;
-}
-
-int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void* const* w8, const float* const* w_scale, const float* images,
-                         float* logits, void* workspace, void* stream) {
-    QV_CHECK_ARG(cfg && params && w8 && w_scale && images && logits && workspace, "qatvit_infer_forward: null argument");
-    if (icheck(*cfg)) return 1;
+    if (ls_gamma)
+        for (int k = 0; k < 2 * cfg->depth; ++k)
+            QV_CHECK_ARG(ls_gamma[k], "%s: ls_gamma[%d] (block %d, ls%d) is null", who, k, k / 2, k % 2 + 1);
     IPlan p;
     if (iplan(*cfg, &p)) return 1;
     const qatvit_cfg& c = *cfg;
@@ -175,6 +143,13 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
     auto aidx = [&](int blk, int k) { return 2 + 6 * blk + k; };                // norm1, qkv, proj, norm2, fc1, fc2
     auto widx = [&](int blk, int k) { return 1 + 4 * blk + k; };                // qkv, proj, fc1, fc2
     auto wsum = [&](int wi) { return reinterpret_cast<const int32_t*>(ws + p.wsum[wi]); };
+    // the residual update of branch `br` (0: attention, 1: MLP) of block blk as a GEMM epilogue: x_out = resid + fq(.), times the branch's gamma under LayerScale
+    auto resid_post = [&](int blk, int br, const float* resid) {
+        NTPost post{};
+        post.mode = ls_gamma ? kEpiResidFqLs : kEpiResidFq; post.qp = qp(aidx(blk, br ? 5 : 2)); post.qmin = qa; post.qmax = qb; post.resid = resid;
+        if (ls_gamma) post.ls_gamma = ls_gamma[2 * blk + br];
+        return post;
+    };
     // the product of layer wi over `rows` rows without its operands: C = (A . w^T) * (*s1) * s_w + bias, the weight scale as the scalar s2 (per-tensor) or the
     // column vector col_scale (per-channel)
     auto request = [&](int wi, int rows, const float* s1, const float* bias, float* C = nullptr) {
@@ -221,8 +196,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
         if (launch_attn_fwd(nullptr, qp(aidx(i, 1)), qa, qb, d.B, d.T, d.H, d.D, nullptr, nullptr, nullptr, st, ws + p.O16_hi, ws + p.O16_lo, scal16, codes, nullptr))
             return 1;
         {
-            NTPost post{};
-            post.mode = kEpiResidFq; post.qp = qp(aidx(i, 2)); post.qmin = qa; post.qmax = qb; post.resid = xA;
+            const NTPost post = resid_post(i, 0, xA);
             NTGemm g = request(widx(i, 1), M, scal16, bprm(i, 5), xB);
             g.A = ws + p.O16_hi; g.A_lo = ws + p.O16_lo; g.B = ws + p.w16[widx(i, 1)];
             if (launch_gemm_nt(kNTF16, g, &post, st)) return 1;
@@ -243,8 +217,7 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
             NTGemm g1 = request8(w1, M, h8, aidx(i, 3), bprm(i, 9));
             if (strip) g1.B_frag = ws + p.w8f[w1];
             if (launch_gemm_nt(kNTI8, g1, &post, st)) return 1;
-            NTPost post2{};
-            post2.mode = kEpiResidFq; post2.qp = qp(aidx(i, 5)); post2.qmin = qa; post2.qmax = qb; post2.resid = xB;
+            const NTPost post2 = resid_post(i, 1, xB);
             NTGemm g2 = request(w2, M, scal16 + 1, bprm(i, 11), xA);
             g2.B = ws + p.w16[w2];
             if (strip) { g2.A = ws + p.G8; g2.lut = glut; }
@@ -261,8 +234,55 @@ int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void*
                     reinterpret_cast<float*>(ws + p.hq), reinterpret_cast<float*>(ws + p.logits_pre), reinterpret_cast<uint32_t*>(ws + p.stats), kStatSlots, d.B,
                     d.D, d.T, d.C, st);
     launch_logits_fq(reinterpret_cast<float*>(ws + p.logits_pre), qp(a_norm + 1), qa, qb, logits, d.B * d.C, st);
-    QV_CHECK_LAUNCH("qatvit_infer_forward");
+    QV_CHECK_LAUNCH(who);
     return 0;
+}
+
+}  // namespace
+}  // namespace qv
+
+using namespace qv;
+
+extern "C" {
+
+int64_t qatvit_infer_workspace_bytes(const qatvit_cfg* cfg) {
+    if (!cfg || icheck(*cfg)) return -1;
+    IPlan p;
+    if (iplan(*cfg, &p)) return -1;
+    return p.total;
+}
+
+int qatvit_infer_prepare(const qatvit_cfg* cfg, const void* const* w8, const float* act_scale, const int32_t* act_zero_point, void* workspace,
+                         void* stream) {
+    QV_CHECK_ARG(cfg && w8 && act_scale && act_zero_point && workspace, "qatvit_infer_prepare: null argument");
+    if (icheck(*cfg)) return 1;
+    IPlan p;
+    if (iplan(*cfg, &p)) return 1;
+    const IDims d = idims(*cfg);
+    char* ws = reinterpret_cast<char*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    k_infer_qp<<<cdiv(d.n_act, 64), 64, 0, st>>>(act_scale, act_zero_point, reinterpret_cast<float*>(ws + p.qp), d.n_act);
+    launch_ws_init(reinterpret_cast<uint32_t*>(ws + p.stats), kStatSlots * kStatStride / 2, st);
+    for (int wi = 0; wi < d.n_w; ++wi) {
+        int N, K; iwshape(d, wi, &N, &K);
+        QV_CHECK_ARG(w8[wi], "qatvit_infer_prepare: weight %d is null", wi);
+        k_infer_wprep<<<N, 256, 0, st>>>(reinterpret_cast<const int8_t*>(w8[wi]), K, reinterpret_cast<int32_t*>(ws + p.wsum[wi]),
+                                         p.w16[wi] >= 0 ? reinterpret_cast<_Float16*>(ws + p.w16[wi]) : nullptr,
+                                         wi == d.n_w - 1 ? reinterpret_cast<__bf16*>(ws + p.head_bf16) : nullptr);
+        if (p.w8f[wi] >= 0 && launch_w8_fragment_order(w8[wi], ws + p.w8f[wi], N, K, st)) return 1;
+    }
+    QV_CHECK_LAUNCH("qatvit_infer_prepare");
+    return 0;
+}
+
+int qatvit_infer_forward(const qatvit_cfg* cfg, void* const* params, const void* const* w8, const float* const* w_scale, const float* images,
+                         float* logits, void* workspace, void* stream) {
+    return infer_forward("qatvit_infer_forward", cfg, params, w8, w_scale, nullptr, images, logits, workspace, stream);
+}
+
+int qatvit_infer_forward_ls(const qatvit_cfg* cfg, void* const* params, const void* const* w8, const float* const* w_scale, const float* const* ls_gamma,
+                            const float* images, float* logits, void* workspace, void* stream) {
+    return infer_forward("qatvit_infer_forward_ls", cfg, params, w8, w_scale, ls_gamma, images, logits, workspace, stream);
 }
 
 }  // extern "C"

@@ -74,10 +74,15 @@ constexpr int kQpStagedWords = 8;
 //                      N == ldc == 384: the tile holds whole LayerNorm rows; qp = the LN output's
 //   kEpiGeluBwdU8  9   as 5, from one byte per code + one mask bit per element                         code8 code_mask colscale out_hi out_lo          bf16 (split A), plane, f16strip
 //                      (bit c % 8 of byte (row * ldc + c) / 8): what mode 4 leaves in out8 / out8_mask (plane / f16strip: o16_mul o16_amax, no out_lo)
+//   kEpiResidFqLs 11   C[orow] = resid[rrow] + __fmul_rn(fq(acc), ls_gamma[col]): mode 6 under LayerScale,    resid embed_np ls_gamma                         f16, codes
+//                      product and sum rounded separately (what k_resid_fq_lnstats_ls of elt_rows.inc
+//                      computes); ls_gamma == 1 gives the bits of mode 6
 //   plane / f16strip emit the gradient as ONE fp16 plane (out_hi) of value * (*o16_mul) and accumulate max |value| into o16_amax (dy16.hip: Dy16Slot::amax).
 // The numbers are fixed: qatvit_i8_strip takes 3 / 4 / 7 (include/qatvit.h), -DQV_NT_EXPERIMENTS=<mode> and tools/stamp_nt.py / stamp_i8strip.py pass them.
+// (11: the numbers 10, 18 and 19 are instantiation ids of gemm.hip - kPmCodesF16, and mode + 10 of the plane forms' 8 / 9)
 enum NTEpi : int {
-    kEpiPlain = 0, kEpiGeluFwd = 2, kEpiStats = 3, kEpiCodes = 4, kEpiGeluBwdU16 = 5, kEpiResidFq = 6, kEpiQkvCodes = 7, kEpiLnBwd = 8, kEpiGeluBwdU8 = 9
+    kEpiPlain = 0, kEpiGeluFwd = 2, kEpiStats = 3, kEpiCodes = 4, kEpiGeluBwdU16 = 5, kEpiResidFq = 6, kEpiQkvCodes = 7, kEpiLnBwd = 8, kEpiGeluBwdU8 = 9,
+    kEpiResidFqLs = 11
 };
 static_assert(kEpiStats == 3 && kEpiCodes == 4 && kEpiQkvCodes == 7, "the modes of qatvit_i8_strip (include/qatvit.h)");
 struct NTPost {
@@ -112,6 +117,7 @@ struct NTPost {
     const void* lnb_nmask = nullptr;   // the next branch output's STE mask words
     const float* o16_mul = nullptr;
     uint32_t* o16_amax = nullptr;
+    const float* ls_gamma = nullptr;   // fp32 [N]: the branch's LayerScale gamma (mode 11)
 };
 
 // ---- the NT GEMMs (gemm.hip): one request record, six named operand forms, one launcher.  A request computes, for the epilogue its NTPost names (NTEpi above),
@@ -119,9 +125,9 @@ struct NTPost {
 // THE table (every form: M >= 1, ldc % 4 == 0; lda / ldb count elements of A / B as stored; s1, s2, col_scale, bias, stats optional; pair = (hi, lo) planes whose sum is the value; integers = grid values, exact):
 //   form              A, A_lo                         B, B_lo                                 required        N %, K %, lda %, ldb %   epilogues (NTEpi numbers)
 //   kNTBf16       0   bf16 plane (integers) or pair   bf16 plane (integers) or pair (A too)   -               128, 64, 8, 8            0 2 3 4 5; 8 9: A_lo, no B_lo, N % 384 == 0
-//   kNTF16        1   fp16 plane or pair              fp16 plane (integers), -                -               384, 64, 8, 8            0; 6: A_lo; 2: out_f16
+//   kNTF16        1   fp16 plane or pair              fp16 plane (integers), -                -               384, 64, 8, 8            0; 6 11: A_lo; 2: out_f16
 //   kNTI8         2   int8 q - center, -              int8 integers, -                        wsum [N], a_qp  384, 64, 16, 16          0 3 4 6 7
-//   kNTCodes      3   uint8 indices of lut, -         fp16 plane (integers), -                A, B, C, lut    384, 64, 16, 8           0 6
+//   kNTCodes      3   uint8 indices of lut, -         fp16 plane (integers), -                A, B, C, lut    384, 64, 16, 8           0 6 11
 //   kNTPlaneF16   4   ONE fp16 plane of value * 2^e   fp16 plane (integers), -                A, B            384, 32, 8, 8            0; 8 9: o16_mul / o16_amax, K % 64 == 0
 //   kNTPlaneBf16  5   ONE bf16 plane                  bf16 plane, -                           A, B            384, 32, 8, 8            0
 // lut: 256 packed fp16 (hi | lo << 16) pairs, A is expanded through it inside the kernel.  wsum / a_qp / center: the row sums of B and the A operand's quantizer {scale, 1 / scale,

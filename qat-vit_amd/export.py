@@ -24,6 +24,27 @@ def _has_layer_scale(export: Dict) -> bool:
     return any(n.endswith((".ls1.gamma", ".ls2.gamma")) for n in export["float"])
 
 
+def _layer_scale_gammas(export: Dict) -> list:
+    """The 2 * depth gammas of an export in branch order (entry 2 i = block i's ``ls1``, 2 i + 1 = its ``ls2``: the order of ``vit.layer_scale_params`` and
+    of ``qatvit_infer_forward_ls``), [] for an export without LayerScale.  Gammas on some branches only, of another length than ``embed_dim`` or of another
+    type than fp32 are a ``ValueError``.  Host work only: nothing here touches a device."""
+    if not _has_layer_scale(export):
+        return []
+    flt, dim, depth = export["float"], export["arch"]["embed_dim"], export["arch"]["depth"]
+    names = [f"model.blocks.{i}.{ls}.gamma" for i in range(depth) for ls in ("ls1", "ls2")]
+    missing = [n for n in names if n not in flt]
+    extra = sorted(n for n in flt if n.endswith((".ls1.gamma", ".ls2.gamma")) and n not in names)
+    if missing or extra:
+        raise ValueError(f"Int8Student: LayerScale gammas on some branches only (depth {depth}: missing {missing}, unexpected {extra})")
+    for n in names:
+        g = flt[n]
+        if g.dtype != torch.float32:
+            raise ValueError(f"Int8Student: {n} is {g.dtype}, the integer forward reads fp32 gammas")
+        if tuple(g.shape) != (dim,):
+            raise ValueError(f"Int8Student: {n} has shape {tuple(g.shape)}, expected ({dim},)")
+    return [flt[n] for n in names]
+
+
 def _fq_items(prepared):
     return {n: m for n, m in prepared.named_modules() if hasattr(m, "activation_post_process") and hasattr(m, "scale") and hasattr(m, "zero_point")}
 
@@ -108,17 +129,24 @@ def import_int8(export: Dict, device="cuda"):
 class Int8Student:
     """The exported student executed from its integers (``qatvit_infer_forward``): int8 MFMA, frozen quantisation parameters, no
     fp32 intermediates beside the residual stream.  Stands where the reference runs ``convert(base.eval())`` + ``evaluate_quantized_cpu``
-    (qat_trainer.py:376-388).  ``Int8Student(export_int8(model))(images)`` equals ``model(images)`` with the observers switched off, bit for bit."""
+    (qat_trainer.py:376-388).  ``Int8Student(export_int8(model))(images)`` equals ``model(images)`` with the observers switched off, bit for bit.
 
-    def __init__(self, export: Dict, device="cuda"):
+    ``layer_scale=True`` admits an export that holds LayerScale gammas (a model built with ``init_values``): it runs through
+    ``qatvit_infer_forward_ls``, whose proj / fc2 epilogues add ``fq(.) * gamma`` into the residual stream - product and sum rounded separately, as the
+    training forward rounds them, so the logits equal the model's bit for bit as well.  An export without gammas runs as ever; gammas on some branches
+    only, of the wrong length or not fp32 are a ``ValueError`` raised before anything touches the device.  Without the keyword an export with gammas is
+    refused as it always was."""
+
+    def __init__(self, export: Dict, device="cuda", layer_scale=False):
         if export.get("format") != FORMAT:
             raise ValueError("not a qatvit int8 export")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Int8Student executes on MI355X only (no CPU fallback exists)")
-        if _has_layer_scale(export):
+        if _has_layer_scale(export) and not layer_scale:
             raise NotImplementedError("Int8Student: the export holds LayerScale gammas; the integer forward adds the residual in a GEMM epilogue that does not "
                                       "know them yet - evaluate import_int8(export) (the native QAT forward) instead")
+        gammas = _layer_scale_gammas(export) if layer_scale else []
         self.lib = native.lib()
         a = export["arch"]
         depth = a["depth"]
@@ -152,6 +180,8 @@ class Int8Student:
         self._ptr_params = (ctypes.c_void_p * len(ps))(*[None if t is None else t.data_ptr() for t in ps])
         self._ptr_w8 = (ctypes.c_void_p * len(self.w8))(*[t.data_ptr() for t in self.w8])
         self._ptr_ws = (ctypes.c_void_p * len(self.w_scale))(*[t.data_ptr() for t in self.w_scale])
+        self.ls_gamma = [g.contiguous().to(dev) for g in gammas]   # 2 * depth, or none
+        self._ptr_ls = (ctypes.c_void_p * len(self.ls_gamma))(*[t.data_ptr() for t in self.ls_gamma]) if self.ls_gamma else None
         self.capacity = 0
         self.workspace = None
 
@@ -180,6 +210,10 @@ class Int8Student:
         self._reserve(b)
         images = images.contiguous()
         logits = torch.empty(b, kw["num_classes"], dtype=torch.float32, device=self.device)
-        native.check(self.lib.qatvit_infer_forward(ctypes.byref(self._cfg(b)), self._ptr_params, self._ptr_w8, self._ptr_ws, images.data_ptr(), logits.data_ptr(),
-                                                   self.workspace.data_ptr(), native.stream_ptr()), "qatvit_infer_forward")
+        if self._ptr_ls is not None:
+            native.check(self.lib.qatvit_infer_forward_ls(ctypes.byref(self._cfg(b)), self._ptr_params, self._ptr_w8, self._ptr_ws, self._ptr_ls, images.data_ptr(),
+                                                          logits.data_ptr(), self.workspace.data_ptr(), native.stream_ptr()), "qatvit_infer_forward_ls")
+        else:
+            native.check(self.lib.qatvit_infer_forward(ctypes.byref(self._cfg(b)), self._ptr_params, self._ptr_w8, self._ptr_ws, images.data_ptr(), logits.data_ptr(),
+                                                       self.workspace.data_ptr(), native.stream_ptr()), "qatvit_infer_forward")
         return logits

@@ -49,6 +49,7 @@ SIGNATURES = {
     "qatvit_ln_apply_quant8": (c_int, [c_void_p] * 6 + [c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p]),
     "qatvit_i8_strip_ln": (c_int, [c_void_p] * 5 + [c_int32, c_int32] + [c_void_p] * 4 + [c_int32] * 5 + [c_void_p] * 5),
     "qatvit_gemm_nt_codes": (c_int, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p] * 6),
+    "qatvit_gemm_nt_resid_fq": (c_int, [c_int32] + [c_void_p] * 5 + [c_int32] * 6 + [c_void_p] * 5 + [c_int32, c_int32, c_void_p, c_void_p]),
     "qatvit_gemm_nt_i8": (c_int, [c_void_p] * 4 + [c_int32, c_void_p] + [c_int32] * 6 + [c_void_p] * 6),
     "qatvit_gemm_tn_scratch_bytes": (c_int64, []),
     "qatvit_gemm_tn": (c_int, [c_void_p] * 5 + [c_int32] * 6 + [c_void_p] * 4 + [c_int32] * 3 + [c_void_p] * 3 + [c_int64, c_void_p]),
@@ -109,6 +110,7 @@ SIGNATURES = {
     "qatvit_infer_workspace_bytes": (c_int64, [c_void_p]),
     "qatvit_infer_prepare": (c_int, [c_void_p] * 6),
     "qatvit_infer_forward": (c_int, [c_void_p] * 8),
+    "qatvit_infer_forward_ls": (c_int, [c_void_p] * 9),
     "qatvit_image_resize_coeffs": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "qatvit_image_table": (c_int, [c_void_p] * 3),
     "qatvit_image_batch": (c_int, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 4),
