@@ -141,6 +141,29 @@ int qatvit_kd_bce_loss(const float* student, const float* teacher, const float* 
                        float label_smoothing, float target_threshold, int32_t sum_classes, float* partials, float* out3, float* dlogits,
                        void* stream);
 
+/* The KD + softmax-CE loss of qatvit_kd_ce_loss / _table / _mix in a CLASS-PARALLEL form, for class counts where one thread per row is too slow
+ * (1000 classes) or refused (above 4096).  One entry for every form, with qatvit_kd_bce_loss's optional-argument rules: teacher [B,C] and
+ * table [table_rows,C] mutually exclusive, a table needs index and table_rows >= 1, both NULL: CE only and alpha ignored; mix NULL or 4-byte aligned.
+ * 1 <= B < 2^30, 2 <= C <= 32768, kd_temp > 0, label_smoothing in [0, 1); fp32 logits.  partials: fp32 [2 * B] workspace, contents on entry ignored.
+ * Arithmetic: per element exactly qatvit_kd_ce_loss_mix's (log-softmax, the smoothed mixed hard target, the KD target of a teacher row or of the
+ * two table rows with 0 log 0 = 0, both gradient terms with 1 / B; all fp32, every operation rounded on its own).  A row with lam == 1, or without a
+ * record, is its own partner: mix == NULL and lam == 1 give the same bits, and the partner's label and table row are read only where lam != 1.  A
+ * label outside [0, C) matches no class.  An index[b], or where lam != 1 an index[p], outside [0, table_rows) reads nothing: that row of dlogits
+ * and all of out3 become NaN.  A NaN logit makes its own row of dlogits and out3 NaN; other rows keep their bits.
+ * What differs from the CE entries:
+ *   - the summation order.  The classes of a row are spread over the 64 lanes of one wave (C <= 1024, 4 rows per workgroup) or the 256 threads of
+ *     one workgroup (C > 1024), thread t adding the classes t, t + 64 (256), ... and the threads' sums then combined by butterflies; the rows'
+ *     sums are added in double in one fixed order (qatvit_kd_bce_loss's second launch).  out3 and dlogits agree with the CE entries' to rounding,
+ *     not bit for bit.  The form depends on C alone: a row's dlogits bits depend on that row, its partner, C and 1 / B only;
+ *   - two launches on `stream` instead of one, no atomics, no zeroed state: the same inputs give the same bits;
+ *   - the partials workspace;
+ *   - the class range, 2 .. 32768 instead of 2 .. 4096.
+ * out3 = {w_kd * kd + w_ce * ce, ce, kd * T^2} as for the CE entries.
+ */
+int qatvit_kd_ce_loss_rows(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                           const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                           float label_smoothing, float* partials, float* out3, float* dlogits, void* stream);
+
 /* ===========================================================================
  * Building blocks of the step, exported for kernel-level parity tests.
  * All matrices row-major; "bf16" = IEEE bfloat16 bit patterns (uint16).

@@ -29,6 +29,15 @@ int launch_kd_bce_loss(const float* student, const float* teacher, const float* 
                        const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
                        float label_smoothing, float target_threshold, bool sum_classes, float* partials, float* out3, float* dlogits,
                        hipStream_t st);
+// its second launch, one 256-thread workgroup: partials[2 * B] -> out3 = {w_kd * kd + w_hard * hard, hard, kd * T^2}, hard = scale * sum, in double, in one order
+__global__ __launch_bounds__(256) void k_kd_bce_finish(const float* __restrict__ partials, int B, float T, float alpha, int kd, float scale,
+                                                       float* __restrict__ out3);
+
+// ---- loss_rows.hip: the KD + softmax-CE loss of launch_kd_ce_loss_mix with a row's classes spread over a wave (C <= 1024) or a workgroup (C <= 32768);
+// rows to partials[2 * batch], then k_kd_bce_finish with scale = 1 / batch (two launches)
+int launch_kd_ce_loss_rows(const float* student, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                           const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                           float label_smoothing, float* partials, float* out3, float* dlogits, hipStream_t st);
 
 // ---- fq.hip (engine pieces)
 int launch_minmax(const float* x, int64_t channels, int64_t inner, int per_channel, uint32_t* ws, int nslots, hipStream_t st);

@@ -152,9 +152,12 @@ class _KDCELossFn(torch.autograd.Function):
         return dlogits * dloss, None, None, None, None, None
 
 
-def kd_ce_loss(student, teacher, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+def kd_ce_loss(student, teacher, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
     """Returns (loss, [loss, ce, kd*T^2]).  ``teacher=None`` -> CE only
-    (the reference's step at /root/reference/src/training/qat_trainer.py:343-349)."""
+    (the reference's step at /root/reference/src/training/qat_trainer.py:343-349).  ``class_parallel=True``: the same loss by
+    ``qatvit_kd_ce_loss_rows`` (see ``kd_ce_loss_mix``)."""
+    if class_parallel:
+        return _KDCELossRowsFn.apply(student, teacher, None, None, labels, None, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss")
     return _KDCELossFn.apply(student, teacher, labels, kd_temp, kd_alpha, label_smoothing)
 
 
@@ -190,48 +193,59 @@ class _KDCELossTableFn(torch.autograd.Function):
         return dlogits * dloss, None, None, None, None, None, None
 
 
-def kd_ce_loss_table(student, table, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+def kd_ce_loss_table(student, table, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
     """``kd_ce_loss(student, table[index], labels, ...)`` in one launch, without the gathered tensor: returns (loss, [loss, ce, kd*T^2]).
     ``table`` is fp32 ``[rows, C]`` (per-sample teacher logits, distill.TeacherLogitTable), ``index`` int64 ``[B]``.  An index outside the table
-    makes the loss and that row of the gradient NaN; it is not an error on the host (nothing here synchronises)."""
+    makes the loss and that row of the gradient NaN; it is not an error on the host (nothing here synchronises).  ``class_parallel=True``: the same
+    loss by ``qatvit_kd_ce_loss_rows`` (see ``kd_ce_loss_mix``)."""
+    if class_parallel:
+        return _KDCELossRowsFn.apply(student, None, table, index, labels, None, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss_table")
     return _KDCELossTableFn.apply(student, table, index, labels, kd_temp, kd_alpha, label_smoothing)
+
+
+def _kd_ce_operands(who, student, teacher, table, index, labels, mix):
+    """The argument checks the mixed CE forms share: (contiguous student, (teacher, table, index, labels, mix) addresses or None, table rows, the
+    converted tensors, which the caller holds until its launch is enqueued)."""
+    _need_cuda(student, who)
+    student = student.contiguous()
+    B, C = student.shape
+    dev = student.device
+    tptr = bptr = iptr = None
+    rows = 0
+    if teacher is not None:
+        teacher = teacher.contiguous().float()
+        if teacher.shape != (B, C) or teacher.device != dev:
+            raise RuntimeError(f"{who}: the teacher must be a [{B}, {C}] tensor on {dev}, got {tuple(teacher.shape)} on {teacher.device}")
+        tptr = teacher.data_ptr()
+    if table is not None:
+        _need_cuda(table, who)
+        if table.dim() != 2 or table.shape[1] != C or table.shape[0] < 1 or not table.is_contiguous() or table.device != dev:
+            raise RuntimeError(f"{who}: the table must be a contiguous [rows, {C}] tensor on {dev}, got {tuple(table.shape)} on {table.device}")
+        index = index.contiguous()
+        if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev:
+            raise RuntimeError(f"{who}: index must be an int64 [{B}] tensor on {dev}")
+        bptr, iptr, rows = table.data_ptr(), index.data_ptr(), table.shape[0]
+    labels = labels.contiguous()
+    if labels.dtype != torch.int64 or labels.shape != (B,) or labels.device != dev:
+        raise RuntimeError(f"{who}: labels must be an int64 [{B}] tensor on {dev}")
+    mptr = None
+    if mix is not None:
+        if mix.dtype != torch.int32 or tuple(mix.shape) != (B, 6) or not mix.is_contiguous() or mix.device != dev:
+            raise RuntimeError(f"{who}: mix must be a contiguous int32 [{B}, 6] tensor on {dev}")
+        mptr = mix.data_ptr()
+    return student, (tptr, bptr, iptr, labels.data_ptr(), mptr), rows, (teacher, index, labels)
 
 
 class _KDCELossMixFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing):
         who = "kd_ce_loss_mix" if table is None else "kd_ce_loss_table_mix"
-        _need_cuda(student, who)
-        student = student.contiguous()
-        B, C = student.shape
-        dev = student.device
-        tptr = bptr = iptr = None
-        rows = 0
-        if teacher is not None:
-            teacher = teacher.contiguous().float()
-            if teacher.shape != (B, C) or teacher.device != dev:
-                raise RuntimeError(f"{who}: the teacher must be a [{B}, {C}] tensor on {dev}, got {tuple(teacher.shape)} on {teacher.device}")
-            tptr = teacher.data_ptr()
-        if table is not None:
-            _need_cuda(table, who)
-            if table.dim() != 2 or table.shape[1] != C or table.shape[0] < 1 or not table.is_contiguous() or table.device != dev:
-                raise RuntimeError(f"{who}: the table must be a contiguous [rows, {C}] tensor on {dev}, got {tuple(table.shape)} on {table.device}")
-            index = index.contiguous()
-            if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev:
-                raise RuntimeError(f"{who}: index must be an int64 [{B}] tensor on {dev}")
-            bptr, iptr, rows = table.data_ptr(), index.data_ptr(), table.shape[0]
-        labels = labels.contiguous()
-        if labels.dtype != torch.int64 or labels.shape != (B,) or labels.device != dev:
-            raise RuntimeError(f"{who}: labels must be an int64 [{B}] tensor on {dev}")
-        mptr = None
-        if mix is not None:
-            if mix.dtype != torch.int32 or tuple(mix.shape) != (B, 6) or not mix.is_contiguous() or mix.device != dev:
-                raise RuntimeError(f"{who}: mix must be a contiguous int32 [{B}, 6] tensor on {dev}")
-            mptr = mix.data_ptr()
+        student, (tptr, bptr, iptr, lptr, mptr), rows, keep = _kd_ce_operands(who, student, teacher, table, index, labels, mix)
+        (B, C), dev = student.shape, student.device
         out3 = torch.empty(3, dtype=torch.float32, device=dev)
         dlogits = torch.empty_like(student)
         native.check(
-            native.lib().qatvit_kd_ce_loss_mix(student.data_ptr(), tptr, bptr, rows, iptr, labels.data_ptr(), mptr, B, C, float(kd_temp),
+            native.lib().qatvit_kd_ce_loss_mix(student.data_ptr(), tptr, bptr, rows, iptr, lptr, mptr, B, C, float(kd_temp),
                                                float(kd_alpha), float(label_smoothing), out3.data_ptr(), dlogits.data_ptr(), native.stream_ptr()),
             "qatvit_kd_ce_loss_mix",
         )
@@ -245,18 +259,53 @@ class _KDCELossMixFn(torch.autograd.Function):
         return (dlogits * dloss,) + (None,) * 8
 
 
-def kd_ce_loss_mix(student, teacher, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+class _KDCELossRowsFn(torch.autograd.Function):
+    """Every form of the KD + CE loss through qatvit_kd_ce_loss_rows: _KDCELossMixFn's checks, plus the partials workspace."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, who):
+        student, (tptr, bptr, iptr, lptr, mptr), rows, keep = _kd_ce_operands(who, student, teacher, table, index, labels, mix)
+        (B, C), dev = student.shape, student.device
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        partials = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        dlogits = torch.empty_like(student)
+        native.check(
+            native.lib().qatvit_kd_ce_loss_rows(student.data_ptr(), tptr, bptr, rows, iptr, lptr, mptr, B, C, float(kd_temp),
+                                                float(kd_alpha), float(label_smoothing), partials.data_ptr(), out3.data_ptr(), dlogits.data_ptr(),
+                                                native.stream_ptr()),
+            "qatvit_kd_ce_loss_rows",
+        )
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(out3)
+        return out3[0], out3
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * dloss,) + (None,) * 9
+
+
+def kd_ce_loss_mix(student, teacher, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
     """``kd_ce_loss`` on a mixed batch: returns (loss, [loss, ce, kd*T^2]).  ``mix`` is the int32 ``[B, 6]`` record tensor the images were mixed
     with (data.MixupCutmix): row b's hard target is ``lam`` on ``labels[b]`` and ``1 - lam`` on the partner's label.  ``teacher`` (``[B, C]`` or
-    None) is the teacher's output on the mixed images, so the KD part is ``kd_ce_loss``'s.  ``mix=None`` is ``kd_ce_loss``."""
+    None) is the teacher's output on the mixed images, so the KD part is ``kd_ce_loss``'s.  ``mix=None`` is ``kd_ce_loss``.
+
+    ``class_parallel=True`` runs the same loss by ``qatvit_kd_ce_loss_rows``: a row's classes spread over one wave (``C <= 1024``) or one workgroup
+    (up to ``C = 32768``; the default form stops at 4096) instead of one thread per row - the form for 100 classes and more.  Two launches instead of
+    one, so at ``C = 10`` the default is the faster one.  Same arithmetic per element; the sums are added in another order, so the results agree to
+    rounding, not bit for bit."""
+    if class_parallel:
+        return _KDCELossRowsFn.apply(student, teacher, None, None, labels, mix, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss_mix")
     return _KDCELossMixFn.apply(student, teacher, None, None, labels, mix, kd_temp, kd_alpha, label_smoothing)
 
 
-def kd_ce_loss_table_mix(student, table, index, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+def kd_ce_loss_table_mix(student, table, index, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
     """``kd_ce_loss_table`` on a mixed batch: the hard target as in ``kd_ce_loss_mix``, the KD target
     ``lam * softmax(table[index[b]] / T) + (1 - lam) * softmax(table[index[p]] / T)`` - the usual mixed soft label, not the teacher's output on
     the mixed image.  An index outside the table, of the row or (where ``lam != 1``) of its partner, makes the loss and that row of the gradient
-    NaN.  ``mix=None`` is ``kd_ce_loss_table``."""
+    NaN.  ``mix=None`` is ``kd_ce_loss_table``.  ``class_parallel=True``: the same loss by ``qatvit_kd_ce_loss_rows`` (see ``kd_ce_loss_mix``)."""
+    if class_parallel:
+        return _KDCELossRowsFn.apply(student, None, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss_table_mix")
     return _KDCELossMixFn.apply(student, None, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
 
 
