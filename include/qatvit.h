@@ -947,6 +947,50 @@ int qatvit_optim_lamb_apply(const void* param_ptrs, const void* exp_avg_ptrs, co
  *   request exceeds 64 KB and the call is refused with an error string that states the byte count, before any HIP call.
  *   D % 4 == 0, 8 <= D <= 384, 1 <= B <= 65535, bytes / table / blur / out not NULL: anything else is refused with an error string before
  *   any HIP call.
+ *
+ * qatvit_image_bytes_randaug: RandAugment (timm's rand-m9-mstd0.5-inc1 recipe), a launch of its own BETWEEN qatvit_image_window_u8 and the
+ *   second stage (qatvit_image_batch* at S = D, or qatvit_image_bytes_blur): bytes in, bytes out, in front of colour, blur, erase and mix.
+ *   bytes, scratch and out are uint8 [B][D][D][3] (HWC, contiguous, 4-byte aligned, on the device) at batch POSITIONS and share no byte;
+ *   bytes is only read, scratch holds intermediate images, out[b] EQUALS, byte for byte, what Pillow gives for sample b's layers applied in
+ *   order.  records int32 [B][layers][16], formed on the host, record [b][l] = layer l of batch position b:
+ *     word 0  the op code, 0 = the layer does nothing; word 1 the integer argument (bits / thresh / add) or, for a geometric op, the
+ *     resample code (2 BILINEAR, 3 BICUBIC: Pillow's numbers); word 2 the fp32 enhance factor; word 3 the fill colour R | G << 8 | B << 16;
+ *     words 4 .. 15 the six doubles a0 .. a5 of the affine matrix (low word first).
+ *   The ops, with img the current image (the fifteen of timm's _RAND_INCREASING_TRANSFORMS):
+ *     1 AutoContrast  ImageOps.autocontrast(img): per channel lo / hi = the lowest / highest value present; hi <= lo: unchanged; else in double
+ *                     scale = 255.0 / (hi - lo), offset = -lo * scale, v -> clip(int(v * scale + offset), 0, 255)
+ *     2 Equalize      ImageOps.equalize(img): per channel with histogram h: unchanged if one value is present or
+ *                     step = (D * D - h[highest value present]) / 255 is 0; else v -> min(255, (step / 2 + h[0] + .. + h[v - 1]) / step), integers
+ *     3 Invert        v -> 255 - v
+ *     4 Posterize     ImageOps.posterize(img, bits): v -> v & ~(2^(8 - bits) - 1); bits clamped to 0 .. 8 (8: unchanged, 0: black)
+ *     5 Solarize      ImageOps.solarize(img, thresh): v -> v < thresh ? v : 255 - v; thresh clamped to 0 .. 256
+ *     6 SolarizeAdd   v -> v < 128 ? min(255, v + add) : v; add clamped to 0 .. 255
+ *     7 Color         ImageEnhance.Color(img).enhance(f) = blend(L, img, f), L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the pixel
+ *     8 Contrast      ImageEnhance.Contrast(img).enhance(f) = blend(m, img, f), m = int(mean(L) + 0.5) over the image
+ *     9 Brightness    ImageEnhance.Brightness(img).enhance(f) = blend(0, img, f)
+ *    10 Sharpness     ImageEnhance.Sharpness(img).enhance(f) = blend(img.filter(SMOOTH), img, f); SMOOTH: the one-pixel border is copied,
+ *                     inside floor((sum of the 3 x 3 + 4 * centre) / 13 + 0.5)
+ *       blend(a, v, f) = fl(a + fl(f * (v - a))) in fp32, each operation rounded (never fused), clipped to 0 .. 255, truncated.
+ *    11 ShearX, 12 ShearY, 13 TranslateX, 14 TranslateY, 15 Rotate   img.transform((D, D), AFFINE, (a0 .. a5), resample, fillcolor=fill); for
+ *       Rotate the matrix is the one Image.rotate(deg) forms (angle % 360, cos and sin of -radians(angle) rounded to 15 decimals, the centre
+ *       (D / 2, D / 2) carried through), for which that transform gives what Image.rotate gives, its shortcuts at 0 / 90 / 180 / 270 included.
+ *       The five codes run the same code.  Per output pixel (x, y), in double, every operation rounded on its own, left to right:
+ *         xin = (a0 * (x + .5) + a1 * (y + .5)) + a2, yin = (a3 * (x + .5) + a4 * (y + .5)) + a5;
+ *         the pixel is `fill` unless 0 <= xin < D and 0 <= yin < D (a NaN is outside);
+ *         xin -= .5, yin -= .5, x0 = floor(xin), y0 = floor(yin), dx = xin - x0, dy = yin - y0;
+ *         BILINEAR, per channel: v1 = a + (b - a) * dx on row clamp(y0) with columns clamp(x0), clamp(x0 + 1); v2 the same on row y0 + 1 if
+ *           that row is inside the image, else v1; the byte is (uint8)(v1 + (v2 - v1) * dy), truncated;
+ *         BICUBIC: x0 -= 1, y0 -= 1, columns clamp(x0 .. x0 + 3); row clamp(y0), then rows y0 + 1 .. y0 + 3, each replaced by the value of
+ *           the row in front of it where it is outside the image; along x, then along y:
+ *           p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4, v = v2 + d (p2 + d (p3 + d p4));
+ *           0 if v <= 0, 255 if v >= 255, else truncated.
+ *   A record is cleaned, not trusted, and nothing is addressed through it: an op code outside 1 .. 15, a resample code other than 2 or 3,
+ *   an enhance factor that is not finite and a matrix with an entry that is not finite make the layer do nothing; integer arguments are
+ *   clamped as stated; of word 3 the low 24 bits are read.  The result is the cleaned records' result.
+ *   One workgroup per sample walks the sample's layers through global memory (scratch and out in turn; a sample none of whose layers does
+ *   anything is one copy), 4 KB of LDS, one launch per batch, no host synchronisation, capturable.
+ *   D % 4 == 0, 8 <= D <= 384, 1 <= B <= 65535, 1 <= layers <= 4, no NULL pointer, three buffers that do not overlap: anything else is refused
+ *   with an error string before any HIP call.
  */
 int qatvit_image_resize_coeffs(int32_t src, int32_t dst, int32_t* xmin_host, int32_t* ntaps_host, int32_t* coef_host);
 int qatvit_image_table(const float* mean_host, const float* std_host, float* table_host);
@@ -983,6 +1027,8 @@ int qatvit_image_window_u8(const uint8_t* data, const int64_t* index, int32_t B,
                            const int32_t* tables, int32_t max_side, const int32_t* rrc, uint8_t* out, void* stream);
 int qatvit_image_bytes_blur(const uint8_t* bytes, int32_t B, int32_t D, const float* table, const int32_t* mix, const int32_t* erase,
                             const int32_t* color, uint32_t* sums, const int32_t* blur, float* out, void* stream);
+int qatvit_image_bytes_randaug(const uint8_t* bytes, int32_t B, int32_t D, const int32_t* records, int32_t layers, uint8_t* scratch,
+                               uint8_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validation counts on the device: one launch per batch of logits, one device-to-host copy per evaluation.

@@ -720,6 +720,26 @@ int qatvit_image_bytes_blur(const uint8_t* bytes, int32_t B, int32_t D, const fl
     return 0;
 }
 
+// The RandAugment stage (image_randaug.hip): every check before any HIP call.  The three images may not share a byte: a layer reads one and writes another
+int qatvit_image_bytes_randaug(const uint8_t* bytes, int32_t B, int32_t D, const int32_t* records, int32_t layers, uint8_t* scratch, uint8_t* out,
+                               void* stream) {
+    const char* who = "qatvit_image_bytes_randaug";
+    QV_CHECK_ARG(bytes && records && scratch && out, "%s: null pointer argument", who);
+    QV_CHECK_ARG(D % 4 == 0 && D >= 8 && D <= kImgMaxD, "%s: output size %d must be a multiple of 4 in 8 .. %d", who, D, kImgMaxD);
+    QV_CHECK_ARG(B >= 1 && B <= 65535, "%s: batch %d must be 1 .. 65535", who, B);
+    QV_CHECK_ARG(layers >= 1 && layers <= kRandaugMaxLayers, "%s: %d layers are outside 1 .. %d", who, layers, kRandaugMaxLayers);
+    QV_CHECK_ARG((((uintptr_t)bytes | (uintptr_t)records | (uintptr_t)scratch | (uintptr_t)out) & 3) == 0, "%s: misaligned pointer", who);
+    const uintptr_t n = (uintptr_t)B * 3 * D * D, p[3] = {(uintptr_t)bytes, (uintptr_t)scratch, (uintptr_t)out};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            QV_CHECK_ARG(p[i] + n <= p[j] || p[j] + n <= p[i], "%s: bytes, scratch and out must be three distinct buffers of B * D * D * 3 bytes", who);
+    ImageRandaug r;
+    r.bytes = bytes, r.B = B, r.D = D, r.records = records, r.layers = layers, r.scratch = scratch, r.out = out;
+    if (int rc = launch_image_randaug(r, (hipStream_t)stream)) return rc;
+    QV_CHECK_LAUNCH(who);
+    return 0;
+}
+
 int qatvit_rows_gather(const void* tall, void* compact, int32_t rows, int32_t T, int32_t width, int64_t stride, void* stream) {
     RowMoveTab t;
     t.n = 1; t.m[0] = RowMove{tall, compact, stride, width};

@@ -456,6 +456,18 @@ int image_bytes_blur_band(int D, bool mixed);          // 16 rows without mix re
 int64_t image_bytes_blur_lds_bytes(int D, bool mixed);
 // nonzero + set_error: 1 before any HIP call where the LDS request exceeds kImgMixMaxLds (mix records above D = 344), 2 where zeroing sums fails
 int launch_image_bytes_blur(const ImageBytesBlur& r, hipStream_t st);
+// image_randaug.hip: the RandAugment stage between the window stage and the second stage: out uint8 [B, D, D, 3] from bytes uint8 [B, D, D, 3] through
+// records int32 [B][layers][kRandaugWords]; scratch is a third buffer of that size.  One workgroup per sample, static LDS, nothing to refuse
+constexpr int kRandaugWords = 16, kRandaugMaxLayers = 4;
+struct ImageRandaug {
+    const uint8_t* bytes = nullptr;
+    int B = 0, D = 0;
+    const int32_t* records = nullptr;
+    int layers = 0;
+    uint8_t* scratch = nullptr;
+    uint8_t* out = nullptr;
+};
+int launch_image_randaug(const ImageRandaug& r, hipStream_t st);
 // eval.hip: validation counts.  The state block of an evaluation: kEvalCounters int64 counters, then the double sum of the finite row losses
 // (include/qatvit.h documents the same ten 8-byte words for the C caller).  Every launch ADDS to it: integer counts are exact and independent of
 // launch and block order; loss_sum is a sum of doubles in arrival order, so its last bits can differ from run to run.

@@ -476,6 +476,150 @@ class ThreeAugment:
         return color.to(torch.int32), _blur_records(choice == 2, self.radius[0] + u * (self.radius[1] - self.radius[0]))
 
 
+RANDAUG_WORDS = 16
+RANDAUG_MAX_LAYERS = 4
+# op code = place + 1 (0: the layer does nothing): the fifteen ops of timm's _RAND_INCREASING_TRANSFORMS, as include/qatvit.h lists them
+RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness", "Sharpness",
+               "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
+RANDAUG_RESAMPLE = {"bilinear": 2, "bicubic": 3}                     # Pillow's Image.BILINEAR / Image.BICUBIC
+RANDAUG_FILL = (124, 116, 104)                                       # timm's img_mean: round(255 * m) of the ImageNet mean
+
+
+def rotate_matrix(degrees, out_size):
+    """The six doubles that Pillow's ``Image.rotate(degrees)`` hands to its affine transform for a ``D x D`` image, formed as it forms them."""
+    c = out_size / 2
+    angle = -math.radians(degrees % 360.0)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    m[2], m[5] = m[0] * -c + m[1] * -c + m[2], m[3] * -c + m[4] * -c + m[5]
+    m[2] += c
+    m[5] += c
+    return m
+
+
+def randaug_record(op, value=0, out_size=None, resample="bilinear", fill=RANDAUG_FILL):
+    """One 16-word int32 record (include/qatvit.h, qatvit_image_bytes_randaug) as a NumPy array.  ``op`` is a name of ``RANDAUG_OPS`` or
+    None (the layer does nothing); ``value`` is what the op takes: bits / threshold / addend for Posterize / Solarize / SolarizeAdd, the
+    enhance factor for Color / Contrast / Brightness / Sharpness, the shear factor, the translation in pixels or the angle in degrees
+    (``Rotate`` needs ``out_size``) for the geometric ops, whose matrix is formed here.  Host only."""
+    rec = np.zeros(RANDAUG_WORDS, np.int32)
+    if op is None:
+        return rec
+    code = RANDAUG_OPS.index(op) + 1
+    v = float(value)
+    matrix = {"ShearX": (1, v, 0, 0, 1, 0), "ShearY": (1, 0, 0, v, 1, 0), "TranslateX": (1, 0, v, 0, 1, 0), "TranslateY": (1, 0, 0, 0, 1, v)}.get(op)
+    if op == "Rotate":
+        matrix = rotate_matrix(v, int(out_size))
+    rec[0] = code
+    rec[1] = RANDAUG_RESAMPLE[resample] if matrix is not None else (int(value) if code <= 6 else 0)
+    rec[2:3] = np.float32(v if 7 <= code <= 10 else 1.0).view(np.int32)
+    rec[3] = int(fill[0]) | int(fill[1]) << 8 | int(fill[2]) << 16
+    rec[4:16] = np.asarray(matrix if matrix is not None else (1, 0, 0, 0, 1, 0), np.float64).view(np.int32)
+    return rec
+
+
+class RandAugment:
+    """timm's RandAugment (``rand-m9-mstd0.5-inc1``, arXiv:1909.13719) as ``num_layers`` 16-word int32 records per sample (include/qatvit.h,
+    qatvit_image_bytes_randaug): per layer the op code, its integer argument or resample code, its fp32 factor, the fill colour and the six
+    doubles of its affine matrix.  The stage applies the layers in order to the uint8 image behind the resize and in front of colour, blur,
+    erase and mix, equal to Pillow's result byte for byte.  The arguments have timm's meaning: ``magnitude`` 0 .. 10, ``mstd`` the standard
+    deviation of the per-op magnitude (above 100: uniform in [0, magnitude]), ``prob`` the probability that a chosen op is applied,
+    ``increasing`` the ``inc1`` level maps, ``fill`` the colour of pixels that a geometric op leaves uncovered, ``interpolation`` the
+    resample filters a geometric op draws from.  Built and drawn on the host; needs no GPU."""
+
+    def __init__(self, magnitude=9, num_layers=2, mstd=0.5, prob=0.5, increasing=True, translate_pct=0.45, fill=RANDAUG_FILL,
+                 interpolation=("bilinear", "bicubic")):
+        number = lambda t: not isinstance(t, bool) and isinstance(t, (int, float)) and not math.isnan(t)   # noqa: E731
+        if not number(magnitude) or not 0 <= magnitude <= 10:
+            raise ValueError(f"magnitude must be a number 0 .. 10, got {magnitude!r}")
+        if isinstance(num_layers, bool) or not isinstance(num_layers, int) or not 1 <= num_layers <= RANDAUG_MAX_LAYERS:
+            raise ValueError(f"num_layers must be an integer 1 .. {RANDAUG_MAX_LAYERS}, got {num_layers!r}")
+        if not number(mstd) or mstd < 0:
+            raise ValueError(f"mstd must be a number >= 0, got {mstd!r}")
+        if not number(prob) or not 0 <= prob <= 1:
+            raise ValueError(f"prob must be a probability 0 .. 1, got {prob!r}")
+        if not number(translate_pct) or not 0 <= translate_pct <= 1:
+            raise ValueError(f"translate_pct must be a number 0 .. 1, got {translate_pct!r}")
+        if isinstance(interpolation, str):
+            interpolation = (interpolation,)
+        if not interpolation or any(t not in RANDAUG_RESAMPLE for t in interpolation):
+            raise ValueError(f"interpolation must be drawn from {sorted(RANDAUG_RESAMPLE)}, got {interpolation!r}")
+        if len(fill) != 3 or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t <= 255 for t in fill):
+            raise ValueError(f"fill must be three integer byte values, got {fill!r}")
+        self.magnitude, self.num_layers, self.mstd, self.prob = float(magnitude), num_layers, float(mstd), float(prob)
+        self.increasing, self.translate_pct, self.fill, self.interpolation = bool(increasing), float(translate_pct), tuple(fill), tuple(interpolation)
+
+    @classmethod
+    def from_config(cls, config, **kwargs):
+        """timm's config string: ``rand`` and then ``m<magnitude>``, ``n<layers>``, ``mstd<std>``, ``p<prob>``, ``inc<0|1>`` joined by ``-``.
+        Any other section (``mmax``, ``w``, ``t``) raises a ValueError.  ``inc`` defaults to 0 here as in timm."""
+        parts = str(config).split("-")
+        if parts[0] != "rand":
+            raise ValueError(f"a RandAugment config starts with 'rand', got {config!r}")
+        kw = dict(increasing=False)
+        for part in parts[1:]:
+            for key, name, kind in (("mstd", "mstd", float), ("inc", "increasing", lambda t: bool(int(t))), ("m", "magnitude", float),
+                                    ("n", "num_layers", int), ("p", "prob", float)):
+                if part.startswith(key) and part[len(key):len(key) + 1].isdigit():
+                    try:
+                        kw[name] = kind(part[len(key):])
+                    except ValueError:
+                        raise ValueError(f"section {part!r} of {config!r} has no number") from None
+                    break
+            else:
+                raise ValueError(f"section {part!r} of {config!r} is not one of m, n, mstd, p, inc")
+        kw.update(kwargs)
+        return cls(**kw)
+
+    def _value(self, op, level, negate, D):
+        """The argument of one op at magnitude `level` (timm's level maps)."""
+        l, inc = level / 10.0, self.increasing
+        sign = -1.0 if negate else 1.0
+        if op == "Rotate":
+            return sign * l * 30.0
+        if op in ("ShearX", "ShearY"):
+            return sign * l * 0.3
+        if op in ("TranslateX", "TranslateY"):
+            return sign * l * self.translate_pct * D
+        if op == "Posterize":
+            return 4 - int(l * 4) if inc else int(l * 4)
+        if op == "Solarize":
+            return 256 - int(l * 256) if inc else min(256, int(l * 256))
+        if op == "SolarizeAdd":
+            return min(128, int(l * 110))
+        if op in ("Color", "Contrast", "Brightness", "Sharpness"):
+            return max(0.1, 1.0 + sign * l * 0.9) if inc else max(0.1, l * 1.8 + 0.1)
+        return 0
+
+    def draw(self, n, out_size, generator=None):
+        """int32 CPU tensor ``[n, num_layers, 16]`` for outputs of side D = `out_size`.  The rule (timm's ``RandAugment`` / ``AugmentOp``,
+        restated: timm is not a dependency), all from `generator`, in this order, every tensor ``[n, num_layers]``:
+        ``k = torch.randint(0, 15, ...)``: the op of the layer, uniform with replacement;
+        ``a = torch.rand(..., dtype=float64)``: the op is applied where ``a < prob``, else the layer does nothing;
+        ``z = torch.randn(..., dtype=float64)``: the magnitude ``clip(magnitude + mstd * z, 0, 10)`` (``mstd > 100``: ``u * magnitude`` of
+        the next draw);
+        ``u = torch.rand(..., dtype=float64)``; ``s = torch.rand(..., dtype=float64)``: the geometric and the ``inc1`` enhance ops are
+        negated where ``s < 0.5``;
+        ``r = torch.randint(0, len(interpolation), ...)``: the resample filter of a geometric op.
+        Every draw is always made, so the generator's position depends on `n` only."""
+        D = int(out_size)
+        if not 8 <= D <= 0xffff:
+            raise ValueError(f"out_size must be 8 .. 65535, got {out_size!r}")
+        shape = (int(n), self.num_layers)
+        k = torch.randint(0, len(RANDAUG_OPS), shape, generator=generator)
+        a = torch.rand(shape, dtype=torch.float64, generator=generator)
+        z = torch.randn(shape, dtype=torch.float64, generator=generator)
+        u = torch.rand(shape, dtype=torch.float64, generator=generator)
+        s = torch.rand(shape, dtype=torch.float64, generator=generator)
+        r = torch.randint(0, len(self.interpolation), shape, generator=generator)
+        level = (u * self.magnitude if self.mstd > 100 else self.magnitude + self.mstd * z).clamp(0.0, 10.0)
+        rec = np.zeros(shape + (RANDAUG_WORDS,), np.int32)
+        for i, j in zip(*np.nonzero((a < self.prob).numpy())):
+            op = RANDAUG_OPS[int(k[i, j])]
+            value = self._value(op, float(level[i, j]), bool(s[i, j] < 0.5), D)
+            rec[i, j] = randaug_record(op, value, D, self.interpolation[int(r[i, j])], self.fill)
+        return torch.from_numpy(rec)
+
+
 def _cuda_device(who, device):
     """The device of a transform: a CUDA device with its index resolved."""
     device = torch.device(device)
@@ -562,8 +706,11 @@ class GpuResizeNormalize:
         return self._sums[B]
 
     def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None, erase=None,
-                 color=None, contrast=True, blur=None):
+                 color=None, contrast=True, blur=None, randaug=None):
         S, D = self.src_size, self.out_size
+        if randaug is not None:
+            raise NotImplementedError("randaug is a stage of its own between the resize and the rest: use GpuWideResizeNormalize, which takes "
+                                      "any source side 8 .. 4 * D (CIFAR-size sources included)")
         if rrc is not None and aug is not None:
             raise ValueError("rrc and aug are mutually exclusive: the rrc record carries its own flip, and padding does not apply to a window")
         N, B, ip = _source_batch("GpuResizeNormalize", data_u8, index, S, S, self.device)
@@ -732,6 +879,40 @@ class GpuBytesBlurNormalize:
         return out
 
 
+class GpuBytesRandAugment:
+    """uint8 ``[B, D, D, 3]`` bytes on the device, at batch positions (what ``GpuWindowResize`` writes) -> uint8 ``[B, D, D, 3]``: per sample the
+    layers of its records (int32 ``[B, layers, 16]``, ``RandAugment.draw``'s; 1 .. 4 layers) applied in order, equal to Pillow's bytes, in one
+    launch of one workgroup per sample (``qatvit_image_bytes_randaug``).  The result and the stage's scratch image live
+    in two buffers this object owns, one pair per batch size, made on first use: no allocation per step and static addresses, so a captured
+    graph replays.  The input is never written."""
+
+    def __init__(self, out_size=224, device="cuda"):
+        self.out_size = int(out_size)
+        self.device = _cuda_device("GpuBytesRandAugment", device)
+        self._buffers = {}
+
+    def buffers(self, B):
+        """``(scratch, out)`` uint8 ``[B, D, D, 3]`` of a batch of B, made on first use and kept for the life of the transform."""
+        if B not in self._buffers:
+            self._buffers[B] = tuple(torch.empty(B, self.out_size, self.out_size, 3, dtype=torch.uint8, device=self.device) for _ in range(2))
+        return self._buffers[B]
+
+    def __call__(self, bytes_u8, records, out=None):
+        D = self.out_size
+        _, B, _ = _source_batch("GpuBytesRandAugment", bytes_u8, None, D, D, self.device)
+        if not isinstance(records, torch.Tensor) or records.dim() != 3 or not 1 <= records.shape[1] <= RANDAUG_MAX_LAYERS:
+            raise ValueError(f"randaug records must be an int32 [B, layers, {RANDAUG_WORDS}] tensor with 1 .. {RANDAUG_MAX_LAYERS} layers")
+        _check_records("randaug", records, (B, records.shape[1], RANDAUG_WORDS), self.device)
+        scratch, own = self.buffers(B)
+        out = own if out is None else _out_batch(out, torch.uint8, (B, D, D, 3), self.device)
+        if not B:
+            return out
+        with torch.cuda.device(self.device):
+            native.check(native.lib().qatvit_image_bytes_randaug(bytes_u8.data_ptr(), B, D, records.data_ptr(), records.shape[1], scratch.data_ptr(),
+                                                                 out.data_ptr(), native.stream_ptr()), "qatvit_image_bytes_randaug")
+        return out
+
+
 class GpuWideResizeNormalize:
     """Stands where a ``GpuResizeNormalize`` stands, for uint8 ``[N, H, W, 3]`` sources that are rectangles or larger than the output (up to
     ``4 * D`` on a side): two launches per batch.  Stage 1 (``GpuWindowResize``) writes the uint8 ``[B, D, D, 3]`` bytes of every sample's
@@ -744,7 +925,10 @@ class GpuWideResizeNormalize:
     ``GpuBytesBlurNormalize`` on the staged bytes (still two launches, plus the statistics launch that colour records with contrast bring),
     which is what ``GpuImageLoader(..., blur=GaussianBlur(...))`` and ``three_augment=ThreeAugment(...)`` need; ``mix`` with ``blur`` is
     refused by the library above D = 344.  Without the switch ``blur`` is refused as before: the one-launch blur forms keep source rows and
-    planes in LDS, and at S = D = 224 that is 89,536 bytes (98,272 with mix records), above the 65,536-byte cap."""
+    planes in LDS, and at S = D = 224 that is 89,536 bytes (98,272 with mix records), above the 65,536-byte cap.
+    ``randaug`` records (int32 ``[B, layers, 16]``, ``RandAugment.draw``'s) put a ``GpuBytesRandAugment`` between the two stages, one launch
+    more: the staged bytes go through every sample's layers, in front of ``color``, ``blur``, ``erase`` and ``mix``, where timm applies
+    RandAugment; its two buffers are made on the first such call.  A call without ``randaug`` issues the launches it issues without the keyword."""
 
     def __init__(self, src_size, out_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda", window=None, blur=False):
         self.stage = GpuWindowResize(src_size, out_size, device, window)
@@ -767,6 +951,12 @@ class GpuWideResizeNormalize:
     def color_sums(self, B):
         return self.inner.color_sums(B)
 
+    def randaug_stage(self):
+        """The ``GpuBytesRandAugment`` between the two stages, made on first use."""
+        if getattr(self, "_randaug", None) is None:
+            self._randaug = GpuBytesRandAugment(self.out_size, self.device)
+        return self._randaug
+
     def refuse(self, aug=None, blur=None):
         """Raises for what this object does not serve: ``aug`` always, ``blur`` unless it was made with ``blur=True`` (an object that never ran
         the constructor has the switch off)."""
@@ -777,12 +967,14 @@ class GpuWideResizeNormalize:
                                       f"they ask for 89,536 bytes, above the cap of {BLUR_LDS_CAP} bytes")
 
     def __call__(self, data_u8, index=None, out=None, aug=None, padding_mode="constant", fill=0, padding=None, mix=None, rrc=None, erase=None,
-                 color=None, contrast=True, blur=None):
+                 color=None, contrast=True, blur=None, randaug=None):
         self.refuse(aug, blur)                                       # padding_mode, fill and padding describe aug, which is refused: nothing reads them
         if not isinstance(data_u8, torch.Tensor) or not data_u8.is_cuda:
             raise RuntimeError("GpuWideResizeNormalize runs on MI355X only: move the uint8 images to the GPU")
         B = data_u8.shape[0] if index is None else index.shape[0]
         staged = self.stage(data_u8, index, rrc, out=self.staged(B))
+        if randaug is not None:
+            staged = self.randaug_stage()(staged, randaug)
         if blur is not None:
             return self.inner_blur(staged, out=out, mix=mix, erase=erase, color=color, contrast=contrast, blur=blur)
         return self.inner(staged, None, out=out, mix=mix, erase=erase, color=color, contrast=contrast)
@@ -820,10 +1012,13 @@ class GpuImageLoader:
     samples its coin picks inside the same launch: an epoch's blur records are drawn last of all, after the colour records, so that a seed
     gives the plan, words, windows, mix, erase and colour records it gives without ``blur``; they travel in the same copy, two int64 elements
     per sample.  ``three_augment`` (a ``ThreeAugment``) stands instead of ``color`` and ``blur`` and draws both kinds of record, where they
-    stand: DeiT-III's one-of-three choice and its colour jitter."""
+    stand: DeiT-III's one-of-three choice and its colour jitter.  ``rand_augment`` (a ``RandAugment``) needs a ``GpuWideResizeNormalize`` as
+    ``transform`` and applies every drawn sample's layers between its two stages: an epoch's records are drawn last of all, after every other
+    kind, and travel in the same copy, ``8 * num_layers`` int64 elements per sample."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle=False, sampler=None, drop_last=False, transform=None, generator=None, device="cuda",
-                 return_index=False, augment=None, mix=None, crop=None, erase=None, color=None, blur=None, three_augment=None):
+                 return_index=False, augment=None, mix=None, crop=None, erase=None, color=None, blur=None, three_augment=None,
+                 rand_augment=None):
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         data_u8, labels = torch.as_tensor(data_u8), torch.as_tensor(labels)
@@ -847,7 +1042,7 @@ class GpuImageLoader:
         self.return_index = bool(return_index)
         for name, v, cls in (("augment", augment, RandomCropFlip), ("mix", mix, MixupCutmix), ("crop", crop, RandomResizedCrop),
                              ("erase", erase, RandomErasing), ("color", color, ColorJitter), ("three_augment", three_augment, ThreeAugment),
-                             ("blur", blur, GaussianBlur)):
+                             ("blur", blur, GaussianBlur), ("rand_augment", rand_augment, RandAugment)):
             if v is None:
                 continue
             if not isinstance(v, cls):
@@ -856,9 +1051,12 @@ class GpuImageLoader:
                 raise ValueError(f"augment.padding {v.padding} exceeds S - 1 = {self.data.shape[1] - 1}")
             if name == "crop" and augment is not None:
                 raise ValueError("crop and augment are mutually exclusive: the crop's record carries its own flip, and padding does not apply")
+            if name == "rand_augment" and not wide:
+                raise NotImplementedError("rand_augment needs transform=GpuWideResizeNormalize(...): the stage stands between its two launches")
             if name == "three_augment" and (color is not None or blur is not None):
                 raise ValueError("three_augment is exclusive with color and blur: it draws both records itself")
         self.augment, self.mix, self.crop, self.erase, self.color, self.blur, self.three_augment = augment, mix, crop, erase, color, blur, three_augment
+        self.rand_augment = rand_augment
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else self.data.shape[0]
@@ -870,7 +1068,8 @@ class GpuImageLoader:
         if not plan:
             return
         flat = torch.cat(plan)
-        n, a, three = flat.shape[0], self.augment, self.three_augment
+        n, a, three, ra = flat.shape[0], self.augment, self.three_augment, self.rand_augment
+        ra_words = ra.num_layers * RANDAUG_WORDS if ra is not None else 0
         size = lambda: self.transform.out_size   # noqa: E731   (read only where a record kind needs it: a loader without options takes any callable)
         # The record kinds in drawing order, which is the order of their sections behind the n indices: (option, the keywords the transform takes
         # the records under, int32 words per sample of each, the draw: one tensor per keyword).  A seed gives the plan and the records of every
@@ -881,7 +1080,8 @@ class GpuImageLoader:
                  (self.erase, ("erase",), (ERASE_WORDS,), lambda: (self.erase.draw(n, size(), g),)),
                  (self.color, ("color",), (COLOR_WORDS,), lambda: (self.color.draw(n, g),)),
                  (self.blur, ("blur",), (BLUR_WORDS,), lambda: (self.blur.draw(n, g),)),
-                 (three, ("color", "blur"), (COLOR_WORDS, BLUR_WORDS), lambda: three.draw(n, g))]
+                 (three, ("color", "blur"), (COLOR_WORDS, BLUR_WORDS), lambda: three.draw(n, g)),
+                 (ra, ("randaug",), (ra_words,), lambda: (ra.draw(n, size(), g).view(n, ra_words),))]
         kinds = [k[1:] for k in kinds if k[0] is not None]
         # one pinned block and one asynchronous copy (the caching host allocator keeps the block until the copy has run): n int64 indices, then
         # every section's n * words int32 in whole int64 elements
@@ -916,6 +1116,8 @@ class GpuImageLoader:
             m = b.shape[0]
             idx, kw = order[o:o + m], dict(fixed, **{key: r[o:o + m] for key, r in records.items()})
             o += m
+            if ra is not None:
+                kw["randaug"] = kw["randaug"].view(m, ra.num_layers, RANDAUG_WORDS)
             x = self.transform(self.data, idx, **kw)
             tail = (idx,) if self.return_index else ()
             yield (x, self.labels.index_select(0, idx)) + tail + ((kw["mix"],) if self.mix is not None else ())
