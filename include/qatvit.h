@@ -1061,6 +1061,39 @@ int qatvit_eval_accumulate(const void* logits, int32_t dtype, int64_t ld, const 
                            const float* other, int64_t other_ld, const int64_t* other_index, int64_t other_rows, void* state,
                            int64_t* confusion, void* stream);
 
+/* Validation at many classes: the RANK of the label among a row's logits, from whose histogram every top-k follows, the label-smoothed
+ * cross-entropy, and per-class counts in 16 * C bytes instead of the [C, C] matrix.  A second, CLASS-PARALLEL entry (a row's classes are spread over
+ * one wave up to 1024 classes, over one workgroup above); qatvit_eval_accumulate is unchanged and the two can run on the same batch.
+ * logits, dtype, ld, labels, other, other_ld, other_index, other_rows and stream mean exactly what they mean for qatvit_eval_accumulate; fp16 / bf16
+ * values are widened exactly to fp32.  1 <= B < 2^30, 2 <= C <= 32768, 0 <= label_smoothing < 1; anything else is refused before any HIP call.
+ * One total order on (value, index) candidates, the one behind qatvit_eval_accumulate's pred: a NaN beats a number, a larger number beats a smaller
+ * one, +0 == -0, and among equals (two NaNs included) the lower index wins.  Per row:
+ *   rank = the number of columns whose candidate beats the label's candidate (x[label], label): the columns with a larger value, plus the columns
+ *     with an EQUAL value at a LOWER index.  rank == 0 exactly when torch.argmax's answer is the label.  A label whose value is NaN is beaten only
+ *     by NaNs at lower indices.  rank_hist[min(rank, 31)] += 1: top-k for any k <= 31 is the sum of the first k bins over the valid labels, bin 31
+ *     collects every rank from 31 up.  This TIE RULE is the argmax order: a label tied with other columns counts as inside the top k only if fewer
+ *     than k columns are larger or equal-and-earlier.  torch.topk documents no tie rule; on rows without ties the two agree.
+ *   L = log(sum_c exp(x_c - m)) - (1 - eps) (x_label - m) - (eps / C) sum_c (x_c - m), m the row's largest number, all in fp32 (the last term
+ *     is left out when eps == 0: then L is qatvit_eval_accumulate's CE in another summation order).  A finite L is added to loss_sum and counted in
+ *     loss_rows, any other in nonfinite_rows.  A NaN, a +inf or an all -inf row is non-finite; with eps > 0 so is a row with any -inf element,
+ *     as for torch's cross_entropy(label_smoothing=eps); with eps == 0 a -inf away from the label is harmless.
+ *   A label outside [0, C) is counted in bad_labels and takes no part in anything else; nothing is read or written through it.
+ *   class_counts (int64 [2, C], zeroed by the caller, or NULL): class_counts[label] += 1 for every valid label, class_counts[C + label] += 1 when
+ *     rank == 0: per-class recall.
+ *   other: the rank of the label in the other row goes to other_rank_hist (valid labels only), same bins; agree counts the rows where the two
+ *     argmaxes are equal (labels play no part); other_rows_seen and bad_index as for qatvit_eval_accumulate.
+ * state: QATVIT_EVAL_RANK_STATE_WORDS 8-byte words, 8-byte aligned, that the caller zeroes once per evaluation and every call ADDS to:
+ *   int64 [0] total [1] bad_labels [2] nonfinite_rows [3] loss_rows [4] other_rows_seen [5] agree [6] bad_index [7] zero, double [8] loss_sum,
+ *   [9] zero, int64 [10..41] rank_hist, [42..73] other_rank_hist.  The integer counts are exact and do not depend on launch or block order;
+ *   loss_sum is accumulated in double in arrival order, so its last bits can differ between runs.  One launch, nothing synchronises with the host.
+ */
+#define QATVIT_EVAL_RANK_BINS 32
+#define QATVIT_EVAL_RANK_STATE_WORDS 74
+int qatvit_eval_accumulate_rank(const void* logits, int32_t dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes,
+                                float label_smoothing,
+                                const float* other, int64_t other_ld, const int64_t* other_index, int64_t other_rows,
+                                void* state, int64_t* class_counts, void* stream);
+
 /* Measurement hooks (bench.py): bracket every launch of one GEMM class inside the steps of ONE engine - identified by its workspace
  * pointer, so engines in the same process do not see each other's sessions - with HIP events on the launch stream.
  * kind: 1 = NT with split (hi+lo) A operand and the plain epilogue (proj / fc2 forward, proj dgrad), 2 = NT with grid A operand on int8 MFMA, plain

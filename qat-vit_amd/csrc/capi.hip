@@ -536,6 +536,30 @@ int qatvit_eval_accumulate(const void* logits, int32_t dtype, int64_t ld, const 
     return 0;
 }
 
+int qatvit_eval_accumulate_rank(const void* logits, int32_t dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes,
+                                float label_smoothing, const float* other, int64_t other_ld, const int64_t* other_index, int64_t other_rows,
+                                void* state, int64_t* class_counts, void* stream) {
+    static_assert(QATVIT_EVAL_RANK_BINS == kEvalRankBins && QATVIT_EVAL_RANK_STATE_WORDS == kEvalRankWords, "qatvit.h mirrors the rank state block");
+    QV_CHECK_ARG(logits && labels && state, "qatvit_eval_accumulate_rank: null pointer argument");
+    QV_CHECK_ARG(batch >= 1 && batch < (1ll << 30), "qatvit_eval_accumulate_rank: batch %lld (1 .. 2^30 - 1)", (long long)batch);
+    QV_CHECK_ARG(classes >= 2 && classes <= 32768, "qatvit_eval_accumulate_rank: classes %lld (2 .. 32768)", (long long)classes);
+    QV_CHECK_ARG(ld >= classes, "qatvit_eval_accumulate_rank: ld %lld is less than classes %lld", (long long)ld, (long long)classes);
+    QV_CHECK_ARG(dtype == QATVIT_EVAL_F32 || dtype == QATVIT_EVAL_F16 || dtype == QATVIT_EVAL_BF16,
+                 "qatvit_eval_accumulate_rank: unknown dtype code %d (0 = fp32, 1 = fp16, 2 = bf16)", dtype);
+    QV_CHECK_ARG(label_smoothing >= 0.f && label_smoothing < 1.f, "qatvit_eval_accumulate_rank: label_smoothing %g is outside [0, 1)",
+                 (double)label_smoothing);
+    QV_CHECK_ARG(other || !other_index, "qatvit_eval_accumulate_rank: other_index given without other");
+    QV_CHECK_ARG(!other || other_ld >= classes, "qatvit_eval_accumulate_rank: other_ld %lld is less than classes %lld", (long long)other_ld,
+                 (long long)classes);
+    QV_CHECK_ARG(!other_index || other_rows >= 1, "qatvit_eval_accumulate_rank: other_rows %lld (at least 1 with an index)", (long long)other_rows);
+    QV_CHECK_ARG(((uintptr_t)state & 7) == 0 && ((uintptr_t)class_counts & 7) == 0, "qatvit_eval_accumulate_rank: misaligned state or class_counts pointer");
+    if (launch_eval_rank(logits, dtype, ld, labels, batch, classes, label_smoothing, other, other_ld, other_index, other_rows, state, class_counts,
+                         (hipStream_t)stream))
+        return 1;
+    QV_CHECK_LAUNCH("qatvit_eval_accumulate_rank");
+    return 0;
+}
+
 static int image_shape_ok(const char* who, int32_t S, int32_t D) {
     QV_CHECK_ARG(S >= 8 && S <= D, "%s: source size %d is outside 8 .. output size %d (downscaling is not supported)", who, S, D);
     QV_CHECK_ARG(D % 4 == 0 && D <= kImgMaxD, "%s: output size %d must be a multiple of 4, at most %d", who, D, kImgMaxD);

@@ -488,6 +488,13 @@ static_assert(sizeof(EvalState) == 8 * (kEvalCounters + 1), "EvalState is ten 8-
 // dtype: 0 fp32, 1 fp16, 2 bf16 (anything else returns 1 without a launch); other / other_index / confusion may be null
 int launch_eval_accumulate(const void* logits, int dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes, const float* other,
                            int64_t other_ld, const int64_t* other_index, int64_t other_rows, EvalState* state, int64_t* confusion, hipStream_t st);
+// eval_rank.hip: validation at many classes.  Its state block is kEvalRankWords 8-byte words that every launch ADDS to (include/qatvit.h lists them):
+// seven int64 counters and a zero word, the double loss sum and a zero word, then two histograms of kEvalRankBins bins of the label's rank - in
+// the logits and in the second opinion - the last bin collecting every rank from kEvalRankBins - 1 up.  class_counts: int64 [2, C] or null.
+constexpr int kEvalRankBins = 32, kEvalRankWords = 10 + 2 * kEvalRankBins;
+int launch_eval_rank(const void* logits, int dtype, int64_t ld, const int64_t* labels, int64_t batch, int64_t classes, float label_smoothing,
+                     const float* other, int64_t other_ld, const int64_t* other_index, int64_t other_rows, void* state, int64_t* class_counts,
+                     hipStream_t st);
 // grid of the float step's flat elementwise kernels (float_step.hip, float_amp.hip)
 inline int flat_grid_fs(int64_t n) {
     int64_t b = (n + 255) / 256;

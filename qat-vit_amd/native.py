@@ -132,6 +132,8 @@ SIGNATURES = {
     "qatvit_image_bytes_blur": (c_int, [c_void_p, c_int32, c_int32] + [c_void_p] * 8),
     "qatvit_image_bytes_randaug": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "qatvit_eval_accumulate": (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "qatvit_eval_accumulate_rank": (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int64, c_float, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                            c_void_p, c_void_p]),
     "qatvit_profile_start": (c_int, [c_void_p, c_int32, c_int32]),
     "qatvit_profile_stop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }
