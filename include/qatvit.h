@@ -164,6 +164,39 @@ int qatvit_kd_ce_loss_rows(const float* student, const float* teacher, const flo
                            const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
                            float label_smoothing, float* partials, float* out3, float* dlogits, void* stream);
 
+/* The COMPRESSED teacher table: per sample the teacher's k largest logits and one logit for all the others, instead of fp32 [C].
+ * Row format, for a dense row t[0..C), 1 <= k <= min(64, C - 1) and a build temperature Tb > 0:
+ *   idx   int16 [k]  the classes of the k largest logits in descending value; equal values lower class first (-0 == +0): the order of
+ *                    qatvit_eval_accumulate_rank's argmax
+ *   val   fp32 [k]   val[e] = t[idx[e]], the bits copied
+ *   tail  fp32       u = m + Tb * (log S - log(C - k)),  m = the row's maximum,  S = max(FLT_MIN, sum over the classes NOT in idx of
+ *                    expf((t[c] - m) / Tb)): the logit that, given to every tail class, keeps the tail's softmax mass at temperature Tb and
+ *                    spreads it uniformly.  All fp32, every operation rounded on its own; the difference of the logarithms is evaluated as
+ *                    logf(S / (float)(C - k)), one rounding of a logarithm instead of two at a several times larger magnitude.
+ * DECOMPRESSION of a row is the dense row r[c] = val[e] where c == idx[e], u elsewhere; an idx entry outside [0, C) is ignored, of entries with
+ * the same class the later one counts.
+ *
+ * qatvit_teacher_topk_rows compresses logits fp32 [batch, classes] into idx [batch, k], val [batch, k], tail [batch] (contents on entry ignored).
+ * The logits are finite; a row that holds a NaN gives idx = 0 .. k - 1 and NaN in val and tail.  1 <= batch < 2^30, 2 <= classes <= 32768;
+ * logits, val, tail 4-byte and idx 2-byte aligned.  One launch on `stream`: one wave of 64 lanes per row (4 rows per workgroup) up to 1024 classes,
+ * one workgroup per row above; the row is read from global memory once, into registers or into LDS.  S is added thread by thread over the classes
+ * t, t + 64 (1024), ... in ascending order, then over the lanes by butterflies and over the workgroup's waves in ascending order.  No atomics, no
+ * zeroed state: the same inputs give the same bits.
+ *
+ * qatvit_kd_ce_loss_topk is qatvit_kd_ce_loss_rows with such a table (idx [table_rows, k], val [table_rows, k], tail [table_rows]) in the place
+ * of `table`, and is DEFINED as that entry on the decompressed rows, for any kd_temp (at kd_temp == Tb the KD target's tail is uniform with the
+ * teacher's tail mass) and for mix records (the rows of a sample and its partner are decompressed, then mixed as qatvit_kd_ce_loss_mix states).
+ * index is required; mix NULL or 4-byte aligned; the other arguments, the NaN rows of an index outside [0, table_rows) and of a NaN logit, partials
+ * and out3 are qatvit_kd_ce_loss_rows'.  The kernel decompresses a row in LDS, never in global memory, and keeps qatvit_kd_ce_loss_rows' ownership
+ * of the classes, its expressions and its summation order: out3 and dlogits equal that entry's on the decompressed table BIT FOR BIT.
+ * Two launches on `stream`, no atomics, no zeroed state.
+ */
+int qatvit_teacher_topk_rows(const float* logits, int64_t batch, int64_t classes, int32_t k, float build_temp, int16_t* idx, float* val, float* tail,
+                             void* stream);
+int qatvit_kd_ce_loss_topk(const float* student, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int32_t k,
+                           const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                           float kd_alpha, float label_smoothing, float* partials, float* out3, float* dlogits, void* stream);
+
 /* ===========================================================================
  * Building blocks of the step, exported for kernel-level parity tests.
  * All matrices row-major; "bf16" = IEEE bfloat16 bit patterns (uint16).

@@ -17,8 +17,8 @@ from .optim import ClipAdamW, ClipLamb, ema_warmup_decay, vit_param_groups  # no
 from .data import ColorJitter, GaussianBlur, ThreeAugment, GpuImageLoader, GpuResizeNormalize, MixupCutmix, RandomCropFlip, RandomErasing, RandomResizedCrop, cifar10_arrays, epoch_batches  # noqa: F401,E402
 from .data import GpuBytesBlurNormalize, GpuWideResizeNormalize, GpuWindowResize, center_crop_window  # noqa: F401,E402
 from .data import GpuBytesRandAugment, RandAugment  # noqa: F401,E402
-from .distill import TeacherLogitTable  # noqa: F401,E402
+from .distill import TeacherLogitTable, TeacherTopKTable  # noqa: F401,E402
 from .evaluate import EvalAccumulator, EvalResult, evaluate  # noqa: F401,E402
 from .loss import BinaryCrossEntropy  # noqa: F401,E402
 
-__all__ = ["BinaryCrossEntropy", "DropPath", "LayerScale", "forced_drop_path", "EvalAccumulator", "EvalResult", "evaluate", "TeacherLogitTable", "native_float", "ClipAdamW", "ClipLamb", "ema_warmup_decay", "vit_param_groups", "ColorJitter", "GaussianBlur", "ThreeAugment", "GpuImageLoader", "GpuResizeNormalize", "GpuBytesBlurNormalize", "GpuWideResizeNormalize", "GpuWindowResize", "center_crop_window", "GpuBytesRandAugment", "RandAugment", "MixupCutmix", "RandomCropFlip", "RandomErasing", "RandomResizedCrop", "cifar10_arrays", "epoch_batches", "Int8Student", "export_int8", "import_int8", "PLATFORM", "QATWrapper", "create_model", "create_student", "create_teacher", "list_available_models", "register_model"]
+__all__ = ["BinaryCrossEntropy", "DropPath", "LayerScale", "forced_drop_path", "EvalAccumulator", "EvalResult", "evaluate", "TeacherLogitTable", "TeacherTopKTable", "native_float", "ClipAdamW", "ClipLamb", "ema_warmup_decay", "vit_param_groups", "ColorJitter", "GaussianBlur", "ThreeAugment", "GpuImageLoader", "GpuResizeNormalize", "GpuBytesBlurNormalize", "GpuWideResizeNormalize", "GpuWindowResize", "center_crop_window", "GpuBytesRandAugment", "RandAugment", "MixupCutmix", "RandomCropFlip", "RandomErasing", "RandomResizedCrop", "cifar10_arrays", "epoch_batches", "Int8Student", "export_int8", "import_int8", "PLATFORM", "QATWrapper", "create_model", "create_student", "create_teacher", "list_available_models", "register_model"]

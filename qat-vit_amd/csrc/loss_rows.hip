@@ -10,46 +10,11 @@
 //     stage in the fixed order (0 + 1) + (2 + 3), so every wave derives the same m and log z.  Writes the row's {sum_c ce terms, KD} to partials[2 * b].
 //   k_kd_bce_finish (bce.hip, unedited) then forms out3 from the partials with scale = 1 / B, in double, in one fixed order.
 // The form is chosen from C alone: a row's dlogits bits depend on the row, its partner, C and 1 / B only.  Two launches, no atomics, no zeroed state.
+#include "loss_rows.h"
 #include "qv_common.h"
 #include "qv_kernels.h"
 
 namespace qv {
-
-static constexpr int kRowsWaveMaxC = 1024, kRowsRegMaxC = 4096;
-
-// One value per wave -> the row's value in every thread.  NT = 64: the butterfly alone.  NT = 256: lane 0 of each wave stores its K values, one barrier,
-// every thread combines the four in one order.  STAGE names the LDS array: each reduction of a kernel has its own, so one barrier per stage is enough.
-template <int NT, int STAGE, bool MAX, int K>
-__device__ __forceinline__ void row_reduce(float (&v)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = MAX ? wave_max(v[k]) : wave_sum(v[k]);
-    if constexpr (NT > 64) {
-        static_assert(NT == 256, "four waves");
-        __shared__ float sh[4][K];
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) sh[threadIdx.x >> 6][k] = v[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            v[k] = MAX ? fmaxf(fmaxf(sh[0][k], sh[1][k]), fmaxf(sh[2][k], sh[3][k])) : (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
-    }
-}
-
-// f(j, c) for every class c = t + NT * j this thread owns: NPL > 0 unrolled over the register slots, NPL = 0 a loop (j stays 0)
-template <int NT, int NPL, class F>
-__device__ __forceinline__ void for_owned(int t, int C, F f) {
-    if constexpr (NPL > 0) {
-#pragma unroll
-        for (int j = 0; j < NPL; ++j) {
-            const int c = t + NT * j;
-            if (c < C) f(j, c);
-        }
-    } else {
-        for (int c = t; c < C; c += NT) f(0, c);
-    }
-}
 
 template <int NT, int NPL>
 __global__ __launch_bounds__(256) void k_kd_ce_rows(const float* __restrict__ s, const float* __restrict__ t, const float* __restrict__ table,

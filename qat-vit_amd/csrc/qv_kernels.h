@@ -39,6 +39,15 @@ int launch_kd_ce_loss_rows(const float* student, const float* teacher, const flo
                            const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
                            float label_smoothing, float* partials, float* out3, float* dlogits, hipStream_t st);
 
+// ---- teacher_topk.hip: the compressed teacher table (include/qatvit.h states the row format).  Rows of logits [batch, classes] -> idx int16 [batch, k],
+// val fp32 [batch, k], tail fp32 [batch] (one launch; nonzero + set_error where the dynamic LDS limit cannot be raised); and launch_kd_ce_loss_rows'
+// table form reading such a table, its rows decompressed in LDS (two launches, the same bits as the dense entry on the decompressed rows)
+int launch_teacher_topk_rows(const float* logits, int64_t batch, int64_t classes, int k, float build_temp, int16_t* idx, float* val, float* tail,
+                             hipStream_t st);
+int launch_kd_ce_loss_topk(const float* student, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int k, const int64_t* index,
+                           const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                           float label_smoothing, float* partials, float* out3, float* dlogits, hipStream_t st);
+
 // ---- fq.hip (engine pieces)
 int launch_minmax(const float* x, int64_t channels, int64_t inner, int per_channel, uint32_t* ws, int nslots, hipStream_t st);
 int launch_ws_init(uint32_t* ws, int64_t slots, hipStream_t st);

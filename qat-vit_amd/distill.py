@@ -1,4 +1,5 @@
-"""Distillation from a per-sample table of teacher logits (libqatvit.so: qatvit_kd_ce_loss_table).
+"""Distillation from a per-sample table of teacher logits (libqatvit.so: qatvit_kd_ce_loss_table), dense
+(``TeacherLogitTable``) or compressed to the k largest logits of a row and one tail logit (``TeacherTopKTable``, at the end of this file; section 7zd).
 
 The reference loop feeds its frozen teacher un-augmented images (Resize + ToTensor + Normalize, nothing random), so the teacher's logits for
 image i are the same in every epoch and in every search trial.  ``TeacherLogitTable.build`` runs the native teacher forward once over the data set
@@ -219,3 +220,176 @@ class TeacherLogitTable:
             same("teacher_form", teacher_form(teacher))
             same("param_digest", param_digest(teacher))
         return cls(logits.to(device).contiguous(), meta, teacher)
+
+
+TOPK_FORMAT = 101
+TOPK_FIELDS = FIELDS + ("k", "tail_temp")
+
+
+class TeacherTopKTable:
+    """The compressed form of a ``TeacherLogitTable`` (libqatvit.so: qatvit_teacher_topk_rows, qatvit_kd_ce_loss_topk): per
+    sample the teacher's ``k`` largest logits (``idx`` int16 ``[N, k]``, ``val`` fp32 ``[N, k]``, descending) and one logit ``tail`` (fp32 ``[N]``)
+    for every other class, which keeps the tail's softmax mass at the temperature ``tail_temp`` the table was built with - ``6 k + 4`` bytes per sample
+    instead of ``4 C``.  ``loss`` is, bit for bit, ``TeacherLogitTable.loss(..., class_parallel=True)`` on the decompressed rows ``rows`` returns.
+    A table is valid under the same conditions as a dense one, and its record holds ``k`` and ``tail_temp`` as well."""
+
+    def __init__(self, idx: torch.Tensor, val: torch.Tensor, tail: torch.Tensor, meta: dict, teacher=None):
+        if idx.dim() != 2 or idx.dtype != torch.int16 or val.dtype != torch.float32 or tail.dtype != torch.float32 or val.shape != idx.shape \
+                or tail.shape != idx.shape[:1] or not (idx.is_contiguous() and val.is_contiguous() and tail.is_contiguous()):
+            raise ValueError("idx, val and tail must be contiguous int16 [N, k], fp32 [N, k] and fp32 [N] tensors")
+        missing = [f for f in TOPK_FIELDS if f not in meta]
+        if missing:
+            raise ValueError(f"table record lacks {missing}")
+        if (int(meta["N"]), int(meta["k"])) != tuple(idx.shape):
+            raise ValueError(f"table record says [{meta['N']}, {meta['k']}], the entries are {tuple(idx.shape)}")
+        if not 1 <= int(meta["k"]) <= min(64, int(meta["C"]) - 1) or not 2 <= int(meta["C"]) <= 32768 or not float(meta["tail_temp"]) > 0:
+            raise ValueError(f"table record: k {meta['k']}, C {meta['C']}, tail_temp {meta['tail_temp']} (1 <= k <= min(64, C - 1), 2 <= C <= 32768, tail_temp > 0)")
+        self.idx, self.val, self.tail = idx, val, tail
+        self.meta = dict(meta)
+        self._teacher = weakref.ref(teacher) if teacher is not None else None
+        self._teacher_versions = _versions(teacher) if teacher is not None else None
+
+    N = property(lambda self: self.idx.shape[0])
+    C = property(lambda self: int(self.meta["C"]))
+    k = property(lambda self: self.idx.shape[1])
+    tail_temp = property(lambda self: float(self.meta["tail_temp"]))
+    device = property(lambda self: self.idx.device)
+    nbytes = property(lambda self: sum(t.numel() * t.element_size() for t in (self.idx, self.val, self.tail)))
+
+    def __len__(self):
+        return self.idx.shape[0]
+
+    @staticmethod
+    def describe(teacher, data_u8, transform, k, kd_temp, labels=None, form=None) -> dict:
+        """``TeacherLogitTable.describe`` plus ``k`` and ``tail_temp``, under this class's format number."""
+        return dict(TeacherLogitTable.describe(teacher, data_u8, transform, labels, form), format=TOPK_FORMAT, k=int(k), tail_temp=float(kd_temp))
+
+    @classmethod
+    def build(cls, teacher, data_u8, transform=None, k=32, kd_temp=4.0, batch_size=256, labels=None):
+        """``TeacherLogitTable.build`` with every chunk compressed as the teacher forward writes it: the peak is one ``[batch_size, C]`` chunk of
+        logits and the compressed table, never ``[N, C]``."""
+        from .teacher import _ENGINES, teacher_forward
+        from .vit import _native_teacher_ok
+
+        data_u8 = torch.as_tensor(data_u8)
+        if not data_u8.is_cuda:
+            raise RuntimeError("TeacherTopKTable.build runs on MI355X only: move the uint8 images to the GPU (there is no CPU fallback)")
+        params = native.vit_params(teacher)
+        if layer_scale_params(teacher):
+            raise RuntimeError("TeacherTopKTable.build: the native teacher forward does not cover a LayerScale teacher (its stock module forward does)")
+        if any(not p.is_cuda for p in params):
+            raise RuntimeError("TeacherTopKTable.build runs on MI355X only: move the teacher to the GPU (there is no CPU fallback)")
+        if any(p.requires_grad for p in teacher.parameters()):
+            raise RuntimeError("TeacherTopKTable.build: the teacher has parameters that require grad; a table is only valid for a frozen teacher "
+                               "(set requires_grad = False on its parameters, as the reference loop does)")
+        if not _native_teacher_ok(teacher):
+            raise RuntimeError("TeacherTopKTable.build: this teacher has no native forward (vit._native_teacher_ok); there is no fallback")
+        batch_size, k = int(batch_size), int(k)
+        if batch_size < 1 or data_u8.shape[0] < 1:
+            raise ValueError("batch_size and the number of images must be at least 1")
+        if transform is None:
+            transform = GpuResizeNormalize(data_u8.shape[1], device=data_u8.device)
+        dev = transform.device
+        N, C = data_u8.shape[0], teacher.head.weight.shape[0]
+        chunks = (N + batch_size - 1) // batch_size
+        idx = torch.empty(chunks * batch_size, k, dtype=torch.int16, device=dev)
+        val = torch.empty(chunks * batch_size, k, dtype=torch.float32, device=dev)
+        tail = torch.empty(chunks * batch_size, dtype=torch.float32, device=dev)
+        chunk = torch.empty(batch_size, C, dtype=torch.float32, device=dev)
+        order = torch.arange(chunks * batch_size, dtype=torch.int64, device=dev).clamp_(max=N - 1)
+        images = torch.empty(batch_size, 3, transform.out_size, transform.out_size, dtype=torch.float32, device=dev)
+        flags = [(m, m.training) for m in teacher.modules()]
+        teacher.eval()
+        try:
+            with torch.no_grad(), torch.cuda.device(dev):
+                for j in range(chunks):
+                    rows = slice(j * batch_size, (j + 1) * batch_size)
+                    teacher_forward(teacher, transform(data_u8, order[rows], out=images), out=chunk)
+                    native.check(native.lib().qatvit_teacher_topk_rows(chunk.data_ptr(), batch_size, C, k, float(kd_temp), idx[rows].data_ptr(),
+                                                                       val[rows].data_ptr(), tail[rows].data_ptr(), native.stream_ptr()),
+                                 "qatvit_teacher_topk_rows")
+        finally:
+            for m, t in flags:
+                m.training = t
+        form = _ENGINES[teacher].passes   # the form that ran
+        meta = cls.describe(teacher, data_u8, transform, k, kd_temp, labels, form)
+        return cls(idx[:N].contiguous(), val[:N].contiguous(), tail[:N].contiguous(), meta, teacher)
+
+    @classmethod
+    def from_dense(cls, table_or_logits, k=32, kd_temp=4.0, batch_size=4096):
+        """The compressed form of a ``TeacherLogitTable`` (its record and freshness watch are taken over) or of a plain fp32 ``[N, C]`` tensor of
+        logits on the device (an empty record), ``batch_size`` rows per launch."""
+        dense = table_or_logits
+        if isinstance(dense, TeacherLogitTable):
+            dense.check_fresh()
+            logits, meta, teacher = dense.logits, dict(dense.meta), dense._teacher() if dense._teacher is not None else None
+        else:
+            logits, teacher = dense, None
+            meta = {"N": int(dense.shape[0]), "C": int(dense.shape[1]), "teacher_form": 0, "transform": (), "data_digest": "", "param_digest": ""}
+        parts = [F.teacher_topk(logits[r:r + batch_size], k, kd_temp) for r in range(0, logits.shape[0], batch_size)]
+        idx, val, tail = (torch.cat(p) for p in zip(*parts))
+        return cls(idx, val, tail, dict(meta, format=TOPK_FORMAT, k=int(k), tail_temp=float(kd_temp)), teacher)
+
+    def check_fresh(self) -> None:
+        """Raises when a parameter of the teacher this table was built from (or loaded against) has been replaced or modified in place since."""
+        t = self._teacher() if self._teacher is not None else None
+        if t is not None and _versions(t) != self._teacher_versions:
+            raise RuntimeError("TeacherTopKTable: a teacher parameter was replaced or modified after the table was built; the rows no longer are this "
+                               "teacher's logits - build the table again")
+
+    def _need_device(self, what):
+        if not self.idx.is_cuda:
+            raise RuntimeError(f"TeacherTopKTable.{what}: qat-vit_amd ops run on MI355X only (the table is on {self.idx.device}); there is no CPU fallback")
+
+    def rows(self, index: torch.Tensor) -> torch.Tensor:
+        """The DECOMPRESSED ``[len(index), C]`` rows of the samples `index`, from torch ops: ``tail`` everywhere, then the entries in order, so of
+        two entries with one class the later counts; an entry outside ``[0, C)`` is left out.  For callers with a loss of their own, and tests."""
+        self.check_fresh()
+        cls_ = self.idx.index_select(0, index).long()
+        val, dense = self.val.index_select(0, index), self.tail.index_select(0, index)[:, None].repeat(1, self.C)
+        at = torch.arange(index.shape[0], device=index.device)
+        for e in range(self.k):
+            ok = (cls_[:, e] >= 0) & (cls_[:, e] < self.C)
+            dense[at[ok], cls_[ok, e]] = val[ok, e]
+        return dense
+
+    def loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None):
+        """``TeacherLogitTable.loss(..., class_parallel=True)`` on the decompressed rows, which never exist in global memory (``F.kd_ce_loss_topk``):
+        (loss, [loss, ce, kd*T^2]).  At ``kd_temp == tail_temp`` the KD target's tail is uniform with the teacher's tail mass."""
+        self._need_device("loss")
+        self.check_fresh()
+        return F.kd_ce_loss_topk(student_logits, self.idx, self.val, self.tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
+
+    def save(self, path) -> None:
+        torch.save({"idx": self.idx.detach().cpu(), "val": self.val.detach().cpu(), "tail": self.tail.detach().cpu(), "meta": self.meta}, path)
+
+    @classmethod
+    def load(cls, path, teacher=None, data_u8=None, transform=None, labels=None, device="cuda", k=None, tail_temp=None, C=None):
+        """The table saved at `path`, on `device`.  Whatever is given of the teacher, the data, the transform, ``k``, ``tail_temp`` and ``C`` is
+        compared with the table's record; a difference raises a ValueError that names the field."""
+        blob = torch.load(path, map_location="cpu", weights_only=True)
+        meta = blob["meta"]
+        if meta.get("format") != TOPK_FORMAT:
+            raise ValueError(f"{path}: table format {meta.get('format')!r}, this version reads {TOPK_FORMAT}")
+
+        def same(field, have):
+            if meta[field] != have:
+                raise ValueError(f"{path}: {field} differs: the table was built with {meta[field]!r}, got {have!r}")
+
+        if k is not None:
+            same("k", int(k))
+        if tail_temp is not None:
+            same("tail_temp", float(tail_temp))
+        if C is not None:
+            same("C", int(C))
+        if data_u8 is not None:
+            data_u8 = torch.as_tensor(data_u8)
+            same("N", int(data_u8.shape[0]))
+            same("data_digest", data_digest(data_u8, labels))
+        if transform is not None:
+            same("transform", transform_tuple(transform))
+        if teacher is not None:
+            same("C", int(teacher.head.weight.shape[0]))
+            same("teacher_form", teacher_form(teacher))
+            same("param_digest", param_digest(teacher))
+        return cls(*(blob[f].to(device).contiguous() for f in ("idx", "val", "tail")), meta, teacher)

@@ -309,6 +309,63 @@ def kd_ce_loss_table_mix(student, table, index, labels, mix, kd_temp=4.0, kd_alp
     return _KDCELossMixFn.apply(student, None, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
 
 
+def teacher_topk(logits, k, kd_temp=4.0):
+    """Teacher logits fp32 ``[B, C]`` -> the compressed rows ``(idx int16 [B, k], val fp32 [B, k], tail fp32 [B])`` of ``qatvit_teacher_topk_rows``:
+    the k largest logits of a row in descending order (equal values lower class first) and the one logit ``tail`` that every other class is given, which
+    keeps the tail's softmax mass at temperature ``kd_temp``.  ``1 <= k <= min(64, C - 1)``, ``2 <= C <= 32768``."""
+    _need_cuda(logits, "teacher_topk")
+    if logits.dim() != 2:
+        raise RuntimeError(f"teacher_topk: the logits must be [B, C], got {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    B, C = logits.shape
+    idx = torch.empty(B, int(k), dtype=torch.int16, device=logits.device)
+    val = torch.empty(B, int(k), dtype=torch.float32, device=logits.device)
+    tail = torch.empty(B, dtype=torch.float32, device=logits.device)
+    native.check(native.lib().qatvit_teacher_topk_rows(logits.data_ptr(), B, C, int(k), float(kd_temp), idx.data_ptr(), val.data_ptr(), tail.data_ptr(),
+                                                       native.stream_ptr()), "qatvit_teacher_topk_rows")
+    return idx, val, tail
+
+
+class _KDCELossTopKFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, student, idx, val, tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing):
+        who = "kd_ce_loss_topk"
+        student, (_, _, _, lptr, mptr), _, keep = _kd_ce_operands(who, student, None, None, None, labels, mix)
+        (B, C), dev = student.shape, student.device
+        rows, k = (idx.shape[0], idx.shape[1]) if idx.dim() == 2 else (0, 0)
+        for name, t, dtype, shape in (("idx", idx, torch.int16, (rows, k)), ("val", val, torch.float32, (rows, k)), ("tail", tail, torch.float32, (rows,))):
+            if t.dtype != dtype or tuple(t.shape) != shape or rows < 1 or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f"{who}: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        index = index.contiguous()
+        if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev:
+            raise RuntimeError(f"{who}: index must be an int64 [{B}] tensor on {dev}")
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        partials = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        dlogits = torch.empty_like(student)
+        native.check(
+            native.lib().qatvit_kd_ce_loss_topk(student.data_ptr(), idx.data_ptr(), val.data_ptr(), tail.data_ptr(), rows, k, index.data_ptr(), lptr, mptr,
+                                                B, C, float(kd_temp), float(kd_alpha), float(label_smoothing), partials.data_ptr(), out3.data_ptr(),
+                                                dlogits.data_ptr(), native.stream_ptr()),
+            "qatvit_kd_ce_loss_topk",
+        )
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(out3)
+        return out3[0], out3
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * dloss,) + (None,) * 9
+
+
+def kd_ce_loss_topk(student, idx, val, tail, index, labels, mix=None, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+    """``kd_ce_loss_table_mix(student, rows, index, labels, mix, ..., class_parallel=True)`` with ``rows`` the decompression of the compressed table
+    ``(idx, val, tail)`` (``teacher_topk``; distill.TeacherTopKTable) - bit for bit, without the dense rows ever existing in global memory: the kernel
+    decompresses the rows of a sample and, where ``lam != 1``, of its partner in LDS.  Returns (loss, [loss, ce, kd*T^2]); an index outside the
+    table makes the loss and that row of the gradient NaN."""
+    return _KDCELossTopKFn.apply(student, idx, val, tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
+
+
 class _KDBCELossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes):
