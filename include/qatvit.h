@@ -197,6 +197,39 @@ int qatvit_kd_ce_loss_topk(const float* student, const int16_t* idx, const float
                            const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
                            float kd_alpha, float label_smoothing, float* partials, float* out3, float* dlogits, void* stream);
 
+/* qatvit_kd_bce_loss's objective (KD + BINARY cross-entropy with logits on the smoothed, mixed, optionally thresholded targets) in the class-parallel
+ * form of qatvit_kd_ce_loss_rows, to 32768 classes, with the teacher read from a COMPRESSED table (idx [table_rows, k], val [table_rows, k],
+ * tail [table_rows]; the format above) in its SPARSE form.  idx == NULL: no teacher - the hard part only, kd_alpha ignored, val / tail / index / k /
+ * table_rows not looked at: plain BCE above qatvit_kd_bce_loss's 4096 classes.  idx given: val, tail and index required, 1 <= k <= min(64, C - 1),
+ * table_rows >= 1, val and tail 4-byte and idx 2-byte aligned.  1 <= B < 2^30, 2 <= C <= 32768, kd_temp > 0, label_smoothing eps in [0, 1), mix NULL
+ * or 4-byte aligned, target_threshold negative: off.  partials: fp32 [2 * B] workspace, contents on entry ignored.
+ * Per element the hard part is qatvit_kd_bce_loss's, expression for expression: the target t[c], l[c], sigma, the gradient term
+ * w_hard * (sigma - t[c]) * scale with scale = 1 / (B * C), or 1 / B where sum_classes != 0; p, lam, oml from the row's record as stated there.
+ * The KD target of a row is that of qatvit_kd_bce_loss on the DECOMPRESSED rows, evaluated from what a compressed row is - the live entries and one
+ * value for every other class - and never from a dense row:
+ *   live entries   entry e of a row is live iff idx[e] is in [0, C) and no later entry of the row names the same class (the decompression rule);
+ *                  n = their number, u = the row's tail
+ *   partition sum  mt = max(live val, u);  zq = sum_live expf((val[e] - mt) / T) + (C - n) * expf((u - mt) / T), the live terms added over the lanes
+ *                  of one wave by a butterfly (entry e in lane e), the tail's term added last
+ *   probabilities  q_e = expf((val[e] - mt) / T - logf(zq)) for a live entry's class,  q0 = expf((u - mt) / T - logf(zq)) for every other class
+ *   target         lam == 1 or no record:  Q[c] = q[c], log Q[c] = the exponent above (no logarithm is taken);
+ *                  lam != 1, with q', q0' the same from table row index[p]:  Q[c] = lam * (q_c or q0) + oml * (q'_c or q0'),  Q0 = lam * q0 + oml * q0'
+ *                  for the classes in neither row; log Q = logf(Q) with 0 log 0 = 0, evaluated once per class that has an entry and once for Q0
+ *   KD = sum_c Q[c] (log Q[c] - log_softmax(x / T)[c]),  gradient term w_kd * T * (softmax(x / T)[c] - Q[c]) / B;  w_kd = alpha, w_hard = 1 - alpha.
+ * Against qatvit_kd_bce_loss on the decompressed rows this differs by rounding only: zq adds one product for the C - n tail classes instead of C - n
+ * terms, and log Q0 is one value.  An index[b], or where lam != 1 an index[p], outside [0, table_rows) reads nothing: that row of dlogits and all of
+ * out3 become NaN.  A row with lam == 1, or without a record, is its own partner: mix == NULL and lam == 1 give the same bits.
+ * Two launches on `stream`.  Thread t of a row's NT threads owns the classes t + NT j: one wave per row (NT = 64, 4 rows per workgroup) to 1024
+ * classes, one workgroup per row (NT = 256) above; to 4096 classes the student's row is read once, into registers, above that it is re-read per sweep.
+ * The sums over c are added per thread in ascending j, over a wave by butterflies, over a workgroup's waves as (0 + 1) + (2 + 3); the rows' sums in
+ * double in one fixed order (qatvit_kd_bce_loss's second launch).  No global atomics, no zeroed state: the same inputs give the same bits.
+ *   out3 = {w_kd * kd + w_hard * bce, bce, kd},  bce = scale * sum_b sum_c l,  kd = T^2 / B * sum_b KD   (idx == NULL: {bce, bce, 0}).
+ */
+int qatvit_kd_bce_loss_topk(const float* student, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int32_t k,
+                            const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                            float kd_alpha, float label_smoothing, float target_threshold, int32_t sum_classes, float* partials, float* out3,
+                            float* dlogits, void* stream);
+
 /* ===========================================================================
  * Building blocks of the step, exported for kernel-level parity tests.
  * All matrices row-major; "bf16" = IEEE bfloat16 bit patterns (uint16).

@@ -277,6 +277,26 @@ int qatvit_kd_ce_loss_topk(const float* student, const int16_t* idx, const float
     return 0;
 }
 
+int qatvit_kd_bce_loss_topk(const float* student, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int32_t k,
+                            const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                            float kd_alpha, float label_smoothing, float target_threshold, int32_t sum_classes, float* partials, float* out3,
+                            float* dlogits, void* stream) {
+    QV_CHECK_ARG(student && labels && partials && out3 && dlogits, "qatvit_kd_bce_loss_topk: null pointer argument");
+    QV_CHECK_ARG(!idx || (val && tail && index), "qatvit_kd_bce_loss_topk: a table (idx) needs val, tail and an index");
+    QV_CHECK_ARG(batch >= 1 && batch <= INT32_MAX / 2 && classes >= 2 && classes <= 32768, "qatvit_kd_bce_loss_topk: bad shape B=%lld C=%lld",
+                 (long long)batch, (long long)classes);
+    QV_CHECK_ARG(!idx || (k >= 1 && k <= 64 && k <= classes - 1), "qatvit_kd_bce_loss_topk: k %d is outside 1 .. min(64, C - 1)", (int)k);
+    QV_CHECK_ARG(!idx || table_rows >= 1, "qatvit_kd_bce_loss_topk: table_rows %lld (at least 1)", (long long)table_rows);
+    QV_CHECK_ARG(kd_temp > 0.f, "qatvit_kd_bce_loss_topk: kd_temp must be > 0");
+    QV_CHECK_ARG(label_smoothing >= 0.f && label_smoothing < 1.f, "qatvit_kd_bce_loss_topk: label_smoothing %g is outside [0, 1)", (double)label_smoothing);
+    QV_CHECK_ARG(!idx || ((((uintptr_t)val | (uintptr_t)tail) & 3) == 0 && ((uintptr_t)idx & 1) == 0), "qatvit_kd_bce_loss_topk: misaligned table pointer");
+    QV_CHECK_ARG(((uintptr_t)mix & 3) == 0, "qatvit_kd_bce_loss_topk: misaligned mix pointer");
+    launch_kd_bce_loss_topk(student, idx, val, tail, table_rows, k, index, labels, mix, batch, classes, kd_temp, kd_alpha, label_smoothing,
+                            target_threshold, sum_classes != 0, partials, out3, dlogits, (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_kd_bce_loss_topk");
+    return 0;
+}
+
 // The NT GEMMs: a wrapper checks its own pointers, writes its parameters into an NTGemm and names the operand form; launch_gemm_nt checks the request itself
 // (gemm.hip nt_request_ok).  QV_NT_REQUEST: the parameters the entry points share, by name (B and ldb: where there are any)
 #define QV_NT_REQUEST(g, a, a_ld, c_ld)                                                                                                         \

@@ -48,6 +48,14 @@ int launch_kd_ce_loss_topk(const float* student, const int16_t* idx, const float
                            const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
                            float label_smoothing, float* partials, float* out3, float* dlogits, hipStream_t st);
 
+// ---- bce_topk.hip: launch_kd_bce_loss's objective with launch_kd_ce_loss_rows' class ownership (to 32768 classes) and the compressed table read in
+// its sparse form: per row at most 128 (class, Q) entries and one constant in LDS, never a dense teacher row.  idx == nullptr: the hard part only.
+// Rows to partials[2 * batch], then k_kd_bce_finish (two launches)
+int launch_kd_bce_loss_topk(const float* student, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int k,
+                            const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                            float kd_alpha, float label_smoothing, float target_threshold, bool sum_classes, float* partials, float* out3,
+                            float* dlogits, hipStream_t st);
+
 // ---- fq.hip (engine pieces)
 int launch_minmax(const float* x, int64_t channels, int64_t inner, int per_channel, uint32_t* ws, int nslots, hipStream_t st);
 int launch_ws_init(uint32_t* ws, int64_t slots, hipStream_t st);

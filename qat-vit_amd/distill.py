@@ -360,6 +360,16 @@ class TeacherTopKTable:
         self.check_fresh()
         return F.kd_ce_loss_topk(student_logits, self.idx, self.val, self.tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
 
+    def bce_loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None, target_threshold=None,
+                 sum_classes=False):
+        """``TeacherLogitTable.bce_loss`` from the compressed rows, to 32768 classes (``F.kd_bce_loss_topk``): (loss, [loss, bce, kd*T^2]).  The KD
+        target is the one of the decompressed rows, evaluated from each row's ``k`` entries and its tail without forming a dense row anywhere; it
+        agrees with the dense evaluation to rounding, not bit for bit."""
+        self._need_device("bce_loss")
+        self.check_fresh()
+        return F.kd_bce_loss_topk(student_logits, labels, self.idx, self.val, self.tail, index, mix, kd_temp, kd_alpha, label_smoothing,
+                                  target_threshold, sum_classes)
+
     def save(self, path) -> None:
         torch.save({"idx": self.idx.detach().cpu(), "val": self.val.detach().cpu(), "tail": self.tail.detach().cpu(), "meta": self.meta}, path)
 

@@ -430,7 +430,66 @@ def kd_bce_loss(student, labels, teacher=None, table=None, index=None, mix=None,
     ``t > threshold``.  The hard part is the mean over all ``B * C`` elements (``BCEWithLogitsLoss()``), or with ``sum_classes`` the sum over the
     classes and the mean over the batch.  ``teacher`` (``[B, C]``: its output on the mixed images) or ``table`` + ``index`` (the mixed soft label of
     ``kd_ce_loss_table_mix``) add the KD part with weight ``kd_alpha``, the hard part then has ``1 - kd_alpha``; with neither, the loss is the hard
-    part.  An index outside the table makes the loss and that row of the gradient NaN; nothing here synchronises."""
+    part.  An index outside the table makes the loss and that row of the gradient NaN; nothing here synchronises.  ``C <= 4096`` with a teacher of
+    either dense kind; the hard part alone runs to ``C = 32768``, and a teacher above 4096 classes is a compressed table (``kd_bce_loss_topk``)."""
     if target_threshold is not None and not isinstance(target_threshold, (int, float)):
         raise RuntimeError("kd_bce_loss: target_threshold must be None or a Python number (a tensor would have to be read on the host)")
+    if teacher is None and table is None and student.dim() == 2 and student.shape[1] > 4096:
+        # above the one-wave-per-row entry's 4096 classes the hard part runs class-parallel over a workgroup (qatvit_kd_bce_loss_topk without a table)
+        return _KDBCELossTopKFn.apply(student, None, None, None, None, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes,
+                                      "kd_bce_loss")
     return _KDBCELossFn.apply(student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes)
+
+
+class _KDBCELossTopKFn(torch.autograd.Function):
+    """qatvit_kd_bce_loss_topk: _KDCELossTopKFn's checks of the compressed table (all of idx, val, tail, index, or none of them), the BCE arguments."""
+
+    @staticmethod
+    def forward(ctx, student, idx, val, tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes, who):
+        student, (_, _, _, lptr, mptr), _, keep = _kd_ce_operands(who, student, None, None, None, labels, mix)
+        (B, C), dev = student.shape, student.device
+        rows = k = 0
+        ptrs = (None, None, None, None)
+        if idx is not None:
+            if val is None or tail is None or index is None:
+                raise RuntimeError(f"{who}: a compressed table is idx, val and tail together, and needs an index")
+            rows, k = (idx.shape[0], idx.shape[1]) if idx.dim() == 2 else (0, 0)
+            for name, t, dtype, shape in (("idx", idx, torch.int16, (rows, k)), ("val", val, torch.float32, (rows, k)), ("tail", tail, torch.float32, (rows,))):
+                if t.dtype != dtype or tuple(t.shape) != shape or rows < 1 or not t.is_contiguous() or t.device != dev:
+                    raise RuntimeError(f"{who}: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            index = index.contiguous()
+            if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev:
+                raise RuntimeError(f"{who}: index must be an int64 [{B}] tensor on {dev}")
+            ptrs = (idx.data_ptr(), val.data_ptr(), tail.data_ptr(), index.data_ptr())
+        elif val is not None or tail is not None:
+            raise RuntimeError(f"{who}: val and tail without idx")
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        partials = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        dlogits = torch.empty_like(student)
+        native.check(
+            native.lib().qatvit_kd_bce_loss_topk(student.data_ptr(), ptrs[0], ptrs[1], ptrs[2], rows, k, ptrs[3], lptr, mptr, B, C, float(kd_temp),
+                                                 float(kd_alpha), float(label_smoothing), -1.0 if target_threshold is None else float(target_threshold),
+                                                 int(bool(sum_classes)), partials.data_ptr(), out3.data_ptr(), dlogits.data_ptr(), native.stream_ptr()),
+            "qatvit_kd_bce_loss_topk",
+        )
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(out3)
+        return out3[0], out3
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * dloss,) + (None,) * 12
+
+
+def kd_bce_loss_topk(student, labels, idx=None, val=None, tail=None, index=None, mix=None, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1,
+                     target_threshold=None, sum_classes=False):
+    """``kd_bce_loss`` to 32768 classes with the teacher read from the compressed table ``(idx, val, tail)`` (``teacher_topk``;
+    distill.TeacherTopKTable): returns (loss, [loss, bce, kd*T^2]).  The KD target is ``kd_bce_loss``'s on the decompressed rows, but evaluated from
+    the rows' at most ``k`` (under a mix record ``2 k``) explicit classes and one constant for all the others - no dense teacher row exists, and the
+    teacher's exp / log run once per entry; the result agrees with the dense evaluation to rounding.  Without a table (``idx=None``) it is the hard part
+    alone: plain BCE at any class count to 32768.  An index outside the table makes the loss and that row of the gradient NaN; nothing synchronises."""
+    if target_threshold is not None and not isinstance(target_threshold, (int, float)):
+        raise RuntimeError("kd_bce_loss_topk: target_threshold must be None or a Python number (a tensor would have to be read on the host)")
+    return _KDBCELossTopKFn.apply(student, idx, val, tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes,
+                                  "kd_bce_loss_topk")

@@ -10,7 +10,8 @@ class BinaryCrossEntropy(torch.nn.Module):
     """timm's ``BinaryCrossEntropy(smoothing, target_threshold, sum_classes=...)`` on integer labels and the mix records of a mixing loader
     instead of a dense ``[B, C]`` target: ``crit(logits, labels, mix=None)`` returns the loss, one native launch pair for the forward and the
     gradient (``F.kd_bce_loss`` without a teacher).  ``labels`` int64 ``[B]``, ``mix`` the int32 ``[B, 6]`` records the images were mixed with
-    (``MixupCutmix``) or None.  No ``weight`` / ``pos_weight``; fp32 logits on the GPU only."""
+    (``MixupCutmix``) or None.  ``2 <= C <= 32768`` (above 4096 classes ``F.kd_bce_loss`` runs the workgroup-per-row form of
+    ``qatvit_kd_bce_loss_topk``).  No ``weight`` / ``pos_weight``; fp32 logits on the GPU only."""
 
     def __init__(self, smoothing=0.1, target_threshold=None, sum_classes=False):
         super().__init__()
