@@ -144,7 +144,7 @@ int qatvit_kd_bce_loss(const float* student, const float* teacher, const float* 
 /* The KD + softmax-CE loss of qatvit_kd_ce_loss / _table / _mix in a CLASS-PARALLEL form, for class counts where one thread per row is too slow
  * (1000 classes) or refused (above 4096).  One entry for every form, with qatvit_kd_bce_loss's optional-argument rules: teacher [B,C] and
  * table [table_rows,C] mutually exclusive, a table needs index and table_rows >= 1, both NULL: CE only and alpha ignored; mix NULL or 4-byte aligned.
- * 1 <= B < 2^30, 2 <= C <= 32768, kd_temp > 0, label_smoothing in [0, 1); fp32 logits.  partials: fp32 [2 * B] workspace, contents on entry ignored.
+ * 1 <= B < 2^30, 2 <= C <= 32768, kd_temp > 0, label_smoothing in [0, 1); fp32 logits (fp16 / bf16: qatvit_kd_ce_loss_rows16, below).  partials: fp32 [2 * B] workspace, contents on entry ignored.
  * Arithmetic: per element exactly qatvit_kd_ce_loss_mix's (log-softmax, the smoothed mixed hard target, the KD target of a teacher row or of the
  * two table rows with 0 log 0 = 0, both gradient terms with 1 / B; all fp32, every operation rounded on its own).  A row with lam == 1, or without a
  * record, is its own partner: mix == NULL and lam == 1 give the same bits, and the partner's label and table row are read only where lam != 1.  A
@@ -229,6 +229,45 @@ int qatvit_kd_bce_loss_topk(const float* student, const int16_t* idx, const floa
                             const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
                             float kd_alpha, float label_smoothing, float target_threshold, int32_t sum_classes, float* partials, float* out3,
                             float* dlogits, void* stream);
+
+/* The three class-parallel entries above on fp16 / bf16 student logits, with the gradient written in the same 16-bit type: what a step under autocast
+ * has (16-bit logits out of the head, a 16-bit gradient into its backward) without the fp32 copy of [B, C], the fp32 dlogits and the cast back.
+ * Each is the fp32 entry of the same name with
+ *   student     const void*, fp16 or bf16 [B, C], 2-byte aligned;  dtype: QATVIT_EVAL_F16 (1) or QATVIT_EVAL_BF16 (2) (the codes of
+ *               qatvit_eval_accumulate, below).  QATVIT_EVAL_F32 is refused: fp32 logits belong to the fp32 entry, which the error text names
+ *   grad_scale  const float*, a device scalar, or NULL: s = *grad_scale, or 1.  It exists for fp16: the unscaled (p - t) / B at B = 1024 and
+ *               C >= 1000 lies in fp16's subnormal range, which is what a GradScaler's factor is for.  out3 is NOT scaled
+ *   dlogits     void*, [B, C] of the student's type, 2-byte aligned
+ * and every other argument, its checks, the partials workspace, the NaN rows (an index outside the table: that row of dlogits and all of out3; a NaN
+ * logit: its own row) and out3 (fp32) as the fp32 entry states them.  The teacher tensor, the tables, val and tail stay fp32.
+ * Arithmetic: x = (float)student[b][c] is exact; every expression after it is the fp32 entry's, operation for operation, in fp32.  The finished
+ * gradient g - the value the fp32 entry would store - is rounded ONCE: dlogits[b][c] = (E)(g * s), round to nearest even, fp16 overflow to +-inf.
+ * This is what stock autocast does (cross_entropy / log_softmax run in fp32, the cast's backward rounds once).
+ * Ownership and summation order.  Row b starts at byte 2 b C of `student`; let h = the number of elements in front of the row's first 16-byte
+ * boundary (0 .. 7, at most C), nb = (C - h) / 8, ts = h + 8 nb.  With NT = 64 threads per row (one wave, 4 rows per workgroup) up to 1024 classes and
+ * NT = 256 (one workgroup) above:
+ *   edge   thread t < h owns class t (the head); thread t with h <= t < h + C - ts owns class ts + t - h (the tail): at most one class per thread,
+ *          2-byte loads and stores
+ *   body   thread t owns the classes h + 8 t + 8 NT j + 0 .. 7, j = 0, 1, ...: one 16-byte load per 8 classes, and one 16-byte store of dlogits where
+ *          the dlogits row has the student row's address modulo 16 (else eight 2-byte stores of the same values)
+ * A thread adds its edge class first, then its groups in ascending j, the 8 classes of a group in ascending order; the threads' sums are combined by
+ * butterflies over a wave and over a workgroup's waves as (0 + 1) + (2 + 3); the rows' sums in double in one fixed order (qatvit_kd_bce_loss's second
+ * launch).  Up to 8192 classes the student's row is read once and held packed, two logits per register; above it is re-read per sweep.  The results
+ * agree with the fp32 entries on the up-cast logits to rounding, not bit for bit (only the order of the per-thread sums differs); they depend on h,
+ * i.e. on the row addresses modulo 16.  mix == NULL and lam == 1 give the same bits.  Two launches on `stream`, no atomics, no zeroed state: the
+ * same inputs at the same addresses modulo 16 give the same bits.
+ */
+int qatvit_kd_ce_loss_rows16(const void* student, int32_t dtype, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                             const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                             float label_smoothing, const float* grad_scale, float* partials, float* out3, void* dlogits, void* stream);
+int qatvit_kd_ce_loss_topk16(const void* student, int32_t dtype, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int32_t k,
+                             const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                             float kd_alpha, float label_smoothing, const float* grad_scale, float* partials, float* out3, void* dlogits,
+                             void* stream);
+int qatvit_kd_bce_loss_topk16(const void* student, int32_t dtype, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int32_t k,
+                              const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                              float kd_alpha, float label_smoothing, float target_threshold, int32_t sum_classes, const float* grad_scale,
+                              float* partials, float* out3, void* dlogits, void* stream);
 
 /* ===========================================================================
  * Building blocks of the step, exported for kernel-level parity tests.

@@ -18,69 +18,12 @@
 //     The student sweeps are k_kd_bce's (bce.hip): maximum; zT; terms and gradient.  In the last one a lane reads its class's bit (the 64 lanes of a
 //     wave read two neighbouring words) and takes (q0, lq0) unless it is set; with the bit set it probes the hash - the rare path.
 //   k_kd_bce_finish (bce.hip, unedited) forms out3.  Two launches, no global atomics, no zeroed state: the same inputs give the same bits.
+#include "bce_topk.h"
 #include "loss_rows.h"
 #include "qv_common.h"
 #include "qv_kernels.h"
 
 namespace qv {
-
-static constexpr int kTkSlots = 256;   // hash slots per row slot: twice the 128 entries a row and its partner can hold
-
-template <int BM>
-struct TkBlock {
-    int key[kTkSlots];     // the class, -1: free
-    float q[kTkSlots];     // while the block is built: the row's own probability (default: its tail's); then Q
-    float lq[kTkSlots];    // while the block is built: the partner's probability (default: its tail's); then log Q
-    unsigned bm[BM];
-    float q0, lq0;
-};
-
-__device__ __forceinline__ int tk_hash(int c) { return (int)(((unsigned)c * 0x9E3779B1u) >> 24); }
-
-// orders the LDS accesses of the lanes of ONE wave: the hardware executes a wave's LDS operations in order, this keeps the compiler from moving them
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// One compressed row, lane e holding entry e: which entries are live, and the log-probabilities at temperature T of the entry and of the tail.
-struct TkRow {
-    int c;          // the class of this lane's entry; -1: not live
-    float lq, lq0;  // log q of the entry, log q of a tail class
-};
-__device__ __forceinline__ TkRow tk_row(const int16_t* __restrict__ tidx, const float* __restrict__ tval, const float* __restrict__ ttail, int64_t i,
-                                        int k, int C, float invT, int lane) {
-    int c = -1;
-    float v = 0.f;
-    if (lane < k) { c = tidx[i * k + lane]; v = tval[i * k + lane]; }
-    const float u = ttail[i];
-    bool live = c >= 0 && c < C;
-    for (int e = 1; e < k; ++e) {   // every lane takes part in the shuffle
-        const int later = __shfl(c, e, 64);
-        live = live && !(e > lane && later == c);
-    }
-    const int n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(live));
-    const float mt = fmaxf(wave_max(live ? v : -INFINITY), u);
-    const float eu = expf((u - mt) * invT);
-    const float zq = wave_sum(live ? expf((v - mt) * invT) : 0.f) + (float)(C - n) * eu;
-    const float lzq = logf(zq);
-    TkRow r;
-    r.c = live ? c : -1;
-    r.lq = (v - mt) * invT - lzq;
-    r.lq0 = (u - mt) * invT - lzq;
-    return r;
-}
-
-// the slot of class c, claimed if it has none yet: at most 128 of the 256 slots are ever in use, so the probe ends
-__device__ __forceinline__ int tk_insert(int* key, int c) {
-    int h = tk_hash(c);
-    for (;;) {
-        const int old = atomicCAS(&key[h], -1, c);
-        if (old == -1 || old == c) return h;
-        h = (h + 1) & (kTkSlots - 1);
-    }
-}
 
 template <int NT, int NPL>
 __global__ __launch_bounds__(256) void k_kd_bce_topk(const float* __restrict__ s, const int16_t* __restrict__ tidx, const float* __restrict__ tval,
@@ -127,6 +70,8 @@ __global__ __launch_bounds__(256) void k_kd_bce_topk(const float* __restrict__ s
     if constexpr (NPL > 0) for_owned<NT, NPL>(tid, C, [&](int j, int c) { sv[j] = sr[c]; });
     auto S = [&](int j, int c) { return NPL > 0 ? sv[j] : sr[c]; };
 
+    // (the block's build below and the lookup in the last sweep have a twin, statement for statement, in bce_topk.h - tk_build, tk_lookup - that
+    // k_kd_bce_topk16 calls; this kernel keeps them inline, which keeps its register allocation.  A change to one is a change to both.)
     // the teacher block, by one wave.  NT = 256: the other waves go on to the student sweeps; the barriers of their two reductions, which this wave
     // meets after the block is complete, make it visible to them before the last sweep reads it
     if (kd && (NT == 64 || wave == 0)) {

@@ -297,6 +297,64 @@ int qatvit_kd_bce_loss_topk(const float* student, const int16_t* idx, const floa
     return 0;
 }
 
+// The 16-bit-logit forms of the three entries above: the fp32 entry's checks, the dtype code and the 2-byte alignment of student / dlogits
+#define QV_CHECK_LOSS16(fn, fp32_entry)                                                                                                              \
+    QV_CHECK_ARG(dtype != QATVIT_EVAL_F32, fn ": fp32 logits (dtype 0) belong to " fp32_entry ", this entry takes 1 = fp16 or 2 = bf16");            \
+    QV_CHECK_ARG(dtype == QATVIT_EVAL_F16 || dtype == QATVIT_EVAL_BF16, fn ": unknown dtype code %d (1 = fp16, 2 = bf16)", dtype);                   \
+    QV_CHECK_ARG(batch >= 1 && batch <= INT32_MAX / 2 && classes >= 2 && classes <= 32768, fn ": bad shape B=%lld C=%lld", (long long)batch,         \
+                 (long long)classes);                                                                                                                \
+    QV_CHECK_ARG(kd_temp > 0.f, fn ": kd_temp must be > 0");                                                                                         \
+    QV_CHECK_ARG(label_smoothing >= 0.f && label_smoothing < 1.f, fn ": label_smoothing %g is outside [0, 1)", (double)label_smoothing);             \
+    QV_CHECK_ARG((((uintptr_t)student | (uintptr_t)dlogits) & 1) == 0, fn ": misaligned student or dlogits pointer (2 bytes)");                      \
+    QV_CHECK_ARG(((uintptr_t)grad_scale & 3) == 0, fn ": misaligned grad_scale pointer");                                                            \
+    QV_CHECK_ARG(((uintptr_t)mix & 3) == 0, fn ": misaligned mix pointer")
+
+int qatvit_kd_ce_loss_rows16(const void* student, int32_t dtype, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                             const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                             float label_smoothing, const float* grad_scale, float* partials, float* out3, void* dlogits, void* stream) {
+    QV_CHECK_ARG(student && labels && partials && out3 && dlogits, "qatvit_kd_ce_loss_rows16: null pointer argument");
+    QV_CHECK_LOSS16("qatvit_kd_ce_loss_rows16", "qatvit_kd_ce_loss_rows");
+    QV_CHECK_ARG(!(teacher && table), "qatvit_kd_ce_loss_rows16: a teacher tensor and a teacher table are mutually exclusive");
+    QV_CHECK_ARG(!table || index, "qatvit_kd_ce_loss_rows16: a teacher table needs an index");
+    QV_CHECK_ARG(!table || table_rows >= 1, "qatvit_kd_ce_loss_rows16: table_rows %lld (at least 1)", (long long)table_rows);
+    launch_kd_ce_loss_rows16(student, dtype == QATVIT_EVAL_BF16, teacher, table, table_rows, index, labels, mix, batch, classes, kd_temp, kd_alpha,
+                             label_smoothing, grad_scale, partials, out3, dlogits, (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_kd_ce_loss_rows16");
+    return 0;
+}
+
+int qatvit_kd_ce_loss_topk16(const void* student, int32_t dtype, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int32_t k,
+                             const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                             float kd_alpha, float label_smoothing, const float* grad_scale, float* partials, float* out3, void* dlogits,
+                             void* stream) {
+    QV_CHECK_ARG(student && idx && val && tail && index && labels && partials && out3 && dlogits, "qatvit_kd_ce_loss_topk16: null pointer argument");
+    QV_CHECK_LOSS16("qatvit_kd_ce_loss_topk16", "qatvit_kd_ce_loss_topk");
+    QV_CHECK_ARG(k >= 1 && k <= 64 && k <= classes - 1, "qatvit_kd_ce_loss_topk16: k %d is outside 1 .. min(64, C - 1)", (int)k);
+    QV_CHECK_ARG(table_rows >= 1, "qatvit_kd_ce_loss_topk16: table_rows %lld (at least 1)", (long long)table_rows);
+    QV_CHECK_ARG((((uintptr_t)val | (uintptr_t)tail) & 3) == 0 && ((uintptr_t)idx & 1) == 0, "qatvit_kd_ce_loss_topk16: misaligned table pointer");
+    launch_kd_ce_loss_topk16(student, dtype == QATVIT_EVAL_BF16, idx, val, tail, table_rows, k, index, labels, mix, batch, classes, kd_temp, kd_alpha,
+                             label_smoothing, grad_scale, partials, out3, dlogits, (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_kd_ce_loss_topk16");
+    return 0;
+}
+
+int qatvit_kd_bce_loss_topk16(const void* student, int32_t dtype, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int32_t k,
+                              const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                              float kd_alpha, float label_smoothing, float target_threshold, int32_t sum_classes, const float* grad_scale,
+                              float* partials, float* out3, void* dlogits, void* stream) {
+    QV_CHECK_ARG(student && labels && partials && out3 && dlogits, "qatvit_kd_bce_loss_topk16: null pointer argument");
+    QV_CHECK_LOSS16("qatvit_kd_bce_loss_topk16", "qatvit_kd_bce_loss_topk");
+    QV_CHECK_ARG(!idx || (val && tail && index), "qatvit_kd_bce_loss_topk16: a table (idx) needs val, tail and an index");
+    QV_CHECK_ARG(!idx || (k >= 1 && k <= 64 && k <= classes - 1), "qatvit_kd_bce_loss_topk16: k %d is outside 1 .. min(64, C - 1)", (int)k);
+    QV_CHECK_ARG(!idx || table_rows >= 1, "qatvit_kd_bce_loss_topk16: table_rows %lld (at least 1)", (long long)table_rows);
+    QV_CHECK_ARG(!idx || ((((uintptr_t)val | (uintptr_t)tail) & 3) == 0 && ((uintptr_t)idx & 1) == 0), "qatvit_kd_bce_loss_topk16: misaligned table pointer");
+    launch_kd_bce_loss_topk16(student, dtype == QATVIT_EVAL_BF16, idx, val, tail, table_rows, k, index, labels, mix, batch, classes, kd_temp, kd_alpha,
+                              label_smoothing, target_threshold, sum_classes != 0, grad_scale, partials, out3, dlogits, (hipStream_t)stream);
+    QV_CHECK_LAUNCH("qatvit_kd_bce_loss_topk16");
+    return 0;
+}
+#undef QV_CHECK_LOSS16
+
 // The NT GEMMs: a wrapper checks its own pointers, writes its parameters into an NTGemm and names the operand form; launch_gemm_nt checks the request itself
 // (gemm.hip nt_request_ok).  QV_NT_REQUEST: the parameters the entry points share, by name (B and ldb: where there are any)
 #define QV_NT_REQUEST(g, a, a_ld, c_ld)                                                                                                         \

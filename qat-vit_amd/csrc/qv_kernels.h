@@ -56,6 +56,21 @@ int launch_kd_bce_loss_topk(const float* student, const int16_t* idx, const floa
                             float kd_alpha, float label_smoothing, float target_threshold, bool sum_classes, float* partials, float* out3,
                             float* dlogits, hipStream_t st);
 
+// ---- loss_rows16.hip: the three class-parallel losses above on fp16 / bf16 student logits (bf16: which of the two), the gradient rounded once to the
+// same type after a multiplication by *grad_scale (nullptr: 1).  A thread owns 8 consecutive classes per 16-byte load, counted from the row's first
+// 16-byte boundary.  Rows to partials[2 * batch], then k_kd_bce_finish (two launches)
+int launch_kd_ce_loss_rows16(const void* student, bool bf16, const float* teacher, const float* table, int64_t table_rows, const int64_t* index,
+                             const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp, float kd_alpha,
+                             float label_smoothing, const float* grad_scale, float* partials, float* out3, void* dlogits, hipStream_t st);
+int launch_kd_ce_loss_topk16(const void* student, bool bf16, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int k,
+                             const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                             float kd_alpha, float label_smoothing, const float* grad_scale, float* partials, float* out3, void* dlogits,
+                             hipStream_t st);
+int launch_kd_bce_loss_topk16(const void* student, bool bf16, const int16_t* idx, const float* val, const float* tail, int64_t table_rows, int k,
+                              const int64_t* index, const int64_t* labels, const int32_t* mix, int64_t batch, int64_t classes, float kd_temp,
+                              float kd_alpha, float label_smoothing, float target_threshold, bool sum_classes, const float* grad_scale, float* partials,
+                              float* out3, void* dlogits, hipStream_t st);
+
 // ---- fq.hip (engine pieces)
 int launch_minmax(const float* x, int64_t channels, int64_t inner, int per_channel, uint32_t* ws, int nslots, hipStream_t st);
 int launch_ws_init(uint32_t* ws, int64_t slots, hipStream_t st);

@@ -173,15 +173,19 @@ class TeacherLogitTable:
         self.check_fresh()
         return self.logits.index_select(0, index)
 
-    def loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None, class_parallel=False):
+    def loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None, class_parallel=False,
+             grad_scale=None):
         """``F.kd_ce_loss(student_logits, teacher(images of index), labels, ...)`` without the teacher forward: (loss, [loss, ce, kd*T^2]).
         ``mix`` (the int32 ``[B, 6]`` records a mixing loader yields) mixes the labels and the teacher's rows of each sample and its partner
-        (``F.kd_ce_loss_table_mix``).  ``class_parallel`` is passed on: the class-parallel form of the same loss, for 100 classes and more."""
+        (``F.kd_ce_loss_table_mix``).  ``class_parallel`` is passed on: the class-parallel form of the same loss, for 100 classes and more; it also takes fp16 / bf16
+        student logits, and ``grad_scale`` with them (``F.kd_ce_loss_mix``)."""
         self._need_device("loss")
         self.check_fresh()
         if mix is not None:
-            return F.kd_ce_loss_table_mix(student_logits, self.logits, index, labels, mix, kd_temp, kd_alpha, label_smoothing, class_parallel=class_parallel)
-        return F.kd_ce_loss_table(student_logits, self.logits, index, labels, kd_temp, kd_alpha, label_smoothing, class_parallel=class_parallel)
+            return F.kd_ce_loss_table_mix(student_logits, self.logits, index, labels, mix, kd_temp, kd_alpha, label_smoothing, class_parallel=class_parallel,
+                                          grad_scale=grad_scale)
+        return F.kd_ce_loss_table(student_logits, self.logits, index, labels, kd_temp, kd_alpha, label_smoothing, class_parallel=class_parallel,
+                                  grad_scale=grad_scale)
 
     def bce_loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None, target_threshold=None,
                  sum_classes=False):
@@ -353,22 +357,24 @@ class TeacherTopKTable:
             dense[at[ok], cls_[ok, e]] = val[ok, e]
         return dense
 
-    def loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None):
+    def loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None, grad_scale=None):
         """``TeacherLogitTable.loss(..., class_parallel=True)`` on the decompressed rows, which never exist in global memory (``F.kd_ce_loss_topk``):
-        (loss, [loss, ce, kd*T^2]).  At ``kd_temp == tail_temp`` the KD target's tail is uniform with the teacher's tail mass."""
+        (loss, [loss, ce, kd*T^2]).  At ``kd_temp == tail_temp`` the KD target's tail is uniform with the teacher's tail mass.  fp16 / bf16 student
+        logits and ``grad_scale``: as ``F.kd_ce_loss_mix`` states."""
         self._need_device("loss")
         self.check_fresh()
-        return F.kd_ce_loss_topk(student_logits, self.idx, self.val, self.tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
+        return F.kd_ce_loss_topk(student_logits, self.idx, self.val, self.tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing,
+                                 grad_scale=grad_scale)
 
     def bce_loss(self, student_logits, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, mix=None, target_threshold=None,
-                 sum_classes=False):
+                 sum_classes=False, grad_scale=None):
         """``TeacherLogitTable.bce_loss`` from the compressed rows, to 32768 classes (``F.kd_bce_loss_topk``): (loss, [loss, bce, kd*T^2]).  The KD
         target is the one of the decompressed rows, evaluated from each row's ``k`` entries and its tail without forming a dense row anywhere; it
-        agrees with the dense evaluation to rounding, not bit for bit."""
+        agrees with the dense evaluation to rounding, not bit for bit.  fp16 / bf16 student logits and ``grad_scale``: as ``F.kd_ce_loss_mix`` states."""
         self._need_device("bce_loss")
         self.check_fresh()
         return F.kd_bce_loss_topk(student_logits, labels, self.idx, self.val, self.tail, index, mix, kd_temp, kd_alpha, label_smoothing,
-                                  target_threshold, sum_classes)
+                                  target_threshold, sum_classes, grad_scale=grad_scale)
 
     def save(self, path) -> None:
         torch.save({"idx": self.idx.detach().cpu(), "val": self.val.detach().cpu(), "tail": self.tail.detach().cpu(), "meta": self.meta}, path)

@@ -11,10 +11,18 @@ import torch
 from . import native
 
 
-def _need_cuda(t: torch.Tensor, what: str) -> None:
+# the dtype codes of include/qatvit.h (QATVIT_EVAL_F16 / _BF16) for the entries that take 16-bit logits
+_DTYPE16 = {torch.float16: 1, torch.bfloat16: 2}
+
+
+def _need_cuda(t: torch.Tensor, what: str, half: bool = False) -> None:
+    """``half``: the tensor is a fp16 / bf16 student of a class-parallel loss instead of a float32 one."""
     if not t.is_cuda:
         raise RuntimeError(f"{what}: qat-vit_amd ops run on MI355X only (got a {t.device} tensor); there is no CPU fallback")
-    if t.dtype != torch.float32:
+    if half:
+        if t.dtype not in _DTYPE16:
+            raise RuntimeError(f"{what}: expected float16 or bfloat16, got {t.dtype}")
+    elif t.dtype != torch.float32:
         raise RuntimeError(f"{what}: expected float32, got {t.dtype}")
 
 
@@ -122,6 +130,12 @@ def layer_norm(x, gamma, beta, eps=1e-6):
     return _LayerNormFn.apply(x, gamma, beta, eps)
 
 
+def _no_grad_scale(who, grad_scale):
+    """The default (one thread per row) forms are float32 only: a ``grad_scale`` there is a mistake, not something to ignore."""
+    if grad_scale is not None:
+        raise RuntimeError(f"{who}: grad_scale belongs to a float16 / bfloat16 student, which this form (class_parallel=False) does not take")
+
+
 class _KDCELossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, student, teacher, labels, kd_temp, kd_alpha, label_smoothing):
@@ -152,12 +166,16 @@ class _KDCELossFn(torch.autograd.Function):
         return dlogits * dloss, None, None, None, None, None
 
 
-def kd_ce_loss(student, teacher, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
+def kd_ce_loss(student, teacher, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False, grad_scale=None):
     """Returns (loss, [loss, ce, kd*T^2]).  ``teacher=None`` -> CE only
     (the reference's step at /root/reference/src/training/qat_trainer.py:343-349).  ``class_parallel=True``: the same loss by
-    ``qatvit_kd_ce_loss_rows`` (see ``kd_ce_loss_mix``)."""
+    ``qatvit_kd_ce_loss_rows`` (see ``kd_ce_loss_mix``, also for a fp16 / bf16 student and ``grad_scale``)."""
     if class_parallel:
+        out = _loss16("kd_ce_loss", student, grad_scale, teacher=teacher, labels=labels, kd_temp=kd_temp, kd_alpha=kd_alpha, label_smoothing=label_smoothing)
+        if out is not None:
+            return out
         return _KDCELossRowsFn.apply(student, teacher, None, None, labels, None, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss")
+    _no_grad_scale("kd_ce_loss", grad_scale)
     return _KDCELossFn.apply(student, teacher, labels, kd_temp, kd_alpha, label_smoothing)
 
 
@@ -193,20 +211,25 @@ class _KDCELossTableFn(torch.autograd.Function):
         return dlogits * dloss, None, None, None, None, None, None
 
 
-def kd_ce_loss_table(student, table, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
+def kd_ce_loss_table(student, table, index, labels, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False, grad_scale=None):
     """``kd_ce_loss(student, table[index], labels, ...)`` in one launch, without the gathered tensor: returns (loss, [loss, ce, kd*T^2]).
     ``table`` is fp32 ``[rows, C]`` (per-sample teacher logits, distill.TeacherLogitTable), ``index`` int64 ``[B]``.  An index outside the table
     makes the loss and that row of the gradient NaN; it is not an error on the host (nothing here synchronises).  ``class_parallel=True``: the same
     loss by ``qatvit_kd_ce_loss_rows`` (see ``kd_ce_loss_mix``)."""
     if class_parallel:
+        out = _loss16("kd_ce_loss_table", student, grad_scale, table=table, index=index, labels=labels, kd_temp=kd_temp, kd_alpha=kd_alpha,
+                      label_smoothing=label_smoothing)
+        if out is not None:
+            return out
         return _KDCELossRowsFn.apply(student, None, table, index, labels, None, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss_table")
+    _no_grad_scale("kd_ce_loss_table", grad_scale)
     return _KDCELossTableFn.apply(student, table, index, labels, kd_temp, kd_alpha, label_smoothing)
 
 
-def _kd_ce_operands(who, student, teacher, table, index, labels, mix):
+def _kd_ce_operands(who, student, teacher, table, index, labels, mix, half=False):
     """The argument checks the mixed CE forms share: (contiguous student, (teacher, table, index, labels, mix) addresses or None, table rows, the
-    converted tensors, which the caller holds until its launch is enqueued)."""
-    _need_cuda(student, who)
+    converted tensors, which the caller holds until its launch is enqueued).  ``half``: a fp16 / bf16 student (_KDLoss16Fn)."""
+    _need_cuda(student, who, half)
     student = student.contiguous()
     B, C = student.shape
     dev = student.device
@@ -285,7 +308,7 @@ class _KDCELossRowsFn(torch.autograd.Function):
         return (dlogits * dloss,) + (None,) * 9
 
 
-def kd_ce_loss_mix(student, teacher, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
+def kd_ce_loss_mix(student, teacher, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False, grad_scale=None):
     """``kd_ce_loss`` on a mixed batch: returns (loss, [loss, ce, kd*T^2]).  ``mix`` is the int32 ``[B, 6]`` record tensor the images were mixed
     with (data.MixupCutmix): row b's hard target is ``lam`` on ``labels[b]`` and ``1 - lam`` on the partner's label.  ``teacher`` (``[B, C]`` or
     None) is the teacher's output on the mixed images, so the KD part is ``kd_ce_loss``'s.  ``mix=None`` is ``kd_ce_loss``.
@@ -293,19 +316,36 @@ def kd_ce_loss_mix(student, teacher, labels, mix, kd_temp=4.0, kd_alpha=0.5, lab
     ``class_parallel=True`` runs the same loss by ``qatvit_kd_ce_loss_rows``: a row's classes spread over one wave (``C <= 1024``) or one workgroup
     (up to ``C = 32768``; the default form stops at 4096) instead of one thread per row - the form for 100 classes and more.  Two launches instead of
     one, so at ``C = 10`` the default is the faster one.  Same arithmetic per element; the sums are added in another order, so the results agree to
-    rounding, not bit for bit."""
+    rounding, not bit for bit.
+
+    The class-parallel forms also take a ``torch.float16`` / ``torch.bfloat16`` student, as a head under autocast returns it
+    (``qatvit_kd_ce_loss_rows16`` and its siblings): the logits are up-cast exactly, the arithmetic is the fp32 entry's, and the gradient comes back
+    in the student's dtype, rounded once.  ``grad_scale`` (a 0-dim float32 tensor on the device, e.g. ``scaler.scale(torch.ones((), device=dev))``)
+    multiplies the gradient before that rounding - without it a fp16 gradient of ``(p - t) / B`` size is subnormal - and backward returns
+    ``dlogits * (dloss / grad_scale)``: under ``scaler.scale(loss).backward()`` the factor is exactly 1.  The returned loss and ``out3`` stay float32
+    and unscaled.  The default (``class_parallel=False``) forms stay float32 only."""
     if class_parallel:
+        out = _loss16("kd_ce_loss_mix", student, grad_scale, teacher=teacher, labels=labels, mix=mix, kd_temp=kd_temp, kd_alpha=kd_alpha,
+                      label_smoothing=label_smoothing)
+        if out is not None:
+            return out
         return _KDCELossRowsFn.apply(student, teacher, None, None, labels, mix, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss_mix")
+    _no_grad_scale("kd_ce_loss_mix", grad_scale)
     return _KDCELossMixFn.apply(student, teacher, None, None, labels, mix, kd_temp, kd_alpha, label_smoothing)
 
 
-def kd_ce_loss_table_mix(student, table, index, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False):
+def kd_ce_loss_table_mix(student, table, index, labels, mix, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, class_parallel=False, grad_scale=None):
     """``kd_ce_loss_table`` on a mixed batch: the hard target as in ``kd_ce_loss_mix``, the KD target
     ``lam * softmax(table[index[b]] / T) + (1 - lam) * softmax(table[index[p]] / T)`` - the usual mixed soft label, not the teacher's output on
     the mixed image.  An index outside the table, of the row or (where ``lam != 1``) of its partner, makes the loss and that row of the gradient
     NaN.  ``mix=None`` is ``kd_ce_loss_table``.  ``class_parallel=True``: the same loss by ``qatvit_kd_ce_loss_rows`` (see ``kd_ce_loss_mix``)."""
     if class_parallel:
+        out = _loss16("kd_ce_loss_table_mix", student, grad_scale, table=table, index=index, labels=labels, mix=mix, kd_temp=kd_temp, kd_alpha=kd_alpha,
+                      label_smoothing=label_smoothing)
+        if out is not None:
+            return out
         return _KDCELossRowsFn.apply(student, None, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, "kd_ce_loss_table_mix")
+    _no_grad_scale("kd_ce_loss_table_mix", grad_scale)
     return _KDCELossMixFn.apply(student, None, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
 
 
@@ -358,11 +398,16 @@ class _KDCELossTopKFn(torch.autograd.Function):
         return (dlogits * dloss,) + (None,) * 9
 
 
-def kd_ce_loss_topk(student, idx, val, tail, index, labels, mix=None, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1):
+def kd_ce_loss_topk(student, idx, val, tail, index, labels, mix=None, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1, grad_scale=None):
     """``kd_ce_loss_table_mix(student, rows, index, labels, mix, ..., class_parallel=True)`` with ``rows`` the decompression of the compressed table
     ``(idx, val, tail)`` (``teacher_topk``; distill.TeacherTopKTable) - bit for bit, without the dense rows ever existing in global memory: the kernel
     decompresses the rows of a sample and, where ``lam != 1``, of its partner in LDS.  Returns (loss, [loss, ce, kd*T^2]); an index outside the
-    table makes the loss and that row of the gradient NaN."""
+    table makes the loss and that row of the gradient NaN.  A fp16 / bf16 student and ``grad_scale``: as ``kd_ce_loss_mix`` states (there the result
+    agrees with the fp32 form on the up-cast logits to rounding)."""
+    out = _loss16("kd_ce_loss_topk", student, grad_scale, topk=(idx, val, tail), index=index, labels=labels, mix=mix, kd_temp=kd_temp, kd_alpha=kd_alpha,
+                  label_smoothing=label_smoothing)
+    if out is not None:
+        return out
     return _KDCELossTopKFn.apply(student, idx, val, tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing)
 
 
@@ -423,7 +468,7 @@ class _KDBCELossFn(torch.autograd.Function):
 
 
 def kd_bce_loss(student, labels, teacher=None, table=None, index=None, mix=None, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1,
-                target_threshold=None, sum_classes=False):
+                target_threshold=None, sum_classes=False, grad_scale=None):
     """KD + binary cross-entropy with logits on smoothed, mixed targets (timm's ``BinaryCrossEntropy`` behind its ``Mixup``; the DeiT-III
     criterion): returns (loss, [loss, bce, kd*T^2]).  The hard target of row b is ``kd_ce_loss_mix``'s - ``lam`` on ``labels[b]``, ``1 - lam`` on
     the partner's label, smoothed to ``(1 - eps) * t + eps / C`` - used per class; ``target_threshold`` (None or negative: off) then turns it into
@@ -431,13 +476,21 @@ def kd_bce_loss(student, labels, teacher=None, table=None, index=None, mix=None,
     classes and the mean over the batch.  ``teacher`` (``[B, C]``: its output on the mixed images) or ``table`` + ``index`` (the mixed soft label of
     ``kd_ce_loss_table_mix``) add the KD part with weight ``kd_alpha``, the hard part then has ``1 - kd_alpha``; with neither, the loss is the hard
     part.  An index outside the table makes the loss and that row of the gradient NaN; nothing here synchronises.  ``C <= 4096`` with a teacher of
-    either dense kind; the hard part alone runs to ``C = 32768``, and a teacher above 4096 classes is a compressed table (``kd_bce_loss_topk``)."""
+    either dense kind; the hard part alone runs to ``C = 32768``, and a teacher above 4096 classes is a compressed table (``kd_bce_loss_topk``).
+    The hard part alone above 4096 classes also takes a fp16 / bf16 student and ``grad_scale`` (see ``kd_ce_loss_mix``); every other form here is
+    float32 only."""
     if target_threshold is not None and not isinstance(target_threshold, (int, float)):
         raise RuntimeError("kd_bce_loss: target_threshold must be None or a Python number (a tensor would have to be read on the host)")
     if teacher is None and table is None and student.dim() == 2 and student.shape[1] > 4096:
         # above the one-wave-per-row entry's 4096 classes the hard part runs class-parallel over a workgroup (qatvit_kd_bce_loss_topk without a table)
+        out = _loss16("kd_bce_loss", student, grad_scale, labels=labels, mix=mix, kd_temp=kd_temp, kd_alpha=kd_alpha, label_smoothing=label_smoothing,
+                      bce=(target_threshold, sum_classes))
+        if out is not None:
+            return out
         return _KDBCELossTopKFn.apply(student, None, None, None, None, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes,
                                       "kd_bce_loss")
+    if grad_scale is not None:
+        raise RuntimeError("kd_bce_loss: grad_scale belongs to a float16 / bfloat16 student, which this form (a teacher, or up to 4096 classes) does not take")
     return _KDBCELossFn.apply(student, teacher, table, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes)
 
 
@@ -483,13 +536,81 @@ class _KDBCELossTopKFn(torch.autograd.Function):
 
 
 def kd_bce_loss_topk(student, labels, idx=None, val=None, tail=None, index=None, mix=None, kd_temp=4.0, kd_alpha=0.5, label_smoothing=0.1,
-                     target_threshold=None, sum_classes=False):
+                     target_threshold=None, sum_classes=False, grad_scale=None):
     """``kd_bce_loss`` to 32768 classes with the teacher read from the compressed table ``(idx, val, tail)`` (``teacher_topk``;
     distill.TeacherTopKTable): returns (loss, [loss, bce, kd*T^2]).  The KD target is ``kd_bce_loss``'s on the decompressed rows, but evaluated from
     the rows' at most ``k`` (under a mix record ``2 k``) explicit classes and one constant for all the others - no dense teacher row exists, and the
     teacher's exp / log run once per entry; the result agrees with the dense evaluation to rounding.  Without a table (``idx=None``) it is the hard part
-    alone: plain BCE at any class count to 32768.  An index outside the table makes the loss and that row of the gradient NaN; nothing synchronises."""
+    alone: plain BCE at any class count to 32768.  An index outside the table makes the loss and that row of the gradient NaN; nothing synchronises.
+    A fp16 / bf16 student and ``grad_scale``: as ``kd_ce_loss_mix`` states."""
     if target_threshold is not None and not isinstance(target_threshold, (int, float)):
         raise RuntimeError("kd_bce_loss_topk: target_threshold must be None or a Python number (a tensor would have to be read on the host)")
+    if idx is None and (val is not None or tail is not None):
+        raise RuntimeError("kd_bce_loss_topk: val and tail without idx")
+    out = _loss16("kd_bce_loss_topk", student, grad_scale, topk=None if idx is None else (idx, val, tail), index=index, labels=labels, mix=mix,
+                  kd_temp=kd_temp, kd_alpha=kd_alpha, label_smoothing=label_smoothing, bce=(target_threshold, sum_classes))
+    if out is not None:
+        return out
     return _KDBCELossTopKFn.apply(student, idx, val, tail, index, labels, mix, kd_temp, kd_alpha, label_smoothing, target_threshold, sum_classes,
                                   "kd_bce_loss_topk")
+
+
+class _KDLoss16Fn(torch.autograd.Function):
+    """The class-parallel losses on a fp16 / bf16 student (qatvit_kd_ce_loss_rows16, qatvit_kd_ce_loss_topk16, qatvit_kd_bce_loss_topk16): the checks
+    of the fp32 Functions, one entry chosen from what is given - ``bce = (target_threshold, sum_classes)``: the BCE entry (``topk`` optional);
+    ``topk = (idx, val, tail)``: the compressed-table CE entry; else the rows entry with ``teacher`` / ``table`` / neither.  ``dlogits`` has the
+    student's dtype and holds ``grad_scale`` times the gradient; backward undoes the factor on ``dloss``, so nothing here reads the scale on the host."""
+
+    @staticmethod
+    def forward(ctx, student, who, teacher, table, topk, index, labels, mix, kd_temp, kd_alpha, label_smoothing, bce, grad_scale):
+        student, (tptr, bptr, iptr, lptr, mptr), rows, keep = _kd_ce_operands(who, student, teacher, table, index, labels, mix, half=True)
+        (B, C), dev = student.shape, student.device
+        if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 or grad_scale.device != dev):
+            raise RuntimeError(f"{who}: grad_scale must be a float32 scalar tensor on {dev}")
+        k = 0
+        ptrs = (None, None, None)
+        if topk is not None:
+            idx, val, tail = topk
+            if idx is None or val is None or tail is None or index is None:
+                raise RuntimeError(f"{who}: a compressed table is idx, val and tail together, and needs an index")
+            rows, k = (idx.shape[0], idx.shape[1]) if idx.dim() == 2 else (0, 0)
+            for name, t, dtype, shape in (("idx", idx, torch.int16, (rows, k)), ("val", val, torch.float32, (rows, k)), ("tail", tail, torch.float32, (rows,))):
+                if t.dtype != dtype or tuple(t.shape) != shape or rows < 1 or not t.is_contiguous() or t.device != dev:
+                    raise RuntimeError(f"{who}: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            index = index.contiguous()
+            if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev:
+                raise RuntimeError(f"{who}: index must be an int64 [{B}] tensor on {dev}")
+            ptrs, iptr = (idx.data_ptr(), val.data_ptr(), tail.data_ptr()), index.data_ptr()
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        partials = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        dlogits = torch.empty_like(student)
+        L, code = native.lib(), _DTYPE16[student.dtype]
+        gptr = None if grad_scale is None else grad_scale.data_ptr()
+        common = (lptr, mptr, B, C, float(kd_temp), float(kd_alpha), float(label_smoothing))
+        tails = (gptr, partials.data_ptr(), out3.data_ptr(), dlogits.data_ptr(), native.stream_ptr())
+        if bce is not None:
+            thr, sum_classes = bce
+            native.check(L.qatvit_kd_bce_loss_topk16(student.data_ptr(), code, *ptrs, rows, k, iptr, *common, -1.0 if thr is None else float(thr),
+                                                     int(bool(sum_classes)), *tails), "qatvit_kd_bce_loss_topk16")
+        elif topk is not None:
+            native.check(L.qatvit_kd_ce_loss_topk16(student.data_ptr(), code, *ptrs, rows, k, iptr, *common, *tails), "qatvit_kd_ce_loss_topk16")
+        else:
+            native.check(L.qatvit_kd_ce_loss_rows16(student.data_ptr(), code, tptr, bptr, rows, iptr, *common, *tails), "qatvit_kd_ce_loss_rows16")
+        ctx.save_for_backward(dlogits, *(() if grad_scale is None else (grad_scale,)))
+        ctx.mark_non_differentiable(out3)
+        return out3[0], out3
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        dlogits, *scale = ctx.saved_tensors
+        return (dlogits * (dloss / scale[0] if scale else dloss),) + (None,) * 12
+
+
+def _loss16(who, student, grad_scale, teacher=None, table=None, topk=None, index=None, labels=None, mix=None, kd_temp=4.0, kd_alpha=0.5,
+            label_smoothing=0.1, bce=None):
+    """None for a float32 student (which takes no ``grad_scale``), else the loss of _KDLoss16Fn."""
+    if student.dtype not in _DTYPE16:
+        if grad_scale is not None:
+            raise RuntimeError(f"{who}: grad_scale belongs to a float16 / bfloat16 student; a float32 gradient needs no scale")
+        return None
+    return _KDLoss16Fn.apply(student, who, teacher, table, topk, index, labels, mix, kd_temp, kd_alpha, label_smoothing, bce, grad_scale)

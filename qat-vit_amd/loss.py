@@ -11,7 +11,8 @@ class BinaryCrossEntropy(torch.nn.Module):
     instead of a dense ``[B, C]`` target: ``crit(logits, labels, mix=None)`` returns the loss, one native launch pair for the forward and the
     gradient (``F.kd_bce_loss`` without a teacher).  ``labels`` int64 ``[B]``, ``mix`` the int32 ``[B, 6]`` records the images were mixed with
     (``MixupCutmix``) or None.  ``2 <= C <= 32768`` (above 4096 classes ``F.kd_bce_loss`` runs the workgroup-per-row form of
-    ``qatvit_kd_bce_loss_topk``).  No ``weight`` / ``pos_weight``; fp32 logits on the GPU only."""
+    ``qatvit_kd_bce_loss_topk``; that form also takes fp16 / bf16 logits and ``grad_scale``, a 0-dim float32 device tensor that multiplies the
+    16-bit gradient before its one rounding - ``F.kd_ce_loss_mix``).  No ``weight`` / ``pos_weight``; up to 4096 classes fp32 logits only; GPU only."""
 
     def __init__(self, smoothing=0.1, target_threshold=None, sum_classes=False):
         super().__init__()
@@ -24,9 +25,9 @@ class BinaryCrossEntropy(torch.nn.Module):
                 raise ValueError(f"target_threshold must be None or in [0, 1), got {target_threshold}")
         self.smoothing, self.target_threshold, self.sum_classes = smoothing, target_threshold, bool(sum_classes)
 
-    def forward(self, logits, labels, mix=None):
+    def forward(self, logits, labels, mix=None, grad_scale=None):
         return F.kd_bce_loss(logits, labels, mix=mix, label_smoothing=self.smoothing, target_threshold=self.target_threshold,
-                             sum_classes=self.sum_classes)[0]
+                             sum_classes=self.sum_classes, grad_scale=grad_scale)[0]
 
     def extra_repr(self):
         return f"smoothing={self.smoothing}, target_threshold={self.target_threshold}, sum_classes={self.sum_classes}"
