@@ -461,6 +461,30 @@ int qatvit_attn_backward_form(const float* qkv, const float* qp, int32_t qmin, i
                               void* dqkv_hi, void* dqkv_lo, const float* col_scale, const void* qkv_codes, const void* qkv_mask,
                               const float* o16_mul, uint32_t* o16_amax, int32_t form, void* stream);
 
+/* The classifier head of the QAT step alone (final LayerNorm apply + fake-quant on the class-token rows, the head GEMM, its backward), with the form named as
+ * qatvit_attn_backward_form names its own.  form 0: one workgroup per image walking the classes (what every configuration below 128 classes runs); form 1: the
+ * MFMA kernels (the whole step takes them from 128 classes up; QATVIT_HEAD_MFMA=0 in the environment: never).  Form 1 exists for D % 64 == 0, D <= 768,
+ * 128 <= C <= 32768 and qmax - qmin <= 255 only: an error elsewhere, nothing is launched.  Both forms: B, T >= 1, D <= 768, C <= 32768.
+ * forward: x [B * T, D] fp32 with the row statistics mean / rstd [B * T] (row b * T is image b's class token), gamma / beta [D], qp_norm / qp_logits = a
+ * quantizer's published {scale, 1 / scale, zero point, enabled}, wq [C, D] the weight's grid integers as bf16, w_scale [C] (w_per_channel) or [1], bias [C].
+ * Writes hq [B, D] fp32 = q - zp, form 1 also hq16 [B, D] bf16 (the same integers; may be NULL for form 0), logits_pre [B, C] fp32 and folds min / max of
+ * logits_pre into stats: QATVIT_STAT_SLOTS {min, max} pairs of order-preserving uint32 words, QATVIT_STAT_STRIDE words apart (initialised to
+ * {0xff800000, 0x007fffff}).  hq, logits_pre and the fold of the pairs over the slots are the same bits in both forms (which slot a value lands in is not).
+ * backward: dlogits [B, C], W [C, D] the fp32 weight with its quantizer's w_scale / w_zp; writes (=) dW [C, D], dbias [C] and dh [B, D], the gradient of the
+ * fake-quantized norm output.  Form 0 reads hq, form 1 reads hq16 and `scratch` (qatvit_head_scratch_bytes(B, D, C) bytes; 0 for shapes form 1 does not
+ * cover): the partial tiles of its class ranges, summed in a fixed order - two calls give the same bits.
+ * Replaces: model.head on the pooled class token and its autograd (reference/src/models/vit.py), with the fake-quantizers around it. */
+#define QATVIT_STAT_SLOTS 32
+#define QATVIT_STAT_STRIDE 32
+int64_t qatvit_head_scratch_bytes(int32_t B, int32_t D, int32_t C);
+int qatvit_head_forward(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp_norm, int32_t qmin,
+                        int32_t qmax, const void* wq, const float* w_scale, int32_t w_per_channel, const float* bias, float* hq, void* hq16,
+                        float* logits_pre, uint32_t* stats, int32_t B, int32_t D, int32_t T, int32_t C, int32_t form, void* stream);
+int qatvit_head_backward(const float* dlogits, const float* logits_pre, const float* qp_logits, int32_t qmin, int32_t qmax, const float* hq, const void* hq16,
+                         const float* qp_norm, const void* wq, const float* W, const float* w_scale, const int32_t* w_zp, int32_t w_per_channel,
+                         int32_t w_qmin, int32_t w_qmax, float* dW, float* dbias, float* dh, void* scratch, int64_t scratch_bytes, int32_t B, int32_t D,
+                         int32_t C, int32_t form, void* stream);
+
 /* The class-token rows of a [rows * T, width bytes] tensor (the student pools the class token, so the gradient entering the last block lives in rows
  * b * T only; the one-plane backward runs that block's MLP and proj on those rows - QATVIT_CLS_BWD=0 in the environment: on all rows).
  * gather: compact[b] = tall[b * T], b < rows; width % 4 == 0, `stride` = bytes between two rows of tall (% 4 == 0, >= width).
@@ -544,6 +568,9 @@ int32_t qatvit_student_dy16_supported(const qatvit_cfg* cfg);
 /* Which LayerNorms of a forward with `flags` run inside the statistics pass that follows them (qatvit_i8_strip_ln) instead of as a launch of their own:
  * bit 0 = norm1 (attn.qkv), bit 1 = norm2 (mlp.fc1), of every block.  QATVIT_LN_STRIP=0 in the environment: 0. */
 int32_t qatvit_student_ln_in_strip(const qatvit_cfg* cfg, int32_t flags);
+/* 1 where the step of this configuration runs its classifier head in form 1 of qatvit_head_forward / _backward (at most 256 activation levels, 128 <= num_classes
+ * <= 32768, embed_dim % 64 == 0; the workspace then ends with the bf16 plane and the scratch that form needs), else 0.  QATVIT_HEAD_MFMA=0 in the environment: 0. */
+int32_t qatvit_student_head_mfma(const qatvit_cfg* cfg);
 /* h1q / h2q of every block from fp16 integers back to bf16 integers, in place (fallback after an overflow: the pair form reads bf16) */
 /* Host mirror of the one-plane backward's overflow flag: host_pinned = int32[2] in pinned host memory (hipHostMalloc / torch pin_memory), NULL to remove it.  Every
  * backward call then writes {overflow flag, generation} there - the generation (a counter that changes with every call) after the flag, system scope - as soon as the

@@ -28,7 +28,7 @@ const Knobs& knobs() {
     static const Knobs k{knob("QATVIT_I8"), knob("QATVIT_F16"), knob("QATVIT_FC2_CODES"), knob("QATVIT_FC1_BITS"), knob("QATVIT_FC2W_CODES"),
                          knob("QATVIT_WBATCH"), knob("QATVIT_ATTN_CODES"), knob("QATVIT_QKV_2PASS"), knob("QATVIT_LNB_FUSE"), knob("QATVIT_QP_LATE"),
                          knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP"), knob("QATVIT_LN_STRIP"),
-                         knob("QATVIT_CLS_BWD"), knob("QATVIT_ATTN_BWD_PIPE")};
+                         knob("QATVIT_CLS_BWD"), knob("QATVIT_ATTN_BWD_PIPE"), knob("QATVIT_HEAD_MFMA")};
     return k;
 }
 int cu_count() {
@@ -623,6 +623,71 @@ int qatvit_attn_backward_form(const float* qkv, const float* qp, int32_t qmin, i
                         o16_amax, 0, false, form))
         return 1;
     QV_CHECK_LAUNCH("qatvit_attn_backward_form");
+    return 0;
+}
+
+// the classifier head alone, by form: 0 the one-block-per-image kernels (elt.hip), 1 the MFMA kernels (head_mfma.hip)
+static int head_shape_check(const char* fn, int32_t B, int32_t D, int32_t T, int32_t C, int32_t qmin, int32_t qmax, int32_t form) {
+    if (form != 0 && form != 1) { set_error("%s: form %d (0 one block per image, 1 MFMA)", fn, form); return 1; }
+    if (B < 1 || D < 1 || T < 1 || C < 1 || D > 768 || C > kHeadMfmaMaxClasses) {
+        set_error("%s: B %d, D %d, T %d, C %d (all >= 1, D <= 768, C <= %d)", fn, B, D, T, C, kHeadMfmaMaxClasses);
+        return 1;
+    }
+    if (form == 1 && (!head_mfma_covers(D, C) || qmax - qmin > 255)) {
+        set_error("%s: form 1 (MFMA) needs D %% 64 == 0, D <= 768, %d <= C <= %d and at most 256 activation levels; got D %d, C %d, levels %d", fn,
+                  kHeadMfmaMinClasses, kHeadMfmaMaxClasses, D, C, qmax - qmin + 1);
+        return 1;
+    }
+    return 0;
+}
+
+int64_t qatvit_head_scratch_bytes(int32_t B, int32_t D, int32_t C) {
+    if (B < 1 || !head_mfma_covers(D, C)) return 0;   // (form 0 needs none)
+    return head_mfma_scratch_bytes(B, D, C);
+}
+
+int qatvit_head_forward(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp_norm, int32_t qmin,
+                        int32_t qmax, const void* wq, const float* w_scale, int32_t w_per_channel, const float* bias, float* hq, void* hq16,
+                        float* logits_pre, uint32_t* stats, int32_t B, int32_t D, int32_t T, int32_t C, int32_t form, void* stream) {
+    static_assert(QATVIT_STAT_SLOTS == kStatSlots && QATVIT_STAT_STRIDE == kStatStride, "qatvit.h mirrors the statistics slot layout");
+    if (head_shape_check("qatvit_head_forward", B, D, T, C, qmin, qmax, form)) return 1;
+    QV_CHECK_ARG(x && mean && rstd && gamma && beta && qp_norm && wq && w_scale && bias && hq && logits_pre && stats && (form == 0 || hq16),
+                 "qatvit_head_forward: null pointer argument");
+    QV_CHECK_ARG(form == 0 || (reinterpret_cast<uintptr_t>(wq) % 16 == 0 && reinterpret_cast<uintptr_t>(hq16) % 16 == 0),
+                 "qatvit_head_forward: form 1 needs wq and hq16 16-byte aligned");
+    if (form == 1) {
+        if (launch_head_fwd_mfma(x, mean, rstd, gamma, beta, qp_norm, qmin, qmax, wq, w_scale, w_per_channel, bias, hq, hq16, logits_pre, stats, kStatSlots, B, D,
+                                 T, C, (hipStream_t)stream))
+            return 1;
+    } else {
+        launch_head_fwd(x, mean, rstd, gamma, beta, qp_norm, qmin, qmax, wq, w_scale, w_per_channel, bias, hq, logits_pre, stats, kStatSlots, B, D, T, C,
+                        (hipStream_t)stream);
+    }
+    QV_CHECK_LAUNCH("qatvit_head_forward");
+    return 0;
+}
+
+int qatvit_head_backward(const float* dlogits, const float* logits_pre, const float* qp_logits, int32_t qmin, int32_t qmax, const float* hq, const void* hq16,
+                         const float* qp_norm, const void* wq, const float* W, const float* w_scale, const int32_t* w_zp, int32_t w_per_channel,
+                         int32_t w_qmin, int32_t w_qmax, float* dW, float* dbias, float* dh, void* scratch, int64_t scratch_bytes, int32_t B, int32_t D,
+                         int32_t C, int32_t form, void* stream) {
+    if (head_shape_check("qatvit_head_backward", B, D, 1, C, qmin, qmax, form)) return 1;
+    QV_CHECK_ARG(dlogits && logits_pre && qp_logits && qp_norm && wq && W && w_scale && w_zp && dW && dbias && dh && (form == 0 ? hq != nullptr : hq16 != nullptr),
+                 "qatvit_head_backward: null pointer argument");
+    if (form == 1) {
+        const int64_t need = head_mfma_scratch_bytes(B, D, C);
+        QV_CHECK_ARG(scratch && scratch_bytes >= need, "qatvit_head_backward: form 1 needs %lld bytes of scratch (qatvit_head_scratch_bytes), got %lld",
+                     (long long)need, (long long)(scratch ? scratch_bytes : 0));
+        QV_CHECK_ARG(reinterpret_cast<uintptr_t>(wq) % 16 == 0 && reinterpret_cast<uintptr_t>(hq16) % 16 == 0 && reinterpret_cast<uintptr_t>(scratch) % 4 == 0,
+                     "qatvit_head_backward: form 1 needs wq and hq16 16-byte aligned");
+        if (launch_head_bwd_mfma(dlogits, logits_pre, qp_logits, qmin, qmax, hq16, qp_norm, wq, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dW, dbias, dh,
+                                 scratch, B, D, C, (hipStream_t)stream))
+            return 1;
+    } else {
+        launch_head_bwd(dlogits, logits_pre, qp_logits, qmin, qmax, hq, qp_norm, wq, W, w_scale, w_zp, w_per_channel, w_qmin, w_qmax, dW, dbias, dh, B, D, C,
+                        (hipStream_t)stream);
+    }
+    QV_CHECK_LAUNCH("qatvit_head_backward");
     return 0;
 }
 

@@ -85,6 +85,7 @@ struct Forms {
     bool dy16;               // the one-plane backward covers this configuration
     bool ln_in_strip;        // norm1 / norm2 apply + quantise inside the statistics pass of qkv / fc1 (launch_i8_strip_ln) where the forward writes the byte plane only (ln_in_strip_of)
     bool cls_bwd;            // the one-plane backward of the final norm and of the last block's MLP + proj on the B class-token rows (Plan::ClsRows; bwd() decides per call)
+    bool head_mfma;          // the classifier head on MFMA (head_mfma.hip: 128 .. 32768 classes, D % 64 == 0), else the one-block-per-image kernels
 };
 // drop_path: a drop-path scale table or a LayerScale binding is bound to the workspace of the call (qatvit_student_set_drop_path, _set_layer_scale)
 static Forms forms_of(const qatvit_cfg& c, const Dims& d, bool drop_path) {
@@ -108,6 +109,7 @@ static Forms forms_of(const qatvit_cfg& c, const Dims& d, bool drop_path) {
     f.dy16 = f.i8 && f.w_batched && d.D % 384 == 0 && d.Hd % 384 == 0 && f.qkv_2pass && f.attn_bwd_fused && f.f16_proj && f.fc2w_codes;
     f.ln_in_strip = k.ln_strip && f.i8 && f.late && f.x_plane_from_q8;
     f.cls_bwd = k.cls_bwd && f.dy16;
+    f.head_mfma = k.head_mfma && byte_codes && d.C >= 128 && d.D % 64 == 0 && d.C <= 32768 && head_mfma_covers(d.D, d.C);
     return f;
 }
 
@@ -136,6 +138,7 @@ struct Plan {
         int64_t G8, Y1m, h2q, x_mid, mean2, rstd2, mproj, O16;      // last block (h2q: the int8 plane q - center, or the fp16 one where the weight gradient reads that)
         int64_t dY1, dYp, dxB, dO, dH;                              // fc1-out / proj-in planes fp16; d x_mid, d attention output, the unfused dgrad's output fp32
     } cls;
+    int64_t hq16, head_scratch;   // Forms::head_mfma (else absent): hq once more as a bf16 plane [B, D]; the partial tiles of the head dgrad's class ranges
     int64_t total, stats_words;
     int TP;
 };
@@ -243,6 +246,11 @@ static int make_plan(const qatvit_cfg& c, Plan* p, bool drop_path = false) {   /
         r.G8 = take(B * Hd); r.Y1m = take(B * Hd / 8); r.h2q = take(B * D * 2); r.x_mid = take(B * D * 4); r.mean2 = take(B * 4); r.rstd2 = take(B * 4);
         r.mproj = take(B * mrow); r.O16 = take(B * D * 2);
         r.dY1 = take(B * Hd * 2); r.dYp = take(B * D * 2); r.dxB = take(B * D * 4); r.dO = take(B * D * 4); r.dH = take(B * D * 4);
+    }
+    p->hq16 = p->head_scratch = -1;
+    if (p->form.head_mfma) {   // (at the very end: every configuration without the form keeps its offsets and its size)
+        p->hq16 = take((int64_t)d.B * D * 2);
+        p->head_scratch = take(head_mfma_scratch_bytes(d.B, d.D, d.C));
     }
     p->total = o;
     return 0;
@@ -723,8 +731,15 @@ static int fwd(const Ctx& x, const float* images, float* logits, int s_from, int
     // ---- final norm (observer saw all tokens: updated behind the last block's residual kernel), cls pooling, head
     const Ctx::LnRows nf = x.norm1(d.depth);
     const int wh = d.n_w - 1;
-    launch_head_fwd(nf.x, nf.mean, nf.rstd, nf.gamma, nf.beta, x.act_qp(nf.ai), qa, qb, x.at<void>(p.w_off[wh]), x.wfq[wh].scale, c.w_per_channel,
-                    x.prm(x.p_tail() + 3), x.at<float>(p.hq), x.at<float>(p.logits_pre), x.act_stats(x.a_head()), kStatSlots, d.B, d.D, d.T, d.C, st);
+    if (F.head_mfma) {
+        if (launch_head_fwd_mfma(nf.x, nf.mean, nf.rstd, nf.gamma, nf.beta, x.act_qp(nf.ai), qa, qb, x.at<void>(p.w_off[wh]), x.wfq[wh].scale, c.w_per_channel,
+                                 x.prm(x.p_tail() + 3), x.at<float>(p.hq), x.at<void>(p.hq16), x.at<float>(p.logits_pre), x.act_stats(x.a_head()), kStatSlots,
+                                 d.B, d.D, d.T, d.C, st))
+            return 1;
+    } else {
+        launch_head_fwd(nf.x, nf.mean, nf.rstd, nf.gamma, nf.beta, x.act_qp(nf.ai), qa, qb, x.at<void>(p.w_off[wh]), x.wfq[wh].scale, c.w_per_channel,
+                        x.prm(x.p_tail() + 3), x.at<float>(p.hq), x.at<float>(p.logits_pre), x.act_stats(x.a_head()), kStatSlots, d.B, d.D, d.T, d.C, st);
+    }
     x.qparams_act(x.a_head());
     launch_logits_fq(x.at<float>(p.logits_pre), x.act_qp(x.a_head()), qa, qb, logits, d.B * d.C, st);
     return 0;
@@ -935,9 +950,16 @@ int Bwd::head(const float* dlogits) {
     const qatvit_cfg& c = x.c;
     const int base = x.p_tail(), wh = d.n_w - 1, last = d.depth - 1;
     Ctx::LnRows nf = x.norm1(d.depth);
-    launch_head_bwd(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), c.act_qmin, c.act_qmax, x.at<float>(p.hq), x.act_qp(nf.ai),
-                    x.at<void>(p.w_off[wh]), x.prm(base + 2), x.wfq[wh].scale, x.wfq[wh].zero_point, c.w_per_channel, c.w_qmin, c.w_qmax,
-                    G(base + 2), G(base + 3), x.at<float>(p.dh), d.B, d.D, d.C, x.st);
+    if (p.form.head_mfma) {
+        if (launch_head_bwd_mfma(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), c.act_qmin, c.act_qmax, x.at<void>(p.hq16), x.act_qp(nf.ai),
+                                 x.at<void>(p.w_off[wh]), x.prm(base + 2), x.wfq[wh].scale, x.wfq[wh].zero_point, c.w_per_channel, c.w_qmin, c.w_qmax,
+                                 G(base + 2), G(base + 3), x.at<float>(p.dh), x.at<void>(p.head_scratch), d.B, d.D, d.C, x.st))
+            return 1;
+    } else {
+        launch_head_bwd(dlogits, x.at<float>(p.logits_pre), x.act_qp(x.a_head()), c.act_qmin, c.act_qmax, x.at<float>(p.hq), x.act_qp(nf.ai),
+                        x.at<void>(p.w_off[wh]), x.prm(base + 2), x.wfq[wh].scale, x.wfq[wh].zero_point, c.w_per_channel, c.w_qmin, c.w_qmax,
+                        G(base + 2), G(base + 3), x.at<float>(p.dh), d.B, d.D, d.C, x.st);
+    }
     const Grad gy = grad(last, DS_FC2, cls);   // the masked gradient entering the last block's fc2
     const void* m2 = x.blk<void>(p.m2, last);
     if (cls) {   // the same kernel on the gathered class-token rows ([B, D], T = 1): the same bits in those rows, and neither the full dxA nor the full plane is written
@@ -1209,6 +1231,13 @@ int32_t qatvit_student_ln_in_strip(const qatvit_cfg* cfg, int32_t flags) {
     if (make_plan(*cfg, &p)) return 0;
     const Dims d = dims_of(*cfg);
     return (ln_in_strip_of(p, d, flags, WB_QKV) ? 1 : 0) | (ln_in_strip_of(p, d, flags, WB_FC1) ? 2 : 0);
+}
+
+int32_t qatvit_student_head_mfma(const qatvit_cfg* cfg) {
+    if (!cfg || check_cfg(*cfg)) return 0;
+    Plan p;
+    if (make_plan(*cfg, &p)) return 0;
+    return p.form.head_mfma ? 1 : 0;
 }
 
 int32_t qatvit_student_dy16_supported(const qatvit_cfg* cfg) {

@@ -47,7 +47,10 @@ constexpr int kMaxIW = 64 * 4 + 8;
 struct IPlan {
     int64_t qp, stats, wsum[kMaxIW], w16[kMaxIW], w8f[kMaxIW], head_bf16, qkvm, G8, Gm, glut;   // w8f: qkv weights in MFMA fragment order (the strip kernel's B operand); qkvm: its mask-bit output (unused here)
     int64_t xA, xB, h8, imgq8, codes, O16_hi, O16_lo, G16_hi, G16_lo, scal16, meanF, rstdF, hq, logits_pre, total;
+    int64_t hq16;   // the MFMA head's bf16 plane of hq, -1 where the head runs one block per image
 };
+// the head's form, decided as the training step decides it (engine.hip Forms::head_mfma)
+bool head_mfma_on(int D, int C) { return knobs().head_mfma && C >= 128 && D % 64 == 0 && C <= 32768 && head_mfma_covers(D, C); }
 int iplan(const qatvit_cfg& c, IPlan* p) {
     const IDims d = idims(c);
     if (d.depth > 64) { set_error("infer: depth %d > 64", d.depth); return 1; }
@@ -75,6 +78,7 @@ int iplan(const qatvit_cfg& c, IPlan* p) {
     p->meanF = take(d.M * 4); p->rstdF = take(d.M * 4);
     p->hq = take((int64_t)d.B * d.D * 4);
     p->logits_pre = take((int64_t)d.B * d.C * 4);
+    p->hq16 = head_mfma_on(d.D, d.C) ? take((int64_t)d.B * d.D * 2) : -1;   // (at the end: the MFMA head's A operand; other configurations keep their size)
     p->total = o;
     return 0;
 }
@@ -230,9 +234,16 @@ int infer_forward(const char* who, const qatvit_cfg* cfg, void* const* params, c
     float* meanF = reinterpret_cast<float*>(ws + p.meanF);
     float* rstdF = reinterpret_cast<float*>(ws + p.rstdF);
     if (launch_ln_quant8(xA, prm(base), prm(base + 1), c.ln_eps, qp(a_norm), qa, qb, center, nullptr, meanF, rstdF, d.B, d.T, d.D, st)) return 1;
-    launch_head_fwd(xA, meanF, rstdF, prm(base), prm(base + 1), qp(a_norm), qa, qb, ws + p.head_bf16, w_scale[wh], c.w_per_channel, prm(base + 3),
-                    reinterpret_cast<float*>(ws + p.hq), reinterpret_cast<float*>(ws + p.logits_pre), reinterpret_cast<uint32_t*>(ws + p.stats), kStatSlots, d.B,
-                    d.D, d.T, d.C, st);
+    if (p.hq16 >= 0) {   // the training step's decision (engine.hip Forms::head_mfma; at most 256 levels always hold here: icheck)
+        if (launch_head_fwd_mfma(xA, meanF, rstdF, prm(base), prm(base + 1), qp(a_norm), qa, qb, ws + p.head_bf16, w_scale[wh], c.w_per_channel, prm(base + 3),
+                                 reinterpret_cast<float*>(ws + p.hq), ws + p.hq16, reinterpret_cast<float*>(ws + p.logits_pre),
+                                 reinterpret_cast<uint32_t*>(ws + p.stats), kStatSlots, d.B, d.D, d.T, d.C, st))
+            return 1;
+    } else {
+        launch_head_fwd(xA, meanF, rstdF, prm(base), prm(base + 1), qp(a_norm), qa, qb, ws + p.head_bf16, w_scale[wh], c.w_per_channel, prm(base + 3),
+                        reinterpret_cast<float*>(ws + p.hq), reinterpret_cast<float*>(ws + p.logits_pre), reinterpret_cast<uint32_t*>(ws + p.stats), kStatSlots,
+                        d.B, d.D, d.T, d.C, st);
+    }
     launch_logits_fq(reinterpret_cast<float*>(ws + p.logits_pre), qp(a_norm + 1), qa, qb, logits, d.B * d.C, st);
     QV_CHECK_LAUNCH(who);
     return 0;

@@ -307,6 +307,18 @@ int launch_logits_fq(const float* pre, const float* qp, int qmin, int qmax, floa
 int launch_head_bwd(const float* dlogits, const float* logits_pre, const float* qp_logits, int qmin, int qmax, const float* hq, const float* qp_norm,
                     const void* wq, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dW,
                     float* dbias, float* dh, int B, int D, int C, hipStream_t st);
+// The same head on MFMA (head_mfma.hip; Forms::head_mfma, QATVIT_HEAD_MFMA): D % 64 == 0, D <= 768, kHeadMfmaMinClasses <= C <= kHeadMfmaMaxClasses, any B.
+// The forward also writes hq as a bf16 plane hq16 [B, D], which the backward reads in place of hq; logits_pre, hq and the folded statistics equal the tiny
+// form's bit for bit.  scratch: head_mfma_scratch_bytes(B, D, C) bytes for the class ranges' partial tiles of the input gradient (summed in a fixed order).
+constexpr int kHeadMfmaMinClasses = 128, kHeadMfmaMaxClasses = 32768;
+bool head_mfma_covers(int D, int C);
+int64_t head_mfma_scratch_bytes(int B, int D, int C);
+int launch_head_fwd_mfma(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* qp_norm, int qmin,
+                         int qmax, const void* wq, const float* w_scale, int w_per_channel, const float* bias, float* hq, void* hq16, float* logits_pre,
+                         uint32_t* stats, int stat_slots, int B, int D, int T, int C, hipStream_t st);
+int launch_head_bwd_mfma(const float* dlogits, const float* logits_pre, const float* qp_logits, int qmin, int qmax, const void* hq16, const float* qp_norm,
+                         const void* wq, const float* W, const float* w_scale, const int32_t* w_zp, int w_per_channel, int w_qmin, int w_qmax, float* dW,
+                         float* dbias, float* dh, void* scratch, int B, int D, int C, hipStream_t st);
 int launch_embed_bwd(const float* dx0, const float* Y0, const float* qp, int qmin, int qmax, float* dpos, float* dcls, void* dY0_hi, void* dY0_lo,
                      int B, int T, int D, hipStream_t st);
 // ---- all weights of the step at once (three launches instead of three per weight): tables passed by value as kernel arguments

@@ -409,6 +409,7 @@ class Step(NamedTuple):
     x16: bool              # the forward wrote h1q / h2q as fp16 integers: its backward is the one-plane form
     fq_mode: Optional[str]
     ln_in_strip: int       # which of its LayerNorms ran inside the statistics pass that follows them (bit 0: norm1 / qkv, bit 1: norm2 / fc1; QATVIT_LN_STRIP)
+    head_mfma: int = 0     # 1: its head ran on MFMA (128 .. 32768 classes, head_mfma.hip; QATVIT_HEAD_MFMA), 0: the one-block-per-image kernels
 
 
 class StudentEngine:
@@ -491,6 +492,7 @@ class StudentEngine:
     _fwd_x16 = property(lambda self: self.last_step.x16)
     fq_mode = property(lambda self: self.last_step.fq_mode)
     ln_in_strip = property(lambda self: self.last_step.ln_in_strip)
+    head_mfma = property(lambda self: self.last_step.head_mfma)
     dy16_fallbacks = property(lambda self: self.overflow.fallbacks)
     _agree_store = property(lambda self: self.overflow.store)
     _mirror_np = property(lambda self: self.overflow.mirror_np)
@@ -601,7 +603,8 @@ class StudentEngine:
         # drop-path (module in training mode): filled here, read by this forward and by its backward - the binding stays until the next forward
         self.drop.bind("qatvit_student_set_drop_path", c, self.workspace, self.drop.step(c.batch, self.capacity, self.frozen))
         self.ls.bind(c, self.workspace)
-        self.last_step = Step(c, self.generation + 1, x16, mode, int(self.lib.qatvit_student_ln_in_strip(ctypes.byref(c), flags)))
+        self.last_step = Step(c, self.generation + 1, x16, mode, int(self.lib.qatvit_student_ln_in_strip(ctypes.byref(c), flags)),
+                              int(self.lib.qatvit_student_head_mfma(ctypes.byref(c))))
         native.check(self.lib.qatvit_student_forward_stages(ctypes.byref(c), self._ptr_params, self._act_structs, self._w_structs, images.data_ptr(),
                                                             logits.data_ptr(), self.workspace.data_ptr(), 0, c.depth + 1, flags, native.stream_ptr()),
                      "qatvit_student_forward")

@@ -93,6 +93,10 @@ SIGNATURES = {
     "qatvit_student_tensor_offset": (c_int64, [c_void_p, c_char_p, c_int32]),
     "qatvit_student_dy16_supported": (c_int32, [c_void_p]),
     "qatvit_student_ln_in_strip": (c_int32, [c_void_p, c_int32]),
+    "qatvit_student_head_mfma": (c_int32, [c_void_p]),
+    "qatvit_head_scratch_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "qatvit_head_forward": (c_int, [c_void_p] * 6 + [c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 5 + [c_int32] * 5 + [c_void_p]),
+    "qatvit_head_backward": (c_int, [c_void_p] * 3 + [c_int32, c_int32] + [c_void_p] * 7 + [c_int32] * 3 + [c_void_p] * 4 + [c_int64] + [c_int32] * 4 + [c_void_p]),
     "qatvit_student_dy16_to_pair": (c_int, [c_void_p, c_void_p, c_void_p]),
     "qatvit_student_dy16_set_mirror": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "qatvit_student_set_drop_path": (c_int, [c_void_p, c_void_p, c_void_p]),
