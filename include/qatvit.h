@@ -485,6 +485,25 @@ int qatvit_head_backward(const float* dlogits, const float* logits_pre, const fl
                          int32_t w_qmin, int32_t w_qmax, float* dW, float* dbias, float* dh, void* scratch, int64_t scratch_bytes, int32_t B, int32_t D,
                          int32_t C, int32_t form, void* stream);
 
+/* The classifier head of the float (pre-QAT) student steps alone (final LayerNorm apply on the class-token rows, the head GEMM, its backward), by element type and
+ * form.  dtype: 0 fp32 (the fp32-accurate step), 1 fp16, 2 bf16 (the autocast forms; E below).  form 0: the scalar kernels - one workgroup per image walking the
+ * classes, one thread per gradient element (what every configuration below 128 classes runs); form 1: the MFMA kernels (the whole step takes them from 128 classes
+ * up; QATVIT_FLOAT_HEAD_MFMA=0 in the environment: never).  Form 1 exists for D % 64 == 0, D <= 768 and 128 <= C <= 32768 only: an error elsewhere, nothing is
+ * launched.  Both forms: B, T >= 1, D <= 768, C <= 32768.  The two forms compute the same contract and differ in the summation order only:
+ * forward: x [B * T, D] fp32 with the row statistics mean / rstd [B * T] (row b * T is image b's class token), gamma / beta [D], W [C, D] and bias [C] fp32.
+ * Writes hn [B, D] fp32 = LN(x[b * T]) (dtype 1 / 2: rounded to E, stored as fp32 values) and logits [B, C]: fp32 hn . W + bias with fp32 products and sums, or
+ * E(acc + E(bias)) of E elements with operands hn and E(W), fp32 accumulate.  stats (fp32 only, may be NULL): min / max of the logits folded into
+ * QATVIT_STAT_SLOTS {min, max} pairs as qatvit_head_forward's; the fold over the slots is the same in both forms.  Form 1 needs W and hn 16-byte aligned.
+ * backward: dlogits [B, C] of the dtype; writes (=) dW [C, D] = sum_b dl hn and dbias [C] = sum_b dl (fp32 sums) and dhn [B, D] = sum_c dl W, in the 16-bit forms
+ * E(sum_c dl E(W)) stored as fp32 (fp16: beyond its range -> +-inf, as stock autocast).  Form 1 reads `scratch` (qatvit_float_head_scratch_bytes(B, D, C) bytes; 0
+ * for shapes form 1 does not cover): the partial tiles of its class ranges, summed in a fixed order - no atomics, two calls give the same bits.
+ * Replaces: model.head on the pooled class token and its autograd (reference/src/models/vit.py), in fp32 or under torch.autocast. */
+int64_t qatvit_float_head_scratch_bytes(int32_t B, int32_t D, int32_t C);
+int qatvit_float_head_forward(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias,
+                              float* hn, void* logits, uint32_t* stats, int32_t B, int32_t D, int32_t T, int32_t C, int32_t dtype, int32_t form, void* stream);
+int qatvit_float_head_backward(const void* dlogits, const float* hn, const float* W, float* dW, float* dbias, float* dhn, void* scratch, int64_t scratch_bytes,
+                               int32_t B, int32_t D, int32_t C, int32_t dtype, int32_t form, void* stream);
+
 /* The class-token rows of a [rows * T, width bytes] tensor (the student pools the class token, so the gradient entering the last block lives in rows
  * b * T only; the one-plane backward runs that block's MLP and proj on those rows - QATVIT_CLS_BWD=0 in the environment: on all rows).
  * gather: compact[b] = tall[b * T], b < rows; width % 4 == 0, `stride` = bytes between two rows of tall (% 4 == 0, >= width).
@@ -698,6 +717,10 @@ int64_t qatvit_float_student_layer_scale_bytes(const qatvit_cfg* cfg);
  *  observe: a device buffer of qatvit_float_student_observe_bytes(cfg) bytes (batch independent), bound once to the modules' buffers by
  *  qatvit_float_student_observe_init (act_fq / weight_fq in the orders above; synchronises the stream) before its first forward. */
 int64_t qatvit_float_student_observe_bytes(const qatvit_cfg* cfg);
+/* 1 where the float steps of this configuration - all three forms and the observe-only forward, from one decision - run their classifier head in form 1 of
+ * qatvit_float_head_forward / _backward (128 <= num_classes <= 32768; each form's workspace then ends with the scratch that form needs), else 0; -1 for a
+ * configuration the float step does not cover.  QATVIT_FLOAT_HEAD_MFMA=0 in the environment: 0. */
+int32_t qatvit_float_student_head_mfma(const qatvit_cfg* cfg);
 int qatvit_float_student_observe_init(const qatvit_cfg* cfg, const qatvit_fq* act_fq, const qatvit_fq* weight_fq, void* observe, void* stream);
 int qatvit_float_student_forward_observe(const qatvit_cfg* cfg, void* const* params, const float* images, float* logits, void* workspace, void* observe,
                                          void* stream);

@@ -28,7 +28,7 @@ const Knobs& knobs() {
     static const Knobs k{knob("QATVIT_I8"), knob("QATVIT_F16"), knob("QATVIT_FC2_CODES"), knob("QATVIT_FC1_BITS"), knob("QATVIT_FC2W_CODES"),
                          knob("QATVIT_WBATCH"), knob("QATVIT_ATTN_CODES"), knob("QATVIT_QKV_2PASS"), knob("QATVIT_LNB_FUSE"), knob("QATVIT_QP_LATE"),
                          knob("QATVIT_TN_STREAM"), knob("QATVIT_TN_Q8"), knob("QATVIT_ATTN_BWD_FUSED"), knob("QATVIT_F16_STRIP"), knob("QATVIT_I8_STRIP"), knob("QATVIT_LN_STRIP"),
-                         knob("QATVIT_CLS_BWD"), knob("QATVIT_ATTN_BWD_PIPE"), knob("QATVIT_HEAD_MFMA")};
+                         knob("QATVIT_CLS_BWD"), knob("QATVIT_ATTN_BWD_PIPE"), knob("QATVIT_HEAD_MFMA"), knob("QATVIT_FLOAT_HEAD_MFMA")};
     return k;
 }
 int cu_count() {
@@ -688,6 +688,66 @@ int qatvit_head_backward(const float* dlogits, const float* logits_pre, const fl
                         (hipStream_t)stream);
     }
     QV_CHECK_LAUNCH("qatvit_head_backward");
+    return 0;
+}
+
+// the float steps' head alone, by element type and form: 0 the scalar kernels (float_step.hip, float_amp.hip), 1 the MFMA kernels (float_head_mfma.hip)
+static int float_head_shape_check(const char* fn, int32_t B, int32_t D, int32_t T, int32_t C, int32_t dtype, int32_t form) {
+    if (form != 0 && form != 1) { set_error("%s: form %d (0 scalar kernels, 1 MFMA)", fn, form); return 1; }
+    if (dtype < kFloatHeadF32 || dtype > kFloatHeadBf16) { set_error("%s: dtype %d (0 fp32, 1 fp16, 2 bf16)", fn, dtype); return 1; }
+    if (B < 1 || D < 1 || T < 1 || C < 1 || D > 768 || C > kFloatHeadMaxClasses) {
+        set_error("%s: B %d, D %d, T %d, C %d (all >= 1, D <= 768, C <= %d)", fn, B, D, T, C, kFloatHeadMaxClasses);
+        return 1;
+    }
+    if (form == 1 && !float_head_mfma_covers(D, C)) {
+        set_error("%s: form 1 (MFMA) needs D %% 64 == 0, D <= 768, %d <= C <= %d; got D %d, C %d", fn, kFloatHeadMinClasses, kFloatHeadMaxClasses, D, C);
+        return 1;
+    }
+    return 0;
+}
+
+int64_t qatvit_float_head_scratch_bytes(int32_t B, int32_t D, int32_t C) {
+    if (B < 1 || !float_head_mfma_covers(D, C)) return 0;   // (form 0 needs none)
+    return float_head_scratch_bytes(B, D, C);
+}
+
+int qatvit_float_head_forward(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias,
+                              float* hn, void* logits, uint32_t* stats, int32_t B, int32_t D, int32_t T, int32_t C, int32_t dtype, int32_t form, void* stream) {
+    if (float_head_shape_check("qatvit_float_head_forward", B, D, T, C, dtype, form)) return 1;
+    QV_CHECK_ARG(x && mean && rstd && gamma && beta && W && bias && hn && logits, "qatvit_float_head_forward: null pointer argument");
+    QV_CHECK_ARG(!stats || dtype == kFloatHeadF32, "qatvit_float_head_forward: stats belong to the fp32 form (dtype %d)", dtype);
+    QV_CHECK_ARG(form == 0 || (reinterpret_cast<uintptr_t>(W) % 16 == 0 && reinterpret_cast<uintptr_t>(hn) % 16 == 0),
+                 "qatvit_float_head_forward: form 1 needs W and hn 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (form == 1) {
+        if (launch_float_head_fwd(x, mean, rstd, gamma, beta, W, bias, hn, logits, stats, B, D, T, C, dtype, st)) return 1;
+    } else if (dtype == kFloatHeadF32) {
+        launch_fs_head_fwd(x, mean, rstd, gamma, beta, W, bias, hn, reinterpret_cast<float*>(logits), stats, B, D, T, C, st);
+    } else {
+        launch_fa_head_fwd(x, mean, rstd, gamma, beta, W, bias, hn, logits, B, D, T, C, st, dtype == kFloatHeadBf16);
+    }
+    QV_CHECK_LAUNCH("qatvit_float_head_forward");
+    return 0;
+}
+
+int qatvit_float_head_backward(const void* dlogits, const float* hn, const float* W, float* dW, float* dbias, float* dhn, void* scratch, int64_t scratch_bytes,
+                               int32_t B, int32_t D, int32_t C, int32_t dtype, int32_t form, void* stream) {
+    if (float_head_shape_check("qatvit_float_head_backward", B, D, 1, C, dtype, form)) return 1;
+    QV_CHECK_ARG(dlogits && hn && W && dW && dbias && dhn, "qatvit_float_head_backward: null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (form == 1) {
+        const int64_t need = float_head_scratch_bytes(B, D, C);
+        QV_CHECK_ARG(scratch && scratch_bytes >= need, "qatvit_float_head_backward: form 1 needs %lld bytes of scratch (qatvit_float_head_scratch_bytes), got %lld",
+                     (long long)need, (long long)(scratch ? scratch_bytes : 0));
+        QV_CHECK_ARG(reinterpret_cast<uintptr_t>(W) % 16 == 0 && reinterpret_cast<uintptr_t>(hn) % 16 == 0 && reinterpret_cast<uintptr_t>(scratch) % 4 == 0,
+                     "qatvit_float_head_backward: form 1 needs W and hn 16-byte aligned");
+        if (launch_float_head_bwd(dlogits, hn, W, dW, dbias, dhn, scratch, B, D, C, dtype, st)) return 1;
+    } else if (dtype == kFloatHeadF32) {
+        launch_fs_head_bwd(reinterpret_cast<const float*>(dlogits), hn, W, dW, dbias, dhn, B, D, C, st);
+    } else {
+        launch_fa_head_bwd(dlogits, hn, W, dW, dbias, dhn, B, D, C, st, dtype == kFloatHeadBf16);
+    }
+    QV_CHECK_LAUNCH("qatvit_float_head_backward");
     return 0;
 }
 

@@ -131,6 +131,18 @@ __global__ __launch_bounds__(256) void k_fs_head_bwd(const float* __restrict__ d
     }
 }
 
+int launch_fs_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias, float* hn,
+                       float* logits, uint32_t* stats, int B, int D, int T, int C, hipStream_t st) {
+    if (stats) k_fs_head_fwd<true><<<B, 256, D * sizeof(float), st>>>(x, mean, rstd, gamma, beta, W, bias, hn, logits, D, T, C, stats);
+    else k_fs_head_fwd<<<B, 256, D * sizeof(float), st>>>(x, mean, rstd, gamma, beta, W, bias, hn, logits, D, T, C);
+    return 0;
+}
+int launch_fs_head_bwd(const float* dl, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st) {
+    const int64_t n = (int64_t)C * D + (int64_t)B * D + C;
+    k_fs_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(dl, hn, W, dW, dbias, dhn, B, D, C);
+    return 0;
+}
+
 // ---------------------------------------------------------------- float attention backward
 // Per (image, head) z = b * H + h, with s = head_dim^-0.5 and the forward's lse:
 //   P = exp(s Q K^T - lse)          dS = P * (dO V^T - delta),  delta_i = dO_i . O_i
@@ -308,8 +320,12 @@ struct FsPlan {
     int64_t ones, p_hi, p_lo, Y0, x_last, meanf, rstdf, hf_hi, hf_lo, hn;
     FsBlock blk[12];
     int64_t Y, dx, dx2, dp_hi, dp_lo, dG, dY1_hi, dY1_lo, dh, dO, dqkv_hi, dqkv_lo, Pm, dS, delta, dhn, dY0_hi, dY0_lo;
+    int64_t head_scratch;   // fs_head_mfma (else absent): the partial tiles of the head dgrad's class ranges
     int64_t ones_words, total;
 };
+// The head's form, for all three float forms and the observe-only forward: the MFMA kernels (float_head_mfma.hip) from 128 classes up, else the scalar
+// kernels.  The one place that decides it: fs_plan, fs_forward and fs_backward read this.
+static bool fs_head_mfma(const qatvit_cfg& c) { return knobs().float_head_mfma && float_head_mfma_covers(c.embed_dim, c.num_classes); }
 static const char* fs_form_name(FsForm form) { return form == FsForm::f16 ? " amp" : form == FsForm::bf16 ? " bf16" : ""; }
 static int fs_check(const qatvit_cfg& c, FsForm form) {
     const bool one = form != FsForm::pair;
@@ -389,6 +405,8 @@ static FsPlan fs_plan(const qatvit_cfg& c, FsForm form) {
     p.delta = pair(B * H * T * 4);
     p.dhn = take(B * D * 4);
     p.dY0_hi = take(B * np * D * 2); p.dY0_lo = pair(B * np * D * 2);
+    // (at the very end: every configuration without the form keeps its offsets and its size)
+    p.head_scratch = fs_head_mfma(c) ? take(float_head_scratch_bytes((int)B, (int)D, c.num_classes)) : -1;
     p.total = o;
     return p;
 }
@@ -514,14 +532,13 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
         else launch_gelu_split(F(k.Y1), V(k.G_hi), V(k.G_lo), M * Hd, st);
     };
     auto head = [&](const float* gamma, const float* beta, const float* W, const float* bias) {
-        if (one)
-            launch_fa_head_fwd(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn), logits, c.batch, D, T, c.num_classes, st, bf16);
-        else if (ob.stats)
-            k_fs_head_fwd<true><<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn),
-                                                                        reinterpret_cast<float*>(logits), D, T, c.num_classes, ob.act(3 + 6 * L));
-        else
-            k_fs_head_fwd<<<c.batch, 256, D * sizeof(float), st>>>(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn),
-                                                                  reinterpret_cast<float*>(logits), D, T, c.num_classes);
+        uint32_t* const stats = ob.stats ? ob.act(3 + 6 * L) : nullptr;   // (the pair form only)
+        if (p.head_scratch >= 0)   // fs_head_mfma
+            return launch_float_head_fwd(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn), logits, stats, c.batch, D, T, c.num_classes,
+                                         f16 ? kFloatHeadF16 : bf16 ? kFloatHeadBf16 : kFloatHeadF32, st);
+        if (one) return launch_fa_head_fwd(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn), logits, c.batch, D, T, c.num_classes, st, bf16);
+        return launch_fs_head_fwd(F(p.x_last), F(p.meanf), F(p.rstdf), gamma, beta, W, bias, F(p.hn), reinterpret_cast<float*>(logits), stats, c.batch, D, T,
+                                  c.num_classes, st);
     };
     fs_consts(p, ws, st);   // (cheap; a workspace bound at another batch keeps working without a second init)
     weight_planes();
@@ -564,7 +581,7 @@ static int fs_forward(const char* fn, FsForm form, const qatvit_cfg* cfg, void* 
                                    drop_row(i, 1), ls_gamma(i, 1));
     }
     const int hb = 4 + 12 * L;
-    head(prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3));
+    if (head(prm(hb), prm(hb + 1), prm(hb + 2), prm(hb + 3))) return 1;
     if (ob.stats)   // every observer at once: nothing in this forward read the quantisers' state, so folding at the end is the stock update
         launch_obs_fold(reinterpret_cast<const ObsFoldEntry*>(reinterpret_cast<char*>(observe) + op.tab), op.n_act + op.n_w, op.nblocks, c.averaging_const, st);
     QV_CHECK_LAUNCH(fn);
@@ -613,13 +630,11 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
         return launch_gemm_tn(!one ? kTNPair : bf16 ? kTNPlaneBf16 : kTNPlaneF16, g, call, st);
     };
     auto head = [&] {   // dhn, and the head's weight / bias gradients
-        if (one) {
-            launch_fa_head_bwd(dlogits, F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), c.batch, D, c.num_classes, st, bf16);
-            return;
-        }
-        const int64_t n = (int64_t)c.num_classes * D + (int64_t)c.batch * D + c.num_classes;
-        k_fs_head_bwd<<<(int)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const float*>(dlogits), F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn),
-                                                              c.batch, D, c.num_classes);
+        if (p.head_scratch >= 0)   // fs_head_mfma
+            return launch_float_head_bwd(dlogits, F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), V(p.head_scratch), c.batch, D, c.num_classes,
+                                         f16 ? kFloatHeadF16 : bf16 ? kFloatHeadBf16 : kFloatHeadF32, st);
+        if (one) return launch_fa_head_bwd(dlogits, F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), c.batch, D, c.num_classes, st, bf16);
+        return launch_fs_head_bwd(reinterpret_cast<const float*>(dlogits), F(p.hn), prm(hb + 2), grd(hb + 2), grd(hb + 3), F(p.dhn), c.batch, D, c.num_classes, st);
     };
     auto gelu_bwd = [&](const FsBlock& k) {   // dY1 = dG * gelu'(Y1)
         if (one) return launch_fa_gelu_bwd(F(p.dG), F(k.Y1), V(p.dY1_hi), M * Hd, st, bf16);
@@ -680,7 +695,7 @@ static int fs_backward(const char* fn, FsForm form, const qatvit_cfg* cfg, void*
         return &next;
     };
     // head, then the final norm on the cls rows (dx of every other row = 0); the residual gradient leaves as fp32 (dx) and as dp
-    head();
+    if (head()) return 1;
     if (launch_ln_bwd_fq(0, F(p.dhn), F(p.x_last), F(p.meanf), F(p.rstdf), prm(hb), prm(hb + 1), qp_off, 0, 255, nullptr, F(p.dx), grd(hb), grd(hb + 1), M, D, T,
                          1, st, next_of(L - 1, 1)))
         return 1;
@@ -764,6 +779,12 @@ int qatvit_float_student_bf16_forward(const qatvit_cfg* cfg, void* const* params
 
 int qatvit_float_student_bf16_backward(const qatvit_cfg* cfg, void* const* params, const void* dlogits_bf16, void* const* grads, void* workspace, void* stream) {
     return fs_backward("qatvit_float_student_bf16_backward", FsForm::bf16, cfg, params, dlogits_bf16, grads, workspace, stream);
+}
+
+int32_t qatvit_float_student_head_mfma(const qatvit_cfg* cfg) {
+    if (!cfg) { set_error("qatvit_float_student_head_mfma: null argument"); return -1; }
+    if (fs_check(*cfg, FsForm::pair)) return -1;
+    return fs_head_mfma(*cfg) ? 1 : 0;
 }
 
 int64_t qatvit_float_student_observe_bytes(const qatvit_cfg* cfg) {

@@ -48,6 +48,7 @@ struct Knobs {
     bool cls_bwd;         // QATVIT_CLS_BWD: the one-plane backward of the last block's MLP and proj on the B class-token rows (the only ones the cls-pooled head reaches); 0: all B * T rows
     bool attn_bwd_pipe;   // QATVIT_ATTN_BWD_PIPE: the fused attention backward as one persistent workgroup per CU that fetches its next head under the sweep (more heads than CUs); 0: one workgroup per head
     bool head_mfma;       // QATVIT_HEAD_MFMA: the classifier head on MFMA from 128 classes up (head_mfma.hip); 0: the one-block-per-image kernels at every class count
+    bool float_head_mfma; // QATVIT_FLOAT_HEAD_MFMA: the float steps' head on MFMA from 128 classes up (float_head_mfma.hip); 0: the scalar head kernels at every class count
 };
 const Knobs& knobs();
 // compute units of the current device, asked once per process (capi.hip); 256 where the runtime does not say or says more: the size of persistent grids

@@ -423,6 +423,21 @@ int launch_fa_head_fwd(const float* x, const float* mean, const float* rstd, con
                        void* logits16, int B, int D, int T, int C, hipStream_t st, bool bf16 = false);
 int launch_fa_head_bwd(const void* dl16, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st,
                        bool bf16 = false);
+// The fp32-accurate form's head, one workgroup per image / one thread per output element (float_step.hip); stats: the observe-only forward's accumulators
+int launch_fs_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias, float* hn,
+                       float* logits, uint32_t* stats, int B, int D, int T, int C, hipStream_t st);
+int launch_fs_head_bwd(const float* dl, const float* hn, const float* W, float* dW, float* dbias, float* dhn, int B, int D, int C, hipStream_t st);
+// The three float forms' head on MFMA (float_head_mfma.hip; QATVIT_FLOAT_HEAD_MFMA): D % 64 == 0, D <= 768, kFloatHeadMinClasses <= C <= kFloatHeadMaxClasses, any
+// B >= 1; W and hn 16-byte aligned.  dtype: the element type of logits / dl.  The scalar kernels' arithmetic in another summation order; stats (fp32 form only, may
+// be null): kStatSlots pairs.  scratch: float_head_scratch_bytes(B, D, C) bytes for the class ranges' partial tiles of dhn (summed in a fixed order).
+constexpr int kFloatHeadMinClasses = 128, kFloatHeadMaxClasses = 32768;
+enum { kFloatHeadF32 = 0, kFloatHeadF16 = 1, kFloatHeadBf16 = 2 };
+bool float_head_mfma_covers(int D, int C);
+int64_t float_head_scratch_bytes(int B, int D, int C);
+int launch_float_head_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* W, const float* bias,
+                          float* hn, void* logits, uint32_t* stats, int B, int D, int T, int C, int dtype, hipStream_t st);
+int launch_float_head_bwd(const void* dl, const float* hn, const float* W, float* dW, float* dbias, float* dhn, void* scratch, int B, int D, int C, int dtype,
+                          hipStream_t st);
 int launch_fa_gelu(const float* Y, void* G16, int64_t n, hipStream_t st, bool bf16 = false);                        // G16 = fp16(gelu(Y)), n % 4 == 0
 int launch_fa_gelu_bwd(const float* dG, const float* Y, void* dY16, int64_t n, hipStream_t st, bool bf16 = false);   // dY16 = fp16(fp16(dG) gelu'(Y)), n % 4 == 0
 // dpos / dcls from dx [B*T, D] (fixed order), dY0_16 = fp16 of dx's patch rows

@@ -158,6 +158,8 @@ class FloatStudentEngine:
     workspace = property(lambda self: self.fp32.workspace)
     capacity = property(lambda self: self.fp32.capacity)
     capacity16 = property(lambda self: self.fp16.capacity)
+    # 1: every form's head runs on MFMA (128 .. 32768 classes, float_head_mfma.hip; QATVIT_FLOAT_HEAD_MFMA), 0: the scalar head kernels
+    head_mfma = property(lambda self: int(self.lib.qatvit_float_student_head_mfma(ctypes.byref(self.cfg_for(1)))))
 
     def workspace_bytes(self, batch: int) -> int:
         return self.fp32.workspace_bytes(self.cfg_for(batch))

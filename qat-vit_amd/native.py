@@ -111,6 +111,10 @@ SIGNATURES = {
     "qatvit_float_student_init": (c_int, [c_void_p] * 3),
     "qatvit_float_student_forward": (c_int, [c_void_p] * 6),
     "qatvit_float_student_backward": (c_int, [c_void_p] * 6),
+    "qatvit_float_student_head_mfma": (c_int32, [c_void_p]),
+    "qatvit_float_head_scratch_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "qatvit_float_head_forward": (c_int, [c_void_p] * 10 + [c_int32] * 6 + [c_void_p]),
+    "qatvit_float_head_backward": (c_int, [c_void_p] * 7 + [c_int64] + [c_int32] * 5 + [c_void_p]),
     "qatvit_float_student_observe_bytes": (c_int64, [c_void_p]),
     "qatvit_float_student_observe_init": (c_int, [c_void_p] * 5),
     "qatvit_float_student_forward_observe": (c_int, [c_void_p] * 7),
